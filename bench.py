@@ -2,7 +2,7 @@
 """bench.py — recommend() throughput on MI355X: SBERT encode -> cosine -> top-20 over the
 49,688-product catalog (BASELINE.json metric), with the kernel roofline and a CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload 49k7|10m]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload 49k7|10m] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic user contexts whose token
 ids are already resident in HBM: icrec_encode (BERT forward + pool + normalise) then
@@ -32,6 +32,7 @@ TOP_K = 20
 PEAK_F32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense fp32 matrix peak
 PEAK_F16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense f16/bf16 MFMA peak
 PEAK_HBM_GBS = 8000.0
+DUMP_CAP_BYTES = 64 << 20
 
 
 def parse():
@@ -56,13 +57,41 @@ def parse():
     ap.add_argument("--no-10m-leg", action="store_true",
                     help="skip the configs[4] leg (4,096 queries over the 10 M-row bf16 catalog) the default line carries")
     ap.add_argument("--no-http", action="store_true", help="skip the /recommend-over-HTTP leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (query embeddings, top-k rows, "
+                         "top-k scores; one row per query of the global batch) as DIR/<name>.npy, float32 or float64, at "
+                         "most 64 MB in all")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.batch is None:
         a.batch = 1024 if a.gpus == 1 else max(4096 // a.gpus, 1)
         a.batch_defaulted = True
     else:
         a.batch_defaulted = False
     return a
+
+
+def dump_outputs(out_dir: Path, arrays: dict, cap_bytes: int = DUMP_CAP_BYTES) -> dict:
+    """Write each array as out_dir/<name>.npy: float32 stays float32, everything else becomes float64 (row numbers stay
+    exact).  The arrays share their first axis (one row per query).  When they would take more than `cap_bytes` in all,
+    the same seeded sample of rows (ascending) is kept from every array and its row numbers go to sample_rows.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    n = {a.shape[0] for a in arrays.values()}
+    assert len(n) == 1, f"arrays to dump differ in their row count: {n}"
+    n = n.pop()
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    budget = cap_bytes - 256 * (len(arrays) + 1)  # room for the .npy headers
+    keep = n if row_bytes * n <= budget else budget // (row_bytes + 8)
+    if keep < n:
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(out_dir / f"{k}.npy", a)
+    return {"dir": str(out_dir), "files": sorted(f"{k}.npy" for k in arrays), "rows": int(keep), "of_rows": int(n),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def cpu_baseline(weights, shape, ids, cu, catalog, n_sample: int):
@@ -432,6 +461,14 @@ def main() -> None:
     (ffn_ms, ffn_n), (enc_ms, _), (srch_ms, _), (skern_ms, _) = timers
     n_keep = min(args.cpu_sample, args.batch)  # the timed step's own outputs, kept for the oracle check at the end
     kept = (emb[:n_keep].cpu().numpy(), idx[:n_keep].cpu().numpy(), sc[:n_keep].cpu().numpy())
+    dumped = None
+    if args.dump_outputs:
+        # before any later leg reuses `emb`; at N > 1 the gather is a collective every rank takes part in
+        emb_all = search.gather_queries(emb)
+        if rank == 0:
+            dumped = dump_outputs(Path(args.dump_outputs), {
+                "query_embeddings": emb_all.cpu().numpy(), "topk_rows": idx.cpu().numpy(), "topk_scores": sc.cpu().numpy()})
+        del emb_all
 
     # ---- BASELINE configs[4] beside it, in the same line at every N: 4,096 user contexts per step in total (4,096 / N
     # encoded per GPU) against a 10 M x 384 bf16 catalog (+ filter fragments) row-sharded N ways, generated on the device
@@ -808,6 +845,7 @@ def main() -> None:
             f"encode {CATALOG_ROWS} products ({catalog_tokens} tokens, from ids in HBM) + normalise into a DeviceIndex",
             "encode_ms_per_step": enc_ms, "search_ms_per_step": srch_ms, "search_kernel_ms": skern_ms,
             "roofline": roofline(enc.gemm_mode, achieved, ffn_n, ffn_ms, ffn_flops, ffn_tokens),
+            "dumped_outputs": dumped,
         }
         # the whole step against the same roof: SURVEY 8d's algorithmic FLOPs (encoder 21,233,664 L + 9,216 L^2 per
         # sequence of L tokens, similarity 2 Q N d; split-precision products count once) / step time / the MFMA roof

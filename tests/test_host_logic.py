@@ -137,3 +137,60 @@ def test_bench_bare_multi_gpu_form_starts_its_own_ranks(monkeypatch):
     assert cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"] and cmd[-7].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     assert ("torch" in sys.modules) == imported_before           # decided before torch is imported by bench.main
+
+
+def _bench_module():
+    import importlib.util
+    from pathlib import Path
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", Path(__file__).resolve().parents[1] / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_rejects_zero_timed_steps(monkeypatch):
+    """--steps sets the timed steps and ms_per_step divides by it: fewer than one is refused at parse time."""
+    import sys
+
+    bench = _bench_module()
+    for argv in (["--steps", "0"], ["--steps", "-3"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        with pytest.raises(SystemExit) as exc:
+            bench.parse()
+        assert exc.value.code == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out"
+
+
+def test_bench_dump_outputs_formats_and_cap(tmp_path):
+    """bench.py --dump-outputs: float32 kept, integer rows as exact float64; past the cap the same seeded row sample of
+    every array (and its row numbers), the same sample on every run, never more than the cap on disk."""
+    bench = _bench_module()
+    rng = np.random.default_rng(1)
+    n = 1000
+    emb = rng.standard_normal((n, 384)).astype(np.float32)
+    rows = rng.integers(0, 10_000_000, (n, 20)).astype(np.int64)
+    sc = rng.standard_normal((n, 20)).astype(np.float32)
+    arrays = {"query_embeddings": emb, "topk_rows": rows, "topk_scores": sc}
+
+    info = bench.dump_outputs(tmp_path / "full", arrays)
+    assert info["rows"] == info["of_rows"] == n and info["files"] == ["query_embeddings.npy", "topk_rows.npy", "topk_scores.npy"]
+    got = {k: np.load(tmp_path / "full" / f"{k}.npy") for k in arrays}
+    assert got["query_embeddings"].dtype == np.float32 and np.array_equal(got["query_embeddings"], emb)
+    assert got["topk_rows"].dtype == np.float64 and np.array_equal(got["topk_rows"].astype(np.int64), rows)
+    assert got["topk_scores"].dtype == np.float32 and np.array_equal(got["topk_scores"], sc)
+
+    cap = 300_000  # ~1,650 bytes per row: room for about 180 of the 1,000
+    for d in ("a", "b"):
+        info = bench.dump_outputs(tmp_path / d, arrays, cap_bytes=cap)
+        assert 0 < info["rows"] < n and "sample_rows.npy" in info["files"]
+        assert sum(p.stat().st_size for p in (tmp_path / d).iterdir()) <= cap
+    pick = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert pick.dtype == np.float64 and (np.diff(pick) > 0).all()
+    pick = pick.astype(np.int64)
+    for k, a in arrays.items():
+        s = np.load(tmp_path / "a" / f"{k}.npy")
+        assert np.array_equal(s, np.load(tmp_path / "b" / f"{k}.npy"))
+        assert np.array_equal(s, a[pick].astype(s.dtype))

@@ -60,15 +60,17 @@ def test_two_ranks_real_kernels_equal_unsharded(tmp_path):
         np.testing.assert_array_equal(got["sc"], ws)
 
 
-def test_bench_multi_rank_flow_rehearsal():
+def test_bench_multi_rank_flow_rehearsal(tmp_path):
     """The BARE form the driver uses, `python bench.py --gpus 2 ...` without a launcher: bench.py starts its own two
     ranks as a fresh child (torch.distributed.run), relays rank 0's line and exits with the child's code.  Rehearsal
     mode: both ranks on cuda:0, gloo.  The line carries the configs[4] leg (here 300,000 rows instead of 10 M) and the
-    verdict of the exchange check, exclusion exchange included."""
+    verdict of the exchange check, exclusion exchange included.  --dump-outputs: rank 0 writes the timed step's outputs
+    for the whole gathered batch, both ranks' query embeddings in rank order."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", ICREC_BENCH_REHEARSAL="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64",
-                        "--rows-10m", "300000"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--rows-10m", "300000", "--dump-outputs", str(tmp_path / "dump")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -78,6 +80,19 @@ def test_bench_multi_rank_flow_rehearsal():
     leg = d["configs4_10m_rows"]
     assert leg["queries_per_step"] == 4096 and leg["contexts_encoded_per_gpu"] == 2048 and leg["rows_per_gpu"] == 150000
     assert leg["result_properties_ok"] and leg["qps"] > 0
+    assert d["dumped_outputs"]["rows"] == d["dumped_outputs"]["of_rows"] == 128
+    emb = np.load(tmp_path / "dump" / "query_embeddings.npy")
+    rows = np.load(tmp_path / "dump" / "topk_rows.npy")
+    sc = np.load(tmp_path / "dump" / "topk_scores.npy")
+    assert emb.shape == (128, 384) and emb.dtype == np.float32
+    assert rows.shape == sc.shape == (128, 20) and rows.dtype == np.float64 and sc.dtype == np.float32
+    assert ((rows >= 0) & (rows < 49_688) & (rows == np.rint(rows))).all()
+    assert np.abs(np.linalg.norm(emb, axis=1) - 1).max() < 1e-5
+    assert not np.array_equal(emb[:64], emb[64:])   # rank 1's contexts come from another seed
+    from instacart_next_order_recommendation_amd import synthetic as syn
+
+    P = syn.synthetic_embeddings(49_688, 384, seed=1).astype(np.float64)  # bench.py's catalog: unit rows
+    np.testing.assert_allclose(sc, np.einsum("qd,qkd->qk", emb.astype(np.float64), P[rows.astype(np.int64)]), atol=1e-5)
 
 
 def test_native_rccl_world1_equals_plain_search():
