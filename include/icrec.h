@@ -66,7 +66,7 @@ typedef struct icrec_bert_cfg {
     int32_t hidden;        /* 384  (must be 384 in this build)               */
     int32_t layers;        /* 6                                              */
     int32_t heads;         /* 12   (head_dim must be 32 in this build)       */
-    int32_t intermediate;  /* 1536 (must be a multiple of 128)               */
+    int32_t intermediate;  /* 1536 (must be a multiple of 384)               */
     int32_t max_position;  /* 512                                            */
     int32_t type_vocab;    /* 2                                              */
     float   ln_eps;        /* 1e-12                                          */
@@ -139,7 +139,8 @@ ICREC_API int icrec_encode_batch_split(const icrec_encoder* enc, int64_t total_t
 /* Build an index over a [n_rows, dim] fp32 row-major matrix in device memory.
  * The library keeps its own copy with every row divided by max(|row|_2,1e-12)
  * (what cos_sim does to its second operand on every call in the reference).
- * `row_offset` is added to every returned row index (catalog shards).        */
+ * `row_offset` is added to every returned row index (catalog shards).
+ * `dim` must be a multiple of 32 in [32, 4096].                              */
 ICREC_API int icrec_index_create(const float* rows_dev, int64_t n_rows, int32_t dim,
                        int64_t row_offset, int device, icrec_index** out);
 
@@ -149,14 +150,18 @@ ICREC_API int icrec_index_create(const float* rows_dev, int64_t n_rows, int32_t 
  *   ICREC_ROWS_BF16  the fp32 quotient rounded to bfloat16, round-to-nearest-even.
  * Only the storage changes: scores are still the fp32 fmaf chain over k of
  * q_hat[k] * float(row[k]) on the exact-f32 MFMA, so results are bit-identical to
- * oracle/icrec_oracle.c:icrec_oracle_search_bf16 (same rounded rows, same chain).       */
+ * oracle/icrec_oracle.c:icrec_oracle_search_bf16 (same rounded rows, same chain).
+ * The bf16 storages (ICREC_ROWS_BF16, ICREC_ROWS_BF16_FILTER) and the filter storages need dim % 64 == 0
+ * (bf16 rows are read in 128-byte slabs of 64 values; every real embedding width - 384, 512, 768, 1024 -
+ * is one); other widths return ICREC_EINVAL.                                                  */
 #define ICREC_ROWS_F32 0
 #define ICREC_ROWS_BF16 1
 /*   ICREC_ROWS_F32_FILTER  fp32 rows PLUS their f16 hi/lo planes (2x the HBM).  Batches of >= 256 queries
  *                    are first ranked on the f16 matrix cores (3 MFMAs per product, scores within ~1e-7, 5x
  *                    the fp32-MFMA rate) keeping k+12 candidates per query; every candidate is then re-scored
  *                    with the exact fp32 chain and the best k returned.  A query whose (k+12)-th candidate
- *                    is not provably below its exact k-th score (1e-4 margin) makes the exact search run
+ *                    is not provably below its exact k-th score (margin max(1e-4, 2 dim 2^-24 + 1e-6):
+ *                    1e-4 up to dim 768, 1.2e-4 at 1,024, 4.9e-4 at 4,096) makes the exact search run
  *                    for the batch instead — results are therefore ALWAYS bit-identical to
  *                    ICREC_ROWS_F32, only faster for large catalogs x large batches.                    */
 #define ICREC_ROWS_F32_FILTER 2

@@ -748,6 +748,10 @@ struct Encoder {
     //                        1,040- / 1,050-context batches (remainders 650 / 1,839 / 3,117 tokens): 9.83 -> 9.35 ms, 9.86 -> 9.60,
     //                        9.89 -> 9.91 (tools/tail_sweep.sh, profiles/r04_small_m_sweep.txt); rounds 2-3: 512
     int tail_m = 2560;
+    // Both are clamped at creation: small_m to [0, SMALL_M_MAX], tail_m to [0, 64 * n_cu - 1] (a remainder is shorter
+    // than one round by definition, so a larger value changes nothing).  Every combination is supported and gives the
+    // same bits; with tail_m > small_m a remainder longer than small_m takes the layer kernels (activation-resident QKV,
+    // fused layer kernel) on the side stream instead of the latency form.
     // Side stream + events of one caller stream: the short remainder of a large batch (batch_split) and the shorter
     // attention buckets run beside the batch kernels of the same layer instead of behind them.  One set per caller
     // stream (created on first use, kept for the encoder's life), so that concurrent icrec_encode calls on different
@@ -803,7 +807,17 @@ static EncWs enc_ws(const icrec_bert_cfg& c, int64_t T) {
 }
 
 typedef TileCfg<2, 2, 2, 2> GemmBig;  // 128 x 128 output tile, 4 waves
-constexpr int X3_SMALL_M = 512;  // a batch's remainder of up to this many tokens goes through the latency-form kernels (batch_split)
+constexpr long long SMALL_M_MAX = 1 << 20;  // ICREC_SMALL_M above this: every call of up to 2^20 tokens takes the latency form
+
+// A non-negative integer knob from the environment, clamped to [0, hi]; `fallback` when unset or not a number.
+static int env_knob(const char* name, int fallback, long long hi) {
+    const char* s = getenv(name);
+    if (!s) return fallback;
+    char* end = nullptr;
+    const long long v = strtoll(s, &end, 10);
+    if (end == s) return fallback;
+    return (int)(v < 0 ? 0 : v > hi ? hi : v);
+}
 
 template <bool GELU>
 static void launch_linear(const float* A, int M, int K, const float* W, int N, const float* bias, float* out,
@@ -911,8 +925,8 @@ int icrec_encoder_create(const float* weights_host, size_t n_floats, const icrec
         const char* fuse_env = getenv("ICREC_FUSE");
         const char* side_env = getenv("ICREC_SIDE_STREAM");
         e->fuse = !(fuse_env && fuse_env[0] == '0');
-        if (const char* sm = getenv("ICREC_SMALL_M")) { const int v = atoi(sm); if (v >= 0) e->small_m = v; }
-        if (const char* tm = getenv("ICREC_TAIL_M")) { const int v = atoi(tm); if (v >= 0) e->tail_m = v; }
+        e->small_m = env_knob("ICREC_SMALL_M", e->small_m, SMALL_M_MAX);
+        e->tail_m = env_knob("ICREC_TAIL_M", e->tail_m, 64LL * e->n_cu - 1);
         e->side_stream = !(side_env && side_env[0] == '0');
     }
     const size_t H = cfg->hidden, I = cfg->intermediate;
@@ -1150,6 +1164,10 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
             // The remainder's kernels run on the side stream: its QKV beside the batch QKV, its attention-out / FFN chain
             // beside the batch's.  Attention covers all rows, so it joins both (ev_qkv_tail in, ev_att out); the side
             // stream's in-order execution keeps its own layers apart.
+            // batches: layer 0 projects Q / K / V in a launch of its own; every later layer's projection is the epilogue of
+            // the previous layer's fused kernel (also for a remainder longer than small_m, see tail_m)
+            const bool qkv_in_fused = fuse && T_main > small_m && H == 384;
+            const bool tail_qkv_in_fused = fuse && T_tail > small_m && H == 384;
             hipStream_t ts = st;
             if (T_tail && use_side) {
                 ts = sd->side;
@@ -1157,14 +1175,12 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
                     ICREC_HIP(hipEventRecord(sd->ev_main, st));
                     ICREC_HIP(hipStreamWaitEvent(ts, sd->ev_main, 0));
                 }
-                if (int rc_ = qkv_stage(T_main, T_tail, ts)) return rc_;
+                if (l == 0 || !tail_qkv_in_fused)
+                    if (int rc_ = qkv_stage(T_main, T_tail, ts)) return rc_;
                 ICREC_HIP(hipEventRecord(sd->ev_qkv_tail, ts));
-            } else if (T_tail) {
+            } else if (T_tail && (l == 0 || !tail_qkv_in_fused)) {
                 if (int rc_ = qkv_stage(T_main, T_tail, st)) return rc_;
             }
-            // batches: layer 0 projects Q / K / V in a launch of its own; every later layer's projection is the epilogue of
-            // the previous layer's fused kernel
-            const bool qkv_in_fused = fuse && T_main > small_m && H == 384;
             if (l == 0 || !qkv_in_fused)
                 if (int rc_ = qkv_stage(0, T_main, st)) return rc_;
             if (T_tail && use_side) ICREC_HIP(hipStreamWaitEvent(st, sd->ev_qkv_tail, 0));

@@ -987,14 +987,20 @@ typedef TileCfg<8, 1, 1, 2> CfgRes;     // 256 rows x  64 queries per round, 8 w
 constexpr int64_t RES_MAX_ROWS = (int64_t)1 << 40;  // no limit (ICREC_FILTER_RESIDENT=<n> sets one, =0 forces the staged form)
 
 // Filter + verify (ICREC_ROWS_F32_FILTER): batches of at least FILTER_MIN_Q queries are ranked by the f16x3 filter
-// pass with FILTER_SLACK extra list entries, then verified exactly.  FILTER_EPS bounds |filter score - exact score|
+// pass with FILTER_SLACK extra list entries, then verified exactly.  filter_eps(dim) bounds |filter score - exact score|
 // for unit vectors: the f16 split drops <= 3 * 2^-22 per product (Cauchy-Schwarz: <= 7.2e-7 per score) and either
-// fp32 accumulation is off by at most 384 * 2^-24 = 2.3e-5 from the real dot product; 1e-4 covers the sum twice.
+// fp32 accumulation is off by at most dim * 2^-24 from the real dot product, so the difference stays below
+// 2 * dim * 2^-24 + 7.2e-7.  The margin is that bound (+1e-6 for the split term and second-order terms), never less
+// than 1e-4: exactly 1e-4 up to dim 830 (at 384 the bound is 4.7e-5, 1e-4 covers it twice), 1.2e-4 at 1,024,
+// 4.9e-4 at 4,096.
 // Below 256 queries the pass's fixed costs (three more launches, longer lists) eat its advantage: measured at
 // 49,688 rows Q=64 0.26 ms vs 0.15 ms exact, Q=256 equal, Q=1024 0.61 vs 0.82 ms; at 2M rows Q=256 2.5 vs 4.2 ms,
 // Q=1024 7.5 vs 14.5 ms.
 constexpr int FILTER_MIN_Q = 256, FILTER_SLACK = 12;
-constexpr float FILTER_EPS = 1.0e-4f;
+static inline float filter_eps(int dim) {
+    const float bound = 2.0f * (float)dim * 0x1p-24f + 1.0e-6f;
+    return bound > 1.0e-4f ? bound : 1.0e-4f;
+}
 static inline int filter_list_len(int k) { int kp = k + FILTER_SLACK; kp = (kp + 7) & ~7; return kp; }
 
 struct Plan {
@@ -1169,10 +1175,10 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
     const bool h = rows_are_bf16(ix);
     if (h)
         hipLaunchKernelGGL(verify_kernel<true>, dim3((Q + 3) / 4), dim3(256), 0, st, (const void*)ix->rows, ix->dim, qn, cand, Q,
-                           f.kp, k, (uint32_t)ix->row_offset, FILTER_EPS, out_idx, out_score, out_keys, flag);
+                           f.kp, k, (uint32_t)ix->row_offset, filter_eps(ix->dim), out_idx, out_score, out_keys, flag);
     else
         hipLaunchKernelGGL(verify_kernel<false>, dim3((Q + 3) / 4), dim3(256), 0, st, (const void*)ix->rows, ix->dim, qn, cand, Q,
-                           f.kp, k, (uint32_t)ix->row_offset, FILTER_EPS, out_idx, out_score, out_keys, flag);
+                           f.kp, k, (uint32_t)ix->row_offset, filter_eps(ix->dim), out_idx, out_score, out_keys, flag);
     ICREC_HIP(hipGetLastError());
     // exact pass: every workgroup returns at once unless verify raised the flag
     int rc;
@@ -1343,6 +1349,8 @@ int icrec_index_create_ex(const float* rows_dev, int64_t n_rows, int32_t dim, in
     const bool with_planes = storage == ICREC_ROWS_F32_FILTER || storage == ICREC_ROWS_BF16_FILTER;
     const bool rows16 = storage == ICREC_ROWS_BF16 || storage == ICREC_ROWS_BF16_FILTER;
     ICREC_REQUIRE(!with_planes || dim % HBK == 0, "icrec_index_create: the filter planes need dim %% %d == 0 (got %d)", HBK, dim);
+    // bf16 rows: the streaming kernel reads 128-byte slabs of 64 values, a final half slab would go unread
+    ICREC_REQUIRE(!rows16 || dim % 64 == 0, "icrec_index_create: bf16 rows need dim %% 64 == 0 (got %d)", dim);
     ICREC_HIP(hipSetDevice(device));
     hipDeviceProp_t prop;
     ICREC_HIP(hipGetDeviceProperties(&prop, device));

@@ -1,0 +1,201 @@
+"""The encoder at the model shapes icrec_encoder_create accepts besides all-MiniLM-L6-v2: 1, 3 and 12 layers
+(paraphrase-MiniLM-L3 / all-MiniLM-L12), intermediate sizes 384 to 3,072, n_normalize 3 and 4, ln_eps 1e-5,
+type_vocab 1, max_position 64.  Every form of the layer - latency form, layer kernel, unfused reference chain,
+whole rounds + a remainder on the side stream - against the oracle and against each other; and the
+ICREC_SMALL_M / ICREC_TAIL_M pair."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests.encoder_shapes import SHAPES
+
+pytestmark = pytest.mark.gpu
+
+EMB_TOL = 5e-6   # as tests/test_encoder_gpu.py
+
+
+def _shape(name):
+    from instacart_next_order_recommendation_amd import synthetic as syn
+
+    return syn.BertShape(vocab_size=2048, **SHAPES[name])
+
+
+def _cfg(shape):
+    from oracle import oracle
+
+    return oracle.make_cfg(vocab_size=shape.vocab_size, hidden=shape.hidden, layers=shape.layers, heads=shape.heads,
+                           intermediate=shape.intermediate, max_position=shape.max_position,
+                           type_vocab=shape.type_vocab, ln_eps=shape.ln_eps, n_normalize=shape.n_normalize)
+
+
+def _batch(shape, seed):
+    """~1,800 tokens in 70 sequences (the batch forms: dispatch order and split attention buckets), lengths on the
+    attention tile boundaries; under max_position 64 every sequence has exactly 64 tokens."""
+    rng = np.random.default_rng(seed)
+    if shape.max_position < 256:
+        lens = [shape.max_position] * 28
+    else:
+        lens = [256, 200, 129, 65, 64, 33, 32, 31, 1] + rng.integers(3, 25, 61).tolist()
+    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    ids = rng.integers(0, shape.vocab_size, int(cu[-1])).astype(np.int32)
+    return ids, cu
+
+
+def _make(monkeypatch, w, shape, mode="f16x3", **env):
+    """An encoder created under the given ICREC_* settings (they are read once, at creation)."""
+    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
+
+    for k, v in env.items():
+        monkeypatch.setenv(k, str(v))
+    try:
+        return DeviceEncoder(w, shape, gemm_mode=mode)
+    finally:
+        for k in env:
+            monkeypatch.delenv(k)
+
+
+def _run(enc, ids, cu):
+    import torch
+
+    return enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(),
+                             int(np.diff(cu).max())).cpu().numpy()
+
+
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_every_layer_form_vs_oracle(monkeypatch, name):
+    """One ~1,800-token batch through: the latency-form kernels (default, <= 3,584 tokens), the layer kernel
+    (ICREC_SMALL_M=512), both under ICREC_FUSE=0 too, and the f32 GEMM mode.  Oracle within EMB_TOL for all;
+    the four f16x3 forms bitwise equal to each other (same per-output chains, same LayerNorm order)."""
+    import torch
+
+    assert torch.cuda.is_available()
+    from instacart_next_order_recommendation_amd import synthetic as syn
+    from oracle import oracle
+
+    shape = _shape(name)
+    w = syn.synthetic_bert_weights(shape, seed=len(name))
+    ids, cu = _batch(shape, seed=len(name))
+    assert 512 < cu[-1] <= 3584
+    want = oracle.encode(w, _cfg(shape), ids, cu)
+    got = {}
+    for form, mode, env in [("latency", "f16x3", {}), ("layer", "f16x3", {"ICREC_SMALL_M": 512}),
+                            ("latency_unfused", "f16x3", {"ICREC_FUSE": 0}),
+                            ("layer_unfused", "f16x3", {"ICREC_SMALL_M": 512, "ICREC_FUSE": 0}),
+                            ("f32", "f32", {})]:
+        enc = _make(monkeypatch, w, shape, mode, **env)
+        got[form] = _run(enc, ids, cu)
+        enc.close()
+        err = float(np.abs(got[form] - want).max())
+        print(f"[{name}] {form}: max|emb - oracle| = {err:.3e}")
+        assert err < EMB_TOL, (form, err)
+    for form in ("layer", "latency_unfused", "layer_unfused"):
+        np.testing.assert_array_equal(got[form], got["latency"], err_msg=form)
+
+
+def test_max_position_is_the_sequence_limit(monkeypatch):
+    """Under max_position 64 a 64-token sequence encodes (against the oracle) and a 65-token one is refused."""
+    import torch
+
+    from instacart_next_order_recommendation_amd import synthetic as syn
+    from instacart_next_order_recommendation_amd._native import IcrecError
+    from oracle import oracle
+
+    shape = _shape("max_position64")
+    w = syn.synthetic_bert_weights(shape, seed=64)
+    enc = _make(monkeypatch, w, shape)
+    ids = np.arange(1, 66, dtype=np.int32)
+    one = _run(enc, ids[:64].copy(), np.array([0, 64], np.int32))
+    assert np.abs(one - oracle.encode(w, _cfg(shape), ids[:64], np.array([0, 64], np.int32))).max() < EMB_TOL
+    with pytest.raises(IcrecError):
+        enc.encode_packed(torch.from_numpy(ids).cuda(), torch.tensor([0, 65], dtype=torch.int32).cuda(), 65)
+    enc.close()
+
+
+def _split(enc, tokens):
+    from instacart_next_order_recommendation_amd import _native
+
+    m, t = C.c_int64(0), C.c_int64(0)
+    _native.check(_native.lib().icrec_encode_batch_split(enc._h, int(tokens), C.byref(m), C.byref(t)),
+                  "icrec_encode_batch_split")
+    return int(m.value), int(t.value)
+
+
+def _round_plus_remainder(enc, ids, cu, lo, hi):
+    """The first prefix of the batch that splits into whole rounds (64 tokens per CU) + a remainder in [lo, hi]."""
+    for n in range(1, cu.size):
+        main_t, tail_t = _split(enc, cu[n])
+        if lo <= tail_t <= hi:
+            return ids[: cu[n]].copy(), cu[: n + 1].copy(), main_t, tail_t
+    raise AssertionError(f"no prefix with a remainder in [{lo}, {hi}]")
+
+
+def _n_cu():
+    import torch
+
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.mark.parametrize("name", ["layers1", "inter3072"])
+def test_rounds_plus_remainder_on_the_side_stream(monkeypatch, name):
+    """Whole rounds through the layer kernels + a remainder through the latency-form kernels on the side stream: the
+    same bits as the unfused chain (ICREC_FUSE=0) and, for the remainder's sequences, as encoding them alone."""
+    from instacart_next_order_recommendation_amd import synthetic as syn
+
+    shape = _shape(name)
+    w = syn.synthetic_bert_weights(shape, seed=7)
+    ids, cu = syn.synthetic_token_batch(400, seed=11, mean_len=90, std_len=60, lo=3, hi=256, vocab_size=2048)
+    enc = _make(monkeypatch, w, shape)
+    ids, cu, main_t, tail_t = _round_plus_remainder(enc, ids, cu, 1, 2560)
+    assert main_t % (64 * _n_cu()) == 0 and int(np.diff(cu).max()) > 128 and cu.size > 65
+    a = _run(enc, ids, cu)
+    ref = _make(monkeypatch, w, shape, ICREC_FUSE=0)
+    np.testing.assert_array_equal(_run(ref, ids, cu), a)
+    ref.close()
+    s0 = int(np.searchsorted(cu, main_t, side="right")) - 1
+    sub_cu = (cu[s0:] - cu[s0]).astype(np.int32)
+    np.testing.assert_array_equal(_run(enc, ids[cu[s0]:].copy(), sub_cu), a[s0:])
+    enc.close()
+
+
+def test_remainder_longer_than_small_m(monkeypatch, minilm_weights):
+    """ICREC_SMALL_M=512 with ICREC_TAIL_M=2560: a ~2,000-token remainder is longer than small_m, so it goes through the
+    layer kernels (activation-resident QKV, fused FFN) on the side stream.  Same bits as the default encoder (the
+    remainder through the latency form) and as the unfused chain."""
+    from instacart_next_order_recommendation_amd import synthetic as syn
+
+    ids, cu = syn.synthetic_token_batch(400, seed=13, mean_len=90, std_len=60, lo=3, hi=256)
+    enc = _make(monkeypatch, minilm_weights, syn.BertShape(), ICREC_SMALL_M=512, ICREC_TAIL_M=2560)
+    ids, cu, main_t, tail_t = _round_plus_remainder(enc, ids, cu, 1700, 2300)
+    assert tail_t > 512 and main_t % (64 * _n_cu()) == 0
+    a = _run(enc, ids, cu)
+    np.testing.assert_array_equal(_run(enc, ids, cu), a)
+    enc.close()
+    for env in ({}, {"ICREC_FUSE": 0}, {"ICREC_SMALL_M": 512, "ICREC_FUSE": 0}):
+        other = _make(monkeypatch, minilm_weights, syn.BertShape(), **env)
+        np.testing.assert_array_equal(_run(other, ids, cu), a, err_msg=str(env))
+        other.close()
+
+
+def test_knob_values_are_clamped(monkeypatch, minilm_weights):
+    """ICREC_TAIL_M is clamped to one round minus one token, ICREC_SMALL_M to 2^20, negative values to 0: an absurd
+    setting behaves exactly as its clamped value - same split, same bits."""
+    from instacart_next_order_recommendation_amd import synthetic as syn
+
+    shape = syn.BertShape()
+    rnd = 64 * _n_cu()
+    ids, cu = syn.synthetic_token_batch(400, seed=17, mean_len=90, std_len=60, lo=3, hi=256)
+    n = int(np.searchsorted(cu, rnd + rnd // 2))       # about half a round past the first whole round
+    ids, cu = ids[: cu[n]].copy(), cu[: n + 1].copy()
+    absurd = _make(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=10 ** 12, ICREC_SMALL_M=10 ** 15)
+    clamped = _make(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=rnd - 1, ICREC_SMALL_M=1 << 20)
+    for t in (1, 513, rnd, rnd + 1, int(cu[-1]), 3 * rnd - 1, 1 << 30):
+        assert _split(absurd, t) == _split(clamped, t), t
+    assert _split(absurd, int(cu[-1])) == (rnd, int(cu[-1]) - rnd)
+    np.testing.assert_array_equal(_run(absurd, ids, cu), _run(clamped, ids, cu))
+    absurd.close(); clamped.close()
+    neg = _make(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=-5)
+    assert _split(neg, int(cu[-1])) == (int(cu[-1]), 0)     # clamped to 0: no remainder rule
+    neg.close()

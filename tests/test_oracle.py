@@ -1,14 +1,17 @@
 """The CPU oracle against the committed golden vectors (library outputs from
-oracle/pin_against_libs.py) — CPU only."""
+oracle/pin_against_libs.py), and against transformers / float64 numpy at the other model shapes and row widths
+the library accepts — CPU only."""
 from __future__ import annotations
 
 import hashlib
 
 import numpy as np
+import pytest
 
 from instacart_next_order_recommendation_amd import synthetic as syn
 from oracle import oracle
 from tests.conftest import excl_lists
+from tests.encoder_shapes import SHAPES as ENCODER_SHAPES
 
 
 def _sha(a):
@@ -141,3 +144,56 @@ def test_bf16_storage_search_is_search_on_rounded_rows(golden_search):
     order = np.lexsort((np.arange(s.shape[1])[None, :].repeat(s.shape[0], 0), -s), axis=1)[:, :k]
     np.testing.assert_array_equal(idx, order)
     np.testing.assert_array_equal(sc, np.take_along_axis(s, order, axis=1))
+
+
+# ---------------------------------------------------------------- the oracle at the other shapes the library accepts
+@pytest.mark.parametrize("name", list(ENCODER_SHAPES))
+def test_encoder_matches_transformers_at_other_shapes(name):
+    """transformers.BertModel built from a BertConfig of the shape, run as oracle/pin_against_libs.py does (padded
+    batch, attention mask, mean pool, n_normalize normalisations): the oracle within the same 2e-6."""
+    pytest.importorskip("transformers")
+    from oracle.pin_against_libs import hf_encode
+
+    shape = syn.BertShape(vocab_size=2048, **ENCODER_SHAPES[name])
+    w = syn.synthetic_bert_weights(shape, seed=len(name))
+    hi = min(shape.max_position, 100)
+    ids, cu = syn.synthetic_token_batch(5, seed=len(name), mean_len=hi // 2, std_len=hi // 2, lo=1, hi=hi, vocab_size=2048)
+    if shape.max_position < 256:  # one sequence of exactly max_position tokens
+        ids = np.concatenate([ids, np.arange(shape.max_position, dtype=np.int32) % 2048])
+        cu = np.append(cu, cu[-1] + shape.max_position).astype(cu.dtype)
+    cfg = oracle.make_cfg(vocab_size=2048, hidden=shape.hidden, layers=shape.layers, heads=shape.heads,
+                          intermediate=shape.intermediate, max_position=shape.max_position, type_vocab=shape.type_vocab,
+                          ln_eps=shape.ln_eps, n_normalize=shape.n_normalize)
+    assert w.size == shape.weight_count() == oracle.weight_count(cfg)
+    want, _ = hf_encode(w, shape, ids, cu)
+    got = oracle.encode(w, cfg, ids, cu)
+    assert np.abs(got - want).max() < 2e-6, np.abs(got - want).max()
+
+
+@pytest.mark.parametrize("dim", [32, 96, 768, 1024, 4096])
+def test_search_matches_float64_cos_sim_at_other_widths(dim):
+    """At widths other than 384: oracle scores within tol of a float64 cos_sim - 1e-6 up to 384, scaled by
+    sqrt(dim / 384) above it (the typical growth of an fp32 chain's rounding error; 3.3e-6 at 4,096) - and its top-k
+    (with exclusions) the float64 order wherever that order is unambiguous (adjacent float64 scores 4 tol apart)."""
+    rng = np.random.default_rng(dim)
+    n, nq, k = 3000, 6, 20
+    P = rng.standard_normal((n, dim), dtype=np.float32)
+    q = rng.standard_normal((nq, dim), dtype=np.float32)
+    q[0] = P[10] + 0.1 * q[0]
+    P64, q64 = P.astype(np.float64), q.astype(np.float64)
+    s64 = (q64 / np.linalg.norm(q64, axis=1, keepdims=True)) @ (P64 / np.linalg.norm(P64, axis=1, keepdims=True)).T
+    s = oracle.scores(oracle.normalize_rows(q), oracle.normalize_rows(P))
+    tol = 1e-6 * max(1.0, np.sqrt(dim / 384))
+    assert np.abs(s - s64).max() < tol
+    excl = [rng.choice(n, 30, replace=False).tolist() for _ in range(nq)]
+    idx, sc = oracle.search(q, P, k, excl)
+    clear = 0
+    for i in range(nq):
+        keep = np.setdiff1d(np.arange(n), excl[i])
+        order = keep[np.argsort(-s64[i, keep], kind="stable")][: k + 1]
+        np.testing.assert_array_less(np.abs(sc[i] - s64[i, idx[i]]), tol)
+        assert not set(idx[i].tolist()) & set(excl[i])
+        if np.diff(-s64[i, order]).min() >= 4 * tol:
+            np.testing.assert_array_equal(idx[i], order[:k])
+            clear += 1
+    assert clear >= nq // 2
