@@ -164,8 +164,8 @@ constexpr int LDQ = 36;  // K LDS row stride (even/odd split layout, like the GE
 // workgroup.  A workgroup whose sequence belongs to another bucket exits at once, so short
 // sequences run with the LDS footprint / occupancy of their own bucket even in a mixed batch.
 // K and V of the (sequence, head) live in LDS; each wave's 32 query rows come straight from
-// global memory into the B-operand registers.
-template <int NKT, int WAVES, bool SPLIT>
+// global memory into the B-operand registers.  Output: the fp32 context rows (`ctx`; ch / cl unused).
+template <int NKT, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void attention_kernel(const float* __restrict__ qkv,
                                                                const int32_t* __restrict__ cu, int heads, int H,
                                                                float scale_log2e, float* __restrict__ ctx,
@@ -285,15 +285,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention_kernel(const float* __re
         const int tq = qb * 32 + qrow;
         if (tq < L) {
             const float v = o[e] / Ls[wave * 32 + qrow];
-            const size_t at = (size_t)(t0 + tq) * H + hd * DH + r;
-            if (SPLIT) {
-                _Float16 hi, lo;
-                split_act(v, hi, lo);
-                ch[at] = hi;
-                cl[at] = lo;
-            } else {
-                ctx[at] = v;
-            }
+            ctx[(size_t)(t0 + tq) * H + hd * DH + r] = v;
         }
     }
 }
@@ -357,8 +349,9 @@ __device__ __forceinline__ half4 lds_read_tr(const _Float16* p) {
                                          (__attribute__((address_space(3))) fp16x4*)(reinterpret_cast<uintptr_t>(p))));
 }
 
-// nlo: sequences of nlo < nkt <= NKT key tiles belong to this launch (the others' workgroups exit at once)
-template <int NKT, int WAVES, bool SPLIT>
+// nlo: sequences of nlo < nkt <= NKT key tiles belong to this launch (the others' workgroups exit at once).
+// Output: the context as f16 hi/lo planes (`ch` / `cl`; ctx unused).
+template <int NKT, int WAVES>
 __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void attention_x3_kernel(const float* __restrict__ qkv,
                                                                   const int32_t* __restrict__ cu, int heads, int H,
                                                                   float scale_log2e, float* __restrict__ ctx,
@@ -387,10 +380,9 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
     __shared__ __attribute__((aligned(16))) _Float16 Vh[NKT * 32 * 32];
     __shared__ __attribute__((aligned(16))) _Float16 Vl[NKT * 32 * 32];
     __shared__ float Ls[WAVES * 32];
-    // Plane output (SPLIT): every wave parks its 32 x 32 output tile (hi | lo) on the K planes once all waves have left
-    // them (second barrier) and writes it out 16 B per lane - 4 store instructions instead of 32 two-byte ones.
-    constexpr bool OB = SPLIT;
-    static_assert(!OB || WAVES * 2 * 32 * 32 <= 2 * NKT * 32 * 32, "the output tiles reuse the K planes");
+    // Plane output: every wave parks its 32 x 32 output tile (hi | lo) on the K planes once all waves have left them
+    // (second barrier) and writes it out 16 B per lane - 4 store instructions instead of 32 two-byte ones.
+    static_assert(WAVES * 2 * 32 * 32 <= 2 * NKT * 32 * 32, "the output tiles reuse the K planes");
     _Float16* const Ob = Kbuf;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -405,7 +397,6 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
 
     const int r = lane & 31, h = lane >> 5;
     const int qb = qb0 + wave;
-    ICREC_STAMP(0, 0);
     half8 qh[2], ql[2];  // B operand of S^T: this lane's query row, dims 16s + 8h .. +7
     {
         int qr = qb * 32 + r;
@@ -422,7 +413,6 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
             ql[ks] = half8{al[0], al[1], al[2], al[3], bl[0], bl[1], bl[2], bl[3]};
         }
     }
-    ICREC_STAMP(0, 6);  // Q rows arrived and split
     // K/V staging: all of this thread's loads are issued before the first one is consumed
     constexpr int STG = NKT * 32 * 8 / (WAVES * 64);  // = 4 for every bucket (WAVES == NKT)
     static_assert(NKT * 32 * 8 % (WAVES * 64) == 0, "staging: whole rounds");
@@ -436,10 +426,6 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
         kreg[it] = *reinterpret_cast<const f32x4*>(src + H);
         vreg[it] = *reinterpret_cast<const f32x4*>(src + 2 * H);
     }
-#ifdef ICREC_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ICREC_STAMP(0, 7);  // K / V rows arrived
-#endif
 #pragma unroll
     for (int it = 0; it < STG; ++it) {
         const int id = tid + it * WAVES * 64;
@@ -455,11 +441,8 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
             *reinterpret_cast<half4*>(Kl + off) = klo;
         }
     }
-    ICREC_STAMP(0, 1);
     __syncthreads();
-    ICREC_STAMP(0, 2);
     const bool active = qb < nkt;
-    if (!RECOMP && !OB && !active) return;  // idle wave (no barrier below)
 
     // raw scores S' = 256 S of key tile kt for this wave's 32 queries, keys beyond the sequence at -inf (only the one
     // tile that has any pays for the selects: uniform branch)
@@ -497,12 +480,7 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
 #pragma unroll
             for (int j = 0; j < 8; j += 2) {
                 half2w a, b;
-#if defined(ICREC_ATT_ABL) && (ICREC_ATT_ABL & 1)  // timing ablation (tools/ffn_bench.hip): no lo plane of P
-                a = __builtin_bit_cast(half2w, __builtin_amdgcn_cvt_pkrtz(pt[8 * ks + j], pt[8 * ks + j + 1]));
-                b = a;
-#else
                 split_pair_prescaled(pt[8 * ks + j], pt[8 * ks + j + 1], a, b);
-#endif
                 ph[j] = a[0]; ph[j + 1] = a[1];
                 pl[j] = b[0]; pl[j + 1] = b[1];
             }
@@ -537,7 +515,6 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
                 }
             }
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            ICREC_STAMP(0, 9);  // first score pass (row maxima) done (slot 8 holds the HW id)
             const float shift = fmaf(-mx, cs, 10.0f);
             float2w ls2 = float2w{0.0f, 0.0f};
 #pragma unroll
@@ -545,11 +522,7 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
                 if (kt < nkt) {
                     f32x16 t = score_tile(kt);
 #pragma unroll
-#if defined(ICREC_ATT_ABL) && (ICREC_ATT_ABL & 2)  // timing ablation: no exponential
-                    for (int e = 0; e < 16; ++e) t[e] = fmaf(t[e], cs, shift);
-#else
                     for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(fmaf(t[e], cs, shift), 15.9f));
-#endif
 #pragma unroll
                     for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{t[e], t[e + 1]};
                     pv_tile(kt, t, o);
@@ -560,9 +533,6 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
             lrow = h == 0 ? lrow + other : other + lrow;
             if (h == 0) Ls[wave * 32 + r] = lrow;
         }
-        ICREC_STAMP(0, 3);
-        __syncthreads();  // every wave has left the K planes: they become the output tiles
-        if (!active) return;
     } else {
     if (active) {
     f32x16 sc[NKT];
@@ -604,70 +574,39 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
         lrow = h == 0 ? lrow + other : other + lrow;
     }
     if (h == 0) Ls[wave * 32 + r] = lrow;
-    ICREC_STAMP(0, 3);
 
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
         if (kt < nkt) pv_tile(kt, sc[kt], o);
     }
-    if (OB) {
-        __syncthreads();  // every wave has left the K planes
-        if (!active) return;
     }
+    __syncthreads();  // every wave has left the K planes: they become the output tiles
+    if (!active) return;
+    // park the wave's 32 x 32 output tile (hi and lo planes) in LDS row-major, then write it out 16 B
+    // per lane: 4 store instructions instead of 32 two-byte ones
+    _Float16* ob = Ob + wave * (2 * 32 * 32);
+#pragma unroll
+    for (int e = 0; e < 16; e += 2) {
+        const int q0 = acc_row(e, lane), q1 = acc_row(e + 1, lane);
+        const float v0 = o[e] * (0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q0]));
+        const float v1 = o[e + 1] * (0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q1]));
+        half2w hi, lo;
+        split_pair_prescaled(v0 * WT_SA, v1 * WT_SA, hi, lo);
+        ob[q0 * 32 + r] = hi[0];
+        ob[q1 * 32 + r] = hi[1];
+        ob[32 * 32 + q0 * 32 + r] = lo[0];
+        ob[32 * 32 + q1 * 32 + r] = lo[1];
     }
-    ICREC_STAMP(0, 4);
-    if (OB) {
-        // park the wave's 32 x 32 output tile (hi and lo planes) in LDS row-major, then write it out 16 B
-        // per lane: 4 store instructions instead of 32 two-byte ones
-        _Float16* ob = Ob + wave * (2 * 32 * 32);
 #pragma unroll
-        for (int e = 0; e < 16; e += 2) {
-            const int q0 = acc_row(e, lane), q1 = acc_row(e + 1, lane);
-            const float v0 = o[e] * (0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q0]));
-            const float v1 = o[e + 1] * (0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q1]));
-            half2w hi, lo;
-            split_pair_prescaled(v0 * WT_SA, v1 * WT_SA, hi, lo);
-            ob[q0 * 32 + r] = hi[0];
-            ob[q1 * 32 + r] = hi[1];
-            ob[32 * 32 + q0 * 32 + r] = lo[0];
-            ob[32 * 32 + q1 * 32 + r] = lo[1];
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int id = lane + 64 * t, qrow = id >> 2, c8 = (id & 3) * 8;
-            const int tq = qb * 32 + qrow;
-            if (tq < L) {
-                const size_t at = (size_t)(t0 + tq) * H + hd * DH + c8;
-                *reinterpret_cast<u32x4*>(ch + at) = *reinterpret_cast<const u32x4*>(ob + qrow * 32 + c8);
-                *reinterpret_cast<u32x4*>(cl + at) = *reinterpret_cast<const u32x4*>(ob + 32 * 32 + qrow * 32 + c8);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int qrow = acc_row(e, lane);
-            const int tq = qb * 32 + qrow;
-            if (tq < L) {
-                const float v = o[e] * (0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + qrow]));
-                const size_t at = (size_t)(t0 + tq) * H + hd * DH + r;
-                if (SPLIT) {
-                    _Float16 hi, lo;
-                    split_act(v, hi, lo);
-                    ch[at] = hi;
-                    cl[at] = lo;
-                } else {
-                    ctx[at] = v;
-                }
-            }
+    for (int t = 0; t < 2; ++t) {
+        const int id = lane + 64 * t, qrow = id >> 2, c8 = (id & 3) * 8;
+        const int tq = qb * 32 + qrow;
+        if (tq < L) {
+            const size_t at = (size_t)(t0 + tq) * H + hd * DH + c8;
+            *reinterpret_cast<u32x4*>(ch + at) = *reinterpret_cast<const u32x4*>(ob + qrow * 32 + c8);
+            *reinterpret_cast<u32x4*>(cl + at) = *reinterpret_cast<const u32x4*>(ob + 32 * 32 + qrow * 32 + c8);
         }
     }
-    ICREC_STAMP(0, 5);
-#ifdef ICREC_STAMPS
-    if (threadIdx.x == 0) {  // where this workgroup ran: HW_ID (cu / sh / se in bits 8..15) and XCC_ID, for the per-CU timeline of the harness
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4), xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);
-        g_stamps[((size_t)blockIdx.x * 2) * 64 + 8] = ((unsigned long long)xcc << 32) | hw;
-    }
-#endif
 }
 
 // ---------------------------------------------------------------- mean pooling + L2 normalise
@@ -838,23 +777,18 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
                              const float* bias, float* out, _Float16* oh, _Float16* ol, hipStream_t st, int small_m) {
     if (T <= small_m) {
         if constexpr (EPI == 0 || EPI == 2) {  // 16-feature tiles per wave, twice the workgroups (wt_linear_half_kernel)
-            if (N % 64 == 0 && K % 128 == 0) {
-                const int nbn = N / 64;
-                if (K % 256 == 0 && K >= 1024)  // FFN-down: weights eight k-steps ahead
-                    hipLaunchKernelGGL((wt_linear_half_kernel<EPI, 8>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp,
-                                       N, bias, out, (const _Float16*)oh, (const _Float16*)ol, nbn);
-                else if (K % 384 == 0)  // K = 384: six of the twelve k-steps ahead
-                    hipLaunchKernelGGL((wt_linear_half_kernel<EPI, 6>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp,
-                                       N, bias, out, (const _Float16*)oh, (const _Float16*)ol, nbn);
-                else
-                hipLaunchKernelGGL((wt_linear_half_kernel<EPI>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp, N,
-                                   bias, out, (const _Float16*)oh, (const _Float16*)ol, nbn);
-                return;
-            }
+            const int nbn = N / 64;
+            if (K % 256 == 0 && K >= 1024)  // FFN-down: weights eight k-steps ahead
+                hipLaunchKernelGGL((wt_linear_half_kernel<EPI, 8>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp,
+                                   N, bias, out, (const _Float16*)oh, (const _Float16*)ol, nbn);
+            else  // K = 384 (or another multiple of 384): six k-steps ahead
+                hipLaunchKernelGGL((wt_linear_half_kernel<EPI, 6>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp,
+                                   N, bias, out, (const _Float16*)oh, (const _Float16*)ol, nbn);
+        } else {
+            const int nbn = N / 128;
+            hipLaunchKernelGGL((wt_linear_kernel<1, 1, 4, EPI>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K,
+                               Wp, N, bias, out, oh, ol, nbn);
         }
-        const int nbn = N / 128;
-        hipLaunchKernelGGL((wt_linear_kernel<1, 1, 4, EPI>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K,
-                           Wp, N, bias, out, oh, ol, nbn);
     } else {
         const int nbn = N / 384;
         hipLaunchKernelGGL((wt_linear_kernel<3, 2, 1, EPI>), dim3(((T + 63) / 64) * nbn), dim3(256), 0, st, Xh, Xl, T, K,
@@ -864,7 +798,8 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
 
 // Launch every length bucket that can occur for max_seqlen (a bucket whose workgroups all exit
 // costs a few microseconds; single-sequence calls launch exactly one bucket).
-template <bool SPLIT, bool X3>
+// X3: the f16x3 kernel, context out as planes (attention_x3_kernel); otherwise exact fp32 rows (attention_kernel).
+template <bool X3>
 static void launch_attention(const float* qkv, const int32_t* cu, int n_seqs, int heads, int H, int max_seqlen,
                              float* ctx, _Float16* ch, _Float16* cl, hipStream_t st, int buckets = 31,
                              const int32_t* order = nullptr) {
@@ -876,18 +811,20 @@ static void launch_attention(const float* qkv, const int32_t* cu, int n_seqs, in
     const dim3 grid1(n_seqs * heads, 1);
 #define ICREC_ATT(NKT, W, NLO)                                                                                   \
     do {                                                                                                         \
-        if (X3) hipLaunchKernelGGL((attention_x3_kernel<NKT, W, SPLIT>), grid1, dim3(W * 64), 0, st, qkv, cu, heads, H, sl2e, ctx, ch, cl, order, NLO); \
-        else hipLaunchKernelGGL((attention_kernel<NKT, W, SPLIT>), grid1, dim3(W * 64), 0, st, qkv, cu, heads, H, sl2e, ctx, ch, cl);      \
+        if constexpr (X3) hipLaunchKernelGGL((attention_x3_kernel<NKT, W>), grid1, dim3(W * 64), 0, st, qkv, cu, heads, H, sl2e, ctx, ch, cl, order, NLO); \
+        else hipLaunchKernelGGL((attention_kernel<NKT, W>), grid1, dim3(W * 64), 0, st, qkv, cu, heads, H, sl2e, ctx, ch, cl);      \
     } while (0)
     if ((buckets & 1) && (single ? nkt_max == 1 : true)) ICREC_ATT(1, 1, 0);
     if ((buckets & 2) && (single ? nkt_max == 2 : nkt_max >= 2)) ICREC_ATT(2, 2, 1);
     if ((buckets & 4) && (single ? (nkt_max == 3 || nkt_max == 4) : nkt_max >= 3)) ICREC_ATT(4, 4, 2);
-    if (X3 && !single) {  // f16x3 batches: the long sequences in two buckets (5-6 and 7-8 key tiles)
-        if ((buckets & 8) && nkt_max >= 5) ICREC_ATT(6, 6, 4);
-        if ((buckets & 16) && nkt_max >= 7) ICREC_ATT(8, 8, 6);
-    } else if ((buckets & 8) && nkt_max >= 5) {
-        ICREC_ATT(8, 8, 4);
+    if constexpr (X3) {
+        if (!single) {  // f16x3 batches: the long sequences in two buckets (5-6 and 7-8 key tiles)
+            if ((buckets & 8) && nkt_max >= 5) ICREC_ATT(6, 6, 4);
+            if ((buckets & 16) && nkt_max >= 7) ICREC_ATT(8, 8, 6);
+            return;
+        }
     }
+    if ((buckets & 8) && nkt_max >= 5) ICREC_ATT(8, 8, 4);
 #undef ICREC_ATT
 }
 
@@ -902,6 +839,8 @@ size_t icrec_encoder_weight_count(const icrec_bert_cfg* cfg) { return cfg ? weig
 int icrec_encoder_create(const float* weights_host, size_t n_floats, const icrec_bert_cfg* cfg, int device,
                          icrec_encoder** out) {
     ICREC_REQUIRE(weights_host && cfg && out, "icrec_encoder_create: NULL argument");
+    // The kernels and their dispatch rely on these two: every GEMM has K = 384 or K = intermediate, a multiple of 384,
+    // and N = 384, 1,152 or intermediate (launch_wt_linear's ring depths and tile splits, the fused FFN's 128-wide chunks).
     ICREC_REQUIRE(cfg->hidden == HID, "icrec_encoder_create: this build supports hidden=384 only (got %d)", cfg->hidden);
     ICREC_REQUIRE(cfg->heads * DH == cfg->hidden, "icrec_encoder_create: head_dim must be 32 (heads=%d)", cfg->heads);
     ICREC_REQUIRE(cfg->intermediate >= 384 && cfg->intermediate % 384 == 0, "icrec_encoder_create: intermediate size must be a multiple of 384 (got %d)", cfg->intermediate);
@@ -1060,8 +999,6 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
     batch_split(e, T, &T_main, &T_tail);
     const bool fuse = e->fuse, side_stream = e->side_stream;
     const int small_m = e->small_m;
-    const bool qkv_res = fuse && H == 384;
-    const bool lnin = fuse && H == 384 && I % 64 == 0;  // small ranges: LayerNorms folded into the consuming GEMMs
     const bool split_att = x3 && side_stream && n_seqs >= 64 && max_seqlen > 128;  // batches with a long bucket
     Encoder::Side* sd = nullptr;
     if (x3 && side_stream && (T_tail || split_att))
@@ -1097,14 +1034,14 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
             // CU, a short remainder [T_main, T) through the small-batch kernels (same arithmetic, same bits) instead
             // of costing every batch kernel an extra, almost empty round.
             auto qkv_stage = [&](int r0, int Tn, hipStream_t st) -> int {
-                if (Tn > small_m && qkv_res) {  // activation-resident form: one 64-token workgroup per CU
+                if (Tn > small_m && fuse) {  // activation-resident form: one 64-token workgroup per CU
                     auto kern = qkv_resident_kernel;
                     if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), QKVR_LDS)) return rc_;
                     hipLaunchKernelGGL(kern, dim3((Tn + 63) / 64), dim3(512), QKVR_LDS, st, xh + (size_t)r0 * H,
                                        xl + (size_t)r0 * H, Tn, L.Wqkv_p, L.bqkv, qkv + (size_t)r0 * 3 * H, 3 * H);
                     return ICREC_OK;
                 }
-                if (lnin && l > 0 && Tn <= small_m) {
+                if (fuse && l > 0 && Tn <= small_m) {
                     // small ranges: the previous layer's FFN LayerNorm is this kernel's prologue (t1 rows -> planes in LDS
                     // and, from the workgroups of feature block 0, to xh / xl): one graph node fewer per layer
                     const LayerW& Lp = e->layers[l - 1];
@@ -1128,7 +1065,7 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
                     // (x1 stays on chip between the two LayerNorm sites)
                     ScopedTimer tm(T_FFN_UP, st);
                     const int nblk = (Tn + 63) / 64;
-                    auto kern = ffn_fused2_kernel<0, true>;
+                    auto kern = ffn_fused2_kernel;
                     if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), FFN2_LDS)) return rc_;
                     // ... and, but for the last layer, the NEXT layer's QKV projection of the rows it has just normalised
                     const bool next_qkv = l + 1 < c.layers;
@@ -1140,7 +1077,7 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
                 } else {
                     _Float16 *const hhr = hh + (size_t)r0 * I, *const hlr = hl + (size_t)r0 * I;
                     launch_wt_linear<2>(chr, clr, Tn, H, L.Wo_p, H, L.bo, t1r, xhr, xlr, st, small_m);  // residual: x planes
-                    if (lnin && Tn <= small_m) {  // LayerNorm + FFN-up in one node (wt_linear_lnin_kernel)
+                    if (fuse && Tn <= small_m) {  // LayerNorm + FFN-up in one node (wt_linear_lnin_kernel)
                         const int nbn = I / 64;
                         hipLaunchKernelGGL((wt_linear_lnin_kernel<1, true>), dim3(((Tn + 31) / 32) * nbn), dim3(256), 0, st,
                                            (const float*)t1r, Tn, L.g1, L.b1n, c.ln_eps, xhr, xlr, L.W1_p, I, L.b1,
@@ -1155,7 +1092,7 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
                     }
                     launch_wt_linear<2>(hhr, hlr, Tn, I, L.W2_p, H, L.b2, t1r, xhr, xlr, st, small_m);
                     // the FFN LayerNorm: the prologue of the next layer's QKV projection (qkv_stage) - but for the last layer
-                    if (!(lnin && Tn <= small_m && l + 1 < c.layers))
+                    if (!(fuse && Tn <= small_m && l + 1 < c.layers))
                     hipLaunchKernelGGL(ln_wt_kernel, dim3((Tn + 15) / 16), dim3(256), 0, st, t1r, Tn, L.g2, L.b2n,
                                        c.ln_eps, xhr, xlr);
                 }
@@ -1166,8 +1103,8 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
             // stream's in-order execution keeps its own layers apart.
             // batches: layer 0 projects Q / K / V in a launch of its own; every later layer's projection is the epilogue of
             // the previous layer's fused kernel (also for a remainder longer than small_m, see tail_m)
-            const bool qkv_in_fused = fuse && T_main > small_m && H == 384;
-            const bool tail_qkv_in_fused = fuse && T_tail > small_m && H == 384;
+            const bool qkv_in_fused = fuse && T_main > small_m;
+            const bool tail_qkv_in_fused = fuse && T_tail > small_m;
             hipStream_t ts = st;
             if (T_tail && use_side) {
                 ts = sd->side;
@@ -1189,12 +1126,12 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
                 // buckets' workgroups run beside it from the side stream instead of after it
                 ICREC_HIP(hipEventRecord(sd->ev_q, st));
                 ICREC_HIP(hipStreamWaitEvent(sd->side, sd->ev_q, 0));
-                launch_attention<true, true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, sd->side, 7 | 16, order);
+                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, sd->side, 7 | 16, order);
                 ICREC_HIP(hipEventRecord(sd->ev_sa, sd->side));
-                launch_attention<true, true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 8, order);
+                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 8, order);
                 ICREC_HIP(hipStreamWaitEvent(st, sd->ev_sa, 0));
             } else {
-                launch_attention<true, true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 31, order);
+                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 31, order);
             }
             if (T_tail) {
                 if (use_side) {
@@ -1210,7 +1147,7 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
             }
         } else {
             launch_linear<false>(x, T, H, L.Wqkv, 3 * H, L.bqkv, qkv, st);
-            launch_attention<false, false>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st);
+            launch_attention<false>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st);
             launch_linear<false>(ctx, T, H, L.Wo, H, L.bo, t1, st);
             hipLaunchKernelGGL((add_ln_kernel<HID, false>), dim3(rows_grid), dim3(256), 0, st, t1, x, T, L.g1, L.b1n,
                                c.ln_eps, xh, xl);

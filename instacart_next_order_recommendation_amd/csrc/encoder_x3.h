@@ -184,9 +184,8 @@ __device__ __forceinline__ int ffn_x_pos(int tok, int ch) { return tok * 768 + (
 // and / or - xs != nullptr - into the resident activation image of the fused kernel in LDS (layout ffn_x_pos; the
 // caller's next barrier orders those writes against their readers).  The fused kernel runs it on all eight waves at once: four
 // hold token block 0, four token block 1, every wave with a transposition tile of its own (`slot`).
-// Every thread of the workgroup calls; `sync` = the workgroup barrier (two of them).  lds: LNT_BYTES8 for eight slots.
-// ptid: index of the thread among the callers (0 .. 191 must be present).
-constexpr int LNT_BYTES8 = LNT_RED + 8 * LNT_TILE + LNT_PAR;   // 58,368 B
+// Every thread of the workgroup calls; `sync` = the workgroup barrier (two of them).  lds: LNT_RED + NSLOT * LNT_TILE +
+// LNT_PAR bytes.  ptid: index of the thread among the callers (0 .. 191 must be present).
 template <int NSLOT, int TTW, int TT, class Sync>
 __device__ __forceinline__ void wt_ln_block(Acc32 (&acc)[3][TTW], int q, int tb, int slot, _Float16* __restrict__ xh,
                                             _Float16* __restrict__ xl, int64_t m0, int64_t T,
@@ -199,7 +198,6 @@ __device__ __forceinline__ void wt_ln_block(Acc32 (&acc)[3][TTW], int q, int tb,
     asm volatile("" : "+v"(lane));  // opaque: the per-lane addresses below are computed HERE, not hoisted to the kernel's
                                     // entry and held (or spilled) across the loops in front of this call
     const int c = lane & 15, g = lane >> 4;
-    ICREC_STAMP(0, 32); ICREC_STAMP(4, 32);
     // gamma / beta -> LDS (visible after the first barrier): each lane needs the 24 values of its quarter of the wave's
     // 96 features - as vector loads that is dozens of 1 KB requests through the texture path per wave for 768 distinct bytes
     if (ptid < 192) *reinterpret_cast<f32x4*>(par + 4 * ptid) = wt_ln_par_load(gam, bet, ptid);
@@ -220,7 +218,6 @@ __device__ __forceinline__ void wt_ln_block(Acc32 (&acc)[3][TTW], int q, int tb,
         part = part + __shfl_xor(part, 32, 64);  // Pq: the same bits in the four lanes of a token
         if (g == 0) red[(tb * 32 + ti * 16 + c) * 4 + q] = part;
     }
-    ICREC_STAMP(0, 33); ICREC_STAMP(4, 33);
     sync();
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti) {
@@ -241,9 +238,7 @@ __device__ __forceinline__ void wt_ln_block(Acc32 (&acc)[3][TTW], int q, int tb,
         sq = sq + __shfl_xor(sq, 32, 64);
         if (g == 0) red[256 + (tb * 32 + ti * 16 + c) * 4 + q] = sq;
     }
-    ICREC_STAMP(0, 34); ICREC_STAMP(4, 34);
     sync();
-    ICREC_STAMP(0, 35); ICREC_STAMP(4, 35);
     float rstd[2];
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti) {
@@ -309,7 +304,6 @@ __device__ __forceinline__ void wt_ln_block(Acc32 (&acc)[3][TTW], int q, int tb,
         if (xs != nullptr) *reinterpret_cast<u32x4*>(xs + FFN2_XPLANE + ffn_x_pos(tb * 32 + row, q * 12 + ch)) = o[k];
         if (xl != nullptr && t0 + row < T) *reinterpret_cast<u32x4*>(xl + (t0 + row) * 384 + q * 96 + ch * 8) = o[k];
     }
-    ICREC_STAMP(0, 36); ICREC_STAMP(4, 36);
 }
 
 // The unfused form of the same LayerNorm (small batches; the unfused reference chain): planes(x) <- LN(a), `a` =
@@ -382,8 +376,8 @@ constexpr int LN_LD = 388;  // floats per staged output row in LDS (+16 B: the 1
 //   EPI 1: erf-GELU (tf:336), result as f16 hi/lo planes   (FFN-up of small batches)
 //   EPI 2: residual + bias (planes rh / rl, row stride N) added to the accumulators after the K loop, out fp32 =
 //          acc * 2^-14: the LayerNorm input of attention-out / FFN-down for small batches (ln_wt_kernel follows)
-// <1, 1, 4, EPI>: the small-batch form (weights four k-steps ahead) (<= 512 tokens and the remainder of a batch): 32-token x 128-feature
-// workgroups, latency-bound.  <3, 2, 1, EPI>: the 64-token x 384-feature form of the UNFUSED reference chain
+// <1, 1, 4, 1>: the small-batch FFN-up (weights four k-steps ahead; small batches and the remainder of a batch take
+// wt_linear_half_kernel for EPI 0 / 2): 32-token x 128-feature workgroups, latency-bound.  <3, 2, 1, EPI>: the 64-token x 384-feature form of the UNFUSED reference chain
 // (ICREC_FUSE=0: tests compare the fused kernels against it bit for bit).
 // Each lane holds 4 consecutive features of one token per register group: 16-B (fp32) / 8-B (planes) stores.
 template <int NTW, int TTW, int D, int EPI>
@@ -450,7 +444,6 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
             }
             if (tt == 0) __syncthreads();
         }
-        ICREC_STAMP(0, 30);
         return;
     }
 
@@ -482,7 +475,6 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
                     }
                 }
         }
-    ICREC_STAMP(0, 30);
 }
 
 // ---------------------------------------------------------------- resident activation image (fused FFN, QKV)
@@ -539,7 +531,7 @@ __device__ __forceinline__ void ffn_x_frag(XFrag& x, const char* Xs, const int (
 // MFMAs) and a workgroup 32 tokens x 64 features: twice the workgroups, half the bytes and half the MFMA chain per CU
 // (measured, same box: FFN-down -12 us per request, attention-out another -10 us; profiles/r04_single_request_anatomy.txt).
 // Per output the chain is wt_kloop's (k-steps ascending, (w_hi,x_hi), (w_lo,x_hi), (w_hi,x_lo)): identical bits.
-template <int EPI, int D = 4>  // 0: out = acc * 2^-14 + bias; 2: residual planes rh / rl + bias added after the loop, out = that * 2^-14
+template <int EPI, int D>  // 0: out = acc * 2^-14 + bias; 2: residual planes rh / rl + bias added after the loop, out = that * 2^-14
 __global__ __launch_bounds__(256, 2) void wt_linear_half_kernel(const _Float16* __restrict__ Xh,
                                                                     const _Float16* __restrict__ Xl, int T, int K,
                                                                     const _Float16* __restrict__ Wp, int N,
@@ -555,7 +547,7 @@ __global__ __launch_bounds__(256, 2) void wt_linear_half_kernel(const _Float16* 
     const unsigned lo8 = lane * 8;
     const int KS = K / 32, nslab = K / 64;
     const _Float16* const wp = Wp + wt_frag_off(nt, 0, KS) + (size_t)fi * (2 * WT_FRAG);
-    static_assert(D == 4 || D == 6 || D == 8, "ring depth: 4, 6 (K a multiple of 384) or 8 (K a multiple of 256) k-steps");
+    static_assert(D == 6 || D == 8, "ring depth: 6 (K a multiple of 384) or 8 (K a multiple of 256) k-steps");
     half8 wh[D], wl[D];
     auto w_load1 = [&](int slot, int ks) {
         const _Float16* p = wp + (size_t)ks * (4 * WT_FRAG);
@@ -601,7 +593,7 @@ __global__ __launch_bounds__(256, 2) void wt_linear_half_kernel(const _Float16* 
         __syncthreads();
     };
     // the ring slot of k-step 2 s + j is 2 (s % (D / 2)) + j, the register buffer of the next slab alternates with s & 1: a trip of
-    // the unrolled loop covers lcm(D / 2, 2) slabs (the host checks that nslab is a multiple of it)
+    // the unrolled loop covers lcm(D / 2, 2) slabs (launch_wt_linear picks D from K so that nslab is a multiple of it)
     if constexpr (D == 6) {
         for (int s = 0; s < nslab; s += 6) {
             slab(s, std::integral_constant<int, 0>{}, xb);
@@ -612,13 +604,11 @@ __global__ __launch_bounds__(256, 2) void wt_linear_half_kernel(const _Float16* 
             slab(s + 5, std::integral_constant<int, 2>{}, xa);
         }
     } else {
-        for (int s = 0; s < nslab; s += D / 2) {
+        for (int s = 0; s < nslab; s += 4) {
             slab(s, std::integral_constant<int, 0>{}, xb);
             slab(s + 1, std::integral_constant<int, 1>{}, xa);
-            if constexpr (D == 8) {
-                slab(s + 2, std::integral_constant<int, 2>{}, xb);
-                slab(s + 3, std::integral_constant<int, 3>{}, xa);
-            }
+            slab(s + 2, std::integral_constant<int, 2>{}, xb);
+            slab(s + 3, std::integral_constant<int, 3>{}, xa);
         }
     }
     const int feat = nt * 32 + fi * 16 + 4 * g;
@@ -926,7 +916,7 @@ __device__ __forceinline__ void bar_lds() {  // LDS hand-off barrier that leaves
 }
 
 //
-// AO = true (the product): the kernel is the whole post-attention half of a layer.  Its prologue is the attention
+// The kernel is the whole post-attention half of a layer.  Its prologue is the attention
 // output projection + residual + LayerNorm (tf:289-293) of the same 64 tokens:
 //   the block's CONTEXT planes (ch / cl) go to the resident image; the producer waves run K = 384 over Wo while the
 //   consumer waves - they own the [96 features x 64 tokens] accumulator layout and its LayerNorm epilogue - stage
@@ -934,9 +924,6 @@ __device__ __forceinline__ void bar_lds() {  // LDS hand-off barrier that leaves
 //   + x) never travels to HBM (-2 x 768 B per token per layer each way, one launch fewer), the FFN proceeds on it as
 //   before.  Per output the same chain and the same LayerNorm order as wt_linear_kernel<.., 2> + ln_wt_kernel:
 //   identical bits.
-// VAR (tools/ffn_bench.hip only; the product uses 0), timing ablations: 1 = no GELU, 4 = no in-loop weight loads,
-// 8 = no in-loop LDS fragment reads, 32 = no sched_group_barrier interleave, 64 = ~16 k idle cycles at the start
-template <int VAR, bool AO = false>
 __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict__ xh, _Float16* __restrict__ xl,
                                                             int T, int I,
                                                             const _Float16* __restrict__ W1p,
@@ -964,138 +951,117 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
     const int64_t m0 = (int64_t)blockIdx.x * 64;
     const int NC = I / FFN_IC, KS2 = I / 32;
 
-    ICREC_STAMP(0, 0);
-    ICREC_STAMP(4, 0);
-    ICREC_STAMP_RT(0, 62);
-    if constexpr ((VAR & 64) != 0) {  // harness: ~16 k idle cycles per workgroup (does time follow cycles or power?)
-        __builtin_amdgcn_s_sleep(127);
-        __builtin_amdgcn_s_sleep(127);
-    }
     unsigned lo8 = lane * 8;
-    if constexpr (AO) {
-        // x1 = LayerNorm(Wo . ctx + bo + x) -> the resident image.
-        // All eight waves share the work; wave (q, half) owns features q*96 .. +95 of token block `half`:
-        //  * it stages its residual rows into the accumulator layout (global -> its private LDS tile -> r);
-        //  * the GEMM runs in the producers' form (one 32-feature block x 64 tokens at a time, weight ring 4 k-steps deep,
-        //    the loop of qkv_resident_kernel): producer p takes blocks p, p + 4 and p + 8 while the consumer on its SIMD
-        //    stages its residual rows (a 2 : 1 split with the consumers' rows staged first left the producers waiting);
-        //  * the products travel through the context image, dead once every wave has left its K loops: 12 blocks x 2
-        //    token blocks x 4 tiles x 1 KB = the 96 KB of the image, each tile in the lane order both sides hold it in
-        //    (conflict-free 16-B accesses); every wave picks up the 12 tiles of its (q, half), adds r and takes part in
-        //    the LayerNorm of its token block, which lands in the image.
-        // Scratch (LayerNorm exchange, eight transposition tiles): the H buffers, idle until the FFN starts.
-        // (the two roles run the same steps from separate instantiations: a value defined on one path only - the early
-        // residual rows, a ring - would otherwise be carried, and spilled, along the other path too)
-        auto prologue = [&](auto role_tag) {
-            constexpr bool PROD = decltype(role_tag)::value;
-            constexpr int tb = PROD ? 0 : 1;  // the token block this wave stages, adds and normalises
-            ResRows rr;  // the wave's residual rows.  Consumers (one GEMM block, registers to spare): requested first of
-                         // all, they arrive under the staging of the context planes and are transposed before the K
-                         // loop.  Producers (two blocks: beside two accumulator sets, the ring and the fragments the
-                         // rows would spill): requested behind the K loops - they finish first and wait anyway.
-            if (!PROD) wt_res_rows_load(rr, q, tb, xh, xl, m0, T);
-            ffn_x_stage<512>(Xs, ch, cl, m0, T);  // the context planes
-            ICREC_STAMP(0, 44); ICREC_STAMP(4, 44);
-            int xb[2][2];
-            ffn_x_bases(xb, c, g);
-            WFrag w[4][1];
-            {
-                const _Float16* const wp0[1] = {Wop + wt_frag_off(q, 0, KS1)};
+    // x1 = LayerNorm(Wo . ctx + bo + x) -> the resident image.
+    // All eight waves share the work; wave (q, half) owns features q*96 .. +95 of token block `half`:
+    //  * it stages its residual rows into the accumulator layout (global -> its private LDS tile -> r);
+    //  * the GEMM runs in the producers' form (one 32-feature block x 64 tokens at a time, weight ring 4 k-steps deep,
+    //    the loop of qkv_resident_kernel): producer p takes blocks p, p + 4 and p + 8 while the consumer on its SIMD
+    //    stages its residual rows (a 2 : 1 split with the consumers' rows staged first left the producers waiting);
+    //  * the products travel through the context image, dead once every wave has left its K loops: 12 blocks x 2
+    //    token blocks x 4 tiles x 1 KB = the 96 KB of the image, each tile in the lane order both sides hold it in
+    //    (conflict-free 16-B accesses); every wave picks up the 12 tiles of its (q, half), adds r and takes part in
+    //    the LayerNorm of its token block, which lands in the image.
+    // Scratch (LayerNorm exchange, eight transposition tiles): the H buffers, idle until the FFN starts.
+    // (the two roles run the same steps from separate instantiations: a value defined on one path only - the early
+    // residual rows, a ring - would otherwise be carried, and spilled, along the other path too)
+    auto prologue = [&](auto role_tag) {
+        constexpr bool PROD = decltype(role_tag)::value;
+        constexpr int tb = PROD ? 0 : 1;  // the token block this wave stages, adds and normalises
+        ResRows rr;  // the wave's residual rows.  Consumers (one GEMM block, registers to spare): requested first of
+                     // all, they arrive under the staging of the context planes and are transposed before the K
+                     // loop.  Producers (two blocks: beside two accumulator sets, the ring and the fragments the
+                     // rows would spill): requested behind the K loops - they finish first and wait anyway.
+        if (!PROD) wt_res_rows_load(rr, q, tb, xh, xl, m0, T);
+        ffn_x_stage<512>(Xs, ch, cl, m0, T);  // the context planes
+        int xb[2][2];
+        ffn_x_bases(xb, c, g);
+        WFrag w[4][1];
+        {
+            const _Float16* const wp0[1] = {Wop + wt_frag_off(q, 0, KS1)};
 #pragma unroll
-                for (int d = 0; d < 4; ++d) w_load<1>(w[d], wp0, d, lo8);
-            }
-            __syncthreads();  // context planes resident
-            ICREC_STAMP(0, 45); ICREC_STAMP(4, 45);
-            // K = 384 of one block; the ring continues into block `nn` (or re-reads this one's last fragments, never consumed)
-            auto ao_block = [&](Acc32 (&S)[2], int nt, int nn) {
-                const _Float16* const wp1[1] = {Wop + wt_frag_off(nt, 0, KS1)};
-                const _Float16* const wpn[1] = {Wop + wt_frag_off(nn, 0, KS1)};
-                acc_zero(S[0]);
-                acc_zero(S[1]);
-                XFrag x[2];
-                ffn_x_frag(x[0], Xs, xb, 0, 0);
+            for (int d = 0; d < 4; ++d) w_load<1>(w[d], wp0, d, lo8);
+        }
+        __syncthreads();  // context planes resident
+        // K = 384 of one block; the ring continues into block `nn` (or re-reads this one's last fragments, never consumed)
+        auto ao_block = [&](Acc32 (&S)[2], int nt, int nn) {
+            const _Float16* const wp1[1] = {Wop + wt_frag_off(nt, 0, KS1)};
+            const _Float16* const wpn[1] = {Wop + wt_frag_off(nn, 0, KS1)};
+            acc_zero(S[0]);
+            acc_zero(S[1]);
+            XFrag x[2];
+            ffn_x_frag(x[0], Xs, xb, 0, 0);
 #pragma unroll
-                for (int ks = 0; ks < KS1; ++ks) {
+            for (int ks = 0; ks < KS1; ++ks) {
 #pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) {
-                        const int u = 2 * ks + tt;
-                        if (u + 1 < 2 * KS1) {
-                            ffn_x_frag(x[(u + 1) & 1], Xs, xb, (u + 1) & 1, (u + 1) >> 1);
-                            __builtin_amdgcn_sched_barrier(0);  // the next unit's LDS reads before this unit's 12 MFMAs
-                        }
-                        wt_mma_block(S[tt], w[ks & 3][0], x[u & 1]);
+                for (int tt = 0; tt < 2; ++tt) {
+                    const int u = 2 * ks + tt;
+                    if (u + 1 < 2 * KS1) {
+                        ffn_x_frag(x[(u + 1) & 1], Xs, xb, (u + 1) & 1, (u + 1) >> 1);
+                        __builtin_amdgcn_sched_barrier(0);  // the next unit's LDS reads before this unit's 12 MFMAs
                     }
-                    if (ks + 4 < KS1) w_load<1>(w[ks & 3], wp1, ks + 4, lo8);
-                    else w_load<1>(w[ks & 3], wpn, ks + 4 - KS1, lo8);
-                    __builtin_amdgcn_sched_barrier(0);  // pin the prefetch to its k-step
+                    wt_mma_block(S[tt], w[ks & 3][0], x[u & 1]);
                 }
-            };
-            auto put = [&](const Acc32 (&S)[2], int nt) {
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                    for (int fi = 0; fi < 2; ++fi)
-#pragma unroll
-                        for (int ti = 0; ti < 2; ++ti)
-                            *reinterpret_cast<f32x4*>(Xs + (((nt * 2 + tt) * 2 + fi) * 2 + ti) * 1024 + lane * 16) = S[tt].t[fi][ti];
-            };
-            Acc32 Y[3][1];
-            auto finish_r = [&]() {  // r is FINISHED here: otherwise the compiler sinks the final fma of every element below
-                                     // the barriers and carries its two inputs instead
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int fi = 0; fi < 2; ++fi)
-#pragma unroll
-                        for (int ti = 0; ti < 2; ++ti) asm volatile("" : "+v"(Y[i][0].t[fi][ti]));
-            };
-            if constexpr (PROD) {
-                Acc32 S0[2], S1[2], S2[2];
-                ao_block(S0, q, q + 4);
-                ao_block(S1, q + 4, q + 8);
-                ao_block(S2, q + 8, q + 8);
-                ICREC_STAMP(0, 28);
-                wt_res_rows_load(rr, q, tb, xh, xl, m0, T);
-                __syncthreads();  // every wave has left the context image: it takes the products
-                put(S0, q);
-                put(S1, q + 4);
-                put(S2, q + 8);
-                wt_res_rows_acc<false, 1, 0>(Y, rr, q, bo, Hs + LNT_RED + wave * LNT_TILE);  // per-wave private tiles
-                finish_r();
-            } else {
-                wt_res_rows_acc<false, 1, 0>(Y, rr, q, bo, Hs + LNT_RED + wave * LNT_TILE);
-                ICREC_STAMP(4, 46);
-                finish_r();
-                ICREC_STAMP(4, 28);
-                __syncthreads();  // every wave has left the context image
+                if (ks + 4 < KS1) w_load<1>(w[ks & 3], wp1, ks + 4, lo8);
+                else w_load<1>(w[ks & 3], wpn, ks + 4 - KS1, lo8);
+                __builtin_amdgcn_sched_barrier(0);  // pin the prefetch to its k-step
             }
-            __syncthreads();  // products visible
-            ICREC_STAMP(0, 29);
-            ICREC_STAMP(4, 29);
+        };
+        auto put = [&](const Acc32 (&S)[2], int nt) {
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                for (int fi = 0; fi < 2; ++fi)
+#pragma unroll
+                    for (int ti = 0; ti < 2; ++ti)
+                        *reinterpret_cast<f32x4*>(Xs + (((nt * 2 + tt) * 2 + fi) * 2 + ti) * 1024 + lane * 16) = S[tt].t[fi][ti];
+        };
+        Acc32 Y[3][1];
+        auto finish_r = [&]() {  // r is FINISHED here: otherwise the compiler sinks the final fma of every element below
+                                 // the barriers and carries its two inputs instead
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
                 for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
-                    for (int ti = 0; ti < 2; ++ti) {
-                        const f32x4 sv = *reinterpret_cast<const f32x4*>(Xs + ((((q * 3 + i) * 2 + tb) * 2 + fi) * 2 + ti) * 1024 + lane * 16);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) Y[i][0].t[fi][ti][j] = sv[j] + Y[i][0].t[fi][ti][j];  // acc + r
-                    }
-            ICREC_STAMP(4, 31);
-            // its first barrier also orders every wave's reads of the products before the first write of x1
-            wt_ln_block<8, 1, 0>(Y, q, tb, wave, nullptr, nullptr, m0, T, gam1, bet1, eps, Hs, [] { __syncthreads(); }, tid, Xs);
+                    for (int ti = 0; ti < 2; ++ti) asm volatile("" : "+v"(Y[i][0].t[fi][ti]));
         };
-        if (producer) prologue(std::true_type{});
-        else prologue(std::false_type{});
-        ICREC_STAMP(0, 31);
-    } else {
-        ffn_x_stage<512>(Xs, xh, xl, m0, T);
-    }
-    if constexpr (AO) {  // the FFN part's per-lane addresses - and with them its first weight-ring loads, 96 registers in
-                         // the consumers - are derived from here on, not hoisted above the prologue (where they spill)
-        asm volatile("" : "+v"(c), "+v"(g), "+v"(lo8));
-    }
+        if constexpr (PROD) {
+            Acc32 S0[2], S1[2], S2[2];
+            ao_block(S0, q, q + 4);
+            ao_block(S1, q + 4, q + 8);
+            ao_block(S2, q + 8, q + 8);
+            wt_res_rows_load(rr, q, tb, xh, xl, m0, T);
+            __syncthreads();  // every wave has left the context image: it takes the products
+            put(S0, q);
+            put(S1, q + 4);
+            put(S2, q + 8);
+            wt_res_rows_acc<false, 1, 0>(Y, rr, q, bo, Hs + LNT_RED + wave * LNT_TILE);  // per-wave private tiles
+            finish_r();
+        } else {
+            wt_res_rows_acc<false, 1, 0>(Y, rr, q, bo, Hs + LNT_RED + wave * LNT_TILE);
+            finish_r();
+            __syncthreads();  // every wave has left the context image
+        }
+        __syncthreads();  // products visible
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int fi = 0; fi < 2; ++fi)
+#pragma unroll
+                for (int ti = 0; ti < 2; ++ti) {
+                    const f32x4 sv = *reinterpret_cast<const f32x4*>(Xs + ((((q * 3 + i) * 2 + tb) * 2 + fi) * 2 + ti) * 1024 + lane * 16);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) Y[i][0].t[fi][ti][j] = sv[j] + Y[i][0].t[fi][ti][j];  // acc + r
+                }
+        // its first barrier also orders every wave's reads of the products before the first write of x1
+        wt_ln_block<8, 1, 0>(Y, q, tb, wave, nullptr, nullptr, m0, T, gam1, bet1, eps, Hs, [] { __syncthreads(); }, tid, Xs);
+    };
+    if (producer) prologue(std::true_type{});
+    else prologue(std::false_type{});
+    // the FFN part's per-lane addresses - and with them its first weight-ring loads, 96 registers in the consumers - are
+    // derived from here on, not hoisted above the prologue (where they spill)
+    asm volatile("" : "+v"(c), "+v"(g), "+v"(lo8));
     if (producer) {
         int xb[2][2];
         ffn_x_bases(xb, c, g);
@@ -1106,7 +1072,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
             for (int d = 0; d < 4; ++d) w_load<1>(w[d], wp0, d, lo8);
         }
         __syncthreads();  // X resident
-        ICREC_STAMP(0, 1);
         // Software pipeline: iteration ch runs P1(ch) with the GELU of chunk ch-1 spread over its k-steps (one 16x16
         // tile = 4 consecutive intermediates of one token per lane on 8 of the 12 k-steps), so the producer's VALU
         // work sits between its own MFMAs and the consumers' instead of behind them.  H[ch-1] is handed over at the
@@ -1140,10 +1105,10 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
                 for (int tt = 0; tt < 2; ++tt) {
                     const int u = 2 * ks + tt;
                     if (MMA) {
-                        if (u + 1 < 2 * KS1 && !(VAR & 8)) ffn_x_frag(x[(u + 1) & 1], Xs, xb, (u + 1) & 1, (u + 1) >> 1);
-                        if (tt == 0) wt_mma<1, 2, 0>(S, w[ks & 3], x[(VAR & 8) ? 0 : (u & 1)]);
-                        else wt_mma<1, 2, 1>(S, w[ks & 3], x[(VAR & 8) ? 0 : (u & 1)]);
-                        if (tt == 1 && !(VAR & 4)) {  // straight-line refill: this chunk's k-step ks+4, or the next chunk's ks+4-12
+                        if (u + 1 < 2 * KS1) ffn_x_frag(x[(u + 1) & 1], Xs, xb, (u + 1) & 1, (u + 1) >> 1);
+                        if (tt == 0) wt_mma<1, 2, 0>(S, w[ks & 3], x[u & 1]);
+                        else wt_mma<1, 2, 1>(S, w[ks & 3], x[u & 1]);
+                        if (tt == 1) {  // straight-line refill: this chunk's k-step ks+4, or the next chunk's ks+4-12
                             if (ks + 4 < KS1) w_load<1>(w[ks & 3], wp1, ks + 4, lo8);
                             else w_load<1>(w[ks & 3], wpn, ks + 4 - KS1, lo8);
                         }
@@ -1156,7 +1121,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
                         const float p0 = fmaf(Sp[0][gtt].t[gfi][gti][j], WT_UNSCALE, biasp[gfi][j]);
                         const float p1 = fmaf(Sp[0][gtt].t[gfi][gti][j + 1], WT_UNSCALE, biasp[gfi][j + 1]);
                         half2w a, d;
-                        split_pair_prescaled((VAR & 1) ? p0 : gelu16_wt(p0), (VAR & 1) ? p1 : gelu16_wt(p1), a, d);
+                        split_pair_prescaled(gelu16_wt(p0), gelu16_wt(p1), a, d);
                         ghi[j] = a[0];
                         ghi[j + 1] = a[1];
                         glo[j] = d[0];
@@ -1168,7 +1133,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
                             *reinterpret_cast<half4*>(Hb + FFN2_HPLANE + pos) = glo;
                         }
                     }
-                    if (MMA && !(VAR & 32)) {  // the next unit's LDS reads first; then one MFMA and a few of the slice's VALU
+                    if (MMA) {  // the next unit's LDS reads first; then one MFMA and a few of the slice's VALU
                                                // instructions, twelve times (the scheduler otherwise sinks the reads to their uses)
                         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
@@ -1187,14 +1152,10 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
         };
         for (int ch = 0; ch < NC; ++ch) {
             iteration(ch, std::true_type{});
-            ICREC_STAMP(0, 2 + 2 * ch);
             if (ch > 0) bar_lds();  // B(ch): H[ch - 1] is complete; the consumers have left H[ch & 1]
-            ICREC_STAMP(0, 3 + 2 * ch);
         }
         iteration(NC, std::false_type{});
         bar_lds();  // B(NC): H[NC - 1]
-        ICREC_STAMP(0, 26);
-        ICREC_STAMP(0, 27);
         // ---- the LayerNorm of token block 1: its accumulators come over from the consumers through the (dead) image
         __syncthreads();  // every reader of the LDS is done: image and H buffers are free
         __syncthreads();  // token block 1 parked
@@ -1223,14 +1184,12 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
 #pragma unroll
         for (int d = 0; d < 2; ++d) w_load<3>(w[d], w2p, d, lo8);
         __syncthreads();  // X resident (matches the producers' first barrier)
-        ICREC_STAMP(4, 1);
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) acc_zero(Y[i][tt]);
         bar_lds();        // B1: H[0] is ready
         for (int ch = 0; ch < NC; ++ch) {
-            ICREC_STAMP(4, 2 + 2 * ch);
             const char* const Hb = Hs + (ch & 1) * FFN2_HBUF;
             XFrag x[2];  // unit u = 2 k2 + tt
             auto h_frag = [&](XFrag& xf, int tt, int k2) {
@@ -1247,24 +1206,20 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt) {
                     const int u = 2 * k2 + tt;
-                    if (u + 1 < 8 && !(VAR & 8)) {
+                    if (u + 1 < 8) {
                         h_frag(x[(u + 1) & 1], (u + 1) & 1, (u + 1) >> 1);
                         __builtin_amdgcn_sched_barrier(0);  // issue the next unit's LDS reads before this unit's 36 MFMAs
                     }
-                    if (tt == 0) wt_mma<3, 2, 0>(Y, w[k2 & 1], x[(VAR & 8) ? 0 : (u & 1)]);
-                    else wt_mma<3, 2, 1>(Y, w[k2 & 1], x[(VAR & 8) ? 0 : (u & 1)]);
+                    if (tt == 0) wt_mma<3, 2, 0>(Y, w[k2 & 1], x[u & 1]);
+                    else wt_mma<3, 2, 1>(Y, w[k2 & 1], x[u & 1]);
                 }
-                if (!(VAR & 4)) {
-                    int nk = ch * 4 + k2 + 2;
-                    nk = nk < KS2 ? nk : KS2 - 1;  // past the end: re-read the last fragment (never consumed)
-                    w_load<3>(w[k2 & 1], w2p, nk, lo8);
-                }
+                int nk = ch * 4 + k2 + 2;
+                nk = nk < KS2 ? nk : KS2 - 1;  // past the end: re-read the last fragment (never consumed)
+                w_load<3>(w[k2 & 1], w2p, nk, lo8);
                 __builtin_amdgcn_sched_barrier(0);  // pin the prefetch to its k-step
             }
-            ICREC_STAMP(4, 3 + 2 * ch);
             if (ch + 1 < NC) bar_lds();  // B(ch+2): done with H[ch & 1]; H[(ch + 1) & 1] is ready
         }
-        ICREC_STAMP(4, 27);
         // ---- + residual + bias: the block's own planes, still resident (the same r as wt_res_global / wt_res_add_direct)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -1297,8 +1252,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
         __syncthreads();  // token block 1 parked
         wt_ln_block<8, 2, 0>(Y, q, 0, wave, xh, xl, m0, T, gam, bet, eps, Hs, [] { __syncthreads(); }, tid, Wqp != nullptr ? Xs : nullptr);
     }
-    ICREC_STAMP(0, 30);
-    ICREC_STAMP(4, 30);
     // ---- the NEXT layer's QKV projection of this block (tf:175-177), on the planes just normalised, still on chip: no
     // separate launch, no re-read of x, and the 4.6 KB of fp32 Q / K / V rows per token leave spread over the whole
     // kernel's time instead of in one burst.  Staging tiles: the H buffers (the LayerNorm scratch is done with).
@@ -1307,9 +1260,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
         asm volatile("" : "+v"(c), "+v"(g), "+v"(lo8));  // (addresses and first ring loads derived here, not hoisted)
         qkv_block_walk(Xs, reinterpret_cast<float*>(Hs + wave * QKVR_STG_BYTES), Wqp, bq, qkv_out, Nq, m0, T, wave, lane, c, g, lo8);
     }
-    ICREC_STAMP(0, 43);
-    ICREC_STAMP(4, 43);
-    ICREC_STAMP_RT(0, 63);
 }
 
 __global__ __launch_bounds__(512, 2) void qkv_resident_kernel(const _Float16* __restrict__ xh,

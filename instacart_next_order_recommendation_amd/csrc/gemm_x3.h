@@ -156,48 +156,6 @@ __device__ __forceinline__ void tile_gemm_h(f32x16 (&acc0)[Cfg::TM][Cfg::TN], f3
     }
 }
 
-// Latency-bound form for small M (a single request: a handful of workgroups, each k-step waiting a full
-// memory round trip): D slabs are kept in flight in registers instead of one, so a K = 384 tile costs
-// ~2 round trips instead of 6.  Same LDS stage, same MFMA order => bit-identical results to tile_gemm_h.
-template <class Cfg, int D>
-__device__ __forceinline__ void tile_gemm_h_deep(f32x16 (&acc0)[Cfg::TM][Cfg::TN], f32x16 (&acc1)[Cfg::TM][Cfg::TN],
-                                                 const _Float16* __restrict__ Ah, const _Float16* __restrict__ Al,
-                                                 int64_t a_row0, int64_t a_rows, const _Float16* __restrict__ Bh,
-                                                 const _Float16* __restrict__ Bl, int64_t b_row0, int64_t b_rows,
-                                                 int K, _Float16* smem) {
-    _Float16* Ahs = smem;
-    _Float16* Als = Ahs + SmemH<Cfg>::A_HALFS;
-    _Float16* Bhs = Als + SmemH<Cfg>::A_HALFS;
-    _Float16* Bls = Bhs + SmemH<Cfg>::B_HALFS;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave / Cfg::WAVES_N, wn = wave % Cfg::WAVES_N;
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < Cfg::TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { acc0[i][j][e] = 0.0f; acc1[i][j][e] = 0.0f; }
-    const int nslab = K / HBK;
-    TileRegsH<Cfg> pre[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d)  // slabs past the end re-read the last one (never consumed)
-        tile_load_h<Cfg>(pre[d], Ah, Al, a_row0, a_rows, Bh, Bl, b_row0, b_rows, K, d < nslab ? d : nslab - 1);
-    for (int s0 = 0; s0 < nslab; s0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const int s = s0 + d;
-            if (s < nslab) {  // block-uniform
-                __syncthreads();
-                tile_store_lds_h<Cfg>(pre[d], Ahs, Als, Bhs, Bls);
-                __syncthreads();
-                const int nxt = s + D;
-                tile_load_h<Cfg>(pre[d], Ah, Al, a_row0, a_rows, Bh, Bl, b_row0, b_rows, K, nxt < nslab ? nxt : nslab - 1);
-                tile_mma_h<Cfg>(acc0, acc1, Ahs, Als, Bhs, Bls, wm, wn, lane);
-            }
-        }
-    }
-}
-
 #endif  // __HIPCC__
 
 }  // namespace icrec

@@ -210,9 +210,6 @@ __device__ __forceinline__ void r32_mma(f32x16 (&acc)[1][2], const half8& wh, co
 //    across rounds (the next round's first fragments land under the selection): no operand staging barriers at all -
 //    PMODE 2 re-stages both operands through LDS for every 128-row tile (two barriers per 64-deep slab).
 // run_flag != NULL: the whole grid exits unless *run_flag != 0 (the exact pass behind a filter pass).
-#ifndef ICREC_STAMP_ROUND0
-#define ICREC_STAMP_ROUND0 0  // tools/search_stamps.hip: first round of a block whose phases are stamped
-#endif
 template <class Cfg, bool EMIT, int PMODE>
 __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
     const void* __restrict__ P, const void* __restrict__ P2, int64_t N, int K, const void* __restrict__ Qn,
@@ -238,7 +235,6 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
     const int chunk = bid / n_qtiles, qtile = bid % n_qtiles;
     const int q0 = qtile * Cfg::BN;
 
-    ICREC_STAMP(0, 60);
     for (int i = tid; i < Cfg::BN; i += Cfg::THREADS) { thr[i] = (q0 + i < Q) ? 0ull : ~0ull; cnt[i] = 0; }
     for (int i = tid; i < Cfg::BN * k; i += Cfg::THREADS) list[i] = 0ull;
     if (tid < 4) flags[tid] = 0;
@@ -302,10 +298,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
         __syncthreads();  // queries resident
     }
 
-    ICREC_STAMP(0, 61);
     for (int tile = t_begin; tile < t_end; ++tile) {
         const int64_t row0 = (int64_t)tile * Cfg::BM;
-        if (tile - t_begin - ICREC_STAMP_ROUND0 >= 0 && tile - t_begin - ICREC_STAMP_ROUND0 < 24) ICREC_STAMP(0, 2 * (tile - t_begin - ICREC_STAMP_ROUND0));
         if constexpr (PMODE == 3) {
             // the wave's TM 32-row tiles of this round, one after the other (fragment tiles (tile * 8 + wave) * TM + i); the
             // selection below then runs once per round over all of them: its barriers and polls are per round, not per tile
@@ -376,7 +370,6 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
                     }
         }
 
-        if (tile - t_begin - ICREC_STAMP_ROUND0 >= 0 && tile - t_begin - ICREC_STAMP_ROUND0 < 24) ICREC_STAMP(0, 2 * (tile - t_begin - ICREC_STAMP_ROUND0) + 1);
         // ---- selection
         // A score is OFFERED (pushed to its query's LDS queue) when it beats the query's threshold.
         //  * warm query (list full): threshold = current k-th best key.  Queues are merged into the
@@ -428,9 +421,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
             offered |= pend;
             if (pass == 0 && lane_cold) flags[2] = 1;
             bool more, wg_cold;
-            [[maybe_unused]] int it_stamp = 0;
             do {
-                if (tile - t_begin - ICREC_STAMP_ROUND0 == 11 && it_stamp < 6) ICREC_STAMP(0, 30 + 3 * it_stamp);
                 bool lane_pending = false;
 #pragma unroll
                 for (int j = 0; j < Cfg::TN; ++j)
@@ -463,10 +454,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
                         }
                     }
                 if (lane_pending) flags[round & 1] = 1;
-                if (tile - t_begin - ICREC_STAMP_ROUND0 == 11 && it_stamp < 6) ICREC_STAMP(0, 31 + 3 * it_stamp);
                 __syncthreads();
-                if (tile - t_begin - ICREC_STAMP_ROUND0 == 11 && it_stamp < 6) ICREC_STAMP(0, 32 + 3 * it_stamp);
-                ++it_stamp;
                 more = flags[round & 1] != 0;
                 wg_cold = flags[2] != 0;
                 if (tid == 0) flags[(round + 1) & 1] = 0;
@@ -512,13 +500,11 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
         if (tid == 0) flags[2] = 0;
     }
 
-    ICREC_STAMP(0, 62);
     // sorted partial lists out
     for (int i = tid; i < Cfg::BN * k; i += Cfg::THREADS) {
         const int q = i / k, e = i % k;
         partial[((size_t)chunk * Qpad + q0 + q) * k + e] = list[(size_t)q * k + e];
     }
-    ICREC_STAMP(0, 63);
 }
 
 // ---------------------------------------------------------------- small-batch streaming search

@@ -17,7 +17,7 @@
 // accumulator bytes per FLOP - but under this engine's load the chip is power-limited, and it holds a higher clock
 // on the 16x16x32 form: on random operands a registers-only loop delivers 1,970 vs 1,710 TFLOP/s (1.95 vs 1.69 GHz,
 // tools/mfma_shape.hip, profiles/r03_mfma_shape_microbench.txt), and the fused FFN kernel issued in this shape ran
-// 1.33x faster before its data layout existed (tools/ffn_bench.hip VAR 64, profiles/r03_ffn_harness_shape_and_stream.txt).
+// 1.33x faster before its data layout existed (a since-removed timing harness, profiles/r03_ffn_harness_shape_and_stream.txt).
 //   lane l = (g << 4 | c), c = l & 15, g = l >> 4
 //   A (16 rows x 32 k):  lane holds A[row c][k = 8g .. 8g+7]        B (32 k x 16 cols): lane holds B[k = 8g .. 8g+7][col c]
 //   D (16 x 16):         lane holds D[row 4g + reg][col c], reg = 0..3      (checked with integer data: tools/mfma16_probe.hip)
@@ -197,25 +197,6 @@ __device__ __forceinline__ void w_load(WFrag (&w)[NTW], const _Float16* const (&
 
 __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// In-kernel phase stamps for tools/ffn_bench.hip (diagnostic builds only: -DICREC_STAMPS; the product never defines it).
-#ifdef ICREC_STAMPS
-__device__ unsigned long long g_stamps[1 << 22];
-#define ICREC_STAMP(slot_wave, k)                                                                        \
-    do {                                                                                                 \
-        if ((threadIdx.x & 63) == 0 && (int)(threadIdx.x >> 6) == (slot_wave))                           \
-            g_stamps[((size_t)blockIdx.x * 2 + ((slot_wave) ? 1 : 0)) * 64 + (k)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-// the 100 MHz constant-rate counter beside a shader-clock stamp: in-kernel clock = d(s_memtime) / d(s_memrealtime) x 100 MHz
-#define ICREC_STAMP_RT(slot_wave, k)                                                                     \
-    do {                                                                                                 \
-        if ((threadIdx.x & 63) == 0 && (int)(threadIdx.x >> 6) == (slot_wave))                           \
-            g_stamps[((size_t)blockIdx.x * 2 + ((slot_wave) ? 1 : 0)) * 64 + (k)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#else
-#define ICREC_STAMP(slot_wave, k) do { } while (0)
-#define ICREC_STAMP_RT(slot_wave, k) do { } while (0)
-#endif
-
 // ---------------------------------------------------------------- whole-K loop of one output tile
 // acc[i][tt] = sum_k W[(nt0 + i) block][k] . X[m0 + tt block][k], K in slabs of 64 (2 k-steps of 32); weight fragments
 // D k-steps ahead in registers (D = 1, 2 or 4: the latency form of single requests keeps four - its few workgroups
@@ -229,7 +210,6 @@ __device__ __forceinline__ void wt_kloop(Acc32 (&acc)[NTW][TTW], const _Float16*
                                          int64_t T, char* smem) {
     static_assert(D == 1 || D == 2 || D == 4, "prefetch depth: 1, 2 or 4 k-steps");
     static_assert(TTW == 1 || TTW == 2, "1 or 2 token blocks per wave");
-    ICREC_STAMP(0, 0);
     const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
     const unsigned lo8 = lane * 8;
     const int KS = K / 32, nslab = K / 64;
@@ -251,7 +231,6 @@ __device__ __forceinline__ void wt_kloop(Acc32 (&acc)[NTW][TTW], const _Float16*
     x_store<TTW>(xa, smem);
     if (nslab > 2) x_load<TTW>(xa, Xh, Xl, m0, T, K, 2);
     __syncthreads();
-    ICREC_STAMP(0, 1);
     auto slab = [&](int s, auto parity, u32x4 (&xnext)[2 * TTW]) {  // xnext holds slab s+1 on entry, slab s+3 on exit
         constexpr int PAR = decltype(parity)::value;  // s & 1: the ring slot of k-step 2 s + j is (2 PAR + j) % D
         const char* st = smem + (s & 1) * XRing<TTW>::STAGE_BYTES;
@@ -281,7 +260,6 @@ __device__ __forceinline__ void wt_kloop(Acc32 (&acc)[NTW][TTW], const _Float16*
             if (s + 3 < nslab) x_load<TTW>(xnext, Xh, Xl, m0, T, K, s + 3);
         }
         __syncthreads();
-        if (s < 24) ICREC_STAMP(0, 2 + s);
     };
     for (int s = 0; s < nslab; s += 2) {  // nslab is even (K is a multiple of 128 for every layer of the encoder)
         slab(s, std::integral_constant<int, 0>{}, xb);
