@@ -98,6 +98,16 @@ ICREC_API int icrec_encoder_create(const float* weights_host, size_t n_floats,
                          icrec_encoder** out);
 ICREC_API int icrec_encoder_destroy(icrec_encoder* enc);
 
+/* Longest sequence any encoder can take: every BERT shape has at most 512 position embeddings. */
+#define ICREC_MAX_SEQLEN 512
+
+/* Raise (or lower) the longest sequence `enc` accepts, in [1, min(ICREC_MAX_SEQLEN, cfg.max_position)]; anything
+ * else returns ICREC_EINVAL.  After icrec_encoder_create the ceiling is min(256, cfg.max_position) (sentence-transformers'
+ * default max_seq_length), so a caller that never sets it sees the 256-token limit.  Set it before the first
+ * icrec_encode, never while another call on `enc` is running.  Sequences of up to 256 tokens encode to the same bits
+ * whatever the ceiling. */
+ICREC_API int icrec_encoder_set_max_seqlen(icrec_encoder* enc, int32_t max_seqlen);
+
 /* Scratch bytes needed to encode `total_tokens` tokens in `n_seqs` sequences. */
 ICREC_API size_t icrec_encode_workspace_bytes(const icrec_encoder* enc,
                                     int64_t total_tokens, int32_t n_seqs);
@@ -107,7 +117,8 @@ ICREC_API size_t icrec_encode_workspace_bytes(const icrec_encoder* enc,
  *                                       (already truncated to max_seq_length,
  *                                       [CLS]/[SEP] included; no pad tokens)
  *   cu_seqlens_dev int32[n_seqs+1]      prefix sums of sequence lengths
- *   max_seqlen     longest sequence in the batch (<= 256 in this build)
+ *   max_seqlen     longest sequence in the batch (<= the encoder's ceiling:
+ *                  256 unless icrec_encoder_set_max_seqlen raised it)
  *   out_dev        float[n_seqs, hidden] L2-normalised sentence embeddings
  * Padding never enters the math: the reference pads per batch and masks the
  * pad keys to weight exactly 0, so the packed form is the same function.

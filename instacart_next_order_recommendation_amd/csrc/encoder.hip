@@ -160,7 +160,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void linear_kernel(const float* __
 constexpr int DH = 32;
 constexpr int LDQ = 36;  // K LDS row stride (even/odd split layout, like the GEMM tiles)
 
-// One launch per length bucket: NKT = max 32-key tiles (1, 2, 4, 8), WAVES = query blocks per
+// One launch per length bucket: NKT = max 32-key tiles (1, 2, 4, 8, 16), WAVES = query blocks per
 // workgroup.  A workgroup whose sequence belongs to another bucket exits at once, so short
 // sequences run with the LDS footprint / occupancy of their own bucket even in a mixed batch.
 // K and V of the (sequence, head) live in LDS; each wave's 32 query rows come straight from
@@ -212,6 +212,63 @@ __global__ __launch_bounds__(WAVES * 64) void attention_kernel(const float* __re
     __syncthreads();
     if (qb >= nkt) return;  // idle wave (no barrier below)
 
+    f32x16 o;
+    if constexpr (NKT > 8) {
+    // ---- the 9-16-tile bucket (257-512 tokens): sixteen score tiles do not fit in registers, so each tile is computed
+    // twice - once for the row maximum, once more for its exponentials, which the P.V product consumes at once.  Same
+    // MFMA chain both times, and the denominator and P.V accumulate in the same order as below: the same bits as the
+    // all-in-registers form would give.
+    auto score_tile = [&](int kt) {
+        f32x16 t;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) t[e] = 0.0f;
+#pragma unroll
+        for (int kq = 0; kq < 4; ++kq) {
+            const float4 kf = *reinterpret_cast<const float4*>(Ks + (kt * 32 + r) * LDQ + kq * 8 + h * 4);
+            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[kq].x, t, 0, 0, 0);
+            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[kq].y, t, 0, 0, 0);
+            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[kq].z, t, 0, 0, 0);
+            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[kq].w, t, 0, 0, 0);
+        }
+        const bool last = kt == nkt - 1;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            float v = t[e] * scale_log2e;
+            if (last && kt * 32 + acc_row(e, lane) >= L) v = -INFINITY;
+            t[e] = v;
+        }
+        return t;
+    };
+    float mx = -INFINITY;
+    for (int kt = 0; kt < nkt; ++kt) {
+        const f32x16 t = score_tile(kt);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float lsum = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[e] = 0.0f;
+    for (int kt = 0; kt < nkt; ++kt) {
+        f32x16 t = score_tile(kt);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float p = __builtin_amdgcn_exp2f(t[e] - mx);
+            t[e] = p;
+            lsum = lsum + p;
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            o = __builtin_amdgcn_mfma_f32_32x32x2f32(t[e], Vs[key * DH + r], o, 0, 0, 0);
+        }
+    }
+    {
+        const float other = __shfl_xor(lsum, 32, 64);
+        lsum = h == 0 ? lsum + other : other + lsum;
+    }
+    if (h == 0) Ls[wave * 32 + r] = lsum;
+    } else {
     // ---- S^T tiles: sc[kt][e] = sum_d K[kt*32 + krow(e)][d] * Q[qb*32 + r][d]
     f32x16 sc[NKT];
 #pragma unroll
@@ -264,7 +321,6 @@ __global__ __launch_bounds__(WAVES * 64) void attention_kernel(const float* __re
     }
     if (h == 0) Ls[wave * 32 + r] = lsum;
     // ---- O = P.V with P taken straight from the accumulator registers
-    f32x16 o;
 #pragma unroll
     for (int e = 0; e < 16; ++e) o[e] = 0.0f;
 #pragma unroll
@@ -276,6 +332,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention_kernel(const float* __re
                 o = __builtin_amdgcn_mfma_f32_32x32x2f32(sc[kt][e], Vs[key * DH + r], o, 0, 0, 0);
             }
         }
+    }
     }
     // ---- normalise rows by their denominator and store (row = query, column = head dim);
     // Ls was written by this wave's own lanes (wave-local LDS ordering makes it visible).
@@ -291,34 +348,33 @@ __global__ __launch_bounds__(WAVES * 64) void attention_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------- dispatch order of the attention workgroups
-// order[0 .. n_seqs) = the sequences sorted by length, longest first (counting sort over the 256 possible lengths;
-// the order inside one length is whatever the atomics give - the workgroups are independent, results do not depend
-// on it).  The attention launches map workgroup b to sequence order[b / heads]: each bucket's workgroups are then
-// dispatched longest-first with the other buckets' (empty) workgroups behind them instead of in between, so a launch
-// does not end on a few 8-tile sequences that started last.
+// order[0 .. n_seqs) = the sequences sorted by key-tile count, longest first (counting sort over the
+// ICREC_MAX_SEQLEN / 32 possible counts; the order inside one count is whatever the atomics give - the workgroups are
+// independent, results do not depend on it).  The attention launches map workgroup b to sequence order[b / heads]: each
+// bucket's workgroups are then dispatched longest-first with the other buckets' (empty) workgroups behind them instead
+// of in between, so a launch does not end on a few long sequences that started last.
 __global__ __launch_bounds__(1024) void seq_order_kernel(const int32_t* __restrict__ cu, int n_seqs,
                                                          int32_t* __restrict__ order) {
-    __shared__ int hist[257];
+    constexpr int NB = ICREC_MAX_SEQLEN / 32;  // bin NB - nkt holds the sequences of nkt key tiles
+    __shared__ int hist[NB];
     const int tid = threadIdx.x;
-    for (int i = tid; i < 257; i += 1024) hist[i] = 0;
+    if (tid < NB) hist[tid] = 0;
     __syncthreads();
-    for (int s0 = tid; s0 < n_seqs; s0 += 1024) {
-        const int s = n_seqs - 1 - s0;
-        int L = cu[s + 1] - cu[s];
-        L = L < 1 ? 1 : (L > 256 ? 256 : L);
-        atomicAdd(&hist[256 - ((L + 31) & ~31)], 1);
-    }
+    auto bin = [&](int s) {
+        const int L = cu[s + 1] - cu[s];
+        const int nkt = (L + 31) >> 5;
+        return NB - (nkt < 1 ? 1 : (nkt > NB ? NB : nkt));
+    };
+    for (int s0 = tid; s0 < n_seqs; s0 += 1024) atomicAdd(&hist[bin(n_seqs - 1 - s0)], 1);
     __syncthreads();
     if (tid == 0) {  // exclusive prefix sum: hist[b] becomes the first slot of bin b
         int run = 0;
-        for (int b = 0; b < 257; ++b) { const int c = hist[b]; hist[b] = run; run += c; }
+        for (int b = 0; b < NB; ++b) { const int c = hist[b]; hist[b] = run; run += c; }
     }
     __syncthreads();
     for (int s0 = tid; s0 < n_seqs; s0 += 1024) {
         const int s = n_seqs - 1 - s0;
-        int L = cu[s + 1] - cu[s];
-        L = L < 1 ? 1 : (L > 256 ? 256 : L);
-        order[atomicAdd(&hist[256 - ((L + 31) & ~31)], 1)] = s;
+        order[atomicAdd(&hist[bin(s)], 1)] = s;
     }
 }
 
@@ -665,6 +721,7 @@ struct Encoder {
     icrec_bert_cfg cfg;
     int device = 0;
     int n_cu = 256;
+    int max_seqlen = 256;       // longest sequence icrec_encode accepts (icrec_encoder_set_max_seqlen)
     float* blob = nullptr;      // the uploaded weight blob
     float* extra = nullptr;     // repacked Wqkv / bqkv
     _Float16* planes = nullptr; // packed weight fragments (F16X3)
@@ -801,10 +858,11 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
 // X3: the f16x3 kernel, context out as planes (attention_x3_kernel); otherwise exact fp32 rows (attention_kernel).
 template <bool X3>
 static void launch_attention(const float* qkv, const int32_t* cu, int n_seqs, int heads, int H, int max_seqlen,
-                             float* ctx, _Float16* ch, _Float16* cl, hipStream_t st, int buckets = 31,
+                             float* ctx, _Float16* ch, _Float16* cl, hipStream_t st, int buckets = 63,
                              const int32_t* order = nullptr) {
-    // buckets: bits 0..2 = the 1-, 2-, 3-4-tile buckets, bit 3 = 5-6 tiles (5-8 outside f16x3 batches), bit 4 = 7-8 tiles
-    // (callers split the buckets over two streams)
+    // buckets: bits 0..2 = the 1-, 2-, 3-4-tile buckets, bit 3 = 5-6 tiles (5-8 outside f16x3 batches), bit 4 = 7-8 tiles,
+    // bit 5 = 9-16 tiles (257-512 tokens: encoders whose ceiling was raised past 256; launched first, the longest bucket
+    // starts first) (callers split the buckets over two streams)
     const float sl2e = (1.0f / sqrtf((float)DH)) * 1.44269504088896340736f;
     const int nkt_max = (max_seqlen + 31) / 32;
     const bool single = n_seqs == 1;
@@ -814,17 +872,18 @@ static void launch_attention(const float* qkv, const int32_t* cu, int n_seqs, in
         if constexpr (X3) hipLaunchKernelGGL((attention_x3_kernel<NKT, W>), grid1, dim3(W * 64), 0, st, qkv, cu, heads, H, sl2e, ctx, ch, cl, order, NLO); \
         else hipLaunchKernelGGL((attention_kernel<NKT, W>), grid1, dim3(W * 64), 0, st, qkv, cu, heads, H, sl2e, ctx, ch, cl);      \
     } while (0)
+    if ((buckets & 32) && nkt_max >= 9) ICREC_ATT(16, 16, 8);
     if ((buckets & 1) && (single ? nkt_max == 1 : true)) ICREC_ATT(1, 1, 0);
     if ((buckets & 2) && (single ? nkt_max == 2 : nkt_max >= 2)) ICREC_ATT(2, 2, 1);
     if ((buckets & 4) && (single ? (nkt_max == 3 || nkt_max == 4) : nkt_max >= 3)) ICREC_ATT(4, 4, 2);
     if constexpr (X3) {
-        if (!single) {  // f16x3 batches: the long sequences in two buckets (5-6 and 7-8 key tiles)
+        if (!single) {  // f16x3 batches: the sequences of 5-8 key tiles in two buckets (5-6 and 7-8 key tiles)
             if ((buckets & 8) && nkt_max >= 5) ICREC_ATT(6, 6, 4);
             if ((buckets & 16) && nkt_max >= 7) ICREC_ATT(8, 8, 6);
             return;
         }
     }
-    if ((buckets & 8) && nkt_max >= 5) ICREC_ATT(8, 8, 4);
+    if ((buckets & 8) && (single ? (nkt_max >= 5 && nkt_max <= 8) : nkt_max >= 5)) ICREC_ATT(8, 8, 4);
 #undef ICREC_ATT
 }
 
@@ -860,6 +919,7 @@ int icrec_encoder_create(const float* weights_host, size_t n_floats, const icrec
     e->cfg = *cfg;
     e->device = device;
     e->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    e->max_seqlen = cfg->max_position < 256 ? cfg->max_position : 256;
     {
         const char* fuse_env = getenv("ICREC_FUSE");
         const char* side_env = getenv("ICREC_SIDE_STREAM");
@@ -940,6 +1000,15 @@ int icrec_encoder_destroy(icrec_encoder* h) {
     return ICREC_OK;
 }
 
+int icrec_encoder_set_max_seqlen(icrec_encoder* h, int32_t max_seqlen) {
+    Encoder* e = reinterpret_cast<Encoder*>(h);
+    ICREC_REQUIRE(e, "icrec_encoder_set_max_seqlen: NULL encoder");
+    const int hi = e->cfg.max_position < ICREC_MAX_SEQLEN ? e->cfg.max_position : ICREC_MAX_SEQLEN;
+    ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= hi, "icrec_encoder_set_max_seqlen: max_seqlen must be in [1, %d] (got %d)", hi, max_seqlen);
+    e->max_seqlen = max_seqlen;
+    return ICREC_OK;
+}
+
 size_t icrec_encode_workspace_bytes(const icrec_encoder* h, int64_t total_tokens, int32_t n_seqs) {
     const Encoder* e = reinterpret_cast<const Encoder*>(h);
     if (!e || total_tokens < 1 || n_seqs < 1) return 0;
@@ -974,7 +1043,7 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
     Encoder* e = reinterpret_cast<Encoder*>(h);
     ICREC_REQUIRE(e && ids_dev && cu_dev && out_dev, "icrec_encode: NULL argument");
     ICREC_REQUIRE(n_seqs >= 1 && T64 >= n_seqs && T64 < (1ll << 31), "icrec_encode: bad n_seqs/total_tokens (%d, %lld)", n_seqs, (long long)T64);
-    ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= 256 && max_seqlen <= e->cfg.max_position, "icrec_encode: max_seqlen must be in [1, 256] (got %d)", max_seqlen);
+    ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= e->max_seqlen, "icrec_encode: max_seqlen must be in [1, %d] (got %d)", e->max_seqlen, max_seqlen);
     const int T = (int)T64;
     const EncWs w = enc_ws(e->cfg, T);
     if (!ws || ws_bytes < w.total) {
@@ -1126,12 +1195,14 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
                 // buckets' workgroups run beside it from the side stream instead of after it
                 ICREC_HIP(hipEventRecord(sd->ev_q, st));
                 ICREC_HIP(hipStreamWaitEvent(sd->side, sd->ev_q, 0));
+                // (sequences of 9-16 key tiles: that bucket goes first, on the caller's stream, ahead of the side stream's)
+                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 32, order);
                 launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, sd->side, 7 | 16, order);
                 ICREC_HIP(hipEventRecord(sd->ev_sa, sd->side));
                 launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 8, order);
                 ICREC_HIP(hipStreamWaitEvent(st, sd->ev_sa, 0));
             } else {
-                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 31, order);
+                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 63, order);
             }
             if (T_tail) {
                 if (use_side) {

@@ -19,16 +19,17 @@ from . import _native
 from .synthetic import BertShape
 
 DEFAULT_GEMM_MODE = "f16x3"
-MAX_SEQ_LEN = 256  # configs/train.yaml:11 (max_seq_length), also the attention kernel's limit
+MAX_SEQ_LEN = 256  # configs/train.yaml:11 (max_seq_length): an encoder's default ceiling
+MAX_SEQ_LEN_LIMIT = _native.ICREC_MAX_SEQLEN  # the highest ceiling (icrec_encoder_set_max_seqlen)
 
 
-def pack_token_ids(seqs: Sequence[Sequence[int]]):
-    """List of id lists -> (ids int32[T], cu_seqlens int32[n+1], max_len)."""
+def pack_token_ids(seqs: Sequence[Sequence[int]], max_len: int = MAX_SEQ_LEN):
+    """List of id lists -> (ids int32[T], cu_seqlens int32[n+1], max_len); sequences longer than `max_len` are refused."""
     lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
     if len(seqs) == 0 or (lens < 1).any():
         raise ValueError("every sequence needs at least one token")
-    if lens.max() > MAX_SEQ_LEN:
-        raise ValueError(f"sequence longer than max_seq_length={MAX_SEQ_LEN}; truncate on the host")
+    if lens.max() > max_len:
+        raise ValueError(f"sequence longer than max_seq_length={max_len}; truncate on the host")
     cu = np.zeros(len(seqs) + 1, np.int32)
     np.cumsum(lens, out=cu[1:])
     ids = np.concatenate([np.asarray(s, np.int32) for s in seqs]) if len(seqs) > 1 else np.asarray(seqs[0], np.int32)
@@ -42,9 +43,13 @@ class DeviceEncoder:
     SPLIT_MIN_TOKENS = 16384   # ... and this many tokens (enough blocks to fill the chip on its own)
 
     def __init__(self, weights: np.ndarray, shape: BertShape = BertShape(), device: str | torch.device = "cuda:0",
-                 gemm_mode: Optional[str] = None):
+                 gemm_mode: Optional[str] = None, max_seq_length: Optional[int] = None):
         """gemm_mode: "f32" (exact f32 MFMA, bit-identical GEMMs) or "f16x3" (3-term split on the f16
-        MFMA, fp32-level accuracy, ~4x faster); default from $ICREC_GEMM_MODE, else DEFAULT_GEMM_MODE."""
+        MFMA, fp32-level accuracy, ~4x faster); default from $ICREC_GEMM_MODE, else DEFAULT_GEMM_MODE.
+        max_seq_length: the longest sequence the encoder must take, up to min(512, shape.max_position).  The
+        ceiling is min(256, shape.max_position) by default and only ever raised: a larger value sets it
+        (icrec_encoder_set_max_seqlen), a smaller one keeps the default.  Sequences of up to 256 tokens encode
+        to the same bits whatever the ceiling."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _native.IcrecError("DeviceEncoder needs a CUDA/HIP device; there is no CPU fallback")
@@ -68,6 +73,14 @@ class DeviceEncoder:
         _native.check(L.icrec_encoder_create(w.ctypes.data_as(C.c_void_p), w.size, C.byref(self._cfg),
                                              self.device.index, C.byref(h)), "icrec_encoder_create")
         self._h = h
+        self.max_seq_length = min(MAX_SEQ_LEN, shape.max_position)
+        if max_seq_length is not None and not 1 <= int(max_seq_length) <= self.max_seq_length:
+            try:
+                _native.check(L.icrec_encoder_set_max_seqlen(h, int(max_seq_length)), "icrec_encoder_set_max_seqlen")
+            except _native.IcrecError:
+                self.close()
+                raise
+            self.max_seq_length = int(max_seq_length)
         self._ws_slots: dict[int, Optional[torch.Tensor]] = {}
         self._side: Optional[torch.cuda.Stream] = None
 
@@ -143,8 +156,8 @@ class DeviceEncoder:
         lens = np.diff(cu)
         if (lens < 1).any():
             raise ValueError("every sequence needs at least one token")
-        if int(lens.max()) > MAX_SEQ_LEN:
-            raise ValueError(f"sequence longer than max_seq_length={MAX_SEQ_LEN}; truncate on the host")
+        if int(lens.max()) > self.max_seq_length:
+            raise ValueError(f"sequence longer than max_seq_length={self.max_seq_length}; truncate on the host")
         if int(ids.min()) < 0 or int(ids.max()) >= self.shape.vocab_size:
             raise ValueError(f"token id out of range [0, {self.shape.vocab_size})")
         start = 0
@@ -170,7 +183,7 @@ class DeviceEncoder:
             while end < n and (end == start or tok + len(seqs[end]) <= max_tokens_per_call):
                 tok += len(seqs[end])
                 end += 1
-            ids, cu, mx = pack_token_ids(seqs[start:end])
+            ids, cu, mx = pack_token_ids(seqs[start:end], self.max_seq_length)
             vmax = int(ids.max()) if ids.size else 0
             if ids.min() < 0 or vmax >= self.shape.vocab_size:
                 raise ValueError(f"token id out of range [0, {self.shape.vocab_size})")

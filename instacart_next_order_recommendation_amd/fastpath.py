@@ -5,7 +5,8 @@ Q = 1 the ~44 kernels of a request are launch-bound; libicrec's hot calls never 
 synchronise, so the whole request is captured once per (token bucket, k) and replayed: the host
 does one small H2D (ids + exclusions), one graph launch and one D2H of k results.
 
-Token buckets coincide with the attention kernel's length buckets (32/64/128/256 tokens): the
+Token buckets coincide with the attention kernel's length buckets (32/64/128/256 tokens, and one more
+at the encoder's ceiling when that is above 256 - 512 for a model served at max_seq_length 512): the
 captured launch processes `bucket` rows, the real length travels in cu_seqlens on the device, so
 rows past it are computed and ignored (pooling and attention read cu_seqlens).
 """
@@ -105,6 +106,9 @@ class SingleRequestPath:
 
     def __init__(self, encoder: DeviceEncoder, index: DeviceIndex):
         self.encoder, self.index = encoder, index
+        # requests of 257 tokens up to the encoder's ceiling share one bucket at that ceiling (9-16 key tiles)
+        ceiling = encoder.max_seq_length
+        self.buckets = BUCKETS + ((ceiling,) if ceiling > BUCKETS[-1] else ())
         self._graphs: dict[tuple[int, int], _Captured] = {}
         self._handles = self._handle_key()
 
@@ -117,7 +121,7 @@ class SingleRequestPath:
         self._handles = self._handle_key()
 
     def supports(self, n_tokens: int, k: int, n_excluded: int) -> bool:
-        return 1 <= n_tokens <= BUCKETS[-1] and n_excluded <= MAX_EXCLUDED and k <= self.index.n_rows
+        return 1 <= n_tokens <= self.buckets[-1] and n_excluded <= MAX_EXCLUDED and k <= self.index.n_rows
 
     def run(self, ids: Sequence[int], k: int, excluded_rows: Optional[Sequence[int]] = None, timed: bool = False):
         """-> (row indices int64 [k], scores float32 [k]) on the host; -1 / 0 padded like icrec_search.
@@ -131,7 +135,7 @@ class SingleRequestPath:
             self.invalidate()
         if self._handles[0] is None or self._handles[1] is None:
             raise _native.IcrecError("SingleRequestPath: encoder or index handle is closed")
-        bucket = next(b for b in BUCKETS if n <= b)
+        bucket = next(b for b in self.buckets if n <= b)
         c = self._graphs.get((bucket, k))
         if c is None:
             c = self._graphs[(bucket, k)] = _Captured(self.encoder, self.index, bucket, k)

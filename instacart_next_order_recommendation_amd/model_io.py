@@ -14,15 +14,19 @@ reference ends up using through transformers, uv.lock:3841).
 from __future__ import annotations
 
 import json
+import logging
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Sequence
 
 import numpy as np
 
+from . import _native
 from .synthetic import BertShape, blob_to_state_dict, state_dict_to_blob, synthetic_bert_weights, synthetic_vocab
 
-DEFAULT_MAX_SEQ_LENGTH = 256  # configs/train.yaml:11
+logger = logging.getLogger(__name__)
+
+DEFAULT_MAX_SEQ_LENGTH = 256  # configs/train.yaml:11; used when sentence_bert_config.json gives none
 
 
 @dataclass
@@ -169,7 +173,12 @@ def load_model_dir(model_dir: Path | str) -> LoadedModel:
     sb = d / "sentence_bert_config.json"
     if sb.exists():
         max_len = int(json.loads(sb.read_text()).get("max_seq_length") or max_len)
-    max_len = min(max_len, DEFAULT_MAX_SEQ_LENGTH, shape.max_position)
+    # the encoder takes up to ICREC_MAX_SEQLEN (512) tokens, and never more than the model has positions
+    limit = min(_native.ICREC_MAX_SEQLEN, shape.max_position)
+    if max_len > limit:
+        logger.warning("%s asks for max_seq_length %d; this encoder serves at most %d tokens for it: using %d",
+                       d, max_len, limit, limit)
+        max_len = limit
     return LoadedModel(shape, weights, max_len, HostTokenizer(d, max_len))
 
 

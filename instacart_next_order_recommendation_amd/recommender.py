@@ -115,7 +115,7 @@ class SbertModel:
         self.max_seq_length = loaded.max_seq_length
         self.shape = loaded.shape
         self.device = device
-        self.encoder = DeviceEncoder(loaded.weights, loaded.shape, device)
+        self.encoder = DeviceEncoder(loaded.weights, loaded.shape, device, max_seq_length=loaded.max_seq_length)
         self._weights = loaded.weights
         self._encoder_no_flag: Optional[DeviceEncoder] = None  # normalize_embeddings=False: one normalisation fewer
 
@@ -145,7 +145,8 @@ class SbertModel:
                 from dataclasses import replace
 
                 self._encoder_no_flag = DeviceEncoder(self._weights, replace(self.shape, n_normalize=self.shape.n_normalize - 1),
-                                                      self.device, gemm_mode=self.encoder.gemm_mode)
+                                                      self.device, gemm_mode=self.encoder.gemm_mode,
+                                                      max_seq_length=self.max_seq_length)
             enc = self._encoder_no_flag
         packed = getattr(self.tokenizer, "packed", None)
         per_call = max(int(batch_size), 1) * 4096
