@@ -748,13 +748,14 @@ struct Encoder {
     // than one round by definition, so a larger value changes nothing).  Every combination is supported and gives the
     // same bits; with tail_m > small_m a remainder longer than small_m takes the layer kernels (activation-resident QKV,
     // fused layer kernel) on the side stream instead of the latency form.
-    // Side stream + events of one caller stream: the short remainder of a large batch (batch_split) and the shorter
+    // Side stream + events of one caller stream: the short remainder of a large batch (batch_tail) and the shorter
     // attention buckets run beside the batch kernels of the same layer instead of behind them.  One set per caller
     // stream (created on first use, kept for the encoder's life), so that concurrent icrec_encode calls on different
     // streams - DeviceEncoder runs the two halves of a batch that way - do not queue behind each other's side work.
+    // Every fork and join records `ev` and waits on it at once (link), so one event serves them all.
     struct Side {
         hipStream_t caller = nullptr, side = nullptr;
-        hipEvent_t ev_main = nullptr, ev_qkv_tail = nullptr, ev_att = nullptr, ev_tail = nullptr, ev_q = nullptr, ev_sa = nullptr;
+        hipEvent_t ev = nullptr;
     };
     std::mutex side_mu;
     std::vector<Side*> sides;
@@ -771,8 +772,7 @@ static int side_for(Encoder* e, hipStream_t caller, Encoder::Side** out) {
     Encoder::Side* sd = new Encoder::Side();
     sd->caller = caller;
     ICREC_HIP(hipStreamCreateWithFlags(&sd->side, hipStreamNonBlocking));
-    for (hipEvent_t* ev : {&sd->ev_main, &sd->ev_qkv_tail, &sd->ev_att, &sd->ev_tail, &sd->ev_q, &sd->ev_sa})
-        ICREC_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    ICREC_HIP(hipEventCreateWithFlags(&sd->ev, hipEventDisableTiming));
     e->sides.push_back(sd);
     *out = sd;
     return ICREC_OK;
@@ -802,6 +802,12 @@ static EncWs enc_ws(const icrec_bert_cfg& c, int64_t T) {
     return w;
 }
 
+// The workspace regions of a call (enc_ws): x, ctx and h also as f16 hi/lo planes, the ctx / h planes in their place.
+struct EncBufs {
+    float *x, *qkv, *ctx, *t1, *h;
+    _Float16 *xh, *xl, *ch, *cl, *hh, *hl;
+};
+
 typedef TileCfg<2, 2, 2, 2> GemmBig;  // 128 x 128 output tile, 4 waves
 constexpr long long SMALL_M_MAX = 1 << 20;  // ICREC_SMALL_M above this: every call of up to 2^20 tokens takes the latency form
 
@@ -823,24 +829,22 @@ static void launch_linear(const float* A, int M, int K, const float* W, int N, c
                        bias, out, nt);
 }
 
-// f16x3 linear layer through the weights-direct engine.  Single requests / micro-batches (up to small_m tokens) are
-// latency-bound - a handful of workgroups, each walking its K loop at the rate ONE CU's vector L1 pulls fragments from
-// L2: they use 32-token x 64-feature workgroups, one 16-feature tile per wave (wt_linear_half_kernel; EPI 1 keeps the
-// 32 x 128 form: its small-batch consumer is wt_linear_lnin_kernel), as many workgroups as the shape allows; batches use
-// 64-token x 384-feature blocks (3 x 2 tiles per wave).  Per-output arithmetic is the same chain in all of them, so a
+// f16x3 linear layer through the weights-direct engine.  Single requests / micro-batches (`small`: up to small_m tokens)
+// are latency-bound - a handful of workgroups, each walking its K loop at the rate ONE CU's vector L1 pulls fragments
+// from L2: they use 32-token x 64-feature workgroups, one 16-feature tile per wave (wt_linear_half_kernel; EPI 1 keeps
+// the 32 x 128 form: its small-batch consumer is wt_linear_lnin_kernel), as many workgroups as the shape allows; batches
+// use 64-token x 384-feature blocks (3 x 2 tiles per wave).  Per-output arithmetic is the same chain in all of them, so a
 // request encodes to the same bits either way.
 template <int EPI>
 static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int K, const _Float16* Wp, int N,
-                             const float* bias, float* out, _Float16* oh, _Float16* ol, hipStream_t st, int small_m) {
-    if (T <= small_m) {
+                             const float* bias, float* out, _Float16* oh, _Float16* ol, hipStream_t st, bool small) {
+    if (small) {
         if constexpr (EPI == 0 || EPI == 2) {  // 16-feature tiles per wave, twice the workgroups (wt_linear_half_kernel)
             const int nbn = N / 64;
-            if (K % 256 == 0 && K >= 1024)  // FFN-down: weights eight k-steps ahead
-                hipLaunchKernelGGL((wt_linear_half_kernel<EPI, 8>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp,
-                                   N, bias, out, (const _Float16*)oh, (const _Float16*)ol, nbn);
-            else  // K = 384 (or another multiple of 384): six k-steps ahead
-                hipLaunchKernelGGL((wt_linear_half_kernel<EPI, 6>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp,
-                                   N, bias, out, (const _Float16*)oh, (const _Float16*)ol, nbn);
+            // FFN-down: weights eight k-steps ahead; K = 384 (or another multiple of 384): six k-steps ahead
+            auto kern = K % 256 == 0 && K >= 1024 ? wt_linear_half_kernel<EPI, 8> : wt_linear_half_kernel<EPI, 6>;
+            hipLaunchKernelGGL(kern, dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp, N, bias, out,
+                               (const _Float16*)oh, (const _Float16*)ol, nbn);
         } else {
             const int nbn = N / 128;
             hipLaunchKernelGGL((wt_linear_kernel<1, 1, 4, EPI>), dim3(((T + 31) / 32) * nbn), dim3(256), 0, st, Xh, Xl, T, K,
@@ -853,38 +857,39 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
     }
 }
 
-// Launch every length bucket that can occur for max_seqlen (a bucket whose workgroups all exit
-// costs a few microseconds; single-sequence calls launch exactly one bucket).
+// The attention length buckets, in launch order: 9-16 key tiles first (257-512 tokens: the longest bucket starts first),
+// then from the shortest up.  f16x3 batches take 5-8 key tiles in two buckets, single sequences and fp32 in one.
+// Bucket k serves [ATT_LO[k], ATT_HI[k]] key tiles with the kernel <NKT = WAVES = ATT_HI[k]>.
+enum AttBucket { ATT_9_16, ATT_1, ATT_2, ATT_3_4, ATT_5_6, ATT_7_8, ATT_5_8, ATT_N };
+constexpr int ATT_LO[ATT_N] = {9, 1, 2, 3, 5, 7, 5}, ATT_HI[ATT_N] = {16, 1, 2, 4, 6, 8, 8};
+
+// Launch, in AttBucket order, the buckets in `mask` (bits 1 << AttBucket) that the call needs: for a batch every bucket
+// that can occur for max_seqlen (one whose workgroups all exit costs a few microseconds), else the one that holds it.
 // X3: the f16x3 kernel, context out as planes (attention_x3_kernel); otherwise exact fp32 rows (attention_kernel).
 template <bool X3>
-static void launch_attention(const float* qkv, const int32_t* cu, int n_seqs, int heads, int H, int max_seqlen,
-                             float* ctx, _Float16* ch, _Float16* cl, hipStream_t st, int buckets = 63,
-                             const int32_t* order = nullptr) {
-    // buckets: bits 0..2 = the 1-, 2-, 3-4-tile buckets, bit 3 = 5-6 tiles (5-8 outside f16x3 batches), bit 4 = 7-8 tiles,
-    // bit 5 = 9-16 tiles (257-512 tokens: encoders whose ceiling was raised past 256; launched first, the longest bucket
-    // starts first) (callers split the buckets over two streams)
-    const float sl2e = (1.0f / sqrtf((float)DH)) * 1.44269504088896340736f;
+static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBufs& b, const int32_t* cu, int n_seqs,
+                             int max_seqlen, const int32_t* order, hipStream_t st) {
     const int nkt_max = (max_seqlen + 31) / 32;
-    const bool single = n_seqs == 1;
-    const dim3 grid1(n_seqs * heads, 1);
-#define ICREC_ATT(NKT, W, NLO)                                                                                   \
-    do {                                                                                                         \
-        if constexpr (X3) hipLaunchKernelGGL((attention_x3_kernel<NKT, W>), grid1, dim3(W * 64), 0, st, qkv, cu, heads, H, sl2e, ctx, ch, cl, order, NLO); \
-        else hipLaunchKernelGGL((attention_kernel<NKT, W>), grid1, dim3(W * 64), 0, st, qkv, cu, heads, H, sl2e, ctx, ch, cl);      \
-    } while (0)
-    if ((buckets & 32) && nkt_max >= 9) ICREC_ATT(16, 16, 8);
-    if ((buckets & 1) && (single ? nkt_max == 1 : true)) ICREC_ATT(1, 1, 0);
-    if ((buckets & 2) && (single ? nkt_max == 2 : nkt_max >= 2)) ICREC_ATT(2, 2, 1);
-    if ((buckets & 4) && (single ? (nkt_max == 3 || nkt_max == 4) : nkt_max >= 3)) ICREC_ATT(4, 4, 2);
-    if constexpr (X3) {
-        if (!single) {  // f16x3 batches: the sequences of 5-8 key tiles in two buckets (5-6 and 7-8 key tiles)
-            if ((buckets & 8) && nkt_max >= 5) ICREC_ATT(6, 6, 4);
-            if ((buckets & 16) && nkt_max >= 7) ICREC_ATT(8, 8, 6);
-            return;
+    const bool single = n_seqs == 1, split_5_8 = X3 && !single;
+    const float sl2e = (1.0f / sqrtf((float)DH)) * 1.44269504088896340736f;
+    for (int k = 0; k < ATT_N; ++k) {
+        if (!(mask >> k & 1) || (split_5_8 ? k == ATT_5_8 : k == ATT_5_6 || k == ATT_7_8) || nkt_max < ATT_LO[k] ||
+            (single && nkt_max > ATT_HI[k]))
+            continue;
+        const dim3 grid(n_seqs * c.heads, 1), block(ATT_HI[k] * 64);
+        if constexpr (X3) {
+            static const decltype(&attention_x3_kernel<1, 1>) kern[ATT_N] = {
+                attention_x3_kernel<16, 16>, attention_x3_kernel<1, 1>, attention_x3_kernel<2, 2>, attention_x3_kernel<4, 4>,
+                attention_x3_kernel<6, 6>, attention_x3_kernel<8, 8>, attention_x3_kernel<8, 8>};
+            hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx, b.ch, b.cl, order,
+                               ATT_LO[k] - 1);
+        } else {  // (f16x3 batches only split 5-8 key tiles)
+            static const decltype(&attention_kernel<1, 1>) kern[ATT_N] = {
+                attention_kernel<16, 16>, attention_kernel<1, 1>, attention_kernel<2, 2>, attention_kernel<4, 4>,
+                nullptr, nullptr, attention_kernel<8, 8>};
+            hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx, b.ch, b.cl);
         }
     }
-    if ((buckets & 8) && (single ? (nkt_max >= 5 && nkt_max <= 8) : nkt_max >= 5)) ICREC_ATT(8, 8, 4);
-#undef ICREC_ATT
 }
 
 }  // namespace icrec
@@ -987,13 +992,10 @@ int icrec_encoder_destroy(icrec_encoder* h) {
     (void)hipFree(e->blob);
     (void)hipFree(e->extra);
     if (e->planes) (void)hipFree(e->planes);
-    for (Encoder::Side* sd : e->sides) {
-        if (sd->side) {
-            (void)hipStreamSynchronize(sd->side);
-            (void)hipStreamDestroy(sd->side);
-        }
-        for (hipEvent_t ev : {sd->ev_main, sd->ev_qkv_tail, sd->ev_att, sd->ev_tail, sd->ev_q, sd->ev_sa})
-            if (ev) (void)hipEventDestroy(ev);
+    for (Encoder::Side* sd : e->sides) {  // (side_for keeps a side only once its stream and event exist)
+        (void)hipStreamSynchronize(sd->side);
+        (void)hipStreamDestroy(sd->side);
+        (void)hipEventDestroy(sd->ev);
         delete sd;
     }
     delete e;
@@ -1015,26 +1017,180 @@ size_t icrec_encode_workspace_bytes(const icrec_encoder* h, int64_t total_tokens
     return enc_ws(e->cfg, total_tokens).total;
 }
 
-// How icrec_encode splits a batch of T tokens (f16x3 mode): [0, main) through the batch kernels in whole rounds of
-// one 64-token workgroup per CU, [main, T) — a short remainder, or everything for small batches — through the
-// small-batch kernels.
-static void batch_split(const Encoder* e, int T, int* t_main, int* t_tail) {
+// How icrec_encode splits a batch of T tokens (f16x3 mode): [0, T - tail) through the batch kernels in whole rounds of
+// one 64-token workgroup per CU, a short remainder [T - tail, T) (tail > 0) through the small-batch kernels.
+static int batch_tail(const Encoder* e, int T) {
     const int round_tokens = 64 * e->n_cu;
-    *t_main = T;
-    *t_tail = 0;
-    if (T > round_tokens && T % round_tokens != 0 && T % round_tokens <= e->tail_m) {
-        *t_tail = T % round_tokens;
-        *t_main = T - *t_tail;
-    }
+    return T > round_tokens && T % round_tokens <= e->tail_m ? T % round_tokens : 0;
 }
 
 int icrec_encode_batch_split(const icrec_encoder* h, int64_t total_tokens, int64_t* main_tokens, int64_t* tail_tokens) {
     const Encoder* e = reinterpret_cast<const Encoder*>(h);
     ICREC_REQUIRE(e && main_tokens && tail_tokens && total_tokens >= 1 && total_tokens < (1ll << 31), "icrec_encode_batch_split: bad argument");
-    int m, t;
-    batch_split(e, (int)total_tokens, &m, &t);
-    *main_tokens = m;
-    *tail_tokens = t;
+    *tail_tokens = batch_tail(e, (int)total_tokens);
+    *main_tokens = total_tokens - *tail_tokens;
+    return ICREC_OK;
+}
+
+// Embeddings + LayerNorm.  f16x3 mode leaves the fp32 x region unused (the residual stream is its two planes): it carries
+// the attention dispatch order of batches, returned here (nullptr: workgroup b serves sequence b / heads, as unfused).
+static const int32_t* embed(const Encoder* e, const EncBufs& b, const int32_t* ids_dev, const int32_t* cu_dev,
+                            int n_seqs, int T, hipStream_t st) {
+    const icrec_bert_cfg& c = e->cfg;
+    const bool x3 = c.gemm_mode == ICREC_GEMM_F16X3;
+    int32_t* order = nullptr;
+    if (x3 && n_seqs >= 64 && e->fuse) {
+        order = reinterpret_cast<int32_t*>(b.x);
+        hipLaunchKernelGGL(seq_order_kernel, dim3(1), dim3(1024), 0, st, cu_dev, n_seqs, order);
+    }
+    hipLaunchKernelGGL((x3 ? embed_ln_kernel<HID, true> : embed_ln_kernel<HID, false>), dim3((T + 3) / 4), dim3(256), 0,
+                       st, ids_dev, cu_dev, n_seqs, T, e->word, e->pos, e->type, e->eg, e->eb, c.ln_eps, c.vocab_size,
+                       c.max_position, b.x, b.xh, b.xl);
+    return order;
+}
+
+// One fork or join: work enqueued on `to` from here on runs behind everything enqueued on `from` so far.
+static hipError_t link(const Encoder::Side* sd, hipStream_t from, hipStream_t to) {
+    const hipError_t err = hipEventRecord(sd->ev, from);
+    return err != hipSuccess ? err : hipStreamWaitEvent(to, sd->ev, 0);
+}
+
+// A token range of an f16x3 call, rows [r0, r0 + n) on stream st, and the form its kernels take, decided once per call.
+struct Range {
+    int r0, n;
+    hipStream_t st;
+    bool small;  // n <= small_m: the latency-form GEMMs (launch_wt_linear), every GEMM a launch of its own
+    bool layer;  // fuse && !small: the layer kernels (qkv_resident_kernel, one ffn_fused2_kernel per layer)
+    bool fold;   // fuse && small: a LayerNorm is the prologue of the GEMM behind it (wt_linear_lnin_kernel)
+    Range(const Encoder* e, int r0, int n, hipStream_t st)
+        : r0(r0), n(n), st(st), small(n <= e->small_m), layer(e->fuse && !small), fold(e->fuse && small) {}
+    bool launches_qkv(int l) const { return l == 0 || !layer; }  // (else ffn_fused2_kernel's epilogue computes it)
+    bool ffn_ln_to_next(int l, int layers) const { return fold && l + 1 < layers; }  // to the next QKV's prologue
+};
+
+static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_seqs, int T, int max_seqlen,
+                     const int32_t* order, hipStream_t st) {
+    const icrec_bert_cfg& c = e->cfg;
+    const int H = c.hidden, I = c.intermediate;
+    const bool split_att = e->side_stream && n_seqs >= 64 && max_seqlen > 128;  // batches with a long bucket
+    // Token ranges: [0, T_main) goes through the batch kernels in whole rounds of one 64-token workgroup per CU, a short
+    // remainder [T_main, T) through the small-batch kernels (same arithmetic, same bits) instead of costing every batch
+    // kernel an extra, almost empty round.
+    const int T_tail = batch_tail(e, T), T_main = T - T_tail;
+    Encoder::Side* sd = nullptr;
+    if (e->side_stream && (T_tail || split_att))
+        if (int rc_ = side_for(e, st, &sd)) return rc_;
+    // The remainder's kernels run on the side stream: its QKV beside the batch QKV, its attention-out / FFN chain beside
+    // the batch's.  Attention covers all rows, so it joins both; the side stream's in-order execution keeps its own
+    // layers apart.
+    const Range main(e, 0, T_main, st), tail(e, T_main, T_tail, sd ? sd->side : st);
+    const bool tail_on_side = T_tail && sd;
+    if (main.layer || tail.layer) {  // the layer kernels' LDS is above the default limit
+        if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(qkv_resident_kernel), QKVR_LDS)) return rc_;
+        if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(ffn_fused2_kernel), FFN2_LDS)) return rc_;
+    }
+
+    auto qkv_stage = [&](const Range& r, int l) {
+        const LayerW& L = e->layers[l];
+        _Float16 *const xhr = b.xh + (size_t)r.r0 * H, *const xlr = b.xl + (size_t)r.r0 * H;
+        float* const qkvr = b.qkv + (size_t)r.r0 * 3 * H;
+        if (r.layer) {  // activation-resident form: one 64-token workgroup per CU
+            hipLaunchKernelGGL(qkv_resident_kernel, dim3((r.n + 63) / 64), dim3(512), QKVR_LDS, r.st, xhr, xlr, r.n,
+                               L.Wqkv_p, L.bqkv, qkvr, 3 * H);
+        } else if (l > 0 && r.ffn_ln_to_next(l - 1, c.layers)) {
+            // the previous layer's FFN LayerNorm is this kernel's prologue (t1 rows -> planes in LDS and, from the
+            // workgroups of feature block 0, to xh / xl): one graph node fewer per layer
+            const LayerW& Lp = e->layers[l - 1];
+            const int nbn = 3 * H / 64;
+            hipLaunchKernelGGL((wt_linear_lnin_kernel<0, true>), dim3(((r.n + 31) / 32) * nbn), dim3(256), 0, r.st,
+                               (const float*)(b.t1 + (size_t)r.r0 * H), r.n, Lp.g2, Lp.b2n, c.ln_eps, xhr, xlr, L.Wqkv_p,
+                               3 * H, L.bqkv, qkvr, (_Float16*)nullptr, (_Float16*)nullptr, nbn);
+        } else {
+            launch_wt_linear<0>(xhr, xlr, r.n, H, L.Wqkv_p, 3 * H, L.bqkv, qkvr, nullptr, nullptr, r.st, r.small);
+        }
+    };
+    auto post_stage = [&](const Range& r, int l) {
+        const LayerW& L = e->layers[l];
+        float* const t1r = b.t1 + (size_t)r.r0 * H;
+        _Float16 *const xhr = b.xh + (size_t)r.r0 * H, *const xlr = b.xl + (size_t)r.r0 * H;
+        const _Float16 *const chr = b.ch + (size_t)r.r0 * H, *const clr = b.cl + (size_t)r.r0 * H;
+        if (r.layer) {
+            // attention-out + residual + LN and the whole FFN block + residual + LN: ONE kernel per half layer
+            // (x1 stays on chip between the two LayerNorm sites)
+            ScopedTimer tm(T_FFN_UP, r.st);
+            // ... and, but for the last layer, the NEXT layer's QKV projection of the rows it has just normalised
+            const bool next_qkv = l + 1 < c.layers;
+            const LayerW& Ln = e->layers[next_qkv ? l + 1 : l];
+            hipLaunchKernelGGL(ffn_fused2_kernel, dim3((r.n + 63) / 64), dim3(512), FFN2_LDS, r.st, xhr, xlr, r.n, I,
+                               L.W1_p, L.b1, L.W2_p, L.b2, L.g2, L.b2n, c.ln_eps, chr, clr, L.Wo_p, L.bo, L.g1, L.b1n,
+                               next_qkv ? (const _Float16*)Ln.Wqkv_p : (const _Float16*)nullptr, (const float*)Ln.bqkv,
+                               b.qkv + (size_t)r.r0 * 3 * H, 3 * H);
+            return;
+        }
+        _Float16 *const hhr = b.hh + (size_t)r.r0 * I, *const hlr = b.hl + (size_t)r.r0 * I;
+        launch_wt_linear<2>(chr, clr, r.n, H, L.Wo_p, H, L.bo, t1r, xhr, xlr, r.st, r.small);  // residual: x planes
+        if (r.fold) {  // LayerNorm + FFN-up in one node (wt_linear_lnin_kernel)
+            const int nbn = I / 64;
+            hipLaunchKernelGGL((wt_linear_lnin_kernel<1, true>), dim3(((r.n + 31) / 32) * nbn), dim3(256), 0, r.st,
+                               (const float*)t1r, r.n, L.g1, L.b1n, c.ln_eps, xhr, xlr, L.W1_p, I, L.b1, (float*)nullptr,
+                               hhr, hlr, nbn);
+        } else {
+            hipLaunchKernelGGL(ln_wt_kernel, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n, L.g1, L.b1n, c.ln_eps,
+                               xhr, xlr);
+            ScopedTimer tm(r.small ? T_NSLOTS - 1 : T_FFN_UP, r.st);
+            launch_wt_linear<1>(xhr, xlr, r.n, H, L.W1_p, I, L.b1, nullptr, hhr, hlr, r.st, r.small);
+        }
+        launch_wt_linear<2>(hhr, hlr, r.n, I, L.W2_p, H, L.b2, t1r, xhr, xlr, r.st, r.small);
+        if (!r.ffn_ln_to_next(l, c.layers))
+            hipLaunchKernelGGL(ln_wt_kernel, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n, L.g2, L.b2n, c.ln_eps,
+                               xhr, xlr);
+    };
+
+    if (tail_on_side) ICREC_HIP(link(sd, st, sd->side));  // the side stream starts behind the embeddings
+    for (int l = 0; l < c.layers; ++l) {
+        if (T_tail && tail.launches_qkv(l)) qkv_stage(tail, l);
+        if (main.launches_qkv(l)) qkv_stage(main, l);
+        if (tail_on_side) ICREC_HIP(link(sd, sd->side, st));
+        if (split_att && sd) {
+            // the long bucket keeps one 8-wave workgroup per CU busy (LDS) with issue slots to spare: the shorter
+            // buckets' workgroups run beside it from the side stream instead of after it (sequences of 9-16 key tiles:
+            // that bucket goes first, on the caller's stream, ahead of the side stream's)
+            ICREC_HIP(link(sd, st, sd->side));
+            const unsigned side_buckets = 1u << ATT_1 | 1u << ATT_2 | 1u << ATT_3_4 | 1u << ATT_7_8;
+            launch_attention<true>(1u << ATT_9_16, c, b, cu_dev, n_seqs, max_seqlen, order, st);
+            launch_attention<true>(side_buckets, c, b, cu_dev, n_seqs, max_seqlen, order, sd->side);
+            launch_attention<true>(1u << ATT_5_6, c, b, cu_dev, n_seqs, max_seqlen, order, st);
+            ICREC_HIP(link(sd, sd->side, st));
+        } else {
+            launch_attention<true>(~0u, c, b, cu_dev, n_seqs, max_seqlen, order, st);
+        }
+        if (tail_on_side) ICREC_HIP(link(sd, st, sd->side));
+        if (T_tail) post_stage(tail, l);
+        post_stage(main, l);
+    }
+    if (tail_on_side) ICREC_HIP(link(sd, sd->side, st));  // pooling reads every row: the side stream joins here
+    return ICREC_OK;
+}
+
+static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_seqs, int T, int max_seqlen,
+                      hipStream_t st) {
+    const icrec_bert_cfg& c = e->cfg;
+    const int H = c.hidden, I = c.intermediate, rows_grid = (T + 3) / 4;
+    for (int l = 0; l < c.layers; ++l) {
+        const LayerW& L = e->layers[l];
+        launch_linear<false>(b.x, T, H, L.Wqkv, 3 * H, L.bqkv, b.qkv, st);
+        launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
+        launch_linear<false>(b.ctx, T, H, L.Wo, H, L.bo, b.t1, st);
+        hipLaunchKernelGGL((add_ln_kernel<HID, false>), dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g1, L.b1n,
+                           c.ln_eps, b.xh, b.xl);
+        {
+            ScopedTimer tm(T_FFN_UP, st);
+            launch_linear<true>(b.x, T, H, L.W1, I, L.b1, b.h, st);
+        }
+        launch_linear<false>(b.h, T, I, L.W2, H, L.b2, b.t1, st);
+        hipLaunchKernelGGL((add_ln_kernel<HID, false>), dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g2, L.b2n,
+                           c.ln_eps, b.xh, b.xl);
+    }
     return ICREC_OK;
 }
 
@@ -1054,185 +1210,27 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
     hipStream_t st = (hipStream_t)stream;
     ScopedTimer whole(T_ENCODE, st);
     char* base = reinterpret_cast<char*>(ws);
-    float* x = reinterpret_cast<float*>(base + w.x);
-    float* qkv = reinterpret_cast<float*>(base + w.qkv);
-    float* ctx = reinterpret_cast<float*>(base + w.ctx);
-    float* t1 = reinterpret_cast<float*>(base + w.t1);
-    float* hb = reinterpret_cast<float*>(base + w.h);
     const icrec_bert_cfg& c = e->cfg;
     const int H = c.hidden, I = c.intermediate;
-    const int rows_grid = (T + 3) / 4;
     const bool x3 = c.gemm_mode == ICREC_GEMM_F16X3;
-    // whole rounds of the fused FFN kernel (one 64-token workgroup per CU) + a short remainder, see the layer loop
-    int T_main, T_tail;
-    batch_split(e, T, &T_main, &T_tail);
-    const bool fuse = e->fuse, side_stream = e->side_stream;
-    const int small_m = e->small_m;
-    const bool split_att = x3 && side_stream && n_seqs >= 64 && max_seqlen > 128;  // batches with a long bucket
-    Encoder::Side* sd = nullptr;
-    if (x3 && side_stream && (T_tail || split_att))
-        if (int rc_ = side_for(e, st, &sd)) return rc_;
-    const bool use_side = sd != nullptr;
-    // f16 hi/lo planes (F16X3): x, ctx and h; ctx/h planes alias the fp32 regions they replace
-    _Float16* xh = reinterpret_cast<_Float16*>(base + w.xs);
-    _Float16* xl = xh + (size_t)T * H;
-    _Float16* ch = reinterpret_cast<_Float16*>(ctx);
-    _Float16* cl = ch + (size_t)T * H;
-    _Float16* hh = reinterpret_cast<_Float16*>(hb);
-    _Float16* hl = hh + (size_t)T * I;
-
-    // f16x3 mode: the fp32 x region of the workspace is unused (the residual stream is its two planes): it carries the
-    // attention dispatch order of batches (the unfused reference chain keeps the natural order: workgroup b serves
-    // sequence b / heads)
-    const int32_t* order = nullptr;
-    if (x3 && n_seqs >= 64 && fuse) {
-        int32_t* ord = reinterpret_cast<int32_t*>(x);
-        hipLaunchKernelGGL(seq_order_kernel, dim3(1), dim3(1024), 0, st, cu_dev, n_seqs, ord);
-        order = ord;
-    }
-    if (x3)
-        hipLaunchKernelGGL((embed_ln_kernel<HID, true>), dim3(rows_grid), dim3(256), 0, st, ids_dev, cu_dev, n_seqs, T,
-                           e->word, e->pos, e->type, e->eg, e->eb, c.ln_eps, c.vocab_size, c.max_position, x, xh, xl);
-    else
-        hipLaunchKernelGGL((embed_ln_kernel<HID, false>), dim3(rows_grid), dim3(256), 0, st, ids_dev, cu_dev, n_seqs, T,
-                           e->word, e->pos, e->type, e->eg, e->eb, c.ln_eps, c.vocab_size, c.max_position, x, xh, xl);
-    for (int l = 0; l < c.layers; ++l) {
-        const LayerW& L = e->layers[l];
-        if (x3) {
-            // Token ranges: [0, T_main) goes through the batch kernels in whole rounds of one 64-token workgroup per
-            // CU, a short remainder [T_main, T) through the small-batch kernels (same arithmetic, same bits) instead
-            // of costing every batch kernel an extra, almost empty round.
-            auto qkv_stage = [&](int r0, int Tn, hipStream_t st) -> int {
-                if (Tn > small_m && fuse) {  // activation-resident form: one 64-token workgroup per CU
-                    auto kern = qkv_resident_kernel;
-                    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), QKVR_LDS)) return rc_;
-                    hipLaunchKernelGGL(kern, dim3((Tn + 63) / 64), dim3(512), QKVR_LDS, st, xh + (size_t)r0 * H,
-                                       xl + (size_t)r0 * H, Tn, L.Wqkv_p, L.bqkv, qkv + (size_t)r0 * 3 * H, 3 * H);
-                    return ICREC_OK;
-                }
-                if (fuse && l > 0 && Tn <= small_m) {
-                    // small ranges: the previous layer's FFN LayerNorm is this kernel's prologue (t1 rows -> planes in LDS
-                    // and, from the workgroups of feature block 0, to xh / xl): one graph node fewer per layer
-                    const LayerW& Lp = e->layers[l - 1];
-                    const int nbn = 3 * H / 64;
-                    hipLaunchKernelGGL((wt_linear_lnin_kernel<0, true>), dim3(((Tn + 31) / 32) * nbn), dim3(256), 0, st,
-                                       (const float*)(t1 + (size_t)r0 * H), Tn, Lp.g2, Lp.b2n, c.ln_eps, xh + (size_t)r0 * H,
-                                       xl + (size_t)r0 * H, L.Wqkv_p, 3 * H, L.bqkv, qkv + (size_t)r0 * 3 * H,
-                                       (_Float16*)nullptr, (_Float16*)nullptr, nbn);
-                    return ICREC_OK;
-                }
-                launch_wt_linear<0>(xh + (size_t)r0 * H, xl + (size_t)r0 * H, Tn, H, L.Wqkv_p, 3 * H, L.bqkv,
-                                    qkv + (size_t)r0 * 3 * H, nullptr, nullptr, st, small_m);
-                return ICREC_OK;
-            };
-            auto post_stage = [&](int r0, int Tn, hipStream_t st) -> int {
-                float* const t1r = t1 + (size_t)r0 * H;
-                _Float16 *const xhr = xh + (size_t)r0 * H, *const xlr = xl + (size_t)r0 * H;
-                const _Float16 *const chr = ch + (size_t)r0 * H, *const clr = cl + (size_t)r0 * H;
-                if (Tn > small_m && fuse) {
-                    // attention-out + residual + LN and the whole FFN block + residual + LN: ONE kernel per half layer
-                    // (x1 stays on chip between the two LayerNorm sites)
-                    ScopedTimer tm(T_FFN_UP, st);
-                    const int nblk = (Tn + 63) / 64;
-                    auto kern = ffn_fused2_kernel;
-                    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), FFN2_LDS)) return rc_;
-                    // ... and, but for the last layer, the NEXT layer's QKV projection of the rows it has just normalised
-                    const bool next_qkv = l + 1 < c.layers;
-                    const LayerW& Ln = e->layers[next_qkv ? l + 1 : l];
-                    hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), FFN2_LDS, st, xhr, xlr, Tn, I, L.W1_p, L.b1, L.W2_p,
-                                       L.b2, L.g2, L.b2n, c.ln_eps, chr, clr, L.Wo_p, L.bo, L.g1, L.b1n,
-                                       next_qkv ? (const _Float16*)Ln.Wqkv_p : (const _Float16*)nullptr, (const float*)Ln.bqkv,
-                                       qkv + (size_t)r0 * 3 * H, 3 * H);
-                } else {
-                    _Float16 *const hhr = hh + (size_t)r0 * I, *const hlr = hl + (size_t)r0 * I;
-                    launch_wt_linear<2>(chr, clr, Tn, H, L.Wo_p, H, L.bo, t1r, xhr, xlr, st, small_m);  // residual: x planes
-                    if (fuse && Tn <= small_m) {  // LayerNorm + FFN-up in one node (wt_linear_lnin_kernel)
-                        const int nbn = I / 64;
-                        hipLaunchKernelGGL((wt_linear_lnin_kernel<1, true>), dim3(((Tn + 31) / 32) * nbn), dim3(256), 0, st,
-                                           (const float*)t1r, Tn, L.g1, L.b1n, c.ln_eps, xhr, xlr, L.W1_p, I, L.b1,
-                                           (float*)nullptr, hhr, hlr, nbn);
-                    } else {
-                    hipLaunchKernelGGL(ln_wt_kernel, dim3((Tn + 15) / 16), dim3(256), 0, st, t1r, Tn, L.g1, L.b1n,
-                                       c.ln_eps, xhr, xlr);
-                    {
-                        ScopedTimer tm(Tn > small_m ? T_FFN_UP : T_NSLOTS - 1, st);
-                        launch_wt_linear<1>(xhr, xlr, Tn, H, L.W1_p, I, L.b1, nullptr, hhr, hlr, st, small_m);
-                    }
-                    }
-                    launch_wt_linear<2>(hhr, hlr, Tn, I, L.W2_p, H, L.b2, t1r, xhr, xlr, st, small_m);
-                    // the FFN LayerNorm: the prologue of the next layer's QKV projection (qkv_stage) - but for the last layer
-                    if (!(fuse && Tn <= small_m && l + 1 < c.layers))
-                    hipLaunchKernelGGL(ln_wt_kernel, dim3((Tn + 15) / 16), dim3(256), 0, st, t1r, Tn, L.g2, L.b2n,
-                                       c.ln_eps, xhr, xlr);
-                }
-                return ICREC_OK;
-            };
-            // The remainder's kernels run on the side stream: its QKV beside the batch QKV, its attention-out / FFN chain
-            // beside the batch's.  Attention covers all rows, so it joins both (ev_qkv_tail in, ev_att out); the side
-            // stream's in-order execution keeps its own layers apart.
-            // batches: layer 0 projects Q / K / V in a launch of its own; every later layer's projection is the epilogue of
-            // the previous layer's fused kernel (also for a remainder longer than small_m, see tail_m)
-            const bool qkv_in_fused = fuse && T_main > small_m;
-            const bool tail_qkv_in_fused = fuse && T_tail > small_m;
-            hipStream_t ts = st;
-            if (T_tail && use_side) {
-                ts = sd->side;
-                if (l == 0) {  // the side stream starts behind the embeddings
-                    ICREC_HIP(hipEventRecord(sd->ev_main, st));
-                    ICREC_HIP(hipStreamWaitEvent(ts, sd->ev_main, 0));
-                }
-                if (l == 0 || !tail_qkv_in_fused)
-                    if (int rc_ = qkv_stage(T_main, T_tail, ts)) return rc_;
-                ICREC_HIP(hipEventRecord(sd->ev_qkv_tail, ts));
-            } else if (T_tail && (l == 0 || !tail_qkv_in_fused)) {
-                if (int rc_ = qkv_stage(T_main, T_tail, st)) return rc_;
-            }
-            if (l == 0 || !qkv_in_fused)
-                if (int rc_ = qkv_stage(0, T_main, st)) return rc_;
-            if (T_tail && use_side) ICREC_HIP(hipStreamWaitEvent(st, sd->ev_qkv_tail, 0));
-            if (split_att && use_side) {
-                // the long bucket keeps one 8-wave workgroup per CU busy (LDS) with issue slots to spare: the shorter
-                // buckets' workgroups run beside it from the side stream instead of after it
-                ICREC_HIP(hipEventRecord(sd->ev_q, st));
-                ICREC_HIP(hipStreamWaitEvent(sd->side, sd->ev_q, 0));
-                // (sequences of 9-16 key tiles: that bucket goes first, on the caller's stream, ahead of the side stream's)
-                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 32, order);
-                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, sd->side, 7 | 16, order);
-                ICREC_HIP(hipEventRecord(sd->ev_sa, sd->side));
-                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 8, order);
-                ICREC_HIP(hipStreamWaitEvent(st, sd->ev_sa, 0));
-            } else {
-                launch_attention<true>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st, 63, order);
-            }
-            if (T_tail) {
-                if (use_side) {
-                    ICREC_HIP(hipEventRecord(sd->ev_att, st));
-                    ICREC_HIP(hipStreamWaitEvent(ts, sd->ev_att, 0));
-                }
-                if (int rc_ = post_stage(T_main, T_tail, ts)) return rc_;
-            }
-            if (int rc_ = post_stage(0, T_main, st)) return rc_;
-            if (T_tail && use_side && l + 1 == c.layers) {  // pooling reads every row: the side stream joins here
-                ICREC_HIP(hipEventRecord(sd->ev_tail, ts));
-                ICREC_HIP(hipStreamWaitEvent(st, sd->ev_tail, 0));
-            }
-        } else {
-            launch_linear<false>(x, T, H, L.Wqkv, 3 * H, L.bqkv, qkv, st);
-            launch_attention<false>(qkv, cu_dev, n_seqs, c.heads, H, max_seqlen, ctx, ch, cl, st);
-            launch_linear<false>(ctx, T, H, L.Wo, H, L.bo, t1, st);
-            hipLaunchKernelGGL((add_ln_kernel<HID, false>), dim3(rows_grid), dim3(256), 0, st, t1, x, T, L.g1, L.b1n,
-                               c.ln_eps, xh, xl);
-            {
-                ScopedTimer tm(T_FFN_UP, st);
-                launch_linear<true>(x, T, H, L.W1, I, L.b1, hb, st);
-            }
-            launch_linear<false>(hb, T, I, L.W2, H, L.b2, t1, st);
-            hipLaunchKernelGGL((add_ln_kernel<HID, false>), dim3(rows_grid), dim3(256), 0, st, t1, x, T, L.g2, L.b2n,
-                               c.ln_eps, xh, xl);
-        }
-    }
-    if (x3) hipLaunchKernelGGL((pool_norm_kernel<HID, true>), dim3(n_seqs), dim3(HID), 0, st, x, xh, xl, cu_dev, c.n_normalize, out_dev);
-    else hipLaunchKernelGGL((pool_norm_kernel<HID, false>), dim3(n_seqs), dim3(HID), 0, st, x, xh, xl, cu_dev, c.n_normalize, out_dev);
+    EncBufs b;
+    b.x = reinterpret_cast<float*>(base + w.x);
+    b.qkv = reinterpret_cast<float*>(base + w.qkv);
+    b.ctx = reinterpret_cast<float*>(base + w.ctx);
+    b.t1 = reinterpret_cast<float*>(base + w.t1);
+    b.h = reinterpret_cast<float*>(base + w.h);
+    b.xh = reinterpret_cast<_Float16*>(base + w.xs);
+    b.xl = b.xh + (size_t)T * H;
+    b.ch = reinterpret_cast<_Float16*>(b.ctx);
+    b.cl = b.ch + (size_t)T * H;
+    b.hh = reinterpret_cast<_Float16*>(b.h);
+    b.hl = b.hh + (size_t)T * I;
+    const int32_t* order = embed(e, b, ids_dev, cu_dev, n_seqs, T, st);
+    if (int rc_ = x3 ? encode_x3(e, b, cu_dev, n_seqs, T, max_seqlen, order, st)
+                     : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
+        return rc_;
+    hipLaunchKernelGGL((x3 ? pool_norm_kernel<HID, true> : pool_norm_kernel<HID, false>), dim3(n_seqs), dim3(HID), 0, st,
+                       b.x, b.xh, b.xl, cu_dev, c.n_normalize, out_dev);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
 }

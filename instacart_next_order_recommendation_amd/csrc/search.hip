@@ -990,11 +990,21 @@ static inline float filter_eps(int dim) {
 static inline int filter_list_len(int k) { int kp = k + FILTER_SLACK; kp = (kp + 7) & ~7; return kp; }
 
 struct Plan {
-    int variant;  // 0 big, 1 mid, 2 small
+    int variant;  // 0 big, 1 mid, 2 small, 3 streaming
     int BM, BN, Qpad, n_qtiles, n_row_tiles, tiles_per_chunk, n_chunks;
-    size_t smem;
+    size_t smem;  // tiled variants (launch_exact sizes the streaming kernel's)
     size_t ws_q, ws_partial, ws_total;
 };
+
+// The rows as n_row_tiles tiles of BM rows, in n_chunks chunks of tiles_per_chunk whole tiles: one chunk per block (of
+// each query tile) and one sorted list per chunk and query: `want` chunks, clamped to [1, cap] and to the tile count.
+static void plan_chunks(int64_t n_rows, int BM, int want, int cap, int* n_row_tiles, int* tiles_per_chunk, int* n_chunks) {
+    *n_row_tiles = (int)((n_rows + BM - 1) / BM);
+    want = want < 1 ? 1 : want > cap ? cap : want;
+    if (want > *n_row_tiles) want = *n_row_tiles;
+    *tiles_per_chunk = (*n_row_tiles + want - 1) / want;
+    *n_chunks = (*n_row_tiles + *tiles_per_chunk - 1) / *tiles_per_chunk;
+}
 
 // Largest batch the streaming kernel takes (ICREC_STREAM_MAX_Q=0 disables it; tuning/diagnostic knob), read ONCE,
 // when the index is created: a handle never changes its kernels between calls.
@@ -1012,66 +1022,25 @@ static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream) {
     const int64_t st_tiles = (ix->n_rows + ST_ROWS - 1) / ST_ROWS;
     if (allow_stream && Q <= ix->stream_max_q && (Q <= 2 || st_tiles >= 2 * 3 * (int64_t)ix->n_cu)) {
         // variant 3: stream_search_kernel<NQ>, one block per chunk of 256-row tiles, no query tiling
-        const int nq = Q <= 1 ? 1 : Q <= 2 ? 2 : Q <= 4 ? 4 : 8;
-        p.variant = 3; p.BM = ST_ROWS; p.BN = nq;
-        p.smem = nq == 1 ? StreamSmem<1>::bytes(k) : nq == 2 ? StreamSmem<2>::bytes(k) : nq == 4 ? StreamSmem<4>::bytes(k)
-                                                                                                 : StreamSmem<8>::bytes(k);
+        p.variant = 3; p.BM = ST_ROWS; p.BN = Q <= 1 ? 1 : Q <= 2 ? 2 : Q <= 4 ? 4 : 8;
+        p.smem = 0;
         p.n_qtiles = 1;
-        p.Qpad = nq;
-        p.n_row_tiles = (int)((ix->n_rows + p.BM - 1) / p.BM);
-        int want_chunks = 3 * ix->n_cu;  // ~3 blocks per CU are resident (LDS)
-        if (want_chunks > MERGE_MAX_LISTS) want_chunks = MERGE_MAX_LISTS;
-        if (want_chunks > p.n_row_tiles) want_chunks = p.n_row_tiles;
-        p.tiles_per_chunk = (p.n_row_tiles + want_chunks - 1) / want_chunks;
-        p.n_chunks = (p.n_row_tiles + p.tiles_per_chunk - 1) / p.tiles_per_chunk;
+        p.Qpad = p.BN;
+        // ~3 blocks per CU are resident (LDS)
+        plan_chunks(ix->n_rows, p.BM, 3 * ix->n_cu, MERGE_MAX_LISTS, &p.n_row_tiles, &p.tiles_per_chunk, &p.n_chunks);
     } else {
         if (Q > 64 && k <= 32) { p.variant = 0; p.BM = CfgBig::BM; p.BN = CfgBig::BN; p.smem = SearchSmem<CfgBig>::bytes(k); }
         else if (Q > 32 && k <= 64) { p.variant = 1; p.BM = CfgMid::BM; p.BN = CfgMid::BN; p.smem = SearchSmem<CfgMid>::bytes(k); }
         else { p.variant = 2; p.BM = CfgSmall::BM; p.BN = CfgSmall::BN; p.smem = SearchSmem<CfgSmall>::bytes(k); }
         p.n_qtiles = (Q + p.BN - 1) / p.BN;
         p.Qpad = p.n_qtiles * p.BN;
-        p.n_row_tiles = (int)((ix->n_rows + p.BM - 1) / p.BM);
         // one full wave of resident blocks (2 per CU fit by LDS/VGPR), at most 256 chunks
-        int want_chunks = (2 * ix->n_cu) / p.n_qtiles;
-        if (want_chunks < 1) want_chunks = 1;
-        if (want_chunks > 256) want_chunks = 256;
-        if (want_chunks > p.n_row_tiles) want_chunks = p.n_row_tiles;
-        p.tiles_per_chunk = (p.n_row_tiles + want_chunks - 1) / want_chunks;
-        p.n_chunks = (p.n_row_tiles + p.tiles_per_chunk - 1) / p.tiles_per_chunk;
+        plan_chunks(ix->n_rows, p.BM, 2 * ix->n_cu / p.n_qtiles, 256, &p.n_row_tiles, &p.tiles_per_chunk, &p.n_chunks);
     }
     p.ws_q = ((size_t)p.Qpad * ix->dim * 4 + 255) & ~(size_t)255;
     p.ws_partial = ((size_t)p.n_chunks * p.Qpad * k * 8 + 255) & ~(size_t)255;
     p.ws_total = p.ws_q + p.ws_partial;
     return p;
-}
-
-template <int NQ, bool P16>
-static int launch_stream(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
-                         const int32_t* eo, u64* partial, hipStream_t st) {
-    ScopedTimer tm(T_SEARCH_KERNEL, st);
-    hipLaunchKernelGGL((stream_search_kernel<NQ, P16>), dim3(p.n_chunks), dim3(ST_ROWS), p.smem, st, (const void*)ix->rows,
-                       ix->n_rows, ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk,
-                       partial);
-    ICREC_HIP(hipGetLastError());
-    return ICREC_OK;
-}
-
-template <class Cfg, bool EMIT, bool P16>
-static int launch_search(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
-                         const int32_t* eo, u64* partial, float* scores_out, hipStream_t st,
-                         const int* run_flag = nullptr) {
-    auto kern = search_kernel<Cfg, EMIT, P16 ? 1 : 0>;
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc_;
-    const int grid = p.n_chunks * p.n_qtiles;
-    {
-        ScopedTimer tm(run_flag == nullptr ? T_SEARCH_KERNEL : T_SEARCH_FALLBACK, st);  // the guarded pass has its own slot
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), p.smem, st, (const void*)ix->rows, (const void*)nullptr,
-                           ix->n_rows, ix->dim, (const void*)qn, (const void*)nullptr, p.Qpad, Q, k, ei, eo,
-                           (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk, p.n_qtiles, partial, scores_out,
-                           run_flag);
-    }
-    ICREC_HIP(hipGetLastError());
-    return ICREC_OK;
 }
 
 // Workspace of the filter + verify path: [qn fp32 | q hi | q lo | flag | candidate keys | partial lists (filter pass,
@@ -1091,17 +1060,11 @@ static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& ex
     // which is the faster one there anyway (measured at 49,688 rows, Q = 1,024, k = 100: staged filter 2.5 ms, exact 1.5 ms)
     if (f.resident && SearchSmem<CfgRes, 3>::bytes(f.kp) > 160 * 1024) f.use = false;
     if (!f.use) { f.ws_total = 0; return f; }
-    const int BMf = f.resident ? CfgRes::BM : CfgFilter::BM;
     f.n_qtiles = (Q + CfgFilter::BN - 1) / CfgFilter::BN;  // 64 queries per tile in both forms
     f.Qpad = f.n_qtiles * CfgFilter::BN;
-    f.n_row_tiles = (int)((ix->n_rows + BMf - 1) / BMf);
     // staged form: two 4-wave blocks per CU; resident form: one 8-wave block per CU (its query planes take 96 KB)
-    int want_chunks = ((f.resident ? 1 : 2) * ix->n_cu) / f.n_qtiles;
-    if (want_chunks < 1) want_chunks = 1;
-    if (want_chunks > 256) want_chunks = 256;
-    if (want_chunks > f.n_row_tiles) want_chunks = f.n_row_tiles;
-    f.tiles_per_chunk = (f.n_row_tiles + want_chunks - 1) / want_chunks;
-    f.n_chunks = (f.n_row_tiles + f.tiles_per_chunk - 1) / f.tiles_per_chunk;
+    plan_chunks(ix->n_rows, f.resident ? CfgRes::BM : CfgFilter::BM, (f.resident ? 1 : 2) * ix->n_cu / f.n_qtiles, 256,
+                &f.n_row_tiles, &f.tiles_per_chunk, &f.n_chunks);
     f.smem = f.resident ? SearchSmem<CfgRes, 3>::bytes(f.kp) : SearchSmem<CfgFilter, 2>::bytes(f.kp);
     const int qpad_max = f.Qpad > exact.Qpad ? f.Qpad : exact.Qpad;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -1115,8 +1078,8 @@ static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& ex
     return f;
 }
 
-static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei, const int32_t* eo, int64_t* out_idx,
-                      float* out_score, u64* out_keys, float* scores_out, void* ws, size_t ws_bytes, hipStream_t st);
+static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
+                        const int32_t* eo, u64* partial, float* scores_out, const int* run_flag, hipStream_t st);
 
 // Filter (f16x3 MFMA, approximate) -> merge -> verify (exact chains on the candidates) -> exact search that runs
 // only if some query could not be proven.  Same outputs, bit for bit, as the exact search.
@@ -1158,29 +1121,61 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
     ICREC_HIP(hipGetLastError());
     hipLaunchKernelGGL(merge_kernel<4>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, f.n_chunks, f.Qpad, Q, f.kp,
                        (int64_t*)nullptr, (float*)nullptr, cand, (const int*)nullptr);
-    const bool h = rows_are_bf16(ix);
-    if (h)
-        hipLaunchKernelGGL(verify_kernel<true>, dim3((Q + 3) / 4), dim3(256), 0, st, (const void*)ix->rows, ix->dim, qn, cand, Q,
-                           f.kp, k, (uint32_t)ix->row_offset, filter_eps(ix->dim), out_idx, out_score, out_keys, flag);
-    else
-        hipLaunchKernelGGL(verify_kernel<false>, dim3((Q + 3) / 4), dim3(256), 0, st, (const void*)ix->rows, ix->dim, qn, cand, Q,
-                           f.kp, k, (uint32_t)ix->row_offset, filter_eps(ix->dim), out_idx, out_score, out_keys, flag);
+    hipLaunchKernelGGL((rows_are_bf16(ix) ? verify_kernel<true> : verify_kernel<false>), dim3((Q + 3) / 4), dim3(256), 0,
+                       st, (const void*)ix->rows, ix->dim, qn, cand, Q, f.kp, k, (uint32_t)ix->row_offset,
+                       filter_eps(ix->dim), out_idx, out_score, out_keys, flag);
     ICREC_HIP(hipGetLastError());
     // exact pass: every workgroup returns at once unless verify raised the flag
-    int rc;
-    if (h)
-        rc = ex.variant == 0   ? launch_search<CfgBig, false, true>(ix, ex, qn, Q, k, ei, eo, partial, nullptr, st, flag)
-             : ex.variant == 1 ? launch_search<CfgMid, false, true>(ix, ex, qn, Q, k, ei, eo, partial, nullptr, st, flag)
-                               : launch_search<CfgSmall, false, true>(ix, ex, qn, Q, k, ei, eo, partial, nullptr, st, flag);
-    else
-        rc = ex.variant == 0   ? launch_search<CfgBig, false, false>(ix, ex, qn, Q, k, ei, eo, partial, nullptr, st, flag)
-             : ex.variant == 1 ? launch_search<CfgMid, false, false>(ix, ex, qn, Q, k, ei, eo, partial, nullptr, st, flag)
-                               : launch_search<CfgSmall, false, false>(ix, ex, qn, Q, k, ei, eo, partial, nullptr, st, flag);
-    if (rc != ICREC_OK) return rc;
+    if (int rc = launch_exact(ix, ex, qn, Q, k, ei, eo, partial, nullptr, flag, st)) return rc;
     hipLaunchKernelGGL(merge_kernel<4>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, ex.n_chunks, ex.Qpad, Q, k, out_idx,
                        out_score, out_keys, (const int*)flag);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
+}
+
+// The exact search of plan p over the index rows (fp32 or bf16): partial lists, or every score into scores_out.  run_flag:
+// the guarded pass of the filter path, which has a timer slot of its own.  (Kernel tables: bf16 rows first.)
+static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
+                        const int32_t* eo, u64* partial, float* scores_out, const int* run_flag, hipStream_t st) {
+    using SearchFn = decltype(&search_kernel<CfgBig, false, 0>);
+    static const SearchFn lists[2][3] = {
+        {search_kernel<CfgBig, false, 1>, search_kernel<CfgMid, false, 1>, search_kernel<CfgSmall, false, 1>},
+        {search_kernel<CfgBig, false, 0>, search_kernel<CfgMid, false, 0>, search_kernel<CfgSmall, false, 0>}};
+    static const decltype(&stream_search_kernel<1, false>) stream[4][2] = {  // NQ = 1, 2, 4, 8
+        {stream_search_kernel<1, true>, stream_search_kernel<1, false>},
+        {stream_search_kernel<2, true>, stream_search_kernel<2, false>},
+        {stream_search_kernel<4, true>, stream_search_kernel<4, false>},
+        {stream_search_kernel<8, true>, stream_search_kernel<8, false>}};
+    static const SearchFn scores[2][3] = {
+        {search_kernel<CfgBig, true, 1>, search_kernel<CfgMid, true, 1>, search_kernel<CfgSmall, true, 1>},
+        {search_kernel<CfgBig, true, 0>, search_kernel<CfgMid, true, 0>, search_kernel<CfgSmall, true, 0>}};
+    const int r = rows_are_bf16(ix) ? 0 : 1;
+    if (p.variant == 3) {
+        const int nq = p.BN == 1 ? 0 : p.BN == 2 ? 1 : p.BN == 4 ? 2 : 3;
+        const size_t smem = nq == 0 ? StreamSmem<1>::bytes(k) : nq == 1 ? StreamSmem<2>::bytes(k)
+                            : nq == 2 ? StreamSmem<4>::bytes(k) : StreamSmem<8>::bytes(k);
+        ScopedTimer tm(T_SEARCH_KERNEL, st);
+        hipLaunchKernelGGL(stream[nq][r], dim3(p.n_chunks), dim3(ST_ROWS), smem, st, (const void*)ix->rows, ix->n_rows,
+                           ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk, partial);
+    } else {
+        const SearchFn kern = (scores_out ? scores : lists)[r][p.variant];
+        if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc_;
+        ScopedTimer tm(run_flag == nullptr ? T_SEARCH_KERNEL : T_SEARCH_FALLBACK, st);
+        hipLaunchKernelGGL(kern, dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st, (const void*)ix->rows,
+                           (const void*)nullptr, ix->n_rows, ix->dim, (const void*)qn, (const void*)nullptr, p.Qpad, Q, k, ei,
+                           eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk, p.n_qtiles, partial, scores_out,
+                           run_flag);
+    }
+    ICREC_HIP(hipGetLastError());
+    return ICREC_OK;
+}
+static_assert(CfgBig::THREADS == CfgMid::THREADS && CfgMid::THREADS == CfgSmall::THREADS, "launch_exact: one block size");
+
+// k-way merge of n_lists sorted lists of k keys per query (keys[list][q_stride][k]): 4 lists per lane up to 256 lists
+static void launch_merge(const u64* keys, int n_lists, int q_stride, int Q, int k, int64_t* out_idx, float* out_score,
+                         u64* out_keys, hipStream_t st) {
+    hipLaunchKernelGGL((n_lists <= 256 ? merge_kernel<4> : merge_kernel<16>), dim3((Q + 3) / 4), dim3(256), 0, st, keys,
+                       n_lists, q_stride, Q, k, out_idx, out_score, out_keys, (const int*)nullptr);
 }
 
 static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei, const int32_t* eo, int64_t* out_idx,
@@ -1213,32 +1208,13 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
     u64* partial = reinterpret_cast<u64*>(reinterpret_cast<char*>(ws) + p.ws_q);
     hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3((p.Qpad + 3) / 4), dim3(256), 0, st, q, (void*)qn, (int64_t)Q,
                        (int64_t)p.Qpad, ix->dim, 1e-12f, p.variant == 3 ? p.Qpad : 0);
-    int rc;
-#define ICREC_SEARCH_DISPATCH(EMIT, P16)                                                                            \
-    (p.variant == 0   ? launch_search<CfgBig, EMIT, P16>(ix, p, qn, Q, k, ei, eo, partial, scores_out, st)          \
-     : p.variant == 1 ? launch_search<CfgMid, EMIT, P16>(ix, p, qn, Q, k, ei, eo, partial, scores_out, st)          \
-                      : launch_search<CfgSmall, EMIT, P16>(ix, p, qn, Q, k, ei, eo, partial, scores_out, st))
-    if (p.variant == 3) {
-        const bool h = rows_are_bf16(ix);
-#define ICREC_STREAM_DISPATCH(NQ) \
-    (h ? launch_stream<NQ, true>(ix, p, qn, Q, k, ei, eo, partial, st) : launch_stream<NQ, false>(ix, p, qn, Q, k, ei, eo, partial, st))
-        rc = p.BN == 1 ? ICREC_STREAM_DISPATCH(1) : p.BN == 2 ? ICREC_STREAM_DISPATCH(2) : p.BN == 4 ? ICREC_STREAM_DISPATCH(4)
-                                                                                                   : ICREC_STREAM_DISPATCH(8);
-#undef ICREC_STREAM_DISPATCH
-    } else if (rows_are_bf16(ix)) rc = scores_out ? ICREC_SEARCH_DISPATCH(true, true) : ICREC_SEARCH_DISPATCH(false, true);
-    else rc = scores_out ? ICREC_SEARCH_DISPATCH(true, false) : ICREC_SEARCH_DISPATCH(false, false);
-#undef ICREC_SEARCH_DISPATCH
-    if (rc != ICREC_OK) return rc;
+    if (int rc = launch_exact(ix, p, qn, Q, k, ei, eo, partial, scores_out, nullptr, st)) return rc;
     if (out_idx || out_keys) {
         if (Q <= 4 && p.n_chunks <= 256 && (int64_t)p.n_chunks * k <= MERGE_BLOCK_KEYS)
             hipLaunchKernelGGL(merge_block_kernel, dim3(Q), dim3(256), 0, st, partial, p.n_chunks, p.Qpad, Q, k, out_idx,
                                out_score, out_keys);
-        else if (p.n_chunks <= 256)
-            hipLaunchKernelGGL(merge_kernel<4>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, p.n_chunks, p.Qpad, Q, k,
-                               out_idx, out_score, out_keys);
         else
-            hipLaunchKernelGGL(merge_kernel<16>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, p.n_chunks, p.Qpad, Q, k,
-                               out_idx, out_score, out_keys);
+            launch_merge(partial, p.n_chunks, p.Qpad, Q, k, out_idx, out_score, out_keys, st);
         ICREC_HIP(hipGetLastError());
     }
     return ICREC_OK;
@@ -1348,18 +1324,18 @@ int icrec_index_create_ex(const float* rows_dev, int64_t n_rows, int32_t dim, in
     ix->n_rows = n_rows; ix->dim = dim; ix->row_offset = row_offset; ix->device = device; ix->storage = storage;
     ix->n_cu = prop.multiProcessorCount;
     ix->stream_max_q = stream_max_q_from_env();
+    auto fail = [&]() {  // a hipMalloc failed: free what the index holds so far
+        icrec_index_destroy(reinterpret_cast<icrec_index*>(ix));
+        return ICREC_ENOMEM;
+    };
     const size_t bytes = (size_t)n_rows * dim * (rows16 ? 2 : 4);
     hipError_t e = hipMalloc(&ix->rows, bytes);
     if (e != hipSuccess) {
-        delete ix;
         set_error("icrec_index_create: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-        return ICREC_ENOMEM;
+        return fail();
     }
-    const dim3 grid((unsigned)((n_rows + 3) / 4));
-    if (rows16)
-        hipLaunchKernelGGL(normalize_rows_kernel<true>, grid, dim3(256), 0, 0, rows_dev, ix->rows, n_rows, n_rows, dim, 1e-12f);
-    else
-        hipLaunchKernelGGL(normalize_rows_kernel<false>, grid, dim3(256), 0, 0, rows_dev, ix->rows, n_rows, n_rows, dim, 1e-12f);
+    hipLaunchKernelGGL((rows16 ? normalize_rows_kernel<true> : normalize_rows_kernel<false>), dim3((unsigned)((n_rows + 3) / 4)),
+                       dim3(256), 0, 0, rows_dev, ix->rows, n_rows, n_rows, dim, 1e-12f, 0);
     ICREC_HIP(hipGetLastError());
     const char* res_env = getenv("ICREC_FILTER_RESIDENT");  // "0": staged form; a number > 1: row limit of the resident form (A/B)
     const int64_t res_max = res_env && atoll(res_env) > 1 ? atoll(res_env) : RES_MAX_ROWS;
@@ -1368,31 +1344,23 @@ int icrec_index_create_ex(const float* rows_dev, int64_t n_rows, int32_t dim, in
         ix->frag_row_tiles = ((n_rows + CfgRes::BM - 1) / CfgRes::BM) * (CfgRes::BM / 32);
         const int64_t n_frag = ix->frag_row_tiles * RES_KS;
         if (hipMalloc(&ix->frag, (size_t)n_frag * 2 * WT_FRAG * sizeof(_Float16)) != hipSuccess) {
-            hipFree(ix->rows);
-            delete ix;
             set_error("icrec_index_create: hipMalloc of the filter fragments (%zu bytes) failed", (size_t)n_frag * 2 * WT_FRAG * 2);
-            return ICREC_ENOMEM;
+            return fail();
         }
-        if (rows16)  // fragments of the ROUNDED rows: the filter then approximates exactly what the exact pass computes
-            hipLaunchKernelGGL(pack_rows_kernel<true>, dim3(4096), dim3(256), 0, 0, (const void*)ix->rows, n_rows, dim, n_frag, ix->frag);
-        else
-            hipLaunchKernelGGL(pack_rows_kernel<false>, dim3(4096), dim3(256), 0, 0, (const void*)ix->rows, n_rows, dim, n_frag, ix->frag);
+        // fragments of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
+        hipLaunchKernelGGL((rows16 ? pack_rows_kernel<true> : pack_rows_kernel<false>), dim3(4096), dim3(256), 0, 0,
+                           (const void*)ix->rows, n_rows, dim, n_frag, ix->frag);
         ICREC_HIP(hipGetLastError());
     } else if (with_planes) {
         const size_t n = (size_t)n_rows * dim;
         hipError_t e1 = hipMalloc(&ix->plane_hi, n * 2), e2 = hipMalloc(&ix->plane_lo, n * 2);
         if (e1 != hipSuccess || e2 != hipSuccess) {
-            hipFree(ix->plane_hi); hipFree(ix->plane_lo); hipFree(ix->rows);
-            delete ix;
             set_error("icrec_index_create: hipMalloc of the filter planes (2 x %zu bytes) failed", n * 2);
-            return ICREC_ENOMEM;
+            return fail();
         }
-        if (rows16)  // planes of the ROUNDED rows: the filter then approximates exactly what the exact pass computes
-            hipLaunchKernelGGL(split_queries_kernel<true>, dim3(4096), dim3(256), 0, 0, (const void*)ix->rows, n, ix->plane_hi,
-                               ix->plane_lo, (int*)nullptr);
-        else
-            hipLaunchKernelGGL(split_queries_kernel<false>, dim3(4096), dim3(256), 0, 0, (const void*)ix->rows, n, ix->plane_hi,
-                               ix->plane_lo, (int*)nullptr);
+        // planes of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
+        hipLaunchKernelGGL((rows16 ? split_queries_kernel<true> : split_queries_kernel<false>), dim3(4096), dim3(256), 0, 0,
+                           (const void*)ix->rows, n, ix->plane_hi, ix->plane_lo, (int*)nullptr);
         ICREC_HIP(hipGetLastError());
     }
     ICREC_HIP(hipStreamSynchronize(0));
@@ -1511,14 +1479,8 @@ int icrec_merge_topk(const uint64_t* keys_dev, int32_t n_lists, int32_t n_querie
     ICREC_REQUIRE(n_lists >= 1 && n_lists <= MERGE_MAX_LISTS, "icrec_merge_topk: n_lists must be in [1, %d]", MERGE_MAX_LISTS);
     ICREC_REQUIRE(n_queries >= 1 && k >= 1 && k <= ICREC_MAX_K, "icrec_merge_topk: bad n_queries/k");
     ICREC_HIP(hipSetDevice(device));
-    if (n_lists <= 256)
-        hipLaunchKernelGGL(merge_kernel<4>, dim3((n_queries + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const u64*>(keys_dev), n_lists, n_queries, n_queries, k, out_idx_dev,
-                           out_score_dev, (u64*)nullptr);
-    else
-        hipLaunchKernelGGL(merge_kernel<16>, dim3((n_queries + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const u64*>(keys_dev), n_lists, n_queries, n_queries, k, out_idx_dev,
-                           out_score_dev, (u64*)nullptr);
+    launch_merge(reinterpret_cast<const u64*>(keys_dev), n_lists, n_queries, n_queries, k, out_idx_dev, out_score_dev,
+                 nullptr, (hipStream_t)stream);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
 }
