@@ -90,8 +90,8 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
 }
 
 // ---------------------------------------------------------------- residual + LN (tf:292, tf:350)
-// x <- LN(a + x); `a` already holds dense(.) + bias.
-template <int H, bool SPLIT>
+// x <- LN(a + x); `a` already holds dense(.) + bias.  f32 mode only (f16x3: ln_wt_kernel and the fused kernels).
+template <int H>
 __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a, float* __restrict__ x, int T,
                                                      const float* __restrict__ g, const float* __restrict__ b,
                                                      float eps, _Float16* __restrict__ xh,
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a
         const int i = lane + 64 * j;
         v[j] = a[(size_t)t * H + i] + x[(size_t)t * H + i];
     }
-    ln_row<H, SPLIT>(v, g, b, eps, x + (size_t)t * H, xh + (size_t)t * H, xl + (size_t)t * H, lane);
+    ln_row<H, false>(v, g, b, eps, x + (size_t)t * H, xh + (size_t)t * H, xl + (size_t)t * H, lane);
 }
 
 // ---------------------------------------------------------------- GEMM: out = A . W^T + bias [, GELU]
@@ -160,31 +160,31 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void linear_kernel(const float* __
 constexpr int DH = 32;
 constexpr int LDQ = 36;  // K LDS row stride (even/odd split layout, like the GEMM tiles)
 
-// One launch per length bucket: NKT = max 32-key tiles (1, 2, 4, 8, 16), WAVES = query blocks per
-// workgroup.  A workgroup whose sequence belongs to another bucket exits at once, so short
+// One launch per length bucket: NKT = max 32-key tiles (1, 2, 4, 8, 16), and as many waves, one per 32-row query
+// block.  A workgroup whose sequence belongs to another bucket exits at once, so short
 // sequences run with the LDS footprint / occupancy of their own bucket even in a mixed batch.
 // K and V of the (sequence, head) live in LDS; each wave's 32 query rows come straight from
 // global memory into the B-operand registers.  Output: the fp32 context rows (`ctx`; ch / cl unused).
-template <int NKT, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void attention_kernel(const float* __restrict__ qkv,
-                                                               const int32_t* __restrict__ cu, int heads, int H,
-                                                               float scale_log2e, float* __restrict__ ctx,
-                                                               _Float16* __restrict__ ch, _Float16* __restrict__ cl) {
+template <int NKT>
+__global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __restrict__ qkv,
+                                                             const int32_t* __restrict__ cu, int heads, int H,
+                                                             float scale_log2e, float* __restrict__ ctx,
+                                                             _Float16* __restrict__ ch, _Float16* __restrict__ cl) {
     __shared__ __attribute__((aligned(16))) float Ks[NKT * 32 * LDQ];
     __shared__ __attribute__((aligned(16))) float Vs[NKT * 32 * DH];
-    __shared__ float Ls[WAVES * 32];
+    __shared__ float Ls[NKT * 32];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = blockIdx.x / heads, hd = blockIdx.x % heads;
     const int t0 = cu[s], L = cu[s + 1] - t0;
     const int nkt = (L + 31) >> 5;
     if (nkt > NKT || (NKT > 1 && nkt <= NKT / 2)) return;  // another bucket's sequence
-    const int qb0 = blockIdx.y * WAVES;
+    const int qb0 = blockIdx.y * NKT;
     if (qb0 >= nkt) return;
     const int ld = 3 * H;
 
     // stage K (even/odd split) and V; rows past L are clamped (masked below / never stored)
-    for (int id = tid; id < nkt * 32 * 8; id += WAVES * 64) {
+    for (int id = tid; id < nkt * 32 * 8; id += NKT * 64) {
         const int row = id >> 3, c = id & 7;
         const int rr = row < L ? row : L - 1;
         const float* src = qkv + (size_t)(t0 + rr) * ld + hd * DH + c * 4;
@@ -389,15 +389,6 @@ __global__ __launch_bounds__(1024) void seq_order_kernel(const int32_t* __restri
 // accumulator register e = 8s + j holds — on both operands.
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void split8(const float (&x)[8], half8& hi, half8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const _Float16 a = (_Float16)x[j];
-        hi[j] = a;
-        lo[j] = (_Float16)((x[j] - (float)a) * LO_SCALE);
-    }
-}
-
 // ds_read_b64_tr_b16 (gfx950): all 64 lanes must be active; `p` is this lane's Mechanism address (8-byte aligned)
 __device__ __forceinline__ half4 lds_read_tr(const _Float16* p) {
     typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
@@ -407,8 +398,8 @@ __device__ __forceinline__ half4 lds_read_tr(const _Float16* p) {
 
 // nlo: sequences of nlo < nkt <= NKT key tiles belong to this launch (the others' workgroups exit at once).
 // Output: the context as f16 hi/lo planes (`ch` / `cl`; ctx unused).
-template <int NKT, int WAVES>
-__global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void attention_x3_kernel(const float* __restrict__ qkv,
+template <int NKT>  // NKT waves, one per 32-row query block
+__global__ __launch_bounds__(NKT * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void attention_x3_kernel(const float* __restrict__ qkv,
                                                                   const int32_t* __restrict__ cu, int heads, int H,
                                                                   float scale_log2e, float* __restrict__ ctx,
                                                                   _Float16* __restrict__ ch, _Float16* __restrict__ cl,
@@ -435,10 +426,10 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
     // half covers 4 rows of 64 B = every bank once).
     __shared__ __attribute__((aligned(16))) _Float16 Vh[NKT * 32 * 32];
     __shared__ __attribute__((aligned(16))) _Float16 Vl[NKT * 32 * 32];
-    __shared__ float Ls[WAVES * 32];
+    __shared__ float Ls[NKT * 32];
     // Plane output: every wave parks its 32 x 32 output tile (hi | lo) on the K planes once all waves have left them
-    // (second barrier) and writes it out 16 B per lane - 4 store instructions instead of 32 two-byte ones.
-    static_assert(WAVES * 2 * 32 * 32 <= 2 * NKT * 32 * 32, "the output tiles reuse the K planes");
+    // (second barrier) and writes it out 16 B per lane - 4 store instructions instead of 32 two-byte ones.  The NKT
+    // tiles fill the K planes exactly.
     _Float16* const Ob = Kbuf;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -447,7 +438,7 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
     const int t0 = cu[s], L = cu[s + 1] - t0;
     const int nkt = (L + 31) >> 5;
     if (nkt > NKT || nkt <= nlo) return;  // another bucket's sequence
-    const int qb0 = blockIdx.y * WAVES;
+    const int qb0 = blockIdx.y * NKT;
     if (qb0 >= nkt) return;
     const int ld = 3 * H;
 
@@ -470,12 +461,12 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
         }
     }
     // K/V staging: all of this thread's loads are issued before the first one is consumed
-    constexpr int STG = NKT * 32 * 8 / (WAVES * 64);  // = 4 for every bucket (WAVES == NKT)
-    static_assert(NKT * 32 * 8 % (WAVES * 64) == 0, "staging: whole rounds");
+    constexpr int STG = NKT * 32 * 8 / (NKT * 64);  // = 4 for every bucket
+    static_assert(NKT * 32 * 8 % (NKT * 64) == 0, "staging: whole rounds");
     f32x4 kreg[STG], vreg[STG];
 #pragma unroll
     for (int it = 0; it < STG; ++it) {
-        const int id = tid + it * WAVES * 64;
+        const int id = tid + it * NKT * 64;
         const int key = id >> 3, c = id & 7;  // c: 4-dim group
         const int rr = key < L ? key : L - 1;
         const float* src = qkv + (size_t)(t0 + rr) * ld + hd * DH + c * 4;
@@ -484,7 +475,7 @@ __global__ __launch_bounds__(WAVES * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void
     }
 #pragma unroll
     for (int it = 0; it < STG; ++it) {
-        const int id = tid + it * WAVES * 64;
+        const int id = tid + it * NKT * 64;
         if (id < nkt * 32 * 8) {
             const int key = id >> 3, c = id & 7;
             half4 khi, klo, vhi, vlo;
@@ -859,7 +850,7 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
 
 // The attention length buckets, in launch order: 9-16 key tiles first (257-512 tokens: the longest bucket starts first),
 // then from the shortest up.  f16x3 batches take 5-8 key tiles in two buckets, single sequences and fp32 in one.
-// Bucket k serves [ATT_LO[k], ATT_HI[k]] key tiles with the kernel <NKT = WAVES = ATT_HI[k]>.
+// Bucket k serves [ATT_LO[k], ATT_HI[k]] key tiles with the kernel <NKT = ATT_HI[k]> (NKT waves per workgroup).
 enum AttBucket { ATT_9_16, ATT_1, ATT_2, ATT_3_4, ATT_5_6, ATT_7_8, ATT_5_8, ATT_N };
 constexpr int ATT_LO[ATT_N] = {9, 1, 2, 3, 5, 7, 5}, ATT_HI[ATT_N] = {16, 1, 2, 4, 6, 8, 8};
 
@@ -878,15 +869,15 @@ static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBu
             continue;
         const dim3 grid(n_seqs * c.heads, 1), block(ATT_HI[k] * 64);
         if constexpr (X3) {
-            static const decltype(&attention_x3_kernel<1, 1>) kern[ATT_N] = {
-                attention_x3_kernel<16, 16>, attention_x3_kernel<1, 1>, attention_x3_kernel<2, 2>, attention_x3_kernel<4, 4>,
-                attention_x3_kernel<6, 6>, attention_x3_kernel<8, 8>, attention_x3_kernel<8, 8>};
+            static const decltype(&attention_x3_kernel<1>) kern[ATT_N] = {
+                attention_x3_kernel<16>, attention_x3_kernel<1>, attention_x3_kernel<2>, attention_x3_kernel<4>,
+                attention_x3_kernel<6>, attention_x3_kernel<8>, attention_x3_kernel<8>};
             hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx, b.ch, b.cl, order,
                                ATT_LO[k] - 1);
         } else {  // (f16x3 batches only split 5-8 key tiles)
-            static const decltype(&attention_kernel<1, 1>) kern[ATT_N] = {
-                attention_kernel<16, 16>, attention_kernel<1, 1>, attention_kernel<2, 2>, attention_kernel<4, 4>,
-                nullptr, nullptr, attention_kernel<8, 8>};
+            static const decltype(&attention_kernel<1>) kern[ATT_N] = {
+                attention_kernel<16>, attention_kernel<1>, attention_kernel<2>, attention_kernel<4>, nullptr, nullptr,
+                attention_kernel<8>};
             hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx, b.ch, b.cl);
         }
     }
@@ -1102,7 +1093,7 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
             // workgroups of feature block 0, to xh / xl): one graph node fewer per layer
             const LayerW& Lp = e->layers[l - 1];
             const int nbn = 3 * H / 64;
-            hipLaunchKernelGGL((wt_linear_lnin_kernel<0, true>), dim3(((r.n + 31) / 32) * nbn), dim3(256), 0, r.st,
+            hipLaunchKernelGGL((wt_linear_lnin_kernel<0>), dim3(((r.n + 31) / 32) * nbn), dim3(256), 0, r.st,
                                (const float*)(b.t1 + (size_t)r.r0 * H), r.n, Lp.g2, Lp.b2n, c.ln_eps, xhr, xlr, L.Wqkv_p,
                                3 * H, L.bqkv, qkvr, (_Float16*)nullptr, (_Float16*)nullptr, nbn);
         } else {
@@ -1131,7 +1122,7 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
         launch_wt_linear<2>(chr, clr, r.n, H, L.Wo_p, H, L.bo, t1r, xhr, xlr, r.st, r.small);  // residual: x planes
         if (r.fold) {  // LayerNorm + FFN-up in one node (wt_linear_lnin_kernel)
             const int nbn = I / 64;
-            hipLaunchKernelGGL((wt_linear_lnin_kernel<1, true>), dim3(((r.n + 31) / 32) * nbn), dim3(256), 0, r.st,
+            hipLaunchKernelGGL((wt_linear_lnin_kernel<1>), dim3(((r.n + 31) / 32) * nbn), dim3(256), 0, r.st,
                                (const float*)t1r, r.n, L.g1, L.b1n, c.ln_eps, xhr, xlr, L.W1_p, I, L.b1, (float*)nullptr,
                                hhr, hlr, nbn);
         } else {
@@ -1181,14 +1172,14 @@ static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev,
         launch_linear<false>(b.x, T, H, L.Wqkv, 3 * H, L.bqkv, b.qkv, st);
         launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
         launch_linear<false>(b.ctx, T, H, L.Wo, H, L.bo, b.t1, st);
-        hipLaunchKernelGGL((add_ln_kernel<HID, false>), dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g1, L.b1n,
+        hipLaunchKernelGGL(add_ln_kernel<HID>, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g1, L.b1n,
                            c.ln_eps, b.xh, b.xl);
         {
             ScopedTimer tm(T_FFN_UP, st);
             launch_linear<true>(b.x, T, H, L.W1, I, L.b1, b.h, st);
         }
         launch_linear<false>(b.h, T, I, L.W2, H, L.b2, b.t1, st);
-        hipLaunchKernelGGL((add_ln_kernel<HID, false>), dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g2, L.b2n,
+        hipLaunchKernelGGL(add_ln_kernel<HID>, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g2, L.b2n,
                            c.ln_eps, b.xh, b.xl);
     }
     return ICREC_OK;

@@ -42,6 +42,25 @@ __device__ __forceinline__ void gelu_split4(const f32x4& acc, const f32x4& bias,
     split4_prescaled(s, hi, lo);
 }
 
+// The epilogue store of four consecutive outputs of one token (acc in units of 2^-14): features feat .. feat+3 of row
+// tok of an [T, N] output.  EPI 0: out = acc * 2^-14 + bias, fp32;  EPI 1: erf-GELU of it as the two planes oh / ol.
+template <int EPI>
+__device__ __forceinline__ void wt_store4(const f32x4& acc, const f32x4& bias, int64_t tok, int N, int feat, float* out,
+                                          _Float16* oh, _Float16* ol) {
+    static_assert(EPI == 0 || EPI == 1, "epilogue: fp32 + bias or GELU planes");
+    if constexpr (EPI == 1) {
+        half4 hi, lo;
+        gelu_split4(acc, bias, hi, lo);
+        *reinterpret_cast<half4*>(oh + tok * N + feat) = hi;
+        *reinterpret_cast<half4*>(ol + tok * N + feat) = lo;
+    } else {
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = fmaf(acc[j], WT_UNSCALE, bias[j]);
+        *reinterpret_cast<f32x4*>(out + tok * N + feat) = v;
+    }
+}
+
 // ---------------------------------------------------------------- residual stream + LayerNorm of the f16x3 engine
 // In f16x3 mode the residual stream x lives in HBM ONLY as its two f16 planes (xh, xl: 16 x to 22 significant bits,
 // wt_gemm.h) — the planes every GEMM reads anyway.  The two LayerNorm sites of a layer (tf:292 attention output,
@@ -70,7 +89,6 @@ constexpr int LNT_ROW = 208;                        // bytes per tile row: 96 ha
 constexpr int LNT_TILE = 32 * LNT_ROW;              // one wave's tile
 constexpr int LNT_RED = 2 * 64 * 4 * 4;             // the two 4-partial exchanges: [2][64 tokens][4 waves] floats
 constexpr int LNT_PAR = 2 * 384 * 4;                // gamma, beta
-constexpr int LNT_BYTES = LNT_RED + 4 * LNT_TILE + LNT_PAR;   // 31,744 B
 
 __device__ __forceinline__ void lds_order() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
@@ -145,28 +163,6 @@ __device__ __forceinline__ void wt_res_rows_acc(Acc32 (&acc)[3][TTW], const ResR
                 }
             }
         lds_order();
-    }
-}
-
-// acc += r for the single-block waves of the small-batch kernels: 8-byte loads straight from global memory (a
-// handful of tokens: latency, not bandwidth).
-__device__ __forceinline__ void wt_res_add_direct(Acc32 (&acc)[1][1], int nt0, const float* __restrict__ bias,
-                                                  const _Float16* __restrict__ xh, const _Float16* __restrict__ xl,
-                                                  int N, int64_t m0, int64_t T) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int fi = 0; fi < 2; ++fi) {
-        const int feat = nt0 * 32 + fi * 16 + 4 * g;
-        const f32x4 b = *reinterpret_cast<const f32x4*>(bias + feat);
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-            int64_t tok = m0 + ti * 16 + c;
-            tok = tok < T ? tok : T - 1;
-            const half4 a = *reinterpret_cast<const half4*>(xh + tok * N + feat);
-            const half4 d = *reinterpret_cast<const half4*>(xl + tok * N + feat);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[0][0].t[fi][ti][j] = acc[0][0].t[fi][ti][j] + res_init_val(a[j], d[j], b[j]);
-        }
     }
 }
 
@@ -306,27 +302,24 @@ __device__ __forceinline__ void wt_ln_block(Acc32 (&acc)[3][TTW], int q, int tb,
     }
 }
 
-// The unfused form of the same LayerNorm (small batches; the unfused reference chain): planes(x) <- LN(a), `a` =
-// dense(.) + bias + residual as the EPI 2 GEMM wrote it.  16 threads per token: thread (q, g) sums its 24 values in
-// (i, fi, reg) order, the 16 partials are combined by shuffles in the fixed tree of wt_ln_block.
-__global__ __launch_bounds__(256) void ln_wt_kernel(const float* __restrict__ a, int T, const float* __restrict__ gam,
-                                                    const float* __restrict__ bet, float eps,
-                                                    _Float16* __restrict__ xh, _Float16* __restrict__ xl) {
-    const int tid = threadIdx.x, slot = tid & 15, q = slot >> 2, g = slot & 3;
-    int64_t tok = (int64_t)blockIdx.x * 16 + (tid >> 4);
-    const bool ok = tok < T;
-    tok = ok ? tok : (int64_t)T - 1;
+// The unfused form of the same LayerNorm at 16 threads per token, one token row `row` (fp32: dense(.) + bias + residual
+// as the EPI 2 GEMM wrote it): thread (q, g) - `base` is the lane of the token's first thread - sums its 24 values, features
+// q*96 + i*32 + fi*16 + 4g + reg, in (i, fi, reg) order, the 16 partials are combined by shuffles in the fixed tree of
+// wt_ln_block.  store(feat, hi, lo) takes the planes of the four features at feat, for each (i, fi) in that order.
+// ln_wt_kernel and the prologue of wt_linear_lnin_kernel both run it: identical bits.
+template <class Store>
+__device__ __forceinline__ void ln16_row(const float* row, const float* gam, const float* bet, float eps, int q, int g,
+                                         int base, Store store) {
     f32x4 v[3][2];
     float part = 0.0f;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int fi = 0; fi < 2; ++fi) {
-            v[i][fi] = *reinterpret_cast<const f32x4*>(a + tok * 384 + q * 96 + i * 32 + fi * 16 + 4 * g);
+            v[i][fi] = *reinterpret_cast<const f32x4*>(row + q * 96 + i * 32 + fi * 16 + 4 * g);
 #pragma unroll
             for (int j = 0; j < 4; ++j) part = part + v[i][fi][j];
         }
-    const int base = (tid & 63) & ~15;  // first lane of this token's 16 threads
     auto tree = [&](float p) {  // ((P0 + P1) + P2) + P3 with Pq = (part(q,0) + part(q,1)) + (part(q,2) + part(q,3))
         p = p + __shfl_xor(p, 1, 64);
         p = p + __shfl_xor(p, 2, 64);
@@ -360,11 +353,24 @@ __global__ __launch_bounds__(256) void ln_wt_kernel(const float* __restrict__ a,
 #pragma unroll
             for (int j = 0; j < 4; ++j) y[j] = fmaf(v[i][fi][j] * rstd, gm[j], bt[j]);
             split_act4(y, hi, lo);
-            if (ok) {
-                *reinterpret_cast<half4*>(xh + tok * 384 + feat) = hi;
-                *reinterpret_cast<half4*>(xl + tok * 384 + feat) = lo;
-            }
+            store(feat, hi, lo);
         }
+}
+
+// planes(x) <- LN(a), 16 tokens per workgroup (small batches; the unfused reference chain)
+__global__ __launch_bounds__(256) void ln_wt_kernel(const float* __restrict__ a, int T, const float* __restrict__ gam,
+                                                    const float* __restrict__ bet, float eps,
+                                                    _Float16* __restrict__ xh, _Float16* __restrict__ xl) {
+    const int tid = threadIdx.x, slot = tid & 15, q = slot >> 2, g = slot & 3;
+    const int64_t tok = (int64_t)blockIdx.x * 16 + (tid >> 4);
+    const bool ok = tok < T;
+    ln16_row(a + (ok ? tok : (int64_t)T - 1) * 384, gam, bet, eps, q, g, (tid & 63) & ~15,
+             [=](int feat, const half4& hi, const half4& lo) {
+                 if (ok) {
+                     *reinterpret_cast<half4*>(xh + tok * 384 + feat) = hi;
+                     *reinterpret_cast<half4*>(xl + tok * 384 + feat) = lo;
+                 }
+             });
 }
 
 constexpr int LN_LD = 388;  // floats per staged output row in LDS (+16 B: the 16-B accesses of consecutive tokens hit distinct banks)
@@ -374,11 +380,12 @@ constexpr int LN_LD = 388;  // floats per staged output row in LDS (+16 B: the 1
 // token slab staged through LDS.  Block = 4 waves; wave q owns NTW 32-feature blocks x TTW 32-token blocks.
 //   EPI 0: out fp32 [T, N] = acc * 2^-14 + bias           (QKV)
 //   EPI 1: erf-GELU (tf:336), result as f16 hi/lo planes   (FFN-up of small batches)
-//   EPI 2: residual + bias (planes rh / rl, row stride N) added to the accumulators after the K loop, out fp32 =
-//          acc * 2^-14: the LayerNorm input of attention-out / FFN-down for small batches (ln_wt_kernel follows)
-// <1, 1, 4, 1>: the small-batch FFN-up (weights four k-steps ahead; small batches and the remainder of a batch take
-// wt_linear_half_kernel for EPI 0 / 2): 32-token x 128-feature workgroups, latency-bound.  <3, 2, 1, EPI>: the 64-token x 384-feature form of the UNFUSED reference chain
-// (ICREC_FUSE=0: tests compare the fused kernels against it bit for bit).
+//   EPI 2: residual + bias (planes oh / ol, row stride 384) added to the accumulators after the K loop, out fp32 =
+//          acc * 2^-14: the LayerNorm input of attention-out / FFN-down (ln_wt_kernel follows)
+// Two forms: <1, 1, 4, 1>, the small-batch FFN-up (weights four k-steps ahead; small batches and the remainder of a batch
+// take wt_linear_half_kernel for EPI 0 / 2): 32-token x 128-feature workgroups, latency-bound.  <3, 2, 1, EPI>: the
+// 64-token x 384-feature form of the UNFUSED reference chain (ICREC_FUSE=0: tests compare the fused kernels against it
+// bit for bit); its EPI 0 / 2 results leave through an LDS stage.
 // Each lane holds 4 consecutive features of one token per register group: 16-B (fp32) / 8-B (planes) stores.
 template <int NTW, int TTW, int D, int EPI>
 __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __restrict__ Xh,
@@ -387,7 +394,9 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
                                                            const float* __restrict__ bias, float* __restrict__ out,
                                                            _Float16* __restrict__ oh, _Float16* __restrict__ ol,
                                                            int n_blocks_n) {
-    constexpr bool STAGED = (NTW == 3 && TTW == 2 && EPI != 1);  // results leave through an LDS stage, coalesced
+    static_assert((NTW == 1 && TTW == 1 && D == 4 && EPI == 1) || (NTW == 3 && TTW == 2 && D == 1),
+                  "the small-batch FFN-up <1, 1, 4, 1> or the batch form <3, 2, 1, EPI>");
+    constexpr bool STAGED = EPI != 1;  // results leave through an LDS stage, coalesced
     constexpr int SM = (STAGED && 32 * LN_LD * 4 > XRing<TTW>::BYTES) ? 32 * LN_LD * 4 : XRing<TTW>::BYTES;
     __shared__ __attribute__((aligned(16))) char smem[SM];
     const int lane = threadIdx.x & 63, q = wave_uniform(threadIdx.x >> 6), c = lane & 15, g = lane >> 4;
@@ -399,17 +408,12 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
     Acc32 acc[NTW][TTW];
     wt_kloop<NTW, TTW, D>(acc, Wp, nt0, K, Xh, Xl, m0, T, smem);  // ends with a barrier: the slab ring is free
     if constexpr (EPI == 2) {  // oh / ol carry the residual planes here: acc += r
-        if constexpr (NTW == 3 && TTW == 2) {
-            ResRows r0, r1;
-            wt_res_rows_load(r0, q, 0, oh + nb * 384, ol + nb * 384, m0, T);
-            wt_res_rows_load(r1, q, 1, oh + nb * 384, ol + nb * 384, m0, T);
-            wt_res_rows_acc<true, 2, 0>(acc, r0, q, bias + nb * 384, smem + q * LNT_TILE);
-            wt_res_rows_acc<true, 2, 1>(acc, r1, q, bias + nb * 384, smem + q * LNT_TILE);
-            __syncthreads();  // the private tiles become the output stage
-        } else {
-            static_assert(NTW == 1 && TTW == 1, "residual: 3 x 2 or 1 x 1 wave tiles");
-            wt_res_add_direct(acc, nt0, bias, oh, ol, N, m0, T);
-        }
+        ResRows r0, r1;
+        wt_res_rows_load(r0, q, 0, oh + nb * 384, ol + nb * 384, m0, T);
+        wt_res_rows_load(r1, q, 1, oh + nb * 384, ol + nb * 384, m0, T);
+        wt_res_rows_acc<true, 2, 0>(acc, r0, q, bias + nb * 384, smem + q * LNT_TILE);
+        wt_res_rows_acc<true, 2, 1>(acc, r1, q, bias + nb * 384, smem + q * LNT_TILE);
+        __syncthreads();  // the private tiles become the output stage
     }
     if constexpr (STAGED) {
         // [384 features x 32 tokens] per pass -> stage[token][feature] (16-B LDS writes), then 16-B chunks in flat
@@ -444,37 +448,22 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
             }
             if (tt == 0) __syncthreads();
         }
-        return;
-    }
-
+    } else {  // EPI 1: GELU planes, 8-byte stores straight from the accumulators
 #pragma unroll
-    for (int i = 0; i < NTW; ++i)
+        for (int i = 0; i < NTW; ++i)
 #pragma unroll
-        for (int fi = 0; fi < 2; ++fi) {
-            const int feat = (nt0 + i) * 32 + fi * 16 + 4 * g;
-            f32x4 b = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            if (EPI != 2) b = *reinterpret_cast<const f32x4*>(bias + feat);
+            for (int fi = 0; fi < 2; ++fi) {
+                const int feat = (nt0 + i) * 32 + fi * 16 + 4 * g;
+                const f32x4 b = *reinterpret_cast<const f32x4*>(bias + feat);
 #pragma unroll
-            for (int tt = 0; tt < TTW; ++tt)
+                for (int tt = 0; tt < TTW; ++tt)
 #pragma unroll
-                for (int ti = 0; ti < 2; ++ti) {
-                    const int64_t tok = m0 + tt * 32 + ti * 16 + c;
-                    if (tok < T) {
-                        if (EPI == 1) {
-                            half4 hi, lo;
-                            gelu_split4(acc[i][tt].t[fi][ti], b, hi, lo);
-                            *reinterpret_cast<half4*>(oh + tok * N + feat) = hi;
-                            *reinterpret_cast<half4*>(ol + tok * N + feat) = lo;
-                        } else {
-                            f32x4 v;
-#pragma unroll
-                            for (int j = 0; j < 4; ++j)
-                                v[j] = EPI == 2 ? acc[i][tt].t[fi][ti][j] * WT_UNSCALE : fmaf(acc[i][tt].t[fi][ti][j], WT_UNSCALE, b[j]);
-                            *reinterpret_cast<f32x4*>(out + tok * N + feat) = v;
-                        }
+                    for (int ti = 0; ti < 2; ++ti) {
+                        const int64_t tok = m0 + tt * 32 + ti * 16 + c;
+                        if (tok < T) wt_store4<EPI>(acc[i][tt].t[fi][ti], b, tok, N, feat, out, oh, ol);
                     }
-                }
-        }
+            }
+    }
 }
 
 // ---------------------------------------------------------------- resident activation image (fused FFN, QKV)
@@ -637,14 +626,14 @@ __global__ __launch_bounds__(256, 2) void wt_linear_half_kernel(const _Float16* 
 // request's LayerNorm nodes did 5 us of nothing else.  The two K = 384 GEMMs that CONSUME a LayerNorm's output (FFN-up
 // behind the attention-output LayerNorm, the next layer's QKV projection behind the FFN LayerNorm) read whole token rows
 // anyway, so every workgroup normalises its 32 rows itself: t1 rows (fp32: dense + bias + residual, as the EPI 2 GEMM
-// wrote them) -> ln_wt_kernel's arithmetic, thread for thread (16 threads per token, the same partial sums, the same
-// shuffle tree: identical bits) -> the planes go into a resident LDS image ([32][384] x 2, layout ffn_x_pos) and - from
-// the workgroups of feature block 0 only - to xh / xl, the residual of the next EPI 2 GEMM.  The weight ring's first four
-// k-steps are requested BEFORE the LayerNorm, so the L2 latency of the first fragments runs under it.  K loop: twelve
-// straight-line k-steps off the image, one 32 x 32 block per wave, per output the chain of wt_kloop (same bits as
-// wt_linear_kernel<1, 1, 4, EPI> on ln_wt_kernel's planes).  EPI 0: fp32 out + bias; EPI 1: erf-GELU planes.
+// wrote them) -> ln16_row, the LayerNorm of ln_wt_kernel (identical bits) -> the planes go into a resident LDS image
+// ([32][384] x 2, layout ffn_x_pos) and - from the workgroups of feature block 0 only - to xh / xl, the residual of the
+// next EPI 2 GEMM.  The weight ring's first eight k-steps are requested BEFORE the LayerNorm, so the L2 latency of the
+// first fragments runs under it.  K loop: twelve straight-line k-steps off the image, one 16-feature tile x 32 tokens
+// per wave (64 features per workgroup, as in wt_linear_half_kernel), per output the chain of wt_kloop (same bits as the
+// unfused GEMMs on ln_wt_kernel's planes).  EPI 0: fp32 out + bias; EPI 1: erf-GELU planes.
 constexpr int LNIN_XPLANE = 32 * 768;
-template <int EPI, bool HALF = false>  // HALF: a wave owns one 16-feature tile (64 features per workgroup) instead of a 32-feature block
+template <int EPI>
 __global__ __launch_bounds__(256, 2) void wt_linear_lnin_kernel(const float* __restrict__ a, int T,
                                                                 const float* __restrict__ gam,
                                                                 const float* __restrict__ bet, float eps,
@@ -659,26 +648,19 @@ __global__ __launch_bounds__(256, 2) void wt_linear_lnin_kernel(const float* __r
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mt = bid / n_blocks_n, nb = bid % n_blocks_n;
     const int64_t m0 = (int64_t)mt * 32;
-    const int ft = nb * 4 + wq;                       // HALF: 16-feature tile index
-    const int nt = HALF ? ft >> 1 : ft, hf = ft & 1;  // the 32-feature block; HALF: which half of it
+    const int ft = nb * 4 + wq, nt = ft >> 1, hf = ft & 1;  // 16-feature tile, its 32-feature block, which half
     const unsigned lo8 = lane * 8;
     constexpr int RD = 8;  // weight ring depth in k-steps: eight of the twelve are requested in front of the LayerNorm
-    WFrag w[RD][1];  // HALF: only [hf] of h / l is loaded and used
-    const _Float16* const wp1[1] = {Wp + wt_frag_off(nt, 0, KS1)};
+    const _Float16* const wp = Wp + wt_frag_off(nt, 0, KS1);
+    half8 wh[RD], wl[RD];
     auto w_ring_load = [&](int slot, int ks) {
-        if constexpr (HALF) {
-            const _Float16* p = wp1[0] + (size_t)ks * (4 * WT_FRAG) + (size_t)hf * (2 * WT_FRAG);
-            w[slot][0].h[0] = *reinterpret_cast<const half8*>(p + lo8);
-            w[slot][0].l[0] = *reinterpret_cast<const half8*>(p + WT_FRAG + lo8);
-        } else {
-            w_load<1>(w[slot], wp1, ks, lo8);
-        }
+        const _Float16* p = wp + (size_t)ks * (4 * WT_FRAG) + (size_t)hf * (2 * WT_FRAG);
+        wh[slot] = *reinterpret_cast<const half8*>(p + lo8);
+        wl[slot] = *reinterpret_cast<const half8*>(p + WT_FRAG + lo8);
     };
 #pragma unroll
     for (int d = 0; d < RD; ++d) w_ring_load(d, d);
-    f32x4 bv[2];
-#pragma unroll
-    for (int fi = 0; fi < 2; ++fi) bv[fi] = *reinterpret_cast<const f32x4*>(bias + nt * 32 + (HALF ? hf : fi) * 16 + 4 * g);
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + nt * 32 + hf * 16 + 4 * g);
     // ---- LayerNorm of the block's 32 rows: two passes of 16 tokens, ln_wt_kernel's thread mapping and order
     {
         const int slot = tid & 15, q = slot >> 2, gg = slot & 3;
@@ -686,60 +668,18 @@ __global__ __launch_bounds__(256, 2) void wt_linear_lnin_kernel(const float* __r
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass) {
             const int row = pass * 16 + (tid >> 4);
-            int64_t tok = m0 + row;
+            const int64_t tok = m0 + row;
             const bool ok = tok < T;
-            tok = ok ? tok : (int64_t)T - 1;
-            f32x4 v[3][2];
-            float part = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int fi = 0; fi < 2; ++fi) {
-                    v[i][fi] = *reinterpret_cast<const f32x4*>(a + tok * 384 + q * 96 + i * 32 + fi * 16 + 4 * gg);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) part = part + v[i][fi][j];
-                }
-            auto tree = [&](float p) {
-                p = p + __shfl_xor(p, 1, 64);
-                p = p + __shfl_xor(p, 2, 64);
-                const float p0 = __shfl(p, base, 64), p1 = __shfl(p, base + 4, 64), p2 = __shfl(p, base + 8, 64),
-                            p3 = __shfl(p, base + 12, 64);
-                return ((p0 + p1) + p2) + p3;
-            };
-            const float mean = tree(part) / 384.0f;
-            float sq = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int fi = 0; fi < 2; ++fi)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float d = v[i][fi][j] - mean;
-                        v[i][fi][j] = d;
-                        sq = fmaf(d, d, sq);
-                    }
-            const float var = tree(sq) / 384.0f;
-            const float rstd = 1.0f / sqrtf(var + eps);
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int fi = 0; fi < 2; ++fi) {
-                    const int feat = q * 96 + i * 32 + fi * 16 + 4 * gg;
-                    const f32x4 gm = *reinterpret_cast<const f32x4*>(gam + feat);
-                    const f32x4 bt = *reinterpret_cast<const f32x4*>(bet + feat);
-                    f32x4 y;
-                    half4 hi, lo;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) y[j] = fmaf(v[i][fi][j] * rstd, gm[j], bt[j]);
-                    split_act4(y, hi, lo);
-                    const int pos = ffn_x_pos(row, feat >> 3) + 8 * ((feat >> 2) & 1);
-                    *reinterpret_cast<half4*>(Xs + pos) = hi;
-                    *reinterpret_cast<half4*>(Xs + LNIN_XPLANE + pos) = lo;
-                    if (nb == 0 && ok) {
-                        *reinterpret_cast<half4*>(xh + tok * 384 + feat) = hi;
-                        *reinterpret_cast<half4*>(xl + tok * 384 + feat) = lo;
-                    }
-                }
+            ln16_row(a + (ok ? tok : (int64_t)T - 1) * 384, gam, bet, eps, q, gg, base,
+                     [=](int feat, const half4& hi, const half4& lo) {
+                         const int pos = ffn_x_pos(row, feat >> 3) + 8 * ((feat >> 2) & 1);
+                         *reinterpret_cast<half4*>(Xs + pos) = hi;
+                         *reinterpret_cast<half4*>(Xs + LNIN_XPLANE + pos) = lo;
+                         if (nb == 0 && ok) {
+                             *reinterpret_cast<half4*>(xh + tok * 384 + feat) = hi;
+                             *reinterpret_cast<half4*>(xl + tok * 384 + feat) = lo;
+                         }
+                     });
         }
     }
     __syncthreads();  // image resident
@@ -755,8 +695,7 @@ __global__ __launch_bounds__(256, 2) void wt_linear_lnin_kernel(const float* __r
             x.l[ti] = *reinterpret_cast<const half8*>(Xs + LNIN_XPLANE + pos);
         }
     };
-    Acc32 S;
-    acc_zero(S);
+    f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
     XFrag x[2];
     x_frag1(x[0], 0);
 #pragma unroll
@@ -765,39 +704,20 @@ __global__ __launch_bounds__(256, 2) void wt_linear_lnin_kernel(const float* __r
             x_frag1(x[(ks + 1) & 1], ks + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (HALF) {
 #pragma unroll
-            for (int ti = 0; ti < 2; ++ti) {
-                S.t[0][ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[ks % RD][0].h[0], x[ks & 1].h[ti], S.t[0][ti], 0, 0, 0);
-                S.t[0][ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[ks % RD][0].l[0], x[ks & 1].h[ti], S.t[0][ti], 0, 0, 0);
-                S.t[0][ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[ks % RD][0].h[0], x[ks & 1].l[ti], S.t[0][ti], 0, 0, 0);
-            }
-        } else {
-            wt_mma_block(S, w[ks % RD][0], x[ks & 1]);
+        for (int ti = 0; ti < 2; ++ti) {
+            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ks % RD], x[ks & 1].h[ti], acc[ti], 0, 0, 0);
+            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[ks % RD], x[ks & 1].h[ti], acc[ti], 0, 0, 0);
+            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ks % RD], x[ks & 1].l[ti], acc[ti], 0, 0, 0);
         }
         if (ks + RD < KS1) w_ring_load(ks % RD, ks + RD);
         __builtin_amdgcn_sched_barrier(0);
     }
+    const int feat = nt * 32 + hf * 16 + 4 * g;
 #pragma unroll
-    for (int fi = 0; fi < (HALF ? 1 : 2); ++fi) {
-        const int feat = nt * 32 + (HALF ? hf : fi) * 16 + 4 * g;
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-            const int64_t tok = m0 + ti * 16 + c;
-            if (tok < T) {
-                if (EPI == 1) {
-                    half4 hi, lo;
-                    gelu_split4(S.t[fi][ti], bv[fi], hi, lo);
-                    *reinterpret_cast<half4*>(oh + tok * N + feat) = hi;
-                    *reinterpret_cast<half4*>(ol + tok * N + feat) = lo;
-                } else {
-                    f32x4 v;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = fmaf(S.t[fi][ti][j], WT_UNSCALE, bv[fi][j]);
-                    *reinterpret_cast<f32x4*>(out + tok * N + feat) = v;
-                }
-            }
-        }
+    for (int ti = 0; ti < 2; ++ti) {
+        const int64_t tok = m0 + ti * 16 + c;
+        if (tok < T) wt_store4<EPI>(acc[ti], bv, tok, N, feat, out, oh, ol);
     }
 }
 
@@ -1220,7 +1140,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
             }
             if (ch + 1 < NC) bar_lds();  // B(ch+2): done with H[ch & 1]; H[(ch + 1) & 1] is ready
         }
-        // ---- + residual + bias: the block's own planes, still resident (the same r as wt_res_global / wt_res_add_direct)
+        // ---- + residual + bias: the block's own planes, still resident (the same r = res_init_val as wt_res_rows_acc)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
