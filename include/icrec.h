@@ -77,7 +77,7 @@ typedef struct icrec_bert_cfg {
                               f32 MFMA (bit-identical to the oracle's fmaf
                               chains); ICREC_GEMM_F16X3: linear layers on the
                               f16 MFMA with 3-term operand splitting (fp32-level
-                              accuracy, ~2^-21 relative per product; csrc/gemm_x3.h) */
+                              accuracy, ~2^-21 relative per product; csrc/wt_gemm.h) */
 } icrec_bert_cfg;
 
 #define ICREC_GEMM_F32 0

@@ -54,6 +54,9 @@ struct ScopedTimer {
 typedef unsigned long long u64;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef __HIPCC__
 
@@ -71,6 +74,10 @@ __device__ __forceinline__ float key_score(u64 key) {
     return __uint_as_float(u);
 }
 __device__ __forceinline__ uint32_t key_row(u64 key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+// bfloat16 -> fp32 is a 16-bit shift: the low / high half of a 32-bit word of bf16 bits, widened exactly
+__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
 
 __device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
     uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
@@ -177,15 +184,12 @@ __device__ __forceinline__ void tile_store_lds(const TileRegs<Cfg, A16>& r, floa
         for (int i = 0; i < TileRegs<Cfg, A16>::A_N; ++i) {
             int id = t + Cfg::THREADS * i;
             int row = id >> 2, c = id & 3;
-            // word w holds k = 2w (low half) and k = 2w+1 (high half); bf16 -> fp32 is a 16-bit shift
+            // word w holds k = 2w (low half) and k = 2w+1 (high half)
             const unsigned w0 = __float_as_uint(r.a[i].x), w1 = __float_as_uint(r.a[i].y),
                            w2 = __float_as_uint(r.a[i].z), w3 = __float_as_uint(r.a[i].w);
             float* p = As + row * LDK + c * 8;
-            *reinterpret_cast<float4*>(p) = make_float4(__uint_as_float(w0 << 16), __uint_as_float(w1 << 16),
-                                                        __uint_as_float(w2 << 16), __uint_as_float(w3 << 16));
-            *reinterpret_cast<float4*>(p + 4) =
-                make_float4(__uint_as_float(w0 & 0xFFFF0000u), __uint_as_float(w1 & 0xFFFF0000u),
-                            __uint_as_float(w2 & 0xFFFF0000u), __uint_as_float(w3 & 0xFFFF0000u));
+            *reinterpret_cast<float4*>(p) = make_float4(bf16_lo(w0), bf16_lo(w1), bf16_lo(w2), bf16_lo(w3));
+            *reinterpret_cast<float4*>(p + 4) = make_float4(bf16_hi(w0), bf16_hi(w1), bf16_hi(w2), bf16_hi(w3));
         }
     } else {
 #pragma unroll
@@ -234,13 +238,12 @@ __device__ __forceinline__ void tile_mma(f32x16 (&acc)[Cfg::TM][Cfg::TN], const 
 }
 
 // Full K loop for one output tile: single LDS buffer, register prefetch of the next slab
-// under the current slab's MFMAs.  `pre` must already hold slab 0 on entry when
-// `preloaded` is true (lets a caller overlap the first loads with its own epilogue).
+// under the current slab's MFMAs.
 template <class Cfg, bool A16 = false>
 __device__ __forceinline__ void tile_gemm(f32x16 (&acc)[Cfg::TM][Cfg::TN], const void* __restrict__ A,
                                           int64_t a_row0, int64_t a_rows, const float* __restrict__ B,
-                                          int64_t b_row0, int64_t b_rows, int K, float* As, float* Bs,
-                                          TileRegs<Cfg, A16>& pre, bool preloaded) {
+                                          int64_t b_row0, int64_t b_rows, int K, float* As, float* Bs) {
+    TileRegs<Cfg, A16> pre;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / Cfg::WAVES_N, wn = wave % Cfg::WAVES_N;
 #pragma unroll
@@ -250,7 +253,7 @@ __device__ __forceinline__ void tile_gemm(f32x16 (&acc)[Cfg::TM][Cfg::TN], const
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
     const int nslab = K / BK;
-    if (!preloaded) tile_load<Cfg, A16>(pre, A, a_row0, a_rows, B, b_row0, b_rows, K, 0);
+    tile_load<Cfg, A16>(pre, A, a_row0, a_rows, B, b_row0, b_rows, K, 0);
     for (int s = 0; s < nslab; ++s) {
         __syncthreads();  // previous slab's LDS reads are done
         tile_store_lds<Cfg, A16>(pre, As, Bs);

@@ -14,7 +14,6 @@
 #include <vector>
 
 #include "common.h"
-#include "gemm_x3.h"
 #include "wt_gemm.h"
 #include "encoder_x3.h"
 
@@ -31,7 +30,7 @@ __device__ __forceinline__ int find_seq(const int32_t* __restrict__ cu, int n_se
 }
 
 // LayerNorm of one 384-wide row held 6 values per lane (element i = lane + 64*j); oracle order.
-// SPLIT additionally writes the row as f16 hi/lo planes for the f16x3 GEMMs (gemm_x3.h).
+// SPLIT additionally writes the row as f16 hi/lo planes for the f16x3 GEMMs (wt_gemm.h: split_act).
 template <int H, bool SPLIT>
 __device__ __forceinline__ void ln_row(float (&v)[H / 64], const float* __restrict__ g, const float* __restrict__ b,
                                        float eps, float* __restrict__ out, _Float16* __restrict__ oh,
@@ -126,9 +125,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void linear_kernel(const float* __
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mt = bid / n_tiles_n, nt = bid % n_tiles_n;  // tiles sharing an A row panel are neighbours
     const int64_t m0 = (int64_t)mt * Cfg::BM, n0 = (int64_t)nt * Cfg::BN;
-    TileRegs<Cfg> pre;
     f32x16 acc[Cfg::TM][Cfg::TN];
-    tile_gemm<Cfg>(acc, A, m0, M, W, n0, N, K, As, Bs, pre, false);
+    tile_gemm<Cfg>(acc, A, m0, M, W, n0, N, K, As, Bs);
 #pragma unroll
     for (int j = 0; j < Cfg::TN; ++j) {
         const int64_t col = n0 + (wn * Cfg::TN + j) * 32 + (lane & 31);
@@ -380,8 +378,9 @@ __global__ __launch_bounds__(1024) void seq_order_kernel(const int32_t* __restri
 
 // ---------------------------------------------------------------- attention, f16x3 arithmetic
 // Same structure as attention_kernel (one block per (sequence, head), S^T on the accumulator rows, P fed
-// back from the accumulators), with both products on the f16 MFMA by the 3-term split of gemm_x3.h:
-//   S^T = K_hi.Q_hi + 2^-11 (K_hi.Q_lo + K_lo.Q_hi)        O = P_hi.V_hi + 2^-11 (P_hi.V_lo + P_lo.V_hi)
+// back from the accumulators), with both products on the f16 MFMA by the 3-term split of wt_gemm.h (one accumulator,
+// the plane scales folded into constants: see the kernel):
+//   S^T ~ K_hi.Q_hi + K_hi.Q_lo + K_lo.Q_hi        O ~ P_hi.V_hi + P_hi.V_lo + P_lo.V_hi
 // K is staged as hi/lo f16 planes [key][32] (64-B rows, 16-B chunks XOR-swizzled by (key>>2)&3), V as
 // TRANSPOSED hi/lo planes [dim][key] so that a lane's eight k-slots (keys) of one head dim are two 8-B
 // reads; Q (per wave) and P (per tile, straight from the accumulators) are split in registers.

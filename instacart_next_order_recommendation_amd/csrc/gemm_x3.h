@@ -1,4 +1,5 @@
-// gemm_x3.h — fp32-accurate GEMM on the f16 matrix cores by operand splitting.
+// gemm_x3.h — fp32-accurate GEMM on the f16 matrix cores by operand splitting: the staged filter pass of the
+// search (search.hip: staged_search_kernel).
 //
 // gfx950 has no TF32/xf32 MFMA; its exact f32 MFMA runs at 1/16 of the f16 rate.  Every fp32
 // operand x is therefore carried as two f16 planes
@@ -20,10 +21,6 @@
 namespace icrec {
 
 #ifdef __HIPCC__
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HBK = 64;   // halfs of K per slab
 constexpr int HLD = 72;   // LDS row stride in halfs (144 B)

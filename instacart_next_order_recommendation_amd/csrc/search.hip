@@ -60,40 +60,10 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
 // bf16 rows widened back to fp32 (icrec_index_export)
 __global__ __launch_bounds__(256) void widen_bf16_kernel(const uint16_t* __restrict__ in, float* __restrict__ out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = __uint_as_float((unsigned)in[i] << 16);
+    if (i < n) out[i] = bf16_lo(in[i]);
 }
 
 // ---------------------------------------------------------------- score + select
-// candidate queue slots per query between two list merges (more when few queries share the LDS)
-// Candidate queue entries per query: 64 for 32-query tiles, 16 for wider ones.  The resident filter pass takes 32 when
-// the lists are short (k <= 32) and a block walks few rounds (res_qcap): the first rounds of a block offer 16-48
-// candidates per query and would otherwise take two or three offer / merge iterations each - at 49,688 rows x 1,024
-// queries those rounds are most of the kernel (0.274 -> 0.229 ms, same box); blocks that walk thousands of rounds
-// keep 16 (10 M rows: 1 % faster with it).
-template <class Cfg> struct QCap { static constexpr int V = Cfg::BN <= 32 ? 64 : 16; };
-constexpr int RES_QCAP_MAX_ROUNDS = 64;
-__host__ __device__ constexpr int res_qcap(int k, int tiles_per_chunk) {
-    return k <= 32 && tiles_per_chunk <= RES_QCAP_MAX_ROUNDS ? 32 : 16;
-}
-
-// Resident filter pass (PMODE 3): the query tile's two activation planes, [64 queries][384] halfs each, live in LDS
-// for the whole block in the layout of the encoder's fused kernels (768-B rows as three XOR-swizzled 256-B sub-rows).
-constexpr int RES_XPLANE = 64 * 768;
-constexpr int RES_X_BYTES = 2 * RES_XPLANE;
-constexpr int RES_KS = 24;  // k-steps of 16: the resident pass is built for dim = 384
-
-template <class Cfg, int MODE = 0>  // MODE: 0 fp32 tiles, 2 f16 hi/lo planes staged per tile, 3 resident query planes
-struct SearchSmem {
-    // operand staging: fp32 tiles (common.h) or the f16 hi/lo planes of the filter pass (gemm_x3.h)
-    static constexpr size_t GEMM = MODE == 3 ? (size_t)RES_X_BYTES
-                                   : MODE == 2 ? (size_t)(2 * Cfg::BM + 2 * Cfg::BN) * HLD * 2 : (size_t)Cfg::LDS_FLOATS * 4;
-    // dynamic LDS carve (all offsets multiples of 16 B)
-    static __host__ __device__ size_t bytes(int k) {
-        return GEMM + (size_t)Cfg::BN * (8 /*thr*/ + 4 /*cnt*/) + 16 /*flags*/ +
-               (size_t)Cfg::BN * k * 8 + (size_t)Cfg::BN * (MODE == 3 && k <= 32 ? 32 : QCap<Cfg>::V) * 8;
-    }
-};
-
 // Is local row `row` in the sorted exclusion segment [lo, hi)?
 __device__ __forceinline__ bool excluded(const int32_t* __restrict__ ex, int lo, int hi, int row) {
     while (lo < hi) {
@@ -175,213 +145,82 @@ __device__ __forceinline__ void merge_queue2(u64* list, const u64* queue, int qc
     }
 }
 
-// Grid: n_chunks * n_qtiles blocks (XCD-remapped).  Block (chunk, qtile) scores catalog row
-// tiles [chunk*tiles_per_chunk, ...) against query tile qtile and keeps, per query, the k best
-// (score, row) seen, then writes them (sorted, as keys) to partial[chunk][query][0..k).
-// ---- fragment helpers of the RESIDENT filter pass (PMODE 3).  This pass keeps the v_mfma_f32_32x32x16_f16 form of
-// the weights-direct engine (its selection code is written for the 32x32 accumulator map; the pass is ~3 % of a
-// recommend step): catalog rows packed as [32-row tile][16-deep k-step][plane] fragments of 1 KB, lane (h << 5 | r)
-// holding row r, k = 16 ks + 8 h .. +7.  (The encoder's linear layers use the 16x16x32 form, wt_gemm.h.)
-__device__ __forceinline__ size_t r32_frag_off(int nt, int ks, int KS) { return ((size_t)nt * KS + ks) * (2 * WT_FRAG); }
-__device__ __forceinline__ void r32_w_load(half8& wh, half8& wl, const _Float16* wp, int ks, unsigned lo8) {
-    const _Float16* p = wp + (size_t)ks * (2 * WT_FRAG);
-    wh = *reinterpret_cast<const half8*>(p + lo8);
-    wl = *reinterpret_cast<const half8*>(p + WT_FRAG + lo8);
-}
-__device__ __forceinline__ void r32_mma(f32x16 (&acc)[1][2], const half8& wh, const half8& wl, const half8 (&xh)[2],
-                                        const half8 (&xl)[2]) {
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-        acc[0][tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh[tt], acc[0][tt], 0, 0, 0);
-        acc[0][tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[tt], acc[0][tt], 0, 0, 0);
-        acc[0][tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[tt], acc[0][tt], 0, 0, 0);
+// ---- per-query top-k selection, shared by the tiled search kernels
+// A block scores tiles of catalog rows against its BN queries; offer() takes one tile's scores in the accumulator map
+// of the 32x32 MFMA (acc[TM][TN]: this wave's row tiles wm, query tiles wn) and keeps, per query, the k best
+// (score, row) keys seen in a sorted LDS list; write() stores the lists.  The LDS carve follows the kernel's operand
+// staging (all offsets multiples of 16 B): thresholds [BN] | queue counters [BN] | flags [4] | lists [BN][k] |
+// candidate queues [BN][qcap].
+//
+// Candidate queue entries per query (qcap): 64 for 32-query tiles, 16 for wider ones.  The resident filter pass takes
+// 32 when the lists are short (k <= 32) and a block walks few rounds: the first rounds of a block offer 16-48
+// candidates per query and would otherwise take two or three offer / merge iterations each - at 49,688 rows x 1,024
+// queries those rounds are most of the kernel (0.274 -> 0.229 ms, same box); blocks that walk thousands of rounds
+// keep 16 (10 M rows: 1 % faster with it).
+constexpr int RES_QCAP_MAX_ROUNDS = 64;
+
+template <class Cfg, bool RESIDENT = false>
+struct TopK {
+    static __host__ __device__ constexpr int qcap(int k, int rounds) {
+        return RESIDENT && k <= 32 && rounds <= RES_QCAP_MAX_ROUNDS ? 32 : Cfg::BN <= 32 ? 64 : 16;
     }
-}
+    // LDS of the selection, sized for a block of one round (the largest queue)
+    static __host__ __device__ size_t bytes(int k) {
+        return (size_t)Cfg::BN * (8 /*thr*/ + 4 /*cnt*/) + 16 /*flags*/ + (size_t)Cfg::BN * k * 8 +
+               (size_t)Cfg::BN * qcap(k, 1) * 8;
+    }
 
-// EMIT = true additionally stores every score to scores_out[q*N + row] (parity checks only).
-// PMODE 0: fp32 rows.  1: rows stored as bfloat16 (ICREC_ROWS_BF16), widened on their way into LDS.
-// 2: the FILTER pass of ICREC_ROWS_F32_FILTER — rows and queries as f16 hi/lo planes (P/P2, Qn/Q2), scores from
-//    three f16 MFMAs per product (gemm_x3.h): within ~1e-7 of the exact chain at 5x its MFMA rate, NOT bit-exact;
-//    its lists only nominate candidates for verify_kernel.
-// 3: the RESIDENT form of the filter pass (dim = 384, catalogs up to RES_MAX_ROWS): P = the rows as packed weight
-//    fragments (wt_gemm.h: the 1 KB one wave feeds to one MFMA is contiguous), Qn/Q2 = the queries' activation planes.
-//    The block's 64 queries are loaded into LDS ONCE and stay there for all its row tiles; every wave owns one
-//    32-row tile of each 256-row round and streams its fragments L2 -> registers through an 8-deep ring that runs
-//    across rounds (the next round's first fragments land under the selection): no operand staging barriers at all -
-//    PMODE 2 re-stages both operands through LDS for every 128-row tile (two barriers per 64-deep slab).
-// run_flag != NULL: the whole grid exits unless *run_flag != 0 (the exact pass behind a filter pass).
-template <class Cfg, bool EMIT, int PMODE>
-__global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
-    const void* __restrict__ P, const void* __restrict__ P2, int64_t N, int K, const void* __restrict__ Qn,
-    const void* __restrict__ Q2, int Qpad, int Q, int k, const int32_t* __restrict__ excl_idx,
-    const int32_t* __restrict__ excl_off, uint32_t row_base, int n_row_tiles, int tiles_per_chunk, int n_qtiles,
-    u64* __restrict__ partial, float* __restrict__ scores_out, const int* __restrict__ run_flag) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    if (run_flag != nullptr && *run_flag == 0) return;  // uniform over the grid
-    constexpr bool P16 = PMODE == 1;
-    float* As = reinterpret_cast<float*>(smem_raw);
-    float* Bs = As + Cfg::BM * LDK;
-    u64* thr = reinterpret_cast<u64*>(smem_raw + SearchSmem<Cfg, PMODE >= 2 ? PMODE : 0>::GEMM);
-    int* cnt = reinterpret_cast<int*>(thr + Cfg::BN);
-    int* flags = cnt + Cfg::BN;  // [0],[1]: alternating "some candidate did not fit" flags
-    u64* list = reinterpret_cast<u64*>(flags + 4);
-    u64* queue = list + (size_t)Cfg::BN * k;
-
-    const int QCAP = PMODE == 3 ? res_qcap(k, tiles_per_chunk) : QCap<Cfg>::V;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / Cfg::WAVES_N, wn = wave % Cfg::WAVES_N;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    // consecutive logical ids share a catalog chunk (and hence an XCD's L2)
-    const int chunk = bid / n_qtiles, qtile = bid % n_qtiles;
-    const int q0 = qtile * Cfg::BN;
-
-    for (int i = tid; i < Cfg::BN; i += Cfg::THREADS) { thr[i] = (q0 + i < Q) ? 0ull : ~0ull; cnt[i] = 0; }
-    for (int i = tid; i < Cfg::BN * k; i += Cfg::THREADS) list[i] = 0ull;
-    if (tid < 4) flags[tid] = 0;
-    __syncthreads();
-
+    u64* thr;    // per query: the k-th key of its list, the offer threshold (~0: padding query)
+    int* cnt;    // per query: candidates in its queue
+    int* flags;  // [0],[1]: alternating "some candidate did not fit" flags; [2]: some lane's query is cold
+    u64* list;   // [BN][k], sorted best first, 0 = empty slot
+    u64* queue;  // [BN][qcap]
+    int k, qcap_, round = 0;
     // this lane's queries: column (lane & 31) of each of its TN column tiles
     int myq[Cfg::TN];
     u64 mythr[Cfg::TN];
     int ex_lo[Cfg::TN], ex_hi[Cfg::TN];
+
+    // Carves the LDS at `lds`, empties the lists (one barrier) and reads this lane's exclusion segments.  `rounds`: the
+    // tiles this block walks (the resident pass's queue capacity depends on it).
+    __device__ __forceinline__ TopK(char* lds, int k_, int Q, int q0, const int32_t* excl_off, int rounds = 1)
+        : k(k_), qcap_(qcap(k_, rounds)) {
+        const int tid = threadIdx.x, lane = tid & 63, wn = (tid >> 6) % Cfg::WAVES_N;
+        thr = reinterpret_cast<u64*>(lds);
+        cnt = reinterpret_cast<int*>(thr + Cfg::BN);
+        flags = cnt + Cfg::BN;
+        list = reinterpret_cast<u64*>(flags + 4);
+        queue = list + (size_t)Cfg::BN * k;
+        for (int i = tid; i < Cfg::BN; i += Cfg::THREADS) { thr[i] = (q0 + i < Q) ? 0ull : ~0ull; cnt[i] = 0; }
+        for (int i = tid; i < Cfg::BN * k; i += Cfg::THREADS) list[i] = 0ull;
+        if (tid < 4) flags[tid] = 0;
+        __syncthreads();
 #pragma unroll
-    for (int j = 0; j < Cfg::TN; ++j) {
-        myq[j] = (wn * Cfg::TN + j) * 32 + (lane & 31);
-        const int gq = q0 + myq[j];
-        mythr[j] = gq < Q ? 0ull : ~0ull;  // padding columns never produce candidates
-        ex_lo[j] = ex_hi[j] = 0;
-        if (excl_off != nullptr && gq < Q) { ex_lo[j] = excl_off[gq]; ex_hi[j] = excl_off[gq + 1]; }
+        for (int j = 0; j < Cfg::TN; ++j) {
+            myq[j] = (wn * Cfg::TN + j) * 32 + (lane & 31);
+            const int gq = q0 + myq[j];
+            mythr[j] = gq < Q ? 0ull : ~0ull;  // padding columns never produce candidates
+            ex_lo[j] = ex_hi[j] = 0;
+            if (excl_off != nullptr && gq < Q) { ex_lo[j] = excl_off[gq]; ex_hi[j] = excl_off[gq + 1]; }
+        }
     }
 
-    const int t_begin = chunk * tiles_per_chunk;
-    const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
-    int round = 0;
-    TileRegs<Cfg, P16> pre;
-    f32x16 acc[Cfg::TM][Cfg::TN];
-
-    // ---- PMODE 3: query planes -> LDS (once), weight ring of the first round
-    half8 rwh[8], rwl[8];
-    int xb0[2] = {0, 0};
-    const unsigned lo8 = lane * 8;
-    if constexpr (PMODE == 3) {
-        static_assert(PMODE != 3 || (Cfg::TM == 1 && Cfg::TN == 2 && Cfg::WAVES_N == 1 && Cfg::WAVES_M == 8),
-                      "resident pass: 8 waves x (1 row tile x 2 query tiles)");
-        const _Float16* qh = static_cast<const _Float16*>(Qn);
-        const _Float16* ql = static_cast<const _Float16*>(Q2);
-        char* const Xs = smem_raw;
-        u32x4 vh[6], vl[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int id = tid + 512 * i, row = id / 48, c = id - row * 48;
-            const int64_t g = (int64_t)(q0 + row) * 384 + c * 8;  // Qpad is a multiple of 64: every row exists
-            vh[i] = *reinterpret_cast<const u32x4*>(qh + g);
-            vl[i] = *reinterpret_cast<const u32x4*>(ql + g);
-        }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int id = tid + 512 * i, row = id / 48, c = id - row * 48;
-            const int pos = row * 768 + (((c & ~15) | ((c ^ row) & 15)) << 4);
-            *reinterpret_cast<u32x4*>(Xs + pos) = vh[i];
-            *reinterpret_cast<u32x4*>(Xs + RES_XPLANE + pos) = vl[i];
-        }
-        // this lane's fragment of query tile tt at k-step ks: xb0[tt] ^ ((ks & 7) << 5), + 256 (ks >> 3)
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int tok = tt * 32 + (lane & 31);
-            xb0[tt] = tok * 768 + (((lane >> 5) ^ (tok & 15)) << 4);
-        }
-        if (t_begin < t_end) {
-            const _Float16* const wp0 = static_cast<const _Float16*>(P) + r32_frag_off((t_begin * 8 + wave) * Cfg::TM, 0, RES_KS);
-#pragma unroll
-            for (int d = 0; d < 8; ++d) r32_w_load(rwh[d], rwl[d], wp0, d, lo8);
-        }
-        __syncthreads();  // queries resident
-    }
-
-    for (int tile = t_begin; tile < t_end; ++tile) {
-        const int64_t row0 = (int64_t)tile * Cfg::BM;
-        if constexpr (PMODE == 3) {
-            // the wave's TM 32-row tiles of this round, one after the other (fragment tiles (tile * 8 + wave) * TM + i); the
-            // selection below then runs once per round over all of them: its barriers and polls are per round, not per tile
-            const char* const Xs = smem_raw;
-#pragma unroll
-            for (int i = 0; i < Cfg::TM; ++i) {
-                const int rt = (tile * 8 + wave) * Cfg::TM + i;
-                // the ring continues into the wave's next tile; past the block's last round: re-read (never consumed)
-                const int rn = i + 1 < Cfg::TM ? rt + 1 : (tile + 1 < t_end ? ((tile + 1) * 8 + wave) * Cfg::TM : rt);
-                const _Float16* const wp1 = static_cast<const _Float16*>(P) + r32_frag_off(rt, 0, RES_KS);
-                const _Float16* const wpn = static_cast<const _Float16*>(P) + r32_frag_off(rn, 0, RES_KS);
-                f32x16 S[1][2];
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) S[0][tt][e] = 0.0f;
-                half8 fh[2][2], fl[2][2];
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) {
-                    fh[0][tt] = *reinterpret_cast<const half8*>(Xs + xb0[tt]);
-                    fl[0][tt] = *reinterpret_cast<const half8*>(Xs + RES_XPLANE + xb0[tt]);
-                }
-#pragma unroll
-                for (int ks = 0; ks < RES_KS; ++ks) {
-                    if (ks + 1 < RES_KS) {
-#pragma unroll
-                        for (int tt = 0; tt < 2; ++tt) {
-                            const int pos = (xb0[tt] ^ (((ks + 1) & 7) << 5)) + ((ks + 1) >> 3) * 256;
-                            fh[(ks + 1) & 1][tt] = *reinterpret_cast<const half8*>(Xs + pos);
-                            fl[(ks + 1) & 1][tt] = *reinterpret_cast<const half8*>(Xs + RES_XPLANE + pos);
-                        }
-                    }
-                    r32_mma(S, rwh[ks & 7], rwl[ks & 7], fh[ks & 1], fl[ks & 1]);
-                    if (ks + 8 < RES_KS) r32_w_load(rwh[ks & 7], rwl[ks & 7], wp1, ks + 8, lo8);
-                    else r32_w_load(rwh[ks & 7], rwl[ks & 7], wpn, ks + 8 - RES_KS, lo8);
-                    __builtin_amdgcn_sched_barrier(0);  // pin the prefetch to its k-step
-                }
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[i][j][e] = S[0][j][e] * WT_UNSCALE;
-            }
-        } else if (PMODE == 2) {
-            f32x16 a0[Cfg::TM][Cfg::TN], a1[Cfg::TM][Cfg::TN];
-            tile_gemm_h<Cfg>(a0, a1, static_cast<const _Float16*>(P), static_cast<const _Float16*>(P2), row0, N,
-                             static_cast<const _Float16*>(Qn), static_cast<const _Float16*>(Q2), q0, Qpad, K,
-                             reinterpret_cast<_Float16*>(smem_raw));
-#pragma unroll
-            for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-                for (int j = 0; j < Cfg::TN; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[i][j][e] = fmaf(a1[i][j][e], LO_UNSCALE, a0[i][j][e]);
-        } else {
-            tile_gemm<Cfg, P16>(acc, P, row0, N, static_cast<const float*>(Qn), q0, Qpad, K, As, Bs, pre, false);
-        }
-
-        if (EMIT) {
-#pragma unroll
-            for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-                for (int j = 0; j < Cfg::TN; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int64_t row = row0 + (wm * Cfg::TM + i) * 32 + acc_row(e, lane);
-                        const int gq = q0 + myq[j];
-                        if (row < N && gq < Q) scores_out[(int64_t)gq * N + row] = acc[i][j][e] + 0.0f;
-                    }
-        }
-
-        // ---- selection
-        // A score is OFFERED (pushed to its query's LDS queue) when it beats the query's threshold.
-        //  * warm query (list full): threshold = current k-th best key.  Queues are merged into the
-        //    sorted lists only when one is at least half full (or at the block's last tile), so a
-        //    stale — lower — threshold only means a few extra offers, never a missed hit.
-        //  * cold query (list not full yet, threshold key 0): instead of offering all of the tile's
-        //    scores, each lane first offers only its own m largest (m = ceil(k / lanes per query) + 1,
-        //    so the lanes together offer >= k), the queues are merged at once, and a second pass
-        //    offers whatever else still beats the now-real threshold (usually nothing).
+    // One tile of scores: rows row0 + (wm * TM + i) * 32 + acc_row(e, lane) of the catalog (rows >= N are padding).
+    // A score is OFFERED (pushed to its query's LDS queue) when it beats the query's threshold.
+    //  * warm query (list full): threshold = current k-th best key.  Queues are merged into the
+    //    sorted lists only when one is at least half full (or at the block's last tile), so a
+    //    stale — lower — threshold only means a few extra offers, never a missed hit.
+    //  * cold query (list not full yet, threshold key 0): instead of offering all of the tile's
+    //    scores, each lane first offers only its own m largest (m = ceil(k / lanes per query) + 1,
+    //    so the lanes together offer >= k), the queues are merged at once, and a second pass
+    //    offers whatever else still beats the now-real threshold (usually nothing).
+    __device__ __forceinline__ void offer(const f32x16 (&acc)[Cfg::TM][Cfg::TN], int64_t row0, int64_t N, uint32_t row_base,
+                                          const int32_t* excl_idx, bool last_tile) {
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        const int wm = wave / Cfg::WAVES_N;
+        const int QCAP = qcap_;
         constexpr int LPQ = 2 * Cfg::WAVES_M;  // lanes holding scores of one query
         const int m_local = (k + LPQ - 1) / LPQ + 1;
-        const bool last_tile = tile == t_end - 1;
         unsigned long long offered = 0ull;
         bool lane_cold = false;
         for (int pass = 0; pass < 2; ++pass) {
@@ -500,11 +339,225 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
         if (tid == 0) flags[2] = 0;
     }
 
-    // sorted partial lists out
-    for (int i = tid; i < Cfg::BN * k; i += Cfg::THREADS) {
-        const int q = i / k, e = i % k;
-        partial[((size_t)chunk * Qpad + q0 + q) * k + e] = list[(size_t)q * k + e];
+    // the sorted lists out: partial[chunk][q0 + q][0..k) for the block's BN queries
+    __device__ __forceinline__ void write(u64* partial, int chunk, int Qpad, int q0) const {
+        for (int i = threadIdx.x; i < Cfg::BN * k; i += Cfg::THREADS) {
+            const int q = i / k, e = i % k;
+            partial[((size_t)chunk * Qpad + q0 + q) * k + e] = list[(size_t)q * k + e];
+        }
     }
+};
+
+// Grid of every tiled search kernel: n_chunks * n_qtiles blocks (XCD-remapped).  Block (chunk, qtile) scores catalog
+// row tiles [chunk*tiles_per_chunk, ...) against query tile qtile and keeps, per query, the k best (score, row) seen,
+// then writes them (sorted, as keys) to partial[chunk][query][0..k).  Consecutive logical ids share a catalog chunk
+// (and hence an XCD's L2).
+//
+// The exact pass: rows in fp32, or (P16) stored as bfloat16 (ICREC_ROWS_BF16) and widened on their way into LDS.
+// EMIT = true additionally stores every score to scores_out[q*N + row] (parity checks only).
+// run_flag != NULL: the whole grid exits unless *run_flag != 0 (the exact pass behind a filter pass).
+template <class Cfg, bool EMIT, bool P16>
+__global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
+    const void* __restrict__ P, int64_t N, int K, const float* __restrict__ Qn, int Qpad, int Q, int k,
+    const int32_t* __restrict__ excl_idx, const int32_t* __restrict__ excl_off, uint32_t row_base, int n_row_tiles,
+    int tiles_per_chunk, int n_qtiles, u64* __restrict__ partial, float* __restrict__ scores_out,
+    const int* __restrict__ run_flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    if (run_flag != nullptr && *run_flag == 0) return;  // uniform over the grid
+    float* As = reinterpret_cast<float*>(smem_raw);
+    float* Bs = As + Cfg::BM * LDK;
+    const int lane = threadIdx.x & 63, wm = (threadIdx.x >> 6) / Cfg::WAVES_N;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
+    TopK<Cfg> sel(smem_raw + (size_t)Cfg::LDS_FLOATS * 4, k, Q, q0, excl_off);
+    const int t_begin = chunk * tiles_per_chunk;
+    const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
+    for (int tile = t_begin; tile < t_end; ++tile) {
+        const int64_t row0 = (int64_t)tile * Cfg::BM;
+        f32x16 acc[Cfg::TM][Cfg::TN];
+        tile_gemm<Cfg, P16>(acc, P, row0, N, Qn, q0, Qpad, K, As, Bs);
+        if (EMIT) {
+#pragma unroll
+            for (int i = 0; i < Cfg::TM; ++i)
+#pragma unroll
+                for (int j = 0; j < Cfg::TN; ++j)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int64_t row = row0 + (wm * Cfg::TM + i) * 32 + acc_row(e, lane);
+                        const int gq = q0 + sel.myq[j];
+                        if (row < N && gq < Q) scores_out[(int64_t)gq * N + row] = acc[i][j][e] + 0.0f;
+                    }
+        }
+        sel.offer(acc, row0, N, row_base, excl_idx, tile == t_end - 1);
+    }
+    sel.write(partial, chunk, Qpad, q0);
+}
+
+// The STAGED filter pass of ICREC_ROWS_F32_FILTER: rows and queries as f16 hi/lo planes (Ph/Pl, Qh/Ql), both staged
+// through LDS per tile, scores from three f16 MFMAs per product (gemm_x3.h): within ~1e-7 of the exact chain at 5x its
+// MFMA rate, NOT bit-exact; its lists only nominate candidates for verify_kernel.
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::THREADS, 2) void staged_search_kernel(
+    const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, int64_t N, int K, const _Float16* __restrict__ Qh,
+    const _Float16* __restrict__ Ql, int Qpad, int Q, int k, const int32_t* __restrict__ excl_idx,
+    const int32_t* __restrict__ excl_off, uint32_t row_base, int n_row_tiles, int tiles_per_chunk, int n_qtiles,
+    u64* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
+    TopK<Cfg> sel(smem_raw + SmemH<Cfg>::BYTES, k, Q, q0, excl_off);
+    const int t_begin = chunk * tiles_per_chunk;
+    const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
+    for (int tile = t_begin; tile < t_end; ++tile) {
+        const int64_t row0 = (int64_t)tile * Cfg::BM;
+        f32x16 a0[Cfg::TM][Cfg::TN], a1[Cfg::TM][Cfg::TN], acc[Cfg::TM][Cfg::TN];
+        tile_gemm_h<Cfg>(a0, a1, Ph, Pl, row0, N, Qh, Ql, q0, Qpad, K, reinterpret_cast<_Float16*>(smem_raw));
+#pragma unroll
+        for (int i = 0; i < Cfg::TM; ++i)
+#pragma unroll
+            for (int j = 0; j < Cfg::TN; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[i][j][e] = fmaf(a1[i][j][e], LO_UNSCALE, a0[i][j][e]);
+        sel.offer(acc, row0, N, row_base, excl_idx, tile == t_end - 1);
+    }
+    sel.write(partial, chunk, Qpad, q0);
+}
+
+// ---- the RESIDENT filter pass's operands.  This pass keeps the v_mfma_f32_32x32x16_f16 form of the weights-direct
+// engine (its selection code is written for the 32x32 accumulator map; the pass is ~3 % of a recommend step): catalog
+// rows packed as [32-row tile][16-deep k-step][plane] fragments of 1 KB, lane (h << 5 | r) holding row r,
+// k = 16 ks + 8 h .. +7.  (The encoder's linear layers use the 16x16x32 form, wt_gemm.h.)  The query tile's two
+// activation planes, [64 queries][384] halfs each, live in LDS for the whole block in the layout of the encoder's
+// fused kernels (768-B rows as three XOR-swizzled 256-B sub-rows).
+constexpr int RES_XPLANE = 64 * 768;
+constexpr int RES_X_BYTES = 2 * RES_XPLANE;
+constexpr int RES_KS = 24;  // k-steps of 16: the resident pass is built for dim = 384
+
+__device__ __forceinline__ size_t r32_frag_off(int nt, int ks, int KS) { return ((size_t)nt * KS + ks) * (2 * WT_FRAG); }
+__device__ __forceinline__ void r32_w_load(half8& wh, half8& wl, const _Float16* wp, int ks, unsigned lo8) {
+    const _Float16* p = wp + (size_t)ks * (2 * WT_FRAG);
+    wh = *reinterpret_cast<const half8*>(p + lo8);
+    wl = *reinterpret_cast<const half8*>(p + WT_FRAG + lo8);
+}
+__device__ __forceinline__ void r32_mma(f32x16 (&acc)[1][2], const half8& wh, const half8& wl, const half8 (&xh)[2],
+                                        const half8 (&xl)[2]) {
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+        acc[0][tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh[tt], acc[0][tt], 0, 0, 0);
+        acc[0][tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[tt], acc[0][tt], 0, 0, 0);
+        acc[0][tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[tt], acc[0][tt], 0, 0, 0);
+    }
+}
+
+// The block's 64 queries q0 .. q0 + 63 (Qpad is a multiple of 64: every row exists), both planes -> LDS at Xs.
+// 512 threads.
+__device__ __forceinline__ void r32_load_queries(char* Xs, const _Float16* qh, const _Float16* ql, int q0, int tid) {
+    u32x4 vh[6], vl[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int id = tid + 512 * i, row = id / 48, c = id - row * 48;
+        const int64_t g = (int64_t)(q0 + row) * 384 + c * 8;
+        vh[i] = *reinterpret_cast<const u32x4*>(qh + g);
+        vl[i] = *reinterpret_cast<const u32x4*>(ql + g);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int id = tid + 512 * i, row = id / 48, c = id - row * 48;
+        const int pos = row * 768 + (((c & ~15) | ((c ^ row) & 15)) << 4);
+        *reinterpret_cast<u32x4*>(Xs + pos) = vh[i];
+        *reinterpret_cast<u32x4*>(Xs + RES_XPLANE + pos) = vl[i];
+    }
+}
+
+// One 32-row fragment tile (wp) against the block's two 32-query tiles: out[tt] = its scores.  The 8-deep weight ring
+// (rwh, rwl) holds k-steps 0-7 of wp on entry and k-steps 0-7 of wpn, the wave's next tile, on return.
+__device__ __forceinline__ void r32_tile(f32x16 (&out)[2], const char* Xs, const int (&xb0)[2], half8 (&rwh)[8],
+                                         half8 (&rwl)[8], const _Float16* wp, const _Float16* wpn, unsigned lo8) {
+    f32x16 S[1][2];
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) S[0][tt][e] = 0.0f;
+    half8 fh[2][2], fl[2][2];
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+        fh[0][tt] = *reinterpret_cast<const half8*>(Xs + xb0[tt]);
+        fl[0][tt] = *reinterpret_cast<const half8*>(Xs + RES_XPLANE + xb0[tt]);
+    }
+#pragma unroll
+    for (int ks = 0; ks < RES_KS; ++ks) {
+        if (ks + 1 < RES_KS) {
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                const int pos = (xb0[tt] ^ (((ks + 1) & 7) << 5)) + ((ks + 1) >> 3) * 256;
+                fh[(ks + 1) & 1][tt] = *reinterpret_cast<const half8*>(Xs + pos);
+                fl[(ks + 1) & 1][tt] = *reinterpret_cast<const half8*>(Xs + RES_XPLANE + pos);
+            }
+        }
+        r32_mma(S, rwh[ks & 7], rwl[ks & 7], fh[ks & 1], fl[ks & 1]);
+        if (ks + 8 < RES_KS) r32_w_load(rwh[ks & 7], rwl[ks & 7], wp, ks + 8, lo8);
+        else r32_w_load(rwh[ks & 7], rwl[ks & 7], wpn, ks + 8 - RES_KS, lo8);
+        __builtin_amdgcn_sched_barrier(0);  // pin the prefetch to its k-step
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) out[j][e] = S[0][j][e] * WT_UNSCALE;
+}
+
+// The RESIDENT form of the filter pass (dim = 384): the rows as packed weight fragments (pack_rows_kernel: the 1 KB one
+// wave feeds to one MFMA is contiguous), Qh/Ql = the queries' activation planes.  The block's 64 queries are loaded into
+// LDS ONCE and stay there for all its row tiles; every wave owns one 32-row tile of each 256-row round and streams its
+// fragments L2 -> registers through an 8-deep ring that runs across rounds (the next round's first fragments land
+// under the selection): no operand staging barriers at all - the staged pass re-stages both operands through LDS for
+// every 128-row tile (two barriers per 64-deep slab).
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::THREADS, 2) void resident_search_kernel(
+    const _Float16* __restrict__ frag, int64_t N, const _Float16* __restrict__ Qh, const _Float16* __restrict__ Ql,
+    int Qpad, int Q, int k, const int32_t* __restrict__ excl_idx, const int32_t* __restrict__ excl_off,
+    uint32_t row_base, int n_row_tiles, int tiles_per_chunk, int n_qtiles, u64* __restrict__ partial) {
+    static_assert(Cfg::TM == 1 && Cfg::TN == 2 && Cfg::WAVES_N == 1 && Cfg::WAVES_M == 8,
+                  "resident pass: 8 waves x (1 row tile x 2 query tiles)");
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
+    TopK<Cfg, true> sel(smem_raw + RES_X_BYTES, k, Q, q0, excl_off, tiles_per_chunk);
+    const int t_begin = chunk * tiles_per_chunk;
+    const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
+
+    // query planes -> LDS (once), weight ring of the first round
+    r32_load_queries(smem_raw, Qh, Ql, q0, tid);
+    int xb0[2];  // this lane's fragment of query tile tt at k-step ks: xb0[tt] ^ ((ks & 7) << 5), + 256 (ks >> 3)
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+        const int tok = tt * 32 + (lane & 31);
+        xb0[tt] = tok * 768 + (((lane >> 5) ^ (tok & 15)) << 4);
+    }
+    const unsigned lo8 = lane * 8;
+    half8 rwh[8], rwl[8];
+    if (t_begin < t_end) {
+        const _Float16* const wp0 = frag + r32_frag_off((t_begin * 8 + wave) * Cfg::TM, 0, RES_KS);
+#pragma unroll
+        for (int d = 0; d < 8; ++d) r32_w_load(rwh[d], rwl[d], wp0, d, lo8);
+    }
+    __syncthreads();  // queries resident
+
+    f32x16 acc[Cfg::TM][Cfg::TN];
+    for (int tile = t_begin; tile < t_end; ++tile) {
+        const int64_t row0 = (int64_t)tile * Cfg::BM;
+        // the wave's TM fragment tiles (tile * 8 + wave) * TM + i of this round, one after the other; the selection then
+        // runs once per round over all of them
+#pragma unroll
+        for (int i = 0; i < Cfg::TM; ++i) {
+            const int rt = (tile * 8 + wave) * Cfg::TM + i;
+            // the ring continues into the wave's next tile; past the block's last round: re-read (never consumed)
+            const int rn = i + 1 < Cfg::TM ? rt + 1 : (tile + 1 < t_end ? ((tile + 1) * 8 + wave) * Cfg::TM : rt);
+            r32_tile(acc[i], smem_raw, xb0, rwh, rwl, frag + r32_frag_off(rt, 0, RES_KS), frag + r32_frag_off(rn, 0, RES_KS), lo8);
+        }
+        sel.offer(acc, row0, N, row_base, excl_idx, tile == t_end - 1);
+    }
+    sel.write(partial, chunk, Qpad, q0);
 }
 
 // ---------------------------------------------------------------- small-batch streaming search
@@ -623,8 +676,8 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
                     if (P16) {
                         const unsigned u = __float_as_uint(w[e]);
                         const int kk = c * 8 + e * 2;
-                        stream_fma<NQ>(acc, qs + kk * NQ, __uint_as_float(u << 16));
-                        stream_fma<NQ>(acc, qs + (kk + 1) * NQ, __uint_as_float(u & 0xFFFF0000u));
+                        stream_fma<NQ>(acc, qs + kk * NQ, bf16_lo(u));
+                        stream_fma<NQ>(acc, qs + (kk + 1) * NQ, bf16_hi(u));
                     } else {
                         stream_fma<NQ>(acc, qs + (c * 4 + e) * NQ, w[e]);
                     }
@@ -683,14 +736,21 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
 }
 
 // ---------------------------------------------------------------- filter + verify (ICREC_ROWS_F32_FILTER)
-// fp32 values -> f16 hi/lo planes (queries per call, catalog rows once at create); clears the fallback flag if given.
+// Output slot o of a final list: the key and / or its (row, score); key 0 is the pad (row -1, score 0).
+__device__ __forceinline__ void store_key(u64 key, size_t o, int64_t* out_idx, float* out_score, u64* out_keys) {
+    if (out_keys) out_keys[o] = key;
+    if (out_idx) out_idx[o] = key ? (int64_t)key_row(key) : -1;
+    if (out_idx) out_score[o] = key ? key_score(key) : 0.0f;  // out_score is set whenever out_idx is
+}
+
+// fp32 values -> f16 hi/lo planes: the queries of the staged filter pass per call, the catalog rows once at index
+// creation; clears the fallback flag if given.
 template <bool SRC16>  // SRC16: the source is bfloat16 bits (ICREC_ROWS_BF16_FILTER rows), widened exactly first
-__global__ __launch_bounds__(256) void split_queries_kernel(const void* __restrict__ src, size_t n, _Float16* __restrict__ hi,
-                                                            _Float16* __restrict__ lo, int* __restrict__ flag) {
+__global__ __launch_bounds__(256) void split_planes_kernel(const void* __restrict__ src, size_t n, _Float16* __restrict__ hi,
+                                                           _Float16* __restrict__ lo, int* __restrict__ flag) {
     if (flag != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *flag = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float v = SRC16 ? __uint_as_float((unsigned)static_cast<const uint16_t*>(src)[i] << 16)
-                              : static_cast<const float*>(src)[i];
+        const float v = SRC16 ? bf16_lo(static_cast<const uint16_t*>(src)[i]) : static_cast<const float*>(src)[i];
         _Float16 a, b;
         split_f16(v, a, b);
         hi[i] = a;
@@ -717,8 +777,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const void* __restrict__
             float v = 0.0f;
             if (row < n_rows) {
                 const size_t at = (size_t)row * K + ks * 16 + 8 * h + j;
-                v = SRC16 ? __uint_as_float((unsigned)static_cast<const uint16_t*>(src)[at] << 16)
-                          : static_cast<const float*>(src)[at];
+                v = SRC16 ? bf16_lo(static_cast<const uint16_t*>(src)[at]) : static_cast<const float*>(src)[at];
             }
             _Float16 a, b;
             split_scaled(v, WT_SW, a, b);
@@ -775,10 +834,10 @@ __global__ __launch_bounds__(256) void verify_kernel(const void* __restrict__ Pv
                 for (int j = 0; j < K; j += 4) {
                     const f32x4 a = *reinterpret_cast<const f32x4*>(qv + j);
                     const uint2 w = *reinterpret_cast<const uint2*>(pr + j);
-                    acc = fmaf(a[0], __uint_as_float(w.x << 16), acc);
-                    acc = fmaf(a[1], __uint_as_float(w.x & 0xFFFF0000u), acc);
-                    acc = fmaf(a[2], __uint_as_float(w.y << 16), acc);
-                    acc = fmaf(a[3], __uint_as_float(w.y & 0xFFFF0000u), acc);
+                    acc = fmaf(a[0], bf16_lo(w.x), acc);
+                    acc = fmaf(a[1], bf16_hi(w.x), acc);
+                    acc = fmaf(a[2], bf16_lo(w.y), acc);
+                    acc = fmaf(a[3], bf16_hi(w.y), acc);
                 }
             } else {
                 const float* pr = static_cast<const float*>(Pv) + (size_t)(grow - row_base) * K;
@@ -820,16 +879,9 @@ __global__ __launch_bounds__(256) void verify_kernel(const void* __restrict__ Pv
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s)
-        if (ek[s] != 0ull && rk[s] < k) {
-            const size_t o = (size_t)q * k + rk[s];
-            if (out_keys) out_keys[o] = ek[s];
-            if (out_idx) { out_idx[o] = (int64_t)key_row(ek[s]); out_score[o] = key_score(ek[s]); }
-        }
-    for (int e = n_valid + lane; e < k; e += 64) {  // pads when the catalog (minus exclusions) is smaller than k
-        const size_t o = (size_t)q * k + e;
-        if (out_keys) out_keys[o] = 0ull;
-        if (out_idx) { out_idx[o] = -1; out_score[o] = 0.0f; }
-    }
+        if (ek[s] != 0ull && rk[s] < k) store_key(ek[s], (size_t)q * k + rk[s], out_idx, out_score, out_keys);
+    for (int e = n_valid + lane; e < k; e += 64)  // pads when the catalog (minus exclusions) is smaller than k
+        store_key(0ull, (size_t)q * k + e, out_idx, out_score, out_keys);
 }
 
 // ---------------------------------------------------------------- k-way merge of sorted lists
@@ -868,13 +920,7 @@ __global__ __launch_bounds__(256) void merge_kernel(const u64* __restrict__ keys
                 }
             }
         }
-        if (lane == 0) {
-            if (out_keys) out_keys[(size_t)q * k + e] = w;
-            if (out_idx) {
-                out_idx[(size_t)q * k + e] = w ? (int64_t)key_row(w) : -1;
-                out_score[(size_t)q * k + e] = w ? key_score(w) : 0.0f;
-            }
-        }
+        if (lane == 0) store_key(w, (size_t)q * k + e, out_idx, out_score, out_keys);
     }
 }
 
@@ -929,17 +975,10 @@ __global__ __launch_bounds__(256) void merge_block_kernel(const u64* __restrict_
         const u64 v = all[cand[ci]];
         int r = 0;
         for (int j = 0; j < C; ++j) r += all[cand[j]] > v ? 1 : 0;
-        if (r < k) {
-            const size_t o = (size_t)q * k + r;
-            if (out_keys) out_keys[o] = v;
-            if (out_idx) { out_idx[o] = (int64_t)key_row(v); out_score[o] = key_score(v); }
-        }
+        if (r < k) store_key(v, (size_t)q * k + r, out_idx, out_score, out_keys);
     }
-    for (int e = (C < k ? C : k) + tid; e < k; e += 256) {  // pads: fewer than k rows left after the exclusions
-        const size_t o = (size_t)q * k + e;
-        if (out_keys) out_keys[o] = 0ull;
-        if (out_idx) { out_idx[o] = -1; out_score[o] = 0.0f; }
-    }
+    for (int e = (C < k ? C : k) + tid; e < k; e += 256)  // pads: fewer than k rows left after the exclusions
+        store_key(0ull, (size_t)q * k + e, out_idx, out_score, out_keys);
 }
 
 // ---------------------------------------------------------------- host side
@@ -1014,6 +1053,11 @@ static int stream_max_q_from_env() {
     return v > 8 ? 8 : v < 0 ? 0 : v;
 }
 
+// Dynamic LDS of the tiled kernels: operand staging, then the selection (TopK).
+template <class Cfg> static size_t exact_smem(int k) { return (size_t)Cfg::LDS_FLOATS * 4 + TopK<Cfg>::bytes(k); }
+static size_t staged_smem(int k) { return SmemH<CfgFilter>::BYTES + TopK<CfgFilter>::bytes(k); }
+static size_t resident_smem(int k) { return RES_X_BYTES + TopK<CfgRes, true>::bytes(k); }
+
 static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream) {
     Plan p;
     // The streaming kernel pays a per-block cold start (rank 256 keys per query by counting) that only amortises
@@ -1029,9 +1073,9 @@ static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream) {
         // ~3 blocks per CU are resident (LDS)
         plan_chunks(ix->n_rows, p.BM, 3 * ix->n_cu, MERGE_MAX_LISTS, &p.n_row_tiles, &p.tiles_per_chunk, &p.n_chunks);
     } else {
-        if (Q > 64 && k <= 32) { p.variant = 0; p.BM = CfgBig::BM; p.BN = CfgBig::BN; p.smem = SearchSmem<CfgBig>::bytes(k); }
-        else if (Q > 32 && k <= 64) { p.variant = 1; p.BM = CfgMid::BM; p.BN = CfgMid::BN; p.smem = SearchSmem<CfgMid>::bytes(k); }
-        else { p.variant = 2; p.BM = CfgSmall::BM; p.BN = CfgSmall::BN; p.smem = SearchSmem<CfgSmall>::bytes(k); }
+        if (Q > 64 && k <= 32) { p.variant = 0; p.BM = CfgBig::BM; p.BN = CfgBig::BN; p.smem = exact_smem<CfgBig>(k); }
+        else if (Q > 32 && k <= 64) { p.variant = 1; p.BM = CfgMid::BM; p.BN = CfgMid::BN; p.smem = exact_smem<CfgMid>(k); }
+        else { p.variant = 2; p.BM = CfgSmall::BM; p.BN = CfgSmall::BN; p.smem = exact_smem<CfgSmall>(k); }
         p.n_qtiles = (Q + p.BN - 1) / p.BN;
         p.Qpad = p.n_qtiles * p.BN;
         // one full wave of resident blocks (2 per CU fit by LDS/VGPR), at most 256 chunks
@@ -1058,14 +1102,14 @@ static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& ex
     f.use = (ix->plane_hi != nullptr || f.resident) && Q >= FILTER_MIN_Q && f.kp <= ICREC_MAX_K;
     // resident form: the query planes leave 64 KB of LDS for the lists (k <= 92); longer lists take the exact search,
     // which is the faster one there anyway (measured at 49,688 rows, Q = 1,024, k = 100: staged filter 2.5 ms, exact 1.5 ms)
-    if (f.resident && SearchSmem<CfgRes, 3>::bytes(f.kp) > 160 * 1024) f.use = false;
+    if (f.resident && resident_smem(f.kp) > 160 * 1024) f.use = false;
     if (!f.use) { f.ws_total = 0; return f; }
     f.n_qtiles = (Q + CfgFilter::BN - 1) / CfgFilter::BN;  // 64 queries per tile in both forms
     f.Qpad = f.n_qtiles * CfgFilter::BN;
     // staged form: two 4-wave blocks per CU; resident form: one 8-wave block per CU (its query planes take 96 KB)
     plan_chunks(ix->n_rows, f.resident ? CfgRes::BM : CfgFilter::BM, (f.resident ? 1 : 2) * ix->n_cu / f.n_qtiles, 256,
                 &f.n_row_tiles, &f.tiles_per_chunk, &f.n_chunks);
-    f.smem = f.resident ? SearchSmem<CfgRes, 3>::bytes(f.kp) : SearchSmem<CfgFilter, 2>::bytes(f.kp);
+    f.smem = f.resident ? resident_smem(f.kp) : staged_smem(f.kp);
     const int qpad_max = f.Qpad > exact.Qpad ? f.Qpad : exact.Qpad;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     f.off_qh = up((size_t)qpad_max * ix->dim * 4);
@@ -1100,23 +1144,22 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
     if (f.resident) {
         hipLaunchKernelGGL(split_queries_act_kernel, dim3((unsigned)((nq / 4 + 255) / 256 < 1024 ? (nq / 4 + 255) / 256 : 1024)),
                            dim3(256), 0, st, (const float*)qn, nq / 4, qh, ql, flag);
-        auto kern = search_kernel<CfgRes, false, 3>;
+        auto kern = resident_search_kernel<CfgRes>;
         if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc_;
         ScopedTimer tm(T_SEARCH_KERNEL, st);
-        hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st,
-                           (const void*)ix->frag, (const void*)nullptr, ix->n_rows, ix->dim, (const void*)qh,
-                           (const void*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset, f.n_row_tiles,
-                           f.tiles_per_chunk, f.n_qtiles, partial, (float*)nullptr, (const int*)nullptr);
+        hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st, (const _Float16*)ix->frag,
+                           ix->n_rows, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo,
+                           (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     } else {
-        hipLaunchKernelGGL(split_queries_kernel<false>, dim3((unsigned)((nq + 255) / 256 < 1024 ? (nq + 255) / 256 : 1024)),
+        hipLaunchKernelGGL(split_planes_kernel<false>, dim3((unsigned)((nq + 255) / 256 < 1024 ? (nq + 255) / 256 : 1024)),
                            dim3(256), 0, st, (const void*)qn, nq, qh, ql, flag);
-        auto kern = search_kernel<CfgFilter, false, 2>;
+        auto kern = staged_search_kernel<CfgFilter>;
         if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc_;
         ScopedTimer tm(T_SEARCH_KERNEL, st);
         hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st,
-                           (const void*)ix->plane_hi, (const void*)ix->plane_lo, ix->n_rows, ix->dim, (const void*)qh,
-                           (const void*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset, f.n_row_tiles,
-                           f.tiles_per_chunk, f.n_qtiles, partial, (float*)nullptr, (const int*)nullptr);
+                           (const _Float16*)ix->plane_hi, (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim,
+                           (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
+                           f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     }
     ICREC_HIP(hipGetLastError());
     hipLaunchKernelGGL(merge_kernel<4>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, f.n_chunks, f.Qpad, Q, f.kp,
@@ -1137,18 +1180,18 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
 // the guarded pass of the filter path, which has a timer slot of its own.  (Kernel tables: bf16 rows first.)
 static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
                         const int32_t* eo, u64* partial, float* scores_out, const int* run_flag, hipStream_t st) {
-    using SearchFn = decltype(&search_kernel<CfgBig, false, 0>);
+    using SearchFn = decltype(&search_kernel<CfgBig, false, false>);
     static const SearchFn lists[2][3] = {
-        {search_kernel<CfgBig, false, 1>, search_kernel<CfgMid, false, 1>, search_kernel<CfgSmall, false, 1>},
-        {search_kernel<CfgBig, false, 0>, search_kernel<CfgMid, false, 0>, search_kernel<CfgSmall, false, 0>}};
+        {search_kernel<CfgBig, false, true>, search_kernel<CfgMid, false, true>, search_kernel<CfgSmall, false, true>},
+        {search_kernel<CfgBig, false, false>, search_kernel<CfgMid, false, false>, search_kernel<CfgSmall, false, false>}};
     static const decltype(&stream_search_kernel<1, false>) stream[4][2] = {  // NQ = 1, 2, 4, 8
         {stream_search_kernel<1, true>, stream_search_kernel<1, false>},
         {stream_search_kernel<2, true>, stream_search_kernel<2, false>},
         {stream_search_kernel<4, true>, stream_search_kernel<4, false>},
         {stream_search_kernel<8, true>, stream_search_kernel<8, false>}};
     static const SearchFn scores[2][3] = {
-        {search_kernel<CfgBig, true, 1>, search_kernel<CfgMid, true, 1>, search_kernel<CfgSmall, true, 1>},
-        {search_kernel<CfgBig, true, 0>, search_kernel<CfgMid, true, 0>, search_kernel<CfgSmall, true, 0>}};
+        {search_kernel<CfgBig, true, true>, search_kernel<CfgMid, true, true>, search_kernel<CfgSmall, true, true>},
+        {search_kernel<CfgBig, true, false>, search_kernel<CfgMid, true, false>, search_kernel<CfgSmall, true, false>}};
     const int r = rows_are_bf16(ix) ? 0 : 1;
     if (p.variant == 3) {
         const int nq = p.BN == 1 ? 0 : p.BN == 2 ? 1 : p.BN == 4 ? 2 : 3;
@@ -1162,9 +1205,8 @@ static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, 
         if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc_;
         ScopedTimer tm(run_flag == nullptr ? T_SEARCH_KERNEL : T_SEARCH_FALLBACK, st);
         hipLaunchKernelGGL(kern, dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st, (const void*)ix->rows,
-                           (const void*)nullptr, ix->n_rows, ix->dim, (const void*)qn, (const void*)nullptr, p.Qpad, Q, k, ei,
-                           eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk, p.n_qtiles, partial, scores_out,
-                           run_flag);
+                           ix->n_rows, ix->dim, qn, p.Qpad, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles,
+                           p.tiles_per_chunk, p.n_qtiles, partial, scores_out, run_flag);
     }
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
@@ -1359,7 +1401,7 @@ int icrec_index_create_ex(const float* rows_dev, int64_t n_rows, int32_t dim, in
             return fail();
         }
         // planes of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
-        hipLaunchKernelGGL((rows16 ? split_queries_kernel<true> : split_queries_kernel<false>), dim3(4096), dim3(256), 0, 0,
+        hipLaunchKernelGGL((rows16 ? split_planes_kernel<true> : split_planes_kernel<false>), dim3(4096), dim3(256), 0, 0,
                            (const void*)ix->rows, n, ix->plane_hi, ix->plane_lo, (int*)nullptr);
         ICREC_HIP(hipGetLastError());
     }

@@ -37,7 +37,6 @@
 // tile position or batch computed it — the bitwise tests between the small-batch, batch and fused forms rest on this.
 #pragma once
 #include "common.h"
-#include "gemm_x3.h"  // half8 / half4 / u32x4
 
 namespace icrec {
 
