@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — recommend() throughput on MI355X: SBERT encode -> cosine -> top-20 over the
-49,688-product catalog (BASELINE.json metric), with the kernel roofline and a CPU baseline.
+49,688-product catalog (BASELINE.json metric), with the kernel roofline (and, with --full, a CPU baseline).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload 49k7|10m] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload 49k7|10m] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic user contexts whose token
 ids are already resident in HBM: icrec_encode (BERT forward + pool + normalise) then
@@ -10,6 +10,10 @@ icrec_search (cosine + top-20, exclusions off), results left in HBM.  At N > 1 (
 torch.distributed.run, one rank per GPU, RCCL) the catalog is row-sharded, each rank encodes
 `--batch` contexts (weak scaling: global batch = N * batch), query embeddings and per-shard
 partial top-k lists are all-gathered and merged (instacart_next_order_recommendation_amd/sharded.py).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  --full adds every
+other leg: HTTP, the 10 M-row configs[4] workload, two-stream / hipGraph / exact-f32 steps, single-request
+latencies, index build, text paths, and the CPU baseline with the oracle check of the timed step's outputs.
 
 Rank 0 prints ONE JSON line.
 """
@@ -49,13 +53,17 @@ def parse():
                          "plus f16 filter planes, results bit-identical to f32; bf16+filter for 10m: bf16 rows as BASELINE configs[4] says, plus filter planes)")
     ap.add_argument("--gemm-mode", default=None, choices=["f32", "f16x3"],
                     help="encoder GEMM arithmetic (default: the package default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (HTTP, configs[4], two-stream, hipGraph, exact f32, "
+                         "latency, index build, text paths, CPU baseline + oracle check); the --no-* options below skip "
+                         "some of them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-request (Q=1) latency loop")
     ap.add_argument("--cpu-sample", type=int, default=128, help="queries in the CPU baseline sample")
     ap.add_argument("--rows-10m", type=int, default=10_000_000,
                     help="catalog rows of the configs[4] workload / leg (tests pass a small number)")
     ap.add_argument("--no-10m-leg", action="store_true",
-                    help="skip the configs[4] leg (4,096 queries over the 10 M-row bf16 catalog) the default line carries")
+                    help="skip the configs[4] leg (4,096 queries over the 10 M-row bf16 catalog) the --full line carries")
     ap.add_argument("--no-http", action="store_true", help="skip the /recommend-over-HTTP leg")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (query embeddings, top-k rows, "
@@ -259,7 +267,7 @@ def main() -> None:
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
     http = None
-    if (args.gpus == 1 and args.workload == "49k7" and not args.no_http and not args.no_latency
+    if (args.full and args.gpus == 1 and args.workload == "49k7" and not args.no_http and not args.no_latency
             and "WORLD_SIZE" not in os.environ):
         http = http_leg()
     import torch
@@ -445,6 +453,7 @@ def main() -> None:
             comm.close()
             comm = None
             search = ShardedSearch(backend, lo, hi, comm=None)
+    # the exchange check runs without --full too: at N > 1 it decides which exchange `value` is measured through
     elapsed, idx, sc, timers, exchange_verified = measure(search)
     if exchange_verified is False and comm is not None:
         # the library's own exchange (icrec_search_sharded over ncclAllGather) has never run on more than one GPU before
@@ -459,8 +468,10 @@ def main() -> None:
     if exchange_verified is False:
         raise SystemExit(f"rank {rank}: sharded result differs from the unsharded search on the 64-query sample")
     (ffn_ms, ffn_n), (enc_ms, _), (srch_ms, _), (skern_ms, _) = timers
-    n_keep = min(args.cpu_sample, args.batch)  # the timed step's own outputs, kept for the oracle check at the end
-    kept = (emb[:n_keep].cpu().numpy(), idx[:n_keep].cpu().numpy(), sc[:n_keep].cpu().numpy())
+    kept = None
+    if args.full:
+        n_keep = min(args.cpu_sample, args.batch)  # the timed step's own outputs, kept for the oracle check at the end
+        kept = (emb[:n_keep].cpu().numpy(), idx[:n_keep].cpu().numpy(), sc[:n_keep].cpu().numpy())
     dumped = None
     if args.dump_outputs:
         # before any later leg reuses `emb`; at N > 1 the gather is a collective every rank takes part in
@@ -470,12 +481,12 @@ def main() -> None:
                 "query_embeddings": emb_all.cpu().numpy(), "topk_rows": idx.cpu().numpy(), "topk_scores": sc.cpu().numpy()})
         del emb_all
 
-    # ---- BASELINE configs[4] beside it, in the same line at every N: 4,096 user contexts per step in total (4,096 / N
+    # ---- --full: BASELINE configs[4] beside it, in the same line at every N: 4,096 user contexts per step in total (4,096 / N
     # encoded per GPU) against a 10 M x 384 bf16 catalog (+ filter fragments) row-sharded N ways, generated on the device
     # per shard.  north_star's ">= 6x at 8 GPUs on a 10M-row catalog" is the ratio of this leg's `qps` at N = 8 to its
     # value at N = 1 (strong scaling: the total work per step does not change with N).
     leg_10m = None
-    if args.workload == "49k7" and not args.no_10m_leg and not (world == 1 and args.no_latency):
+    if args.full and args.workload == "49k7" and not args.no_10m_leg and not (world == 1 and args.no_latency):
         q_total = 4096 - 4096 % world
         per_rank = q_total // world
         be10, lo10, hi10, _ = make_shard(args.rows_10m, True, "bf16+filter")
@@ -510,7 +521,7 @@ def main() -> None:
     # timed region above keeps ONE icrec_encode per step so that per-kernel event times and the rocprof
     # averages describe the same launches.
     two_stream = None
-    if rank == 0 and world == 1 and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and not args.no_latency:
         def step2():
             enc.encode_packed(ids_d, cu_d, max_len, out=emb, cu_host=cu_h)
             return search.search(emb, TOP_K)
@@ -528,7 +539,7 @@ def main() -> None:
     # the host / command-processor side.  Not `value`: a serving batch has a different token count every time, and a graph
     # bakes it; reported so that the gap is a number.
     graph_leg = None
-    if rank == 0 and world == 1 and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and not args.no_latency:
         try:
             g_idx = torch.empty((args.batch, TOP_K), dtype=torch.int64, device=dev)
             g_sc = torch.empty((args.batch, TOP_K), dtype=torch.float32, device=dev)
@@ -570,7 +581,7 @@ def main() -> None:
     # chains), measured in the same run on the same inputs, plus how far the default mode's embeddings and
     # top-20 lists are from it: the record carries a plain-fp32 number next to the f16x3 one.
     f32_leg = None
-    if rank == 0 and world == 1 and not args.no_latency and enc.gemm_mode != "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_latency and enc.gemm_mode != "f32":
         enc32 = DeviceEncoder(weights, shape, dev, gemm_mode="f32")
         emb32 = torch.empty_like(emb)
 
@@ -619,7 +630,7 @@ def main() -> None:
     # from token ids in host memory to k results in host memory.  (a) hipGraph replay (fastpath.py,
     # the product path), (b) the same two library calls launched kernel by kernel.
     p50_ms = p50_plain_ms = None
-    if rank == 0 and world == 1 and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and not args.no_latency:
         from instacart_next_order_recommendation_amd.fastpath import SingleRequestPath
 
         n_tok = int(cu_h[1])
@@ -646,7 +657,7 @@ def main() -> None:
     # ---- catalog index build (start-up path, BASELINE configs[1]): encode 49,688 product texts
     # (token-packed, lengths ~ clipped N(20,5) as SURVEY.md §8d) and build the normalised index
     index_build_ms = None
-    if rank == 0 and world == 1 and args.workload == "49k7" and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and args.workload == "49k7" and not args.no_latency:
         from instacart_next_order_recommendation_amd.search import DeviceIndex
 
         cat_ids, cat_cu = syn.synthetic_token_batch(CATALOG_ROWS, seed=42, mean_len=20, std_len=5, lo=8, hi=40)
@@ -673,7 +684,7 @@ def main() -> None:
     # ---- the same step from TEXT in host memory (not `value`): native tokenizer on the host cores, one
     # H2D of the packed ids, encode + search, D2H of the results — the PCIe- and tokeniser-inclusive rate
     text_path = strings_pipelined = None
-    if rank == 0 and world == 1 and args.workload == "49k7" and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and args.workload == "49k7" and not args.no_latency:
         import tempfile
 
         from instacart_next_order_recommendation_amd.model_io import NativeTokenizer
@@ -735,7 +746,7 @@ def main() -> None:
     # ---- single request from a STRING through the serving objects themselves (what /recommend constructs:
     # MonitoredRecommender, reference src/api/main.py:73): tokenise -> replayed hipGraph(s) -> k results on the host
     p50_rec_ms = p50_mon_ms = mon_fields = None
-    if rank == 0 and world == 1 and args.workload == "49k7" and not args.no_latency:
+    if args.full and rank == 0 and world == 1 and args.workload == "49k7" and not args.no_latency:
         import tempfile
 
         from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
@@ -792,7 +803,7 @@ def main() -> None:
             "metric": "recommend_qps_top20_49k7_catalog" if args.workload == "49k7" else "recommend_qps_top20_10m_catalog",
             "value": q_per_step * args.steps / elapsed,
             "unit": "queries/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "strong" if (world > 1 and args.batch_defaulted and args.workload == "49k7") else "weak",
@@ -860,7 +871,7 @@ def main() -> None:
                                              "the same MFMA roof (x n_gpus); attention and search run partly on other "
                                              "instructions, the roof is the one of the dominant kernel")
         failed_check = None
-        if not args.no_cpu_baseline and world == 1 and args.workload == "49k7":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "49k7":
             n_chk = min(args.cpu_sample, args.batch)
             out["cpu_baseline"] = cpu_baseline(weights, shape, ids_h, cu_h, catalog, n_chk)
             # ---- the line certifies itself: the embeddings and top-20 lists the TIMED step left in HBM for the first

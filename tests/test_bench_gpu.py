@@ -1,0 +1,50 @@
+"""bench.py on one GPU in its plain form (no --full): the headline line, none of the other legs, and the timed step's
+dumped outputs checked against the C oracle (the check a plain run no longer makes itself)."""
+from __future__ import annotations
+
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = Path(__file__).resolve().parents[1]
+
+
+def test_bench_plain_run_single_gpu(tmp_path):
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "64",
+                        "--dump-outputs", str(tmp_path / "dump")],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["metric"] == "recommend_qps_top20_49k7_catalog" and d["unit"] == "queries/s" and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False
+    assert d["dtype"].startswith("f16x3") and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(64 * 1e3 / d["ms_per_step"], rel=1e-9)
+    for leg in ("http", "configs4_10m_rows", "with_two_stream_encode", "with_hipgraph_replay", "exact_f32_gemm_mode",
+                "p50_latency_ms_single_request", "catalog_index_build_ms", "from_text_in_host_memory",
+                "from_strings_pipelined", "monitored_recommend", "cpu_baseline", "exchange_verified"):
+        assert d[leg] is None, leg
+    assert "checked_vs_oracle" not in d
+    assert d["dumped_outputs"]["rows"] == d["dumped_outputs"]["of_rows"] == 64
+
+    from instacart_next_order_recommendation_amd import synthetic as syn
+    from oracle import oracle
+
+    emb = np.load(tmp_path / "dump" / "query_embeddings.npy")
+    rows = np.load(tmp_path / "dump" / "topk_rows.npy").astype(np.int64)
+    sc = np.load(tmp_path / "dump" / "topk_scores.npy")
+    assert emb.shape == (64, 384) and rows.shape == sc.shape == (64, 20)
+    shape = syn.BertShape()
+    ids, cu = syn.synthetic_token_batch(64, seed=1234)  # bench.py's step input at --batch 64, rank 0
+    n = 8
+    want = oracle.encode(syn.synthetic_bert_weights(shape, seed=0),
+                         oracle.make_cfg(vocab_size=shape.vocab_size, n_normalize=shape.n_normalize), ids[:cu[n]], cu[:n + 1])
+    assert float(np.abs(emb[:n] - want).max()) < 5e-6
+    P = syn.synthetic_embeddings(49_688, 384, seed=1)  # bench.py's catalog
+    wi, ws = oracle.search(emb, P, 20, None)
+    np.testing.assert_array_equal(rows, wi)
+    np.testing.assert_array_equal(sc, ws)

@@ -161,7 +161,9 @@ def test_bench_rejects_zero_timed_steps(monkeypatch):
         assert exc.value.code == 2
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
     a = bench.parse()
-    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out"
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out" and not a.full  # a plain run unless asked
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full
 
 
 def test_bench_dump_outputs_formats_and_cap(tmp_path):

@@ -63,13 +63,13 @@ def test_two_ranks_real_kernels_equal_unsharded(tmp_path):
 def test_bench_multi_rank_flow_rehearsal(tmp_path):
     """The BARE form the driver uses, `python bench.py --gpus 2 ...` without a launcher: bench.py starts its own two
     ranks as a fresh child (torch.distributed.run), relays rank 0's line and exits with the child's code.  Rehearsal
-    mode: both ranks on cuda:0, gloo.  The line carries the configs[4] leg (here 300,000 rows instead of 10 M) and the
-    verdict of the exchange check, exclusion exchange included.  --dump-outputs: rank 0 writes the timed step's outputs
-    for the whole gathered batch, both ranks' query embeddings in rank order."""
+    mode: both ranks on cuda:0, gloo.  With --full the line carries the configs[4] leg (here 300,000 rows instead of
+    10 M) and the verdict of the exchange check, exclusion exchange included.  --dump-outputs: rank 0 writes the timed
+    step's outputs for the whole gathered batch, both ranks' query embeddings in rank order."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", ICREC_BENCH_REHEARSAL="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64",
-                        "--rows-10m", "300000", "--dump-outputs", str(tmp_path / "dump")],
+                        "--rows-10m", "300000", "--dump-outputs", str(tmp_path / "dump"), "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

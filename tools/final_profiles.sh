@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 B="python3 bench.py --no-cpu-baseline --no-latency"
 if [ "$1" != "pmc" ]; then   # `pmc`: only the counter passes
 python -m pytest tests -q -m gpu > $O/gpu_tests.log 2>&1; echo "exit=$?" >> $O/gpu_tests.log; tail -2 $O/gpu_tests.log
-python bench.py > $O/bench.json 2> $O/bench.err && echo bench-ok
+python bench.py --full > $O/bench.json 2> $O/bench.err && echo bench-ok
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $B --steps 10 --warmup 2 > $O/bench_under_rocprof.json 2> $O/trace.err && echo trace-ok
 python tools/prof_summary.py $O/trace > $O/kernel_summary.txt
 cp $(ls $O/trace/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv
