@@ -143,6 +143,49 @@ def check(rc: int, what: str) -> None:
         raise IcrecError(f"{what} failed (status {rc}): {msg}")
 
 
+def ptr(t) -> C.c_void_p:
+    """A tensor's address as a `void *` argument; NULL for None."""
+    return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def stream_ptr(device) -> C.c_void_p:
+    """The current stream of a HIP device as a `hipStream_t` argument."""
+    import torch
+
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def hip_device(device, who: str):
+    """`device` as a torch.device with its index filled in; anything but a cuda/HIP device raises."""
+    import torch
+
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise IcrecError(f"{who} needs a CUDA/HIP device; there is no CPU fallback")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+class StreamScratch(dict):
+    """Grow-only scratch blocks by stream handle, ONE PER STREAM: calls issued on different streams (pipeline.py
+    searches on a side stream while the caller may use the same object from its own) never share scratch memory, and
+    a block is only ever allocated, used and dropped on the stream it belongs to, so the caching allocator's
+    stream-ordered reuse is safe when it grows."""
+
+    def __init__(self, device):
+        super().__init__()
+        self.device = device
+
+    def block(self, need: int):
+        """The current stream's block, at least `need` bytes."""
+        import torch
+
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        if key not in self or self[key].numel() < need:
+            self.pop(key, None)  # the old block is freed before the larger one is allocated
+            self[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self[key]
+
+
 def timing_enable(on: bool) -> None:
     lib().icrec_timing_enable(1 if on else 0)
 

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _native
+from ._native import ptr, stream_ptr
 from .synthetic import BertShape
 
 DEFAULT_GEMM_MODE = "f16x3"
@@ -50,11 +51,7 @@ class DeviceEncoder:
         ceiling is min(256, shape.max_position) by default and only ever raised: a larger value sets it
         (icrec_encoder_set_max_seqlen), a smaller one keeps the default.  Sequences of up to 256 tokens encode
         to the same bits whatever the ceiling."""
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.IcrecError("DeviceEncoder needs a CUDA/HIP device; there is no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _native.hip_device(device, "DeviceEncoder")
         self.shape = shape
         L = _native.lib()
         import os
@@ -81,7 +78,7 @@ class DeviceEncoder:
                 self.close()
                 raise
             self.max_seq_length = int(max_seq_length)
-        self._ws_slots: dict[int, Optional[torch.Tensor]] = {}
+        self._ws_by_stream = _native.StreamScratch(self.device)
         self._side: Optional[torch.cuda.Stream] = None
 
     def close(self) -> None:
@@ -95,21 +92,15 @@ class DeviceEncoder:
         except Exception:
             pass
 
-    def _workspace(self, total_tokens: int, n_seqs: int, slot: int = 0) -> torch.Tensor:
-        need = int(_native.lib().icrec_encode_workspace_bytes(self._h, total_tokens, n_seqs))
-        ws = self._ws_slots.get(slot)
-        if ws is None or ws.numel() < need:
-            self._ws_slots[slot] = None
-            ws = self._ws_slots[slot] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return ws
-
-    def _encode_call(self, ids: torch.Tensor, cu: torch.Tensor, n: int, T: int, max_seqlen: int, out: torch.Tensor,
-                     slot: int) -> None:
-        ws = self._workspace(T, n, slot)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _native.check(_native.lib().icrec_encode(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(cu.data_ptr()), n, T,
-                                                 int(max_seqlen), C.c_void_p(out.data_ptr()),
-                                                 C.c_void_p(ws.data_ptr()), ws.numel(), st), "icrec_encode")
+    def encode_into(self, ids: torch.Tensor, cu: torch.Tensor, n: int, T: int, max_seqlen: int, out: torch.Tensor,
+                    ws: Optional[torch.Tensor] = None) -> None:
+        """One icrec_encode on the current stream: device int32 ids[T] and cu_seqlens[n+1] -> out float32 [n, hidden].
+        `ws`: a workspace the caller owns (a captured graph bakes its address); by default this stream's block."""
+        L = _native.lib()
+        if ws is None:
+            ws = self._ws_by_stream.block(int(L.icrec_encode_workspace_bytes(self._h, T, n)))
+        _native.check(L.icrec_encode(self._h, ptr(ids), ptr(cu), n, T, int(max_seqlen), ptr(out), ptr(ws), ws.numel(),
+                                     stream_ptr(self.device)), "icrec_encode")
 
     def encode_packed(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int,
                       out: Optional[torch.Tensor] = None, cu_host: Optional[np.ndarray] = None) -> torch.Tensor:
@@ -127,7 +118,7 @@ class DeviceEncoder:
         if out is None:
             out = torch.empty((n, self.shape.hidden), dtype=torch.float32, device=self.device)
         if cu_host is None or n < 2 * self.SPLIT_MIN_SEQS or T < 2 * self.SPLIT_MIN_TOKENS:
-            self._encode_call(ids, cu, n, T, max_seqlen, out, 0)
+            self.encode_into(ids, cu, n, T, max_seqlen, out)
             return out
         half = n // 2
         t_half = int(cu_host[half])
@@ -140,15 +131,15 @@ class DeviceEncoder:
             self._side = torch.cuda.Stream(self.device)
         self._side.wait_stream(main)
         with torch.cuda.stream(self._side):
-            self._encode_call(ids[t_half:], cu_b, n - half, T - t_half, max_seqlen, out[half:], 1)
-        self._encode_call(ids[:t_half], cu[: half + 1], half, t_half, max_seqlen, out[:half], 0)
+            self.encode_into(ids[t_half:], cu_b, n - half, T - t_half, max_seqlen, out[half:])
+        self.encode_into(ids[:t_half], cu[: half + 1], half, t_half, max_seqlen, out[:half])
         main.wait_stream(self._side)
         return out
 
     def encode_packed_host(self, ids: np.ndarray, cu: np.ndarray, max_tokens_per_call: int = 1 << 18) -> torch.Tensor:
         """Host arrays in the packed form (ids int32[T], cu_seqlens int32[n+1], e.g. HostTokenizer.packed) ->
         embeddings [n, hidden] on the device, in input order; split into calls of at most
-        `max_tokens_per_call` tokens like encode_ids."""
+        `max_tokens_per_call` tokens."""
         n = int(cu.shape[0]) - 1
         out = torch.empty((n, self.shape.hidden), dtype=torch.float32, device=self.device)
         if n == 0:
@@ -173,22 +164,9 @@ class DeviceEncoder:
         return out
 
     def encode_ids(self, seqs: Sequence[Sequence[int]], max_tokens_per_call: int = 1 << 18) -> torch.Tensor:
-        """Host token-id lists -> embeddings [n, hidden] on the device, in input order.
-        Long inputs are split into calls of at most `max_tokens_per_call` tokens."""
-        n = len(seqs)
-        out = torch.empty((n, self.shape.hidden), dtype=torch.float32, device=self.device)
-        start = 0
-        while start < n:
-            tok, end = 0, start
-            while end < n and (end == start or tok + len(seqs[end]) <= max_tokens_per_call):
-                tok += len(seqs[end])
-                end += 1
-            ids, cu, mx = pack_token_ids(seqs[start:end], self.max_seq_length)
-            vmax = int(ids.max()) if ids.size else 0
-            if ids.min() < 0 or vmax >= self.shape.vocab_size:
-                raise ValueError(f"token id out of range [0, {self.shape.vocab_size})")
-            self.encode_packed(torch.from_numpy(ids).to(self.device, non_blocking=True),
-                               torch.from_numpy(cu).to(self.device, non_blocking=True), mx, out=out[start:end],
-                               cu_host=cu)
-            start = end
-        return out
+        """Host token-id lists -> embeddings [n, hidden] on the device, in input order: pack_token_ids, then
+        encode_packed_host."""
+        if len(seqs) == 0:
+            return torch.empty((0, self.shape.hidden), dtype=torch.float32, device=self.device)
+        ids, cu, _ = pack_token_ids(seqs, self.max_seq_length)
+        return self.encode_packed_host(ids, cu, max_tokens_per_call)

@@ -14,9 +14,6 @@ from __future__ import annotations
 
 from typing import Optional, Sequence
 
-import ctypes as C
-
-import numpy as np
 import torch
 
 from . import _native
@@ -57,18 +54,12 @@ class _Captured:
         L = _native.lib()
         self.enc_ws = torch.empty(int(L.icrec_encode_workspace_bytes(enc._h, bucket, 1)), dtype=torch.uint8, device=dev)
         self.srch_ws = torch.empty(int(L.icrec_search_workspace_bytes(index._h, 1, k)), dtype=torch.uint8, device=dev)
-        P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
 
         def body_encode():
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _native.check(L.icrec_encode(enc._h, P(self.ids), P(self.cu), 1, bucket, bucket, P(self.emb),
-                                         P(self.enc_ws), self.enc_ws.numel(), st), "icrec_encode")
+            enc.encode_into(self.ids, self.cu, 1, bucket, bucket, self.emb, self.enc_ws)
 
         def body_search():
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _native.check(L.icrec_search(index._h, P(self.emb), 1, k, P(self.excl_idx), P(self.excl_off),
-                                         P(self.out_idx), P(self.out_sc), P(self.srch_ws), self.srch_ws.numel(), st),
-                          "icrec_search")
+            index.search_into(self.emb, k, self.excl_idx, self.excl_off, self.out_idx, self.out_sc, self.srch_ws)
 
         self._bodies = (body_encode, body_search)
         side = torch.cuda.Stream(device=dev)
@@ -110,15 +101,6 @@ class SingleRequestPath:
         ceiling = encoder.max_seq_length
         self.buckets = BUCKETS + ((ceiling,) if ceiling > BUCKETS[-1] else ())
         self._graphs: dict[tuple[int, int], _Captured] = {}
-        self._handles = self._handle_key()
-
-    def _handle_key(self):
-        return (self.encoder._h.value if self.encoder._h else None, self.index._h.value if self.index._h else None)
-
-    def invalidate(self) -> None:
-        """Drop every captured graph (they bake raw handles, buffers and workspaces)."""
-        self._graphs.clear()
-        self._handles = self._handle_key()
 
     def supports(self, n_tokens: int, k: int, n_excluded: int) -> bool:
         return 1 <= n_tokens <= self.buckets[-1] and n_excluded <= MAX_EXCLUDED and k <= self.index.n_rows
@@ -131,9 +113,7 @@ class SingleRequestPath:
         ex = sorted(set(int(r) for r in excluded_rows)) if excluded_rows else []
         if not self.supports(n, k, len(ex)):
             raise ValueError("request outside the captured fast path")
-        if self._handle_key() != self._handles:  # encoder / index re-created under us (close() + new handle)
-            self.invalidate()
-        if self._handles[0] is None or self._handles[1] is None:
+        if not self.encoder._h or not self.index._h:
             raise _native.IcrecError("SingleRequestPath: encoder or index handle is closed")
         bucket = next(b for b in self.buckets if n <= b)
         c = self._graphs.get((bucket, k))

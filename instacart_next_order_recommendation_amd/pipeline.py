@@ -19,14 +19,13 @@ import numpy as np
 import torch
 
 
-def pipelined_search(tokenizer: Callable[[Sequence[str]], list], encoder, search: Callable, batches: Iterable[Sequence[str]],
+def pipelined_search(tokenizer, encoder, search: Callable, batches: Iterable[Sequence[str]],
                      k: int, exclude: Optional[Callable[[int], Optional[list]]] = None
                      ) -> Iterator[tuple[np.ndarray, np.ndarray]]:
     """Yields (idx int64 [n, k], score float32 [n, k]) per batch, in batch order.
 
-    tokenizer: texts -> list of token-id lists (host); if it has a `packed(texts)` method (HostTokenizer,
-    NativeTokenizer) that form is used instead: (ids, cu_seqlens) arrays without per-sequence Python lists.
-    encoder: DeviceEncoder.  search: (emb, k, exclude_lists) -> (idx, score) device tensors.
+    tokenizer: needs `packed(texts)` -> (ids int32[T], cu_seqlens int32[n+1]) host arrays (HostTokenizer,
+    NativeTokenizer).  encoder: DeviceEncoder.  search: (emb, k, exclude_lists) -> (idx, score) device tensors.
     exclude(i): per-query exclusion rows of batch i, or None."""
     device = encoder.device
     stream = torch.cuda.current_stream(device)
@@ -35,11 +34,9 @@ def pipelined_search(tokenizer: Callable[[Sequence[str]], list], encoder, search
     side = torch.cuda.Stream(device) if os.getenv("ICREC_PIPELINE_SIDE", "1") != "0" else stream
     it = iter(batches)
 
-    packed = getattr(tokenizer, "packed", None)
-
     def fetch(pool):
         b = next(it, None)
-        return None if b is None else pool.submit(packed or tokenizer, list(b))
+        return None if b is None else pool.submit(tokenizer.packed, list(b))
 
     def collect(p):
         ev, idx_h, sc_h = p
@@ -53,8 +50,8 @@ def pipelined_search(tokenizer: Callable[[Sequence[str]], list], encoder, search
         while fut is not None:
             ids = fut.result()
             fut = fetch(pool)                      # batch i+1 is tokenised while batch i is launched and runs
-            if (ids[1].shape[0] > 1) if packed else bool(ids):
-                emb = encoder.encode_packed_host(*ids) if packed else encoder.encode_ids(ids)
+            if ids[1].shape[0] > 1:
+                emb = encoder.encode_packed_host(*ids)
                 encoded = torch.cuda.Event()
                 encoded.record(stream)
                 excl = exclude(i) if exclude is not None else None

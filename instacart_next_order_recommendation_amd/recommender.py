@@ -121,10 +121,7 @@ class SbertModel:
 
     def encode_to_device(self, texts: Sequence[str], tokens_per_call: int = 1 << 18) -> torch.Tensor:
         """Embeddings [n, 384] left on the GPU (serving path: no host round trip)."""
-        packed = getattr(self.tokenizer, "packed", None)
-        if packed is not None:
-            return self.encoder.encode_packed_host(*packed(texts), max_tokens_per_call=tokens_per_call)
-        return self.encoder.encode_ids(self.tokenizer(texts), max_tokens_per_call=tokens_per_call)
+        return self.encoder.encode_packed_host(*self.tokenizer.packed(texts), max_tokens_per_call=tokens_per_call)
 
     def encode(self, sentences, batch_size: int = 64, show_progress_bar: bool = False,
                normalize_embeddings: bool = True, **_ignored) -> np.ndarray:
@@ -148,10 +145,8 @@ class SbertModel:
                                                       self.device, gemm_mode=self.encoder.gemm_mode,
                                                       max_seq_length=self.max_seq_length)
             enc = self._encoder_no_flag
-        packed = getattr(self.tokenizer, "packed", None)
         per_call = max(int(batch_size), 1) * 4096
-        emb = (enc.encode_packed_host(*packed(texts), max_tokens_per_call=per_call) if packed is not None
-               else enc.encode_ids(self.tokenizer(texts), max_tokens_per_call=per_call)).cpu().numpy()
+        emb = enc.encode_packed_host(*self.tokenizer.packed(texts), max_tokens_per_call=per_call).cpu().numpy()
         return emb[0] if single else emb
 
 
@@ -221,18 +216,54 @@ class Recommender:
         return embeddings
 
     # -- the hot path -------------------------------------------------------------------------
-    def _excluded_rows(self, exclude_product_ids) -> list[int]:
-        if not exclude_product_ids:
-            return []
-        return [self._pid_to_row[p] for p in exclude_product_ids if p in self._pid_to_row]
-
-    def _rank(self, query_emb: torch.Tensor, top_k: int, exclude_lists: Optional[list[list[int]]]):
-        k = min(int(top_k), _native.ICREC_MAX_K, len(self.product_ids))
+    def _k(self, top_k: int) -> int:
+        """The search width for a request's top_k, checked before any GPU work: at least 1 (the reference's loop
+        appends before testing len >= top_k, :223-224), at most the catalog."""
+        top_k = max(int(top_k), 1)
         if top_k > _native.ICREC_MAX_K:
             raise ValueError(f"top_k={top_k} exceeds the kernel limit {_native.ICREC_MAX_K} "
                              "(the API schema allows at most 100)")
-        idx, sc = self._index.search(query_emb, k, exclude_lists)
-        return idx.cpu().numpy(), sc.cpu().numpy()
+        return min(top_k, len(self.product_ids))
+
+    def _exclusion_rows(self, exclude_product_ids) -> Optional[list[list[int]]]:
+        """Per-query product-id sets -> per-query catalog rows, or None when nothing is excluded."""
+        if exclude_product_ids is None or not any(exclude_product_ids):
+            return None
+        return [[self._pid_to_row[p] for p in e if p in self._pid_to_row] if e else [] for e in exclude_product_ids]
+
+    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False):
+        """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
+        current stream; timed=True adds (encode ms, search ms) from HIP events around the two."""
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
+        stream = torch.cuda.current_stream(self.device)
+        if ev:
+            ev[0].record(stream)
+        emb = self.model.encoder.encode_packed_host(ids, cu)
+        if ev:
+            ev[1].record(stream)
+        idx, sc = self._index.search(emb, k, ex)
+        if ev:
+            ev[2].record(stream)
+        idx, sc = idx.cpu().numpy(), sc.cpu().numpy()  # synchronises the stream
+        return (idx, sc, ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])) if ev else (idx, sc)
+
+    def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False):
+        """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path.
+        -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
+        k = self._k(top_k)
+        t0 = time.time()
+        ids, cu = self.model.tokenizer.packed([query])
+        tok_ms = (time.time() - t0) * 1000
+        ex = self._exclusion_rows([exclude_product_ids])
+        rows = ex[0] if ex else []
+        fast = self._fast_path()
+        if fast is not None and fast.supports(len(ids), k, len(rows)):
+            idx, sc, *ms = fast.run(ids, k, rows, timed=timed)
+        else:
+            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed)
+            idx, sc = idx[0], sc[0]
+        results = self._to_results(idx, sc)
+        return (results, tok_ms + ms[0], ms[1]) if timed else results
 
     def _to_results(self, idx_row: np.ndarray, sc_row: np.ndarray) -> list[tuple[str, float]]:
         return [(self.product_ids[int(i)], float(s)) for i, s in zip(idx_row, sc_row) if i >= 0]
@@ -243,12 +274,9 @@ class Recommender:
         """Many contexts in one GPU pass; element i equals recommend(queries[i], ...)."""
         if not queries:
             return []
-        top_k = max(int(top_k), 1)  # the reference's loop appends before testing len >= top_k (:223-224)
-        ex = None
-        if exclude_product_ids is not None and any(exclude_product_ids):
-            ex = [self._excluded_rows(e) for e in exclude_product_ids]
-        emb = self.model.encode_to_device(list(queries))
-        idx, sc = self._rank(emb, top_k, ex)
+        k = self._k(top_k)
+        ex = self._exclusion_rows(exclude_product_ids)
+        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))]
 
     def recommend_batches(self, batches, top_k: int = 10, exclude_product_ids=None):
@@ -257,15 +285,10 @@ class Recommender:
         batch j is read back after batch j+1 has been launched (pipeline.py)."""
         from .pipeline import pipelined_search
 
-        top_k = max(int(top_k), 1)
-        if top_k > _native.ICREC_MAX_K:
-            raise ValueError(f"top_k={top_k} exceeds the kernel limit {_native.ICREC_MAX_K} "
-                             "(the API schema allows at most 100)")
-        k = min(top_k, len(self.product_ids))
+        k = self._k(top_k)
 
         def exclude(j):
-            e = exclude_product_ids[j] if exclude_product_ids is not None else None
-            return [self._excluded_rows(x) for x in e] if e is not None and any(e) else None
+            return self._exclusion_rows(exclude_product_ids[j]) if exclude_product_ids is not None else None
 
         for idx, sc in pipelined_search(self.model.tokenizer, self.model.encoder, self._index.search, batches, k, exclude):
             yield [self._to_results(idx[i], sc[i]) for i in range(idx.shape[0])]
@@ -273,41 +296,19 @@ class Recommender:
     def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None):
         """recommend_batch plus (embedding ms incl. host tokenisation, similarity ms) from HIP events
         on the launch stream — what the micro-batching server reports as per-request stats."""
-        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-        top_k = max(int(top_k), 1)
-        ex = None
-        if exclude_product_ids is not None and any(exclude_product_ids):
-            ex = [self._excluded_rows(e) for e in exclude_product_ids]
+        k = self._k(top_k)
+        ex = self._exclusion_rows(exclude_product_ids)
         t0 = time.time()
-        packed = getattr(self.model.tokenizer, "packed", None)
-        ids = packed(list(queries)) if packed is not None else self.model.tokenizer(list(queries))
+        ids, cu = self.model.tokenizer.packed(list(queries))
         tok_ms = (time.time() - t0) * 1000
-        stream = torch.cuda.current_stream(self.device)
-        e0.record(stream)
-        emb = self.model.encoder.encode_packed_host(*ids) if packed is not None else self.model.encoder.encode_ids(ids)
-        e1.record(stream)
-        if top_k > _native.ICREC_MAX_K:
-            raise ValueError(f"top_k={top_k} exceeds the kernel limit {_native.ICREC_MAX_K}")
-        idx_d, sc_d = self._index.search(emb, min(top_k, len(self.product_ids)), ex)
-        e2.record(stream)
-        idx, sc = idx_d.cpu().numpy(), sc_d.cpu().numpy()
-        return ([self._to_results(idx[i], sc[i]) for i in range(len(queries))],
-                tok_ms + e0.elapsed_time(e1), e1.elapsed_time(e2))
+        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True)
+        return [self._to_results(idx[i], sc[i]) for i in range(len(queries))], tok_ms + enc_ms, sim_ms
 
     def recommend(self, query: str, top_k: int = 10,
                   exclude_product_ids: set[str] | None = None) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
         One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0"."""
-        fast = self._fast_path()
-        if fast is not None:
-            top_k = max(int(top_k), 1)
-            ids = self.model.tokenizer([query])[0]
-            ex = self._excluded_rows(exclude_product_ids)
-            k = min(top_k, len(self.product_ids))
-            if top_k <= _native.ICREC_MAX_K and fast.supports(len(ids), k, len(ex)):
-                idx, sc = fast.run(ids, k, ex)
-                return self._to_results(idx, sc)
-        return self.recommend_batch([query], top_k, [exclude_product_ids])[0]
+        return self._recommend_one(query, top_k, exclude_product_ids)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -329,37 +330,10 @@ class MonitoredRecommender(Recommender):
 
     def recommend(self, query: str, top_k: int = 10, user_id: Optional[str] = None,
                   exclude_product_ids: set[str] | None = None) -> list[tuple[str, float]]:
+        """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
+        replays (fastpath.py): the three timing fields keep their meaning there."""
         start = time.time()
-        top_k = max(int(top_k), 1)  # the reference's loop appends before testing len >= top_k (:259-262)
-        t_tok = time.time()
-        ids = self.model.tokenizer([query])
-        tok_ms = (time.time() - t_tok) * 1000
-        fast = self._fast_path()
-        if fast is not None and top_k <= _native.ICREC_MAX_K:
-            # the same replayed request as Recommender.recommend, cut at the encode / search seam with HIP events
-            # around the two replays (fastpath.py): the three timing fields keep their meaning on the graph path
-            ex_rows = self._excluded_rows(exclude_product_ids)
-            k = min(top_k, len(self.product_ids))
-            if fast.supports(len(ids[0]), k, len(ex_rows)):
-                idx1, sc1, enc_ms, sim_ms = fast.run(ids[0], k, ex_rows, timed=True)
-                results = self._to_results(idx1, sc1)
-                self.note_served(results, user_id, tok_ms + enc_ms, sim_ms, (time.time() - start) * 1000)
-                return results
-        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-        stream = torch.cuda.current_stream(self.device)
-        e0.record(stream)
-        emb = self.model.encoder.encode_ids(ids)
-        e1.record(stream)
-        ex = [self._excluded_rows(exclude_product_ids)] if exclude_product_ids else None
-        k = min(top_k, len(self.product_ids))
-        if top_k > _native.ICREC_MAX_K:
-            raise ValueError(f"top_k={top_k} exceeds the kernel limit {_native.ICREC_MAX_K}")
-        idx_d, sc_d = self._index.search(emb, k, ex)
-        e2.record(stream)
-        idx, sc = idx_d.cpu().numpy(), sc_d.cpu().numpy()  # synchronises the stream
-        encode_ms = tok_ms + e0.elapsed_time(e1)
-        sim_ms = e1.elapsed_time(e2)
-        results = self._to_results(idx[0], sc[0])
+        results, encode_ms, sim_ms = self._recommend_one(query, top_k, exclude_product_ids, timed=True)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

@@ -17,32 +17,37 @@ import numpy as np
 import torch
 
 from . import _native
+from ._native import ptr, stream_ptr
 
 
-def _stream_ptr(device: torch.device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
-def exclusion_csr(exclude: Optional[Sequence[Iterable[int]]], n_queries: int, device: torch.device):
-    """Per-query iterables of LOCAL row numbers -> (idx int32[nnz], off int32[Q+1]) on `device`
-    (sorted, unique per query), or (None, None) when nothing is excluded."""
+def exclusion_csr(exclude: Optional[Sequence[Iterable[int]]], n_queries: int, device: Optional[torch.device] = None,
+                  excl_cap: Optional[int] = None, of: str = "queries"):
+    """Per-query iterables of row numbers -> (idx int32[nnz], off int32[Q+1]), sorted and unique per query, on
+    `device` (numpy arrays without one); (None, None) when nothing is excluded.  With `excl_cap` (the sharded
+    exchange's fixed id capacity) idx is zero-padded to excl_cap entries and always returned.  `of` names the
+    queries in the count mismatch error."""
     if exclude is None:
         return None, None
     if len(exclude) != n_queries:
-        raise ValueError(f"exclude has {len(exclude)} entries for {n_queries} queries")
+        raise ValueError(f"exclude has {len(exclude)} entries for {n_queries} {of}")
     off = np.zeros(n_queries + 1, np.int32)
     flat: list[int] = []
     for i, e in enumerate(exclude):
         flat.extend(sorted(set(int(v) for v in e)))
         off[i + 1] = len(flat)
-    if not flat:
-        return None, None
-    idx = torch.from_numpy(np.asarray(flat, np.int32)).to(device)
-    return idx, torch.from_numpy(off).to(device)
+    if excl_cap is None:
+        if not flat:
+            return None, None
+        idx = np.asarray(flat, np.int32)
+    else:
+        if len(flat) > excl_cap:
+            raise ValueError(f"{len(flat)} excluded rows on this rank exceed excl_cap={excl_cap} "
+                             "(the same constant on every rank)")
+        idx = np.zeros(excl_cap, np.int32)
+        idx[:len(flat)] = flat
+    if device is None:
+        return idx, off
+    return torch.from_numpy(idx).to(device), torch.from_numpy(off).to(device)
 
 
 ROW_STORAGE = {"f32": 0, "bf16": 1, "f32+filter": 2, "bf16+filter": 3}  # ICREC_ROWS_* in include/icrec.h
@@ -62,11 +67,8 @@ class DeviceIndex:
         if storage not in ROW_STORAGE:
             raise ValueError(f"storage must be one of {sorted(ROW_STORAGE)}, got {storage!r}")
         self.storage = storage
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.IcrecError("DeviceIndex needs a CUDA/HIP device; there is no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _native.hip_device(device, "DeviceIndex")
+        self._ws_by_stream = _native.StreamScratch(self.device)
         L = _native.lib()
         rows = torch.as_tensor(embeddings)
         if rows.dim() != 2:
@@ -76,16 +78,15 @@ class DeviceIndex:
         self.row_offset = int(row_offset)
         h = C.c_void_p()
         torch.cuda.synchronize(self.device)
-        _native.check(L.icrec_index_create_ex(_ptr(rows), self.n_rows, self.dim, self.row_offset, self.device.index,
+        _native.check(L.icrec_index_create_ex(ptr(rows), self.n_rows, self.dim, self.row_offset, self.device.index,
                                               ROW_STORAGE[storage], C.byref(h)), "icrec_index_create_ex")
         self._h = h
-        self._ws_by_stream: dict[int, torch.Tensor] = {}
 
     def close(self) -> None:
         if getattr(self, "_h", None):
             _native.lib().icrec_index_destroy(self._h)
             self._h = None
-        self._ws_by_stream = {}
+        self._ws_by_stream.clear()
 
     def __del__(self):  # pragma: no cover - best effort
         try:
@@ -95,19 +96,11 @@ class DeviceIndex:
 
     # ------------------------------------------------------------------ helpers
     def _workspace(self, n_queries: int, k: int) -> torch.Tensor:
-        """Scratch block for one search, ONE PER STREAM: searches issued on different streams (pipeline.py runs batch
-        i's search on a side stream while the caller may use the index from its own stream) never share scratch memory,
-        and a block is only ever allocated, used and dropped on the stream it belongs to, so the caching allocator's
-        stream-ordered reuse is safe when it grows."""
+        """This stream's scratch block, large enough for one search of this shape."""
         need = int(_native.lib().icrec_search_workspace_bytes(self._h, n_queries, k))
         if need == 0:
             raise _native.IcrecError(f"bad search shape: n_queries={n_queries}, k={k}")
-        key = int(torch.cuda.current_stream(self.device).cuda_stream)
-        ws = self._ws_by_stream.get(key)
-        if ws is None or ws.numel() < need:
-            self._ws_by_stream.pop(key, None)
-            ws = self._ws_by_stream[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return ws
+        return self._ws_by_stream.block(need)
 
     def _queries(self, q) -> torch.Tensor:
         q = torch.as_tensor(q)
@@ -126,19 +119,19 @@ class DeviceIndex:
         ei, eo = exclusion_csr(exclude, Q, self.device)
         idx = torch.empty((Q, k), dtype=torch.int64, device=self.device)
         sc = torch.empty((Q, k), dtype=torch.float32, device=self.device)
-        ws = self._workspace(Q, k)
-        _native.check(_native.lib().icrec_search(self._h, _ptr(q), Q, k, _ptr(ei), _ptr(eo), _ptr(idx), _ptr(sc),
-                                                 _ptr(ws), ws.numel(), _stream_ptr(self.device)), "icrec_search")
+        self.search_into(q, k, ei, eo, idx, sc)
         return idx, sc
 
     def search_into(self, q: torch.Tensor, k: int, excl_idx: Optional[torch.Tensor], excl_off: Optional[torch.Tensor],
-                    out_idx: torch.Tensor, out_score: torch.Tensor) -> None:
+                    out_idx: torch.Tensor, out_score: torch.Tensor, ws: Optional[torch.Tensor] = None) -> None:
         """Allocation-free form of `search` on caller-owned device buffers (hipGraph-capturable once the
-        workspace for this (Q, k) exists): q float32 [Q, dim], out_idx int64 [Q, k], out_score float32 [Q, k]."""
+        workspace for this (Q, k) exists, or with `ws` of the caller's own): q float32 [Q, dim],
+        out_idx int64 [Q, k], out_score float32 [Q, k]."""
         Q = int(q.shape[0])
-        ws = self._workspace(Q, k)
-        _native.check(_native.lib().icrec_search(self._h, _ptr(q), Q, k, _ptr(excl_idx), _ptr(excl_off), _ptr(out_idx),
-                                                 _ptr(out_score), _ptr(ws), ws.numel(), _stream_ptr(self.device)),
+        if ws is None:
+            ws = self._workspace(Q, k)
+        _native.check(_native.lib().icrec_search(self._h, ptr(q), Q, k, ptr(excl_idx), ptr(excl_off), ptr(out_idx),
+                                                 ptr(out_score), ptr(ws), ws.numel(), stream_ptr(self.device)),
                       "icrec_search")
 
     def search_partial(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None) -> torch.Tensor:
@@ -148,8 +141,8 @@ class DeviceIndex:
         ei, eo = exclusion_csr(exclude, Q, self.device)
         keys = torch.empty((Q, k), dtype=torch.int64, device=self.device)
         ws = self._workspace(Q, k)
-        _native.check(_native.lib().icrec_search_partial(self._h, _ptr(q), Q, k, _ptr(ei), _ptr(eo), _ptr(keys),
-                                                         _ptr(ws), ws.numel(), _stream_ptr(self.device)),
+        _native.check(_native.lib().icrec_search_partial(self._h, ptr(q), Q, k, ptr(ei), ptr(eo), ptr(keys),
+                                                         ptr(ws), ws.numel(), stream_ptr(self.device)),
                       "icrec_search_partial")
         return keys
 
@@ -159,8 +152,8 @@ class DeviceIndex:
         Q = int(q.shape[0])
         out = torch.empty((Q, self.n_rows), dtype=torch.float32, device=self.device)
         ws = self._workspace(Q, 1)
-        _native.check(_native.lib().icrec_scores(self._h, _ptr(q), Q, _ptr(out), _ptr(ws), ws.numel(),
-                                                 _stream_ptr(self.device)), "icrec_scores")
+        _native.check(_native.lib().icrec_scores(self._h, ptr(q), Q, ptr(out), ptr(ws), ws.numel(),
+                                                 stream_ptr(self.device)), "icrec_scores")
         return out
 
     def rank_all(self, q) -> torch.Tensor:
@@ -175,14 +168,14 @@ class DeviceIndex:
             raise _native.IcrecError(f"bad rank_all shape: n_queries={Q}")
         ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         out = torch.empty((Q, self.n_rows), dtype=torch.int64, device=self.device)
-        _native.check(L.icrec_rank_all(self._h, _ptr(q), Q, _ptr(out), _ptr(ws), ws.numel(), _stream_ptr(self.device)),
+        _native.check(L.icrec_rank_all(self._h, ptr(q), Q, ptr(out), ptr(ws), ws.numel(), stream_ptr(self.device)),
                       "icrec_rank_all")
         return out
 
     def export(self) -> torch.Tensor:
         """The normalised rows the index holds, [n_rows, dim] fp32 on the device."""
         out = torch.empty((self.n_rows, self.dim), dtype=torch.float32, device=self.device)
-        _native.check(_native.lib().icrec_index_export(self._h, _ptr(out), _stream_ptr(self.device)),
+        _native.check(_native.lib().icrec_index_export(self._h, ptr(out), stream_ptr(self.device)),
                       "icrec_index_export")
         return out
 
@@ -195,8 +188,8 @@ def merge_topk(keys: torch.Tensor, k: int):
     n_lists, Q = int(keys.shape[0]), int(keys.shape[1])
     idx = torch.empty((Q, k), dtype=torch.int64, device=keys.device)
     sc = torch.empty((Q, k), dtype=torch.float32, device=keys.device)
-    _native.check(_native.lib().icrec_merge_topk(_ptr(keys), n_lists, Q, k, _ptr(idx), _ptr(sc), keys.device.index,
-                                                 _stream_ptr(keys.device)), "icrec_merge_topk")
+    _native.check(_native.lib().icrec_merge_topk(ptr(keys), n_lists, Q, k, ptr(idx), ptr(sc), keys.device.index,
+                                                 stream_ptr(keys.device)), "icrec_merge_topk")
     return idx, sc
 
 
@@ -204,6 +197,6 @@ def normalize_rows(x: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
     """x / max(|x|_2, eps) row-wise on the device (torch.nn.functional.normalize as cos_sim uses it)."""
     x = x.to(dtype=torch.float32).contiguous()
     out = torch.empty_like(x)
-    _native.check(_native.lib().icrec_normalize_rows(_ptr(x), _ptr(out), x.shape[0], x.shape[1], eps,
-                                                     x.device.index, _stream_ptr(x.device)), "icrec_normalize_rows")
+    _native.check(_native.lib().icrec_normalize_rows(ptr(x), ptr(out), x.shape[0], x.shape[1], eps,
+                                                     x.device.index, stream_ptr(x.device)), "icrec_normalize_rows")
     return out

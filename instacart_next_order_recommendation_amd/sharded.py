@@ -29,6 +29,10 @@ from typing import Iterable, Optional, Protocol, Sequence
 import torch
 import torch.distributed as dist
 
+from . import _native
+from ._native import ptr, stream_ptr
+from .search import DeviceIndex, exclusion_csr, merge_topk
+
 
 def shard_bounds(n_rows: int, world: int) -> list[int]:
     """Even row split; the first n_rows % world shards get one extra row."""
@@ -44,8 +48,6 @@ def exclusions_to_shard_csr(off_all: torch.Tensor, rows_all: torch.Tensor, row_l
     gathered buffers `off_all` int32 [world, n_local + 1] and `rows_all` int32 [world, excl_cap] (GLOBAL rows) ->
     (csr_off int32 [world * n_local + 1], csr_idx int32 [world * excl_cap]) of LOCAL rows for the shard
     [row_lo, row_hi), as icrec_search / icrec_search_partial take them."""
-    from . import _native
-
     if off_all.dtype != torch.int32 or rows_all.dtype != torch.int32 or off_all.dim() != 2 or rows_all.dim() != 2 \
             or off_all.shape[0] != rows_all.shape[0] or not off_all.is_cuda or rows_all.device != off_all.device:
         raise ValueError("off_all int32 [world, n_local + 1] and rows_all int32 [world, excl_cap] on one HIP device")
@@ -55,11 +57,9 @@ def exclusions_to_shard_csr(off_all: torch.Tensor, rows_all: torch.Tensor, row_l
     ws = torch.empty(int(L.icrec_exclusions_to_shard_csr_workspace_bytes(world, n_local)), dtype=torch.uint8, device=dev)
     csr_off = torch.empty(world * n_local + 1, dtype=torch.int32, device=dev)
     csr_idx = torch.zeros(world * cap, dtype=torch.int32, device=dev)
-    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    _native.check(L.icrec_exclusions_to_shard_csr(P(off_all.contiguous()), P(rows_all.contiguous()), world, n_local, cap,
-                                                  int(row_lo), int(row_hi), P(csr_off), P(csr_idx), P(ws), ws.numel(),
-                                                  dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                  "icrec_exclusions_to_shard_csr")
+    _native.check(L.icrec_exclusions_to_shard_csr(ptr(off_all.contiguous()), ptr(rows_all.contiguous()), world, n_local,
+                                                  cap, int(row_lo), int(row_hi), ptr(csr_off), ptr(csr_idx), ptr(ws),
+                                                  ws.numel(), dev.index, stream_ptr(dev)), "icrec_exclusions_to_shard_csr")
     return csr_off, csr_idx
 
 
@@ -72,16 +72,12 @@ class HipShardBackend:
     """The product backend: libicrec kernels on this rank's GPU."""
 
     def __init__(self, shard_rows, row_offset: int, device, storage: str = "f32"):
-        from .search import DeviceIndex
-
         self.index = DeviceIndex(shard_rows, device, row_offset=row_offset, storage=storage)
 
     def search_partial(self, q, k, exclude):
         return self.index.search_partial(q, k, exclude)
 
     def merge(self, keys, k):
-        from .search import merge_topk
-
         return merge_topk(keys, k)
 
 
@@ -89,12 +85,7 @@ class NativeComm:
     """An RCCL communicator owned by libicrec (include/icrec.h: icrec_comm_*): one per process/GPU."""
 
     def __init__(self, rank: int, world: int, device, unique_id: Optional[bytes] = None):
-        from . import _native
-
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _native.IcrecError("NativeComm needs a CUDA/HIP device")
-        self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        self.device = _native.hip_device(device, "NativeComm")
         self.rank, self.world = int(rank), int(world)
         if unique_id is not None and len(unique_id) != _native.COMM_ID_BYTES:
             raise ValueError(f"unique_id must be {_native.COMM_ID_BYTES} bytes")
@@ -107,8 +98,6 @@ class NativeComm:
     @staticmethod
     def unique_id() -> bytes:
         """ncclGetUniqueId (call on ONE rank, ship the bytes to the others)."""
-        from . import _native
-
         buf = C.create_string_buffer(_native.COMM_ID_BYTES)
         _native.check(_native.lib().icrec_comm_unique_id(buf), "icrec_comm_unique_id")
         return buf.raw
@@ -125,8 +114,6 @@ class NativeComm:
         ncclCommInitRank.  A rank that dies inside (4) leaves the others waiting there: that is RCCL's contract and
         cannot be repaired from outside.  The world > 1 RCCL path has run on a one-rank communicator only (no
         multi-GPU box is available to the build); bench.py verifies its first real run against an unsharded search."""
-        from . import _native
-
         if not dist.is_initialized():
             return cls(0, 1, device, None)
         rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -155,8 +142,6 @@ class NativeComm:
 
     def close(self) -> None:
         if getattr(self, "_h", None):
-            from . import _native
-
             _native.lib().icrec_comm_destroy(self._h)
             self._h = None
 
@@ -183,94 +168,44 @@ class ShardedSearch:
             self.world = comm.world
         else:
             self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self._ws_by_stream: dict[int, torch.Tensor] = {}
-
-    def _workspace(self, need: int, device) -> torch.Tensor:
-        """One scratch block per stream (see DeviceIndex._workspace)."""
-        key = int(torch.cuda.current_stream(device).cuda_stream)
-        ws = self._ws_by_stream.get(key)
-        if ws is None or ws.numel() < need:
-            self._ws_by_stream.pop(key, None)
-            ws = self._ws_by_stream[key] = torch.empty(need, dtype=torch.uint8, device=device)
-        return ws
-
-    def _search_native(self, q_local: torch.Tensor, k: int, exclude_global):
-        """icrec_search_sharded: all-gather, shard-local search, all-gather, merge — one C call."""
-        from . import _native
-        from .search import exclusion_csr
-
-        ix = self.backend.index
-        q = q_local.to(device=ix.device, dtype=torch.float32).contiguous()
-        n_local = int(q.shape[0])
-        Q = n_local * self.world
-        ei, eo = exclusion_csr(self._local_exclusions(exclude_global), Q, ix.device) if exclude_global is not None \
-            else (None, None)
-        L = _native.lib()
-        need = int(L.icrec_search_sharded_workspace_bytes(ix._h, self.comm._h, n_local, k))
-        if need == 0:
-            raise _native.IcrecError(f"bad sharded search shape: n_local={n_local}, k={k}")
-        ws = self._workspace(need, ix.device)
-        idx = torch.empty((Q, k), dtype=torch.int64, device=ix.device)
-        sc = torch.empty((Q, k), dtype=torch.float32, device=ix.device)
-        P = lambda t: C.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
-        st = C.c_void_p(torch.cuda.current_stream(ix.device).cuda_stream)
-        _native.check(L.icrec_search_sharded(ix._h, self.comm._h, P(q), n_local, k, P(ei), P(eo), P(idx), P(sc),
-                                             P(ws), ws.numel(), st), "icrec_search_sharded")
-        return idx, sc
+        self._ws_by_stream = _native.StreamScratch(backend.index.device) if comm is not None else None
 
     DEFAULT_EXCL_PER_QUERY = 128  # default id capacity per local query of the exclusion exchange (excl_cap = n_local x this)
 
     def _excl_cap(self, n_local: int, excl_cap: Optional[int]) -> int:
         return int(excl_cap) if excl_cap else n_local * self.DEFAULT_EXCL_PER_QUERY
 
-    @staticmethod
-    def _local_csr(exclude_local, n_local: int, cap: int):
-        """This rank's per-query GLOBAL rows -> (rows int32[cap] zero-padded, off int32[n_local+1]) numpy arrays."""
-        import numpy as np
-
-        if len(exclude_local) != n_local:
-            raise ValueError(f"exclude_local has {len(exclude_local)} entries for {n_local} local queries")
-        off = np.zeros(n_local + 1, np.int32)
-        flat: list[int] = []
-        for i, e in enumerate(exclude_local):
-            flat.extend(sorted(set(int(v) for v in e)))
-            off[i + 1] = len(flat)
-        if len(flat) > cap:
-            raise ValueError(f"{len(flat)} excluded rows on this rank exceed excl_cap={cap} (the same constant on every rank)")
-        rows = np.zeros(cap, np.int32)
-        rows[:len(flat)] = flat
-        return rows, off
-
-    def _search_native_local_excl(self, q_local: torch.Tensor, k: int, exclude_local, excl_cap: Optional[int]):
-        """icrec_search_sharded_excl: every rank hands in the exclusions of ITS queries (global rows); the library
-        exchanges them (two more all-gathers) and applies each list on the shard that holds the rows."""
-        from . import _native
-
-        ix = self.backend.index
+    def _search_native(self, q_local: torch.Tensor, k: int, exclude_global=None, exclude_local=None,
+                       excl_cap: Optional[int] = None):
+        """One C call runs all-gather, shard-local search, all-gather and merge: icrec_search_sharded with the
+        replicated exclusions, or icrec_search_sharded_excl, where every rank hands in the exclusions of ITS queries
+        (global rows) and the library exchanges them (two more all-gathers) and applies each list on the shard that
+        holds the rows."""
+        L, ix = _native.lib(), self.backend.index
         q = q_local.to(device=ix.device, dtype=torch.float32).contiguous()
         n_local = int(q.shape[0])
         Q = n_local * self.world
-        cap = self._excl_cap(n_local, excl_cap)
-        rows_h, off_h = self._local_csr(exclude_local, n_local, cap)
-        rows = torch.from_numpy(rows_h).to(ix.device)
-        off = torch.from_numpy(off_h).to(ix.device)
-        L = _native.lib()
-        need = int(L.icrec_search_sharded_excl_workspace_bytes(ix._h, self.comm._h, n_local, k, cap))
+        if exclude_local is None:
+            call, shape = L.icrec_search_sharded, ""
+            excl = [ptr(t) for t in exclusion_csr(self._local_exclusions(exclude_global), Q, ix.device)]
+            need = L.icrec_search_sharded_workspace_bytes(ix._h, self.comm._h, n_local, k)
+        else:
+            cap = self._excl_cap(n_local, excl_cap)
+            call, shape = L.icrec_search_sharded_excl, f", excl_cap={cap}"
+            excl = [ptr(t) for t in exclusion_csr(exclude_local, n_local, ix.device, cap, "local queries")] + [cap]
+            need = L.icrec_search_sharded_excl_workspace_bytes(ix._h, self.comm._h, n_local, k, cap)
         if need == 0:
-            raise _native.IcrecError(f"bad sharded search shape: n_local={n_local}, k={k}, excl_cap={cap}")
-        ws = self._workspace(need, ix.device)
+            raise _native.IcrecError(f"bad sharded search shape: n_local={n_local}, k={k}{shape}")
+        ws = self._ws_by_stream.block(int(need))
         idx = torch.empty((Q, k), dtype=torch.int64, device=ix.device)
         sc = torch.empty((Q, k), dtype=torch.float32, device=ix.device)
-        P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        st = C.c_void_p(torch.cuda.current_stream(ix.device).cuda_stream)
-        _native.check(L.icrec_search_sharded_excl(ix._h, self.comm._h, P(q), n_local, k, P(rows), P(off), cap, P(idx), P(sc),
-                                                  P(ws), ws.numel(), st), "icrec_search_sharded_excl")
+        _native.check(call(ix._h, self.comm._h, ptr(q), n_local, k, *excl, ptr(idx), ptr(sc), ptr(ws), ws.numel(),
+                           stream_ptr(ix.device)), call.__name__)
         return idx, sc
 
     def _gather_local_exclusions(self, exclude_local, n_local: int, excl_cap: Optional[int]):
         """torch.distributed form of the same exchange: -> per gathered query (rank-major) the global rows."""
-        cap = self._excl_cap(n_local, excl_cap)
-        rows_h, off_h = self._local_csr(exclude_local, n_local, cap)
+        rows_h, off_h = exclusion_csr(exclude_local, n_local, None, self._excl_cap(n_local, excl_cap), "local queries")
         if self.world == 1:
             rows_all, off_all = rows_h[None], off_h[None]
         else:
@@ -310,7 +245,7 @@ class ShardedSearch:
             if exclude_global is not None:
                 raise ValueError("give exclusions either per local query (exclude_local) or replicated (exclude_global)")
             if self.comm is not None:
-                return self._search_native_local_excl(q_local, k, exclude_local, excl_cap)
+                return self._search_native(q_local, k, exclude_local=exclude_local, excl_cap=excl_cap)
             exclude_global = self._gather_local_exclusions(exclude_local, int(q_local.shape[0]), excl_cap)
         if self.comm is not None:
             return self._search_native(q_local, k, exclude_global)

@@ -307,7 +307,7 @@ def test_side_stream_changes_nothing(minilm_weights, monkeypatch):
 
 
 @pytest.mark.parametrize("shape", ["short_batch", "long_batch", "single"])
-def test_workspace_contents_never_leak_into_results(minilm_weights, shape):
+def test_stream_workspace_contents_never_leak_into_results(minilm_weights, shape):
     """The caller-owned workspace may hold anything (here: NaN bit patterns everywhere) — every byte a kernel reads
     must have been written by the same icrec_encode call.  Poisoned and zeroed workspaces give identical bits."""
     import torch
@@ -324,7 +324,7 @@ def test_workspace_contents_never_leak_into_results(minilm_weights, shape):
         ids, cu = syn.synthetic_token_batch(1, seed=5, mean_len=70, std_len=1, lo=69, hi=71)
     args = (torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max()))
     enc.encode_packed(*args)                      # sizes the workspace
-    ws = enc._ws_slots[0]
+    ws = enc._ws_by_stream[torch.cuda.current_stream().cuda_stream]  # the caller's stream's block
     out = []
     for fill in (0xFF, 0x00, 0x7F):
         ws.fill_(fill)

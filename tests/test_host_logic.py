@@ -83,6 +83,21 @@ def test_pack_token_ids():
         pack_token_ids([[0] * 257])
 
 
+def test_top_k_above_the_kernel_limit_is_refused_before_any_encode():
+    from instacart_next_order_recommendation_amd.recommender import Recommender
+
+    class NoModel:
+        def __getattr__(self, name):
+            raise AssertionError(f"model.{name} used before top_k was checked")
+
+    rec = Recommender.__new__(Recommender)
+    rec.model, rec.product_ids, rec._pid_to_row = NoModel(), ["1", "2"], {"1": 0, "2": 1}
+    for call in (lambda: rec.recommend_batch(["milk"], top_k=129), lambda: rec.recommend_batch_timed(["milk"], 129),
+                 lambda: rec.recommend("milk", top_k=129)):
+        with pytest.raises(ValueError, match="top_k=129 exceeds the kernel limit 128"):
+            call()
+
+
 def test_shard_bounds():
     from instacart_next_order_recommendation_amd.sharded import shard_bounds
 
