@@ -62,11 +62,14 @@ typedef struct icrec_index icrec_index;
 /* ------------------------------------------------------------------------- */
 
 typedef struct icrec_bert_cfg {
-    int32_t vocab_size;    /* 30522 for all-MiniLM-L6-v2                     */
-    int32_t hidden;        /* 384  (must be 384 in this build)               */
-    int32_t layers;        /* 6                                              */
-    int32_t heads;         /* 12   (head_dim must be 32 in this build)       */
-    int32_t intermediate;  /* 1536 (must be a multiple of 384)               */
+    int32_t vocab_size;    /* 30522 for all-MiniLM-L6-v2 and BERT-base        */
+    int32_t hidden;        /* 384 (all-MiniLM) or 768 (BERT-base: e5-base-v2,
+                              gte-base, bert-base-nli-mean-tokens)            */
+    int32_t layers;        /* 6 / 12; in [1, 64]                              */
+    int32_t heads;         /* 12: head_dim must be 32 at hidden 384 and 64 at
+                              hidden 768; any other (hidden, heads) pair is
+                              ICREC_EINVAL                                    */
+    int32_t intermediate;  /* 1536 / 3072 (must be a multiple of 384)         */
     int32_t max_position;  /* 512                                            */
     int32_t type_vocab;    /* 2                                              */
     float   ln_eps;        /* 1e-12                                          */
@@ -119,7 +122,7 @@ ICREC_API size_t icrec_encode_workspace_bytes(const icrec_encoder* enc,
  *   cu_seqlens_dev int32[n_seqs+1]      prefix sums of sequence lengths
  *   max_seqlen     longest sequence in the batch (<= the encoder's ceiling:
  *                  256 unless icrec_encoder_set_max_seqlen raised it)
- *   out_dev        float[n_seqs, hidden] L2-normalised sentence embeddings
+ *   out_dev        float[n_seqs, hidden] L2-normalised sentence embeddings (hidden 384 or 768)
  * Padding never enters the math: the reference pads per batch and masks the
  * pad keys to weight exactly 0, so the packed form is the same function.
  * Stream semantics: asynchronous on `stream`; everything the call enqueues is ordered before whatever the caller
@@ -135,7 +138,7 @@ ICREC_API int icrec_encode(icrec_encoder* enc,
                  void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* How icrec_encode will split `total_tokens` (f16x3 mode): main_tokens go through the batch kernels (whole
- * rounds of one 64-token workgroup per CU; the fused FFN kernel sees exactly this many tokens), tail_tokens — a
+ * rounds of one 64-token workgroup per CU; at hidden 384 the fused FFN kernel sees exactly this many tokens), tail_tokens — a
  * remainder of at most 512 tokens — through the small-batch kernels.  Same arithmetic either way; bench.py uses
  * it to count the FLOPs of the launches it times. */
 ICREC_API int icrec_encode_batch_split(const icrec_encoder* enc, int64_t total_tokens,

@@ -345,6 +345,146 @@ __global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __rest
     }
 }
 
+// ---------------------------------------------------------------- attention over 64-dim heads (hidden 768: BERT-base)
+// The same (sequence, head) x 32-query-block mapping, S^T-on-the-accumulator-rows layout and P fed back from the
+// accumulators as attention_kernel / attention_x3_kernel, for head_dim 64: the score chain runs over 64 dims, the output
+// of a wave is two 32 x 32 tiles (dims r and 32 + r of the lane's column).  K and V of one (sequence, head) take twice the
+// LDS of a 32-dim head, so they are staged in chunks of at most ATT64_KC key tiles (256 keys): a sequence of up to 256
+// tokens is staged once; a longer one (the 9-16-tile bucket, up to 512 keys) is staged chunk by chunk, twice - K alone
+// for the row maximum, then K and V for the exponentials and P.V.  Every bucket runs the same two-pass form (the score
+// tiles are computed once for the maximum and once more for the exponentials, each tile consumed by P.V as soon as it
+// exists), and the per-query arithmetic depends neither on the bucket nor on the chunking: a sequence gives the same
+// bits whichever launch serves it.
+constexpr int DH64 = 64;
+constexpr int LDQ64 = 68;    // K LDS row stride of the fp32 kernel (even/odd split layout, as LDQ)
+constexpr int ATT64_KC = 8;  // key tiles staged in LDS at once
+
+// Exact fp32 form (gemm_mode F32): scores on v_mfma_f32_32x32x2_f32, dims in pairs ascending; per 32-key tile the P.V
+// key order of attention_kernel ((e&3) + 8(e>>2) + 4h); denominator: each half-wave's keys ascending, the halves added.
+template <int NKT>
+__global__ __launch_bounds__(NKT * 64) void attention64_kernel(const float* __restrict__ qkv,
+                                                               const int32_t* __restrict__ cu, int heads, int H,
+                                                               float scale_log2e, float* __restrict__ ctx) {
+    constexpr int KC = NKT < ATT64_KC ? NKT : ATT64_KC;
+    __shared__ __attribute__((aligned(16))) float Ks[KC * 32 * LDQ64];
+    __shared__ __attribute__((aligned(16))) float Vs[KC * 32 * DH64];
+    __shared__ float Ls[NKT * 32];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x / heads, hd = blockIdx.x % heads;
+    const int t0 = cu[s], L = cu[s + 1] - t0;
+    const int nkt = (L + 31) >> 5;
+    if (nkt > NKT || (NKT > 1 && nkt <= NKT / 2)) return;  // another bucket's sequence
+    const int ld = 3 * H;
+    const int r = lane & 31, h = lane >> 5, qb = wave;
+    const bool active = qb < nkt;  // wave-uniform; idle waves still take part in the barriers of the staging
+    float4 qf[8];  // this lane's query row: lane half h supplies the even / odd dims of every pair
+    {
+        int qr = qb * 32 + r;
+        qr = qr < L ? qr : L - 1;
+        const float4* qp = reinterpret_cast<const float4*>(qkv + (size_t)(t0 + qr) * ld + hd * DH64);
+#pragma unroll
+        for (int kq = 0; kq < 8; ++kq) {
+            const float4 a = qp[2 * kq], b = qp[2 * kq + 1];
+            qf[kq] = h == 0 ? make_float4(a.x, a.z, b.x, b.z) : make_float4(a.y, a.w, b.y, b.w);
+        }
+    }
+    // key tiles [c0, c0 + KC) -> LDS (K in the even/odd split layout, V row-major); rows past L are clamped
+    auto stage = [&](int c0, bool with_v) {
+        __syncthreads();  // the previous chunk's readers are done
+        const int nk = (nkt - c0 < KC ? nkt - c0 : KC) * 32;
+        for (int id = tid; id < nk * 16; id += NKT * 64) {
+            const int row = id >> 4, c = id & 15;
+            const int key = c0 * 32 + row, rr = key < L ? key : L - 1;
+            const float* src = qkv + (size_t)(t0 + rr) * ld + hd * DH64 + c * 4;
+            const float4 kv = *reinterpret_cast<const float4*>(src + H);
+            float* kp = Ks + row * LDQ64 + (c >> 1) * 8 + (c & 1) * 2;
+            *reinterpret_cast<float2*>(kp) = make_float2(kv.x, kv.z);
+            *reinterpret_cast<float2*>(kp + 4) = make_float2(kv.y, kv.w);
+            if (with_v) *reinterpret_cast<float4*>(Vs + row * DH64 + c * 4) = *reinterpret_cast<const float4*>(src + 2 * H);
+        }
+        __syncthreads();
+    };
+    auto score_tile = [&](int kt, int c0) {  // log2-unit scores of key tile kt (staged from c0), tail keys at -inf
+        f32x16 t;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) t[e] = 0.0f;
+#pragma unroll
+        for (int kq = 0; kq < 8; ++kq) {
+            const float4 kf = *reinterpret_cast<const float4*>(Ks + ((kt - c0) * 32 + r) * LDQ64 + kq * 8 + h * 4);
+            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[kq].x, t, 0, 0, 0);
+            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[kq].y, t, 0, 0, 0);
+            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[kq].z, t, 0, 0, 0);
+            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[kq].w, t, 0, 0, 0);
+        }
+        const bool last = kt == nkt - 1;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            float v = t[e] * scale_log2e;
+            if (last && kt * 32 + acc_row(e, lane) >= L) v = -INFINITY;
+            t[e] = v;
+        }
+        return t;
+    };
+    const bool once = nkt <= KC;  // the whole sequence fits: staged once, K and V
+    if (once) stage(0, true);
+    float mx = -INFINITY;
+    for (int c0 = 0; c0 < nkt; c0 += KC) {
+        if (!once) stage(c0, false);
+        if (active) {
+            const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
+            for (int kt = c0; kt < c1; ++kt) {
+                const f32x16 t = score_tile(kt, c0);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
+            }
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float lsum = 0.0f;
+    f32x16 o[2];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[0][e] = o[1][e] = 0.0f;
+    for (int c0 = 0; c0 < nkt; c0 += KC) {
+        if (!once) stage(c0, true);
+        if (active) {
+            const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
+            for (int kt = c0; kt < c1; ++kt) {
+                f32x16 t = score_tile(kt, c0);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float p = __builtin_amdgcn_exp2f(t[e] - mx);
+                    t[e] = p;
+                    lsum = lsum + p;
+                }
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int key = (kt - c0) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(t[e], Vs[key * DH64 + r], o[0], 0, 0, 0);
+                    o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(t[e], Vs[key * DH64 + 32 + r], o[1], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (!active) return;  // (no barrier below)
+    {
+        const float other = __shfl_xor(lsum, 32, 64);
+        lsum = h == 0 ? lsum + other : other + lsum;
+    }
+    if (h == 0) Ls[wave * 32 + r] = lsum;  // read back by this wave's own lanes only
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int qrow = acc_row(e, lane);
+        const int tq = qb * 32 + qrow;
+        if (tq < L) {
+            const float l = Ls[wave * 32 + qrow];
+            float* dst = ctx + (size_t)(t0 + tq) * H + hd * DH64 + r;
+            dst[0] = o[0][e] / l;
+            dst[32] = o[1][e] / l;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- dispatch order of the attention workgroups
 // order[0 .. n_seqs) = the sequences sorted by key-tile count, longest first (counting sort over the
 // ICREC_MAX_SEQLEN / 32 possible counts; the order inside one count is whatever the atomics give - the workgroups are
@@ -655,6 +795,186 @@ __global__ __launch_bounds__(NKT * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void a
     }
 }
 
+// f16x3 form over 64-dim heads: the products of attention_x3_kernel (S' = 256 S and O' on the 3-term split, one fp32
+// accumulator, p' = 1024 p) in the two-pass form of its long buckets (row maximum from the hi x hi products, exponent
+// clamped), with attention64_kernel's chunked staging.  K as hi/lo planes [key][64] (128-B rows, 16-B chunks XOR-swizzled
+// by key & 7), V as row-major hi/lo planes read through the transposing LDS read.  Output: the context planes, stored
+// straight from the accumulators.
+template <int NKT>
+__global__ __launch_bounds__(NKT * 64) void attention64_x3_kernel(const float* __restrict__ qkv,
+                                                                  const int32_t* __restrict__ cu, int heads, int H,
+                                                                  float scale_log2e, _Float16* __restrict__ ch,
+                                                                  _Float16* __restrict__ cl,
+                                                                  const int32_t* __restrict__ order) {
+    constexpr int KC = NKT < ATT64_KC ? NKT : ATT64_KC;
+    __shared__ __attribute__((aligned(16))) _Float16 Kh[KC * 32 * DH64];
+    __shared__ __attribute__((aligned(16))) _Float16 Kl[KC * 32 * DH64];
+    __shared__ __attribute__((aligned(16))) _Float16 Vh[KC * 32 * DH64];
+    __shared__ __attribute__((aligned(16))) _Float16 Vl[KC * 32 * DH64];
+    __shared__ float Ls[NKT * 32];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sidx = blockIdx.x / heads, hd = blockIdx.x % heads;
+    const int s = order != nullptr ? order[sidx] : sidx;
+    const int t0 = cu[s], L = cu[s + 1] - t0;
+    const int nkt = (L + 31) >> 5;
+    if (nkt > NKT || (NKT > 1 && nkt <= NKT / 2)) return;  // another bucket's sequence
+    const int ld = 3 * H;
+    const int r = lane & 31, h = lane >> 5, qb = wave;
+    const bool active = qb < nkt;
+    half8 qh[4], ql[4];  // B operand of S^T: this lane's query row, dims 16 ks + 8 h .. +7
+    {
+        int qr = qb * 32 + r;
+        qr = qr < L ? qr : L - 1;
+        const float* qp = qkv + (size_t)(t0 + qr) * ld + hd * DH64;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 8 * h);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 8 * h + 4);
+            half4 ah, al, bh, bl;
+            split_act4(a, ah, al);
+            split_act4(b, bh, bl);
+            qh[ks] = half8{ah[0], ah[1], ah[2], ah[3], bh[0], bh[1], bh[2], bh[3]};
+            ql[ks] = half8{al[0], al[1], al[2], al[3], bl[0], bl[1], bl[2], bl[3]};
+        }
+    }
+    auto stage = [&](int c0, bool with_v) {
+        __syncthreads();
+        const int nk = (nkt - c0 < KC ? nkt - c0 : KC) * 32;
+        for (int id = tid; id < nk * 16; id += NKT * 64) {
+            const int row = id >> 4, c = id & 15;  // c: 4-dim group
+            const int key = c0 * 32 + row, rr = key < L ? key : L - 1;
+            const float* src = qkv + (size_t)(t0 + rr) * ld + hd * DH64 + c * 4;
+            half4 khi, klo;
+            split_act4(*reinterpret_cast<const f32x4*>(src + H), khi, klo);
+            const int off = row * DH64 + ((((c >> 1) ^ (row & 7)) << 3) | ((c & 1) << 2));
+            *reinterpret_cast<half4*>(Kh + off) = khi;
+            *reinterpret_cast<half4*>(Kl + off) = klo;
+            if (with_v) {
+                half4 vhi, vlo;
+                split_act4(*reinterpret_cast<const f32x4*>(src + 2 * H), vhi, vlo);
+                *reinterpret_cast<half4*>(Vh + row * DH64 + c * 4) = vhi;
+                *reinterpret_cast<half4*>(Vl + row * DH64 + c * 4) = vlo;
+            }
+        }
+        __syncthreads();
+    };
+    // raw scores S' = 256 S of key tile kt (staged from c0); hi_only: the hi x hi products alone (the row-maximum pass)
+    auto score_tile = [&](int kt, int c0, bool hi_only) {
+        f32x16 t;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) t[e] = 0.0f;
+        const int row = (kt - c0) * 32 + r;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const int off = row * DH64 + (((2 * ks + h) ^ (row & 7)) << 3);
+            const half8 kh = *reinterpret_cast<const half8*>(Kh + off);
+            const half8 kl = *reinterpret_cast<const half8*>(Kl + off);
+            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], t, 0, 0, 0);
+            if (hi_only) continue;
+            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], t, 0, 0, 0);
+            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], t, 0, 0, 0);
+        }
+        if (kt == nkt - 1 && kt * 32 + 32 > L) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+                if (kt * 32 + acc_row(e, lane) >= L) t[e] = -INFINITY;
+        }
+        return t;
+    };
+    f32x16 o[2];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[0][e] = o[1][e] = 0.0f;
+    auto pv_tile = [&](int kt, int c0, const f32x16& pt) {  // o[dt] += P' V for head dims 32 dt + r
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            half8 ph, pl;
+#pragma unroll
+            for (int j = 0; j < 8; j += 2) {
+                half2w a, b;
+                split_pair_prescaled(pt[8 * ks + j], pt[8 * ks + j + 1], a, b);
+                ph[j] = a[0]; ph[j + 1] = a[1];
+                pl[j] = b[0]; pl[j + 1] = b[1];
+            }
+            const int base = (kt - c0) * 32 + 4 * h + 16 * ks;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                const int tr_at = (base + ((lane & 15) >> 2)) * DH64 + 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+                const half4 v0h = lds_read_tr(Vh + tr_at);
+                const half4 v1h = lds_read_tr(Vh + tr_at + 8 * DH64);
+                const half4 v0l = lds_read_tr(Vl + tr_at);
+                const half4 v1l = lds_read_tr(Vl + tr_at + 8 * DH64);
+                const half8 vh = {v0h[0], v0h[1], v0h[2], v0h[3], v1h[0], v1h[1], v1h[2], v1h[3]};
+                const half8 vl = {v0l[0], v0l[1], v0l[2], v0l[3], v1l[0], v1l[1], v1l[2], v1l[3]};
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh, o[dt], 0, 0, 0);
+            }
+        }
+    };
+    typedef float float2w __attribute__((ext_vector_type(2)));
+    const float cs = scale_log2e * (1.0f / 256.0f);
+    const bool once = nkt <= KC;
+    if (once) stage(0, true);
+    float mx = -INFINITY;
+    for (int c0 = 0; c0 < nkt; c0 += KC) {
+        if (!once) stage(c0, false);
+        if (active) {
+            const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
+            for (int kt = c0; kt < c1; ++kt) {
+                const f32x16 t = score_tile(kt, c0, true);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
+            }
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float shift = fmaf(-mx, cs, 10.0f);
+    float2w ls2 = float2w{0.0f, 0.0f};
+    for (int c0 = 0; c0 < nkt; c0 += KC) {
+        if (!once) stage(c0, true);
+        if (active) {
+            const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
+            for (int kt = c0; kt < c1; ++kt) {
+                f32x16 t = score_tile(kt, c0, false);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(fmaf(t[e], cs, shift), 15.9f));
+#pragma unroll
+                for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{t[e], t[e + 1]};
+                pv_tile(kt, c0, t);
+            }
+        }
+    }
+    if (!active) return;  // (no barrier below)
+    float lrow = ls2[0] + ls2[1];
+    {
+        const float other = __shfl_xor(lrow, 32, 64);
+        lrow = h == 0 ? lrow + other : other + lrow;
+    }
+    if (h == 0) Ls[wave * 32 + r] = lrow;  // read back by this wave's own lanes only
+#pragma unroll
+    for (int e = 0; e < 16; e += 2) {
+        const int q0 = acc_row(e, lane), q1 = acc_row(e + 1, lane);
+        const float s0 = 0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q0]);
+        const float s1 = 0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q1]);
+        const int tq0 = qb * 32 + q0, tq1 = qb * 32 + q1;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+            half2w hi, lo;
+            split_pair_prescaled(o[dt][e] * s0 * WT_SA, o[dt][e + 1] * s1 * WT_SA, hi, lo);
+            const size_t c = (size_t)hd * DH64 + 32 * dt + r;
+            if (tq0 < L) {
+                ch[(size_t)(t0 + tq0) * H + c] = hi[0];
+                cl[(size_t)(t0 + tq0) * H + c] = lo[0];
+            }
+            if (tq1 < L) {
+                ch[(size_t)(t0 + tq1) * H + c] = hi[1];
+                cl[(size_t)(t0 + tq1) * H + c] = lo[1];
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- mean pooling + L2 normalise
 // sentence_transformers Pooling(mean): sum_t h_t / clamp(count, 1e-9); then n_norm times
 // x / max(|x|_2, 1e-12) (Normalize module, normalize_embeddings=True).  One workgroup of
@@ -700,7 +1020,8 @@ __global__ __launch_bounds__(H) void pool_norm_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------- host side
-constexpr int HID = 384;
+constexpr int HID = 384;     // all-MiniLM width: 32-dim heads, the fused layer kernels
+constexpr int HID_BASE = 768;  // BERT-base width: 64-dim heads, the unfused chain (f16x3) / attention64_kernel (f32)
 
 struct LayerW {
     float *Wqkv, *bqkv, *Wo, *bo, *g1, *b1n, *W1, *b1, *W2, *b2, *g2, *b2n;
@@ -842,8 +1163,10 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
         }
     } else {
         const int nbn = N / 384;
-        hipLaunchKernelGGL((wt_linear_kernel<3, 2, 1, EPI>), dim3(((T + 63) / 64) * nbn), dim3(256), 0, st, Xh, Xl, T, K,
-                           Wp, N, bias, out, oh, ol, nbn);
+        // the residual epilogue at hidden 768 reads residual rows of 768 features (EPI 3)
+        auto kern = EPI == 2 && N == HID_BASE ? wt_linear_kernel<3, 2, 1, 3> : wt_linear_kernel<3, 2, 1, EPI>;
+        hipLaunchKernelGGL(kern, dim3(((T + 63) / 64) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp, N, bias, out, oh, ol,
+                           nbn);
     }
 }
 
@@ -882,6 +1205,33 @@ static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBu
     }
 }
 
+// The attention launches of a hidden-768 model (64-dim heads): buckets of 9-16 key tiles first, then 1, 2, 3-4, 5-8; for a
+// single sequence only the one that holds it.  X3: attention64_x3_kernel (context planes), else attention64_kernel.
+template <bool X3>
+static void launch_attention64(const icrec_bert_cfg& c, const EncBufs& b, const int32_t* cu, int n_seqs, int max_seqlen,
+                               const int32_t* order, hipStream_t st) {
+    constexpr int NB = 5;
+    constexpr int LO[NB] = {9, 1, 2, 3, 5}, HI[NB] = {16, 1, 2, 4, 8};
+    const int nkt_max = (max_seqlen + 31) / 32;
+    const bool single = n_seqs == 1;
+    const float sl2e = (1.0f / sqrtf((float)DH64)) * 1.44269504088896340736f;
+    for (int k = 0; k < NB; ++k) {
+        if (nkt_max < LO[k] || (single && nkt_max > HI[k])) continue;
+        const dim3 grid(n_seqs * c.heads, 1), block(HI[k] * 64);
+        if constexpr (X3) {
+            static const decltype(&attention64_x3_kernel<1>) kern[NB] = {
+                attention64_x3_kernel<16>, attention64_x3_kernel<1>, attention64_x3_kernel<2>, attention64_x3_kernel<4>,
+                attention64_x3_kernel<8>};
+            hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ch, b.cl, order);
+        } else {
+            static const decltype(&attention64_kernel<1>) kern[NB] = {
+                attention64_kernel<16>, attention64_kernel<1>, attention64_kernel<2>, attention64_kernel<4>,
+                attention64_kernel<8>};
+            hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx);
+        }
+    }
+}
+
 }  // namespace icrec
 
 using namespace icrec;
@@ -893,10 +1243,12 @@ size_t icrec_encoder_weight_count(const icrec_bert_cfg* cfg) { return cfg ? weig
 int icrec_encoder_create(const float* weights_host, size_t n_floats, const icrec_bert_cfg* cfg, int device,
                          icrec_encoder** out) {
     ICREC_REQUIRE(weights_host && cfg && out, "icrec_encoder_create: NULL argument");
-    // The kernels and their dispatch rely on these two: every GEMM has K = 384 or K = intermediate, a multiple of 384,
-    // and N = 384, 1,152 or intermediate (launch_wt_linear's ring depths and tile splits, the fused FFN's 128-wide chunks).
-    ICREC_REQUIRE(cfg->hidden == HID, "icrec_encoder_create: this build supports hidden=384 only (got %d)", cfg->hidden);
-    ICREC_REQUIRE(cfg->heads * DH == cfg->hidden, "icrec_encoder_create: head_dim must be 32 (heads=%d)", cfg->heads);
+    // The kernels and their dispatch rely on these: every GEMM has K = hidden or K = intermediate, a multiple of 384, and
+    // N = hidden, 3 x hidden or intermediate (launch_wt_linear's ring depths and tile splits, the fused FFN's 128-wide
+    // chunks); the attention kernels exist for 32-dim heads at hidden 384 and 64-dim heads at hidden 768.
+    ICREC_REQUIRE((cfg->hidden == HID && cfg->heads * DH == HID) || (cfg->hidden == HID_BASE && cfg->heads * DH64 == HID_BASE),
+                  "icrec_encoder_create: (hidden, heads) must be (384, 12) or (768, 12): head_dim 32 at hidden 384, head_dim 64 "
+                  "at hidden 768 (got hidden=%d, heads=%d)", cfg->hidden, cfg->heads);
     ICREC_REQUIRE(cfg->intermediate >= 384 && cfg->intermediate % 384 == 0, "icrec_encoder_create: intermediate size must be a multiple of 384 (got %d)", cfg->intermediate);
     ICREC_REQUIRE(cfg->layers >= 1 && cfg->layers <= 64, "icrec_encoder_create: layers must be in [1,64]");
     ICREC_REQUIRE(cfg->vocab_size >= 1 && cfg->max_position >= 1 && cfg->type_vocab >= 1, "icrec_encoder_create: bad vocab/position sizes");
@@ -1033,8 +1385,9 @@ static const int32_t* embed(const Encoder* e, const EncBufs& b, const int32_t* i
         order = reinterpret_cast<int32_t*>(b.x);
         hipLaunchKernelGGL(seq_order_kernel, dim3(1), dim3(1024), 0, st, cu_dev, n_seqs, order);
     }
-    hipLaunchKernelGGL((x3 ? embed_ln_kernel<HID, true> : embed_ln_kernel<HID, false>), dim3((T + 3) / 4), dim3(256), 0,
-                       st, ids_dev, cu_dev, n_seqs, T, e->word, e->pos, e->type, e->eg, e->eb, c.ln_eps, c.vocab_size,
+    const auto kern = c.hidden == HID_BASE ? (x3 ? embed_ln_kernel<HID_BASE, true> : embed_ln_kernel<HID_BASE, false>)
+                                           : (x3 ? embed_ln_kernel<HID, true> : embed_ln_kernel<HID, false>);
+    hipLaunchKernelGGL(kern, dim3((T + 3) / 4), dim3(256), 0, st, ids_dev, cu_dev, n_seqs, T, e->word, e->pos, e->type, e->eg, e->eb, c.ln_eps, c.vocab_size,
                        c.max_position, b.x, b.xh, b.xl);
     return order;
 }
@@ -1052,8 +1405,10 @@ struct Range {
     bool small;  // n <= small_m: the latency-form GEMMs (launch_wt_linear), every GEMM a launch of its own
     bool layer;  // fuse && !small: the layer kernels (qkv_resident_kernel, one ffn_fused2_kernel per layer)
     bool fold;   // fuse && small: a LayerNorm is the prologue of the GEMM behind it (wt_linear_lnin_kernel)
+    // (the layer kernels and the folded LayerNorm exist at hidden 384 only: a hidden-768 model always runs the unfused chain)
     Range(const Encoder* e, int r0, int n, hipStream_t st)
-        : r0(r0), n(n), st(st), small(n <= e->small_m), layer(e->fuse && !small), fold(e->fuse && small) {}
+        : r0(r0), n(n), st(st), small(n <= e->small_m), layer(e->fuse && !small && e->cfg.hidden == HID),
+          fold(e->fuse && small && e->cfg.hidden == HID) {}
     bool launches_qkv(int l) const { return l == 0 || !layer; }  // (else ffn_fused2_kernel's epilogue computes it)
     bool ffn_ln_to_next(int l, int layers) const { return fold && l + 1 < layers; }  // to the next QKV's prologue
 };
@@ -1062,7 +1417,8 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
                      const int32_t* order, hipStream_t st) {
     const icrec_bert_cfg& c = e->cfg;
     const int H = c.hidden, I = c.intermediate;
-    const bool split_att = e->side_stream && n_seqs >= 64 && max_seqlen > 128;  // batches with a long bucket
+    const bool base = H == HID_BASE;
+    const bool split_att = !base && e->side_stream && n_seqs >= 64 && max_seqlen > 128;  // batches with a long bucket
     // Token ranges: [0, T_main) goes through the batch kernels in whole rounds of one 64-token workgroup per CU, a short
     // remainder [T_main, T) through the small-batch kernels (same arithmetic, same bits) instead of costing every batch
     // kernel an extra, almost empty round.
@@ -1125,15 +1481,15 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
                                (const float*)t1r, r.n, L.g1, L.b1n, c.ln_eps, xhr, xlr, L.W1_p, I, L.b1, (float*)nullptr,
                                hhr, hlr, nbn);
         } else {
-            hipLaunchKernelGGL(ln_wt_kernel, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n, L.g1, L.b1n, c.ln_eps,
-                               xhr, xlr);
+            hipLaunchKernelGGL(base ? ln_wt768_kernel : ln_wt_kernel, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n,
+                               L.g1, L.b1n, c.ln_eps, xhr, xlr);
             ScopedTimer tm(r.small ? T_NSLOTS - 1 : T_FFN_UP, r.st);
             launch_wt_linear<1>(xhr, xlr, r.n, H, L.W1_p, I, L.b1, nullptr, hhr, hlr, r.st, r.small);
         }
         launch_wt_linear<2>(hhr, hlr, r.n, I, L.W2_p, H, L.b2, t1r, xhr, xlr, r.st, r.small);
         if (!r.ffn_ln_to_next(l, c.layers))
-            hipLaunchKernelGGL(ln_wt_kernel, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n, L.g2, L.b2n, c.ln_eps,
-                               xhr, xlr);
+            hipLaunchKernelGGL(base ? ln_wt768_kernel : ln_wt_kernel, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n,
+                               L.g2, L.b2n, c.ln_eps, xhr, xlr);
     };
 
     if (tail_on_side) ICREC_HIP(link(sd, st, sd->side));  // the side stream starts behind the embeddings
@@ -1151,6 +1507,8 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
             launch_attention<true>(side_buckets, c, b, cu_dev, n_seqs, max_seqlen, order, sd->side);
             launch_attention<true>(1u << ATT_5_6, c, b, cu_dev, n_seqs, max_seqlen, order, st);
             ICREC_HIP(link(sd, sd->side, st));
+        } else if (base) {
+            launch_attention64<true>(c, b, cu_dev, n_seqs, max_seqlen, order, st);
         } else {
             launch_attention<true>(~0u, c, b, cu_dev, n_seqs, max_seqlen, order, st);
         }
@@ -1166,19 +1524,24 @@ static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev,
                       hipStream_t st) {
     const icrec_bert_cfg& c = e->cfg;
     const int H = c.hidden, I = c.intermediate, rows_grid = (T + 3) / 4;
+    const bool base = H == HID_BASE;
+    const auto add_ln = base ? add_ln_kernel<HID_BASE> : add_ln_kernel<HID>;
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& L = e->layers[l];
         launch_linear<false>(b.x, T, H, L.Wqkv, 3 * H, L.bqkv, b.qkv, st);
-        launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
+        if (base)
+            launch_attention64<false>(c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
+        else
+            launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
         launch_linear<false>(b.ctx, T, H, L.Wo, H, L.bo, b.t1, st);
-        hipLaunchKernelGGL(add_ln_kernel<HID>, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g1, L.b1n,
+        hipLaunchKernelGGL(add_ln, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g1, L.b1n,
                            c.ln_eps, b.xh, b.xl);
         {
             ScopedTimer tm(T_FFN_UP, st);
             launch_linear<true>(b.x, T, H, L.W1, I, L.b1, b.h, st);
         }
         launch_linear<false>(b.h, T, I, L.W2, H, L.b2, b.t1, st);
-        hipLaunchKernelGGL(add_ln_kernel<HID>, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g2, L.b2n,
+        hipLaunchKernelGGL(add_ln, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g2, L.b2n,
                            c.ln_eps, b.xh, b.xl);
     }
     return ICREC_OK;
@@ -1219,8 +1582,9 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
     if (int rc_ = x3 ? encode_x3(e, b, cu_dev, n_seqs, T, max_seqlen, order, st)
                      : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
         return rc_;
-    hipLaunchKernelGGL((x3 ? pool_norm_kernel<HID, true> : pool_norm_kernel<HID, false>), dim3(n_seqs), dim3(HID), 0, st,
-                       b.x, b.xh, b.xl, cu_dev, c.n_normalize, out_dev);
+    const auto pool = H == HID_BASE ? (x3 ? pool_norm_kernel<HID_BASE, true> : pool_norm_kernel<HID_BASE, false>)
+                                    : (x3 ? pool_norm_kernel<HID, true> : pool_norm_kernel<HID, false>);
+    hipLaunchKernelGGL(pool, dim3(n_seqs), dim3(H), 0, st, b.x, b.xh, b.xl, cu_dev, c.n_normalize, out_dev);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
 }

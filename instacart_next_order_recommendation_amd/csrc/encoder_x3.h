@@ -107,8 +107,9 @@ __device__ __forceinline__ void lnt_flat(int lane, int k, int& row, int& c) {
 // global memory, in two steps so that a caller can put work between the request and the use: wt_res_rows_load issues
 // the 12 coalesced 16-byte loads of the rows (12 lanes cover one token's 192 bytes of a plane), wt_res_rows_acc
 // transposes them through the wave's private LDS tile (`tile`: LNT_TILE bytes) into the accumulator layout:
-// acc[.][TT] = r (ADD = false) or += r (ADD = true).
+// acc[.][TT] = r (ADD = false) or += r (ADD = true).  RS: row stride of the planes, the model's hidden size.
 struct ResRows { u32x4 v[2][6]; };  // [plane][chunk]
+template <int RS = 384>
 __device__ __forceinline__ void wt_res_rows_load(ResRows& rr, int q, int tb, const _Float16* __restrict__ xh,
                                                  const _Float16* __restrict__ xl, int64_t m0, int64_t T) {
     const int lane = threadIdx.x & 63;
@@ -118,7 +119,7 @@ __device__ __forceinline__ void wt_res_rows_load(ResRows& rr, int q, int tb, con
         lnt_flat(lane, k, row, ch);
         int64_t gr = m0 + tb * 32 + row;
         gr = gr < T ? gr : T - 1;
-        const int64_t off = gr * 384 + q * 96 + ch * 8;
+        const int64_t off = gr * RS + q * 96 + ch * 8;
         rr.v[0][k] = *reinterpret_cast<const u32x4*>(xh + off);
         rr.v[1][k] = *reinterpret_cast<const u32x4*>(xl + off);
     }
@@ -307,16 +308,20 @@ __device__ __forceinline__ void wt_ln_block(Acc32 (&acc)[3][TTW], int q, int tb,
 // q*96 + i*32 + fi*16 + 4g + reg, in (i, fi, reg) order, the 16 partials are combined by shuffles in the fixed tree of
 // wt_ln_block.  store(feat, hi, lo) takes the planes of the four features at feat, for each (i, fi) in that order.
 // ln_wt_kernel and the prologue of wt_linear_lnin_kernel both run it: identical bits.
-template <class Store>
+// H = 768 (BERT-base width; only ln_wt768_kernel) is the same tree over twice the values: thread (q, g) sums its 48
+// values, features q*192 + i*32 + fi*16 + 4g + reg (i < 6), in (i, fi, reg) order; mean and variance divide by 768.
+template <int H = 384, class Store>
 __device__ __forceinline__ void ln16_row(const float* row, const float* gam, const float* bet, float eps, int q, int g,
                                          int base, Store store) {
-    f32x4 v[3][2];
+    static_assert(H == 384 || H == 768, "LayerNorm widths: 384, 768");
+    constexpr int NI = H / 128, QW = H / 4;  // 32-feature groups per thread, features per quarter
+    f32x4 v[NI][2];
     float part = 0.0f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NI; ++i)
 #pragma unroll
         for (int fi = 0; fi < 2; ++fi) {
-            v[i][fi] = *reinterpret_cast<const f32x4*>(row + q * 96 + i * 32 + fi * 16 + 4 * g);
+            v[i][fi] = *reinterpret_cast<const f32x4*>(row + q * QW + i * 32 + fi * 16 + 4 * g);
 #pragma unroll
             for (int j = 0; j < 4; ++j) part = part + v[i][fi][j];
         }
@@ -327,10 +332,10 @@ __device__ __forceinline__ void ln16_row(const float* row, const float* gam, con
                     p3 = __shfl(p, base + 12, 64);
         return ((p0 + p1) + p2) + p3;
     };
-    const float mean = tree(part) / 384.0f;
+    const float mean = tree(part) / (float)H;
     float sq = 0.0f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NI; ++i)
 #pragma unroll
         for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
@@ -339,13 +344,13 @@ __device__ __forceinline__ void ln16_row(const float* row, const float* gam, con
                 v[i][fi][j] = d;
                 sq = fmaf(d, d, sq);
             }
-    const float var = tree(sq) / 384.0f;
+    const float var = tree(sq) / (float)H;
     const float rstd = 1.0f / sqrtf(var + eps);
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NI; ++i)
 #pragma unroll
         for (int fi = 0; fi < 2; ++fi) {
-            const int feat = q * 96 + i * 32 + fi * 16 + 4 * g;
+            const int feat = q * QW + i * 32 + fi * 16 + 4 * g;
             const f32x4 gm = *reinterpret_cast<const f32x4*>(gam + feat);
             const f32x4 bt = *reinterpret_cast<const f32x4*>(bet + feat);
             f32x4 y;
@@ -373,6 +378,22 @@ __global__ __launch_bounds__(256) void ln_wt_kernel(const float* __restrict__ a,
              });
 }
 
+// the same at hidden 768 (ln16_row<768>; the unfused chain every 768-wide model runs)
+__global__ __launch_bounds__(256) void ln_wt768_kernel(const float* __restrict__ a, int T, const float* __restrict__ gam,
+                                                       const float* __restrict__ bet, float eps,
+                                                       _Float16* __restrict__ xh, _Float16* __restrict__ xl) {
+    const int tid = threadIdx.x, slot = tid & 15, q = slot >> 2, g = slot & 3;
+    const int64_t tok = (int64_t)blockIdx.x * 16 + (tid >> 4);
+    const bool ok = tok < T;
+    ln16_row<768>(a + (ok ? tok : (int64_t)T - 1) * 768, gam, bet, eps, q, g, (tid & 63) & ~15,
+                  [=](int feat, const half4& hi, const half4& lo) {
+                      if (ok) {
+                          *reinterpret_cast<half4*>(xh + tok * 768 + feat) = hi;
+                          *reinterpret_cast<half4*>(xl + tok * 768 + feat) = lo;
+                      }
+                  });
+}
+
 constexpr int LN_LD = 388;  // floats per staged output row in LDS (+16 B: the 16-B accesses of consecutive tokens hit distinct banks)
 
 // ---------------------------------------------------------------- f16x3 linear layers, slab-ring form
@@ -382,6 +403,7 @@ constexpr int LN_LD = 388;  // floats per staged output row in LDS (+16 B: the 1
 //   EPI 1: erf-GELU (tf:336), result as f16 hi/lo planes   (FFN-up of small batches)
 //   EPI 2: residual + bias (planes oh / ol, row stride 384) added to the accumulators after the K loop, out fp32 =
 //          acc * 2^-14: the LayerNorm input of attention-out / FFN-down (ln_wt_kernel follows)
+//   EPI 3: EPI 2 at hidden 768 (residual row stride 768, two 384-feature blocks per row; ln_wt768_kernel follows)
 // Two forms: <1, 1, 4, 1>, the small-batch FFN-up (weights four k-steps ahead; small batches and the remainder of a batch
 // take wt_linear_half_kernel for EPI 0 / 2): 32-token x 128-feature workgroups, latency-bound.  <3, 2, 1, EPI>: the
 // 64-token x 384-feature form of the UNFUSED reference chain (ICREC_FUSE=0: tests compare the fused kernels against it
@@ -397,6 +419,8 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
     static_assert((NTW == 1 && TTW == 1 && D == 4 && EPI == 1) || (NTW == 3 && TTW == 2 && D == 1),
                   "the small-batch FFN-up <1, 1, 4, 1> or the batch form <3, 2, 1, EPI>");
     constexpr bool STAGED = EPI != 1;  // results leave through an LDS stage, coalesced
+    constexpr bool RES = EPI == 2 || EPI == 3;
+    constexpr int RS = EPI == 3 ? 768 : 384;  // residual row stride
     constexpr int SM = (STAGED && 32 * LN_LD * 4 > XRing<TTW>::BYTES) ? 32 * LN_LD * 4 : XRing<TTW>::BYTES;
     __shared__ __attribute__((aligned(16))) char smem[SM];
     const int lane = threadIdx.x & 63, q = wave_uniform(threadIdx.x >> 6), c = lane & 15, g = lane >> 4;
@@ -407,10 +431,10 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
     const int nt0 = (nb * 4 + q) * NTW;
     Acc32 acc[NTW][TTW];
     wt_kloop<NTW, TTW, D>(acc, Wp, nt0, K, Xh, Xl, m0, T, smem);  // ends with a barrier: the slab ring is free
-    if constexpr (EPI == 2) {  // oh / ol carry the residual planes here: acc += r
+    if constexpr (RES) {  // oh / ol carry the residual planes here: acc += r
         ResRows r0, r1;
-        wt_res_rows_load(r0, q, 0, oh + nb * 384, ol + nb * 384, m0, T);
-        wt_res_rows_load(r1, q, 1, oh + nb * 384, ol + nb * 384, m0, T);
+        wt_res_rows_load<RS>(r0, q, 0, oh + nb * 384, ol + nb * 384, m0, T);
+        wt_res_rows_load<RS>(r1, q, 1, oh + nb * 384, ol + nb * 384, m0, T);
         wt_res_rows_acc<true, 2, 0>(acc, r0, q, bias + nb * 384, smem + q * LNT_TILE);
         wt_res_rows_acc<true, 2, 1>(acc, r1, q, bias + nb * 384, smem + q * LNT_TILE);
         __syncthreads();  // the private tiles become the output stage
@@ -428,13 +452,13 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
                 for (int fi = 0; fi < 2; ++fi) {
                     const int fl = q * 96 + i * 32 + fi * 16 + 4 * g;
                     f32x4 b = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                    if (EPI == 0) b = *reinterpret_cast<const f32x4*>(bias + n0 + fl);
+                    if (!RES) b = *reinterpret_cast<const f32x4*>(bias + n0 + fl);
 #pragma unroll
                     for (int ti = 0; ti < 2; ++ti) {
                         f32x4 v;
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
-                            v[j] = EPI == 2 ? acc[i][tt].t[fi][ti][j] * WT_UNSCALE : fmaf(acc[i][tt].t[fi][ti][j], WT_UNSCALE, b[j]);
+                            v[j] = RES ? acc[i][tt].t[fi][ti][j] * WT_UNSCALE : fmaf(acc[i][tt].t[fi][ti][j], WT_UNSCALE, b[j]);
                         *reinterpret_cast<f32x4*>(stage + (ti * 16 + c) * LN_LD + fl) = v;
                     }
                 }

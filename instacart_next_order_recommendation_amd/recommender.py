@@ -55,7 +55,7 @@ class RecommendationMetrics:
 
 
 class EmbeddingIndex:
-    """On-disk cache of the [N, 384] fp32 product matrix, byte-compatible with the reference's
+    """On-disk cache of the [N, hidden] fp32 product matrix, byte-compatible with the reference's
     (:66-130): <corpus dir>/.embedding_index/<sha256("model_dir|corpus_path")[:16]>/
     {manifest.json, embeddings.npy, product_ids.json}; valid only for the same corpus path,
     model dir, corpus mtime and product-id list."""
@@ -120,12 +120,12 @@ class SbertModel:
         self._encoder_no_flag: Optional[DeviceEncoder] = None  # normalize_embeddings=False: one normalisation fewer
 
     def encode_to_device(self, texts: Sequence[str], tokens_per_call: int = 1 << 18) -> torch.Tensor:
-        """Embeddings [n, 384] left on the GPU (serving path: no host round trip)."""
+        """Embeddings [n, hidden] left on the GPU (serving path: no host round trip)."""
         return self.encoder.encode_packed_host(*self.tokenizer.packed(texts), max_tokens_per_call=tokens_per_call)
 
     def encode(self, sentences, batch_size: int = 64, show_progress_bar: bool = False,
                normalize_embeddings: bool = True, **_ignored) -> np.ndarray:
-        """SentenceTransformer.encode-compatible: numpy float32 [n, 384] (or [384] for a str).
+        """SentenceTransformer.encode-compatible: numpy float32 [n, hidden] (or [hidden] for a str).
 
         The reference pads and runs `batch_size` texts per forward; packed varlen batching makes
         the result independent of batch composition, so `batch_size` only bounds tokens per call."""

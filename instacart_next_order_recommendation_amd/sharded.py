@@ -4,7 +4,7 @@ One process per GPU (torch.distributed, backend "nccl" = RCCL over xGMI).  Rank 
 rows [bounds[r], bounds[r+1]) as a DeviceIndex with row_offset = bounds[r], encodes its slice of
 the query batch, then:
 
-    all_gather(query embeddings)          [Q/W, 384] fp32 per rank  ->  [Q, 384]
+    all_gather(query embeddings)          [Q/W, d] fp32 per rank    ->  [Q, d]
     local fused score + top-k             every query against the local shard -> keys [Q, k]
     all_gather(partial keys)              [Q, k] u64 per rank       ->  [W, Q, k]
     k-way merge                           -> global top-k, identical to the unsharded result

@@ -1,0 +1,68 @@
+"""BERT-base width (hidden 768, 12 heads of 64) at the C ABI, without a GPU: icrec_encoder_create accepts the
+(768, 12) configuration and refuses every other (hidden, heads) pair, and the oracle at that width agrees with
+transformers.BertModel."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from instacart_next_order_recommendation_amd import _native
+from instacart_next_order_recommendation_amd import synthetic as syn
+from oracle import oracle
+
+ICREC_EINVAL, ICREC_EHIP, ICREC_ENODEV = -1, -2, -4
+
+
+def _create(shape: syn.BertShape, gemm_mode: int = _native.GEMM_F16X3) -> int:
+    """icrec_encoder_create on a correctly sized blob of `shape`; destroys the encoder if one was made."""
+    L = _native.lib()
+    cfg = _native.BertCfg(shape.vocab_size, shape.hidden, shape.layers, shape.heads, shape.intermediate,
+                          shape.max_position, shape.type_vocab, shape.ln_eps, shape.n_normalize, gemm_mode)
+    n = int(L.icrec_encoder_weight_count(C.byref(cfg)))
+    assert n == shape.weight_count()
+    w = np.zeros(n, np.float32)
+    h = C.c_void_p()
+    rc = L.icrec_encoder_create(w.ctypes.data_as(C.c_void_p), n, C.byref(cfg), 0, C.byref(h))
+    if rc == 0:
+        assert h.value
+        assert L.icrec_encoder_destroy(h) == 0
+    return rc
+
+
+@pytest.mark.parametrize("mode", [_native.GEMM_F32, _native.GEMM_F16X3])
+def test_create_accepts_bert_base_width(mode):
+    """(768, 12 heads of 64): not refused as a shape.  Without a GPU the call fails at the device (ENODEV / EHIP);
+    with one it succeeds."""
+    shape = syn.BertShape(vocab_size=2048, hidden=768, heads=12, intermediate=3072, layers=1)
+    rc = _create(shape, mode)
+    assert rc in (0, ICREC_ENODEV, ICREC_EHIP), (rc, _native.lib().icrec_last_error())
+
+
+@pytest.mark.parametrize("hidden,heads", [(768, 24), (512, 8), (384, 6), (1024, 16), (768, 6), (384, 24)])
+def test_create_refuses_other_widths(hidden, heads):
+    """Only (384, head_dim 32) and (768, head_dim 64) are served: anything else is ICREC_EINVAL, and the message
+    names the two supported pairs."""
+    shape = syn.BertShape(vocab_size=2048, hidden=hidden, heads=heads, intermediate=1536, layers=1)
+    assert _create(shape) == ICREC_EINVAL
+    msg = _native.lib().icrec_last_error().decode()
+    assert "384" in msg and "768" in msg, msg
+
+
+def test_oracle_matches_transformers_at_bert_base_width():
+    """transformers.BertModel at hidden 768 / 12 heads of 64 / intermediate 3,072 (padded batch, attention mask, mean
+    pool, normalisations, as oracle/pin_against_libs.py runs it): the oracle within 2e-6."""
+    pytest.importorskip("transformers")
+    from oracle.pin_against_libs import hf_encode
+
+    shape = syn.BertShape(vocab_size=2048, hidden=768, heads=12, intermediate=3072, layers=2)
+    w = syn.synthetic_bert_weights(shape, seed=768)
+    ids, cu = syn.synthetic_token_batch(5, seed=768, mean_len=50, std_len=50, lo=1, hi=100, vocab_size=2048)
+    cfg = oracle.make_cfg(vocab_size=2048, hidden=768, layers=2, heads=12, intermediate=3072,
+                          n_normalize=shape.n_normalize)
+    assert w.size == shape.weight_count() == oracle.weight_count(cfg)
+    want, _ = hf_encode(w, shape, ids, cu)
+    got = oracle.encode(w, cfg, ids, cu)
+    assert got.shape == (5, 768)
+    assert np.abs(got - want).max() < 2e-6, np.abs(got - want).max()
