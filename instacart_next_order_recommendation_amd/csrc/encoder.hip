@@ -146,7 +146,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void linear_kernel(const float* __
 }
 
 // ---------------------------------------------------------------- attention (tf:111-136, 164-203)
-// One workgroup = one (sequence, head) and up to four 32-row query blocks (one per wave).
+// One workgroup = one (sequence, head) and up to sixteen 32-row query blocks (one per wave), for heads of D = 32
+// (hidden 384) or D = 64 dims (hidden 768: BERT-base).
 // S^T = K.Q^T is computed with keys on the accumulator rows, so each lane ends up with the
 // scores of ONE query (column = lane & 31) against 16 keys per 32-key tile.  The softmax is
 // then lane-local plus one exchange with lane^32, and the exponentiated accumulator registers
@@ -154,75 +155,90 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void linear_kernel(const float* __
 // round trip.  Key order inside the P.V chain is therefore, per 32-key tile,
 //   e = 0..15: key (e&3)+8(e>>2) then key (e&3)+8(e>>2)+4
 // and the softmax denominator is the sum of the two half-wave partial sums; the oracle
-// (icrec_oracle.c, attention block) accumulates in exactly this order.
-constexpr int DH = 32;
-constexpr int LDQ = 36;  // K LDS row stride (even/odd split layout, like the GEMM tiles)
-
-// One launch per length bucket: NKT = max 32-key tiles (1, 2, 4, 8, 16), and as many waves, one per 32-row query
-// block.  A workgroup whose sequence belongs to another bucket exits at once, so short
-// sequences run with the LDS footprint / occupancy of their own bucket even in a mixed batch.
+// (icrec_oracle.c, attention block) accumulates in exactly this order.  A wave's output is D / 32 tiles of 32 x 32
+// (dims 32 dt + r of the lane's column).
+//
+// One launch per length bucket: NKT = max 32-key tiles (1, 2, 4, 6, 8, 16), and as many waves; sequences of
+// nlo < nkt <= NKT key tiles belong to the launch.  A workgroup whose sequence belongs to another bucket exits at once,
+// so short sequences run with the LDS footprint / occupancy of their own bucket even in a mixed batch.
 // K and V of the (sequence, head) live in LDS; each wave's 32 query rows come straight from
-// global memory into the B-operand registers.  Output: the fp32 context rows (`ctx`; ch / cl unused).
-template <int NKT>
+// global memory into the B-operand registers.
+//
+// Key tiles that LDS holds at once: a 32-dim head's K and V fit whole (KC = NKT); a 64-dim head's take twice the LDS, so
+// its longest bucket (9-16 tiles, up to 512 keys) is staged in chunks of 8 tiles, twice - K alone for the row maximum,
+// then K and V for the exponentials and P.V.  The per-query arithmetic depends neither on the bucket nor on the
+// chunking: a sequence gives the same bits whichever launch serves it.
+constexpr int att_kc(int D, int NKT) { return D == 64 && NKT > 8 ? 8 : NKT; }
+
+// A row's denominator from the two half-waves' partial sums: half 0's + half 1's, in both halves.
+__device__ __forceinline__ float join_halves(float v, int h) {
+    const float other = __shfl_xor(v, 32, 64);
+    return h == 0 ? v + other : other + v;
+}
+
+// Exact fp32 form (gemm_mode F32): both products on v_mfma_f32_32x32x2_f32, head dims in pairs ascending.
+// Output: the fp32 context rows.
+template <int D, int NKT>
 __global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __restrict__ qkv,
                                                              const int32_t* __restrict__ cu, int heads, int H,
-                                                             float scale_log2e, float* __restrict__ ctx,
-                                                             _Float16* __restrict__ ch, _Float16* __restrict__ cl) {
-    __shared__ __attribute__((aligned(16))) float Ks[NKT * 32 * LDQ];
-    __shared__ __attribute__((aligned(16))) float Vs[NKT * 32 * DH];
+                                                             float scale_log2e, float* __restrict__ ctx, int nlo) {
+    constexpr int KC = att_kc(D, NKT);
+    constexpr int LDK = D + 4;  // K LDS row stride (even/odd split layout, like the GEMM tiles)
+    // Sixteen score tiles do not fit in registers (and 64-dim heads leave room for none): each tile is then computed
+    // twice - once for the row maximum, once more for its exponentials, which the P.V product consumes at once.  Same
+    // MFMA chain both times, and the denominator and P.V accumulate in the same order as in the all-in-registers form:
+    // the same bits.
+    constexpr bool RECOMP = D == 64 || NKT > 8;
+    __shared__ __attribute__((aligned(16))) float Ks[KC * 32 * LDK];
+    __shared__ __attribute__((aligned(16))) float Vs[KC * 32 * D];
     __shared__ float Ls[NKT * 32];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = blockIdx.x / heads, hd = blockIdx.x % heads;
     const int t0 = cu[s], L = cu[s + 1] - t0;
     const int nkt = (L + 31) >> 5;
-    if (nkt > NKT || (NKT > 1 && nkt <= NKT / 2)) return;  // another bucket's sequence
-    const int qb0 = blockIdx.y * NKT;
-    if (qb0 >= nkt) return;
+    if (nkt > NKT || nkt <= nlo) return;  // another bucket's sequence
     const int ld = 3 * H;
-
-    // stage K (even/odd split) and V; rows past L are clamped (masked below / never stored)
-    for (int id = tid; id < nkt * 32 * 8; id += NKT * 64) {
-        const int row = id >> 3, c = id & 7;
-        const int rr = row < L ? row : L - 1;
-        const float* src = qkv + (size_t)(t0 + rr) * ld + hd * DH + c * 4;
-        const float4 kv = *reinterpret_cast<const float4*>(src + H);
-        const float4 vv = *reinterpret_cast<const float4*>(src + 2 * H);
-        float* kp = Ks + row * LDQ + (c >> 1) * 8 + (c & 1) * 2;
-        *reinterpret_cast<float2*>(kp) = make_float2(kv.x, kv.z);
-        *reinterpret_cast<float2*>(kp + 4) = make_float2(kv.y, kv.w);
-        *reinterpret_cast<float4*>(Vs + row * DH + c * 4) = vv;
-    }
-    const int r = lane & 31, h = lane >> 5;
-    const int qb = qb0 + wave;
-    // this lane's query row -> B fragments (lane half h supplies the even / odd head dims)
-    float4 qf[4];
+    const int r = lane & 31, h = lane >> 5, qb = wave;
+    const bool active = qb < nkt;  // wave-uniform; idle waves still take part in the barriers of the staging
+    float4 qf[D / 8];  // this lane's query row -> B fragments (lane half h supplies the even / odd dims of every pair)
     {
         int qr = qb * 32 + r;
         qr = qr < L ? qr : L - 1;
-        const float4* qp = reinterpret_cast<const float4*>(qkv + (size_t)(t0 + qr) * ld + hd * DH);
+        const float4* qp = reinterpret_cast<const float4*>(qkv + (size_t)(t0 + qr) * ld + hd * D);
 #pragma unroll
-        for (int kq = 0; kq < 4; ++kq) {
+        for (int kq = 0; kq < D / 8; ++kq) {
             const float4 a = qp[2 * kq], b = qp[2 * kq + 1];
             qf[kq] = h == 0 ? make_float4(a.x, a.z, b.x, b.z) : make_float4(a.y, a.w, b.y, b.w);
         }
     }
-    __syncthreads();
-    if (qb >= nkt) return;  // idle wave (no barrier below)
-
-    f32x16 o;
-    if constexpr (NKT > 8) {
-    // ---- the 9-16-tile bucket (257-512 tokens): sixteen score tiles do not fit in registers, so each tile is computed
-    // twice - once for the row maximum, once more for its exponentials, which the P.V product consumes at once.  Same
-    // MFMA chain both times, and the denominator and P.V accumulate in the same order as below: the same bits as the
-    // all-in-registers form would give.
-    auto score_tile = [&](int kt) {
+    const bool once = KC == NKT || nkt <= KC;  // the whole sequence fits: staged once, K and V
+    // key tiles [c0, c0 + KC) -> LDS (K in the even/odd split layout, V row-major); rows past L are clamped (masked
+    // below / never stored)
+    auto stage = [&](int c0, bool with_v) {
+        if (!once) __syncthreads();  // the previous chunk's readers are done
+        const int nk = (nkt - c0 < KC ? nkt - c0 : KC) * 32;
+        for (int id = tid; id < nk * (D / 4); id += NKT * 64) {
+            const int row = id / (D / 4), c = id % (D / 4);
+            const int key = c0 * 32 + row, rr = key < L ? key : L - 1;
+            const float* src = qkv + (size_t)(t0 + rr) * ld + hd * D + c * 4;
+            const float4 kv = *reinterpret_cast<const float4*>(src + H);
+            float* kp = Ks + row * LDK + (c >> 1) * 8 + (c & 1) * 2;
+            *reinterpret_cast<float2*>(kp) = make_float2(kv.x, kv.z);
+            *reinterpret_cast<float2*>(kp + 4) = make_float2(kv.y, kv.w);
+            if (with_v) *reinterpret_cast<float4*>(Vs + row * D + c * 4) = *reinterpret_cast<const float4*>(src + 2 * H);
+        }
+        __syncthreads();
+    };
+    // scores of key tile kt (staged from c0) in log2 units (scale * log2(e) folded), tail keys at -inf:
+    // t[e] = scale_log2e * sum_d K[kt*32 + krow(e)][d] * Q[qb*32 + r][d]
+    auto score_tile = [&](int kt, int c0) {
         f32x16 t;
 #pragma unroll
         for (int e = 0; e < 16; ++e) t[e] = 0.0f;
 #pragma unroll
-        for (int kq = 0; kq < 4; ++kq) {
-            const float4 kf = *reinterpret_cast<const float4*>(Ks + (kt * 32 + r) * LDQ + kq * 8 + h * 4);
+        for (int kq = 0; kq < D / 8; ++kq) {
+            const float4 kf = *reinterpret_cast<const float4*>(Ks + ((kt - c0) * 32 + r) * LDK + kq * 8 + h * 4);
             t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[kq].x, t, 0, 0, 0);
             t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[kq].y, t, 0, 0, 0);
             t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[kq].z, t, 0, 0, 0);
@@ -237,101 +253,85 @@ __global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __rest
         }
         return t;
     };
-    float mx = -INFINITY;
-    for (int kt = 0; kt < nkt; ++kt) {
-        const f32x16 t = score_tile(kt);
+    // O += P.V for key tile kt, with P taken straight from the accumulator registers
+    f32x16 o[D / 32];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float lsum = 0.0f;
+    for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) o[e] = 0.0f;
-    for (int kt = 0; kt < nkt; ++kt) {
-        f32x16 t = score_tile(kt);
+        for (int e = 0; e < 16; ++e) o[dt][e] = 0.0f;
+    auto pv_tile = [&](int kt, int c0, const f32x16& p) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const float p = __builtin_amdgcn_exp2f(t[e] - mx);
-            t[e] = p;
-            lsum = lsum + p;
+            const int key = (kt - c0) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+#pragma unroll
+            for (int dt = 0; dt < D / 32; ++dt)
+                o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(p[e], Vs[key * D + 32 * dt + r], o[dt], 0, 0, 0);
         }
+    };
+    // every key tile of the sequence, chunk by chunk (one chunk when the sequence was staged whole)
+    auto for_tiles = [&](bool with_v, auto&& f) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            o = __builtin_amdgcn_mfma_f32_32x32x2f32(t[e], Vs[key * DH + r], o, 0, 0, 0);
-        }
-    }
-    {
-        const float other = __shfl_xor(lsum, 32, 64);
-        lsum = h == 0 ? lsum + other : other + lsum;
-    }
-    if (h == 0) Ls[wave * 32 + r] = lsum;
-    } else {
-    // ---- S^T tiles: sc[kt][e] = sum_d K[kt*32 + krow(e)][d] * Q[qb*32 + r][d]
-    f32x16 sc[NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sc[kt][e] = 0.0f;
-        if (kt < nkt) {
-#pragma unroll
-            for (int kq = 0; kq < 4; ++kq) {
-                const float4 kf = *reinterpret_cast<const float4*>(Ks + (kt * 32 + r) * LDQ + kq * 8 + h * 4);
-                sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[kq].x, sc[kt], 0, 0, 0);
-                sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[kq].y, sc[kt], 0, 0, 0);
-                sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[kq].z, sc[kt], 0, 0, 0);
-                sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[kq].w, sc[kt], 0, 0, 0);
+        for (int c0 = 0; c0 < NKT; c0 += KC) {
+            if (c0 < nkt) {
+                if (!once) stage(c0, with_v);
+                if (active) {
+                    const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
+                    for (int kt = c0; kt < c1; ++kt) f(kt, c0);
+                }
             }
         }
-    }
-    // ---- scores in log2 units (scale * log2(e) folded), key tail masked, row max
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-        if (kt < nkt) {
-            const bool last = kt == nkt - 1;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float v = sc[kt][e] * scale_log2e;
-                if (last && kt * 32 + acc_row(e, lane) >= L) v = -INFINITY;
-                sc[kt][e] = v;
-                mx = fmaxf(mx, v);
-            }
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // ---- p = 2^(v - max); denominator = this half-wave's keys ascending, then the two halves added
+    };
+    if (once) stage(0, true);
+    // p = 2^(v - max); denominator = this half-wave's keys ascending, then the two halves added
     float lsum = 0.0f;
+    if constexpr (RECOMP) {
+        float mx = -INFINITY;
+        for_tiles(false, [&](int kt, int c0) {
+            const f32x16 t = score_tile(kt, c0);
 #pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-        if (kt < nkt) {
+            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
+        });
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        for_tiles(true, [&](int kt, int c0) {
+            f32x16 t = score_tile(kt, c0);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const float p = __builtin_amdgcn_exp2f(sc[kt][e] - mx);
-                sc[kt][e] = p;
+                const float p = __builtin_amdgcn_exp2f(t[e] - mx);
+                t[e] = p;
                 lsum = lsum + p;
             }
-        }
-    }
-    {
-        const float other = __shfl_xor(lsum, 32, 64);
-        lsum = h == 0 ? lsum + other : other + lsum;  // l0 + l1 in both halves
-    }
-    if (h == 0) Ls[wave * 32 + r] = lsum;
-    // ---- O = P.V with P taken straight from the accumulator registers
+            pv_tile(kt, c0, t);
+        });
+    } else if (active) {
+        f32x16 sc[NKT];
+        float mx = -INFINITY;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) o[e] = 0.0f;
+        for (int kt = 0; kt < NKT; ++kt) {
+            if (kt < nkt) {
+                sc[kt] = score_tile(kt, 0);
 #pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-        if (kt < nkt) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                o = __builtin_amdgcn_mfma_f32_32x32x2f32(sc[kt][e], Vs[key * DH + r], o, 0, 0, 0);
+                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sc[kt][e]);
             }
         }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            if (kt < nkt) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float p = __builtin_amdgcn_exp2f(sc[kt][e] - mx);
+                    sc[kt][e] = p;
+                    lsum = lsum + p;
+                }
+            }
+        }
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+            if (kt < nkt) pv_tile(kt, 0, sc[kt]);
     }
-    }
+    if (!active) return;  // (no barrier below)
+    lsum = join_halves(lsum, h);
+    if (h == 0) Ls[wave * 32 + r] = lsum;
     // ---- normalise rows by their denominator and store (row = query, column = head dim);
     // Ls was written by this wave's own lanes (wave-local LDS ordering makes it visible).
 #pragma unroll
@@ -339,148 +339,10 @@ __global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __rest
         const int qrow = acc_row(e, lane);
         const int tq = qb * 32 + qrow;
         if (tq < L) {
-            const float v = o[e] / Ls[wave * 32 + qrow];
-            ctx[(size_t)(t0 + tq) * H + hd * DH + r] = v;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- attention over 64-dim heads (hidden 768: BERT-base)
-// The same (sequence, head) x 32-query-block mapping, S^T-on-the-accumulator-rows layout and P fed back from the
-// accumulators as attention_kernel / attention_x3_kernel, for head_dim 64: the score chain runs over 64 dims, the output
-// of a wave is two 32 x 32 tiles (dims r and 32 + r of the lane's column).  K and V of one (sequence, head) take twice the
-// LDS of a 32-dim head, so they are staged in chunks of at most ATT64_KC key tiles (256 keys): a sequence of up to 256
-// tokens is staged once; a longer one (the 9-16-tile bucket, up to 512 keys) is staged chunk by chunk, twice - K alone
-// for the row maximum, then K and V for the exponentials and P.V.  Every bucket runs the same two-pass form (the score
-// tiles are computed once for the maximum and once more for the exponentials, each tile consumed by P.V as soon as it
-// exists), and the per-query arithmetic depends neither on the bucket nor on the chunking: a sequence gives the same
-// bits whichever launch serves it.
-constexpr int DH64 = 64;
-constexpr int LDQ64 = 68;    // K LDS row stride of the fp32 kernel (even/odd split layout, as LDQ)
-constexpr int ATT64_KC = 8;  // key tiles staged in LDS at once
-
-// Exact fp32 form (gemm_mode F32): scores on v_mfma_f32_32x32x2_f32, dims in pairs ascending; per 32-key tile the P.V
-// key order of attention_kernel ((e&3) + 8(e>>2) + 4h); denominator: each half-wave's keys ascending, the halves added.
-template <int NKT>
-__global__ __launch_bounds__(NKT * 64) void attention64_kernel(const float* __restrict__ qkv,
-                                                               const int32_t* __restrict__ cu, int heads, int H,
-                                                               float scale_log2e, float* __restrict__ ctx) {
-    constexpr int KC = NKT < ATT64_KC ? NKT : ATT64_KC;
-    __shared__ __attribute__((aligned(16))) float Ks[KC * 32 * LDQ64];
-    __shared__ __attribute__((aligned(16))) float Vs[KC * 32 * DH64];
-    __shared__ float Ls[NKT * 32];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int s = blockIdx.x / heads, hd = blockIdx.x % heads;
-    const int t0 = cu[s], L = cu[s + 1] - t0;
-    const int nkt = (L + 31) >> 5;
-    if (nkt > NKT || (NKT > 1 && nkt <= NKT / 2)) return;  // another bucket's sequence
-    const int ld = 3 * H;
-    const int r = lane & 31, h = lane >> 5, qb = wave;
-    const bool active = qb < nkt;  // wave-uniform; idle waves still take part in the barriers of the staging
-    float4 qf[8];  // this lane's query row: lane half h supplies the even / odd dims of every pair
-    {
-        int qr = qb * 32 + r;
-        qr = qr < L ? qr : L - 1;
-        const float4* qp = reinterpret_cast<const float4*>(qkv + (size_t)(t0 + qr) * ld + hd * DH64);
-#pragma unroll
-        for (int kq = 0; kq < 8; ++kq) {
-            const float4 a = qp[2 * kq], b = qp[2 * kq + 1];
-            qf[kq] = h == 0 ? make_float4(a.x, a.z, b.x, b.z) : make_float4(a.y, a.w, b.y, b.w);
-        }
-    }
-    // key tiles [c0, c0 + KC) -> LDS (K in the even/odd split layout, V row-major); rows past L are clamped
-    auto stage = [&](int c0, bool with_v) {
-        __syncthreads();  // the previous chunk's readers are done
-        const int nk = (nkt - c0 < KC ? nkt - c0 : KC) * 32;
-        for (int id = tid; id < nk * 16; id += NKT * 64) {
-            const int row = id >> 4, c = id & 15;
-            const int key = c0 * 32 + row, rr = key < L ? key : L - 1;
-            const float* src = qkv + (size_t)(t0 + rr) * ld + hd * DH64 + c * 4;
-            const float4 kv = *reinterpret_cast<const float4*>(src + H);
-            float* kp = Ks + row * LDQ64 + (c >> 1) * 8 + (c & 1) * 2;
-            *reinterpret_cast<float2*>(kp) = make_float2(kv.x, kv.z);
-            *reinterpret_cast<float2*>(kp + 4) = make_float2(kv.y, kv.w);
-            if (with_v) *reinterpret_cast<float4*>(Vs + row * DH64 + c * 4) = *reinterpret_cast<const float4*>(src + 2 * H);
-        }
-        __syncthreads();
-    };
-    auto score_tile = [&](int kt, int c0) {  // log2-unit scores of key tile kt (staged from c0), tail keys at -inf
-        f32x16 t;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t[e] = 0.0f;
-#pragma unroll
-        for (int kq = 0; kq < 8; ++kq) {
-            const float4 kf = *reinterpret_cast<const float4*>(Ks + ((kt - c0) * 32 + r) * LDQ64 + kq * 8 + h * 4);
-            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[kq].x, t, 0, 0, 0);
-            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[kq].y, t, 0, 0, 0);
-            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[kq].z, t, 0, 0, 0);
-            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[kq].w, t, 0, 0, 0);
-        }
-        const bool last = kt == nkt - 1;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            float v = t[e] * scale_log2e;
-            if (last && kt * 32 + acc_row(e, lane) >= L) v = -INFINITY;
-            t[e] = v;
-        }
-        return t;
-    };
-    const bool once = nkt <= KC;  // the whole sequence fits: staged once, K and V
-    if (once) stage(0, true);
-    float mx = -INFINITY;
-    for (int c0 = 0; c0 < nkt; c0 += KC) {
-        if (!once) stage(c0, false);
-        if (active) {
-            const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
-            for (int kt = c0; kt < c1; ++kt) {
-                const f32x16 t = score_tile(kt, c0);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
-            }
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float lsum = 0.0f;
-    f32x16 o[2];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[0][e] = o[1][e] = 0.0f;
-    for (int c0 = 0; c0 < nkt; c0 += KC) {
-        if (!once) stage(c0, true);
-        if (active) {
-            const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
-            for (int kt = c0; kt < c1; ++kt) {
-                f32x16 t = score_tile(kt, c0);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float p = __builtin_amdgcn_exp2f(t[e] - mx);
-                    t[e] = p;
-                    lsum = lsum + p;
-                }
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int key = (kt - c0) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                    o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(t[e], Vs[key * DH64 + r], o[0], 0, 0, 0);
-                    o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(t[e], Vs[key * DH64 + 32 + r], o[1], 0, 0, 0);
-                }
-            }
-        }
-    }
-    if (!active) return;  // (no barrier below)
-    {
-        const float other = __shfl_xor(lsum, 32, 64);
-        lsum = h == 0 ? lsum + other : other + lsum;
-    }
-    if (h == 0) Ls[wave * 32 + r] = lsum;  // read back by this wave's own lanes only
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int qrow = acc_row(e, lane);
-        const int tq = qb * 32 + qrow;
-        if (tq < L) {
             const float l = Ls[wave * 32 + qrow];
-            float* dst = ctx + (size_t)(t0 + tq) * H + hd * DH64 + r;
-            dst[0] = o[0][e] / l;
-            dst[32] = o[1][e] / l;
+            float* dst = ctx + (size_t)(t0 + tq) * H + hd * D + r;
+#pragma unroll
+            for (int dt = 0; dt < D / 32; ++dt) dst[32 * dt] = o[dt][e] / l;
         }
     }
 }
@@ -521,9 +383,9 @@ __global__ __launch_bounds__(1024) void seq_order_kernel(const int32_t* __restri
 // back from the accumulators), with both products on the f16 MFMA by the 3-term split of wt_gemm.h (one accumulator,
 // the plane scales folded into constants: see the kernel):
 //   S^T ~ K_hi.Q_hi + K_hi.Q_lo + K_lo.Q_hi        O ~ P_hi.V_hi + P_hi.V_lo + P_lo.V_hi
-// K is staged as hi/lo f16 planes [key][32] (64-B rows, 16-B chunks XOR-swizzled by (key>>2)&3), V as
-// TRANSPOSED hi/lo planes [dim][key] so that a lane's eight k-slots (keys) of one head dim are two 8-B
-// reads; Q (per wave) and P (per tile, straight from the accumulators) are split in registers.
+// K is staged as hi/lo f16 planes [key][D] with the 16-B chunks of a row XOR-swizzled (att_k_swz), V as row-major hi/lo
+// planes [key][D] read through the transposing LDS read; Q (per wave) and P (per tile, straight from the accumulators)
+// are split in registers.
 // For a 32-key tile and k-step s, slot j of lane-half h is key 4h + (j&3) + 8(2s + (j>>2)) — the keys
 // accumulator register e = 8s + j holds — on both operands.
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
@@ -535,41 +397,46 @@ __device__ __forceinline__ half4 lds_read_tr(const _Float16* p) {
                                          (__attribute__((address_space(3))) fp16x4*)(reinterpret_cast<uintptr_t>(p))));
 }
 
-// nlo: sequences of nlo < nkt <= NKT key tiles belong to this launch (the others' workgroups exit at once).
-// Output: the context as f16 hi/lo planes (`ch` / `cl`; ctx unused).
-template <int NKT>  // NKT waves, one per 32-row query block
-__global__ __launch_bounds__(NKT * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void attention_x3_kernel(const float* __restrict__ qkv,
-                                                                  const int32_t* __restrict__ cu, int heads, int H,
-                                                                  float scale_log2e, float* __restrict__ ctx,
-                                                                  _Float16* __restrict__ ch, _Float16* __restrict__ cl,
-                                                                  const int32_t* __restrict__ order, int nlo) {
+// Swizzle key of a K plane row: 64-B rows (D = 32) repeat their bank pattern every 4 rows, 128-B rows (D = 64) every row.
+constexpr int att_k_swz(int D, int row) { return D == 32 ? (row >> 2) & 3 : row & 7; }
+// Workgroups per CU the register allocation aims at (32-dim heads; 64-dim heads are bound by their LDS).
+constexpr int att_x3_wgs(int D, int NKT) { return D != 32 ? 1 : NKT >= 6 ? 4 : NKT == 4 ? 3 : 1; }
+
+// Output: the context as f16 hi/lo planes (`ch` / `cl`).  order: seq_order_kernel's dispatch order, or nullptr.
+template <int D, int NKT>  // NKT waves, one per 32-row query block
+__global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_kernel(
+    const float* __restrict__ qkv, const int32_t* __restrict__ cu, int heads, int H, float scale_log2e,
+    _Float16* __restrict__ ch, _Float16* __restrict__ cl, const int32_t* __restrict__ order, int nlo) {
     // Single-accumulator form of the split (wt_gemm.h): every operand is carried as hi/lo f16 planes of 16 x (Q, K, V)
     // or 1024 p (the probabilities), the three products of a k-step accumulate into ONE fp32 tile, and the power-of-two
     // scales are folded into constants: S' = 256 S, O' = 16384 sum_k p_k V_k, l' = 1024 sum_k p_k, O = O' / (16 l').
     // All splits are the 3-instruction form (mask / subtract / v_cvt_pkrtz pairs).
     //
-    // Long buckets (NKT >= 6, RECOMP): the score tiles are computed TWICE - once for the row maximum (on the hi x hi
-    // products alone, see score_tile), once more in full for the exponentials, each tile consumed by the PV product as
-    // soon as it exists - instead of all of them being held in 128 registers between the two passes: 16 more MFMAs per
-    // wave, and the kernel drops under 128 VGPRs; with the output tile parked on the K
+    // Long buckets (NKT >= 6) and 64-dim heads, RECOMP: the score tiles are computed TWICE - once for the row maximum
+    // (on the hi x hi products alone, see score_tile), once more in full for the exponentials, each tile consumed by the
+    // PV product as soon as it exists - instead of all of them being held in 128 registers between the two passes: 16
+    // more MFMAs per wave, and the 32-dim kernel drops under 128 VGPRs; with the output tile parked on the K
     // planes (behind one more barrier) it also drops to 67 KB of LDS - TWO workgroups per CU, so one's staging and
     // barrier phases run under the other's arithmetic.
-    constexpr bool RECOMP = NKT >= 6;
-    __shared__ __attribute__((aligned(16))) _Float16 Kbuf[2 * NKT * 32 * 32];
+    constexpr int KC = att_kc(D, NKT), G = D / 4;  // G: 4-dim groups of a row
+    constexpr bool RECOMP = D == 64 || NKT >= 6;
+    // The two places where the widths differ for speed, not for width.  32-dim heads issue all of a thread's K/V loads
+    // before the first one is consumed (PREFETCH) and park each wave's output tile (hi | lo) on the K planes once all waves
+    // have left them, to write it out 16 B per lane - 4 store instructions instead of 32 two-byte ones (PARK; the NKT
+    // tiles fill the K planes exactly).  64-dim heads stage with a plain loop and store straight from the accumulators.
+    constexpr bool PREFETCH = D == 32, PARK = D == 32;
+    static_assert(!PARK || KC == NKT, "the parked output tiles need the K planes of all NKT key tiles");
+    __shared__ __attribute__((aligned(16))) _Float16 Kbuf[2 * KC * 32 * D];
     _Float16* const Kh = Kbuf;
-    _Float16* const Kl = Kbuf + NKT * 32 * 32;
-    // V as it arrives: row-major hi / lo planes [key][32 dims] (64-B rows, one 8-byte store per thread and plane where the
+    _Float16* const Kl = Kbuf + KC * 32 * D;
+    // V as it arrives: row-major hi / lo planes [key][D] (one 8-byte store per thread and plane where the
     // transposed image took four 2-byte ones); the P.V product reads its B operand - 4 consecutive keys of one head
     // dimension per lane - with the transposing LDS read (ds_read_b64_tr_b16: per 16-lane group a block of 4 keys x 16
-    // dims, lane 4q + p supplying the address of key q, dims 4p..4p+3, lane i receiving dim i of the 4 keys; a 32-lane
-    // half covers 4 rows of 64 B = every bank once).
-    __shared__ __attribute__((aligned(16))) _Float16 Vh[NKT * 32 * 32];
-    __shared__ __attribute__((aligned(16))) _Float16 Vl[NKT * 32 * 32];
+    // dims, lane 4q + p supplying the address of key q, dims 4p..4p+3, lane i receiving dim i of the 4 keys; at D = 32 a
+    // 32-lane half covers 4 rows of 64 B = every bank once).
+    __shared__ __attribute__((aligned(16))) _Float16 Vh[KC * 32 * D];
+    __shared__ __attribute__((aligned(16))) _Float16 Vl[KC * 32 * D];
     __shared__ float Ls[NKT * 32];
-    // Plane output: every wave parks its 32 x 32 output tile (hi | lo) on the K planes once all waves have left them
-    // (second barrier) and writes it out 16 B per lane - 4 store instructions instead of 32 two-byte ones.  The NKT
-    // tiles fill the K planes exactly.
-    _Float16* const Ob = Kbuf;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int sidx = blockIdx.x / heads, hd = blockIdx.x % heads;
@@ -577,19 +444,16 @@ __global__ __launch_bounds__(NKT * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void a
     const int t0 = cu[s], L = cu[s + 1] - t0;
     const int nkt = (L + 31) >> 5;
     if (nkt > NKT || nkt <= nlo) return;  // another bucket's sequence
-    const int qb0 = blockIdx.y * NKT;
-    if (qb0 >= nkt) return;
     const int ld = 3 * H;
-
-    const int r = lane & 31, h = lane >> 5;
-    const int qb = qb0 + wave;
-    half8 qh[2], ql[2];  // B operand of S^T: this lane's query row, dims 16s + 8h .. +7
+    const int r = lane & 31, h = lane >> 5, qb = wave;
+    const bool active = qb < nkt;  // wave-uniform; idle waves still take part in the barriers
+    half8 qh[D / 16], ql[D / 16];  // B operand of S^T: this lane's query row, dims 16 ks + 8 h .. +7
     {
         int qr = qb * 32 + r;
         qr = qr < L ? qr : L - 1;
-        const float* qp = qkv + (size_t)(t0 + qr) * ld + hd * DH;
+        const float* qp = qkv + (size_t)(t0 + qr) * ld + hd * D;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
+        for (int ks = 0; ks < D / 16; ++ks) {
             const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 8 * h);
             const f32x4 b = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 8 * h + 4);
             half4 ah, al, bh, bl;
@@ -599,275 +463,66 @@ __global__ __launch_bounds__(NKT * 64, (NKT >= 6 ? 4 : NKT == 4 ? 3 : 1)) void a
             ql[ks] = half8{al[0], al[1], al[2], al[3], bl[0], bl[1], bl[2], bl[3]};
         }
     }
-    // K/V staging: all of this thread's loads are issued before the first one is consumed
-    constexpr int STG = NKT * 32 * 8 / (NKT * 64);  // = 4 for every bucket
-    static_assert(NKT * 32 * 8 % (NKT * 64) == 0, "staging: whole rounds");
-    f32x4 kreg[STG], vreg[STG];
-#pragma unroll
-    for (int it = 0; it < STG; ++it) {
-        const int id = tid + it * NKT * 64;
-        const int key = id >> 3, c = id & 7;  // c: 4-dim group
-        const int rr = key < L ? key : L - 1;
-        const float* src = qkv + (size_t)(t0 + rr) * ld + hd * DH + c * 4;
-        kreg[it] = *reinterpret_cast<const f32x4*>(src + H);
-        vreg[it] = *reinterpret_cast<const f32x4*>(src + 2 * H);
-    }
-#pragma unroll
-    for (int it = 0; it < STG; ++it) {
-        const int id = tid + it * NKT * 64;
-        if (id < nkt * 32 * 8) {
-            const int key = id >> 3, c = id & 7;
-            half4 khi, klo, vhi, vlo;
-            split_act4(kreg[it], khi, klo);
-            split_act4(vreg[it], vhi, vlo);
-            *reinterpret_cast<half4*>(Vh + key * 32 + c * 4) = vhi;
-            *reinterpret_cast<half4*>(Vl + key * 32 + c * 4) = vlo;
-            const int off = key * 32 + ((((c >> 1) ^ ((key >> 2) & 3)) << 3) | ((c & 1) << 2));
+    const bool once = KC == NKT || nkt <= KC;  // the whole sequence fits: staged once, K and V
+    // key tiles [c0, c0 + KC) -> the LDS planes; rows past L are clamped (masked below / never stored)
+    auto stage = [&](int c0, bool with_v) {
+        if (!once) __syncthreads();  // the previous chunk's readers are done
+        const int nk = (nkt - c0 < KC ? nkt - c0 : KC) * 32;
+        auto src_of = [&](int id) {  // item id = (row, 4-dim group) of the chunk
+            const int key = c0 * 32 + id / G, rr = key < L ? key : L - 1;
+            return qkv + (size_t)(t0 + rr) * ld + hd * D + (id % G) * 4;
+        };
+        auto put = [&](int id, const f32x4& k, const f32x4& v) {
+            const int row = id / G, c = id % G;
+            half4 khi, klo;
+            split_act4(k, khi, klo);
+            if (with_v) {
+                half4 vhi, vlo;
+                split_act4(v, vhi, vlo);
+                *reinterpret_cast<half4*>(Vh + row * D + c * 4) = vhi;
+                *reinterpret_cast<half4*>(Vl + row * D + c * 4) = vlo;
+            }
+            const int off = row * D + ((((c >> 1) ^ att_k_swz(D, row)) << 3) | ((c & 1) << 2));
             *reinterpret_cast<half4*>(Kh + off) = khi;
             *reinterpret_cast<half4*>(Kl + off) = klo;
+        };
+        if constexpr (PREFETCH) {
+            constexpr int STG = KC * 32 * G / (NKT * 64);
+            static_assert(KC * 32 * G % (NKT * 64) == 0, "staging: whole rounds");
+            f32x4 kreg[STG], vreg[STG];
+#pragma unroll
+            for (int it = 0; it < STG; ++it) {
+                const float* src = src_of(tid + it * NKT * 64);
+                kreg[it] = *reinterpret_cast<const f32x4*>(src + H);
+                if (with_v) vreg[it] = *reinterpret_cast<const f32x4*>(src + 2 * H);
+            }
+#pragma unroll
+            for (int it = 0; it < STG; ++it)
+                if (tid + it * NKT * 64 < nk * G) put(tid + it * NKT * 64, kreg[it], vreg[it]);
+        } else {
+            for (int id = tid; id < nk * G; id += NKT * 64) {
+                const float* src = src_of(id);
+                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (with_v) v = *reinterpret_cast<const f32x4*>(src + 2 * H);
+                put(id, *reinterpret_cast<const f32x4*>(src + H), v);
+            }
         }
-    }
-    __syncthreads();
-    const bool active = qb < nkt;
-
-    // raw scores S' = 256 S of key tile kt for this wave's 32 queries, keys beyond the sequence at -inf (only the one
-    // tile that has any pays for the selects: uniform branch)
-    // hi_only (the row-maxima pass of the long buckets): the hi x hi products alone - 2 MFMAs per tile instead of 6.  The
+        __syncthreads();
+    };
+    // raw scores S' = 256 S of key tile kt (staged from c0) for this wave's 32 queries, keys beyond the sequence at -inf
+    // (only the one tile that has any pays for the selects: uniform branch)
+    // hi_only (the row-maxima pass): the hi x hi products alone - a third of the MFMAs.  The
     // softmax does not care which shift it is given as long as the exponentials stay in range; this approximate maximum
     // can sit below the true one by at most 2^-10 |q| |k| in score units, the planes of p' = 2^10 p have 2^6 of head room,
     // and the exponent is clamped for whatever lies beyond (|q| |k| > 2.4e4: two hundred times a BERT head's).
-    auto score_tile = [&](int kt, bool hi_only = false) {
-        f32x16 t;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t[e] = 0.0f;
-        const int key = kt * 32 + r;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int off = key * 32 + (((2 * ks + h) ^ ((key >> 2) & 3)) << 3);
-            const half8 kh = *reinterpret_cast<const half8*>(Kh + off);
-            const half8 kl = *reinterpret_cast<const half8*>(Kl + off);
-            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], t, 0, 0, 0);
-            if (hi_only) continue;
-            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], t, 0, 0, 0);
-            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], t, 0, 0, 0);
-        }
-        if (kt == nkt - 1 && kt * 32 + 32 > L) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (kt * 32 + acc_row(e, lane) >= L) t[e] = -INFINITY;
-        }
-        return t;
-    };
-    // P (a tile of p' = 1024 p in the accumulator layout) times V, into o
-    auto pv_tile = [&](int kt, const f32x16& pt, f32x16& o) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 ph, pl;
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                half2w a, b;
-                split_pair_prescaled(pt[8 * ks + j], pt[8 * ks + j + 1], a, b);
-                ph[j] = a[0]; ph[j + 1] = a[1];
-                pl[j] = b[0]; pl[j + 1] = b[1];
-            }
-            // this lane's head dim r, keys base .. base+3 and base+8 .. base+11: two transposed 4-key x 16-dim blocks per plane
-            const int base = kt * 32 + 4 * h + 16 * ks;
-            const int tr_at = (base + ((lane & 15) >> 2)) * 32 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-            const half4 v0h = lds_read_tr(Vh + tr_at);
-            const half4 v1h = lds_read_tr(Vh + tr_at + 8 * 32);
-            const half4 v0l = lds_read_tr(Vl + tr_at);
-            const half4 v1l = lds_read_tr(Vl + tr_at + 8 * 32);
-            const half8 vh = {v0h[0], v0h[1], v0h[2], v0h[3], v1h[0], v1h[1], v1h[2], v1h[3]};
-            const half8 vl = {v0l[0], v0l[1], v0l[2], v0l[3], v1l[0], v1l[1], v1l[2], v1l[3]};
-            o = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh, o, 0, 0, 0);
-            o = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl, o, 0, 0, 0);
-            o = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh, o, 0, 0, 0);
-        }
-    };
-    typedef float float2w __attribute__((ext_vector_type(2)));
-    const float cs = scale_log2e * (1.0f / 256.0f);  // scores in log2 units from S' = 256 S
-    f32x16 o;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[e] = 0.0f;
-    if (RECOMP) {
-        if (active) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt) {
-                if (kt < nkt) {
-                    const f32x16 t = score_tile(kt, true);
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
-                }
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float shift = fmaf(-mx, cs, 10.0f);
-            float2w ls2 = float2w{0.0f, 0.0f};
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt) {
-                if (kt < nkt) {
-                    f32x16 t = score_tile(kt);
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(fmaf(t[e], cs, shift), 15.9f));
-#pragma unroll
-                    for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{t[e], t[e + 1]};
-                    pv_tile(kt, t, o);
-                }
-            }
-            float lrow = ls2[0] + ls2[1];
-            const float other = __shfl_xor(lrow, 32, 64);
-            lrow = h == 0 ? lrow + other : other + lrow;
-            if (h == 0) Ls[wave * 32 + r] = lrow;
-        }
-    } else {
-    if (active) {
-    f32x16 sc[NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-        if (kt < nkt) sc[kt] = score_tile(kt);
-    // Softmax on the raw scores (S' = 256 S): the keys beyond the sequence are masked in the one tile that has any
-    // (uniform branch), the maximum is taken before scaling, and scale, shift and the 2^10 factor of p' = 1024 p go
-    // into one fma in front of the exponential: p' = 2^(S' cs - max' cs + 10).
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-        if (kt < nkt) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sc[kt][e]);
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float shift = fmaf(-mx, cs, 10.0f);
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-        if (kt < nkt) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sc[kt][e] = __builtin_amdgcn_exp2f(fmaf(sc[kt][e], cs, shift));
-        }
-    }
-    // row sums l' = sum_k p'_k: two interleaved chains per lane (packed adds), the halves of a row joined by a shuffle
-    float2w ls2 = float2w{0.0f, 0.0f};
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-        if (kt < nkt) {
-#pragma unroll
-            for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{sc[kt][e], sc[kt][e + 1]};
-        }
-    }
-    float lrow = ls2[0] + ls2[1];
-    {
-        const float other = __shfl_xor(lrow, 32, 64);
-        lrow = h == 0 ? lrow + other : other + lrow;
-    }
-    if (h == 0) Ls[wave * 32 + r] = lrow;
-
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-        if (kt < nkt) pv_tile(kt, sc[kt], o);
-    }
-    }
-    __syncthreads();  // every wave has left the K planes: they become the output tiles
-    if (!active) return;
-    // park the wave's 32 x 32 output tile (hi and lo planes) in LDS row-major, then write it out 16 B
-    // per lane: 4 store instructions instead of 32 two-byte ones
-    _Float16* ob = Ob + wave * (2 * 32 * 32);
-#pragma unroll
-    for (int e = 0; e < 16; e += 2) {
-        const int q0 = acc_row(e, lane), q1 = acc_row(e + 1, lane);
-        const float v0 = o[e] * (0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q0]));
-        const float v1 = o[e + 1] * (0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q1]));
-        half2w hi, lo;
-        split_pair_prescaled(v0 * WT_SA, v1 * WT_SA, hi, lo);
-        ob[q0 * 32 + r] = hi[0];
-        ob[q1 * 32 + r] = hi[1];
-        ob[32 * 32 + q0 * 32 + r] = lo[0];
-        ob[32 * 32 + q1 * 32 + r] = lo[1];
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int id = lane + 64 * t, qrow = id >> 2, c8 = (id & 3) * 8;
-        const int tq = qb * 32 + qrow;
-        if (tq < L) {
-            const size_t at = (size_t)(t0 + tq) * H + hd * DH + c8;
-            *reinterpret_cast<u32x4*>(ch + at) = *reinterpret_cast<const u32x4*>(ob + qrow * 32 + c8);
-            *reinterpret_cast<u32x4*>(cl + at) = *reinterpret_cast<const u32x4*>(ob + 32 * 32 + qrow * 32 + c8);
-        }
-    }
-}
-
-// f16x3 form over 64-dim heads: the products of attention_x3_kernel (S' = 256 S and O' on the 3-term split, one fp32
-// accumulator, p' = 1024 p) in the two-pass form of its long buckets (row maximum from the hi x hi products, exponent
-// clamped), with attention64_kernel's chunked staging.  K as hi/lo planes [key][64] (128-B rows, 16-B chunks XOR-swizzled
-// by key & 7), V as row-major hi/lo planes read through the transposing LDS read.  Output: the context planes, stored
-// straight from the accumulators.
-template <int NKT>
-__global__ __launch_bounds__(NKT * 64) void attention64_x3_kernel(const float* __restrict__ qkv,
-                                                                  const int32_t* __restrict__ cu, int heads, int H,
-                                                                  float scale_log2e, _Float16* __restrict__ ch,
-                                                                  _Float16* __restrict__ cl,
-                                                                  const int32_t* __restrict__ order) {
-    constexpr int KC = NKT < ATT64_KC ? NKT : ATT64_KC;
-    __shared__ __attribute__((aligned(16))) _Float16 Kh[KC * 32 * DH64];
-    __shared__ __attribute__((aligned(16))) _Float16 Kl[KC * 32 * DH64];
-    __shared__ __attribute__((aligned(16))) _Float16 Vh[KC * 32 * DH64];
-    __shared__ __attribute__((aligned(16))) _Float16 Vl[KC * 32 * DH64];
-    __shared__ float Ls[NKT * 32];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sidx = blockIdx.x / heads, hd = blockIdx.x % heads;
-    const int s = order != nullptr ? order[sidx] : sidx;
-    const int t0 = cu[s], L = cu[s + 1] - t0;
-    const int nkt = (L + 31) >> 5;
-    if (nkt > NKT || (NKT > 1 && nkt <= NKT / 2)) return;  // another bucket's sequence
-    const int ld = 3 * H;
-    const int r = lane & 31, h = lane >> 5, qb = wave;
-    const bool active = qb < nkt;
-    half8 qh[4], ql[4];  // B operand of S^T: this lane's query row, dims 16 ks + 8 h .. +7
-    {
-        int qr = qb * 32 + r;
-        qr = qr < L ? qr : L - 1;
-        const float* qp = qkv + (size_t)(t0 + qr) * ld + hd * DH64;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 8 * h);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 8 * h + 4);
-            half4 ah, al, bh, bl;
-            split_act4(a, ah, al);
-            split_act4(b, bh, bl);
-            qh[ks] = half8{ah[0], ah[1], ah[2], ah[3], bh[0], bh[1], bh[2], bh[3]};
-            ql[ks] = half8{al[0], al[1], al[2], al[3], bl[0], bl[1], bl[2], bl[3]};
-        }
-    }
-    auto stage = [&](int c0, bool with_v) {
-        __syncthreads();
-        const int nk = (nkt - c0 < KC ? nkt - c0 : KC) * 32;
-        for (int id = tid; id < nk * 16; id += NKT * 64) {
-            const int row = id >> 4, c = id & 15;  // c: 4-dim group
-            const int key = c0 * 32 + row, rr = key < L ? key : L - 1;
-            const float* src = qkv + (size_t)(t0 + rr) * ld + hd * DH64 + c * 4;
-            half4 khi, klo;
-            split_act4(*reinterpret_cast<const f32x4*>(src + H), khi, klo);
-            const int off = row * DH64 + ((((c >> 1) ^ (row & 7)) << 3) | ((c & 1) << 2));
-            *reinterpret_cast<half4*>(Kh + off) = khi;
-            *reinterpret_cast<half4*>(Kl + off) = klo;
-            if (with_v) {
-                half4 vhi, vlo;
-                split_act4(*reinterpret_cast<const f32x4*>(src + 2 * H), vhi, vlo);
-                *reinterpret_cast<half4*>(Vh + row * DH64 + c * 4) = vhi;
-                *reinterpret_cast<half4*>(Vl + row * DH64 + c * 4) = vlo;
-            }
-        }
-        __syncthreads();
-    };
-    // raw scores S' = 256 S of key tile kt (staged from c0); hi_only: the hi x hi products alone (the row-maximum pass)
     auto score_tile = [&](int kt, int c0, bool hi_only) {
         f32x16 t;
 #pragma unroll
         for (int e = 0; e < 16; ++e) t[e] = 0.0f;
         const int row = (kt - c0) * 32 + r;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const int off = row * DH64 + (((2 * ks + h) ^ (row & 7)) << 3);
+        for (int ks = 0; ks < D / 16; ++ks) {
+            const int off = row * D + (((2 * ks + h) ^ att_k_swz(D, row)) << 3);
             const half8 kh = *reinterpret_cast<const half8*>(Kh + off);
             const half8 kl = *reinterpret_cast<const half8*>(Kl + off);
             t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], t, 0, 0, 0);
@@ -882,10 +537,13 @@ __global__ __launch_bounds__(NKT * 64) void attention64_x3_kernel(const float* _
         }
         return t;
     };
-    f32x16 o[2];
+    // O' += P'.V for key tile kt: pt is a tile of p' = 1024 p in the accumulator layout; o[dt] holds head dims 32 dt + r
+    f32x16 o[D / 32];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) o[0][e] = o[1][e] = 0.0f;
-    auto pv_tile = [&](int kt, int c0, const f32x16& pt) {  // o[dt] += P' V for head dims 32 dt + r
+    for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[dt][e] = 0.0f;
+    auto pv_tile = [&](int kt, int c0, const f32x16& pt) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             half8 ph, pl;
@@ -896,14 +554,15 @@ __global__ __launch_bounds__(NKT * 64) void attention64_x3_kernel(const float* _
                 ph[j] = a[0]; ph[j + 1] = a[1];
                 pl[j] = b[0]; pl[j + 1] = b[1];
             }
+            // this lane's head dim, keys base .. base+3 and base+8 .. base+11: two transposed 4-key x 16-dim blocks per plane
             const int base = (kt - c0) * 32 + 4 * h + 16 * ks;
 #pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const int tr_at = (base + ((lane & 15) >> 2)) * DH64 + 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+            for (int dt = 0; dt < D / 32; ++dt) {
+                const int tr_at = (base + ((lane & 15) >> 2)) * D + 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
                 const half4 v0h = lds_read_tr(Vh + tr_at);
-                const half4 v1h = lds_read_tr(Vh + tr_at + 8 * DH64);
+                const half4 v1h = lds_read_tr(Vh + tr_at + 8 * D);
                 const half4 v0l = lds_read_tr(Vl + tr_at);
-                const half4 v1l = lds_read_tr(Vl + tr_at + 8 * DH64);
+                const half4 v1l = lds_read_tr(Vl + tr_at + 8 * D);
                 const half8 vh = {v0h[0], v0h[1], v0h[2], v0h[3], v1h[0], v1h[1], v1h[2], v1h[3]};
                 const half8 vl = {v0l[0], v0l[1], v0l[2], v0l[3], v1l[0], v1l[1], v1l[2], v1l[3]};
                 o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh, o[dt], 0, 0, 0);
@@ -912,46 +571,87 @@ __global__ __launch_bounds__(NKT * 64) void attention64_x3_kernel(const float* _
             }
         }
     };
+    // every key tile of the sequence, chunk by chunk (one chunk when the sequence was staged whole)
+    auto for_tiles = [&](bool with_v, auto&& f) {
+#pragma unroll
+        for (int c0 = 0; c0 < NKT; c0 += KC) {
+            if (c0 < nkt) {
+                if (!once) stage(c0, with_v);
+                if (active) {
+#pragma unroll
+                    for (int j = 0; j < KC; ++j)
+                        if (c0 + j < nkt) f(c0 + j, c0);
+                }
+            }
+        }
+    };
     typedef float float2w __attribute__((ext_vector_type(2)));
-    const float cs = scale_log2e * (1.0f / 256.0f);
-    const bool once = nkt <= KC;
-    if (once) stage(0, true);
-    float mx = -INFINITY;
-    for (int c0 = 0; c0 < nkt; c0 += KC) {
-        if (!once) stage(c0, false);
-        if (active) {
-            const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
-            for (int kt = c0; kt < c1; ++kt) {
-                const f32x16 t = score_tile(kt, c0, true);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
-            }
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float shift = fmaf(-mx, cs, 10.0f);
+    const float cs = scale_log2e * (1.0f / 256.0f);  // scores in log2 units from S' = 256 S
+    // Softmax on the raw scores (S' = 256 S): the maximum is taken before scaling, and scale, shift and the 2^10 factor
+    // of p' = 1024 p go into one fma in front of the exponential: p' = 2^(S' cs - max' cs + 10).
+    // row sums l' = sum_k p'_k: two interleaved chains per lane (packed adds), the halves of a row joined by a shuffle
     float2w ls2 = float2w{0.0f, 0.0f};
-    for (int c0 = 0; c0 < nkt; c0 += KC) {
-        if (!once) stage(c0, true);
-        if (active) {
-            const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
-            for (int kt = c0; kt < c1; ++kt) {
-                f32x16 t = score_tile(kt, c0, false);
+    auto join_rows = [&]() {
+        const float lrow = join_halves(ls2[0] + ls2[1], h);
+        if (h == 0) Ls[wave * 32 + r] = lrow;  // read back by this wave's own lanes only
+    };
+    if (once) stage(0, true);
+    if constexpr (RECOMP) {
+        float mx = -INFINITY;
+        for_tiles(false, [&](int kt, int c0) {
+            const f32x16 t = score_tile(kt, c0, true);
 #pragma unroll
-                for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(fmaf(t[e], cs, shift), 15.9f));
+            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
+        });
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float shift = fmaf(-mx, cs, 10.0f);
+        for_tiles(true, [&](int kt, int c0) {
+            f32x16 t = score_tile(kt, c0, false);
 #pragma unroll
-                for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{t[e], t[e + 1]};
-                pv_tile(kt, c0, t);
+            for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(fmaf(t[e], cs, shift), 15.9f));
+#pragma unroll
+            for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{t[e], t[e + 1]};
+            pv_tile(kt, c0, t);
+        });
+        if (active) join_rows();
+    } else if (active) {
+        f32x16 sc[NKT];
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+            if (kt < nkt) sc[kt] = score_tile(kt, 0, false);
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            if (kt < nkt) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sc[kt][e]);
             }
         }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float shift = fmaf(-mx, cs, 10.0f);
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            if (kt < nkt) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) sc[kt][e] = __builtin_amdgcn_exp2f(fmaf(sc[kt][e], cs, shift));
+            }
+        }
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            if (kt < nkt) {
+#pragma unroll
+                for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{sc[kt][e], sc[kt][e + 1]};
+            }
+        }
+        join_rows();
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+            if (kt < nkt) pv_tile(kt, 0, sc[kt]);
     }
-    if (!active) return;  // (no barrier below)
-    float lrow = ls2[0] + ls2[1];
-    {
-        const float other = __shfl_xor(lrow, 32, 64);
-        lrow = h == 0 ? lrow + other : other + lrow;
-    }
-    if (h == 0) Ls[wave * 32 + r] = lrow;  // read back by this wave's own lanes only
+    if (PARK) __syncthreads();  // every wave has left the K planes: they become the output tiles
+    if (!active) return;
+    // normalise, split into the hi / lo planes and store: PARK row-major into the wave's LDS tile, else to memory
+    _Float16* const ob = Kbuf + wave * (2 * 32 * D);
 #pragma unroll
     for (int e = 0; e < 16; e += 2) {
         const int q0 = acc_row(e, lane), q1 = acc_row(e + 1, lane);
@@ -959,17 +659,36 @@ __global__ __launch_bounds__(NKT * 64) void attention64_x3_kernel(const float* _
         const float s1 = 0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q1]);
         const int tq0 = qb * 32 + q0, tq1 = qb * 32 + q1;
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
+        for (int dt = 0; dt < D / 32; ++dt) {
             half2w hi, lo;
             split_pair_prescaled(o[dt][e] * s0 * WT_SA, o[dt][e + 1] * s1 * WT_SA, hi, lo);
-            const size_t c = (size_t)hd * DH64 + 32 * dt + r;
-            if (tq0 < L) {
-                ch[(size_t)(t0 + tq0) * H + c] = hi[0];
-                cl[(size_t)(t0 + tq0) * H + c] = lo[0];
+            const int c = 32 * dt + r;
+            if constexpr (PARK) {
+                ob[q0 * D + c] = hi[0];
+                ob[q1 * D + c] = hi[1];
+                ob[32 * D + q0 * D + c] = lo[0];
+                ob[32 * D + q1 * D + c] = lo[1];
+            } else {
+                if (tq0 < L) {
+                    ch[(size_t)(t0 + tq0) * H + hd * D + c] = hi[0];
+                    cl[(size_t)(t0 + tq0) * H + hd * D + c] = lo[0];
+                }
+                if (tq1 < L) {
+                    ch[(size_t)(t0 + tq1) * H + hd * D + c] = hi[1];
+                    cl[(size_t)(t0 + tq1) * H + hd * D + c] = lo[1];
+                }
             }
-            if (tq1 < L) {
-                ch[(size_t)(t0 + tq1) * H + c] = hi[1];
-                cl[(size_t)(t0 + tq1) * H + c] = lo[1];
+        }
+    }
+    if constexpr (PARK) {
+#pragma unroll
+        for (int t = 0; t < D / 16; ++t) {
+            const int id = lane + 64 * t, qrow = id / (D / 8), c8 = (id % (D / 8)) * 8;
+            const int tq = qb * 32 + qrow;
+            if (tq < L) {
+                const size_t at = (size_t)(t0 + tq) * H + hd * D + c8;
+                *reinterpret_cast<u32x4*>(ch + at) = *reinterpret_cast<const u32x4*>(ob + qrow * D + c8);
+                *reinterpret_cast<u32x4*>(cl + at) = *reinterpret_cast<const u32x4*>(ob + 32 * D + qrow * D + c8);
             }
         }
     }
@@ -1021,7 +740,7 @@ __global__ __launch_bounds__(H) void pool_norm_kernel(const float* __restrict__ 
 
 // ---------------------------------------------------------------- host side
 constexpr int HID = 384;     // all-MiniLM width: 32-dim heads, the fused layer kernels
-constexpr int HID_BASE = 768;  // BERT-base width: 64-dim heads, the unfused chain (f16x3) / attention64_kernel (f32)
+constexpr int HID_BASE = 768;  // BERT-base width: 64-dim heads, the unfused chain
 
 struct LayerW {
     float *Wqkv, *bqkv, *Wo, *bo, *g1, *b1n, *W1, *b1, *W2, *b2, *g2, *b2n;
@@ -1171,7 +890,8 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
 }
 
 // The attention length buckets, in launch order: 9-16 key tiles first (257-512 tokens: the longest bucket starts first),
-// then from the shortest up.  f16x3 batches take 5-8 key tiles in two buckets, single sequences and fp32 in one.
+// then from the shortest up.  f16x3 batches over 32-dim heads take 5-8 key tiles in two buckets; single sequences, fp32
+// and 64-dim heads in one.
 // Bucket k serves [ATT_LO[k], ATT_HI[k]] key tiles with the kernel <NKT = ATT_HI[k]> (NKT waves per workgroup).
 enum AttBucket { ATT_9_16, ATT_1, ATT_2, ATT_3_4, ATT_5_6, ATT_7_8, ATT_5_8, ATT_N };
 constexpr int ATT_LO[ATT_N] = {9, 1, 2, 3, 5, 7, 5}, ATT_HI[ATT_N] = {16, 1, 2, 4, 6, 8, 8};
@@ -1183,51 +903,31 @@ template <bool X3>
 static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBufs& b, const int32_t* cu, int n_seqs,
                              int max_seqlen, const int32_t* order, hipStream_t st) {
     const int nkt_max = (max_seqlen + 31) / 32;
-    const bool single = n_seqs == 1, split_5_8 = X3 && !single;
-    const float sl2e = (1.0f / sqrtf((float)DH)) * 1.44269504088896340736f;
+    const int dh = c.hidden / c.heads;  // 32 or 64 (icrec_encoder_create)
+    const bool single = n_seqs == 1, split_5_8 = X3 && !single && dh == 32;
+    const float sl2e = (1.0f / sqrtf((float)dh)) * 1.44269504088896340736f;
     for (int k = 0; k < ATT_N; ++k) {
         if (!(mask >> k & 1) || (split_5_8 ? k == ATT_5_8 : k == ATT_5_6 || k == ATT_7_8) || nkt_max < ATT_LO[k] ||
             (single && nkt_max > ATT_HI[k]))
             continue;
-        const dim3 grid(n_seqs * c.heads, 1), block(ATT_HI[k] * 64);
-        if constexpr (X3) {
-            static const decltype(&attention_x3_kernel<1>) kern[ATT_N] = {
-                attention_x3_kernel<16>, attention_x3_kernel<1>, attention_x3_kernel<2>, attention_x3_kernel<4>,
-                attention_x3_kernel<6>, attention_x3_kernel<8>, attention_x3_kernel<8>};
-            hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx, b.ch, b.cl, order,
+        const dim3 grid(n_seqs * c.heads), block(ATT_HI[k] * 64);
+        if constexpr (X3) {  // (only 32-dim heads split 5-8 key tiles)
+            static const decltype(&attention_x3_kernel<32, 1>) kern[2][ATT_N] = {
+                {attention_x3_kernel<32, 16>, attention_x3_kernel<32, 1>, attention_x3_kernel<32, 2>,
+                 attention_x3_kernel<32, 4>, attention_x3_kernel<32, 6>, attention_x3_kernel<32, 8>,
+                 attention_x3_kernel<32, 8>},
+                {attention_x3_kernel<64, 16>, attention_x3_kernel<64, 1>, attention_x3_kernel<64, 2>,
+                 attention_x3_kernel<64, 4>, nullptr, nullptr, attention_x3_kernel<64, 8>}};
+            hipLaunchKernelGGL(kern[dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ch, b.cl, order,
                                ATT_LO[k] - 1);
-        } else {  // (f16x3 batches only split 5-8 key tiles)
-            static const decltype(&attention_kernel<1>) kern[ATT_N] = {
-                attention_kernel<16>, attention_kernel<1>, attention_kernel<2>, attention_kernel<4>, nullptr, nullptr,
-                attention_kernel<8>};
-            hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx, b.ch, b.cl);
-        }
-    }
-}
-
-// The attention launches of a hidden-768 model (64-dim heads): buckets of 9-16 key tiles first, then 1, 2, 3-4, 5-8; for a
-// single sequence only the one that holds it.  X3: attention64_x3_kernel (context planes), else attention64_kernel.
-template <bool X3>
-static void launch_attention64(const icrec_bert_cfg& c, const EncBufs& b, const int32_t* cu, int n_seqs, int max_seqlen,
-                               const int32_t* order, hipStream_t st) {
-    constexpr int NB = 5;
-    constexpr int LO[NB] = {9, 1, 2, 3, 5}, HI[NB] = {16, 1, 2, 4, 8};
-    const int nkt_max = (max_seqlen + 31) / 32;
-    const bool single = n_seqs == 1;
-    const float sl2e = (1.0f / sqrtf((float)DH64)) * 1.44269504088896340736f;
-    for (int k = 0; k < NB; ++k) {
-        if (nkt_max < LO[k] || (single && nkt_max > HI[k])) continue;
-        const dim3 grid(n_seqs * c.heads, 1), block(HI[k] * 64);
-        if constexpr (X3) {
-            static const decltype(&attention64_x3_kernel<1>) kern[NB] = {
-                attention64_x3_kernel<16>, attention64_x3_kernel<1>, attention64_x3_kernel<2>, attention64_x3_kernel<4>,
-                attention64_x3_kernel<8>};
-            hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ch, b.cl, order);
         } else {
-            static const decltype(&attention64_kernel<1>) kern[NB] = {
-                attention64_kernel<16>, attention64_kernel<1>, attention64_kernel<2>, attention64_kernel<4>,
-                attention64_kernel<8>};
-            hipLaunchKernelGGL(kern[k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx);
+            static const decltype(&attention_kernel<32, 1>) kern[2][ATT_N] = {
+                {attention_kernel<32, 16>, attention_kernel<32, 1>, attention_kernel<32, 2>, attention_kernel<32, 4>,
+                 nullptr, nullptr, attention_kernel<32, 8>},
+                {attention_kernel<64, 16>, attention_kernel<64, 1>, attention_kernel<64, 2>, attention_kernel<64, 4>,
+                 nullptr, nullptr, attention_kernel<64, 8>}};
+            hipLaunchKernelGGL(kern[dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx,
+                               ATT_LO[k] - 1);
         }
     }
 }
@@ -1246,7 +946,7 @@ int icrec_encoder_create(const float* weights_host, size_t n_floats, const icrec
     // The kernels and their dispatch rely on these: every GEMM has K = hidden or K = intermediate, a multiple of 384, and
     // N = hidden, 3 x hidden or intermediate (launch_wt_linear's ring depths and tile splits, the fused FFN's 128-wide
     // chunks); the attention kernels exist for 32-dim heads at hidden 384 and 64-dim heads at hidden 768.
-    ICREC_REQUIRE((cfg->hidden == HID && cfg->heads * DH == HID) || (cfg->hidden == HID_BASE && cfg->heads * DH64 == HID_BASE),
+    ICREC_REQUIRE((cfg->hidden == HID && cfg->heads * 32 == HID) || (cfg->hidden == HID_BASE && cfg->heads * 64 == HID_BASE),
                   "icrec_encoder_create: (hidden, heads) must be (384, 12) or (768, 12): head_dim 32 at hidden 384, head_dim 64 "
                   "at hidden 768 (got hidden=%d, heads=%d)", cfg->hidden, cfg->heads);
     ICREC_REQUIRE(cfg->intermediate >= 384 && cfg->intermediate % 384 == 0, "icrec_encoder_create: intermediate size must be a multiple of 384 (got %d)", cfg->intermediate);
@@ -1507,8 +1207,6 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
             launch_attention<true>(side_buckets, c, b, cu_dev, n_seqs, max_seqlen, order, sd->side);
             launch_attention<true>(1u << ATT_5_6, c, b, cu_dev, n_seqs, max_seqlen, order, st);
             ICREC_HIP(link(sd, sd->side, st));
-        } else if (base) {
-            launch_attention64<true>(c, b, cu_dev, n_seqs, max_seqlen, order, st);
         } else {
             launch_attention<true>(~0u, c, b, cu_dev, n_seqs, max_seqlen, order, st);
         }
@@ -1529,10 +1227,7 @@ static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev,
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& L = e->layers[l];
         launch_linear<false>(b.x, T, H, L.Wqkv, 3 * H, L.bqkv, b.qkv, st);
-        if (base)
-            launch_attention64<false>(c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
-        else
-            launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
+        launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
         launch_linear<false>(b.ctx, T, H, L.Wo, H, L.bo, b.t1, st);
         hipLaunchKernelGGL(add_ln, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g1, L.b1n,
                            c.ln_eps, b.xh, b.xl);
