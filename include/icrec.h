@@ -137,6 +137,18 @@ ICREC_API int icrec_encode(icrec_encoder* enc,
                  float* out_dev,
                  void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* icrec_encode, and additionally the last hidden state of every token (what
+ * SentenceTransformer.encode(output_value="token_embeddings") returns) when tokens_out_dev != NULL:
+ *   tokens_out_dev float[total_tokens, hidden]  row t is token t of the packed batch; 16-byte aligned
+ * The rows are the very values mean pooling summed (in f16x3 mode the two f16 planes of the residual stream, widened
+ * exactly), written by one extra copy kernel on `stream` behind the pooling kernel.  With tokens_out_dev == NULL this
+ * IS icrec_encode: the same launches, the same bits.  Same workspace size either way. */
+ICREC_API int icrec_encode_ex(icrec_encoder* enc,
+                    const int32_t* ids_dev, const int32_t* cu_seqlens_dev,
+                    int32_t n_seqs, int64_t total_tokens, int32_t max_seqlen,
+                    float* out_dev, float* tokens_out_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* How icrec_encode will split `total_tokens` (f16x3 mode): main_tokens go through the batch kernels (whole
  * rounds of one 64-token workgroup per CU; at hidden 384 the fused FFN kernel sees exactly this many tokens), tail_tokens — a
  * remainder of at most 512 tokens — through the small-batch kernels.  Same arithmetic either way; bench.py uses

@@ -738,6 +738,25 @@ __global__ __launch_bounds__(H) void pool_norm_kernel(const float* __restrict__ 
     out[(size_t)s * H + i] = val;
 }
 
+// The last hidden state as fp32 rows (icrec_encode_ex's tokens_out): the very values pool_norm_kernel sums, read the
+// same way.  One thread per 4 features; n4 = total_tokens * hidden / 4.
+template <bool PLANES>
+__global__ __launch_bounds__(256) void tokens_out_kernel(const float* __restrict__ x, const _Float16* __restrict__ xh,
+                                                         const _Float16* __restrict__ xl, size_t n4,
+                                                         float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 v;
+    if (PLANES) {
+        const half4 hi = *reinterpret_cast<const half4*>(xh + 4 * i), lo = *reinterpret_cast<const half4*>(xl + 4 * i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = ((float)hi[j] + (float)lo[j]) * (1.0f / WT_SA);
+    } else {
+        v = *reinterpret_cast<const f32x4*>(x + 4 * i);
+    }
+    *reinterpret_cast<f32x4*>(out + 4 * i) = v;
+}
+
 // ---------------------------------------------------------------- host side
 constexpr int HID = 384;     // all-MiniLM width: 32-dim heads, the fused layer kernels
 constexpr int HID_BASE = 768;  // BERT-base width: 64-dim heads, the unfused chain
@@ -1244,8 +1263,15 @@ static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev,
 
 int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev, int32_t n_seqs, int64_t T64,
                  int32_t max_seqlen, float* out_dev, void* ws, size_t ws_bytes, void* stream) {
+    return icrec_encode_ex(h, ids_dev, cu_dev, n_seqs, T64, max_seqlen, out_dev, nullptr, ws, ws_bytes, stream);
+}
+
+int icrec_encode_ex(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev, int32_t n_seqs, int64_t T64,
+                    int32_t max_seqlen, float* out_dev, float* tokens_out_dev, void* ws, size_t ws_bytes,
+                    void* stream) {
     Encoder* e = reinterpret_cast<Encoder*>(h);
     ICREC_REQUIRE(e && ids_dev && cu_dev && out_dev, "icrec_encode: NULL argument");
+    ICREC_REQUIRE((reinterpret_cast<uintptr_t>(tokens_out_dev) & 15) == 0, "icrec_encode_ex: tokens_out_dev must be 16-byte aligned");
     ICREC_REQUIRE(n_seqs >= 1 && T64 >= n_seqs && T64 < (1ll << 31), "icrec_encode: bad n_seqs/total_tokens (%d, %lld)", n_seqs, (long long)T64);
     ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= e->max_seqlen, "icrec_encode: max_seqlen must be in [1, %d] (got %d)", e->max_seqlen, max_seqlen);
     const int T = (int)T64;
@@ -1280,6 +1306,11 @@ int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev
     const auto pool = H == HID_BASE ? (x3 ? pool_norm_kernel<HID_BASE, true> : pool_norm_kernel<HID_BASE, false>)
                                     : (x3 ? pool_norm_kernel<HID, true> : pool_norm_kernel<HID, false>);
     hipLaunchKernelGGL(pool, dim3(n_seqs), dim3(H), 0, st, b.x, b.xh, b.xl, cu_dev, c.n_normalize, out_dev);
+    if (tokens_out_dev) {  // hidden is a multiple of 4: every thread's 4 features are 16 (planes: 8) bytes, aligned
+        const size_t n4 = (size_t)T * H / 4;
+        hipLaunchKernelGGL(x3 ? tokens_out_kernel<true> : tokens_out_kernel<false>, dim3((unsigned)((n4 + 255) / 256)),
+                           dim3(256), 0, st, b.x, b.xh, b.xl, n4, tokens_out_dev);
+    }
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
 }

@@ -93,18 +93,28 @@ class DeviceEncoder:
             pass
 
     def encode_into(self, ids: torch.Tensor, cu: torch.Tensor, n: int, T: int, max_seqlen: int, out: torch.Tensor,
-                    ws: Optional[torch.Tensor] = None) -> None:
+                    ws: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None) -> None:
         """One icrec_encode on the current stream: device int32 ids[T] and cu_seqlens[n+1] -> out float32 [n, hidden].
-        `ws`: a workspace the caller owns (a captured graph bakes its address); by default this stream's block."""
+        `ws`: a workspace the caller owns (a captured graph bakes its address); by default this stream's block.
+        `tokens`: float32 [T, hidden] that also receives every token's last hidden state (icrec_encode_ex)."""
         L = _native.lib()
         if ws is None:
             ws = self._ws_by_stream.block(int(L.icrec_encode_workspace_bytes(self._h, T, n)))
-        _native.check(L.icrec_encode(self._h, ptr(ids), ptr(cu), n, T, int(max_seqlen), ptr(out), ptr(ws), ws.numel(),
-                                     stream_ptr(self.device)), "icrec_encode")
+        if tokens is None:
+            _native.check(L.icrec_encode(self._h, ptr(ids), ptr(cu), n, T, int(max_seqlen), ptr(out), ptr(ws),
+                                         ws.numel(), stream_ptr(self.device)), "icrec_encode")
+        else:
+            _native.check(L.icrec_encode_ex(self._h, ptr(ids), ptr(cu), n, T, int(max_seqlen), ptr(out), ptr(tokens),
+                                            ptr(ws), ws.numel(), stream_ptr(self.device)), "icrec_encode_ex")
 
     def encode_packed(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int,
-                      out: Optional[torch.Tensor] = None, cu_host: Optional[np.ndarray] = None) -> torch.Tensor:
+                      out: Optional[torch.Tensor] = None, cu_host: Optional[np.ndarray] = None,
+                      return_tokens: bool = False, tokens_out: Optional[torch.Tensor] = None):
         """Device tensors in (int32 ids[T], int32 cu_seqlens[n+1]) -> float32 [n, hidden] on the device.
+
+        With `return_tokens` the result is `(emb, tokens)`: tokens float32 [T, hidden] is the last hidden state of
+        every token (SentenceTransformer.encode(output_value="token_embeddings")), the very rows the pooling summed;
+        `tokens_out` is a contiguous float32 [T, hidden] device tensor to receive them (allocated when None).
 
         With `cu_host` (the host copy of cu_seqlens) and a large batch, the two halves of the batch run
         concurrently on two HIP streams (own workspaces, fork/join by events): one half's bandwidth-bound
@@ -117,9 +127,17 @@ class DeviceEncoder:
         n, T = int(cu.numel()) - 1, int(ids.numel())
         if out is None:
             out = torch.empty((n, self.shape.hidden), dtype=torch.float32, device=self.device)
+        tok = None
+        if return_tokens:
+            tok = tokens_out
+            if tok is None:
+                tok = torch.empty((T, self.shape.hidden), dtype=torch.float32, device=self.device)
+            elif (tok.dtype != torch.float32 or tuple(tok.shape) != (T, self.shape.hidden) or not tok.is_contiguous()
+                  or tok.device != self.device):
+                raise TypeError(f"tokens_out must be a contiguous float32 [{T}, {self.shape.hidden}] tensor on {self.device}")
         if cu_host is None or n < 2 * self.SPLIT_MIN_SEQS or T < 2 * self.SPLIT_MIN_TOKENS:
-            self.encode_into(ids, cu, n, T, max_seqlen, out)
-            return out
+            self.encode_into(ids, cu, n, T, max_seqlen, out, tokens=tok)
+            return (out, tok) if return_tokens else out
         half = n // 2
         t_half = int(cu_host[half])
         # the second half's rebased cu_seqlens, computed per call on the caller's stream (one tiny kernel).  Never
@@ -131,10 +149,12 @@ class DeviceEncoder:
             self._side = torch.cuda.Stream(self.device)
         self._side.wait_stream(main)
         with torch.cuda.stream(self._side):
-            self.encode_into(ids[t_half:], cu_b, n - half, T - t_half, max_seqlen, out[half:])
-        self.encode_into(ids[:t_half], cu[: half + 1], half, t_half, max_seqlen, out[:half])
+            self.encode_into(ids[t_half:], cu_b, n - half, T - t_half, max_seqlen, out[half:],
+                             tokens=None if tok is None else tok[t_half:])
+        self.encode_into(ids[:t_half], cu[: half + 1], half, t_half, max_seqlen, out[:half],
+                         tokens=None if tok is None else tok[:t_half])
         main.wait_stream(self._side)
-        return out
+        return (out, tok) if return_tokens else out
 
     def encode_packed_host(self, ids: np.ndarray, cu: np.ndarray, max_tokens_per_call: int = 1 << 18) -> torch.Tensor:
         """Host arrays in the packed form (ids int32[T], cu_seqlens int32[n+1], e.g. HostTokenizer.packed) ->

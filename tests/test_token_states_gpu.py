@@ -1,0 +1,252 @@
+"""Per-token hidden states of the HIP encoder (DeviceEncoder.encode_packed(return_tokens=True), icrec_encode_ex) against
+the float64 reference (oracle/float64_reference.py), at every width, weight set, f16x3 dispatch form and attention
+bucket edge.
+
+The bound is `margin x E_ref` (tests/token_states.py): E_ref is the fp32 C oracle's error against the same float64
+hidden states on the same inputs - per-token-row rms, with a max-abs check beside it - and the margins are the ones
+chosen in profiles/token_state_errors.md.  Every comparison prints `ratio rms / abs` = E_gpu / E_ref before it
+asserts; on failure the worst (sequence, position, feature, got, want) is named."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import token_states as ts
+
+pytestmark = pytest.mark.gpu
+
+MODES = ("f32", "f16x3")
+# every attention bucket edge (key tiles of 32; buckets of 1 / 2 / 3-4 / 5-6 / 7-8 / 9-16 tiles)
+EDGE_LENS = [1, 2, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129, 159, 160, 161, 191, 192, 193, 223, 224, 225,
+             255, 256, 257, 383, 384, 385, 511, 512]
+MIXED_LENS = [5, 33, 128, 256, 1, 2, 64, 97]
+
+_refs: dict = {}
+
+
+def _reference(kind, hidden, layers, lens, seed):
+    """Weights, inputs, the float64 hidden states and the oracle's hidden states: computed once per batch,
+    shared by the modes and forms that run it."""
+    key = (kind, hidden, layers, tuple(lens), seed)
+    if key not in _refs:
+        from oracle import float64_reference as f64
+        from oracle import oracle
+
+        s = ts.shape(hidden, layers)
+        w = ts.weights(kind, s)
+        ids, cu = ts.packed(lens, seed)
+        want_h, _ = f64.encode(w, s, ids, cu)
+        _, ora_h = oracle.encode(w, ts.oracle_cfg(s), ids, cu, return_hidden=True)
+        _refs[key] = dict(s=s, w=w, ids=ids, cu=cu, want_h=want_h, ora_h=ora_h, kind=kind)
+    return _refs[key]
+
+
+def _make(monkeypatch, r, mode, max_seq_length=None, **env):
+    """An encoder created under the given ICREC_* settings (they are read once, at creation)."""
+    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
+
+    for k, v in env.items():
+        monkeypatch.setenv(k, str(v))
+    try:
+        return DeviceEncoder(r["w"], r["s"], gemm_mode=mode, max_seq_length=max_seq_length)
+    finally:
+        for k in env:
+            monkeypatch.delenv(k)
+
+
+def _run(enc, ids, cu, **kw):
+    import torch
+
+    emb, tok = enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max()),
+                                 return_tokens=True, **kw)
+    return emb.cpu().numpy(), tok.cpu().numpy()
+
+
+def _check(what, mode, r, emb, tok, first_seq=0, n_seqs=None):
+    """tok (sequences [first_seq, first_seq + n_seqs) of r's batch; all by default) against the float64 hidden states
+    within margin x E_ref, and tok mean-pooled in float64 against emb."""
+    s, kind = r["s"], r["kind"]
+    n_seqs = r["cu"].size - 1 - first_seq if n_seqs is None else n_seqs
+    cu = r["cu"][first_seq: first_seq + n_seqs + 1].astype(np.int64)
+    rows = slice(int(cu[0]), int(cu[-1]))
+    want, ora = r["want_h"][rows], r["ora_h"][rows]
+    cu = cu - cu[0]
+    assert tok.shape == want.shape and tok.dtype == np.float32 and np.isfinite(tok).all()
+    e_rms, e_abs = ts.row_errors(ora, want)
+    g_rms, g_abs = ts.row_errors(tok, want)
+    m_rms, m_abs = ts.MARGINS[(mode, s.hidden, kind)]
+    print(f"token states [{what}] mode={mode} hidden={s.hidden} layers={s.layers} weights={kind} tokens={tok.shape[0]}: "
+          f"E_gpu rms {g_rms:.3e} abs {g_abs:.3e}, E_ref rms {e_rms:.3e} abs {e_abs:.3e}, "
+          f"ratio rms {g_rms / e_rms:.2f} abs {g_abs / e_abs:.2f} (margins {m_rms} / {m_abs})")
+    assert g_rms <= m_rms * e_rms and g_abs <= m_abs * e_abs, \
+        f"{what} mode={mode} weights={kind}: " + ts.worst_element(tok, want, cu)
+    # The embedding of the same call is the mean of these rows, normalised.  fp32 pooling sums n rows one after the
+    # other: |error of the mean| <= n u mean|h| (u = 2^-24); the two normalisations (fmaf chain of H / 64, a 6-step
+    # butterfly, sqrt, divide) cost at most 32 more roundings of a component that is <= 1.
+    t64 = tok.astype(np.float64)
+    u = 2.0 ** -24
+    for i in range(cu.size - 1):
+        rows_i = t64[cu[i]:cu[i + 1]]
+        pooled = rows_i.mean(0)
+        norm = np.linalg.norm(pooled)
+        v = pooled
+        for _ in range(s.n_normalize):
+            v = v / max(np.linalg.norm(v), 1e-12)
+        tol = rows_i.shape[0] * u * np.abs(rows_i).mean(0) / norm + 32 * u
+        assert (np.abs(emb[i] - v) <= tol).all(), (what, mode, i, float(np.abs(emb[i] - v).max()), float(tol.min()))
+
+
+@pytest.mark.parametrize("kind", ts.KINDS)
+@pytest.mark.parametrize("hidden,layers", [(384, 6), (384, 1), (768, 2)])
+@pytest.mark.parametrize("mode", MODES)
+def test_small_batch_every_width(monkeypatch, mode, hidden, layers, kind):
+    """~590 tokens in 8 sequences: the small / latency forms.  6 layers and 1 layer at hidden 384 (layer 0's stand-alone
+    QKV, the next-layer QKV prologue / epilogue and the last layer without one are different code), 2 layers at 768.
+    f16x3 also under ICREC_FUSE=0 (separate LayerNorm launches)."""
+    r = _reference(kind, hidden, layers, MIXED_LENS, seed=2)
+    for env in ({}, {"ICREC_FUSE": 0}) if mode == "f16x3" else ({},):
+        enc = _make(monkeypatch, r, mode, **env)
+        emb, tok = _run(enc, r["ids"], r["cu"])
+        _check(f"small {env}", mode, r, emb, tok)
+        enc.close()
+
+
+def _split(enc, tokens):
+    from instacart_next_order_recommendation_amd import _native
+
+    m, t = C.c_int64(0), C.c_int64(0)
+    _native.check(_native.lib().icrec_encode_batch_split(enc._h, int(tokens), C.byref(m), C.byref(t)),
+                  "icrec_encode_batch_split")
+    return int(m.value), int(t.value)
+
+
+def _batch_lens(n, seed):
+    from instacart_next_order_recommendation_amd import synthetic as syn
+
+    _, cu = syn.synthetic_token_batch(n, seed=seed, mean_len=90, std_len=60, lo=3, hi=256, vocab_size=ts.VOCAB)
+    return np.diff(cu).tolist()
+
+
+@pytest.mark.parametrize("kind", ts.KINDS)
+@pytest.mark.parametrize("hidden", [384, 768])
+def test_batch_forms(monkeypatch, hidden, kind):
+    """60 sequences, > 3,584 tokens, 2 layers.  Hidden 384: the layer kernels (f16x3 default), the unfused slab-ring
+    chain (ICREC_FUSE=0) and f32.  Hidden 768: the slab-ring form (default above 3,584 tokens, and forced on the same
+    batch's first 1,500 tokens with ICREC_SMALL_M=512), the latency form of those 1,500 tokens, and f32."""
+    lens = _batch_lens(60, seed=33)
+    r = _reference(kind, hidden, 2, lens, seed=3)
+    assert r["cu"][-1] > 3584 + 512
+    for mode, env in (("f32", {}), ("f16x3", {}), ("f16x3", {"ICREC_FUSE": 0})):
+        enc = _make(monkeypatch, r, mode, **env)
+        emb, tok = _run(enc, r["ids"], r["cu"])
+        _check(f"batch {env}", mode, r, emb, tok)
+        enc.close()
+    if hidden == 768:
+        n = int(np.searchsorted(r["cu"], 1500, side="right")) - 1
+        t = int(r["cu"][n])
+        assert 1000 < t <= 1500
+        for env in ({}, {"ICREC_SMALL_M": 512}):
+            enc = _make(monkeypatch, r, "f16x3", **env)
+            emb, tok = _run(enc, r["ids"][:t].copy(), r["cu"][: n + 1].copy())
+            _check(f"first {t} tokens {env}", "f16x3", r, emb, tok, 0, n)
+            enc.close()
+
+
+@pytest.mark.parametrize("kind", ts.KINDS)
+@pytest.mark.parametrize("hidden", [384, 768])
+def test_rounds_plus_remainder(monkeypatch, hidden, kind):
+    """f16x3, 2 layers: a token count that icrec_encode_batch_split cuts into whole rounds (64 tokens per CU) + a
+    remainder, which runs through the small-batch kernels on the library's side stream."""
+    lens = _batch_lens(400, seed=11)
+    cu_all = np.concatenate([[0], np.cumsum(lens)])
+    probe = _make(monkeypatch, _reference(kind, hidden, 2, [4], seed=0), "f16x3")
+    main_t = tail_t = n = 0
+    for n in range(64, 400):  # the first cut whose token count splits into whole rounds + a remainder
+        main_t, tail_t = _split(probe, int(cu_all[n]))
+        if tail_t:
+            break
+    probe.close()
+    assert tail_t and main_t > 0 and n >= 64, (main_t, tail_t, n)
+    r = _reference(kind, hidden, 2, lens[:n], seed=4)
+    enc = _make(monkeypatch, r, "f16x3")
+    assert _split(enc, int(r["cu"][-1])) == (main_t, tail_t)
+    emb, tok = _run(enc, r["ids"], r["cu"])
+    _check(f"rounds {main_t} + remainder {tail_t}", "f16x3", r, emb, tok)
+    enc.close()
+
+
+@pytest.mark.parametrize("kind", ts.KINDS)
+@pytest.mark.parametrize("hidden,layers", [(384, 6), (768, 2)])
+@pytest.mark.parametrize("mode", MODES)
+def test_attention_bucket_edges(monkeypatch, mode, hidden, layers, kind):
+    """Ceiling raised to 512: a sequence on each side of every key-tile bucket edge, all in one batch, then each alone
+    (a lone sequence may take another bucket's kernel than the same sequence in a batch)."""
+    r = _reference(kind, hidden, layers, EDGE_LENS, seed=5)
+    enc = _make(monkeypatch, r, mode, max_seq_length=512)
+    emb, tok = _run(enc, r["ids"], r["cu"])
+    _check("edges mixed", mode, r, emb, tok)
+    cu = r["cu"]
+    for i, n in enumerate(EDGE_LENS):
+        a, b = int(cu[i]), int(cu[i + 1])
+        e1, t1 = _run(enc, r["ids"][a:b].copy(), np.array([0, n], np.int32))
+        _check(f"length {n} alone", mode, r, e1, t1, i, 1)
+    enc.close()
+
+
+@pytest.mark.parametrize("hidden,layers", [(384, 6), (768, 2)])
+@pytest.mark.parametrize("mode", MODES)
+def test_token_output_changes_nothing_and_reads_nothing_stale(monkeypatch, mode, hidden, layers):
+    """The embeddings of a call that also returns tokens are those of plain encode_packed bit for bit; a workspace and a
+    tokens_out buffer full of 0xFF give the same token bits as zeroed ones."""
+    import torch
+
+    r = _reference("sharp", hidden, layers, MIXED_LENS, seed=2)
+    enc = _make(monkeypatch, r, mode)
+    ids, cu = torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda()
+    mx = int(np.diff(r["cu"]).max())
+    plain = enc.encode_packed(ids, cu, mx).cpu().numpy()
+    ws = enc._ws_by_stream[torch.cuda.current_stream().cuda_stream]
+    buf = torch.empty((int(r["cu"][-1]), hidden), dtype=torch.float32, device="cuda")
+    got = []
+    for fill in (0xFF, 0x00):
+        ws.fill_(fill)
+        buf.view(torch.uint8).fill_(fill)
+        emb, tok = enc.encode_packed(ids, cu, mx, return_tokens=True, tokens_out=buf)
+        assert tok.data_ptr() == buf.data_ptr()
+        got.append((emb.cpu().numpy(), tok.cpu().numpy()))
+        assert np.isfinite(got[-1][1]).all(), f"byte 0x{fill:02X} leaked into the token states"
+        np.testing.assert_array_equal(got[-1][0], plain)
+    np.testing.assert_array_equal(got[0][1], got[1][1])
+    np.testing.assert_array_equal(enc.encode_packed(ids, cu, mx).cpu().numpy(), plain)
+    enc.close()
+
+
+def test_token_output_under_graph_capture(monkeypatch):
+    """icrec_encode_ex is capturable like icrec_encode: a replayed graph writes the same token bits as the eager call."""
+    import torch
+
+    r = _reference("sharp", 384, 6, MIXED_LENS, seed=2)
+    enc = _make(monkeypatch, r, "f16x3")
+    ids, cu = torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda()
+    n, T, mx = r["cu"].size - 1, int(r["cu"][-1]), int(np.diff(r["cu"]).max())
+    emb, tok = enc.encode_packed(ids, cu, mx, return_tokens=True)
+    out = torch.zeros((n, 384), dtype=torch.float32, device="cuda")
+    buf = torch.zeros((T, 384), dtype=torch.float32, device="cuda")
+    ws = torch.empty(enc._ws_by_stream[torch.cuda.current_stream().cuda_stream].numel(), dtype=torch.uint8, device="cuda")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # warm-up outside the capture, as fastpath.py does
+        enc.encode_into(ids, cu, n, T, mx, out, ws, tokens=buf)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        enc.encode_into(ids, cu, n, T, mx, out, ws, tokens=buf)
+    buf.zero_(); out.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(buf.cpu().numpy(), tok.cpu().numpy())
+    np.testing.assert_array_equal(out.cpu().numpy(), emb.cpu().numpy())
+    enc.close()
