@@ -6,6 +6,8 @@ requests are coalesced: everything queued while the previous GPU pass was runnin
 server has seen concurrency, arrivals within `max_wait_ms`, up to `max_batch`) goes into ONE
 recommend_batch() GPU pass in a worker thread and every caller gets its own slice.  Results are identical to per-request recommend() calls
 because packed varlen encoding and per-query top-k are batch-invariant.
+
+The HTTP routes and the worker socket serve from a Backend: LocalBackend (here) or RemoteBackend (remote.py).
 """
 from __future__ import annotations
 
@@ -13,7 +15,10 @@ import asyncio
 import time
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
+from pathlib import Path
 from typing import Optional
+
+from ..recommender import MonitoredRecommender
 
 
 @dataclass
@@ -148,3 +153,61 @@ class MicroBatcher:
                 for p in batch:
                     if not p.future.done():
                         p.future.set_exception(exc)
+
+
+class Backend:
+    """What serves /recommend and /admin/corpus in this process.  Besides the attributes below:
+    `await submit(query, top_k, exclude, user_id)` -> (results, BatchTimings - None when no batch was formed),
+    `await reindex(corpus_path)` -> number of products of the catalog now served, `await stop()`."""
+
+    recommender = None  # the recommender in this process, if it has one
+    stats = False       # responses carry `stats` (a MonitoredRecommender computes them)
+    connected = True    # /ready
+    corpus_path: Path
+    pid_to_text: dict
+
+    async def start(self) -> None:
+        pass
+
+
+class LocalBackend(Backend):
+    """A recommender built by `factory(corpus_path)` and the MicroBatcher in front of it."""
+
+    def __init__(self, factory, corpus_path, max_batch: int, max_wait_ms: float):
+        self._factory, self._max_batch, self._max_wait_ms = factory, max_batch, max_wait_ms
+        self._adopt(factory(Path(corpus_path)), corpus_path)
+
+    def _adopt(self, rec, corpus_path) -> None:
+        """Plain attribute stores, no await: a request sees either the old recommender + batcher or the new."""
+        self._monitored = isinstance(rec, MonitoredRecommender)
+        # a duck-typed recommender (the reference's tests patch in a MagicMock) is called directly, per request
+        self._direct = type(rec).__module__.startswith("unittest.mock") or not (
+            hasattr(rec, "recommend_batch_timed") or hasattr(rec, "recommend_batch"))
+        self.batcher = MicroBatcher(rec, self._max_batch, self._max_wait_ms)
+        self.recommender, self.corpus_path, self.stats = rec, Path(corpus_path), self._monitored and not self._direct
+
+    @property
+    def pid_to_text(self):
+        return self.recommender.pid_to_text
+
+    async def stop(self) -> None:
+        await self.batcher.stop()
+
+    async def submit(self, query, top_k, exclude, user_id=None):
+        if self._direct:
+            kw = {"user_id": user_id} if self._monitored else {}
+            return self.recommender.recommend(query=query, top_k=top_k, exclude_product_ids=exclude, **kw), None
+        try:
+            return await self.batcher.submit(query, top_k, exclude, user_id)
+        except BatcherStopped:  # raced a reindex: self.batcher is the new one by now
+            return await self.batcher.submit(query, top_k, exclude, user_id)
+
+    async def reindex(self, corpus_path) -> int:
+        """The new recommender (a full GPU re-encode) is built in a worker thread while the old one keeps serving (the
+        reference builds it inline and stalls its event loop, routes/corpus.py:87-98); then one swap, and the old
+        batcher stops gracefully: what it has queued (and the batch on the GPU) is still answered."""
+        rec = await asyncio.get_running_loop().run_in_executor(None, self._factory, Path(corpus_path))
+        old = self.batcher
+        self._adopt(rec, corpus_path)
+        await old.stop()
+        return len(rec.product_ids)

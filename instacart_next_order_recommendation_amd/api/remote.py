@@ -1,5 +1,6 @@
-"""Front-end side of the multi-process server: what `app.state.recommender` / `app.state.batcher` are in a
-process that does not own the GPU (ICREC_GPU_WORKER_SOCKET set).  See worker.py for the protocol."""
+"""Front-end side of the multi-process server: RemoteBackend is what the app serves from in a process that does not
+own the GPU (ICREC_GPU_WORKER_SOCKET set) - the corpus texts plus a RemoteBatcher per worker socket.  See worker.py
+for the protocol."""
 from __future__ import annotations
 
 import asyncio
@@ -8,27 +9,8 @@ import json
 from pathlib import Path
 from typing import Optional
 
-from .batcher import BatchTimings
+from .batcher import Backend, BatchTimings
 from .worker import frame, read_frame
-
-
-class CorpusView:
-    """The attributes the routes read from a recommender (pid_to_text, corpus_path, product_ids) loaded from the
-    corpus JSON alone — no model, no GPU (reference: Recommender._load_corpus, serve_recommendations.py:158-164)."""
-
-    reports_stats = True   # the worker runs a MonitoredRecommender: responses carry `stats`
-    remote = True
-
-    def __init__(self, corpus_path):
-        self.corpus_path = Path(corpus_path).resolve()
-        with open(self.corpus_path) as f:
-            corpus = json.load(f)
-        self.product_ids = list(corpus.keys())
-        self.pid_to_text = corpus
-        self.model_dir = None
-
-    def recommend_batch(self, *a, **k):  # pragma: no cover - marks the object as batch-capable for the route
-        raise RuntimeError("front-end processes forward to the GPU worker")
 
 
 class WorkerUnavailable(RuntimeError):
@@ -185,3 +167,32 @@ class MultiRemoteBatcher:
         for w in self._workers:
             out = await w.reindex(corpus_path)
         return out
+
+
+class RemoteBackend(Backend):
+    """The corpus texts, loaded from the corpus JSON alone - no model, no GPU (reference: Recommender._load_corpus,
+    serve_recommendations.py:158-164) - and the socket(s) to the GPU-owner process(es), which answer everything else."""
+
+    stats = True  # the workers run a MonitoredRecommender
+
+    def __init__(self, sock_paths, corpus_path):
+        self._load_texts(corpus_path)
+        # the worker re-indexed (this or another front-end's /admin/corpus): its broadcast reloads the texts here
+        self.batcher = (RemoteBatcher(sock_paths[0], self._load_texts) if len(sock_paths) == 1
+                        else MultiRemoteBatcher(sock_paths, self._load_texts))
+        # the batcher's own bound methods, no wrapper frame per request; start() connects: /ready is right from then on
+        self.start, self.stop, self.submit = self.batcher.start, self.batcher.stop, self.batcher.submit
+
+    def _load_texts(self, corpus_path) -> None:
+        with open(corpus_path) as f:
+            self.pid_to_text = json.load(f)
+        self.corpus_path = Path(corpus_path)
+
+    @property
+    def connected(self) -> bool:
+        return self.batcher.connected
+
+    async def reindex(self, corpus_path) -> int:
+        """Every worker re-encodes (in a thread of its own, still serving the old catalog) and swaps; the "corpus" frame
+        that answers this call reloads the texts here like any other front-end's broadcast."""
+        return (await self.batcher.reindex(str(corpus_path)))[1]

@@ -14,18 +14,15 @@ import os
 import signal
 import tempfile
 
+from . import DEFAULT_CORPUS_PATH, DEFAULT_MODEL_DIR
+
 
 def _frontend(sock_path: str, host: str, port: int, ready) -> None:
     os.environ["ICREC_GPU_WORKER_SOCKET"] = sock_path
     from .app import app
     from .fastserve import serve
-    from .worker import _settle_heap
 
-    def on_ready():
-        _settle_heap()  # the corpus texts are loaded by now (lifespan): keep them out of later full collections
-        ready.set()
-
-    asyncio.run(serve(app, host, port, reuse_port=True, ready=on_ready))
+    asyncio.run(serve(app, host, port, reuse_port=True, ready=ready.set))  # the app's lifespan settles the heap
 
 
 def _worker(sock_path: str, model_dir: str, corpus_path: str, ready) -> None:
@@ -73,8 +70,8 @@ def main() -> None:
     ap.add_argument("--host", default="0.0.0.0")
     ap.add_argument("--port", type=int, default=8000)
     args = ap.parse_args()
-    model_dir = os.getenv("MODEL_DIR", "models/two_tower_sbert/final")
-    corpus_path = os.getenv("CORPUS_PATH", "processed/p5_mp20_ef0.1/eval_corpus.json")
+    model_dir = os.getenv("MODEL_DIR", DEFAULT_MODEL_DIR)
+    corpus_path = os.getenv("CORPUS_PATH", DEFAULT_CORPUS_PATH)
     procs, _ = start(args.workers, args.host, args.port, model_dir, corpus_path, args.gpu_workers)
     print(f"serving on {args.host}:{args.port} with {args.workers} front-ends + {args.gpu_workers} GPU worker(s)", flush=True)
     signal.signal(signal.SIGTERM, lambda *_: (_ for _ in ()).throw(KeyboardInterrupt()))

@@ -1,6 +1,7 @@
 """The GPU-owner process of the multi-process server (serve.py).
 
-One process holds the MonitoredRecommender (model + catalog index in HBM) and runs the MicroBatcher; N
+One process holds a LocalBackend (the MonitoredRecommender - model + catalog index in HBM - and its MicroBatcher,
+the same object the single-process app serves from) and answers its submit / reindex over a socket; N
 front-end processes (FastAPI app, one event loop each) parse / validate / serialise HTTP and forward
 (query, top_k, exclusions) over a Unix socket.  Frames: 4-byte little-endian length + msgpack.
 
@@ -20,11 +21,10 @@ import asyncio
 import logging
 import os
 import struct
-from pathlib import Path
 
 import msgpack
 
-from .batcher import BatcherStopped
+from .batcher import LocalBackend
 
 logger = logging.getLogger(__name__)
 
@@ -42,54 +42,37 @@ def frame(obj) -> bytes:
 class GpuWorker:
     def __init__(self, model_dir, corpus_path, factory=None):
         """factory(corpus_path) -> recommender; default: MonitoredRecommender on this process's GPU."""
-        from .batcher import MicroBatcher
-
         if factory is None:
             from ..recommender import MonitoredRecommender
 
             def factory(cp):
                 return MonitoredRecommender(model_dir=model_dir, corpus_path=cp)
-        self._mk = factory
-        self._Batcher = MicroBatcher
-        self.model_dir, self.corpus_path = model_dir, Path(corpus_path)
-        self.recommender = self._mk(self.corpus_path)
-        self.batcher = self._new_batcher(self.recommender)
+        self.backend = LocalBackend(factory, corpus_path, max_batch=int(os.getenv("BATCH_MAX_SIZE", "1024")),
+                                    max_wait_ms=float(os.getenv("BATCH_MAX_WAIT_MS", "2")))
         self.writers: set[asyncio.StreamWriter] = set()
 
-    def _new_batcher(self, rec):
-        return self._Batcher(rec, max_batch=int(os.getenv("BATCH_MAX_SIZE", "1024")),
-                             max_wait_ms=float(os.getenv("BATCH_MAX_WAIT_MS", "2")))
+    batcher = property(lambda self: self.backend.batcher)
+    recommender = property(lambda self: self.backend.recommender)
 
     async def _one(self, writer, msg):
         kind, rid = msg[0], msg[1]
         try:
             if kind == "rec":
-                for attempt in (0, 1):
-                    try:
-                        results, tm = await self.batcher.submit(msg[2], int(msg[3]), set(msg[4]) if msg[4] else None,
-                                                                msg[5] if len(msg) > 5 else None)
-                        break
-                    except BatcherStopped:  # raced a corpus swap: self.batcher is the new one by now
-                        if attempt:
-                            raise
+                results, tm = await self.backend.submit(msg[2], int(msg[3]), set(msg[4]) if msg[4] else None,
+                                                        msg[5] if len(msg) > 5 else None)
                 writer.write(frame(["ok", rid, results, tm.encode_ms, tm.search_ms, tm.batch_size]))
             elif kind == "corpus":
-                # build the NEW recommender off the event loop (a full GPU re-encode), keep serving the old one
-                # meanwhile, then swap batcher + recommender in one step and tell every front-end; the old batcher
-                # stops gracefully: what it has queued (and the batch on the GPU) is still answered
-                new_rec = await asyncio.get_running_loop().run_in_executor(None, self._mk, Path(msg[2]))
-                old = self.batcher
-                self.recommender, self.batcher, self.corpus_path = new_rec, self._new_batcher(new_rec), Path(msg[2])
-                await old.stop()
-                note = frame(["corpus", None, str(self.corpus_path), len(new_rec.product_ids)])
+                n = await self.backend.reindex(msg[2])  # keeps serving the old catalog meanwhile; then tell every front-end
+                path = str(self.backend.corpus_path)
+                note = frame(["corpus", None, path, n])
                 for w in list(self.writers):
                     if w is not writer:
                         w.write(note)
-                writer.write(frame(["corpus", rid, str(self.corpus_path), len(new_rec.product_ids)]))
+                writer.write(frame(["corpus", rid, path, n]))
             else:
                 writer.write(frame(["err", rid, f"unknown message {kind!r}"]))
         except Exception as exc:  # noqa: BLE001 - the caller must see the failure
-            writer.write(frame(["err", rid, f"{type(exc).__name__}: {exc}"]))
+            writer.write(frame(["err", rid, f"{exc.__class__.__name__}: {exc}"]))
 
     async def handle(self, reader: asyncio.StreamReader, writer: asyncio.StreamWriter):
         self.writers.add(writer)
@@ -104,7 +87,7 @@ class GpuWorker:
             writer.close()
 
 
-def _settle_heap() -> None:
+def settle_heap() -> None:
     """The catalog (two 49,688-entry containers of strings), the tokenizer vocabulary and the imported modules are
     millions of objects that live as long as the process: a full collection walks all of them - tens of milliseconds
     in which this single-threaded process answers nobody, every few seconds at >10 k requests per second (each leaves a
@@ -127,7 +110,7 @@ def run(sock_path: str, model_dir, corpus_path, ready=None) -> None:
 
     async def main():
         w = GpuWorker(model_dir, corpus_path)
-        _settle_heap()
+        settle_heap()
         server = await asyncio.start_unix_server(w.handle, path=sock_path, limit=1 << 26)
         logger.info("GPU worker ready on %s (%d products)", sock_path, len(w.recommender.product_ids))
         if ready is not None:

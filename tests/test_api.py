@@ -82,7 +82,7 @@ def test_recommend_forwards_exclusions_and_query(client, mock_recommender):
 
 def test_user_id_resolves_through_eval_queries(client, mock_recommender, tmp_path):
     (tmp_path / "eval_queries.json").write_text('{"42": "[+3d w1h9] Banana, Greek Yogurt."}')
-    client.app.state.corpus_path = tmp_path / "eval_corpus.json"
+    client.app.state.backend.corpus_path = tmp_path / "eval_corpus.json"
     resp = client.post("/recommend", json={"user_id": "42"})
     assert resp.status_code == 200 and resp.json()["purchase_history_used"] == "[+3d w1h9] Banana, Greek Yogurt."
     assert client.post("/recommend", json={"user_id": "43"}).status_code == 400
@@ -181,13 +181,12 @@ def test_micro_batcher_respects_max_batch_and_propagates_errors():
 
 def test_recommender_is_loaded_on_demand_when_not_preloaded(mock_recommender):
     """The reference's fallback (src/api/routes/recommend.py:76-80): a request that finds no recommender on the app
-    constructs one.  Here the lifespan's recommender is removed behind the app's back; the next /recommend must load
+    constructs one.  Here the lifespan's backend is removed behind the app's back; the next /recommend must load
     one (ONE constructor call even though it is awaited off the event loop) and answer 200."""
     with patch(f"{APP_MOD}.MonitoredRecommender", return_value=mock_recommender) as ctor:
         with TestClient(app) as c:
             assert ctor.call_count == 1
-            app.state.recommender = None
-            app.state.batcher = None
+            app.state.backend = None
             assert c.get("/ready").json() == {"status": "not_ready"}
             r = c.post("/recommend", json={"user_context": "[+7d w4h14] Organic Milk.", "top_k": 3})
             assert r.status_code == 200 and len(r.json()["recommendations"]) == 3
@@ -198,9 +197,9 @@ def test_recommender_is_loaded_on_demand_when_not_preloaded(mock_recommender):
 def test_on_demand_load_failure_is_a_503(mock_recommender):
     with patch(f"{APP_MOD}.MonitoredRecommender", return_value=mock_recommender) as ctor:
         with TestClient(app) as c:
-            app.state.recommender = None
+            installed, app.state.backend = app.state.backend, None
             ctor.side_effect = FileNotFoundError("no such model dir")
             r = c.post("/recommend", json={"user_context": "x", "top_k": 3})
             assert r.status_code == 503 and "no such model dir" in r.json()["detail"]
             ctor.side_effect = None
-            app.state.recommender = mock_recommender
+            app.state.backend = installed

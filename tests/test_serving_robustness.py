@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import asyncio
 import contextlib
+import json
 import logging
 import multiprocessing as mp
 import os
@@ -93,6 +94,63 @@ def test_worker_corpus_swap_completes_every_request():
         assert made == ["/tmp/c0.json", "/tmp/c1.json"]
 
     asyncio.run(main())
+
+
+class CatalogRec:
+    """What the app constructs in place of a MonitoredRecommender: a catalog read from the corpus JSON, a slow
+    constructor (the re-encode) and a slow recommend_batch, so that requests are in flight across the swap."""
+
+    def __init__(self, model_dir, corpus_path):
+        self.model_dir, self.corpus_path = model_dir, corpus_path
+        with open(corpus_path) as f:
+            self.pid_to_text = json.load(f)
+        self.product_ids = list(self.pid_to_text)
+        time.sleep(0.1)
+
+    def recommend_batch(self, queries, top_k, excl):
+        time.sleep(0.01)
+        return [[(p, 1.0 - 0.01 * i) for i, p in enumerate(self.product_ids[:top_k])] for _ in queries]
+
+
+def test_app_corpus_upload_completes_every_request(tmp_path, monkeypatch):
+    """The single-process twin of test_worker_corpus_swap_completes_every_request: /recommend requests issued
+    concurrently with a /admin/corpus upload all answer 200, each from the old catalog or the new, texts included."""
+    from concurrent.futures import ThreadPoolExecutor
+    from unittest.mock import patch
+
+    from fastapi.testclient import TestClient
+
+    from instacart_next_order_recommendation_amd.api.app import app
+
+    old = {f"o{i}": f"Product: Old {i}." for i in range(6)}
+    new = {f"n{i}": f"Product: New {i}." for i in range(6)}
+    (tmp_path / "eval_corpus.json").write_text(json.dumps(old))
+    monkeypatch.setenv("CORPUS_PATH", str(tmp_path / "eval_corpus.json"))
+    monkeypatch.setenv("MODEL_DIR", str(tmp_path))
+    monkeypatch.delenv("ICREC_GPU_WORKER_SOCKET", raising=False)
+
+    def ask(i):
+        time.sleep(0.004 * i)  # spread over ~0.3 s: before, during and after the 0.1 s rebuild
+        return c.post("/recommend", json={"user_context": f"q{i}", "top_k": 3})
+
+    def catalog_of(resp):
+        assert resp.status_code == 200, resp.text
+        items = resp.json()["recommendations"]
+        cat = old if items[0]["product_id"] in old else new
+        assert [(x["product_id"], x["product_text"]) for x in items] == list(cat.items())[:3]
+        return cat
+
+    with patch("instacart_next_order_recommendation_amd.api.app.MonitoredRecommender", CatalogRec):
+        with TestClient(app) as c:
+            assert catalog_of(ask(0)) is old
+            with ThreadPoolExecutor(16) as pool:
+                futs = [pool.submit(ask, i) for i in range(80)]
+                time.sleep(0.05)
+                up = c.post("/admin/corpus", json={"corpus": new})
+                assert up.status_code == 200 and up.json() == {"status": "ok", "n_products": 6}
+                seen = [catalog_of(f.result()) for f in futs]
+            assert any(s is old for s in seen)
+            assert catalog_of(ask(0)) is new
 
 
 class StubMonitored(MonitoredRecommender):
