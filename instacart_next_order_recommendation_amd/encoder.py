@@ -92,6 +92,16 @@ class DeviceEncoder:
         except Exception:
             pass
 
+    def batch_split(self, total_tokens: int) -> tuple[int, int]:
+        """(main_tokens, tail_tokens): how icrec_encode cuts a call of `total_tokens` tokens into whole rounds of
+        64 tokens per CU for the batch kernels and a remainder for the small-batch kernels on the library's side
+        stream (icrec_encode_batch_split).  The one Python call site of that entry besides bench.py, which keeps a
+        raw call of its own."""
+        m, t = C.c_int64(0), C.c_int64(0)
+        _native.check(_native.lib().icrec_encode_batch_split(self._h, int(total_tokens), C.byref(m), C.byref(t)),
+                      "icrec_encode_batch_split")
+        return int(m.value), int(t.value)
+
     def encode_into(self, ids: torch.Tensor, cu: torch.Tensor, n: int, T: int, max_seqlen: int, out: torch.Tensor,
                     ws: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None) -> None:
         """One icrec_encode on the current stream: device int32 ids[T] and cu_seqlens[n+1] -> out float32 [n, hidden].

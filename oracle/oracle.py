@@ -88,6 +88,13 @@ def make_cfg(vocab_size=30522, hidden=384, layers=6, heads=12, intermediate=1536
                    ln_eps, n_normalize, 0)
 
 
+def cfg_for(shape) -> BertCfg:
+    """The config of a model shape (synthetic.BertShape or anything with its fields): every field comes from the
+    shape, none from make_cfg's defaults."""
+    return BertCfg(shape.vocab_size, shape.hidden, shape.layers, shape.heads, shape.intermediate,
+                   shape.max_position, shape.type_vocab, shape.ln_eps, shape.n_normalize, 0)
+
+
 def weight_count(cfg: BertCfg) -> int:
     return int(lib().icrec_oracle_weight_count(C.byref(cfg)))
 

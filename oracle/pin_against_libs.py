@@ -104,7 +104,7 @@ def main() -> None:
     torch.set_num_threads(8)
     GOLD.mkdir(parents=True, exist_ok=True)
     shape = syn.BertShape()
-    ocfg = oracle.make_cfg(n_normalize=shape.n_normalize)
+    ocfg = oracle.cfg_for(shape)
 
     # ---------------------------------------------------------------- encoder
     blob = syn.synthetic_bert_weights(shape, seed=0)

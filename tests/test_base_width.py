@@ -59,8 +59,7 @@ def test_oracle_matches_transformers_at_bert_base_width():
     shape = syn.BertShape(vocab_size=2048, hidden=768, heads=12, intermediate=3072, layers=2)
     w = syn.synthetic_bert_weights(shape, seed=768)
     ids, cu = syn.synthetic_token_batch(5, seed=768, mean_len=50, std_len=50, lo=1, hi=100, vocab_size=2048)
-    cfg = oracle.make_cfg(vocab_size=2048, hidden=768, layers=2, heads=12, intermediate=3072,
-                          n_normalize=shape.n_normalize)
+    cfg = oracle.cfg_for(shape)
     assert w.size == shape.weight_count() == oracle.weight_count(cfg)
     want, _ = hf_encode(w, shape, ids, cu)
     got = oracle.encode(w, cfg, ids, cu)

@@ -9,9 +9,11 @@ import json
 import numpy as np
 import pytest
 
+from oracle import oracle
+from tests.encoder_harness import EMB_TOL, make_encoder, n_cu, oracle_rows, packed, round_plus_remainder, run
+
 pytestmark = pytest.mark.gpu
 
-EMB_TOL = 5e-6  # as tests/test_encoder_gpu.py
 BASE = dict(vocab_size=2048, hidden=768, heads=12, intermediate=3072)
 
 
@@ -19,40 +21,6 @@ def _shape(layers=2):
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     return syn.BertShape(layers=layers, **BASE)
-
-
-def _cfg(shape):
-    from oracle import oracle
-
-    return oracle.make_cfg(vocab_size=shape.vocab_size, hidden=shape.hidden, layers=shape.layers, heads=shape.heads,
-                           intermediate=shape.intermediate, max_position=shape.max_position,
-                           type_vocab=shape.type_vocab, ln_eps=shape.ln_eps, n_normalize=shape.n_normalize)
-
-
-def _make(monkeypatch, w, shape, mode="f16x3", max_seq_length=None, **env):
-    """An encoder created under the given ICREC_* settings (they are read once, at creation)."""
-    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-
-    for k, v in env.items():
-        monkeypatch.setenv(k, str(v))
-    try:
-        return DeviceEncoder(w, shape, gemm_mode=mode, max_seq_length=max_seq_length)
-    finally:
-        for k in env:
-            monkeypatch.delenv(k)
-
-
-def _run(enc, ids, cu):
-    import torch
-
-    return enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(),
-                             int(np.diff(cu).max())).cpu().numpy()
-
-
-def _packed(lens, seed):
-    rng = np.random.default_rng(seed)
-    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    return rng.integers(0, BASE["vocab_size"], int(cu[-1])).astype(np.int32), cu
 
 
 @pytest.fixture(scope="module")
@@ -63,13 +31,12 @@ def base2():
 
     assert torch.cuda.is_available()
     from instacart_next_order_recommendation_amd import synthetic as syn
-    from oracle import oracle
 
     shape = _shape(2)
     w = syn.synthetic_bert_weights(shape, seed=768)
     lens = [256, 200, 129, 65, 64, 33, 32, 31, 1] + np.random.default_rng(5).integers(3, 25, 61).tolist()
-    ids, cu = _packed(lens, seed=6)
-    return {"shape": shape, "w": w, "ids": ids, "cu": cu, "want": oracle.encode(w, _cfg(shape), ids, cu)}
+    ids, cu = packed(lens, 6, BASE["vocab_size"])
+    return {"shape": shape, "w": w, "ids": ids, "cu": cu, "want": oracle_rows(w, shape, ids, cu)}
 
 
 def test_every_form_vs_oracle(monkeypatch, base2):
@@ -81,8 +48,8 @@ def test_every_form_vs_oracle(monkeypatch, base2):
     for form, mode, env in [("f32", "f32", {}), ("latency", "f16x3", {}), ("batch", "f16x3", {"ICREC_SMALL_M": 512}),
                             ("latency_unfused", "f16x3", {"ICREC_FUSE": 0}),
                             ("batch_unfused", "f16x3", {"ICREC_SMALL_M": 512, "ICREC_FUSE": 0})]:
-        enc = _make(monkeypatch, base2["w"], base2["shape"], mode, **env)
-        got[form] = _run(enc, ids, cu)
+        enc = make_encoder(monkeypatch, base2["w"], base2["shape"], mode, **env)
+        got[form] = run(enc, ids, cu)
         enc.close()
         assert got[form].shape == (cu.size - 1, 768)
         err = float(np.abs(got[form] - want).max())
@@ -96,20 +63,18 @@ def test_every_form_vs_oracle(monkeypatch, base2):
 def test_long_sequences(monkeypatch, base2, mode):
     """After icrec_encoder_set_max_seqlen(512): 257, 300, 511 and 512 tokens (the 9-16-key-tile bucket, K/V staged in
     two chunks) against the oracle; each sequence gives the same bits alone and inside a mixed batch of 70."""
-    from oracle import oracle
-
     shape, w = base2["shape"], base2["w"]
     long_lens = [257, 300, 511, 512]
     lens = long_lens + [33, 96, 1, 160] + np.random.default_rng(8).integers(2, 40, 62).tolist()
-    ids, cu = _packed(lens, seed=9)
-    want = oracle.encode(w, _cfg(shape), ids[: cu[4]], cu[:5])
-    enc = _make(monkeypatch, w, shape, mode, max_seq_length=512)
-    mixed = _run(enc, ids, cu)
+    ids, cu = packed(lens, 9, BASE["vocab_size"])
+    want = oracle_rows(w, shape, ids[: cu[4]], cu[:5])
+    enc = make_encoder(monkeypatch, w, shape, mode, max_seq_length=512)
+    mixed = run(enc, ids, cu)
     err = float(np.abs(mixed[:4] - want).max())
     print(f"{mode}: long sequences max|emb - oracle| = {err:.3e}")
     assert err < EMB_TOL, err
     for s in range(8):  # the long ones and a few shorter ones, alone
-        one = _run(enc, ids[cu[s]: cu[s + 1]].copy(), np.array([0, cu[s + 1] - cu[s]], np.int32))
+        one = run(enc, ids[cu[s]: cu[s + 1]].copy(), np.array([0, cu[s + 1] - cu[s]], np.int32))
         np.testing.assert_array_equal(one[0], mixed[s], err_msg=f"sequence {s} ({lens[s]} tokens)")
     enc.close()
 
@@ -117,33 +82,22 @@ def test_long_sequences(monkeypatch, base2, mode):
 def test_rounds_plus_remainder_on_the_side_stream(monkeypatch, base2):
     """Whole rounds (64 tokens per CU) through the batch-form GEMMs + a remainder through the latency form on the side
     stream: the same bits as the unfused chain and, for the remainder's sequences, as encoding them alone."""
-    import ctypes as C
-
-    import torch
-
-    from instacart_next_order_recommendation_amd import _native
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     shape, w = base2["shape"], base2["w"]
     ids, cu = syn.synthetic_token_batch(400, seed=11, mean_len=90, std_len=60, lo=3, hi=256, vocab_size=2048)
-    enc = _make(monkeypatch, w, shape)
-    round_tokens = 64 * torch.cuda.get_device_properties(0).multi_processor_count
-    for n in range(1, cu.size):  # the first prefix that splits into whole rounds + a remainder of 1 .. 2,560 tokens
-        m, t = C.c_int64(0), C.c_int64(0)
-        _native.check(_native.lib().icrec_encode_batch_split(enc._h, int(cu[n]), C.byref(m), C.byref(t)), "split")
-        if 1 <= t.value <= 2560:
-            break
-    else:
-        raise AssertionError("no prefix with a remainder")
-    ids, cu, main_t = ids[: cu[n]].copy(), cu[: n + 1].copy(), int(m.value)
+    enc = make_encoder(monkeypatch, w, shape)
+    round_tokens = 64 * n_cu()
+    n, main_t, _ = round_plus_remainder(enc, cu, 1, 2560)
+    ids, cu = ids[: cu[n]].copy(), cu[: n + 1].copy()
     assert main_t % round_tokens == 0 and main_t > 0
-    a = _run(enc, ids, cu)
-    ref = _make(monkeypatch, w, shape, ICREC_FUSE=0, ICREC_SIDE_STREAM=0)
-    np.testing.assert_array_equal(_run(ref, ids, cu), a)
+    a = run(enc, ids, cu)
+    ref = make_encoder(monkeypatch, w, shape, ICREC_FUSE=0, ICREC_SIDE_STREAM=0)
+    np.testing.assert_array_equal(run(ref, ids, cu), a)
     ref.close()
     s0 = int(np.searchsorted(cu, main_t, side="right")) - 1
     sub_cu = (cu[s0:] - cu[s0]).astype(np.int32)
-    np.testing.assert_array_equal(_run(enc, ids[cu[s0]:].copy(), sub_cu), a[s0:])
+    np.testing.assert_array_equal(run(enc, ids[cu[s0]:].copy(), sub_cu), a[s0:])
     enc.close()
 
 
@@ -152,15 +106,14 @@ def test_workspace_contents_never_leak_into_results(monkeypatch, base2, mode):
     """A workspace full of NaN bit patterns gives the same bits as a zeroed one."""
     import torch
 
-    enc = _make(monkeypatch, base2["w"], base2["shape"], mode)
+    enc = make_encoder(monkeypatch, base2["w"], base2["shape"], mode)
     ids, cu = base2["ids"], base2["cu"]
-    args = (torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max()))
-    enc.encode_packed(*args)
+    run(enc, ids, cu)
     ws = enc._ws_by_stream[torch.cuda.current_stream().cuda_stream]
     out = []
     for fill in (0xFF, 0x00):
         ws.fill_(fill)
-        out.append(enc.encode_packed(*args).cpu().numpy())
+        out.append(run(enc, ids, cu))
         assert np.isfinite(out[-1]).all(), f"workspace byte 0x{fill:02X} leaked into the embeddings"
     np.testing.assert_array_equal(out[0], out[1])
     enc.close()
@@ -170,14 +123,13 @@ def test_workspace_contents_never_leak_into_results(monkeypatch, base2, mode):
 def test_twelve_layer_bert_base(monkeypatch, mode):
     """The whole BERT-base shape (12 layers), ~300 tokens in 5 sequences: within EMB_TOL of the oracle."""
     from instacart_next_order_recommendation_amd import synthetic as syn
-    from oracle import oracle
 
     shape = _shape(12)
     w = syn.synthetic_bert_weights(shape, seed=12)
-    ids, cu = _packed([120, 77, 64, 31, 9], seed=12)
-    want = oracle.encode(w, _cfg(shape), ids, cu)
-    enc = _make(monkeypatch, w, shape, mode)
-    err = float(np.abs(_run(enc, ids, cu) - want).max())
+    ids, cu = packed([120, 77, 64, 31, 9], 12, BASE["vocab_size"])
+    want = oracle_rows(w, shape, ids, cu)
+    enc = make_encoder(monkeypatch, w, shape, mode)
+    err = float(np.abs(run(enc, ids, cu) - want).max())
     enc.close()
     print(f"{mode}: 12 layers max|emb - oracle| = {err:.3e}")
     assert err < EMB_TOL, err
@@ -191,7 +143,6 @@ def test_recommender_end_to_end(tmp_path, monkeypatch):
     from instacart_next_order_recommendation_amd.encoder import pack_token_ids
     from instacart_next_order_recommendation_amd.model_io import load_model_dir, write_synthetic_model_dir
     from instacart_next_order_recommendation_amd.recommender import Recommender
-    from oracle import oracle
 
     vocab = len(syn.synthetic_vocab())
     shape = syn.BertShape(vocab_size=vocab, hidden=768, heads=12, intermediate=3072, layers=2)
@@ -206,7 +157,7 @@ def test_recommender_end_to_end(tmp_path, monkeypatch):
     assert rec._fast is not None
 
     loaded = load_model_dir(model_dir)
-    cfg = _cfg(loaded.shape)
+    cfg = oracle.cfg_for(loaded.shape)
     pids, cu_p, _ = pack_token_ids(rec.model.tokenizer(rec.product_texts))
     P = oracle.encode(loaded.weights, cfg, pids, cu_p)
     assert np.abs(rec.product_embeddings - P).max() < EMB_TOL

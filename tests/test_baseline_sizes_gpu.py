@@ -14,9 +14,9 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from tests.encoder_harness import EMB_TOL, run
 
-EMB_TOL = 5e-6  # same bar as tests/test_encoder_gpu.py
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -30,7 +30,6 @@ def cuda():
 @pytest.mark.parametrize("mode", ["f16x3", "f32"])
 def test_bench_batch_encode_vs_oracle(cuda, minilm_weights, mode):
     """bench.py's step input (synthetic_token_batch(1024, seed=1234)): >= 160 of its 1,024 sequences vs oracle.encode."""
-    torch = cuda
     from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
     from oracle import oracle
@@ -38,7 +37,7 @@ def test_bench_batch_encode_vs_oracle(cuda, minilm_weights, mode):
     ids, cu = syn.synthetic_token_batch(1024, seed=1234)
     assert int(cu[-1]) == 131150
     enc = DeviceEncoder(minilm_weights, gemm_mode=mode)
-    emb = enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max())).cpu().numpy()
+    emb = run(enc, ids, cu)
     assert np.isfinite(emb).all() and np.abs(np.linalg.norm(emb, axis=1) - 1).max() < 1e-6
     lens = np.diff(cu)
     pick = sorted({*range(128), 1023, int(lens.argmin()), int(lens.argmax()),
@@ -52,7 +51,7 @@ def test_bench_batch_encode_vs_oracle(cuda, minilm_weights, mode):
     print(f"[{mode}] 1,024-context batch: max|emb - oracle| over {len(pick)} sampled sequences = {err:.3e}")
     assert err < EMB_TOL
     # the sampled sequences encode to the same bits on their own (batch invariance at this size)
-    alone = enc.encode_packed(torch.from_numpy(sub_ids).cuda(), torch.from_numpy(sub_cu).cuda(), int(np.diff(sub_cu).max())).cpu().numpy()
+    alone = run(enc, sub_ids, sub_cu)
     np.testing.assert_array_equal(alone, emb[pick])
     enc.close()
 

@@ -25,7 +25,7 @@ def test_rank_all_matches_oracle_topk(tmp_path):
     assert list(ranked) == list(queries) and all(len(v) == 100 and len(set(v)) == 100 for v in ranked.values())
 
     m = load_model_dir(model_dir)
-    cfg = oracle.make_cfg(vocab_size=m.shape.vocab_size, n_normalize=m.shape.n_normalize)
+    cfg = oracle.cfg_for(m.shape)
     ids, cu, _ = pack_token_ids(m.tokenizer(list(queries.values())))
     q_emb = oracle.encode(m.weights, cfg, ids, cu)
     pids, pcu, _ = pack_token_ids(m.tokenizer(list(corpus.values())))

@@ -41,8 +41,7 @@ def test_bench_plain_run_single_gpu(tmp_path):
     shape = syn.BertShape()
     ids, cu = syn.synthetic_token_batch(64, seed=1234)  # bench.py's step input at --batch 64, rank 0
     n = 8
-    want = oracle.encode(syn.synthetic_bert_weights(shape, seed=0),
-                         oracle.make_cfg(vocab_size=shape.vocab_size, n_normalize=shape.n_normalize), ids[:cu[n]], cu[:n + 1])
+    want = oracle.encode(syn.synthetic_bert_weights(shape, seed=0), oracle.cfg_for(shape), ids[:cu[n]], cu[:n + 1])
     assert float(np.abs(emb[:n] - want).max()) < 5e-6
     P = syn.synthetic_embeddings(49_688, 384, seed=1)  # bench.py's catalog
     wi, ws = oracle.search(emb, P, 20, None)

@@ -4,11 +4,11 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from oracle import oracle
+from tests.encoder_harness import EMB_TOL, make_encoder, packed, round_plus_remainder, run
+
 pytestmark = pytest.mark.gpu
 
-# Tolerance for embeddings (unit vectors): fp32 everywhere, GEMM / LayerNorm / pooling orders are
-# identical to the oracle's; the only differences are expf / erff (device libm vs glibc) by a few ulp.
-EMB_TOL = 5e-6
 # north_star: cosine scores within 1e-4 of the fp32 reference
 COS_TOL = 1e-4
 
@@ -25,16 +25,9 @@ def encoder(request, minilm_weights):
     return DeviceEncoder(minilm_weights, gemm_mode=request.param)
 
 
-def _encode(encoder, ids, cu):
-    import torch
-
-    mx = int(np.diff(cu).max())
-    return encoder.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), mx).cpu().numpy()
-
-
 def test_golden_short_batch(encoder, golden_encoder):
     g = golden_encoder
-    emb = _encode(encoder, g["ids"], g["cu_seqlens"])
+    emb = run(encoder, g["ids"], g["cu_seqlens"])
     print(f"[{encoder.gemm_mode}] max|emb - oracle| = {np.abs(emb - g['oracle_embeddings']).max():.3e}")
     assert np.abs(emb - g["oracle_embeddings"]).max() < EMB_TOL
     assert np.abs(emb - g["hf_embeddings"]).max() < EMB_TOL          # transformers.BertModel output
@@ -43,7 +36,7 @@ def test_golden_short_batch(encoder, golden_encoder):
 
 def test_golden_long_sequences(encoder, golden_encoder):
     g = golden_encoder
-    emb = _encode(encoder, g["ids_long"], g["cu_seqlens_long"])
+    emb = run(encoder, g["ids_long"], g["cu_seqlens_long"])
     print(f"[{encoder.gemm_mode}] long: max|emb - oracle| = {np.abs(emb - g['oracle_embeddings_long']).max():.3e}")
     assert np.abs(emb - g["oracle_embeddings_long"]).max() < EMB_TOL
     assert np.abs(emb - g["hf_embeddings_long"]).max() < EMB_TOL
@@ -53,13 +46,9 @@ def test_golden_long_sequences(encoder, golden_encoder):
                                   [159, 160, 161], [191, 192, 193, 96], [223, 224, 225]])
 def test_ragged_lengths_vs_oracle(encoder, minilm_weights, lens):
     """Tile-boundary lengths for every attention bucket (1 / 2 / 3-4 / 5-6 / 7-8 key tiles), mixed in one batch."""
-    from oracle import oracle
-
-    rng = np.random.default_rng(sum(lens))
-    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    ids = rng.integers(0, 30522, size=int(cu[-1])).astype(np.int32)
+    ids, cu = packed(lens, sum(lens), 30522)
     want = oracle.encode(minilm_weights, oracle.make_cfg(), ids, cu)
-    got = _encode(encoder, ids, cu)
+    got = run(encoder, ids, cu)
     assert np.abs(got - want).max() < EMB_TOL
 
 
@@ -68,9 +57,9 @@ def test_batch_invariance_bitwise(encoder):
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     ids, cu = syn.synthetic_token_batch(6, seed=21, mean_len=40, std_len=30, lo=2, hi=150)
-    full = _encode(encoder, ids, cu)
+    full = run(encoder, ids, cu)
     for s in [0, 3, 5]:
-        one = _encode(encoder, ids[cu[s]:cu[s + 1]].copy(), np.array([0, cu[s + 1] - cu[s]], np.int32))
+        one = run(encoder, ids[cu[s]:cu[s + 1]].copy(), np.array([0, cu[s + 1] - cu[s]], np.int32))
         np.testing.assert_array_equal(one[0], full[s])
 
 
@@ -79,12 +68,10 @@ def test_attention_bucket_boundaries_alone_equal_in_batch(encoder):
     through the 8-tile one (and 3-4 tiles through the 4-tile one either way): the same bits on both sides of every
     bucket boundary."""
     lens = [96, 97, 128, 129, 160, 161, 192, 193, 224, 256]
-    rng = np.random.default_rng(5)
-    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    ids = rng.integers(0, 30522, size=int(cu[-1])).astype(np.int32)
-    full = _encode(encoder, ids, cu)
+    ids, cu = packed(lens, 5, 30522)
+    full = run(encoder, ids, cu)
     for s, n in enumerate(lens):
-        one = _encode(encoder, ids[cu[s]:cu[s + 1]].copy(), np.array([0, n], np.int32))
+        one = run(encoder, ids[cu[s]:cu[s + 1]].copy(), np.array([0, n], np.int32))
         np.testing.assert_array_equal(one[0], full[s], err_msg=f"length {n}")
 
 
@@ -94,39 +81,35 @@ def test_small_and_batch_gemm_paths_agree_bitwise(encoder, minilm_weights, monke
     either (same per-output MFMA chains, same LayerNorm tree) - alone, inside a 6,000-token batch, and inside a
     2,400-token batch whichever of the two forms that batch is given (ICREC_SMALL_M at encoder creation)."""
     from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
 
     ids, cu = syn.synthetic_token_batch(60, seed=33, mean_len=100, std_len=40, lo=5, hi=256)
     assert cu[-1] > 3584 + 512
-    full = _encode(encoder, ids, cu)
+    full = run(encoder, ids, cu)
     for s in [0, 7, 23, 59]:
         n = int(cu[s + 1] - cu[s])
-        one = _encode(encoder, ids[cu[s]:cu[s + 1]].copy(), np.array([0, n], np.int32))
+        one = run(encoder, ids[cu[s]:cu[s + 1]].copy(), np.array([0, n], np.int32))
         np.testing.assert_array_equal(one[0], full[s])
     mid_ids, mid_cu = ids[:cu[24]].copy(), cu[:25].copy()
     assert 1024 < mid_cu[-1] <= 3584
-    mid = _encode(encoder, mid_ids, mid_cu)                       # latency form
+    mid = run(encoder, mid_ids, mid_cu)                       # latency form
     np.testing.assert_array_equal(mid, full[:24])
-    monkeypatch.setenv("ICREC_SMALL_M", "512")
-    batch_form = DeviceEncoder(minilm_weights, gemm_mode=encoder.gemm_mode)  # the same 2,400 tokens through the layer kernel
-    monkeypatch.delenv("ICREC_SMALL_M")
-    np.testing.assert_array_equal(_encode(batch_form, mid_ids, mid_cu), mid)
+    # the same 2,400 tokens through the layer kernel
+    batch_form = make_encoder(monkeypatch, minilm_weights, syn.BertShape(), encoder.gemm_mode, ICREC_SMALL_M=512)
+    np.testing.assert_array_equal(run(batch_form, mid_ids, mid_cu), mid)
     batch_form.close()
 
 
 def test_n_normalize_variants(minilm_weights):
     """n_normalize = 0 (raw mean pool) and 1 match the oracle; 2 is the default path."""
-    import torch
     from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-    from oracle import oracle
 
     ids, cu = syn.synthetic_token_batch(2, seed=3, mean_len=10, std_len=3, lo=3, hi=20)
     for nn in (0, 1):
         shape = syn.BertShape(n_normalize=nn)
         enc = DeviceEncoder(minilm_weights, shape)
-        got = enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max())).cpu().numpy()
-        want = oracle.encode(minilm_weights, oracle.make_cfg(n_normalize=nn), ids, cu)
+        got = run(enc, ids, cu)
+        want = oracle.encode(minilm_weights, oracle.cfg_for(shape), ids, cu)
         assert np.abs(got - want).max() < (2e-5 if nn == 0 else EMB_TOL)
         enc.close()
 
@@ -162,10 +145,8 @@ def test_wide_dynamic_range(mode):
     """Weights 4x larger than BERT's init and LayerNorm gains of ~3: hidden activations reach tens,
     FFN intermediates hundreds, attention is sharply peaked; tiny-magnitude weights ride along in the
     same matrices.  The f16x3 split must stay at fp32-level agreement with the oracle."""
-    import torch
     from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-    from oracle import oracle
 
     shape = syn.BertShape(vocab_size=2048, layers=2)
     w = syn.synthetic_bert_weights(shape, seed=9, std=0.2)
@@ -176,10 +157,10 @@ def test_wide_dynamic_range(mode):
         if name.endswith("intermediate.dense.weight"):
             a[::7] *= 1e-4                            # rows of very small weights next to large ones
     ids, cu = syn.synthetic_token_batch(5, seed=2, mean_len=60, std_len=40, lo=3, hi=200, vocab_size=2048)
-    want, hid = oracle.encode(w, oracle.make_cfg(vocab_size=2048, layers=2), ids, cu, return_hidden=True)
+    want, hid = oracle.encode(w, oracle.cfg_for(shape), ids, cu, return_hidden=True)
     assert np.abs(hid).max() > 5.0                   # the stress actually stresses
     enc = DeviceEncoder(w, shape, gemm_mode=mode)
-    got = enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max())).cpu().numpy()
+    got = run(enc, ids, cu)
     err = np.abs(got - want).max()
     print(f"[{mode}] wide-range max|emb - oracle| = {err:.3e}, max|hidden| = {np.abs(hid).max():.1f}")
     assert err < EMB_TOL
@@ -214,9 +195,7 @@ def test_fused_layer_kernels_equal_unfused_bitwise(minilm_weights, monkeypatch, 
     from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
 
     enc = DeviceEncoder(minilm_weights, gemm_mode="f16x3")
-    monkeypatch.setenv("ICREC_FUSE", "0")
-    ref = DeviceEncoder(minilm_weights, gemm_mode="f16x3")
-    monkeypatch.delenv("ICREC_FUSE")
+    ref = make_encoder(monkeypatch, minilm_weights, syn.BertShape(), ICREC_FUSE=0)
     ids, cu = syn.synthetic_token_batch(n_seqs, seed=5, mean_len=90, std_len=60, lo=3, hi=256)
     assert int(cu[-1]) > {19: 512, 60: 3584, 400: 2 * 64 * 256}[n_seqs]
     mx = int(np.diff(cu).max())
@@ -238,12 +217,11 @@ def test_small_batches_with_layernorms_folded_into_the_gemms_bitwise(minilm_weig
     thread => identical bits; rows of a 32-token block past the end of the batch never reach a real row."""
     import torch
 
+    from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
 
     enc = DeviceEncoder(minilm_weights, gemm_mode="f16x3")
-    monkeypatch.setenv("ICREC_FUSE", "0")
-    ref = DeviceEncoder(minilm_weights, gemm_mode="f16x3")
-    monkeypatch.delenv("ICREC_FUSE")
+    ref = make_encoder(monkeypatch, minilm_weights, syn.BertShape(), ICREC_FUSE=0)
     rng = np.random.default_rng(len(lens))
     ids = rng.integers(1000, 30000, size=int(np.sum(lens))).astype(np.int32)
     cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
@@ -262,23 +240,12 @@ def test_side_stream_changes_nothing(minilm_weights, monkeypatch):
     An encoder created under ICREC_SIDE_STREAM=0 keeps every kernel on the caller's stream: same bits, and repeated calls stay identical."""
     import torch
 
-    from instacart_next_order_recommendation_amd import _native, synthetic as syn
+    from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
 
     enc = DeviceEncoder(minilm_weights, gemm_mode="f16x3")
     ids, cu = syn.synthetic_token_batch(400, seed=11, mean_len=90, std_len=60, lo=3, hi=256)
-    import ctypes as C
-
-    def split(tokens):
-        m, t = C.c_int64(0), C.c_int64(0)
-        _native.check(_native.lib().icrec_encode_batch_split(enc._h, tokens, C.byref(m), C.byref(t)), "icrec_encode_batch_split")
-        return int(m.value), int(t.value)
-
-    main_t, tail_t, n = 0, 0, 0
-    for n in range(64, 400):  # the first cut whose token count splits into whole rounds + a remainder
-        main_t, tail_t = split(int(cu[n]))
-        if tail_t:
-            break
+    n, main_t, tail_t = round_plus_remainder(enc, cu, 1, np.inf, first=64)
     assert tail_t and main_t % (64 * 256) == 0 and n >= 64, (main_t, tail_t, n)
     ids, cu = ids[: cu[n]], cu[: n + 1]
     mx = int(np.diff(cu).max())
@@ -286,23 +253,19 @@ def test_side_stream_changes_nothing(minilm_weights, monkeypatch):
     args = (torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), mx)
     a = enc.encode_packed(*args).cpu().numpy()
     b = enc.encode_packed(*args).cpu().numpy()
-    monkeypatch.setenv("ICREC_SIDE_STREAM", "0")   # read once, at icrec_encoder_create
-    enc_one_stream = DeviceEncoder(minilm_weights, gemm_mode="f16x3")
-    monkeypatch.delenv("ICREC_SIDE_STREAM")
+    enc_one_stream = make_encoder(monkeypatch, minilm_weights, syn.BertShape(), ICREC_SIDE_STREAM=0)
     c = enc_one_stream.encode_packed(*args).cpu().numpy()
     enc_one_stream.close()
     np.testing.assert_array_equal(a, b)
     np.testing.assert_array_equal(a, c)
-    monkeypatch.setenv("ICREC_TAIL_M", "0")        # no remainder rule: the same tokens as a partial round of the batch kernels
-    enc_no_tail = DeviceEncoder(minilm_weights, gemm_mode="f16x3")
-    monkeypatch.delenv("ICREC_TAIL_M")
+    # no remainder rule: the same tokens as a partial round of the batch kernels
+    enc_no_tail = make_encoder(monkeypatch, minilm_weights, syn.BertShape(), ICREC_TAIL_M=0)
     np.testing.assert_array_equal(enc_no_tail.encode_packed(*args).cpu().numpy(), a)
     enc_no_tail.close()
     # the remainder's sequences encode to the same bits on their own (small-batch kernels on the caller's stream)
     s0 = int(np.searchsorted(cu, main_t, side="right")) - 1
     sub_cu = (cu[s0:] - cu[s0]).astype(np.int32)
-    sub = enc.encode_packed(torch.from_numpy(ids[cu[s0]:]).cuda(), torch.from_numpy(sub_cu).cuda(), int(np.diff(sub_cu).max()))
-    np.testing.assert_array_equal(sub.cpu().numpy(), a[s0:])
+    np.testing.assert_array_equal(run(enc, ids[cu[s0]:], sub_cu), a[s0:])
     enc.close()
 
 

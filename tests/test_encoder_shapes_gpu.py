@@ -5,30 +5,19 @@ whole rounds + a remainder on the side stream - against the oracle and against e
 ICREC_SMALL_M / ICREC_TAIL_M pair."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from tests.encoder_harness import EMB_TOL, make_encoder, n_cu, oracle_rows, round_plus_remainder, run
 from tests.encoder_shapes import SHAPES
 
 pytestmark = pytest.mark.gpu
-
-EMB_TOL = 5e-6   # as tests/test_encoder_gpu.py
 
 
 def _shape(name):
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     return syn.BertShape(vocab_size=2048, **SHAPES[name])
-
-
-def _cfg(shape):
-    from oracle import oracle
-
-    return oracle.make_cfg(vocab_size=shape.vocab_size, hidden=shape.hidden, layers=shape.layers, heads=shape.heads,
-                           intermediate=shape.intermediate, max_position=shape.max_position,
-                           type_vocab=shape.type_vocab, ln_eps=shape.ln_eps, n_normalize=shape.n_normalize)
 
 
 def _batch(shape, seed):
@@ -44,26 +33,6 @@ def _batch(shape, seed):
     return ids, cu
 
 
-def _make(monkeypatch, w, shape, mode="f16x3", **env):
-    """An encoder created under the given ICREC_* settings (they are read once, at creation)."""
-    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-
-    for k, v in env.items():
-        monkeypatch.setenv(k, str(v))
-    try:
-        return DeviceEncoder(w, shape, gemm_mode=mode)
-    finally:
-        for k in env:
-            monkeypatch.delenv(k)
-
-
-def _run(enc, ids, cu):
-    import torch
-
-    return enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(),
-                             int(np.diff(cu).max())).cpu().numpy()
-
-
 @pytest.mark.parametrize("name", list(SHAPES))
 def test_every_layer_form_vs_oracle(monkeypatch, name):
     """One ~1,800-token batch through: the latency-form kernels (default, <= 3,584 tokens), the layer kernel
@@ -73,20 +42,19 @@ def test_every_layer_form_vs_oracle(monkeypatch, name):
 
     assert torch.cuda.is_available()
     from instacart_next_order_recommendation_amd import synthetic as syn
-    from oracle import oracle
 
     shape = _shape(name)
     w = syn.synthetic_bert_weights(shape, seed=len(name))
     ids, cu = _batch(shape, seed=len(name))
     assert 512 < cu[-1] <= 3584
-    want = oracle.encode(w, _cfg(shape), ids, cu)
+    want = oracle_rows(w, shape, ids, cu)
     got = {}
     for form, mode, env in [("latency", "f16x3", {}), ("layer", "f16x3", {"ICREC_SMALL_M": 512}),
                             ("latency_unfused", "f16x3", {"ICREC_FUSE": 0}),
                             ("layer_unfused", "f16x3", {"ICREC_SMALL_M": 512, "ICREC_FUSE": 0}),
                             ("f32", "f32", {})]:
-        enc = _make(monkeypatch, w, shape, mode, **env)
-        got[form] = _run(enc, ids, cu)
+        enc = make_encoder(monkeypatch, w, shape, mode, **env)
+        got[form] = run(enc, ids, cu)
         enc.close()
         err = float(np.abs(got[form] - want).max())
         print(f"[{name}] {form}: max|emb - oracle| = {err:.3e}")
@@ -101,41 +69,16 @@ def test_max_position_is_the_sequence_limit(monkeypatch):
 
     from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd._native import IcrecError
-    from oracle import oracle
 
     shape = _shape("max_position64")
     w = syn.synthetic_bert_weights(shape, seed=64)
-    enc = _make(monkeypatch, w, shape)
+    enc = make_encoder(monkeypatch, w, shape)
     ids = np.arange(1, 66, dtype=np.int32)
-    one = _run(enc, ids[:64].copy(), np.array([0, 64], np.int32))
-    assert np.abs(one - oracle.encode(w, _cfg(shape), ids[:64], np.array([0, 64], np.int32))).max() < EMB_TOL
+    one = run(enc, ids[:64].copy(), np.array([0, 64], np.int32))
+    assert np.abs(one - oracle_rows(w, shape, ids[:64], np.array([0, 64], np.int32))).max() < EMB_TOL
     with pytest.raises(IcrecError):
         enc.encode_packed(torch.from_numpy(ids).cuda(), torch.tensor([0, 65], dtype=torch.int32).cuda(), 65)
     enc.close()
-
-
-def _split(enc, tokens):
-    from instacart_next_order_recommendation_amd import _native
-
-    m, t = C.c_int64(0), C.c_int64(0)
-    _native.check(_native.lib().icrec_encode_batch_split(enc._h, int(tokens), C.byref(m), C.byref(t)),
-                  "icrec_encode_batch_split")
-    return int(m.value), int(t.value)
-
-
-def _round_plus_remainder(enc, ids, cu, lo, hi):
-    """The first prefix of the batch that splits into whole rounds (64 tokens per CU) + a remainder in [lo, hi]."""
-    for n in range(1, cu.size):
-        main_t, tail_t = _split(enc, cu[n])
-        if lo <= tail_t <= hi:
-            return ids[: cu[n]].copy(), cu[: n + 1].copy(), main_t, tail_t
-    raise AssertionError(f"no prefix with a remainder in [{lo}, {hi}]")
-
-
-def _n_cu():
-    import torch
-
-    return torch.cuda.get_device_properties(0).multi_processor_count
 
 
 @pytest.mark.parametrize("name", ["layers1", "inter3072"])
@@ -147,16 +90,17 @@ def test_rounds_plus_remainder_on_the_side_stream(monkeypatch, name):
     shape = _shape(name)
     w = syn.synthetic_bert_weights(shape, seed=7)
     ids, cu = syn.synthetic_token_batch(400, seed=11, mean_len=90, std_len=60, lo=3, hi=256, vocab_size=2048)
-    enc = _make(monkeypatch, w, shape)
-    ids, cu, main_t, tail_t = _round_plus_remainder(enc, ids, cu, 1, 2560)
-    assert main_t % (64 * _n_cu()) == 0 and int(np.diff(cu).max()) > 128 and cu.size > 65
-    a = _run(enc, ids, cu)
-    ref = _make(monkeypatch, w, shape, ICREC_FUSE=0)
-    np.testing.assert_array_equal(_run(ref, ids, cu), a)
+    enc = make_encoder(monkeypatch, w, shape)
+    n, main_t, tail_t = round_plus_remainder(enc, cu, 1, 2560)
+    ids, cu = ids[: cu[n]].copy(), cu[: n + 1].copy()
+    assert main_t % (64 * n_cu()) == 0 and int(np.diff(cu).max()) > 128 and cu.size > 65
+    a = run(enc, ids, cu)
+    ref = make_encoder(monkeypatch, w, shape, ICREC_FUSE=0)
+    np.testing.assert_array_equal(run(ref, ids, cu), a)
     ref.close()
     s0 = int(np.searchsorted(cu, main_t, side="right")) - 1
     sub_cu = (cu[s0:] - cu[s0]).astype(np.int32)
-    np.testing.assert_array_equal(_run(enc, ids[cu[s0]:].copy(), sub_cu), a[s0:])
+    np.testing.assert_array_equal(run(enc, ids[cu[s0]:].copy(), sub_cu), a[s0:])
     enc.close()
 
 
@@ -167,15 +111,16 @@ def test_remainder_longer_than_small_m(monkeypatch, minilm_weights):
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     ids, cu = syn.synthetic_token_batch(400, seed=13, mean_len=90, std_len=60, lo=3, hi=256)
-    enc = _make(monkeypatch, minilm_weights, syn.BertShape(), ICREC_SMALL_M=512, ICREC_TAIL_M=2560)
-    ids, cu, main_t, tail_t = _round_plus_remainder(enc, ids, cu, 1700, 2300)
-    assert tail_t > 512 and main_t % (64 * _n_cu()) == 0
-    a = _run(enc, ids, cu)
-    np.testing.assert_array_equal(_run(enc, ids, cu), a)
+    enc = make_encoder(monkeypatch, minilm_weights, syn.BertShape(), ICREC_SMALL_M=512, ICREC_TAIL_M=2560)
+    n, main_t, tail_t = round_plus_remainder(enc, cu, 1700, 2300)
+    ids, cu = ids[: cu[n]].copy(), cu[: n + 1].copy()
+    assert tail_t > 512 and main_t % (64 * n_cu()) == 0
+    a = run(enc, ids, cu)
+    np.testing.assert_array_equal(run(enc, ids, cu), a)
     enc.close()
     for env in ({}, {"ICREC_FUSE": 0}, {"ICREC_SMALL_M": 512, "ICREC_FUSE": 0}):
-        other = _make(monkeypatch, minilm_weights, syn.BertShape(), **env)
-        np.testing.assert_array_equal(_run(other, ids, cu), a, err_msg=str(env))
+        other = make_encoder(monkeypatch, minilm_weights, syn.BertShape(), **env)
+        np.testing.assert_array_equal(run(other, ids, cu), a, err_msg=str(env))
         other.close()
 
 
@@ -185,17 +130,17 @@ def test_knob_values_are_clamped(monkeypatch, minilm_weights):
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     shape = syn.BertShape()
-    rnd = 64 * _n_cu()
+    rnd = 64 * n_cu()
     ids, cu = syn.synthetic_token_batch(400, seed=17, mean_len=90, std_len=60, lo=3, hi=256)
     n = int(np.searchsorted(cu, rnd + rnd // 2))       # about half a round past the first whole round
     ids, cu = ids[: cu[n]].copy(), cu[: n + 1].copy()
-    absurd = _make(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=10 ** 12, ICREC_SMALL_M=10 ** 15)
-    clamped = _make(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=rnd - 1, ICREC_SMALL_M=1 << 20)
+    absurd = make_encoder(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=10 ** 12, ICREC_SMALL_M=10 ** 15)
+    clamped = make_encoder(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=rnd - 1, ICREC_SMALL_M=1 << 20)
     for t in (1, 513, rnd, rnd + 1, int(cu[-1]), 3 * rnd - 1, 1 << 30):
-        assert _split(absurd, t) == _split(clamped, t), t
-    assert _split(absurd, int(cu[-1])) == (rnd, int(cu[-1]) - rnd)
-    np.testing.assert_array_equal(_run(absurd, ids, cu), _run(clamped, ids, cu))
+        assert absurd.batch_split(t) == clamped.batch_split(t), t
+    assert absurd.batch_split(int(cu[-1])) == (rnd, int(cu[-1]) - rnd)
+    np.testing.assert_array_equal(run(absurd, ids, cu), run(clamped, ids, cu))
     absurd.close(); clamped.close()
-    neg = _make(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=-5)
-    assert _split(neg, int(cu[-1])) == (int(cu[-1]), 0)     # clamped to 0: no remainder rule
+    neg = make_encoder(monkeypatch, minilm_weights, shape, ICREC_TAIL_M=-5)
+    assert neg.batch_split(int(cu[-1])) == (int(cu[-1]), 0)     # clamped to 0: no remainder rule
     neg.close()

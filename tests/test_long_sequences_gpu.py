@@ -9,51 +9,12 @@ import json
 import numpy as np
 import pytest
 
+from tests.encoder_harness import EMB_TOL, make_encoder, oracle_rows, packed, run
 from tests.test_long_sequences import long_contexts
 
 pytestmark = pytest.mark.gpu
 
-EMB_TOL = 5e-6   # as tests/test_encoder_gpu.py
 MODES = ["f16x3", "f32"]
-
-
-def _make(monkeypatch, w, shape, mode="f16x3", max_seq_length=512, **env):
-    """An encoder with the given ceiling, created under the given ICREC_* settings (read once, at creation)."""
-    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-
-    for k, v in env.items():
-        monkeypatch.setenv(k, str(v))
-    try:
-        return DeviceEncoder(w, shape, gemm_mode=mode, max_seq_length=max_seq_length)
-    finally:
-        for k in env:
-            monkeypatch.delenv(k)
-
-
-def _run(enc, ids, cu, two_stream=False):
-    import torch
-
-    return enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max()),
-                             cu_host=cu if two_stream else None).cpu().numpy()
-
-
-def _oracle(w, ids, cu, rows=None, shape=None):
-    """Oracle embeddings of `rows` (default all) of the packed batch; the oracle is batch-invariant."""
-    from oracle import oracle
-
-    cfg = oracle.make_cfg() if shape is None else oracle.make_cfg(
-        vocab_size=shape.vocab_size, max_position=shape.max_position, n_normalize=shape.n_normalize)
-    if rows is None:
-        return oracle.encode(w, cfg, ids, cu)
-    sub_ids = np.concatenate([ids[cu[r]:cu[r + 1]] for r in rows])
-    sub_cu = np.concatenate([[0], np.cumsum([cu[r + 1] - cu[r] for r in rows])]).astype(np.int32)
-    return oracle.encode(w, cfg, sub_ids, sub_cu)
-
-
-def _packed(lens, seed):
-    rng = np.random.default_rng(seed)
-    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    return rng.integers(0, 30522, int(cu[-1])).astype(np.int32), cu
 
 
 def test_ceiling_bounds(monkeypatch, minilm_weights):
@@ -71,7 +32,7 @@ def test_ceiling_bounds(monkeypatch, minilm_weights):
     for bad in (0, -1, 513):
         with pytest.raises(IcrecError):
             _native.check(L.icrec_encoder_set_max_seqlen(enc._h, bad), "icrec_encoder_set_max_seqlen")
-    ids, cu = _packed([512], seed=1)
+    ids, cu = packed([512], 1, 30522)
     ids_d, cu_d = torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda()
     with pytest.raises(IcrecError):  # the default ceiling refuses 512 tokens ...
         enc.encode_packed(ids_d, cu_d, 512)
@@ -84,10 +45,10 @@ def test_ceiling_bounds(monkeypatch, minilm_weights):
     raised.close()
     with pytest.raises(IcrecError):
         DeviceEncoder(minilm_weights, shape, max_seq_length=513)
-    big = _make(monkeypatch, minilm_weights, shape)
+    big = make_encoder(monkeypatch, minilm_weights, shape, max_seq_length=512)
     assert big.max_seq_length == 512
     np.testing.assert_array_equal(big.encode_ids([ids.tolist()]).cpu().numpy(), one)
-    assert np.abs(one - _oracle(minilm_weights, ids, cu)).max() < EMB_TOL
+    assert np.abs(one - oracle_rows(minilm_weights, shape, ids, cu)).max() < EMB_TOL
     big.close()
     # under max_position 300 the ceiling stops at 300
     short = syn.BertShape(vocab_size=2048, max_position=300)
@@ -96,8 +57,8 @@ def test_ceiling_bounds(monkeypatch, minilm_weights):
         DeviceEncoder(w, short, max_seq_length=301)
     e300 = DeviceEncoder(w, short, max_seq_length=300)
     ids3 = (ids[:300] % 2048).copy()
-    got = _run(e300, ids3, np.array([0, 300], np.int32))
-    assert np.abs(got - _oracle(w, ids3, np.array([0, 300], np.int32), shape=short)).max() < EMB_TOL
+    got = run(e300, ids3, np.array([0, 300], np.int32))
+    assert np.abs(got - oracle_rows(w, short, ids3, np.array([0, 300], np.int32))).max() < EMB_TOL
     e300.close()
 
 
@@ -106,11 +67,12 @@ def test_single_sequences_vs_oracle(monkeypatch, minilm_weights, mode):
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     lens = [257, 288, 289, 300, 384, 480, 511, 512]
-    ids, cu = _packed(lens, seed=7)
-    want = _oracle(minilm_weights, ids, cu)
-    enc = _make(monkeypatch, minilm_weights, syn.BertShape(), mode)
+    ids, cu = packed(lens, 7, 30522)
+    shape = syn.BertShape()
+    want = oracle_rows(minilm_weights, shape, ids, cu)
+    enc = make_encoder(monkeypatch, minilm_weights, shape, mode, max_seq_length=512)
     for s, n in enumerate(lens):
-        got = _run(enc, ids[cu[s]:cu[s + 1]].copy(), np.array([0, n], np.int32))[0]
+        got = run(enc, ids[cu[s]:cu[s + 1]].copy(), np.array([0, n], np.int32))[0]
         err = float(np.abs(got - want[s]).max())
         print(f"[{mode}] {n} tokens alone: max|emb - oracle| = {err:.3e}")
         assert err < EMB_TOL, (n, err)
@@ -122,7 +84,7 @@ def _mixed(seed):
     order, attention buckets split over two streams)."""
     rng = np.random.default_rng(seed)
     lens = [512, 511, 481, 480, 300, 289, 288, 257, 256, 200, 129, 65, 33, 1] + rng.integers(3, 25, 56).tolist()
-    return _packed(lens, seed)
+    return packed(lens, seed, 30522)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -131,15 +93,16 @@ def test_mixed_batch_vs_oracle(monkeypatch, minilm_weights, mode):
 
     ids, cu = _mixed(seed=11)
     assert cu.size - 1 >= 64 and 3584 < cu[-1] < 8192  # past ICREC_SMALL_M's default: the layer kernel by default
-    want = _oracle(minilm_weights, ids, cu)
+    shape = syn.BertShape()
+    want = oracle_rows(minilm_weights, shape, ids, cu)
     forms = [("layer", {})]
     if mode == "f16x3":
         forms += [("latency", {"ICREC_SMALL_M": 8192}), ("layer_unfused", {"ICREC_FUSE": 0}),
                   ("latency_unfused", {"ICREC_SMALL_M": 8192, "ICREC_FUSE": 0}), ("one_stream", {"ICREC_SIDE_STREAM": 0})]
     got = {}
     for form, env in forms:
-        enc = _make(monkeypatch, minilm_weights, syn.BertShape(), mode, **env)
-        got[form] = _run(enc, ids, cu)
+        enc = make_encoder(monkeypatch, minilm_weights, shape, mode, max_seq_length=512, **env)
+        got[form] = run(enc, ids, cu)
         enc.close()
         err = float(np.abs(got[form] - want).max())
         print(f"[{mode}] mixed batch, {form}: max|emb - oracle| = {err:.3e}")
@@ -157,7 +120,7 @@ def _large(seed):
     lens = np.diff(cu)
     long_at = np.arange(3, 300, 12)
     lens[long_at] = np.linspace(257, 512, long_at.size).astype(np.int64)
-    return _packed(lens.tolist(), seed)
+    return packed(lens.tolist(), seed, 30522)
 
 
 def test_large_batch_two_stream_paths(monkeypatch, minilm_weights):
@@ -173,16 +136,16 @@ def test_large_batch_two_stream_paths(monkeypatch, minilm_weights):
     assert cu[-1] - cu[n // 2] >= DeviceEncoder.SPLIT_MIN_TOKENS
     assert (lens[: n // 2] > 256).any() and (lens[n // 2:] > 256).any()
     sample = [int(r) for r in np.flatnonzero(lens > 256)[::5]] + [int(np.argmax(lens)), 0, 1, n - 1]
-    want = _oracle(minilm_weights, ids, cu, sample)
     shape = syn.BertShape()
+    want = oracle_rows(minilm_weights, shape, ids, cu, sample)
     got = {}
     for form, env in [("default", {}), ("layer", {"ICREC_SMALL_M": 512}), ("unfused", {"ICREC_FUSE": 0})]:
-        enc = _make(monkeypatch, minilm_weights, shape, **env)
+        enc = make_encoder(monkeypatch, minilm_weights, shape, max_seq_length=512, **env)
         for two in (False, True):
-            got[(form, two)] = _run(enc, ids, cu, two_stream=two)
+            got[(form, two)] = run(enc, ids, cu, cu_host=cu if two else None)
         if form == "default":
             for s in np.flatnonzero(lens > 256):
-                alone = _run(enc, ids[cu[s]:cu[s + 1]].copy(), np.array([0, lens[s]], np.int32))
+                alone = run(enc, ids[cu[s]:cu[s + 1]].copy(), np.array([0, lens[s]], np.int32))
                 np.testing.assert_array_equal(alone[0], got[(form, False)][s], err_msg=f"sequence {s} ({lens[s]} tokens)")
         enc.close()
     ref = got[("default", False)]
@@ -191,8 +154,8 @@ def test_large_batch_two_stream_paths(monkeypatch, minilm_weights):
     err = float(np.abs(ref[sample] - want).max())
     print(f"[f16x3] large batch: max|emb - oracle| over {len(sample)} rows = {err:.3e}")
     assert err < EMB_TOL
-    enc = _make(monkeypatch, minilm_weights, shape, "f32")
-    e32 = _run(enc, ids, cu, two_stream=True)
+    enc = make_encoder(monkeypatch, minilm_weights, shape, "f32", max_seq_length=512)
+    e32 = run(enc, ids, cu, cu_host=cu)
     enc.close()
     err = float(np.abs(e32[sample] - want).max())
     print(f"[f32] large batch: max|emb - oracle| over {len(sample)} rows = {err:.3e}")
@@ -205,14 +168,14 @@ def test_no_change_at_256_tokens_or_fewer(monkeypatch, minilm_weights, mode):
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     rng = np.random.default_rng(5)
-    ids, cu = _packed([256, 200, 129, 65, 64, 33, 32, 31, 1] + rng.integers(3, 25, 61).tolist(), seed=5)
+    ids, cu = packed([256, 200, 129, 65, 64, 33, 32, 31, 1] + rng.integers(3, 25, 61).tolist(), 5, 30522)
     shape = syn.BertShape()
-    default = _make(monkeypatch, minilm_weights, shape, mode, max_seq_length=None)
-    raised = _make(monkeypatch, minilm_weights, shape, mode)
+    default = make_encoder(monkeypatch, minilm_weights, shape, mode)
+    raised = make_encoder(monkeypatch, minilm_weights, shape, mode, max_seq_length=512)
     assert default.max_seq_length == 256 and raised.max_seq_length == 512
-    np.testing.assert_array_equal(_run(raised, ids, cu), _run(default, ids, cu))
+    np.testing.assert_array_equal(run(raised, ids, cu), run(default, ids, cu))
     one = ids[: cu[1]].copy(), cu[:2].copy()
-    np.testing.assert_array_equal(_run(raised, *one), _run(default, *one))
+    np.testing.assert_array_equal(run(raised, *one), run(default, *one))
     default.close(); raised.close()
 
 
@@ -264,7 +227,7 @@ def test_recommender_end_to_end_long_contexts(long_world, monkeypatch):
     assert graph == batch == eager
     # the oracle on the recommender's own token ids; embeddings within 5e-6, so ids agree except across near-ties
     shape = rec.model.shape
-    cfg = oracle.make_cfg(vocab_size=shape.vocab_size, max_position=shape.max_position, n_normalize=shape.n_normalize)
+    cfg = oracle.cfg_for(shape)
     w = load_model_dir(rec.model_dir).weights
     ids, cu, _ = pack_token_ids(toks, limit)
     q_emb = oracle.encode(w, cfg, ids, cu)

@@ -161,9 +161,7 @@ def test_encoder_matches_transformers_at_other_shapes(name):
     if shape.max_position < 256:  # one sequence of exactly max_position tokens
         ids = np.concatenate([ids, np.arange(shape.max_position, dtype=np.int32) % 2048])
         cu = np.append(cu, cu[-1] + shape.max_position).astype(cu.dtype)
-    cfg = oracle.make_cfg(vocab_size=2048, hidden=shape.hidden, layers=shape.layers, heads=shape.heads,
-                          intermediate=shape.intermediate, max_position=shape.max_position, type_vocab=shape.type_vocab,
-                          ln_eps=shape.ln_eps, n_normalize=shape.n_normalize)
+    cfg = oracle.cfg_for(shape)
     assert w.size == shape.weight_count() == oracle.weight_count(cfg)
     want, _ = hf_encode(w, shape, ids, cu)
     got = oracle.encode(w, cfg, ids, cu)

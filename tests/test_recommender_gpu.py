@@ -32,8 +32,7 @@ def _oracle_pipeline(rec, queries, k, excl_pids):
     """The reference's recommend() restated with the oracle on the recommender's own token ids."""
     from oracle import oracle
 
-    shape = rec.model.shape
-    cfg = oracle.make_cfg(vocab_size=shape.vocab_size, n_normalize=shape.n_normalize)
+    cfg = oracle.cfg_for(rec.model.shape)
     from instacart_next_order_recommendation_amd.encoder import pack_token_ids
     from instacart_next_order_recommendation_amd.model_io import load_model_dir
 

@@ -6,6 +6,8 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from tests import encoder_harness
+
 pytestmark = pytest.mark.gpu
 
 WIDTHS = [32, 64, 96, 128, 256, 416, 512, 768, 1024, 4096]
@@ -40,12 +42,6 @@ def _S():
     from instacart_next_order_recommendation_amd import search
 
     return search
-
-
-def _n_cu():
-    import torch
-
-    return torch.cuda.get_device_properties(0).multi_processor_count
 
 
 def _rows(n, Q, dim):
@@ -110,7 +106,7 @@ def multi_tile_catalogs():
     """Catalogs sized from the CU count, at widths 64, 256 and 768: at least 6 x n_cu row tiles of 256, so that the
     streaming kernel takes 5 queries too (make_plan), and more tiles than blocks (at most 3 x n_cu), so that blocks
     walk several tiles."""
-    n_cu = _n_cu()
+    n_cu = encoder_harness.n_cu()
     n = (6 * n_cu + 27) * 256 + 5
     assert (n + 255) // 256 >= 6 * n_cu
     out = {}

@@ -19,6 +19,7 @@ import pytest
 from oracle import float64_reference as f64
 from oracle import oracle
 from tests import token_states as ts
+from tests.encoder_harness import packed
 
 SHAPES = [(384, 6), (384, 1), (768, 2)]
 FAULT_LENS = (5, 33, 128, 256, 512)
@@ -41,9 +42,9 @@ def _model(kind, hidden, layers):
 def _clean(kind, hidden, layers, n):
     """One sequence of n tokens: (ids, cu, clean float64 hidden state, E_ref row rms of the oracle on it)."""
     s, w, m = _model(kind, hidden, layers)
-    ids, cu = ts.packed([n], seed=n)
+    ids, cu = packed([n], n, ts.VOCAB)
     clean, _ = m.encode(ids, cu)
-    _, hid = oracle.encode(w, ts.oracle_cfg(s), ids, cu, return_hidden=True)
+    _, hid = oracle.encode(w, oracle.cfg_for(s), ids, cu, return_hidden=True)
     return ids, cu, clean, ts.row_errors(hid, clean)[0]
 
 
@@ -79,9 +80,9 @@ def test_oracle_error_against_float64(hidden, layers, kind):
     1e-7 per-row rms on hidden states of rms ~1 (a few hundred roundings of 6e-8, added in quadrature, per layer); the
     assertions only pin that scale (within 1e-5 rms, pooled within 1e-6) - the GPU bound uses the measured value."""
     s, w, m = _model(kind, hidden, layers)
-    ids, cu = ts.packed([5, 33, 128, 256, 512, 1, 2, 64], seed=2)
+    ids, cu = packed([5, 33, 128, 256, 512, 1, 2, 64], 2, ts.VOCAB)
     want_h, want_e = m.encode(ids, cu)
-    emb, hid = oracle.encode(w, ts.oracle_cfg(s), ids, cu, return_hidden=True)
+    emb, hid = oracle.encode(w, oracle.cfg_for(s), ids, cu, return_hidden=True)
     e_rms, e_abs = ts.row_errors(hid, want_h)
     e_emb = float(np.abs(emb - want_e).max())
     print(f"hidden {hidden} layers {layers} {kind}: oracle vs float64 row rms {e_rms:.3e} max abs {e_abs:.3e}, "
@@ -126,7 +127,7 @@ def test_faults_change_only_what_they_say():
     """A fault in the last layer leaves a sequence of one token alone where it needs a neighbour (stale row, dropped
     key), and an unknown fault name is refused."""
     s, w, m = _model("sharp", 384, 1)
-    ids, cu = ts.packed([1, 7], seed=3)
+    ids, cu = packed([1, 7], 3, ts.VOCAB)
     clean, _ = m.encode(ids, cu)
     for fault in ("stale_last_row", "drop_last_key"):
         bad, _ = m.encode(ids, cu, fault=(fault, 0))

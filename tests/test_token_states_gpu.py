@@ -8,12 +8,11 @@ chosen in profiles/token_state_errors.md.  Every comparison prints `ratio rms / 
 asserts; on failure the worst (sequence, position, feature, got, want) is named."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from tests import token_states as ts
+from tests.encoder_harness import make_encoder, packed, round_plus_remainder, run
 
 pytestmark = pytest.mark.gpu
 
@@ -36,32 +35,11 @@ def _reference(kind, hidden, layers, lens, seed):
 
         s = ts.shape(hidden, layers)
         w = ts.weights(kind, s)
-        ids, cu = ts.packed(lens, seed)
+        ids, cu = packed(lens, seed, ts.VOCAB)
         want_h, _ = f64.encode(w, s, ids, cu)
-        _, ora_h = oracle.encode(w, ts.oracle_cfg(s), ids, cu, return_hidden=True)
+        _, ora_h = oracle.encode(w, oracle.cfg_for(s), ids, cu, return_hidden=True)
         _refs[key] = dict(s=s, w=w, ids=ids, cu=cu, want_h=want_h, ora_h=ora_h, kind=kind)
     return _refs[key]
-
-
-def _make(monkeypatch, r, mode, max_seq_length=None, **env):
-    """An encoder created under the given ICREC_* settings (they are read once, at creation)."""
-    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-
-    for k, v in env.items():
-        monkeypatch.setenv(k, str(v))
-    try:
-        return DeviceEncoder(r["w"], r["s"], gemm_mode=mode, max_seq_length=max_seq_length)
-    finally:
-        for k in env:
-            monkeypatch.delenv(k)
-
-
-def _run(enc, ids, cu, **kw):
-    import torch
-
-    emb, tok = enc.encode_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max()),
-                                 return_tokens=True, **kw)
-    return emb.cpu().numpy(), tok.cpu().numpy()
 
 
 def _check(what, mode, r, emb, tok, first_seq=0, n_seqs=None):
@@ -107,19 +85,10 @@ def test_small_batch_every_width(monkeypatch, mode, hidden, layers, kind):
     f16x3 also under ICREC_FUSE=0 (separate LayerNorm launches)."""
     r = _reference(kind, hidden, layers, MIXED_LENS, seed=2)
     for env in ({}, {"ICREC_FUSE": 0}) if mode == "f16x3" else ({},):
-        enc = _make(monkeypatch, r, mode, **env)
-        emb, tok = _run(enc, r["ids"], r["cu"])
+        enc = make_encoder(monkeypatch, r["w"], r["s"], mode, **env)
+        emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
         _check(f"small {env}", mode, r, emb, tok)
         enc.close()
-
-
-def _split(enc, tokens):
-    from instacart_next_order_recommendation_amd import _native
-
-    m, t = C.c_int64(0), C.c_int64(0)
-    _native.check(_native.lib().icrec_encode_batch_split(enc._h, int(tokens), C.byref(m), C.byref(t)),
-                  "icrec_encode_batch_split")
-    return int(m.value), int(t.value)
 
 
 def _batch_lens(n, seed):
@@ -139,8 +108,8 @@ def test_batch_forms(monkeypatch, hidden, kind):
     r = _reference(kind, hidden, 2, lens, seed=3)
     assert r["cu"][-1] > 3584 + 512
     for mode, env in (("f32", {}), ("f16x3", {}), ("f16x3", {"ICREC_FUSE": 0})):
-        enc = _make(monkeypatch, r, mode, **env)
-        emb, tok = _run(enc, r["ids"], r["cu"])
+        enc = make_encoder(monkeypatch, r["w"], r["s"], mode, **env)
+        emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
         _check(f"batch {env}", mode, r, emb, tok)
         enc.close()
     if hidden == 768:
@@ -148,8 +117,8 @@ def test_batch_forms(monkeypatch, hidden, kind):
         t = int(r["cu"][n])
         assert 1000 < t <= 1500
         for env in ({}, {"ICREC_SMALL_M": 512}):
-            enc = _make(monkeypatch, r, "f16x3", **env)
-            emb, tok = _run(enc, r["ids"][:t].copy(), r["cu"][: n + 1].copy())
+            enc = make_encoder(monkeypatch, r["w"], r["s"], "f16x3", **env)
+            emb, tok = run(enc, r["ids"][:t].copy(), r["cu"][: n + 1].copy(), return_tokens=True)
             _check(f"first {t} tokens {env}", "f16x3", r, emb, tok, 0, n)
             enc.close()
 
@@ -161,18 +130,15 @@ def test_rounds_plus_remainder(monkeypatch, hidden, kind):
     remainder, which runs through the small-batch kernels on the library's side stream."""
     lens = _batch_lens(400, seed=11)
     cu_all = np.concatenate([[0], np.cumsum(lens)])
-    probe = _make(monkeypatch, _reference(kind, hidden, 2, [4], seed=0), "f16x3")
-    main_t = tail_t = n = 0
-    for n in range(64, 400):  # the first cut whose token count splits into whole rounds + a remainder
-        main_t, tail_t = _split(probe, int(cu_all[n]))
-        if tail_t:
-            break
+    r = _reference(kind, hidden, 2, [4], seed=0)
+    probe = make_encoder(monkeypatch, r["w"], r["s"], "f16x3")
+    n, main_t, tail_t = round_plus_remainder(probe, cu_all, 1, np.inf, first=64)
     probe.close()
     assert tail_t and main_t > 0 and n >= 64, (main_t, tail_t, n)
     r = _reference(kind, hidden, 2, lens[:n], seed=4)
-    enc = _make(monkeypatch, r, "f16x3")
-    assert _split(enc, int(r["cu"][-1])) == (main_t, tail_t)
-    emb, tok = _run(enc, r["ids"], r["cu"])
+    enc = make_encoder(monkeypatch, r["w"], r["s"], "f16x3")
+    assert enc.batch_split(int(r["cu"][-1])) == (main_t, tail_t)
+    emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
     _check(f"rounds {main_t} + remainder {tail_t}", "f16x3", r, emb, tok)
     enc.close()
 
@@ -184,13 +150,13 @@ def test_attention_bucket_edges(monkeypatch, mode, hidden, layers, kind):
     """Ceiling raised to 512: a sequence on each side of every key-tile bucket edge, all in one batch, then each alone
     (a lone sequence may take another bucket's kernel than the same sequence in a batch)."""
     r = _reference(kind, hidden, layers, EDGE_LENS, seed=5)
-    enc = _make(monkeypatch, r, mode, max_seq_length=512)
-    emb, tok = _run(enc, r["ids"], r["cu"])
+    enc = make_encoder(monkeypatch, r["w"], r["s"], mode, max_seq_length=512)
+    emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
     _check("edges mixed", mode, r, emb, tok)
     cu = r["cu"]
     for i, n in enumerate(EDGE_LENS):
         a, b = int(cu[i]), int(cu[i + 1])
-        e1, t1 = _run(enc, r["ids"][a:b].copy(), np.array([0, n], np.int32))
+        e1, t1 = run(enc, r["ids"][a:b].copy(), np.array([0, n], np.int32), return_tokens=True)
         _check(f"length {n} alone", mode, r, e1, t1, i, 1)
     enc.close()
 
@@ -203,7 +169,7 @@ def test_token_output_changes_nothing_and_reads_nothing_stale(monkeypatch, mode,
     import torch
 
     r = _reference("sharp", hidden, layers, MIXED_LENS, seed=2)
-    enc = _make(monkeypatch, r, mode)
+    enc = make_encoder(monkeypatch, r["w"], r["s"], mode)
     ids, cu = torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda()
     mx = int(np.diff(r["cu"]).max())
     plain = enc.encode_packed(ids, cu, mx).cpu().numpy()
@@ -228,7 +194,7 @@ def test_token_output_under_graph_capture(monkeypatch):
     import torch
 
     r = _reference("sharp", 384, 6, MIXED_LENS, seed=2)
-    enc = _make(monkeypatch, r, "f16x3")
+    enc = make_encoder(monkeypatch, r["w"], r["s"], "f16x3")
     ids, cu = torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda()
     n, T, mx = r["cu"].size - 1, int(r["cu"][-1]), int(np.diff(r["cu"]).max())
     emb, tok = enc.encode_packed(ids, cu, mx, return_tokens=True)

@@ -10,6 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from instacart_next_order_recommendation_amd import synthetic as syn
+from tests.encoder_harness import packed
 
 VOCAB = 2048
 WIDTHS = {384: dict(hidden=384, heads=12, intermediate=1536), 768: dict(hidden=768, heads=12, intermediate=3072)}
@@ -35,14 +36,6 @@ def shape(hidden: int, layers: int) -> syn.BertShape:
     return syn.BertShape(vocab_size=VOCAB, layers=layers, **WIDTHS[hidden])
 
 
-def oracle_cfg(s: syn.BertShape):
-    from oracle import oracle
-
-    return oracle.make_cfg(vocab_size=s.vocab_size, hidden=s.hidden, layers=s.layers, heads=s.heads,
-                           intermediate=s.intermediate, max_position=s.max_position, type_vocab=s.type_vocab,
-                           ln_eps=s.ln_eps, n_normalize=s.n_normalize)
-
-
 def weights(kind: str, s: syn.BertShape, seed: int = 17, qk_scale: float | None = None) -> np.ndarray:
     """The weight blob of a set.
 
@@ -65,15 +58,9 @@ def weights(kind: str, s: syn.BertShape, seed: int = 17, qk_scale: float | None 
     return w
 
 
-def packed(lens, seed: int):
-    """Random ids in [0, VOCAB) for sequences of the given lengths -> (ids int32[T], cu int32[n+1])."""
-    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    return np.random.default_rng(seed).integers(0, VOCAB, int(cu[-1])).astype(np.int32), cu
-
-
 def calibration_batch():
     """Lengths 5 / 33 / 128 / 256: what the sharp set's Q/K factor is found on."""
-    return packed([5, 33, 128, 256], seed=1)
+    return packed([5, 33, 128, 256], 1, VOCAB)
 
 
 def logit_stats(w: np.ndarray, s: syn.BertShape, ids, cu):

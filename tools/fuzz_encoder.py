@@ -18,7 +18,7 @@ n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 shape = syn.BertShape()
 w = syn.synthetic_bert_weights(shape, seed=0)
-cfg = o.make_cfg(vocab_size=shape.vocab_size, n_normalize=shape.n_normalize)
+cfg = o.cfg_for(shape)
 o.set_threads(o.usable_cpus())
 encs = {m: DeviceEncoder(w, shape, "cuda:0", gemm_mode=m) for m in ("f16x3", "f32")}
 ref64 = f64.Float64Bert(w, shape)
