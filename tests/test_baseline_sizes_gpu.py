@@ -15,16 +15,10 @@ import numpy as np
 import pytest
 
 from tests.encoder_harness import EMB_TOL, run
+from tests.search_harness import DeviceIndex, assert_ranked_lists, assert_search, oracle
+from tests.search_harness import torch_cuda as cuda  # noqa: F401  (fixture, under this file's name for it)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def cuda():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
 
 
 @pytest.mark.parametrize("mode", ["f16x3", "f32"])
@@ -98,9 +92,6 @@ def test_2m_row_bf16_catalog_vs_oracle(cuda, monkeypatch):
     staged form with row-major planes): Q in {1, 64, 1024}; a sample of queries is checked bit for bit against
     oracle.search(storage="bf16") over the same fp32 input rows."""
     torch = cuda
-    from instacart_next_order_recommendation_amd.search import DeviceIndex
-    from oracle import oracle
-
     n = 2_000_000
     rows = _device_catalog(torch, n, seed=11)
     q_all = torch.nn.functional.normalize(rows[torch.randint(0, n, (1024,), device=rows.device)] +
@@ -116,8 +107,7 @@ def test_2m_row_bf16_catalog_vs_oracle(cuda, monkeypatch):
             idx, sc = ix.search(q_all[:nq], 20)
             got = [s for s in sample if s < nq]
             sel = [sample.index(s) for s in got]
-            np.testing.assert_array_equal(idx[got].cpu().numpy(), want_i[sel])
-            np.testing.assert_array_equal(sc[got].cpu().numpy(), want_s[sel])
+            assert_search((idx[got], sc[got]), (want_i[sel], want_s[sel]))
         ix.close()
     del rows
 
@@ -128,8 +118,6 @@ def test_10m_row_catalog_properties(cuda):
     returned scores are the library's own exact score matrix at the returned rows, and the k-th score is the
     k-th largest of the full score row; the filter path equals the exact bf16 path."""
     torch = cuda
-    from instacart_next_order_recommendation_amd.search import DeviceIndex
-
     n = 10_000_000
     rows = _device_catalog(torch, n, seed=1000)
     q = torch.nn.functional.normalize(rows[torch.randint(0, n, (256,), device=rows.device)] +
@@ -140,14 +128,7 @@ def test_10m_row_catalog_properties(cuda):
     idx, sc = ix.search(q, 20)                      # filter + verify path (Q >= 256)
     idx2, sc2 = ix.search(q, 20)
     assert torch.equal(idx, idx2) and torch.equal(sc, sc2)
-    i_h, s_h = idx.cpu().numpy(), sc.cpu().numpy()
-    assert i_h.min() >= 0 and i_h.max() < n
-    for r in range(256):
-        assert len(set(i_h[r].tolist())) == 20
-        d = np.diff(s_h[r])
-        assert (d <= 0).all()
-        ties = np.nonzero(d == 0)[0]
-        assert all(i_h[r][t] < i_h[r][t + 1] for t in ties)
+    assert_ranked_lists(idx, sc, 0, n, 20)
     # exact streaming / MFMA paths on subsets of the same queries give the same lists
     for nq in (1, 8, 64):
         i_s, s_s = ix.search(q[:nq], 20)

@@ -5,8 +5,11 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+import torch
 
-from tests import encoder_harness
+from tests.search_harness import (DeviceIndex, assert_search, check, full_ranking, merge_topk, n_cu, oracle, search,
+                                  sharded_partial_keys, sorted_exclusions, tie_block_catalog, timed)
+from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,47 +27,9 @@ def _skip_refused(dim, storage):
         pytest.skip("bf16 rows need dim % 64 == 0: refused at creation (test_bf16_width_limit)")
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-def _oracle():
-    from oracle import oracle
-
-    return oracle
-
-
-def _S():
-    from instacart_next_order_recommendation_amd import search
-
-    return search
-
-
 def _rows(n, Q, dim):
     """n scaled down so that one oracle call stays within ORACLE_FMAS."""
     return max(1, min(n, ORACLE_FMAS // (Q * dim)))
-
-
-def _excl(rng, n, Q, must=None, size=40):
-    out = []
-    for i in range(Q):
-        e = set(rng.choice(n, size=int(rng.integers(0, min(n, size) + 1)), replace=False).tolist())
-        if must is not None:
-            e |= set(must[i].tolist())
-        out.append(sorted(e))
-    return out
-
-
-def _check(ix, q, P, k, excl, storage, row_offset=0):
-    wi, ws = _oracle().search(q, P, k, excl, row_offset=row_offset, storage="bf16" if storage.startswith("bf16") else "f32")
-    idx, sc = ix.search(q, k, excl)
-    np.testing.assert_array_equal(idx.cpu().numpy(), wi)
-    np.testing.assert_array_equal(sc.cpu().numpy(), ws)
-    return wi, ws
 
 
 @pytest.mark.parametrize("dim,storage", _pairs(WIDTHS))
@@ -78,11 +43,11 @@ def test_streaming_kernel_over_widths(torch_cuda, dim, storage):
     P = rng.standard_normal((n, dim), dtype=np.float32)
     q = rng.standard_normal((2, dim), dtype=np.float32)
     q[1] = P[n // 2] + 0.1 * q[1]                         # one query with a clear best match
-    ix = _S().DeviceIndex(P, storage=storage, row_offset=5000)
-    top, _ = _oracle().search(q, P, 6, storage=storage)
+    ix = DeviceIndex(P, storage=storage, row_offset=5000)
+    top, _ = oracle.search(q, P, 6, storage=storage)
     for nq, k in [(1, 1), (1, 20), (2, 128), (2, 20)]:
-        excl = _excl(rng, n, nq, must=top[:nq, ::2]) if k != 1 else None
-        _check(ix, q[:nq], P, k, excl, storage, row_offset=5000)
+        excl = sorted_exclusions(rng, n, nq, must=top[:nq, ::2]) if k != 1 else None
+        check(ix, q[:nq], P, k, excl)
     ix.close()
 
 
@@ -96,8 +61,8 @@ def test_mfma_tile_variants_over_widths(torch_cuda, dim, storage):
         n = _rows(n, nq, dim)
         P = rng.standard_normal((n, dim), dtype=np.float32)
         q = rng.standard_normal((nq, dim), dtype=np.float32)
-        ix = _S().DeviceIndex(P, storage=storage, row_offset=nq)
-        _check(ix, q, P, k, _excl(rng, n, nq), storage, row_offset=nq)
+        ix = DeviceIndex(P, storage=storage, row_offset=nq)
+        check(ix, q, P, k, sorted_exclusions(rng, n, nq))
         ix.close()
 
 
@@ -106,9 +71,8 @@ def multi_tile_catalogs():
     """Catalogs sized from the CU count, at widths 64, 256 and 768: at least 6 x n_cu row tiles of 256, so that the
     streaming kernel takes 5 queries too (make_plan), and more tiles than blocks (at most 3 x n_cu), so that blocks
     walk several tiles."""
-    n_cu = encoder_harness.n_cu()
-    n = (6 * n_cu + 27) * 256 + 5
-    assert (n + 255) // 256 >= 6 * n_cu
+    n = (6 * n_cu() + 27) * 256 + 5
+    assert (n + 255) // 256 >= 6 * n_cu()
     out = {}
     for dim in (64, 256, 768):
         rng = np.random.default_rng(dim + 11)
@@ -127,19 +91,17 @@ def test_streaming_kernel_five_queries_multi_tile(torch_cuda, monkeypatch, multi
     for dim, (P, q) in multi_tile_catalogs.items():
         n = P.shape[0]
         rng = np.random.default_rng(dim)
-        top, _ = _oracle().search(q, P, 8, storage=storage)
-        excl = _excl(rng, n, 5, must=top[:, ::3])
+        top, _ = oracle.search(q, P, 8, storage=storage)
+        excl = sorted_exclusions(rng, n, 5, must=top[:, ::3])
         monkeypatch.setenv("ICREC_STREAM_MAX_Q", "8")
-        ix = _S().DeviceIndex(P, storage=storage)
+        ix = DeviceIndex(P, storage=storage)
         monkeypatch.setenv("ICREC_STREAM_MAX_Q", "0")
-        ix_mfma = _S().DeviceIndex(P, storage=storage)
+        ix_mfma = DeviceIndex(P, storage=storage)
         monkeypatch.delenv("ICREC_STREAM_MAX_Q")
-        wi, ws = _check(ix, q, P, 20, excl, storage)
-        i2, s2 = ix_mfma.search(q, 20, excl)
-        np.testing.assert_array_equal(i2.cpu().numpy(), wi)
-        np.testing.assert_array_equal(s2.cpu().numpy(), ws)
-        _check(ix, q[:1], P, 128, excl[:1], storage)
-        _check(ix, q[:2], P, 20, excl[:2], storage)
+        want = check(ix, q, P, 20, excl)
+        assert_search(ix_mfma.search(q, 20, excl), want)
+        check(ix, q[:1], P, 128, excl[:1])
+        check(ix, q[:2], P, 20, excl[:2])
         ix.close(); ix_mfma.close()
 
 
@@ -147,29 +109,6 @@ def test_streaming_kernel_five_queries_multi_tile(torch_cuda, monkeypatch, multi
 def _filter_eps(dim):
     """filter_eps in csrc/search.hip: the verify pass's margin."""
     return max(1e-4, 2 * dim * 2.0 ** -24 + 1e-6)
-
-
-def _timed(fn):
-    """fn() once with the library's launch timers on -> (result, {slot: (avg ms, launches)}); slot 0 = search kernels,
-    4 = the guarded exact pass behind a filter pass (include/icrec.h, icrec_timing_query)."""
-    import torch
-
-    from instacart_next_order_recommendation_amd import _native
-
-    torch.cuda.synchronize()
-    _native.timing_reset()
-    _native.timing_enable(True)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        _native.timing_enable(False)
-    return out, {s: _native.timing_query(s) for s in (0, 4)}
-
-
-def _assert_search(out, want):
-    np.testing.assert_array_equal(out[0].cpu().numpy(), want[0])
-    np.testing.assert_array_equal(out[1].cpu().numpy(), want[1])
 
 
 @pytest.mark.parametrize("dim,base", [(d, b) for d in FILTER_WIDTHS for b in ("f32", "bf16")])
@@ -180,44 +119,38 @@ def test_filter_storage_over_widths(torch_cuda, dim, base):
     - a quarter of the queries next to a block of 300 identical rows and 200 near-ties 1e-6 apart: those lists cannot
       be proven (300 > the k + 12 candidates), the guarded exact pass runs.
     Both bit-exact against the oracle (indices and scores), with exclusions; partial lists + merge too."""
-    S, o = _S(), _oracle()
     rng = np.random.default_rng(dim + 7)
     nq, k = 288, 20
     n = min(65_536, 2 ** 23 // dim)
-    P = rng.standard_normal((n, dim), dtype=np.float32)
-    base_row = rng.standard_normal(dim, dtype=np.float32)
-    dup = rng.choice(n, 300, replace=False)
-    P[dup] = base_row
-    near = rng.choice(np.setdiff1d(np.arange(n), dup), 200, replace=False)
-    P[near] = base_row + 1e-6 * rng.standard_normal((200, dim), dtype=np.float32)
+    P, base_row = tie_block_catalog(rng, n, dim, draw_f32=True)
     q_free = rng.standard_normal((nq, dim), dtype=np.float32)
     b = base_row / np.linalg.norm(base_row)
     q_free -= np.outer(q_free @ b, b).astype(np.float32)      # the tie block scores ~0 for these: never near the top
     q_tie = rng.standard_normal((nq, dim), dtype=np.float32)
     q_tie[: nq // 4] = base_row + 0.05 * q_tie[: nq // 4]
-    ex_free, ex_tie = _excl(rng, n, nq, size=30), _excl(rng, n, nq, size=30)
-    want_free = o.search(q_free, P, k, ex_free, row_offset=100, storage=base)
-    want_tie = o.search(q_tie, P, k, ex_tie, row_offset=100, storage=base)
+    ex_free, ex_tie = sorted_exclusions(rng, n, nq, cap=30), sorted_exclusions(rng, n, nq, cap=30)
+    want_free = oracle.search(q_free, P, k, ex_free, row_offset=100, storage=base)
+    want_tie = oracle.search(q_tie, P, k, ex_tie, row_offset=100, storage=base)
 
-    plain = S.DeviceIndex(P, storage=base, row_offset=100)
+    plain = DeviceIndex(P, storage=base, row_offset=100)
     plain.search(q_free, k, ex_free)                             # first launches out of the timed region
-    out, t = _timed(lambda: plain.search(q_free, k, ex_free))
-    _assert_search(out, want_free)
+    out, t = timed(lambda: plain.search(q_free, k, ex_free))
+    assert_search(out, want_free)
     exact_ms = t[0][0]
     plain.close()
 
-    fx = S.DeviceIndex(P, storage=base + "+filter", row_offset=100)
+    fx = DeviceIndex(P, storage=base + "+filter", row_offset=100)
     fx.search(q_free, k, ex_free)
-    out, t = _timed(lambda: fx.search(q_free, k, ex_free))
-    _assert_search(out, want_free)
+    out, t = timed(lambda: fx.search(q_free, k, ex_free))
+    assert_search(out, want_free)
     fb_ms, n_fb = t[4]
     assert n_fb == 1 and fb_ms < 0.25 * exact_ms, ("the fallback ran on the provable batch", fb_ms, exact_ms)
-    out, t = _timed(lambda: fx.search(q_tie, k, ex_tie))
-    _assert_search(out, want_tie)
+    out, t = timed(lambda: fx.search(q_tie, k, ex_tie))
+    assert_search(out, want_tie)
     fb_ms, n_fb = t[4]
     assert n_fb == 1 and fb_ms > 0.5 * exact_ms, ("the fallback did not run on the tie batch", fb_ms, exact_ms)
     for q, ex, want in ((q_free, ex_free, want_free), (q_tie, ex_tie, want_tie)):
-        _assert_search(S.merge_topk(fx.search_partial(q, k, ex).unsqueeze(0), k), want)
+        assert_search(merge_topk(fx.search_partial(q, k, ex).unsqueeze(0), k), want)
     fx.close()
 
 
@@ -227,7 +160,6 @@ def test_filter_margin_follows_the_width(torch_cuda, dim):
     vectors): 1e-4 at 512, 1.2e-4 at 1,024, 4.9e-4 at 4,096.  Rows built so that every query's 20 best rows score 0.9 and
     the next ones 0.9 - 3e-4: the candidate list is provable under a 1e-4 or 1.2e-4 margin (no fallback) and not under
     4.9e-4 (the guarded exact pass runs).  Bit-exact against the oracle either way."""
-    S, o = _S(), _oracle()
     rng = np.random.default_rng(dim + 5)
     nq, k, gap = 288, 20, 3e-4
     n = 2 ** 23 // dim
@@ -242,20 +174,20 @@ def test_filter_margin_follows_the_width(torch_cuda, dim):
     P = (a[:, None] * d[None, :] + np.sqrt(1 - a * a)[:, None] * g).astype(np.float32)
     P = P[rng.permutation(n)]
     q = np.repeat(d[None, :].astype(np.float32), nq, axis=0)
-    wi, ws = o.search(q[:1], P, k)
+    wi, ws = oracle.search(q[:1], P, k)
     want = (np.repeat(wi, nq, 0), np.repeat(ws, nq, 0))
     assert 0.9 - ws[0, -1] < 1e-5                              # the construction holds in fp32
 
-    plain = S.DeviceIndex(P)
+    plain = DeviceIndex(P)
     plain.search(q, k)
-    out, t = _timed(lambda: plain.search(q, k))
-    _assert_search(out, want)
+    out, t = timed(lambda: plain.search(q, k))
+    assert_search(out, want)
     exact_ms = t[0][0]
     plain.close()
-    fx = S.DeviceIndex(P, storage="f32+filter")
+    fx = DeviceIndex(P, storage="f32+filter")
     fx.search(q, k)
-    out, t = _timed(lambda: fx.search(q, k))
-    _assert_search(out, want)
+    out, t = timed(lambda: fx.search(q, k))
+    assert_search(out, want)
     fb_ms, n_fb = t[4]
     assert n_fb == 1
     if _filter_eps(dim) > gap:
@@ -270,39 +202,30 @@ def test_partial_merge_rank_all_export_over_widths(torch_cuda, dim, storage):
     """Shard-local partial lists of three uneven shards + icrec_merge_topk (streaming and MFMA batches), the complete
     ranking (icrec_rank_all, duplicate rows included), export() and normalize_rows - all bit-exact."""
     _skip_refused(dim, storage)
-    torch = torch_cuda
-    o, S = _oracle(), _S()
     rng = np.random.default_rng(dim + 3)
     n = 3000
     P = rng.standard_normal((n, dim), dtype=np.float32) * np.float32(3.0)
     P[17] = P[3]
     P[n - 1] = P[3]
     q = rng.standard_normal((40, dim), dtype=np.float32)
-    np.testing.assert_array_equal(S.normalize_rows(torch.from_numpy(P).cuda()).cpu().numpy(), o.normalize_rows(P))
-    ix = S.DeviceIndex(P, storage=storage, row_offset=1000)
-    rows = o.normalize_rows(P)
+    np.testing.assert_array_equal(search.normalize_rows(torch.from_numpy(P).cuda()).cpu().numpy(), oracle.normalize_rows(P))
+    ix = DeviceIndex(P, storage=storage, row_offset=1000)
+    rows = oracle.normalize_rows(P)
     if storage == "bf16":
-        rows = o.round_bf16(rows)
+        rows = oracle.round_bf16(rows)
     np.testing.assert_array_equal(ix.export().cpu().numpy(), rows)
     # complete ranking: score desc, row asc
     got = ix.rank_all(torch.from_numpy(q[:3]).cuda()).cpu().numpy()
-    sc = o.scores(o.normalize_rows(q[:3]), rows)
+    sc = oracle.scores(oracle.normalize_rows(q[:3]), rows)
     for i in range(3):
-        np.testing.assert_array_equal(got[i] - 1000, np.lexsort((np.arange(n), -sc[i].astype(np.float64))))
+        np.testing.assert_array_equal(got[i] - 1000, full_ranking(sc[i]))
     ix.close()
     # partial lists of uneven shards + merge == the oracle on the whole catalog
     bounds = [0, 700, 701, n]
     for nq, k in [(2, 20), (40, 128)]:
-        excl = _excl(rng, n, nq)
-        wi, ws = o.search(q[:nq], P, k, excl, storage=storage)
-        keys = []
-        for a, b in zip(bounds[:-1], bounds[1:]):
-            shard = S.DeviceIndex(P[a:b], storage=storage, row_offset=a)
-            keys.append(shard.search_partial(q[:nq], k, [[r - a for r in e if a <= r < b] for e in excl]))
-            shard.close()
-        gi, gs = S.merge_topk(torch.stack(keys), k)
-        np.testing.assert_array_equal(gi.cpu().numpy(), wi)
-        np.testing.assert_array_equal(gs.cpu().numpy(), ws)
+        excl = sorted_exclusions(rng, n, nq)
+        keys = sharded_partial_keys(P, q[:nq], k, excl, bounds, storage=storage)
+        assert_search(merge_topk(keys, k), oracle.search(q[:nq], P, k, excl, storage=storage))
 
 
 def test_bf16_width_limit(torch_cuda):
@@ -310,13 +233,12 @@ def test_bf16_width_limit(torch_cuda):
     creation (every real embedding width - 384, 512, 768, 1,024 - is one), while fp32 rows take any multiple of 32."""
     from instacart_next_order_recommendation_amd._native import IcrecError
 
-    S = _S()
     for dim in (32, 96, 160, 416):
         P = np.ones((300, dim), np.float32)
         for storage in ("bf16", "bf16+filter"):
             with pytest.raises(IcrecError):
-                S.DeviceIndex(P, storage=storage)
-        S.DeviceIndex(P, storage="f32").close()
+                DeviceIndex(P, storage=storage)
+        DeviceIndex(P, storage="f32").close()
     for dim in (0, 16, 48, 4128):
         with pytest.raises((IcrecError, ValueError)):
-            S.DeviceIndex(np.ones((4, dim), np.float32))
+            DeviceIndex(np.ones((4, dim), np.float32))

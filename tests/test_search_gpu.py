@@ -3,48 +3,26 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+import torch
 
 from tests.conftest import excl_lists
+from tests.search_harness import (DeviceIndex, assert_ranked_lists, assert_search, bench_catalog, bench_queries, check,
+                                  distinct_exclusions, full_ranking, merge_topk, oracle, search, sharded_partial_keys,
+                                  synthetic as syn, tie_block_catalog, timed)
+from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return torch
-
-
-def _oracle():
-    from oracle import oracle
-
-    return oracle
-
-
-def _syn():
-    from instacart_next_order_recommendation_amd import synthetic
-
-    return synthetic
-
-
-def _search_mod():
-    from instacart_next_order_recommendation_amd import search
-
-    return search
-
-
 def test_normalize_rows_bit_exact(torch_cuda, golden_search):
-    torch = torch_cuda
     x = golden_search["P"]
-    got = _search_mod().normalize_rows(torch.from_numpy(x).cuda()).cpu().numpy()
-    np.testing.assert_array_equal(got, _oracle().normalize_rows(x))
+    got = search.normalize_rows(torch.from_numpy(x).cuda()).cpu().numpy()
+    np.testing.assert_array_equal(got, oracle.normalize_rows(x))
 
 
 def test_index_holds_normalized_rows(torch_cuda, golden_search):
-    ix = _search_mod().DeviceIndex(golden_search["P"])
-    np.testing.assert_array_equal(ix.export().cpu().numpy(), _oracle().normalize_rows(golden_search["P"]))
+    ix = DeviceIndex(golden_search["P"])
+    np.testing.assert_array_equal(ix.export().cpu().numpy(), oracle.normalize_rows(golden_search["P"]))
 
 
 @pytest.mark.parametrize("nq", [1, 16])
@@ -52,7 +30,7 @@ def test_scores_bit_exact_vs_oracle(torch_cuda, golden_search, nq):
     """Every cosine score equals the oracle's k-ascending fmaf chain bit for bit, and
     sentence_transformers.util.cos_sim's torch restatement within 1e-4 (north_star)."""
     g = golden_search
-    ix = _search_mod().DeviceIndex(g["P"])
+    ix = DeviceIndex(g["P"])
     got = ix.scores(g["q"][:nq]).cpu().numpy()
     np.testing.assert_array_equal(got, g["oracle_scores"][:nq])
     assert np.abs(got - g["torch_scores"][:nq]).max() < 1e-4
@@ -62,10 +40,8 @@ def test_topk_golden_with_exclusions(torch_cuda, golden_search):
     g = golden_search
     k = int(g["k"])
     excl = excl_lists(g["excl_flat"], g["excl_off"])
-    ix = _search_mod().DeviceIndex(g["P"])
-    idx, sc = ix.search(g["q"], k, excl)
-    np.testing.assert_array_equal(idx.cpu().numpy(), g["oracle_idx"])
-    np.testing.assert_array_equal(sc.cpu().numpy(), g["oracle_topk_scores"])
+    idx, sc = DeviceIndex(g["P"]).search(g["q"], k, excl)
+    assert_search((idx, sc), (g["oracle_idx"], g["oracle_topk_scores"]))
     # and against the torch restatement of the reference wherever torch's own order is unambiguous
     amb = g["torch_ambiguous"]
     np.testing.assert_array_equal(idx.cpu().numpy()[~amb], g["torch_idx"][~amb])
@@ -73,21 +49,16 @@ def test_topk_golden_with_exclusions(torch_cuda, golden_search):
 
 def test_tie_policy(torch_cuda, golden_search):
     g = golden_search
-    ix = _search_mod().DeviceIndex(g["P_tie"])
-    idx, sc = ix.search(g["q"][:4], int(g["k"]))
-    np.testing.assert_array_equal(idx.cpu().numpy(), g["oracle_tie_idx"])
-    np.testing.assert_array_equal(sc.cpu().numpy(), g["oracle_tie_scores"])
+    ix = DeviceIndex(g["P_tie"])
+    assert_search(ix.search(g["q"][:4], int(g["k"])), (g["oracle_tie_idx"], g["oracle_tie_scores"]))
 
 
 def test_full_catalog_golden(torch_cuda, golden_search_full):
     g = golden_search_full
-    syn = _syn()
     P = syn.synthetic_embeddings(49688, 384, seed=int(g["P_seed"]))
     q = syn.synthetic_embeddings(8, 384, seed=int(g["q_seed"]))
-    ix = _search_mod().DeviceIndex(P)
-    idx, sc = ix.search(q, int(g["k"]))
-    np.testing.assert_array_equal(idx.cpu().numpy(), g["oracle_idx"])
-    np.testing.assert_array_equal(sc.cpu().numpy(), g["oracle_topk_scores"])
+    ix = DeviceIndex(P)
+    assert_search(ix.search(q, int(g["k"])), (g["oracle_idx"], g["oracle_topk_scores"]))
     # single query (the /recommend shape) gives the same row
     idx1, sc1 = ix.search(q[3], int(g["k"]))
     np.testing.assert_array_equal(idx1.cpu().numpy()[0], g["oracle_idx"][3])
@@ -100,29 +71,20 @@ def test_shapes_vs_oracle(torch_cuda, nq, k, n):
     rng = np.random.default_rng(nq * 1000 + k)
     P = rng.standard_normal((n, 384)).astype(np.float32)
     q = rng.standard_normal((nq, 384)).astype(np.float32)
-    excl = [rng.choice(n, size=rng.integers(0, min(n, 40)), replace=False).tolist() for _ in range(nq)]
-    want_i, want_s = _oracle().search(q, P, k, excl)
-    ix = _search_mod().DeviceIndex(P)
-    idx, sc = ix.search(q, k, excl)
-    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
-    np.testing.assert_array_equal(sc.cpu().numpy(), want_s)
+    check(DeviceIndex(P), q, P, k, distinct_exclusions(rng, n, nq))
 
 
 def test_edge_cases(torch_cuda):
     rng = np.random.default_rng(0)
     P = rng.standard_normal((7, 384)).astype(np.float32)
     q = rng.standard_normal((2, 384)).astype(np.float32)
-    o = _oracle()
-    ix = _search_mod().DeviceIndex(P)
+    ix = DeviceIndex(P)
     for k, excl in [(10, None), (5, [list(range(7)), [0]]), (3, [[], [1, 2, 3]])]:
-        idx, sc = ix.search(q, k, excl)
-        wi, ws = o.search(q, P, k, excl)
-        np.testing.assert_array_equal(idx.cpu().numpy(), wi)
-        np.testing.assert_array_equal(sc.cpu().numpy(), ws)
+        check(ix, q, P, k, excl)
     z = np.zeros((1, 384), np.float32)  # zero query: all scores 0, ties resolved by row order
     idx, sc = ix.search(z, 3)
     assert idx.cpu().numpy()[0].tolist() == [0, 1, 2] and (sc.cpu().numpy() == 0).all()
-    ix_off = _search_mod().DeviceIndex(P, row_offset=1000)
+    ix_off = DeviceIndex(P, row_offset=1000)
     idx, _ = ix_off.search(q, 3)
     assert idx.min().item() >= 1000
 
@@ -131,55 +93,35 @@ def test_bad_arguments_raise(torch_cuda):
     from instacart_next_order_recommendation_amd._native import IcrecError
 
     P = np.ones((4, 384), np.float32)
-    ix = _search_mod().DeviceIndex(P)
+    ix = DeviceIndex(P)
     with pytest.raises(IcrecError):
         ix.search(P[:1], 0)
     with pytest.raises(IcrecError):
         ix.search(P[:1], 129)
     with pytest.raises(IcrecError):
-        _search_mod().DeviceIndex(np.ones((4, 100), np.float32))  # dim not a multiple of 32
+        DeviceIndex(np.ones((4, 100), np.float32))  # dim not a multiple of 32
 
 
 def test_sharded_merge_equals_unsharded(torch_cuda, golden_search):
     """Per-shard partial lists + k-way merge == single-index result (the multi-GPU exactness claim)."""
-    torch = torch_cuda
     g = golden_search
-    S = _search_mod()
     k = int(g["k"])
-    P, q = g["P"], g["q"]
     excl = excl_lists(g["excl_flat"], g["excl_off"])
     bounds = [0, 100, 356, 700, 1024]  # uneven shards
-    keys = []
-    for a, b in zip(bounds[:-1], bounds[1:]):
-        shard = S.DeviceIndex(P[a:b], row_offset=a)
-        local = [[r - a for r in e if a <= r < b] for e in excl]
-        keys.append(shard.search_partial(q, k, local))
-    idx, sc = S.merge_topk(torch.stack(keys), k)
-    np.testing.assert_array_equal(idx.cpu().numpy(), g["oracle_idx"])
-    np.testing.assert_array_equal(sc.cpu().numpy(), g["oracle_topk_scores"])
+    keys = sharded_partial_keys(g["P"], g["q"], k, excl, bounds)
+    assert_search(merge_topk(keys, k), (g["oracle_idx"], g["oracle_topk_scores"]))
 
 
 def test_large_batch_properties(torch_cuda):
     """BASELINE config 3 size (1024 x 49,688): size-independent properties — sorted output,
     scores reproduce from the returned rows, k-th score bounds every unreturned row on a sample."""
-    torch = torch_cuda
-    syn = _syn()
-    P = syn.synthetic_embeddings(49688, 384, seed=1)
-    q = syn.synthetic_embeddings(1024, 384, seed=3)
-    ix = _search_mod().DeviceIndex(P)
+    P, q = bench_catalog(), bench_queries(1024, 3)
+    ix = DeviceIndex(P)
     idx, sc = ix.search(q, 20)
-    idx_h, sc_h = idx.cpu().numpy(), sc.cpu().numpy()
-    assert (idx_h >= 0).all() and (idx_h < 49688).all()
-    assert all(len(set(r.tolist())) == 20 for r in idx_h)
-    d = np.diff(sc_h, axis=1)
-    assert (d <= 0).all()
-    tie = d == 0
-    assert (np.diff(idx_h, axis=1)[tie] > 0).all()
+    assert_ranked_lists(idx, sc, 0, 49688, 20)
     # exact check of a sample of queries against the oracle
     sample = [0, 1, 511, 777, 1023]
-    wi, ws = _oracle().search(q[sample], P, 20)
-    np.testing.assert_array_equal(idx_h[sample], wi)
-    np.testing.assert_array_equal(sc_h[sample], ws)
+    assert_search((idx[sample], sc[sample]), oracle.search(q[sample], P, 20))
     # idempotence: same call, same bits
     idx2, sc2 = ix.search(q, 20)
     assert torch.equal(idx, idx2) and torch.equal(sc, sc2)
@@ -189,13 +131,11 @@ def test_large_batch_properties(torch_cuda):
 def test_bf16_index_holds_rounded_rows(torch_cuda, golden_search):
     """ICREC_ROWS_BF16: normalise in fp32, then round to bfloat16 (RNE) — bit-identical to the oracle
     and to torch's own fp32 -> bf16 conversion of the same normalised rows."""
-    torch = torch_cuda
-    o = _oracle()
-    ix = _search_mod().DeviceIndex(golden_search["P"], storage="bf16")
+    ix = DeviceIndex(golden_search["P"], storage="bf16")
     got = ix.export().cpu().numpy()
-    want = o.round_bf16(o.normalize_rows(golden_search["P"]))
+    want = oracle.round_bf16(oracle.normalize_rows(golden_search["P"]))
     np.testing.assert_array_equal(got, want)
-    t = torch.from_numpy(o.normalize_rows(golden_search["P"])).to(torch.bfloat16).float().numpy()
+    t = torch.from_numpy(oracle.normalize_rows(golden_search["P"])).to(torch.bfloat16).float().numpy()
     np.testing.assert_array_equal(got, t)
 
 
@@ -207,36 +147,26 @@ def test_bf16_rows_search_vs_oracle(torch_cuda, nq, k, n):
     rng = np.random.default_rng(nq * 977 + k)
     P = rng.standard_normal((n, 384)).astype(np.float32)
     q = rng.standard_normal((nq, 384)).astype(np.float32)
-    excl = [rng.choice(n, size=rng.integers(0, min(n, 40)), replace=False).tolist() for _ in range(nq)]
-    want_i, want_s = _oracle().search(q, P, k, excl, storage="bf16")
-    ix = _search_mod().DeviceIndex(P, storage="bf16")
-    idx, sc = ix.search(q, k, excl)
-    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
-    np.testing.assert_array_equal(sc.cpu().numpy(), want_s)
+    ix = DeviceIndex(P, storage="bf16")
+    check(ix, q, P, k, distinct_exclusions(rng, n, nq))
     # the full score matrix too
-    o = _oracle()
     full = ix.scores(q).cpu().numpy()
-    np.testing.assert_array_equal(full, o.scores(o.normalize_rows(q), o.round_bf16(o.normalize_rows(P))))
+    np.testing.assert_array_equal(full, oracle.scores(oracle.normalize_rows(q), oracle.round_bf16(oracle.normalize_rows(P))))
     # and it is a faithful approximation of the fp32 catalog: cosine within bf16 rounding of the rows
-    ref = o.scores(o.normalize_rows(q), o.normalize_rows(P))
+    ref = oracle.scores(oracle.normalize_rows(q), oracle.normalize_rows(P))
     assert np.abs(full - ref).max() < 2e-3
 
 
 def test_bf16_rows_full_catalog_sample(torch_cuda):
     """49,688 rows x 1,024 queries in bf16 storage: sorted, unique, and a sample of queries exact vs the oracle."""
-    syn = _syn()
-    P = syn.synthetic_embeddings(49688, 384, seed=1)
-    q = syn.synthetic_embeddings(1024, 384, seed=3)
-    ix = _search_mod().DeviceIndex(P, storage="bf16")
+    P, q = bench_catalog(), bench_queries(1024, 3)
+    ix = DeviceIndex(P, storage="bf16")
     idx, sc = ix.search(q, 20)
-    idx_h, sc_h = idx.cpu().numpy(), sc.cpu().numpy()
-    assert (np.diff(sc_h, axis=1) <= 0).all() and all(len(set(r.tolist())) == 20 for r in idx_h)
+    assert_ranked_lists(idx, sc, 0, 49688, 20)
     sample = [0, 5, 512, 1023]
-    wi, ws = _oracle().search(q[sample], P, 20, storage="bf16")
-    np.testing.assert_array_equal(idx_h[sample], wi)
-    np.testing.assert_array_equal(sc_h[sample], ws)
+    assert_search((idx[sample], sc[sample]), oracle.search(q[sample], P, 20, storage="bf16"))
     with pytest.raises(ValueError):
-        _search_mod().DeviceIndex(P[:4], storage="fp8")
+        DeviceIndex(P[:4], storage="fp8")
 
 
 # ---------------------------------------------------------------- small-batch streaming kernel (Q <= 8)
@@ -259,25 +189,16 @@ def test_stream_kernel_multi_tile_chunks(torch_cuda, big_clustered, storage, nq,
     n = 400_000
     P, qall = big_clustered
     q = qall[:nq]
-    o = _oracle()
-    top_i, _ = o.search(q, P, 8, storage=storage)
+    top_i, _ = oracle.search(q, P, 8, storage=storage)
     rng = np.random.default_rng(nq + k)
     excl = [sorted(set(top_i[i, ::2].tolist()) | set(rng.choice(n, 30, replace=False).tolist())) for i in range(nq)]
     excl[0] = []  # one query without exclusions
-    want_i, want_s = o.search(q, P, k, excl, storage=storage)
-    ix = _search_mod().DeviceIndex(P, storage=storage)
-    idx, sc = ix.search(q, k, excl)
-    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
-    np.testing.assert_array_equal(sc.cpu().numpy(), want_s)
-    # shard-local lists + merge agree too (row_offset, > 256 lists through the 16-lists-per-lane merge)
-    keys = ix.search_partial(q, k, excl)
-    idx2, sc2 = _search_mod().merge_topk(keys.unsqueeze(0), k)
-    np.testing.assert_array_equal(idx2.cpu().numpy(), want_i)
+    # the search itself, and its partial lists + merge (> 256 lists through the 16-lists-per-lane merge)
+    check(DeviceIndex(P, storage=storage), q, P, k, excl, partial=True)
 
 
 def test_merge_many_lists(torch_cuda):
     """icrec_merge_topk with 700 lists (the streaming kernel's chunk count exceeds 256)."""
-    torch = torch_cuda
     rng = np.random.default_rng(3)
     n_lists, Q, k = 700, 3, 20
     sc = rng.standard_normal((n_lists, Q, k)).astype(np.float32)
@@ -286,10 +207,7 @@ def test_merge_many_lists(torch_cuda):
     u = sc.view(np.uint32).astype(np.uint64)
     u = np.where(u & 0x80000000, ~u & 0xFFFFFFFF, u | 0x80000000)
     keys = (u << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - idx.astype(np.uint64))
-    got_i, got_s = _search_mod().merge_topk(torch.from_numpy(keys.view(np.int64)).cuda(), k)
-    want_i, want_s = _oracle().merge(idx, sc)
-    np.testing.assert_array_equal(got_i.cpu().numpy(), want_i)
-    np.testing.assert_array_equal(got_s.cpu().numpy(), want_s)
+    assert_search(merge_topk(torch.from_numpy(keys.view(np.int64)).cuda(), k), oracle.merge(idx, sc))
 
 
 # ---------------------------------------------------------------- filter + verify (ICREC_ROWS_F32_FILTER)
@@ -304,16 +222,7 @@ def test_filter_index_is_bit_identical_to_exact(torch_cuda, monkeypatch, residen
     rng = np.random.default_rng(nq * 31 + k)
     P = rng.standard_normal((n, 384)).astype(np.float32)
     q = rng.standard_normal((nq, 384)).astype(np.float32)
-    excl = [rng.choice(n, size=rng.integers(0, min(n, 40)), replace=False).tolist() for _ in range(nq)]
-    want_i, want_s = _oracle().search(q, P, k, excl)
-    ix = _search_mod().DeviceIndex(P, storage="f32+filter")
-    idx, sc = ix.search(q, k, excl)
-    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
-    np.testing.assert_array_equal(sc.cpu().numpy(), want_s)
-    keys = ix.search_partial(q, k, excl)
-    idx2, sc2 = _search_mod().merge_topk(keys.unsqueeze(0), k)
-    np.testing.assert_array_equal(idx2.cpu().numpy(), want_i)
-    np.testing.assert_array_equal(sc2.cpu().numpy(), want_s)
+    check(DeviceIndex(P, storage="f32+filter"), q, P, k, distinct_exclusions(rng, n, nq), partial=True)
 
 
 @pytest.mark.parametrize("order", ["ascending", "random"])
@@ -324,7 +233,6 @@ def test_resident_filter_long_blocks_ascending_scores(torch_cuda, order):
     worst case of the selection.  Result: bit-identical to the exact index on all queries, to the oracle on a sample;
     with exclusion lists that knock out some of the very best rows.  (Written in round 4 for a barrier-free form of the
     selection that was measured and dropped, profiles/r04_search_epoch_mode_ab.txt; kept as the adversarial case.)"""
-    torch = torch_cuda
     rng = np.random.default_rng(17)
     n, nq, k = 49_688, 4096, 20
     d = rng.standard_normal(384).astype(np.float32)
@@ -337,20 +245,18 @@ def test_resident_filter_long_blocks_ascending_scores(torch_cuda, order):
         t = rng.permutation(t)
     P = u[None, :] + t[:, None] * d[None, :] + 0.02 * rng.standard_normal((n, 384)).astype(np.float32)
     q = d[None, :] + 0.02 * rng.standard_normal((nq, 384)).astype(np.float32)
-    excl = [rng.choice(n, size=int(rng.integers(0, 30)), replace=False).tolist() if i % 3 == 0 else [] for i in range(nq)]
+    excl = distinct_exclusions(rng, n, nq, cap=30, every=3)
     if order == "ascending":  # also knock out a few of the very best rows of some queries
         for i in range(0, nq, 7):
             excl[i] = sorted(set(excl[i]) | {n - 1, n - 2, n - 5})
     Pd, qd = torch.from_numpy(P).cuda(), torch.from_numpy(q).cuda()
-    fi = _search_mod().DeviceIndex(Pd, storage="f32+filter")
-    ei = _search_mod().DeviceIndex(Pd, storage="f32")
+    fi = DeviceIndex(Pd, storage="f32+filter")
+    ei = DeviceIndex(Pd, storage="f32")
     idx, sc = fi.search(qd, k, excl)
     xi, xs = ei.search(qd, k, excl)
     assert torch.equal(idx, xi) and torch.equal(sc, xs)
     sample = [0, 1, 7, 63, 64, 2047, 4095]
-    wi, ws = _oracle().search(q[sample], P, k, [excl[i] for i in sample])
-    np.testing.assert_array_equal(idx[sample].cpu().numpy(), wi)
-    np.testing.assert_array_equal(sc[sample].cpu().numpy(), ws)
+    assert_search((idx[sample], sc[sample]), oracle.search(q[sample], P, k, [excl[i] for i in sample]))
     fi.close(); ei.close()
 
 
@@ -360,69 +266,44 @@ def test_filter_falls_back_when_it_cannot_prove_the_result(torch_cuda):
     pass must deliver the oracle's answer (lower row first among equals)."""
     rng = np.random.default_rng(9)
     n, nq, k = 6000, 288, 20
-    P = rng.standard_normal((n, 384)).astype(np.float32)
-    base = rng.standard_normal(384).astype(np.float32)
-    dup = rng.choice(n, 300, replace=False)
-    P[dup] = base
-    near = rng.choice(np.setdiff1d(np.arange(n), dup), 200, replace=False)
-    P[near] = base + 1e-6 * rng.standard_normal((200, 384)).astype(np.float32)
+    P, base = tie_block_catalog(rng, n, 384)
     q = base[None, :] + 0.05 * rng.standard_normal((nq, 384)).astype(np.float32)
-    want_i, want_s = _oracle().search(q, P, k)
-    ix = _search_mod().DeviceIndex(P, storage="f32+filter")
-    idx, sc = ix.search(q, k)
-    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
-    np.testing.assert_array_equal(sc.cpu().numpy(), want_s)
+    check(DeviceIndex(P, storage="f32+filter"), q, P, k)
     # a small catalog where k exceeds the admissible rows (lists not full -> proven complete, pads)
     Ps = P[:30]
-    excl = [list(range(0, 30, 2))] * 288
-    wi, ws = _oracle().search(q, Ps, 20, excl)
-    i2, s2 = _search_mod().DeviceIndex(Ps, storage="f32+filter").search(q, 20, excl)
-    np.testing.assert_array_equal(i2.cpu().numpy(), wi)
-    np.testing.assert_array_equal(s2.cpu().numpy(), ws)
+    check(DeviceIndex(Ps, storage="f32+filter"), q, Ps, 20, [list(range(0, 30, 2))] * 288)
 
 
 def test_filter_full_catalog_batch(torch_cuda):
     """BASELINE configs[2] size through the filter path: 1,024 x 49,688, all lists equal to the exact index's —
     and proven by the verify pass alone: the guarded exact pass (timer slot 4) exits at once, whereas the
     adversarial catalog of the previous test makes it run."""
-    torch = torch_cuda
-    from instacart_next_order_recommendation_amd import _native
-
-    syn = _syn()
-    P = syn.synthetic_embeddings(49688, 384, seed=1)
-    q = syn.synthetic_embeddings(1024, 384, seed=3)
-    S = _search_mod()
-    exact = S.DeviceIndex(P)
+    P, q = bench_catalog(), bench_queries(1024, 3)
+    exact = DeviceIndex(P)
     ie, se = exact.search(q, 20)
-    fx = S.DeviceIndex(P, storage="f32+filter")
+    fx = DeviceIndex(P, storage="f32+filter")
     fx.search(q, 20)
-    torch.cuda.synchronize()
-    _native.timing_reset(); _native.timing_enable(True)
-    fi, fs = fx.search(q, 20)
-    exact.search(q, 20)
-    torch.cuda.synchronize()
-    _native.timing_enable(False)
+
+    def filter_then_exact():
+        out = fx.search(q, 20)
+        exact.search(q, 20)
+        return out
+
+    (fi, fs), t = timed(filter_then_exact)
     assert torch.equal(ie, fi) and torch.equal(se, fs)
     sample = [0, 255, 256, 777, 1023]   # and against the oracle on THIS index, not only against the exact HIP path
-    wi, ws = _oracle().search(q[sample], P, 20)
-    np.testing.assert_array_equal(fi[sample].cpu().numpy(), wi)
-    np.testing.assert_array_equal(fs[sample].cpu().numpy(), ws)
-    fallback_ms, n_fb = _native.timing_query(4)
-    exact_ms, _ = _native.timing_query(0)
+    assert_search((fi[sample], fs[sample]), oracle.search(q[sample], P, 20))
+    (fallback_ms, n_fb), (exact_ms, _) = t[4], t[0]
     assert n_fb == 1 and fallback_ms < 0.1 * exact_ms, (fallback_ms, exact_ms)  # exited at once: nothing was flagged
     # the adversarial case: the fallback really runs
     rng = np.random.default_rng(9)
     Pd = rng.standard_normal((6000, 384)).astype(np.float32)
     Pd[rng.choice(6000, 300, replace=False)] = Pd[0]
     qd = Pd[0][None, :] + 0.05 * rng.standard_normal((288, 384)).astype(np.float32)
-    fd = S.DeviceIndex(Pd, storage="f32+filter")
+    fd = DeviceIndex(Pd, storage="f32+filter")
     fd.search(qd, 20)
-    torch.cuda.synchronize()
-    _native.timing_reset(); _native.timing_enable(True)
-    fd.search(qd, 20)
-    torch.cuda.synchronize()
-    _native.timing_enable(False)
-    fb2, _ = _native.timing_query(4)
+    _, t = timed(lambda: fd.search(qd, 20))
+    fb2, _ = t[4]
     assert fb2 > 3 * fallback_ms, (fb2, fallback_ms)
 
 
@@ -438,24 +319,15 @@ def test_bf16_filter_index_is_bit_identical_to_bf16_exact(torch_cuda, monkeypatc
     P[rng.choice(n, 200, replace=False)] = P[1]  # 200 identical rows: some queries cannot be proven
     q = rng.standard_normal((nq, 384)).astype(np.float32)
     q[: nq // 4] = P[1] + 0.05 * q[: nq // 4]
-    excl = [rng.choice(n, size=rng.integers(0, 30), replace=False).tolist() for _ in range(nq)]
-    want_i, want_s = _oracle().search(q, P, k, excl, storage="bf16")
-    ix = _search_mod().DeviceIndex(P, storage="bf16+filter")
-    idx, sc = ix.search(q, k, excl)
-    np.testing.assert_array_equal(idx.cpu().numpy(), want_i)
-    np.testing.assert_array_equal(sc.cpu().numpy(), want_s)
-    np.testing.assert_array_equal(ix.export().cpu().numpy(), _oracle().round_bf16(_oracle().normalize_rows(P)))
+    ix = DeviceIndex(P, storage="bf16+filter")
+    check(ix, q, P, k, distinct_exclusions(rng, n, nq, cap=30))
+    np.testing.assert_array_equal(ix.export().cpu().numpy(), oracle.round_bf16(oracle.normalize_rows(P)))
 
 
 @pytest.mark.parametrize("n,nq,storage", [(49_688, 5, "f32"), (1000, 3, "f32"), (8192, 2, "f32"), (20_001, 4, "bf16"), (7, 2, "f32")])
 def test_rank_all_full_order_vs_oracle(torch_cuda, n, nq, storage):
     """icrec_rank_all = the complete argsort(descending) of every score row under the library's total order:
     bit-exact scores (oracle) sorted by (score desc, row asc), duplicate rows included."""
-    torch = torch_cuda
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.search import DeviceIndex
-    from oracle import oracle
-
     P = syn.synthetic_embeddings(n, 384, seed=31)
     if n > 100:
         P[17] = P[3]          # exact ties
@@ -469,6 +341,5 @@ def test_rank_all_full_order_vs_oracle(torch_cuda, n, nq, storage):
         Pn = oracle.round_bf16(Pn)
     sc = oracle.scores(oracle.normalize_rows(q), Pn)
     for i in range(nq):
-        want = np.lexsort((np.arange(n), -sc[i].astype(np.float64)))  # score desc, row asc
-        np.testing.assert_array_equal(got[i] - 1000, want)
+        np.testing.assert_array_equal(got[i] - 1000, full_ranking(sc[i]))
     ix.close()

@@ -10,6 +10,12 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+import torch
+
+from tests.search_harness import (DeviceIndex, HipShardBackend, NativeComm, ShardedSearch, assert_ranked_lists,
+                                  assert_search, bench_catalog, bench_queries, exclusions_to_shard_csr,
+                                  local_exclusions, merge_topk, oracle, redrawn_exclusions, shard_bounds,
+                                  sharded_partial_keys, synthetic as syn)
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parents[1]
@@ -43,9 +49,6 @@ def _torchrun(args, env_extra, timeout=600):
 
 
 def test_two_ranks_real_kernels_equal_unsharded(tmp_path):
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from oracle import oracle
-
     script = tmp_path / "worker.py"
     script.write_text(WORKER)
     r = _torchrun([str(script)], {"ICREC_ROOT": str(ROOT), "ICREC_OUT": str(tmp_path)})
@@ -89,21 +92,13 @@ def test_bench_multi_rank_flow_rehearsal(tmp_path):
     assert ((rows >= 0) & (rows < 49_688) & (rows == np.rint(rows))).all()
     assert np.abs(np.linalg.norm(emb, axis=1) - 1).max() < 1e-5
     assert not np.array_equal(emb[:64], emb[64:])   # rank 1's contexts come from another seed
-    from instacart_next_order_recommendation_amd import synthetic as syn
-
-    P = syn.synthetic_embeddings(49_688, 384, seed=1).astype(np.float64)  # bench.py's catalog: unit rows
+    P = bench_catalog().astype(np.float64)  # bench.py's catalog: unit rows
     np.testing.assert_allclose(sc, np.einsum("qd,qkd->qk", emb.astype(np.float64), P[rows.astype(np.int64)]), atol=1e-5)
 
 
 def test_native_rccl_world1_equals_plain_search():
     """icrec_comm_init (a real ncclCommInitRank on one rank) + icrec_search_sharded: both ncclAllGathers run
     on the stream and the result is bit-equal to icrec_search and to the oracle, exclusions included."""
-    import torch
-
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.sharded import HipShardBackend, NativeComm, ShardedSearch
-    from oracle import oracle
-
     dev = torch.device("cuda:0")
     P = syn.synthetic_embeddings(6211, 384, seed=1)   # one shard of configs[3] (49,688 / 8 rows)
     q = syn.synthetic_embeddings(512, 384, seed=2)    # 4,096 / 8 queries
@@ -117,16 +112,12 @@ def test_native_rccl_world1_equals_plain_search():
         idx, sc = ss.search(qd, 20, ex)
         pi, ps = be.index.search(qd, 20, ex)
         assert torch.equal(idx, pi) and torch.equal(sc, ps)
-        wi, ws = oracle.search(q, P, 20, ex)
-        np.testing.assert_array_equal(idx.cpu().numpy(), wi)
-        np.testing.assert_array_equal(sc.cpu().numpy(), ws)
+        assert_search((idx, sc), oracle.search(q, P, 20, ex))
     # a shard with a row offset: global rows come back
     be2 = HipShardBackend(torch.from_numpy(P[1000:3000]).to(dev), 1000, dev)
     ss2 = ShardedSearch(be2, 1000, 3000, comm=comm)
-    idx2, sc2 = ss2.search(qd[:64], 20, [[1500, 2999, 5]] * 64)
     wi2, ws2 = oracle.search(q[:64], P[1000:3000], 20, [[500, 1999]] * 64)
-    np.testing.assert_array_equal(idx2.cpu().numpy(), wi2 + 1000)
-    np.testing.assert_array_equal(sc2.cpu().numpy(), ws2)
+    assert_search(ss2.search(qd[:64], 20, [[1500, 2999, 5]] * 64), (wi2 + 1000, ws2))
     comm.close()
 
 
@@ -134,12 +125,6 @@ def test_native_per_rank_exclusions_world1():
     """icrec_search_sharded_excl through a real one-rank RCCL communicator: the exclusions arrive as GLOBAL rows of
     this rank's own queries, are all-gathered (offsets + padded ids), cut to the shard and turned into the local
     CSR on the device - same bits as the replicated form and as the oracle, with a row offset."""
-    import torch
-
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.sharded import HipShardBackend, NativeComm, ShardedSearch
-    from oracle import oracle
-
     dev = torch.device("cuda:0")
     P = syn.synthetic_embeddings(6211, 384, seed=1)
     q = syn.synthetic_embeddings(512, 384, seed=2)
@@ -149,13 +134,11 @@ def test_native_per_rank_exclusions_world1():
     ss = ShardedSearch(be, lo, hi, comm=comm)
     qd = torch.from_numpy(q).to(dev)
     rng = np.random.default_rng(5)
-    excl = [sorted(set(rng.integers(0, 6211, size=int(rng.integers(0, 40))).tolist())) if i % 4 else [] for i in range(512)]
+    excl = redrawn_exclusions(rng, 6211, 512, cap=40, none_every=4)
     idx, sc = ss.search(qd, 20, exclude_local=excl, excl_cap=512 * 40)
     ridx, rsc = ss.search(qd, 20, exclude_global=excl)
     assert torch.equal(idx, ridx) and torch.equal(sc, rsc)
-    wi, ws = oracle.search(q, P[lo:hi], 20, [[r - lo for r in e if lo <= r < hi] for e in excl], row_offset=lo)
-    np.testing.assert_array_equal(idx.cpu().numpy(), wi)
-    np.testing.assert_array_equal(sc.cpu().numpy(), ws)
+    assert_search((idx, sc), oracle.search(q, P[lo:hi], 20, local_exclusions(excl, lo, hi), row_offset=lo))
     # every query excludes its own best hit: the exchange really reaches the kernel
     pi, ps = ss.search(qd, 20)
     best = pi[:, 0].cpu().tolist()
@@ -172,16 +155,8 @@ def test_configs3_sizes_4096_queries():
     """BASELINE configs[3] at its own sizes on one GPU: (a) 4,096 queries over the whole 49,688-row catalog (filter
     index, 8-query oracle sample, bit-equal to the exact index); (b) the 4,096 gathered queries over ONE
     6,211-row shard (rows 6,211 .. 12,421) through icrec_search_sharded with a one-rank RCCL communicator."""
-    import torch
-
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.search import DeviceIndex
-    from instacart_next_order_recommendation_amd.sharded import HipShardBackend, NativeComm, ShardedSearch, shard_bounds
-    from oracle import oracle
-
     dev = torch.device("cuda:0")
-    P = syn.synthetic_embeddings(49_688, 384, seed=1)
-    q = syn.synthetic_embeddings(4096, 384, seed=2)
+    P, q = bench_catalog(), bench_queries(4096, 2)
     qd = torch.from_numpy(q).to(dev)
     Pd = torch.from_numpy(P).to(dev)
     fi = DeviceIndex(Pd, dev, storage="f32+filter")
@@ -190,9 +165,7 @@ def test_configs3_sizes_4096_queries():
     xi, xs = ei.search(qd, 20)
     assert torch.equal(idx, xi) and torch.equal(sc, xs)
     sample = [0, 1, 511, 512, 2047, 2048, 4094, 4095]
-    wi, ws = oracle.search(q[sample], P, 20)
-    np.testing.assert_array_equal(idx[sample].cpu().numpy(), wi)
-    np.testing.assert_array_equal(sc[sample].cpu().numpy(), ws)
+    assert_search((idx[sample], sc[sample]), oracle.search(q[sample], P, 20))
     b = shard_bounds(49_688, 8)
     assert b[1] - b[0] == 6211
     lo, hi = b[1], b[2]
@@ -200,14 +173,9 @@ def test_configs3_sizes_4096_queries():
     be = HipShardBackend(Pd[lo:hi], lo, dev, storage="f32+filter")
     ss = ShardedSearch(be, lo, hi, comm=comm)
     si, s_sc = ss.search(qd, 20)
-    wi2, ws2 = oracle.search(q[sample], P[lo:hi], 20, row_offset=lo)
-    np.testing.assert_array_equal(si[sample].cpu().numpy(), wi2)
-    np.testing.assert_array_equal(s_sc[sample].cpu().numpy(), ws2)
+    assert_search((si[sample], s_sc[sample]), oracle.search(q[sample], P[lo:hi], 20, row_offset=lo))
     # shard-level property at full size: each list is sorted (score desc, row asc), rows inside the shard
-    s_np, i_np = s_sc.cpu().numpy(), si.cpu().numpy()
-    assert ((i_np >= lo) & (i_np < hi)).all()
-    d = np.diff(s_np, axis=1)
-    assert (d <= 0).all() and ((d < 0) | (np.diff(i_np, axis=1) > 0)).all()
+    assert_ranked_lists(si, s_sc, lo, hi, 20)
     comm.close()
     fi.close(); ei.close()
 
@@ -234,13 +202,6 @@ def test_exclusion_exchange_layout_world8_on_one_gpu():
     ranks x 512 local queries, shard 1 of the 49,688-row catalog), lists incl. empty and cap-full ranks, against a
     numpy restatement; then MALFORMED offsets (negative, beyond cap, decreasing — ADVICE r3): never out of bounds,
     equal to the restatement's sanitised reading; and the CSR drives icrec_search to the oracle's result."""
-    import torch
-
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.search import DeviceIndex
-    from instacart_next_order_recommendation_amd.sharded import exclusions_to_shard_csr, shard_bounds
-    from oracle import oracle
-
     dev = torch.device("cuda:0")
     W, n_local, cap = 8, 512, 512 * 12
     b = shard_bounds(49_688, W)
@@ -272,16 +233,14 @@ def test_exclusion_exchange_layout_world8_on_one_gpu():
     np.testing.assert_array_equal(got_off.cpu().numpy(), want_off)
     np.testing.assert_array_equal(got_idx.cpu().numpy()[:want_off[-1]], want_idx)
     # the CSR means what the search expects: gathered queries against the shard, a sample against the oracle
-    P = syn.synthetic_embeddings(49_688, 384, seed=1)
-    q = syn.synthetic_embeddings(W * n_local, 384, seed=2)
+    P, q = bench_catalog(), bench_queries(W * n_local, 2)
     ix = DeviceIndex(torch.from_numpy(P[lo:hi]).to(dev), dev, row_offset=lo)
     idx = torch.empty((W * n_local, 20), dtype=torch.int64, device=dev)
     sc = torch.empty((W * n_local, 20), dtype=torch.float32, device=dev)
     ix.search_into(torch.from_numpy(q).to(dev), 20, got_idx, got_off, idx, sc)
     sample = [0, 1, 511, 512, 513, 1535, 1536, 2560, 2561, 3071, 4095]
-    wi, ws = oracle.search(q[sample], P[lo:hi], 20, [[v - lo for v in lists[g] if lo <= v < hi] for g in sample], row_offset=lo)
-    np.testing.assert_array_equal(idx[sample].cpu().numpy(), wi)
-    np.testing.assert_array_equal(sc[sample].cpu().numpy(), ws)
+    want = oracle.search(q[sample], P[lo:hi], 20, local_exclusions([lists[g] for g in sample], lo, hi), row_offset=lo)
+    assert_search((idx[sample], sc[sample]), want)
     ix.close()
     # malformed offsets from "another rank": overlapping full segments, negatives, beyond cap, decreasing runs
     bad = off_all.copy()
@@ -303,36 +262,21 @@ def test_gathered_partial_keys_layout_world8_on_one_gpu():
     ncclAllGather of the per-rank [4096, 20] key blocks lays down) -> icrec_merge_topk == the unsharded index, bit
     for bit on all 4,096 queries, and == the oracle on a sample.  The first and last shards have 6,211 rows each
     (49,688 = 8 x 6,211)."""
-    import torch
-
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.search import DeviceIndex, merge_topk
-    from instacart_next_order_recommendation_amd.sharded import shard_bounds
-    from oracle import oracle
-
     dev = torch.device("cuda:0")
     W, Q, k = 8, 4096, 20
-    P = syn.synthetic_embeddings(49_688, 384, seed=1)
-    q = syn.synthetic_embeddings(Q, 384, seed=2)
+    P, q = bench_catalog(), bench_queries(Q, 2)
     Pd, qd = torch.from_numpy(P).to(dev), torch.from_numpy(q).to(dev)
     b = shard_bounds(49_688, W)
     assert all(b[r + 1] - b[r] == 6211 for r in range(W))
     rng = np.random.default_rng(3)
-    excl = [sorted(set(rng.integers(0, 49_688, size=int(rng.integers(0, 30))).tolist())) if g % 3 else [] for g in range(Q)]
-    keys_all = torch.empty((W, Q, k), dtype=torch.int64, device=dev)
-    for r in range(W):
-        lo, hi = b[r], b[r + 1]
-        shard = DeviceIndex(Pd[lo:hi], dev, row_offset=lo, storage="f32+filter" if r % 2 else "f32")
-        keys_all[r] = shard.search_partial(qd, k, [[v - lo for v in e if lo <= v < hi] for e in excl])
-        shard.close()
+    excl = redrawn_exclusions(rng, 49_688, Q, cap=30, none_every=3)
+    keys_all = sharded_partial_keys(Pd, qd, k, excl, b, storage=lambda r: "f32+filter" if r % 2 else "f32")
     idx, sc = merge_topk(keys_all, k)
     full = DeviceIndex(Pd, dev)
     fi, fs = full.search(qd, k, excl)
     assert torch.equal(idx, fi) and torch.equal(sc, fs)
     sample = [0, 1, 511, 512, 2047, 2048, 4094, 4095]
-    wi, ws = oracle.search(q[sample], P, k, [excl[g] for g in sample])
-    np.testing.assert_array_equal(idx[sample].cpu().numpy(), wi)
-    np.testing.assert_array_equal(sc[sample].cpu().numpy(), ws)
+    assert_search((idx[sample], sc[sample]), oracle.search(q[sample], P, k, [excl[g] for g in sample]))
     # a rank-major slip would not survive: swapping two ranks' blocks changes nothing (the merge is order-free in the
     # rank axis), but reading the buffer query-major does
     wrong, _ = merge_topk(keys_all.permute(1, 0, 2).contiguous().view(W, Q, k), k)
