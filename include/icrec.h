@@ -111,7 +111,23 @@ ICREC_API int icrec_encoder_destroy(icrec_encoder* enc);
  * whatever the ceiling. */
 ICREC_API int icrec_encoder_set_max_seqlen(icrec_encoder* enc, int32_t max_seqlen);
 
-/* Scratch bytes needed to encode `total_tokens` tokens in `n_seqs` sequences. */
+/* How the last hidden states become one row per sequence (sentence-transformers' Pooling module). */
+#define ICREC_POOL_MEAN 0   /* sentence-transformers Pooling(mean): the default after icrec_encoder_create */
+#define ICREC_POOL_CLS  1   /* Pooling(cls): the last hidden state of each sequence's first token */
+
+/* Choose the pooling mode of `enc`; any other value returns ICREC_EINVAL.  Same contract as
+ * icrec_encoder_set_max_seqlen: set it before the first icrec_encode, never while another call on `enc` is running.
+ * The weights are untouched, and cfg.n_normalize applies after pooling in either mode: in CLS mode out_dev[s] is the
+ * last hidden state of token cu_seqlens[s], normalised n_normalize times; tokens_out_dev does not depend on the mode.
+ * In f16x3 mode a CLS encoder computes its last layer for the first token of each sequence only (the layer's K and V
+ * still cover every token) unless tokens_out_dev asks for every row; the embedding has the same bits either way.
+ * ICREC_CLS_PRUNE=0 in the environment at icrec_encoder_create forces the full last layer. */
+ICREC_API int icrec_encoder_set_pooling(icrec_encoder* enc, int32_t mode);
+/* The pooling mode of `enc`; -1 for a NULL handle. */
+ICREC_API int32_t icrec_encoder_pooling(const icrec_encoder* enc);
+
+/* Scratch bytes needed to encode `total_tokens` tokens in `n_seqs` sequences.  Depends on the pooling mode (a CLS
+ * encoder adds room for `n_seqs` compact rows): ask after icrec_encoder_set_pooling. */
 ICREC_API size_t icrec_encode_workspace_bytes(const icrec_encoder* enc,
                                     int64_t total_tokens, int32_t n_seqs);
 

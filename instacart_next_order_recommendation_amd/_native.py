@@ -18,10 +18,13 @@ ICREC_MAX_SEQLEN = 512
 COMM_ID_BYTES = 128
 GEMM_F32, GEMM_F16X3 = 0, 1
 GEMM_MODES = {"f32": GEMM_F32, "f16x3": GEMM_F16X3}
+POOL_MEAN, POOL_CLS = 0, 1
+POOLING_MODES = {"mean": POOL_MEAN, "cls": POOL_CLS}
 
 #: every symbol include/icrec.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "icrec_encoder_weight_count", "icrec_encoder_create", "icrec_encoder_destroy", "icrec_encoder_set_max_seqlen",
+    "icrec_encoder_set_pooling", "icrec_encoder_pooling",
     "icrec_encode_workspace_bytes", "icrec_encode", "icrec_encode_ex", "icrec_encode_batch_split",
     "icrec_index_create", "icrec_index_create_ex", "icrec_index_destroy", "icrec_index_rows", "icrec_index_storage",
     "icrec_index_export", "icrec_index_dim", "icrec_index_device",
@@ -88,6 +91,8 @@ def lib() -> C.CDLL:
         "icrec_encoder_create": (C.c_int, [vp, sz, C.POINTER(BertCfg), C.c_int, C.POINTER(vp)]),
         "icrec_encoder_destroy": (C.c_int, [vp]),
         "icrec_encoder_set_max_seqlen": (C.c_int, [vp, i32]),
+        "icrec_encoder_set_pooling": (C.c_int, [vp, i32]),
+        "icrec_encoder_pooling": (i32, [vp]),
         "icrec_encode_workspace_bytes": (sz, [vp, i64, i32]),
         "icrec_encode": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, vp, sz, vp]),
         "icrec_encode_ex": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, vp, vp, sz, vp]),

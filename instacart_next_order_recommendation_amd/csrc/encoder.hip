@@ -403,10 +403,13 @@ constexpr int att_k_swz(int D, int row) { return D == 32 ? (row >> 2) & 3 : row 
 constexpr int att_x3_wgs(int D, int NKT) { return D != 32 ? 1 : NKT >= 6 ? 4 : NKT == 4 ? 3 : 1; }
 
 // Output: the context as f16 hi/lo planes (`ch` / `cl`).  order: seq_order_kernel's dispatch order, or nullptr.
+// nqb: the query blocks to compute, from block 0 - NKT for all of them; 1 for the last layer of a CLS-pooled encoder,
+// which reads each sequence's first row only: every wave still stages K / V and meets every barrier, only wave 0 runs
+// the score / softmax / P.V loop and stores its tile, the very bits a full launch gives those rows.
 template <int D, int NKT>  // NKT waves, one per 32-row query block
 __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_kernel(
     const float* __restrict__ qkv, const int32_t* __restrict__ cu, int heads, int H, float scale_log2e,
-    _Float16* __restrict__ ch, _Float16* __restrict__ cl, const int32_t* __restrict__ order, int nlo) {
+    _Float16* __restrict__ ch, _Float16* __restrict__ cl, const int32_t* __restrict__ order, int nlo, int nqb) {
     // Single-accumulator form of the split (wt_gemm.h): every operand is carried as hi/lo f16 planes of 16 x (Q, K, V)
     // or 1024 p (the probabilities), the three products of a k-step accumulate into ONE fp32 tile, and the power-of-two
     // scales are folded into constants: S' = 256 S, O' = 16384 sum_k p_k V_k, l' = 1024 sum_k p_k, O = O' / (16 l').
@@ -446,7 +449,7 @@ __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_ker
     if (nkt > NKT || nkt <= nlo) return;  // another bucket's sequence
     const int ld = 3 * H;
     const int r = lane & 31, h = lane >> 5, qb = wave;
-    const bool active = qb < nkt;  // wave-uniform; idle waves still take part in the barriers
+    const bool active = qb < nkt && qb < nqb;  // wave-uniform; idle waves still take part in the barriers
     half8 qh[D / 16], ql[D / 16];  // B operand of S^T: this lane's query row, dims 16 ks + 8 h .. +7
     {
         int qr = qb * 32 + r;
@@ -694,20 +697,42 @@ __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_ker
     }
 }
 
-// ---------------------------------------------------------------- mean pooling + L2 normalise
-// sentence_transformers Pooling(mean): sum_t h_t / clamp(count, 1e-9); then n_norm times
-// x / max(|x|_2, 1e-12) (Normalize module, normalize_embeddings=True).  One workgroup of
+// ---------------------------------------------------------------- pooling + L2 normalise
+// sentence_transformers Pooling(mean): sum_t h_t / clamp(count, 1e-9), or Pooling(cls): h of the sequence's first
+// token; then n_norm times x / max(|x|_2, 1e-12) (Normalize module, normalize_embeddings=True).  One workgroup of
 // H threads per sequence; norm in oracle order by wave 0.
+enum PoolRows { POOL_ROWS_MEAN, POOL_ROWS_CLS, POOL_ROWS_CLS_COMPACT };  // COMPACT: row s IS sequence s's first token
+
 template <int H, bool PLANES>
 __global__ __launch_bounds__(H) void pool_norm_kernel(const float* __restrict__ x, const _Float16* __restrict__ xh,
                                                       const _Float16* __restrict__ xl, const int32_t* __restrict__ cu,
-                                                      int n_norm, float* __restrict__ out) {
+                                                      int n_norm, float* __restrict__ out, int rows) {
     // PLANES (f16x3 mode): the hidden state is its two planes, h_t = (float(hi) + float(lo)) / 16 exactly
     auto at = [&](size_t idx) { return PLANES ? ((float)xh[idx] + (float)xl[idx]) * (1.0f / WT_SA) : x[idx]; };
     __shared__ float v[H];
     __shared__ float den_s;
     const int s = blockIdx.x, i = threadIdx.x;
+    auto normalize = [&](float val) {  // (the branches that lead here are uniform over the workgroup)
+        for (int rep = 0; rep < n_norm; ++rep) {
+            v[i] = val;
+            __syncthreads();
+            if (i < 64) {
+                float a = 0.0f;
+#pragma unroll
+                for (int j = 0; j < H / 64; ++j) a = fmaf(v[i + 64 * j], v[i + 64 * j], a);
+                const float nrm = sqrtf(wave_sum_f32(a));
+                if (i == 0) den_s = nrm > 1e-12f ? nrm : 1e-12f;
+            }
+            __syncthreads();
+            val = val / den_s;
+            __syncthreads();
+        }
+        out[(size_t)s * H + i] = val;
+    };
+    auto cls_pool = [&](int row) { normalize(at((size_t)row * H + i)); };
+    if (rows == POOL_ROWS_CLS_COMPACT) return cls_pool(s);
     const int t0 = cu[s], t1 = cu[s + 1];
+    if (rows == POOL_ROWS_CLS) return cls_pool(t0);
     float acc = 0.0f;
     int t = t0;
     for (; t + 8 <= t1; t += 8) {  // 8 independent loads in flight, summed in ascending token order
@@ -720,22 +745,7 @@ __global__ __launch_bounds__(H) void pool_norm_kernel(const float* __restrict__ 
     for (; t < t1; ++t) acc = acc + at((size_t)t * H + i);
     float cnt = (float)(t1 - t0);
     cnt = cnt < 1e-9f ? 1e-9f : cnt;
-    float val = acc / cnt;
-    for (int rep = 0; rep < n_norm; ++rep) {
-        v[i] = val;
-        __syncthreads();
-        if (i < 64) {
-            float a = 0.0f;
-#pragma unroll
-            for (int j = 0; j < H / 64; ++j) a = fmaf(v[i + 64 * j], v[i + 64 * j], a);
-            const float nrm = sqrtf(wave_sum_f32(a));
-            if (i == 0) den_s = nrm > 1e-12f ? nrm : 1e-12f;
-        }
-        __syncthreads();
-        val = val / den_s;
-        __syncthreads();
-    }
-    out[(size_t)s * H + i] = val;
+    normalize(acc / cnt);
 }
 
 // The last hidden state as fp32 rows (icrec_encode_ex's tokens_out): the very values pool_norm_kernel sums, read the
@@ -757,6 +767,23 @@ __global__ __launch_bounds__(256) void tokens_out_kernel(const float* __restrict
     *reinterpret_cast<f32x4*>(out + 4 * i) = v;
 }
 
+// CLS pooling, pruned last layer: the context planes and the residual (x) planes of each sequence's first token, rows
+// cu[s], -> compact [n_seqs, H] planes.  One thread per 8 features (16 bytes of a plane); h8 = H / 8.
+__global__ __launch_bounds__(256) void gather_cls_rows_kernel(const _Float16* __restrict__ ch, const _Float16* __restrict__ cl,
+                                                              const _Float16* __restrict__ xh, const _Float16* __restrict__ xl,
+                                                              const int32_t* __restrict__ cu, int n_seqs, int h8,
+                                                              _Float16* __restrict__ cch, _Float16* __restrict__ ccl,
+                                                              _Float16* __restrict__ cxh, _Float16* __restrict__ cxl) {
+    const int id = blockIdx.x * 256 + threadIdx.x;  // (n_seqs * h8 < 2^31: a workspace for 2^31 / 96 sequences exceeds HBM)
+    const int s = id / h8;
+    if (s >= n_seqs) return;
+    const size_t from = ((size_t)cu[s] * h8 + id % h8) * 8, to = (size_t)id * 8;
+    *reinterpret_cast<u32x4*>(cch + to) = *reinterpret_cast<const u32x4*>(ch + from);
+    *reinterpret_cast<u32x4*>(ccl + to) = *reinterpret_cast<const u32x4*>(cl + from);
+    *reinterpret_cast<u32x4*>(cxh + to) = *reinterpret_cast<const u32x4*>(xh + from);
+    *reinterpret_cast<u32x4*>(cxl + to) = *reinterpret_cast<const u32x4*>(xl + from);
+}
+
 // ---------------------------------------------------------------- host side
 constexpr int HID = 384;     // all-MiniLM width: 32-dim heads, the fused layer kernels
 constexpr int HID_BASE = 768;  // BERT-base width: 64-dim heads, the unfused chain
@@ -771,6 +798,7 @@ struct Encoder {
     int device = 0;
     int n_cu = 256;
     int max_seqlen = 256;       // longest sequence icrec_encode accepts (icrec_encoder_set_max_seqlen)
+    int pooling = ICREC_POOL_MEAN;  // icrec_encoder_set_pooling
     float* blob = nullptr;      // the uploaded weight blob
     float* extra = nullptr;     // repacked Wqkv / bqkv
     _Float16* planes = nullptr; // packed weight fragments (F16X3)
@@ -781,7 +809,9 @@ struct Encoder {
     //   ICREC_FUSE=0         the UNFUSED reference chain for batches: slab-ring QKV, attention-out GEMM + LayerNorm,
     //                        FFN-up, FFN-down + LayerNorm as separate launches in natural sequence order (same bits)
     //   ICREC_SIDE_STREAM=0  every kernel on the caller's stream (no side stream for the batch remainder / short buckets)
-    bool fuse = true, side_stream = true;
+    //   ICREC_CLS_PRUNE=0    a CLS-pooled f16x3 encoder runs its last layer over every token, like a mean-pooled one,
+    //                        instead of over each sequence's first token only (same bits)
+    bool fuse = true, side_stream = true, cls_prune = true;
     //   ICREC_SMALL_M=n      token count up to which a call takes the latency-form kernels (32-token x 64-feature
     //                        workgroups, every GEMM a launch of its own) instead of the layer kernel (one 64-token workgroup
     //                        per CU).  Round 4: 3,584 - measured crossover ~4,000 tokens (tools/small_m_sweep.py: 897 tokens
@@ -837,13 +867,14 @@ static size_t weight_count(const icrec_bert_cfg* c) {
 struct EncWs {
     size_t x, xs, qkv, ctx, t1, h, total;
 };
-static EncWs enc_ws(const icrec_bert_cfg& c, int64_t T) {
+// post_only: the regions the post-attention chain of T rows works in (no fp32 x, no QKV rows)
+static EncWs enc_ws(const icrec_bert_cfg& c, int64_t T, bool post_only = false) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     EncWs w;
     size_t o = 0;
-    w.x = o;   o += al((size_t)T * c.hidden * 4);
+    w.x = o;   o += post_only ? 0 : al((size_t)T * c.hidden * 4);
     w.xs = o;  o += al((size_t)T * c.hidden * 4);        // x as f16 hi/lo planes (F16X3)
-    w.qkv = o; o += al((size_t)T * 3 * c.hidden * 4);
+    w.qkv = o; o += post_only ? 0 : al((size_t)T * 3 * c.hidden * 4);
     w.ctx = o; o += al((size_t)T * c.hidden * 4);        // fp32 ctx, or its two f16 planes
     w.t1 = o;  o += al((size_t)T * c.hidden * 4);
     w.h = o;   o += al((size_t)T * c.intermediate * 4);  // fp32 h, or its two f16 planes
@@ -855,7 +886,20 @@ static EncWs enc_ws(const icrec_bert_cfg& c, int64_t T) {
 struct EncBufs {
     float *x, *qkv, *ctx, *t1, *h;
     _Float16 *xh, *xl, *ch, *cl, *hh, *hl;
+    EncBufs(char* base, const EncWs& w, const icrec_bert_cfg& c, size_t T)
+        : x(reinterpret_cast<float*>(base + w.x)), qkv(reinterpret_cast<float*>(base + w.qkv)),
+          ctx(reinterpret_cast<float*>(base + w.ctx)), t1(reinterpret_cast<float*>(base + w.t1)),
+          h(reinterpret_cast<float*>(base + w.h)), xh(reinterpret_cast<_Float16*>(base + w.xs)), xl(xh + T * c.hidden),
+          ch(reinterpret_cast<_Float16*>(ctx)), cl(ch + T * c.hidden), hh(reinterpret_cast<_Float16*>(h)),
+          hl(hh + T * c.intermediate) {}
 };
+
+// A CLS-pooled f16x3 encoder reads row cu[s] of the last hidden state and nothing else: its last layer runs attention for
+// query block 0 of each (sequence, head) and the post-attention chain over n_seqs compact rows (encode_x3), which take
+// their scratch from the caller's workspace behind the call's own regions.
+static bool cls_prunes(const Encoder* e) {
+    return e->pooling == ICREC_POOL_CLS && e->cls_prune && e->cfg.gemm_mode == ICREC_GEMM_F16X3;
+}
 
 typedef TileCfg<2, 2, 2, 2> GemmBig;  // 128 x 128 output tile, 4 waves
 constexpr long long SMALL_M_MAX = 1 << 20;  // ICREC_SMALL_M above this: every call of up to 2^20 tokens takes the latency form
@@ -918,9 +962,10 @@ constexpr int ATT_LO[ATT_N] = {9, 1, 2, 3, 5, 7, 5}, ATT_HI[ATT_N] = {16, 1, 2, 
 // Launch, in AttBucket order, the buckets in `mask` (bits 1 << AttBucket) that the call needs: for a batch every bucket
 // that can occur for max_seqlen (one whose workgroups all exit costs a few microseconds), else the one that holds it.
 // X3: the f16x3 kernel, context out as planes (attention_x3_kernel); otherwise exact fp32 rows (attention_kernel).
+// block0_only (X3): query block 0 of every (sequence, head) alone - the pruned last layer of a CLS-pooled encoder.
 template <bool X3>
 static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBufs& b, const int32_t* cu, int n_seqs,
-                             int max_seqlen, const int32_t* order, hipStream_t st) {
+                             int max_seqlen, const int32_t* order, hipStream_t st, bool block0_only = false) {
     const int nkt_max = (max_seqlen + 31) / 32;
     const int dh = c.hidden / c.heads;  // 32 or 64 (icrec_encoder_create)
     const bool single = n_seqs == 1, split_5_8 = X3 && !single && dh == 32;
@@ -938,7 +983,7 @@ static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBu
                 {attention_x3_kernel<64, 16>, attention_x3_kernel<64, 1>, attention_x3_kernel<64, 2>,
                  attention_x3_kernel<64, 4>, nullptr, nullptr, attention_x3_kernel<64, 8>}};
             hipLaunchKernelGGL(kern[dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ch, b.cl, order,
-                               ATT_LO[k] - 1);
+                               ATT_LO[k] - 1, block0_only ? 1 : ATT_HI[k]);
         } else {
             static const decltype(&attention_kernel<32, 1>) kern[2][ATT_N] = {
                 {attention_kernel<32, 16>, attention_kernel<32, 1>, attention_kernel<32, 2>, attention_kernel<32, 4>,
@@ -993,6 +1038,8 @@ int icrec_encoder_create(const float* weights_host, size_t n_floats, const icrec
         e->small_m = env_knob("ICREC_SMALL_M", e->small_m, SMALL_M_MAX);
         e->tail_m = env_knob("ICREC_TAIL_M", e->tail_m, 64LL * e->n_cu - 1);
         e->side_stream = !(side_env && side_env[0] == '0');
+        const char* prune_env = getenv("ICREC_CLS_PRUNE");
+        e->cls_prune = !(prune_env && prune_env[0] == '0');
     }
     const size_t H = cfg->hidden, I = cfg->intermediate;
     const size_t mat_per_layer = 3 * H * H + H * H + I * H + H * I;
@@ -1072,10 +1119,28 @@ int icrec_encoder_set_max_seqlen(icrec_encoder* h, int32_t max_seqlen) {
     return ICREC_OK;
 }
 
+int icrec_encoder_set_pooling(icrec_encoder* h, int32_t mode) {
+    Encoder* e = reinterpret_cast<Encoder*>(h);
+    ICREC_REQUIRE(e, "icrec_encoder_set_pooling: NULL encoder");
+    ICREC_REQUIRE(mode == ICREC_POOL_MEAN || mode == ICREC_POOL_CLS, "icrec_encoder_set_pooling: mode must be ICREC_POOL_MEAN (0) or ICREC_POOL_CLS (1) (got %d)", mode);
+    e->pooling = mode;
+    return ICREC_OK;
+}
+
+int32_t icrec_encoder_pooling(const icrec_encoder* h) {
+    const Encoder* e = reinterpret_cast<const Encoder*>(h);
+    return e ? e->pooling : -1;
+}
+
+// The call's own regions, then (cls_prunes) the compact rows' of the pruned last layer.
+static size_t workspace_bytes(const Encoder* e, int64_t T, int n_seqs) {
+    return enc_ws(e->cfg, T).total + (cls_prunes(e) ? enc_ws(e->cfg, n_seqs, true).total : 0);
+}
+
 size_t icrec_encode_workspace_bytes(const icrec_encoder* h, int64_t total_tokens, int32_t n_seqs) {
     const Encoder* e = reinterpret_cast<const Encoder*>(h);
     if (!e || total_tokens < 1 || n_seqs < 1) return 0;
-    return enc_ws(e->cfg, total_tokens).total;
+    return workspace_bytes(e, total_tokens, n_seqs);
 }
 
 // How icrec_encode splits a batch of T tokens (f16x3 mode): [0, T - tail) through the batch kernels in whole rounds of
@@ -1132,8 +1197,10 @@ struct Range {
     bool ffn_ln_to_next(int l, int layers) const { return fold && l + 1 < layers; }  // to the next QKV's prologue
 };
 
-static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_seqs, int T, int max_seqlen,
-                     const int32_t* order, hipStream_t st) {
+// cls: the compact rows' regions when the last layer is pruned to each sequence's first token (cls_prunes), else nullptr.
+// The last hidden state is then rows [0, n_seqs) of cls->xh / cls->xl and b's x planes stay one layer behind.
+static int encode_x3(Encoder* e, const EncBufs& b, const EncBufs* cls, const int32_t* cu_dev, int n_seqs, int T,
+                     int max_seqlen, const int32_t* order, hipStream_t st) {
     const icrec_bert_cfg& c = e->cfg;
     const int H = c.hidden, I = c.intermediate;
     const bool base = H == HID_BASE;
@@ -1174,7 +1241,7 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
             launch_wt_linear<0>(xhr, xlr, r.n, H, L.Wqkv_p, 3 * H, L.bqkv, qkvr, nullptr, nullptr, r.st, r.small);
         }
     };
-    auto post_stage = [&](const Range& r, int l) {
+    auto post_stage = [&](const Range& r, int l, const EncBufs& b) {  // (b: the call's regions, or the compact rows')
         const LayerW& L = e->layers[l];
         float* const t1r = b.t1 + (size_t)r.r0 * H;
         _Float16 *const xhr = b.xh + (size_t)r.r0 * H, *const xlr = b.xl + (size_t)r.r0 * H;
@@ -1213,6 +1280,7 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
 
     if (tail_on_side) ICREC_HIP(link(sd, st, sd->side));  // the side stream starts behind the embeddings
     for (int l = 0; l < c.layers; ++l) {
+        const bool pruned = cls && l == c.layers - 1;
         if (T_tail && tail.launches_qkv(l)) qkv_stage(tail, l);
         if (main.launches_qkv(l)) qkv_stage(main, l);
         if (tail_on_side) ICREC_HIP(link(sd, sd->side, st));
@@ -1222,16 +1290,27 @@ static int encode_x3(Encoder* e, const EncBufs& b, const int32_t* cu_dev, int n_
             // that bucket goes first, on the caller's stream, ahead of the side stream's)
             ICREC_HIP(link(sd, st, sd->side));
             const unsigned side_buckets = 1u << ATT_1 | 1u << ATT_2 | 1u << ATT_3_4 | 1u << ATT_7_8;
-            launch_attention<true>(1u << ATT_9_16, c, b, cu_dev, n_seqs, max_seqlen, order, st);
-            launch_attention<true>(side_buckets, c, b, cu_dev, n_seqs, max_seqlen, order, sd->side);
-            launch_attention<true>(1u << ATT_5_6, c, b, cu_dev, n_seqs, max_seqlen, order, st);
+            launch_attention<true>(1u << ATT_9_16, c, b, cu_dev, n_seqs, max_seqlen, order, st, pruned);
+            launch_attention<true>(side_buckets, c, b, cu_dev, n_seqs, max_seqlen, order, sd->side, pruned);
+            launch_attention<true>(1u << ATT_5_6, c, b, cu_dev, n_seqs, max_seqlen, order, st, pruned);
             ICREC_HIP(link(sd, sd->side, st));
         } else {
-            launch_attention<true>(~0u, c, b, cu_dev, n_seqs, max_seqlen, order, st);
+            launch_attention<true>(~0u, c, b, cu_dev, n_seqs, max_seqlen, order, st, pruned);
+        }
+        if (pruned) {
+            // Rows cu[s] of the context (query block 0 wrote them) and of x -> compact rows, then the unfused chain over
+            // those n_seqs rows on the caller's stream, in the form their number picks.  The side stream joined above
+            // and gets no more work: nothing is left to join before the pooling.
+            hipLaunchKernelGGL(gather_cls_rows_kernel, dim3((n_seqs * (H / 8) + 255) / 256), dim3(256), 0, st, b.ch, b.cl,
+                               b.xh, b.xl, cu_dev, n_seqs, H / 8, cls->ch, cls->cl, cls->xh, cls->xl);
+            Range rows(e, 0, n_seqs, st);
+            rows.layer = false;  // (no layer kernel for compact rows: above small_m they take the batch-form GEMMs)
+            post_stage(rows, l, *cls);
+            return ICREC_OK;
         }
         if (tail_on_side) ICREC_HIP(link(sd, st, sd->side));
-        if (T_tail) post_stage(tail, l);
-        post_stage(main, l);
+        if (T_tail) post_stage(tail, l, b);
+        post_stage(main, l, b);
     }
     if (tail_on_side) ICREC_HIP(link(sd, sd->side, st));  // pooling reads every row: the side stream joins here
     return ICREC_OK;
@@ -1276,8 +1355,9 @@ int icrec_encode_ex(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_
     ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= e->max_seqlen, "icrec_encode: max_seqlen must be in [1, %d] (got %d)", e->max_seqlen, max_seqlen);
     const int T = (int)T64;
     const EncWs w = enc_ws(e->cfg, T);
-    if (!ws || ws_bytes < w.total) {
-        set_error("icrec_encode: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    const size_t need = workspace_bytes(e, T, n_seqs);
+    if (!ws || ws_bytes < need) {
+        set_error("icrec_encode: workspace too small (%zu < %zu)", ws_bytes, need);
         return ICREC_ENOMEM;
     }
     ICREC_HIP(hipSetDevice(e->device));
@@ -1285,27 +1365,23 @@ int icrec_encode_ex(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_
     ScopedTimer whole(T_ENCODE, st);
     char* base = reinterpret_cast<char*>(ws);
     const icrec_bert_cfg& c = e->cfg;
-    const int H = c.hidden, I = c.intermediate;
+    const int H = c.hidden;
     const bool x3 = c.gemm_mode == ICREC_GEMM_F16X3;
-    EncBufs b;
-    b.x = reinterpret_cast<float*>(base + w.x);
-    b.qkv = reinterpret_cast<float*>(base + w.qkv);
-    b.ctx = reinterpret_cast<float*>(base + w.ctx);
-    b.t1 = reinterpret_cast<float*>(base + w.t1);
-    b.h = reinterpret_cast<float*>(base + w.h);
-    b.xh = reinterpret_cast<_Float16*>(base + w.xs);
-    b.xl = b.xh + (size_t)T * H;
-    b.ch = reinterpret_cast<_Float16*>(b.ctx);
-    b.cl = b.ch + (size_t)T * H;
-    b.hh = reinterpret_cast<_Float16*>(b.h);
-    b.hl = b.hh + (size_t)T * I;
+    const EncBufs b(base, w, c, T);
+    // The last layer is pruned to each sequence's first token when nothing else of it is read: not when the caller
+    // wants every token's state, and not when every token is a first token (nothing to save).
+    const bool pruned = cls_prunes(e) && !tokens_out_dev && n_seqs < T;
+    const EncBufs cls(base + w.total, enc_ws(c, n_seqs, true), c, n_seqs);  // (inside the workspace only if cls_prunes)
     const int32_t* order = embed(e, b, ids_dev, cu_dev, n_seqs, T, st);
-    if (int rc_ = x3 ? encode_x3(e, b, cu_dev, n_seqs, T, max_seqlen, order, st)
+    if (int rc_ = x3 ? encode_x3(e, b, pruned ? &cls : nullptr, cu_dev, n_seqs, T, max_seqlen, order, st)
                      : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
         return rc_;
     const auto pool = H == HID_BASE ? (x3 ? pool_norm_kernel<HID_BASE, true> : pool_norm_kernel<HID_BASE, false>)
                                     : (x3 ? pool_norm_kernel<HID, true> : pool_norm_kernel<HID, false>);
-    hipLaunchKernelGGL(pool, dim3(n_seqs), dim3(H), 0, st, b.x, b.xh, b.xl, cu_dev, c.n_normalize, out_dev);
+    const EncBufs& last = pruned ? cls : b;  // where the last hidden state of the pooled rows is
+    const int pool_rows = e->pooling != ICREC_POOL_CLS ? POOL_ROWS_MEAN : pruned ? POOL_ROWS_CLS_COMPACT : POOL_ROWS_CLS;
+    hipLaunchKernelGGL(pool, dim3(n_seqs), dim3(H), 0, st, last.x, last.xh, last.xl, cu_dev, c.n_normalize, out_dev,
+                       pool_rows);
     if (tokens_out_dev) {  // hidden is a multiple of 4: every thread's 4 features are 16 (planes: 8) bytes, aligned
         const size_t n4 = (size_t)T * H / 4;
         hipLaunchKernelGGL(x3 ? tokens_out_kernel<true> : tokens_out_kernel<false>, dim3((unsigned)((n4 + 255) / 256)),

@@ -3,7 +3,7 @@
 The reference calls `self.model.encode(texts, batch_size=64, normalize_embeddings=True)`
 (src/inference/serve_recommendations.py:195-200, :213, :246).  Here tokenisation is a
 separate host stage (tokenizer.py); this module takes token ids, packs them back to back
-(no padding), and runs libicrec's fp32-MFMA BERT forward + mean-pool + L2-normalise.
+(no padding), and runs libicrec's fp32-MFMA BERT forward + pooling (mean, or the [CLS] token's state) + L2-normalise.
 
 torch is used for device memory and streams only.
 """
@@ -44,13 +44,15 @@ class DeviceEncoder:
     SPLIT_MIN_TOKENS = 16384   # ... and this many tokens (enough blocks to fill the chip on its own)
 
     def __init__(self, weights: np.ndarray, shape: BertShape = BertShape(), device: str | torch.device = "cuda:0",
-                 gemm_mode: Optional[str] = None, max_seq_length: Optional[int] = None):
+                 gemm_mode: Optional[str] = None, max_seq_length: Optional[int] = None, pooling: str = "mean"):
         """gemm_mode: "f32" (exact f32 MFMA, bit-identical GEMMs) or "f16x3" (3-term split on the f16
         MFMA, fp32-level accuracy, ~4x faster); default from $ICREC_GEMM_MODE, else DEFAULT_GEMM_MODE.
         max_seq_length: the longest sequence the encoder must take, up to min(512, shape.max_position).  The
         ceiling is min(256, shape.max_position) by default and only ever raised: a larger value sets it
         (icrec_encoder_set_max_seqlen), a smaller one keeps the default.  Sequences of up to 256 tokens encode
-        to the same bits whatever the ceiling."""
+        to the same bits whatever the ceiling.
+        pooling: "mean" (sentence-transformers Pooling(mean), all-MiniLM) or "cls" (Pooling(cls), the BGE family: the
+        last hidden state of each sequence's first token), set once here (icrec_encoder_set_pooling)."""
         self.device = _native.hip_device(device, "DeviceEncoder")
         self.shape = shape
         L = _native.lib()
@@ -59,6 +61,9 @@ class DeviceEncoder:
         self.gemm_mode = gemm_mode or os.getenv("ICREC_GEMM_MODE") or DEFAULT_GEMM_MODE
         if self.gemm_mode not in _native.GEMM_MODES:
             raise ValueError(f"gemm_mode must be one of {sorted(_native.GEMM_MODES)}, got {self.gemm_mode!r}")
+        if pooling not in _native.POOLING_MODES:
+            raise ValueError(f"pooling must be one of {sorted(_native.POOLING_MODES)}, got {pooling!r}")
+        self.pooling = pooling
         self._cfg = _native.BertCfg(shape.vocab_size, shape.hidden, shape.layers, shape.heads, shape.intermediate,
                                     shape.max_position, shape.type_vocab, shape.ln_eps, shape.n_normalize,
                                     _native.GEMM_MODES[self.gemm_mode])
@@ -71,13 +76,15 @@ class DeviceEncoder:
                                              self.device.index, C.byref(h)), "icrec_encoder_create")
         self._h = h
         self.max_seq_length = min(MAX_SEQ_LEN, shape.max_position)
-        if max_seq_length is not None and not 1 <= int(max_seq_length) <= self.max_seq_length:
-            try:
+        try:
+            if pooling != "mean":  # (a mean-pooled encoder makes the calls it always made)
+                _native.check(L.icrec_encoder_set_pooling(h, _native.POOLING_MODES[pooling]), "icrec_encoder_set_pooling")
+            if max_seq_length is not None and not 1 <= int(max_seq_length) <= self.max_seq_length:
                 _native.check(L.icrec_encoder_set_max_seqlen(h, int(max_seq_length)), "icrec_encoder_set_max_seqlen")
-            except _native.IcrecError:
-                self.close()
-                raise
-            self.max_seq_length = int(max_seq_length)
+                self.max_seq_length = int(max_seq_length)
+        except _native.IcrecError:
+            self.close()
+            raise
         self._ws_by_stream = _native.StreamScratch(self.device)
         self._side: Optional[torch.cuda.Stream] = None
 

@@ -35,6 +35,7 @@ class LoadedModel:
     weights: np.ndarray  # flat fp32 blob, include/icrec.h order
     max_seq_length: int
     tokenizer: "HostTokenizer"
+    pooling: str = "mean"  # "mean" or "cls": the one mode 1_Pooling/config.json switches on
 
 
 class NativeTokenizer:
@@ -147,6 +148,7 @@ def load_model_dir(model_dir: Path | str) -> LoadedModel:
     if cfg.get("hidden_act", "gelu") != "gelu":
         raise ValueError(f"unsupported hidden_act {cfg.get('hidden_act')!r} (kernels implement erf-GELU)")
     n_norm = 1  # encode(..., normalize_embeddings=True) at every reference call site
+    pooling = "mean"  # sentence-transformers' default when the directory names no mode
     mj = d / "modules.json"
     if mj.exists():
         for m in json.loads(mj.read_text()):
@@ -157,9 +159,15 @@ def load_model_dir(model_dir: Path | str) -> LoadedModel:
                 pc = d / m.get("path", "1_Pooling") / "config.json"
                 if pc.exists():
                     p = json.loads(pc.read_text())
-                    others = [k for k, v in p.items() if k.startswith("pooling_mode_") and v and k != "pooling_mode_mean_tokens"]
-                    if not p.get("pooling_mode_mean_tokens", True) or others:
-                        raise ValueError(f"only mean-token pooling is implemented (got {p})")
+                    # exactly one of mean / cls: the other modes (max, mean-sqrt-len, weighted mean, last token) are
+                    # not implemented, and any combination of modes widens the output
+                    on = {"pooling_mode_mean_tokens": bool(p.get("pooling_mode_mean_tokens", True))}
+                    on.update({k: bool(v) for k, v in p.items() if k.startswith("pooling_mode_") and k not in on})
+                    chosen = [k for k, v in on.items() if v]
+                    served = {"pooling_mode_mean_tokens": "mean", "pooling_mode_cls_token": "cls"}
+                    if len(chosen) != 1 or chosen[0] not in served:
+                        raise ValueError(f"only mean-token or CLS-token pooling, one of the two, is implemented (got {p})")
+                    pooling = served[chosen[0]]
     shape = BertShape(vocab_size=int(cfg["vocab_size"]), hidden=int(cfg["hidden_size"]),
                       layers=int(cfg["num_hidden_layers"]), heads=int(cfg["num_attention_heads"]),
                       intermediate=int(cfg["intermediate_size"]), max_position=int(cfg["max_position_embeddings"]),
@@ -179,14 +187,18 @@ def load_model_dir(model_dir: Path | str) -> LoadedModel:
         logger.warning("%s asks for max_seq_length %d; this encoder serves at most %d tokens for it: using %d",
                        d, max_len, limit, limit)
         max_len = limit
-    return LoadedModel(shape, weights, max_len, HostTokenizer(d, max_len))
+    return LoadedModel(shape, weights, max_len, HostTokenizer(d, max_len), pooling)
 
 
-def write_synthetic_model_dir(path: Path | str, seed: int = 0, shape: BertShape | None = None) -> Path:
+def write_synthetic_model_dir(path: Path | str, seed: int = 0, shape: BertShape | None = None,
+                              pooling: str = "mean") -> Path:
     """Write a SentenceTransformer-layout directory with seeded random weights and the synthetic
-    WordPiece vocab (stand-in for the fine-tuned all-MiniLM-L6-v2 that cannot be downloaded here)."""
+    WordPiece vocab (stand-in for the fine-tuned all-MiniLM-L6-v2 that cannot be downloaded here).
+    pooling: "mean" or "cls", what 1_Pooling/config.json switches on (all-MiniLM: mean; the BGE family: cls)."""
     from safetensors.numpy import save_file
 
+    if pooling not in ("mean", "cls"):
+        raise ValueError(f"pooling must be 'mean' or 'cls', got {pooling!r}")
     d = Path(path)
     d.mkdir(parents=True, exist_ok=True)
     vocab = synthetic_vocab()
@@ -212,7 +224,7 @@ def write_synthetic_model_dir(path: Path | str, seed: int = 0, shape: BertShape 
         {"idx": 2, "name": "2", "path": "2_Normalize", "type": "sentence_transformers.models.Normalize"}], indent=2))
     (d / "1_Pooling").mkdir(exist_ok=True)
     (d / "1_Pooling" / "config.json").write_text(json.dumps({
-        "word_embedding_dimension": shape.hidden, "pooling_mode_cls_token": False,
-        "pooling_mode_mean_tokens": True, "pooling_mode_max_tokens": False}))
+        "word_embedding_dimension": shape.hidden, "pooling_mode_cls_token": pooling == "cls",
+        "pooling_mode_mean_tokens": pooling == "mean", "pooling_mode_max_tokens": False}))
     (d / "2_Normalize").mkdir(exist_ok=True)
     return d
