@@ -126,8 +126,22 @@ ICREC_API int icrec_encoder_set_pooling(icrec_encoder* enc, int32_t mode);
 /* The pooling mode of `enc`; -1 for a NULL handle. */
 ICREC_API int32_t icrec_encoder_pooling(const icrec_encoder* enc);
 
+/* Additive attention bias by relative position (MPNet / T5 style).  bias_host: float[heads][2*ICREC_MAX_SEQLEN - 1],
+ * head-major; entry [h][ICREC_MAX_SEQLEN - 1 + (j - i)] is added to the logit of query i against key j of head h
+ * (positions inside the token's own sequence), after the 1/sqrt(head_dim) scale and before the softmax, in EVERY layer.
+ * NULL removes the bias.  heads must equal cfg.heads; every value must be finite; anything else is ICREC_EINVAL and
+ * changes nothing.  Same contract as icrec_encoder_set_pooling: before the first icrec_encode, never while a call on
+ * `enc` is running.  A set-up call like icrec_encoder_create: it allocates and copies, and may synchronise the device.
+ * The table (kept in log2 units, 4 KB per head) lives on the handle: icrec_bert_cfg, the weight blob and
+ * icrec_encode_workspace_bytes do not know it.  An encoder with a bias launches the BIAS arm of the two attention
+ * kernels (the head's row in LDS, one fma per logit, the row maximum taken over the biased logits) in every form
+ * attention is launched in; one without launches what it always did, to the same bits.  A sequence encodes to the same
+ * bits alone and inside any batch, with or without a bias. */
+ICREC_API int icrec_encoder_set_attention_bias(icrec_encoder* enc, const float* bias_host, int32_t heads);
+ICREC_API int32_t icrec_encoder_has_attention_bias(const icrec_encoder* enc);   /* 0 / 1; -1 for NULL */
+
 /* Scratch bytes needed to encode `total_tokens` tokens in `n_seqs` sequences.  Depends on the pooling mode (a CLS
- * encoder adds room for `n_seqs` compact rows): ask after icrec_encoder_set_pooling. */
+ * encoder adds room for `n_seqs` compact rows): ask after icrec_encoder_set_pooling.  Does not depend on the bias. */
 ICREC_API size_t icrec_encode_workspace_bytes(const icrec_encoder* enc,
                                     int64_t total_tokens, int32_t n_seqs);
 
@@ -378,6 +392,12 @@ typedef struct icrec_tokenizer icrec_tokenizer;
  * max_len: [CLS] + tokens + [SEP] is truncated to this many ids (256). */
 ICREC_API int icrec_tokenizer_create(const char* vocab_path, int do_lower_case, int max_len,
                            icrec_tokenizer** out);
+/* The same tokenizer for a vocabulary whose special tokens carry other names (MPNet: <s> </s> <unk> <pad> <mask>).
+ * cls, sep and unk must be in the vocabulary; pad and mask may be NULL or absent from it.  All five are matched
+ * verbatim in the raw text, never split.  The sequence template stays `cls tokens sep`. */
+ICREC_API int icrec_tokenizer_create_ex(const char* vocab_path, int do_lower_case, int max_len,
+                              const char* cls, const char* sep, const char* unk, const char* pad, const char* mask,
+                              icrec_tokenizer** out);
 ICREC_API int icrec_tokenizer_destroy(icrec_tokenizer* tok);
 ICREC_API int32_t icrec_tokenizer_vocab_size(const icrec_tokenizer* tok);
 

@@ -25,6 +25,7 @@ POOLING_MODES = {"mean": POOL_MEAN, "cls": POOL_CLS}
 EXPORTS = [
     "icrec_encoder_weight_count", "icrec_encoder_create", "icrec_encoder_destroy", "icrec_encoder_set_max_seqlen",
     "icrec_encoder_set_pooling", "icrec_encoder_pooling",
+    "icrec_encoder_set_attention_bias", "icrec_encoder_has_attention_bias",
     "icrec_encode_workspace_bytes", "icrec_encode", "icrec_encode_ex", "icrec_encode_batch_split",
     "icrec_index_create", "icrec_index_create_ex", "icrec_index_destroy", "icrec_index_rows", "icrec_index_storage",
     "icrec_index_export", "icrec_index_dim", "icrec_index_device",
@@ -34,7 +35,7 @@ EXPORTS = [
     "icrec_exclusions_to_shard_csr_workspace_bytes", "icrec_exclusions_to_shard_csr",
     "icrec_search_workspace_bytes", "icrec_search", "icrec_search_partial", "icrec_merge_topk",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
-    "icrec_tokenizer_create", "icrec_tokenizer_destroy", "icrec_tokenizer_vocab_size", "icrec_tokenize",
+    "icrec_tokenizer_create", "icrec_tokenizer_create_ex", "icrec_tokenizer_destroy", "icrec_tokenizer_vocab_size", "icrec_tokenize",
     "icrec_last_error", "icrec_version",
     "icrec_timing_enable", "icrec_timing_reset", "icrec_timing_query",
 ]
@@ -93,6 +94,8 @@ def lib() -> C.CDLL:
         "icrec_encoder_set_max_seqlen": (C.c_int, [vp, i32]),
         "icrec_encoder_set_pooling": (C.c_int, [vp, i32]),
         "icrec_encoder_pooling": (i32, [vp]),
+        "icrec_encoder_set_attention_bias": (C.c_int, [vp, vp, i32]),
+        "icrec_encoder_has_attention_bias": (i32, [vp]),
         "icrec_encode_workspace_bytes": (sz, [vp, i64, i32]),
         "icrec_encode": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, vp, sz, vp]),
         "icrec_encode_ex": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, vp, vp, sz, vp]),
@@ -126,6 +129,8 @@ def lib() -> C.CDLL:
         "icrec_rank_all": (C.c_int, [vp, vp, i32, vp, vp, sz, vp]),
         "icrec_normalize_rows": (C.c_int, [vp, vp, i64, i32, C.c_float, C.c_int, vp]),
         "icrec_tokenizer_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]),
+        "icrec_tokenizer_create_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                                C.c_char_p, C.POINTER(vp)]),
         "icrec_tokenizer_destroy": (C.c_int, [vp]),
         "icrec_tokenizer_vocab_size": (i32, [vp]),
         "icrec_tokenize": (C.c_int, [vp, C.POINTER(C.c_char_p), i32, vp, i64, vp, i32]),

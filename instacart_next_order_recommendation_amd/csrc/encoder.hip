@@ -176,12 +176,32 @@ __device__ __forceinline__ float join_halves(float v, int h) {
     return h == 0 ? v + other : other + v;
 }
 
+// Relative-position attention bias (MPNet / T5 style; icrec_encoder_set_attention_bias): the BIAS arm of both kernels
+// adds bias[head][key - query] to every scaled logit, in every layer.  The device table holds, per head, ATT_BIAS_LD
+// floats in log2 units (pre-multiplied by log2(e), like the scale): entry ICREC_MAX_SEQLEN - 1 + (key - query), the last
+// one padding.  A workgroup copies its head's row into LDS (4 KB) ahead of the first staging barrier; a lane owns one
+// query, so register e of key tile kt reads entry  att_bias_base(..) + 32 kt + (e & 3) + 8 (e >> 2)  - per tile 16 reads
+// at immediate offsets from one address, consecutive lanes on consecutive banks.  Keys and queries past the sequence
+// (clamped rows, masked / never stored) stay inside the table: both positions are below ICREC_MAX_SEQLEN.
+// The biased logit is ONE fma, scale * s + bias, and the row maximum is taken over it - whatever the bucket, the
+// chunking or the dispatch form: the same bits for a sequence alone and inside any batch.
+constexpr int ATT_BIAS_LD = 2 * ICREC_MAX_SEQLEN;
+__device__ __forceinline__ void att_bias_to_lds(float* dst, const float* __restrict__ bias, int hd, int tid, int nthreads) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(bias + (size_t)hd * ATT_BIAS_LD);
+    for (int i = tid; i < ATT_BIAS_LD / 4; i += nthreads) reinterpret_cast<f32x4*>(dst)[i] = src[i];
+}
+// entry of (query qb*32 + r, key acc_row(0, lane)) of key tile 0
+__device__ __forceinline__ int att_bias_base(int qb, int lane) {
+    return ICREC_MAX_SEQLEN - 1 - (qb * 32 + (lane & 31)) + acc_row(0, lane);
+}
+
 // Exact fp32 form (gemm_mode F32): both products on v_mfma_f32_32x32x2_f32, head dims in pairs ascending.
 // Output: the fp32 context rows.
-template <int D, int NKT>
+template <int D, int NKT, bool BIAS = false>
 __global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __restrict__ qkv,
                                                              const int32_t* __restrict__ cu, int heads, int H,
-                                                             float scale_log2e, float* __restrict__ ctx, int nlo) {
+                                                             float scale_log2e, float* __restrict__ ctx, int nlo,
+                                                             const float* __restrict__ bias) {
     constexpr int KC = att_kc(D, NKT);
     constexpr int LDK = D + 4;  // K LDS row stride (even/odd split layout, like the GEMM tiles)
     // Sixteen score tiles do not fit in registers (and 64-dim heads leave room for none): each tile is then computed
@@ -201,6 +221,12 @@ __global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __rest
     const int ld = 3 * H;
     const int r = lane & 31, h = lane >> 5, qb = wave;
     const bool active = qb < nkt;  // wave-uniform; idle waves still take part in the barriers of the staging
+    const float* bt = nullptr;  // this lane's window of the head's bias row (BIAS), visible behind the staging barrier
+    if constexpr (BIAS) {
+        __shared__ __attribute__((aligned(16))) float Bs[ATT_BIAS_LD];
+        att_bias_to_lds(Bs, bias, hd, tid, NKT * 64);
+        bt = Bs + att_bias_base(qb, lane);
+    }
     float4 qf[D / 8];  // this lane's query row -> B fragments (lane half h supplies the even / odd dims of every pair)
     {
         int qr = qb * 32 + r;
@@ -231,7 +257,7 @@ __global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __rest
         __syncthreads();
     };
     // scores of key tile kt (staged from c0) in log2 units (scale * log2(e) folded), tail keys at -inf:
-    // t[e] = scale_log2e * sum_d K[kt*32 + krow(e)][d] * Q[qb*32 + r][d]
+    // t[e] = scale_log2e * sum_d K[kt*32 + krow(e)][d] * Q[qb*32 + r][d]   (BIAS: ... + bias[krow(e) - query], one fma)
     auto score_tile = [&](int kt, int c0) {
         f32x16 t;
 #pragma unroll
@@ -247,7 +273,9 @@ __global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __rest
         const bool last = kt == nkt - 1;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            float v = t[e] * scale_log2e;
+            float v;
+            if constexpr (BIAS) v = fmaf(t[e], scale_log2e, bt[kt * 32 + (e & 3) + 8 * (e >> 2)]);
+            else v = t[e] * scale_log2e;
             if (last && kt * 32 + acc_row(e, lane) >= L) v = -INFINITY;
             t[e] = v;
         }
@@ -406,10 +434,12 @@ constexpr int att_x3_wgs(int D, int NKT) { return D != 32 ? 1 : NKT >= 6 ? 4 : N
 // nqb: the query blocks to compute, from block 0 - NKT for all of them; 1 for the last layer of a CLS-pooled encoder,
 // which reads each sequence's first row only: every wave still stages K / V and meets every barrier, only wave 0 runs
 // the score / softmax / P.V loop and stores its tile, the very bits a full launch gives those rows.
-template <int D, int NKT>  // NKT waves, one per 32-row query block
+// BIAS: the relative-position bias arm (see att_bias_to_lds), 4 KB of LDS more.
+template <int D, int NKT, bool BIAS = false>  // NKT waves, one per 32-row query block
 __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_kernel(
     const float* __restrict__ qkv, const int32_t* __restrict__ cu, int heads, int H, float scale_log2e,
-    _Float16* __restrict__ ch, _Float16* __restrict__ cl, const int32_t* __restrict__ order, int nlo, int nqb) {
+    _Float16* __restrict__ ch, _Float16* __restrict__ cl, const int32_t* __restrict__ order, int nlo, int nqb,
+    const float* __restrict__ bias) {
     // Single-accumulator form of the split (wt_gemm.h): every operand is carried as hi/lo f16 planes of 16 x (Q, K, V)
     // or 1024 p (the probabilities), the three products of a k-step accumulate into ONE fp32 tile, and the power-of-two
     // scales are folded into constants: S' = 256 S, O' = 16384 sum_k p_k V_k, l' = 1024 sum_k p_k, O = O' / (16 l').
@@ -450,6 +480,12 @@ __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_ker
     const int ld = 3 * H;
     const int r = lane & 31, h = lane >> 5, qb = wave;
     const bool active = qb < nkt && qb < nqb;  // wave-uniform; idle waves still take part in the barriers
+    const float* bt = nullptr;  // this lane's window of the head's bias row (BIAS), visible behind the staging barrier
+    if constexpr (BIAS) {
+        __shared__ __attribute__((aligned(16))) float Bs[ATT_BIAS_LD];
+        att_bias_to_lds(Bs, bias, hd, tid, NKT * 64);
+        bt = Bs + att_bias_base(qb, lane);
+    }
     half8 qh[D / 16], ql[D / 16];  // B operand of S^T: this lane's query row, dims 16 ks + 8 h .. +7
     {
         int qr = qb * 32 + r;
@@ -592,6 +628,13 @@ __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_ker
     const float cs = scale_log2e * (1.0f / 256.0f);  // scores in log2 units from S' = 256 S
     // Softmax on the raw scores (S' = 256 S): the maximum is taken before scaling, and scale, shift and the 2^10 factor
     // of p' = 1024 p go into one fma in front of the exponential: p' = 2^(S' cs - max' cs + 10).
+    // BIAS: the logit in log2 units is v = S' cs + bias, one fma; the maximum is taken over v (a maximum over S' alone
+    // would let a large bias on a small logit run past every head room), and p' = 2^(v - max + 10).  On the hi x hi
+    // maximum of the RECOMP form the exponent clamp still covers what the two dropped products add, as without a bias.
+    auto biased = [&](f32x16& t, int kt) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) t[e] = fmaf(t[e], cs, bt[kt * 32 + (e & 3) + 8 * (e >> 2)]);
+    };
     // row sums l' = sum_k p'_k: two interleaved chains per lane (packed adds), the halves of a row joined by a shuffle
     float2w ls2 = float2w{0.0f, 0.0f};
     auto join_rows = [&]() {
@@ -602,16 +645,23 @@ __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_ker
     if constexpr (RECOMP) {
         float mx = -INFINITY;
         for_tiles(false, [&](int kt, int c0) {
-            const f32x16 t = score_tile(kt, c0, true);
+            f32x16 t = score_tile(kt, c0, true);
+            if constexpr (BIAS) biased(t, kt);
 #pragma unroll
             for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
         });
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float shift = fmaf(-mx, cs, 10.0f);
+        const float shift = BIAS ? 10.0f - mx : fmaf(-mx, cs, 10.0f);
         for_tiles(true, [&](int kt, int c0) {
             f32x16 t = score_tile(kt, c0, false);
+            if constexpr (BIAS) {
+                biased(t, kt);
 #pragma unroll
-            for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(fmaf(t[e], cs, shift), 15.9f));
+                for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(t[e] + shift, 15.9f));
+            } else {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(fmaf(t[e], cs, shift), 15.9f));
+            }
 #pragma unroll
             for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{t[e], t[e + 1]};
             pv_tile(kt, c0, t);
@@ -620,8 +670,12 @@ __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_ker
     } else if (active) {
         f32x16 sc[NKT];
 #pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-            if (kt < nkt) sc[kt] = score_tile(kt, 0, false);
+        for (int kt = 0; kt < NKT; ++kt) {
+            if (kt < nkt) {
+                sc[kt] = score_tile(kt, 0, false);
+                if constexpr (BIAS) biased(sc[kt], kt);
+            }
+        }
         float mx = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
@@ -631,12 +685,13 @@ __global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_ker
             }
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float shift = fmaf(-mx, cs, 10.0f);
+        const float shift = BIAS ? 10.0f - mx : fmaf(-mx, cs, 10.0f);
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
             if (kt < nkt) {
 #pragma unroll
-                for (int e = 0; e < 16; ++e) sc[kt][e] = __builtin_amdgcn_exp2f(fmaf(sc[kt][e], cs, shift));
+                for (int e = 0; e < 16; ++e)
+                    sc[kt][e] = __builtin_amdgcn_exp2f(BIAS ? sc[kt][e] + shift : fmaf(sc[kt][e], cs, shift));
             }
         }
 #pragma unroll
@@ -799,6 +854,7 @@ struct Encoder {
     int n_cu = 256;
     int max_seqlen = 256;       // longest sequence icrec_encode accepts (icrec_encoder_set_max_seqlen)
     int pooling = ICREC_POOL_MEAN;  // icrec_encoder_set_pooling
+    float* att_bias = nullptr;  // icrec_encoder_set_attention_bias: [heads][ATT_BIAS_LD] in log2 units, or none
     float* blob = nullptr;      // the uploaded weight blob
     float* extra = nullptr;     // repacked Wqkv / bqkv
     _Float16* planes = nullptr; // packed weight fragments (F16X3)
@@ -963,9 +1019,11 @@ constexpr int ATT_LO[ATT_N] = {9, 1, 2, 3, 5, 7, 5}, ATT_HI[ATT_N] = {16, 1, 2, 
 // that can occur for max_seqlen (one whose workgroups all exit costs a few microseconds), else the one that holds it.
 // X3: the f16x3 kernel, context out as planes (attention_x3_kernel); otherwise exact fp32 rows (attention_kernel).
 // block0_only (X3): query block 0 of every (sequence, head) alone - the pruned last layer of a CLS-pooled encoder.
+// bias: the encoder's relative-position table (the kernels' BIAS arm), or nullptr: the launches of an encoder without one.
 template <bool X3>
 static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBufs& b, const int32_t* cu, int n_seqs,
-                             int max_seqlen, const int32_t* order, hipStream_t st, bool block0_only = false) {
+                             int max_seqlen, const int32_t* order, const float* bias, hipStream_t st,
+                             bool block0_only = false) {
     const int nkt_max = (max_seqlen + 31) / 32;
     const int dh = c.hidden / c.heads;  // 32 or 64 (icrec_encoder_create)
     const bool single = n_seqs == 1, split_5_8 = X3 && !single && dh == 32;
@@ -976,22 +1034,20 @@ static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBu
             continue;
         const dim3 grid(n_seqs * c.heads), block(ATT_HI[k] * 64);
         if constexpr (X3) {  // (only 32-dim heads split 5-8 key tiles)
-            static const decltype(&attention_x3_kernel<32, 1>) kern[2][ATT_N] = {
-                {attention_x3_kernel<32, 16>, attention_x3_kernel<32, 1>, attention_x3_kernel<32, 2>,
-                 attention_x3_kernel<32, 4>, attention_x3_kernel<32, 6>, attention_x3_kernel<32, 8>,
-                 attention_x3_kernel<32, 8>},
-                {attention_x3_kernel<64, 16>, attention_x3_kernel<64, 1>, attention_x3_kernel<64, 2>,
-                 attention_x3_kernel<64, 4>, nullptr, nullptr, attention_x3_kernel<64, 8>}};
-            hipLaunchKernelGGL(kern[dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ch, b.cl, order,
-                               ATT_LO[k] - 1, block0_only ? 1 : ATT_HI[k]);
+#define ICREC_ATT_ROW(K, D, B) {K<D, 16, B>, K<D, 1, B>, K<D, 2, B>, K<D, 4, B>, D == 32 ? K<32, 6, B> : nullptr, D == 32 ? K<32, 8, B> : nullptr, K<D, 8, B>}
+            static const decltype(&attention_x3_kernel<32, 1>) kern[2][2][ATT_N] = {
+                {ICREC_ATT_ROW(attention_x3_kernel, 32, false), ICREC_ATT_ROW(attention_x3_kernel, 64, false)},
+                {ICREC_ATT_ROW(attention_x3_kernel, 32, true), ICREC_ATT_ROW(attention_x3_kernel, 64, true)}};
+#undef ICREC_ATT_ROW
+            hipLaunchKernelGGL(kern[bias != nullptr][dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e,
+                               b.ch, b.cl, order, ATT_LO[k] - 1, block0_only ? 1 : ATT_HI[k], bias);
         } else {
-            static const decltype(&attention_kernel<32, 1>) kern[2][ATT_N] = {
-                {attention_kernel<32, 16>, attention_kernel<32, 1>, attention_kernel<32, 2>, attention_kernel<32, 4>,
-                 nullptr, nullptr, attention_kernel<32, 8>},
-                {attention_kernel<64, 16>, attention_kernel<64, 1>, attention_kernel<64, 2>, attention_kernel<64, 4>,
-                 nullptr, nullptr, attention_kernel<64, 8>}};
-            hipLaunchKernelGGL(kern[dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e, b.ctx,
-                               ATT_LO[k] - 1);
+#define ICREC_ATT_ROW(D, B) {attention_kernel<D, 16, B>, attention_kernel<D, 1, B>, attention_kernel<D, 2, B>, attention_kernel<D, 4, B>, nullptr, nullptr, attention_kernel<D, 8, B>}
+            static const decltype(&attention_kernel<32, 1>) kern[2][2][ATT_N] = {
+                {ICREC_ATT_ROW(32, false), ICREC_ATT_ROW(64, false)}, {ICREC_ATT_ROW(32, true), ICREC_ATT_ROW(64, true)}};
+#undef ICREC_ATT_ROW
+            hipLaunchKernelGGL(kern[bias != nullptr][dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e,
+                               b.ctx, ATT_LO[k] - 1, bias);
         }
     }
 }
@@ -1100,6 +1156,7 @@ int icrec_encoder_destroy(icrec_encoder* h) {
     (void)hipFree(e->blob);
     (void)hipFree(e->extra);
     if (e->planes) (void)hipFree(e->planes);
+    if (e->att_bias) (void)hipFree(e->att_bias);
     for (Encoder::Side* sd : e->sides) {  // (side_for keeps a side only once its stream and event exist)
         (void)hipStreamSynchronize(sd->side);
         (void)hipStreamDestroy(sd->side);
@@ -1130,6 +1187,42 @@ int icrec_encoder_set_pooling(icrec_encoder* h, int32_t mode) {
 int32_t icrec_encoder_pooling(const icrec_encoder* h) {
     const Encoder* e = reinterpret_cast<const Encoder*>(h);
     return e ? e->pooling : -1;
+}
+
+int icrec_encoder_set_attention_bias(icrec_encoder* h, const float* bias_host, int32_t heads) {
+    Encoder* e = reinterpret_cast<Encoder*>(h);
+    ICREC_REQUIRE(e, "icrec_encoder_set_attention_bias: NULL encoder");
+    ICREC_HIP(hipSetDevice(e->device));
+    if (!bias_host) {  // back to the launches of an encoder that never had one
+        if (e->att_bias) ICREC_HIP(hipFree(e->att_bias));
+        e->att_bias = nullptr;
+        return ICREC_OK;
+    }
+    ICREC_REQUIRE(heads == e->cfg.heads, "icrec_encoder_set_attention_bias: heads must be %d, the encoder's (got %d)", e->cfg.heads, heads);
+    constexpr int N = 2 * ICREC_MAX_SEQLEN - 1;
+    // log2 units, like the kernels' scale: the product in double, rounded once
+    std::vector<float> tab((size_t)heads * ATT_BIAS_LD, 0.0f);
+    for (int hd = 0; hd < heads; ++hd)
+        for (int i = 0; i < N; ++i) {
+            const float v = bias_host[(size_t)hd * N + i];
+            ICREC_REQUIRE(v - v == 0.0f, "icrec_encoder_set_attention_bias: entry [%d][%d] is not finite", hd, i);
+            tab[(size_t)hd * ATT_BIAS_LD + i] = (float)((double)v * 1.44269504088896340736);
+        }
+    float* dev = e->att_bias;
+    if (!dev && hipMalloc(&dev, tab.size() * 4) != hipSuccess) {
+        set_error("icrec_encoder_set_attention_bias: hipMalloc failed");
+        return ICREC_ENOMEM;
+    }
+    const hipError_t err = hipMemcpy(dev, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+    if (err != hipSuccess && !e->att_bias) (void)hipFree(dev);
+    ICREC_HIP(err);
+    e->att_bias = dev;
+    return ICREC_OK;
+}
+
+int32_t icrec_encoder_has_attention_bias(const icrec_encoder* h) {
+    const Encoder* e = reinterpret_cast<const Encoder*>(h);
+    return e ? (e->att_bias != nullptr) : -1;
 }
 
 // The call's own regions, then (cls_prunes) the compact rows' of the pruned last layer.
@@ -1290,12 +1383,12 @@ static int encode_x3(Encoder* e, const EncBufs& b, const EncBufs* cls, const int
             // that bucket goes first, on the caller's stream, ahead of the side stream's)
             ICREC_HIP(link(sd, st, sd->side));
             const unsigned side_buckets = 1u << ATT_1 | 1u << ATT_2 | 1u << ATT_3_4 | 1u << ATT_7_8;
-            launch_attention<true>(1u << ATT_9_16, c, b, cu_dev, n_seqs, max_seqlen, order, st, pruned);
-            launch_attention<true>(side_buckets, c, b, cu_dev, n_seqs, max_seqlen, order, sd->side, pruned);
-            launch_attention<true>(1u << ATT_5_6, c, b, cu_dev, n_seqs, max_seqlen, order, st, pruned);
+            launch_attention<true>(1u << ATT_9_16, c, b, cu_dev, n_seqs, max_seqlen, order, e->att_bias, st, pruned);
+            launch_attention<true>(side_buckets, c, b, cu_dev, n_seqs, max_seqlen, order, e->att_bias, sd->side, pruned);
+            launch_attention<true>(1u << ATT_5_6, c, b, cu_dev, n_seqs, max_seqlen, order, e->att_bias, st, pruned);
             ICREC_HIP(link(sd, sd->side, st));
         } else {
-            launch_attention<true>(~0u, c, b, cu_dev, n_seqs, max_seqlen, order, st, pruned);
+            launch_attention<true>(~0u, c, b, cu_dev, n_seqs, max_seqlen, order, e->att_bias, st, pruned);
         }
         if (pruned) {
             // Rows cu[s] of the context (query block 0 wrote them) and of x -> compact rows, then the unfused chain over
@@ -1325,7 +1418,7 @@ static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev,
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& L = e->layers[l];
         launch_linear<false>(b.x, T, H, L.Wqkv, 3 * H, L.bqkv, b.qkv, st);
-        launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, st);
+        launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, e->att_bias, st);
         launch_linear<false>(b.ctx, T, H, L.Wo, H, L.bo, b.t1, st);
         hipLaunchKernelGGL(add_ln, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g1, L.b1n,
                            c.ln_eps, b.xh, b.xl);

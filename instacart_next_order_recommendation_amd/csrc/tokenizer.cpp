@@ -4,7 +4,8 @@
 // through transformers' BertTokenizer -> the Rust `tokenizers` crate (uv.lock:3841).  This is a C++
 // restatement of that pipeline so a serving process can tokenise request batches on worker threads
 // without the GIL:
-//   special-token extraction ([PAD] [UNK] [CLS] [SEP] [MASK] matched verbatim in the raw text)
+//   special-token extraction ([PAD] [UNK] [CLS] [SEP] [MASK], or the names icrec_tokenizer_create_ex is given,
+//                    matched verbatim in the raw text)
 //   BertNormalizer   clean_text (drop NUL / U+FFFD / control, whitespace -> ' '), spaces around CJK
 //                    ideographs, strip accents (NFD, drop Mn) when lower-casing, lower-case
 //   BertPreTokenizer split on whitespace, isolate punctuation (ASCII punctuation + Unicode P*)
@@ -187,7 +188,7 @@ struct icrec_tokenizer {
         size_t pos = 0, seg = 0;
         while (pos < n) {  // special tokens are matched verbatim in the raw text, never split
             bool hit = false;
-            if (text[pos] == '[') {
+            if (text[pos] == '[' || text[pos] == '<') {  // (every served family's specials start with one of the two)
                 for (auto& sp : specials)
                     if (n - pos >= sp.first.size() && memcmp(text + pos, sp.first.data(), sp.first.size()) == 0) {
                         if (pos > seg) segment(text + seg, pos - seg, body);
@@ -211,7 +212,17 @@ struct icrec_tokenizer {
 extern "C" {
 
 int icrec_tokenizer_create(const char* vocab_path, int do_lower_case, int max_len, icrec_tokenizer** out) {
-    if (!vocab_path || !out) { set_error("icrec_tokenizer_create: NULL argument"); return ICREC_EINVAL; }
+    return icrec_tokenizer_create_ex(vocab_path, do_lower_case, max_len, "[CLS]", "[SEP]", "[UNK]", "[PAD]", "[MASK]", out);
+}
+
+int icrec_tokenizer_create_ex(const char* vocab_path, int do_lower_case, int max_len, const char* cls, const char* sep,
+                              const char* unk, const char* pad, const char* mask, icrec_tokenizer** out) {
+    if (!vocab_path || !out || !cls || !sep || !unk) { set_error("icrec_tokenizer_create: NULL argument"); return ICREC_EINVAL; }
+    for (const char* sp : {cls, sep, unk, pad, mask})
+        if (sp && sp[0] != '[' && sp[0] != '<') {
+            set_error("icrec_tokenizer_create: special token %s must start with '[' or '<'", sp);
+            return ICREC_EINVAL;
+        }
     if (max_len < 2) { set_error("icrec_tokenizer_create: max_len must be >= 2"); return ICREC_EINVAL; }
     std::ifstream f(vocab_path);
     if (!f) { set_error("icrec_tokenizer_create: cannot open %s", vocab_path); return ICREC_EINVAL; }
@@ -230,12 +241,13 @@ int icrec_tokenizer_create(const char* vocab_path, int do_lower_case, int max_le
         dst = it->second;
         return true;
     };
-    if (!need("[UNK]", t->unk) || !need("[CLS]", t->cls) || !need("[SEP]", t->sep)) {
+    if (!need(unk, t->unk) || !need(cls, t->cls) || !need(sep, t->sep)) {
         delete t;
-        set_error("icrec_tokenizer_create: %s lacks [UNK]/[CLS]/[SEP]", vocab_path);
+        set_error("icrec_tokenizer_create: %s lacks %s/%s/%s", vocab_path, unk, cls, sep);
         return ICREC_EINVAL;
     }
-    for (const char* sp : {"[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"}) {
+    for (const char* sp : {pad, unk, cls, sep, mask}) {
+        if (!sp) continue;
         auto it = t->vocab.find(sp);
         if (it != t->vocab.end()) t->specials.emplace_back(sp, it->second);
     }

@@ -44,7 +44,8 @@ class DeviceEncoder:
     SPLIT_MIN_TOKENS = 16384   # ... and this many tokens (enough blocks to fill the chip on its own)
 
     def __init__(self, weights: np.ndarray, shape: BertShape = BertShape(), device: str | torch.device = "cuda:0",
-                 gemm_mode: Optional[str] = None, max_seq_length: Optional[int] = None, pooling: str = "mean"):
+                 gemm_mode: Optional[str] = None, max_seq_length: Optional[int] = None, pooling: str = "mean",
+                 attention_bias: Optional[np.ndarray] = None):
         """gemm_mode: "f32" (exact f32 MFMA, bit-identical GEMMs) or "f16x3" (3-term split on the f16
         MFMA, fp32-level accuracy, ~4x faster); default from $ICREC_GEMM_MODE, else DEFAULT_GEMM_MODE.
         max_seq_length: the longest sequence the encoder must take, up to min(512, shape.max_position).  The
@@ -52,7 +53,10 @@ class DeviceEncoder:
         (icrec_encoder_set_max_seqlen), a smaller one keeps the default.  Sequences of up to 256 tokens encode
         to the same bits whatever the ceiling.
         pooling: "mean" (sentence-transformers Pooling(mean), all-MiniLM) or "cls" (Pooling(cls), the BGE family: the
-        last hidden state of each sequence's first token), set once here (icrec_encoder_set_pooling)."""
+        last hidden state of each sequence's first token), set once here (icrec_encoder_set_pooling).
+        attention_bias: float32 [heads, 2 * 512 - 1], the MPNet family's relative-position bias: entry
+        [h, 511 + (key - query)] is added to every scaled attention logit of head h in every layer
+        (icrec_encoder_set_attention_bias; relative_bias.table_from_buckets makes it from a model's bucket table)."""
         self.device = _native.hip_device(device, "DeviceEncoder")
         self.shape = shape
         L = _native.lib()
@@ -79,6 +83,8 @@ class DeviceEncoder:
         try:
             if pooling != "mean":  # (a mean-pooled encoder makes the calls it always made)
                 _native.check(L.icrec_encoder_set_pooling(h, _native.POOLING_MODES[pooling]), "icrec_encoder_set_pooling")
+            if attention_bias is not None:  # (an encoder without one makes the calls it always made)
+                self.set_attention_bias(attention_bias)
             if max_seq_length is not None and not 1 <= int(max_seq_length) <= self.max_seq_length:
                 _native.check(L.icrec_encoder_set_max_seqlen(h, int(max_seq_length)), "icrec_encoder_set_max_seqlen")
                 self.max_seq_length = int(max_seq_length)
@@ -87,6 +93,23 @@ class DeviceEncoder:
             raise
         self._ws_by_stream = _native.StreamScratch(self.device)
         self._side: Optional[torch.cuda.Stream] = None
+
+    def set_attention_bias(self, table: Optional[np.ndarray]) -> None:
+        """Set (float32 [heads, 2 * 512 - 1]) or, with None, remove the relative-position attention bias.  Like the
+        pooling mode it belongs before the first encode; a refused table leaves the encoder as it was."""
+        L = _native.lib()
+        if table is None:
+            _native.check(L.icrec_encoder_set_attention_bias(self._h, None, 0), "icrec_encoder_set_attention_bias")
+            return
+        t = np.ascontiguousarray(table, dtype=np.float32)
+        if t.ndim != 2 or t.shape[1] != 2 * _native.ICREC_MAX_SEQLEN - 1:
+            raise ValueError(f"attention_bias must be [heads, {2 * _native.ICREC_MAX_SEQLEN - 1}], got {t.shape}")
+        _native.check(L.icrec_encoder_set_attention_bias(self._h, t.ctypes.data_as(C.c_void_p), t.shape[0]),
+                      "icrec_encoder_set_attention_bias")
+
+    @property
+    def has_attention_bias(self) -> bool:
+        return _native.lib().icrec_encoder_has_attention_bias(self._h) == 1
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -17,11 +17,11 @@ import json
 import logging
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _native
+from . import _native, relative_bias
 from .synthetic import BertShape, blob_to_state_dict, state_dict_to_blob, synthetic_bert_weights, synthetic_vocab
 
 logger = logging.getLogger(__name__)
@@ -36,20 +36,52 @@ class LoadedModel:
     max_seq_length: int
     tokenizer: "HostTokenizer"
     pooling: str = "mean"  # "mean" or "cls": the one mode 1_Pooling/config.json switches on
+    attention_bias: Optional[np.ndarray] = None  # MPNet: float32 [heads, 1023] by relative offset (relative_bias.py)
+
+
+#: the special tokens of a BERT vocabulary: what a directory that names none gets
+BERT_SPECIALS = {"cls_token": "[CLS]", "sep_token": "[SEP]", "unk_token": "[UNK]", "pad_token": "[PAD]",
+                 "mask_token": "[MASK]"}
+
+
+def special_tokens(model_dir: Path) -> dict:
+    """The directory's special-token names: BERT_SPECIALS overridden by tokenizer_config.json, then by
+    special_tokens_map.json (an entry is a string or an AddedToken dict with "content")."""
+    out = dict(BERT_SPECIALS)
+    for name in ("tokenizer_config.json", "special_tokens_map.json"):
+        f = Path(model_dir) / name
+        if not f.exists():
+            continue
+        cfg = json.loads(f.read_text())
+        for k in out:
+            v = cfg.get(k)
+            if isinstance(v, dict):
+                v = v.get("content")
+            if isinstance(v, str) and v:
+                out[k] = v
+    return out
 
 
 class NativeTokenizer:
     """libicrec's C++ WordPiece tokenizer (csrc/tokenizer.cpp): batched, multi-threaded, GIL-free."""
 
-    def __init__(self, vocab_path: Path, lowercase: bool, max_seq_length: int, n_threads: int = 0):
+    def __init__(self, vocab_path: Path, lowercase: bool, max_seq_length: int, n_threads: int = 0,
+                 specials: Optional[dict] = None):
+        """specials: the vocabulary's special-token names (keys of BERT_SPECIALS) when they are not BERT's."""
         import ctypes as C
 
         from . import _native
 
         self._C, self._native = C, _native
         h = C.c_void_p()
-        _native.check(_native.lib().icrec_tokenizer_create(str(vocab_path).encode(), 1 if lowercase else 0,
-                                                           int(max_seq_length), C.byref(h)), "icrec_tokenizer_create")
+        if specials is None or specials == BERT_SPECIALS:
+            _native.check(_native.lib().icrec_tokenizer_create(str(vocab_path).encode(), 1 if lowercase else 0,
+                                                               int(max_seq_length), C.byref(h)), "icrec_tokenizer_create")
+        else:
+            sp = [specials[k].encode() for k in ("cls_token", "sep_token", "unk_token", "pad_token", "mask_token")]
+            _native.check(_native.lib().icrec_tokenizer_create_ex(str(vocab_path).encode(), 1 if lowercase else 0,
+                                                                  int(max_seq_length), *sp, C.byref(h)),
+                          "icrec_tokenizer_create_ex")
         self._h, self.max_seq_length, self.n_threads = h, max_seq_length, n_threads
 
     def packed(self, texts: Sequence[str]) -> tuple[np.ndarray, np.ndarray]:
@@ -81,7 +113,8 @@ class NativeTokenizer:
 
 
 class HostTokenizer:
-    """BERT WordPiece tokenisation on the host ([CLS] ... [SEP], truncation to max_seq_length).
+    """BERT WordPiece tokenisation on the host ([CLS] ... [SEP], truncation to max_seq_length); a directory whose
+    tokenizer_config.json / special_tokens_map.json name other specials (MPNet: <s> ... </s>) gets those.
 
     backend "native" (default when the directory has vocab.txt): libicrec's C++ tokenizer, ~6x the
     throughput of the Rust one on 8 cores (68k vs 11k user contexts/s) — at >50k QPS per GPU the
@@ -101,10 +134,11 @@ class HostTokenizer:
             lower = bool(json.loads(tc.read_text()).get("do_lower_case", True))
         self.max_seq_length = max_seq_length
         self.backend = backend
+        self.specials = special_tokens(model_dir)
         if backend == "native":
             if not vt.exists():
                 raise FileNotFoundError(f"{vt} missing: the native tokenizer needs vocab.txt")
-            self._native_tok = NativeTokenizer(vt, lower, max_seq_length)
+            self._native_tok = NativeTokenizer(vt, lower, max_seq_length, specials=self.specials)
             return
         if backend != "tokenizers":
             raise ValueError(f"unknown tokenizer backend {backend!r}")
@@ -114,7 +148,7 @@ class HostTokenizer:
         if tj.exists():
             self._tok = Tokenizer.from_file(str(tj))
         elif vt.exists():
-            self._tok = BertWordPieceTokenizer(str(vt), lowercase=lower)._tokenizer
+            self._tok = BertWordPieceTokenizer(str(vt), lowercase=lower, **self.specials)._tokenizer
         else:
             raise FileNotFoundError(f"{model_dir} has neither tokenizer.json nor vocab.txt")
         self._tok.no_padding()
@@ -145,6 +179,11 @@ def load_model_dir(model_dir: Path | str) -> LoadedModel:
         raise FileNotFoundError(
             f"model_dir {model_dir!r} is not a local directory (hub ids cannot be fetched: no network)")
     cfg = json.loads((d / "config.json").read_text())
+    model_type = cfg.get("model_type", "bert")
+    if model_type not in ("bert", "mpnet"):
+        raise ValueError(f"unsupported model_type {model_type!r}: this encoder serves BERT and MPNet models "
+                         "(RoBERTa, DistilBERT and the other families name and arrange their weights differently)")
+    mpnet = model_type == "mpnet"
     if cfg.get("hidden_act", "gelu") != "gelu":
         raise ValueError(f"unsupported hidden_act {cfg.get('hidden_act')!r} (kernels implement erf-GELU)")
     n_norm = 1  # encode(..., normalize_embeddings=True) at every reference call site
@@ -168,15 +207,30 @@ def load_model_dir(model_dir: Path | str) -> LoadedModel:
                     if len(chosen) != 1 or chosen[0] not in served:
                         raise ValueError(f"only mean-token or CLS-token pooling, one of the two, is implemented (got {p})")
                     pooling = served[chosen[0]]
+    # MPNet: position ids start at padding_idx + 1 = 2 (rows 0 and 1 of the table are never read: max_position is two
+    # less), and there is no token-type table (one zero row stands in)
     shape = BertShape(vocab_size=int(cfg["vocab_size"]), hidden=int(cfg["hidden_size"]),
                       layers=int(cfg["num_hidden_layers"]), heads=int(cfg["num_attention_heads"]),
-                      intermediate=int(cfg["intermediate_size"]), max_position=int(cfg["max_position_embeddings"]),
-                      type_vocab=int(cfg.get("type_vocab_size", 2)), ln_eps=float(cfg.get("layer_norm_eps", 1e-12)),
-                      n_normalize=n_norm)
+                      intermediate=int(cfg["intermediate_size"]),
+                      max_position=int(cfg["max_position_embeddings"]) - (2 if mpnet else 0),
+                      type_vocab=1 if mpnet else int(cfg.get("type_vocab_size", 2)),
+                      ln_eps=float(cfg.get("layer_norm_eps", 1e-12)), n_normalize=n_norm)
     st = d / "model.safetensors"
     if not st.exists():
         raise FileNotFoundError(f"{st} missing (pytorch_model.bin pickles are not loaded: only safetensors)")
-    weights = state_dict_to_blob(load_file(str(st)), shape)
+    sd = load_file(str(st))
+    attention_bias = None
+    if mpnet:
+        if int(cfg.get("pad_token_id", 1)) != 1:
+            raise ValueError(f"MPNet with pad_token_id {cfg.get('pad_token_id')}: position ids are taken to start at 2")
+        sd, buckets = mpnet_to_bert_state_dict(sd, shape)
+        n_buckets = int(cfg.get("relative_attention_num_buckets", relative_bias.NUM_BUCKETS))
+        # (transformers buckets offsets into 32 whatever the config says: a table of another size is not an MPNet)
+        if buckets.shape != (n_buckets, shape.heads) or n_buckets != relative_bias.NUM_BUCKETS:
+            raise ValueError(f"relative_attention_bias.weight is {buckets.shape}, expected "
+                             f"({relative_bias.NUM_BUCKETS}, {shape.heads}) (relative_attention_num_buckets={n_buckets})")
+        attention_bias = relative_bias.table_from_buckets(buckets)
+    weights = state_dict_to_blob(sd, shape)
     max_len = DEFAULT_MAX_SEQ_LENGTH
     sb = d / "sentence_bert_config.json"
     if sb.exists():
@@ -187,36 +241,114 @@ def load_model_dir(model_dir: Path | str) -> LoadedModel:
         logger.warning("%s asks for max_seq_length %d; this encoder serves at most %d tokens for it: using %d",
                        d, max_len, limit, limit)
         max_len = limit
-    return LoadedModel(shape, weights, max_len, HostTokenizer(d, max_len), pooling)
+    return LoadedModel(shape, weights, max_len, HostTokenizer(d, max_len), pooling, attention_bias)
+
+
+#: MPNet's names of a layer's tensors -> BertModel's (the layer itself is a BERT layer: relative_bias.py has the one
+#: term that differs)
+_MPNET_TO_BERT = {"attention.attn.q": "attention.self.query", "attention.attn.k": "attention.self.key",
+                  "attention.attn.v": "attention.self.value", "attention.attn.o": "attention.output.dense",
+                  "attention.LayerNorm": "attention.output.LayerNorm"}
+
+
+def mpnet_to_bert_state_dict(sd: dict, shape: BertShape) -> tuple[dict, np.ndarray]:
+    """An MPNetModel state dict (optional 'mpnet.' prefix) -> (the BertModel-named dict state_dict_to_blob takes, the
+    [num_buckets, heads] relative-attention table).  `shape` is the BERT view: max_position two less than the table."""
+    sd = {(k[len("mpnet."):] if k.startswith("mpnet.") else k): np.asarray(v) for k, v in sd.items()}
+    out = {}
+    for k, v in sd.items():
+        for a, b in _MPNET_TO_BERT.items():
+            if f".{a}." in k:
+                k = k.replace(f".{a}.", f".{b}.")
+                break
+        out[k] = v
+    out["embeddings.position_embeddings.weight"] = sd["embeddings.position_embeddings.weight"][2:]
+    out["embeddings.token_type_embeddings.weight"] = np.zeros((1, shape.hidden), np.float32)
+    return out, np.asarray(out.pop("encoder.relative_attention_bias.weight"), np.float32)
+
+
+def bert_to_mpnet_state_dict(sd: dict, buckets: np.ndarray, seed: int) -> dict:
+    """The inverse, for write_synthetic_model_dir: MPNet names, no token-type table, two seeded rows (never read) in front
+    of the position table, the bucket table added."""
+    from .synthetic import normalish
+
+    out = {}
+    for k, v in sd.items():
+        for a, b in _MPNET_TO_BERT.items():
+            if f".{b}." in k:
+                k = k.replace(f".{b}.", f".{a}.")
+                break
+        out[k] = v
+    del out["embeddings.token_type_embeddings.weight"]
+    pos = out["embeddings.position_embeddings.weight"]
+    head = normalish(seed, 9_001, 2 * pos.shape[1], 0.05).reshape(2, pos.shape[1])
+    out["embeddings.position_embeddings.weight"] = np.concatenate([head, pos]).astype(np.float32)
+    out["encoder.relative_attention_bias.weight"] = np.asarray(buckets, np.float32)
+    return out
+
+
+def synthetic_mpnet_vocab() -> list[str]:
+    """synthetic_vocab() with MPNet's specials: <s>=0 <pad>=1 </s>=2 <unk>=3 in front, <mask> last, the BERT specials'
+    slots filled with unused entries so that every ordinary token keeps its id."""
+    v = synthetic_vocab()
+    for i, tok in enumerate(v):
+        if tok in BERT_SPECIALS.values():
+            v[i] = f"[unused_{i}]"
+    v[:4] = ["<s>", "<pad>", "</s>", "<unk>"]
+    return v + ["<mask>"]
 
 
 def write_synthetic_model_dir(path: Path | str, seed: int = 0, shape: BertShape | None = None,
-                              pooling: str = "mean") -> Path:
+                              pooling: str = "mean", architecture: str = "bert") -> Path:
     """Write a SentenceTransformer-layout directory with seeded random weights and the synthetic
     WordPiece vocab (stand-in for the fine-tuned all-MiniLM-L6-v2 that cannot be downloaded here).
-    pooling: "mean" or "cls", what 1_Pooling/config.json switches on (all-MiniLM: mean; the BGE family: cls)."""
+    pooling: "mean" or "cls", what 1_Pooling/config.json switches on (all-MiniLM: mean; the BGE family: cls).
+    architecture: "bert", or "mpnet" (all-mpnet-base-v2's layout): MPNet-named tensors with a [32, heads] relative-attention
+    table uniform in [-4, 4], an MPNet config.json and the vocab with MPNet's specials.  `shape` is then the BERT view
+    load_model_dir gives back - type_vocab 1, max_position two less than the written position table, ln_eps 1e-5 - and
+    by default BertShape(vocab_size=len(vocab), type_vocab=1, ln_eps=1e-5) at MiniLM's sizes."""
     from safetensors.numpy import save_file
 
     if pooling not in ("mean", "cls"):
         raise ValueError(f"pooling must be 'mean' or 'cls', got {pooling!r}")
+    if architecture not in ("bert", "mpnet"):
+        raise ValueError(f"architecture must be 'bert' or 'mpnet', got {architecture!r}")
+    mpnet = architecture == "mpnet"
     d = Path(path)
     d.mkdir(parents=True, exist_ok=True)
-    vocab = synthetic_vocab()
+    vocab = synthetic_mpnet_vocab() if mpnet else synthetic_vocab()
     if shape is None:
-        shape = BertShape(vocab_size=len(vocab))
+        shape = BertShape(vocab_size=len(vocab), type_vocab=1, ln_eps=1e-5) if mpnet else BertShape(vocab_size=len(vocab))
     if shape.vocab_size < len(vocab):
         raise ValueError("shape.vocab_size smaller than the synthetic vocab")
+    if mpnet and shape.type_vocab != 1:
+        raise ValueError("an MPNet has no token-type table: shape.type_vocab must be 1")
     blob = synthetic_bert_weights(shape, seed=seed)
-    save_file({k: np.ascontiguousarray(v) for k, v in blob_to_state_dict(blob, shape).items()},
-              str(d / "model.safetensors"))
-    (d / "config.json").write_text(json.dumps({
-        "architectures": ["BertModel"], "model_type": "bert", "vocab_size": shape.vocab_size,
-        "hidden_size": shape.hidden, "num_hidden_layers": shape.layers, "num_attention_heads": shape.heads,
-        "intermediate_size": shape.intermediate, "hidden_act": "gelu",
-        "max_position_embeddings": shape.max_position, "type_vocab_size": shape.type_vocab,
-        "layer_norm_eps": shape.ln_eps}, indent=2))
+    sd = blob_to_state_dict(blob, shape)
+    config = {"vocab_size": shape.vocab_size, "hidden_size": shape.hidden, "num_hidden_layers": shape.layers,
+              "num_attention_heads": shape.heads, "intermediate_size": shape.intermediate, "hidden_act": "gelu",
+              "layer_norm_eps": shape.ln_eps}
+    if mpnet:
+        from .synthetic import uniform
+
+        buckets = (8.0 * uniform(seed, 9_000, relative_bias.NUM_BUCKETS * shape.heads) - 4.0).astype(np.float32)
+        sd = bert_to_mpnet_state_dict(sd, buckets.reshape(relative_bias.NUM_BUCKETS, shape.heads), seed)
+        config.update({"architectures": ["MPNetModel"], "model_type": "mpnet",
+                       "max_position_embeddings": shape.max_position + 2,
+                       "relative_attention_num_buckets": relative_bias.NUM_BUCKETS,
+                       "pad_token_id": 1, "bos_token_id": 0, "eos_token_id": 2})
+        tok_cfg = {"do_lower_case": True, "tokenizer_class": "MPNetTokenizer", "bos_token": "<s>", "eos_token": "</s>",
+                   "cls_token": "<s>", "sep_token": "</s>", "unk_token": "<unk>", "pad_token": "<pad>",
+                   "mask_token": "<mask>"}
+        (d / "special_tokens_map.json").write_text(json.dumps({k: v for k, v in tok_cfg.items() if k.endswith("_token")}))
+    else:
+        config.update({"architectures": ["BertModel"], "model_type": "bert",
+                       "max_position_embeddings": shape.max_position, "type_vocab_size": shape.type_vocab})
+        tok_cfg = {"do_lower_case": True, "tokenizer_class": "BertTokenizer"}
+    save_file({k: np.ascontiguousarray(v) for k, v in sd.items()}, str(d / "model.safetensors"))
+    (d / "config.json").write_text(json.dumps(config, indent=2))
     (d / "vocab.txt").write_text("\n".join(vocab) + "\n")
-    (d / "tokenizer_config.json").write_text(json.dumps({"do_lower_case": True, "tokenizer_class": "BertTokenizer"}))
+    (d / "tokenizer_config.json").write_text(json.dumps(tok_cfg))
     (d / "sentence_bert_config.json").write_text(json.dumps({"max_seq_length": 256, "do_lower_case": False}))
     (d / "modules.json").write_text(json.dumps([
         {"idx": 0, "name": "0", "path": "", "type": "sentence_transformers.models.Transformer"},

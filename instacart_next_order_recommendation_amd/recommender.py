@@ -116,8 +116,9 @@ class SbertModel:
         self.shape = loaded.shape
         self.device = device
         self.pooling = loaded.pooling
+        self.attention_bias = loaded.attention_bias  # the MPNet family's relative-position table, or None
         self.encoder = DeviceEncoder(loaded.weights, loaded.shape, device, max_seq_length=loaded.max_seq_length,
-                                     pooling=loaded.pooling)
+                                     pooling=loaded.pooling, attention_bias=loaded.attention_bias)
         self._weights = loaded.weights
         self._encoder_no_flag: Optional[DeviceEncoder] = None  # normalize_embeddings=False: one normalisation fewer
 
@@ -145,7 +146,8 @@ class SbertModel:
 
                 self._encoder_no_flag = DeviceEncoder(self._weights, replace(self.shape, n_normalize=self.shape.n_normalize - 1),
                                                       self.device, gemm_mode=self.encoder.gemm_mode,
-                                                      max_seq_length=self.max_seq_length, pooling=self.pooling)
+                                                      max_seq_length=self.max_seq_length, pooling=self.pooling,
+                                                      attention_bias=self.attention_bias)
             enc = self._encoder_no_flag
         per_call = max(int(batch_size), 1) * 4096
         emb = enc.encode_packed_host(*self.tokenizer.packed(texts), max_tokens_per_call=per_call).cpu().numpy()
