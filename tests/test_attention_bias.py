@@ -1,6 +1,6 @@
 """The relative-position attention bias without a GPU: the ABI's NULL-handle answers, the MPNet bucket function against
 transformers, a synthetic MPNet model directory against transformers.MPNetModel in float64, the native tokenizer with
-MPNet's special tokens against the Rust one, and the proof that the float64 helper of tests/relative_bias.py would
+MPNet's special tokens against the Rust one, and the proof that the float64 reference (oracle/float64_reference.py) would
 notice a mirrored, shifted or head-rotated table."""
 from __future__ import annotations
 
@@ -9,6 +9,7 @@ import pytest
 
 from instacart_next_order_recommendation_amd import relative_bias as rb
 from instacart_next_order_recommendation_amd import synthetic as syn
+from oracle import float64_reference as f64
 from tests import relative_bias as tb
 from tests import token_states as ts
 from tests.encoder_harness import packed
@@ -73,7 +74,7 @@ def test_synthetic_mpnet_dir_against_transformers(tmp_path, hidden):
     rng = np.random.default_rng(5)
     cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
     ids = rng.integers(4, n_vocab, int(cu[-1])).astype(np.int32)  # (no <pad>: transformers counts positions by it)
-    got, _ = tb.encode(m.weights, m.shape, ids, cu, m.attention_bias, torch.float64)
+    got, _ = f64.encode(m.weights, m.shape, ids, cu, attention_bias=m.attention_bias)
 
     model = tr.MPNetModel.from_pretrained(str(d), torch_dtype=torch.float64).double().eval()
     padded = np.ones((len(lens), max(lens)), np.int64)  # pad_token_id 1
@@ -88,7 +89,7 @@ def test_synthetic_mpnet_dir_against_transformers(tmp_path, hidden):
     print(f"synthetic MPNet directory, hidden {hidden}: max |helper - transformers| = {err:.2e}")
     assert err < 1e-10
     # the bias is not a no-op in this model
-    plain, _ = tb.encode(m.weights, m.shape, ids, cu, None, torch.float64)
+    plain, _ = f64.encode(m.weights, m.shape, ids, cu)
     assert np.abs(plain - want).max() > 1e-3
 
 
@@ -151,14 +152,14 @@ def test_float64_helper_notices_a_wrong_table(kind):
     t = tb.table("dense", s.heads)
     wrong = {"mirrored": np.ascontiguousarray(t[:, ::-1]), "shifted_by_one": np.roll(t, 1, axis=1),
              "rotated_by_one_head": np.roll(t, 1, axis=0)}
-    margin = max(max(tb.TOKEN_MARGINS[(mode, 384, kind)]) for mode in ("f32", "f16x3"))
+    margin = max(max(ts.TOKEN_MARGINS[(mode, 384, kind)]) for mode in ("f32", "f16x3"))
     for n in SENSITIVITY_LENS:
         ids, cu = packed([n], 40 + n, ts.VOCAB)
-        h64, _ = tb.encode(w, s, ids, cu, t, torch.float64)
-        h32, _ = tb.encode(w, s, ids, cu, t, torch.float32)
+        h64, _ = f64.encode(w, s, ids, cu, attention_bias=t)
+        h32, _ = f64.encode(w, s, ids, cu, dtype=torch.float32, attention_bias=t)
         e_rms, e_abs = ts.row_errors(h32, h64)
         for name, tw in wrong.items():
-            bad, _ = tb.encode(w, s, ids, cu, tw, torch.float64)
+            bad, _ = f64.encode(w, s, ids, cu, attention_bias=tw)
             b_rms, b_abs = ts.row_errors(bad, h64)
             print(f"{kind} length {n} {name}: rms {b_rms:.3e} = {b_rms / (margin * e_rms):.0f} x bound, "
                   f"abs {b_abs:.3e} = {b_abs / (margin * e_abs):.0f} x bound")

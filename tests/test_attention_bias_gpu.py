@@ -1,5 +1,5 @@
 """The relative-position attention bias on the GPU (icrec_encoder_set_attention_bias, DeviceEncoder(attention_bias=)):
-token states and embeddings against the float64 / float32 helper of tests/relative_bias.py, the same bits in every
+token states and embeddings against the float64 / float32 reference (oracle/float64_reference.py), the same bits in every
 dispatch form, CLS pooling with a bias, the setter's semantics, poisoned workspaces, graph capture, and a synthetic MPNet
 model directory served end to end."""
 from __future__ import annotations
@@ -11,26 +11,11 @@ import pytest
 
 from tests import relative_bias as tb
 from tests import token_states as ts
-from tests.encoder_harness import packed, round_plus_remainder, run
+from tests.encoder_harness import FORMS, long_rounds_plus_remainder, make_encoder, packed, poisoned_runs, replay_matches_eager, run
 
 pytestmark = pytest.mark.gpu
 
 MODES = ("f32", "f16x3")
-
-
-def _encoder(monkeypatch, w, shape, mode="f16x3", max_seq_length=None, pooling="mean", table=None, **env):
-    """A DeviceEncoder with a bias table, created under the given ICREC_* settings (read once, at creation)."""
-    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-
-    for k, v in env.items():
-        monkeypatch.setenv(k, str(v))
-    try:
-        enc = DeviceEncoder(w, shape, gemm_mode=mode, max_seq_length=max_seq_length, pooling=pooling, attention_bias=table)
-    finally:
-        for k in env:
-            monkeypatch.delenv(k)
-    assert enc.has_attention_bias == (table is not None)
-    return enc
 
 
 # ---------------------------------------------------------------- 1. against the reference
@@ -45,27 +30,23 @@ def test_token_states_and_embeddings_against_the_reference(monkeypatch, mode, hi
     check, token states only).  Prints the ratios before it asserts (profiles/attention_bias_errors.md holds the measured
     ones)."""
     r = tb.reference(kind, hidden, layers, batch, table_name)
-    enc = _encoder(monkeypatch, r["w"], r["s"], mode, max_seq_length=r["max_len"], table=r["table"])
+    enc = make_encoder(monkeypatch, r["w"], r["s"], mode, max_seq_length=r["max_len"], attention_bias=r["table"])
     emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
     plain = run(enc, r["ids"], r["cu"])
     enc.close()
     assert tok.shape == r["h64"].shape and np.isfinite(tok).all() and np.isfinite(emb).all()
     np.testing.assert_array_equal(plain, emb)  # icrec_encode and icrec_encode_ex: the same launches
     case = f"mode={mode} hidden={hidden} layers={layers} weights={kind} table={table_name} batch={batch}"
-    tb.check(f"tokens {case}", tok, r["h64"], r["h32"], tb.margins(r, mode), r["cu"])
+    ts.check(f"tokens {case}", tok, r["h64"], r["h32"], tb.margins(r, mode), r["cu"])
     if r["table"] is not None:
-        tb.check(f"embeddings {case}", emb, r["e64"], r["e32"], tb.margins(r, mode, "embeddings"))
+        ts.check(f"embeddings {case}", emb, r["e64"], r["e32"], tb.margins(r, mode, "embeddings"))
 
 
 # ---------------------------------------------------------------- 2. same bits in every form
-FORMS = [("default", {}), ("unfused", {"ICREC_FUSE": 0}), ("one_stream", {"ICREC_SIDE_STREAM": 0}),
-         ("batch_form", {"ICREC_SMALL_M": 4})]
-
-
 def _same_bits_in_every_form(monkeypatch, w, s, table, ids, cu, alone):
     got = {}
-    for form, env in FORMS:
-        enc = _encoder(monkeypatch, w, s, max_seq_length=512, table=table, **env)
+    for form, env in FORMS + [("batch_form", {"ICREC_SMALL_M": 4})]:
+        enc = make_encoder(monkeypatch, w, s, max_seq_length=512, attention_bias=table, **env)
         emb, tok = run(enc, ids, cu, return_tokens=True)
         got[form] = (run(enc, ids, cu), tok)
         np.testing.assert_array_equal(emb, got[form][0], err_msg=form)
@@ -98,23 +79,11 @@ def test_same_bits_in_every_form_small_batch(monkeypatch, hidden, layers, table_
 def test_same_bits_in_every_form_rounds_plus_remainder(monkeypatch, hidden):
     """Whole rounds of 64 tokens per CU plus a remainder (the side stream's range) with sequences of up to 512 tokens, 2
     layers, dense table: the four forms write the same bits; every sequence longer than 256 alone equals its batch row."""
-    from instacart_next_order_recommendation_amd import synthetic as syn
-
     s = ts.shape(hidden, 2)
     w = ts.weights("sharp", s)
-    _, cu0 = syn.synthetic_token_batch(420, seed=11, mean_len=90, std_len=60, lo=1, hi=256, vocab_size=ts.VOCAB)
-    lens = np.diff(cu0)
-    long_at = np.arange(3, 420, 12)
-    lens[long_at] = np.linspace(257, 512, long_at.size).astype(np.int64)
-    cu_all = np.concatenate([[0], np.cumsum(lens)])
     table = tb.table("dense", s.heads)
-    probe = _encoder(monkeypatch, w, s, max_seq_length=512, table=table)
-    n, main_t, tail_t = round_plus_remainder(probe, cu_all, 1, np.inf, first=64)
-    probe.close()
-    assert tail_t and main_t > 0 and n > 64, (main_t, tail_t, n)
-    ids, cu = packed(lens[:n].tolist(), 4, ts.VOCAB)
+    ids, cu, _ = long_rounds_plus_remainder(monkeypatch, w, s, ts.VOCAB, attention_bias=table)
     long = np.flatnonzero(np.diff(cu) > 256)
-    assert long.size >= 3
     _same_bits_in_every_form(monkeypatch, w, s, table, ids, cu, alone=long)
 
 
@@ -127,9 +96,9 @@ def test_cls_pooling_with_a_bias(monkeypatch, hidden, layers, batch):
     from oracle import oracle
 
     r = tb.reference("sharp", hidden, layers, batch, "dense")
-    kw = dict(max_seq_length=r["max_len"], pooling="cls", table=r["table"])
-    pruned = _encoder(monkeypatch, r["w"], r["s"], **kw)
-    full = _encoder(monkeypatch, r["w"], r["s"], ICREC_CLS_PRUNE=0, **kw)
+    kw = dict(max_seq_length=r["max_len"], pooling="cls", attention_bias=r["table"])
+    pruned = make_encoder(monkeypatch, r["w"], r["s"], **kw)
+    full = make_encoder(monkeypatch, r["w"], r["s"], ICREC_CLS_PRUNE=0, **kw)
     a = run(pruned, r["ids"], r["cu"])
     b = run(full, r["ids"], r["cu"])
     c, tok = run(pruned, r["ids"], r["cu"], return_tokens=True)
@@ -140,7 +109,9 @@ def test_cls_pooling_with_a_bias(monkeypatch, hidden, layers, batch):
     for _ in range(r["s"].n_normalize):
         rows = oracle.normalize_rows(rows)
     np.testing.assert_array_equal(a, rows)
-    tb.check(f"cls embeddings hidden={hidden} layers={layers} batch={batch}", a, r["c64"], r["c32"], tb.margins(r, "f16x3", "embeddings"))
+    n = r["s"].n_normalize
+    ts.check(f"cls embeddings hidden={hidden} layers={layers} batch={batch}", a, r["cls64"][n], r["cls32"][n],
+             tb.margins(r, "f16x3", "embeddings"))
 
 
 # ---------------------------------------------------------------- 4. setter semantics
@@ -155,8 +126,8 @@ def test_setter_semantics(monkeypatch, mode):
     L = _native.lib()
     r = tb.reference("sharp", 384, 1, "to256", "dense")
     s, n, T = r["s"], r["cu"].size - 1, int(r["cu"][-1])
-    never = _encoder(monkeypatch, r["w"], s, mode)
-    enc = _encoder(monkeypatch, r["w"], s, mode)
+    never = make_encoder(monkeypatch, r["w"], s, mode)
+    enc = make_encoder(monkeypatch, r["w"], s, mode)
     ws_bytes = L.icrec_encode_workspace_bytes(never._h, T, n)
     before = run(never, r["ids"], r["cu"])
     enc.set_attention_bias(r["table"])
@@ -194,51 +165,18 @@ def test_setter_semantics(monkeypatch, mode):
 @pytest.mark.parametrize("batch", list(tb.BATCHES))
 @pytest.mark.parametrize("hidden", [384, 768])
 def test_poisoned_workspace_never_reaches_the_embeddings(monkeypatch, hidden, batch):
-    import torch
-
-    from instacart_next_order_recommendation_amd import _native
-
     r = tb.reference("sharp", hidden, 1 if hidden == 384 else 2, batch, "dense")
-    enc = _encoder(monkeypatch, r["w"], r["s"], max_seq_length=r["max_len"], table=r["table"])
-    args = (torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda(), int(np.diff(r["cu"]).max()))
-    enc.encode_packed(*args)  # sizes the workspace
-    ws = enc._ws_by_stream[torch.cuda.current_stream().cuda_stream]
-    assert ws.numel() == _native.lib().icrec_encode_workspace_bytes(enc._h, int(r["cu"][-1]), r["cu"].size - 1)
-    out = []
-    for fill in (0xFF, 0x00, 0x7F):
-        ws.fill_(fill)
-        out.append(enc.encode_packed(*args).cpu().numpy())
-        assert np.isfinite(out[-1]).all(), f"workspace byte 0x{fill:02X} leaked into the embeddings"
-    np.testing.assert_array_equal(out[0], out[1])
-    np.testing.assert_array_equal(out[0], out[2])
+    enc = make_encoder(monkeypatch, r["w"], r["s"], max_seq_length=r["max_len"], attention_bias=r["table"])
+    poisoned_runs(enc, r["ids"], r["cu"])
     enc.close()
 
 
 # ---------------------------------------------------------------- 6. graph capture
 def test_biased_encode_under_graph_capture(monkeypatch):
     """A captured biased encode, replayed once over a poisoned workspace of its own, writes the eager bits."""
-    import torch
-
     r = tb.reference("sharp", 384, 6, "to256", "dense")
-    enc = _encoder(monkeypatch, r["w"], r["s"], table=r["table"])
-    ids, cu = torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda()
-    n, T, mx = r["cu"].size - 1, int(r["cu"][-1]), int(np.diff(r["cu"]).max())
-    eager = enc.encode_packed(ids, cu, mx).cpu().numpy()
-    out = torch.zeros((n, 384), dtype=torch.float32, device="cuda")
-    ws = torch.empty(enc._ws_by_stream[torch.cuda.current_stream().cuda_stream].numel(), dtype=torch.uint8, device="cuda")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):  # warm-up outside the capture, as fastpath.py does
-        enc.encode_into(ids, cu, n, T, mx, out, ws)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        enc.encode_into(ids, cu, n, T, mx, out, ws)
-    out.zero_(); ws.fill_(0xFF)
-    g.replay()
-    torch.cuda.synchronize()
-    np.testing.assert_array_equal(out.cpu().numpy(), eager)
+    enc = make_encoder(monkeypatch, r["w"], r["s"], attention_bias=r["table"])
+    replay_matches_eager(enc, r["ids"], r["cu"])
     enc.close()
 
 
@@ -248,20 +186,21 @@ E2E_TOP_K, E2E_MIN_RANKS, NEAR_TIE = 20, 10, 1e-5
 
 
 def e2e_reference(model_dir, product_texts, queries):
-    """The float64 pipeline (tokenise, tests/relative_bias.encode in float64, cosine scores, descending order, lower row
-    first on ties) and the float32 helper's embeddings.  Per query: the top-20 rows and how many leading ranks stand
+    """The float64 pipeline (tokenise, oracle/float64_reference.py in float64, cosine scores, descending order, lower row
+    first on ties) and the float32 reference's embeddings.  Per query: the top-20 rows and how many leading ranks stand
     before the first near-tie (adjacent reference scores within 1e-5)."""
     import torch
 
     from instacart_next_order_recommendation_amd.encoder import pack_token_ids
     from instacart_next_order_recommendation_amd.model_io import load_model_dir
+    from oracle import float64_reference as f64
 
     m = load_model_dir(model_dir)
     out = {}
     for name, texts in (("P", product_texts), ("Q", queries)):
         ids, cu, _ = pack_token_ids(m.tokenizer(texts))
-        out[name + "64"] = tb.encode(m.weights, m.shape, ids, cu, m.attention_bias, torch.float64)[1]
-        out[name + "32"] = tb.encode(m.weights, m.shape, ids, cu, m.attention_bias, torch.float32)[1]
+        out[name + "64"] = f64.encode(m.weights, m.shape, ids, cu, attention_bias=m.attention_bias)[1]
+        out[name + "32"] = f64.encode(m.weights, m.shape, ids, cu, dtype=torch.float32, attention_bias=m.attention_bias)[1]
     scores = out["Q64"] @ out["P64"].T
     order = np.argsort(-scores, axis=1, kind="stable")[:, :E2E_TOP_K + 1]
     top = np.take_along_axis(scores, order, axis=1)
@@ -298,12 +237,12 @@ def test_mpnet_model_dir_through_recommender(tmp_path):
     ref = e2e_reference(rec.model_dir, rec.product_texts, queries)
     assert min(ref["ranks"]) >= E2E_MIN_RANKS, ref["ranks"]
     # the directory's weights are neither of token_states' two sets: the wider of their two margins at this width
-    m = tuple(max(tb.EMB_MARGINS[("f16x3", 768, k)][i] for k in ts.KINDS) for i in range(2))
-    tb.check("end to end, catalog embeddings", rec.product_embeddings, ref["P64"], ref["P32"], m)
-    tb.check("end to end, query embeddings", rec.model.encode(queries), ref["Q64"], ref["Q32"], m)
+    m = tuple(max(ts.EMB_MARGINS[("f16x3", 768, k)][i] for k in ts.KINDS) for i in range(2))
+    ts.check("end to end, catalog embeddings", rec.product_embeddings, ref["P64"], ref["P32"], m)
+    ts.check("end to end, query embeddings", rec.model.encode(queries), ref["Q64"], ref["Q32"], m)
     unnorm = rec.model.encode(queries, normalize_embeddings=False)
     assert rec.model._encoder_no_flag.has_attention_bias
-    tb.check("end to end, normalize_embeddings=False", unnorm, ref["Q64"], ref["Q32"], m)  # (unit rows either way)
+    ts.check("end to end, normalize_embeddings=False", unnorm, ref["Q64"], ref["Q32"], m)  # (unit rows either way)
 
     graph = [rec.recommend(q, E2E_TOP_K) for q in queries]
     assert rec._fast._graphs  # the single-request graphs were captured with the biased encoder

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
-from tests.encoder_harness import EMB_TOL, make_encoder, n_cu, oracle_rows, packed, round_plus_remainder, run
+from tests.encoder_harness import EMB_TOL, make_encoder, n_cu, oracle_rows, packed, poisoned_runs, round_plus_remainder, run
 
 pytestmark = pytest.mark.gpu
 
@@ -104,18 +104,8 @@ def test_rounds_plus_remainder_on_the_side_stream(monkeypatch, base2):
 @pytest.mark.parametrize("mode", ["f32", "f16x3"])
 def test_workspace_contents_never_leak_into_results(monkeypatch, base2, mode):
     """A workspace full of NaN bit patterns gives the same bits as a zeroed one."""
-    import torch
-
     enc = make_encoder(monkeypatch, base2["w"], base2["shape"], mode)
-    ids, cu = base2["ids"], base2["cu"]
-    run(enc, ids, cu)
-    ws = enc._ws_by_stream[torch.cuda.current_stream().cuda_stream]
-    out = []
-    for fill in (0xFF, 0x00):
-        ws.fill_(fill)
-        out.append(run(enc, ids, cu))
-        assert np.isfinite(out[-1]).all(), f"workspace byte 0x{fill:02X} leaked into the embeddings"
-    np.testing.assert_array_equal(out[0], out[1])
+    poisoned_runs(enc, base2["ids"], base2["cu"], fills=(0xFF, 0x00))
     enc.close()
 
 

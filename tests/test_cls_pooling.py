@@ -1,5 +1,5 @@
 """CLS pooling without a GPU: the model-directory loader's pooling modes, and the references tests/test_cls_pooling_gpu.py
-compares against (tests/cls_pooling.py) - that the fp32 and the float64 reference agree as closely as their hidden
+compares against (tests/cls_pooling.py, tests/token_states.py) - that the fp32 and the float64 reference agree as closely as their hidden
 states say they must, and that on the GPU tests' inputs a CLS embedding is far enough from the mean embedding of the
 same sequence for the GPU bound to tell the two apart."""
 from __future__ import annotations
@@ -84,16 +84,16 @@ def test_references_agree_and_cls_is_not_mean(kind, hidden, layers, batch):
     r = cp.reference(kind, hidden, layers, batch)
     cu = r["cu"]
     first = cu[:-1].astype(np.int64)
-    e_rms, _ = ts.row_errors(r["ora_h"], r["want_h"])
+    e_rms, _ = ts.row_errors(r["h32"], r["h64"])
     m_rms, _ = ts.MARGINS[("f32", hidden, kind)]
-    h_norm = float(np.linalg.norm(r["want_h"][first], axis=1).min())
+    h_norm = float(np.linalg.norm(r["h64"][first], axis=1).min())
     for n in cp.N_NORMALIZE:
         got = float(np.abs(r["cls32"][n].astype(np.float64) - r["cls64"][n]).max())
         limit = m_rms * np.sqrt(hidden) * e_rms / h_norm + n * 32 * 2.0 ** -24
         print(f"[{kind} {hidden}x{layers} {batch} n_normalize={n}] max|cls32 - cls64| = {got:.3e} (limit {limit:.3e})")
         assert 0 < got <= limit
         assert np.abs(np.linalg.norm(r["cls64"][n], axis=1) - 1).max() < 1e-12
-        loosest = max(cp.bound(r, mode, n)[1] for mode in MODES)
+        loosest = max(ts.MARGINS[(mode, hidden, kind)][1] for mode in MODES) * ts.row_errors(r["cls32"][n], r["cls64"][n])[1]
         many = np.flatnonzero(np.diff(cu) >= 2)
         assert many.size >= 3
         apart = np.abs(r["cls64"][n][many] - r["mean64"][n][many]).max(axis=1)

@@ -12,24 +12,12 @@ import pytest
 
 from tests import cls_pooling as cp
 from tests import token_states as ts
-from tests.encoder_harness import EMB_TOL, make_encoder, packed, round_plus_remainder, run
+from tests.encoder_harness import (EMB_TOL, FORMS, long_rounds_plus_remainder, make_encoder, packed, poisoned_runs,
+                                   replay_matches_eager, run)
 
 pytestmark = pytest.mark.gpu
 
 MODES = ("f32", "f16x3")
-
-
-def _encoder(monkeypatch, w, shape, mode="f16x3", max_seq_length=None, pooling="cls", **env):
-    """encoder_harness.make_encoder with a pooling mode: the ICREC_* settings hold during creation only."""
-    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-
-    for k, v in env.items():
-        monkeypatch.setenv(k, str(v))
-    try:
-        return DeviceEncoder(w, shape, gemm_mode=mode, max_seq_length=max_seq_length, pooling=pooling)
-    finally:
-        for k in env:
-            monkeypatch.delenv(k)
 
 
 def _with_n_normalize(shape, n):
@@ -44,23 +32,18 @@ def _with_n_normalize(shape, n):
 @pytest.mark.parametrize("hidden,layers", cp.SHAPES)
 @pytest.mark.parametrize("mode", MODES)
 def test_cls_embeddings_against_the_references(monkeypatch, mode, hidden, layers, kind, batch):
-    """E_gpu <= margin x E_ref (tests/cls_pooling.py), per-row rms and max abs, for n_normalize 1 and 2; f32 mode also
+    """E_gpu <= margin x E_ref (tests/token_states.py), per-row rms and max abs, for n_normalize 1 and 2; f32 mode also
     within EMB_TOL of the fp32 oracle's CLS embedding.  Prints the ratios before it asserts
     (profiles/cls_pooling_errors.md holds the measured ones)."""
     r = cp.reference(kind, hidden, layers, batch)
-    assert cp.bound(r, mode, 1)[3] > 0
     for n in cp.N_NORMALIZE:
-        enc = _encoder(monkeypatch, r["w"], _with_n_normalize(r["s"], n), mode, max_seq_length=r["max_len"])
+        enc = make_encoder(monkeypatch, r["w"], _with_n_normalize(r["s"], n), mode, max_seq_length=r["max_len"], pooling="cls")
         assert enc.pooling == "cls"
         emb = run(enc, r["ids"], r["cu"])
         enc.close()
         assert emb.shape == r["cls64"][n].shape and emb.dtype == np.float32 and np.isfinite(emb).all()
-        b_rms, b_abs, e_rms, e_abs = cp.bound(r, mode, n)
-        g_rms, g_abs = ts.row_errors(emb, r["cls64"][n])
-        print(f"cls embeddings mode={mode} hidden={hidden} layers={layers} weights={kind} batch={batch} n_normalize={n}: "
-              f"E_gpu rms {g_rms:.3e} abs {g_abs:.3e}, E_ref rms {e_rms:.3e} abs {e_abs:.3e}, "
-              f"ratio rms {g_rms / e_rms:.2f} abs {g_abs / e_abs:.2f} (margins {b_rms / e_rms:.0f} / {b_abs / e_abs:.0f})")
-        assert g_rms <= b_rms and g_abs <= b_abs, (mode, hidden, layers, kind, batch, n)
+        ts.check(f"cls embeddings mode={mode} hidden={hidden} layers={layers} weights={kind} batch={batch} n_normalize={n}",
+                 emb, r["cls64"][n], r["cls32"][n], ts.MARGINS[(mode, hidden, kind)])
         if mode == "f32":
             assert np.abs(emb - r["cls32"][n]).max() < EMB_TOL
 
@@ -70,8 +53,8 @@ def _three_forms(monkeypatch, w, shape, ids, cu, max_seq_length=None, **env):
     """The CLS embeddings of one batch from the pruned last layer, from the full one (ICREC_CLS_PRUNE=0) and from the
     call that also returns every token (full last layer, by contract): asserted bitwise equal; returns them and the
     pruned encoder (caller closes it)."""
-    pruned = _encoder(monkeypatch, w, shape, max_seq_length=max_seq_length, **env)
-    full = _encoder(monkeypatch, w, shape, max_seq_length=max_seq_length, ICREC_CLS_PRUNE=0, **env)
+    pruned = make_encoder(monkeypatch, w, shape, max_seq_length=max_seq_length, pooling="cls", **env)
+    full = make_encoder(monkeypatch, w, shape, max_seq_length=max_seq_length, pooling="cls", ICREC_CLS_PRUNE=0, **env)
     a = run(pruned, ids, cu)
     b = run(full, ids, cu)
     c, tok = run(pruned, ids, cu, return_tokens=True)
@@ -85,17 +68,6 @@ def _three_forms(monkeypatch, w, shape, ids, cu, max_seq_length=None, **env):
     return a, pruned
 
 
-def _big_lens(n, seed):
-    """n sequences of 1-256 tokens with one of 257-512 at every twelfth place."""
-    from instacart_next_order_recommendation_amd import synthetic as syn
-
-    _, cu = syn.synthetic_token_batch(n, seed=seed, mean_len=90, std_len=60, lo=1, hi=256, vocab_size=ts.VOCAB)
-    lens = np.diff(cu)
-    long_at = np.arange(3, n, 12)
-    lens[long_at] = np.linspace(257, 512, long_at.size).astype(np.int64)
-    return lens.tolist()
-
-
 @pytest.mark.parametrize("hidden", [384, 768])
 def test_pruned_full_and_token_forms_agree_bitwise_large_batch(monkeypatch, hidden):
     """Whole rounds of 64 tokens per CU plus a remainder (the side stream's range), sequences of up to 512 tokens, 2
@@ -104,22 +76,14 @@ def test_pruned_full_and_token_forms_agree_bitwise_large_batch(monkeypatch, hidd
     the same bits; every sequence of more than 256 tokens encoded alone equals its batch row."""
     s = ts.shape(hidden, 2)
     w = ts.weights("sharp", s)
-    lens = _big_lens(420, seed=11)
-    cu_all = np.concatenate([[0], np.cumsum(lens)])
-    probe = make_encoder(monkeypatch, w, s, max_seq_length=512)
-    n, main_t, tail_t = round_plus_remainder(probe, cu_all, 1, np.inf, first=64)
-    probe.close()
-    assert tail_t and main_t > 0 and n > 64, (main_t, tail_t, n)
-    ids, cu = packed(lens[:n], 4, ts.VOCAB)
+    ids, cu, split = long_rounds_plus_remainder(monkeypatch, w, s, ts.VOCAB)
     lens = np.diff(cu)
-    assert (lens > 256).sum() >= 3
     got = {}
-    for form, env in [("default", {}), ("unfused", {"ICREC_FUSE": 0}), ("one_stream", {"ICREC_SIDE_STREAM": 0}),
-                      ("compact_batch_form", {"ICREC_SMALL_M": 64}),
-                      ("compact_batch_form_unfused", {"ICREC_SMALL_M": 64, "ICREC_FUSE": 0})]:
+    for form, env in FORMS + [("compact_batch_form", {"ICREC_SMALL_M": 64}),
+                              ("compact_batch_form_unfused", {"ICREC_SMALL_M": 64, "ICREC_FUSE": 0})]:
         got[form], enc = _three_forms(monkeypatch, w, s, ids, cu, max_seq_length=512, **env)
         if form == "default":
-            assert enc.batch_split(int(cu[-1])) == (main_t, tail_t)
+            assert enc.batch_split(int(cu[-1])) == split
             for i in np.flatnonzero(lens > 256):
                 alone = run(enc, ids[cu[i]:cu[i + 1]].copy(), np.array([0, lens[i]], np.int32))
                 np.testing.assert_array_equal(alone[0], got[form][i], err_msg=f"sequence {i} ({lens[i]} tokens) alone")
@@ -140,8 +104,7 @@ def test_pruned_full_and_token_forms_agree_bitwise_small(monkeypatch, hidden, la
     w = ts.weights("sharp", s)
     ids, cu = packed(lens, 6, ts.VOCAB)
     got = {}
-    for form, env in [("default", {}), ("unfused", {"ICREC_FUSE": 0}), ("one_stream", {"ICREC_SIDE_STREAM": 0}),
-                      ("batch_form", {"ICREC_SMALL_M": 4}), ("batch_form_unfused", {"ICREC_SMALL_M": 4, "ICREC_FUSE": 0})]:
+    for form, env in FORMS + [("batch_form", {"ICREC_SMALL_M": 4}), ("batch_form_unfused", {"ICREC_SMALL_M": 4, "ICREC_FUSE": 0})]:
         got[form], enc = _three_forms(monkeypatch, w, s, ids, cu, max_seq_length=512, **env)
         if form == "default" and len(lens) > 1:
             for i, n in enumerate(lens):
@@ -165,7 +128,7 @@ def test_cls_embedding_is_the_normalised_first_token_row(monkeypatch, mode, hidd
 
     r = cp.reference("sharp", hidden, layers, "to256")
     s = _with_n_normalize(r["s"], n_norm)
-    enc = _encoder(monkeypatch, r["w"], s, mode)
+    enc = make_encoder(monkeypatch, r["w"], s, mode, pooling="cls")
     emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
     plain = run(enc, r["ids"], r["cu"])
     want = np.ascontiguousarray(tok[r["cu"][:-1]])
@@ -173,7 +136,7 @@ def test_cls_embedding_is_the_normalised_first_token_row(monkeypatch, mode, hidd
         want = oracle.normalize_rows(want)
     np.testing.assert_array_equal(emb, want)
     np.testing.assert_array_equal(plain, want)
-    mean = _encoder(monkeypatch, r["w"], s, mode, pooling="mean")
+    mean = make_encoder(monkeypatch, r["w"], s, mode, pooling="mean")
     assert mean.pooling == "mean"
     mean_emb, mean_tok = run(mean, r["ids"], r["cu"], return_tokens=True)
     np.testing.assert_array_equal(mean_tok, tok)  # the token states do not depend on the pooling mode
@@ -226,13 +189,10 @@ def test_mean_encoder_is_untouched(monkeypatch, mode):
 def test_poisoned_workspace_never_reaches_the_cls_embeddings(monkeypatch, hidden, shape):
     """Every workspace byte - the compact rows' regions and the context rows no CLS query wrote included - holds a NaN
     pattern before a pruned call: no NaN reaches `out`, and the bits are those of a zeroed workspace."""
-    import torch
-
-    from instacart_next_order_recommendation_amd import _native
     from instacart_next_order_recommendation_amd import synthetic as syn
 
     s = ts.shape(hidden, 2)
-    enc = _encoder(monkeypatch, ts.weights("sharp", s), s)
+    enc = make_encoder(monkeypatch, ts.weights("sharp", s), s, pooling="cls")
     kw = dict(vocab_size=ts.VOCAB)
     if shape == "short_batch":
         ids, cu = syn.synthetic_token_batch(700, seed=3, mean_len=25, std_len=6, lo=8, hi=40, **kw)
@@ -242,44 +202,15 @@ def test_poisoned_workspace_never_reaches_the_cls_embeddings(monkeypatch, hidden
         ids, cu = packed([5, 33, 128, 256, 1, 2, 64, 97], 2, ts.VOCAB)
     else:
         ids, cu = packed([70], 5, ts.VOCAB)
-    args = (torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), int(np.diff(cu).max()))
-    enc.encode_packed(*args)  # sizes the workspace
-    ws = enc._ws_by_stream[torch.cuda.current_stream().cuda_stream]
-    assert ws.numel() == _native.lib().icrec_encode_workspace_bytes(enc._h, int(cu[-1]), cu.size - 1)
-    out = []
-    for fill in (0xFF, 0x00, 0x7F):
-        ws.fill_(fill)
-        out.append(enc.encode_packed(*args).cpu().numpy())
-        assert np.isfinite(out[-1]).all(), f"workspace byte 0x{fill:02X} leaked into the embeddings"
-    np.testing.assert_array_equal(out[0], out[1])
-    np.testing.assert_array_equal(out[0], out[2])
+    poisoned_runs(enc, ids, cu)
     enc.close()
 
 
 def test_pruned_call_under_graph_capture(monkeypatch):
     """The pruned call is capturable: a replayed graph over a poisoned workspace of its own writes the eager bits."""
-    import torch
-
     r = cp.reference("sharp", 384, 6, "to256")
-    enc = _encoder(monkeypatch, r["w"], r["s"])
-    ids, cu = torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda()
-    n, T, mx = r["cu"].size - 1, int(r["cu"][-1]), int(np.diff(r["cu"]).max())
-    eager = enc.encode_packed(ids, cu, mx).cpu().numpy()
-    out = torch.zeros((n, 384), dtype=torch.float32, device="cuda")
-    ws = torch.empty(enc._ws_by_stream[torch.cuda.current_stream().cuda_stream].numel(), dtype=torch.uint8, device="cuda")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):  # warm-up outside the capture, as fastpath.py does
-        enc.encode_into(ids, cu, n, T, mx, out, ws)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        enc.encode_into(ids, cu, n, T, mx, out, ws)
-    out.zero_(); ws.fill_(0xFF)
-    g.replay()
-    torch.cuda.synchronize()
-    np.testing.assert_array_equal(out.cpu().numpy(), eager)
+    enc = make_encoder(monkeypatch, r["w"], r["s"], pooling="cls")
+    replay_matches_eager(enc, r["ids"], r["cu"])
     enc.close()
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from tests import token_states as ts
-from tests.encoder_harness import make_encoder, packed, round_plus_remainder, run
+from tests.encoder_harness import make_encoder, poisoned_runs, replay_matches_eager, round_plus_remainder, run
 
 pytestmark = pytest.mark.gpu
 
@@ -22,25 +22,6 @@ EDGE_LENS = [1, 2, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129, 159, 160, 
              255, 256, 257, 383, 384, 385, 511, 512]
 MIXED_LENS = [5, 33, 128, 256, 1, 2, 64, 97]
 
-_refs: dict = {}
-
-
-def _reference(kind, hidden, layers, lens, seed):
-    """Weights, inputs, the float64 hidden states and the oracle's hidden states: computed once per batch,
-    shared by the modes and forms that run it."""
-    key = (kind, hidden, layers, tuple(lens), seed)
-    if key not in _refs:
-        from oracle import float64_reference as f64
-        from oracle import oracle
-
-        s = ts.shape(hidden, layers)
-        w = ts.weights(kind, s)
-        ids, cu = packed(lens, seed, ts.VOCAB)
-        want_h, _ = f64.encode(w, s, ids, cu)
-        _, ora_h = oracle.encode(w, oracle.cfg_for(s), ids, cu, return_hidden=True)
-        _refs[key] = dict(s=s, w=w, ids=ids, cu=cu, want_h=want_h, ora_h=ora_h, kind=kind)
-    return _refs[key]
-
 
 def _check(what, mode, r, emb, tok, first_seq=0, n_seqs=None):
     """tok (sequences [first_seq, first_seq + n_seqs) of r's batch; all by default) against the float64 hidden states
@@ -49,17 +30,11 @@ def _check(what, mode, r, emb, tok, first_seq=0, n_seqs=None):
     n_seqs = r["cu"].size - 1 - first_seq if n_seqs is None else n_seqs
     cu = r["cu"][first_seq: first_seq + n_seqs + 1].astype(np.int64)
     rows = slice(int(cu[0]), int(cu[-1]))
-    want, ora = r["want_h"][rows], r["ora_h"][rows]
+    want, ora = r["h64"][rows], r["h32"][rows]
     cu = cu - cu[0]
     assert tok.shape == want.shape and tok.dtype == np.float32 and np.isfinite(tok).all()
-    e_rms, e_abs = ts.row_errors(ora, want)
-    g_rms, g_abs = ts.row_errors(tok, want)
-    m_rms, m_abs = ts.MARGINS[(mode, s.hidden, kind)]
-    print(f"token states [{what}] mode={mode} hidden={s.hidden} layers={s.layers} weights={kind} tokens={tok.shape[0]}: "
-          f"E_gpu rms {g_rms:.3e} abs {g_abs:.3e}, E_ref rms {e_rms:.3e} abs {e_abs:.3e}, "
-          f"ratio rms {g_rms / e_rms:.2f} abs {g_abs / e_abs:.2f} (margins {m_rms} / {m_abs})")
-    assert g_rms <= m_rms * e_rms and g_abs <= m_abs * e_abs, \
-        f"{what} mode={mode} weights={kind}: " + ts.worst_element(tok, want, cu)
+    ts.check(f"token states [{what}] mode={mode} hidden={s.hidden} layers={s.layers} weights={kind} tokens={tok.shape[0]}",
+             tok, want, ora, ts.MARGINS[(mode, s.hidden, kind)], cu)
     # The embedding of the same call is the mean of these rows, normalised.  fp32 pooling sums n rows one after the
     # other: |error of the mean| <= n u mean|h| (u = 2^-24); the two normalisations (fmaf chain of H / 64, a 6-step
     # butterfly, sqrt, divide) cost at most 32 more roundings of a component that is <= 1.
@@ -83,7 +58,7 @@ def test_small_batch_every_width(monkeypatch, mode, hidden, layers, kind):
     """~590 tokens in 8 sequences: the small / latency forms.  6 layers and 1 layer at hidden 384 (layer 0's stand-alone
     QKV, the next-layer QKV prologue / epilogue and the last layer without one are different code), 2 layers at 768.
     f16x3 also under ICREC_FUSE=0 (separate LayerNorm launches)."""
-    r = _reference(kind, hidden, layers, MIXED_LENS, seed=2)
+    r = ts.reference(kind, hidden, layers, MIXED_LENS, seed=2)
     for env in ({}, {"ICREC_FUSE": 0}) if mode == "f16x3" else ({},):
         enc = make_encoder(monkeypatch, r["w"], r["s"], mode, **env)
         emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
@@ -105,7 +80,7 @@ def test_batch_forms(monkeypatch, hidden, kind):
     chain (ICREC_FUSE=0) and f32.  Hidden 768: the slab-ring form (default above 3,584 tokens, and forced on the same
     batch's first 1,500 tokens with ICREC_SMALL_M=512), the latency form of those 1,500 tokens, and f32."""
     lens = _batch_lens(60, seed=33)
-    r = _reference(kind, hidden, 2, lens, seed=3)
+    r = ts.reference(kind, hidden, 2, lens, seed=3)
     assert r["cu"][-1] > 3584 + 512
     for mode, env in (("f32", {}), ("f16x3", {}), ("f16x3", {"ICREC_FUSE": 0})):
         enc = make_encoder(monkeypatch, r["w"], r["s"], mode, **env)
@@ -130,12 +105,12 @@ def test_rounds_plus_remainder(monkeypatch, hidden, kind):
     remainder, which runs through the small-batch kernels on the library's side stream."""
     lens = _batch_lens(400, seed=11)
     cu_all = np.concatenate([[0], np.cumsum(lens)])
-    r = _reference(kind, hidden, 2, [4], seed=0)
+    r = ts.reference(kind, hidden, 2, [4], seed=0)
     probe = make_encoder(monkeypatch, r["w"], r["s"], "f16x3")
     n, main_t, tail_t = round_plus_remainder(probe, cu_all, 1, np.inf, first=64)
     probe.close()
     assert tail_t and main_t > 0 and n >= 64, (main_t, tail_t, n)
-    r = _reference(kind, hidden, 2, lens[:n], seed=4)
+    r = ts.reference(kind, hidden, 2, lens[:n], seed=4)
     enc = make_encoder(monkeypatch, r["w"], r["s"], "f16x3")
     assert enc.batch_split(int(r["cu"][-1])) == (main_t, tail_t)
     emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
@@ -149,7 +124,7 @@ def test_rounds_plus_remainder(monkeypatch, hidden, kind):
 def test_attention_bucket_edges(monkeypatch, mode, hidden, layers, kind):
     """Ceiling raised to 512: a sequence on each side of every key-tile bucket edge, all in one batch, then each alone
     (a lone sequence may take another bucket's kernel than the same sequence in a batch)."""
-    r = _reference(kind, hidden, layers, EDGE_LENS, seed=5)
+    r = ts.reference(kind, hidden, layers, EDGE_LENS, seed=5)
     enc = make_encoder(monkeypatch, r["w"], r["s"], mode, max_seq_length=512)
     emb, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
     _check("edges mixed", mode, r, emb, tok)
@@ -166,53 +141,18 @@ def test_attention_bucket_edges(monkeypatch, mode, hidden, layers, kind):
 def test_token_output_changes_nothing_and_reads_nothing_stale(monkeypatch, mode, hidden, layers):
     """The embeddings of a call that also returns tokens are those of plain encode_packed bit for bit; a workspace and a
     tokens_out buffer full of 0xFF give the same token bits as zeroed ones."""
-    import torch
-
-    r = _reference("sharp", hidden, layers, MIXED_LENS, seed=2)
+    r = ts.reference("sharp", hidden, layers, MIXED_LENS, seed=2)
     enc = make_encoder(monkeypatch, r["w"], r["s"], mode)
-    ids, cu = torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda()
-    mx = int(np.diff(r["cu"]).max())
-    plain = enc.encode_packed(ids, cu, mx).cpu().numpy()
-    ws = enc._ws_by_stream[torch.cuda.current_stream().cuda_stream]
-    buf = torch.empty((int(r["cu"][-1]), hidden), dtype=torch.float32, device="cuda")
-    got = []
-    for fill in (0xFF, 0x00):
-        ws.fill_(fill)
-        buf.view(torch.uint8).fill_(fill)
-        emb, tok = enc.encode_packed(ids, cu, mx, return_tokens=True, tokens_out=buf)
-        assert tok.data_ptr() == buf.data_ptr()
-        got.append((emb.cpu().numpy(), tok.cpu().numpy()))
-        assert np.isfinite(got[-1][1]).all(), f"byte 0x{fill:02X} leaked into the token states"
-        np.testing.assert_array_equal(got[-1][0], plain)
-    np.testing.assert_array_equal(got[0][1], got[1][1])
-    np.testing.assert_array_equal(enc.encode_packed(ids, cu, mx).cpu().numpy(), plain)
+    plain = run(enc, r["ids"], r["cu"])
+    emb, _ = poisoned_runs(enc, r["ids"], r["cu"], fills=(0xFF, 0x00), tokens=True)
+    np.testing.assert_array_equal(emb, plain)
+    np.testing.assert_array_equal(run(enc, r["ids"], r["cu"]), plain)
     enc.close()
 
 
 def test_token_output_under_graph_capture(monkeypatch):
     """icrec_encode_ex is capturable like icrec_encode: a replayed graph writes the same token bits as the eager call."""
-    import torch
-
-    r = _reference("sharp", 384, 6, MIXED_LENS, seed=2)
+    r = ts.reference("sharp", 384, 6, MIXED_LENS, seed=2)
     enc = make_encoder(monkeypatch, r["w"], r["s"], "f16x3")
-    ids, cu = torch.from_numpy(r["ids"]).cuda(), torch.from_numpy(r["cu"]).cuda()
-    n, T, mx = r["cu"].size - 1, int(r["cu"][-1]), int(np.diff(r["cu"]).max())
-    emb, tok = enc.encode_packed(ids, cu, mx, return_tokens=True)
-    out = torch.zeros((n, 384), dtype=torch.float32, device="cuda")
-    buf = torch.zeros((T, 384), dtype=torch.float32, device="cuda")
-    ws = torch.empty(enc._ws_by_stream[torch.cuda.current_stream().cuda_stream].numel(), dtype=torch.uint8, device="cuda")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):  # warm-up outside the capture, as fastpath.py does
-        enc.encode_into(ids, cu, n, T, mx, out, ws, tokens=buf)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        enc.encode_into(ids, cu, n, T, mx, out, ws, tokens=buf)
-    buf.zero_(); out.zero_()
-    g.replay()
-    torch.cuda.synchronize()
-    np.testing.assert_array_equal(buf.cpu().numpy(), tok.cpu().numpy())
-    np.testing.assert_array_equal(out.cpu().numpy(), emb.cpu().numpy())
+    replay_matches_eager(enc, r["ids"], r["cu"], tokens=True)
     enc.close()

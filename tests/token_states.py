@@ -1,9 +1,12 @@
-"""Shared by tests/test_token_states.py (CPU), tests/test_token_states_gpu.py and tools/fuzz_encoder.py: the two weight
-sets, the error metric and the margins of the per-token comparison against oracle/float64_reference.py.
+"""Shared by the token-state, CLS-pooling and attention-bias tests (CPU and GPU) and tools/fuzz_encoder.py: the two weight
+sets, the cases' references (`reference`), the error metric, the margins and the one comparison (`check`) against
+oracle/float64_reference.py.
 
 The bound a GPU result must meet is never a number written down here: it is `margin x E_ref`, where E_ref is the error
-of the fp32 C oracle against the float64 reference ON THE SAME INPUTS under the same metric (`row_errors`), and
-the margin comes from MARGINS, chosen from the ratios measured on the MI355X (profiles/token_state_errors.md).
+of an fp32 implementation against the float64 reference ON THE SAME INPUTS under the same metric (`row_errors`) - the
+fp32 C oracle, or, where a case has an attention bias (the oracle knows none), the reference's own code in float32 -
+and the margin comes from MARGINS (chosen from the ratios measured on the MI355X, profiles/token_state_errors.md) or,
+with a bias, TOKEN_MARGINS / EMB_MARGINS (profiles/attention_bias_errors.md).
 """
 from __future__ import annotations
 
@@ -30,6 +33,28 @@ MARGINS = {
     ("f16x3", 384, "standard"): (3, 6), ("f16x3", 384, "sharp"): (3, 4),
     ("f16x3", 768, "standard"): (2, 2), ("f16x3", 768, "sharp"): (2, 3),
 }
+
+#: margin on E_ref per (gemm mode, hidden, weight set): (per-token-row rms, max abs) - TOKEN_MARGINS for the token states
+#: of the biased cases, EMB_MARGINS for their pooled rows (mean and CLS embeddings: the reference pools with torch's
+#: pairwise mean, the kernels add the tokens in order, so a pooled row's ratios are larger than its tokens').  Each is
+#: the smallest of {2, 3, 4, 6, 8} that leaves 1.5x headroom over the worst ratio E_gpu / E_ref measured on the MI355X
+#: over every case of tests/test_attention_bias_gpu.py (profiles/attention_bias_errors.md holds the ratios; the worst of
+#: all is 5.13, under 8 / 1.5).
+TOKEN_MARGINS = {
+    ("f32", 384, "standard"): (2, 2), ("f32", 384, "sharp"): (2, 2),
+    ("f32", 768, "standard"): (2, 2), ("f32", 768, "sharp"): (2, 2),
+    ("f16x3", 384, "standard"): (3, 3), ("f16x3", 384, "sharp"): (3, 4),
+    ("f16x3", 768, "standard"): (2, 2), ("f16x3", 768, "sharp"): (2, 2),
+}
+EMB_MARGINS = {
+    ("f32", 384, "standard"): (6, 6), ("f32", 384, "sharp"): (6, 8),
+    ("f32", 768, "standard"): (6, 6), ("f32", 768, "sharp"): (4, 6),
+    ("f16x3", 384, "standard"): (6, 8), ("f16x3", 384, "sharp"): (6, 8),
+    ("f16x3", 768, "standard"): (6, 6), ("f16x3", 768, "sharp"): (6, 6),
+}
+
+#: the n_normalize values `reference` prepares CLS / mean embeddings for
+N_NORMALIZE = (1, 2)
 
 
 def shape(hidden: int, layers: int) -> syn.BertShape:
@@ -105,3 +130,69 @@ def worst_element(got: np.ndarray, want: np.ndarray, cu: np.ndarray) -> str:
                    f"feature {f}, got {float(got[t, f]):.9g}, want {float(want[t, f]):.9g}, "
                    f"row rms error {float(np.sqrt((d[t] ** 2).mean())):.3e}")
     return "; ".join(out)
+
+
+def normalize_rows(v: np.ndarray, n: int) -> np.ndarray:
+    """n times v / max(|v|_2, 1e-12) per row, in v's own precision."""
+    for _ in range(n):
+        v = v / np.maximum(np.linalg.norm(v, axis=1, keepdims=True), v.dtype.type(1e-12))
+    return v
+
+
+_refs: dict = {}
+
+
+def reference(kind: str, hidden: int, layers: int, lens, seed: int, max_len=None, table=None, ref32: str = "oracle") -> dict:
+    """Weights, inputs and both precisions' results of one case, computed once and shared by every test that runs it;
+    the weights and every result are read-only (ids and cu stay writable: torch.from_numpy warns about memory that is not):
+
+    s, w, ids, cu, kind, max_len (the encoder's max_seq_length), table (float32 [heads, 1023] or None);
+    h64 / e64      the float64 reference's token states / mean-pooled embeddings;
+    h32 / e32      the same from the fp32 implementation whose error is E_ref: the C oracle (ref32 = "oracle", cases
+                   without a table only) or the reference's own code in float32 (ref32 = "float32");
+    cls64[n] / mean64[n] / cls32[n], n in N_NORMALIZE: the first-token rows of h64, the float64 means of each sequence's
+                   rows of h64 and the first-token rows of h32, normalised n times - cls32 by the implementation that
+                   made h32 (oracle.normalize_rows, or float32 numpy)."""
+    key = (kind, hidden, layers, tuple(lens), seed, max_len, None if table is None else table.tobytes(), ref32)
+    if key not in _refs:
+        import torch
+
+        from oracle import float64_reference as f64
+        from oracle import oracle
+
+        s = shape(hidden, layers)
+        w = weights(kind, s)
+        ids, cu = packed(lens, seed, VOCAB)
+        h64, e64 = f64.encode(w, s, ids, cu, attention_bias=table)
+        first = cu[:-1].astype(np.int64)
+        if ref32 == "oracle":
+            assert table is None, "the C oracle knows no attention bias"
+            e32, h32 = oracle.encode(w, oracle.cfg_for(s), ids, cu, return_hidden=True)
+            cls32 = {0: np.ascontiguousarray(h32[first])}
+            for n in range(1, max(N_NORMALIZE) + 1):
+                cls32[n] = oracle.normalize_rows(cls32[n - 1])
+        else:
+            assert ref32 == "float32", ref32
+            h32, e32 = f64.encode(w, s, ids, cu, dtype=torch.float32, attention_bias=table)
+            cls32 = {n: normalize_rows(h32[first], n) for n in N_NORMALIZE}
+        mean_h = np.stack([h64[a:b].mean(0) for a, b in zip(cu[:-1], cu[1:])])
+        r = dict(s=s, w=w, ids=ids, cu=cu, kind=kind, max_len=max_len, table=table, h64=h64, e64=e64, h32=h32, e32=e32,
+                 cls64={n: normalize_rows(h64[first], n) for n in N_NORMALIZE},
+                 mean64={n: normalize_rows(mean_h, n) for n in N_NORMALIZE},
+                 cls32={n: cls32[n] for n in N_NORMALIZE})
+        for a in (w, h64, e64, h32, e32, *r["cls64"].values(), *r["mean64"].values(), *r["cls32"].values()):
+            a.setflags(write=False)
+        _refs[key] = r
+    return _refs[key]
+
+
+def check(what: str, got: np.ndarray, want64: np.ndarray, ref32: np.ndarray, margin, cu=None):
+    """Prints `RATIO ...` (E_gpu / E_ref, rms and max abs), then asserts E_gpu <= margin x E_ref for both; with `cu` a
+    failure names the worst token and element."""
+    e_rms, e_abs = row_errors(ref32, want64)
+    g_rms, g_abs = row_errors(got, want64)
+    assert e_rms > 0 and e_abs > 0
+    print(f"RATIO {what}: E_gpu rms {g_rms:.3e} abs {g_abs:.3e}, E_ref rms {e_rms:.3e} abs {e_abs:.3e}, "
+          f"ratio rms {g_rms / e_rms:.2f} abs {g_abs / e_abs:.2f} (margins {margin[0]} / {margin[1]})")
+    where = "" if cu is None else worst_element(got, want64, cu)
+    assert g_rms <= margin[0] * e_rms and g_abs <= margin[1] * e_abs, (what, where)
