@@ -842,6 +842,11 @@ __global__ __launch_bounds__(256) void gather_cls_rows_kernel(const _Float16* __
 // ---------------------------------------------------------------- host side
 constexpr int HID = 384;     // all-MiniLM width: 32-dim heads, the fused layer kernels
 constexpr int HID_BASE = 768;  // BERT-base width: 64-dim heads, the unfused chain
+// f(h) with the hidden size (HID or HID_BASE: icrec_encoder_create admits no other) as the compile-time constant h()
+template <class F>
+static auto for_hidden(int hidden, F f) {
+    return hidden == HID_BASE ? f(std::integral_constant<int, HID_BASE>{}) : f(std::integral_constant<int, HID>{});
+}
 
 struct LayerW {
     float *Wqkv, *bqkv, *Wo, *bo, *g1, *b1n, *W1, *b1, *W2, *b2, *g2, *b2n;
@@ -1001,8 +1006,9 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
         }
     } else {
         const int nbn = N / 384;
-        // the residual epilogue at hidden 768 reads residual rows of 768 features (EPI 3)
-        auto kern = EPI == 2 && N == HID_BASE ? wt_linear_kernel<3, 2, 1, 3> : wt_linear_kernel<3, 2, 1, EPI>;
+        auto kern = wt_linear_kernel<3, 2, 1, EPI>;
+        // the residual epilogue reads residual rows of N = hidden features
+        if constexpr (EPI == 2) kern = for_hidden(N, [](auto h) { return wt_linear_kernel<3, 2, 1, 2, h()>; });
         hipLaunchKernelGGL(kern, dim3(((T + 63) / 64) * nbn), dim3(256), 0, st, Xh, Xl, T, K, Wp, N, bias, out, oh, ol,
                            nbn);
     }
@@ -1262,8 +1268,8 @@ static const int32_t* embed(const Encoder* e, const EncBufs& b, const int32_t* i
         order = reinterpret_cast<int32_t*>(b.x);
         hipLaunchKernelGGL(seq_order_kernel, dim3(1), dim3(1024), 0, st, cu_dev, n_seqs, order);
     }
-    const auto kern = c.hidden == HID_BASE ? (x3 ? embed_ln_kernel<HID_BASE, true> : embed_ln_kernel<HID_BASE, false>)
-                                           : (x3 ? embed_ln_kernel<HID, true> : embed_ln_kernel<HID, false>);
+    const auto kern =
+        for_hidden(c.hidden, [x3](auto h) { return x3 ? embed_ln_kernel<h(), true> : embed_ln_kernel<h(), false>; });
     hipLaunchKernelGGL(kern, dim3((T + 3) / 4), dim3(256), 0, st, ids_dev, cu_dev, n_seqs, T, e->word, e->pos, e->type, e->eg, e->eb, c.ln_eps, c.vocab_size,
                        c.max_position, b.x, b.xh, b.xl);
     return order;
@@ -1296,8 +1302,8 @@ static int encode_x3(Encoder* e, const EncBufs& b, const EncBufs* cls, const int
                      int max_seqlen, const int32_t* order, hipStream_t st) {
     const icrec_bert_cfg& c = e->cfg;
     const int H = c.hidden, I = c.intermediate;
-    const bool base = H == HID_BASE;
-    const bool split_att = !base && e->side_stream && n_seqs >= 64 && max_seqlen > 128;  // batches with a long bucket
+    const auto ln_wt = for_hidden(H, [](auto h) { return ln_wt_kernel<h()>; });
+    const bool split_att = H == HID && e->side_stream && n_seqs >= 64 && max_seqlen > 128;  // batches with a long bucket
     // Token ranges: [0, T_main) goes through the batch kernels in whole rounds of one 64-token workgroup per CU, a short
     // remainder [T_main, T) through the small-batch kernels (same arithmetic, same bits) instead of costing every batch
     // kernel an extra, almost empty round.
@@ -1360,15 +1366,15 @@ static int encode_x3(Encoder* e, const EncBufs& b, const EncBufs* cls, const int
                                (const float*)t1r, r.n, L.g1, L.b1n, c.ln_eps, xhr, xlr, L.W1_p, I, L.b1, (float*)nullptr,
                                hhr, hlr, nbn);
         } else {
-            hipLaunchKernelGGL(base ? ln_wt768_kernel : ln_wt_kernel, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n,
-                               L.g1, L.b1n, c.ln_eps, xhr, xlr);
+            hipLaunchKernelGGL(ln_wt, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n, L.g1, L.b1n, c.ln_eps,
+                               xhr, xlr);
             ScopedTimer tm(r.small ? T_NSLOTS - 1 : T_FFN_UP, r.st);
             launch_wt_linear<1>(xhr, xlr, r.n, H, L.W1_p, I, L.b1, nullptr, hhr, hlr, r.st, r.small);
         }
         launch_wt_linear<2>(hhr, hlr, r.n, I, L.W2_p, H, L.b2, t1r, xhr, xlr, r.st, r.small);
         if (!r.ffn_ln_to_next(l, c.layers))
-            hipLaunchKernelGGL(base ? ln_wt768_kernel : ln_wt_kernel, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n,
-                               L.g2, L.b2n, c.ln_eps, xhr, xlr);
+            hipLaunchKernelGGL(ln_wt, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n, L.g2, L.b2n, c.ln_eps,
+                               xhr, xlr);
     };
 
     if (tail_on_side) ICREC_HIP(link(sd, st, sd->side));  // the side stream starts behind the embeddings
@@ -1413,8 +1419,7 @@ static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev,
                       hipStream_t st) {
     const icrec_bert_cfg& c = e->cfg;
     const int H = c.hidden, I = c.intermediate, rows_grid = (T + 3) / 4;
-    const bool base = H == HID_BASE;
-    const auto add_ln = base ? add_ln_kernel<HID_BASE> : add_ln_kernel<HID>;
+    const auto add_ln = for_hidden(H, [](auto h) { return add_ln_kernel<h()>; });
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& L = e->layers[l];
         launch_linear<false>(b.x, T, H, L.Wqkv, 3 * H, L.bqkv, b.qkv, st);
@@ -1469,8 +1474,8 @@ int icrec_encode_ex(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_
     if (int rc_ = x3 ? encode_x3(e, b, pruned ? &cls : nullptr, cu_dev, n_seqs, T, max_seqlen, order, st)
                      : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
         return rc_;
-    const auto pool = H == HID_BASE ? (x3 ? pool_norm_kernel<HID_BASE, true> : pool_norm_kernel<HID_BASE, false>)
-                                    : (x3 ? pool_norm_kernel<HID, true> : pool_norm_kernel<HID, false>);
+    const auto pool =
+        for_hidden(H, [x3](auto h) { return x3 ? pool_norm_kernel<h(), true> : pool_norm_kernel<h(), false>; });
     const EncBufs& last = pruned ? cls : b;  // where the last hidden state of the pooled rows is
     const int pool_rows = e->pooling != ICREC_POOL_CLS ? POOL_ROWS_MEAN : pruned ? POOL_ROWS_CLS_COMPACT : POOL_ROWS_CLS;
     hipLaunchKernelGGL(pool, dim3(n_seqs), dim3(H), 0, st, last.x, last.xh, last.xl, cu_dev, c.n_normalize, out_dev,

@@ -308,7 +308,7 @@ __device__ __forceinline__ void wt_ln_block(Acc32 (&acc)[3][TTW], int q, int tb,
 // q*96 + i*32 + fi*16 + 4g + reg, in (i, fi, reg) order, the 16 partials are combined by shuffles in the fixed tree of
 // wt_ln_block.  store(feat, hi, lo) takes the planes of the four features at feat, for each (i, fi) in that order.
 // ln_wt_kernel and the prologue of wt_linear_lnin_kernel both run it: identical bits.
-// H = 768 (BERT-base width; only ln_wt768_kernel) is the same tree over twice the values: thread (q, g) sums its 48
+// H = 768 (BERT-base width; only ln_wt_kernel<768>) is the same tree over twice the values: thread (q, g) sums its 48
 // values, features q*192 + i*32 + fi*16 + 4g + reg (i < 6), in (i, fi, reg) order; mean and variance divide by 768.
 template <int H = 384, class Store>
 __device__ __forceinline__ void ln16_row(const float* row, const float* gam, const float* bet, float eps, int q, int g,
@@ -362,36 +362,22 @@ __device__ __forceinline__ void ln16_row(const float* row, const float* gam, con
         }
 }
 
-// planes(x) <- LN(a), 16 tokens per workgroup (small batches; the unfused reference chain)
+// planes(x) <- LN(a) over H features, 16 tokens per workgroup (small batches; the unfused reference chain, which every
+// 768-wide model runs)
+template <int H>
 __global__ __launch_bounds__(256) void ln_wt_kernel(const float* __restrict__ a, int T, const float* __restrict__ gam,
                                                     const float* __restrict__ bet, float eps,
                                                     _Float16* __restrict__ xh, _Float16* __restrict__ xl) {
     const int tid = threadIdx.x, slot = tid & 15, q = slot >> 2, g = slot & 3;
     const int64_t tok = (int64_t)blockIdx.x * 16 + (tid >> 4);
     const bool ok = tok < T;
-    ln16_row(a + (ok ? tok : (int64_t)T - 1) * 384, gam, bet, eps, q, g, (tid & 63) & ~15,
-             [=](int feat, const half4& hi, const half4& lo) {
-                 if (ok) {
-                     *reinterpret_cast<half4*>(xh + tok * 384 + feat) = hi;
-                     *reinterpret_cast<half4*>(xl + tok * 384 + feat) = lo;
-                 }
-             });
-}
-
-// the same at hidden 768 (ln16_row<768>; the unfused chain every 768-wide model runs)
-__global__ __launch_bounds__(256) void ln_wt768_kernel(const float* __restrict__ a, int T, const float* __restrict__ gam,
-                                                       const float* __restrict__ bet, float eps,
-                                                       _Float16* __restrict__ xh, _Float16* __restrict__ xl) {
-    const int tid = threadIdx.x, slot = tid & 15, q = slot >> 2, g = slot & 3;
-    const int64_t tok = (int64_t)blockIdx.x * 16 + (tid >> 4);
-    const bool ok = tok < T;
-    ln16_row<768>(a + (ok ? tok : (int64_t)T - 1) * 768, gam, bet, eps, q, g, (tid & 63) & ~15,
-                  [=](int feat, const half4& hi, const half4& lo) {
-                      if (ok) {
-                          *reinterpret_cast<half4*>(xh + tok * 768 + feat) = hi;
-                          *reinterpret_cast<half4*>(xl + tok * 768 + feat) = lo;
-                      }
-                  });
+    ln16_row<H>(a + (ok ? tok : (int64_t)T - 1) * H, gam, bet, eps, q, g, (tid & 63) & ~15,
+                [=](int feat, const half4& hi, const half4& lo) {
+                    if (ok) {
+                        *reinterpret_cast<half4*>(xh + tok * H + feat) = hi;
+                        *reinterpret_cast<half4*>(xl + tok * H + feat) = lo;
+                    }
+                });
 }
 
 constexpr int LN_LD = 388;  // floats per staged output row in LDS (+16 B: the 16-B accesses of consecutive tokens hit distinct banks)
@@ -401,15 +387,15 @@ constexpr int LN_LD = 388;  // floats per staged output row in LDS (+16 B: the 1
 // token slab staged through LDS.  Block = 4 waves; wave q owns NTW 32-feature blocks x TTW 32-token blocks.
 //   EPI 0: out fp32 [T, N] = acc * 2^-14 + bias           (QKV)
 //   EPI 1: erf-GELU (tf:336), result as f16 hi/lo planes   (FFN-up of small batches)
-//   EPI 2: residual + bias (planes oh / ol, row stride 384) added to the accumulators after the K loop, out fp32 =
-//          acc * 2^-14: the LayerNorm input of attention-out / FFN-down (ln_wt_kernel follows)
-//   EPI 3: EPI 2 at hidden 768 (residual row stride 768, two 384-feature blocks per row; ln_wt768_kernel follows)
+//   EPI 2: residual + bias (planes oh / ol, row stride RS = the hidden size: at 768 two 384-feature blocks per row)
+//          added to the accumulators after the K loop, out fp32 = acc * 2^-14: the LayerNorm input of attention-out /
+//          FFN-down (ln_wt_kernel<RS> follows)
 // Two forms: <1, 1, 4, 1>, the small-batch FFN-up (weights four k-steps ahead; small batches and the remainder of a batch
 // take wt_linear_half_kernel for EPI 0 / 2): 32-token x 128-feature workgroups, latency-bound.  <3, 2, 1, EPI>: the
 // 64-token x 384-feature form of the UNFUSED reference chain (ICREC_FUSE=0: tests compare the fused kernels against it
 // bit for bit); its EPI 0 / 2 results leave through an LDS stage.
 // Each lane holds 4 consecutive features of one token per register group: 16-B (fp32) / 8-B (planes) stores.
-template <int NTW, int TTW, int D, int EPI>
+template <int NTW, int TTW, int D, int EPI, int RS = 384>
 __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __restrict__ Xh,
                                                            const _Float16* __restrict__ Xl, int T, int K,
                                                            const _Float16* __restrict__ Wp, int N,
@@ -419,8 +405,8 @@ __global__ __launch_bounds__(256, 2) void wt_linear_kernel(const _Float16* __res
     static_assert((NTW == 1 && TTW == 1 && D == 4 && EPI == 1) || (NTW == 3 && TTW == 2 && D == 1),
                   "the small-batch FFN-up <1, 1, 4, 1> or the batch form <3, 2, 1, EPI>");
     constexpr bool STAGED = EPI != 1;  // results leave through an LDS stage, coalesced
-    constexpr bool RES = EPI == 2 || EPI == 3;
-    constexpr int RS = EPI == 3 ? 768 : 384;  // residual row stride
+    static_assert(RS == 384 || (RS == 768 && EPI == 2), "residual row stride: the hidden size");
+    constexpr bool RES = EPI == 2;
     constexpr int SM = (STAGED && 32 * LN_LD * 4 > XRing<TTW>::BYTES) ? 32 * LN_LD * 4 : XRing<TTW>::BYTES;
     __shared__ __attribute__((aligned(16))) char smem[SM];
     const int lane = threadIdx.x & 63, q = wave_uniform(threadIdx.x >> 6), c = lane & 15, g = lane >> 4;
@@ -528,12 +514,44 @@ __device__ __forceinline__ void ffn_x_bases(int (&xb)[2][2], int c, int g) {
 #pragma unroll
         for (int ti = 0; ti < 2; ++ti) xb[tt][ti] = (tt * 32 + ti * 16 + c) * 768 + ((g ^ c) << 4);
 }
+template <int XPLANE = FFN2_XPLANE>  // bytes per plane: 64 token rows, or 32 (wt_linear_lnin_kernel, tt = 0 only)
 __device__ __forceinline__ void ffn_x_frag(XFrag& x, const char* Xs, const int (&xb)[2][2], int tt, int ks) {
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti) {
         const int pos = (xb[tt][ti] ^ ((ks & 3) << 6)) + (ks >> 2) * 256;
         x.h[ti] = *reinterpret_cast<const half8*>(Xs + pos);
-        x.l[ti] = *reinterpret_cast<const half8*>(Xs + FFN2_XPLANE + pos);
+        x.l[ti] = *reinterpret_cast<const half8*>(Xs + XPLANE + pos);
+    }
+}
+
+// K = 384 of one 32-feature block nt over the 64 tokens of the resident image: S[tt] = W[nt] . X[tt]^T as twelve
+// straight-line k-steps of two units (u = 2 ks + tt), the fragments of unit u + 1 read under the MFMAs of unit u.  The
+// weight ring is four k-steps deep: on entry w holds k-steps 0 .. 3 of block nt (the caller's loads, or the previous
+// call's), on exit those of block nn (nn == nt past the last block: this one's re-read, never consumed).  Wp is a
+// plain pointer: as a __restrict__ one it reorders the ring loads of both callers.
+__device__ __forceinline__ void resident_block_k384(Acc32 (&S)[2], const char* Xs, const int (&xb)[2][2],
+                                                    WFrag (&w)[4][1], const _Float16* Wp, int nt, int nn, unsigned lo8) {
+    constexpr int KS1 = 12;
+    const _Float16* const wp1[1] = {Wp + wt_frag_off(nt, 0, KS1)};
+    const _Float16* const wpn[1] = {Wp + wt_frag_off(nn, 0, KS1)};
+    acc_zero(S[0]);
+    acc_zero(S[1]);
+    XFrag x[2];
+    ffn_x_frag(x[0], Xs, xb, 0, 0);
+#pragma unroll
+    for (int ks = 0; ks < KS1; ++ks) {
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const int u = 2 * ks + tt;
+            if (u + 1 < 2 * KS1) {
+                ffn_x_frag(x[(u + 1) & 1], Xs, xb, (u + 1) & 1, (u + 1) >> 1);
+                __builtin_amdgcn_sched_barrier(0);  // the next unit's LDS reads are issued before this unit's 12 MFMAs
+            }
+            wt_mma_block(S[tt], w[ks & 3][0], x[u & 1]);
+        }
+        if (ks + 4 < KS1) w_load<1>(w[ks & 3], wp1, ks + 4, lo8);
+        else w_load<1>(w[ks & 3], wpn, ks + 4 - KS1, lo8);
+        __builtin_amdgcn_sched_barrier(0);  // pin the prefetch to its k-step
     }
 }
 
@@ -544,6 +562,32 @@ __device__ __forceinline__ void ffn_x_frag(XFrag& x, const char* Xs, const int (
 // MFMAs) and a workgroup 32 tokens x 64 features: twice the workgroups, half the bytes and half the MFMA chain per CU
 // (measured, same box: FFN-down -12 us per request, attention-out another -10 us; profiles/r04_single_request_anatomy.txt).
 // Per output the chain is wt_kloop's (k-steps ascending, (w_hi,x_hi), (w_lo,x_hi), (w_hi,x_lo)): identical bits.
+//
+// The 16-feature tile of wave q in feature block nb of such a workgroup: its 32-feature block and which half of it
+struct Tile16 { int nt, fi; };
+__device__ __forceinline__ Tile16 wt_tile16(int nb, int q) {
+    const int ft = nb * 4 + q;
+    return {ft >> 1, ft & 1};
+}
+// The two weight fragments (hi, lo) of k-step ks of a tile: half fi of the block whose fragments of k-step 0 are at wp.
+// wt_linear_half_kernel keeps the half's offset in wp (fi = 0 here); wt_linear_lnin_kernel passes fi, added behind the
+// k-step: with the offset folded into wp, that kernel's twelve constant k-steps compile to four scalar instructions
+// and one SGPR fewer - a change of its own, not made here.
+__device__ __forceinline__ void w_load16(half8& wh, half8& wl, const _Float16* wp, int ks, unsigned lo8, int fi = 0) {
+    const _Float16* p = wp + (size_t)ks * (4 * WT_FRAG) + (size_t)fi * (2 * WT_FRAG);
+    wh = *reinterpret_cast<const half8*>(p + lo8);
+    wl = *reinterpret_cast<const half8*>(p + WT_FRAG + lo8);
+}
+// one k-step of the tile over a 32-token block: wt_mma_block's chain for one fi
+__device__ __forceinline__ void wt_mma16(f32x4 (&acc)[2], const half8& wh, const half8& wl, const XFrag& x) {
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti) {
+        acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, x.h[ti], acc[ti], 0, 0, 0);
+        acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, x.h[ti], acc[ti], 0, 0, 0);
+        acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, x.l[ti], acc[ti], 0, 0, 0);
+    }
+}
+
 template <int EPI, int D>  // 0: out = acc * 2^-14 + bias; 2: residual planes rh / rl + bias added after the loop, out = that * 2^-14
 __global__ __launch_bounds__(256, 2) void wt_linear_half_kernel(const _Float16* __restrict__ Xh,
                                                                     const _Float16* __restrict__ Xl, int T, int K,
@@ -556,22 +600,17 @@ __global__ __launch_bounds__(256, 2) void wt_linear_half_kernel(const _Float16* 
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mt = bid / n_blocks_n, nb = bid % n_blocks_n;
     const int64_t m0 = (int64_t)mt * 32;
-    const int ft = nb * 4 + q, nt = ft >> 1, fi = ft & 1;  // 16-feature tile, its 32-feature block, which half
+    const auto [nt, fi] = wt_tile16(nb, q);
     const unsigned lo8 = lane * 8;
     const int KS = K / 32, nslab = K / 64;
     const _Float16* const wp = Wp + wt_frag_off(nt, 0, KS) + (size_t)fi * (2 * WT_FRAG);
     static_assert(D == 6 || D == 8, "ring depth: 6 (K a multiple of 384) or 8 (K a multiple of 256) k-steps");
     half8 wh[D], wl[D];
-    auto w_load1 = [&](int slot, int ks) {
-        const _Float16* p = wp + (size_t)ks * (4 * WT_FRAG);
-        wh[slot] = *reinterpret_cast<const half8*>(p + lo8);
-        wl[slot] = *reinterpret_cast<const half8*>(p + WT_FRAG + lo8);
-    };
     f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
     u32x4 xa[2], xb[2];
     x_load<1>(xa, Xh, Xl, m0, T, K, 0);
 #pragma unroll
-    for (int d = 0; d < D; ++d) w_load1(d, d);
+    for (int d = 0; d < D; ++d) w_load16(wh[d], wl[d], wp, d, lo8);
     if (nslab > 1) x_load<1>(xb, Xh, Xl, m0, T, K, 1);
     x_store<1>(xa, smem);
     if (nslab > 2) x_load<1>(xa, Xh, Xl, m0, T, K, 2);
@@ -587,16 +626,11 @@ __global__ __launch_bounds__(256, 2) void wt_linear_half_kernel(const _Float16* 
                 x_frag<1>(x[1], st, 0, 1, c, g);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti) {
-                acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[2 * PAR + j], x[j].h[ti], acc[ti], 0, 0, 0);
-                acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[2 * PAR + j], x[j].h[ti], acc[ti], 0, 0, 0);
-                acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[2 * PAR + j], x[j].l[ti], acc[ti], 0, 0, 0);
-            }
+            wt_mma16(acc, wh[2 * PAR + j], wl[2 * PAR + j], x[j]);
             __builtin_amdgcn_sched_barrier(0);
             int nk = 2 * s + j + D;
             nk = nk < KS ? nk : KS - 1;
-            w_load1(2 * PAR + j, nk);
+            w_load16(wh[2 * PAR + j], wl[2 * PAR + j], wp, nk, lo8);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (s + 1 < nslab) {
@@ -672,18 +706,13 @@ __global__ __launch_bounds__(256, 2) void wt_linear_lnin_kernel(const float* __r
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mt = bid / n_blocks_n, nb = bid % n_blocks_n;
     const int64_t m0 = (int64_t)mt * 32;
-    const int ft = nb * 4 + wq, nt = ft >> 1, hf = ft & 1;  // 16-feature tile, its 32-feature block, which half
+    const auto [nt, hf] = wt_tile16(nb, wq);
     const unsigned lo8 = lane * 8;
     constexpr int RD = 8;  // weight ring depth in k-steps: eight of the twelve are requested in front of the LayerNorm
     const _Float16* const wp = Wp + wt_frag_off(nt, 0, KS1);
     half8 wh[RD], wl[RD];
-    auto w_ring_load = [&](int slot, int ks) {
-        const _Float16* p = wp + (size_t)ks * (4 * WT_FRAG) + (size_t)hf * (2 * WT_FRAG);
-        wh[slot] = *reinterpret_cast<const half8*>(p + lo8);
-        wl[slot] = *reinterpret_cast<const half8*>(p + WT_FRAG + lo8);
-    };
 #pragma unroll
-    for (int d = 0; d < RD; ++d) w_ring_load(d, d);
+    for (int d = 0; d < RD; ++d) w_load16(wh[d], wl[d], wp, d, lo8, hf);
     const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + nt * 32 + hf * 16 + 4 * g);
     // ---- LayerNorm of the block's 32 rows: two passes of 16 tokens, ln_wt_kernel's thread mapping and order
     {
@@ -708,33 +737,19 @@ __global__ __launch_bounds__(256, 2) void wt_linear_lnin_kernel(const float* __r
     }
     __syncthreads();  // image resident
     // ---- K = 384 off the image
-    int xb[2];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti) xb[ti] = (ti * 16 + c) * 768 + ((g ^ c) << 4);
-    auto x_frag1 = [&](XFrag& x, int ks) {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-            const int pos = (xb[ti] ^ ((ks & 3) << 6)) + (ks >> 2) * 256;
-            x.h[ti] = *reinterpret_cast<const half8*>(Xs + pos);
-            x.l[ti] = *reinterpret_cast<const half8*>(Xs + LNIN_XPLANE + pos);
-        }
-    };
+    int xb[2][2];  // (token block 0 only: the image holds 32 rows)
+    ffn_x_bases(xb, c, g);
     f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
     XFrag x[2];
-    x_frag1(x[0], 0);
+    ffn_x_frag<LNIN_XPLANE>(x[0], Xs, xb, 0, 0);
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) {
         if (ks + 1 < KS1) {
-            x_frag1(x[(ks + 1) & 1], ks + 1);
+            ffn_x_frag<LNIN_XPLANE>(x[(ks + 1) & 1], Xs, xb, 0, ks + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ks % RD], x[ks & 1].h[ti], acc[ti], 0, 0, 0);
-            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[ks % RD], x[ks & 1].h[ti], acc[ti], 0, 0, 0);
-            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ks % RD], x[ks & 1].l[ti], acc[ti], 0, 0, 0);
-        }
-        if (ks + RD < KS1) w_ring_load(ks % RD, ks + RD);
+        wt_mma16(acc, wh[ks % RD], wl[ks % RD], x[ks & 1]);
+        if (ks + RD < KS1) w_load16(wh[ks % RD], wl[ks % RD], wp, ks + RD, lo8, hf);
         __builtin_amdgcn_sched_barrier(0);
     }
     const int feat = nt * 32 + hf * 16 + 4 * g;
@@ -774,32 +789,11 @@ __device__ __forceinline__ void qkv_block_walk(const char* Xs, float* stg, const
     }
     for (int nt = wave; nt < NT; nt += 8) {
         const int nn = nt + 8 < NT ? nt + 8 : nt;  // past the last block: re-read this one's fragments (never consumed)
-        const _Float16* const wp1[1] = {Wp + wt_frag_off(nt, 0, KS1)};
-        const _Float16* const wpn[1] = {Wp + wt_frag_off(nn, 0, KS1)};
         f32x4 bv[2];  // loaded BEFORE the k-loop (vmcnt counts in order: behind the ring it would wait for the whole ring)
 #pragma unroll
         for (int fi = 0; fi < 2; ++fi) bv[fi] = *reinterpret_cast<const f32x4*>(bias + nt * 32 + fi * 16 + 4 * g);
-        Acc32 S[1][2];
-        acc_zero(S[0][0]);
-        acc_zero(S[0][1]);
-        XFrag x[2];
-        ffn_x_frag(x[0], Xs, xb, 0, 0);
-#pragma unroll
-        for (int ks = 0; ks < KS1; ++ks) {
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) {
-                const int u = 2 * ks + tt;
-                if (u + 1 < 2 * KS1) {
-                    ffn_x_frag(x[(u + 1) & 1], Xs, xb, (u + 1) & 1, (u + 1) >> 1);
-                    __builtin_amdgcn_sched_barrier(0);  // the next unit's LDS reads are issued before this unit's 12 MFMAs
-                }
-                if (tt == 0) wt_mma<1, 2, 0>(S, w[ks & 3], x[u & 1]);
-                else wt_mma<1, 2, 1>(S, w[ks & 3], x[u & 1]);
-            }
-            if (ks + 4 < KS1) w_load<1>(w[ks & 3], wp1, ks + 4, lo8);
-            else w_load<1>(w[ks & 3], wpn, ks + 4 - KS1, lo8);
-            __builtin_amdgcn_sched_barrier(0);  // pin the prefetch to its k-step
-        }
+        Acc32 S[2];
+        resident_block_k384(S, Xs, xb, w, Wp, nt, nn, lo8);
         // ---- this block out: [32 tokens][32 features] per pass through the wave's private LDS tile
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -809,7 +803,7 @@ __device__ __forceinline__ void qkv_block_walk(const char* Xs, float* stg, const
                 for (int ti = 0; ti < 2; ++ti) {
                     f32x4 v;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = fmaf(S[0][tt].t[fi][ti][j], WT_UNSCALE, bv[fi][j]);
+                    for (int j = 0; j < 4; ++j) v[j] = fmaf(S[tt].t[fi][ti][j], WT_UNSCALE, bv[fi][j]);
                     *reinterpret_cast<f32x4*>(stg + (ti * 16 + c) * QKVR_STG_LD + fi * 16 + 4 * g) = v;
                 }
             lds_order();
@@ -868,6 +862,8 @@ __device__ __forceinline__ void bar_lds() {  // LDS hand-off barrier that leaves
 //   + x) never travels to HBM (-2 x 768 B per token per layer each way, one launch fewer), the FFN proceeds on it as
 //   before.  Per output the same chain and the same LayerNorm order as wt_linear_kernel<.., 2> + ln_wt_kernel:
 //   identical bits.
+// Of the pointer arguments only Wqp may be null: it switches the trailing QKV projection (bq, qkv_out and Nq are read
+// only with it); the prologue and the FFN dereference every other one.
 __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict__ xh, _Float16* __restrict__ xl,
                                                             int T, int I,
                                                             const _Float16* __restrict__ W1p,
@@ -876,15 +872,15 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
                                                             const float* __restrict__ b2,
                                                             const float* __restrict__ gam,
                                                             const float* __restrict__ bet, float eps,
-                                                            const _Float16* __restrict__ ch = nullptr,
-                                                            const _Float16* __restrict__ cl = nullptr,
-                                                            const _Float16* __restrict__ Wop = nullptr,
-                                                            const float* __restrict__ bo = nullptr,
-                                                            const float* __restrict__ gam1 = nullptr,
-                                                            const float* __restrict__ bet1 = nullptr,
-                                                            const _Float16* __restrict__ Wqp = nullptr,
-                                                            const float* __restrict__ bq = nullptr,
-                                                            float* __restrict__ qkv_out = nullptr, int Nq = 0) {
+                                                            const _Float16* __restrict__ ch,
+                                                            const _Float16* __restrict__ cl,
+                                                            const _Float16* __restrict__ Wop,
+                                                            const float* __restrict__ bo,
+                                                            const float* __restrict__ gam1,
+                                                            const float* __restrict__ bet1,
+                                                            const _Float16* __restrict__ Wqp,
+                                                            const float* __restrict__ bq,
+                                                            float* __restrict__ qkv_out, int Nq) {
     constexpr int KS1 = 12;  // k-steps of 32 over K = 384
     extern __shared__ __attribute__((aligned(16))) char smem2[];
     char* const Xs = smem2;
@@ -899,9 +895,9 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
     // x1 = LayerNorm(Wo . ctx + bo + x) -> the resident image.
     // All eight waves share the work; wave (q, half) owns features q*96 .. +95 of token block `half`:
     //  * it stages its residual rows into the accumulator layout (global -> its private LDS tile -> r);
-    //  * the GEMM runs in the producers' form (one 32-feature block x 64 tokens at a time, weight ring 4 k-steps deep,
-    //    the loop of qkv_resident_kernel): producer p takes blocks p, p + 4 and p + 8 while the consumer on its SIMD
-    //    stages its residual rows (a 2 : 1 split with the consumers' rows staged first left the producers waiting);
+    //  * the GEMM runs in the producers' form (one 32-feature block x 64 tokens at a time, weight ring 4 k-steps deep:
+    //    resident_block_k384, as in qkv_block_walk): producer p takes blocks p, p + 4 and p + 8 while the consumer on its
+    //    SIMD stages its residual rows (a 2 : 1 split with the consumers' rows staged first left the producers waiting);
     //  * the products travel through the context image, dead once every wave has left its K loops: 12 blocks x 2
     //    token blocks x 4 tiles x 1 KB = the 96 KB of the image, each tile in the lane order both sides hold it in
     //    (conflict-free 16-B accesses); every wave picks up the 12 tiles of its (q, half), adds r and takes part in
@@ -927,30 +923,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
             for (int d = 0; d < 4; ++d) w_load<1>(w[d], wp0, d, lo8);
         }
         __syncthreads();  // context planes resident
-        // K = 384 of one block; the ring continues into block `nn` (or re-reads this one's last fragments, never consumed)
-        auto ao_block = [&](Acc32 (&S)[2], int nt, int nn) {
-            const _Float16* const wp1[1] = {Wop + wt_frag_off(nt, 0, KS1)};
-            const _Float16* const wpn[1] = {Wop + wt_frag_off(nn, 0, KS1)};
-            acc_zero(S[0]);
-            acc_zero(S[1]);
-            XFrag x[2];
-            ffn_x_frag(x[0], Xs, xb, 0, 0);
-#pragma unroll
-            for (int ks = 0; ks < KS1; ++ks) {
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) {
-                    const int u = 2 * ks + tt;
-                    if (u + 1 < 2 * KS1) {
-                        ffn_x_frag(x[(u + 1) & 1], Xs, xb, (u + 1) & 1, (u + 1) >> 1);
-                        __builtin_amdgcn_sched_barrier(0);  // the next unit's LDS reads before this unit's 12 MFMAs
-                    }
-                    wt_mma_block(S[tt], w[ks & 3][0], x[u & 1]);
-                }
-                if (ks + 4 < KS1) w_load<1>(w[ks & 3], wp1, ks + 4, lo8);
-                else w_load<1>(w[ks & 3], wpn, ks + 4 - KS1, lo8);
-                __builtin_amdgcn_sched_barrier(0);  // pin the prefetch to its k-step
-            }
-        };
         auto put = [&](const Acc32 (&S)[2], int nt) {
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt)
@@ -972,9 +944,9 @@ __global__ __launch_bounds__(512, 2) void ffn_fused2_kernel(_Float16* __restrict
         };
         if constexpr (PROD) {
             Acc32 S0[2], S1[2], S2[2];
-            ao_block(S0, q, q + 4);
-            ao_block(S1, q + 4, q + 8);
-            ao_block(S2, q + 8, q + 8);
+            resident_block_k384(S0, Xs, xb, w, Wop, q, q + 4, lo8);
+            resident_block_k384(S1, Xs, xb, w, Wop, q + 4, q + 8, lo8);
+            resident_block_k384(S2, Xs, xb, w, Wop, q + 8, q + 8, lo8);
             wt_res_rows_load(rr, q, tb, xh, xl, m0, T);
             __syncthreads();  // every wave has left the context image: it takes the products
             put(S0, q);
