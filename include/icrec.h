@@ -92,7 +92,8 @@ typedef struct icrec_bert_cfg {
  *   then per layer:
  *   Wq[H,H] bq[H] Wk[H,H] bk[H] Wv[H,H] bv[H] Wo[H,H] bo[H] ln1_g[H] ln1_b[H]
  *   W1[I,H] b1[I] W2[H,I] b2[H] ln2_g[H] ln2_b[H]
- * (the BertPooler is not used by mean pooling and is not part of the blob). */
+ * (the BertPooler is not used by mean pooling and is not part of the blob; a cross-encoder's pooler and classifier are
+ * set on the handle: icrec_encoder_set_score_head). */
 ICREC_API size_t icrec_encoder_weight_count(const icrec_bert_cfg* cfg);
 
 /* Upload weights (host pointer; the library copies them to `device`). */
@@ -140,6 +141,21 @@ ICREC_API int32_t icrec_encoder_pooling(const icrec_encoder* enc);
 ICREC_API int icrec_encoder_set_attention_bias(icrec_encoder* enc, const float* bias_host, int32_t heads);
 ICREC_API int32_t icrec_encoder_has_attention_bias(const icrec_encoder* enc);   /* 0 / 1; -1 for NULL */
 
+/* Score head of a cross-encoder (BertForSequenceClassification with num_labels = 1: the cross-encoder/ms-marco-MiniLM
+ * family): the BertPooler and the classifier, applied by icrec_score_pairs to the last hidden state h of each sequence's
+ * first token:  p = tanh(pooler_w . h + pooler_b),  logit = cls_w . p + cls_b.
+ *   pooler_w_host float[hidden][hidden] row-major [out, in] as nn.Linear stores it;  pooler_b_host float[hidden];
+ *   cls_w_host float[hidden];  cls_b_host float[1].
+ * pooler_w_host == NULL removes the head.  Every value must be finite and cfg.type_vocab must be >= 2 (a pair's second
+ * segment takes token-type row 1); anything else is ICREC_EINVAL and changes nothing.  Same contract as
+ * icrec_encoder_set_attention_bias: a set-up call that allocates and copies, before the first compute call, never while a
+ * call on `enc` is running.  The head lives on the handle: icrec_bert_cfg, the weight blob, icrec_encoder_weight_count and
+ * icrec_encode_workspace_bytes do not know it, and icrec_encode on an encoder with a head launches what it launches on
+ * one without, to the same bits. */
+ICREC_API int icrec_encoder_set_score_head(icrec_encoder* enc, const float* pooler_w_host, const float* pooler_b_host,
+                                 const float* cls_w_host, const float* cls_b_host);
+ICREC_API int32_t icrec_encoder_has_score_head(const icrec_encoder* enc);   /* 0 / 1; -1 for NULL */
+
 /* Scratch bytes needed to encode `total_tokens` tokens in `n_seqs` sequences.  Depends on the pooling mode (a CLS
  * encoder adds room for `n_seqs` compact rows): ask after icrec_encoder_set_pooling.  Does not depend on the bias. */
 ICREC_API size_t icrec_encode_workspace_bytes(const icrec_encoder* enc,
@@ -185,6 +201,28 @@ ICREC_API int icrec_encode_ex(icrec_encoder* enc,
  * it to count the FLOPs of the launches it times. */
 ICREC_API int icrec_encode_batch_split(const icrec_encoder* enc, int64_t total_tokens,
                              int64_t* main_tokens, int64_t* tail_tokens);
+
+/* Scratch bytes icrec_score_pairs needs for `total_tokens` tokens in `n_seqs` pairs (0 for a bad argument).  Does not
+ * depend on the pooling mode. */
+ICREC_API size_t icrec_score_pairs_workspace_bytes(const icrec_encoder* enc, int64_t total_tokens, int32_t n_seqs);
+
+/* Score a token-packed batch of (query, document) pairs: what sentence-transformers' CrossEncoder.predict computes on the
+ * device, before its activation function.  Each sequence is `[CLS] query [SEP] document [SEP]`, packed as for icrec_encode.
+ *   seg_b_dev      int32[n_seqs]  where each pair's second segment starts: token t of sequence s takes token-type row 1
+ *                                 when t - cu_seqlens[s] >= seg_b[s] and row 0 otherwise (BERT's token_type_ids are
+ *                                 always a run of 0s, then a run of 1s); seg_b[s] is clamped to [0, length of s]
+ *   scores_out_dev float[n_seqs]  the raw logit of each pair (sigmoid or identity is the caller's choice)
+ * The layers run as in icrec_encode_ex; only the first token's last hidden state is read, so in f16x3 mode the last layer is
+ * computed for the first token of each sequence only, as for a CLS-pooled encoder and whatever the handle's pooling mode
+ * (ICREC_CLS_PRUNE=0 at icrec_encoder_create forces the full layer: same bits); the pooling mode and cfg.n_normalize do not
+ * enter.  The head is fp32 with one summation order: a pair's logit has the same bits alone and inside any batch.
+ * ICREC_EINVAL without a score head; the other argument checks, the stream semantics and graph-capturability are
+ * icrec_encode's.  Workspace: icrec_score_pairs_workspace_bytes. */
+ICREC_API int icrec_score_pairs(icrec_encoder* enc,
+                      const int32_t* ids_dev, const int32_t* cu_seqlens_dev, const int32_t* seg_b_dev,
+                      int32_t n_seqs, int64_t total_tokens, int32_t max_seqlen,
+                      float* scores_out_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Index + search: replaces cos_sim(query_emb, product_embeddings)            */

@@ -26,6 +26,8 @@ EXPORTS = [
     "icrec_encoder_weight_count", "icrec_encoder_create", "icrec_encoder_destroy", "icrec_encoder_set_max_seqlen",
     "icrec_encoder_set_pooling", "icrec_encoder_pooling",
     "icrec_encoder_set_attention_bias", "icrec_encoder_has_attention_bias",
+    "icrec_encoder_set_score_head", "icrec_encoder_has_score_head",
+    "icrec_score_pairs_workspace_bytes", "icrec_score_pairs",
     "icrec_encode_workspace_bytes", "icrec_encode", "icrec_encode_ex", "icrec_encode_batch_split",
     "icrec_index_create", "icrec_index_create_ex", "icrec_index_destroy", "icrec_index_rows", "icrec_index_storage",
     "icrec_index_export", "icrec_index_dim", "icrec_index_device",
@@ -96,6 +98,10 @@ def lib() -> C.CDLL:
         "icrec_encoder_pooling": (i32, [vp]),
         "icrec_encoder_set_attention_bias": (C.c_int, [vp, vp, i32]),
         "icrec_encoder_has_attention_bias": (i32, [vp]),
+        "icrec_encoder_set_score_head": (C.c_int, [vp, vp, vp, vp, vp]),
+        "icrec_encoder_has_score_head": (i32, [vp]),
+        "icrec_score_pairs_workspace_bytes": (sz, [vp, i64, i32]),
+        "icrec_score_pairs": (C.c_int, [vp, vp, vp, vp, i32, i64, i32, vp, vp, sz, vp]),
         "icrec_encode_workspace_bytes": (sz, [vp, i64, i32]),
         "icrec_encode": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, vp, sz, vp]),
         "icrec_encode_ex": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, vp, vp, sz, vp]),

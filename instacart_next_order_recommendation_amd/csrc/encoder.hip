@@ -63,14 +63,18 @@ __device__ __forceinline__ void ln_row(float (&v)[H / 64], const float* __restri
 }
 
 // ---------------------------------------------------------------- K1: embeddings + LN (tf:98-107)
-template <int H, bool SPLIT>
+// SEG (icrec_score_pairs): sequence s is a pair whose second segment starts at position seg_b[s]; its tokens take type
+// row 1 (token_type_ids: a run of 0s, then a run of 1s).  Positions lie in [0, len_s), so the comparison clamps
+// seg_b[s] to [0, len_s] by itself.  Without SEG every token takes row 0 and seg_b is not read.
+template <int H, bool SPLIT, bool SEG = false>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids,
                                                        const int32_t* __restrict__ cu, int n_seqs, int T,
                                                        const float* __restrict__ word, const float* __restrict__ pos,
                                                        const float* __restrict__ type, const float* __restrict__ g,
                                                        const float* __restrict__ b, float eps, int vocab, int max_pos,
                                                        float* __restrict__ x, _Float16* __restrict__ xh,
-                                                       _Float16* __restrict__ xl) {
+                                                       _Float16* __restrict__ xl,
+                                                       const int32_t* __restrict__ seg_b) {
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= T) return;
@@ -78,6 +82,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
     int id = ids[t];
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     int p = t - cu[s];
+    if constexpr (SEG) type += p >= seg_b[s] ? H : 0;
     p = p >= max_pos ? max_pos - 1 : p;
     float v[H / 64];
 #pragma unroll
@@ -839,6 +844,68 @@ __global__ __launch_bounds__(256) void gather_cls_rows_kernel(const _Float16* __
     *reinterpret_cast<u32x4*>(cxl + to) = *reinterpret_cast<const u32x4*>(xl + from);
 }
 
+// ---------------------------------------------------------------- pair score head (icrec_score_pairs)
+// BertPooler + classifier of BertForSequenceClassification(num_labels = 1) on the last hidden state h of each sequence's
+// first token:  p_j = tanhf(bp[j] + sum_k Wp[j][k] h[k]),  logit = bc + sum_j wc[j] p_j  - every sum ONE fp32 fmaf chain in
+// ascending index order, so a pair's logit has the same bits alone, in any batch and from any of the three row sources:
+// the x planes (row cu[s]; widened as pool_norm_kernel widens them), the compact rows of the pruned last layer (row s),
+// or fp32 x (row cu[s]).
+// A workgroup of 384 threads serves HEAD_SEQS sequences: their rows in LDS as hs[k][seq] (one k = HEAD_SEQS contiguous
+// floats, read as broadcast 16-byte loads), thread t the outputs j = t (+ 384 at hidden 768) with one accumulator per
+// (j, sequence), so that a k-step's weights - wpt is Wp transposed, [in][out]: a wave reads 256 contiguous bytes - are
+// fetched from L2 once per HEAD_SEQS sequences, not once per sequence.  Then p in LDS as ps[j][seq] (over hs) and thread
+// s < HEAD_SEQS walks sequence s's classifier chain (conflict-free: adjacent lanes, adjacent banks).
+template <int H>
+constexpr int HEAD_SEQS = 32 * 384 / H;  // 48 KB of rows in LDS, 32 accumulators per thread, at either width
+
+template <int H, bool PLANES>
+__global__ __launch_bounds__(384) void score_head_kernel(const float* __restrict__ x, const _Float16* __restrict__ xh,
+                                                         const _Float16* __restrict__ xl, const int32_t* __restrict__ cu,
+                                                         int n_seqs, bool compact, const float* __restrict__ wpt,
+                                                         const float* __restrict__ bp, const float* __restrict__ wc,
+                                                         const float* __restrict__ bc, float* __restrict__ scores) {
+    constexpr int S = HEAD_SEQS<H>, JPT = H / 384;
+    auto at = [&](size_t idx) { return PLANES ? ((float)xh[idx] + (float)xl[idx]) * (1.0f / WT_SA) : x[idx]; };
+    __shared__ __attribute__((aligned(16))) float hs[H * S];
+    const int tid = threadIdx.x, s0 = blockIdx.x * S;
+    for (int i = tid; i < H * S; i += 384) {  // (consecutive threads, consecutive features of one row)
+        const int sl = i / H, k = i % H, s = s0 + sl;
+        hs[k * S + sl] = s < n_seqs ? at((size_t)(compact ? s : cu[s]) * H + k) : 0.0f;
+    }
+    __syncthreads();
+    float acc[JPT][S];
+#pragma unroll
+    for (int r = 0; r < JPT; ++r)
+#pragma unroll
+        for (int sl = 0; sl < S; ++sl) acc[r][sl] = bp[tid + 384 * r];
+#pragma unroll 4
+    for (int k = 0; k < H; ++k) {
+        float w[JPT];
+#pragma unroll
+        for (int r = 0; r < JPT; ++r) w[r] = wpt[(size_t)k * H + tid + 384 * r];
+#pragma unroll
+        for (int q = 0; q < S / 4; ++q) {
+            const f32x4 h4 = *reinterpret_cast<const f32x4*>(hs + k * S + 4 * q);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int r = 0; r < JPT; ++r) acc[r][4 * q + u] = fmaf(w[r], h4[u], acc[r][4 * q + u]);
+        }
+    }
+    __syncthreads();  // every thread is done with hs: ps takes its place
+    float* const ps = hs;
+#pragma unroll
+    for (int r = 0; r < JPT; ++r)
+#pragma unroll
+        for (int sl = 0; sl < S; ++sl) ps[(tid + 384 * r) * S + sl] = tanhf(acc[r][sl]);
+    __syncthreads();
+    if (tid < S && s0 + tid < n_seqs) {
+        float logit = bc[0];
+        for (int j = 0; j < H; ++j) logit = fmaf(wc[j], ps[j * S + tid], logit);
+        scores[s0 + tid] = logit;
+    }
+}
+
 // ---------------------------------------------------------------- host side
 constexpr int HID = 384;     // all-MiniLM width: 32-dim heads, the fused layer kernels
 constexpr int HID_BASE = 768;  // BERT-base width: 64-dim heads, the unfused chain
@@ -860,6 +927,7 @@ struct Encoder {
     int max_seqlen = 256;       // longest sequence icrec_encode accepts (icrec_encoder_set_max_seqlen)
     int pooling = ICREC_POOL_MEAN;  // icrec_encoder_set_pooling
     float* att_bias = nullptr;  // icrec_encoder_set_attention_bias: [heads][ATT_BIAS_LD] in log2 units, or none
+    float* score_head = nullptr;  // icrec_encoder_set_score_head: Wp^T [H in][H out], bp[H], wc[H], bc[1], or none
     float* blob = nullptr;      // the uploaded weight blob
     float* extra = nullptr;     // repacked Wqkv / bqkv
     _Float16* planes = nullptr; // packed weight fragments (F16X3)
@@ -1163,6 +1231,7 @@ int icrec_encoder_destroy(icrec_encoder* h) {
     (void)hipFree(e->extra);
     if (e->planes) (void)hipFree(e->planes);
     if (e->att_bias) (void)hipFree(e->att_bias);
+    if (e->score_head) (void)hipFree(e->score_head);
     for (Encoder::Side* sd : e->sides) {  // (side_for keeps a side only once its stream and event exist)
         (void)hipStreamSynchronize(sd->side);
         (void)hipStreamDestroy(sd->side);
@@ -1231,6 +1300,51 @@ int32_t icrec_encoder_has_attention_bias(const icrec_encoder* h) {
     return e ? (e->att_bias != nullptr) : -1;
 }
 
+int icrec_encoder_set_score_head(icrec_encoder* h, const float* pooler_w_host, const float* pooler_b_host,
+                                 const float* cls_w_host, const float* cls_b_host) {
+    Encoder* e = reinterpret_cast<Encoder*>(h);
+    ICREC_REQUIRE(e, "icrec_encoder_set_score_head: NULL encoder");
+    ICREC_HIP(hipSetDevice(e->device));
+    if (!pooler_w_host) {  // back to an encoder that never had one
+        if (e->score_head) ICREC_HIP(hipFree(e->score_head));
+        e->score_head = nullptr;
+        return ICREC_OK;
+    }
+    ICREC_REQUIRE(pooler_b_host && cls_w_host && cls_b_host, "icrec_encoder_set_score_head: NULL bias or classifier with a pooler weight");
+    ICREC_REQUIRE(e->cfg.type_vocab >= 2, "icrec_encoder_set_score_head: a pair needs two token-type rows (type_vocab is %d)", e->cfg.type_vocab);
+    const size_t H = e->cfg.hidden;
+    std::vector<float> host(H * H + 2 * H + 1);  // Wp transposed ([in][out]: score_head_kernel), bp, wc, bc
+    float *const bp = host.data() + H * H, *const wc = bp + H;
+    for (size_t j = 0; j < H; ++j) {
+        for (size_t k = 0; k < H; ++k) {
+            const float v = pooler_w_host[j * H + k];
+            ICREC_REQUIRE(v - v == 0.0f, "icrec_encoder_set_score_head: pooler weight [%zu][%zu] is not finite", j, k);
+            host[k * H + j] = v;
+        }
+        bp[j] = pooler_b_host[j];
+        wc[j] = cls_w_host[j];
+        ICREC_REQUIRE(bp[j] - bp[j] == 0.0f, "icrec_encoder_set_score_head: pooler bias [%zu] is not finite", j);
+        ICREC_REQUIRE(wc[j] - wc[j] == 0.0f, "icrec_encoder_set_score_head: classifier weight [%zu] is not finite", j);
+    }
+    wc[H] = cls_b_host[0];
+    ICREC_REQUIRE(wc[H] - wc[H] == 0.0f, "icrec_encoder_set_score_head: classifier bias is not finite");
+    float* dev = e->score_head;
+    if (!dev && hipMalloc(&dev, host.size() * 4) != hipSuccess) {
+        set_error("icrec_encoder_set_score_head: hipMalloc failed");
+        return ICREC_ENOMEM;
+    }
+    const hipError_t err = hipMemcpy(dev, host.data(), host.size() * 4, hipMemcpyHostToDevice);
+    if (err != hipSuccess && !e->score_head) (void)hipFree(dev);
+    ICREC_HIP(err);
+    e->score_head = dev;
+    return ICREC_OK;
+}
+
+int32_t icrec_encoder_has_score_head(const icrec_encoder* h) {
+    const Encoder* e = reinterpret_cast<const Encoder*>(h);
+    return e ? (e->score_head != nullptr) : -1;
+}
+
 // The call's own regions, then (cls_prunes) the compact rows' of the pruned last layer.
 static size_t workspace_bytes(const Encoder* e, int64_t T, int n_seqs) {
     return enc_ws(e->cfg, T).total + (cls_prunes(e) ? enc_ws(e->cfg, n_seqs, true).total : 0);
@@ -1259,8 +1373,9 @@ int icrec_encode_batch_split(const icrec_encoder* h, int64_t total_tokens, int64
 
 // Embeddings + LayerNorm.  f16x3 mode leaves the fp32 x region unused (the residual stream is its two planes): it carries
 // the attention dispatch order of batches, returned here (nullptr: workgroup b serves sequence b / heads, as unfused).
+// seg_b_dev (icrec_score_pairs): each sequence's first position of token type 1 - the kernel's SEG arm; nullptr: type 0.
 static const int32_t* embed(const Encoder* e, const EncBufs& b, const int32_t* ids_dev, const int32_t* cu_dev,
-                            int n_seqs, int T, hipStream_t st) {
+                            const int32_t* seg_b_dev, int n_seqs, int T, hipStream_t st) {
     const icrec_bert_cfg& c = e->cfg;
     const bool x3 = c.gemm_mode == ICREC_GEMM_F16X3;
     int32_t* order = nullptr;
@@ -1268,10 +1383,12 @@ static const int32_t* embed(const Encoder* e, const EncBufs& b, const int32_t* i
         order = reinterpret_cast<int32_t*>(b.x);
         hipLaunchKernelGGL(seq_order_kernel, dim3(1), dim3(1024), 0, st, cu_dev, n_seqs, order);
     }
-    const auto kern =
+    auto kern =
         for_hidden(c.hidden, [x3](auto h) { return x3 ? embed_ln_kernel<h(), true> : embed_ln_kernel<h(), false>; });
+    if (seg_b_dev)
+        kern = for_hidden(c.hidden, [x3](auto h) { return x3 ? embed_ln_kernel<h(), true, true> : embed_ln_kernel<h(), false, true>; });
     hipLaunchKernelGGL(kern, dim3((T + 3) / 4), dim3(256), 0, st, ids_dev, cu_dev, n_seqs, T, e->word, e->pos, e->type, e->eg, e->eb, c.ln_eps, c.vocab_size,
-                       c.max_position, b.x, b.xh, b.xl);
+                       c.max_position, b.x, b.xh, b.xl, seg_b_dev);
     return order;
 }
 
@@ -1470,7 +1587,7 @@ int icrec_encode_ex(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_
     // wants every token's state, and not when every token is a first token (nothing to save).
     const bool pruned = cls_prunes(e) && !tokens_out_dev && n_seqs < T;
     const EncBufs cls(base + w.total, enc_ws(c, n_seqs, true), c, n_seqs);  // (inside the workspace only if cls_prunes)
-    const int32_t* order = embed(e, b, ids_dev, cu_dev, n_seqs, T, st);
+    const int32_t* order = embed(e, b, ids_dev, cu_dev, nullptr, n_seqs, T, st);
     if (int rc_ = x3 ? encode_x3(e, b, pruned ? &cls : nullptr, cu_dev, n_seqs, T, max_seqlen, order, st)
                      : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
         return rc_;
@@ -1485,6 +1602,55 @@ int icrec_encode_ex(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_
         hipLaunchKernelGGL(x3 ? tokens_out_kernel<true> : tokens_out_kernel<false>, dim3((unsigned)((n4 + 255) / 256)),
                            dim3(256), 0, st, b.x, b.xh, b.xl, n4, tokens_out_dev);
     }
+    ICREC_HIP(hipGetLastError());
+    return ICREC_OK;
+}
+
+// A pair's score reads row cu[s] of the last hidden state and nothing else, whatever the handle's pooling mode: in f16x3
+// mode the last layer is pruned as a CLS-pooled encoder's is, its compact rows behind the call's own regions.
+static bool score_prunes(const Encoder* e) { return e->cls_prune && e->cfg.gemm_mode == ICREC_GEMM_F16X3; }
+
+size_t icrec_score_pairs_workspace_bytes(const icrec_encoder* h, int64_t total_tokens, int32_t n_seqs) {
+    const Encoder* e = reinterpret_cast<const Encoder*>(h);
+    if (!e || total_tokens < 1 || n_seqs < 1) return 0;
+    return enc_ws(e->cfg, total_tokens).total + (score_prunes(e) ? enc_ws(e->cfg, n_seqs, true).total : 0);
+}
+
+int icrec_score_pairs(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* seg_b_dev,
+                      int32_t n_seqs, int64_t T64, int32_t max_seqlen, float* scores_out_dev, void* ws, size_t ws_bytes,
+                      void* stream) {
+    Encoder* e = reinterpret_cast<Encoder*>(h);
+    ICREC_REQUIRE(e && ids_dev && cu_dev && seg_b_dev && scores_out_dev, "icrec_score_pairs: NULL argument");
+    ICREC_REQUIRE(e->score_head, "icrec_score_pairs: the encoder has no score head (icrec_encoder_set_score_head)");
+    ICREC_REQUIRE(n_seqs >= 1 && T64 >= n_seqs && T64 < (1ll << 31), "icrec_score_pairs: bad n_seqs/total_tokens (%d, %lld)", n_seqs, (long long)T64);
+    ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= e->max_seqlen, "icrec_score_pairs: max_seqlen must be in [1, %d] (got %d)", e->max_seqlen, max_seqlen);
+    const int T = (int)T64;
+    const size_t need = icrec_score_pairs_workspace_bytes(h, T, n_seqs);
+    if (!ws || ws_bytes < need) {
+        set_error("icrec_score_pairs: workspace too small (%zu < %zu)", ws_bytes, need);
+        return ICREC_ENOMEM;
+    }
+    ICREC_HIP(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    char* base = reinterpret_cast<char*>(ws);
+    const icrec_bert_cfg& c = e->cfg;
+    const int H = c.hidden;
+    const bool x3 = c.gemm_mode == ICREC_GEMM_F16X3;
+    const EncWs w = enc_ws(c, T);
+    const EncBufs b(base, w, c, T);
+    const bool pruned = score_prunes(e) && n_seqs < T;  // (every token a first token: nothing to save)
+    const EncBufs cls(base + w.total, enc_ws(c, n_seqs, true), c, n_seqs);  // (inside the workspace only if score_prunes)
+    const int32_t* order = embed(e, b, ids_dev, cu_dev, seg_b_dev, n_seqs, T, st);
+    if (int rc_ = x3 ? encode_x3(e, b, pruned ? &cls : nullptr, cu_dev, n_seqs, T, max_seqlen, order, st)
+                     : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
+        return rc_;
+    const EncBufs& last = pruned ? cls : b;
+    const float *const wpt = e->score_head, *const bp = wpt + (size_t)H * H, *const wc = bp + H, *const bc = wc + H;
+    const auto kern =
+        for_hidden(H, [x3](auto h) { return x3 ? score_head_kernel<h(), true> : score_head_kernel<h(), false>; });
+    const int per_wg = H == HID_BASE ? HEAD_SEQS<HID_BASE> : HEAD_SEQS<HID>;
+    hipLaunchKernelGGL(kern, dim3((n_seqs + per_wg - 1) / per_wg), dim3(384), 0, st, last.x, last.xh, last.xl, cu_dev,
+                       n_seqs, pruned, wpt, bp, wc, bc, scores_out_dev);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
 }

@@ -111,6 +111,30 @@ class DeviceEncoder:
     def has_attention_bias(self) -> bool:
         return _native.lib().icrec_encoder_has_attention_bias(self._h) == 1
 
+    def set_score_head(self, pooler_w: Optional[np.ndarray], pooler_b: Optional[np.ndarray] = None,
+                       cls_w: Optional[np.ndarray] = None, cls_b: Optional[np.ndarray] = None) -> None:
+        """Set a cross-encoder's score head - BertPooler weight float32 [hidden, hidden] ([out, in]) and bias [hidden],
+        classifier weight [hidden] and bias [1] - or, with pooler_w None, remove it (icrec_encoder_set_score_head).
+        Like the attention bias it belongs before the first compute call; a refused head leaves the encoder as it was."""
+        L = _native.lib()
+        if pooler_w is None:
+            _native.check(L.icrec_encoder_set_score_head(self._h, None, None, None, None), "icrec_encoder_set_score_head")
+            return
+        H = self.shape.hidden
+        arrs = []
+        for name, a, shp in (("pooler_w", pooler_w, (H, H)), ("pooler_b", pooler_b, (H,)), ("cls_w", cls_w, (H,)),
+                             ("cls_b", cls_b, (1,))):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.size != int(np.prod(shp)) or (name == "pooler_w" and a.shape != shp):
+                raise ValueError(f"{name} must be float32 {list(shp)}, got {list(a.shape)}")
+            arrs.append(a)
+        _native.check(L.icrec_encoder_set_score_head(self._h, *(a.ctypes.data_as(C.c_void_p) for a in arrs)),
+                      "icrec_encoder_set_score_head")
+
+    @property
+    def has_score_head(self) -> bool:
+        return _native.lib().icrec_encoder_has_score_head(self._h) == 1
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _native.lib().icrec_encoder_destroy(self._h)
@@ -146,6 +170,34 @@ class DeviceEncoder:
         else:
             _native.check(L.icrec_encode_ex(self._h, ptr(ids), ptr(cu), n, T, int(max_seqlen), ptr(out), ptr(tokens),
                                             ptr(ws), ws.numel(), stream_ptr(self.device)), "icrec_encode_ex")
+
+    def score_into(self, ids: torch.Tensor, cu: torch.Tensor, seg_b: torch.Tensor, n: int, T: int, max_seqlen: int,
+                   out: torch.Tensor, ws: Optional[torch.Tensor] = None) -> None:
+        """One icrec_score_pairs on the current stream: device int32 ids[T], cu_seqlens[n+1] and seg_b[n] -> out float32
+        [n], each pair's raw logit.  `ws`: a workspace the caller owns (a captured graph bakes its address); by default
+        this stream's block."""
+        L = _native.lib()
+        if ws is None:
+            ws = self._ws_by_stream.block(int(L.icrec_score_pairs_workspace_bytes(self._h, T, n)))
+        _native.check(L.icrec_score_pairs(self._h, ptr(ids), ptr(cu), ptr(seg_b), n, T, int(max_seqlen), ptr(out), ptr(ws),
+                                          ws.numel(), stream_ptr(self.device)), "icrec_score_pairs")
+
+    def score_packed(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, seg_b: torch.Tensor, max_seqlen: int,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Packed pairs (int32 ids[T], cu_seqlens[n+1], seg_b[n]: model_io.assemble_pairs) -> float32 [n] raw logits on
+        the device, through the score head (set_score_head)."""
+        if ids.dtype != torch.int32 or cu_seqlens.dtype != torch.int32 or seg_b.dtype != torch.int32:
+            raise TypeError("ids, cu_seqlens and seg_b must be int32")
+        ids = ids.to(self.device).contiguous()
+        cu = cu_seqlens.to(self.device).contiguous()
+        seg = seg_b.to(self.device).contiguous()
+        n, T = int(cu.numel()) - 1, int(ids.numel())
+        if int(seg.numel()) != n:
+            raise ValueError(f"seg_b has {int(seg.numel())} entries for {n} pairs")
+        if out is None:
+            out = torch.empty((n,), dtype=torch.float32, device=self.device)
+        self.score_into(ids, cu, seg, n, T, max_seqlen, out)
+        return out
 
     def encode_packed(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int,
                       out: Optional[torch.Tensor] = None, cu_host: Optional[np.ndarray] = None,

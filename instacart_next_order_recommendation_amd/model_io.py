@@ -360,3 +360,177 @@ def write_synthetic_model_dir(path: Path | str, seed: int = 0, shape: BertShape 
         "pooling_mode_mean_tokens": pooling == "mean", "pooling_mode_max_tokens": False}))
     (d / "2_Normalize").mkdir(exist_ok=True)
     return d
+
+
+# --------------------------------------------------------------------------- cross-encoders (reranker.py)
+#: A side of a pair is tokenised on its own and keeps up to this many tokens before the pair is assembled and truncated
+#: (assemble_pairs): the pair's truncation needs the sides' real lengths, and no side of up to 2,048 tokens is cut early.
+SIDE_MAX_TOKENS = 2048
+
+
+@dataclass
+class LoadedCrossEncoder:
+    """A BertForSequenceClassification(num_labels=1) directory: the encoder's blob, and the score head beside it."""
+
+    shape: BertShape
+    weights: np.ndarray   # flat fp32 blob, include/icrec.h order (the head is not part of it)
+    pooler_w: np.ndarray  # float32 [hidden, hidden], [out, in]
+    pooler_b: np.ndarray  # float32 [hidden]
+    cls_w: np.ndarray     # float32 [hidden]
+    cls_b: np.ndarray     # float32 [1]
+    max_seq_length: int
+    tokenizer: HostTokenizer  # tokenises ONE side ([CLS] side [SEP], cut at SIDE_MAX_TOKENS only: strip_specials)
+    activation: str       # "sigmoid" or "identity": what CrossEncoder.predict applies to the logit
+
+
+def load_cross_encoder_dir(model_dir: Path | str) -> LoadedCrossEncoder:
+    """Parse a local cross-encoder directory (the cross-encoder/ms-marco-MiniLM-L-*-v2 layout: config.json of a
+    BertForSequenceClassification with one label, model.safetensors with bert.embeddings.* / bert.encoder.* /
+    bert.pooler.dense.* / classifier.*, the tokenizer files).  Anything else raises ValueError naming the field."""
+    from safetensors.numpy import load_file
+
+    d = Path(model_dir)
+    if not d.is_dir():
+        raise FileNotFoundError(
+            f"model_dir {model_dir!r} is not a local directory (hub ids cannot be fetched: no network)")
+    cfg = json.loads((d / "config.json").read_text())
+    if cfg.get("model_type", "bert") != "bert":
+        raise ValueError(f"unsupported model_type {cfg.get('model_type')!r}: the reranker serves BERT cross-encoders")
+    if cfg.get("hidden_act", "gelu") != "gelu":
+        raise ValueError(f"unsupported hidden_act {cfg.get('hidden_act')!r} (kernels implement erf-GELU)")
+    n_labels = len(cfg["id2label"]) if "id2label" in cfg else int(cfg.get("num_labels", 2))
+    if "num_labels" in cfg and int(cfg["num_labels"]) != n_labels:
+        raise ValueError(f"num_labels {cfg['num_labels']} contradicts id2label of size {n_labels}")
+    if n_labels != 1:
+        raise ValueError(f"num_labels / id2label of size {n_labels}: only single-logit cross-encoders (num_labels = 1) are served")
+    if int(cfg.get("type_vocab_size", 2)) < 2:
+        raise ValueError(f"type_vocab_size {cfg.get('type_vocab_size')}: a pair needs two token-type rows")
+    act = str(cfg.get("sbert_ce_default_activation_function") or "torch.nn.modules.activation.Sigmoid")
+    if not act.endswith(("Sigmoid", "Identity")):
+        raise ValueError(f"unsupported sbert_ce_default_activation_function {act!r} (Sigmoid or Identity)")
+    shape = BertShape(vocab_size=int(cfg["vocab_size"]), hidden=int(cfg["hidden_size"]),
+                      layers=int(cfg["num_hidden_layers"]), heads=int(cfg["num_attention_heads"]),
+                      intermediate=int(cfg["intermediate_size"]), max_position=int(cfg["max_position_embeddings"]),
+                      type_vocab=int(cfg.get("type_vocab_size", 2)), ln_eps=float(cfg.get("layer_norm_eps", 1e-12)),
+                      n_normalize=0)
+    st = d / "model.safetensors"
+    if not st.exists():
+        raise FileNotFoundError(f"{st} missing (pytorch_model.bin pickles are not loaded: only safetensors)")
+    sd = load_file(str(st))
+    H = shape.hidden
+    head = {}
+    for name, shp in (("bert.pooler.dense.weight", (H, H)), ("bert.pooler.dense.bias", (H,)),
+                      ("classifier.weight", (1, H)), ("classifier.bias", (1,))):
+        if name not in sd:
+            raise ValueError(f"{name} missing from {st.name}: not a BertForSequenceClassification with a pooler")
+        if tuple(sd[name].shape) != shp:
+            raise ValueError(f"{name}: expected {shp}, got {tuple(sd[name].shape)}")
+        head[name] = np.ascontiguousarray(sd[name], dtype=np.float32)
+    weights = state_dict_to_blob(sd, shape)
+    limit = min(_native.ICREC_MAX_SEQLEN, shape.max_position)
+    max_len = limit  # a cross-encoder reads up to the model's positions (tokenizer_config.json may ask for fewer)
+    tc = d / "tokenizer_config.json"
+    if tc.exists():
+        asked = json.loads(tc.read_text()).get("model_max_length")
+        if isinstance(asked, int) and 4 <= asked < max_len:
+            max_len = asked
+    return LoadedCrossEncoder(shape, weights, head["bert.pooler.dense.weight"], head["bert.pooler.dense.bias"],
+                              head["classifier.weight"].reshape(H), head["classifier.bias"], max_len,
+                              HostTokenizer(d, SIDE_MAX_TOKENS + 2), "identity" if act.endswith("Identity") else "sigmoid")
+
+
+def write_synthetic_cross_encoder_dir(path: Path | str, seed: int = 0, shape: BertShape | None = None,
+                                      activation: Optional[str] = None, max_length: Optional[int] = None) -> Path:
+    """Write a cross-encoder directory (load_cross_encoder_dir's layout) with seeded random weights and the synthetic
+    WordPiece vocab.  The encoder's tensors are synthetic_bert_weights(shape, seed) under the `bert.` prefix - its two
+    token-type rows are independent draws, so row 1 differs from row 0 -, the pooler ~ N(0, 0.05) with bias ~ N(0, 0.02),
+    the classifier ~ N(0, 0.1).  activation: None (no entry: sigmoid), "sigmoid" or "identity";  max_length: the
+    tokenizer's model_max_length (default: the model's positions)."""
+    from safetensors.numpy import save_file
+
+    from .synthetic import normalish
+
+    if activation not in (None, "sigmoid", "identity"):
+        raise ValueError(f"activation must be None, 'sigmoid' or 'identity', got {activation!r}")
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    vocab = synthetic_vocab()
+    if shape is None:
+        shape = BertShape(vocab_size=len(vocab), n_normalize=0)
+    if shape.vocab_size < len(vocab):
+        raise ValueError("shape.vocab_size smaller than the synthetic vocab")
+    if shape.type_vocab < 2:
+        raise ValueError("a cross-encoder needs two token-type rows: shape.type_vocab must be >= 2")
+    H = shape.hidden
+    sd = {"bert." + k: v for k, v in blob_to_state_dict(synthetic_bert_weights(shape, seed=seed), shape).items()}
+    types = sd["bert.embeddings.token_type_embeddings.weight"]
+    assert np.abs(types[1] - types[0]).max() > 0
+    sd["bert.pooler.dense.weight"] = normalish(seed, 8_001, H * H, 0.05).reshape(H, H)
+    sd["bert.pooler.dense.bias"] = normalish(seed, 8_002, H, 0.02)
+    sd["classifier.weight"] = normalish(seed, 8_003, H, 0.1).reshape(1, H)
+    sd["classifier.bias"] = normalish(seed, 8_004, 1, 0.02)
+    config = {"architectures": ["BertForSequenceClassification"], "model_type": "bert", "vocab_size": shape.vocab_size,
+              "hidden_size": H, "num_hidden_layers": shape.layers, "num_attention_heads": shape.heads,
+              "intermediate_size": shape.intermediate, "hidden_act": "gelu", "layer_norm_eps": shape.ln_eps,
+              "max_position_embeddings": shape.max_position, "type_vocab_size": shape.type_vocab,
+              "id2label": {"0": "LABEL_0"}, "label2id": {"LABEL_0": 0}}
+    if activation is not None:
+        config["sbert_ce_default_activation_function"] = "torch.nn.modules." + (
+            "linear.Identity" if activation == "identity" else "activation.Sigmoid")
+    save_file({k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sd.items()}, str(d / "model.safetensors"))
+    (d / "config.json").write_text(json.dumps(config, indent=2))
+    (d / "vocab.txt").write_text("\n".join(vocab) + "\n")
+    tok_cfg = {"do_lower_case": True, "tokenizer_class": "BertTokenizer"}
+    if max_length is not None:
+        tok_cfg["model_max_length"] = int(max_length)
+    (d / "tokenizer_config.json").write_text(json.dumps(tok_cfg))
+    return d
+
+
+def strip_specials(ids: np.ndarray, cu: np.ndarray) -> list[np.ndarray]:
+    """HostTokenizer.packed output (`[CLS] tokens [SEP]` back to back) -> each text's tokens without the two specials."""
+    return [ids[cu[i] + 1:cu[i + 1] - 1] for i in range(len(cu) - 1)]
+
+
+def truncate_pair(len_a: int, len_b: int, max_len: int) -> tuple[int, int]:
+    """How many tokens of each side of a pair survive truncation to `max_len` ids, three of them special: the
+    `longest_first` strategy as the `tokenizers` library (what sentence-transformers' CrossEncoder tokenises with)
+    applies it, in closed form.  Tokens go one at a time from the end of the longer side until the pair fits; once the
+    sides are level the shorter one - the FIRST on an exact tie - ends with floor(budget / 2) tokens and the other with
+    the rest.  (transformers' pure-Python tokenizers break the tie the other way; the Rust library is the one matched.)"""
+    budget = max_len - 3
+    if budget < 0:
+        raise ValueError(f"max_len {max_len} leaves no room for [CLS] [SEP] [SEP]")
+    if len_a + len_b <= budget:
+        return len_a, len_b
+    a_short = len_a <= len_b
+    short, long_ = (len_a, len_b) if a_short else (len_b, len_a)
+    if 2 * short <= budget:
+        long_ = budget - short
+    else:
+        short, long_ = budget // 2, budget - budget // 2
+    return (short, long_) if a_short else (long_, short)
+
+
+def assemble_pairs(a_ids: Sequence[Sequence[int]], b_ids: Sequence[Sequence[int]], max_len: int, cls_id: int,
+                   sep_id: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Pair i = `[CLS] a_ids[i] [SEP] b_ids[i] [SEP]` truncated to max_len (truncate_pair), from the two sides' token ids
+    without specials -> (ids int32[T], cu_seqlens int32[n+1], seg_b int32[n]): icrec_score_pairs' packed input, seg_b[i]
+    = kept tokens of side a + 2 the position of the first token of type 1."""
+    if len(a_ids) != len(b_ids):
+        raise ValueError(f"{len(a_ids)} first sides against {len(b_ids)} second sides")
+    n = len(a_ids)
+    kept = [truncate_pair(len(a), len(b), max_len) for a, b in zip(a_ids, b_ids)]
+    cu = np.zeros(n + 1, np.int32)
+    np.cumsum([ka + kb + 3 for ka, kb in kept], out=cu[1:])
+    ids = np.empty(int(cu[-1]), np.int32)
+    seg_b = np.empty(n, np.int32)
+    for i, (ka, kb) in enumerate(kept):
+        o = int(cu[i])
+        ids[o] = cls_id
+        ids[o + 1:o + 1 + ka] = a_ids[i][:ka]
+        ids[o + 1 + ka] = sep_id
+        ids[o + 2 + ka:o + 2 + ka + kb] = b_ids[i][:kb]
+        ids[o + 2 + ka + kb] = sep_id
+        seg_b[i] = ka + 2
+    return ids, cu, seg_b

@@ -1,0 +1,295 @@
+"""Pair scoring on the GPU (icrec_score_pairs, DeviceEncoder.score_packed, reranker.py): the logits against the float64
+reference of tests/pair_reference.py, the head alone against the numpy float64 head on icrec_encode_ex's token rows, the
+same bits alone / in a batch / in every dispatch form / with the full last layer, icrec_encode untouched by a head,
+poisoned workspaces, graph capture, the ABI's refusals, and a reranked recommender end to end."""
+from __future__ import annotations
+
+import ctypes as C
+import json
+
+import numpy as np
+import pytest
+
+from tests import pair_reference as pr
+from tests.encoder_harness import FORMS, make_encoder, run
+
+pytestmark = pytest.mark.gpu
+
+CASES = [(h, l, name) for h, l in pr.SHAPES for name in pr.BATCHES]
+
+
+def scorer(monkeypatch, r, mode="f16x3", head=True, **env):
+    enc = make_encoder(monkeypatch, r["w"], r["s"], mode, max_seq_length=r["max_len"], **env)
+    assert not enc.has_score_head
+    if head:
+        enc.set_score_head(*r["head"])
+        assert enc.has_score_head
+    return enc
+
+
+def score(enc, ids, cu, seg_b):
+    import torch
+
+    out = enc.score_packed(torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda(), torch.from_numpy(seg_b).cuda(),
+                           int(np.diff(cu).max()))
+    assert out.shape == (cu.size - 1,) and out.dtype == torch.float32
+    return out.cpu().numpy()
+
+
+# ---------------------------------------------------------------- 1. against the reference
+@pytest.mark.parametrize("hidden,layers,name", CASES)
+@pytest.mark.parametrize("mode", pr.MODES)
+def test_logits_against_the_float64_reference(monkeypatch, mode, hidden, layers, name):
+    """|logit_gpu - logit_f64| <= margin x E_ref; prints the ratio first (profiles/pair_score_errors.md holds them)."""
+    r = pr.case(hidden, layers, name)
+    enc = scorer(monkeypatch, r, mode)
+    got = score(enc, r["ids"], r["cu"], r["seg_b"])
+    enc.close()
+    assert np.isfinite(got).all()
+    pr.check(f"pair logits mode={mode} hidden={hidden} layers={layers} batch={name}", got, r["l64"], r["l32"],
+             pr.MARGINS[(mode, hidden)])
+
+
+@pytest.mark.parametrize("hidden,layers,name", CASES)
+@pytest.mark.parametrize("mode", pr.MODES)
+def test_head_alone_against_numpy_on_the_token_rows(monkeypatch, mode, hidden, layers, name):
+    """With seg_b = len for every pair the layers are icrec_encode_ex's: the logit is the numpy float64 head applied to row
+    cu[s] of tokens_out for the same ids, within margin x the head's own E_ref (the float32 head against the float64
+    head on the float32 reference's rows)."""
+    r = pr.case(hidden, layers, name)
+    enc = scorer(monkeypatch, r, mode)
+    got = score(enc, r["ids"], r["cu"], r["whole"])
+    _, tok = run(enc, r["ids"], r["cu"], return_tokens=True)
+    enc.close()
+    e_ref = pr.errors(r["whole32"], r["head64"])
+    e_gpu = pr.errors(got, pr.head64(tok[r["cu"][:-1]], r["head"]))
+    margin = pr.HEAD_MARGINS[(mode, hidden)]
+    print(f"RATIO head alone mode={mode} hidden={hidden} layers={layers} batch={name}: E_gpu {e_gpu:.3e}, "
+          f"E_ref {e_ref:.3e}, ratio {e_gpu / e_ref:.2f} (margin {margin})")
+    assert e_ref > 0 and e_gpu <= margin * e_ref
+
+
+# ---------------------------------------------------------------- 2. same bits
+@pytest.mark.parametrize("hidden,layers,name", CASES)
+@pytest.mark.parametrize("mode", pr.MODES)
+def test_same_bits_alone_in_batch_and_in_every_form(monkeypatch, mode, hidden, layers, name):
+    """Each pair alone equals its batch entry; the dispatch forms of encoder_harness.FORMS, ICREC_SMALL_M=512 (the batch
+    kernels for the main batch) and ICREC_CLS_PRUNE=0 (the full last layer) all give the default's bits."""
+    r = pr.case(hidden, layers, name)
+    ids, cu, seg_b = r["ids"], r["cu"], r["seg_b"]
+    enc = scorer(monkeypatch, r, mode)
+    want = score(enc, ids, cu, seg_b)
+    for i, n in enumerate(np.diff(cu)):
+        alone = score(enc, ids[cu[i]:cu[i + 1]].copy(), np.array([0, n], np.int32), seg_b[i:i + 1].copy())
+        assert alone[0] == want[i], f"pair {i} ({n} tokens, seg_b {seg_b[i]}) alone"
+    enc.close()
+    forms = FORMS[1:] + [("small_m_512", {"ICREC_SMALL_M": 512}), ("full_last_layer", {"ICREC_CLS_PRUNE": 0}),
+                         ("full_last_layer_unfused", {"ICREC_CLS_PRUNE": 0, "ICREC_FUSE": 0})]
+    for form, env in forms:
+        other = scorer(monkeypatch, r, mode, **env)
+        np.testing.assert_array_equal(score(other, ids, cu, seg_b), want, err_msg=form)
+        other.close()
+    # the pooling mode of the handle does not enter
+    cls = make_encoder(monkeypatch, r["w"], r["s"], mode, max_seq_length=r["max_len"], pooling="cls")
+    cls.set_score_head(*r["head"])
+    np.testing.assert_array_equal(score(cls, ids, cu, seg_b), want, err_msg="CLS-pooled handle")
+    cls.close()
+
+
+@pytest.mark.parametrize("mode", pr.MODES)
+def test_out_of_range_segment_starts_are_clamped(monkeypatch, mode):
+    """seg_b below 0 scores as 0, above the length as the length."""
+    r = pr.case(384, 2, "to256")
+    enc = scorer(monkeypatch, r, mode)
+    lens = np.diff(r["cu"]).astype(np.int32)
+    np.testing.assert_array_equal(score(enc, r["ids"], r["cu"], lens + 1000), score(enc, r["ids"], r["cu"], lens))
+    np.testing.assert_array_equal(score(enc, r["ids"], r["cu"], -lens), score(enc, r["ids"], r["cu"], 0 * lens))
+    enc.close()
+
+
+@pytest.mark.parametrize("mode", pr.MODES)
+def test_a_head_does_not_change_encoding(monkeypatch, mode):
+    """icrec_encode on an encoder with a head gives the bits of one without, before and after a score call, and asks for
+    the same workspace."""
+    from instacart_next_order_recommendation_amd import _native
+
+    L = _native.lib()
+    r = pr.case(384, 2, "to256")
+    n, T = r["cu"].size - 1, int(r["cu"][-1])
+    plain = scorer(monkeypatch, r, mode, head=False)
+    emb, tok = run(plain, r["ids"], r["cu"], return_tokens=True)
+    want = run(plain, r["ids"], r["cu"])
+    with_head = scorer(monkeypatch, r, mode)
+    assert L.icrec_encode_workspace_bytes(with_head._h, T, n) == L.icrec_encode_workspace_bytes(plain._h, T, n)
+    np.testing.assert_array_equal(run(with_head, r["ids"], r["cu"]), want)
+    score(with_head, r["ids"], r["cu"], r["seg_b"])
+    np.testing.assert_array_equal(run(with_head, r["ids"], r["cu"]), want)
+    emb2, tok2 = run(with_head, r["ids"], r["cu"], return_tokens=True)
+    np.testing.assert_array_equal(emb2, emb)
+    np.testing.assert_array_equal(tok2, tok)
+    with_head.set_score_head(None)  # removed again
+    assert not with_head.has_score_head
+    np.testing.assert_array_equal(run(with_head, r["ids"], r["cu"]), want)
+    plain.close(); with_head.close()
+
+
+# ---------------------------------------------------------------- 3. workspace and capture
+@pytest.mark.parametrize("hidden,layers,name", CASES)
+@pytest.mark.parametrize("mode", pr.MODES)
+def test_poisoned_workspace_never_reaches_the_logits(monkeypatch, mode, hidden, layers, name):
+    import torch
+
+    from instacart_next_order_recommendation_amd import _native
+
+    r = pr.case(hidden, layers, name)
+    enc = scorer(monkeypatch, r, mode)
+    first = score(enc, r["ids"], r["cu"], r["seg_b"])  # sizes the workspace
+    ws = enc._ws_by_stream[torch.cuda.current_stream().cuda_stream]
+    assert ws.numel() == _native.lib().icrec_score_pairs_workspace_bytes(enc._h, int(r["cu"][-1]), r["cu"].size - 1)
+    for fill in (0xFF, 0x00):
+        ws.fill_(fill)
+        got = score(enc, r["ids"], r["cu"], r["seg_b"])
+        assert np.isfinite(got).all(), f"byte 0x{fill:02X} leaked into the logits"
+        np.testing.assert_array_equal(got, first, err_msg=f"fill 0x{fill:02X}")
+    enc.close()
+
+
+@pytest.mark.parametrize("mode", pr.MODES)
+def test_score_into_under_graph_capture(monkeypatch, mode):
+    """score_into is capturable: warmed up on a side stream, captured with a workspace of its own, then - output zeroed,
+    workspace full of 0xFF - replayed once: the eager call's bits (encoder_harness.replay_matches_eager's pattern)."""
+    import torch
+
+    r = pr.case(384, 2, "to256")
+    enc = scorer(monkeypatch, r, mode)
+    eager = score(enc, r["ids"], r["cu"], r["seg_b"])
+    d_ids, d_cu, d_seg = (torch.from_numpy(r[k]).cuda() for k in ("ids", "cu", "seg_b"))
+    n, T, mx = r["cu"].size - 1, int(r["cu"][-1]), int(np.diff(r["cu"]).max())
+    out = torch.zeros((n,), dtype=torch.float32, device="cuda")
+    ws = torch.empty(enc._ws_by_stream[torch.cuda.current_stream().cuda_stream].numel(), dtype=torch.uint8, device="cuda")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # warm-up outside the capture
+        enc.score_into(d_ids, d_cu, d_seg, n, T, mx, out, ws)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        enc.score_into(d_ids, d_cu, d_seg, n, T, mx, out, ws)
+    out.zero_(); ws.fill_(0xFF)
+    g.replay()
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(out.cpu().numpy(), eager)
+    enc.close()
+
+
+# ---------------------------------------------------------------- 4. refusals
+def test_refusals_change_nothing(monkeypatch):
+    import torch
+
+    from instacart_next_order_recommendation_amd import _native, synthetic as syn
+
+    L = _native.lib()
+    r = pr.case(384, 2, "to256")
+    enc = scorer(monkeypatch, r, head=False)
+    d_ids, d_cu, d_seg = (torch.from_numpy(r[k]).cuda() for k in ("ids", "cu", "seg_b"))
+    n, T = r["cu"].size - 1, int(r["cu"][-1])
+    out = torch.full((n,), 7.0, dtype=torch.float32, device="cuda")
+    ws = torch.empty(int(L.icrec_score_pairs_workspace_bytes(enc._h, T, n)), dtype=torch.uint8, device="cuda")
+    args = (enc._h, _native.ptr(d_ids), _native.ptr(d_cu), _native.ptr(d_seg), n, T, 256, _native.ptr(out), _native.ptr(ws),
+            ws.numel(), _native.stream_ptr(enc.device))
+    assert L.icrec_score_pairs(*args) == -1  # no head set
+    assert b"score head" in L.icrec_last_error()
+    torch.cuda.synchronize()
+    assert (out == 7.0).all()
+    head = [np.array(a, np.float32) for a in r["head"]]
+    for which, at in ((0, (5, 7)), (1, 3), (2, 380), (3, 0)):
+        for bad_value in (np.nan, np.inf):
+            bad = [a.copy() for a in head]
+            bad[which][at] = bad_value
+            with pytest.raises(_native.IcrecError, match="not finite"):
+                enc.set_score_head(*bad)
+            assert not enc.has_score_head
+    enc.set_score_head(*head)
+    want = score(enc, r["ids"], r["cu"], r["seg_b"])
+    bad = [a.copy() for a in head]
+    bad[0][0, 0] = -np.inf
+    with pytest.raises(_native.IcrecError):
+        enc.set_score_head(*bad)
+    assert enc.has_score_head  # a refused head leaves the one in place
+    np.testing.assert_array_equal(score(enc, r["ids"], r["cu"], r["seg_b"]), want)
+    assert L.icrec_score_pairs(*args[:6], 257, *args[7:]) == -1  # beyond the encoder's ceiling, as icrec_encode
+    assert L.icrec_score_pairs(*args[:9], ws.numel() - 1, args[10]) == -3  # ICREC_ENOMEM
+    enc.close()
+    s1 = syn.BertShape(vocab_size=pr.VOCAB, layers=1, type_vocab=1)
+    one = make_encoder(monkeypatch, syn.synthetic_bert_weights(s1, seed=2), s1)
+    with pytest.raises(_native.IcrecError, match="type_vocab"):
+        one.set_score_head(*head)
+    assert not one.has_score_head
+    one.close()
+    assert C.sizeof(_native.BertCfg) == 40  # the head lives on the handle, not in icrec_bert_cfg
+
+
+# ---------------------------------------------------------------- 5. end to end
+def test_reranked_recommender_end_to_end(tmp_path):
+    """A synthetic cross-encoder directory, a synthetic bi-encoder directory and a 300-product catalog:
+    RerankedRecommender.recommend(q, 10, exclude) returns the candidates of Recommender.recommend(q, 100, exclude) in the
+    order of CrossEncoderReranker.predict, no excluded id among them; predict agrees with the reference within the
+    accuracy margin."""
+    import torch
+
+    from instacart_next_order_recommendation_amd import synthetic as syn
+    from instacart_next_order_recommendation_amd.model_io import (assemble_pairs, load_cross_encoder_dir,
+                                                                  write_synthetic_cross_encoder_dir, write_synthetic_model_dir)
+    from instacart_next_order_recommendation_amd.recommender import Recommender
+    from instacart_next_order_recommendation_amd.reranker import CrossEncoderReranker, RerankedRecommender
+
+    n_vocab = len(syn.synthetic_vocab())
+    bi_dir = write_synthetic_model_dir(tmp_path / "bi", seed=8, shape=syn.BertShape(vocab_size=n_vocab, layers=2))
+    ce_shape = syn.BertShape(vocab_size=n_vocab, layers=2, n_normalize=0)
+    ce_dir = write_synthetic_cross_encoder_dir(tmp_path / "ce", seed=9, shape=ce_shape, activation="identity")
+    corpus_path = tmp_path / "processed" / "eval_corpus.json"
+    corpus_path.parent.mkdir()
+    catalog = syn.synthetic_catalog(300)
+    corpus_path.write_text(json.dumps(catalog))
+    rec = Recommender(bi_dir, corpus_path)
+    rr = CrossEncoderReranker(ce_dir)
+    assert rr.activation == "identity" and rr.encoder.has_score_head and rr.encoder.gemm_mode == "f16x3"
+    both = RerankedRecommender(rec, rr, candidates=100)
+    queries = syn.synthetic_user_contexts(3, seed=9)
+    excl = [None, {"1", "2", "17"}, set(str(i) for i in range(1, 60))]
+    m = load_cross_encoder_dir(ce_dir)
+    ref64 = pr.PairBert(m.weights, m.shape, (m.pooler_w, m.pooler_b, m.cls_w, m.cls_b))
+    ref32 = pr.PairBert(m.weights, m.shape, (m.pooler_w, m.pooler_b, m.cls_w, m.cls_b), torch.float32)
+    e_ref = None
+    for q, ex in zip(queries, excl):
+        found = rec.recommend(q, 100, ex)
+        assert len(found) == 100
+        pairs = [(q, catalog[pid]) for pid, _ in found]
+        scores = rr.predict(pairs)
+        if e_ref is None:  # the references of the first query's first 40 pairs (a pair scores alike in any batch)
+            sub = pairs[:40]
+            ids, cu, seg_b = assemble_pairs(rr.side_ids([a for a, _ in sub]), rr.side_ids([b for _, b in sub]),
+                                            rr.max_seq_length, rr.cls_id, rr.sep_id)
+            l64, l32 = ref64.logits(ids, cu, seg_b), ref32.logits(ids, cu, seg_b)
+            pr.check(f"predict, {len(sub)} pairs of {int(np.diff(cu).mean())} tokens", scores[:40], l64, l32,
+                     pr.MARGINS[("f16x3", 384)])
+            np.testing.assert_array_equal(rr.predict(sub), scores[:40])
+            e_ref = pr.errors(l32, l64)
+        got = both.recommend(q, 10, ex)
+        assert len(got) == 10 and not ({p for p, _ in got} & (ex or set()))
+        by_pid = {pid: float(s) for (pid, _), s in zip(found, scores)}
+        for pid, s in got:  # a pair scores to the same bits in predict's batch and in recommend's
+            assert by_pid[pid] == s
+        want = [found[i][0] for i in np.argsort(-scores, kind="stable")[:10]]
+        for g, w in zip([p for p, _ in got], want):
+            assert g == w or abs(by_pid[g] - by_pid[w]) <= 10 * e_ref, (g, w)
+        assert [s for _, s in got] == sorted((s for _, s in got), reverse=True)
+        ranked = rr.rank(q, [catalog[pid] for pid, _ in found], top_k=10)
+        assert [found[i][0] for i, _ in ranked] == [p for p, _ in got]
+    # the default activation is the sigmoid of the same logit
+    sg = CrossEncoderReranker(write_synthetic_cross_encoder_dir(tmp_path / "sg", seed=9, shape=ce_shape))
+    assert sg.activation == "sigmoid"
+    p = sg.predict(pairs)
+    np.testing.assert_allclose(p, 1 / (1 + np.exp(-scores.astype(np.float64))), rtol=1e-6)
+    rr.close(); sg.close()
