@@ -225,6 +225,67 @@ ICREC_API int icrec_score_pairs(icrec_encoder* enc,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Reranking glue: icrec_search's candidates -> icrec_score_pairs' packed     */
+/* input, and the logits -> the final top k, all on the device.  With these    */
+/* retrieve -> rerank is icrec_encode, icrec_search, icrec_assemble_pairs,     */
+/* icrec_score_pairs, icrec_rerank_select on one stream with no host step in   */
+/* between: capturable for one request, batched for many.  Neither call takes  */
+/* an encoder or index handle; `device` is the HIP ordinal of the pointers.    */
+/* ------------------------------------------------------------------------- */
+
+/* Scratch bytes icrec_assemble_pairs needs (0 for n_queries < 1 or k outside [1, ICREC_MAX_K]). */
+ICREC_API size_t icrec_assemble_pairs_workspace_bytes(int32_t n_queries, int32_t k);
+
+/* Assemble pair p = q * k + j = `[CLS] q_side(q)[:ka] [SEP] cat_side(cand[q][j] - row_offset)[:kb] [SEP]` for every
+ * query q and candidate j, packed back to back as icrec_score_pairs takes them.
+ *   q_ids_dev / q_cu_dev      int32[q_cu[n_queries]] / int32[n_queries+1]  the queries' cross-encoder token ids, without
+ *                             specials, packed, and their prefix sums
+ *   cat_ids_dev / cat_cu_dev  int32[cat_cu[n_rows]] / int32[n_rows+1]      the same for the catalog's product sides; row r
+ *                             is the index's row row_offset + r
+ *   cand_idx_dev              int64[n_queries, k]  icrec_search's out_idx (global rows, -1 pads)
+ *   max_len                   ids per pair after truncation, in [3, ICREC_MAX_SEQLEN]
+ *   ids_out_dev               int32[ids_cap]       the packed ids; entries from cu_out[n_queries*k] on are NOT written
+ *   cu_out_dev                int32[n_queries*k+1] exclusive prefix sums of the pair lengths, computed on the device
+ *   seg_b_out_dev             int32[n_queries*k]   ka + 2: where each pair's second segment starts
+ * (ka, kb) is the `longest_first` truncation of the `tokenizers` library in closed form: nothing is cut when
+ * len_a + len_b <= max_len - 3; otherwise the longer side gives way until the sides are level, and from there the shorter
+ * side - the FIRST on an exact tie - ends with floor((max_len - 3) / 2) tokens and the other with the rest.
+ * A candidate that is negative or outside [row_offset, row_offset + n_rows) becomes the three-token pair
+ * `[CLS] [SEP] [SEP]` with seg_b = 2: no sequence is ever empty.
+ * Which candidates arrive is known on the device only, so the caller bounds the token count from the host:
+ *   ids_cap >= sum over q of k * min(max_len, 3 + len_q + longest product side)
+ * and then calls icrec_score_pairs(n_seqs = n_queries*k, total_tokens = ids_cap, max_seqlen = the largest term's
+ * min(...)): token rows past cu_out[n_seqs] are computed and ignored (the embedding kernel clamps ids and positions, every
+ * other kernel is per row or reads cu_seqlens), and a pair's logit has the bits it has in an exactly sized batch.
+ * Every write is clamped to ids_cap: should the lengths not fit, the pairs from the first one that would leave fewer
+ * than three tokens for each later pair are all emitted as `[CLS] [SEP] [SEP]` - a safety net a correct bound never meets.
+ * ICREC_EINVAL: a NULL pointer, n_queries < 1, k outside [1, ICREC_MAX_K], max_len outside [3, ICREC_MAX_SEQLEN],
+ * n_queries * k * max_len >= 2^31 (the prefix sums are int32), ids_cap < 3 * n_queries * k.  ICREC_ENOMEM: workspace. */
+ICREC_API int icrec_assemble_pairs(const int32_t* q_ids_dev, const int32_t* q_cu_dev, int32_t n_queries,
+                         const int32_t* cat_ids_dev, const int32_t* cat_cu_dev, int64_t n_rows, int64_t row_offset,
+                         const int64_t* cand_idx_dev, int32_t k,
+                         int32_t max_len, int32_t cls_id, int32_t sep_id,
+                         int32_t* ids_out_dev, int64_t ids_cap, int32_t* cu_out_dev, int32_t* seg_b_out_dev,
+                         void* workspace_dev, size_t workspace_bytes, int device, void* stream);
+
+/* The best top_k <= k candidates of each query by cross-encoder logit.
+ *   logits_dev     float[n_queries, k]      icrec_score_pairs' output for icrec_assemble_pairs' pairs
+ *   cand_idx_dev   int64[n_queries, k]      the candidates (icrec_search's out_idx)
+ *   cand_score_dev float[n_queries, k]      icrec_search's out_score, or NULL: not read (the retrieval order is the
+ *                                           position j), taken so that a caller passes a search result as it is
+ *   out_idx_dev    int64[n_queries, top_k]  best first; -1 where fewer than top_k candidates had idx >= 0
+ *   out_logit_dev  float[n_queries, top_k]  their raw logits (0 where idx == -1)
+ * Order: logit descending (compared as floats), ties by lower retrieval position j, a NaN logit after every number;
+ * candidates with idx < 0 are skipped.  The outputs may be pinned host memory.  The model's activation (sigmoid or
+ * identity) is the caller's, applied to the top_k returned logits.  Ordering on the logit refines ordering on the
+ * activated score: the two differ only where float32 sigmoid maps distinct logits to one value, and there the logit order
+ * still separates what the score order leaves to the position.
+ * ICREC_EINVAL: a NULL pointer (cand_score_dev excepted), n_queries < 1, k outside [1, ICREC_MAX_K], top_k outside [1, k]. */
+ICREC_API int icrec_rerank_select(const float* logits_dev, const int64_t* cand_idx_dev, const float* cand_score_dev,
+                        int32_t n_queries, int32_t k, int32_t top_k,
+                        int64_t* out_idx_dev, float* out_logit_dev, int device, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Index + search: replaces cos_sim(query_emb, product_embeddings)            */
 /* (serve_recommendations.py:214/:250), scores.argsort(descending=True)       */
 /* (:215/:251) and the exclusion/top-k loop (:216-225/:254-262).              */

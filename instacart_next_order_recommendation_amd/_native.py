@@ -28,6 +28,7 @@ EXPORTS = [
     "icrec_encoder_set_attention_bias", "icrec_encoder_has_attention_bias",
     "icrec_encoder_set_score_head", "icrec_encoder_has_score_head",
     "icrec_score_pairs_workspace_bytes", "icrec_score_pairs",
+    "icrec_assemble_pairs_workspace_bytes", "icrec_assemble_pairs", "icrec_rerank_select",
     "icrec_encode_workspace_bytes", "icrec_encode", "icrec_encode_ex", "icrec_encode_batch_split",
     "icrec_index_create", "icrec_index_create_ex", "icrec_index_destroy", "icrec_index_rows", "icrec_index_storage",
     "icrec_index_export", "icrec_index_dim", "icrec_index_device",
@@ -102,6 +103,10 @@ def lib() -> C.CDLL:
         "icrec_encoder_has_score_head": (i32, [vp]),
         "icrec_score_pairs_workspace_bytes": (sz, [vp, i64, i32]),
         "icrec_score_pairs": (C.c_int, [vp, vp, vp, vp, i32, i64, i32, vp, vp, sz, vp]),
+        "icrec_assemble_pairs_workspace_bytes": (sz, [i32, i32]),
+        "icrec_assemble_pairs": (C.c_int, [vp, vp, i32, vp, vp, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, sz,
+                                           C.c_int, vp]),
+        "icrec_rerank_select": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, C.c_int, vp]),
         "icrec_encode_workspace_bytes": (sz, [vp, i64, i32]),
         "icrec_encode": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, vp, sz, vp]),
         "icrec_encode_ex": (C.c_int, [vp, vp, vp, i32, i64, i32, vp, vp, vp, sz, vp]),

@@ -1,0 +1,297 @@
+"""Device reranking on the GPU (icrec_assemble_pairs, icrec_rerank_select, DeviceReranker.rerank_into,
+RerankedRecommender's device path): the assembly element by element against model_io.assemble_pairs with guard words
+around every output, the selection against best_first, rerank_into's logits bit for bit against score_packed on the exact
+packing, the recommender end to end against its device_assembly=False twin, and the ABI's refusals."""
+from __future__ import annotations
+
+import json
+
+import numpy as np
+import pytest
+
+from tests import rerank_cases as rc
+
+pytestmark = pytest.mark.gpu
+
+POISON = 0x5A5A5A5A
+GUARD = 64  # guard words behind every output
+
+
+def dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def poisoned(n, dtype):
+    import torch
+
+    return torch.full((n + GUARD,), POISON, dtype=dtype, device="cuda")
+
+
+# ---------------------------------------------------------------- 1. assembly
+@pytest.mark.parametrize("max_len,k,n_queries", rc.ASSEMBLY_CASES)
+def test_assembly_is_exact(max_len, k, n_queries):
+    import torch
+
+    from instacart_next_order_recommendation_amd import _native
+    from instacart_next_order_recommendation_amd.reranker import pair_token_bound
+
+    L = _native.lib()
+    c = rc.assembly_case(max_len, k, n_queries)
+    want_ids, want_cu, want_seg = c["want"]
+    n_pairs, total = n_queries * k, int(want_cu[-1])
+    (q_ids, q_cu), (cat_ids, cat_cu) = rc.pack(c["q_sides"]), rc.pack(c["cat_sides"])
+    cap = pair_token_bound([len(q) for q in c["q_sides"]], k, max(len(s) for s in c["cat_sides"]), max_len)
+    assert cap >= total
+    ws_bytes = int(L.icrec_assemble_pairs_workspace_bytes(n_queries, k))
+    ids, cu, seg = poisoned(cap, torch.int32), poisoned(n_pairs + 1, torch.int32), poisoned(n_pairs, torch.int32)
+    ws = torch.full((ws_bytes + 4 * GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
+    d = [dev(a) for a in (q_ids, q_cu, cat_ids, cat_cu, c["cand"])]
+    rcode = L.icrec_assemble_pairs(_native.ptr(d[0]), _native.ptr(d[1]), n_queries, _native.ptr(d[2]), _native.ptr(d[3]),
+                                   len(c["cat_sides"]), rc.ROW_OFFSET, _native.ptr(d[4]), k, max_len, rc.CLS, rc.SEP,
+                                   _native.ptr(ids), cap, _native.ptr(cu), _native.ptr(seg), _native.ptr(ws), ws_bytes, 0,
+                                   _native.stream_ptr(ids.device))
+    assert rcode == 0, L.icrec_last_error()
+    torch.cuda.synchronize()
+    ids, cu, seg, ws = ids.cpu().numpy(), cu.cpu().numpy(), seg.cpu().numpy(), ws.cpu().numpy()
+    np.testing.assert_array_equal(cu[:n_pairs + 1], want_cu)
+    np.testing.assert_array_equal(seg[:n_pairs], want_seg)
+    np.testing.assert_array_equal(ids[:total], want_ids)
+    assert (ids[total:] == POISON).all(), "ids_out written past cu[-1]"
+    assert (cu[n_pairs + 1:] == POISON).all() and (seg[n_pairs:] == POISON).all() and (ws[ws_bytes:] == 0x5A).all()
+
+
+def test_the_safety_clamp_keeps_every_write_inside_ids_cap():
+    """An ids_cap below the bound is a caller's mistake the contract still defines: the pairs from the first one that would
+    leave fewer than three tokens for each later pair are `[CLS] [SEP] [SEP]`, and nothing is written at or past ids_cap."""
+    import torch
+
+    from instacart_next_order_recommendation_amd import _native
+
+    L = _native.lib()
+    max_len, k, n_queries = 16, 5, 205
+    c = rc.assembly_case(max_len, k, n_queries)
+    want_ids, want_cu, want_seg = c["want"]
+    n_pairs = n_queries * k
+    cap = int(want_cu[-1]) // 2
+    ends = want_cu[1:].astype(np.int64) + 3 * (n_pairs - 1 - np.arange(n_pairs))
+    pstar = int(np.argmax(ends > cap))
+    assert 0 < pstar < n_pairs and cap >= 3 * n_pairs
+    (q_ids, q_cu), (cat_ids, cat_cu) = rc.pack(c["q_sides"]), rc.pack(c["cat_sides"])
+    ids, cu, seg = poisoned(cap, torch.int32), poisoned(n_pairs + 1, torch.int32), poisoned(n_pairs, torch.int32)
+    ws = torch.empty(int(L.icrec_assemble_pairs_workspace_bytes(n_queries, k)), dtype=torch.uint8, device="cuda")
+    d = [dev(a) for a in (q_ids, q_cu, cat_ids, cat_cu, c["cand"])]
+    rcode = L.icrec_assemble_pairs(_native.ptr(d[0]), _native.ptr(d[1]), n_queries, _native.ptr(d[2]), _native.ptr(d[3]),
+                                   len(c["cat_sides"]), rc.ROW_OFFSET, _native.ptr(d[4]), k, max_len, rc.CLS, rc.SEP,
+                                   _native.ptr(ids), cap, _native.ptr(cu), _native.ptr(seg), _native.ptr(ws), ws.numel(), 0,
+                                   _native.stream_ptr(ids.device))
+    assert rcode == 0, L.icrec_last_error()
+    torch.cuda.synchronize()
+    ids, cu, seg = ids.cpu().numpy(), cu.cpu().numpy(), seg.cpu().numpy()
+    np.testing.assert_array_equal(cu[:pstar + 1], want_cu[:pstar + 1])
+    np.testing.assert_array_equal(cu[pstar:n_pairs + 1], want_cu[pstar] + 3 * np.arange(n_pairs - pstar + 1))
+    np.testing.assert_array_equal(seg[:pstar], want_seg[:pstar])
+    assert (seg[pstar:n_pairs] == 2).all()
+    total = int(cu[n_pairs])
+    assert total <= cap
+    np.testing.assert_array_equal(ids[:want_cu[pstar]], want_ids[:want_cu[pstar]])
+    np.testing.assert_array_equal(ids[want_cu[pstar]:total], np.tile([rc.CLS, rc.SEP, rc.SEP], n_pairs - pstar))
+    assert (ids[total:] == POISON).all() and (cu[n_pairs + 1:] == POISON).all() and (seg[n_pairs:] == POISON).all()
+
+
+# ---------------------------------------------------------------- 2. selection
+@pytest.mark.parametrize("k", rc.SELECT_K)
+def test_select_is_exact(k):
+    import torch
+
+    from instacart_next_order_recommendation_amd import _native
+
+    L = _native.lib()
+    c = rc.select_case(k)
+    n = len(c["names"])
+    logits, cand = dev(c["logits"]), dev(c["cand"])
+    for top_k in sorted({1, k}):
+        for pinned in (False, True):  # the outputs may be pinned host memory
+            if pinned:
+                out_idx = torch.full((n * top_k + GUARD,), POISON, dtype=torch.int64).pin_memory()
+                out_lg = torch.full((n * top_k + GUARD,), 7.0, dtype=torch.float32).pin_memory()
+            else:
+                out_idx, out_lg = poisoned(n * top_k, torch.int64), torch.full((n * top_k + GUARD,), 7.0, device="cuda")
+            rcode = L.icrec_rerank_select(_native.ptr(logits), _native.ptr(cand), None, n, k, top_k, _native.ptr(out_idx),
+                                          _native.ptr(out_lg), 0, _native.stream_ptr(logits.device))
+            assert rcode == 0, L.icrec_last_error()
+            torch.cuda.synchronize()
+            got_idx, got_lg = out_idx.cpu().numpy(), out_lg.cpu().numpy()
+            want_idx, want_lg = c["want"](top_k)
+            for q, name in enumerate(c["names"]):
+                np.testing.assert_array_equal(got_idx[q * top_k:(q + 1) * top_k], want_idx[q], err_msg=f"{name}, top_k {top_k}")
+                np.testing.assert_array_equal(got_lg[q * top_k:(q + 1) * top_k], want_lg[q], err_msg=f"{name}, top_k {top_k}")
+            assert (got_idx[n * top_k:] == POISON).all() and (got_lg[n * top_k:] == 7.0).all()
+
+
+# ---------------------------------------------------------------- the synthetic stack, built once
+_STACK = {}
+
+
+def stack(tmp_path_factory):
+    """A synthetic bi-encoder, a synthetic cross-encoder (hidden 384, 2 layers, sigmoid) and a 300-product catalog."""
+    if not _STACK:
+        from instacart_next_order_recommendation_amd import synthetic as syn
+        from instacart_next_order_recommendation_amd.model_io import write_synthetic_cross_encoder_dir, write_synthetic_model_dir
+
+        root = tmp_path_factory.mktemp("rerank_device")
+        n_vocab = len(syn.synthetic_vocab())
+        _STACK["bi_dir"] = write_synthetic_model_dir(root / "bi", seed=8, shape=syn.BertShape(vocab_size=n_vocab, layers=2))
+        _STACK["ce_dir"] = write_synthetic_cross_encoder_dir(root / "ce", seed=9,
+                                                             shape=syn.BertShape(vocab_size=n_vocab, layers=2, n_normalize=0))
+        _STACK["catalog"] = syn.synthetic_catalog(300)
+        path = root / "processed" / "eval_corpus.json"
+        path.parent.mkdir()
+        path.write_text(json.dumps(_STACK["catalog"]))
+        _STACK["corpus_path"] = path
+        _STACK["contexts"] = syn.synthetic_user_contexts(12, seed=9)
+    return _STACK
+
+
+# ---------------------------------------------------------------- 3. same bits as the host path
+@pytest.mark.parametrize("mode", ["f16x3", "f32"])
+def test_rerank_into_has_the_bits_of_the_exact_packing(tmp_path_factory, mode):
+    """3 queries x 20 candidates: the logits behind a padded total_tokens (ids_cap at the bound, and 1,000 beyond it, the
+    rows past cu[-1] full of poison) equal score_packed on assemble_pairs' exact packing; the selection is best_first's."""
+    import torch
+
+    from instacart_next_order_recommendation_amd.model_io import assemble_pairs
+    from instacart_next_order_recommendation_amd.reranker import (CrossEncoderReranker, DeviceReranker, RerankBuffers,
+                                                                  best_first)
+
+    s = stack(tmp_path_factory)
+    rr = CrossEncoderReranker(s["ce_dir"], gemm_mode=mode)
+    sides = rr.side_ids(list(s["catalog"].values()))
+    q_sides = rr.side_ids(s["contexts"][:3])
+    k, rng = 20, np.random.default_rng(5)
+    cand = np.stack([rng.permutation(len(sides))[:k] for _ in q_sides]).astype(np.int64)
+    cand[1, 7] = -1
+    empty = np.zeros(0, np.int32)
+    a = [q_sides[q] if c >= 0 else empty for q in range(3) for c in cand[q]]
+    b = [sides[c] if c >= 0 else empty for q in range(3) for c in cand[q]]
+    ids, cu, seg_b = assemble_pairs(a, b, rr.max_seq_length, rr.cls_id, rr.sep_id)
+    want = rr.encoder.score_packed(dev(ids), dev(cu), dev(seg_b), int(np.diff(cu).max())).cpu().numpy()
+    assert np.isfinite(want).all()
+    dr = DeviceReranker(rr, sides)
+    q_ids, q_cu = rc.pack(q_sides)
+    bound = dr.token_bound([len(q) for q in q_sides], k)
+    assert bound >= ids.size
+    print(f"slack at the bound: {(bound - ids.size) / bound:.3f} of {bound} rows")
+    for cap in (bound, bound + 1000):
+        bufs = RerankBuffers(dr, 3, k, k, cap)
+        bufs.ids.fill_(POISON)
+        bufs.logits.fill_(7.0)
+        dr.rerank_into(dev(q_ids), dev(q_cu), dev(cand), dr.max_pair_len(max(len(q) for q in q_sides)), bufs)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(bufs.cu.cpu().numpy(), cu)
+        np.testing.assert_array_equal(bufs.ids.cpu().numpy()[:ids.size], ids)
+        got = bufs.logits.cpu().numpy()
+        assert (got == want).all(), f"ids_cap {cap}: {np.flatnonzero(got != want)}"
+        out_idx, out_lg = bufs.out_idx.cpu().numpy(), bufs.out_logit.cpu().numpy()
+        for q in range(3):
+            valid = np.flatnonzero(cand[q] >= 0)
+            order = best_first(want[q * k:(q + 1) * k][valid])
+            np.testing.assert_array_equal(out_idx[q][:len(order)], [cand[q][valid[i]] for i, _ in order])
+            np.testing.assert_array_equal(out_lg[q][:len(order)], np.array([v for _, v in order], np.float32))
+            assert (out_idx[q][len(order):] == -1).all() and (out_lg[q][len(order):] == 0).all()
+    rr.close()
+
+
+# ---------------------------------------------------------------- 4. end to end
+def test_recommender_device_path_equals_the_host_path(tmp_path_factory):
+    """recommend(q, 10, exclude) through the captured graph equals the device_assembly=False instance's result, ids and
+    float scores alike; recommend_batch equals the per-query calls on both paths; a replayed graph serves its new query."""
+    from instacart_next_order_recommendation_amd.recommender import Recommender
+    from instacart_next_order_recommendation_amd.reranker import CrossEncoderReranker, RerankedRecommender
+
+    s = stack(tmp_path_factory)
+    rec = Recommender(s["bi_dir"], s["corpus_path"])
+    rr = CrossEncoderReranker(s["ce_dir"])
+    assert rr.activation == "sigmoid"
+    device = RerankedRecommender(rec, rr, candidates=100)
+    host = RerankedRecommender(rec, rr, candidates=100, device_assembly=False)
+    assert device.device_assembly and not host.device_assembly
+    # a query of 31 or 32 cross-encoder ids: 33 or 34 bi-encoder ids with [CLS] / [SEP], one bucket further up
+    words, straddle = " ".join(s["contexts"]).split(), []
+    for w in words:
+        if len(rr.side_ids([" ".join(straddle + [w])])[0]) <= 32:
+            straddle.append(w)
+    straddle = " ".join(straddle)
+    n_ce, n_bi = len(rr.side_ids([straddle])[0]), len(rec.model.tokenizer.packed([straddle])[0])
+    assert n_ce <= 32 < n_bi, (n_ce, n_bi)
+    queries = list(s["contexts"][:4]) + [straddle, s["contexts"][4]]
+    excl = [None, {"1", "2", "17"}, set(str(i) for i in range(1, 60)), None, {"5"}, None]
+    want = []
+    for q, ex in zip(queries, excl):
+        # the precondition of comparing a logit order with a score order (sigmoid never inverts an order, it can only merge
+        # neighbours): this query's best activated scores are distinct
+        found = rec.recommend(q, 100, ex)
+        scores = rr.predict([(q, s["catalog"][pid]) for pid, _ in found])
+        top = np.sort(scores)[::-1][:11]  # distinct down to the 11th: the best 10 and their order are the logits' too
+        assert len(found) == 100 and len(set(top.tolist())) == len(top), top
+        want.append(host.recommend(q, 10, ex))
+        assert len(want[-1]) == 10 and not ({p for p, _ in want[-1]} & (ex or set()))
+    n_graphs = []
+    for q, ex, w in zip(queries, excl, want):
+        assert device.recommend(q, 10, ex) == w, q
+        n_graphs.append(len(device._graphs))
+    assert n_graphs[-1] >= 2  # the straddling query took a graph of its own
+    # replays: every shape is captured by now, each query still gets its own answer, in another order
+    for i in (5, 0, 4, 2):
+        assert device.recommend(queries[i], 10, excl[i]) == want[i]
+    assert len(device._graphs) == n_graphs[-1]
+    assert device.recommend_batch(queries, 10, excl) == want
+    assert host.recommend_batch(queries, 10, excl) == want
+    assert device.recommend_batch([], 10) == []
+    # fewer candidates than asked for, top_k above them, and the un-captured single request
+    most = set(str(i) for i in range(1, 296))
+    assert device.recommend(queries[0], 10, most) == host.recommend(queries[0], 10, most)
+    assert len(device.recommend(queries[0], 10, most)) == 5
+    rec._fast = None
+    assert device.recommend(queries[1], 10, excl[1]) == want[1]
+    rr.close()
+
+
+# ---------------------------------------------------------------- 5. refusals
+def test_refusals_leave_the_outputs_untouched():
+    import torch
+
+    from instacart_next_order_recommendation_amd import _native
+
+    L = _native.lib()
+    c = rc.assembly_case(64, 5, 13)
+    (q_ids, q_cu), (cat_ids, cat_cu) = rc.pack(c["q_sides"]), rc.pack(c["cat_sides"])
+    n_pairs, cap = 65, 65 * 64
+    ids, cu, seg = poisoned(cap, torch.int32), poisoned(n_pairs + 1, torch.int32), poisoned(n_pairs, torch.int32)
+    ws = torch.full((int(L.icrec_assemble_pairs_workspace_bytes(13, 5)),), 0x5A, dtype=torch.uint8, device="cuda")
+    d = [dev(a) for a in (q_ids, q_cu, cat_ids, cat_cu, c["cand"])]
+    ok = dict(q_ids=_native.ptr(d[0]), q_cu=_native.ptr(d[1]), n_queries=13, cat_ids=_native.ptr(d[2]), cat_cu=_native.ptr(d[3]),
+              n_rows=len(c["cat_sides"]), row_offset=rc.ROW_OFFSET, cand=_native.ptr(d[4]), k=5, max_len=64, cls=rc.CLS,
+              sep=rc.SEP, ids_out=_native.ptr(ids), ids_cap=cap, cu_out=_native.ptr(cu), seg_b=_native.ptr(seg),
+              ws=_native.ptr(ws), ws_bytes=ws.numel(), device=0, stream=_native.stream_ptr(ids.device))
+    bad = [dict(k=0), dict(k=_native.ICREC_MAX_K + 1), dict(max_len=2), dict(max_len=_native.ICREC_MAX_SEQLEN + 1),
+           dict(n_queries=0), dict(n_queries=1 << 24, k=128, max_len=512), dict(ids_cap=3 * n_pairs - 1)]
+    bad += [{name: None} for name in ("q_ids", "q_cu", "cat_ids", "cat_cu", "cand", "ids_out", "cu_out", "seg_b", "ws")]
+    for kw in bad:
+        assert L.icrec_assemble_pairs(*{**ok, **kw}.values()) == -1, kw
+        assert b"icrec_assemble_pairs" in L.icrec_last_error()
+    assert L.icrec_assemble_pairs(*{**ok, "ws_bytes": ws.numel() - 1}.values()) == -3
+    torch.cuda.synchronize()
+    assert (ids == POISON).all() and (cu == POISON).all() and (seg == POISON).all() and (ws == 0x5A).all()
+
+    logits, cand = torch.zeros((2, 8), device="cuda"), dev(np.arange(16, dtype=np.int64).reshape(2, 8))
+    out_idx, out_lg = poisoned(16, torch.int64), torch.full((16,), 7.0, device="cuda")
+    ok = dict(logits=_native.ptr(logits), cand=_native.ptr(cand), cand_score=None, n_queries=2, k=8, top_k=8,
+              out_idx=_native.ptr(out_idx), out_logit=_native.ptr(out_lg), device=0, stream=_native.stream_ptr(logits.device))
+    for kw in (dict(k=0), dict(k=_native.ICREC_MAX_K + 1), dict(top_k=0), dict(top_k=9), dict(n_queries=0), dict(logits=None),
+               dict(cand=None), dict(out_idx=None), dict(out_logit=None)):
+        assert L.icrec_rerank_select(*{**ok, **kw}.values()) == -1, kw
+        assert b"icrec_rerank_select" in L.icrec_last_error()
+    torch.cuda.synchronize()
+    assert (out_idx == POISON).all() and (out_lg == 7.0).all()
