@@ -53,6 +53,7 @@ enum {
 
 typedef struct icrec_encoder icrec_encoder;
 typedef struct icrec_index icrec_index;
+typedef struct icrec_cf icrec_cf;
 
 /* ------------------------------------------------------------------------- */
 /* Encoder: replaces SentenceTransformer.encode's device work                 */
@@ -399,6 +400,94 @@ ICREC_API int icrec_scores(icrec_index* idx, const float* q_dev, int32_t n_queri
  * (torch.nn.functional.normalize(p=2, dim=1) as used by cos_sim.)            */
 ICREC_API int icrec_normalize_rows(const float* x_dev, float* out_dev, int64_t n_rows,
                          int32_t dim, float eps, int device, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Item-item co-occurrence collaborative filtering: replaces the reference's  */
+/* ItemItemCFBaseline (src/baselines/collaborative_filtering.py:104-163): its  */
+/* co-occurrence dict and the |corpus| x |history| lookups of rank_all.        */
+/*   score(q, p) = sum over h in history(q) of cooc(p, h)                      */
+/*               = sum over the orders o that hold p of |basket_o ∩ history(q)| */
+/* so two sparse passes over the order x item incidence matrix rank a whole    */
+/* tile of queries and no co-occurrence table exists (csrc/cf.hip).            */
+/* ------------------------------------------------------------------------- */
+
+/* Items are numbered 0 .. n_items-1.  The first n_candidates are the corpus rows, the only items that are ranked; the
+ * rest occur in baskets and histories only (the reference keeps them as history and never ranks them).
+ *   order_off   int64[n_orders+1]  HOST CSR offsets of the baskets (order_off[0] == 0, non-decreasing)
+ *   order_items int32[order_off[n_orders]]  HOST item ids; an item may repeat inside a basket
+ * On `device` the library builds the de-duplicated baskets (the reference's dict.fromkeys) and their transpose
+ * item -> orders (count, prefix sum, fill).  A set-up call: it allocates, copies and synchronises.
+ * ICREC_EINVAL, before anything is launched: a NULL pointer, n_orders or n_items outside [1, 2^31), n_candidates outside
+ * [1, n_items] or >= 2^32, an item outside [0, n_items), offsets that decrease, 2^31 or more entries, more items than fit
+ * the LDS membership words of the narrowest query tile (327,680).  ICREC_EINVAL after the build: a basket of more than
+ * 65,535 distinct items, or (longest basket) x (orders of the most frequent item) >= 2^31 - 1, the simple bound under
+ * which every score + 1 fits 31 bits.
+ * Queries are ranked in tiles of 16, or of 8 or 4 when n_items is above 81,920 / 163,840 (the tile's history
+ * membership, one bit per query and item, must fit the 160 KB LDS); ICREC_CF_TILE=16|8|4 in the environment at create
+ * narrows the tile (same results). */
+ICREC_API int icrec_cf_create(const int64_t* order_off, const int32_t* order_items, int64_t n_orders, int64_t n_items,
+                    int64_t n_candidates, int device, icrec_cf** out);
+ICREC_API int icrec_cf_destroy(icrec_cf* cf);
+ICREC_API int64_t icrec_cf_orders(const icrec_cf* cf);      /* 0 for a NULL handle, like the three below */
+ICREC_API int64_t icrec_cf_items(const icrec_cf* cf);
+ICREC_API int64_t icrec_cf_candidates(const icrec_cf* cf);
+ICREC_API int64_t icrec_cf_nnz(const icrec_cf* cf);         /* basket entries after de-duplication */
+ICREC_API int32_t icrec_cf_tile(const icrec_cf* cf);        /* queries per tile: 16, 8 or 4 */
+
+/* Scratch bytes of icrec_cf_rank: n_queries x (n_orders x 2 + next_pow2(n_candidates) x 8) plus the merge lists; 0 for
+ * a bad argument.  Callers stream large query sets in passes. */
+ICREC_API size_t icrec_cf_rank_workspace_bytes(const icrec_cf* cf, int32_t n_queries, int32_t k);
+
+/* The best k candidates of each query by co-occurrence score.
+ *   hist_off_dev   int32[n_queries+1]         CSR offsets into hist_items_dev
+ *   hist_items_dev int32[hist_off[n_queries]] each query's history, ascending and unique within its segment (the
+ *                                             format of icrec_search's exclusion lists); may be NULL when every
+ *                                             history is empty
+ *   out_idx_dev    int64[n_queries, k]        candidate rows, best first; -1 pads when fewer than k remain
+ *   out_score_dev  int32[n_queries, k]        their scores (0 where idx == -1); exact integers, never a float
+ * Candidates that are in the query's history are left out (collaborative_filtering.py:154-155).  A candidate that
+ * occurs in no order scores 0 and is still ranked.  Order: score descending, ties by lower row first: the reference's
+ * stable sorted(..., key=-score) over corpus order.  A history id outside [0, n_items) is skipped without being
+ * dereferenced.  Asynchronous on `stream`, no host synchronisation: hipGraph-capturable like icrec_search.
+ * ICREC_EINVAL: a NULL pointer, n_queries outside [1, 65535], k outside [1, ICREC_MAX_K], more than 8,388,608
+ * candidates (icrec_cf_rank_all has no such limit).  ICREC_ENOMEM: workspace. */
+ICREC_API int icrec_cf_rank(icrec_cf* cf, const int32_t* hist_off_dev, const int32_t* hist_items_dev, int32_t n_queries,
+                  int32_t k, int64_t* out_idx_dev, int32_t* out_score_dev,
+                  void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The complete order of the candidates for each query (what the reference's rank_all returns):
+ *   out_rows_dev int64[n_queries, n_candidates]  best first; the |history ∩ candidates| left-out rows are -1 pads at
+ *                                                the tail
+ * Same order, history format and stream semantics as icrec_cf_rank. */
+ICREC_API size_t icrec_cf_rank_all_workspace_bytes(const icrec_cf* cf, int32_t n_queries);
+ICREC_API int icrec_cf_rank_all(icrec_cf* cf, const int32_t* hist_off_dev, const int32_t* hist_items_dev, int32_t n_queries,
+                      int64_t* out_rows_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* IR metrics: replaces compute_ir_metrics (src/baselines/metrics.py:122-176)  */
+/* over ranked rows that are already on the device (icrec_search's out_idx,    */
+/* icrec_cf_rank's out_idx).  Needs no handle.                                 */
+/* ------------------------------------------------------------------------- */
+
+/* Per query, in this order: accuracy@1, @3, @5, @10, recall@10, reciprocal rank@10, NDCG@10, average precision@100.
+ *   ranked_rows_dev   int64[n_queries, depth]  best first; the first negative row ends a query's list
+ *   depth             in [1, ICREC_MAX_K]
+ *   rel_off_dev       int64[n_queries+1]       CSR offsets of the relevant rows
+ *   rel_rows_dev      int64[rel_off[n_queries]] each query's relevant rows, ascending and unique
+ *   out_sums_dev      double[9]                the eight values summed over the queries that count, then their number;
+ *                                              the caller divides.  A query with no relevant row does not count.
+ *   out_per_query_dev double[n_queries, 8] or NULL  the values of every query (zeros where it does not count)
+ * The definitions are the reference's, two quirks included: NDCG@10 divides by the DCG of the top-10's OWN hits moved
+ * to the front (not an ideal built from |relevant|; 0 without a hit), and AP@100 sums hits_so_far / j over the hits in
+ * the first min(100, valid entries) and divides by min(|relevant|, that many entries).  Everything is double, added in
+ * rank order as the reference's loops do; the ten discounts 1 / log2(i + 2) are computed on the host and passed to the
+ * kernel.  The sum over queries is one fixed tree without atomics: the same bits on every run.
+ * ICREC_EINVAL: a NULL pointer (rel_rows_dev, out_per_query_dev excepted), n_queries < 1, depth out of range.
+ * ICREC_ENOMEM: workspace (icrec_ir_metrics_workspace_bytes).  Asynchronous on `stream`, capturable. */
+ICREC_API size_t icrec_ir_metrics_workspace_bytes(int32_t n_queries);
+ICREC_API int icrec_ir_metrics(const int64_t* ranked_rows_dev, int32_t depth, const int64_t* rel_off_dev,
+                     const int64_t* rel_rows_dev, int32_t n_queries, double* out_sums_dev, double* out_per_query_dev,
+                     void* workspace_dev, size_t workspace_bytes, int device, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Multi-GPU exchange (new design, the reference has none:      */

@@ -38,6 +38,9 @@ EXPORTS = [
     "icrec_exclusions_to_shard_csr_workspace_bytes", "icrec_exclusions_to_shard_csr",
     "icrec_search_workspace_bytes", "icrec_search", "icrec_search_partial", "icrec_merge_topk",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
+    "icrec_cf_create", "icrec_cf_destroy", "icrec_cf_orders", "icrec_cf_items", "icrec_cf_candidates", "icrec_cf_nnz",
+    "icrec_cf_tile", "icrec_cf_rank_workspace_bytes", "icrec_cf_rank", "icrec_cf_rank_all_workspace_bytes",
+    "icrec_cf_rank_all", "icrec_ir_metrics_workspace_bytes", "icrec_ir_metrics",
     "icrec_tokenizer_create", "icrec_tokenizer_create_ex", "icrec_tokenizer_destroy", "icrec_tokenizer_vocab_size", "icrec_tokenize",
     "icrec_last_error", "icrec_version",
     "icrec_timing_enable", "icrec_timing_reset", "icrec_timing_query",
@@ -138,6 +141,19 @@ def lib() -> C.CDLL:
         "icrec_scores": (C.c_int, [vp, vp, i32, vp, vp, sz, vp]),
         "icrec_rank_all_workspace_bytes": (sz, [vp, i32]),
         "icrec_rank_all": (C.c_int, [vp, vp, i32, vp, vp, sz, vp]),
+        "icrec_cf_create": (C.c_int, [vp, vp, i64, i64, i64, C.c_int, C.POINTER(vp)]),
+        "icrec_cf_destroy": (C.c_int, [vp]),
+        "icrec_cf_orders": (i64, [vp]),
+        "icrec_cf_items": (i64, [vp]),
+        "icrec_cf_candidates": (i64, [vp]),
+        "icrec_cf_nnz": (i64, [vp]),
+        "icrec_cf_tile": (i32, [vp]),
+        "icrec_cf_rank_workspace_bytes": (sz, [vp, i32, i32]),
+        "icrec_cf_rank": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+        "icrec_cf_rank_all_workspace_bytes": (sz, [vp, i32]),
+        "icrec_cf_rank_all": (C.c_int, [vp, vp, vp, i32, vp, vp, sz, vp]),
+        "icrec_ir_metrics_workspace_bytes": (sz, [i32]),
+        "icrec_ir_metrics": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, sz, C.c_int, vp]),
         "icrec_normalize_rows": (C.c_int, [vp, vp, i64, i32, C.c_float, C.c_int, vp]),
         "icrec_tokenizer_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]),
         "icrec_tokenizer_create_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,

@@ -7,6 +7,12 @@ output is either a table or one JSON object per result, and nothing is fetched f
 ignored; a missing model directory or corpus file is an error).
 
     python -m instacart_next_order_recommendation_amd --config configs/inference.yaml [--query "..."] [--json]
+
+`baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
+and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
+processed_dir, data_dir, model_name, content_only, cf_only).
+
+    python -m instacart_next_order_recommendation_amd baselines --config configs/baselines.yaml [--cf-only]
 """
 from __future__ import annotations
 
@@ -46,7 +52,59 @@ def pick_query(cfg: dict, override: str | None) -> tuple[str, str]:
     return _FALLBACK_QUERY, "built-in demo context"
 
 
+_BASELINE_DEFAULTS = {"processed_dir": "processed/p5_mp20_ef0.1", "data_dir": "data",
+                      "model_name": "sentence-transformers/all-MiniLM-L6-v2", "content_only": False, "cf_only": False}
+
+
+def print_metrics(name: str, metrics: dict) -> None:
+    """The reference's eight lines per baseline (run_baselines.py:32-42)."""
+    print(f"\n--- {name} ---")
+    for label, key in (("Accuracy@1:  ", "accuracy_at_1"), ("Accuracy@3:  ", "accuracy_at_3"), ("Accuracy@5:  ", "accuracy_at_5"),
+                       ("Accuracy@10: ", "accuracy_at_10"), ("Recall@10:   ", "recall_at_10"), ("MRR@10:      ", "mrr_at_10"),
+                       ("NDCG@10:     ", "ndcg_at_10"), ("MAP@100:     ", "map_at_100")):
+        print(f"  {label} {metrics[key]:.4f}")
+
+
+def baselines_main(argv) -> int:
+    ap = argparse.ArgumentParser(prog="instacart_next_order_recommendation_amd baselines",
+                                 description="Content-based and item-item CF baselines: eight IR metrics each.")
+    ap.add_argument("--config", type=Path, default=None, help="YAML settings (default: configs/baselines.yaml if it exists)")
+    ap.add_argument("--processed-dir", type=Path, default=None, help="overrides processed_dir of the config")
+    ap.add_argument("--data-dir", type=Path, default=None, help="overrides data_dir of the config (orders.csv, order_products__prior.csv)")
+    ap.add_argument("--model-name", type=Path, default=None, help="overrides model_name: a LOCAL SentenceTransformer directory")
+    ap.add_argument("--content-only", action="store_true", help="only the content-based baseline")
+    ap.add_argument("--cf-only", action="store_true", help="only the collaborative-filtering baseline")
+    args = ap.parse_args(argv)
+    path = args.config or (Path("configs/baselines.yaml") if Path("configs/baselines.yaml").exists() else None)
+    raw = (yaml.safe_load(Path(path).read_text()) or {}) if path else {}
+    cfg = {key: (raw[key] if raw.get(key) is not None else default) for key, default in _BASELINE_DEFAULTS.items()}
+    processed_dir = Path(args.processed_dir or str(cfg["processed_dir"]))
+    data_dir = Path(args.data_dir or str(cfg["data_dir"]))
+    model_name = Path(args.model_name or str(cfg["model_name"]))
+    content_only, cf_only = args.content_only or bool(cfg["content_only"]), args.cf_only or bool(cfg["cf_only"])
+    if not (processed_dir / "eval_queries.json").exists():
+        raise SystemExit(f"{processed_dir} holds no eval_queries.json (this build never downloads one)")
+
+    from .baselines import ContentBasedBaseline, ItemItemCFBaseline
+    from .ir_metrics import load_eval_data
+
+    eval_queries, eval_corpus, relevant = load_eval_data(processed_dir)
+    print(f"Processed dir: {processed_dir}\nEval queries: {len(eval_queries)}, corpus size: {len(eval_corpus)}")
+    if not cf_only:
+        if not model_name.is_dir():
+            raise SystemExit(f"model_name {model_name} is not a local model directory (nothing is fetched from a hub)")
+        cb = ContentBasedBaseline(eval_queries, eval_corpus, model_name=model_name)
+        print_metrics("Content-based (untrained SBERT)", cb.evaluate(relevant))
+    if not content_only:
+        cf = ItemItemCFBaseline(data_dir, processed_dir)
+        print_metrics("Collaborative filtering (item-item)", cf.evaluate(relevant))
+    return 0
+
+
 def main(argv=None) -> int:
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv and argv[0] == "baselines":
+        return baselines_main(argv[1:])
     ap = argparse.ArgumentParser(prog="instacart_next_order_recommendation_amd", description=__doc__.splitlines()[0])
     ap.add_argument("--config", type=Path, default=None, help="YAML settings (default: configs/inference.yaml)")
     ap.add_argument("--query", default=None, help="user context to rank for (overrides the config)")

@@ -52,6 +52,17 @@ struct ScopedTimer {
 };
 
 typedef unsigned long long u64;
+
+// search.hip's sorters of packed 64-bit ranking keys (larger key = better hit, key 0 = pad), shared with cf.hip:
+// the k-way merge of n_lists descending lists of k keys per query (keys[list][q_stride][k]; any of the three outputs
+// may be NULL, out_score goes with out_idx), and the complete bitonic sort of keys[n_queries][P] in place followed by
+// out[q][i] = row_offset + row of the i-th best key, -1 where that key is 0 (P = rank_pow2(n_rows)).
+void launch_merge(const u64* keys, int n_lists, int q_stride, int Q, int k, int64_t* out_idx, float* out_score,
+                  u64* out_keys, hipStream_t st);
+int64_t rank_pow2(int64_t n);
+void launch_rank_sort_emit(u64* keys, int64_t n_rows, int64_t P, int n_queries, int64_t row_offset, int64_t* out,
+                           hipStream_t st);
+constexpr int MERGE_MAX_LISTS = 1024;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -74,6 +85,14 @@ __device__ __forceinline__ float key_score(u64 key) {
     return __uint_as_float(u);
 }
 __device__ __forceinline__ uint32_t key_row(u64 key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+// descending bitonic compare-exchange on a[i], a[i ^ j] inside the size-k subsequence containing i
+__device__ __forceinline__ void bitonic_cx(u64& lo_slot, u64& hi_slot, bool desc) {
+    const u64 a = lo_slot, b = hi_slot;
+    const bool swap = desc ? (a < b) : (a > b);
+    lo_slot = swap ? b : a;
+    hi_slot = swap ? a : b;
+}
 
 // bfloat16 -> fp32 is a 16-bit shift: the low / high half of a 32-bit word of bf16 bits, widened exactly
 __device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }

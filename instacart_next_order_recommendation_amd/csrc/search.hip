@@ -887,7 +887,6 @@ __global__ __launch_bounds__(256) void verify_kernel(const void* __restrict__ Pv
 // ---------------------------------------------------------------- k-way merge of sorted lists
 // keys: [n_lists][q_stride][k] sorted descending per (list, query); one wavefront per query
 // runs a tournament: every lane holds the heads of up to MERGE_LPL lists.
-constexpr int MERGE_MAX_LISTS = 1024;
 template <int MERGE_LPL>  // lists per lane: 4 (<= 256 lists) or 16 (<= 1024)
 __global__ __launch_bounds__(256) void merge_kernel(const u64* __restrict__ keys, int n_lists, int q_stride, int Q,
                                                     int k, int64_t* __restrict__ out_idx,
@@ -1214,8 +1213,8 @@ static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, 
 static_assert(CfgBig::THREADS == CfgMid::THREADS && CfgMid::THREADS == CfgSmall::THREADS, "launch_exact: one block size");
 
 // k-way merge of n_lists sorted lists of k keys per query (keys[list][q_stride][k]): 4 lists per lane up to 256 lists
-static void launch_merge(const u64* keys, int n_lists, int q_stride, int Q, int k, int64_t* out_idx, float* out_score,
-                         u64* out_keys, hipStream_t st) {
+void launch_merge(const u64* keys, int n_lists, int q_stride, int Q, int k, int64_t* out_idx, float* out_score,
+                  u64* out_keys, hipStream_t st) {
     hipLaunchKernelGGL((n_lists <= 256 ? merge_kernel<4> : merge_kernel<16>), dim3((Q + 3) / 4), dim3(256), 0, st, keys,
                        n_lists, q_stride, Q, k, out_idx, out_score, out_keys, (const int*)nullptr);
 }
@@ -1276,14 +1275,6 @@ __global__ __launch_bounds__(1024) void rank_keys_kernel(const float* __restrict
         keys[qi * P + i] = i < n_rows ? make_key(scores[qi * n_rows + i], (uint32_t)i) : 0ull;
 }
 
-// descending bitonic compare-exchange on a[i], a[i ^ j] inside the size-k subsequence containing i
-__device__ __forceinline__ void bitonic_cx(u64& lo_slot, u64& hi_slot, bool desc) {
-    const u64 a = lo_slot, b = hi_slot;
-    const bool swap = desc ? (a < b) : (a > b);
-    lo_slot = swap ? b : a;
-    hi_slot = swap ? a : b;
-}
-
 __global__ __launch_bounds__(1024) void rank_sort_kernel(u64* __restrict__ keys, int64_t P) {
     __shared__ u64 seg[RANK_SEG];
     u64* const a = keys + (int64_t)blockIdx.x * P;
@@ -1326,14 +1317,24 @@ __global__ __launch_bounds__(1024) void rank_sort_kernel(u64* __restrict__ keys,
 __global__ __launch_bounds__(256) void rank_emit_kernel(const u64* __restrict__ keys, int64_t n_rows, int64_t P,
                                                         int64_t row_offset, int64_t* __restrict__ out) {
     const int64_t qi = blockIdx.y;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_rows; i += (int64_t)gridDim.x * 256)
-        out[qi * n_rows + i] = row_offset + (int64_t)key_row(keys[qi * P + i]);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_rows; i += (int64_t)gridDim.x * 256) {
+        const u64 key = keys[qi * P + i];  // key 0: a pad that sorted into the first n_rows (cf.hip's left-out rows)
+        out[qi * n_rows + i] = key ? row_offset + (int64_t)key_row(key) : -1;
+    }
 }
 
-static int64_t rank_pow2(int64_t n) {
+int64_t rank_pow2(int64_t n) {
     int64_t p = 1;
     while (p < n) p <<= 1;
     return p;
+}
+
+// keys[n_queries][P] (P = rank_pow2(n_rows), pads = key 0) -> sorted descending in place -> out[n_queries][n_rows]
+void launch_rank_sort_emit(u64* keys, int64_t n_rows, int64_t P, int n_queries, int64_t row_offset, int64_t* out,
+                           hipStream_t st) {
+    const unsigned gx = (unsigned)((P + 1023) / 1024 < 64 ? (P + 1023) / 1024 : 64);
+    hipLaunchKernelGGL(rank_sort_kernel, dim3(n_queries), dim3(1024), 0, st, keys, P);
+    hipLaunchKernelGGL(rank_emit_kernel, dim3(gx * 4, n_queries), dim3(256), 0, st, (const u64*)keys, n_rows, P, row_offset, out);
 }
 
 }  // namespace icrec
@@ -1508,9 +1509,7 @@ int icrec_rank_all(icrec_index* h, const float* q_dev, int32_t n_queries, int64_
     hipStream_t st = (hipStream_t)stream;
     const unsigned gx = (unsigned)((P + 1023) / 1024 < 64 ? (P + 1023) / 1024 : 64);
     hipLaunchKernelGGL(rank_keys_kernel, dim3(gx, n_queries), dim3(1024), 0, st, scores, ix->n_rows, P, keys);
-    hipLaunchKernelGGL(rank_sort_kernel, dim3(n_queries), dim3(1024), 0, st, keys, P);
-    hipLaunchKernelGGL(rank_emit_kernel, dim3(gx * 4, n_queries), dim3(256), 0, st, keys, ix->n_rows, P, ix->row_offset,
-                       out_rows_dev);
+    launch_rank_sort_emit(keys, ix->n_rows, P, n_queries, ix->row_offset, out_rows_dev, st);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
 }
