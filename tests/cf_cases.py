@@ -1,4 +1,5 @@
-"""Shared inputs of the CF tests: the committed upstream fixture and seeded synthetic basket sets."""
+"""Shared inputs of the CF tests: the committed upstream fixture, seeded synthetic basket sets and a vectorised
+statement of the ranking for the cases that are too large for the plain-Python reference."""
 from __future__ import annotations
 
 import json
@@ -46,6 +47,52 @@ def synthetic_histories(n_queries: int, n_items: int, seed: int) -> list[list[in
     for q in range(n_queries):
         n = min((0, 1, 3, 12, 40)[q % 5], n_items)
         out.append(sorted(rng.sample(range(n_items), n)))
+    return out
+
+
+def as_csr(baskets):
+    """(off int64, items int64) of a list of baskets, or of an (off, items) pair that is already CSR."""
+    import numpy as np
+
+    if isinstance(baskets, tuple):
+        return np.asarray(baskets[0], np.int64), np.asarray(baskets[1], np.int64)
+    off = np.zeros(len(baskets) + 1, np.int64)
+    np.cumsum([len(b) for b in baskets], out=off[1:])
+    return off, np.asarray([p for b in baskets for p in b], np.int64)
+
+
+def numpy_rank(baskets, histories, n_candidates: int, k: int | None = None):
+    """cf_reference.cf_rank in int64 matrix form, for a thousand queries or a basket of 65,535 items: B the
+    de-duplicated 0/1 incidence (orders x items), M the history membership (items x Q, ids outside [0, n_items) ignored),
+    W = B @ M, S = B[:, :n_candidates].T @ W, order by (-score, row) without the history's own candidates, padded
+    like cf_rank.  B is held as its non-zero (order, item) pairs and both products are summed over those pairs: the
+    dense B of 32,767 orders x 65,535 items would be 17 GB.  tests/test_cf.py holds this equal to cf_rank."""
+    import numpy as np
+
+    off, items = as_csr(baskets)
+    n_orders, Q = len(off) - 1, len(histories)
+    n_items = max(int(n_candidates), int(items.max()) + 1 if len(items) else 0)  # ids above these occur in no basket
+    M = np.zeros((n_items, Q), np.int64)
+    for q, history in enumerate(histories):
+        h = np.asarray(list(history), np.int64)
+        M[h[(h >= 0) & (h < n_items)], q] = 1
+    pair = np.unique(np.repeat(np.arange(n_orders, dtype=np.int64), np.diff(off)) * n_items + items)  # de-duplicated
+    eo, ei = pair // n_items, pair % n_items
+    W = np.zeros((n_orders, Q), np.int64)
+    np.add.at(W, eo, M[ei])                      # W = B @ M
+    cand = ei < n_candidates
+    S = np.zeros((n_candidates, Q), np.int64)
+    np.add.at(S, ei[cand], W[eo[cand]])          # S = B[:, :n_candidates].T @ W
+    rows = np.arange(n_candidates, dtype=np.int64)
+    out = []
+    for q in range(Q):
+        order = np.lexsort((rows, -S[:, q]))
+        order = order[M[order, q] == 0]
+        r, sc = order.tolist(), S[order, q].tolist()
+        if k is not None:
+            r, sc = r[:k], sc[:k]
+            r, sc = r + [-1] * (k - len(r)), sc + [0] * (k - len(sc))
+        out.append((r, sc))
     return out
 
 
@@ -103,14 +150,20 @@ class DeviceCF:
         self.rank_into(off, items, len(histories), k, rows, scores, ws)
         return rows.cpu().tolist(), scores.cpu().tolist()
 
-    def rank_all(self, histories):
-        n, torch = self.n, self.torch
-        off, items = self.hist(histories)
-        Q = len(histories)
-        need = int(n.lib().icrec_cf_rank_all_workspace_bytes(self.h, Q))
-        assert need > 0
-        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        rows = torch.empty((Q, self.n_candidates), dtype=torch.int64, device=self.device)
+    def rank_all_into(self, off, items, Q, rows, ws):
+        n = self.n
         n.check(n.lib().icrec_cf_rank_all(self.h, n.ptr(off), n.ptr(items), Q, n.ptr(rows), n.ptr(ws), ws.numel(),
                                           n.stream_ptr(self.device)), "icrec_cf_rank_all")
+
+    def rank_all_buffers(self, Q):
+        torch = self.torch
+        need = int(self.n.lib().icrec_cf_rank_all_workspace_bytes(self.h, Q))
+        assert need > 0
+        return (torch.empty((Q, self.n_candidates), dtype=torch.int64, device=self.device),
+                torch.empty(need, dtype=torch.uint8, device=self.device))
+
+    def rank_all(self, histories):
+        off, items = self.hist(histories)
+        rows, ws = self.rank_all_buffers(len(histories))
+        self.rank_all_into(off, items, len(histories), rows, ws)
         return rows.cpu().tolist()

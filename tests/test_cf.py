@@ -37,6 +37,27 @@ def test_reference_reproduces_upstream_rankings(rec):
         assert [rec["corpus_ids"][r] for r in rows] == rec["rankings"][qid], qid
 
 
+def test_numpy_rank_equals_the_reference(rec):
+    """cf_cases.numpy_rank, which the large GPU cases are held against, is the plain-Python reference in matrix form."""
+    from tests.test_cf_gpu import SHAPES
+
+    baskets, histories, n_cand, _, _ = cf_cases.fixture_as_items(rec)
+    cases = [(baskets, histories, n_cand)]
+    for n_cand, extra, n_orders, Q in (SHAPES[2], SHAPES[4]):            # (63, 0, 257, 33) and (1000, 37, 257, 33)
+        n_items = n_cand + extra
+        baskets = cf_cases.synthetic_baskets(n_orders, n_items, seed=n_cand + n_orders)
+        assert any(len(b) != len(set(b)) for b in baskets) and any(not b for b in baskets)
+        histories = cf_cases.synthetic_histories(Q, n_items, seed=Q)
+        histories[3] = [-3] + histories[3] + [n_items + 5]              # ids outside the catalog count for nothing
+        cases.append((baskets, histories, n_cand))
+    for baskets, histories, n_cand in cases:
+        for k in (None, 1, 20, n_cand + 3):
+            assert cf_cases.numpy_rank(baskets, histories, n_cand, k) == cf_reference.cf_rank(baskets, histories, n_cand, k)
+        off, items = cf_cases.as_csr(baskets)
+        assert cf_cases.numpy_rank((off, items.astype(np.int32)), histories, n_cand) == cf_reference.cf_rank(baskets, histories, n_cand)
+    assert cf_cases.numpy_rank([[0, 1], [1, 2]], [[-3, 1, 8]], 3) == cf_reference.cf_rank([[0, 1], [1, 2]], [[1]], 3)
+
+
 def test_reference_reproduces_upstream_metrics(rec):
     import json
 
@@ -105,6 +126,8 @@ def test_create_refuses_bad_baskets_before_touching_a_device(native):
     rc, msg = create([0, 1], [0], 2 ** 32 + 5, 2 ** 32 + 1)
     assert rc == -1
     rc, msg = create([0, 1], [0], 400_000, 10)   # no tile narrow enough for the LDS membership words
+    assert rc == -1 and b"LDS" in msg
+    rc, msg = create([0, 1], [0], 327_681, 10)   # one item past the 4-query tile's 163,840 bytes
     assert rc == -1 and b"LDS" in msg
     assert lib.icrec_cf_create(None, None, 1, 1, 1, 0, None) == -1
 
