@@ -63,6 +63,94 @@ def full_ranking(scores_row):
     return np.lexsort((np.arange(scores_row.size), -scores_row.astype(np.float64)))
 
 
+# ---------------------------------------------------------------- the tiled kernels' launch plan and selection, in numpy
+TILE_VARIANTS = {"big": (128, 128), "mid": (256, 64), "small": (256, 32)}  # (BM rows, BN queries): CfgBig / CfgMid / CfgSmall
+
+
+def tiled_plan(n_rows, Q, k, n_cu):
+    """csrc/search.hip's make_plan with allow_stream false, and its plan_chunks, restated with the same integer
+    arithmetic -> (variant, BM, BN, n_qtiles, tiles_per_chunk, n_chunks).  Block (chunk, query tile) of a tiled kernel
+    walks row tiles chunk * tiles_per_chunk ... of BM rows each; its selection is warm from the second tile on."""
+    variant = "big" if Q > 64 and k <= 32 else "mid" if Q > 32 and k <= 64 else "small"
+    BM, BN = TILE_VARIANTS[variant]
+    n_qtiles = (Q + BN - 1) // BN
+    n_row_tiles = (n_rows + BM - 1) // BM
+    want = min(max(2 * n_cu // n_qtiles, 1), 256)
+    want = min(want, n_row_tiles)
+    tiles_per_chunk = (n_row_tiles + want - 1) // want
+    n_chunks = (n_row_tiles + tiles_per_chunk - 1) // tiles_per_chunk
+    return variant, BM, BN, n_qtiles, tiles_per_chunk, n_chunks
+
+
+def select_from_scores(scores, k, excl=None, row_offset=0):
+    """The library's selection on a complete [Q, n] float32 score matrix: per query the k best rows that its list
+    excl[i] (local rows, as oracle.search takes them) does not name, score descending and row ascending among equal
+    scores -> (idx int64 [Q, k], score float32 [Q, k]), idx = row_offset + row, padded with (-1, 0) where fewer than k
+    rows are admissible - oracle.search's conventions.  Each (score, row) becomes one integer that grows with the
+    score and, among equal scores, falls with the row; -0 counts as +0; scores must not be NaN."""
+    s = np.ascontiguousarray(scores, dtype=np.float32)
+    Q, n = s.shape
+    idx = np.full((Q, k), -1, np.int64)
+    sc = np.zeros((Q, k), np.float32)
+    m = min(k, n)
+    low = np.uint64(0xFFFFFFFF) - np.arange(n, dtype=np.uint64)
+    for lo in range(0, Q, 64):  # blocks of queries: the keys of 64 x n scores at a time
+        blk = s[lo:lo + 64] + np.float32(0.0)
+        u = blk.view(np.uint32)
+        ordered = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+        keys = (ordered.astype(np.uint64) << np.uint64(32)) | low[None, :]
+        if excl is not None:
+            for i in range(blk.shape[0]):
+                e = np.asarray(sorted(set(int(v) for v in excl[lo + i])), np.int64)
+                keys[i, e[(e >= 0) & (e < n)]] = 0  # below every real key
+        top = np.sort(np.partition(keys, n - m, axis=1)[:, n - m:], axis=1)[:, ::-1]
+        real = top != 0
+        rows = (np.uint64(0xFFFFFFFF) - (top & np.uint64(0xFFFFFFFF))).astype(np.int64)
+        rows[~real] = 0
+        idx[lo:lo + 64, :m] = np.where(real, row_offset + rows, -1)
+        sc[lo:lo + 64, :m] = np.where(real, np.take_along_axis(blk, rows, axis=1), np.float32(0.0))
+    return idx, sc
+
+
+def warm_tile_beaters(scores, k, BM, tiles_per_chunk):
+    """For every block of tiles_per_chunk row tiles of BM rows and every tile after the block's first: how many of the
+    tile's rows score above the k-th best of the block's earlier rows - what a warm tile has to offer.  (A later row
+    that only EQUALS that score loses on the row number and is not counted.)  scores: [S, n] float32 with inadmissible
+    rows at -inf -> (counts int [S, n_chunks, tiles_per_chunk - 1], exists bool [n_chunks, tiles_per_chunk - 1])."""
+    S, n = scores.shape
+    n_tiles = (n + BM - 1) // BM
+    n_chunks = (n_tiles + tiles_per_chunk - 1) // tiles_per_chunk
+    padded = np.full((S, n_chunks * tiles_per_chunk * BM), -np.inf, np.float32)
+    padded[:, :n] = scores
+    blocks = padded.reshape(S, n_chunks, tiles_per_chunk, BM)
+    counts = np.zeros((S, n_chunks, tiles_per_chunk - 1), np.int64)
+    for j in range(1, tiles_per_chunk):
+        earlier = blocks[:, :, :j].reshape(S, n_chunks, j * BM)
+        kth = np.partition(earlier, j * BM - k, axis=2)[:, :, j * BM - k]
+        counts[:, :, j - 1] = (blocks[:, :, j] > kth[:, :, None]).sum(axis=2)
+    tile = np.arange(n_chunks)[:, None] * tiles_per_chunk + np.arange(1, tiles_per_chunk)[None, :]
+    return counts, tile < n_tiles
+
+
+def first_pass_offers(tile_scores, k, BM):
+    """What the first pass of TopK::offer offers for one query from a COLD tile of BM rows (csrc/search.hip): the
+    scores of tile row r sit in the lane group (r // 64, r % 8 // 4) - wave r // 64 owns 64 rows, acc_row gives each
+    half of the wavefront alternate runs of 4 - so 2 * BM / 64 lanes hold 32 scores each, and each lane offers its
+    scores down to its m-th largest distinct one, m = ceil(k / lanes) + 1 (every score if it has fewer).  Excluded
+    rows count here; they are dropped afterwards.  tile_scores: [BM] float32 -> bool [BM]."""
+    r = np.arange(BM)
+    group = (r // 64) * 2 + (r % 8) // 4
+    lanes = 2 * BM // 64
+    m = -(-k // lanes) + 1
+    offered = np.zeros(BM, bool)
+    for g in range(lanes):
+        mine = tile_scores[group == g]
+        distinct = np.unique(mine)[::-1]
+        t = distinct[m - 1] if distinct.size >= m else -np.inf
+        offered[group == g] = mine >= t
+    return offered
+
+
 # ---------------------------------------------------------------- random exclusion lists, one per draw sequence
 def distinct_exclusions(rng, n, nq, cap=40, every=1):
     """Per query 0 .. min(n, cap) - 1 distinct rows in draw order; with every > 1 only queries 0, every, 2 every, ...
@@ -129,6 +217,81 @@ def tie_block_catalog(rng, n, dim, n_dup=300, n_near=200, *, draw_f32=False):
 def _frozen(a):
     a.flags.writeable = False
     return a
+
+
+def direction_catalog(order, n, dim, nq, seed):
+    """Rows u + t d + noise along a unit direction d (u a unit vector across it), t from -1 to 1, and nq queries
+    d + 0.02 noise: every query's score t / sqrt(1 + t^2) grows with t.  order "ascending": t grows with the row number,
+    "descending": falls, "random": shuffled.  The row noise is 1 / n per component, about half the score step between
+    neighbouring rows at the flat ends of the curve (0.35 * 2 / n): neighbours swap places, a tile does not overlap
+    the tile before it.  -> (P [n, dim], q [nq, dim]), float32, read-only."""
+    rng = np.random.default_rng(seed)
+    d = rng.standard_normal(dim).astype(np.float32)
+    d /= np.linalg.norm(d)
+    u = rng.standard_normal(dim).astype(np.float32)
+    u -= u.dot(d) * d
+    u /= np.linalg.norm(u)
+    t = np.linspace(-1.0, 1.0, n, dtype=np.float32)
+    if order == "descending":
+        t = t[::-1]
+    elif order == "random":
+        t = rng.permutation(t)
+    else:
+        assert order == "ascending", order
+    P = u[None, :] + t[:, None] * d[None, :] + np.float32(1.0 / n) * rng.standard_normal((n, dim), dtype=np.float32)
+    q = d[None, :] + np.float32(0.02) * rng.standard_normal((nq, dim), dtype=np.float32)
+    return _frozen(P), _frozen(q)
+
+
+def tie_run_catalog(n, dim, nq, BM, tiles_per_chunk, run_len, seed):
+    """Random rows with three runs of run_len copies of ONE row b, placed against the blocks of tiles_per_chunk tiles
+    of BM rows that a tiled kernel walks: run 0 has its first run_len - 7 copies at the end of block 1's first tile
+    and 7 in its second, run 1 starts 7 rows before the middle block boundary and goes on in the next block, run 2
+    lies inside the last, ragged tile.  The queries are b + w + 0.05 noise with w a unit vector across b, and 47 near
+    rows b + g w sit in block 1: for 0 < g < 1 such a row scores above b for every query, for g < 0 below it (fp32
+    rows; bfloat16 rounding blurs the smallest steps).  16 near rows, 8 above b and 8 below, lie in the block's third
+    tile.  31 lie in its first tile at the rows r < 64 with r % 8 < 4 - the 32 scores that ONE lane holds per query
+    (first_pass_offers) - n_above of them above b, n_above = 20 for runs longer than 128 and 10 otherwise: more than
+    the m scores a lane offers in the first pass of a cold tile at every k the tiled kernels take up to run_len - 7.
+    The 32nd of those rows, r = 17, is one more copy of b, the stray: its lane does not offer it in the first pass,
+    while the run_len - 7 >= k copies of run 0 in the same tile, top scores of their own lanes, are all offered.  The
+    k-th key after the first pass is then a copy of b with a HIGHER row number than the stray, which enters in the
+    second pass on a score EQUAL to the threshold's and belongs in front of every other copy.  Near rows, stray and
+    runs are every query's best matches, and among the equal scores only the row number decides.
+    -> (P, q, [(first row, end row) of each run], near rows, the stray's row), read-only."""
+    rng = np.random.default_rng(seed)
+    n_tiles = (n + BM - 1) // BM
+    n_chunks = (n_tiles + tiles_per_chunk - 1) // tiles_per_chunk
+    block = tiles_per_chunk * BM
+    assert 7 < run_len <= BM - 57 and BM >= 128 and n_chunks >= 5 and tiles_per_chunk >= 3
+    starts = [block + BM - (run_len - 7), (n_chunks // 2) * block - 7, (n_tiles - 1) * BM + 11]
+    runs = [(s, s + run_len) for s in starts]
+    assert runs[0][0] >= block + 64 and runs[2][1] <= n
+    P = rng.standard_normal((n, dim), dtype=np.float32)
+    base = rng.standard_normal(dim, dtype=np.float32)
+    w = rng.standard_normal(dim).astype(np.float32)
+    w -= w.dot(base) / base.dot(base) * base
+    w /= np.linalg.norm(w)
+    for lo, hi in runs:
+        P[lo:hi] = base
+    n_above = 20 if run_len > 128 else 10
+    lane = rng.permutation([r for r in range(64) if r % 8 < 4 and r != 17])        # 31 rows of one lane
+    third = rng.permutation(2 * BM + 5 + 7 * np.arange(16))                           # 16 rows of the third tile
+    # g > 0, best first, dealt in turn to the third tile (8) and the lane (n_above); g < 0 likewise (8 and the rest)
+    up = 0.8 * np.arange(n_above + 8, 0, -1) / (n_above + 8)
+    down = -0.8 * np.arange(1, 31 - n_above + 8 + 1) / (31 - n_above + 8)
+    rows_up = [third[i // 2] if i % 2 == 0 and i < 16 else None for i in range(n_above + 8)]
+    rest = iter(lane[:n_above])
+    rows_up = [r if r is not None else next(rest) for r in rows_up]
+    rows_down = [third[8 + i // 2] if i % 2 == 0 and i < 16 else None for i in range(31 - n_above + 8)]
+    rest = iter(lane[n_above:])
+    rows_down = [r if r is not None else next(rest) for r in rows_down]
+    near = block + np.asarray(rows_up + rows_down)
+    P[near] = base[None, :] + np.concatenate([up, down]).astype(np.float32)[:, None] * w[None, :]
+    stray = block + 17
+    P[stray] = base
+    q = (base + w)[None, :] + np.float32(0.05) * rng.standard_normal((nq, dim), dtype=np.float32)
+    return _frozen(P), _frozen(q), runs, near, stray
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,0 +1,136 @@
+"""The numpy helpers of the multi-tile search tests (tests/search_harness.py), without a GPU: tiled_plan against
+hand-computed plans, select_from_scores against the oracle's ranking loop, and the tile bookkeeping of
+warm_tile_beaters and tie_run_catalog on shapes small enough to check by eye."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from oracle import oracle
+from tests.search_harness import (direction_catalog, first_pass_offers, select_from_scores, tie_run_catalog, tiled_plan,
+                                  warm_tile_beaters)
+
+
+@pytest.mark.parametrize("shape,want", [
+    # 193 tiles of 128 rows, 8 query tiles: 2 * 256 / 8 = 64 chunks wanted -> ceil(193 / 64) = 4 tiles per chunk, and
+    # 4 tiles per chunk cover 193 tiles in ceil(193 / 4) = 49 chunks, the last of one tile
+    ((24_613, 1024, 32), ("big", 128, 128, 8, 4, 49)),
+    # 389 tiles, 64 wanted -> 7 per chunk -> 56 chunks (bench.py's shape)
+    ((49_688, 1024, 20), ("big", 128, 128, 8, 7, 56)),
+    # k = 33 leaves the big tile: 98 tiles of 256 rows, 16 query tiles, 32 chunks wanted -> 4 per chunk -> 25 chunks
+    ((25_000, 1024, 33), ("mid", 256, 64, 16, 4, 25)),
+    ((25_000, 1024, 64), ("mid", 256, 64, 16, 4, 25)),
+    # 64 queries are not "more than 64": mid at k = 20; one query tile: 512 wanted, capped at 256; 770 tiles -> 4, 193
+    ((197_093, 64, 20), ("mid", 256, 64, 1, 4, 193)),
+    ((197_000, 32, 32), ("small", 256, 32, 1, 4, 193)),
+    # k > 64: small whatever the batch; 16 query tiles of 32 -> 32 wanted, 98 tiles
+    ((25_000, 512, 65), ("small", 256, 32, 16, 4, 25)),
+    ((25_000, 512, 128), ("small", 256, 32, 16, 4, 25)),
+    # more chunks wanted (2 query tiles -> 256) than there are tiles (40): one tile per chunk
+    ((5_000, 130, 20), ("big", 128, 128, 2, 1, 40)),
+    # 2,000 queries in 16 big tiles -> 32 wanted; exactly 96 tiles -> 3 per chunk, 32 chunks; one row more -> 4, 25
+    ((96 * 128, 2000, 1), ("big", 128, 128, 16, 3, 32)),
+    ((96 * 128 + 1, 2000, 1), ("big", 128, 128, 16, 4, 25)),
+    # 40,000 queries: 313 query tiles, 2 * 256 / 313 = 1 chunk of all 8 tiles
+    ((1_000, 40_000, 20), ("big", 128, 128, 313, 8, 1)),
+])
+def test_tiled_plan_pins(shape, want):
+    """(n_rows, Q, k) at 256 CUs -> (variant, BM, BN, n_qtiles, tiles_per_chunk, n_chunks), worked out by hand."""
+    assert tiled_plan(*shape, 256) == want
+
+
+def test_tiled_plan_follows_the_cu_count():
+    # 304 CUs, 8 query tiles: 76 chunks wanted; 193 tiles -> 3 per chunk -> 65 chunks
+    assert tiled_plan(24_613, 1024, 32, 304) == ("big", 128, 128, 8, 3, 65)
+    # 3 CUs, 8 query tiles: 6 / 8 = 0 -> one chunk
+    assert tiled_plan(24_613, 1024, 32, 3) == ("big", 128, 128, 8, 193, 1)
+
+
+def test_select_from_scores_is_the_oracles_ranking():
+    """Duplicate rows (equal scores), a zero query (every score +-0), exclusions that hit the top and rows outside the
+    catalog, a row offset, and a k beyond the admissible rows: indices and scores equal to oracle.search."""
+    rng = np.random.default_rng(3)
+    n, nq, dim = 300, 70, 32
+    P = rng.standard_normal((n, dim), dtype=np.float32)
+    P[[5, 17, 40, 41, 42, 299]] = P[3]
+    P[100:110] = -P[3]
+    q = rng.standard_normal((nq, dim), dtype=np.float32)
+    q[:8] = P[3] + 0.01 * q[:8]
+    q[8] = 0.0
+    scores = oracle.scores(oracle.normalize_rows(q), oracle.normalize_rows(P))
+    for k in (1, 20, 128):
+        top, _ = oracle.search(q, P, 6)
+        excl = [sorted(set(top[i, ::2].tolist()) | set(rng.choice(n, 9, replace=False).tolist())) if i % 3 else []
+                for i in range(nq)]
+        excl[1] = sorted(set(excl[1]) | {n, n + 5})                # outside the catalog: ignored
+        excl[2] = list(range(0, n, 2)) + list(range(1, 181, 2))    # 60 rows left, fewer than k = 128
+        excl[4] = list(range(n))                                   # nothing left
+        want = oracle.search(q, P, k, excl, row_offset=1000)
+        got = select_from_scores(scores, k, excl, row_offset=1000)
+        np.testing.assert_array_equal(got[0], want[0])
+        np.testing.assert_array_equal(got[1], want[1])
+        assert got[0].dtype == np.int64 and got[1].dtype == np.float32
+        assert (got[0][4] == -1).all() and (got[1][4] == 0).all()
+        if k == 128:
+            assert (got[0][2, 60:] == -1).all() and (got[0][2, :60] >= 1000).all()
+    # k beyond the catalog, no exclusions, -0 scores rank as +0 (row order)
+    want = oracle.search(q, P[:7], 10)
+    got = select_from_scores(scores[:, :7], 10)
+    np.testing.assert_array_equal(got[0], want[0])
+    np.testing.assert_array_equal(got[1], want[1])
+    z = np.array([[0.0, -0.0, 0.0, -1.0, -0.0]], np.float32)
+    assert select_from_scores(z, 4)[0].tolist() == [[0, 1, 2, 4]]
+
+
+def test_first_pass_offers_by_hand():
+    """128 rows, 4 lanes of 32 scores: lane (wave 0, half 0) holds rows 0-3, 8-11, ... of the first 64.  k = 4: m = 2."""
+    s = np.zeros(128, np.float32)
+    s[[0, 1, 2, 8]] = [5, 4, 4, 3]          # lane 0: distinct 5, 4, 3, 0 -> offers down to 4
+    s[[4, 5]] = [7, 7]                      # lane 1: distinct 7, 0 -> offers everything (32 scores)
+    s[64:128] = np.arange(64)               # lanes 2 and 3: all distinct -> the best two each
+    got = first_pass_offers(s, 4, 128)
+    assert np.flatnonzero(got[:64]).tolist() == [0, 1, 2] + [r for r in range(64) if r % 8 >= 4]
+    assert np.flatnonzero(got[64:]).tolist() == [58, 59, 62, 63]   # rows 122, 123 (half 0) and 126, 127 (half 1)
+
+
+def test_warm_tile_beaters_counts_by_hand():
+    """Blocks of 3 tiles of 4 rows over 22 rows: 6 tiles, 2 blocks, the last tile of 2 rows."""
+    s = np.array([[9, 8, 7, 6,   8, 9, 10, 1,   10, 11, 0, 0,
+                   1, 2, 3, 4,   5, -np.inf, 2, 3,   6, 1]], np.float32)
+    counts, exists = warm_tile_beaters(s, 2, 4, 3)
+    assert exists.tolist() == [[True, True], [True, True]]
+    # block 0: 2nd best of tile 0 is 8 -> 9, 10 beat it (the second 8 only equals it); then 2nd best of 8 rows is 9
+    # (10, 9, 9): 10 and 11 beat it.  block 1: 2nd best 3 -> 5; then 2nd best of (1 2 3 4 5 2 3) is 4 -> 6
+    assert counts.tolist() == [[[2, 2], [1, 1]]]
+    counts, exists = warm_tile_beaters(s[:, :20], 2, 4, 3)       # 5 tiles: the last block's third tile does not exist
+    assert exists.tolist() == [[True, True], [True, False]] and counts[0, 1].tolist() == [1, 0]
+
+
+def test_catalog_builders_place_what_they_promise():
+    P, q, runs, near, stray = tie_run_catalog(n=20 * 128 - 27, dim=32, nq=6, BM=128, tiles_per_chunk=4, run_len=41, seed=1)
+    block = 4 * 128   # 20 tiles in 5 blocks; run 0 ends 7 rows into block 1's second tile, run 1 starts 7 before block 2
+    assert runs == [(block + 94, block + 135), (2 * block - 7, 2 * block + 34), (19 * 128 + 11, 19 * 128 + 52)]
+    for lo, hi in runs:
+        assert (P[lo:hi] == P[stray]).all()
+    dup = (P == P[stray]).all(axis=1)
+    assert stray == block + 17 and dup.sum() == 3 * 41 + 1 and not dup[near].any() and len(set(near.tolist())) == 47
+    lane, third = near[near < block + 64], near[near >= block + 64]
+    assert lane.size == 31 and ((lane - block) % 8 < 4).all() and third.size == 16 and (third // 128 == 4 + 2).all()
+    top = oracle.search(q, P, 60)[0]
+    for t in top:   # 18 near rows above the duplicated row (10 of them in the lane), then the stray copy, then run 0
+        assert set(t[:18].tolist()) <= set(near.tolist()) and np.isin(t[:18], lane).sum() == 10
+        assert t[18] == stray and t[19:].tolist() == list(range(runs[0][0], runs[0][1]))
+    # the cold tile of block 1 at k = 32 (4 lanes, m = 9): the stray's lane holds 10 better scores and withholds it; the
+    # 34 copies of run 0 in the tile are offered, so the 32nd best offer is a copy with the stray's score
+    sc = oracle.scores(oracle.normalize_rows(q), oracle.normalize_rows(P))[0, block:block + 128]
+    offered = first_pass_offers(sc, 32, 128)
+    assert not offered[17] and offered[94:].all() and offered[near[near < block + 64] - block].sum() == 9
+    assert np.sort(sc[offered])[::-1][31] == sc[17]
+    # ascending: the ranking of every query is the row order reversed, up to swaps of near neighbours
+    P, q = direction_catalog("ascending", 2000, 64, 3, seed=2)
+    top = oracle.search(q, P, 50)[0]
+    assert (top >= 2000 - 60).all()
+    Pd, _ = direction_catalog("descending", 2000, 64, 3, seed=2)
+    assert (oracle.search(q, Pd, 50)[0] < 60).all()
+    with pytest.raises(ValueError):
+        P[0, 0] = 1.0                                             # shared between tests: read-only
