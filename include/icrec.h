@@ -359,6 +359,43 @@ ICREC_API int icrec_search(icrec_index* idx, const float* q_dev, int32_t n_queri
                  int64_t* out_idx_dev, float* out_score_dev,
                  void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Facets: restrict each query to rows whose attributes it allows ("only from these departments").
+ * An index may carry n_facets in [1, ICREC_MAX_FACETS] attribute bytes per row (values 0..255); a query carries, per
+ * facet, a 256-bit allow mask of ICREC_FACET_MASK_WORDS uint32 words: bit (v & 31) of word (v >> 5) admits value v.
+ * A row is admissible for a query iff, for every facet, the bit of the row's value is set - and the row is not in the
+ * query's exclusion list; the two compose.  An all-ones mask leaves a facet unconstrained, an all-zero mask admits
+ * nothing (the result is all -1 / 0.0 pads, as when exclusions exhaust the catalog).
+ * The result of icrec_search_faceted is bit-identical, indices and scores, to icrec_search with exclusion lists equal
+ * to the given exclusions united with every inadmissible row, for every row storage and every batch size. */
+#define ICREC_MAX_FACETS 2
+#define ICREC_FACET_MASK_WORDS 8
+
+/* Set, replace or (facets_host == NULL) remove the index's facets.
+ *   facets_host  uint8[n_rows, n_facets]  HOST pointer, row-major; copied to the device before the call returns
+ * n_facets outside [1, ICREC_MAX_FACETS] (with a non-NULL facets_host) is ICREC_EINVAL and changes nothing.
+ * A set-up call like icrec_encoder_set_attention_bias: it allocates, may synchronise the device, and must never be
+ * issued while a call on the index is running.  The rows and their filter planes / fragments are not touched, and
+ * icrec_search, icrec_search_partial, icrec_rank_all and icrec_scores ignore the facets. */
+ICREC_API int icrec_index_set_facets(icrec_index* idx, const uint8_t* facets_host, int32_t n_facets);
+/* Facets per row of the index: 0 when none are set, -1 for a NULL handle. */
+ICREC_API int32_t icrec_index_facets(const icrec_index* idx);
+
+/* Scratch bytes of icrec_search_faceted (0 for a bad argument); equal to icrec_search_workspace_bytes. */
+ICREC_API size_t icrec_search_faceted_workspace_bytes(const icrec_index* idx, int32_t n_queries, int32_t k);
+
+/* icrec_search restricted by facets.
+ *   allow_dev    uint32[n_queries, n_facets, ICREC_FACET_MASK_WORDS]  the queries' allow masks in DEVICE memory,
+ *                n_facets = icrec_index_facets(idx); or NULL
+ * allow_dev == NULL: this IS icrec_search - the same launches, the same bits.  allow_dev != NULL on an index without
+ * facets: ICREC_EINVAL.  Otherwise the argument checks, the stream semantics and the graph-capturability are
+ * icrec_search's: nothing is allocated, nothing synchronises.  The masks are read from device memory when the kernels
+ * run: a captured graph replayed after the caller rewrote the mask buffer follows the new masks. */
+ICREC_API int icrec_search_faceted(icrec_index* idx, const float* q_dev, int32_t n_queries, int32_t k,
+                         const int32_t* excl_idx_dev, const int32_t* excl_off_dev,
+                         const uint32_t* allow_dev,
+                         int64_t* out_idx_dev, float* out_score_dev,
+                         void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Shard-local half of a sharded search: same as icrec_search but emits the
  * sorted partial lists as packed 64-bit keys
  *   key = (orderable(score) << 32) | (0xFFFFFFFF - global_row)

@@ -14,6 +14,8 @@ _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libicrec.so"
 
 ICREC_MAX_K = 128
+ICREC_MAX_FACETS = 2
+ICREC_FACET_MASK_WORDS = 8
 ICREC_MAX_SEQLEN = 512
 COMM_ID_BYTES = 128
 GEMM_F32, GEMM_F16X3 = 0, 1
@@ -37,6 +39,7 @@ EXPORTS = [
     "icrec_search_sharded_excl_workspace_bytes", "icrec_search_sharded_excl", "icrec_index_row_offset",
     "icrec_exclusions_to_shard_csr_workspace_bytes", "icrec_exclusions_to_shard_csr",
     "icrec_search_workspace_bytes", "icrec_search", "icrec_search_partial", "icrec_merge_topk",
+    "icrec_index_set_facets", "icrec_index_facets", "icrec_search_faceted_workspace_bytes", "icrec_search_faceted",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
     "icrec_cf_create", "icrec_cf_destroy", "icrec_cf_orders", "icrec_cf_items", "icrec_cf_candidates", "icrec_cf_nnz",
     "icrec_cf_tile", "icrec_cf_rank_workspace_bytes", "icrec_cf_rank", "icrec_cf_rank_all_workspace_bytes",
@@ -137,6 +140,10 @@ def lib() -> C.CDLL:
         "icrec_search_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_search": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
         "icrec_search_partial": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+        "icrec_index_set_facets": (C.c_int, [vp, vp, i32]),
+        "icrec_index_facets": (i32, [vp]),
+        "icrec_search_faceted_workspace_bytes": (sz, [vp, i32, i32]),
+        "icrec_search_faceted": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
         "icrec_merge_topk": (C.c_int, [vp, i32, i32, i32, vp, vp, C.c_int, vp]),
         "icrec_scores": (C.c_int, [vp, vp, i32, vp, vp, sz, vp]),
         "icrec_rank_all_workspace_bytes": (sz, [vp, i32]),

@@ -7,6 +7,7 @@ output is either a table or one JSON object per result, and nothing is fetched f
 ignored; a missing model directory or corpus file is an error).
 
     python -m instacart_next_order_recommendation_amd --config configs/inference.yaml [--query "..."] [--json]
+                                                      [--aisle NAME]... [--department NAME]...
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
 and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
@@ -110,6 +111,10 @@ def main(argv=None) -> int:
     ap.add_argument("--query", default=None, help="user context to rank for (overrides the config)")
     ap.add_argument("--top-k", type=int, default=None, help="overrides top_k of the config")
     ap.add_argument("--json", action="store_true", help="one JSON object per result instead of the table")
+    ap.add_argument("--aisle", action="append", default=None, metavar="NAME",
+                    help="only products of this aisle (repeatable: any of the named aisles)")
+    ap.add_argument("--department", action="append", default=None, metavar="NAME",
+                    help="only products of this department (repeatable: any of the named departments)")
     args = ap.parse_args(argv)
     cfg = read_settings(args.config)
     if not cfg["corpus"].exists():
@@ -120,7 +125,10 @@ def main(argv=None) -> int:
     from .recommender import Recommender
 
     rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"])
-    hits = rec.recommend(query=query, top_k=top_k)
+    try:
+        hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department)
+    except ValueError as e:  # an aisle / department the catalog does not have
+        raise SystemExit(str(e))
     if args.json:
         for rank, (pid, score) in enumerate(hits, 1):
             print(json.dumps({"rank": rank, "product_id": pid, "score": score, "product_text": rec.pid_to_text[pid]}))

@@ -6,6 +6,8 @@
 //   scores.argsort(descending=True)                                      :215/:251
 //   the exclusion / top-k Python loop                                    :216-225/:254-262
 // of /root/reference/src/inference/serve_recommendations.py.
+#include <vector>
+
 #include "common.h"
 #include "gemm_x3.h"
 #include "wt_gemm.h"
@@ -73,6 +75,43 @@ __device__ __forceinline__ bool excluded(const int32_t* __restrict__ ex, int lo,
         if (v < row) lo = mid + 1; else hi = mid;
     }
     return false;
+}
+
+// ---- facets (icrec_search_faceted): one or two attribute bytes per row against a 256-bit allow mask per query and
+// facet.  A row is a candidate only if every facet's mask has the bit of the row's value; like an excluded row it is
+// then never offered, so the lists, the merges and the verification see admitted rows only.
+// The index keeps a row's bytes in ONE 16-bit word (facet 0 in the low byte; 0 for a facet it does not have), zero
+// padded to whole 256-row tiles: every tile of every kernel reads inside the array.  A block keeps its queries' masks
+// in LDS as [query][ICREC_MAX_FACETS][8] words: all ones for a facet the index does not have, zero for a padding
+// query.  The FACET arm of a kernel is the instantiation whose parameter pack `Facet` holds one FacetArgs; with an
+// empty pack the kernel's parameters and code are what they were before facets existed.
+struct FacetArgs {
+    const uint16_t* rows;   // [n_rows rounded up to 256] facet words
+    const uint32_t* allow;  // [Q][n_facets][ICREC_FACET_MASK_WORDS], read when the kernel runs
+    int n_facets;
+};
+constexpr int FACET_LDS_WORDS = ICREC_MAX_FACETS * ICREC_FACET_MASK_WORDS;  // per query
+static_assert(ICREC_MAX_FACETS == 2 && ICREC_FACET_MASK_WORDS == 8, "a row's facets are the two bytes of a 16-bit word");
+
+__device__ __forceinline__ FacetArgs facet_args() { return FacetArgs{nullptr, nullptr, 0}; }
+__device__ __forceinline__ FacetArgs facet_args(const FacetArgs& fa) { return fa; }
+
+// The masks of queries q0 .. q0 + nq - 1 -> LDS at am; the caller's next barrier publishes them.
+__device__ __forceinline__ void facet_load_masks(uint32_t* am, const FacetArgs& fa, int q0, int nq, int Q, int tid,
+                                                 int n_threads) {
+    for (int i = tid; i < nq * FACET_LDS_WORDS; i += n_threads) {
+        const int q = i / FACET_LDS_WORDS, f = i / ICREC_FACET_MASK_WORDS % ICREC_MAX_FACETS, w = i % ICREC_FACET_MASK_WORDS;
+        am[i] = q0 + q >= Q      ? 0u
+                : f < fa.n_facets ? fa.allow[((size_t)(q0 + q) * fa.n_facets + f) * ICREC_FACET_MASK_WORDS + w]
+                                  : ~0u;
+    }
+}
+
+// Does the mask of the block's query q (in LDS at am) admit a row whose facet word is fw?
+__device__ __forceinline__ bool facet_admits(const uint32_t* am, int q, unsigned fw) {
+    const unsigned v0 = fw & 255u, v1 = (fw >> 8) & 255u;
+    const uint32_t* m = am + q * FACET_LDS_WORDS;
+    return ((m[v0 >> 5] >> (v0 & 31)) & (m[ICREC_FACET_MASK_WORDS + (v1 >> 5)] >> (v1 & 31)) & 1u) != 0u;
 }
 
 // Merge the queue of query q into its sorted list; one wavefront, all 64 lanes call this.
@@ -149,8 +188,9 @@ __device__ __forceinline__ void merge_queue2(u64* list, const u64* queue, int qc
 // A block scores tiles of catalog rows against its BN queries; offer() takes one tile's scores in the accumulator map
 // of the 32x32 MFMA (acc[TM][TN]: this wave's row tiles wm, query tiles wn) and keeps, per query, the k best
 // (score, row) keys seen in a sorted LDS list; write() stores the lists.  The LDS carve follows the kernel's operand
-// staging (all offsets multiples of 16 B): thresholds [BN] | queue counters [BN] | flags [4] | lists [BN][k] |
-// candidate queues [BN][qcap].
+// staging (all offsets multiples of 16 B): thresholds [BN] | queue counters [BN] | flags [4] | FACET: allow masks
+// [BN][FACET_LDS_WORDS], facet words of the current and the next tile [2][BM] | lists [BN][k] | candidate queues
+// [BN][qcap].
 //
 // Candidate queue entries per query (qcap): 64 for 32-query tiles, 16 for wider ones.  The resident filter pass takes
 // 32 when the lists are short (k <= 32) and a block walks few rounds: the first rounds of a block offer 16-48
@@ -159,15 +199,15 @@ __device__ __forceinline__ void merge_queue2(u64* list, const u64* queue, int qc
 // keep 16 (10 M rows: 1 % faster with it).
 constexpr int RES_QCAP_MAX_ROUNDS = 64;
 
-template <class Cfg, bool RESIDENT = false>
+template <class Cfg, bool RESIDENT = false, bool FACET = false>
 struct TopK {
     static __host__ __device__ constexpr int qcap(int k, int rounds) {
         return RESIDENT && k <= 32 && rounds <= RES_QCAP_MAX_ROUNDS ? 32 : Cfg::BN <= 32 ? 64 : 16;
     }
     // LDS of the selection, sized for a block of one round (the largest queue)
     static __host__ __device__ size_t bytes(int k) {
-        return (size_t)Cfg::BN * (8 /*thr*/ + 4 /*cnt*/) + 16 /*flags*/ + (size_t)Cfg::BN * k * 8 +
-               (size_t)Cfg::BN * qcap(k, 1) * 8;
+        return (size_t)Cfg::BN * (8 /*thr*/ + 4 /*cnt*/) + 16 /*flags*/ + (FACET ? Cfg::BN * FACET_LDS_WORDS * 4 + 2 * Cfg::BM * 2 : 0) +
+               (size_t)Cfg::BN * k * 8 + (size_t)Cfg::BN * qcap(k, 1) * 8;
     }
 
     u64* thr;    // per query: the k-th key of its list, the offer threshold (~0: padding query)
@@ -175,6 +215,10 @@ struct TopK {
     int* flags;  // [0],[1]: alternating "some candidate did not fit" flags; [2]: some lane's query is cold
     u64* list;   // [BN][k], sorted best first, 0 = empty slot
     u64* queue;  // [BN][qcap]
+    uint32_t* amask;        // FACET: the queries' allow masks
+    uint16_t* ftile;        // FACET: [2][BM] facet words of the tile being offered (half fcur) and of the one after it
+    const uint16_t* frows;  // FACET: the index's facet words
+    int fcur = 0;
     int k, qcap_, round = 0;
     // this lane's queries: column (lane & 31) of each of its TN column tiles
     int myq[Cfg::TN];
@@ -182,18 +226,22 @@ struct TopK {
     int ex_lo[Cfg::TN], ex_hi[Cfg::TN];
 
     // Carves the LDS at `lds`, empties the lists (one barrier) and reads this lane's exclusion segments.  `rounds`: the
-    // tiles this block walks (the resident pass's queue capacity depends on it).
-    __device__ __forceinline__ TopK(char* lds, int k_, int Q, int q0, const int32_t* excl_off, int rounds = 1)
-        : k(k_), qcap_(qcap(k_, rounds)) {
+    // tiles this block walks (the resident pass's queue capacity depends on it).  FACET: also loads the masks.
+    __device__ __forceinline__ TopK(char* lds, int k_, int Q, int q0, const int32_t* excl_off, int rounds = 1,
+                                    const FacetArgs& fa = facet_args())
+        : frows(fa.rows), k(k_), qcap_(qcap(k_, rounds)) {
         const int tid = threadIdx.x, lane = tid & 63, wn = (tid >> 6) % Cfg::WAVES_N;
         thr = reinterpret_cast<u64*>(lds);
         cnt = reinterpret_cast<int*>(thr + Cfg::BN);
         flags = cnt + Cfg::BN;
-        list = reinterpret_cast<u64*>(flags + 4);
+        amask = reinterpret_cast<uint32_t*>(flags + 4);
+        ftile = reinterpret_cast<uint16_t*>(amask + (FACET ? Cfg::BN * FACET_LDS_WORDS : 0));
+        list = reinterpret_cast<u64*>(ftile + (FACET ? 2 * Cfg::BM : 0));
         queue = list + (size_t)Cfg::BN * k;
         for (int i = tid; i < Cfg::BN; i += Cfg::THREADS) { thr[i] = (q0 + i < Q) ? 0ull : ~0ull; cnt[i] = 0; }
         for (int i = tid; i < Cfg::BN * k; i += Cfg::THREADS) list[i] = 0ull;
         if (tid < 4) flags[tid] = 0;
+        if (FACET) facet_load_masks(amask, fa, q0, Cfg::BN, Q, tid, Cfg::THREADS);
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < Cfg::TN; ++j) {
@@ -214,6 +262,13 @@ struct TopK {
     //    scores, each lane first offers only its own m largest (m = ceil(k / lanes per query) + 1,
     //    so the lanes together offer >= k), the queues are merged at once, and a second pass
     //    offers whatever else still beats the now-real threshold (usually nothing).
+    // FACET: a warm lane tests a candidate's row against its query's mask where it tests the exclusions.  A lane with
+    // a cold query first works out which of its (row, query) pairs the masks admit (admitted()) and counts only those
+    // towards its m largest and its offers: under a mask that admits a handful of rows per tile a block stays cold
+    // for its whole chunk, and would otherwise push every score of every tile through the per-candidate test.
+    // Both read the tile's facet words from LDS: offer() of one tile fetches the next tile's words (the block walks
+    // consecutive tiles) and stores them before its first barrier, so no candidate waits for a global load; the
+    // kernel puts the first tile's there with stage_first_tile().
     __device__ __forceinline__ void offer(const f32x16 (&acc)[Cfg::TM][Cfg::TN], int64_t row0, int64_t N, uint32_t row_base,
                                           const int32_t* excl_idx, bool last_tile) {
         const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -223,7 +278,20 @@ struct TopK {
         const int m_local = (k + LPQ - 1) / LPQ + 1;
         unsigned long long offered = 0ull;
         bool lane_cold = false;
+        unsigned long long adm = ~0ull;  // FACET: pend-numbered bits of the admitted (row, query) pairs, once known
+        bool adm_known = false;
+        const uint16_t* const fw_tile = ftile + fcur * Cfg::BM;
+        unsigned next_words = 0u;  // two rows of the next tile per thread (inside the padded array: the tile exists)
+        bool next_staged = !FACET || last_tile;
+        if (FACET && !last_tile && tid < Cfg::BM / 2)
+            next_words = *reinterpret_cast<const unsigned*>(frows + row0 + Cfg::BM + 2 * tid);
         for (int pass = 0; pass < 2; ++pass) {
+            if (FACET && pass == 0) {
+                bool cold = false;
+#pragma unroll
+                for (int j = 0; j < Cfg::TN; ++j) cold |= mythr[j] == 0ull;
+                if (cold) { adm = admitted(fw_tile, wm, lane); adm_known = true; }
+            }
             // pend bit (j*TM+i)*16+e: score e of accumulator tile (i,j) has to be offered
             unsigned long long pend = 0ull;
 #pragma unroll
@@ -240,7 +308,8 @@ struct TopK {
                         for (int i = 0; i < Cfg::TM; ++i)
 #pragma unroll
                             for (int e = 0; e < 16; ++e) {
-                                const bool valid = row0 + (wm * Cfg::TM + i) * 32 + acc_row(e, lane) < N;
+                                const bool valid = row0 + (wm * Cfg::TM + i) * 32 + acc_row(e, lane) < N &&
+                                                   (!FACET || (adm >> ((j * Cfg::TM + i) * 16 + e) & 1ull) != 0ull);
                                 const float v = acc[i][j][e] + 0.0f;
                                 best = (valid && v < t && v > best) ? v : best;
                             }
@@ -257,6 +326,7 @@ struct TopK {
                         if (acc[i][j][e] + 0.0f >= thr_s) pend |= 1ull << ((j * Cfg::TM + i) * 16 + e);
             }
             pend &= ~offered;
+            if (FACET) pend &= adm;
             offered |= pend;
             if (pass == 0 && lane_cold) flags[2] = 1;
             bool more, wg_cold;
@@ -282,6 +352,7 @@ struct TopK {
                                 key = make_key(sc, row_base + (uint32_t)row);
                                 take = key > mythr[j];
                             }
+                            if (FACET && take && !adm_known) take = facet_admits(amask, myq[j], fw_tile[row - row0]);
                             if (take && ex_hi[j] > ex_lo[j]) take = !excluded(excl_idx, ex_lo[j], ex_hi[j], (int)row);
                             bool settled = true;
                             if (take) {
@@ -293,6 +364,10 @@ struct TopK {
                         }
                     }
                 if (lane_pending) flags[round & 1] = 1;
+                if (!next_staged) {  // the other half was last read in the previous tile's offer(), which ended on a barrier
+                    if (tid < Cfg::BM / 2) reinterpret_cast<unsigned*>(ftile + (fcur ^ 1) * Cfg::BM)[tid] = next_words;
+                    next_staged = true;
+                }
                 __syncthreads();
                 more = flags[round & 1] != 0;
                 wg_cold = flags[2] != 0;
@@ -337,6 +412,36 @@ struct TopK {
         }
         __syncthreads();
         if (tid == 0) flags[2] = 0;
+        if (FACET) fcur ^= 1;
+    }
+
+    // FACET: the facet words of the block's first tile -> LDS (one barrier); the block has at least that tile.
+    __device__ __forceinline__ void stage_first_tile(int64_t row0) {
+        if (threadIdx.x < Cfg::BM / 2)
+            reinterpret_cast<unsigned*>(ftile)[threadIdx.x] = *reinterpret_cast<const unsigned*>(frows + row0 + 2 * threadIdx.x);
+        __syncthreads();
+    }
+
+    // FACET: bit (j * TM + i) * 16 + e (pend's numbering) is set iff the mask of this lane's query j admits the row of
+    // accumulator element e of row tile i.  Elements 4g .. 4g + 3 are four consecutive rows (acc_row) whose facet
+    // words (fw_tile: the tile's, in LDS) are one aligned 8-byte read; rows past N hold the array's zero padding and
+    // are dropped by the row test.
+    __device__ __forceinline__ unsigned long long admitted(const uint16_t* fw_tile, int wm, int lane) const {
+        unsigned long long bits = 0ull;
+#pragma unroll
+        for (int i = 0; i < Cfg::TM; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint2 w = *reinterpret_cast<const uint2*>(fw_tile + (wm * Cfg::TM + i) * 32 + acc_row(4 * g, lane));
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const unsigned fw = ((t & 2 ? w.y : w.x) >> (16 * (t & 1))) & 0xFFFFu;
+#pragma unroll
+                    for (int j = 0; j < Cfg::TN; ++j)
+                        if (facet_admits(amask, myq[j], fw)) bits |= 1ull << ((j * Cfg::TM + i) * 16 + 4 * g + t);
+                }
+            }
+        return bits;
     }
 
     // the sorted lists out: partial[chunk][q0 + q][0..k) for the block's BN queries
@@ -356,12 +461,13 @@ struct TopK {
 // The exact pass: rows in fp32, or (P16) stored as bfloat16 (ICREC_ROWS_BF16) and widened on their way into LDS.
 // EMIT = true additionally stores every score to scores_out[q*N + row] (parity checks only).
 // run_flag != NULL: the whole grid exits unless *run_flag != 0 (the exact pass behind a filter pass).
-template <class Cfg, bool EMIT, bool P16>
+// Facet = FacetArgs: the FACET arm (no EMIT form).
+template <class Cfg, bool EMIT, bool P16, class... Facet>
 __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
     const void* __restrict__ P, int64_t N, int K, const float* __restrict__ Qn, int Qpad, int Q, int k,
     const int32_t* __restrict__ excl_idx, const int32_t* __restrict__ excl_off, uint32_t row_base, int n_row_tiles,
     int tiles_per_chunk, int n_qtiles, u64* __restrict__ partial, float* __restrict__ scores_out,
-    const int* __restrict__ run_flag) {
+    const int* __restrict__ run_flag, Facet... facet) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     if (run_flag != nullptr && *run_flag == 0) return;  // uniform over the grid
     float* As = reinterpret_cast<float*>(smem_raw);
@@ -369,9 +475,11 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
     const int lane = threadIdx.x & 63, wm = (threadIdx.x >> 6) / Cfg::WAVES_N;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
-    TopK<Cfg> sel(smem_raw + (size_t)Cfg::LDS_FLOATS * 4, k, Q, q0, excl_off);
+    TopK<Cfg, false, sizeof...(Facet) != 0> sel(smem_raw + (size_t)Cfg::LDS_FLOATS * 4, k, Q, q0, excl_off, 1,
+                                                facet_args(facet...));
     const int t_begin = chunk * tiles_per_chunk;
     const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
+    if (sizeof...(Facet) != 0 && t_begin < t_end) sel.stage_first_tile((int64_t)t_begin * Cfg::BM);
     for (int tile = t_begin; tile < t_end; ++tile) {
         const int64_t row0 = (int64_t)tile * Cfg::BM;
         f32x16 acc[Cfg::TM][Cfg::TN];
@@ -396,18 +504,19 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
 // The STAGED filter pass of ICREC_ROWS_F32_FILTER: rows and queries as f16 hi/lo planes (Ph/Pl, Qh/Ql), both staged
 // through LDS per tile, scores from three f16 MFMAs per product (gemm_x3.h): within ~1e-7 of the exact chain at 5x its
 // MFMA rate, NOT bit-exact; its lists only nominate candidates for verify_kernel.
-template <class Cfg>
+template <class Cfg, class... Facet>
 __global__ __launch_bounds__(Cfg::THREADS, 2) void staged_search_kernel(
     const _Float16* __restrict__ Ph, const _Float16* __restrict__ Pl, int64_t N, int K, const _Float16* __restrict__ Qh,
     const _Float16* __restrict__ Ql, int Qpad, int Q, int k, const int32_t* __restrict__ excl_idx,
     const int32_t* __restrict__ excl_off, uint32_t row_base, int n_row_tiles, int tiles_per_chunk, int n_qtiles,
-    u64* __restrict__ partial) {
+    u64* __restrict__ partial, Facet... facet) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
-    TopK<Cfg> sel(smem_raw + SmemH<Cfg>::BYTES, k, Q, q0, excl_off);
+    TopK<Cfg, false, sizeof...(Facet) != 0> sel(smem_raw + SmemH<Cfg>::BYTES, k, Q, q0, excl_off, 1, facet_args(facet...));
     const int t_begin = chunk * tiles_per_chunk;
     const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
+    if (sizeof...(Facet) != 0 && t_begin < t_end) sel.stage_first_tile((int64_t)t_begin * Cfg::BM);
     for (int tile = t_begin; tile < t_end; ++tile) {
         const int64_t row0 = (int64_t)tile * Cfg::BM;
         f32x16 a0[Cfg::TM][Cfg::TN], a1[Cfg::TM][Cfg::TN], acc[Cfg::TM][Cfg::TN];
@@ -511,20 +620,22 @@ __device__ __forceinline__ void r32_tile(f32x16 (&out)[2], const char* Xs, const
 // fragments L2 -> registers through an 8-deep ring that runs across rounds (the next round's first fragments land
 // under the selection): no operand staging barriers at all - the staged pass re-stages both operands through LDS for
 // every 128-row tile (two barriers per 64-deep slab).
-template <class Cfg>
+template <class Cfg, class... Facet>
 __global__ __launch_bounds__(Cfg::THREADS, 2) void resident_search_kernel(
     const _Float16* __restrict__ frag, int64_t N, const _Float16* __restrict__ Qh, const _Float16* __restrict__ Ql,
     int Qpad, int Q, int k, const int32_t* __restrict__ excl_idx, const int32_t* __restrict__ excl_off,
-    uint32_t row_base, int n_row_tiles, int tiles_per_chunk, int n_qtiles, u64* __restrict__ partial) {
+    uint32_t row_base, int n_row_tiles, int tiles_per_chunk, int n_qtiles, u64* __restrict__ partial, Facet... facet) {
     static_assert(Cfg::TM == 1 && Cfg::TN == 2 && Cfg::WAVES_N == 1 && Cfg::WAVES_M == 8,
                   "resident pass: 8 waves x (1 row tile x 2 query tiles)");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
-    TopK<Cfg, true> sel(smem_raw + RES_X_BYTES, k, Q, q0, excl_off, tiles_per_chunk);
+    TopK<Cfg, true, sizeof...(Facet) != 0> sel(smem_raw + RES_X_BYTES, k, Q, q0, excl_off, tiles_per_chunk,
+                                               facet_args(facet...));
     const int t_begin = chunk * tiles_per_chunk;
     const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
+    if (sizeof...(Facet) != 0 && t_begin < t_end) sel.stage_first_tile((int64_t)t_begin * Cfg::BM);
 
     // query planes -> LDS (once), weight ring of the first round
     r32_load_queries(smem_raw, Qh, Ql, q0, tid);
@@ -574,8 +685,9 @@ constexpr int ST_ROWS = 256, ST_LDB = 144;  // LDS row stride 144 B: conflict-fr
 
 template <int NQ>
 struct StreamSmem {
-    static __host__ __device__ size_t bytes(int k) {
-        return (size_t)ST_ROWS * ST_LDB + 64 /*thr*/ + 64 /*cnt*/ + (size_t)((NQ * k + 1) & ~1) * 8 + (size_t)NQ * ST_ROWS * 8;
+    static __host__ __device__ size_t bytes(int k, bool facet = false) {
+        return (size_t)ST_ROWS * ST_LDB + 64 /*thr*/ + 64 /*cnt*/ + (size_t)((NQ * k + 1) & ~1) * 8 + (size_t)NQ * ST_ROWS * 8 +
+               (facet ? NQ * FACET_LDS_WORDS * 4 : 0) /*allow masks*/;
     }
 };
 
@@ -610,17 +722,20 @@ __device__ __forceinline__ void stream_load_slab(v4f (&pre)[8], const char* __re
     }
 }
 
-template <int NQ, bool P16>
+template <int NQ, bool P16, class... Facet>  // Facet = FacetArgs: the FACET arm
 __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
     const void* __restrict__ P, int64_t N, int K, const float* __restrict__ Qn /* [K][NQ], zero-padded columns */, int Q,
     int k, const int32_t* __restrict__ excl_idx, const int32_t* __restrict__ excl_off, uint32_t row_base, int n_row_tiles,
-    int tiles_per_chunk, u64* __restrict__ partial) {
+    int tiles_per_chunk, u64* __restrict__ partial, Facet... facet) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    constexpr bool FACET = sizeof...(Facet) != 0;
+    const FacetArgs fa = facet_args(facet...);
     char* rows_s = smem_raw;
     u64* thr = reinterpret_cast<u64*>(smem_raw + ST_ROWS * ST_LDB);
     int* cnt = reinterpret_cast<int*>(thr + 8);
     u64* list = reinterpret_cast<u64*>(cnt + 16);
     u64* queue = list + (size_t)((NQ * k + 1) & ~1);  // 16-B aligned: the cold path reads it two keys at a time
+    uint32_t* amask = reinterpret_cast<uint32_t*>(queue + NQ * ST_ROWS);  // FACET: [NQ][FACET_LDS_WORDS]
 
     constexpr int EPW = P16 ? 2 : 1;             // elements per 32-bit word
     constexpr int SLAB_ELEMS = 32 * EPW;         // 128 B of one row
@@ -632,6 +747,7 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
 
     if (tid < NQ) { thr[tid] = tid < Q ? 0ull : ~0ull; cnt[tid] = 0; }
     for (int i = tid; i < NQ * k; i += ST_ROWS) list[i] = 0ull;
+    if (FACET) facet_load_masks(amask, fa, 0, NQ, Q, tid, ST_ROWS);
 
     u64 mythr[NQ];
     int ex_lo[NQ], ex_hi[NQ];
@@ -648,6 +764,8 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
     stream_load_slab(pre, Pb, N, row_bytes, min(t_begin, n_row_tiles - 1), 0, tid);
 
     for (int tile = t_begin; tile < t_end; ++tile) {
+        // FACET: this thread's row's facet word, in flight under the FMAs (inside the padded array also past N)
+        const unsigned fw = FACET ? fa.rows[(int64_t)tile * ST_ROWS + tid] : 0u;
         float acc[NQ];
 #pragma unroll
         for (int j = 0; j < NQ; ++j) acc[j] = 0.0f;
@@ -692,6 +810,7 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
         for (int j = 0; j < NQ; ++j) {
             const u64 kx = make_key(acc[j] + 0.0f, row_base + (uint32_t)row);
             bool take = row < N && mythr[j] != ~0ull && kx > mythr[j];
+            if (FACET && take) take = facet_admits(amask, j, fw);
             if (take && ex_hi[j] > ex_lo[j]) take = !excluded(excl_idx, ex_lo[j], ex_hi[j], (int)row);
             key[j] = take ? kx : 0ull;
         }
@@ -994,6 +1113,8 @@ struct Index {
     int device = 0;
     int n_cu = 256;
     int stream_max_q = 8;          // ICREC_STREAM_MAX_Q at creation
+    uint16_t* facets = nullptr;    // icrec_index_set_facets: one word per row, zero padded to whole 256-row tiles
+    int n_facets = 0;
 };
 
 static inline bool rows_are_bf16(const Index* ix) { return ix->storage == ICREC_ROWS_BF16 || ix->storage == ICREC_ROWS_BF16_FILTER; }
@@ -1052,12 +1173,20 @@ static int stream_max_q_from_env() {
     return v > 8 ? 8 : v < 0 ? 0 : v;
 }
 
-// Dynamic LDS of the tiled kernels: operand staging, then the selection (TopK).
-template <class Cfg> static size_t exact_smem(int k) { return (size_t)Cfg::LDS_FLOATS * 4 + TopK<Cfg>::bytes(k); }
-static size_t staged_smem(int k) { return SmemH<CfgFilter>::BYTES + TopK<CfgFilter>::bytes(k); }
-static size_t resident_smem(int k) { return RES_X_BYTES + TopK<CfgRes, true>::bytes(k); }
+// Dynamic LDS of the tiled kernels: operand staging, then the selection (TopK; `facet`: with the allow masks and the tiles' facet words).
+template <class Cfg> static size_t exact_smem(int k, bool facet) {
+    return (size_t)Cfg::LDS_FLOATS * 4 + (facet ? TopK<Cfg, false, true>::bytes(k) : TopK<Cfg>::bytes(k));
+}
+static size_t staged_smem(int k, bool facet) {
+    return SmemH<CfgFilter>::BYTES + (facet ? TopK<CfgFilter, false, true>::bytes(k) : TopK<CfgFilter>::bytes(k));
+}
+static size_t resident_smem(int k, bool facet) {
+    return RES_X_BYTES + (facet ? TopK<CfgRes, true, true>::bytes(k) : TopK<CfgRes, true>::bytes(k));
+}
+constexpr size_t LDS_MAX = 160 * 1024;
 
-static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream) {
+// `facet`: the plan of a faceted search - the same tiles and chunks (and hence the same workspace), more LDS.
+static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream, bool facet = false) {
     Plan p;
     // The streaming kernel pays a per-block cold start (rank 256 keys per query by counting) that only amortises
     // over several tiles: take it for Q <= 2 always, for Q <= 8 once every block has >= 2 tiles (measured at
@@ -1072,9 +1201,9 @@ static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream) {
         // ~3 blocks per CU are resident (LDS)
         plan_chunks(ix->n_rows, p.BM, 3 * ix->n_cu, MERGE_MAX_LISTS, &p.n_row_tiles, &p.tiles_per_chunk, &p.n_chunks);
     } else {
-        if (Q > 64 && k <= 32) { p.variant = 0; p.BM = CfgBig::BM; p.BN = CfgBig::BN; p.smem = exact_smem<CfgBig>(k); }
-        else if (Q > 32 && k <= 64) { p.variant = 1; p.BM = CfgMid::BM; p.BN = CfgMid::BN; p.smem = exact_smem<CfgMid>(k); }
-        else { p.variant = 2; p.BM = CfgSmall::BM; p.BN = CfgSmall::BN; p.smem = exact_smem<CfgSmall>(k); }
+        if (Q > 64 && k <= 32) { p.variant = 0; p.BM = CfgBig::BM; p.BN = CfgBig::BN; p.smem = exact_smem<CfgBig>(k, facet); }
+        else if (Q > 32 && k <= 64) { p.variant = 1; p.BM = CfgMid::BM; p.BN = CfgMid::BN; p.smem = exact_smem<CfgMid>(k, facet); }
+        else { p.variant = 2; p.BM = CfgSmall::BM; p.BN = CfgSmall::BN; p.smem = exact_smem<CfgSmall>(k, facet); }
         p.n_qtiles = (Q + p.BN - 1) / p.BN;
         p.Qpad = p.n_qtiles * p.BN;
         // one full wave of resident blocks (2 per CU fit by LDS/VGPR), at most 256 chunks
@@ -1094,21 +1223,22 @@ struct FilterPlan {
     size_t smem, off_qh, off_ql, off_flag, off_cand, off_partial, ws_total;
 };
 
-static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& exact) {
+static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& exact, bool facet = false) {
     FilterPlan f;
     f.kp = filter_list_len(k);
     f.resident = ix->frag != nullptr;
     f.use = (ix->plane_hi != nullptr || f.resident) && Q >= FILTER_MIN_Q && f.kp <= ICREC_MAX_K;
     // resident form: the query planes leave 64 KB of LDS for the lists (k <= 92); longer lists take the exact search,
     // which is the faster one there anyway (measured at 49,688 rows, Q = 1,024, k = 100: staged filter 2.5 ms, exact 1.5 ms)
-    if (f.resident && resident_smem(f.kp) > 160 * 1024) f.use = false;
+    // (with the allow masks of a faceted search: k <= 84)
+    if (f.resident && resident_smem(f.kp, facet) > LDS_MAX) f.use = false;
     if (!f.use) { f.ws_total = 0; return f; }
     f.n_qtiles = (Q + CfgFilter::BN - 1) / CfgFilter::BN;  // 64 queries per tile in both forms
     f.Qpad = f.n_qtiles * CfgFilter::BN;
     // staged form: two 4-wave blocks per CU; resident form: one 8-wave block per CU (its query planes take 96 KB)
     plan_chunks(ix->n_rows, f.resident ? CfgRes::BM : CfgFilter::BM, (f.resident ? 1 : 2) * ix->n_cu / f.n_qtiles, 256,
                 &f.n_row_tiles, &f.tiles_per_chunk, &f.n_chunks);
-    f.smem = f.resident ? resident_smem(f.kp) : staged_smem(f.kp);
+    f.smem = f.resident ? resident_smem(f.kp, facet) : staged_smem(f.kp, facet);
     const int qpad_max = f.Qpad > exact.Qpad ? f.Qpad : exact.Qpad;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     f.off_qh = up((size_t)qpad_max * ix->dim * 4);
@@ -1122,13 +1252,16 @@ static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& ex
 }
 
 static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
-                        const int32_t* eo, u64* partial, float* scores_out, const int* run_flag, hipStream_t st);
+                        const int32_t* eo, const uint32_t* allow, u64* partial, float* scores_out, const int* run_flag,
+                        hipStream_t st);
 
 // Filter (f16x3 MFMA, approximate) -> merge -> verify (exact chains on the candidates) -> exact search that runs
-// only if some query could not be proven.  Same outputs, bit for bit, as the exact search.
+// only if some query could not be proven.  Same outputs, bit for bit, as the exact search.  allow != NULL: the filter
+// pass and the guarded exact pass both run their FACET arm with the same masks.
 static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, const float* q, int Q, int k,
-                               const int32_t* ei, const int32_t* eo, int64_t* out_idx, float* out_score, u64* out_keys,
-                               void* ws, hipStream_t st) {
+                               const int32_t* ei, const int32_t* eo, const uint32_t* allow, int64_t* out_idx,
+                               float* out_score, u64* out_keys, void* ws, hipStream_t st) {
+    const FacetArgs fa{ix->facets, allow, ix->n_facets};
     char* base = reinterpret_cast<char*>(ws);
     float* qn = reinterpret_cast<float*>(base);
     _Float16* qh = reinterpret_cast<_Float16*>(base + f.off_qh);
@@ -1144,21 +1277,38 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
         hipLaunchKernelGGL(split_queries_act_kernel, dim3((unsigned)((nq / 4 + 255) / 256 < 1024 ? (nq / 4 + 255) / 256 : 1024)),
                            dim3(256), 0, st, (const float*)qn, nq / 4, qh, ql, flag);
         auto kern = resident_search_kernel<CfgRes>;
-        if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc_;
+        auto kern_f = resident_search_kernel<CfgRes, FacetArgs>;
+        if (int rc_ = ensure_dynamic_lds(allow ? reinterpret_cast<const void*>(kern_f) : reinterpret_cast<const void*>(kern),
+                                         160 * 1024))
+            return rc_;
         ScopedTimer tm(T_SEARCH_KERNEL, st);
-        hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st, (const _Float16*)ix->frag,
-                           ix->n_rows, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo,
-                           (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
+        if (allow)
+            hipLaunchKernelGGL(kern_f, dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st,
+                               (const _Float16*)ix->frag, ix->n_rows, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp,
+                               ei, eo, (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial, fa);
+        else
+            hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st, (const _Float16*)ix->frag,
+                               ix->n_rows, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo,
+                               (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     } else {
         hipLaunchKernelGGL(split_planes_kernel<false>, dim3((unsigned)((nq + 255) / 256 < 1024 ? (nq + 255) / 256 : 1024)),
                            dim3(256), 0, st, (const void*)qn, nq, qh, ql, flag);
         auto kern = staged_search_kernel<CfgFilter>;
-        if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc_;
+        auto kern_f = staged_search_kernel<CfgFilter, FacetArgs>;
+        if (int rc_ = ensure_dynamic_lds(allow ? reinterpret_cast<const void*>(kern_f) : reinterpret_cast<const void*>(kern),
+                                         160 * 1024))
+            return rc_;
         ScopedTimer tm(T_SEARCH_KERNEL, st);
-        hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st,
-                           (const _Float16*)ix->plane_hi, (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim,
-                           (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
-                           f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
+        if (allow)
+            hipLaunchKernelGGL(kern_f, dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st,
+                               (const _Float16*)ix->plane_hi, (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim,
+                               (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
+                               f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial, fa);
+        else
+            hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st,
+                               (const _Float16*)ix->plane_hi, (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim,
+                               (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
+                               f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     }
     ICREC_HIP(hipGetLastError());
     hipLaunchKernelGGL(merge_kernel<4>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, f.n_chunks, f.Qpad, Q, f.kp,
@@ -1168,7 +1318,7 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
                        filter_eps(ix->dim), out_idx, out_score, out_keys, flag);
     ICREC_HIP(hipGetLastError());
     // exact pass: every workgroup returns at once unless verify raised the flag
-    if (int rc = launch_exact(ix, ex, qn, Q, k, ei, eo, partial, nullptr, flag, st)) return rc;
+    if (int rc = launch_exact(ix, ex, qn, Q, k, ei, eo, allow, partial, nullptr, flag, st)) return rc;
     hipLaunchKernelGGL(merge_kernel<4>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, ex.n_chunks, ex.Qpad, Q, k, out_idx,
                        out_score, out_keys, (const int*)flag);
     ICREC_HIP(hipGetLastError());
@@ -1176,9 +1326,11 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
 }
 
 // The exact search of plan p over the index rows (fp32 or bf16): partial lists, or every score into scores_out.  run_flag:
-// the guarded pass of the filter path, which has a timer slot of its own.  (Kernel tables: bf16 rows first.)
+// the guarded pass of the filter path, which has a timer slot of its own.  allow != NULL: the FACET arms (never with
+// scores_out).  (Kernel tables: bf16 rows first.)
 static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
-                        const int32_t* eo, u64* partial, float* scores_out, const int* run_flag, hipStream_t st) {
+                        const int32_t* eo, const uint32_t* allow, u64* partial, float* scores_out, const int* run_flag,
+                        hipStream_t st) {
     using SearchFn = decltype(&search_kernel<CfgBig, false, false>);
     static const SearchFn lists[2][3] = {
         {search_kernel<CfgBig, false, true>, search_kernel<CfgMid, false, true>, search_kernel<CfgSmall, false, true>},
@@ -1191,21 +1343,47 @@ static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, 
     static const SearchFn scores[2][3] = {
         {search_kernel<CfgBig, true, true>, search_kernel<CfgMid, true, true>, search_kernel<CfgSmall, true, true>},
         {search_kernel<CfgBig, true, false>, search_kernel<CfgMid, true, false>, search_kernel<CfgSmall, true, false>}};
+    using FacetFn = decltype(&search_kernel<CfgBig, false, false, FacetArgs>);
+    static const FacetFn facet_lists[2][3] = {
+        {search_kernel<CfgBig, false, true, FacetArgs>, search_kernel<CfgMid, false, true, FacetArgs>,
+         search_kernel<CfgSmall, false, true, FacetArgs>},
+        {search_kernel<CfgBig, false, false, FacetArgs>, search_kernel<CfgMid, false, false, FacetArgs>,
+         search_kernel<CfgSmall, false, false, FacetArgs>}};
+    static const decltype(&stream_search_kernel<1, false, FacetArgs>) facet_stream[4][2] = {
+        {stream_search_kernel<1, true, FacetArgs>, stream_search_kernel<1, false, FacetArgs>},
+        {stream_search_kernel<2, true, FacetArgs>, stream_search_kernel<2, false, FacetArgs>},
+        {stream_search_kernel<4, true, FacetArgs>, stream_search_kernel<4, false, FacetArgs>},
+        {stream_search_kernel<8, true, FacetArgs>, stream_search_kernel<8, false, FacetArgs>}};
+    const FacetArgs fa{ix->facets, allow, ix->n_facets};
     const int r = rows_are_bf16(ix) ? 0 : 1;
     if (p.variant == 3) {
         const int nq = p.BN == 1 ? 0 : p.BN == 2 ? 1 : p.BN == 4 ? 2 : 3;
-        const size_t smem = nq == 0 ? StreamSmem<1>::bytes(k) : nq == 1 ? StreamSmem<2>::bytes(k)
-                            : nq == 2 ? StreamSmem<4>::bytes(k) : StreamSmem<8>::bytes(k);
+        const bool f = allow != nullptr;
+        const size_t smem = nq == 0 ? StreamSmem<1>::bytes(k, f) : nq == 1 ? StreamSmem<2>::bytes(k, f)
+                            : nq == 2 ? StreamSmem<4>::bytes(k, f) : StreamSmem<8>::bytes(k, f);
         ScopedTimer tm(T_SEARCH_KERNEL, st);
-        hipLaunchKernelGGL(stream[nq][r], dim3(p.n_chunks), dim3(ST_ROWS), smem, st, (const void*)ix->rows, ix->n_rows,
-                           ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk, partial);
+        if (allow)
+            hipLaunchKernelGGL(facet_stream[nq][r], dim3(p.n_chunks), dim3(ST_ROWS), smem, st, (const void*)ix->rows,
+                               ix->n_rows, ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles,
+                               p.tiles_per_chunk, partial, fa);
+        else
+            hipLaunchKernelGGL(stream[nq][r], dim3(p.n_chunks), dim3(ST_ROWS), smem, st, (const void*)ix->rows, ix->n_rows,
+                               ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk, partial);
     } else {
         const SearchFn kern = (scores_out ? scores : lists)[r][p.variant];
-        if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc_;
+        const FacetFn kern_f = facet_lists[r][p.variant];
+        if (int rc_ = ensure_dynamic_lds(allow ? reinterpret_cast<const void*>(kern_f) : reinterpret_cast<const void*>(kern),
+                                         160 * 1024))
+            return rc_;
         ScopedTimer tm(run_flag == nullptr ? T_SEARCH_KERNEL : T_SEARCH_FALLBACK, st);
-        hipLaunchKernelGGL(kern, dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st, (const void*)ix->rows,
-                           ix->n_rows, ix->dim, qn, p.Qpad, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles,
-                           p.tiles_per_chunk, p.n_qtiles, partial, scores_out, run_flag);
+        if (allow)
+            hipLaunchKernelGGL(kern_f, dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st,
+                               (const void*)ix->rows, ix->n_rows, ix->dim, qn, p.Qpad, Q, k, ei, eo, (uint32_t)ix->row_offset,
+                               p.n_row_tiles, p.tiles_per_chunk, p.n_qtiles, partial, scores_out, run_flag, fa);
+        else
+            hipLaunchKernelGGL(kern, dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st, (const void*)ix->rows,
+                               ix->n_rows, ix->dim, qn, p.Qpad, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles,
+                               p.tiles_per_chunk, p.n_qtiles, partial, scores_out, run_flag);
     }
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
@@ -1219,15 +1397,19 @@ void launch_merge(const u64* keys, int n_lists, int q_stride, int Q, int k, int6
                        n_lists, q_stride, Q, k, out_idx, out_score, out_keys, (const int*)nullptr);
 }
 
+// allow != NULL (icrec_search_faceted): every selecting kernel runs its FACET arm on the index's facets.
 static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei, const int32_t* eo, int64_t* out_idx,
-                      float* out_score, u64* out_keys, float* scores_out, void* ws, size_t ws_bytes, hipStream_t st) {
+                      float* out_score, u64* out_keys, float* scores_out, void* ws, size_t ws_bytes, hipStream_t st,
+                      const uint32_t* allow = nullptr) {
     ICREC_REQUIRE(ix && q, "icrec_search: NULL index or queries");
     ICREC_REQUIRE(Q >= 1, "icrec_search: n_queries must be >= 1 (got %d)", Q);
     ICREC_REQUIRE(k >= 1 && k <= ICREC_MAX_K, "icrec_search: k must be in [1, %d] (got %d)", ICREC_MAX_K, k);
     ICREC_REQUIRE((ei == nullptr) == (eo == nullptr), "icrec_search: excl_idx and excl_off must both be set or both NULL");
+    ICREC_REQUIRE(allow == nullptr || ix->facets != nullptr, "icrec_search_faceted: allow masks on an index without facets");
+    const bool facet = allow != nullptr;
     if (scores_out == nullptr && (ix->plane_hi != nullptr || ix->frag != nullptr)) {
-        const Plan ex = make_plan(ix, Q, k, false);
-        const FilterPlan f = make_filter_plan(ix, Q, k, ex);
+        const Plan ex = make_plan(ix, Q, k, false, facet);
+        const FilterPlan f = make_filter_plan(ix, Q, k, ex, facet);
         if (f.use) {
             if (ws_bytes < f.ws_total || ws == nullptr) {
                 set_error("icrec_search: workspace too small (%zu < %zu)", ws_bytes, f.ws_total);
@@ -1235,10 +1417,10 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
             }
             ICREC_HIP(hipSetDevice(ix->device));
             ScopedTimer whole(T_SEARCH, st);
-            return run_search_filtered(ix, f, ex, q, Q, k, ei, eo, out_idx, out_score, out_keys, ws, st);
+            return run_search_filtered(ix, f, ex, q, Q, k, ei, eo, allow, out_idx, out_score, out_keys, ws, st);
         }
     }
-    const Plan p = make_plan(ix, Q, k, scores_out == nullptr);
+    const Plan p = make_plan(ix, Q, k, scores_out == nullptr, facet);
     if (ws_bytes < p.ws_total || ws == nullptr) {
         set_error("icrec_search: workspace too small (%zu < %zu)", ws_bytes, p.ws_total);
         return ICREC_ENOMEM;
@@ -1249,7 +1431,7 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
     u64* partial = reinterpret_cast<u64*>(reinterpret_cast<char*>(ws) + p.ws_q);
     hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3((p.Qpad + 3) / 4), dim3(256), 0, st, q, (void*)qn, (int64_t)Q,
                        (int64_t)p.Qpad, ix->dim, 1e-12f, p.variant == 3 ? p.Qpad : 0);
-    if (int rc = launch_exact(ix, p, qn, Q, k, ei, eo, partial, scores_out, nullptr, st)) return rc;
+    if (int rc = launch_exact(ix, p, qn, Q, k, ei, eo, allow, partial, scores_out, nullptr, st)) return rc;
     if (out_idx || out_keys) {
         if (Q <= 4 && p.n_chunks <= 256 && (int64_t)p.n_chunks * k <= MERGE_BLOCK_KEYS)
             hipLaunchKernelGGL(merge_block_kernel, dim3(Q), dim3(256), 0, st, partial, p.n_chunks, p.Qpad, Q, k, out_idx,
@@ -1428,9 +1610,45 @@ int icrec_index_destroy(icrec_index* h) {
     hipFree(ix->plane_hi);
     hipFree(ix->plane_lo);
     hipFree(ix->frag);
+    hipFree(ix->facets);
     delete ix;
     return ICREC_OK;
 }
+
+int icrec_index_set_facets(icrec_index* h, const uint8_t* facets_host, int32_t n_facets) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix, "icrec_index_set_facets: NULL index");
+    ICREC_HIP(hipSetDevice(ix->device));
+    if (facets_host == nullptr) {
+        ICREC_HIP(hipFree(ix->facets));
+        ix->facets = nullptr;
+        ix->n_facets = 0;
+        return ICREC_OK;
+    }
+    ICREC_REQUIRE(n_facets >= 1 && n_facets <= ICREC_MAX_FACETS, "icrec_index_set_facets: n_facets must be in [1, %d] (got %d)",
+                  ICREC_MAX_FACETS, n_facets);
+    // one word per row, zero padded to whole 256-row tiles (the widest tile any search kernel walks)
+    const size_t padded = (size_t)((ix->n_rows + 255) / 256) * 256;
+    std::vector<uint16_t> words(padded, 0);
+    for (int64_t i = 0; i < ix->n_rows; ++i)
+        words[i] = n_facets == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * i] | (facets_host[2 * i + 1] << 8));
+    uint16_t* dev = nullptr;
+    if (hipMalloc(&dev, padded * 2) != hipSuccess) {
+        set_error("icrec_index_set_facets: hipMalloc of %zu bytes failed", padded * 2);
+        return ICREC_ENOMEM;
+    }
+    if (hipMemcpy(dev, words.data(), padded * 2, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        set_error("icrec_index_set_facets: copying the facets to the device failed");
+        return ICREC_EHIP;
+    }
+    (void)hipFree(ix->facets);
+    ix->facets = dev;
+    ix->n_facets = n_facets;
+    return ICREC_OK;
+}
+
+int32_t icrec_index_facets(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_facets : -1; }
 
 int64_t icrec_index_rows(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_rows : 0; }
 int64_t icrec_index_row_offset(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->row_offset : 0; }
@@ -1465,6 +1683,18 @@ int icrec_search(icrec_index* h, const float* q_dev, int32_t n_queries, int32_t 
     ICREC_REQUIRE(out_idx_dev && out_score_dev, "icrec_search: NULL output");
     return run_search(reinterpret_cast<Index*>(h), q_dev, n_queries, k, excl_idx_dev, excl_off_dev, out_idx_dev,
                       out_score_dev, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t icrec_search_faceted_workspace_bytes(const icrec_index* h, int32_t n_queries, int32_t k) {
+    return icrec_search_workspace_bytes(h, n_queries, k);  // the plans of a faceted search cut the rows the same way
+}
+
+int icrec_search_faceted(icrec_index* h, const float* q_dev, int32_t n_queries, int32_t k, const int32_t* excl_idx_dev,
+                         const int32_t* excl_off_dev, const uint32_t* allow_dev, int64_t* out_idx_dev, float* out_score_dev,
+                         void* ws, size_t ws_bytes, void* stream) {
+    ICREC_REQUIRE(out_idx_dev && out_score_dev, "icrec_search_faceted: NULL output");
+    return run_search(reinterpret_cast<Index*>(h), q_dev, n_queries, k, excl_idx_dev, excl_off_dev, out_idx_dev,
+                      out_score_dev, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream, allow_dev);
 }
 
 int icrec_search_partial(icrec_index* h, const float* q_dev, int32_t n_queries, int32_t k, const int32_t* excl_idx_dev,

@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .encoder import DeviceEncoder
 from .model_io import LoadedModel, load_model_dir
-from .search import DeviceIndex
+from .search import DeviceIndex, facet_masks
 
 logger = logging.getLogger(__name__)
 
@@ -106,6 +106,28 @@ class EmbeddingIndex:
         logger.info("Saved embedding index to %s (%d products)", self._dir, len(product_ids))
 
 
+def catalog_facets(texts: Sequence[str]):
+    """The aisle and the department of every catalog text "Product: {name}. Aisle: {aisle}. Department: {department}."
+    (the reference's corpus format), parsed from the right so that a product name may hold the markers itself:
+    the department is what follows the last ". Department: " without the final ".", the aisle what lies between the
+    last ". Aisle: " before that point and it.  -> (aisle names, department names, codes uint8 [n, 2]), names in
+    order of first appearance, codes[i] = (index of text i's aisle, index of its department); None when a text does
+    not parse or a facet has more than 256 distinct values (a recommender then has no facets)."""
+    names: tuple[dict[str, int], dict[str, int]] = ({}, {})
+    codes = np.zeros((len(texts), 2), np.uint8)
+    for i, text in enumerate(texts):
+        d = text.rfind(". Department: ")
+        a = text.rfind(". Aisle: ", 0, d) if d >= 0 else -1
+        if a < 0 or not text.endswith("."):
+            return None
+        for f, value in enumerate((text[a + len(". Aisle: "):d], text[d + len(". Department: "):-1])):
+            code = names[f].setdefault(value, len(names[f]))
+            if code > 255:
+                return None
+            codes[i, f] = code
+    return list(names[0]), list(names[1]), codes
+
+
 class SbertModel:
     """What `self.model` is in the reference (a SentenceTransformer): tokenizer + device encoder
     with an `encode(texts, batch_size, show_progress_bar, normalize_embeddings)` method."""
@@ -170,6 +192,7 @@ class Recommender:
         # exactly — same bits out as plain "f32" (ICREC_INDEX_STORAGE=f32 turns the planes off, =bf16 halves the rows)
         self._index = DeviceIndex(self.product_embeddings, self.device,
                                   storage=os.getenv("ICREC_INDEX_STORAGE", "f32+filter"))
+        self._set_facets()
         self._fast = None
         if os.getenv("ICREC_USE_GRAPH", "1") != "0":
             from .fastpath import SingleRequestPath
@@ -219,6 +242,14 @@ class Recommender:
         logger.info("Loaded model from %s, corpus %d products", self.model_dir, len(self.product_ids))
         return embeddings
 
+    def _set_facets(self) -> None:
+        """Aisle and department codes of the catalog texts onto the index (a re-index builds a new Recommender and
+        so comes through here too); a catalog in another format has none: .aisles / .departments are then None."""
+        parsed = catalog_facets(self.product_texts)
+        self.aisles, self.departments = (parsed[0], parsed[1]) if parsed else (None, None)
+        if parsed:
+            self._index.set_facets(parsed[2])
+
     # -- the hot path -------------------------------------------------------------------------
     def _k(self, top_k: int) -> int:
         """The search width for a request's top_k, checked before any GPU work: at least 1 (the reference's loop
@@ -235,9 +266,42 @@ class Recommender:
             return None
         return [[self._pid_to_row[p] for p in e if p in self._pid_to_row] if e else [] for e in exclude_product_ids]
 
-    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False):
+    def _facet_allow(self, aisles, departments, n: int):
+        """Per-query aisle / department name lists (each None, or n entries of None or an iterable of names) -> the
+        per-query constraints facet_masks takes, or None when no query is constrained."""
+        if aisles is None and departments is None:
+            return None
+        if self.aisles is None:
+            raise ValueError("this catalog has no aisle / department facets (its texts are not in the "
+                             "'Product: .. Aisle: .. Department: ..' format)")
+        per_facet = []
+        for what, given, known in (("aisle", aisles, self.aisles), ("department", departments, self.departments)):
+            if given is None:
+                given = [None] * n
+            if len(given) != n:
+                raise ValueError(f"{what}s has {len(given)} entries for {n} queries")
+            code = {name: i for i, name in enumerate(known)}
+            col = []
+            for names in given:
+                if names is None:
+                    col.append(None)
+                    continue
+                names = [names] if isinstance(names, str) else list(names)
+                unknown = [x for x in names if x not in code]
+                if unknown:
+                    raise ValueError(f"unknown {what} {unknown[0]!r}")
+                col.append([code[x] for x in names])
+            per_facet.append(col)
+        if all(a is None and d is None for a, d in zip(*per_facet)):
+            return None
+        return [None if a is None and d is None else (a, d) for a, d in zip(*per_facet)]
+
+    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
-        current stream; timed=True adds (encode ms, search ms) from HIP events around the two."""
+        current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  allow: per-query
+        facet constraints (_facet_allow)."""
+        if allow is not None:
+            allow = facet_masks(allow, len(cu) - 1, self._index.n_facets, self.device)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
         stream = torch.cuda.current_stream(self.device)
         if ev:
@@ -245,26 +309,29 @@ class Recommender:
         emb = self.model.encoder.encode_packed_host(ids, cu)
         if ev:
             ev[1].record(stream)
-        idx, sc = self._index.search(emb, k, ex)
+        idx, sc = self._index.search(emb, k, ex, allow)
         if ev:
             ev[2].record(stream)
         idx, sc = idx.cpu().numpy(), sc.cpu().numpy()  # synchronises the stream
         return (idx, sc, ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])) if ev else (idx, sc)
 
-    def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False):
-        """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path.
+    def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, aisles=None,
+                       departments=None):
+        """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path (always
+        when the request names aisles or departments).
         -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
+        allow = self._facet_allow(None if aisles is None else [aisles], None if departments is None else [departments], 1)
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed([query])
         tok_ms = (time.time() - t0) * 1000
         ex = self._exclusion_rows([exclude_product_ids])
         rows = ex[0] if ex else []
-        fast = self._fast_path()
+        fast = self._fast_path() if allow is None else None
         if fast is not None and fast.supports(len(ids), k, len(rows)):
             idx, sc, *ms = fast.run(ids, k, rows, timed=timed)
         else:
-            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed)
+            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow)
             idx, sc = idx[0], sc[0]
         results = self._to_results(idx, sc)
         return (results, tok_ms + ms[0], ms[1]) if timed else results
@@ -273,14 +340,18 @@ class Recommender:
         return [(self.product_ids[int(i)], float(s)) for i, s in zip(idx_row, sc_row) if i >= 0]
 
     def recommend_batch(self, queries: Sequence[str], top_k: int = 10,
-                        exclude_product_ids: Optional[Sequence[Optional[set[str]]]] = None
+                        exclude_product_ids: Optional[Sequence[Optional[set[str]]]] = None, *,
+                        aisles: Optional[Sequence[Optional[Sequence[str]]]] = None,
+                        departments: Optional[Sequence[Optional[Sequence[str]]]] = None
                         ) -> list[list[tuple[str, float]]]:
-        """Many contexts in one GPU pass; element i equals recommend(queries[i], ...)."""
+        """Many contexts in one GPU pass; element i equals recommend(queries[i], ...).  aisles / departments: per
+        query None or the admitted names, as recommend takes them."""
         if not queries:
             return []
         k = self._k(top_k)
         ex = self._exclusion_rows(exclude_product_ids)
-        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex)
+        allow = self._facet_allow(aisles, departments, len(queries))
+        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))]
 
     def recommend_batches(self, batches, top_k: int = 10, exclude_product_ids=None):
@@ -297,22 +368,29 @@ class Recommender:
         for idx, sc in pipelined_search(self.model.tokenizer, self.model.encoder, self._index.search, batches, k, exclude):
             yield [self._to_results(idx[i], sc[i]) for i in range(idx.shape[0])]
 
-    def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None):
+    def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None, *, aisles=None,
+                              departments=None):
         """recommend_batch plus (embedding ms incl. host tokenisation, similarity ms) from HIP events
         on the launch stream — what the micro-batching server reports as per-request stats."""
         k = self._k(top_k)
         ex = self._exclusion_rows(exclude_product_ids)
+        allow = self._facet_allow(aisles, departments, len(queries))
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed(list(queries))
         tok_ms = (time.time() - t0) * 1000
-        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True)
+        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))], tok_ms + enc_ms, sim_ms
 
     def recommend(self, query: str, top_k: int = 10,
-                  exclude_product_ids: set[str] | None = None) -> list[tuple[str, float]]:
+                  exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
+                  departments: Optional[Sequence[str]] = None) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
-        One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0"."""
-        return self._recommend_one(query, top_k, exclude_product_ids)
+        One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0".
+        aisles / departments (keyword-only; names from .aisles / .departments): only products of one of these aisles
+        AND one of these departments - the result of excluding every other product.  None leaves a facet open, []
+        admits nothing; a name the catalog does not have raises ValueError.  Such a request takes the un-captured
+        path."""
+        return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -333,11 +411,13 @@ class MonitoredRecommender(Recommender):
         self.last_metrics: Optional[RecommendationMetrics] = None
 
     def recommend(self, query: str, top_k: int = 10, user_id: Optional[str] = None,
-                  exclude_product_ids: set[str] | None = None) -> list[tuple[str, float]]:
+                  exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
+                  departments: Optional[Sequence[str]] = None) -> list[tuple[str, float]]:
         """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
         replays (fastpath.py): the three timing fields keep their meaning there."""
         start = time.time()
-        results, encode_ms, sim_ms = self._recommend_one(query, top_k, exclude_product_ids, timed=True)
+        results, encode_ms, sim_ms = self._recommend_one(query, top_k, exclude_product_ids, timed=True, aisles=aisles,
+                                                         departments=departments)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

@@ -50,6 +50,35 @@ def exclusion_csr(exclude: Optional[Sequence[Iterable[int]]], n_queries: int, de
     return torch.from_numpy(idx).to(device), torch.from_numpy(off).to(device)
 
 
+def facet_masks(allow, n_queries: int, n_facets: int, device=None):
+    """Per-query facet constraints -> the allow masks icrec_search_faceted takes, uint32 [n_queries, n_facets, 8] (a
+    torch tensor on `device`, a numpy array without one).  allow[i] is None (query i is unconstrained) or a sequence
+    of n_facets entries, each None (that facet is unconstrained: all ones) or an iterable of the admitted values
+    0..255 ([] admits nothing).  Bit v & 31 of word v >> 5 admits value v."""
+    if len(allow) != n_queries:
+        raise ValueError(f"allow has {len(allow)} entries for {n_queries} queries")
+    W = _native.ICREC_FACET_MASK_WORDS
+    m = np.zeros((n_queries, n_facets, W), np.uint32)
+    for i, per_query in enumerate(allow):
+        if per_query is None:
+            m[i] = 0xFFFFFFFF
+            continue
+        if len(per_query) != n_facets:
+            raise ValueError(f"allow[{i}] has {len(per_query)} entries for {n_facets} facets")
+        for f, values in enumerate(per_query):
+            if values is None:
+                m[i, f] = 0xFFFFFFFF
+                continue
+            for v in values:
+                v = int(v)
+                if not 0 <= v <= 255:
+                    raise ValueError(f"facet value {v} of allow[{i}][{f}] is outside 0..255")
+                m[i, f, v >> 5] |= np.uint32(1 << (v & 31))
+    if device is None:
+        return m
+    return torch.from_numpy(m.view(np.int32)).to(device).view(torch.uint32)
+
+
 ROW_STORAGE = {"f32": 0, "bf16": 1, "f32+filter": 2, "bf16+filter": 3}  # ICREC_ROWS_* in include/icrec.h
 
 
@@ -82,6 +111,26 @@ class DeviceIndex:
                                               ROW_STORAGE[storage], C.byref(h)), "icrec_index_create_ex")
         self._h = h
 
+    def set_facets(self, values) -> None:
+        """Give every row its facet values, uint8 [n_rows, n_facets] with n_facets 1 or 2 (for a catalog: aisle and
+        department codes), or take them away with None.  A set-up call: never while a search on this index runs.
+        Only searches that pass `allow` look at them."""
+        L = _native.lib()
+        if values is None:
+            _native.check(L.icrec_index_set_facets(self._h, None, 0), "icrec_index_set_facets")
+            return
+        v = np.asarray(values)
+        if v.dtype != np.uint8 or v.ndim != 2 or v.shape[0] != self.n_rows:
+            raise ValueError(f"facets must be uint8 [{self.n_rows}, n_facets], got {v.dtype} {v.shape}")
+        v = np.ascontiguousarray(v)
+        _native.check(L.icrec_index_set_facets(self._h, v.ctypes.data_as(C.c_void_p), int(v.shape[1])),
+                      "icrec_index_set_facets")
+
+    @property
+    def n_facets(self) -> int:
+        """Facet values per row (0: none set)."""
+        return int(_native.lib().icrec_index_facets(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _native.lib().icrec_index_destroy(self._h)
@@ -111,25 +160,39 @@ class DeviceIndex:
         return q.to(device=self.device, dtype=torch.float32).contiguous()
 
     # ------------------------------------------------------------------ API
-    def search(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None):
+    def search(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None):
         """Top-k rows per query: (idx int64[Q,k] with -1 pads, score float32[Q,k]).
-        Order: score descending, lower row first on ties.  `exclude`: per-query local rows."""
+        Order: score descending, lower row first on ties.  `exclude`: per-query local rows.  `allow`: the queries'
+        facet masks, a device uint32 tensor [Q, n_facets, 8] (facet_masks builds it): only rows whose facet values
+        the masks admit are returned - the same bits as excluding every other row."""
         q = self._queries(q)
         Q = int(q.shape[0])
         ei, eo = exclusion_csr(exclude, Q, self.device)
         idx = torch.empty((Q, k), dtype=torch.int64, device=self.device)
         sc = torch.empty((Q, k), dtype=torch.float32, device=self.device)
-        self.search_into(q, k, ei, eo, idx, sc)
+        self.search_into(q, k, ei, eo, idx, sc, allow=allow)
         return idx, sc
 
     def search_into(self, q: torch.Tensor, k: int, excl_idx: Optional[torch.Tensor], excl_off: Optional[torch.Tensor],
-                    out_idx: torch.Tensor, out_score: torch.Tensor, ws: Optional[torch.Tensor] = None) -> None:
+                    out_idx: torch.Tensor, out_score: torch.Tensor, ws: Optional[torch.Tensor] = None,
+                    allow: Optional[torch.Tensor] = None) -> None:
         """Allocation-free form of `search` on caller-owned device buffers (hipGraph-capturable once the
         workspace for this (Q, k) exists, or with `ws` of the caller's own): q float32 [Q, dim],
-        out_idx int64 [Q, k], out_score float32 [Q, k]."""
+        out_idx int64 [Q, k], out_score float32 [Q, k].  The kernels read `allow` when they run: a captured graph
+        follows what the mask buffer holds at replay."""
         Q = int(q.shape[0])
         if ws is None:
             ws = self._workspace(Q, k)
+        if allow is not None:
+            nf = self.n_facets  # 0: the library refuses the call (ICREC_EINVAL)
+            if allow.dtype != torch.uint32 or allow.device != self.device or not allow.is_contiguous() \
+                    or tuple(allow.shape) != (Q, nf or allow.shape[1], _native.ICREC_FACET_MASK_WORDS):
+                raise ValueError(f"allow must be a contiguous uint32 tensor [{Q}, {nf}, {_native.ICREC_FACET_MASK_WORDS}] "
+                                 f"on {self.device}, got {allow.dtype} {tuple(allow.shape)} on {allow.device}")
+            _native.check(_native.lib().icrec_search_faceted(self._h, ptr(q), Q, k, ptr(excl_idx), ptr(excl_off), ptr(allow),
+                                                             ptr(out_idx), ptr(out_score), ptr(ws), ws.numel(),
+                                                             stream_ptr(self.device)), "icrec_search_faceted")
+            return
         _native.check(_native.lib().icrec_search(self._h, ptr(q), Q, k, ptr(excl_idx), ptr(excl_off), ptr(out_idx),
                                                  ptr(out_score), ptr(ws), ws.numel(), stream_ptr(self.device)),
                       "icrec_search")
