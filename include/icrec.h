@@ -396,6 +396,47 @@ ICREC_API int icrec_search_faceted(icrec_index* idx, const float* q_dev, int32_t
                          int64_t* out_idx_dev, float* out_score_dev,
                          void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Diversity re-selection of a search result: Maximal Marginal Relevance (Carbonell & Goldstein 1998) over each
+ * query's k candidates, entirely on the device.  Scratch bytes (0 for a NULL index, n_queries < 1 or k outside
+ * [1, ICREC_MAX_K]): the queries' k x k similarity matrices. */
+ICREC_API size_t icrec_mmr_select_workspace_bytes(const icrec_index* idx, int32_t n_queries, int32_t k);
+
+/* Pick top_k of each query's k candidates greedily, trading relevance against similarity to what is already picked.
+ *   cand_idx_dev  int64[n_queries, k]      icrec_search's out_idx: global rows, -1 pads
+ *   rel_dev       float[n_queries, k]      relevance of each candidate (icrec_search's out_score, or cross-encoder
+ *                                          logits); need not be sorted
+ *   lambda        in [0, 1]                1: relevance only, 0: after the first pick, dissimilarity only
+ *   out_idx_dev   int64[n_queries, top_k]  the picks in selection order; -1 pads
+ *   out_rel_dev   float[n_queries, top_k]  the chosen candidates' rel, bits unchanged; 0 at pads
+ * The definition, which the result follows bit for bit:
+ *   Validity.  Candidate j of a query is valid iff cand >= 0 and cand - row_offset lies in [0, n_rows) of idx.  Invalid
+ *     candidates are never selected and their rows are never read.  A row that appears twice in a list is two
+ *     candidates.
+ *   Similarity.  sim(a, b) is the fp32 chain s = 0; for j = 0 .. dim-1: s = fmaf(pa[j], pb[j], s) over the index's
+ *     STORED normalised rows (bf16 storage widened exactly; the rows are not normalised again): icrec_scores'
+ *     arithmetic with a stored row on the query side.  sim(a, b) and sim(b, a) have the same bits.  The filter planes
+ *     and fragments are not used.
+ *   Order.  x is ordered before y iff x is a number and y a NaN, else iff x > y (compared as floats, -0 == +0), else
+ *     (equal, or both NaN) iff x's position j is lower: icrec_rerank_select's rule.
+ *   First pick: the valid candidate whose rel is ordered first.
+ *   Later picks: among the valid candidates not yet selected, the one whose
+ *         v(c) = (lambda * rel[c]) - (oml * maxsim[c])
+ *     is ordered first, where maxsim[c] is the greatest sim(s, c) over the selected s and oml is the float
+ *     1.0f - lambda computed on the host.  v takes three fp32 roundings - the two products, then the difference -
+ *     and no fused multiply-add.
+ *   Termination: after top_k picks, or when no valid candidate is left; the remaining outputs are -1 / 0.0f.
+ * lambda = 1 gives the valid candidates in the order of their rel: on an icrec_search result, its first top_k entries.
+ * A query's result has the same bits alone and inside any batch, for every row storage.
+ * ICREC_EINVAL: a NULL pointer, n_queries < 1, k outside [1, ICREC_MAX_K], top_k outside [1, k], lambda NaN or outside
+ * [0, 1].  ICREC_ENOMEM: workspace_bytes < icrec_mmr_select_workspace_bytes.  Nothing is launched on an error.
+ * The outputs must not alias the inputs.  Asynchronous on `stream`: nothing is allocated, nothing synchronises, every
+ * launch goes to that one stream, and the call can be captured into a hipGraph.  Facets and exclusion lists compose
+ * with it through the search whose result it consumes. */
+ICREC_API int icrec_mmr_select(icrec_index* idx, const int64_t* cand_idx_dev, const float* rel_dev,
+                     int32_t n_queries, int32_t k, int32_t top_k, float lambda,
+                     int64_t* out_idx_dev, float* out_rel_dev,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Shard-local half of a sharded search: same as icrec_search but emits the
  * sorted partial lists as packed 64-bit keys
  *   key = (orderable(score) << 32) | (0xFFFFFFFF - global_row)
@@ -644,7 +685,8 @@ ICREC_API const char* icrec_version(void);
  *        2 = whole encode() call, 3 = whole search() call,
  *        4 = the guarded exact pass behind a filter pass (ICREC_ROWS_F32_FILTER):
  *            a few microseconds when every query was proven, a full search
- *            when the fallback ran.                                           */
+ *            when the fallback ran,
+ *        5 = icrec_mmr_select's similarity-matrix kernel, 6 = its selection kernel. */
 ICREC_API int icrec_timing_enable(int on);
 ICREC_API int icrec_timing_reset(void);
 ICREC_API int icrec_timing_query(int which, double* avg_ms, int64_t* n_launches);

@@ -40,6 +40,7 @@ EXPORTS = [
     "icrec_exclusions_to_shard_csr_workspace_bytes", "icrec_exclusions_to_shard_csr",
     "icrec_search_workspace_bytes", "icrec_search", "icrec_search_partial", "icrec_merge_topk",
     "icrec_index_set_facets", "icrec_index_facets", "icrec_search_faceted_workspace_bytes", "icrec_search_faceted",
+    "icrec_mmr_select_workspace_bytes", "icrec_mmr_select",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
     "icrec_cf_create", "icrec_cf_destroy", "icrec_cf_orders", "icrec_cf_items", "icrec_cf_candidates", "icrec_cf_nnz",
     "icrec_cf_tile", "icrec_cf_rank_workspace_bytes", "icrec_cf_rank", "icrec_cf_rank_all_workspace_bytes",
@@ -144,6 +145,8 @@ def lib() -> C.CDLL:
         "icrec_index_facets": (i32, [vp]),
         "icrec_search_faceted_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_search_faceted": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "icrec_mmr_select_workspace_bytes": (sz, [vp, i32, i32]),
+        "icrec_mmr_select": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, sz, vp]),
         "icrec_merge_topk": (C.c_int, [vp, i32, i32, i32, vp, vp, C.c_int, vp]),
         "icrec_scores": (C.c_int, [vp, vp, i32, vp, vp, sz, vp]),
         "icrec_rank_all_workspace_bytes": (sz, [vp, i32]),
@@ -229,6 +232,14 @@ class StreamScratch(dict):
             self.pop(key, None)  # the old block is freed before the larger one is allocated
             self[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self[key]
+
+
+def mmr_select(index_handle, cand_idx, rel, top_k: int, lam: float, out_idx, out_rel, ws, device) -> None:
+    """icrec_mmr_select on device tensors: cand_idx int64 [Q, k] and rel float32 [Q, k] in, out_idx int64 [Q, top_k]
+    and out_rel float32 [Q, top_k] out, ws a uint8 scratch tensor; asynchronous on `device`'s current stream."""
+    Q, k = int(cand_idx.shape[0]), int(cand_idx.shape[1])
+    check(lib().icrec_mmr_select(index_handle, ptr(cand_idx), ptr(rel), Q, k, int(top_k), float(lam), ptr(out_idx),
+                                 ptr(out_rel), ptr(ws), ws.numel(), stream_ptr(device)), "icrec_mmr_select")
 
 
 def timing_enable(on: bool) -> None:

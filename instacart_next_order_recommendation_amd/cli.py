@@ -8,6 +8,7 @@ ignored; a missing model directory or corpus file is an error).
 
     python -m instacart_next_order_recommendation_amd --config configs/inference.yaml [--query "..."] [--json]
                                                       [--aisle NAME]... [--department NAME]...
+                                                      [--diversity FLOAT] [--candidates INT]
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
 and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
@@ -115,6 +116,11 @@ def main(argv=None) -> int:
                     help="only products of this aisle (repeatable: any of the named aisles)")
     ap.add_argument("--department", action="append", default=None, metavar="NAME",
                     help="only products of this department (repeatable: any of the named departments)")
+    ap.add_argument("--diversity", type=float, default=None, metavar="FLOAT",
+                    help="0..1: re-select the results for diversity (Maximal Marginal Relevance, lambda = 1 - FLOAT); "
+                         "they are then listed in selection order, not by score")
+    ap.add_argument("--candidates", type=int, default=None, metavar="INT",
+                    help="how many best matches a diversified request chooses from (default min(128, 4 * top_k))")
     args = ap.parse_args(argv)
     cfg = read_settings(args.config)
     if not cfg["corpus"].exists():
@@ -126,8 +132,9 @@ def main(argv=None) -> int:
 
     rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"])
     try:
-        hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department)
-    except ValueError as e:  # an aisle / department the catalog does not have
+        hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department,
+                             diversity=args.diversity, candidates=args.candidates)
+    except ValueError as e:  # an aisle / department the catalog does not have, a bad --diversity / --candidates
         raise SystemExit(str(e))
     if args.json:
         for rank, (pid, score) in enumerate(hits, 1):

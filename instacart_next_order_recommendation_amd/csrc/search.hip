@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "gemm_x3.h"
+#include "index.h"
 #include "wt_gemm.h"
 
 namespace icrec {
@@ -1100,25 +1101,6 @@ __global__ __launch_bounds__(256) void merge_block_kernel(const u64* __restrict_
 }
 
 // ---------------------------------------------------------------- host side
-struct Index {
-    void* rows = nullptr;  // normalised [n_rows, dim], fp32 or bf16 bits
-    _Float16* plane_hi = nullptr;  // ICREC_ROWS_F32_FILTER: f16 hi/lo planes of `rows` for the filter pass
-    _Float16* plane_lo = nullptr;
-    _Float16* frag = nullptr;      // resident filter pass (dim 384, <= RES_MAX_ROWS rows): the rows as packed fragments
-    int64_t frag_row_tiles = 0;    // 32-row tiles in `frag` (whole rounds of CfgRes::BM rows)
-    int storage = ICREC_ROWS_F32;
-    int64_t n_rows = 0;
-    int dim = 0;
-    int64_t row_offset = 0;
-    int device = 0;
-    int n_cu = 256;
-    int stream_max_q = 8;          // ICREC_STREAM_MAX_Q at creation
-    uint16_t* facets = nullptr;    // icrec_index_set_facets: one word per row, zero padded to whole 256-row tiles
-    int n_facets = 0;
-};
-
-static inline bool rows_are_bf16(const Index* ix) { return ix->storage == ICREC_ROWS_BF16 || ix->storage == ICREC_ROWS_BF16_FILTER; }
-
 typedef TileCfg<2, 2, 2, 2> CfgBig;    // 128 rows x 128 queries
 typedef TileCfg<4, 1, 2, 2> CfgMid;    // 256 rows x  64 queries
 typedef TileCfg<4, 1, 2, 1> CfgSmall;  // 256 rows x  32 queries

@@ -128,6 +128,23 @@ def catalog_facets(texts: Sequence[str]):
     return list(names[0]), list(names[1]), codes
 
 
+def diversity_plan(diversity, candidates, top_k: int, n_products: int):
+    """A request's `diversity` / `candidates` arguments, checked before any GPU work
+    -> None (the plain path: diversity is None or 0) or (lambda, candidate count) for the MMR re-selection.
+    diversity must lie in [0, 1] (lambda = 1 - diversity), candidates in [top_k, ICREC_MAX_K]; ValueError otherwise.
+    The candidate count defaults to min(ICREC_MAX_K, 4 * top_k) and is clipped to the catalog, never below top_k's own
+    clipped width."""
+    top_k = max(int(top_k), 1)
+    if diversity is not None and not 0.0 <= float(diversity) <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError(f"diversity must be in [0, 1], got {diversity!r}")
+    if candidates is not None and not top_k <= int(candidates) <= _native.ICREC_MAX_K:
+        raise ValueError(f"candidates must be in [top_k = {top_k}, {_native.ICREC_MAX_K}], got {candidates!r}")
+    if diversity is None or float(diversity) == 0.0:
+        return None
+    n = int(candidates) if candidates is not None else min(_native.ICREC_MAX_K, 4 * top_k)
+    return 1.0 - float(diversity), max(min(n, n_products), min(top_k, n_products))
+
+
 class SbertModel:
     """What `self.model` is in the reference (a SentenceTransformer): tokenizer + device encoder
     with an `encode(texts, batch_size, show_progress_bar, normalize_embeddings)` method."""
@@ -296,10 +313,11 @@ class Recommender:
             return None
         return [None if a is None and d is None else (a, d) for a, d in zip(*per_facet)]
 
-    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None):
+    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None, mmr=None):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
         current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  allow: per-query
-        facet constraints (_facet_allow)."""
+        facet constraints (_facet_allow).  mmr: (lambda, candidates) of diversity_plan - the search is then
+        `candidates` wide and the k results are re-selected from it on the device, inside the search time."""
         if allow is not None:
             allow = facet_masks(allow, len(cu) - 1, self._index.n_facets, self.device)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
@@ -309,29 +327,33 @@ class Recommender:
         emb = self.model.encoder.encode_packed_host(ids, cu)
         if ev:
             ev[1].record(stream)
-        idx, sc = self._index.search(emb, k, ex, allow)
+        if mmr is None:
+            idx, sc = self._index.search(emb, k, ex, allow)
+        else:
+            idx, sc = self._index.search_diverse(emb, k, mmr[0], mmr[1], ex, allow)
         if ev:
             ev[2].record(stream)
         idx, sc = idx.cpu().numpy(), sc.cpu().numpy()  # synchronises the stream
         return (idx, sc, ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])) if ev else (idx, sc)
 
     def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, aisles=None,
-                       departments=None):
+                       departments=None, diversity=None, candidates=None):
         """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path (always
-        when the request names aisles or departments).
+        when the request names aisles or departments, or asks for diversity).
         -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
+        mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         allow = self._facet_allow(None if aisles is None else [aisles], None if departments is None else [departments], 1)
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed([query])
         tok_ms = (time.time() - t0) * 1000
         ex = self._exclusion_rows([exclude_product_ids])
         rows = ex[0] if ex else []
-        fast = self._fast_path() if allow is None else None
+        fast = self._fast_path() if allow is None and mmr is None else None
         if fast is not None and fast.supports(len(ids), k, len(rows)):
             idx, sc, *ms = fast.run(ids, k, rows, timed=timed)
         else:
-            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow)
+            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr)
             idx, sc = idx[0], sc[0]
         results = self._to_results(idx, sc)
         return (results, tok_ms + ms[0], ms[1]) if timed else results
@@ -342,16 +364,19 @@ class Recommender:
     def recommend_batch(self, queries: Sequence[str], top_k: int = 10,
                         exclude_product_ids: Optional[Sequence[Optional[set[str]]]] = None, *,
                         aisles: Optional[Sequence[Optional[Sequence[str]]]] = None,
-                        departments: Optional[Sequence[Optional[Sequence[str]]]] = None
+                        departments: Optional[Sequence[Optional[Sequence[str]]]] = None,
+                        diversity: float | None = None, candidates: int | None = None
                         ) -> list[list[tuple[str, float]]]:
         """Many contexts in one GPU pass; element i equals recommend(queries[i], ...).  aisles / departments: per
-        query None or the admitted names, as recommend takes them."""
+        query None or the admitted names, as recommend takes them.  diversity / candidates: one value for the whole
+        batch, as recommend takes them."""
+        mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         if not queries:
             return []
         k = self._k(top_k)
         ex = self._exclusion_rows(exclude_product_ids)
         allow = self._facet_allow(aisles, departments, len(queries))
-        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow)
+        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow, mmr=mmr)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))]
 
     def recommend_batches(self, batches, top_k: int = 10, exclude_product_ids=None):
@@ -369,28 +394,40 @@ class Recommender:
             yield [self._to_results(idx[i], sc[i]) for i in range(idx.shape[0])]
 
     def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None, *, aisles=None,
-                              departments=None):
+                              departments=None, diversity: float | None = None, candidates: int | None = None):
         """recommend_batch plus (embedding ms incl. host tokenisation, similarity ms) from HIP events
-        on the launch stream — what the micro-batching server reports as per-request stats."""
+        on the launch stream — what the micro-batching server reports as per-request stats.  A diversified batch's
+        re-selection counts into the similarity time."""
         k = self._k(top_k)
+        mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         ex = self._exclusion_rows(exclude_product_ids)
         allow = self._facet_allow(aisles, departments, len(queries))
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed(list(queries))
         tok_ms = (time.time() - t0) * 1000
-        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow)
+        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow, mmr=mmr)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))], tok_ms + enc_ms, sim_ms
 
     def recommend(self, query: str, top_k: int = 10,
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
-                  departments: Optional[Sequence[str]] = None) -> list[tuple[str, float]]:
+                  departments: Optional[Sequence[str]] = None, diversity: float | None = None,
+                  candidates: int | None = None) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
         One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0".
         aisles / departments (keyword-only; names from .aisles / .departments): only products of one of these aisles
         AND one of these departments - the result of excluding every other product.  None leaves a facet open, []
         admits nothing; a name the catalog does not have raises ValueError.  Such a request takes the un-captured
-        path."""
-        return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments)
+        path.
+        diversity in (0, 1] (keyword-only): the top_k are re-selected on the GPU from the `candidates` best matches
+        (default min(128, 4 * top_k), at most the catalog) by Maximal Marginal Relevance with lambda = 1 - diversity
+        (DeviceIndex.mmr_select): the best match first, then at each step the product with the best trade of cosine
+        score against similarity to the products already chosen.  The returned scores are still the cosine scores of
+        the chosen products, in SELECTION order - that order is not score-descending.  It composes with
+        exclude_product_ids, aisles and departments (they shape the candidates) and takes the un-captured path.
+        diversity None or 0 is the plain request: the same launches, the same results.  diversity outside [0, 1] or
+        candidates outside [top_k, 128] raises ValueError."""
+        return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments,
+                                   diversity=diversity, candidates=candidates)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -412,12 +449,15 @@ class MonitoredRecommender(Recommender):
 
     def recommend(self, query: str, top_k: int = 10, user_id: Optional[str] = None,
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
-                  departments: Optional[Sequence[str]] = None) -> list[tuple[str, float]]:
+                  departments: Optional[Sequence[str]] = None, diversity: float | None = None,
+                  candidates: int | None = None) -> list[tuple[str, float]]:
         """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
-        replays (fastpath.py): the three timing fields keep their meaning there."""
+        replays (fastpath.py): the three timing fields keep their meaning there.  A diversified request's
+        re-selection counts into the similarity time."""
         start = time.time()
         results, encode_ms, sim_ms = self._recommend_one(query, top_k, exclude_product_ids, timed=True, aisles=aisles,
-                                                         departments=departments)
+                                                         departments=departments, diversity=diversity,
+                                                         candidates=candidates)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

@@ -98,6 +98,7 @@ class DeviceIndex:
         self.storage = storage
         self.device = _native.hip_device(device, "DeviceIndex")
         self._ws_by_stream = _native.StreamScratch(self.device)
+        self._mmr_ws_by_stream = _native.StreamScratch(self.device)  # its own blocks: growing one never moves a search's
         L = _native.lib()
         rows = torch.as_tensor(embeddings)
         if rows.dim() != 2:
@@ -136,6 +137,7 @@ class DeviceIndex:
             _native.lib().icrec_index_destroy(self._h)
             self._h = None
         self._ws_by_stream.clear()
+        self._mmr_ws_by_stream.clear()
 
     def __del__(self):  # pragma: no cover - best effort
         try:
@@ -196,6 +198,42 @@ class DeviceIndex:
         _native.check(_native.lib().icrec_search(self._h, ptr(q), Q, k, ptr(excl_idx), ptr(excl_off), ptr(out_idx),
                                                  ptr(out_score), ptr(ws), ws.numel(), stream_ptr(self.device)),
                       "icrec_search")
+
+    def mmr_select(self, idx: torch.Tensor, rel: torch.Tensor, top_k: int, lam: float):
+        """Diversity re-selection of a search result (Maximal Marginal Relevance, icrec_mmr_select): idx int64 [Q, k]
+        candidate rows as `search` returns them (-1 pads; rows outside this shard are skipped) and rel float32 [Q, k]
+        their relevance (the search scores, or any other: it need not be sorted), both device tensors
+        -> (idx int64 [Q, top_k], rel float32 [Q, top_k]) on the device, in SELECTION order: the most relevant
+        candidate first, then at each step the candidate that maximises lam * rel - (1 - lam) * (its greatest
+        similarity to a row already picked).  lam = 1 keeps the relevance order, lam = 0 only avoids similarity."""
+        if idx.dim() != 2 or idx.dtype != torch.int64 or rel.dtype != torch.float32 or rel.shape != idx.shape:
+            raise ValueError(f"idx must be int64 [Q, k] and rel float32 [Q, k], got {idx.dtype} {tuple(idx.shape)} "
+                             f"and {rel.dtype} {tuple(rel.shape)}")
+        idx, rel = idx.to(self.device).contiguous(), rel.to(self.device).contiguous()
+        out_idx = torch.empty((idx.shape[0], top_k), dtype=torch.int64, device=self.device)
+        out_rel = torch.empty((idx.shape[0], top_k), dtype=torch.float32, device=self.device)
+        self.mmr_select_into(idx, rel, top_k, lam, out_idx, out_rel)
+        return out_idx, out_rel
+
+    def mmr_select_into(self, idx: torch.Tensor, rel: torch.Tensor, top_k: int, lam: float, out_idx: torch.Tensor,
+                        out_rel: torch.Tensor, ws: Optional[torch.Tensor] = None) -> None:
+        """Allocation-free form of `mmr_select` on caller-owned contiguous device buffers (hipGraph-capturable once the
+        workspace for this (Q, k) exists, or with `ws` of the caller's own).  The outputs must not alias the inputs."""
+        Q, k = int(idx.shape[0]), int(idx.shape[1])
+        if ws is None:
+            need = int(_native.lib().icrec_mmr_select_workspace_bytes(self._h, Q, k))
+            if need == 0:
+                raise _native.IcrecError(f"bad mmr_select shape: n_queries={Q}, k={k}")
+            ws = self._mmr_ws_by_stream.block(need)
+        _native.mmr_select(self._h, idx, rel, top_k, lam, out_idx, out_rel, ws, self.device)
+
+    def search_diverse(self, q, top_k: int, lam: float, candidates: int,
+                       exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None):
+        """`search(q, candidates, exclude, allow)` followed by `mmr_select(.., top_k, lam)` on its result, without a
+        host step in between: the top_k most relevant-yet-diverse of each query's `candidates` best rows, with their
+        cosine scores, in selection order (not score-descending)."""
+        idx, sc = self.search(q, candidates, exclude, allow)
+        return self.mmr_select(idx, sc, top_k, lam)
 
     def search_partial(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None) -> torch.Tensor:
         """Shard-local sorted lists as packed keys, int64-viewed uint64 [Q,k] (see icrec_search_partial)."""

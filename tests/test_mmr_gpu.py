@@ -1,0 +1,314 @@
+"""icrec_mmr_select on the GPU against tests/mmr_reference.py: every comparison is bit-equal, on the indices and on the
+returned relevance.  The shapes are the smallest that reach each path of the two kernels: the 32-wide chain steps and
+the tile triangle of the similarity kernel (k around 32 / 64 / 96 / 128), the two candidate slots of a selection lane
+(k around 64), both LDS copy loops (k even / odd), the grid tails, the four row storages, shards, pads."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from instacart_next_order_recommendation_amd import _native
+from instacart_next_order_recommendation_amd.search import DeviceIndex, facet_masks
+from oracle import oracle
+from tests import mmr_reference as ref
+from tests.search_harness import tie_block_catalog, torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+
+
+def clustered(seed, n, dim, nq, n_centres=12):
+    """n rows around n_centres centres and nq queries near rows: a top list holds near-copies, so MMR reorders it."""
+    rng = np.random.default_rng(seed)
+    centres = rng.standard_normal((n_centres, dim), dtype=np.float32)
+    P = centres[rng.integers(0, n_centres, n)] + np.float32(0.35) * rng.standard_normal((n, dim), dtype=np.float32)
+    q = P[rng.choice(n, nq, replace=False)] + np.float32(0.1) * rng.standard_normal((nq, dim), dtype=np.float32)
+    return P, q
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def check(ix, P, cand, rel, top_k, lam):
+    """ix.mmr_select(cand, rel, top_k, lam) equals the reference over the rows an index of ix's storage holds for P."""
+    cand, rel = np.ascontiguousarray(cand, np.int64), np.ascontiguousarray(rel, np.float32)
+    want = ref.mmr_select(ref.stored_rows(P, ix.storage), cand, rel, top_k, lam, ix.row_offset)
+    got = ix.mmr_select(torch.from_numpy(cand).to(ix.device), torch.from_numpy(rel).to(ix.device), top_k, lam)
+    got = got[0].cpu().numpy(), got[1].cpu().numpy()
+    np.testing.assert_array_equal(got[0], want[0])
+    np.testing.assert_array_equal(bits(got[1]), bits(want[1]))
+    return want
+
+
+def searched(ix, q, k):
+    idx, sc = ix.search(q, k)
+    return idx.cpu().numpy(), sc.cpu().numpy()
+
+
+# ---------------------------------------------------------------- chain and staging boundaries
+@pytest.mark.parametrize("dim,n,nq", [(32, 600, 3), (96, 600, 3), (384, 600, 3), (1024, 600, 3), (4096, 300, 2)])
+def test_dims(torch_cuda, dim, n, nq):
+    P, q = clustered(dim, n, dim, nq)
+    ix = DeviceIndex(P)
+    cand, rel = searched(ix, q, 40)
+    changed = 0
+    for lam in (0.7, 0.3):
+        want = check(ix, P, cand, rel, 20, lam)
+        changed += sum(set(want[0][i]) != set(cand[i, :20]) for i in range(nq))
+    assert changed > 0  # the diversified lists are not the plain order
+    ix.close()
+
+
+# ---------------------------------------------------------------- candidate-slot boundaries
+@pytest.fixture(scope="module")
+def slots_case(torch_cuda):
+    P, q = clustered(21, 600, 64, 2)
+    ix = DeviceIndex(P)
+    yield ix, P, q
+    ix.close()
+
+
+@pytest.mark.parametrize("k", [1, 2, 63, 64, 65, 127, 128])
+def test_candidate_slots(slots_case, k):
+    ix, P, q = slots_case
+    cand, rel = searched(ix, q, k)
+    for top_k in sorted({1, (k + 1) // 2, k}):
+        for lam in (1.0, 0.7, 0.5, 0.0):
+            want = check(ix, P, cand, rel, top_k, lam)
+            if lam == 1.0:  # an icrec_search result's own first top_k entries
+                np.testing.assert_array_equal(want[0], cand[:, :top_k])
+                np.testing.assert_array_equal(bits(want[1]), bits(rel[:, :top_k]))
+
+
+# ---------------------------------------------------------------- grid tails, batch independence
+def test_batch_sizes_and_batch_independence(torch_cuda):
+    P, q = clustered(22, 600, 64, 257)
+    ix = DeviceIndex(P)
+    cand, rel = searched(ix, q, 40)
+    for nq in (1, 3, 257):
+        want = check(ix, P, cand[:nq], rel[:nq], 10, 0.5)
+    alone = check(ix, P, cand[5:6], rel[5:6], 10, 0.5)
+    np.testing.assert_array_equal(alone[0][0], want[0][5])
+    np.testing.assert_array_equal(bits(alone[1][0]), bits(want[1][5]))
+    ix.close()
+
+
+# ---------------------------------------------------------------- storages
+@pytest.mark.parametrize("dim", [384, 64, 128])
+@pytest.mark.parametrize("storage", ["f32", "bf16", "f32+filter", "bf16+filter"])
+def test_storages(torch_cuda, storage, dim):
+    """dim 384 keeps a filter storage's rows as packed fragments, the other widths as row-major planes; MMR reads
+    neither, only the stored rows."""
+    P, q = clustered(23 + dim, 600, dim, 3)
+    ix = DeviceIndex(P, storage=storage)
+    cand, rel = searched(ix, q, 70)
+    np.testing.assert_array_equal(cand, oracle.search(q, P, 70, storage="bf16" if storage.startswith("bf16") else "f32")[0])
+    check(ix, P, cand, rel, 30, 0.6)
+    ix.close()
+
+
+# ---------------------------------------------------------------- row offset, pads, invalid candidates
+def test_row_offset_and_candidates_outside_the_shard(torch_cuda):
+    off = 1_000_000
+    P, q = clustered(24, 600, 64, 3)
+    ix = DeviceIndex(P, row_offset=off)
+    cand, rel = searched(ix, q, 40)
+    assert cand.min() >= off
+    check(ix, P, cand, rel, 20, 0.5)
+    # every third candidate belongs to another shard (below, above) or is a pad: skipped, never read
+    cand2 = cand.copy()
+    cand2[:, 0::6] = cand[:, 0::6] - off       # rows of the shard before
+    cand2[:, 3::6] = off + 600 + np.arange(cand[:, 3::6].shape[1])[None, :]
+    cand2[:, 5::9] = -1
+    want = check(ix, P, cand2, rel, 40, 0.5)
+    n_valid = int(ref.valid_candidates(cand2[0], 600, off).sum())
+    assert 0 < n_valid < 40 and (want[0][0, :n_valid] >= off).all() and (want[0][0, n_valid:] == -1).all()
+    # a query without a single valid candidate: all pads
+    cand2[1] = np.where(np.arange(40) % 2 == 0, -1, 5)
+    want = check(ix, P, cand2, rel, 7, 0.5)
+    assert (want[0][1] == -1).all() and (want[1][1] == 0).all()
+    ix.close()
+
+
+def test_small_catalog_pads_in_pads_out(torch_cuda):
+    rng = np.random.default_rng(25)
+    P = rng.standard_normal((10, 64), dtype=np.float32)
+    q = rng.standard_normal((2, 64), dtype=np.float32)
+    ix = DeviceIndex(P)
+    cand, rel = searched(ix, q, 16)
+    assert (cand[:, 10:] == -1).all()
+    want = check(ix, P, cand, rel, 16, 0.5)
+    assert (want[0][:, :10] >= 0).all() and (want[0][:, 10:] == -1).all() and (want[1][:, 10:] == 0).all()
+    ix.close()
+
+
+# ---------------------------------------------------------------- the relevance: unsorted, NaN, ties, duplicates
+def test_unsorted_relevance(torch_cuda):
+    """Cross-encoder style logits in [-8, 8], in an order unrelated to the retrieval order."""
+    P, q = clustered(26, 600, 64, 3)
+    ix = DeviceIndex(P)
+    cand, _ = searched(ix, q, 70)
+    rng = np.random.default_rng(26)
+    rel = rng.uniform(-8, 8, cand.shape).astype(np.float32)
+    rel[:, 0] = -7.5  # position 0 is not the maximum
+    for lam in (1.0, 0.5):
+        want = check(ix, P, cand, rel, 25, lam)
+        for i in range(3):
+            assert want[0][i, 0] == cand[i, int(np.argmax(rel[i]))] and want[1][i, 0] == rel[i].max()
+    shuffled = np.stack([rng.permutation(r) for r in searched(ix, q, 70)[1]])
+    check(ix, P, cand, shuffled, 25, 0.5)
+    ix.close()
+
+
+def test_nan_relevance_sorts_last_in_position_order(torch_cuda):
+    P, q = clustered(27, 600, 64, 2)
+    ix = DeviceIndex(P)
+    cand, rel = searched(ix, q, 12)
+    rel[:, 3] = np.nan
+    rel[:, 8] = np.nan
+    for lam in (1.0, 0.5):
+        want = check(ix, P, cand, rel, 12, lam)
+        np.testing.assert_array_equal(want[0][:, 10:], cand[:, [3, 8]])
+        assert np.isnan(want[1][:, 10:]).all() and not np.isnan(want[1][:, :10]).any()
+    check(ix, P, cand, rel, 11, 0.5)
+    ix.close()
+
+
+def test_ties_are_decided_by_position(torch_cuda):
+    """Candidates that are one identical row with one identical score: the first pick is the copy at the lowest
+    position, the copies are taken in position order, and at lambda = 0.5 a copy's value drops to about zero once one
+    copy is selected (its similarity to it is 1), below every distinct row of a list of logits."""
+    rng = np.random.default_rng(28)
+    P, base = tie_block_catalog(rng, 1000, 64, draw_f32=True)
+    q = (base + np.float32(0.05) * rng.standard_normal(64, dtype=np.float32))[None, :]
+    ix = DeviceIndex(P)
+    cand, rel = searched(ix, q, 100)
+    copies = np.flatnonzero((P == base).all(axis=1))
+    assert np.isin(cand[0], copies).sum() >= 30  # the list is full of the tie block
+    for lam in (1.0, 0.5, 0.0):
+        check(ix, P, cand, rel, 50, lam)
+    # 40 copies with one logit among 24 distinct rows with lower ones
+    p_hat = ref.stored_rows(P)
+    others = np.flatnonzero(np.abs(p_hat @ p_hat[copies[0]]) < 0.5)[:24]  # neither copies nor the rows beside them
+    mixed = np.concatenate([copies[:40], others])[rng.permutation(64)][None, :].astype(np.int64)
+    is_copy = np.isin(mixed[0], copies)
+    logit = np.where(is_copy, np.float32(2.5), rng.uniform(2.2, 2.4, 64).astype(np.float32))[None, :].astype(np.float32)
+    want = check(ix, P, mixed, logit, 64, 0.5)
+    order = [int(np.flatnonzero(mixed[0] == r)[0]) if not np.isin(r, copies) else -1 for r in want[0][0]]
+    assert want[0][0, 0] == mixed[0, np.flatnonzero(is_copy)[0]]        # the first copy by position
+    assert all(o >= 0 for o in order[1:25]) and all(o < 0 for o in order[25:])  # then every distinct row, then the copies
+    np.testing.assert_array_equal(want[0][0, 25:], mixed[0, np.flatnonzero(is_copy)[1:]])  # ... in position order
+    ix.close()
+
+
+def test_a_row_listed_twice_is_two_candidates(torch_cuda):
+    P, q = clustered(29, 600, 64, 2)
+    ix = DeviceIndex(P)
+    cand, rel = searched(ix, q, 20)
+    cand[:, 7] = cand[:, 0]
+    rel[:, 7] = rel[:, 0]
+    for lam in (1.0, 0.5):
+        want = check(ix, P, cand, rel, 20, lam)
+        assert (np.sort(want[0], axis=1) == np.sort(cand, axis=1)).all()
+    np.testing.assert_array_equal(check(ix, P, cand, rel, 20, 1.0)[0][:, :2], cand[:, [0, 7]])
+    ix.close()
+
+
+# ---------------------------------------------------------------- argument errors
+def test_argument_errors_launch_nothing(torch_cuda):
+    P, q = clustered(30, 600, 64, 2)
+    ix = DeviceIndex(P)
+    idx, sc = ix.search(q, 16)
+    out_idx = torch.full((2, 16), -7, dtype=torch.int64, device=ix.device)
+    out_rel = torch.full((2, 16), -7.0, dtype=torch.float32, device=ix.device)
+    for lam in (-0.1, 1.5, math.nan):
+        with pytest.raises(_native.IcrecError, match=r"status -1.*lambda"):
+            ix.mmr_select_into(idx, sc, 4, lam, out_idx, out_rel)
+    with pytest.raises(_native.IcrecError, match=r"status -1.*top_k"):
+        ix.mmr_select_into(idx, sc, 17, 0.5, out_idx, out_rel)
+    wide = torch.zeros((2, 129), dtype=torch.int64, device=ix.device)
+    with pytest.raises(_native.IcrecError, match="bad mmr_select shape"):
+        ix.mmr_select_into(wide, wide.float(), 4, 0.5, out_idx, out_rel)
+    big = torch.empty(1 << 20, dtype=torch.uint8, device=ix.device)
+    with pytest.raises(_native.IcrecError, match=r"status -1.*k must"):
+        ix.mmr_select_into(wide, wide.float(), 4, 0.5, out_idx, out_rel, ws=big)
+    need = int(_native.lib().icrec_mmr_select_workspace_bytes(ix._h, 2, 16))
+    assert need >= 2 * 16 * 16 * 4
+    with pytest.raises(_native.IcrecError, match=r"status -3.*workspace"):
+        ix.mmr_select_into(idx, sc, 4, 0.5, out_idx, out_rel, ws=big[:need - 1])
+    torch.cuda.synchronize()
+    assert (out_idx == -7).all() and (out_rel == -7.0).all()  # nothing ran
+    ix.mmr_select_into(idx, sc, 4, 0.5, out_idx[:, :4].contiguous(), out_rel[:, :4].contiguous(), ws=big[:need])
+    torch.cuda.synchronize()
+    ix.close()
+
+
+# ---------------------------------------------------------------- graph capture
+def test_captured_search_plus_mmr_follows_the_query_buffer(torch_cuda):
+    P, q = clustered(31, 600, 384, 2)
+    ix = DeviceIndex(P)
+    lib = _native.lib()
+    k, top_k, lam = 48, 12, 0.5
+    qd = torch.from_numpy(q[:1].copy()).to(ix.device)
+    idx = torch.empty((1, k), dtype=torch.int64, device=ix.device)
+    sc = torch.empty((1, k), dtype=torch.float32, device=ix.device)
+    out_idx = torch.empty((1, top_k), dtype=torch.int64, device=ix.device)
+    out_rel = torch.empty((1, top_k), dtype=torch.float32, device=ix.device)
+    ws = torch.empty(int(lib.icrec_search_workspace_bytes(ix._h, 1, k)), dtype=torch.uint8, device=ix.device)
+    mws = torch.empty(int(lib.icrec_mmr_select_workspace_bytes(ix._h, 1, k)), dtype=torch.uint8, device=ix.device)
+
+    def both():
+        ix.search_into(qd, k, None, None, idx, sc, ws=ws)
+        ix.mmr_select_into(idx, sc, top_k, lam, out_idx, out_rel, ws=mws)
+
+    both()  # first launches outside the capture
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        both()
+    p_hat = ref.stored_rows(P)
+    lists = []
+    for i in (0, 1):
+        qd.copy_(torch.from_numpy(q[i:i + 1].copy()))
+        out_idx.fill_(-7)
+        g.replay()
+        torch.cuda.synchronize()
+        want = ref.mmr_select(p_hat, *oracle.search(q[i:i + 1], P, k), top_k, lam)
+        np.testing.assert_array_equal(out_idx.cpu().numpy(), want[0])
+        np.testing.assert_array_equal(bits(out_rel.cpu().numpy()), bits(want[1]))
+        lists.append(want[0])
+    assert not np.array_equal(lists[0], lists[1])
+    ix.close()
+
+
+# ---------------------------------------------------------------- composition with exclusions and facets
+def test_search_diverse_with_exclusions_and_facets(torch_cuda):
+    P, q = clustered(32, 600, 64, 4)
+    rng = np.random.default_rng(32)
+    F = rng.integers(0, 5, (600, 2)).astype(np.uint8)
+    ix = DeviceIndex(P)
+    ix.set_facets(F)
+    excl = [sorted(rng.choice(600, 30, replace=False).tolist()) for _ in range(4)]
+    allow = [[[0, 1, 2], None], None, [[3], [1]], [[], None]]
+    masks = facet_masks(allow, 4, 2, ix.device)
+    got = ix.search_diverse(q, 30, 0.5, 60, exclude=excl, allow=masks)
+    # the oracle's search over the admissible rows: the exclusions united with every row a mask refuses
+    full = []
+    for i, a in enumerate(allow):
+        bad = np.zeros(600, bool)
+        if a is not None:
+            for f, values in enumerate(a):
+                if values is not None:
+                    bad |= ~np.isin(F[:, f], values)
+        full.append(sorted(set(excl[i]) | set(np.flatnonzero(bad).tolist())))
+    cand, rel = oracle.search(q, P, 60, full)
+    want = ref.mmr_select(ref.stored_rows(P), cand, rel, 30, 0.5)
+    np.testing.assert_array_equal(got[0].cpu().numpy(), want[0])
+    np.testing.assert_array_equal(bits(got[1].cpu().numpy()), bits(want[1]))
+    assert (want[0][3] == -1).all() and 0 < (want[0][2] >= 0).sum() < 30 == (want[0][0] >= 0).sum()
+    for i in range(4):
+        assert not set(want[0][i].tolist()) & set(full[i])
+    ix.close()

@@ -1,0 +1,135 @@
+"""Recommender.recommend(..., diversity=, candidates=) end to end on the GPU, on the synthetic 2-layer model directory
+and 700-product catalog of the facet recommender test: a diversified request equals tests/mmr_reference.py applied to
+the `candidates`-wide plain result, bit for bit, and diversity None / 0 is today's request."""
+from __future__ import annotations
+
+import json
+import math
+
+import numpy as np
+import pytest
+
+from instacart_next_order_recommendation_amd import synthetic as syn
+from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
+from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender
+from tests import mmr_reference as ref
+from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def rec(tmp_path_factory, torch_cuda):
+    tmp = tmp_path_factory.mktemp("mmr_rec")
+    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
+    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
+    corpus_path = tmp / "processed" / "eval_corpus.json"
+    corpus_path.parent.mkdir()
+    corpus_path.write_text(json.dumps(syn.synthetic_catalog(700)))
+    r = MonitoredRecommender(model_dir, corpus_path, use_index=False)
+    assert r._fast is not None and r._index.n_facets == 2
+    return r
+
+
+@pytest.fixture(scope="module")
+def p_hat(rec):
+    return ref.stored_rows(rec.product_embeddings, rec._index.storage)
+
+
+QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
+
+
+def expected(rec, p_hat, wide, top_k, lam):
+    """The reference's re-selection of a plain (product id, score) result."""
+    cand = np.asarray([[rec._pid_to_row[p] for p, _ in wide]], np.int64)
+    rel = np.asarray([[s for _, s in wide]], np.float32)  # (a float32 score survives the trip through a Python float)
+    idx, out = ref.mmr_select(p_hat, cand, rel, top_k, lam)
+    return [(rec.product_ids[int(i)], float(s)) for i, s in zip(idx[0], out[0]) if i >= 0]
+
+
+def test_no_diversity_is_the_plain_request_on_the_graph_path(rec, monkeypatch):
+    fast = rec._fast_path()
+    calls = []
+    real_run = type(fast).run
+
+    def run(self, *a, **kw):
+        calls.append(1)
+        return real_run(self, *a, **kw)
+
+    monkeypatch.setattr(type(fast), "run", run)
+    for q in QUERIES:
+        plain = rec.recommend(q, 20)
+        assert rec.recommend(q, 20, diversity=None) == plain
+        assert rec.recommend(q, 20, diversity=0) == plain
+        assert rec.recommend(q, 20, diversity=0.0, candidates=64) == plain
+    assert len(calls) == 4 * len(QUERIES)
+    rec.recommend(QUERIES[0], 20, diversity=0.5)  # a diversified request takes the un-captured path
+    assert len(calls) == 4 * len(QUERIES)
+    assert rec.recommend_batch(QUERIES, 20, diversity=0) == rec.recommend_batch(QUERIES, 20)
+
+
+def test_diversified_request_equals_the_reference(rec, p_hat):
+    differs = 0
+    for q in QUERIES:
+        wide = rec.recommend(q, 80)
+        assert len(wide) == 80
+        got = rec.recommend(q, 20, diversity=0.5)  # candidates default to 4 * top_k
+        assert got == expected(rec, p_hat, wide, 20, 0.5)
+        assert got[0] == wide[0] and got != wide[:20]
+        differs += {p for p, _ in got} != {p for p, _ in wide[:20]}
+        assert rec.recommend(q, 20, diversity=0.5, candidates=80) == got
+        assert rec.recommend(q, 20, diversity=0.25, candidates=50) == expected(rec, p_hat, wide[:50], 20, 0.75)
+        assert rec.recommend(q, 20, diversity=1, candidates=128) == expected(rec, p_hat, rec.recommend(q, 128), 20, 0.0)
+    assert differs > 0  # lists are changed, not only reordered
+
+
+def test_composes_with_departments_and_exclusions(rec, p_hat):
+    d = rec.departments[0]
+    for q in QUERIES[:3]:
+        drop = {p for p, _ in rec.recommend(q, 20, departments=[d])[:3]}
+        wide = rec.recommend(q, 40, exclude_product_ids=drop, departments=[d])
+        got = rec.recommend(q, 10, exclude_product_ids=drop, departments=[d], diversity=0.5)
+        assert got and got == expected(rec, p_hat, wide, 10, 0.5)
+        assert not drop & {p for p, _ in got}
+        assert all(rec.pid_to_text[p].endswith(f". Department: {d}.") for p, _ in got)
+    assert rec.recommend(QUERIES[0], 10, aisles=[], diversity=0.5) == []
+
+
+def test_batch_equals_single_calls(rec):
+    excl = [None, {"1", "2", "3"}, None, {"10"}, None]
+    departments = [None, None, [rec.departments[1]], None, [rec.departments[0], rec.departments[2]]]
+    batch = rec.recommend_batch(QUERIES, 20, excl, departments=departments, diversity=0.4, candidates=70)
+    for i, q in enumerate(QUERIES):
+        assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], departments=departments[i], diversity=0.4,
+                                         candidates=70), i
+    assert batch != rec.recommend_batch(QUERIES, 20, excl, departments=departments)
+    timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 20, excl, departments=departments, diversity=0.4, candidates=70)
+    assert timed == batch and enc_ms > 0 and sim_ms > 0
+
+
+def test_monitored_fills_last_metrics(rec):
+    rec.last_metrics = None
+    got = rec.recommend(QUERIES[0], 20, user_id="u7", diversity=0.5)
+    m = rec.last_metrics
+    assert m is not None and m.user_id == "u7" and m.num_recommendations == len(got) == 20
+    assert m.top_score == got[0][1] and m.similarity_compute_time_ms > 0 and m.query_embedding_time_ms > 0
+
+
+def test_bad_arguments_raise_before_any_gpu_work(rec, monkeypatch):
+    def no_gpu(*a, **kw):
+        raise AssertionError("GPU work before the argument check")
+
+    monkeypatch.setattr(rec, "_encode_search", no_gpu)
+    monkeypatch.setattr(type(rec._fast_path()), "run", no_gpu)
+    for bad in (-0.1, 1.5, math.nan):
+        with pytest.raises(ValueError, match="diversity"):
+            rec.recommend(QUERIES[0], 20, diversity=bad)
+        with pytest.raises(ValueError, match="diversity"):
+            rec.recommend_batch(QUERIES[:2], 20, diversity=bad)
+        with pytest.raises(ValueError, match="diversity"):
+            rec.recommend_batch_timed(QUERIES[:2], 20, diversity=bad)
+    for bad in (19, 129):
+        with pytest.raises(ValueError, match="candidates"):
+            rec.recommend(QUERIES[0], 20, diversity=0.5, candidates=bad)
+        with pytest.raises(ValueError, match="candidates"):
+            rec.recommend_batch(QUERIES[:2], 20, diversity=0.5, candidates=bad)
