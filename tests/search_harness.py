@@ -1,7 +1,8 @@
 """Shared by the search GPU tests (test_search_gpu, test_search_dims_gpu, test_sharded_gpu, the search tests of
 test_baseline_sizes_gpu): the imports and the GPU fixture, the check of an index against the oracle, the random
 exclusion lists (one function per draw sequence), shard cutting, the tie-block catalog, the launch timers, the
-properties of a result list and the memoised bench catalog.  One definition each; importing this needs no GPU."""
+properties of a result list, the memoised bench catalog, the launch plans and the selection in numpy, and which rows
+a query's facet masks admit.  One definition each; importing this needs no GPU."""
 from __future__ import annotations
 
 import functools
@@ -82,14 +83,17 @@ def tiled_plan(n_rows, Q, k, n_cu):
     return variant, BM, BN, n_qtiles, tiles_per_chunk, n_chunks
 
 
-def select_from_scores(scores, k, excl=None, row_offset=0):
+def select_from_scores(scores, k, excl=None, row_offset=0, admit=None):
     """The library's selection on a complete [Q, n] float32 score matrix: per query the k best rows that its list
     excl[i] (local rows, as oracle.search takes them) does not name, score descending and row ascending among equal
     scores -> (idx int64 [Q, k], score float32 [Q, k]), idx = row_offset + row, padded with (-1, 0) where fewer than k
     rows are admissible - oracle.search's conventions.  Each (score, row) becomes one integer that grows with the
-    score and, among equal scores, falls with the row; -0 counts as +0; scores must not be NaN."""
+    score and, among equal scores, falls with the row; -0 counts as +0; scores must not be NaN.  admit: bool [Q, n],
+    False = the row is inadmissible for that query, exactly like a row its exclusion list names (facet masks over a
+    large catalog, where the rejected rows as lists would be millions of Python ints)."""
     s = np.ascontiguousarray(scores, dtype=np.float32)
     Q, n = s.shape
+    assert admit is None or (admit.dtype == np.bool_ and admit.shape == (Q, n)), "admit: bool [Q, n]"
     idx = np.full((Q, k), -1, np.int64)
     sc = np.zeros((Q, k), np.float32)
     m = min(k, n)
@@ -103,6 +107,8 @@ def select_from_scores(scores, k, excl=None, row_offset=0):
             for i in range(blk.shape[0]):
                 e = np.asarray(sorted(set(int(v) for v in excl[lo + i])), np.int64)
                 keys[i, e[(e >= 0) & (e < n)]] = 0  # below every real key
+        if admit is not None:
+            keys[~admit[lo:lo + 64]] = 0
         top = np.sort(np.partition(keys, n - m, axis=1)[:, n - m:], axis=1)[:, ::-1]
         real = top != 0
         rows = (np.uint64(0xFFFFFFFF) - (top & np.uint64(0xFFFFFFFF))).astype(np.int64)
@@ -149,6 +155,67 @@ def first_pass_offers(tile_scores, k, BM):
         t = distinct[m - 1] if distinct.size >= m else -np.inf
         offered[group == g] = mine >= t
     return offered
+
+
+# ---------------------------------------------------------------- facets: which rows a query's allow masks admit
+def admitted_matrix(F, masks):
+    """include/icrec.h's definition of a faceted search: row r is admissible for query i iff, for EVERY facet f, bit
+    v & 31 of word v >> 5 of masks[i, f] is set, v = F[r, f].  F: uint8 [n, n_facets], masks: uint32 [Q, n_facets, 8]
+    (search.facet_masks without a device) -> bool [Q, n]."""
+    F, masks = np.asarray(F), np.asarray(masks)
+    assert F.dtype == np.uint8 and F.ndim == 2 and masks.dtype == np.uint32 and masks.shape[1:] == (F.shape[1], 8)
+    ok = np.ones((masks.shape[0], F.shape[0]), bool)
+    for f in range(F.shape[1]):
+        v = F[:, f].astype(np.int64)
+        word, bit = v >> 5, (v & 31).astype(np.uint32)
+        for lo in range(0, masks.shape[0], 256):  # blocks of queries: 256 x n words at a time
+            ok[lo:lo + 256] &= ((masks[lo:lo + 256, f][:, word] >> bit[None, :]) & np.uint32(1)).astype(bool)
+    return ok
+
+
+def admitted_per_tile(admit_row, BM, tiles_per_chunk):
+    """One query's admitted rows (bool [n]) counted per row tile of the blocks a tiled kernel walks: int [n_chunks,
+    tiles_per_chunk], entry [c, j] = admitted rows in tile c * tiles_per_chunk + j of BM rows (0 for a tile past the
+    catalog's last).  Several queries at once, bool [..., n], give [..., n_chunks, tiles_per_chunk].  Computed from the
+    inputs only: the preconditions of the faceted multi-tile tests."""
+    admit_row = np.asarray(admit_row, bool)
+    n = admit_row.shape[-1]
+    n_tiles = (n + BM - 1) // BM
+    n_chunks = (n_tiles + tiles_per_chunk - 1) // tiles_per_chunk
+    padded = np.zeros(admit_row.shape[:-1] + (n_chunks * tiles_per_chunk * BM,), bool)
+    padded[..., :n] = admit_row
+    return padded.reshape(admit_row.shape[:-1] + (n_chunks, tiles_per_chunk, BM)).sum(axis=-1)
+
+
+# ---------------------------------------------------------------- the filter pass's launch plan, in numpy
+FILTER_MIN_Q, RES_QCAP_MAX_ROUNDS, LDS_MAX = 256, 64, 160 * 1024   # csrc/search.hip's constants of the same names
+
+
+def filter_list_len(k):
+    """Length of the filter pass's candidate lists for a search of k: k + 12, rounded up to a multiple of 8."""
+    return (k + 12 + 7) & ~7
+
+
+def filter_plan(n_rows, Q, n_cu, resident):
+    """csrc/search.hip's make_filter_plan, the part that cuts the rows: the resident form (dim 384) walks rounds of 256
+    rows with one block per CU, the staged form tiles of 128 rows with two; 64 queries per tile in both
+    -> (BM, n_qtiles, tiles_per_chunk, n_chunks)."""
+    BM = 256 if resident else 128
+    n_qtiles = (Q + 63) // 64
+    n_row_tiles = (n_rows + BM - 1) // BM
+    want = min(max((1 if resident else 2) * n_cu // n_qtiles, 1), 256)
+    want = min(want, n_row_tiles)
+    tiles_per_chunk = (n_row_tiles + want - 1) // want
+    return BM, n_qtiles, tiles_per_chunk, (n_row_tiles + tiles_per_chunk - 1) // tiles_per_chunk
+
+
+def resident_lds(kp, facet):
+    """Dynamic LDS of the resident filter pass at list length kp (resident_smem / TopK<CfgRes, true, FACET>::bytes in
+    csrc/search.hip): two query planes of 64 x 768 B | 64 thresholds (8 B) and queue counters (4 B) | 16 B of flags |
+    FACET: 64 queries' masks of 2 x 8 words and 2 x 256 facet words of 2 B | 64 lists of kp keys | 64 queues sized for
+    a block of ONE round: 32 slots up to kp = 32, else 16.  The pass is taken while this is at most LDS_MAX."""
+    return 2 * 64 * 768 + 64 * (8 + 4) + 16 + (64 * 2 * 8 * 4 + 2 * 256 * 2 if facet else 0) + 64 * kp * 8 \
+        + 64 * (32 if kp <= 32 else 16) * 8
 
 
 # ---------------------------------------------------------------- random exclusion lists, one per draw sequence

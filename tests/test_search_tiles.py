@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 
 from oracle import oracle
-from tests.search_harness import (direction_catalog, first_pass_offers, select_from_scores, tie_run_catalog, tiled_plan,
+from instacart_next_order_recommendation_amd.search import facet_masks
+from tests.search_harness import (admitted_matrix, admitted_per_tile, direction_catalog, filter_list_len, filter_plan,
+                                  first_pass_offers, resident_lds, select_from_scores, tie_run_catalog, tiled_plan,
                                   warm_tile_beaters)
 
 
@@ -80,6 +82,87 @@ def test_select_from_scores_is_the_oracles_ranking():
     np.testing.assert_array_equal(got[1], want[1])
     z = np.array([[0.0, -0.0, 0.0, -1.0, -0.0]], np.float32)
     assert select_from_scores(z, 4)[0].tolist() == [[0, 1, 2, 4]]
+
+
+def test_select_from_scores_admit_is_an_exclusion_list():
+    """admit = False on a row is that row in the query's exclusion list: the same result from either spelling, alone
+    and on top of other exclusions, with queries that admit nothing, everything, and fewer rows than k; without admit
+    nothing changes (the test above)."""
+    rng = np.random.default_rng(11)
+    n, nq = 517, 70                                               # two blocks of 64 queries, the second partial
+    s = rng.standard_normal((nq, n)).astype(np.float32)
+    s[:, 40:60] = s[:, 39:40]                                     # equal scores: row order among the admitted copies
+    admit = rng.random((nq, n)) < 0.3
+    admit[0], admit[1], admit[2] = False, True, False
+    admit[2, [41, 45, 500]] = True                                # 3 rows, fewer than any k below
+    admit[65, 40:60:2] = False
+    other = [sorted(rng.choice(n, 12, replace=False).tolist()) if i % 3 else [] for i in range(nq)]
+    as_lists = [np.flatnonzero(~a).tolist() for a in admit]
+    both = [sorted(set(a) | set(b)) for a, b in zip(as_lists, other)]
+    for k in (1, 20, 128):
+        for excl, lists in ((None, as_lists), (other, both)):
+            got = select_from_scores(s, k, excl, row_offset=7, admit=admit)
+            want = select_from_scores(s, k, lists, row_offset=7)
+            np.testing.assert_array_equal(got[0], want[0])
+            np.testing.assert_array_equal(got[1], want[1])
+        assert (got[0][0] == -1).all() and (got[0][2, 3:] == -1).all() and (got[0][2, :min(k, 3)] >= 7).all()
+    open_ = select_from_scores(s, 20, other, admit=np.ones((nq, n), bool))
+    np.testing.assert_array_equal(open_[0], select_from_scores(s, 20, other)[0])
+    with pytest.raises(AssertionError):
+        select_from_scores(s, 20, admit=admit[:, :-1])
+
+
+def test_admitted_matrix_is_icrec_hs_definition():
+    """Against facet_masks (which sets bit v & 31 of word v >> 5 for an admitted value v): the bit edges 0, 31, 32 and
+    255 in either facet, both facets at once, open and all-zero masks, and a one-facet index."""
+    F = np.array([[0, 0], [31, 0], [32, 1], [255, 1], [0, 31], [31, 32], [32, 255], [255, 255], [7, 7], [33, 30]], np.uint8)
+    allow = [[[0], None], [[31], None], [[32], None], [[255], None],
+             [None, [0]], [None, [31]], [None, [32]], [None, [255]],
+             [[0, 255], [255, 0]], [[31, 32], [1, 32]], None, [[], []], [None, []], [[1, 30, 33, 63, 254], None]]
+    got = admitted_matrix(F, facet_masks(allow, len(allow), 2))
+    want = np.array([[(a is None or ((a[0] is None or int(v0) in a[0]) and (a[1] is None or int(v1) in a[1])))
+                      for v0, v1 in F] for a in allow])
+    np.testing.assert_array_equal(got, want)
+    assert got.dtype == np.bool_ and got.shape == (len(allow), len(F))
+    assert got[0].tolist() == [True, False, False, False, True, False, False, False, False, False]   # aisle 0 only
+    assert got[8].tolist() == [True] + [False] * 6 + [True, False, False] and got[13].tolist() == [False] * 9 + [True]
+    assert got[10].all() and not got[11].any() and not got[12].any()
+    one = np.ascontiguousarray(F[:, :1])
+    allow1 = [[[0]], [[31]], [[32]], [[255]], None, [[]], [[31, 32, 255]]]
+    got1 = admitted_matrix(one, facet_masks(allow1, len(allow1), 1))
+    want1 = np.array([[a is None or int(v) in a[0] for v in one[:, 0]] for a in allow1])
+    np.testing.assert_array_equal(got1, want1)
+    # more queries than one block of 256: every block is filled
+    many = admitted_matrix(F, facet_masks([allow[i % len(allow)] for i in range(600)], 600, 2))
+    np.testing.assert_array_equal(many, want[np.arange(600) % len(allow)])
+
+
+def test_admitted_per_tile_counts_by_hand():
+    """22 rows in tiles of 4, blocks of 3 tiles: 6 tiles, 2 blocks, the last tile of 2 rows."""
+    a = np.zeros(22, bool)
+    a[[0, 3, 4, 11, 12, 13, 14, 15, 21]] = True
+    assert admitted_per_tile(a, 4, 3).tolist() == [[2, 1, 1], [4, 0, 1]]
+    assert admitted_per_tile(a[:20], 4, 3).tolist() == [[2, 1, 1], [4, 0, 0]]      # the sixth tile does not exist
+    assert admitted_per_tile(a, 4, 4).tolist() == [[2, 1, 1, 4], [0, 1, 0, 0]]
+    both = admitted_per_tile(np.stack([a, ~a]), 4, 3)               # several queries at once
+    assert both.tolist() == [[[2, 1, 1], [4, 0, 1]], [[2, 3, 3], [0, 4, 1]]]
+
+
+def test_filter_plan_pins():
+    """(n_rows, Q) at 256 CUs -> (BM, n_qtiles, rounds or tiles per block, blocks), worked out by hand; the list
+    lengths and the resident pass's LDS at the edge where a faceted search stops filtering."""
+    # 1,024 queries: 16 query tiles.  Resident: 16 blocks wanted, 50 rounds of 256 rows -> 4 per block -> 13 blocks.
+    assert filter_plan(12_773, 1024, 256, True) == (256, 16, 4, 13)
+    # staged: 32 wanted, 100 tiles of 128 rows -> 4 per block -> 25 blocks
+    assert filter_plan(12_773, 1024, 256, False) == (128, 16, 4, 25)
+    # 4,096 queries: 64 query tiles, 4 blocks wanted; 264 rounds -> 66 per block, past RES_QCAP_MAX_ROUNDS = 64
+    assert filter_plan(67_557, 4096, 256, True) == (256, 64, 66, 4)
+    assert filter_plan(49_688, 1024, 256, True) == (256, 16, 13, 15)
+    assert [filter_list_len(k) for k in (1, 4, 5, 20, 40, 84, 85, 92, 93, 116, 117)] == \
+        [16, 16, 24, 32, 56, 96, 104, 104, 112, 128, 136]
+    assert resident_lds(96, True) == 161_552 <= 160 * 1024 < resident_lds(104, True) == 165_648
+    assert resident_lds(104, False) == 160_528 <= 160 * 1024 < resident_lds(112, False)
+    assert resident_lds(32, False) == 98_304 + 784 + 64 * 32 * 8 + 64 * 32 * 8
 
 
 def test_first_pass_offers_by_hand():
