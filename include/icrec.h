@@ -437,6 +437,66 @@ ICREC_API int icrec_mmr_select(icrec_index* idx, const int64_t* cand_idx_dev, co
                      int64_t* out_idx_dev, float* out_rel_dev,
                      void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Boosting each query's listed rows on a search result ("buy it again"): rank the union of a query's candidates and a
+ * list of rows the caller names - the products a user has bought before - with a per-row weight added to the listed
+ * rows' cosine scores, entirely on the device. */
+#define ICREC_MAX_BOOSTS 1024   /* listed rows per query */
+
+/* Scratch bytes of icrec_boost_select (0 for a NULL index, n_queries < 1 or max_boosts outside [0, ICREC_MAX_BOOSTS]):
+ * the normalised queries and one 64-bit word per query and listed entry. */
+ICREC_API size_t icrec_boost_select_workspace_bytes(const icrec_index* idx, int32_t n_queries, int32_t max_boosts);
+
+/* The best top_k of each query's listed rows and candidates under the adjusted score a(r) = cos(r) + w(r).
+ *   q_dev           float[n_queries, dim]     the queries icrec_search takes (not normalised)
+ *   cand_idx_dev    int64[n_queries, k]       icrec_search's out_idx: global rows, -1 pads; or NULL (with cand_score_dev):
+ *   cand_score_dev  float[n_queries, k]       icrec_search's out_score                     no candidates
+ *   boost_off_dev   int32[n_queries+1]        CSR offsets into boost_rows_dev / boost_w_dev
+ *   boost_rows_dev  int32[...]                each query's listed LOCAL rows, ascending and unique within its segment
+ *                                             (the format of icrec_search's exclusion lists)
+ *   boost_w_dev     float[...]                their weights; NULL: every weight is 0
+ *   max_boosts      in [0, ICREC_MAX_BOOSTS]  only the first max_boosts entries of a segment are read
+ *   excl_idx_dev / excl_off_dev, allow_dev    the exclusion lists and facet masks of icrec_search_faceted, or NULL
+ *   out_idx_dev     int64[n_queries, top_k]   row_offset + row, best first; -1 pads
+ *   out_score_dev   float[n_queries, top_k]   the adjusted scores; 0 at pads
+ * The definition, which the result follows bit for bit:
+ *   Lists.  Query i's list is entries [boost_off[i], boost_off[i+1]) of boost_rows_dev, of which the first max_boosts
+ *     are read; a segment whose end lies before its start is empty.  A list that is not ascending and unique gives an
+ *     unspecified result, but a memory-safe one.
+ *   Validity of a listed entry.  0 <= row < n_rows, the row is not in the query's exclusion segment, and with allow_dev
+ *     the query's facet masks admit it: icrec_search_faceted's rules.  An invalid entry is never returned and its row is
+ *     never read.
+ *   Effective weight.  w_eff = w if w >= 0 (+inf included), else 0: a NaN or a negative weight counts as 0 (the weights
+ *     live on the device, where the host cannot refuse them; a(r) >= cos(r) then holds for every input).
+ *   Cosine.  The query is normalised as icrec_search normalises it; cos is the fp32 chain s = 0; for j = 0 .. dim-1:
+ *     s = fmaf(q_hat[j], p[j], s) over the index's STORED row (bf16 storage widened exactly): icrec_scores' bits.  The
+ *     filter planes and fragments are not used.
+ *   Adjusted score.  a = cos, bits unchanged, when w_eff == 0; otherwise a = cos + w_eff, one fp32 addition.
+ *   Candidates.  Candidate j is valid iff cand >= 0 and cand - row_offset lies in [0, n_rows) of idx.  Its score is
+ *     cand_score[j] as given; it is not computed again.  A candidate whose row is among the entries read from the
+ *     query's list (valid or not) is dropped: the listed entry stands for it.
+ *   Result.  The best top_k of {valid listed entries} and {remaining valid candidates}, ordered as icrec_search orders:
+ *     score descending compared as floats (-0 == +0), lower row first on ties; then -1 / 0.0f pads.
+ * Consequences.  With w_eff >= 0 an unlisted row among the best top_k of the whole catalog under a has fewer than
+ * top_k rows before it under plain cosine as well.  So if the candidates are icrec_search(_faceted)'s result for the same
+ * q, exclusions, masks and k >= top_k, the result is the top_k of the WHOLE catalog under a.  If all weights are 0 (or
+ * boost_w_dev is NULL) it is that search's first top_k entries, bit for bit.  Without candidates only the listed rows
+ * are ranked.  A query's result has the same bits alone and inside any batch, for every row storage.
+ * ICREC_EINVAL, before any HIP call: a NULL among idx, q_dev, boost_off_dev, the outputs, the workspace; boost_rows_dev
+ * NULL with max_boosts > 0; cand_idx_dev and cand_score_dev (excl_idx_dev and excl_off_dev) not both set or both NULL;
+ * n_queries < 1; k outside [1, ICREC_MAX_K] when there are candidates; top_k outside [1, ICREC_MAX_K], or top_k > k
+ * with candidates; max_boosts outside [0, ICREC_MAX_BOOSTS]; neither candidates nor max_boosts > 0; allow_dev on an index
+ * without facets.  ICREC_ENOMEM: workspace_bytes < icrec_boost_select_workspace_bytes.  Nothing is launched on an error.
+ * The outputs must not alias the inputs.  Asynchronous on `stream`: nothing is allocated, nothing synchronises, every
+ * launch goes to that one stream, and the call can be captured into a hipGraph.  The lists, weights and masks are read
+ * from device memory when the kernels run: a replayed graph follows what the buffers hold then. */
+ICREC_API int icrec_boost_select(icrec_index* idx, const float* q_dev, int32_t n_queries,
+                       const int64_t* cand_idx_dev, const float* cand_score_dev, int32_t k,
+                       const int32_t* boost_off_dev, const int32_t* boost_rows_dev, const float* boost_w_dev,
+                       int32_t max_boosts,
+                       const int32_t* excl_idx_dev, const int32_t* excl_off_dev, const uint32_t* allow_dev,
+                       int32_t top_k, int64_t* out_idx_dev, float* out_score_dev,
+                       void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Shard-local half of a sharded search: same as icrec_search but emits the
  * sorted partial lists as packed 64-bit keys
  *   key = (orderable(score) << 32) | (0xFFFFFFFF - global_row)
@@ -686,7 +746,8 @@ ICREC_API const char* icrec_version(void);
  *        4 = the guarded exact pass behind a filter pass (ICREC_ROWS_F32_FILTER):
  *            a few microseconds when every query was proven, a full search
  *            when the fallback ran,
- *        5 = icrec_mmr_select's similarity-matrix kernel, 6 = its selection kernel. */
+ *        5 = icrec_mmr_select's similarity-matrix kernel, 6 = its selection kernel,
+ *        7 = icrec_boost_select's scoring kernel, 8 = its selection kernel. */
 ICREC_API int icrec_timing_enable(int on);
 ICREC_API int icrec_timing_reset(void);
 ICREC_API int icrec_timing_query(int which, double* avg_ms, int64_t* n_launches);

@@ -14,6 +14,7 @@ _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libicrec.so"
 
 ICREC_MAX_K = 128
+ICREC_MAX_BOOSTS = 1024
 ICREC_MAX_FACETS = 2
 ICREC_FACET_MASK_WORDS = 8
 ICREC_MAX_SEQLEN = 512
@@ -41,6 +42,7 @@ EXPORTS = [
     "icrec_search_workspace_bytes", "icrec_search", "icrec_search_partial", "icrec_merge_topk",
     "icrec_index_set_facets", "icrec_index_facets", "icrec_search_faceted_workspace_bytes", "icrec_search_faceted",
     "icrec_mmr_select_workspace_bytes", "icrec_mmr_select",
+    "icrec_boost_select_workspace_bytes", "icrec_boost_select",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
     "icrec_cf_create", "icrec_cf_destroy", "icrec_cf_orders", "icrec_cf_items", "icrec_cf_candidates", "icrec_cf_nnz",
     "icrec_cf_tile", "icrec_cf_rank_workspace_bytes", "icrec_cf_rank", "icrec_cf_rank_all_workspace_bytes",
@@ -147,6 +149,8 @@ def lib() -> C.CDLL:
         "icrec_search_faceted": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
         "icrec_mmr_select_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_mmr_select": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, sz, vp]),
+        "icrec_boost_select_workspace_bytes": (sz, [vp, i32, i32]),
+        "icrec_boost_select": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
         "icrec_merge_topk": (C.c_int, [vp, i32, i32, i32, vp, vp, C.c_int, vp]),
         "icrec_scores": (C.c_int, [vp, vp, i32, vp, vp, sz, vp]),
         "icrec_rank_all_workspace_bytes": (sz, [vp, i32]),
@@ -240,6 +244,20 @@ def mmr_select(index_handle, cand_idx, rel, top_k: int, lam: float, out_idx, out
     Q, k = int(cand_idx.shape[0]), int(cand_idx.shape[1])
     check(lib().icrec_mmr_select(index_handle, ptr(cand_idx), ptr(rel), Q, k, int(top_k), float(lam), ptr(out_idx),
                                  ptr(out_rel), ptr(ws), ws.numel(), stream_ptr(device)), "icrec_mmr_select")
+
+
+def boost_select(index_handle, q, cand_idx, cand_score, boost_off, boost_rows, boost_w, max_boosts: int, excl_idx,
+                 excl_off, allow, top_k: int, out_idx, out_score, ws, device) -> None:
+    """icrec_boost_select on device tensors: q float32 [Q, dim], cand_idx int64 [Q, k] and cand_score float32 [Q, k] (both
+    None: no candidates), the lists as boost_off int32 [Q+1], boost_rows int32 and boost_w float32 (or None), the search's
+    exclusion CSR and allow masks or None, out_idx int64 [Q, top_k] and out_score float32 [Q, top_k] out, ws a uint8
+    scratch tensor; asynchronous on `device`'s current stream."""
+    Q = int(q.shape[0])
+    k = int(cand_idx.shape[1]) if cand_idx is not None else 0
+    check(lib().icrec_boost_select(index_handle, ptr(q), Q, ptr(cand_idx), ptr(cand_score), k, ptr(boost_off),
+                                   ptr(boost_rows), ptr(boost_w), int(max_boosts), ptr(excl_idx), ptr(excl_off), ptr(allow),
+                                   int(top_k), ptr(out_idx), ptr(out_score), ptr(ws), ws.numel(), stream_ptr(device)),
+          "icrec_boost_select")
 
 
 def timing_enable(on: bool) -> None:

@@ -27,11 +27,12 @@ from .recommender import SbertModel
 from .search import DeviceIndex
 
 
-def _evaluate(baseline, relevant_docs: dict[str, set[str]], depth: int, queries_per_pass: int | None) -> dict[str, float]:
+def _evaluate(baseline, relevant_docs: dict[str, set[str]], depth: int, queries_per_pass: int | None,
+              **pass_args) -> dict[str, float]:
     """The eight IR metrics of a baseline's top-`depth` rows, pass by pass on the device."""
     row_of = {pid: j for j, pid in enumerate(baseline.product_ids)}
     sums = []
-    for rows, qids in baseline._row_passes(depth, queries_per_pass):
+    for rows, qids in baseline._row_passes(depth, queries_per_pass, **pass_args):
         off, rel = ir_metrics.relevant_csr(qids, relevant_docs, row_of, baseline.device)
         sums.append(ir_metrics.ir_metrics_rows_raw(rows, off, rel)[0])
     if not sums:
@@ -76,26 +77,42 @@ class ContentBasedBaseline:
                 out[qid] = [self.product_ids[j] for j in idx[i] if j >= 0]
         return out
 
-    def _row_passes(self, depth: int, queries_per_pass: int | None):
+    def boost_lists(self, query_ids: list[str], boosts: dict, boost_weight) -> list[dict[int, float]]:
+        """query id -> product ids to boost (e.g. ItemItemCFBaseline's histories) -> per query {corpus row: weight},
+        what DeviceIndex.search_boosted takes.  Products outside the corpus are skipped; a list of more than
+        ICREC_MAX_BOOSTS corpus products keeps the first ICREC_MAX_BOOSTS in corpus order."""
+        if boost_weight is None or not float(boost_weight) >= 0.0:  # (a NaN fails the comparison)
+            raise ValueError(f"boosts needs a boost_weight >= 0, got {boost_weight!r}")
+        if not hasattr(self, "_row_of"):
+            self._row_of = {pid: j for j, pid in enumerate(self.product_ids)}
+        w = float(boost_weight)
+        return [{r: w for r in sorted(self._row_of[p] for p in set(boosts.get(q, ())) if p in self._row_of)[:_native.ICREC_MAX_BOOSTS]}
+                for q in query_ids]
+
+    def _row_passes(self, depth: int, queries_per_pass: int | None, boosts: dict | None = None, boost_weight=None):
         if not 1 <= depth <= _native.ICREC_MAX_K:
             raise ValueError(f"depth must be in [1, {_native.ICREC_MAX_K}]")
         query_ids = list(self.eval_queries.keys())
         step = queries_per_pass or 1024
         for s in range(0, len(query_ids), step):
             qids = query_ids[s:s + step]
+            lists = None if boosts is None else self.boost_lists(qids, boosts, boost_weight)
             emb = self.model.encode_to_device([self.eval_queries[q] for q in qids])
-            yield self._index.search(emb, depth)[0], qids
+            yield (self._index.search(emb, depth) if lists is None else self._index.search_boosted(emb, depth, lists))[0], qids
 
-    def rank_rows(self, depth: int = 100, queries_per_pass: int | None = None) -> tuple[torch.Tensor, list[str]]:
+    def rank_rows(self, depth: int = 100, queries_per_pass: int | None = None, boosts: dict | None = None,
+                  boost_weight=None) -> tuple[torch.Tensor, list[str]]:
         """(int64 [Q, depth] corpus rows on the device, best first with -1 pads; the query ids in row order): what
-        `rank_all(depth)` turns into id strings."""
-        passes = list(self._row_passes(depth, queries_per_pass))
+        `rank_all(depth)` turns into id strings.  boosts: query id -> the products to lift by boost_weight (a user's
+        earlier purchases): the ranking is then by cosine + boost_weight for those, over the whole corpus."""
+        passes = list(self._row_passes(depth, queries_per_pass, boosts, boost_weight))
         return torch.cat([r for r, _ in passes]), [q for _, qs in passes for q in qs]
 
     def evaluate(self, relevant_docs: dict[str, set[str]], depth: int = 100,
-                 queries_per_pass: int | None = None) -> dict[str, float]:
-        """compute_ir_metrics(rank_all(depth), relevant_docs) without leaving the device: the eight-metric dict."""
-        return _evaluate(self, relevant_docs, depth, queries_per_pass)
+                 queries_per_pass: int | None = None, boosts: dict | None = None, boost_weight=None) -> dict[str, float]:
+        """compute_ir_metrics(rank_all(depth), relevant_docs) without leaving the device: the eight-metric dict.
+        boosts / boost_weight: as rank_rows takes them."""
+        return _evaluate(self, relevant_docs, depth, queries_per_pass, boosts=boosts, boost_weight=boost_weight)
 
 
 def _read_csv_columns(path: Path, names: tuple[str, ...]):

@@ -9,12 +9,14 @@ ignored; a missing model directory or corpus file is an error).
     python -m instacart_next_order_recommendation_amd --config configs/inference.yaml [--query "..."] [--json]
                                                       [--aisle NAME]... [--department NAME]...
                                                       [--diversity FLOAT] [--candidates INT]
+                                                      [--boost PID[=W]]... [--boost-weight W] [--only-boosted]
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
 and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
 processed_dir, data_dir, model_name, content_only, cf_only).
 
     python -m instacart_next_order_recommendation_amd baselines --config configs/baselines.yaml [--cf-only]
+                                                                [--reorder-boost W]
 """
 from __future__ import annotations
 
@@ -76,6 +78,9 @@ def baselines_main(argv) -> int:
     ap.add_argument("--model-name", type=Path, default=None, help="overrides model_name: a LOCAL SentenceTransformer directory")
     ap.add_argument("--content-only", action="store_true", help="only the content-based baseline")
     ap.add_argument("--cf-only", action="store_true", help="only the collaborative-filtering baseline")
+    ap.add_argument("--reorder-boost", type=float, default=None, metavar="W",
+                    help="a third block: the content-based ranking with W added to the scores of the products of the "
+                         "user's earlier orders (the histories the CF baseline reads)")
     args = ap.parse_args(argv)
     path = args.config or (Path("configs/baselines.yaml") if Path("configs/baselines.yaml").exists() else None)
     raw = (yaml.safe_load(Path(path).read_text()) or {}) if path else {}
@@ -86,6 +91,8 @@ def baselines_main(argv) -> int:
     content_only, cf_only = args.content_only or bool(cfg["content_only"]), args.cf_only or bool(cfg["cf_only"])
     if not (processed_dir / "eval_queries.json").exists():
         raise SystemExit(f"{processed_dir} holds no eval_queries.json (this build never downloads one)")
+    if args.reorder_boost is not None and (cf_only or not args.reorder_boost >= 0.0):
+        raise SystemExit("--reorder-boost takes a weight >= 0 and needs the content-based baseline (not --cf-only)")
 
     from .baselines import ContentBasedBaseline, ItemItemCFBaseline
     from .ir_metrics import load_eval_data
@@ -100,7 +107,27 @@ def baselines_main(argv) -> int:
     if not content_only:
         cf = ItemItemCFBaseline(data_dir, processed_dir)
         print_metrics("Collaborative filtering (item-item)", cf.evaluate(relevant))
+    if args.reorder_boost is not None:
+        histories = cf.eval_order_to_history if not content_only else ItemItemCFBaseline.load_arrays(data_dir, processed_dir)["histories"]
+        print_metrics(f"Content-based + reorder boost ({args.reorder_boost:g})",
+                      cb.evaluate(relevant, boosts=histories, boost_weight=args.reorder_boost))
     return 0
+
+
+def parse_boosts(entries):
+    """The --boost PID[=W] arguments -> (mapping PID -> W or None for an entry without a weight); ValueError for a W
+    that is not a number."""
+    out = {}
+    for e in entries or ():
+        pid, eq, w = e.rpartition("=")
+        if not eq:
+            out[e] = None
+            continue
+        try:
+            out[pid] = float(w)
+        except ValueError:
+            raise ValueError(f"--boost {e!r}: {w!r} is not a weight")
+    return out
 
 
 def main(argv=None) -> int:
@@ -121,20 +148,34 @@ def main(argv=None) -> int:
                          "they are then listed in selection order, not by score")
     ap.add_argument("--candidates", type=int, default=None, metavar="INT",
                     help="how many best matches a diversified request chooses from (default min(128, 4 * top_k))")
+    ap.add_argument("--boost", action="append", default=None, metavar="PID[=W]",
+                    help="a product the user has bought before: W (>= 0) is added to its score (repeatable; without =W "
+                         "it takes --boost-weight)")
+    ap.add_argument("--boost-weight", type=float, default=None, metavar="W", help="the weight of every --boost without its own")
+    ap.add_argument("--only-boosted", action="store_true", help="rank the --boost products alone (buy it again)")
     args = ap.parse_args(argv)
     cfg = read_settings(args.config)
     if not cfg["corpus"].exists():
         raise SystemExit(f"corpus file {cfg['corpus']} does not exist (this build never downloads one)")
     query, origin = pick_query(cfg, args.query)
     top_k = args.top_k or cfg["top_k"]
+    try:
+        boosts = parse_boosts(args.boost)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if any(w is None for w in boosts.values()):
+        if args.boost_weight is None:
+            raise SystemExit("--boost without =W needs --boost-weight")
+        boosts = {pid: args.boost_weight if w is None else w for pid, w in boosts.items()}
 
     from .recommender import Recommender
 
     rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"])
     try:
         hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department,
-                             diversity=args.diversity, candidates=args.candidates)
-    except ValueError as e:  # an aisle / department the catalog does not have, a bad --diversity / --candidates
+                             diversity=args.diversity, candidates=args.candidates, boosts=boosts or None,
+                             only_boosted=args.only_boosted)
+    except ValueError as e:  # an aisle / department the catalog does not have, a bad --diversity / --candidates / --boost
         raise SystemExit(str(e))
     if args.json:
         for rank, (pid, score) in enumerate(hits, 1):

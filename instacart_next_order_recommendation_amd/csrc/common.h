@@ -40,7 +40,8 @@ struct TimingSlot {
     double total_ms = 0.0;
     int64_t n = 0;
 };
-enum { T_SEARCH_KERNEL = 0, T_FFN_UP = 1, T_ENCODE = 2, T_SEARCH = 3, T_SEARCH_FALLBACK = 4, T_MMR_GRAM = 5, T_MMR_SELECT = 6, T_NSLOTS = 8 };
+enum { T_SEARCH_KERNEL = 0, T_FFN_UP = 1, T_ENCODE = 2, T_SEARCH = 3, T_SEARCH_FALLBACK = 4, T_MMR_GRAM = 5, T_MMR_SELECT = 6,
+       T_BOOST_SCORE = 7, T_BOOST_SELECT = 8, T_NSLOTS = 10 };  // (the last slot is a spare of encoder.hip's)
 bool timing_on();
 // Records [start, stop] around a launch when timing is enabled; resolved lazily at query time.
 struct ScopedTimer {

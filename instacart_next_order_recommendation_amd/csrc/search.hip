@@ -15,50 +15,7 @@
 
 namespace icrec {
 
-// ---------------------------------------------------------------- row normalisation
-// out = x / max(|x|_2, eps) — torch.nn.functional.normalize(p=2, dim=1) as cos_sim applies it.
-// One wavefront per row; reduction order = 64 strided fmaf partials + xor butterfly, identical
-// to oracle/icrec_oracle.c:wave_sum(mode 2).
-// float -> bfloat16 bits, round to nearest even (inputs are finite: normalised rows)
-__device__ __forceinline__ uint16_t bf16_rne(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-// tr_cols > 0 (fp32 only): write the result transposed, out[i * tr_cols + row] (n_out_rows == tr_cols) — the
-// k-major query layout of stream_search_kernel.
-template <bool OUT16>
-__global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __restrict__ x, void* __restrict__ outv,
-                                                             int64_t n_rows, int64_t n_out_rows, int dim, float eps,
-                                                             int tr_cols = 0) {
-    float* out = static_cast<float*>(outv);
-    uint16_t* out16 = static_cast<uint16_t*>(outv);
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_out_rows) return;
-    if (row >= n_rows) {  // zero padding rows (query tiles are padded to the tile width)
-        for (int i = lane; i < dim; i += 64) {
-            if (OUT16) out16[row * dim + i] = 0;
-            else if (tr_cols > 0) out[(int64_t)i * tr_cols + row] = 0.0f;
-            else out[row * dim + i] = 0.0f;
-        }
-        return;
-    }
-    const float* xr = x + row * dim;
-    float acc = 0.0f;
-    for (int i = lane; i < dim; i += 64) {
-        float v = xr[i];
-        acc = fmaf(v, v, acc);
-    }
-    float nrm = sqrtf(wave_sum_f32(acc));
-    float den = nrm > eps ? nrm : eps;
-    for (int i = lane; i < dim; i += 64) {
-        const float v = xr[i] / den;
-        if (OUT16) out16[row * dim + i] = bf16_rne(v);
-        else if (tr_cols > 0) out[(int64_t)i * tr_cols + row] = v;
-        else out[row * dim + i] = v;
-    }
-}
+// (row normalisation, the exclusion search and the facet test live in index.h: boost.hip uses them too)
 
 // bf16 rows widened back to fp32 (icrec_index_export)
 __global__ __launch_bounds__(256) void widen_bf16_kernel(const uint16_t* __restrict__ in, float* __restrict__ out, int64_t n) {
@@ -67,53 +24,6 @@ __global__ __launch_bounds__(256) void widen_bf16_kernel(const uint16_t* __restr
 }
 
 // ---------------------------------------------------------------- score + select
-// Is local row `row` in the sorted exclusion segment [lo, hi)?
-__device__ __forceinline__ bool excluded(const int32_t* __restrict__ ex, int lo, int hi, int row) {
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        int v = ex[mid];
-        if (v == row) return true;
-        if (v < row) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
-
-// ---- facets (icrec_search_faceted): one or two attribute bytes per row against a 256-bit allow mask per query and
-// facet.  A row is a candidate only if every facet's mask has the bit of the row's value; like an excluded row it is
-// then never offered, so the lists, the merges and the verification see admitted rows only.
-// The index keeps a row's bytes in ONE 16-bit word (facet 0 in the low byte; 0 for a facet it does not have), zero
-// padded to whole 256-row tiles: every tile of every kernel reads inside the array.  A block keeps its queries' masks
-// in LDS as [query][ICREC_MAX_FACETS][8] words: all ones for a facet the index does not have, zero for a padding
-// query.  The FACET arm of a kernel is the instantiation whose parameter pack `Facet` holds one FacetArgs; with an
-// empty pack the kernel's parameters and code are what they were before facets existed.
-struct FacetArgs {
-    const uint16_t* rows;   // [n_rows rounded up to 256] facet words
-    const uint32_t* allow;  // [Q][n_facets][ICREC_FACET_MASK_WORDS], read when the kernel runs
-    int n_facets;
-};
-constexpr int FACET_LDS_WORDS = ICREC_MAX_FACETS * ICREC_FACET_MASK_WORDS;  // per query
-static_assert(ICREC_MAX_FACETS == 2 && ICREC_FACET_MASK_WORDS == 8, "a row's facets are the two bytes of a 16-bit word");
-
-__device__ __forceinline__ FacetArgs facet_args() { return FacetArgs{nullptr, nullptr, 0}; }
-__device__ __forceinline__ FacetArgs facet_args(const FacetArgs& fa) { return fa; }
-
-// The masks of queries q0 .. q0 + nq - 1 -> LDS at am; the caller's next barrier publishes them.
-__device__ __forceinline__ void facet_load_masks(uint32_t* am, const FacetArgs& fa, int q0, int nq, int Q, int tid,
-                                                 int n_threads) {
-    for (int i = tid; i < nq * FACET_LDS_WORDS; i += n_threads) {
-        const int q = i / FACET_LDS_WORDS, f = i / ICREC_FACET_MASK_WORDS % ICREC_MAX_FACETS, w = i % ICREC_FACET_MASK_WORDS;
-        am[i] = q0 + q >= Q      ? 0u
-                : f < fa.n_facets ? fa.allow[((size_t)(q0 + q) * fa.n_facets + f) * ICREC_FACET_MASK_WORDS + w]
-                                  : ~0u;
-    }
-}
-
-// Does the mask of the block's query q (in LDS at am) admit a row whose facet word is fw?
-__device__ __forceinline__ bool facet_admits(const uint32_t* am, int q, unsigned fw) {
-    const unsigned v0 = fw & 255u, v1 = (fw >> 8) & 255u;
-    const uint32_t* m = am + q * FACET_LDS_WORDS;
-    return ((m[v0 >> 5] >> (v0 & 31)) & (m[ICREC_FACET_MASK_WORDS + (v1 >> 5)] >> (v1 & 31)) & 1u) != 0u;
-}
 
 // Merge the queue of query q into its sorted list; one wavefront, all 64 lanes call this.
 // Every element's new position is its rank in the union (keys are unique): a list entry keeps its

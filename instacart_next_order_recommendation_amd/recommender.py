@@ -145,6 +145,58 @@ def diversity_plan(diversity, candidates, top_k: int, n_products: int):
     return 1.0 - float(diversity), max(min(n, n_products), min(top_k, n_products))
 
 
+def boost_rows(boosts, boost_weight, only_boosted: bool, pid_to_row) -> Optional[dict[int, float]]:
+    """One request's `boosts` / `boost_weight` / `only_boosted` arguments, checked before any GPU work
+    -> None (the plain request: nothing to boost and only_boosted false) or {catalog row: weight}, the list
+    DeviceIndex.search_boosted takes (empty with only_boosted and nothing known to boost: no result).
+    boosts is a mapping product id -> weight, or an iterable of ids that all take boost_weight, which is then required.
+    Ids the catalog does not have are skipped, as for exclusions.  ValueError: a string for boosts, a weight (or
+    boost_weight) that is not a number >= 0, an iterable without boost_weight, more than ICREC_MAX_BOOSTS known ids."""
+    def weight(v, what):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if not 0.0 <= f:  # (a NaN fails the comparison)
+            raise ValueError(f"{what} must be a number >= 0, got {v!r}")
+        return f
+
+    if boost_weight is not None:
+        boost_weight = weight(boost_weight, "boost_weight")
+    if isinstance(boosts, (str, bytes)):
+        raise ValueError("boosts must be a mapping product id -> weight or an iterable of product ids, not a string")
+    if boosts is None:
+        pairs = {}
+    elif hasattr(boosts, "items"):
+        pairs = {pid_to_row[p]: weight(v, f"the boost weight of {p!r}") for p, v in boosts.items() if p in pid_to_row}
+    else:
+        ids = list(boosts)
+        if ids and boost_weight is None:
+            raise ValueError("boosts given as ids needs boost_weight")
+        pairs = {pid_to_row[p]: boost_weight for p in ids if p in pid_to_row}
+    if len(pairs) > _native.ICREC_MAX_BOOSTS:
+        raise ValueError(f"{len(pairs)} boosted products exceed the limit {_native.ICREC_MAX_BOOSTS}")
+    if not pairs and not only_boosted:
+        return None
+    return pairs
+
+
+def boost_plan(boosts, boost_weight, only_boosted: bool, n_queries: int, pid_to_row):
+    """A batch's boost arguments (boosts: None or one entry per query, each as boost_rows takes it; boost_weight and
+    only_boosted: one value for the batch) -> None (the plain path) or (per-query {row: weight} or None, only_boosted)."""
+    if boosts is None:
+        boosts = [None] * n_queries
+    elif hasattr(boosts, "items") or isinstance(boosts, (str, bytes)):
+        raise ValueError("boosts of a batch is a sequence with one entry per query")
+    boosts = list(boosts)
+    if len(boosts) != n_queries:
+        raise ValueError(f"boosts has {len(boosts)} entries for {n_queries} queries")
+    lists = [boost_rows(b, boost_weight, only_boosted, pid_to_row) for b in boosts]
+    if all(b is None for b in lists):
+        return None
+    return lists, bool(only_boosted)
+
+
 class SbertModel:
     """What `self.model` is in the reference (a SentenceTransformer): tokenizer + device encoder
     with an `encode(texts, batch_size, show_progress_bar, normalize_embeddings)` method."""
@@ -313,11 +365,15 @@ class Recommender:
             return None
         return [None if a is None and d is None else (a, d) for a, d in zip(*per_facet)]
 
-    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None, mmr=None):
+    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None, mmr=None,
+                       boost=None):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
         current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  allow: per-query
         facet constraints (_facet_allow).  mmr: (lambda, candidates) of diversity_plan - the search is then
-        `candidates` wide and the k results are re-selected from it on the device, inside the search time."""
+        `candidates` wide and the k results are re-selected from it on the device, inside the search time.
+        boost: (per-query {row: weight} or None, only_boosted) of boost_plan - the search result is merged with the
+        listed rows on the device (DeviceIndex.search_boosted; with only_boosted there is no search), at the width the
+        MMR re-selection consumes when there is one, inside the search time."""
         if allow is not None:
             allow = facet_masks(allow, len(cu) - 1, self._index.n_facets, self.device)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
@@ -327,7 +383,11 @@ class Recommender:
         emb = self.model.encoder.encode_packed_host(ids, cu)
         if ev:
             ev[1].record(stream)
-        if mmr is None:
+        if boost is not None:
+            idx, sc = self._index.search_boosted(emb, k if mmr is None else mmr[1], boost[0], ex, allow, only=boost[1])
+            if mmr is not None:
+                idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
+        elif mmr is None:
             idx, sc = self._index.search(emb, k, ex, allow)
         else:
             idx, sc = self._index.search_diverse(emb, k, mmr[0], mmr[1], ex, allow)
@@ -337,23 +397,25 @@ class Recommender:
         return (idx, sc, ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])) if ev else (idx, sc)
 
     def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, aisles=None,
-                       departments=None, diversity=None, candidates=None):
+                       departments=None, diversity=None, candidates=None, boosts=None, boost_weight=None,
+                       only_boosted=False):
         """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path (always
-        when the request names aisles or departments, or asks for diversity).
+        when the request names aisles or departments, asks for diversity, or boosts products).
         -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         allow = self._facet_allow(None if aisles is None else [aisles], None if departments is None else [departments], 1)
+        boost = boost_plan([boosts], boost_weight, only_boosted, 1, self._pid_to_row)
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed([query])
         tok_ms = (time.time() - t0) * 1000
         ex = self._exclusion_rows([exclude_product_ids])
         rows = ex[0] if ex else []
-        fast = self._fast_path() if allow is None and mmr is None else None
+        fast = self._fast_path() if allow is None and mmr is None and boost is None else None
         if fast is not None and fast.supports(len(ids), k, len(rows)):
             idx, sc, *ms = fast.run(ids, k, rows, timed=timed)
         else:
-            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr)
+            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr, boost)
             idx, sc = idx[0], sc[0]
         results = self._to_results(idx, sc)
         return (results, tok_ms + ms[0], ms[1]) if timed else results
@@ -365,18 +427,21 @@ class Recommender:
                         exclude_product_ids: Optional[Sequence[Optional[set[str]]]] = None, *,
                         aisles: Optional[Sequence[Optional[Sequence[str]]]] = None,
                         departments: Optional[Sequence[Optional[Sequence[str]]]] = None,
-                        diversity: float | None = None, candidates: int | None = None
+                        diversity: float | None = None, candidates: int | None = None, boosts=None,
+                        boost_weight: float | None = None, only_boosted: bool = False
                         ) -> list[list[tuple[str, float]]]:
         """Many contexts in one GPU pass; element i equals recommend(queries[i], ...).  aisles / departments: per
         query None or the admitted names, as recommend takes them.  diversity / candidates: one value for the whole
-        batch, as recommend takes them."""
+        batch, as recommend takes them.  boosts: None or one entry per query, each as recommend takes it; boost_weight
+        and only_boosted: one value for the whole batch."""
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
+        boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
         if not queries:
             return []
         k = self._k(top_k)
         ex = self._exclusion_rows(exclude_product_ids)
         allow = self._facet_allow(aisles, departments, len(queries))
-        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow, mmr=mmr)
+        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow, mmr=mmr, boost=boost)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))]
 
     def recommend_batches(self, batches, top_k: int = 10, exclude_product_ids=None):
@@ -394,24 +459,27 @@ class Recommender:
             yield [self._to_results(idx[i], sc[i]) for i in range(idx.shape[0])]
 
     def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None, *, aisles=None,
-                              departments=None, diversity: float | None = None, candidates: int | None = None):
+                              departments=None, diversity: float | None = None, candidates: int | None = None,
+                              boosts=None, boost_weight: float | None = None, only_boosted: bool = False):
         """recommend_batch plus (embedding ms incl. host tokenisation, similarity ms) from HIP events
         on the launch stream — what the micro-batching server reports as per-request stats.  A diversified batch's
-        re-selection counts into the similarity time."""
+        re-selection and a boosted batch's merge count into the similarity time."""
         k = self._k(top_k)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
+        boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
         ex = self._exclusion_rows(exclude_product_ids)
         allow = self._facet_allow(aisles, departments, len(queries))
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed(list(queries))
         tok_ms = (time.time() - t0) * 1000
-        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow, mmr=mmr)
+        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow, mmr=mmr, boost=boost)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))], tok_ms + enc_ms, sim_ms
 
     def recommend(self, query: str, top_k: int = 10,
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
-                  candidates: int | None = None) -> list[tuple[str, float]]:
+                  candidates: int | None = None, boosts=None, boost_weight: float | None = None,
+                  only_boosted: bool = False) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
         One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0".
         aisles / departments (keyword-only; names from .aisles / .departments): only products of one of these aisles
@@ -425,9 +493,20 @@ class Recommender:
         the chosen products, in SELECTION order - that order is not score-descending.  It composes with
         exclude_product_ids, aisles and departments (they shape the candidates) and takes the un-captured path.
         diversity None or 0 is the plain request: the same launches, the same results.  diversity outside [0, 1] or
-        candidates outside [top_k, 128] raises ValueError."""
+        candidates outside [top_k, 128] raises ValueError.
+        boosts (keyword-only; "buy it again"): the products this user has bought before, a mapping product id -> weight
+        or an iterable of ids that all take boost_weight.  The result is the top_k of the WHOLE catalog under
+        cosine + weight for these products and plain cosine for the rest, exactly (DeviceIndex.search_boosted): a
+        boosted product is found wherever it ranked before, and the returned scores are the adjusted ones.  Weights
+        are numbers >= 0 (at most 1,024 products); ids the catalog does not have are skipped, and an id that is also
+        excluded stays excluded.  only_boosted=True ranks the boosted products alone, best first (weight 0: the
+        user's history by the model's score).  It composes with exclude_product_ids, aisles and departments; with
+        diversity the boosted ranking is `candidates` wide and MMR re-selects from it, with the adjusted scores as the
+        relevance.  Such a request takes the un-captured path; boosts None or empty without only_boosted is the plain
+        request: the same launches, the same results.  Bad arguments raise ValueError before any GPU work."""
         return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments,
-                                   diversity=diversity, candidates=candidates)
+                                   diversity=diversity, candidates=candidates, boosts=boosts, boost_weight=boost_weight,
+                                   only_boosted=only_boosted)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -450,14 +529,16 @@ class MonitoredRecommender(Recommender):
     def recommend(self, query: str, top_k: int = 10, user_id: Optional[str] = None,
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
-                  candidates: int | None = None) -> list[tuple[str, float]]:
+                  candidates: int | None = None, boosts=None, boost_weight: float | None = None,
+                  only_boosted: bool = False) -> list[tuple[str, float]]:
         """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
         replays (fastpath.py): the three timing fields keep their meaning there.  A diversified request's
-        re-selection counts into the similarity time."""
+        re-selection and a boosted request's merge count into the similarity time."""
         start = time.time()
         results, encode_ms, sim_ms = self._recommend_one(query, top_k, exclude_product_ids, timed=True, aisles=aisles,
                                                          departments=departments, diversity=diversity,
-                                                         candidates=candidates)
+                                                         candidates=candidates, boosts=boosts, boost_weight=boost_weight,
+                                                         only_boosted=only_boosted)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

@@ -79,6 +79,41 @@ def facet_masks(allow, n_queries: int, n_facets: int, device=None):
     return torch.from_numpy(m.view(np.int32)).to(device).view(torch.uint32)
 
 
+def boost_csr(boosts, n_queries: int, device: Optional[torch.device] = None):
+    """Per-query boost lists -> (off int32[Q+1], rows int32, w float32, max_len): the CSR icrec_boost_select takes, each
+    query's rows ascending, on `device` (numpy arrays without one); max_len is the longest list.  boosts[i] is None (no
+    list), a mapping row -> weight, or an iterable of rows (weight 0: the rows are ranked, not lifted).  rows and w
+    hold at least one entry, so that they are never a NULL pointer.  ValueError: a count mismatch, more than
+    ICREC_MAX_BOOSTS rows in one list, a weight that is NaN or negative."""
+    if len(boosts) != n_queries:
+        raise ValueError(f"boosts has {len(boosts)} entries for {n_queries} queries")
+    off = np.zeros(n_queries + 1, np.int32)
+    rows: list[int] = []
+    w: list[float] = []
+    max_len = 0
+    for i, b in enumerate(boosts):
+        if b is None:
+            pairs = {}
+        elif hasattr(b, "items"):
+            pairs = {int(r): float(v) for r, v in b.items()}
+        else:
+            pairs = {int(r): 0.0 for r in b}
+        if len(pairs) > _native.ICREC_MAX_BOOSTS:
+            raise ValueError(f"boosts[{i}] lists {len(pairs)} rows, more than ICREC_MAX_BOOSTS = {_native.ICREC_MAX_BOOSTS}")
+        for r in sorted(pairs):
+            if not pairs[r] >= 0.0:  # (a NaN fails the comparison)
+                raise ValueError(f"boosts[{i}]: the weight of row {r} is {pairs[r]!r}; weights must be >= 0")
+            rows.append(r)
+            w.append(pairs[r])
+        off[i + 1] = len(rows)
+        max_len = max(max_len, len(pairs))
+    rows_a = np.asarray(rows or [0], np.int32)
+    w_a = np.asarray(w or [0.0], np.float32)
+    if device is None:
+        return off, rows_a, w_a, max_len
+    return torch.from_numpy(off).to(device), torch.from_numpy(rows_a).to(device), torch.from_numpy(w_a).to(device), max_len
+
+
 ROW_STORAGE = {"f32": 0, "bf16": 1, "f32+filter": 2, "bf16+filter": 3}  # ICREC_ROWS_* in include/icrec.h
 
 
@@ -99,6 +134,7 @@ class DeviceIndex:
         self.device = _native.hip_device(device, "DeviceIndex")
         self._ws_by_stream = _native.StreamScratch(self.device)
         self._mmr_ws_by_stream = _native.StreamScratch(self.device)  # its own blocks: growing one never moves a search's
+        self._boost_ws_by_stream = _native.StreamScratch(self.device)  # likewise
         L = _native.lib()
         rows = torch.as_tensor(embeddings)
         if rows.dim() != 2:
@@ -138,6 +174,7 @@ class DeviceIndex:
             self._h = None
         self._ws_by_stream.clear()
         self._mmr_ws_by_stream.clear()
+        self._boost_ws_by_stream.clear()
 
     def __del__(self):  # pragma: no cover - best effort
         try:
@@ -160,6 +197,13 @@ class DeviceIndex:
         if q.dim() != 2 or q.shape[1] != self.dim:
             raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
         return q.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _check_allow(self, allow: torch.Tensor, Q: int) -> None:
+        nf = self.n_facets  # 0: the library refuses the call (ICREC_EINVAL)
+        if allow.dtype != torch.uint32 or allow.device != self.device or not allow.is_contiguous() \
+                or tuple(allow.shape) != (Q, nf or allow.shape[1], _native.ICREC_FACET_MASK_WORDS):
+            raise ValueError(f"allow must be a contiguous uint32 tensor [{Q}, {nf}, {_native.ICREC_FACET_MASK_WORDS}] "
+                             f"on {self.device}, got {allow.dtype} {tuple(allow.shape)} on {allow.device}")
 
     # ------------------------------------------------------------------ API
     def search(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None):
@@ -186,11 +230,7 @@ class DeviceIndex:
         if ws is None:
             ws = self._workspace(Q, k)
         if allow is not None:
-            nf = self.n_facets  # 0: the library refuses the call (ICREC_EINVAL)
-            if allow.dtype != torch.uint32 or allow.device != self.device or not allow.is_contiguous() \
-                    or tuple(allow.shape) != (Q, nf or allow.shape[1], _native.ICREC_FACET_MASK_WORDS):
-                raise ValueError(f"allow must be a contiguous uint32 tensor [{Q}, {nf}, {_native.ICREC_FACET_MASK_WORDS}] "
-                                 f"on {self.device}, got {allow.dtype} {tuple(allow.shape)} on {allow.device}")
+            self._check_allow(allow, Q)
             _native.check(_native.lib().icrec_search_faceted(self._h, ptr(q), Q, k, ptr(excl_idx), ptr(excl_off), ptr(allow),
                                                              ptr(out_idx), ptr(out_score), ptr(ws), ws.numel(),
                                                              stream_ptr(self.device)), "icrec_search_faceted")
@@ -234,6 +274,62 @@ class DeviceIndex:
         cosine scores, in selection order (not score-descending)."""
         idx, sc = self.search(q, candidates, exclude, allow)
         return self.mmr_select(idx, sc, top_k, lam)
+
+    def boost_select(self, q, idx: Optional[torch.Tensor], sc: Optional[torch.Tensor], boosts, top_k: int,
+                     exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None):
+        """Boost each query's listed rows on a search result (icrec_boost_select): q the queries that were searched,
+        idx int64 [Q, k] and sc float32 [Q, k] the result of `search(q, k, exclude, allow)` as device tensors (both
+        None: no candidates, only the listed rows are ranked), boosts the per-query lists boost_csr takes (local rows)
+        -> (idx int64 [Q, top_k], score float32 [Q, top_k]) on the device: the top_k of the WHOLE shard under
+        cosine + weight for the listed rows and plain cosine for the others, score descending, -1 / 0 pads.  `exclude`
+        and `allow` must be the search's own: a listed row that is excluded or not admitted is never returned."""
+        q = self._queries(q)
+        Q = int(q.shape[0])
+        if (idx is None) != (sc is None):
+            raise ValueError("idx and sc must both be given or both be None")
+        if idx is not None:
+            if idx.dim() != 2 or idx.dtype != torch.int64 or sc.dtype != torch.float32 or sc.shape != idx.shape \
+                    or idx.shape[0] != Q:
+                raise ValueError(f"idx must be int64 [{Q}, k] and sc float32 [{Q}, k], got {idx.dtype} {tuple(idx.shape)} "
+                                 f"and {sc.dtype} {tuple(sc.shape)}")
+            idx, sc = idx.to(self.device).contiguous(), sc.to(self.device).contiguous()
+        off, rows, w, max_len = boost_csr(boosts, Q, self.device)
+        ei, eo = exclusion_csr(exclude, Q, self.device)
+        out_idx = torch.empty((Q, top_k), dtype=torch.int64, device=self.device)
+        out_sc = torch.empty((Q, top_k), dtype=torch.float32, device=self.device)
+        self.boost_select_into(q, idx, sc, off, rows, w, max_len if idx is not None else max(max_len, 1), top_k, ei, eo,
+                               allow, out_idx, out_sc)
+        return out_idx, out_sc
+
+    def boost_select_into(self, q: torch.Tensor, idx: Optional[torch.Tensor], sc: Optional[torch.Tensor],
+                          boost_off: torch.Tensor, boost_rows: torch.Tensor, boost_w: Optional[torch.Tensor],
+                          max_boosts: int, top_k: int, excl_idx: Optional[torch.Tensor], excl_off: Optional[torch.Tensor],
+                          allow: Optional[torch.Tensor], out_idx: torch.Tensor, out_score: torch.Tensor,
+                          ws: Optional[torch.Tensor] = None) -> None:
+        """Allocation-free form of `boost_select` on caller-owned contiguous device buffers (hipGraph-capturable once the
+        workspace for this (Q, max_boosts) exists, or with `ws` of the caller's own): the lists as boost_csr lays them
+        out, of which the first max_boosts entries per query are read.  The kernels read the lists, weights and masks
+        when they run: a captured graph follows what the buffers hold at replay.  The outputs must not alias the
+        inputs."""
+        Q = int(q.shape[0])
+        if allow is not None:
+            self._check_allow(allow, Q)
+        if ws is None:
+            need = int(_native.lib().icrec_boost_select_workspace_bytes(self._h, Q, max_boosts))
+            if need == 0:
+                raise _native.IcrecError(f"bad boost_select shape: n_queries={Q}, max_boosts={max_boosts}")
+            ws = self._boost_ws_by_stream.block(need)
+        _native.boost_select(self._h, q, idx, sc, boost_off, boost_rows, boost_w, max_boosts, excl_idx, excl_off, allow,
+                             top_k, out_idx, out_score, ws, self.device)
+
+    def search_boosted(self, q, k: int, boosts, exclude: Optional[Sequence[Iterable[int]]] = None,
+                       allow: Optional[torch.Tensor] = None, only: bool = False):
+        """`search(q, k, exclude, allow)` followed by `boost_select(.., boosts, k, exclude, allow)` on its result,
+        without a host step in between: the k best rows of the shard under cosine + weight.  only=True ranks each
+        query's listed rows alone ("buy it again": the history, best first) and runs no search."""
+        q = self._queries(q)
+        idx, sc = (None, None) if only else self.search(q, k, exclude, allow)
+        return self.boost_select(q, idx, sc, boosts, k, exclude, allow)
 
     def search_partial(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None) -> torch.Tensor:
         """Shard-local sorted lists as packed keys, int64-viewed uint64 [Q,k] (see icrec_search_partial)."""

@@ -1,0 +1,263 @@
+"""Recommender.recommend(..., boosts=, boost_weight=, only_boosted=) end to end on the GPU, on the synthetic 2-layer
+model directory and 700-product catalog of the MMR recommender test: a boosted request equals tests/boost_reference.py's
+full-catalog form applied to `product_embeddings`, bit for bit; no boosts is today's request on the graph path; and the
+content-based baseline's boosted ranking on tests/golden/cf_small equals the reference on the baseline's own
+embeddings."""
+from __future__ import annotations
+
+import json
+import math
+
+import numpy as np
+import pytest
+
+from instacart_next_order_recommendation_amd import synthetic as syn
+from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
+from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender
+from tests import boost_reference as ref
+from tests import mmr_reference
+from tests.cf_cases import FIXTURE
+from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def rec(tmp_path_factory, torch_cuda):
+    tmp = tmp_path_factory.mktemp("boost_rec")
+    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
+    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
+    corpus_path = tmp / "processed" / "eval_corpus.json"
+    corpus_path.parent.mkdir()
+    corpus_path.write_text(json.dumps(syn.synthetic_catalog(700)))
+    r = MonitoredRecommender(model_dir, corpus_path, use_index=False)
+    assert r._fast is not None and r._index.n_facets == 2
+    return r
+
+
+QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
+
+
+@pytest.fixture(scope="module")
+def scores(rec):
+    """The reference's cosine of every query with every product, from the recommender's own embeddings."""
+    return ref.catalog_scores(rec.model.encode(QUERIES), rec.product_embeddings, rec._index.storage)
+
+
+@pytest.fixture(scope="module")
+def boosts(rec, scores):
+    """Per query a mapping product id -> weight: 10 of its plain top 40, 50 other products, two ids the catalog does
+    not have.  The synthetic model's cosines lie within a few hundredths of each other, so the weights are drawn from
+    [0, the query's best score - its 40th best]: a product from outside the top 40 never passes the best match, one
+    from inside it can.  Every 7th weight is 0."""
+    rng = np.random.default_rng(12)
+    out = []
+    for i in range(len(QUERIES)):
+        top = np.argsort(-scores[i], kind="stable")[:40]
+        rows = np.concatenate([rng.choice(top, 10, replace=False), rng.choice(np.setdiff1d(np.arange(700), top), 50, replace=False)])
+        w = rng.uniform(0.0, float(scores[i][top[0]] - scores[i][top[39]]), rows.size).astype(np.float32)
+        w[::7] = 0
+        b = {rec.product_ids[int(r)]: float(x) for r, x in zip(rows, w)}
+        b["no-such-product"] = 0.5
+        b["-1"] = 0.5
+        out.append(b)
+    return out
+
+
+def as_list(rec, b, weight=None):
+    """A request's boosts -> the reference's (rows ascending, weights)."""
+    pairs = {rec._pid_to_row[p]: np.float32(weight if weight is not None else b[p]) for p in b if p in rec._pid_to_row}
+    rows = np.asarray(sorted(pairs), np.int64)
+    return rows, np.asarray([pairs[int(r)] for r in rows], np.float32)
+
+
+def expected(rec, scores, i, b, top_k, exclude=(), department=None, only=False, weight=None):
+    """The reference's full-catalog form for query i -> [(product id, score)]."""
+    excl = [[rec._pid_to_row[p] for p in exclude if p in rec._pid_to_row]]
+    admit = None
+    if department is not None:
+        admit = np.asarray([[t.endswith(f". Department: {department}.") for t in rec.product_texts]], bool)
+    idx, sc = ref.full_catalog(scores[i:i + 1], [as_list(rec, b, weight)], top_k, excl, admit, only)
+    return [(rec.product_ids[int(r)], float(s)) for r, s in zip(idx[0], sc[0]) if r >= 0]
+
+
+def test_boosted_request_equals_the_reference(rec, scores, boosts):
+    gained = kept_unlisted = 0
+    for i, q in enumerate(QUERIES):
+        plain = rec.recommend(q, 20)
+        assert plain == expected(rec, scores, i, {}, 20)  # the reference's scores are the recommender's
+        got = rec.recommend(q, 20, boosts=boosts[i])
+        assert got == expected(rec, scores, i, boosts[i], 20) and got != plain
+        gained += len({p for p, _ in got} - {p for p, _ in plain})
+        kept_unlisted += len({p for p, _ in got} - set(boosts[i]))
+        ids = list(boosts[i])
+        assert rec.recommend(q, 20, boosts=ids, boost_weight=0.25) == expected(rec, scores, i, boosts[i], 20, weight=0.25)
+        assert rec.recommend(q, 20, boosts=iter(ids), boost_weight=0) == plain  # weight 0 lifts nothing
+    assert gained > 0 and kept_unlisted > 0
+
+
+def test_no_boosts_is_the_plain_request_on_the_graph_path(rec, boosts, monkeypatch):
+    fast = rec._fast_path()
+    calls = []
+    real_run = type(fast).run
+
+    def run(self, *a, **kw):
+        calls.append(1)
+        return real_run(self, *a, **kw)
+
+    monkeypatch.setattr(type(fast), "run", run)
+    for q in QUERIES:
+        plain = rec.recommend(q, 20)
+        assert rec.recommend(q, 20, boosts=None) == plain
+        assert rec.recommend(q, 20, boosts={}, boost_weight=0.3) == plain
+        assert rec.recommend(q, 20, boosts=["no-such-product"], boost_weight=0.3) == plain
+    assert len(calls) == 4 * len(QUERIES)
+    rec.recommend(QUERIES[0], 20, boosts=boosts[0])  # a boosted request takes the un-captured path
+    rec.recommend(QUERIES[0], 20, only_boosted=True)
+    assert len(calls) == 4 * len(QUERIES)
+    assert rec.recommend_batch(QUERIES, 20, boosts=[None] * len(QUERIES)) == rec.recommend_batch(QUERIES, 20)
+
+
+def test_only_boosted(rec, scores, boosts):
+    for i, q in enumerate(QUERIES[:3]):
+        got = rec.recommend(q, 20, boosts=boosts[i], only_boosted=True)
+        assert got == expected(rec, scores, i, boosts[i], 20, only=True)
+        assert len(got) == 20 and {p for p, _ in got} <= set(boosts[i])
+        history = list(boosts[i])[:7]
+        again = rec.recommend(q, 20, boosts=history, boost_weight=0, only_boosted=True)  # buy it again: the history by score
+        assert [p for p, _ in again] == [p for p, _ in sorted(((p, scores[i][rec._pid_to_row[p]]) for p in history),
+                                                              key=lambda t: (-t[1], rec._pid_to_row[t[0]]))]
+        assert again == expected(rec, scores, i, dict.fromkeys(history, 0.0), 20, only=True)
+    assert rec.recommend(QUERIES[0], 20, only_boosted=True) == []
+    assert rec.recommend(QUERIES[0], 20, boosts=["no-such-product"], boost_weight=1, only_boosted=True) == []
+
+
+def test_composes_with_departments_exclusions_and_diversity(rec, scores, boosts):
+    d = rec.departments[0]
+    p_hat = mmr_reference.stored_rows(rec.product_embeddings, rec._index.storage)
+    reordered = 0
+    for i, q in enumerate(QUERIES[:3]):
+        boosted = rec.recommend(q, 20, boosts=boosts[i])
+        drop = {p for p, _ in boosted[:3]} | set(list(boosts[i])[:5])  # excluded AND boosted: excluded
+        got = rec.recommend(q, 10, exclude_product_ids=drop, departments=[d], boosts=boosts[i])
+        assert got and got == expected(rec, scores, i, boosts[i], 10, drop, d)
+        assert not drop & {p for p, _ in got}
+        assert all(rec.pid_to_text[p].endswith(f". Department: {d}.") for p, _ in got)
+        assert rec.recommend(q, 10, exclude_product_ids=drop, departments=[d], boosts=boosts[i], only_boosted=True) \
+            == expected(rec, scores, i, boosts[i], 10, drop, d, only=True)
+        # diversity: MMR over the boosted `candidates`-wide result, with the adjusted scores as the relevance
+        wide = rec.recommend(q, 40, exclude_product_ids=drop, boosts=boosts[i])
+        assert wide == expected(rec, scores, i, boosts[i], 40, drop)
+        cand = np.asarray([[rec._pid_to_row[p] for p, _ in wide]], np.int64)
+        rel = np.asarray([[s for _, s in wide]], np.float32)
+        idx, out = mmr_reference.mmr_select(p_hat, cand, rel, 10, 0.5)
+        want = [(rec.product_ids[int(r)], float(s)) for r, s in zip(idx[0], out[0]) if r >= 0]
+        assert rec.recommend(q, 10, exclude_product_ids=drop, boosts=boosts[i], diversity=0.5) == want
+        reordered += want != wide[:10]
+    assert reordered > 0  # the re-selection changes lists
+    assert rec.recommend(QUERIES[0], 10, aisles=[], boosts=boosts[0]) == []
+
+
+def test_batch_equals_single_calls(rec, boosts):
+    excl = [None, {"1", "2", "3"}, None, {"10"}, None]
+    departments = [None, None, [rec.departments[1]], None, [rec.departments[0], rec.departments[2]]]
+    per_query = [boosts[0], None, boosts[2], {}, boosts[4]]
+    batch = rec.recommend_batch(QUERIES, 20, excl, departments=departments, boosts=per_query)
+    for i, q in enumerate(QUERIES):
+        assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], departments=departments[i], boosts=per_query[i]), i
+    assert batch != rec.recommend_batch(QUERIES, 20, excl, departments=departments)
+    ids = [list(b) if b else b for b in per_query]
+    batch = rec.recommend_batch(QUERIES, 20, excl, boosts=ids, boost_weight=0.2, only_boosted=True, diversity=0.4, candidates=70)
+    for i, q in enumerate(QUERIES):
+        assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], boosts=ids[i], boost_weight=0.2,
+                                         only_boosted=True, diversity=0.4, candidates=70), i
+    assert batch[1] == [] and batch[3] == [] and len(batch[0]) == 20
+    timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 20, excl, departments=departments, boosts=per_query)
+    assert timed == rec.recommend_batch(QUERIES, 20, excl, departments=departments, boosts=per_query)
+    assert enc_ms > 0 and sim_ms > 0
+
+
+def test_monitored_fills_last_metrics(rec, boosts):
+    rec.last_metrics = None
+    got = rec.recommend(QUERIES[0], 20, user_id="u7", boosts=boosts[0])
+    m = rec.last_metrics
+    assert m is not None and m.user_id == "u7" and m.num_recommendations == len(got) == 20
+    assert m.top_score == got[0][1] and m.similarity_compute_time_ms > 0 and m.query_embedding_time_ms > 0
+
+
+def test_bad_arguments_raise_before_any_gpu_work(rec, monkeypatch):
+    def no_gpu(*a, **kw):
+        raise AssertionError("GPU work before the argument check")
+
+    monkeypatch.setattr(rec, "_encode_search", no_gpu)
+    monkeypatch.setattr(type(rec._fast_path()), "run", no_gpu)
+    for bad in (math.nan, -0.1, "x"):
+        with pytest.raises(ValueError, match=">= 0"):
+            rec.recommend(QUERIES[0], 20, boosts={"1": bad})
+        with pytest.raises(ValueError, match="boost_weight"):
+            rec.recommend(QUERIES[0], 20, boosts=["1"], boost_weight=bad)
+        with pytest.raises(ValueError, match=">= 0"):
+            rec.recommend_batch(QUERIES[:2], 20, boosts=[None, {"1": bad}])
+        with pytest.raises(ValueError, match="boost_weight"):
+            rec.recommend_batch_timed(QUERIES[:2], 20, boosts=[["1"], None], boost_weight=bad)
+    with pytest.raises(ValueError, match="needs boost_weight"):
+        rec.recommend(QUERIES[0], 20, boosts=["1", "2"])
+    with pytest.raises(ValueError, match="not a string"):
+        rec.recommend(QUERIES[0], 20, boosts="12", boost_weight=0.1)
+    with pytest.raises(ValueError, match="entries for 2 queries"):
+        rec.recommend_batch(QUERIES[:2], 20, boosts=[None])
+    with pytest.raises(ValueError, match="one entry per query"):
+        rec.recommend_batch(QUERIES[:2], 20, boosts={"1": 0.5})
+
+
+def test_cli_boost_arguments(rec, tmp_path, capsys):
+    import yaml
+
+    from instacart_next_order_recommendation_amd import cli
+
+    cfg = tmp_path / "inference.yaml"
+    cfg.write_text(yaml.safe_dump({"model_dir": str(rec.model_dir), "corpus": str(rec.corpus_path), "use_index": False,
+                                   "top_k": 5, "query": QUERIES[0]}))
+    far = [p for p, _ in rec.recommend(QUERIES[0], 60)][-2:]
+    assert cli.main(["--config", str(cfg), "--json", "--boost", f"{far[0]}=2.5", "--boost", far[1], "--boost-weight", "2"]) == 0
+    rows = [json.loads(ln) for ln in capsys.readouterr().out.splitlines()]
+    assert [(r["product_id"], r["score"]) for r in rows] == rec.recommend(QUERIES[0], 5, boosts={far[0]: 2.5, far[1]: 2.0})
+    assert [r["product_id"] for r in rows[:2]] == far
+    assert cli.main(["--config", str(cfg), "--json", "--boost", far[1], "--boost-weight", "0", "--only-boosted"]) == 0
+    rows = [json.loads(ln) for ln in capsys.readouterr().out.splitlines()]
+    assert [r["product_id"] for r in rows] == [far[1]]
+    with pytest.raises(SystemExit, match="boost-weight"):
+        cli.main(["--config", str(cfg), "--boost", "12"])
+    with pytest.raises(SystemExit, match="not a weight"):
+        cli.main(["--config", str(cfg), "--boost", "12=abc"])
+    with pytest.raises(SystemExit, match=">= 0"):
+        cli.main(["--config", str(cfg), "--boost", "12=-1"])
+
+
+def test_content_based_baseline_with_reorder_boosts(tmp_path, torch_cuda):
+    from instacart_next_order_recommendation_amd.baselines import ContentBasedBaseline, ItemItemCFBaseline
+    from instacart_next_order_recommendation_amd.ir_metrics import compute_ir_metrics_rows, load_eval_data, relevant_csr
+
+    queries, corpus, relevant = load_eval_data(FIXTURE / "processed")
+    histories = ItemItemCFBaseline.load_arrays(FIXTURE / "data", FIXTURE / "processed")["histories"]
+    cb = ContentBasedBaseline(queries, corpus, write_synthetic_model_dir(tmp_path / "m", seed=6))
+    rows, qids = cb.rank_rows(depth=20, queries_per_pass=16, boosts=histories, boost_weight=0.3)  # two passes, one ragged
+    assert qids == list(queries)
+    scores = ref.catalog_scores(cb.model.encode([queries[q] for q in qids]), cb.corpus_embeddings)
+    row_of = {p: j for j, p in enumerate(cb.product_ids)}
+    lists = []
+    for q in qids:
+        r = np.asarray(sorted(row_of[p] for p in histories[q] if p in row_of), np.int64)
+        lists.append((r, np.full(r.size, 0.3, np.float32)))
+    assert sum(r.size for r, _ in lists) > 0 and any(r.size == 0 for r, _ in lists)
+    want = ref.full_catalog(scores, lists, 20)[0]
+    np.testing.assert_array_equal(rows.cpu().numpy(), want)
+    plain = cb.rank_rows(depth=20)[0].cpu().numpy()
+    assert not np.array_equal(plain, want)
+    # evaluate: the device metrics of exactly those rows (one pass, the same queries: the same summation tree)
+    off, rel = relevant_csr(qids, relevant, row_of, cb.device)
+    got = cb.evaluate(relevant, depth=20, boosts=histories, boost_weight=0.3)
+    assert got == compute_ir_metrics_rows(torch_cuda.from_numpy(want).to(cb.device), off, rel)
+    assert got != cb.evaluate(relevant, depth=20) and got["accuracy_at_10"] > 0
+    with pytest.raises(ValueError, match="boost_weight"):
+        cb.rank_rows(depth=20, boosts=histories)
