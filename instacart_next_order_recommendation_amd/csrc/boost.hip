@@ -168,15 +168,7 @@ __global__ __launch_bounds__(SELECT_THREADS) void boost_select_kernel(
         keys[i] = key;
     }
     __syncthreads();
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P / 2; i += SELECT_THREADS) {
-                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));  // bit j clear; its partner has it set
-                bitonic_cx(keys[lo], keys[lo | j], (lo & size) == 0);
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_lds(keys, P, tid, SELECT_THREADS);
     for (int i = tid; i < top_k; i += SELECT_THREADS) {
         const u64 key = i < P ? keys[i] : 0ull;
         int64_t row = -1;
@@ -193,8 +185,6 @@ __global__ __launch_bounds__(SELECT_THREADS) void boost_select_kernel(
         out_score[q * top_k + i] = s;
     }
 }
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace
 }  // namespace icrec

@@ -7,7 +7,7 @@
 // bits per item, a thread walks one basket and counts per bit.  Pass B (product-major) sums w over a product's
 // column; w is stored [tile][order][T] so one column entry serves the whole tile with one contiguous read.  Scores
 // are int32 and exact in any summation order; they become keys ((score + 1) << 32) | ~row, the total order of
-// make_key's keys with 0 as the pad / "left out" value, and are sorted by search.hip's sorters (common.h).
+// make_key's keys with 0 as the pad / "left out" value, and are sorted by sort.hip's sorters (common.h).
 #include <stdlib.h>
 
 #include <vector>
@@ -211,17 +211,7 @@ __global__ __launch_bounds__(256) void cf_chunk_topk_kernel(const u64* __restric
     const u64* src = keys + (size_t)q * P + (size_t)c * CH;
     for (int i = t; i < CH; i += 256) seg[i] = src[i];
     __syncthreads();
-    for (int kk = 2; kk <= CH; kk <<= 1)
-        for (int j = kk >> 1; j >= 1; j >>= 1) {
-            for (int p = t; p < CH / 2; p += 256) {
-                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                u64 x = seg[i], y = seg[i | j];
-                bitonic_cx(x, y, (i & kk) == 0);
-                seg[i] = x;
-                seg[i | j] = y;
-            }
-            __syncthreads();
-        }
+    bitonic_sort_lds(seg, CH, t, 256);
     for (int e = t; e < k; e += 256) partial[((size_t)c * Q + q) * k + e] = e < CH ? seg[e] : 0ull;
 }
 
@@ -235,8 +225,6 @@ __global__ __launch_bounds__(256) void cf_emit_kernel(const u64* __restrict__ ke
 }
 
 // ------------------------------------------------------------------ host side
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct CfPlan {
     int n_tiles = 0, CH = 0, n_chunks = 0;
     int64_t P = 0;
@@ -249,9 +237,9 @@ static CfPlan cf_plan(const Cf* cf, int Q, int k, const char** why) {
     *why = nullptr;
     p.n_tiles = (Q + cf->tile - 1) / cf->tile;
     p.P = rank_pow2(cf->n_candidates);
-    size_t at = al256((size_t)p.n_tiles * cf->n_orders * cf->tile * 2);
+    size_t at = align256((size_t)p.n_tiles * cf->n_orders * cf->tile * 2);
     p.off_keys = at;
-    at += al256((size_t)Q * p.P * 8);
+    at += align256((size_t)Q * p.P * 8);
     if (k > 0) {
         int64_t ch = 1024;
         while (p.P / ch > MERGE_MAX_LISTS && ch < CF_CHUNK_MAX) ch <<= 1;
@@ -263,9 +251,9 @@ static CfPlan cf_plan(const Cf* cf, int Q, int k, const char** why) {
         p.CH = (int)ch;
         p.n_chunks = (int)(p.P / ch);
         p.off_partial = at;
-        at += al256((size_t)p.n_chunks * Q * k * 8);
+        at += align256((size_t)p.n_chunks * Q * k * 8);
         p.off_merged = at;
-        at += al256((size_t)Q * k * 8);
+        at += align256((size_t)Q * k * 8);
     }
     p.total = at;
     return p;
@@ -479,7 +467,7 @@ int icrec_cf_rank(icrec_cf* h, const int32_t* hist_off_dev, const int32_t* hist_
     u64* merged = reinterpret_cast<u64*>(base + p.off_merged);
     hipLaunchKernelGGL(cf_chunk_topk_kernel, dim3(p.n_chunks, n_queries), dim3(256), 0, st, keys, p.P, p.CH, n_queries, k,
                        partial);
-    launch_merge(partial, p.n_chunks, n_queries, n_queries, k, nullptr, nullptr, merged, st);
+    launch_merge(partial, p.n_chunks, n_queries, n_queries, k, nullptr, nullptr, merged, nullptr, st);
     const int64_t n = (int64_t)n_queries * k;
     hipLaunchKernelGGL(cf_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const u64*)merged, n, out_idx_dev,
                        out_score_dev);

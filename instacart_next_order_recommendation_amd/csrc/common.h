@@ -1,4 +1,5 @@
-// common.h — host-side error plumbing and device helpers shared by the gfx950 kernels.
+// common.h — host-side error plumbing, the declarations of sort.hip's key sorters, and the device helpers shared by
+// the gfx950 kernels: ranking keys, the LDS bitonic network, wave reductions and the fp32 MFMA tile engine.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,12 +55,19 @@ struct ScopedTimer {
 
 typedef unsigned long long u64;
 
-// search.hip's sorters of packed 64-bit ranking keys (larger key = better hit, key 0 = pad), shared with cf.hip:
+// Workspace sections start on 256-byte boundaries.
+static inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// sort.hip's sorters of packed 64-bit ranking keys (larger key = better hit, key 0 = pad), used by search.hip and cf.hip:
 // the k-way merge of n_lists descending lists of k keys per query (keys[list][q_stride][k]; any of the three outputs
-// may be NULL, out_score goes with out_idx), and the complete bitonic sort of keys[n_queries][P] in place followed by
+// may be NULL, out_score goes with out_idx; run_flag != NULL: nothing is written unless *run_flag != 0 when the kernel
+// runs), its single-workgroup form for a few queries with few lists (false, and nothing launched, where that form does
+// not apply), and the complete bitonic sort of keys[n_queries][P] in place followed by
 // out[q][i] = row_offset + row of the i-th best key, -1 where that key is 0 (P = rank_pow2(n_rows)).
 void launch_merge(const u64* keys, int n_lists, int q_stride, int Q, int k, int64_t* out_idx, float* out_score,
-                  u64* out_keys, hipStream_t st);
+                  u64* out_keys, const int* run_flag, hipStream_t st);
+bool launch_merge_block(const u64* keys, int n_lists, int q_stride, int Q, int k, int64_t* out_idx, float* out_score,
+                        u64* out_keys, hipStream_t st);
 int64_t rank_pow2(int64_t n);
 void launch_rank_sort_emit(u64* keys, int64_t n_rows, int64_t P, int n_queries, int64_t row_offset, int64_t* out,
                            hipStream_t st);
@@ -86,6 +94,12 @@ __device__ __forceinline__ float key_score(u64 key) {
     return __uint_as_float(u);
 }
 __device__ __forceinline__ uint32_t key_row(u64 key) { return 0xFFFFFFFFu - (uint32_t)key; }
+// Output slot o of a final list: the key and / or its (row, score); key 0 is the pad (row -1, score 0).
+__device__ __forceinline__ void store_key(u64 key, size_t o, int64_t* out_idx, float* out_score, u64* out_keys) {
+    if (out_keys) out_keys[o] = key;
+    if (out_idx) out_idx[o] = key ? (int64_t)key_row(key) : -1;
+    if (out_idx) out_score[o] = key ? key_score(key) : 0.0f;  // out_score is set whenever out_idx is
+}
 
 // descending bitonic compare-exchange on a[i], a[i ^ j] inside the size-k subsequence containing i
 __device__ __forceinline__ void bitonic_cx(u64& lo_slot, u64& hi_slot, bool desc) {
@@ -93,6 +107,18 @@ __device__ __forceinline__ void bitonic_cx(u64& lo_slot, u64& hi_slot, bool desc
     const bool swap = desc ? (a < b) : (a > b);
     lo_slot = swap ? b : a;
     hi_slot = swap ? a : b;
+}
+// keys[0 .. n) in LDS, n a power of two, sorted descending by the whole bitonic network; every one of the workgroup's
+// n_threads threads calls it after the barrier that published the keys, and it ends on a barrier.
+__device__ __forceinline__ void bitonic_sort_lds(u64* keys, int n, int tid, int n_threads) {
+    for (int size = 2; size <= n; size <<= 1)
+        for (int j = size >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n / 2; i += n_threads) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));  // bit j clear; its partner has it set
+                bitonic_cx(keys[lo], keys[lo | j], (lo & size) == 0);
+            }
+            __syncthreads();
+        }
 }
 
 // bfloat16 -> fp32 is a 16-bit shift: the low / high half of a 32-bit word of bf16 bits, widened exactly

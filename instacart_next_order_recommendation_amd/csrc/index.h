@@ -1,6 +1,7 @@
-// index.h — what an icrec_index handle points to, shared by search.hip (which creates, searches and destroys it),
-// mmr.hip and boost.hip (which read its stored rows), and the device code that search.hip and boost.hip both use: the
-// row normalisation kernel, the exclusion search and the facet test.
+// index.h — what an icrec_index handle points to, shared by index.hip (which creates and destroys it), search.hip
+// (which builds its filter storage and searches it), sort.hip (icrec_rank_all), mmr.hip and boost.hip (which read its
+// stored rows), and the device code that index.hip, search.hip and boost.hip share: the row normalisation kernel, the
+// exclusion search and the facet test.
 #pragma once
 
 #include "common.h"
@@ -25,6 +26,13 @@ struct Index {
 };
 
 static inline bool rows_are_bf16(const Index* ix) { return ix->storage == ICREC_ROWS_BF16 || ix->storage == ICREC_ROWS_BF16_FILTER; }
+
+// search.hip, for index.hip's icrec_index_create_ex: the filter pass's copy of the normalised rows of a *_FILTER
+// storage (whose dim is a multiple of FILTER_DIM_STEP), in the layout of the pass that will read it - `frag` or the two
+// planes.  Allocates and launches on the null stream; ICREC_ENOMEM (a hipMalloc failed) or ICREC_EHIP with the error
+// text set.
+constexpr int FILTER_DIM_STEP = 64;
+int build_filter_storage(Index* ix);
 
 #ifdef __HIPCC__
 

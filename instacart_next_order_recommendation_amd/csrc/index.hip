@@ -1,0 +1,162 @@
+// index.hip — the life cycle of an icrec_index handle (index.h: struct Index): creation with row normalisation,
+// facets, export, the accessors and destruction; and icrec_normalize_rows.  The filter storages' layout belongs to the
+// kernels that read it: search.hip builds it (build_filter_storage).
+#include <stdlib.h>
+
+#include <vector>
+
+#include "index.h"
+
+namespace icrec {
+
+// bf16 rows widened back to fp32 (icrec_index_export)
+__global__ __launch_bounds__(256) void widen_bf16_kernel(const uint16_t* __restrict__ in, float* __restrict__ out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = bf16_lo(in[i]);
+}
+
+// Largest batch the streaming kernel takes (ICREC_STREAM_MAX_Q=0 disables it; tuning/diagnostic knob), read ONCE,
+// when the index is created: a handle never changes its kernels between calls.
+static int stream_max_q_from_env() {
+    const char* e = getenv("ICREC_STREAM_MAX_Q");
+    const int v = e ? atoi(e) : 8;
+    return v > 8 ? 8 : v < 0 ? 0 : v;
+}
+
+}  // namespace icrec
+
+using namespace icrec;
+
+extern "C" {
+
+int icrec_index_create_ex(const float* rows_dev, int64_t n_rows, int32_t dim, int64_t row_offset, int device,
+                          int32_t storage, icrec_index** out) {
+    ICREC_REQUIRE(rows_dev && out, "icrec_index_create: NULL argument");
+    ICREC_REQUIRE(n_rows >= 1, "icrec_index_create: n_rows must be >= 1");
+    ICREC_REQUIRE(dim >= BK && dim % BK == 0 && dim <= 4096, "icrec_index_create: dim must be a multiple of %d (got %d)", BK, dim);
+    ICREC_REQUIRE(row_offset >= 0 && row_offset + n_rows < 0xFFFFFFFFll, "icrec_index_create: row_offset + n_rows must be < 2^32-1");
+    ICREC_REQUIRE(storage >= ICREC_ROWS_F32 && storage <= ICREC_ROWS_BF16_FILTER,
+                  "icrec_index_create: storage must be one of ICREC_ROWS_F32 (0), _BF16 (1), _F32_FILTER (2), _BF16_FILTER (3), got %d", storage);
+    const bool with_planes = storage == ICREC_ROWS_F32_FILTER || storage == ICREC_ROWS_BF16_FILTER;
+    const bool rows16 = storage == ICREC_ROWS_BF16 || storage == ICREC_ROWS_BF16_FILTER;
+    ICREC_REQUIRE(!with_planes || dim % FILTER_DIM_STEP == 0, "icrec_index_create: the filter planes need dim %% %d == 0 (got %d)",
+                  FILTER_DIM_STEP, dim);
+    // bf16 rows: the streaming kernel reads 128-byte slabs of 64 values, a final half slab would go unread
+    ICREC_REQUIRE(!rows16 || dim % 64 == 0, "icrec_index_create: bf16 rows need dim %% 64 == 0 (got %d)", dim);
+    ICREC_HIP(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    ICREC_HIP(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        set_error("icrec_index_create: device %d is %s, this library is built for gfx950 only", device, prop.gcnArchName);
+        return ICREC_ENODEV;
+    }
+    Index* ix = new Index();
+    ix->n_rows = n_rows; ix->dim = dim; ix->row_offset = row_offset; ix->device = device; ix->storage = storage;
+    ix->n_cu = prop.multiProcessorCount;
+    ix->stream_max_q = stream_max_q_from_env();
+    auto fail = [&]() {  // a hipMalloc failed: free what the index holds so far
+        icrec_index_destroy(reinterpret_cast<icrec_index*>(ix));
+        return ICREC_ENOMEM;
+    };
+    const size_t bytes = (size_t)n_rows * dim * (rows16 ? 2 : 4);
+    hipError_t e = hipMalloc(&ix->rows, bytes);
+    if (e != hipSuccess) {
+        set_error("icrec_index_create: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+        return fail();
+    }
+    hipLaunchKernelGGL((rows16 ? normalize_rows_kernel<true> : normalize_rows_kernel<false>), dim3((unsigned)((n_rows + 3) / 4)),
+                       dim3(256), 0, 0, rows_dev, ix->rows, n_rows, n_rows, dim, 1e-12f, 0);
+    ICREC_HIP(hipGetLastError());
+    if (with_planes)
+        if (int rc = build_filter_storage(ix)) return rc == ICREC_ENOMEM ? fail() : rc;
+    ICREC_HIP(hipStreamSynchronize(0));
+    *out = reinterpret_cast<icrec_index*>(ix);
+    return ICREC_OK;
+}
+
+int icrec_index_create(const float* rows_dev, int64_t n_rows, int32_t dim, int64_t row_offset, int device,
+                       icrec_index** out) {
+    return icrec_index_create_ex(rows_dev, n_rows, dim, row_offset, device, ICREC_ROWS_F32, out);
+}
+
+int32_t icrec_index_storage(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->storage : -1; }
+int32_t icrec_index_dim(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->dim : 0; }
+int32_t icrec_index_device(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->device : -1; }
+
+int icrec_index_destroy(icrec_index* h) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    if (!ix) return ICREC_OK;
+    hipSetDevice(ix->device);
+    hipFree(ix->rows);
+    hipFree(ix->plane_hi);
+    hipFree(ix->plane_lo);
+    hipFree(ix->frag);
+    hipFree(ix->facets);
+    delete ix;
+    return ICREC_OK;
+}
+
+int icrec_index_set_facets(icrec_index* h, const uint8_t* facets_host, int32_t n_facets) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix, "icrec_index_set_facets: NULL index");
+    ICREC_HIP(hipSetDevice(ix->device));
+    if (facets_host == nullptr) {
+        ICREC_HIP(hipFree(ix->facets));
+        ix->facets = nullptr;
+        ix->n_facets = 0;
+        return ICREC_OK;
+    }
+    ICREC_REQUIRE(n_facets >= 1 && n_facets <= ICREC_MAX_FACETS, "icrec_index_set_facets: n_facets must be in [1, %d] (got %d)",
+                  ICREC_MAX_FACETS, n_facets);
+    // one word per row, zero padded to whole 256-row tiles (the widest tile any search kernel walks)
+    const size_t padded = (size_t)((ix->n_rows + 255) / 256) * 256;
+    std::vector<uint16_t> words(padded, 0);
+    for (int64_t i = 0; i < ix->n_rows; ++i)
+        words[i] = n_facets == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * i] | (facets_host[2 * i + 1] << 8));
+    uint16_t* dev = nullptr;
+    if (hipMalloc(&dev, padded * 2) != hipSuccess) {
+        set_error("icrec_index_set_facets: hipMalloc of %zu bytes failed", padded * 2);
+        return ICREC_ENOMEM;
+    }
+    if (hipMemcpy(dev, words.data(), padded * 2, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        set_error("icrec_index_set_facets: copying the facets to the device failed");
+        return ICREC_EHIP;
+    }
+    (void)hipFree(ix->facets);
+    ix->facets = dev;
+    ix->n_facets = n_facets;
+    return ICREC_OK;
+}
+
+int32_t icrec_index_facets(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_facets : -1; }
+
+int64_t icrec_index_rows(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_rows : 0; }
+int64_t icrec_index_row_offset(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->row_offset : 0; }
+
+int icrec_index_export(const icrec_index* h, float* rows_dev, void* stream) {
+    const Index* ix = reinterpret_cast<const Index*>(h);
+    ICREC_REQUIRE(ix && rows_dev, "icrec_index_export: NULL argument");
+    const int64_t n = ix->n_rows * ix->dim;
+    if (rows_are_bf16(ix)) {
+        ICREC_HIP(hipSetDevice(ix->device));
+        hipLaunchKernelGGL(widen_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           static_cast<const uint16_t*>(ix->rows), rows_dev, n);
+        ICREC_HIP(hipGetLastError());
+    } else {
+        ICREC_HIP(hipMemcpyAsync(rows_dev, ix->rows, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    return ICREC_OK;
+}
+
+int icrec_normalize_rows(const float* x_dev, float* out_dev, int64_t n_rows, int32_t dim, float eps, int device,
+                         void* stream) {
+    ICREC_REQUIRE(x_dev && out_dev && n_rows >= 1 && dim >= 1, "icrec_normalize_rows: bad argument");
+    ICREC_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       x_dev, (void*)out_dev, n_rows, n_rows, dim, eps);
+    ICREC_HIP(hipGetLastError());
+    return ICREC_OK;
+}
+
+}  // extern "C"

@@ -189,7 +189,7 @@ extern "C" {
 
 size_t icrec_mmr_select_workspace_bytes(const icrec_index* h, int32_t n_queries, int32_t k) {
     if (!h || !shape_ok(n_queries, k)) return 0;
-    return (((size_t)n_queries * k * k * sizeof(float)) + 255) & ~(size_t)255;
+    return align256((size_t)n_queries * k * k * sizeof(float));
 }
 
 int icrec_mmr_select(icrec_index* h, const int64_t* cand_idx_dev, const float* rel_dev, int32_t n_queries, int32_t k,

@@ -187,8 +187,6 @@ __global__ __launch_bounds__(SELECT_WAVES * 64) void rerank_select_kernel(const 
     }
 }
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 bool pair_count_ok(int32_t n_queries, int32_t k, int32_t max_len) {
     return n_queries >= 1 && k >= 1 && max_len >= 3 && (int64_t)n_queries * k * max_len < (1ll << 31);
 }

@@ -1,12 +1,13 @@
-// search.hip — cosine scoring fused with per-query top-k selection (no score matrix is
-// ever written), the k-way merge of sorted partial lists, and row L2-normalisation.
+// search.hip — cosine scoring fused with per-query top-k selection (no score matrix is ever written): the score +
+// select kernels, the filter + verify path with the filter storage's layout, and their planning.  The partial lists
+// are merged by sort.hip's sorters (common.h); the index handle's life cycle is index.hip's.
 //
 // Replaces, on the device:
 //   sentence_transformers.util.cos_sim(query_emb, product_embeddings)  serve_recommendations.py:214/:250
 //   scores.argsort(descending=True)                                      :215/:251
 //   the exclusion / top-k Python loop                                    :216-225/:254-262
-// of /root/reference/src/inference/serve_recommendations.py.
-#include <vector>
+// of the reference's src/inference/serve_recommendations.py.
+#include <stdlib.h>
 
 #include "common.h"
 #include "gemm_x3.h"
@@ -16,12 +17,6 @@
 namespace icrec {
 
 // (row normalisation, the exclusion search and the facet test live in index.h: boost.hip uses them too)
-
-// bf16 rows widened back to fp32 (icrec_index_export)
-__global__ __launch_bounds__(256) void widen_bf16_kernel(const uint16_t* __restrict__ in, float* __restrict__ out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = bf16_lo(in[i]);
-}
 
 // ---------------------------------------------------------------- score + select
 
@@ -766,13 +761,6 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
 }
 
 // ---------------------------------------------------------------- filter + verify (ICREC_ROWS_F32_FILTER)
-// Output slot o of a final list: the key and / or its (row, score); key 0 is the pad (row -1, score 0).
-__device__ __forceinline__ void store_key(u64 key, size_t o, int64_t* out_idx, float* out_score, u64* out_keys) {
-    if (out_keys) out_keys[o] = key;
-    if (out_idx) out_idx[o] = key ? (int64_t)key_row(key) : -1;
-    if (out_idx) out_score[o] = key ? key_score(key) : 0.0f;  // out_score is set whenever out_idx is
-}
-
 // fp32 values -> f16 hi/lo planes: the queries of the staged filter pass per call, the catalog rows once at index
 // creation; clears the fallback flag if given.
 template <bool SRC16>  // SRC16: the source is bfloat16 bits (ICREC_ROWS_BF16_FILTER rows), widened exactly first
@@ -914,102 +902,6 @@ __global__ __launch_bounds__(256) void verify_kernel(const void* __restrict__ Pv
         store_key(0ull, (size_t)q * k + e, out_idx, out_score, out_keys);
 }
 
-// ---------------------------------------------------------------- k-way merge of sorted lists
-// keys: [n_lists][q_stride][k] sorted descending per (list, query); one wavefront per query
-// runs a tournament: every lane holds the heads of up to MERGE_LPL lists.
-template <int MERGE_LPL>  // lists per lane: 4 (<= 256 lists) or 16 (<= 1024)
-__global__ __launch_bounds__(256) void merge_kernel(const u64* __restrict__ keys, int n_lists, int q_stride, int Q,
-                                                    int k, int64_t* __restrict__ out_idx,
-                                                    float* __restrict__ out_score, u64* __restrict__ out_keys,
-                                                    const int* __restrict__ run_flag = nullptr) {
-    const int lane = threadIdx.x & 63;
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= Q) return;
-    if (run_flag != nullptr && *run_flag == 0) return;
-    u64 head[MERGE_LPL];
-    int pos[MERGE_LPL];
-#pragma unroll
-    for (int s = 0; s < MERGE_LPL; ++s) {
-        const int c = lane + 64 * s;
-        pos[s] = 0;
-        head[s] = c < n_lists ? keys[((size_t)c * q_stride + q) * k] : 0ull;
-    }
-    for (int e = 0; e < k; ++e) {
-        u64 best = 0ull;
-#pragma unroll
-        for (int s = 0; s < MERGE_LPL; ++s) best = head[s] > best ? head[s] : best;
-        const u64 w = wave_max_u64(best);
-        if (w != 0ull) {
-#pragma unroll
-            for (int s = 0; s < MERGE_LPL; ++s) {
-                if (head[s] == w) {  // keys are unique: exactly one (lane, s) advances
-                    const int c = lane + 64 * s;
-                    ++pos[s];
-                    head[s] = pos[s] < k ? keys[((size_t)c * q_stride + q) * k + pos[s]] : 0ull;
-                }
-            }
-        }
-        if (lane == 0) store_key(w, (size_t)q * k + e, out_idx, out_score, out_keys);
-    }
-}
-
-// Few queries, few lists (a single request: ~200 partial lists of k): ONE global round trip and three short LDS passes
-// instead of k dependent rounds (merge_kernel's every round waits for a global load behind a 12-shuffle wave maximum:
-// 12 us of a 0.35 ms request at 195 lists x 20).  A 256-thread workgroup per query:
-//   1. all n_lists * k keys (<= MERGE_BLOCK_KEYS) -> LDS, coalesced;
-//   2. h = the k-th largest list HEAD (rank by counting over the <= 256 heads): at least k keys are >= h, so the k
-//      best keys are all >= h, and only lists whose head is >= h (at most k of them) hold any;
-//   3. those lists hand their keys >= h to a candidate array (they are sorted: stop at the first smaller one);
-//   4. every candidate's rank by counting; rank r < k goes to output r.  Keys are unique (score bits | row) and 0 is
-//      the empty pad, so ranks are exact: the same (score desc, row asc) order and outputs as merge_kernel.
-constexpr int MERGE_BLOCK_KEYS = 16 * 256;
-__global__ __launch_bounds__(256) void merge_block_kernel(const u64* __restrict__ keys, int n_lists, int q_stride, int Q,
-                                                          int k, int64_t* __restrict__ out_idx,
-                                                          float* __restrict__ out_score, u64* __restrict__ out_keys) {
-    __shared__ __attribute__((aligned(16))) u64 all[MERGE_BLOCK_KEYS];
-    __shared__ uint16_t cand[MERGE_BLOCK_KEYS];  // candidates as indices into `all`
-    __shared__ u64 h_s;
-    __shared__ int ncand;
-    const int tid = threadIdx.x;
-    const int q = blockIdx.x;
-    const int n_keys = n_lists * k;
-    if (tid == 0) { h_s = 0ull; ncand = 0; }
-#pragma unroll
-    for (int s = 0; s < MERGE_BLOCK_KEYS / 256; ++s) {
-        const int f = tid + 256 * s;
-        if (f < n_keys) {
-            const int c = f / k, e = f - c * k;
-            all[f] = keys[((size_t)c * q_stride + q) * k + e];
-        }
-    }
-    __syncthreads();
-    const u64 head = tid < n_lists ? all[tid * k] : 0ull;
-    if (head != 0ull) {
-        int r = 0;
-        for (int i = 0; i < n_lists; ++i) r += all[i * k] > head ? 1 : 0;  // LDS broadcast reads
-        if (r == k - 1) h_s = head;  // unique keys: at most one thread
-    }
-    __syncthreads();
-    const u64 h = h_s;  // 0 when fewer than k lists are non-empty: every key is a candidate
-    if (head != 0ull && head >= h) {
-        for (int e = 0; e < k; ++e) {
-            const u64 v = all[tid * k + e];
-            if (v == 0ull || v < h) break;
-            cand[atomicAdd(&ncand, 1)] = (uint16_t)(tid * k + e);
-        }
-    }
-    __syncthreads();
-    const int C = ncand;
-    for (int ci = tid; ci < C; ci += 256) {
-        const u64 v = all[cand[ci]];
-        int r = 0;
-        for (int j = 0; j < C; ++j) r += all[cand[j]] > v ? 1 : 0;
-        if (r < k) store_key(v, (size_t)q * k + r, out_idx, out_score, out_keys);
-    }
-    for (int e = (C < k ? C : k) + tid; e < k; e += 256)  // pads: fewer than k rows left after the exclusions
-        store_key(0ull, (size_t)q * k + e, out_idx, out_score, out_keys);
-}
-
 // ---------------------------------------------------------------- host side
 typedef TileCfg<2, 2, 2, 2> CfgBig;    // 128 rows x 128 queries
 typedef TileCfg<4, 1, 2, 2> CfgMid;    // 256 rows x  64 queries
@@ -1022,6 +914,40 @@ typedef TileCfg<8, 1, 1, 2> CfgRes;     // 256 rows x  64 queries per round, 8 w
 // the staged pass (same box, top-20): 49,688 rows x 1,024 queries 0.26 vs 0.39 ms; 2 M rows 4.5 vs 6.5 ms; 10 M rows
 // 19.6 vs 30.1 ms, x 4,096 queries 74 vs 124 ms (425 TF-equivalent = 0.51 of the 3-pass f16 roof).
 constexpr int64_t RES_MAX_ROWS = (int64_t)1 << 40;  // no limit (ICREC_FILTER_RESIDENT=<n> sets one, =0 forces the staged form)
+static_assert(FILTER_DIM_STEP == HBK, "index.hip admits the dims whose rows the staged pass walks in whole slabs");
+
+// index.h: the filter storage of a new index, in the layout the pass that will read it expects.
+int build_filter_storage(Index* ix) {
+    const int64_t n_rows = ix->n_rows;
+    const int dim = ix->dim;
+    const bool rows16 = rows_are_bf16(ix);
+    const char* res_env = getenv("ICREC_FILTER_RESIDENT");  // "0": staged form; a number > 1: row limit of the resident form (A/B)
+    const int64_t res_max = res_env && atoll(res_env) > 1 ? atoll(res_env) : RES_MAX_ROWS;
+    if (dim == 16 * RES_KS && n_rows <= res_max && !(res_env && res_env[0] == '0' && res_env[1] == 0)) {
+        // resident filter pass: packed fragments instead of the row-major planes
+        ix->frag_row_tiles = ((n_rows + CfgRes::BM - 1) / CfgRes::BM) * (CfgRes::BM / 32);
+        const int64_t n_frag = ix->frag_row_tiles * RES_KS;
+        if (hipMalloc(&ix->frag, (size_t)n_frag * 2 * WT_FRAG * sizeof(_Float16)) != hipSuccess) {
+            set_error("icrec_index_create: hipMalloc of the filter fragments (%zu bytes) failed", (size_t)n_frag * 2 * WT_FRAG * 2);
+            return ICREC_ENOMEM;
+        }
+        // fragments of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
+        hipLaunchKernelGGL((rows16 ? pack_rows_kernel<true> : pack_rows_kernel<false>), dim3(4096), dim3(256), 0, 0,
+                           (const void*)ix->rows, n_rows, dim, n_frag, ix->frag);
+    } else {
+        const size_t n = (size_t)n_rows * dim;
+        hipError_t e1 = hipMalloc(&ix->plane_hi, n * 2), e2 = hipMalloc(&ix->plane_lo, n * 2);
+        if (e1 != hipSuccess || e2 != hipSuccess) {
+            set_error("icrec_index_create: hipMalloc of the filter planes (2 x %zu bytes) failed", n * 2);
+            return ICREC_ENOMEM;
+        }
+        // planes of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
+        hipLaunchKernelGGL((rows16 ? split_planes_kernel<true> : split_planes_kernel<false>), dim3(4096), dim3(256), 0, 0,
+                           (const void*)ix->rows, n, ix->plane_hi, ix->plane_lo, (int*)nullptr);
+    }
+    ICREC_HIP(hipGetLastError());
+    return ICREC_OK;
+}
 
 // Filter + verify (ICREC_ROWS_F32_FILTER): batches of at least FILTER_MIN_Q queries are ranked by the f16x3 filter
 // pass with FILTER_SLACK extra list entries, then verified exactly.  filter_eps(dim) bounds |filter score - exact score|
@@ -1055,14 +981,6 @@ static void plan_chunks(int64_t n_rows, int BM, int want, int cap, int* n_row_ti
     if (want > *n_row_tiles) want = *n_row_tiles;
     *tiles_per_chunk = (*n_row_tiles + want - 1) / want;
     *n_chunks = (*n_row_tiles + *tiles_per_chunk - 1) / *tiles_per_chunk;
-}
-
-// Largest batch the streaming kernel takes (ICREC_STREAM_MAX_Q=0 disables it; tuning/diagnostic knob), read ONCE,
-// when the index is created: a handle never changes its kernels between calls.
-static int stream_max_q_from_env() {
-    const char* e = getenv("ICREC_STREAM_MAX_Q");
-    const int v = e ? atoi(e) : 8;
-    return v > 8 ? 8 : v < 0 ? 0 : v;
 }
 
 // Dynamic LDS of the tiled kernels: operand staging, then the selection (TopK; `facet`: with the allow masks and the tiles' facet words).
@@ -1101,8 +1019,8 @@ static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream, bool fac
         // one full wave of resident blocks (2 per CU fit by LDS/VGPR), at most 256 chunks
         plan_chunks(ix->n_rows, p.BM, 2 * ix->n_cu / p.n_qtiles, 256, &p.n_row_tiles, &p.tiles_per_chunk, &p.n_chunks);
     }
-    p.ws_q = ((size_t)p.Qpad * ix->dim * 4 + 255) & ~(size_t)255;
-    p.ws_partial = ((size_t)p.n_chunks * p.Qpad * k * 8 + 255) & ~(size_t)255;
+    p.ws_q = align256((size_t)p.Qpad * ix->dim * 4);
+    p.ws_partial = align256((size_t)p.n_chunks * p.Qpad * k * 8);
     p.ws_total = p.ws_q + p.ws_partial;
     return p;
 }
@@ -1132,28 +1050,85 @@ static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& ex
                 &f.n_row_tiles, &f.tiles_per_chunk, &f.n_chunks);
     f.smem = f.resident ? resident_smem(f.kp, facet) : staged_smem(f.kp, facet);
     const int qpad_max = f.Qpad > exact.Qpad ? f.Qpad : exact.Qpad;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    f.off_qh = up((size_t)qpad_max * ix->dim * 4);
-    f.off_ql = f.off_qh + up((size_t)f.Qpad * ix->dim * 2);
-    f.off_flag = f.off_ql + up((size_t)f.Qpad * ix->dim * 2);
+    f.off_qh = align256((size_t)qpad_max * ix->dim * 4);
+    f.off_ql = f.off_qh + align256((size_t)f.Qpad * ix->dim * 2);
+    f.off_flag = f.off_ql + align256((size_t)f.Qpad * ix->dim * 2);
     f.off_cand = f.off_flag + 256;
-    f.off_partial = f.off_cand + up((size_t)Q * f.kp * 8);
+    f.off_partial = f.off_cand + align256((size_t)Q * f.kp * 8);
     const size_t part_filter = (size_t)f.n_chunks * f.Qpad * f.kp * 8;
-    f.ws_total = f.off_partial + up(part_filter > exact.ws_partial ? part_filter : exact.ws_partial);
+    f.ws_total = f.off_partial + align256(part_filter > exact.ws_partial ? part_filter : exact.ws_partial);
     return f;
 }
 
+// One launch of a kernel family, timed in slot `timer`: the FACET arm `facet` (fa appended to the arguments) when the
+// search has allow masks, the kernel `plain` otherwise.  big_lds: the family's dynamic LDS can exceed the 64 KB default.
+template <class Plain, class FacetArm, class... Args>
+static int launch_arm(Plain plain, FacetArm facet, const FacetArgs& fa, bool big_lds, int timer, dim3 grid, dim3 block,
+                      size_t smem, hipStream_t st, Args... args) {
+    if (big_lds)
+        if (int rc = ensure_dynamic_lds(fa.allow ? reinterpret_cast<const void*>(facet) : reinterpret_cast<const void*>(plain),
+                                        160 * 1024))
+            return rc;
+    ScopedTimer tm(timer, st);
+    if (fa.allow) hipLaunchKernelGGL(facet, grid, block, smem, st, args..., fa);
+    else hipLaunchKernelGGL(plain, grid, block, smem, st, args...);
+    return ICREC_OK;
+}
+
+// The exact search's kernels for one tile shape or query count and one row format: the plain kernel, its EMIT form
+// (tiled kernels only) and its FACET arm.
+using SearchFn = decltype(&search_kernel<CfgBig, false, false>);
+using StreamFn = decltype(&stream_search_kernel<1, false>);
+struct TiledArms { SearchFn plain, scores; decltype(&search_kernel<CfgBig, false, false, FacetArgs>) facet; };
+struct StreamArms { StreamFn plain; decltype(&stream_search_kernel<1, false, FacetArgs>) facet; };
+template <class Cfg, bool P16> static TiledArms tiled_arms() {
+    return {search_kernel<Cfg, false, P16>, search_kernel<Cfg, true, P16>, search_kernel<Cfg, false, P16, FacetArgs>};
+}
+template <int NQ, bool P16> static StreamArms stream_arms() {
+    return {stream_search_kernel<NQ, P16>, stream_search_kernel<NQ, P16, FacetArgs>};
+}
+
+// The exact search of plan p over the index rows (fp32 or bf16): partial lists, or every score into scores_out.  run_flag:
+// the guarded pass of the filter path, which has a timer slot of its own.  fa.allow != NULL: the FACET arms (never with
+// scores_out).  (Kernel tables: bf16 rows first.)
 static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
-                        const int32_t* eo, const uint32_t* allow, u64* partial, float* scores_out, const int* run_flag,
-                        hipStream_t st);
+                        const int32_t* eo, const FacetArgs& fa, u64* partial, float* scores_out, const int* run_flag,
+                        hipStream_t st) {
+    static const TiledArms tiled[2][3] = {{tiled_arms<CfgBig, true>(), tiled_arms<CfgMid, true>(), tiled_arms<CfgSmall, true>()},
+                                          {tiled_arms<CfgBig, false>(), tiled_arms<CfgMid, false>(), tiled_arms<CfgSmall, false>()}};
+    static const StreamArms stream[4][2] = {{stream_arms<1, true>(), stream_arms<1, false>()},  // NQ = 1, 2, 4, 8
+                                            {stream_arms<2, true>(), stream_arms<2, false>()},
+                                            {stream_arms<4, true>(), stream_arms<4, false>()},
+                                            {stream_arms<8, true>(), stream_arms<8, false>()}};
+    const int r = rows_are_bf16(ix) ? 0 : 1;
+    int rc;
+    if (p.variant == 3) {
+        const int nq = p.BN == 1 ? 0 : p.BN == 2 ? 1 : p.BN == 4 ? 2 : 3;
+        const bool f = fa.allow != nullptr;
+        const size_t smem = nq == 0 ? StreamSmem<1>::bytes(k, f) : nq == 1 ? StreamSmem<2>::bytes(k, f)
+                            : nq == 2 ? StreamSmem<4>::bytes(k, f) : StreamSmem<8>::bytes(k, f);
+        rc = launch_arm(stream[nq][r].plain, stream[nq][r].facet, fa, false, T_SEARCH_KERNEL, dim3(p.n_chunks), dim3(ST_ROWS),
+                        smem, st, (const void*)ix->rows, ix->n_rows, ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset,
+                        p.n_row_tiles, p.tiles_per_chunk, partial);
+    } else {
+        const TiledArms& t = tiled[r][p.variant];
+        rc = launch_arm(scores_out ? t.scores : t.plain, t.facet, fa, true, run_flag == nullptr ? T_SEARCH_KERNEL : T_SEARCH_FALLBACK,
+                        dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st, (const void*)ix->rows, ix->n_rows,
+                        ix->dim, qn, p.Qpad, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk,
+                        p.n_qtiles, partial, scores_out, run_flag);
+    }
+    if (rc) return rc;
+    ICREC_HIP(hipGetLastError());
+    return ICREC_OK;
+}
+static_assert(CfgBig::THREADS == CfgMid::THREADS && CfgMid::THREADS == CfgSmall::THREADS, "launch_exact: one block size");
 
 // Filter (f16x3 MFMA, approximate) -> merge -> verify (exact chains on the candidates) -> exact search that runs
-// only if some query could not be proven.  Same outputs, bit for bit, as the exact search.  allow != NULL: the filter
+// only if some query could not be proven.  Same outputs, bit for bit, as the exact search.  fa.allow != NULL: the filter
 // pass and the guarded exact pass both run their FACET arm with the same masks.
 static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, const float* q, int Q, int k,
-                               const int32_t* ei, const int32_t* eo, const uint32_t* allow, int64_t* out_idx,
+                               const int32_t* ei, const int32_t* eo, const FacetArgs& fa, int64_t* out_idx,
                                float* out_score, u64* out_keys, void* ws, hipStream_t st) {
-    const FacetArgs fa{ix->facets, allow, ix->n_facets};
     char* base = reinterpret_cast<char*>(ws);
     float* qn = reinterpret_cast<float*>(base);
     _Float16* qh = reinterpret_cast<_Float16*>(base + f.off_qh);
@@ -1165,128 +1140,34 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
     hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3((qpad_max + 3) / 4), dim3(256), 0, st, q, (void*)qn, (int64_t)Q,
                        (int64_t)qpad_max, ix->dim, 1e-12f, 0);
     const size_t nq = (size_t)f.Qpad * ix->dim;
+    int rc;
     if (f.resident) {
         hipLaunchKernelGGL(split_queries_act_kernel, dim3((unsigned)((nq / 4 + 255) / 256 < 1024 ? (nq / 4 + 255) / 256 : 1024)),
                            dim3(256), 0, st, (const float*)qn, nq / 4, qh, ql, flag);
-        auto kern = resident_search_kernel<CfgRes>;
-        auto kern_f = resident_search_kernel<CfgRes, FacetArgs>;
-        if (int rc_ = ensure_dynamic_lds(allow ? reinterpret_cast<const void*>(kern_f) : reinterpret_cast<const void*>(kern),
-                                         160 * 1024))
-            return rc_;
-        ScopedTimer tm(T_SEARCH_KERNEL, st);
-        if (allow)
-            hipLaunchKernelGGL(kern_f, dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st,
-                               (const _Float16*)ix->frag, ix->n_rows, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp,
-                               ei, eo, (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial, fa);
-        else
-            hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st, (const _Float16*)ix->frag,
-                               ix->n_rows, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo,
-                               (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
+        rc = launch_arm(resident_search_kernel<CfgRes>, resident_search_kernel<CfgRes, FacetArgs>, fa, true, T_SEARCH_KERNEL,
+                        dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st, (const _Float16*)ix->frag, ix->n_rows,
+                        (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
+                        f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     } else {
         hipLaunchKernelGGL(split_planes_kernel<false>, dim3((unsigned)((nq + 255) / 256 < 1024 ? (nq + 255) / 256 : 1024)),
                            dim3(256), 0, st, (const void*)qn, nq, qh, ql, flag);
-        auto kern = staged_search_kernel<CfgFilter>;
-        auto kern_f = staged_search_kernel<CfgFilter, FacetArgs>;
-        if (int rc_ = ensure_dynamic_lds(allow ? reinterpret_cast<const void*>(kern_f) : reinterpret_cast<const void*>(kern),
-                                         160 * 1024))
-            return rc_;
-        ScopedTimer tm(T_SEARCH_KERNEL, st);
-        if (allow)
-            hipLaunchKernelGGL(kern_f, dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st,
-                               (const _Float16*)ix->plane_hi, (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim,
-                               (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
-                               f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial, fa);
-        else
-            hipLaunchKernelGGL(kern, dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st,
-                               (const _Float16*)ix->plane_hi, (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim,
-                               (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
-                               f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
+        rc = launch_arm(staged_search_kernel<CfgFilter>, staged_search_kernel<CfgFilter, FacetArgs>, fa, true, T_SEARCH_KERNEL,
+                        dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st, (const _Float16*)ix->plane_hi,
+                        (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q,
+                        f.kp, ei, eo, (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     }
+    if (rc) return rc;
     ICREC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(merge_kernel<4>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, f.n_chunks, f.Qpad, Q, f.kp,
-                       (int64_t*)nullptr, (float*)nullptr, cand, (const int*)nullptr);
+    launch_merge(partial, f.n_chunks, f.Qpad, Q, f.kp, nullptr, nullptr, cand, nullptr, st);  // (at most 256 lists)
     hipLaunchKernelGGL((rows_are_bf16(ix) ? verify_kernel<true> : verify_kernel<false>), dim3((Q + 3) / 4), dim3(256), 0,
                        st, (const void*)ix->rows, ix->dim, qn, cand, Q, f.kp, k, (uint32_t)ix->row_offset,
                        filter_eps(ix->dim), out_idx, out_score, out_keys, flag);
     ICREC_HIP(hipGetLastError());
     // exact pass: every workgroup returns at once unless verify raised the flag
-    if (int rc = launch_exact(ix, ex, qn, Q, k, ei, eo, allow, partial, nullptr, flag, st)) return rc;
-    hipLaunchKernelGGL(merge_kernel<4>, dim3((Q + 3) / 4), dim3(256), 0, st, partial, ex.n_chunks, ex.Qpad, Q, k, out_idx,
-                       out_score, out_keys, (const int*)flag);
+    if (int rc2 = launch_exact(ix, ex, qn, Q, k, ei, eo, fa, partial, nullptr, flag, st)) return rc2;
+    launch_merge(partial, ex.n_chunks, ex.Qpad, Q, k, out_idx, out_score, out_keys, flag, st);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
-}
-
-// The exact search of plan p over the index rows (fp32 or bf16): partial lists, or every score into scores_out.  run_flag:
-// the guarded pass of the filter path, which has a timer slot of its own.  allow != NULL: the FACET arms (never with
-// scores_out).  (Kernel tables: bf16 rows first.)
-static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
-                        const int32_t* eo, const uint32_t* allow, u64* partial, float* scores_out, const int* run_flag,
-                        hipStream_t st) {
-    using SearchFn = decltype(&search_kernel<CfgBig, false, false>);
-    static const SearchFn lists[2][3] = {
-        {search_kernel<CfgBig, false, true>, search_kernel<CfgMid, false, true>, search_kernel<CfgSmall, false, true>},
-        {search_kernel<CfgBig, false, false>, search_kernel<CfgMid, false, false>, search_kernel<CfgSmall, false, false>}};
-    static const decltype(&stream_search_kernel<1, false>) stream[4][2] = {  // NQ = 1, 2, 4, 8
-        {stream_search_kernel<1, true>, stream_search_kernel<1, false>},
-        {stream_search_kernel<2, true>, stream_search_kernel<2, false>},
-        {stream_search_kernel<4, true>, stream_search_kernel<4, false>},
-        {stream_search_kernel<8, true>, stream_search_kernel<8, false>}};
-    static const SearchFn scores[2][3] = {
-        {search_kernel<CfgBig, true, true>, search_kernel<CfgMid, true, true>, search_kernel<CfgSmall, true, true>},
-        {search_kernel<CfgBig, true, false>, search_kernel<CfgMid, true, false>, search_kernel<CfgSmall, true, false>}};
-    using FacetFn = decltype(&search_kernel<CfgBig, false, false, FacetArgs>);
-    static const FacetFn facet_lists[2][3] = {
-        {search_kernel<CfgBig, false, true, FacetArgs>, search_kernel<CfgMid, false, true, FacetArgs>,
-         search_kernel<CfgSmall, false, true, FacetArgs>},
-        {search_kernel<CfgBig, false, false, FacetArgs>, search_kernel<CfgMid, false, false, FacetArgs>,
-         search_kernel<CfgSmall, false, false, FacetArgs>}};
-    static const decltype(&stream_search_kernel<1, false, FacetArgs>) facet_stream[4][2] = {
-        {stream_search_kernel<1, true, FacetArgs>, stream_search_kernel<1, false, FacetArgs>},
-        {stream_search_kernel<2, true, FacetArgs>, stream_search_kernel<2, false, FacetArgs>},
-        {stream_search_kernel<4, true, FacetArgs>, stream_search_kernel<4, false, FacetArgs>},
-        {stream_search_kernel<8, true, FacetArgs>, stream_search_kernel<8, false, FacetArgs>}};
-    const FacetArgs fa{ix->facets, allow, ix->n_facets};
-    const int r = rows_are_bf16(ix) ? 0 : 1;
-    if (p.variant == 3) {
-        const int nq = p.BN == 1 ? 0 : p.BN == 2 ? 1 : p.BN == 4 ? 2 : 3;
-        const bool f = allow != nullptr;
-        const size_t smem = nq == 0 ? StreamSmem<1>::bytes(k, f) : nq == 1 ? StreamSmem<2>::bytes(k, f)
-                            : nq == 2 ? StreamSmem<4>::bytes(k, f) : StreamSmem<8>::bytes(k, f);
-        ScopedTimer tm(T_SEARCH_KERNEL, st);
-        if (allow)
-            hipLaunchKernelGGL(facet_stream[nq][r], dim3(p.n_chunks), dim3(ST_ROWS), smem, st, (const void*)ix->rows,
-                               ix->n_rows, ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles,
-                               p.tiles_per_chunk, partial, fa);
-        else
-            hipLaunchKernelGGL(stream[nq][r], dim3(p.n_chunks), dim3(ST_ROWS), smem, st, (const void*)ix->rows, ix->n_rows,
-                               ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk, partial);
-    } else {
-        const SearchFn kern = (scores_out ? scores : lists)[r][p.variant];
-        const FacetFn kern_f = facet_lists[r][p.variant];
-        if (int rc_ = ensure_dynamic_lds(allow ? reinterpret_cast<const void*>(kern_f) : reinterpret_cast<const void*>(kern),
-                                         160 * 1024))
-            return rc_;
-        ScopedTimer tm(run_flag == nullptr ? T_SEARCH_KERNEL : T_SEARCH_FALLBACK, st);
-        if (allow)
-            hipLaunchKernelGGL(kern_f, dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st,
-                               (const void*)ix->rows, ix->n_rows, ix->dim, qn, p.Qpad, Q, k, ei, eo, (uint32_t)ix->row_offset,
-                               p.n_row_tiles, p.tiles_per_chunk, p.n_qtiles, partial, scores_out, run_flag, fa);
-        else
-            hipLaunchKernelGGL(kern, dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st, (const void*)ix->rows,
-                               ix->n_rows, ix->dim, qn, p.Qpad, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles,
-                               p.tiles_per_chunk, p.n_qtiles, partial, scores_out, run_flag);
-    }
-    ICREC_HIP(hipGetLastError());
-    return ICREC_OK;
-}
-static_assert(CfgBig::THREADS == CfgMid::THREADS && CfgMid::THREADS == CfgSmall::THREADS, "launch_exact: one block size");
-
-// k-way merge of n_lists sorted lists of k keys per query (keys[list][q_stride][k]): 4 lists per lane up to 256 lists
-void launch_merge(const u64* keys, int n_lists, int q_stride, int Q, int k, int64_t* out_idx, float* out_score,
-                  u64* out_keys, hipStream_t st) {
-    hipLaunchKernelGGL((n_lists <= 256 ? merge_kernel<4> : merge_kernel<16>), dim3((Q + 3) / 4), dim3(256), 0, st, keys,
-                       n_lists, q_stride, Q, k, out_idx, out_score, out_keys, (const int*)nullptr);
 }
 
 // allow != NULL (icrec_search_faceted): every selecting kernel runs its FACET arm on the index's facets.
@@ -1299,6 +1180,7 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
     ICREC_REQUIRE((ei == nullptr) == (eo == nullptr), "icrec_search: excl_idx and excl_off must both be set or both NULL");
     ICREC_REQUIRE(allow == nullptr || ix->facets != nullptr, "icrec_search_faceted: allow masks on an index without facets");
     const bool facet = allow != nullptr;
+    const FacetArgs fa{ix->facets, allow, ix->n_facets};
     if (scores_out == nullptr && (ix->plane_hi != nullptr || ix->frag != nullptr)) {
         const Plan ex = make_plan(ix, Q, k, false, facet);
         const FilterPlan f = make_filter_plan(ix, Q, k, ex, facet);
@@ -1309,7 +1191,7 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
             }
             ICREC_HIP(hipSetDevice(ix->device));
             ScopedTimer whole(T_SEARCH, st);
-            return run_search_filtered(ix, f, ex, q, Q, k, ei, eo, allow, out_idx, out_score, out_keys, ws, st);
+            return run_search_filtered(ix, f, ex, q, Q, k, ei, eo, fa, out_idx, out_score, out_keys, ws, st);
         }
     }
     const Plan p = make_plan(ix, Q, k, scores_out == nullptr, facet);
@@ -1323,92 +1205,13 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
     u64* partial = reinterpret_cast<u64*>(reinterpret_cast<char*>(ws) + p.ws_q);
     hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3((p.Qpad + 3) / 4), dim3(256), 0, st, q, (void*)qn, (int64_t)Q,
                        (int64_t)p.Qpad, ix->dim, 1e-12f, p.variant == 3 ? p.Qpad : 0);
-    if (int rc = launch_exact(ix, p, qn, Q, k, ei, eo, allow, partial, scores_out, nullptr, st)) return rc;
+    if (int rc = launch_exact(ix, p, qn, Q, k, ei, eo, fa, partial, scores_out, nullptr, st)) return rc;
     if (out_idx || out_keys) {
-        if (Q <= 4 && p.n_chunks <= 256 && (int64_t)p.n_chunks * k <= MERGE_BLOCK_KEYS)
-            hipLaunchKernelGGL(merge_block_kernel, dim3(Q), dim3(256), 0, st, partial, p.n_chunks, p.Qpad, Q, k, out_idx,
-                               out_score, out_keys);
-        else
-            launch_merge(partial, p.n_chunks, p.Qpad, Q, k, out_idx, out_score, out_keys, st);
+        if (!launch_merge_block(partial, p.n_chunks, p.Qpad, Q, k, out_idx, out_score, out_keys, st))
+            launch_merge(partial, p.n_chunks, p.Qpad, Q, k, out_idx, out_score, out_keys, nullptr, st);
         ICREC_HIP(hipGetLastError());
     }
     return ICREC_OK;
-}
-
-// ---------------------------------------------------------------- full ranking (offline evaluation consumers)
-// The reference's ContentBasedBaseline.rank_all / compare_untrained_vs_trained (src/baselines/content_based.py:58-63,
-// scripts/compare_untrained_vs_trained.py:74-85) argsort every score row completely.  One workgroup per query sorts the
-// packed keys (orderable(score) << 32 | ~row: the search kernels' total order, score descending then row ascending)
-// with a bitonic network: P = next power of two >= n_rows keys per query in global scratch (pads = key 0, which sorts
-// last), stages with partner distance < 4,096 run on an 8,192-key segment in LDS, the rest in global memory.
-constexpr int RANK_SEG = 8192;  // keys per LDS segment (64 KB)
-__global__ __launch_bounds__(1024) void rank_keys_kernel(const float* __restrict__ scores, int64_t n_rows, int64_t P,
-                                                         u64* __restrict__ keys) {
-    const int64_t qi = blockIdx.y;
-    for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x; i < P; i += (int64_t)gridDim.x * 1024)
-        keys[qi * P + i] = i < n_rows ? make_key(scores[qi * n_rows + i], (uint32_t)i) : 0ull;
-}
-
-__global__ __launch_bounds__(1024) void rank_sort_kernel(u64* __restrict__ keys, int64_t P) {
-    __shared__ u64 seg[RANK_SEG];
-    u64* const a = keys + (int64_t)blockIdx.x * P;
-    const int t = threadIdx.x;
-    const int64_t seg_len = P < RANK_SEG ? P : RANK_SEG, nseg = P / seg_len;
-    // the stages j = j_hi, j_hi/2, ..., 1 of size-k merges, for one segment held in LDS (partners stay inside it)
-    auto local_stages = [&](int64_t base, int64_t k_lo, int64_t k_hi, int64_t j_cap) {
-        for (int64_t i = t; i < seg_len; i += 1024) seg[i] = a[base + i];
-        __syncthreads();
-        for (int64_t k = k_lo; k <= k_hi; k <<= 1)
-            for (int64_t j = (k >> 1) < j_cap ? (k >> 1) : j_cap; j >= 1; j >>= 1) {
-                for (int64_t p = t; p < seg_len / 2; p += 1024) {
-                    const int64_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                    u64 x = seg[i], y = seg[i | j];
-                    bitonic_cx(x, y, ((base + i) & k) == 0);
-                    seg[i] = x;
-                    seg[i | j] = y;
-                }
-                __syncthreads();
-            }
-        for (int64_t i = t; i < seg_len; i += 1024) a[base + i] = seg[i];
-        __syncthreads();
-    };
-    for (int64_t sidx = 0; sidx < nseg; ++sidx) local_stages(sidx * seg_len, 2, seg_len, seg_len / 2);  // k <= seg_len
-    for (int64_t k = seg_len * 2; k <= P; k <<= 1) {
-        for (int64_t j = k >> 1; j >= seg_len; j >>= 1) {  // partners in different segments: global memory
-            for (int64_t p = t; p < P / 2; p += 1024) {
-                const int64_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
-                u64 x = a[i], y = a[i | j];
-                bitonic_cx(x, y, (i & k) == 0);
-                a[i] = x;
-                a[i | j] = y;
-            }
-            __syncthreads();  // one workgroup owns the row; the barrier orders its global writes for its own reads
-        }
-        for (int64_t sidx = 0; sidx < nseg; ++sidx) local_stages(sidx * seg_len, k, k, seg_len / 2);
-    }
-}
-
-__global__ __launch_bounds__(256) void rank_emit_kernel(const u64* __restrict__ keys, int64_t n_rows, int64_t P,
-                                                        int64_t row_offset, int64_t* __restrict__ out) {
-    const int64_t qi = blockIdx.y;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_rows; i += (int64_t)gridDim.x * 256) {
-        const u64 key = keys[qi * P + i];  // key 0: a pad that sorted into the first n_rows (cf.hip's left-out rows)
-        out[qi * n_rows + i] = key ? row_offset + (int64_t)key_row(key) : -1;
-    }
-}
-
-int64_t rank_pow2(int64_t n) {
-    int64_t p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-// keys[n_queries][P] (P = rank_pow2(n_rows), pads = key 0) -> sorted descending in place -> out[n_queries][n_rows]
-void launch_rank_sort_emit(u64* keys, int64_t n_rows, int64_t P, int n_queries, int64_t row_offset, int64_t* out,
-                           hipStream_t st) {
-    const unsigned gx = (unsigned)((P + 1023) / 1024 < 64 ? (P + 1023) / 1024 : 64);
-    hipLaunchKernelGGL(rank_sort_kernel, dim3(n_queries), dim3(1024), 0, st, keys, P);
-    hipLaunchKernelGGL(rank_emit_kernel, dim3(gx * 4, n_queries), dim3(256), 0, st, (const u64*)keys, n_rows, P, row_offset, out);
 }
 
 }  // namespace icrec
@@ -1416,149 +1219,6 @@ void launch_rank_sort_emit(u64* keys, int64_t n_rows, int64_t P, int n_queries, 
 using namespace icrec;
 
 extern "C" {
-
-int icrec_index_create_ex(const float* rows_dev, int64_t n_rows, int32_t dim, int64_t row_offset, int device,
-                          int32_t storage, icrec_index** out) {
-    ICREC_REQUIRE(rows_dev && out, "icrec_index_create: NULL argument");
-    ICREC_REQUIRE(n_rows >= 1, "icrec_index_create: n_rows must be >= 1");
-    ICREC_REQUIRE(dim >= BK && dim % BK == 0 && dim <= 4096, "icrec_index_create: dim must be a multiple of %d (got %d)", BK, dim);
-    ICREC_REQUIRE(row_offset >= 0 && row_offset + n_rows < 0xFFFFFFFFll, "icrec_index_create: row_offset + n_rows must be < 2^32-1");
-    ICREC_REQUIRE(storage >= ICREC_ROWS_F32 && storage <= ICREC_ROWS_BF16_FILTER,
-                  "icrec_index_create: storage must be one of ICREC_ROWS_F32 (0), _BF16 (1), _F32_FILTER (2), _BF16_FILTER (3), got %d", storage);
-    const bool with_planes = storage == ICREC_ROWS_F32_FILTER || storage == ICREC_ROWS_BF16_FILTER;
-    const bool rows16 = storage == ICREC_ROWS_BF16 || storage == ICREC_ROWS_BF16_FILTER;
-    ICREC_REQUIRE(!with_planes || dim % HBK == 0, "icrec_index_create: the filter planes need dim %% %d == 0 (got %d)", HBK, dim);
-    // bf16 rows: the streaming kernel reads 128-byte slabs of 64 values, a final half slab would go unread
-    ICREC_REQUIRE(!rows16 || dim % 64 == 0, "icrec_index_create: bf16 rows need dim %% 64 == 0 (got %d)", dim);
-    ICREC_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    ICREC_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_error("icrec_index_create: device %d is %s, this library is built for gfx950 only", device, prop.gcnArchName);
-        return ICREC_ENODEV;
-    }
-    Index* ix = new Index();
-    ix->n_rows = n_rows; ix->dim = dim; ix->row_offset = row_offset; ix->device = device; ix->storage = storage;
-    ix->n_cu = prop.multiProcessorCount;
-    ix->stream_max_q = stream_max_q_from_env();
-    auto fail = [&]() {  // a hipMalloc failed: free what the index holds so far
-        icrec_index_destroy(reinterpret_cast<icrec_index*>(ix));
-        return ICREC_ENOMEM;
-    };
-    const size_t bytes = (size_t)n_rows * dim * (rows16 ? 2 : 4);
-    hipError_t e = hipMalloc(&ix->rows, bytes);
-    if (e != hipSuccess) {
-        set_error("icrec_index_create: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-        return fail();
-    }
-    hipLaunchKernelGGL((rows16 ? normalize_rows_kernel<true> : normalize_rows_kernel<false>), dim3((unsigned)((n_rows + 3) / 4)),
-                       dim3(256), 0, 0, rows_dev, ix->rows, n_rows, n_rows, dim, 1e-12f, 0);
-    ICREC_HIP(hipGetLastError());
-    const char* res_env = getenv("ICREC_FILTER_RESIDENT");  // "0": staged form; a number > 1: row limit of the resident form (A/B)
-    const int64_t res_max = res_env && atoll(res_env) > 1 ? atoll(res_env) : RES_MAX_ROWS;
-    if (with_planes && dim == 16 * RES_KS && n_rows <= res_max && !(res_env && res_env[0] == '0' && res_env[1] == 0)) {
-        // resident filter pass: packed fragments instead of the row-major planes
-        ix->frag_row_tiles = ((n_rows + CfgRes::BM - 1) / CfgRes::BM) * (CfgRes::BM / 32);
-        const int64_t n_frag = ix->frag_row_tiles * RES_KS;
-        if (hipMalloc(&ix->frag, (size_t)n_frag * 2 * WT_FRAG * sizeof(_Float16)) != hipSuccess) {
-            set_error("icrec_index_create: hipMalloc of the filter fragments (%zu bytes) failed", (size_t)n_frag * 2 * WT_FRAG * 2);
-            return fail();
-        }
-        // fragments of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
-        hipLaunchKernelGGL((rows16 ? pack_rows_kernel<true> : pack_rows_kernel<false>), dim3(4096), dim3(256), 0, 0,
-                           (const void*)ix->rows, n_rows, dim, n_frag, ix->frag);
-        ICREC_HIP(hipGetLastError());
-    } else if (with_planes) {
-        const size_t n = (size_t)n_rows * dim;
-        hipError_t e1 = hipMalloc(&ix->plane_hi, n * 2), e2 = hipMalloc(&ix->plane_lo, n * 2);
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            set_error("icrec_index_create: hipMalloc of the filter planes (2 x %zu bytes) failed", n * 2);
-            return fail();
-        }
-        // planes of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
-        hipLaunchKernelGGL((rows16 ? split_planes_kernel<true> : split_planes_kernel<false>), dim3(4096), dim3(256), 0, 0,
-                           (const void*)ix->rows, n, ix->plane_hi, ix->plane_lo, (int*)nullptr);
-        ICREC_HIP(hipGetLastError());
-    }
-    ICREC_HIP(hipStreamSynchronize(0));
-    *out = reinterpret_cast<icrec_index*>(ix);
-    return ICREC_OK;
-}
-
-int icrec_index_create(const float* rows_dev, int64_t n_rows, int32_t dim, int64_t row_offset, int device,
-                       icrec_index** out) {
-    return icrec_index_create_ex(rows_dev, n_rows, dim, row_offset, device, ICREC_ROWS_F32, out);
-}
-
-int32_t icrec_index_storage(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->storage : -1; }
-int32_t icrec_index_dim(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->dim : 0; }
-int32_t icrec_index_device(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->device : -1; }
-
-int icrec_index_destroy(icrec_index* h) {
-    Index* ix = reinterpret_cast<Index*>(h);
-    if (!ix) return ICREC_OK;
-    hipSetDevice(ix->device);
-    hipFree(ix->rows);
-    hipFree(ix->plane_hi);
-    hipFree(ix->plane_lo);
-    hipFree(ix->frag);
-    hipFree(ix->facets);
-    delete ix;
-    return ICREC_OK;
-}
-
-int icrec_index_set_facets(icrec_index* h, const uint8_t* facets_host, int32_t n_facets) {
-    Index* ix = reinterpret_cast<Index*>(h);
-    ICREC_REQUIRE(ix, "icrec_index_set_facets: NULL index");
-    ICREC_HIP(hipSetDevice(ix->device));
-    if (facets_host == nullptr) {
-        ICREC_HIP(hipFree(ix->facets));
-        ix->facets = nullptr;
-        ix->n_facets = 0;
-        return ICREC_OK;
-    }
-    ICREC_REQUIRE(n_facets >= 1 && n_facets <= ICREC_MAX_FACETS, "icrec_index_set_facets: n_facets must be in [1, %d] (got %d)",
-                  ICREC_MAX_FACETS, n_facets);
-    // one word per row, zero padded to whole 256-row tiles (the widest tile any search kernel walks)
-    const size_t padded = (size_t)((ix->n_rows + 255) / 256) * 256;
-    std::vector<uint16_t> words(padded, 0);
-    for (int64_t i = 0; i < ix->n_rows; ++i)
-        words[i] = n_facets == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * i] | (facets_host[2 * i + 1] << 8));
-    uint16_t* dev = nullptr;
-    if (hipMalloc(&dev, padded * 2) != hipSuccess) {
-        set_error("icrec_index_set_facets: hipMalloc of %zu bytes failed", padded * 2);
-        return ICREC_ENOMEM;
-    }
-    if (hipMemcpy(dev, words.data(), padded * 2, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dev);
-        set_error("icrec_index_set_facets: copying the facets to the device failed");
-        return ICREC_EHIP;
-    }
-    (void)hipFree(ix->facets);
-    ix->facets = dev;
-    ix->n_facets = n_facets;
-    return ICREC_OK;
-}
-
-int32_t icrec_index_facets(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_facets : -1; }
-
-int64_t icrec_index_rows(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_rows : 0; }
-int64_t icrec_index_row_offset(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->row_offset : 0; }
-
-int icrec_index_export(const icrec_index* h, float* rows_dev, void* stream) {
-    const Index* ix = reinterpret_cast<const Index*>(h);
-    ICREC_REQUIRE(ix && rows_dev, "icrec_index_export: NULL argument");
-    const int64_t n = ix->n_rows * ix->dim;
-    if (rows_are_bf16(ix)) {
-        ICREC_HIP(hipSetDevice(ix->device));
-        hipLaunchKernelGGL(widen_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           static_cast<const uint16_t*>(ix->rows), rows_dev, n);
-        ICREC_HIP(hipGetLastError());
-    } else {
-        ICREC_HIP(hipMemcpyAsync(rows_dev, ix->rows, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    }
-    return ICREC_OK;
-}
 
 size_t icrec_search_workspace_bytes(const icrec_index* h, int32_t n_queries, int32_t k) {
     const Index* ix = reinterpret_cast<const Index*>(h);
@@ -1601,61 +1261,6 @@ int icrec_scores(icrec_index* h, const float* q_dev, int32_t n_queries, float* o
     ICREC_REQUIRE(out_dev, "icrec_scores: NULL output");
     return run_search(reinterpret_cast<Index*>(h), q_dev, n_queries, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
                       out_dev, ws, ws_bytes, (hipStream_t)stream);
-}
-
-size_t icrec_rank_all_workspace_bytes(const icrec_index* h, int32_t n_queries) {
-    const Index* ix = reinterpret_cast<const Index*>(h);
-    if (!ix || n_queries < 1) return 0;
-    const size_t sw = icrec_search_workspace_bytes(h, n_queries, 1);
-    if (sw == 0) return 0;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    return al((size_t)n_queries * ix->n_rows * 4) + al((size_t)n_queries * rank_pow2(ix->n_rows) * 8) + al(sw);
-}
-
-int icrec_rank_all(icrec_index* h, const float* q_dev, int32_t n_queries, int64_t* out_rows_dev, void* ws,
-                   size_t ws_bytes, void* stream) {
-    Index* ix = reinterpret_cast<Index*>(h);
-    ICREC_REQUIRE(ix && q_dev && out_rows_dev && n_queries >= 1, "icrec_rank_all: bad argument");
-    const size_t need = icrec_rank_all_workspace_bytes(h, n_queries);
-    if (!ws || ws_bytes < need || need == 0) {
-        set_error("icrec_rank_all: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ICREC_ENOMEM;
-    }
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const int64_t P = rank_pow2(ix->n_rows);
-    char* base = reinterpret_cast<char*>(ws);
-    float* scores = reinterpret_cast<float*>(base);
-    u64* keys = reinterpret_cast<u64*>(base + al((size_t)n_queries * ix->n_rows * 4));
-    char* sws = reinterpret_cast<char*>(keys) + al((size_t)n_queries * P * 8);
-    if (int rc = icrec_scores(h, q_dev, n_queries, scores, sws, ws_bytes - (size_t)(sws - base), stream)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned gx = (unsigned)((P + 1023) / 1024 < 64 ? (P + 1023) / 1024 : 64);
-    hipLaunchKernelGGL(rank_keys_kernel, dim3(gx, n_queries), dim3(1024), 0, st, scores, ix->n_rows, P, keys);
-    launch_rank_sort_emit(keys, ix->n_rows, P, n_queries, ix->row_offset, out_rows_dev, st);
-    ICREC_HIP(hipGetLastError());
-    return ICREC_OK;
-}
-
-int icrec_merge_topk(const uint64_t* keys_dev, int32_t n_lists, int32_t n_queries, int32_t k, int64_t* out_idx_dev,
-                     float* out_score_dev, int device, void* stream) {
-    ICREC_REQUIRE(keys_dev && out_idx_dev && out_score_dev, "icrec_merge_topk: NULL argument");
-    ICREC_REQUIRE(n_lists >= 1 && n_lists <= MERGE_MAX_LISTS, "icrec_merge_topk: n_lists must be in [1, %d]", MERGE_MAX_LISTS);
-    ICREC_REQUIRE(n_queries >= 1 && k >= 1 && k <= ICREC_MAX_K, "icrec_merge_topk: bad n_queries/k");
-    ICREC_HIP(hipSetDevice(device));
-    launch_merge(reinterpret_cast<const u64*>(keys_dev), n_lists, n_queries, n_queries, k, out_idx_dev, out_score_dev,
-                 nullptr, (hipStream_t)stream);
-    ICREC_HIP(hipGetLastError());
-    return ICREC_OK;
-}
-
-int icrec_normalize_rows(const float* x_dev, float* out_dev, int64_t n_rows, int32_t dim, float eps, int device,
-                         void* stream) {
-    ICREC_REQUIRE(x_dev && out_dev && n_rows >= 1 && dim >= 1, "icrec_normalize_rows: bad argument");
-    ICREC_HIP(hipSetDevice(device));
-    hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       x_dev, (void*)out_dev, n_rows, n_rows, dim, eps);
-    ICREC_HIP(hipGetLastError());
-    return ICREC_OK;
 }
 
 }  // extern "C"
