@@ -1,8 +1,9 @@
 """Shared by the search GPU tests (test_search_gpu, test_search_dims_gpu, test_sharded_gpu, the search tests of
 test_baseline_sizes_gpu): the imports and the GPU fixture, the check of an index against the oracle, the random
 exclusion lists (one function per draw sequence), shard cutting, the tie-block catalog, the launch timers, the
-properties of a result list, the memoised bench catalog, the launch plans and the selection in numpy, and which rows
-a query's facet masks admit.  One definition each; importing this needs no GPU."""
+properties of a result list, the memoised bench catalog, the launch plans and the selection in numpy, which rows
+a query's facet masks admit, the packed ranking keys and the merges in numpy, and the restatement of the exclusion
+exchange's CSR.  One definition each; importing this needs no GPU."""
 from __future__ import annotations
 
 import functools
@@ -83,6 +84,67 @@ def tiled_plan(n_rows, Q, k, n_cu):
     return variant, BM, BN, n_qtiles, tiles_per_chunk, n_chunks
 
 
+def stream_plan(n_rows, Q, n_cu, stream_max_q=8):
+    """csrc/search.hip's make_plan with allow_stream true, the branch of variant 3 (stream_search_kernel), and its
+    plan_chunks, restated with the same integer arithmetic -> ("stream", 256, BN, 1, tiles_per_chunk, n_chunks), the
+    tuple of tiled_plan; None where make_plan takes a tiled kernel instead: more than stream_max_q queries (8 unless
+    ICREC_STREAM_MAX_Q said otherwise when the index was made), or 3 .. 8 queries over fewer than 6 tiles of 256 rows
+    per CU.  One block per chunk, one sorted list per chunk and query, at most 1,024 chunks (MERGE_MAX_LISTS)."""
+    BM = 256
+    n_row_tiles = (n_rows + BM - 1) // BM
+    if not (Q <= stream_max_q and (Q <= 2 or n_row_tiles >= 2 * 3 * n_cu)):
+        return None
+    BN = 1 if Q <= 1 else 2 if Q <= 2 else 4 if Q <= 4 else 8
+    want = min(max(3 * n_cu, 1), 1024)
+    want = min(want, n_row_tiles)
+    tiles_per_chunk = (n_row_tiles + want - 1) // want
+    n_chunks = (n_row_tiles + tiles_per_chunk - 1) // tiles_per_chunk
+    return "stream", BM, BN, 1, tiles_per_chunk, n_chunks
+
+
+def search_plan(n_rows, Q, k, n_cu):
+    """The plan icrec_search takes on a plain (f32 or bf16) index: stream_plan where it applies, else tiled_plan."""
+    return stream_plan(n_rows, Q, n_cu) or tiled_plan(n_rows, Q, k, n_cu)
+
+
+MERGE_BLOCK_KEYS, MERGE_MAX_LISTS = 16 * 256, 1024   # csrc/sort.hip, csrc/common.h
+
+
+def merge_form(n_lists, Q, k, block=True):
+    """Which kernel of csrc/sort.hip merges n_lists lists of k keys for Q queries: "block" (merge_block_kernel,
+    launch_merge_block's condition), else launch_merge's arm, "wave4" (merge_kernel<4>, up to 256 lists) or "wave16"
+    (merge_kernel<16>).  block=False: a caller that never tries the block merge (icrec_merge_topk; a search does)."""
+    assert 1 <= n_lists <= MERGE_MAX_LISTS
+    if block and Q <= 4 and n_lists <= 256 and n_lists * k <= MERGE_BLOCK_KEYS:
+        return "block"
+    return "wave4" if n_lists <= 256 else "wave16"
+
+
+def plan_workspace_bytes(plan, dim, k):
+    """Plan::ws_q + Plan::ws_partial of make_plan for a plan tuple: [queries, padded to whole tiles | one list of k keys
+    per chunk and padded query], each part rounded up to 256 B."""
+    _, _, BN, n_qtiles, _, n_chunks = plan
+    up = lambda v: (v + 255) & ~255  # noqa: E731
+    Qpad = n_qtiles * BN
+    return up(Qpad * dim * 4) + up(n_chunks * Qpad * k * 8)
+
+
+def assert_plan_is_the_librarys(ix, Q, k, plan):
+    """plan is the one a search of Q queries at k takes on the plain (f32 or bf16) index ix, and the library cuts the
+    rows as the restated plans do: icrec_search_workspace_bytes returns, for an index without filter planes, the larger
+    of its tiled plan's and its streaming plan's workspace (the same plan twice where no streaming kernel applies),
+    each laid out as plan_workspace_bytes says - the library's own BN and chunk counts, against tiled_plan's and
+    stream_plan's.  This restates icrec_search_workspace_bytes and make_plan in csrc/search.hip: when that layout
+    changes, this function changes with it.  (Where a search streams, the tiled plan's lists of 32 padded queries are
+    the larger part: the streaming plan's chunk count then shows in the sum only where it is the larger one.)"""
+    tiled = tiled_plan(ix.n_rows, Q, k, n_cu())
+    stream = stream_plan(ix.n_rows, Q, n_cu())
+    assert plan == (stream or tiled), (plan, stream, tiled)
+    want = max(plan_workspace_bytes(p, ix.dim, k) for p in (tiled, stream) if p is not None)
+    got = int(_native.lib().icrec_search_workspace_bytes(ix._h, Q, k))
+    assert got == want, (got, want, plan)
+
+
 def select_from_scores(scores, k, excl=None, row_offset=0, admit=None):
     """The library's selection on a complete [Q, n] float32 score matrix: per query the k best rows that its list
     excl[i] (local rows, as oracle.search takes them) does not name, score descending and row ascending among equal
@@ -155,6 +217,81 @@ def first_pass_offers(tile_scores, k, BM):
         t = distinct[m - 1] if distinct.size >= m else -np.inf
         offered[group == g] = mine >= t
     return offered
+
+
+# ---------------------------------------------------------------- packed ranking keys and their merges, in numpy
+def pack_keys(scores, rows):
+    """csrc/common.h's make_key: (orderable(score bits) << 32) | (0xFFFFFFFF - row), uint64, where orderable flips
+    every bit of a negative score and sets the sign bit of the others - a larger key is a better hit under (score
+    descending, row ascending).  scores: float32, rows: integers in [0, 2^32 - 2], broadcast against each other.  The
+    score's bits are taken as they are: -0.0 packs below +0.0 (the search kernels add +0 first; this does not)."""
+    s, r = np.broadcast_arrays(np.asarray(scores, np.float32), np.asarray(rows))
+    assert r.dtype.kind in "iu" and (r >= 0).all() and (r <= 0xFFFFFFFE).all()
+    u = np.ascontiguousarray(s).view(np.uint32).ravel()
+    ordered = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    return ((ordered.astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - r.astype(np.uint64).ravel())).reshape(s.shape)
+
+
+def unpack_keys(keys):
+    """csrc/common.h's store_key: keys uint64 -> (idx int64, score float32) with the score's BITS as they were packed;
+    key 0, the pad, gives (-1, 0.0)."""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    hi = (keys >> np.uint64(32)).astype(np.uint32)
+    u = np.where(hi & np.uint32(0x80000000), hi & np.uint32(0x7FFFFFFF), ~hi)
+    score = np.ascontiguousarray(u).view(np.float32)
+    idx = (np.uint64(0xFFFFFFFF) - (keys & np.uint64(0xFFFFFFFF))).astype(np.int64)
+    pad = keys == 0
+    return np.where(pad, np.int64(-1), idx), np.where(pad, np.float32(0.0), score)
+
+
+def merge_reference(keys, k):
+    """The k-way merge on keys uint64 [n_lists, Q, k]: per query ALL its keys sorted as descending integers, the first k
+    kept and decoded with unpack_keys -> (idx int64 [Q, k], score float32 [Q, k]).  Pads (key 0) sort last."""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    n_lists, Q, kk = keys.shape
+    assert kk == k
+    per_query = keys.transpose(1, 0, 2).reshape(Q, n_lists * k)
+    return unpack_keys(np.sort(per_query, axis=1)[:, ::-1][:, :k])
+
+
+def block_merge_candidates(scores_row, k, BM, tiles_per_chunk):
+    """How many keys C merge_block_kernel (csrc/sort.hip) ranks for one query: the rows are cut into chunks of
+    tiles_per_chunk tiles of BM rows, each chunk gives its k best keys as one sorted list (fewer where it has fewer
+    admissible rows); h is the k-th largest list head, or 0 if fewer than k lists are non-empty; C counts the keys
+    >= h in the lists whose head is >= h.  The kernel's ranking loop takes a second trip iff C > 256.
+    scores_row: float32 [n], inadmissible rows at -inf; -0 counts as +0, as in the search kernels."""
+    s = np.ascontiguousarray(scores_row, np.float32)
+    n = s.size
+    keys = pack_keys(s + np.float32(0.0), np.arange(n))
+    keys[np.isneginf(s)] = 0
+    block = BM * tiles_per_chunk
+    n_chunks = (n + block - 1) // block
+    padded = np.zeros(n_chunks * max(block, k), np.uint64).reshape(n_chunks, -1)
+    for c in range(n_chunks):
+        mine = keys[c * block:(c + 1) * block]
+        padded[c, :mine.size] = mine
+    lists = np.sort(padded, axis=1)[:, ::-1][:, :k]
+    heads = lists[:, 0]
+    real = np.sort(heads[heads != 0])[::-1]
+    h = real[k - 1] if real.size >= k else np.uint64(0)
+    taken = lists[(heads != 0) & (heads >= h)]
+    return int(((taken != 0) & (taken >= h)).sum())
+
+
+# ---------------------------------------------------------------- the exclusion exchange's CSR, in numpy
+def csr_restatement(off_all, rows_all, cap, row_lo, row_hi):
+    """numpy restatement of comm.hip's excl_sanitize / count / scan / fill: offsets clamped to [0, cap] and made
+    non-decreasing by a running maximum, then per gathered query (rank-major) the ids inside [row_lo, row_hi), rebased."""
+    world, n1 = off_all.shape
+    off = np.maximum.accumulate(np.clip(off_all.astype(np.int64), 0, cap), axis=1)
+    csr_off, csr_idx = [0], []
+    for r in range(world):
+        for i in range(n1 - 1):
+            seg = rows_all[r, off[r, i]:off[r, i + 1]].astype(np.int64)
+            seg = seg[(seg >= row_lo) & (seg < row_hi)] - row_lo
+            csr_idx.extend(seg.tolist())
+            csr_off.append(len(csr_idx))
+    return np.asarray(csr_off, np.int32), np.asarray(csr_idx, np.int32)
 
 
 # ---------------------------------------------------------------- facets: which rows a query's allow masks admit

@@ -57,8 +57,10 @@ def check(ranked, relevant):
     return sums, pq, means
 
 
-@pytest.mark.parametrize("Q", [1, 65, 1000])
-@pytest.mark.parametrize("depth", [1, 10, 100, 128])
+# ir_reduce_kernel's thread t adds queries t, t + 1024, ...: from 1,025 queries on some threads add a second value, at
+# 2,500 some a third and some only two (depth 10 and 128 only there: the reference is a Python loop)
+@pytest.mark.parametrize("depth,Q", [(depth, Q) for Q in (1, 65, 1000) for depth in (1, 10, 100, 128)]
+                         + [(depth, Q) for Q in (1024, 1025, 2500) for depth in (10, 128)])
 def test_metrics_match_reference(Q, depth):
     ranked, relevant = make_case(Q, depth, seed=Q * 131 + depth)
     if Q == 1:
@@ -95,9 +97,10 @@ def test_short_lists_and_large_relevant_sets():
 
 
 def test_two_runs_give_identical_bits():
-    ranked, relevant = make_case(1000, 100, seed=5)
-    a, b = run_device(ranked, relevant), run_device(ranked, relevant)
-    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+    for Q in (1000, 2500):   # 2,500: the threads of ir_reduce_kernel add two or three values each
+        ranked, relevant = make_case(Q, 100, seed=5)
+        a, b = run_device(ranked, relevant), run_device(ranked, relevant)
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
 
 
 def test_compute_ir_metrics_on_id_strings():

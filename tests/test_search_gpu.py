@@ -7,8 +7,8 @@ import torch
 
 from tests.conftest import excl_lists
 from tests.search_harness import (DeviceIndex, assert_ranked_lists, assert_search, bench_catalog, bench_queries, check,
-                                  distinct_exclusions, full_ranking, merge_topk, oracle, search, sharded_partial_keys,
-                                  synthetic as syn, tie_block_catalog, timed)
+                                  distinct_exclusions, full_ranking, merge_topk, oracle, pack_keys, search,
+                                  sharded_partial_keys, synthetic as syn, tie_block_catalog, timed)
 from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -204,9 +204,7 @@ def test_merge_many_lists(torch_cuda):
     sc = rng.standard_normal((n_lists, Q, k)).astype(np.float32)
     sc = -np.sort(-sc, axis=2)
     idx = (np.arange(n_lists)[:, None, None] * 1000 + np.arange(k)[None, None, :] + np.zeros((1, Q, 1), np.int64)).astype(np.int64)
-    u = sc.view(np.uint32).astype(np.uint64)
-    u = np.where(u & 0x80000000, ~u & 0xFFFFFFFF, u | 0x80000000)
-    keys = (u << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - idx.astype(np.uint64))
+    keys = pack_keys(sc, idx)
     assert_search(merge_topk(torch.from_numpy(keys.view(np.int64)).cuda(), k), oracle.merge(idx, sc))
 
 

@@ -14,9 +14,9 @@ import numpy as np
 import pytest
 import torch
 
-from tests.search_harness import (DeviceIndex, _native, assert_search, direction_catalog, first_pass_offers,
-                                  merge_topk, n_cu, oracle, select_from_scores, tie_run_catalog, tiled_plan, timed,
-                                  warm_tile_beaters)
+from tests.search_harness import (DeviceIndex, assert_plan_is_the_librarys, assert_search, direction_catalog,
+                                  first_pass_offers, merge_topk, n_cu, oracle, select_from_scores, tie_run_catalog,
+                                  tiled_plan, timed, warm_tile_beaters)
 from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -109,18 +109,6 @@ def exclusion_lists(top8, runs, n, rng):
             e |= set(range(runs[0][0], runs[0][1] - 10))
         excl.append(sorted(e))
     return excl, np.asarray(top_rows)
-
-
-def assert_plan_is_the_librarys(ix, Q, k, plan):
-    """A plain (f32 or bf16) index sizes its workspace as [queries, padded to whole tiles | one list of k keys per chunk
-    and padded query], each part rounded up to 256 B: the library's own BN and chunk count, against tiled_plan's.
-    This restates Plan::ws_q and Plan::ws_partial of make_plan in csrc/search.hip (icrec_search_workspace_bytes returns
-    their sum for an index without filter planes): when that layout changes, this function changes with it."""
-    _, _, BN, n_qtiles, _, n_chunks = plan
-    up = lambda v: (v + 255) & ~255  # noqa: E731
-    Qpad = n_qtiles * BN
-    got = int(_native.lib().icrec_search_workspace_bytes(ix._h, Q, k))
-    assert got == up(Qpad * ix.dim * 4) + up(n_chunks * Qpad * k * 8), (got, plan)
 
 
 @pytest.mark.parametrize("storage", ["f32", "bf16"])

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from tests.search_harness import (DeviceIndex, HipShardBackend, NativeComm, ShardedSearch, assert_ranked_lists,
-                                  assert_search, bench_catalog, bench_queries, exclusions_to_shard_csr,
+                                  assert_search, bench_catalog, bench_queries, csr_restatement, exclusions_to_shard_csr,
                                   local_exclusions, merge_topk, oracle, redrawn_exclusions, shard_bounds,
                                   sharded_partial_keys, synthetic as syn)
 
@@ -180,21 +180,6 @@ def test_configs3_sizes_4096_queries():
     fi.close(); ei.close()
 
 
-def _csr_restatement(off_all, rows_all, cap, row_lo, row_hi):
-    """numpy restatement of comm.hip's excl_sanitize / count / scan / fill: offsets clamped to [0, cap] and made
-    non-decreasing by a running maximum, then per gathered query (rank-major) the ids inside [row_lo, row_hi), rebased."""
-    world, n1 = off_all.shape
-    off = np.maximum.accumulate(np.clip(off_all.astype(np.int64), 0, cap), axis=1)
-    csr_off, csr_idx = [0], []
-    for r in range(world):
-        for i in range(n1 - 1):
-            seg = rows_all[r, off[r, i]:off[r, i + 1]].astype(np.int64)
-            seg = seg[(seg >= row_lo) & (seg < row_hi)] - row_lo
-            csr_idx.extend(seg.tolist())
-            csr_off.append(len(csr_idx))
-    return np.asarray(csr_off, np.int32), np.asarray(csr_idx, np.int32)
-
-
 def test_exclusion_exchange_layout_world8_on_one_gpu():
     """The W > 1 branch of icrec_search_sharded_excl without a second GPU: the device-side step
     (icrec_exclusions_to_shard_csr = excl_sanitize / count / scan / fill of csrc/comm.hip) on gathered buffers laid out
@@ -228,7 +213,7 @@ def test_exclusion_exchange_layout_world8_on_one_gpu():
         rows_all[r, :len(flat)] = flat
         rows_all[r, len(flat):] = 7          # padding past the last offset must be ignored
     assert off_all[5, -1] == cap
-    want_off, want_idx = _csr_restatement(off_all, rows_all, cap, lo, hi)
+    want_off, want_idx = csr_restatement(off_all, rows_all, cap, lo, hi)
     got_off, got_idx = exclusions_to_shard_csr(torch.from_numpy(off_all).to(dev), torch.from_numpy(rows_all).to(dev), lo, hi)
     np.testing.assert_array_equal(got_off.cpu().numpy(), want_off)
     np.testing.assert_array_equal(got_idx.cpu().numpy()[:want_off[-1]], want_idx)
@@ -248,12 +233,79 @@ def test_exclusion_exchange_layout_world8_on_one_gpu():
     bad[1, 1:9] = [-5, 2 * cap, 3, 2, 1, -1, cap + 1, 0]
     bad[2] = bad[2][::-1]
     bad[4, -1] = 2**31 - 1
-    want_off, want_idx = _csr_restatement(bad, rows_all, cap, lo, hi)
+    want_off, want_idx = csr_restatement(bad, rows_all, cap, lo, hi)
     assert want_off[-1] <= W * cap
     got_off, got_idx = exclusions_to_shard_csr(torch.from_numpy(bad).to(dev), torch.from_numpy(rows_all).to(dev), lo, hi)
     torch.cuda.synchronize()
     np.testing.assert_array_equal(got_off.cpu().numpy(), want_off)
     np.testing.assert_array_equal(got_idx.cpu().numpy()[:want_off[-1]], want_idx)
+
+
+def _scan_case_lists(rng, world, n_local, cap, id_space):
+    """Well-formed gathered buffers: rank 0 fills its buffer to the last slot, the last rank of three or more has no
+    exclusion at all, the others draw 0 .. 2 cap / n_local ids per query (a fifth of the queries none); the slots past
+    a rank's last offset hold 7, which must be ignored."""
+    off_all = np.zeros((world, n_local + 1), np.int32)
+    rows_all = np.full((world, cap), 7, np.int32)
+    for r in range(world):
+        if r == 0:
+            cuts = np.sort(rng.integers(0, cap + 1, size=n_local - 1))
+            counts = np.diff(np.concatenate([[0], cuts, [cap]]))
+        elif r == world - 1 and world >= 3:
+            counts = np.zeros(n_local, np.int64)
+        else:
+            counts = rng.integers(0, 2 * cap // n_local + 1, size=n_local) * (rng.random(n_local) < 0.8)
+            while counts.sum() > cap:
+                counts //= 2
+        flat = [np.sort(rng.choice(id_space, size=int(c), replace=False)) for c in counts]
+        off_all[r, 1:] = np.cumsum(counts)
+        rows_all[r, :off_all[r, -1]] = np.concatenate(flat) if flat else []
+    assert off_all[0, -1] == cap
+    return off_all, rows_all
+
+
+@pytest.mark.parametrize("world,n_local", [(1, 1023), (1, 1024), (2, 1025), (3, 2049), (5, 13)])
+def test_exclusion_scans_carry_across_chunks(world, n_local):
+    """excl_sanitize_kernel walks each rank's n_local + 1 offsets in chunks of 1,024 with a carried running maximum,
+    excl_scan_kernel the world * n_local counts likewise with a carried sum: one full chunk (1,023 + 1 offsets), a chunk
+    and one entry, three chunks, counts that are no multiple of 1,024 (3,075 and 6,147) and fewer than one wavefront of
+    them (65), against the numpy restatement; cap = 4,096 ids per rank, the shard holds rows 2,000 .. 4,999 of 10,000.
+    Then malformed offsets placed so that the carry decides: the maximum in chunk 0 (entry 5 = cap - 7) followed by
+    decreasing and negative values through every later chunk; a spike in the last wavefront of chunk 0 that chunk 1
+    inherits; a value beyond cap at entry 1,024 exactly, the first of chunk 1.  csr_idx comes back zero-filled from
+    the wrapper: the slots past the last offset are still zero."""
+    dev = torch.device("cuda:0")
+    cap, id_space, lo, hi = 4096, 10_000, 2000, 5000
+    rng = np.random.default_rng(world * 10_000 + n_local)
+    off_all, rows_all = _scan_case_lists(rng, world, n_local, cap, id_space)
+    n1 = n_local + 1
+    variants = [("well-formed", off_all)]
+    r = world - 2 if world >= 3 else world - 1     # a rank with random lists where there is one
+    bad = off_all.copy()
+    bad[r, 5] = cap - 7
+    bad[r, 6:] = (cap - 8 - 5 * np.arange(n1 - 6)).astype(np.int32)          # below zero from entry 824 on
+    variants.append(("maximum in chunk 0", bad))
+    if n1 > 1024:
+        bad = off_all.copy()
+        bad[r, :1000] = np.minimum(bad[r, :1000], cap // 2)
+        bad[r, 1000] = cap - 3                                                # wavefront 15 of chunk 0
+        bad[r, 1001:] = np.minimum(bad[r, 1001:], cap // 2 - 5)
+        bad[r, 1030:1040] = -3
+        variants.append(("spike in wavefront 15", bad))
+        bad = off_all.copy()
+        bad[r, 1024] = cap + 5
+        bad[r, 1025:] = (np.arange(n1 - 1025) % 9 - 4).astype(np.int32)
+        variants.append(("beyond cap at entry 1,024", bad))
+    for what, off in variants:
+        want_off, want_idx = csr_restatement(off, rows_all, cap, lo, hi)
+        assert want_off[-1] <= world * cap, what
+        assert want_off.size == world * n_local + 1
+        got_off, got_idx = exclusions_to_shard_csr(torch.from_numpy(off).to(dev), torch.from_numpy(rows_all).to(dev), lo, hi)
+        torch.cuda.synchronize()
+        got_idx = got_idx.cpu().numpy()
+        np.testing.assert_array_equal(got_off.cpu().numpy(), want_off, err_msg=what)
+        np.testing.assert_array_equal(got_idx[:want_off[-1]], want_idx, err_msg=what)
+        assert got_idx.size == world * cap and not got_idx[want_off[-1]:].any(), what
 
 
 def test_gathered_partial_keys_layout_world8_on_one_gpu():
