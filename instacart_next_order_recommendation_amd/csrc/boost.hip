@@ -33,11 +33,8 @@ __device__ __forceinline__ int list_len(const int32_t* __restrict__ off, int64_t
 // One wave per 32 listed entries of one query: the entries' rows are operand A of v_mfma_f32_32x32x2_f32, the query is
 // every column of operand B, so each of the 32 columns of the tile holds the 32 cosines
 //   s = 0; for j = 0 .. dim-1: s = fmaf(q_hat[j], p[j], s)
-// (common.h: each step adds the products of two consecutive j in order; lanes 0-31 supply the even j of a step and
-// lanes 32-63 the odd j).  As in mmr_gram_kernel a lane reads the 32 consecutive values of its row that sixteen steps
-// consume straight from global memory (128 B of fp32, 64 B of bf16 widened exactly) and keeps its half; the query's
-// values are one address for the whole wave.  Entry r's cosine is taken from column r: the lane r or r + 32 whose
-// accumulator rows (acc_row) include r.
+// by common.h's gathered_tile (fmaf(p[j], q_hat[j], s) is the same value); the query's values are one address for the
+// whole wave.  Entry r's cosine is taken from column r: the lane r or r + 32 whose accumulator rows (acc_row) include r.
 // An invalid entry (row outside the shard, excluded, or refused by the query's facet masks) gets the word 0; its lanes
 // read row 0 of the shard instead, so nothing outside the rows is touched.  A tile without a valid entry does no math.
 template <bool P16>
@@ -78,41 +75,7 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void boost_score_kernel(
     for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
     if (__ballot(valid) != 0ull) {  // wave-uniform
         const int64_t lr = valid ? row : 0;
-        const float* pb = qn + (size_t)q * K;
-        if (P16) {
-            const uint16_t* pa = static_cast<const uint16_t*>(rows) + lr * K;
-            for (int d0 = 0; d0 < K; d0 += BK) {  // (dim is a multiple of BK = 32)
-                u32x4 a[4];  // word w of a[u]: d0 + 8u + 2w (low half), d0 + 8u + 2w + 1 (high half)
-                f32x4 b[8];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const u32x4*>(pa + d0 + 8 * u);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) b[u] = *reinterpret_cast<const f32x4*>(pb + d0 + 4 * u);
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int x = 0; x < 4; ++x) {
-                        const f32x4 bq = b[2 * u + (x >> 1)];
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? bf16_hi(a[u][x]) : bf16_lo(a[u][x]),
-                                                                   h ? bq[2 * (x & 1) + 1] : bq[2 * (x & 1)], acc, 0, 0, 0);
-                    }
-            }
-        } else {
-            const float* pa = static_cast<const float*>(rows) + lr * K;
-            for (int d0 = 0; d0 < K; d0 += BK) {  // (dim is a multiple of BK = 32)
-                f32x4 a[8], b[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    a[u] = *reinterpret_cast<const f32x4*>(pa + d0 + 4 * u);
-                    b[u] = *reinterpret_cast<const f32x4*>(pb + d0 + 4 * u);
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a[u][1] : a[u][0], h ? b[u][1] : b[u][0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a[u][3] : a[u][2], h ? b[u][3] : b[u][2], acc, 0, 0, 0);
-                }
-            }
-        }
+        gathered_tile(acc, static_cast<const row_elem_t<P16>*>(rows) + lr * K, qn + (size_t)q * K, K, h);
     }
     // acc[i]: entry t * 32 + acc_row(i, lane) (operand A) against the query (every column).  Entry r sits in the
     // half of the wave with h == bit 2 of r; lanes r and r + 32 hold the same row, weight and validity.
@@ -160,9 +123,8 @@ __global__ __launch_bounds__(SELECT_THREADS) void boost_select_kernel(
             if (s & SCORED_VALID) key = order_key(__uint_as_float((uint32_t)(s >> 32)), (uint32_t)boost_rows[(int64_t)start + i], nz, &nz_n);
         } else if (i < n) {
             const int j = i - n_b;
-            const int64_t c = cand_idx[q * k + j];
-            const int64_t lr = c - row_offset;
-            if (c >= 0 && lr >= 0 && lr < n_rows && !(lr <= 0x7FFFFFFFll && excluded(boost_rows, start, start + n_b, (int)lr)))
+            const int64_t lr = local_row(cand_idx[q * k + j], row_offset, n_rows);
+            if (lr >= 0 && !(lr <= 0x7FFFFFFFll && excluded(boost_rows, start, start + n_b, (int)lr)))
                 key = order_key(cand_score[q * k + j], (uint32_t)lr, nz, &nz_n);
         }
         keys[i] = key;

@@ -7,7 +7,8 @@
 // bits per item, a thread walks one basket and counts per bit.  Pass B (product-major) sums w over a product's
 // column; w is stored [tile][order][T] so one column entry serves the whole tile with one contiguous read.  Scores
 // are int32 and exact in any summation order; they become keys ((score + 1) << 32) | ~row, the total order of
-// make_key's keys with 0 as the pad / "left out" value, and are sorted by sort.hip's sorters (common.h).
+// make_key's keys with 0 as the pad / "left out" value, and are sorted by sort.hip's sorters (common.h); the CSR
+// offsets of the index are sort.hip's prefix sums.
 #include <stdlib.h>
 
 #include <vector>
@@ -53,40 +54,6 @@ __global__ __launch_bounds__(256) void cf_dedup_kernel(const int64_t* __restrict
     if (first) {
         atomicAdd(&b_len[lo], 1);
         atomicAdd(&c_len[it], 1);
-    }
-}
-
-// out[0..n] = exclusive prefix sums of len[0..n), stats[slot] = max(len): one workgroup, contiguous slices per thread.
-__global__ __launch_bounds__(1024) void cf_scan_kernel(const int32_t* __restrict__ len, int64_t n, int32_t* __restrict__ out,
-                                                       int32_t* __restrict__ stats, int slot) {
-    __shared__ int32_t part[1024];
-    __shared__ int32_t pmax[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024, lo = t * per, hi = lo + per < n ? lo + per : n;
-    int32_t s = 0, m = 0;
-    for (int64_t i = lo; i < hi; ++i) {
-        s += len[i];
-        m = len[i] > m ? len[i] : m;
-    }
-    part[t] = s;
-    pmax[t] = m;
-    __syncthreads();
-    if (t == 0) {
-        int32_t run = 0, mx = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const int32_t v = part[i];
-            part[i] = run;
-            run += v;
-            mx = pmax[i] > mx ? pmax[i] : mx;
-        }
-        out[n] = run;
-        stats[slot] = mx;
-    }
-    __syncthreads();
-    int32_t run = part[t];
-    for (int64_t i = lo; i < hi; ++i) {
-        out[i] = run;
-        run += len[i];
     }
 }
 
@@ -380,8 +347,8 @@ int icrec_cf_create(const int64_t* order_off, const int32_t* order_items, int64_
     if (nnz > 0)
         hipLaunchKernelGGL(cf_dedup_kernel, dim3(ge), dim3(256), 0, 0, (const int64_t*)d_off, (const int32_t*)d_items, n_orders,
                            nnz, d_keep, d_order_of, d_blen, d_clen);
-    hipLaunchKernelGGL(cf_scan_kernel, dim3(1), dim3(1024), 0, 0, (const int32_t*)d_blen, n_orders, cf->b_off, d_stats, 0);
-    hipLaunchKernelGGL(cf_scan_kernel, dim3(1), dim3(1024), 0, 0, (const int32_t*)d_clen, n_items, cf->c_off, d_stats, 1);
+    launch_prefix_sum(d_blen, n_orders, cf->b_off, d_stats, 0);      // stats[0]: the longest basket
+    launch_prefix_sum(d_clen, n_items, cf->c_off, d_stats + 1, 0);  // stats[1]: the most frequent item's column
     CF_TRY(hipGetLastError());
     int32_t stats[2] = {0, 0}, kept = 0;
     CF_TRY(hipMemcpy(stats, d_stats, 8, hipMemcpyDeviceToHost));

@@ -124,32 +124,15 @@ static ExclWs excl_ws(const icrec_index* idx, int n_local, int world, int k, int
 // is then non-decreasing inside [0, cap], every query's segment [off[i], off[i+1]) is well-formed, the segments of a
 // rank are disjoint and together hold at most cap ids - so excl_fill_kernel can never write past csr_idx[world * cap]
 // whatever the input was (a malformed list excludes less, it never reads or writes out of bounds: icrec.h).
-__global__ __launch_bounds__(1024) void excl_sanitize_kernel(int32_t* __restrict__ off_all, int n_local, int cap) {
-    __shared__ int part[16];
-    __shared__ int carry_s;
+__global__ __launch_bounds__(SCAN_THREADS) void excl_sanitize_kernel(int32_t* __restrict__ off_all, int n_local, int cap) {
     int32_t* off = off_all + (size_t)blockIdx.x * (n_local + 1);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base <= n_local; base += 1024) {
-        const int i = base + tid;
-        int x = i <= n_local ? off[i] : 0;
-        x = x < 0 ? 0 : (x > cap ? cap : x);
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {  // inclusive max-scan inside the wave
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x = x > y ? x : y;
-        }
-        if (lane == 63) part[wave] = x;
-        __syncthreads();
-        int m = carry_s;
-        for (int w = 0; w < wave; ++w) m = m > part[w] ? m : part[w];
-        x = x > m ? x : m;
-        if (i <= n_local) off[i] = x;
-        __syncthreads();
-        if (tid == 1023) carry_s = x;
-        __syncthreads();
-    }
+    workgroup_scan<ScanMax>(
+        (int64_t)n_local + 1,
+        [&](int64_t i) {
+            const int x = off[i];
+            return x < 0 ? 0 : (x > cap ? cap : x);
+        },
+        [&](int64_t i, int, int running_max) { off[i] = running_max; });
 }
 
 // gathered query g = (rank r, local query i): its ids are rows_all[r][lo .. hi), lo / hi from the sanitised
@@ -179,35 +162,6 @@ __global__ __launch_bounds__(256) void excl_count_kernel(const int32_t* __restri
     cnt[g] = c;
 }
 
-// exclusive prefix sum of cnt[0 .. Q) -> off[0 .. Q]; one 1,024-thread workgroup, chunks of 1,024 with a carry
-__global__ __launch_bounds__(1024) void excl_scan_kernel(const int32_t* __restrict__ cnt, int Q, int32_t* __restrict__ off) {
-    __shared__ int part[16];
-    __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base < Q; base += 1024) {
-        const int g = base + tid;
-        const int v = g < Q ? cnt[g] : 0;
-        int x = v;  // inclusive scan inside the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) part[wave] = x;
-        __syncthreads();
-        int wbase = 0;
-        for (int w = 0; w < wave; ++w) wbase += part[w];
-        const int carry = carry_s;
-        if (g < Q) off[g] = carry + wbase + x - v;
-        __syncthreads();
-        if (tid == 1023) carry_s = carry + wbase + x;
-        __syncthreads();
-    }
-    if (tid == 0) off[Q] = carry_s;
-}
-
 __global__ __launch_bounds__(256) void excl_fill_kernel(const int32_t* __restrict__ off_all,
                                                         const int32_t* __restrict__ rows_all, int n_local, int cap,
                                                         int Q, int64_t row_lo, int64_t row_hi,
@@ -227,10 +181,10 @@ __global__ __launch_bounds__(256) void excl_fill_kernel(const int32_t* __restric
 static int build_local_csr(int32_t* off_all, const int32_t* rows_all, int world, int n_local, int cap, int64_t row_lo,
                            int64_t row_hi, int32_t* cnt, int32_t* csr_off, int32_t* csr_idx, hipStream_t st) {
     const int Q = n_local * world;
-    hipLaunchKernelGGL(excl_sanitize_kernel, dim3(world), dim3(1024), 0, st, off_all, n_local, cap);
+    hipLaunchKernelGGL(excl_sanitize_kernel, dim3(world), dim3(SCAN_THREADS), 0, st, off_all, n_local, cap);
     hipLaunchKernelGGL(excl_count_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, (const int32_t*)off_all, rows_all,
                        n_local, cap, Q, row_lo, row_hi, cnt);
-    hipLaunchKernelGGL(excl_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t*)cnt, Q, csr_off);
+    launch_prefix_sum(cnt, Q, csr_off, nullptr, st);
     hipLaunchKernelGGL(excl_fill_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, (const int32_t*)off_all, rows_all,
                        n_local, cap, Q, row_lo, row_hi, (const int32_t*)csr_off, csr_idx);
     ICREC_HIP(hipGetLastError());

@@ -1,5 +1,8 @@
-// common.h — host-side error plumbing, the declarations of sort.hip's key sorters, and the device helpers shared by
-// the gfx950 kernels: ranking keys, the LDS bitonic network, wave reductions and the fp32 MFMA tile engine.
+// common.h — host-side error plumbing, the declarations of sort.hip's key sorters and prefix-sum launcher, and the
+// device helpers shared by the gfx950 kernels: ranking keys (search.hip, sort.hip, cf.hip, boost.hip), the
+// (value, position) key (mmr.hip, rerank.hip), the shard row rule (mmr.hip, boost.hip, rerank.hip), the LDS bitonic
+// network, wave reductions, the workgroup scan (sort.hip, rerank.hip, comm.hip), the fp32 MFMA tile engine
+// (search.hip) and the gathered exact-cosine wave tile (mmr.hip, boost.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -72,6 +75,9 @@ int64_t rank_pow2(int64_t n);
 void launch_rank_sort_emit(u64* keys, int64_t n_rows, int64_t P, int n_queries, int64_t row_offset, int64_t* out,
                            hipStream_t st);
 constexpr int MERGE_MAX_LISTS = 1024;
+// sort.hip's prefix sums, used by cf.hip and comm.hip: out[0 .. n] = the exclusive prefix sums of len[0 .. n) (int32,
+// wrapping; the callers bound the total), and *max_out = max(0, the largest len) unless max_out is NULL.
+void launch_prefix_sum(const int32_t* len, int64_t n, int32_t* out, int32_t* max_out, hipStream_t st);
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -99,6 +105,27 @@ __device__ __forceinline__ void store_key(u64 key, size_t o, int64_t* out_idx, f
     if (out_keys) out_keys[o] = key;
     if (out_idx) out_idx[o] = key ? (int64_t)key_row(key) : -1;
     if (out_idx) out_score[o] = key ? key_score(key) : 0.0f;  // out_score is set whenever out_idx is
+}
+
+// The key of (value, position j) for a choice among one query's candidates: a larger key is ordered before, under "a
+// number before a NaN, then the greater value compared as floats (-0 == +0), then the lower position".  A NaN's high
+// word is 0, below every number's (-inf maps to 0x007FFFFF); v + 0.0f turns -0 into +0, after which make_key's map of
+// the bits is strictly increasing over the numbers, -inf and +inf included; equal high words leave the order to the
+// low word, which falls as j rises.  No real key is 0 (j <= ICREC_MAX_K - 1), so 0 stands for "not a candidate".
+__device__ __forceinline__ u64 value_pos_key(float v, int j) {
+    uint32_t u = 0u;
+    if (v == v) {
+        u = __float_as_uint(v + 0.0f);
+        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    }
+    return ((u64)u << 32) | (u64)(0xFFFFFFFFu - (uint32_t)j);
+}
+
+// Candidate c (a global row, or a negative pad) of an index shard: its local row, or -1 when it is a pad or lies
+// outside [row_offset, row_offset + n_rows).
+__device__ __forceinline__ int64_t local_row(int64_t c, int64_t row_offset, int64_t n_rows) {
+    const int64_t r = c - row_offset;
+    return (c >= 0 && r >= 0 && r < n_rows) ? r : -1;
 }
 
 // descending bitonic compare-exchange on a[i], a[i ^ j] inside the size-k subsequence containing i
@@ -150,6 +177,52 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
     return v;
+}
+
+// ------------------------------------------------------------------ workgroup scan
+// A workgroup of SCAN_THREADS threads walks i = 0 .. n-1 in chunks of SCAN_THREADS.  Thread t of a chunk takes
+// v = load(i) and is handed emit(i, v, inc), inc = Op over load(0) .. load(i): an inclusive scan inside the wave by
+// shuffles, the 16 wave totals through LDS, and the carry of the chunks before in a register of every thread (each
+// thread folds all 16 totals into it, in wave order, so all threads hold the same carry).  For ScanSum the exclusive
+// result is inc - v.  Sums wrap as int32 arithmetic does; the entry points bound them.
+// The hazard: no thread may overwrite the wave totals of chunk c before every thread has read them.  Two barriers per
+// chunk, and they suffice: the first stands between the reads of chunk c - 1 and the writes of chunk c, the second
+// between those writes and the reads of chunk c; nothing else is shared.  The first barrier of the first chunk does
+// the same for whatever used the LDS before, so a kernel may scan twice.  Every thread of the workgroup calls it.
+constexpr int SCAN_THREADS = 1024;
+struct ScanSum {
+    static constexpr int identity = 0;
+    static __device__ __forceinline__ int op(int a, int b) { return a + b; }
+};
+struct ScanMax {
+    static constexpr int identity = INT32_MIN;
+    static __device__ __forceinline__ int op(int a, int b) { return a > b ? a : b; }
+};
+template <class Op, class Load, class Emit>
+__device__ __forceinline__ void workgroup_scan(int64_t n, Load load, Emit emit) {
+    __shared__ int wave_tot[SCAN_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int carry = Op::identity;
+    for (int64_t i0 = 0; i0 < n; i0 += SCAN_THREADS) {
+        const int64_t i = i0 + tid;
+        const int v = i < n ? load(i) : Op::identity;
+        int inc = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc = Op::op(o, inc);
+        }
+        __syncthreads();
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        int before = carry;
+#pragma unroll
+        for (int w = 0; w < SCAN_THREADS / 64; ++w) {
+            if (w == wave) before = carry;
+            carry = Op::op(carry, wave_tot[w]);
+        }
+        if (i < n) emit(i, v, Op::op(before, inc));
+    }
 }
 
 // ------------------------------------------------------------------ fp32 MFMA tile engine
@@ -306,6 +379,45 @@ __device__ __forceinline__ void tile_gemm(f32x16 (&acc)[Cfg::TM][Cfg::TN], const
         __syncthreads();
         if (s + 1 < nslab) tile_load<Cfg, A16>(pre, A, a_row0, a_rows, B, b_row0, b_rows, K, s + 1);
         tile_mma<Cfg>(acc, As, Bs, wm, wn, lane);
+    }
+}
+
+// ------------------------------------------------------------------ gathered exact-cosine wave tile
+// One wave, one 32 x 32 tile: acc[.] += the chain s = fmaf(a[d], b[d], s) over d = 0 .. K-1 ascending (K a multiple
+// of BK) between the row at pa (operand A: lane l gives the row of tile row l & 31) and the row at pb (operand B: the
+// row of tile column l & 31), by v_mfma_f32_32x32x2_f32.  No row passes through LDS: per slab of BK values a lane
+// reads the slab of each of its two rows straight from global memory in 16-byte loads (128 B of fp32, 64 B of bf16
+// bits) and keeps the half that its sixteen MFMA steps consume - step s adds the products of d = 2s and 2s + 1 in
+// that order, lanes 0-31 (h = 0) supply the even d and lanes 32-63 (h = 1) the odd d.  The half is chosen as each 16
+// bytes arrive, between constant elements (a choice inside the step loop becomes a variable element index); bf16
+// values are widened exactly.  The two halves of the wave read the same bytes, which the L1 serves once.
+// A storage is float (fp32 values) or uint16_t (bf16 bits); mmr.hip gathers both operands from the index rows,
+// boost.hip operand A, with the normalised fp32 query (one address for the whole wave) as operand B.
+__device__ __forceinline__ void gathered_half_slab(const float* p, int h, float (&v)[BK / 2]) {
+#pragma unroll
+    for (int u = 0; u < BK / 4; ++u) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(p + 4 * u);
+        v[2 * u] = h ? x[1] : x[0];
+        v[2 * u + 1] = h ? x[3] : x[2];
+    }
+}
+__device__ __forceinline__ void gathered_half_slab(const uint16_t* p, int h, float (&v)[BK / 2]) {
+#pragma unroll
+    for (int u = 0; u < BK / 8; ++u) {
+        const u32x4 x = *reinterpret_cast<const u32x4*>(p + 8 * u);  // word w: d = 8u + 2w (low half), + 1 (high half)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) v[4 * u + w] = h ? bf16_hi(x[w]) : bf16_lo(x[w]);
+    }
+}
+template <class TA, class TB>
+__device__ __forceinline__ void gathered_tile(f32x16& acc, const TA* __restrict__ pa, const TB* __restrict__ pb, int K,
+                                              int h) {
+    for (int d0 = 0; d0 < K; d0 += BK) {
+        float a[BK / 2], b[BK / 2];
+        gathered_half_slab(pa + d0, h, a);
+        gathered_half_slab(pb + d0, h, b);
+#pragma unroll
+        for (int s = 0; s < BK / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[s], acc, 0, 0, 0);
     }
 }
 

@@ -1,8 +1,11 @@
 // index.h — what an icrec_index handle points to, shared by index.hip (which creates and destroys it), search.hip
 // (which builds its filter storage and searches it), sort.hip (icrec_rank_all), mmr.hip and boost.hip (which read its
 // stored rows), and the device code that index.hip, search.hip and boost.hip share: the row normalisation kernel, the
-// exclusion search and the facet test.
+// exclusion search and the facet test.  What needs no handle - the shard row rule, the gathered exact-cosine tile that
+// mmr.hip and boost.hip read the stored rows with - is in common.h.
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -26,6 +29,9 @@ struct Index {
 };
 
 static inline bool rows_are_bf16(const Index* ix) { return ix->storage == ICREC_ROWS_BF16 || ix->storage == ICREC_ROWS_BF16_FILTER; }
+// One stored value of `rows` in a kernel templated on "the rows are bf16": bf16 bits or a float.
+template <bool P16>
+using row_elem_t = std::conditional_t<P16, uint16_t, float>;
 
 // search.hip, for index.hip's icrec_index_create_ex: the filter pass's copy of the normalised rows of a *_FILTER
 // storage (whose dim is a multiple of FILTER_DIM_STEP), in the layout of the pass that will read it - `frag` or the two

@@ -15,28 +15,19 @@ constexpr int GRAM_WAVES = 4;      // (query, tile) items per Gram workgroup, on
 constexpr int SELECT_THREADS = 256;  // all of them copy the matrix into LDS, the first wave selects
 static_assert(ICREC_MAX_K <= 128, "a lane of the selection wave holds two candidates; the matrix is at most 64 KB of LDS");
 
-// Candidate c of an index shard: its local row, or -1 when it is a pad or lies outside the shard.
-__device__ __forceinline__ int64_t local_row(int64_t c, int64_t row_offset, int64_t n_rows) {
-    const int64_t r = c - row_offset;
-    return (c >= 0 && r >= 0 && r < n_rows) ? r : -1;
-}
-
 // ---------------------------------------------------------------- candidate x candidate similarities
 // One wave per 32 x 32 tile of a query's matrix, lower triangle of tiles only (tile (ti, tj), tj <= ti, is item
 // ti (ti + 1) / 2 + tj of the query); a single request at k = 128 is ten waves on ten compute units.
-// G[i][j] = the fp32 chain s = fmaf(row_i[d], row_j[d], s) over d ascending, by v_mfma_f32_32x32x2_f32: each step adds
-// the products of two consecutive d in order (common.h: the search kernels rely on the same property), lanes 0-31
-// supply the even d of a step and lanes 32-63 the odd d.  A lane reads the 8 consecutive values of its row that four
-// steps consume (32 B of fp32, 16 B of bf16 widened exactly) straight from global memory and keeps its half of them:
-// the two halves of the wave read the same bytes, which the L1 serves once, and no row passes through LDS - a tile's
-// 64 rows are read by one wave only.  fmaf(a, b, s) == fmaf(b, a, s), so the matrix is bit-symmetric and the transposed
-// entry of an off-diagonal tile is a second store of the same value.
+// G[i][j] = the fp32 chain s = fmaf(row_i[d], row_j[d], s) over d ascending, by common.h's gathered_tile with both
+// operands gathered from the stored rows - a tile's 64 rows are read by one wave only.  fmaf(a, b, s) == fmaf(b, a, s),
+// so the matrix is bit-symmetric and the transposed entry of an off-diagonal tile is a second store of the same value.
 // Entries in the row or column of an invalid candidate are not stored (nor read by the selection); the lanes of such
 // a candidate read row 0 of the shard instead of the candidate's row, so nothing outside the rows is touched.
 template <bool P16>
 __global__ __launch_bounds__(GRAM_WAVES * 64) void mmr_gram_kernel(const void* __restrict__ rows, int K, int64_t n_rows,
                                                                    int64_t row_offset, const int64_t* __restrict__ cand,
                                                                    int Q, int k, int n_tiles, float* __restrict__ G) {
+    typedef row_elem_t<P16> Row;
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const int64_t item = (int64_t)blockIdx.x * GRAM_WAVES + (threadIdx.x >> 6);
     if (item >= (int64_t)Q * n_tiles) return;  // whole waves leave
@@ -53,40 +44,8 @@ __global__ __launch_bounds__(GRAM_WAVES * 64) void mmr_gram_kernel(const void* _
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-    if (P16) {
-        const uint16_t* pa = static_cast<const uint16_t*>(rows) + (la >= 0 ? la : 0) * K;
-        const uint16_t* pb = static_cast<const uint16_t*>(rows) + (lb >= 0 ? lb : 0) * K;
-        for (int d0 = 0; d0 < K; d0 += BK) {  // (dim is a multiple of BK = 32)
-            u32x4 a[4], b[4];  // word w of a[u]: d0 + 8u + 2w (low half), d0 + 8u + 2w + 1 (high half)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[u] = *reinterpret_cast<const u32x4*>(pa + d0 + 8 * u);
-                b[u] = *reinterpret_cast<const u32x4*>(pb + d0 + 8 * u);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int w = 0; w < 4; ++w)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? bf16_hi(a[u][w]) : bf16_lo(a[u][w]),
-                                                               h ? bf16_hi(b[u][w]) : bf16_lo(b[u][w]), acc, 0, 0, 0);
-        }
-    } else {
-        const float* pa = static_cast<const float*>(rows) + (la >= 0 ? la : 0) * K;
-        const float* pb = static_cast<const float*>(rows) + (lb >= 0 ? lb : 0) * K;
-        for (int d0 = 0; d0 < K; d0 += BK) {  // (dim is a multiple of BK = 32)
-            f32x4 a[8], b[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                a[u] = *reinterpret_cast<const f32x4*>(pa + d0 + 4 * u);
-                b[u] = *reinterpret_cast<const f32x4*>(pb + d0 + 4 * u);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a[u][1] : a[u][0], h ? b[u][1] : b[u][0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a[u][3] : a[u][2], h ? b[u][3] : b[u][2], acc, 0, 0, 0);
-            }
-        }
-    }
+    const Row* base = static_cast<const Row*>(rows);
+    gathered_tile(acc, base + (la >= 0 ? la : 0) * K, base + (lb >= 0 ? lb : 0) * K, K, h);
     // acc[e]: row ti * 32 + acc_row(e, lane) (operand A), column tj * 32 + r (operand B); both < k when valid
     float* Gq = G + (size_t)q * k * k;
     const bool col_ok = (valid_b >> r) & 1ull;  // (lanes r and r + 32 hold the same candidate)
@@ -102,20 +61,9 @@ __global__ __launch_bounds__(GRAM_WAVES * 64) void mmr_gram_kernel(const void* _
 }
 
 // ---------------------------------------------------------------- greedy selection
-// A candidate's key for the wave arg-max: a larger key is ordered before, key 0 = not a candidate.  The order is
-// rerank.hip's ordered_before on (value, position): a number before a NaN, the greater value (compared as floats:
-// -0 == +0), the lower position.  No real key is 0 (position <= 127).
-__device__ __forceinline__ u64 pick_key(float v, int j) {
-    uint32_t u = 0u;  // NaN: below every number (-inf maps to 0x007FFFFF)
-    if (v == v) {
-        u = __float_as_uint(v + 0.0f);
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((u64)u << 32) | (u64)(0xFFFFFFFFu - (uint32_t)j);
-}
-
 // One workgroup per query: its k x k matrix goes to LDS (every pick reads one row of it, and which row is known only
-// after the pick before), then the first wave picks; lane l owns candidates l and l + 64.
+// after the pick before), then the first wave picks; lane l owns candidates l and l + 64.  A pick is the wave maximum
+// of common.h's value_pos_key, key 0 = not a candidate.
 __global__ __launch_bounds__(SELECT_THREADS) void mmr_select_kernel(const float* __restrict__ G,
                                                                     const int64_t* __restrict__ cand,
                                                                     const float* __restrict__ rel, int64_t n_rows,
@@ -152,7 +100,7 @@ __global__ __launch_bounds__(SELECT_THREADS) void mmr_select_kernel(const float*
         for (int s = 0; s < 2; ++s) {
             // three roundings, never fused: the two products, then the difference (the first pick is by rel alone)
             const float v = t == 0 ? rl[s] : __fsub_rn(__fmul_rn(lambda, rl[s]), __fmul_rn(oml, ms[s]));
-            const u64 ks = avail[s] ? pick_key(v, s * 64 + lane) : 0ull;
+            const u64 ks = avail[s] ? value_pos_key(v, s * 64 + lane) : 0ull;
             key = ks > key ? ks : key;
         }
         key = wave_max_u64(key);

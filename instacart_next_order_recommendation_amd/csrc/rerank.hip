@@ -6,7 +6,6 @@
 namespace icrec {
 namespace {
 
-constexpr int SCAN_THREADS = 1024;
 constexpr int FILL_WAVES = 4;    // pairs per fill workgroup, one wave each
 constexpr int SELECT_WAVES = 4;  // queries per select workgroup, one wave each
 constexpr int SELECT_SLOTS = (ICREC_MAX_K + 63) / 64;
@@ -23,10 +22,9 @@ __global__ __launch_bounds__(256) void pair_len_kernel(const int32_t* __restrict
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n_pairs) return;
     const int q = p / k;
-    const int64_t c = cand[p];
-    const int64_t r = c - row_offset;
+    const int64_t r = local_row(cand[p], row_offset, n_rows);
     int ka = 0, kb = 0;
-    if (c >= 0 && r >= 0 && r < n_rows) {
+    if (r >= 0) {
         int la = q_cu[q + 1] - q_cu[q], lb = cat_cu[r + 1] - cat_cu[r];
         la = la < 0 ? 0 : la;
         lb = lb < 0 ? 0 : lb;
@@ -52,53 +50,34 @@ __global__ __launch_bounds__(256) void pair_len_kernel(const int32_t* __restrict
 }
 
 // ---------------------------------------------------------------- cu = exclusive prefix sum of the lengths
-// One workgroup walks the pairs in tiles of 1,024 (a wave scan by shuffles, the 16 wave totals through LDS, a running
-// carry).  The sums fit an int32: the entry point refuses n_pairs * max_len >= 2^31.
+// One workgroup walks the pairs by common.h's workgroup_scan.  The sums fit an int32: the entry point refuses
+// n_pairs * max_len >= 2^31.
 // Safety clamp: pair p keeps its length only while every later pair still has room for three tokens, i.e. while
 // S_end[p] + 3 * (n - 1 - p) <= ids_cap (S_end the inclusive sum).  The left side never decreases with p, so the pairs
 // from the first failing one - pstar - on all shrink to `[CLS] [SEP] [SEP]`: cu[p] = cu[pstar] + 3 * (p - pstar), seg_b = 2.
 // With ids_cap >= 3 * n (checked by the entry point) cu[n] <= ids_cap always.
 __global__ __launch_bounds__(SCAN_THREADS) void pair_scan_kernel(const int32_t* __restrict__ len, int n, int64_t ids_cap,
                                                                  int32_t* __restrict__ cu, int32_t* __restrict__ seg_b) {
-    __shared__ int wave_tot[SCAN_THREADS / 64];
-    __shared__ int carry_s, pstar_s, base_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) {
-        carry_s = 0;
-        pstar_s = n;
-        base_s = 0;
-    }
-    __syncthreads();
-    for (int p0 = 0; p0 < n; p0 += SCAN_THREADS) {
-        const int p = p0 + tid;
-        const int v = p < n ? len[p] : 0;
-        int inc = v;  // inclusive scan inside the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += o;
-        }
-        if (lane == 63) wave_tot[wave] = inc;
-        __syncthreads();
-        int before = carry_s;
-        for (int w = 0; w < wave; ++w) before += wave_tot[w];
-        const int excl = before + inc - v;
-        if (p < n) {
+    __shared__ int total_s, pstar_s, base_s;
+    const int tid = threadIdx.x;
+    if (tid == 0) pstar_s = n;  // (the scan's barriers stand between this and the one thread that lowers it)
+    workgroup_scan<ScanSum>(
+        n, [&](int64_t p) { return len[p]; },
+        [&](int64_t p, int v, int inc) {
+            const int excl = inc - v;
             cu[p] = excl;
-            const bool fits = (int64_t)excl + v + 3 * (int64_t)(n - 1 - p) <= ids_cap;
-            const bool prev_fits = p == 0 || (int64_t)excl + 3 * (int64_t)(n - p) <= ids_cap;
+            const bool fits = (int64_t)excl + v + 3 * (n - 1 - p) <= ids_cap;
+            const bool prev_fits = p == 0 || (int64_t)excl + 3 * (n - p) <= ids_cap;
             if (!fits && prev_fits) {  // exactly one thread: the predicate is monotone
-                pstar_s = p;
+                pstar_s = (int)p;
                 base_s = excl;
             }
-        }
-        __syncthreads();  // every thread has read carry_s and wave_tot
-        if (tid == SCAN_THREADS - 1) carry_s = before + inc;
-    }
+            if (p == n - 1) total_s = inc;
+        });
     __syncthreads();
     const int pstar = pstar_s;
     if (pstar >= n) {
-        if (tid == 0) cu[n] = carry_s;
+        if (tid == 0) cu[n] = total_s;
         return;
     }
     const int base = base_s;
@@ -137,13 +116,15 @@ __global__ __launch_bounds__(FILL_WAVES * 64) void pair_fill_kernel(
 // One wave per query; lane l owns candidates l and l + 64.  A candidate's rank is the number of candidates ordered
 // before it: idx >= 0 before idx < 0 (skipped), then a number before a NaN, then the larger logit (compared as floats:
 // -0 == +0, as numpy's stable argsort of the negated scores compares them), then the lower position j.
-__device__ __forceinline__ bool ordered_before(float la, int ja, float lb, int jb) {
-    const bool na = la != la, nb = lb != lb;
-    if (na != nb) return nb;
-    if (!na && la != lb) return la > lb;
-    return ja < jb;
-}
-
+// Candidate (la, ja) is ordered before (lb, jb) exactly when value_pos_key(la, ja) > value_pos_key(lb, jb) (common.h):
+//   one NaN         the NaN's high word is 0, a number's at least 0x007FFFFF: the number's key is greater;
+//   two NaNs        both high words are 0 whatever the payloads: the low word decides, greater for the lower j;
+//   -0 and +0       v + 0.0f is +0 for both, the high words are equal: the lower j, as for la == lb;
+//   +-inf           -inf maps to 0x007FFFFF, below every finite number, +inf to 0xFF800000, above: la > lb as floats;
+//   two numbers     the map of the bits is strictly increasing, so la > lb gives the greater high word, and equal
+//                   values (two positions of one logit) equal high words and again the lower j;
+//   itself          equal keys: not before, as ja < jb is false.
+// A skipped candidate's key is 0, which is greater than no key.
 __global__ __launch_bounds__(SELECT_WAVES * 64) void rerank_select_kernel(const float* __restrict__ logits,
                                                                           const int64_t* __restrict__ cand, int n_queries,
                                                                           int k, int top_k, int64_t* __restrict__ out_idx,
@@ -152,25 +133,25 @@ __global__ __launch_bounds__(SELECT_WAVES * 64) void rerank_select_kernel(const 
     if (q >= n_queries) return;  // (whole waves leave: the shuffles below always see 64 lanes)
     float lg[SELECT_SLOTS];
     int64_t ix[SELECT_SLOTS];
+    u64 key[SELECT_SLOTS];
     int rank[SELECT_SLOTS];
 #pragma unroll
     for (int s = 0; s < SELECT_SLOTS; ++s) {
         const int j = s * 64 + lane;
         lg[s] = j < k ? logits[(size_t)q * k + j] : 0.0f;
         ix[s] = j < k ? cand[(size_t)q * k + j] : -1;
+        key[s] = ix[s] >= 0 ? value_pos_key(lg[s], j) : 0ull;
         rank[s] = 0;
     }
     int n_valid = 0;
 #pragma unroll
     for (int so = 0; so < SELECT_SLOTS; ++so) {
         for (int lo = 0; lo < 64 && so * 64 + lo < k; ++lo) {  // wave-uniform bounds
-            const float ol = __shfl(lg[so], lo, 64);
-            const bool ov = __shfl((int)(ix[so] >= 0), lo, 64) != 0;
-            if (!ov) continue;
+            const u64 ok = shfl_u64(key[so], lo);
+            if (ok == 0ull) continue;
             ++n_valid;
 #pragma unroll
-            for (int s = 0; s < SELECT_SLOTS; ++s)
-                rank[s] += ordered_before(ol, so * 64 + lo, lg[s], s * 64 + lane) ? 1 : 0;
+            for (int s = 0; s < SELECT_SLOTS; ++s) rank[s] += ok > key[s] ? 1 : 0;
         }
     }
 #pragma unroll

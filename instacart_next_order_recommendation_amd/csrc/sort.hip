@@ -1,6 +1,8 @@
 // sort.hip — the sorters of packed 64-bit ranking keys (common.h: make_key; a larger key is a better hit, key 0 is
 // the pad), declared in common.h for search.hip and cf.hip: the k-way merge of sorted partial lists (a wave tournament,
-// or one workgroup for a single request's few lists) and the complete bitonic sort behind the full rankings.
+// or one workgroup for a single request's few lists) and the complete bitonic sort behind the full rankings; and the
+// one-workgroup prefix sums of int32 counts, declared in common.h for cf.hip (CSR offsets and the longest segment) and
+// comm.hip (a shard's exclusion CSR).
 // Entry points: icrec_merge_topk, icrec_rank_all.
 #include "index.h"
 
@@ -192,6 +194,37 @@ void launch_rank_sort_emit(u64* keys, int64_t n_rows, int64_t P, int n_queries, 
     const unsigned gx = (unsigned)((P + 1023) / 1024 < 64 ? (P + 1023) / 1024 : 64);
     hipLaunchKernelGGL(rank_sort_kernel, dim3(n_queries), dim3(1024), 0, st, keys, P);
     hipLaunchKernelGGL(rank_emit_kernel, dim3(gx * 4, n_queries), dim3(256), 0, st, (const u64*)keys, n_rows, P, row_offset, out);
+}
+
+// ---------------------------------------------------------------- prefix sums (cf.hip's CSR offsets, comm.hip's)
+// out[0 .. n] = the exclusive prefix sums of len[0 .. n), *max_out = max(0, the largest len): one workgroup on
+// common.h's workgroup_scan.  A thread keeps the maximum of what it loaded; the workgroup's maximum is the last
+// thread's result of a second, one-chunk scan over those.
+__global__ __launch_bounds__(SCAN_THREADS) void prefix_sum_kernel(const int32_t* __restrict__ len, int64_t n,
+                                                                  int32_t* __restrict__ out, int32_t* __restrict__ max_out) {
+    int m = 0;
+    if (n == 0 && threadIdx.x == 0) out[0] = 0;
+    workgroup_scan<ScanSum>(
+        n,
+        [&](int64_t i) {
+            const int v = len[i];
+            m = v > m ? v : m;
+            return v;
+        },
+        [&](int64_t i, int v, int inc) {
+            out[i] = inc - v;
+            if (i == n - 1) out[n] = inc;
+        });
+    if (max_out != nullptr)
+        workgroup_scan<ScanMax>(
+            SCAN_THREADS, [&](int64_t) { return m; },
+            [&](int64_t t, int, int running_max) {
+                if (t == SCAN_THREADS - 1) *max_out = running_max;
+            });
+}
+
+void launch_prefix_sum(const int32_t* len, int64_t n, int32_t* out, int32_t* max_out, hipStream_t st) {
+    hipLaunchKernelGGL(prefix_sum_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, len, n, out, max_out);
 }
 
 }  // namespace icrec

@@ -29,7 +29,11 @@ def check_against_reference(cf, baskets, histories, n_cand, ks=KS):
 # (n_candidates, extra non-corpus items, n_orders, Q)
 SHAPES = [(1, 0, 1, 1), (1, 37, 257, 17), (63, 0, 257, 33), (63, 37, 5000, 17), (1000, 37, 257, 33), (1000, 0, 5000, 17),
           (1000, 37, 1, 1),
-          (9000, 37, 257, 5)]   # 16,384 keys per query: 16 top-k chunks to merge, bitonic stages in global memory
+          (9000, 37, 257, 5),   # 16,384 keys per query: 16 top-k chunks to merge, bitonic stages in global memory
+          # icrec_cf_create scans the basket lengths (n_orders of them) and the column lengths (n_items) in chunks of
+          # 1,024: the shapes above give each array a length below 64 and one above 2,048 that is no multiple of 1,024
+          # (orders 1 and 5,000, items 1 and 9,037); here both are one full chunk exactly
+          (1000, 24, 1024, 5)]
 
 
 @pytest.mark.parametrize("n_cand,extra,n_orders,Q", SHAPES)

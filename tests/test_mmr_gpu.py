@@ -110,6 +110,32 @@ def test_storages(torch_cuda, storage, dim):
     ix.close()
 
 
+@pytest.mark.parametrize("storage", ["f32", "bf16"])
+def test_similarity_matrix_has_the_bits_of_the_chain(torch_cuda, storage):
+    """The selection shows a similarity only where it flips a pick.  The matrix itself, which icrec_mmr_select leaves in
+    its workspace (include/icrec.h: the queries' k x k matrices; mmr.hip: float32 [Q][k][k]), is oracle.scores - the j-ascending fmaf chain - of
+    the stored rows bit for bit wherever row and column are valid candidates: k = 70 is three tiles a side with a
+    ragged last one, at a width that is not 384, with a pad and a foreign row among the candidates."""
+    k = 70
+    P, q = clustered(26, 600, 128, 2)  # (bf16 rows need a multiple of 64)
+    ix = DeviceIndex(P, storage=storage)
+    cand, rel = searched(ix, q, k)
+    cand[0, 33], cand[1, 64] = -1, 600
+    ws = torch.zeros(int(_native.lib().icrec_mmr_select_workspace_bytes(ix._h, 2, k)), dtype=torch.uint8, device=ix.device)
+    out_idx = torch.empty((2, 10), dtype=torch.int64, device=ix.device)
+    out_rel = torch.empty((2, 10), dtype=torch.float32, device=ix.device)
+    ix.mmr_select_into(torch.from_numpy(cand).to(ix.device), torch.from_numpy(rel).to(ix.device), 10, 0.5, out_idx, out_rel, ws=ws)
+    torch.cuda.synchronize()
+    G = ws.cpu().numpy()[:2 * k * k * 4].view(np.float32).reshape(2, k, k)
+    p_hat = ref.stored_rows(P, storage)
+    for i in range(2):
+        where = np.flatnonzero(ref.valid_candidates(cand[i], 600))
+        assert where.size == k - 1
+        rows = np.ascontiguousarray(p_hat[cand[i][where]])
+        np.testing.assert_array_equal(bits(G[i][np.ix_(where, where)]), bits(oracle.scores(rows, rows)), err_msg=f"query {i}")
+    ix.close()
+
+
 # ---------------------------------------------------------------- row offset, pads, invalid candidates
 def test_row_offset_and_candidates_outside_the_shard(torch_cuda):
     off = 1_000_000

@@ -62,22 +62,23 @@ def test_assembly_is_exact(max_len, k, n_queries):
     assert (cu[n_pairs + 1:] == POISON).all() and (seg[n_pairs:] == POISON).all() and (ws[ws_bytes:] == 0x5A).all()
 
 
-def test_the_safety_clamp_keeps_every_write_inside_ids_cap():
-    """An ids_cap below the bound is a caller's mistake the contract still defines: the pairs from the first one that would
-    leave fewer than three tokens for each later pair are `[CLS] [SEP] [SEP]`, and nothing is written at or past ids_cap."""
+def clamp_ends(c):
+    """ends[p]: the tokens through pair p as assemble_pairs packs them, plus three for every later pair."""
+    n_pairs = c["n_queries"] * c["k"]
+    return c["want"][1][1:].astype(np.int64) + 3 * (n_pairs - 1 - np.arange(n_pairs))
+
+
+def check_clamped_assembly(c, cap, pstar):
+    """icrec_assemble_pairs on case c with ids_cap = cap, whose first pair that no longer fits is pstar: exact before it,
+    `[CLS] [SEP] [SEP]` from it on, nothing written at or past ids_cap."""
     import torch
 
     from instacart_next_order_recommendation_amd import _native
 
     L = _native.lib()
-    max_len, k, n_queries = 16, 5, 205
-    c = rc.assembly_case(max_len, k, n_queries)
+    max_len, k, n_queries = c["max_len"], c["k"], c["n_queries"]
     want_ids, want_cu, want_seg = c["want"]
     n_pairs = n_queries * k
-    cap = int(want_cu[-1]) // 2
-    ends = want_cu[1:].astype(np.int64) + 3 * (n_pairs - 1 - np.arange(n_pairs))
-    pstar = int(np.argmax(ends > cap))
-    assert 0 < pstar < n_pairs and cap >= 3 * n_pairs
     (q_ids, q_cu), (cat_ids, cat_cu) = rc.pack(c["q_sides"]), rc.pack(c["cat_sides"])
     ids, cu, seg = poisoned(cap, torch.int32), poisoned(n_pairs + 1, torch.int32), poisoned(n_pairs, torch.int32)
     ws = torch.empty(int(L.icrec_assemble_pairs_workspace_bytes(n_queries, k)), dtype=torch.uint8, device="cuda")
@@ -98,6 +99,30 @@ def test_the_safety_clamp_keeps_every_write_inside_ids_cap():
     np.testing.assert_array_equal(ids[:want_cu[pstar]], want_ids[:want_cu[pstar]])
     np.testing.assert_array_equal(ids[want_cu[pstar]:total], np.tile([rc.CLS, rc.SEP, rc.SEP], n_pairs - pstar))
     assert (ids[total:] == POISON).all() and (cu[n_pairs + 1:] == POISON).all() and (seg[n_pairs:] == POISON).all()
+
+
+def test_the_safety_clamp_keeps_every_write_inside_ids_cap():
+    """An ids_cap below the bound is a caller's mistake the contract still defines: the pairs from the first one that would
+    leave fewer than three tokens for each later pair are `[CLS] [SEP] [SEP]`, and nothing is written at or past ids_cap."""
+    c = rc.assembly_case(16, 5, 205)
+    n_pairs = 205 * 5
+    cap = int(c["want"][1][-1]) // 2
+    pstar = int(np.argmax(clamp_ends(c) > cap))
+    assert 0 < pstar < n_pairs and cap >= 3 * n_pairs
+    check_clamped_assembly(c, cap, pstar)
+
+
+def test_the_safety_clamp_with_the_first_shrunk_pair_in_a_later_chunk():
+    """2,100 pairs are three chunks of the 1,024-thread scan; ids_cap is one token short of what pair 1,536 needs, so the
+    first pair that shrinks lies in the second chunk: its offset carries the first chunk's sum, and the pairs of the third
+    chunk are written by the tail loop alone."""
+    c = rc.assembly_case(16, 5, 420)
+    n_pairs = 420 * 5
+    ends = clamp_ends(c)
+    cap = int(ends[1536]) - 1
+    pstar = int(np.argmax(ends > cap))
+    assert 1024 < pstar < 2048 and cap >= 3 * n_pairs
+    check_clamped_assembly(c, cap, pstar)
 
 
 # ---------------------------------------------------------------- 2. selection

@@ -267,7 +267,7 @@ def _scan_case_lists(rng, world, n_local, cap, id_space):
 @pytest.mark.parametrize("world,n_local", [(1, 1023), (1, 1024), (2, 1025), (3, 2049), (5, 13)])
 def test_exclusion_scans_carry_across_chunks(world, n_local):
     """excl_sanitize_kernel walks each rank's n_local + 1 offsets in chunks of 1,024 with a carried running maximum,
-    excl_scan_kernel the world * n_local counts likewise with a carried sum: one full chunk (1,023 + 1 offsets), a chunk
+    sort.hip's prefix_sum_kernel the world * n_local counts likewise with a carried sum: one full chunk (1,023 + 1 offsets), a chunk
     and one entry, three chunks, counts that are no multiple of 1,024 (3,075 and 6,147) and fewer than one wavefront of
     them (65), against the numpy restatement; cap = 4,096 ids per rank, the shard holds rows 2,000 .. 4,999 of 10,000.
     Then malformed offsets placed so that the carry decides: the maximum in chunk 0 (entry 5 = cap - 7) followed by
