@@ -497,6 +497,51 @@ ICREC_API int icrec_boost_select(icrec_index* idx, const float* q_dev, int32_t n
                        int32_t top_k, int64_t* out_idx_dev, float* out_score_dev,
                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* IVF: an inverted-file index over an icrec_index (the base).  The rows are split into n_lists lists around centroids;
+ * a query scans only the nprobe lists whose centroids it matches best.  Approximate in WHICH rows it looks at, exact
+ * in everything else.  The definition, which every result follows bit for bit:
+ *   Centroid index.  centroids float[n_lists, dim] of any norm go into a private ICREC_ROWS_F32 index with row offset
+ *     0, normalised as every index normalises its rows.
+ *   Assignment.  list(r) = the row returned by icrec_search(centroid index, stored_row(r), k = 1), stored_row(r) being
+ *     what icrec_index_export returns for row r (the normalised fp32 row, or the bf16 row widened exactly): the
+ *     library's own search with its own query normalisation and tie rule (the lower list wins).
+ *   Layout.  perm int32[n_rows] = the local rows sorted by (list, row); list_off int64[n_lists + 1] = the list
+ *     boundaries in perm.  The IVF owns a copy of the stored rows in perm order, in the base's row element type; it
+ *     never reads the base's filter planes or fragments.  n_rows < 2^31.
+ *   Search(q, k, nprobe, exclusions).  probes(q) = the nprobe rows of icrec_search(centroid index, q, k = nprobe),
+ *     without exclusions.  The result is the k best rows r among those with list(r) in probes(q) and r not in q's
+ *     exclusion list; each score is s = fmaf(q_hat[j], stored_row(r)[j], s) for j = 0 .. dim-1 with q_hat the query
+ *     normalised as icrec_search normalises it: the bits icrec_search gives that row.  Order: score descending (-0
+ *     counts as +0), lower ORIGINAL row first on ties.  Outputs row_offset + r and the score; (-1, 0.0) pads where
+ *     fewer than k rows qualify.  The result does not depend on the order of rows inside a list, on how a list is cut
+ *     into slices or on how many workgroups run.
+ * Consequences.  With nprobe == n_lists the result is icrec_search's on the base, bit for bit, for every query, k and
+ * exclusion list.  For a fixed query the probed set at nprobe is a prefix of the probed set at nprobe + 1.
+ * Every base storage is accepted (the *_FILTER ones included).  The base index must outlive the IVF, which keeps its
+ * row_offset, dim, device and row element type. */
+typedef struct icrec_ivf icrec_ivf;
+
+/* Build the IVF.  centroids_dev: float[n_lists, dim] in DEVICE memory.  ICREC_EINVAL: a NULL argument, n_lists < 1 or
+ * n_lists > n_rows, a base of 2^31 rows or more.  A set-up call like icrec_index_set_facets: it allocates (the
+ * gathered rows: as many bytes as the base's rows), synchronises, assigns the rows in passes over slices of them, sorts
+ * on the host, and must never be issued while a call on the base index is running. */
+ICREC_API int icrec_ivf_create(icrec_index* base, const float* centroids_dev, int32_t n_lists, icrec_ivf** out);
+ICREC_API int icrec_ivf_destroy(icrec_ivf* ivf);
+ICREC_API int32_t icrec_ivf_lists(const icrec_ivf* ivf);                      /* n_lists; -1 for NULL */
+/* perm_dev int32[n_rows] and list_off_dev int64[n_lists + 1] (device memory) <- the layout; asynchronous on `stream`. */
+ICREC_API int icrec_ivf_layout(const icrec_ivf* ivf, int32_t* perm_dev, int64_t* list_off_dev, void* stream);
+/* Scratch bytes of icrec_ivf_search (0 for a bad argument). */
+ICREC_API size_t icrec_ivf_search_workspace_bytes(const icrec_ivf* ivf, int32_t n_queries, int32_t k, int32_t nprobe);
+/* The search defined above; q_dev, the exclusion lists (LOCAL original rows, sorted and unique, CSR) and the outputs
+ * are icrec_search's.  ICREC_EINVAL, before any launch: a NULL among ivf, q_dev, the outputs; n_queries < 1; k outside
+ * [1, ICREC_MAX_K]; nprobe outside [1, min(n_lists, ICREC_MAX_K)]; only one of the two exclusion pointers set.
+ * ICREC_ENOMEM: workspace_bytes < icrec_ivf_search_workspace_bytes.  Asynchronous on `stream`: nothing is allocated,
+ * nothing synchronises, every launch goes to that one stream, and the call can be captured into a hipGraph. */
+ICREC_API int icrec_ivf_search(icrec_ivf* ivf, const float* q_dev, int32_t n_queries, int32_t k, int32_t nprobe,
+                     const int32_t* excl_idx_dev, const int32_t* excl_off_dev,
+                     int64_t* out_idx_dev, float* out_score_dev,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Shard-local half of a sharded search: same as icrec_search but emits the
  * sorted partial lists as packed 64-bit keys
  *   key = (orderable(score) << 32) | (0xFFFFFFFF - global_row)
@@ -747,7 +792,8 @@ ICREC_API const char* icrec_version(void);
  *            a few microseconds when every query was proven, a full search
  *            when the fallback ran,
  *        5 = icrec_mmr_select's similarity-matrix kernel, 6 = its selection kernel,
- *        7 = icrec_boost_select's scoring kernel, 8 = its selection kernel. */
+ *        7 = icrec_boost_select's scoring kernel, 8 = its selection kernel,
+ *        10 = icrec_ivf_search's list scan kernel (9 is a spare of the encoder's). */
 ICREC_API int icrec_timing_enable(int on);
 ICREC_API int icrec_timing_reset(void);
 ICREC_API int icrec_timing_query(int which, double* avg_ms, int64_t* n_launches);

@@ -43,6 +43,8 @@ EXPORTS = [
     "icrec_index_set_facets", "icrec_index_facets", "icrec_search_faceted_workspace_bytes", "icrec_search_faceted",
     "icrec_mmr_select_workspace_bytes", "icrec_mmr_select",
     "icrec_boost_select_workspace_bytes", "icrec_boost_select",
+    "icrec_ivf_create", "icrec_ivf_destroy", "icrec_ivf_lists", "icrec_ivf_layout",
+    "icrec_ivf_search_workspace_bytes", "icrec_ivf_search",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
     "icrec_cf_create", "icrec_cf_destroy", "icrec_cf_orders", "icrec_cf_items", "icrec_cf_candidates", "icrec_cf_nnz",
     "icrec_cf_tile", "icrec_cf_rank_workspace_bytes", "icrec_cf_rank", "icrec_cf_rank_all_workspace_bytes",
@@ -151,6 +153,12 @@ def lib() -> C.CDLL:
         "icrec_mmr_select": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, sz, vp]),
         "icrec_boost_select_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_boost_select": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+        "icrec_ivf_create": (C.c_int, [vp, vp, i32, C.POINTER(vp)]),
+        "icrec_ivf_destroy": (C.c_int, [vp]),
+        "icrec_ivf_lists": (i32, [vp]),
+        "icrec_ivf_layout": (C.c_int, [vp, vp, vp, vp]),
+        "icrec_ivf_search_workspace_bytes": (sz, [vp, i32, i32, i32]),
+        "icrec_ivf_search": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
         "icrec_merge_topk": (C.c_int, [vp, i32, i32, i32, vp, vp, C.c_int, vp]),
         "icrec_scores": (C.c_int, [vp, vp, i32, vp, vp, sz, vp]),
         "icrec_rank_all_workspace_bytes": (sz, [vp, i32]),

@@ -9,6 +9,7 @@ ignored; a missing model directory or corpus file is an error).
     python -m instacart_next_order_recommendation_amd --config configs/inference.yaml [--query "..."] [--json]
                                                       [--aisle NAME]... [--department NAME]...
                                                       [--diversity FLOAT] [--candidates INT]
+                                                      [--ann-lists N --probes P]
                                                       [--boost PID[=W]]... [--boost-weight W] [--only-boosted]
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
@@ -130,10 +131,8 @@ def parse_boosts(entries):
     return out
 
 
-def main(argv=None) -> int:
-    argv = sys.argv[1:] if argv is None else list(argv)
-    if argv and argv[0] == "baselines":
-        return baselines_main(argv[1:])
+def build_parser() -> argparse.ArgumentParser:
+    """The recommend command's arguments."""
     ap = argparse.ArgumentParser(prog="instacart_next_order_recommendation_amd", description=__doc__.splitlines()[0])
     ap.add_argument("--config", type=Path, default=None, help="YAML settings (default: configs/inference.yaml)")
     ap.add_argument("--query", default=None, help="user context to rank for (overrides the config)")
@@ -148,12 +147,34 @@ def main(argv=None) -> int:
                          "they are then listed in selection order, not by score")
     ap.add_argument("--candidates", type=int, default=None, metavar="INT",
                     help="how many best matches a diversified request chooses from (default min(128, 4 * top_k))")
+    ap.add_argument("--ann-lists", type=int, default=None, metavar="N",
+                    help="build an IVF index of N lists beside the exact one (k-means on the catalog at start-up)")
+    ap.add_argument("--probes", type=int, default=None, metavar="P",
+                    help="search only the P best of the --ann-lists lists (approximate; P = N is the exact result)")
     ap.add_argument("--boost", action="append", default=None, metavar="PID[=W]",
                     help="a product the user has bought before: W (>= 0) is added to its score (repeatable; without =W "
                          "it takes --boost-weight)")
     ap.add_argument("--boost-weight", type=float, default=None, metavar="W", help="the weight of every --boost without its own")
     ap.add_argument("--only-boosted", action="store_true", help="rank the --boost products alone (buy it again)")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def ann_args(args) -> tuple[int | None, int | None]:
+    """(--ann-lists, --probes) checked against each other: each needs the other, both are >= 1, P <= N."""
+    n, p = args.ann_lists, args.probes
+    if (n is None) != (p is None):
+        raise SystemExit("--ann-lists and --probes go together")
+    if n is not None and not 1 <= p <= n:
+        raise SystemExit(f"--probes must be in [1, --ann-lists = {n}], got {p}")
+    return n, p
+
+
+def main(argv=None) -> int:
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv and argv[0] == "baselines":
+        return baselines_main(argv[1:])
+    args = build_parser().parse_args(argv)
+    ann_lists, probes = ann_args(args)
     cfg = read_settings(args.config)
     if not cfg["corpus"].exists():
         raise SystemExit(f"corpus file {cfg['corpus']} does not exist (this build never downloads one)")
@@ -170,12 +191,13 @@ def main(argv=None) -> int:
 
     from .recommender import Recommender
 
-    rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"])
+    rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"],
+                      ann_lists=ann_lists)
     try:
         hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department,
                              diversity=args.diversity, candidates=args.candidates, boosts=boosts or None,
-                             only_boosted=args.only_boosted)
-    except ValueError as e:  # an aisle / department the catalog does not have, a bad --diversity / --candidates / --boost
+                             only_boosted=args.only_boosted, probes=probes)
+    except ValueError as e:  # an aisle / department the catalog does not have, a bad --diversity / --candidates / --boost / --probes
         raise SystemExit(str(e))
     if args.json:
         for rank, (pid, score) in enumerate(hits, 1):

@@ -1485,7 +1485,7 @@ static int encode_x3(Encoder* e, const EncBufs& b, const EncBufs* cls, const int
         } else {
             hipLaunchKernelGGL(ln_wt, dim3((r.n + 15) / 16), dim3(256), 0, r.st, t1r, r.n, L.g1, L.b1n, c.ln_eps,
                                xhr, xlr);
-            ScopedTimer tm(r.small ? T_NSLOTS - 1 : T_FFN_UP, r.st);
+            ScopedTimer tm(r.small ? T_FFN_UP_SMALL : T_FFN_UP, r.st);
             launch_wt_linear<1>(xhr, xlr, r.n, H, L.W1_p, I, L.b1, nullptr, hhr, hlr, r.st, r.small);
         }
         launch_wt_linear<2>(hhr, hlr, r.n, I, L.W2_p, H, L.b2, t1r, xhr, xlr, r.st, r.small);

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "gemm_x3.h"
 #include "index.h"
+#include "stream.h"
 #include "wt_gemm.h"
 
 namespace icrec {
@@ -20,29 +21,7 @@ namespace icrec {
 
 // ---------------------------------------------------------------- score + select
 
-// Merge the queue of query q into its sorted list; one wavefront, all 64 lanes call this.
-// Every element's new position is its rank in the union (keys are unique): a list entry keeps its
-// index plus the number of better candidates; candidate i gets (#better candidates) + (#better list
-// entries), the latter from a ballot over the lanes holding the list — no search, no extra LDS trips.
-__device__ __forceinline__ void merge_queue(u64* list, const u64* queue, int n, int k, int lane) {
-    const u64 c = lane < n ? queue[lane] : 0ull;
-    const u64 e0 = lane < k ? list[lane] : 0ull;
-    const u64 e1 = lane + 64 < k ? list[lane + 64] : 0ull;
-    int rc = 0, r0 = 0, r1 = 0, lc = 0;
-    for (int i = 0; i < n; ++i) {
-        const u64 ci = queue[i];  // LDS broadcast
-        rc += ci > c;
-        r0 += ci > e0;
-        r1 += ci > e1;
-        const int better = __popcll(__ballot(e0 > ci)) + (k > 64 ? __popcll(__ballot(e1 > ci)) : 0);
-        lc = lane == i ? better : lc;
-    }
-    const int pc = rc + lc, p0 = lane + r0, p1 = lane + 64 + r1;
-    // all reads above are complete (their values are consumed) before any lane writes
-    if (lane < n && pc < k) list[pc] = c;
-    if (lane < k && p0 < k) list[p0] = e0;
-    if (lane + 64 < k && p1 < k) list[p1] = e1;
-}
+// (merge_queue, the fold of one query's candidate queue into its sorted list, lives in stream.h: ivf.hip uses it too)
 
 // Two queries per call for k <= 32 and queues of <= 32 slots: lanes 0-31 merge query qa, lanes 32-63 query qb
 // (nb == 0: no partner).  Same ranking rule as merge_queue; the ballot's two halves serve the two queries.  Also
@@ -586,9 +565,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void resident_search_kernel(
 // query, k ascending from 0 — the very chain the f32 MFMA computes, so scores stay bit-identical to
 // the oracle.  Query values are block-uniform (scalar loads).  Selection: the block's first tile ranks
 // its 256 keys per query by counting (no merges); later tiles offer only keys above the running k-th
-// best into a 256-slot LDS queue that merge_queue folds into the sorted list.
-constexpr int ST_ROWS = 256, ST_LDB = 144;  // LDS row stride 144 B: conflict-free 16-B reads at one row per lane
-
+// best into a 256-slot LDS queue that merge_queue folds into the sorted list.  (Tile geometry: stream.h.)
 template <int NQ>
 struct StreamSmem {
     static __host__ __device__ size_t bytes(int k, bool facet = false) {
@@ -597,7 +574,6 @@ struct StreamSmem {
     }
 };
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 // acc[j] = fmaf(q[j], p, acc[j]) for the NQ queries of one k; pairs of queries share one packed FMA
 // (v_pk_fma_f32: two independent IEEE fmas, so each chain is unchanged).

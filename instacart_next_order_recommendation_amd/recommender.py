@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .encoder import DeviceEncoder
 from .model_io import LoadedModel, load_model_dir
-from .search import DeviceIndex, facet_masks
+from .search import DeviceIndex, IvfIndex, facet_masks, train_centroids
 
 logger = logging.getLogger(__name__)
 
@@ -197,6 +197,25 @@ def boost_plan(boosts, boost_weight, only_boosted: bool, n_queries: int, pid_to_
     return lists, bool(only_boosted)
 
 
+def ann_plan(probes, n_lists, *, aisles=None, departments=None, boosts=None, only_boosted: bool = False):
+    """A request's `probes` argument, checked before any GPU work -> None (the exact search: probes is None) or the
+    number of lists the IVF search scans.  n_lists: the lists of the recommender's IvfIndex, None without one
+    (Recommender(ann_lists=None)).  ValueError: probes without an IVF index, probes together with aisles, departments
+    or boosts (the IVF scan reads neither facets nor boost lists), probes outside [1, min(n_lists, ICREC_MAX_K)]."""
+    if probes is None:
+        return None
+    if n_lists is None:
+        raise ValueError("probes needs a recommender built with ann_lists")
+    for what, given in (("aisles", aisles is not None), ("departments", departments is not None),
+                        ("boosts", boosts is not None or bool(only_boosted))):
+        if given:
+            raise ValueError(f"probes cannot be combined with {what}: the IVF search takes exclusions and diversity only")
+    limit = min(int(n_lists), _native.ICREC_MAX_K)
+    if isinstance(probes, bool) or int(probes) != probes or not 1 <= int(probes) <= limit:
+        raise ValueError(f"probes must be an integer in [1, {limit}], got {probes!r}")
+    return int(probes)
+
+
 class SbertModel:
     """What `self.model` is in the reference (a SentenceTransformer): tokenizer + device encoder
     with an `encode(texts, batch_size, show_progress_bar, normalize_embeddings)` method."""
@@ -248,7 +267,10 @@ class SbertModel:
 class Recommender:
     """Two-tower recommender: same surface as the reference's Recommender (:133-225)."""
 
-    def __init__(self, model_dir: Path | str, corpus_path: Path, batch_size: int = 64, use_index: bool = True):
+    _ann: Optional[IvfIndex] = None  # the IVF index beside _index (ann_lists), searched by requests that pass `probes`
+
+    def __init__(self, model_dir: Path | str, corpus_path: Path, batch_size: int = 64, use_index: bool = True,
+                 ann_lists: int | None = None):
         self.model_dir = self._resolve_model_dir(model_dir)
         self.corpus_path = Path(corpus_path).resolve()
         self.product_ids, self.product_texts = self._load_corpus()
@@ -262,6 +284,9 @@ class Recommender:
         self._index = DeviceIndex(self.product_embeddings, self.device,
                                   storage=os.getenv("ICREC_INDEX_STORAGE", "f32+filter"))
         self._set_facets()
+        # ann_lists: an IVF index of that many lists beside the exact one (a second copy of the rows); only requests
+        # that pass `probes` search it
+        self._ann = IvfIndex(self._index, train_centroids(self._index, int(ann_lists))) if ann_lists else None
         self._fast = None
         if os.getenv("ICREC_USE_GRAPH", "1") != "0":
             from .fastpath import SingleRequestPath
@@ -366,14 +391,16 @@ class Recommender:
         return [None if a is None and d is None else (a, d) for a, d in zip(*per_facet)]
 
     def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None, mmr=None,
-                       boost=None):
+                       boost=None, probes=None):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
         current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  allow: per-query
         facet constraints (_facet_allow).  mmr: (lambda, candidates) of diversity_plan - the search is then
         `candidates` wide and the k results are re-selected from it on the device, inside the search time.
         boost: (per-query {row: weight} or None, only_boosted) of boost_plan - the search result is merged with the
         listed rows on the device (DeviceIndex.search_boosted; with only_boosted there is no search), at the width the
-        MMR re-selection consumes when there is one, inside the search time."""
+        MMR re-selection consumes when there is one, inside the search time.
+        probes: ann_plan's count - the IVF index is searched instead of the exact one (never with allow or boost), at
+        the candidate width when mmr is given; the re-selection reads the exact index's rows."""
         if allow is not None:
             allow = facet_masks(allow, len(cu) - 1, self._index.n_facets, self.device)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
@@ -383,7 +410,11 @@ class Recommender:
         emb = self.model.encoder.encode_packed_host(ids, cu)
         if ev:
             ev[1].record(stream)
-        if boost is not None:
+        if probes is not None:
+            idx, sc = self._ann.search(emb, k if mmr is None else mmr[1], probes, ex)
+            if mmr is not None:
+                idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
+        elif boost is not None:
             idx, sc = self._index.search_boosted(emb, k if mmr is None else mmr[1], boost[0], ex, allow, only=boost[1])
             if mmr is not None:
                 idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
@@ -398,11 +429,13 @@ class Recommender:
 
     def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, aisles=None,
                        departments=None, diversity=None, candidates=None, boosts=None, boost_weight=None,
-                       only_boosted=False):
+                       only_boosted=False, probes=None):
         """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path (always
-        when the request names aisles or departments, asks for diversity, or boosts products).
+        when the request names aisles or departments, asks for diversity, boosts products, or probes the IVF index).
         -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
+        probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
+                          boosts=boosts, only_boosted=only_boosted)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         allow = self._facet_allow(None if aisles is None else [aisles], None if departments is None else [departments], 1)
         boost = boost_plan([boosts], boost_weight, only_boosted, 1, self._pid_to_row)
@@ -411,11 +444,11 @@ class Recommender:
         tok_ms = (time.time() - t0) * 1000
         ex = self._exclusion_rows([exclude_product_ids])
         rows = ex[0] if ex else []
-        fast = self._fast_path() if allow is None and mmr is None and boost is None else None
+        fast = self._fast_path() if allow is None and mmr is None and boost is None and probes is None else None
         if fast is not None and fast.supports(len(ids), k, len(rows)):
             idx, sc, *ms = fast.run(ids, k, rows, timed=timed)
         else:
-            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr, boost)
+            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr, boost, probes)
             idx, sc = idx[0], sc[0]
         results = self._to_results(idx, sc)
         return (results, tok_ms + ms[0], ms[1]) if timed else results
@@ -428,12 +461,14 @@ class Recommender:
                         aisles: Optional[Sequence[Optional[Sequence[str]]]] = None,
                         departments: Optional[Sequence[Optional[Sequence[str]]]] = None,
                         diversity: float | None = None, candidates: int | None = None, boosts=None,
-                        boost_weight: float | None = None, only_boosted: bool = False
+                        boost_weight: float | None = None, only_boosted: bool = False, probes: int | None = None
                         ) -> list[list[tuple[str, float]]]:
         """Many contexts in one GPU pass; element i equals recommend(queries[i], ...).  aisles / departments: per
         query None or the admitted names, as recommend takes them.  diversity / candidates: one value for the whole
         batch, as recommend takes them.  boosts: None or one entry per query, each as recommend takes it; boost_weight
-        and only_boosted: one value for the whole batch."""
+        and only_boosted: one value for the whole batch.  probes: one value for the whole batch, as recommend takes it."""
+        probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
+                          boosts=boosts, only_boosted=only_boosted)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
         if not queries:
@@ -441,7 +476,8 @@ class Recommender:
         k = self._k(top_k)
         ex = self._exclusion_rows(exclude_product_ids)
         allow = self._facet_allow(aisles, departments, len(queries))
-        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow, mmr=mmr, boost=boost)
+        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow, mmr=mmr, boost=boost,
+                                      probes=probes)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))]
 
     def recommend_batches(self, batches, top_k: int = 10, exclude_product_ids=None):
@@ -479,7 +515,7 @@ class Recommender:
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
-                  only_boosted: bool = False) -> list[tuple[str, float]]:
+                  only_boosted: bool = False, probes: int | None = None) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
         One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0".
         aisles / departments (keyword-only; names from .aisles / .departments): only products of one of these aisles
@@ -503,10 +539,15 @@ class Recommender:
         user's history by the model's score).  It composes with exclude_product_ids, aisles and departments; with
         diversity the boosted ranking is `candidates` wide and MMR re-selects from it, with the adjusted scores as the
         relevance.  Such a request takes the un-captured path; boosts None or empty without only_boosted is the plain
-        request: the same launches, the same results.  Bad arguments raise ValueError before any GPU work."""
+        request: the same launches, the same results.  Bad arguments raise ValueError before any GPU work.
+        probes (keyword-only; a recommender built with ann_lists): search only the `probes` lists of the IVF index whose
+        centroids match the query best (IvfIndex.search): the exact top_k of those lists, approximate only in which
+        products it looks at; probes = ann_lists is the exact search's result.  It composes with exclude_product_ids
+        and with diversity (the IVF search is then `candidates` wide) and takes the un-captured path; together with
+        aisles, departments or boosts, or without ann_lists, it raises ValueError.  probes None is the plain request."""
         return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments,
                                    diversity=diversity, candidates=candidates, boosts=boosts, boost_weight=boost_weight,
-                                   only_boosted=only_boosted)
+                                   only_boosted=only_boosted, probes=probes)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -530,7 +571,7 @@ class MonitoredRecommender(Recommender):
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
-                  only_boosted: bool = False) -> list[tuple[str, float]]:
+                  only_boosted: bool = False, probes: int | None = None) -> list[tuple[str, float]]:
         """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
         replays (fastpath.py): the three timing fields keep their meaning there.  A diversified request's
         re-selection and a boosted request's merge count into the similarity time."""
@@ -538,7 +579,7 @@ class MonitoredRecommender(Recommender):
         results, encode_ms, sim_ms = self._recommend_one(query, top_k, exclude_product_ids, timed=True, aisles=aisles,
                                                          departments=departments, diversity=diversity,
                                                          candidates=candidates, boosts=boosts, boost_weight=boost_weight,
-                                                         only_boosted=only_boosted)
+                                                         only_boosted=only_boosted, probes=probes)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

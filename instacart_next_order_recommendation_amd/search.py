@@ -377,6 +377,120 @@ class DeviceIndex:
         return out
 
 
+class IvfIndex:
+    """An inverted-file index beside a DeviceIndex (icrec_ivf, include/icrec.h): the rows split into
+    n_lists = len(centroids) lists, each row in the list whose centroid the library's own search names for it; a
+    search scans only each query's `probes` best lists.  The result is the exact top-k of the probed lists, in
+    DeviceIndex.search's bits; with probes == n_lists it is DeviceIndex.search's.  Holds a second copy of the rows (in
+    list order); `index` must outlive it.  Creation is a set-up call: never while a call on `index` runs."""
+
+    def __init__(self, index: DeviceIndex, centroids):
+        self.index = index
+        self.device = index.device
+        self._ws_by_stream = _native.StreamScratch(self.device)
+        c = torch.as_tensor(centroids)
+        if c.dim() != 2 or c.shape[1] != index.dim:
+            raise ValueError(f"centroids must be [n_lists, {index.dim}], got {tuple(c.shape)}")
+        c = c.to(device=self.device, dtype=torch.float32).contiguous()
+        h = C.c_void_p()
+        torch.cuda.synchronize(self.device)
+        _native.check(_native.lib().icrec_ivf_create(index._h, ptr(c), int(c.shape[0]), C.byref(h)), "icrec_ivf_create")
+        self._h = h
+
+    @property
+    def n_lists(self) -> int:
+        return int(_native.lib().icrec_ivf_lists(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _native.lib().icrec_ivf_destroy(self._h)
+            self._h = None
+        self._ws_by_stream.clear()
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def layout(self):
+        """(perm int32 [n_rows], list_off int64 [n_lists + 1]) device tensors: the local rows sorted by (list, row) and
+        the list boundaries in that order."""
+        perm = torch.empty(self.index.n_rows, dtype=torch.int32, device=self.device)
+        off = torch.empty(self.n_lists + 1, dtype=torch.int64, device=self.device)
+        _native.check(_native.lib().icrec_ivf_layout(self._h, ptr(perm), ptr(off), stream_ptr(self.device)),
+                      "icrec_ivf_layout")
+        return perm, off
+
+    def _workspace(self, n_queries: int, k: int, probes: int) -> torch.Tensor:
+        """This stream's scratch block, large enough for one search of this shape."""
+        need = int(_native.lib().icrec_ivf_search_workspace_bytes(self._h, n_queries, k, probes))
+        if need == 0:
+            raise _native.IcrecError(f"bad IVF search shape: n_queries={n_queries}, k={k}, probes={probes} "
+                                     f"of {self.n_lists} lists")
+        return self._ws_by_stream.block(need)
+
+    def search(self, q, k: int, probes: int, exclude: Optional[Sequence[Iterable[int]]] = None):
+        """The k best rows of each query's `probes` best lists: (idx int64[Q,k] with -1 pads, score float32[Q,k]),
+        ordered as DeviceIndex.search orders.  `exclude`: per-query local (original) rows."""
+        q = self.index._queries(q)
+        Q = int(q.shape[0])
+        ei, eo = exclusion_csr(exclude, Q, self.device)
+        idx = torch.empty((Q, k), dtype=torch.int64, device=self.device)
+        sc = torch.empty((Q, k), dtype=torch.float32, device=self.device)
+        self.search_into(q, k, probes, ei, eo, idx, sc)
+        return idx, sc
+
+    def search_into(self, q: torch.Tensor, k: int, probes: int, excl_idx: Optional[torch.Tensor],
+                    excl_off: Optional[torch.Tensor], out_idx: torch.Tensor, out_score: torch.Tensor,
+                    ws: Optional[torch.Tensor] = None) -> None:
+        """Allocation-free form of `search` on caller-owned device buffers (hipGraph-capturable once the workspace for
+        this (Q, k, probes) exists, or with `ws` of the caller's own): q float32 [Q, dim], out_idx int64 [Q, k],
+        out_score float32 [Q, k]."""
+        Q = int(q.shape[0])
+        if ws is None:
+            ws = self._workspace(Q, k, probes)
+        _native.check(_native.lib().icrec_ivf_search(self._h, ptr(q), Q, k, probes, ptr(excl_idx), ptr(excl_off),
+                                                     ptr(out_idx), ptr(out_score), ptr(ws), ws.numel(),
+                                                     stream_ptr(self.device)), "icrec_ivf_search")
+
+
+def train_centroids(index: DeviceIndex, n_lists: int, iters: int = 10, sample: int = 64, seed: int = 0) -> torch.Tensor:
+    """Centroids for an IvfIndex over `index`, float32 [n_lists, dim] on its device: spherical k-means on at most
+    sample * n_lists of the stored rows, chosen by a seeded permutation, whose first n_lists rows are the initial
+    centroids.  Each iteration assigns the sample with the library (a temporary DeviceIndex of the centroids, searched
+    at k = 1 in chunks of rows) and replaces every centroid by the normalised mean of its members; a list without
+    members keeps its centroid.  The sums are taken in float64 over the members in sample order (sorted by list, then
+    segment sums): no atomics, so one seed gives the same bits every time on one machine.  torch does the plumbing;
+    this is not the hot path."""
+    if not 1 <= n_lists <= index.n_rows:
+        raise ValueError(f"n_lists must be in [1, {index.n_rows}], got {n_lists}")
+    dev = index.device
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(int(seed))
+    m = min(index.n_rows, int(sample) * n_lists)
+    rows = torch.randperm(index.n_rows, generator=gen)[:m].to(dev)
+    X = index.export()[rows]  # (the export is a transient fp32 copy of the whole shard, freed on return from here)
+    cent = X[:n_lists].clone()
+    chunk = 1 << 16
+    for _ in range(int(iters)):
+        tmp = DeviceIndex(cent, device=dev)
+        try:
+            assign = torch.cat([tmp.search(X[lo:lo + chunk], 1)[0][:, 0] for lo in range(0, m, chunk)])
+        finally:
+            tmp.close()
+        order = torch.argsort(assign, stable=True)
+        counts = torch.bincount(assign, minlength=n_lists)
+        csum = torch.cumsum(X[order].to(torch.float64), dim=0)  # a sequential scan per column: order-fixed
+        end = torch.cumsum(counts, 0)
+        zero = torch.zeros((1, index.dim), dtype=torch.float64, device=dev)
+        upto = torch.cat([zero, csum])[end]
+        sums = upto - torch.cat([zero, upto[:-1]])
+        mean = torch.nn.functional.normalize(sums, p=2, dim=1, eps=1e-12).to(torch.float32)
+        cent = torch.where((counts > 0)[:, None], mean, cent)
+    return cent.contiguous()
+
+
 def merge_topk(keys: torch.Tensor, k: int):
     """Merge sorted partial key lists [n_lists, Q, k] (int64-viewed uint64) into (idx, score) [Q,k]."""
     if keys.dim() != 3 or keys.shape[2] != k:
