@@ -396,6 +396,59 @@ ICREC_API int icrec_search_faceted(icrec_index* idx, const float* q_dev, int32_t
                          int64_t* out_idx_dev, float* out_score_dev,
                          void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Row sets: restrict each query to named sets of rows ("only products sold at this store", "in stock", "vegan").
+ * Unlike a facet, which gives a row exactly one value, a row may belong to any number of sets.  An index may carry
+ * n_sets in [1, ICREC_MAX_ROWSETS] row sets, each a bitmap over its LOCAL rows; a query names up to
+ * ICREC_MAX_SETS_PER_QUERY of them by id, in slots:
+ *   - a slot with id < 0 constrains nothing;
+ *   - a slot with id in [0, n_sets) requires the row's bit in that set;
+ *   - a slot with id >= n_sets admits no row (such an id is never used as an index: the ids live in device memory,
+ *     where the host cannot refuse them, and the rule is memory-safe for every int32);
+ *   - the same id in two slots counts once.
+ * A row is admissible for a query iff every slot admits it, the facet masks admit it (when allow_dev is given) and it
+ * is not in the query's exclusion segment.
+ * The result of icrec_search_in_sets is bit-identical, indices and scores, to icrec_search with exclusion lists equal
+ * to the given exclusions united with every inadmissible row, for every row storage, every k and every batch size.  A
+ * query with no admissible row gets (-1, 0.0) pads; a query whose slots are all < 0 gets icrec_search_faceted's bits. */
+#define ICREC_MAX_ROWSETS 65535
+#define ICREC_MAX_SETS_PER_QUERY 4
+
+/* Set, replace or (bits_host == NULL) remove the index's row sets.
+ *   bits_host  uint32[n_sets][W], W = ceil(n_rows / 32)  HOST pointer; bit (r & 31) of word (r >> 5) of set s says
+ *              that local row r is in s.  Bits at or past n_rows in the last word are ignored (the library clears
+ *              them).  Copied to the device before the call returns.
+ * n_sets outside [1, ICREC_MAX_ROWSETS] (with a non-NULL bits_host) is ICREC_EINVAL and changes nothing; a failed
+ * allocation is ICREC_ENOMEM and changes nothing either.
+ * A set-up call like icrec_index_set_facets: it allocates, may synchronise the device, and must never be issued while
+ * a call on the index is running.  The rows, their filter planes / fragments and the facets are not touched, and
+ * icrec_search, icrec_search_faceted (icrec_search_in_sets without set ids), icrec_search_partial, icrec_rank_all,
+ * icrec_scores, icrec_ivf_search and icrec_boost_select ignore the sets. */
+ICREC_API int icrec_index_set_rowsets(icrec_index* idx, const uint32_t* bits_host, int32_t n_sets);
+/* Replace the W words of one set (an in-stock bitmap that changes through the day); bits_host as one set of
+ * icrec_index_set_rowsets.  ICREC_EINVAL for `set` outside [0, n_sets) or an index without sets.  A set-up call under
+ * the same contract: it copies and may synchronise.  A captured graph replayed afterwards follows the new set. */
+ICREC_API int icrec_index_write_rowset(icrec_index* idx, int32_t set, const uint32_t* bits_host);
+/* Row sets of the index: 0 when none are set, -1 for a NULL handle. */
+ICREC_API int32_t icrec_index_rowsets(const icrec_index* idx);
+
+/* Scratch bytes of icrec_search_in_sets (0 for a bad argument); equal to icrec_search_workspace_bytes. */
+ICREC_API size_t icrec_search_in_sets_workspace_bytes(const icrec_index* idx, int32_t n_queries, int32_t k);
+
+/* icrec_search_faceted restricted to row sets.
+ *   set_ids_dev     int32[n_queries][sets_per_query]  the queries' slots in DEVICE memory, or NULL
+ *   sets_per_query  in [1, ICREC_MAX_SETS_PER_QUERY] (not looked at when set_ids_dev is NULL)
+ * set_ids_dev == NULL: this IS icrec_search_faceted - the same launches, the same bits.  ICREC_EINVAL: set_ids_dev !=
+ * NULL on an index without sets, sets_per_query out of range; the other argument checks are icrec_search's.
+ * Nothing is allocated and nothing synchronises; the call is graph-capturable.  The ids and the bitmaps are read from
+ * device memory when the kernels run: a captured graph replayed after the caller rewrote the id buffer, or after
+ * icrec_index_write_rowset rewrote a set, follows the new contents. */
+ICREC_API int icrec_search_in_sets(icrec_index* idx, const float* q_dev, int32_t n_queries, int32_t k,
+                         const int32_t* excl_idx_dev, const int32_t* excl_off_dev,
+                         const uint32_t* allow_dev,
+                         const int32_t* set_ids_dev, int32_t sets_per_query,
+                         int64_t* out_idx_dev, float* out_score_dev,
+                         void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Diversity re-selection of a search result: Maximal Marginal Relevance (Carbonell & Goldstein 1998) over each
  * query's k candidates, entirely on the device.  Scratch bytes (0 for a NULL index, n_queries < 1 or k outside
  * [1, ICREC_MAX_K]): the queries' k x k similarity matrices. */

@@ -17,6 +17,8 @@ ICREC_MAX_K = 128
 ICREC_MAX_BOOSTS = 1024
 ICREC_MAX_FACETS = 2
 ICREC_FACET_MASK_WORDS = 8
+ICREC_MAX_ROWSETS = 65535
+ICREC_MAX_SETS_PER_QUERY = 4
 ICREC_MAX_SEQLEN = 512
 COMM_ID_BYTES = 128
 GEMM_F32, GEMM_F16X3 = 0, 1
@@ -41,6 +43,8 @@ EXPORTS = [
     "icrec_exclusions_to_shard_csr_workspace_bytes", "icrec_exclusions_to_shard_csr",
     "icrec_search_workspace_bytes", "icrec_search", "icrec_search_partial", "icrec_merge_topk",
     "icrec_index_set_facets", "icrec_index_facets", "icrec_search_faceted_workspace_bytes", "icrec_search_faceted",
+    "icrec_index_set_rowsets", "icrec_index_write_rowset", "icrec_index_rowsets",
+    "icrec_search_in_sets_workspace_bytes", "icrec_search_in_sets",
     "icrec_mmr_select_workspace_bytes", "icrec_mmr_select",
     "icrec_boost_select_workspace_bytes", "icrec_boost_select",
     "icrec_ivf_create", "icrec_ivf_destroy", "icrec_ivf_lists", "icrec_ivf_layout",
@@ -149,6 +153,11 @@ def lib() -> C.CDLL:
         "icrec_index_facets": (i32, [vp]),
         "icrec_search_faceted_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_search_faceted": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "icrec_index_set_rowsets": (C.c_int, [vp, vp, i32]),
+        "icrec_index_write_rowset": (C.c_int, [vp, i32, vp]),
+        "icrec_index_rowsets": (i32, [vp]),
+        "icrec_search_in_sets_workspace_bytes": (sz, [vp, i32, i32]),
+        "icrec_search_in_sets": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
         "icrec_mmr_select_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_mmr_select": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, sz, vp]),
         "icrec_boost_select_workspace_bytes": (sz, [vp, i32, i32]),

@@ -11,6 +11,7 @@ ignored; a missing model directory or corpus file is an error).
                                                       [--diversity FLOAT] [--candidates INT]
                                                       [--ann-lists N --probes P]
                                                       [--boost PID[=W]]... [--boost-weight W] [--only-boosted]
+                                                      [--product-sets FILE --within NAME]...
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
 and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
@@ -156,6 +157,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "it takes --boost-weight)")
     ap.add_argument("--boost-weight", type=float, default=None, metavar="W", help="the weight of every --boost without its own")
     ap.add_argument("--only-boosted", action="store_true", help="rank the --boost products alone (buy it again)")
+    ap.add_argument("--product-sets", type=Path, default=None, metavar="FILE",
+                    help="JSON file {set name: [product id, ...]}: named product sets (store assortments, in stock, ...)")
+    ap.add_argument("--within", action="append", default=None, metavar="NAME",
+                    help="only products of this --product-sets set (repeatable, up to 4: products in every named set)")
     return ap
 
 
@@ -175,6 +180,10 @@ def main(argv=None) -> int:
         return baselines_main(argv[1:])
     args = build_parser().parse_args(argv)
     ann_lists, probes = ann_args(args)
+    if args.within and args.product_sets is None:
+        raise SystemExit("--within needs --product-sets")
+    if args.product_sets is not None and not args.product_sets.exists():
+        raise SystemExit(f"product sets file {args.product_sets} does not exist")
     cfg = read_settings(args.config)
     if not cfg["corpus"].exists():
         raise SystemExit(f"corpus file {cfg['corpus']} does not exist (this build never downloads one)")
@@ -189,15 +198,19 @@ def main(argv=None) -> int:
             raise SystemExit("--boost without =W needs --boost-weight")
         boosts = {pid: args.boost_weight if w is None else w for pid, w in boosts.items()}
 
-    from .recommender import Recommender
+    from .recommender import Recommender, load_product_sets
 
+    try:
+        product_sets = load_product_sets(args.product_sets) if args.product_sets is not None else None
+    except ValueError as e:  # (a file that is not JSON raises json.JSONDecodeError, a ValueError too)
+        raise SystemExit(f"--product-sets {args.product_sets}: {e}")
     rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"],
-                      ann_lists=ann_lists)
+                      ann_lists=ann_lists, product_sets=product_sets)
     try:
         hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department,
                              diversity=args.diversity, candidates=args.candidates, boosts=boosts or None,
-                             only_boosted=args.only_boosted, probes=probes)
-    except ValueError as e:  # an aisle / department the catalog does not have, a bad --diversity / --candidates / --boost / --probes
+                             only_boosted=args.only_boosted, probes=probes, within=args.within)
+    except ValueError as e:  # an aisle / department / product set the catalog does not have, a bad --diversity / --candidates / --boost / --probes
         raise SystemExit(str(e))
     if args.json:
         for rank, (pid, score) in enumerate(hits, 1):

@@ -1,8 +1,8 @@
 // index.h — what an icrec_index handle points to, shared by index.hip (which creates and destroys it), search.hip
 // (which builds its filter storage and searches it), sort.hip (icrec_rank_all), mmr.hip and boost.hip (which read its
 // stored rows), and the device code that index.hip, search.hip and boost.hip share: the row normalisation kernel, the
-// exclusion search and the facet test.  What needs no handle - the shard row rule, the gathered exact-cosine tile that
-// mmr.hip and boost.hip read the stored rows with - is in common.h.
+// exclusion search, the facet test and the row set words.  What needs no handle - the shard row rule, the gathered
+// exact-cosine tile that mmr.hip and boost.hip read the stored rows with - is in common.h.
 #pragma once
 
 #include <type_traits>
@@ -26,7 +26,13 @@ struct Index {
     int stream_max_q = 8;          // ICREC_STREAM_MAX_Q at creation
     uint16_t* facets = nullptr;    // icrec_index_set_facets: one word per row, zero padded to whole 256-row tiles
     int n_facets = 0;
+    uint32_t* rowsets = nullptr;   // icrec_index_set_rowsets: [n_rowsets][rowset_words(n_rows)] bitmaps over the local rows
+    int n_rowsets = 0;
 };
+
+// Words of one row set on the device: ceil(n_rows / 32) bitmap words, zero padded to whole 256-row tiles (8 words per
+// tile, the widest tile any search kernel walks), as the facet words are: every tile of every kernel reads inside it.
+static inline int64_t rowset_words(int64_t n_rows) { return (n_rows + 255) / 256 * 8; }
 
 static inline bool rows_are_bf16(const Index* ix) { return ix->storage == ICREC_ROWS_BF16 || ix->storage == ICREC_ROWS_BF16_FILTER; }
 // One stored value of `rows` in a kernel templated on "the rows are bf16": bf16 bits or a float.
@@ -134,6 +140,57 @@ __device__ __forceinline__ bool facet_admits(const uint32_t* am, int q, unsigned
     const unsigned v0 = fw & 255u, v1 = (fw >> 8) & 255u;
     const uint32_t* m = am + q * FACET_LDS_WORDS;
     return ((m[v0 >> 5] >> (v0 & 31)) & (m[ICREC_FACET_MASK_WORDS + (v1 >> 5)] >> (v1 & 31)) & 1u) != 0u;
+}
+
+// ---- row sets (icrec_search_in_sets): the index's bitmaps over its local rows, and up to ICREC_MAX_SETS_PER_QUERY set
+// ids per query; a row is a candidate only if every slot of its query admits it.  The SETS arm of a kernel is the
+// instantiation whose parameter pack holds one SetArgs; it applies the facet test as well (facet.allow == NULL: the
+// masks it loads are all ones, facet.rows == NULL: every facet word reads as 0), so the FACET arm and the plain arm
+// stay what they were before sets existed.  A block turns each of its queries' slots into SET_FREE (id < 0, or no such
+// slot: constrains nothing), SET_NONE (id >= n_sets, or a padding query: admits no row; never used as an index) or
+// the id, once; per tile it then ANDs the words of the query's sets into ONE word per (query, 32 rows) in LDS, and the
+// per-candidate test is that word and a shift whatever per_query is.  The same id in two slots ANDs the same word twice.
+struct SetArgs {
+    FacetArgs facet;
+    const uint32_t* bits;  // [n_sets][words], words = rowset_words(n_rows)
+    const int32_t* ids;    // [Q][per_query], read when the kernel runs
+    int n_sets, per_query;
+    int64_t words;
+};
+static_assert(ICREC_MAX_SETS_PER_QUERY == 4, "a query's slots are one int4");
+constexpr int SET_FREE = -1, SET_NONE = -2;
+
+__device__ __forceinline__ FacetArgs facet_args(const SetArgs& sa) { return sa.facet; }
+__device__ __forceinline__ SetArgs set_args() { return SetArgs{facet_args(), nullptr, nullptr, 0, 0, 0}; }
+__device__ __forceinline__ SetArgs set_args(const FacetArgs&) { return set_args(); }
+__device__ __forceinline__ SetArgs set_args(const SetArgs& sa) { return sa; }
+template <class... A>
+constexpr bool has_sets = (std::is_same_v<A, SetArgs> || ... || false);
+
+// The four slots of query q (of Q), as SET_FREE, SET_NONE or a set id in [0, n_sets).
+__device__ __forceinline__ int4 set_slots(const SetArgs& sa, int q, int Q) {
+    int s[ICREC_MAX_SETS_PER_QUERY];
+#pragma unroll
+    for (int i = 0; i < ICREC_MAX_SETS_PER_QUERY; ++i) {
+        s[i] = q >= Q ? SET_NONE : SET_FREE;
+        if (q < Q && i < sa.per_query) {
+            const int id = sa.ids[(size_t)q * sa.per_query + i];
+            s[i] = id < 0 ? SET_FREE : id >= sa.n_sets ? SET_NONE : id;
+        }
+    }
+    return make_int4(s[0], s[1], s[2], s[3]);
+}
+
+// Word gw (rows 32 gw .. 32 gw + 31) of the intersection of the sets in `slots`; gw < words.
+__device__ __forceinline__ uint32_t set_word(const uint32_t* __restrict__ bits, int64_t words, const int4& slots, int64_t gw) {
+    const int s[ICREC_MAX_SETS_PER_QUERY] = {slots.x, slots.y, slots.z, slots.w};
+    uint32_t r = ~0u;
+#pragma unroll
+    for (int i = 0; i < ICREC_MAX_SETS_PER_QUERY; ++i) {
+        if (s[i] == SET_NONE) r = 0u;
+        else if (s[i] >= 0) r &= bits[(size_t)s[i] * words + gw];
+    }
+    return r;
 }
 
 #endif  // __HIPCC__

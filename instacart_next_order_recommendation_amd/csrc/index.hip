@@ -1,8 +1,9 @@
 // index.hip — the life cycle of an icrec_index handle (index.h: struct Index): creation with row normalisation,
-// facets, export, the accessors and destruction; and icrec_normalize_rows.  The filter storages' layout belongs to the
+// facets, row sets, export, the accessors and destruction; and icrec_normalize_rows.  The filter storages' layout belongs to the
 // kernels that read it: search.hip builds it (build_filter_storage).
 #include <stdlib.h>
 
+#include <new>
 #include <vector>
 
 #include "index.h"
@@ -92,6 +93,7 @@ int icrec_index_destroy(icrec_index* h) {
     hipFree(ix->plane_lo);
     hipFree(ix->frag);
     hipFree(ix->facets);
+    (void)hipFree(ix->rowsets);
     delete ix;
     return ICREC_OK;
 }
@@ -130,6 +132,67 @@ int icrec_index_set_facets(icrec_index* h, const uint8_t* facets_host, int32_t n
 }
 
 int32_t icrec_index_facets(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_facets : -1; }
+
+// One set's words as the device keeps them: the caller's ceil(n_rows / 32) words with the bits at or past n_rows
+// cleared, zero padded to rowset_words(n_rows).
+static void pad_rowset(const Index* ix, const uint32_t* src, uint32_t* dst) {
+    const int64_t w = (ix->n_rows + 31) / 32, padded = rowset_words(ix->n_rows);
+    for (int64_t i = 0; i < w; ++i) dst[i] = src[i];
+    if (ix->n_rows % 32) dst[w - 1] &= (1u << (ix->n_rows % 32)) - 1u;
+    for (int64_t i = w; i < padded; ++i) dst[i] = 0u;
+}
+
+int icrec_index_set_rowsets(icrec_index* h, const uint32_t* bits_host, int32_t n_sets) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix, "icrec_index_set_rowsets: NULL index");
+    ICREC_HIP(hipSetDevice(ix->device));
+    if (bits_host == nullptr) {
+        ICREC_HIP(hipFree(ix->rowsets));
+        ix->rowsets = nullptr;
+        ix->n_rowsets = 0;
+        return ICREC_OK;
+    }
+    ICREC_REQUIRE(n_sets >= 1 && n_sets <= ICREC_MAX_ROWSETS, "icrec_index_set_rowsets: n_sets must be in [1, %d] (got %d)",
+                  ICREC_MAX_ROWSETS, n_sets);
+    const size_t w = (size_t)((ix->n_rows + 31) / 32), padded = (size_t)rowset_words(ix->n_rows);
+    std::vector<uint32_t> words;
+    try {
+        words.resize(padded * n_sets);
+    } catch (const std::bad_alloc&) {
+        set_error("icrec_index_set_rowsets: no host memory for %zu bytes", padded * n_sets * 4);
+        return ICREC_ENOMEM;
+    }
+    for (int32_t s = 0; s < n_sets; ++s) pad_rowset(ix, bits_host + s * w, words.data() + s * padded);
+    uint32_t* dev = nullptr;
+    if (hipMalloc(&dev, words.size() * 4) != hipSuccess) {
+        set_error("icrec_index_set_rowsets: hipMalloc of %zu bytes failed", words.size() * 4);
+        return ICREC_ENOMEM;
+    }
+    if (hipMemcpy(dev, words.data(), words.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        set_error("icrec_index_set_rowsets: copying the row sets to the device failed");
+        return ICREC_EHIP;
+    }
+    (void)hipFree(ix->rowsets);
+    ix->rowsets = dev;
+    ix->n_rowsets = n_sets;
+    return ICREC_OK;
+}
+
+int icrec_index_write_rowset(icrec_index* h, int32_t set, const uint32_t* bits_host) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix && bits_host, "icrec_index_write_rowset: NULL argument");
+    ICREC_REQUIRE(ix->rowsets != nullptr, "icrec_index_write_rowset: the index has no row sets");
+    ICREC_REQUIRE(set >= 0 && set < ix->n_rowsets, "icrec_index_write_rowset: set must be in [0, %d) (got %d)", ix->n_rowsets, set);
+    ICREC_HIP(hipSetDevice(ix->device));
+    const size_t padded = (size_t)rowset_words(ix->n_rows);
+    std::vector<uint32_t> words(padded);
+    pad_rowset(ix, bits_host, words.data());
+    ICREC_HIP(hipMemcpy(ix->rowsets + (size_t)set * padded, words.data(), padded * 4, hipMemcpyHostToDevice));
+    return ICREC_OK;
+}
+
+int32_t icrec_index_rowsets(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_rowsets : -1; }
 
 int64_t icrec_index_rows(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_rows : 0; }
 int64_t icrec_index_row_offset(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->row_offset : 0; }

@@ -74,8 +74,8 @@ __device__ __forceinline__ void merge_queue2(u64* list, const u64* queue, int qc
 // of the 32x32 MFMA (acc[TM][TN]: this wave's row tiles wm, query tiles wn) and keeps, per query, the k best
 // (score, row) keys seen in a sorted LDS list; write() stores the lists.  The LDS carve follows the kernel's operand
 // staging (all offsets multiples of 16 B): thresholds [BN] | queue counters [BN] | flags [4] | FACET: allow masks
-// [BN][FACET_LDS_WORDS], facet words of the current and the next tile [2][BM] | lists [BN][k] | candidate queues
-// [BN][qcap].
+// [BN][FACET_LDS_WORDS], facet words of the current and the next tile [2][BM] | SETS: the queries' slots [BN] (int4),
+// set words of the current and the next tile [2][BM / 32][BN] | lists [BN][k] | candidate queues [BN][qcap].
 //
 // Candidate queue entries per query (qcap): 64 for 32-query tiles, 16 for wider ones.  The resident filter pass takes
 // 32 when the lists are short (k <= 32) and a block walks few rounds: the first rounds of a block offer 16-48
@@ -84,14 +84,19 @@ __device__ __forceinline__ void merge_queue2(u64* list, const u64* queue, int qc
 // keep 16 (10 M rows: 1 % faster with it).
 constexpr int RES_QCAP_MAX_ROUNDS = 64;
 
-template <class Cfg, bool RESIDENT = false, bool FACET = false>
+template <class Cfg, bool RESIDENT = false, bool FACET = false, bool SETS = false>
 struct TopK {
+    static_assert(FACET || !SETS, "the SETS arm applies the facet test too");
+    // SETS: one word per (query, 32 rows) of a tile, SET_NSW of them staged by every thread
+    static constexpr int SET_TILE_WORDS = Cfg::BM / 32 * Cfg::BN, SET_NSW = SET_TILE_WORDS / Cfg::THREADS;
+    static_assert(SET_TILE_WORDS % Cfg::THREADS == 0 && Cfg::THREADS % Cfg::BN == 0, "whole words per thread, all of one query");
     static __host__ __device__ constexpr int qcap(int k, int rounds) {
         return RESIDENT && k <= 32 && rounds <= RES_QCAP_MAX_ROUNDS ? 32 : Cfg::BN <= 32 ? 64 : 16;
     }
     // LDS of the selection, sized for a block of one round (the largest queue)
     static __host__ __device__ size_t bytes(int k) {
         return (size_t)Cfg::BN * (8 /*thr*/ + 4 /*cnt*/) + 16 /*flags*/ + (FACET ? Cfg::BN * FACET_LDS_WORDS * 4 + 2 * Cfg::BM * 2 : 0) +
+               (SETS ? Cfg::BN * 16 + 2 * SET_TILE_WORDS * 4 : 0) +
                (size_t)Cfg::BN * k * 8 + (size_t)Cfg::BN * qcap(k, 1) * 8;
     }
 
@@ -104,6 +109,10 @@ struct TopK {
     uint16_t* ftile;        // FACET: [2][BM] facet words of the tile being offered (half fcur) and of the one after it
     const uint16_t* frows;  // FACET: the index's facet words
     int fcur = 0;
+    int4* sslot;            // SETS: the queries' slots (set_slots)
+    uint32_t* stile;        // SETS: [2][BM / 32][BN] set words, halves as ftile's
+    const uint32_t* sbits;  // SETS: the index's bitmaps, swords words each
+    int64_t swords;
     int k, qcap_, round = 0;
     // this lane's queries: column (lane & 31) of each of its TN column tiles
     int myq[Cfg::TN];
@@ -113,20 +122,24 @@ struct TopK {
     // Carves the LDS at `lds`, empties the lists (one barrier) and reads this lane's exclusion segments.  `rounds`: the
     // tiles this block walks (the resident pass's queue capacity depends on it).  FACET: also loads the masks.
     __device__ __forceinline__ TopK(char* lds, int k_, int Q, int q0, const int32_t* excl_off, int rounds = 1,
-                                    const FacetArgs& fa = facet_args())
-        : frows(fa.rows), k(k_), qcap_(qcap(k_, rounds)) {
+                                    const FacetArgs& fa = facet_args(), const SetArgs& sa = set_args())
+        : frows(fa.rows), sbits(sa.bits), swords(sa.words), k(k_), qcap_(qcap(k_, rounds)) {
         const int tid = threadIdx.x, lane = tid & 63, wn = (tid >> 6) % Cfg::WAVES_N;
         thr = reinterpret_cast<u64*>(lds);
         cnt = reinterpret_cast<int*>(thr + Cfg::BN);
         flags = cnt + Cfg::BN;
         amask = reinterpret_cast<uint32_t*>(flags + 4);
         ftile = reinterpret_cast<uint16_t*>(amask + (FACET ? Cfg::BN * FACET_LDS_WORDS : 0));
-        list = reinterpret_cast<u64*>(ftile + (FACET ? 2 * Cfg::BM : 0));
+        sslot = reinterpret_cast<int4*>(ftile + (FACET ? 2 * Cfg::BM : 0));
+        stile = reinterpret_cast<uint32_t*>(sslot + (SETS ? Cfg::BN : 0));
+        list = reinterpret_cast<u64*>(stile + (SETS ? 2 * SET_TILE_WORDS : 0));
         queue = list + (size_t)Cfg::BN * k;
         for (int i = tid; i < Cfg::BN; i += Cfg::THREADS) { thr[i] = (q0 + i < Q) ? 0ull : ~0ull; cnt[i] = 0; }
         for (int i = tid; i < Cfg::BN * k; i += Cfg::THREADS) list[i] = 0ull;
         if (tid < 4) flags[tid] = 0;
         if (FACET) facet_load_masks(amask, fa, q0, Cfg::BN, Q, tid, Cfg::THREADS);
+        if (SETS)
+            for (int i = tid; i < Cfg::BN; i += Cfg::THREADS) sslot[i] = set_slots(sa, q0 + i, Q);
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < Cfg::TN; ++j) {
@@ -154,6 +167,8 @@ struct TopK {
     // Both read the tile's facet words from LDS: offer() of one tile fetches the next tile's words (the block walks
     // consecutive tiles) and stores them before its first barrier, so no candidate waits for a global load; the
     // kernel puts the first tile's there with stage_first_tile().
+    // SETS: the tile's set words travel the same way (the next tile's are fetched and ANDed by the threads that stage
+    // them); admitted() and the warm lane's test read one word and shift.
     __device__ __forceinline__ void offer(const f32x16 (&acc)[Cfg::TM][Cfg::TN], int64_t row0, int64_t N, uint32_t row_base,
                                           const int32_t* excl_idx, bool last_tile) {
         const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -168,14 +183,17 @@ struct TopK {
         const uint16_t* const fw_tile = ftile + fcur * Cfg::BM;
         unsigned next_words = 0u;  // two rows of the next tile per thread (inside the padded array: the tile exists)
         bool next_staged = !FACET || last_tile;
-        if (FACET && !last_tile && tid < Cfg::BM / 2)
+        if (FACET && !last_tile && tid < Cfg::BM / 2 && (!SETS || frows != nullptr))
             next_words = *reinterpret_cast<const unsigned*>(frows + row0 + Cfg::BM + 2 * tid);
+        uint32_t next_sw[SETS ? SET_NSW : 1];
+        if (SETS && !last_tile) load_set_words(next_sw, row0 + Cfg::BM);
+        const uint32_t* const sw_tile = stile + fcur * SET_TILE_WORDS;
         for (int pass = 0; pass < 2; ++pass) {
             if (FACET && pass == 0) {
                 bool cold = false;
 #pragma unroll
                 for (int j = 0; j < Cfg::TN; ++j) cold |= mythr[j] == 0ull;
-                if (cold) { adm = admitted(fw_tile, wm, lane); adm_known = true; }
+                if (cold) { adm = admitted(fw_tile, sw_tile, wm, lane); adm_known = true; }
             }
             // pend bit (j*TM+i)*16+e: score e of accumulator tile (i,j) has to be offered
             unsigned long long pend = 0ull;
@@ -238,6 +256,8 @@ struct TopK {
                                 take = key > mythr[j];
                             }
                             if (FACET && take && !adm_known) take = facet_admits(amask, myq[j], fw_tile[row - row0]);
+                            if (SETS && take && !adm_known)
+                                take = (sw_tile[(int)((row - row0) >> 5) * Cfg::BN + myq[j]] >> ((row - row0) & 31) & 1u) != 0u;
                             if (take && ex_hi[j] > ex_lo[j]) take = !excluded(excl_idx, ex_lo[j], ex_hi[j], (int)row);
                             bool settled = true;
                             if (take) {
@@ -251,6 +271,7 @@ struct TopK {
                 if (lane_pending) flags[round & 1] = 1;
                 if (!next_staged) {  // the other half was last read in the previous tile's offer(), which ended on a barrier
                     if (tid < Cfg::BM / 2) reinterpret_cast<unsigned*>(ftile + (fcur ^ 1) * Cfg::BM)[tid] = next_words;
+                    if (SETS) store_set_words(next_sw, fcur ^ 1);
                     next_staged = true;
                 }
                 __syncthreads();
@@ -301,17 +322,38 @@ struct TopK {
     }
 
     // FACET: the facet words of the block's first tile -> LDS (one barrier); the block has at least that tile.
+    // SETS: and its set words (the slots were published by the constructor's barrier); without facets the words are 0.
     __device__ __forceinline__ void stage_first_tile(int64_t row0) {
         if (threadIdx.x < Cfg::BM / 2)
-            reinterpret_cast<unsigned*>(ftile)[threadIdx.x] = *reinterpret_cast<const unsigned*>(frows + row0 + 2 * threadIdx.x);
+            reinterpret_cast<unsigned*>(ftile)[threadIdx.x] =
+                SETS && frows == nullptr ? 0u : *reinterpret_cast<const unsigned*>(frows + row0 + 2 * threadIdx.x);
+        if (SETS) {
+            uint32_t sw[SETS ? SET_NSW : 1];
+            load_set_words(sw, row0);
+            store_set_words(sw, 0);
+        }
         __syncthreads();
+    }
+
+    // SETS: this thread's SET_NSW words of the tile at row0 (inside the padded bitmaps: the tile exists) - word
+    // i = tid + THREADS * u is query i % BN, rows row0 + 32 (i / BN) .. + 31 - and their place in half `half` of stile.
+    __device__ __forceinline__ void load_set_words(uint32_t (&sw)[SETS ? SET_NSW : 1], int64_t row0) const {
+        const int4 slots = sslot[threadIdx.x % Cfg::BN];
+#pragma unroll
+        for (int u = 0; u < SET_NSW; ++u)
+            sw[u] = set_word(sbits, swords, slots, (row0 >> 5) + (threadIdx.x + Cfg::THREADS * u) / Cfg::BN);
+    }
+    __device__ __forceinline__ void store_set_words(const uint32_t (&sw)[SETS ? SET_NSW : 1], int half) {
+#pragma unroll
+        for (int u = 0; u < SET_NSW; ++u) stile[half * SET_TILE_WORDS + threadIdx.x + Cfg::THREADS * u] = sw[u];
     }
 
     // FACET: bit (j * TM + i) * 16 + e (pend's numbering) is set iff the mask of this lane's query j admits the row of
     // accumulator element e of row tile i.  Elements 4g .. 4g + 3 are four consecutive rows (acc_row) whose facet
     // words (fw_tile: the tile's, in LDS) are one aligned 8-byte read; rows past N hold the array's zero padding and
-    // are dropped by the row test.
-    __device__ __forceinline__ unsigned long long admitted(const uint16_t* fw_tile, int wm, int lane) const {
+    // are dropped by the row test.  SETS: and the query's set word of row tile i has the row's bit.
+    __device__ __forceinline__ unsigned long long admitted(const uint16_t* fw_tile, const uint32_t* sw_tile, int wm,
+                                                           int lane) const {
         unsigned long long bits = 0ull;
 #pragma unroll
         for (int i = 0; i < Cfg::TM; ++i)
@@ -323,7 +365,9 @@ struct TopK {
                     const unsigned fw = ((t & 2 ? w.y : w.x) >> (16 * (t & 1))) & 0xFFFFu;
 #pragma unroll
                     for (int j = 0; j < Cfg::TN; ++j)
-                        if (facet_admits(amask, myq[j], fw)) bits |= 1ull << ((j * Cfg::TM + i) * 16 + 4 * g + t);
+                        if (facet_admits(amask, myq[j], fw) &&
+                            (!SETS || (sw_tile[(wm * Cfg::TM + i) * Cfg::BN + myq[j]] >> acc_row(4 * g + t, lane) & 1u) != 0u))
+                            bits |= 1ull << ((j * Cfg::TM + i) * 16 + 4 * g + t);
                 }
             }
         return bits;
@@ -346,7 +390,7 @@ struct TopK {
 // The exact pass: rows in fp32, or (P16) stored as bfloat16 (ICREC_ROWS_BF16) and widened on their way into LDS.
 // EMIT = true additionally stores every score to scores_out[q*N + row] (parity checks only).
 // run_flag != NULL: the whole grid exits unless *run_flag != 0 (the exact pass behind a filter pass).
-// Facet = FacetArgs: the FACET arm (no EMIT form).
+// Facet = FacetArgs: the FACET arm; Facet = SetArgs: the SETS arm (no EMIT forms).
 template <class Cfg, bool EMIT, bool P16, class... Facet>
 __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
     const void* __restrict__ P, int64_t N, int K, const float* __restrict__ Qn, int Qpad, int Q, int k,
@@ -360,8 +404,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void search_kernel(
     const int lane = threadIdx.x & 63, wm = (threadIdx.x >> 6) / Cfg::WAVES_N;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
-    TopK<Cfg, false, sizeof...(Facet) != 0> sel(smem_raw + (size_t)Cfg::LDS_FLOATS * 4, k, Q, q0, excl_off, 1,
-                                                facet_args(facet...));
+    TopK<Cfg, false, sizeof...(Facet) != 0, has_sets<Facet...>> sel(smem_raw + (size_t)Cfg::LDS_FLOATS * 4, k, Q, q0, excl_off, 1,
+                                                                    facet_args(facet...), set_args(facet...));
     const int t_begin = chunk * tiles_per_chunk;
     const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
     if (sizeof...(Facet) != 0 && t_begin < t_end) sel.stage_first_tile((int64_t)t_begin * Cfg::BM);
@@ -398,7 +442,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void staged_search_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
-    TopK<Cfg, false, sizeof...(Facet) != 0> sel(smem_raw + SmemH<Cfg>::BYTES, k, Q, q0, excl_off, 1, facet_args(facet...));
+    TopK<Cfg, false, sizeof...(Facet) != 0, has_sets<Facet...>> sel(smem_raw + SmemH<Cfg>::BYTES, k, Q, q0, excl_off, 1,
+                                                                    facet_args(facet...), set_args(facet...));
     const int t_begin = chunk * tiles_per_chunk;
     const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
     if (sizeof...(Facet) != 0 && t_begin < t_end) sel.stage_first_tile((int64_t)t_begin * Cfg::BM);
@@ -516,8 +561,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void resident_search_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int chunk = bid / n_qtiles, q0 = bid % n_qtiles * Cfg::BN;
-    TopK<Cfg, true, sizeof...(Facet) != 0> sel(smem_raw + RES_X_BYTES, k, Q, q0, excl_off, tiles_per_chunk,
-                                               facet_args(facet...));
+    TopK<Cfg, true, sizeof...(Facet) != 0, has_sets<Facet...>> sel(smem_raw + RES_X_BYTES, k, Q, q0, excl_off, tiles_per_chunk,
+                                                                   facet_args(facet...), set_args(facet...));
     const int t_begin = chunk * tiles_per_chunk;
     const int t_end = min(n_row_tiles, t_begin + tiles_per_chunk);
     if (sizeof...(Facet) != 0 && t_begin < t_end) sel.stage_first_tile((int64_t)t_begin * Cfg::BM);
@@ -568,9 +613,9 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void resident_search_kernel(
 // best into a 256-slot LDS queue that merge_queue folds into the sorted list.  (Tile geometry: stream.h.)
 template <int NQ>
 struct StreamSmem {
-    static __host__ __device__ size_t bytes(int k, bool facet = false) {
+    static __host__ __device__ size_t bytes(int k, bool facet = false, bool sets = false) {
         return (size_t)ST_ROWS * ST_LDB + 64 /*thr*/ + 64 /*cnt*/ + (size_t)((NQ * k + 1) & ~1) * 8 + (size_t)NQ * ST_ROWS * 8 +
-               (facet ? NQ * FACET_LDS_WORDS * 4 : 0) /*allow masks*/;
+               (facet ? NQ * FACET_LDS_WORDS * 4 : 0) /*allow masks*/ + (sets ? NQ * (ST_ROWS / 32) * 4 : 0) /*set words of a tile*/;
     }
 };
 
@@ -604,20 +649,24 @@ __device__ __forceinline__ void stream_load_slab(v4f (&pre)[8], const char* __re
     }
 }
 
-template <int NQ, bool P16, class... Facet>  // Facet = FacetArgs: the FACET arm
+template <int NQ, bool P16, class... Facet>  // Facet = FacetArgs: the FACET arm, SetArgs: the SETS arm
 __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
     const void* __restrict__ P, int64_t N, int K, const float* __restrict__ Qn /* [K][NQ], zero-padded columns */, int Q,
     int k, const int32_t* __restrict__ excl_idx, const int32_t* __restrict__ excl_off, uint32_t row_base, int n_row_tiles,
     int tiles_per_chunk, u64* __restrict__ partial, Facet... facet) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr bool FACET = sizeof...(Facet) != 0;
+    constexpr bool FACET = sizeof...(Facet) != 0, SETS = has_sets<Facet...>;
     const FacetArgs fa = facet_args(facet...);
+    const SetArgs sa = set_args(facet...);
     char* rows_s = smem_raw;
     u64* thr = reinterpret_cast<u64*>(smem_raw + ST_ROWS * ST_LDB);
     int* cnt = reinterpret_cast<int*>(thr + 8);
     u64* list = reinterpret_cast<u64*>(cnt + 16);
     u64* queue = list + (size_t)((NQ * k + 1) & ~1);  // 16-B aligned: the cold path reads it two keys at a time
     uint32_t* amask = reinterpret_cast<uint32_t*>(queue + NQ * ST_ROWS);  // FACET: [NQ][FACET_LDS_WORDS]
+    // SETS: [NQ][8], word (j, w) = the intersection of query j's sets over rows 32 w .. 32 w + 31 of the tile
+    uint32_t* swords = amask + NQ * FACET_LDS_WORDS;
+    constexpr int SW = ST_ROWS / 32;
 
     constexpr int EPW = P16 ? 2 : 1;             // elements per 32-bit word
     constexpr int SLAB_ELEMS = 32 * EPW;         // 128 B of one row
@@ -630,6 +679,8 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
     if (tid < NQ) { thr[tid] = tid < Q ? 0ull : ~0ull; cnt[tid] = 0; }
     for (int i = tid; i < NQ * k; i += ST_ROWS) list[i] = 0ull;
     if (FACET) facet_load_masks(amask, fa, 0, NQ, Q, tid, ST_ROWS);
+    int4 slots = make_int4(SET_NONE, SET_NONE, SET_NONE, SET_NONE);  // SETS: thread j * 8 + w stages word (j, w)
+    if (SETS && tid < NQ * SW) slots = set_slots(sa, tid / SW, Q);
 
     u64 mythr[NQ];
     int ex_lo[NQ], ex_hi[NQ];
@@ -647,7 +698,10 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
 
     for (int tile = t_begin; tile < t_end; ++tile) {
         // FACET: this thread's row's facet word, in flight under the FMAs (inside the padded array also past N)
-        const unsigned fw = FACET ? fa.rows[(int64_t)tile * ST_ROWS + tid] : 0u;
+        const unsigned fw = FACET && (!SETS || fa.rows != nullptr) ? fa.rows[(int64_t)tile * ST_ROWS + tid] : 0u;
+        // SETS: the tile's set words (inside the padded bitmaps); the previous tile's were last read before its
+        // selection's barriers, the slab loop's first barrier publishes these
+        if (SETS && tid < NQ * SW) swords[tid] = set_word(sa.bits, sa.words, slots, (int64_t)tile * SW + tid % SW);
         float acc[NQ];
 #pragma unroll
         for (int j = 0; j < NQ; ++j) acc[j] = 0.0f;
@@ -693,6 +747,7 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
             const u64 kx = make_key(acc[j] + 0.0f, row_base + (uint32_t)row);
             bool take = row < N && mythr[j] != ~0ull && kx > mythr[j];
             if (FACET && take) take = facet_admits(amask, j, fw);
+            if (SETS && take) take = (swords[j * SW + (tid >> 5)] >> (tid & 31) & 1u) != 0u;
             if (take && ex_hi[j] > ex_lo[j]) take = !excluded(excl_idx, ex_lo[j], ex_hi[j], (int)row);
             key[j] = take ? kx : 0ull;
         }
@@ -959,20 +1014,23 @@ static void plan_chunks(int64_t n_rows, int BM, int want, int cap, int* n_row_ti
     *n_chunks = (*n_row_tiles + *tiles_per_chunk - 1) / *tiles_per_chunk;
 }
 
-// Dynamic LDS of the tiled kernels: operand staging, then the selection (TopK; `facet`: with the allow masks and the tiles' facet words).
-template <class Cfg> static size_t exact_smem(int k, bool facet) {
-    return (size_t)Cfg::LDS_FLOATS * 4 + (facet ? TopK<Cfg, false, true>::bytes(k) : TopK<Cfg>::bytes(k));
+// The arm of a search's selecting kernels: ARM_FACET with allow masks, ARM_SETS with set ids (and allow masks or not).
+enum Arm { ARM_PLAIN = 0, ARM_FACET = 1, ARM_SETS = 2 };
+// Dynamic LDS of the tiled kernels: operand staging, then the selection (TopK; ARM_FACET: with the allow masks and the
+// tiles' facet words, ARM_SETS: and the queries' slots and the tiles' set words).
+template <class Cfg, bool RESIDENT = false> static size_t topk_bytes(int k, Arm arm) {
+    return arm == ARM_SETS    ? TopK<Cfg, RESIDENT, true, true>::bytes(k)
+           : arm == ARM_FACET ? TopK<Cfg, RESIDENT, true>::bytes(k)
+                              : TopK<Cfg, RESIDENT>::bytes(k);
 }
-static size_t staged_smem(int k, bool facet) {
-    return SmemH<CfgFilter>::BYTES + (facet ? TopK<CfgFilter, false, true>::bytes(k) : TopK<CfgFilter>::bytes(k));
-}
-static size_t resident_smem(int k, bool facet) {
-    return RES_X_BYTES + (facet ? TopK<CfgRes, true, true>::bytes(k) : TopK<CfgRes, true>::bytes(k));
-}
+template <class Cfg> static size_t exact_smem(int k, Arm arm) { return (size_t)Cfg::LDS_FLOATS * 4 + topk_bytes<Cfg>(k, arm); }
+static size_t staged_smem(int k, Arm arm) { return SmemH<CfgFilter>::BYTES + topk_bytes<CfgFilter>(k, arm); }
+static size_t resident_smem(int k, Arm arm) { return RES_X_BYTES + topk_bytes<CfgRes, true>(k, arm); }
 constexpr size_t LDS_MAX = 160 * 1024;
 
-// `facet`: the plan of a faceted search - the same tiles and chunks (and hence the same workspace), more LDS.
-static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream, bool facet = false) {
+// `arm`: the plan of a faceted or set-restricted search - the same tiles and chunks (and hence the same workspace),
+// more LDS.
+static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream, Arm arm = ARM_PLAIN) {
     Plan p;
     // The streaming kernel pays a per-block cold start (rank 256 keys per query by counting) that only amortises
     // over several tiles: take it for Q <= 2 always, for Q <= 8 once every block has >= 2 tiles (measured at
@@ -987,9 +1045,9 @@ static Plan make_plan(const Index* ix, int Q, int k, bool allow_stream, bool fac
         // ~3 blocks per CU are resident (LDS)
         plan_chunks(ix->n_rows, p.BM, 3 * ix->n_cu, MERGE_MAX_LISTS, &p.n_row_tiles, &p.tiles_per_chunk, &p.n_chunks);
     } else {
-        if (Q > 64 && k <= 32) { p.variant = 0; p.BM = CfgBig::BM; p.BN = CfgBig::BN; p.smem = exact_smem<CfgBig>(k, facet); }
-        else if (Q > 32 && k <= 64) { p.variant = 1; p.BM = CfgMid::BM; p.BN = CfgMid::BN; p.smem = exact_smem<CfgMid>(k, facet); }
-        else { p.variant = 2; p.BM = CfgSmall::BM; p.BN = CfgSmall::BN; p.smem = exact_smem<CfgSmall>(k, facet); }
+        if (Q > 64 && k <= 32) { p.variant = 0; p.BM = CfgBig::BM; p.BN = CfgBig::BN; p.smem = exact_smem<CfgBig>(k, arm); }
+        else if (Q > 32 && k <= 64) { p.variant = 1; p.BM = CfgMid::BM; p.BN = CfgMid::BN; p.smem = exact_smem<CfgMid>(k, arm); }
+        else { p.variant = 2; p.BM = CfgSmall::BM; p.BN = CfgSmall::BN; p.smem = exact_smem<CfgSmall>(k, arm); }
         p.n_qtiles = (Q + p.BN - 1) / p.BN;
         p.Qpad = p.n_qtiles * p.BN;
         // one full wave of resident blocks (2 per CU fit by LDS/VGPR), at most 256 chunks
@@ -1009,22 +1067,22 @@ struct FilterPlan {
     size_t smem, off_qh, off_ql, off_flag, off_cand, off_partial, ws_total;
 };
 
-static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& exact, bool facet = false) {
+static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& exact, Arm arm = ARM_PLAIN) {
     FilterPlan f;
     f.kp = filter_list_len(k);
     f.resident = ix->frag != nullptr;
     f.use = (ix->plane_hi != nullptr || f.resident) && Q >= FILTER_MIN_Q && f.kp <= ICREC_MAX_K;
     // resident form: the query planes leave 64 KB of LDS for the lists (k <= 92); longer lists take the exact search,
     // which is the faster one there anyway (measured at 49,688 rows, Q = 1,024, k = 100: staged filter 2.5 ms, exact 1.5 ms)
-    // (with the allow masks of a faceted search: k <= 84)
-    if (f.resident && resident_smem(f.kp, facet) > LDS_MAX) f.use = false;
+    // (with the allow masks of a faceted search: k <= 84; with the set words of a set-restricted one: k <= 76)
+    if (f.resident && resident_smem(f.kp, arm) > LDS_MAX) f.use = false;
     if (!f.use) { f.ws_total = 0; return f; }
     f.n_qtiles = (Q + CfgFilter::BN - 1) / CfgFilter::BN;  // 64 queries per tile in both forms
     f.Qpad = f.n_qtiles * CfgFilter::BN;
     // staged form: two 4-wave blocks per CU; resident form: one 8-wave block per CU (its query planes take 96 KB)
     plan_chunks(ix->n_rows, f.resident ? CfgRes::BM : CfgFilter::BM, (f.resident ? 1 : 2) * ix->n_cu / f.n_qtiles, 256,
                 &f.n_row_tiles, &f.tiles_per_chunk, &f.n_chunks);
-    f.smem = f.resident ? resident_smem(f.kp, facet) : staged_smem(f.kp, facet);
+    f.smem = f.resident ? resident_smem(f.kp, arm) : staged_smem(f.kp, arm);
     const int qpad_max = f.Qpad > exact.Qpad ? f.Qpad : exact.Qpad;
     f.off_qh = align256((size_t)qpad_max * ix->dim * 4);
     f.off_ql = f.off_qh + align256((size_t)f.Qpad * ix->dim * 2);
@@ -1036,39 +1094,54 @@ static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& ex
     return f;
 }
 
-// One launch of a kernel family, timed in slot `timer`: the FACET arm `facet` (fa appended to the arguments) when the
-// search has allow masks, the kernel `plain` otherwise.  big_lds: the family's dynamic LDS can exceed the 64 KB default.
-template <class Plain, class FacetArm, class... Args>
-static int launch_arm(Plain plain, FacetArm facet, const FacetArgs& fa, bool big_lds, int timer, dim3 grid, dim3 block,
-                      size_t smem, hipStream_t st, Args... args) {
+// One launch of a kernel family, timed in slot `timer`: the SETS arm `sets` (sa appended to the arguments) when the
+// search has set ids, the FACET arm `facet` (sa.facet appended) when it has allow masks only, the kernel `plain`
+// otherwise.  big_lds: the family's dynamic LDS can exceed the 64 KB default.
+static inline Arm arm_of(const SetArgs& sa) { return sa.ids ? ARM_SETS : sa.facet.allow ? ARM_FACET : ARM_PLAIN; }
+template <class Plain, class FacetArm, class SetsArm, class... Args>
+static int launch_arm(Plain plain, FacetArm facet, SetsArm sets, const SetArgs& sa, bool big_lds, int timer, dim3 grid,
+                      dim3 block, size_t smem, hipStream_t st, Args... args) {
+    const Arm arm = arm_of(sa);
     if (big_lds)
-        if (int rc = ensure_dynamic_lds(fa.allow ? reinterpret_cast<const void*>(facet) : reinterpret_cast<const void*>(plain),
+        if (int rc = ensure_dynamic_lds(arm == ARM_SETS    ? reinterpret_cast<const void*>(sets)
+                                        : arm == ARM_FACET ? reinterpret_cast<const void*>(facet)
+                                                           : reinterpret_cast<const void*>(plain),
                                         160 * 1024))
             return rc;
     ScopedTimer tm(timer, st);
-    if (fa.allow) hipLaunchKernelGGL(facet, grid, block, smem, st, args..., fa);
+    if (arm == ARM_SETS) hipLaunchKernelGGL(sets, grid, block, smem, st, args..., sa);
+    else if (arm == ARM_FACET) hipLaunchKernelGGL(facet, grid, block, smem, st, args..., sa.facet);
     else hipLaunchKernelGGL(plain, grid, block, smem, st, args...);
     return ICREC_OK;
 }
 
 // The exact search's kernels for one tile shape or query count and one row format: the plain kernel, its EMIT form
-// (tiled kernels only) and its FACET arm.
+// (tiled kernels only), its FACET arm and its SETS arm.
 using SearchFn = decltype(&search_kernel<CfgBig, false, false>);
 using StreamFn = decltype(&stream_search_kernel<1, false>);
-struct TiledArms { SearchFn plain, scores; decltype(&search_kernel<CfgBig, false, false, FacetArgs>) facet; };
-struct StreamArms { StreamFn plain; decltype(&stream_search_kernel<1, false, FacetArgs>) facet; };
+struct TiledArms {
+    SearchFn plain, scores;
+    decltype(&search_kernel<CfgBig, false, false, FacetArgs>) facet;
+    decltype(&search_kernel<CfgBig, false, false, SetArgs>) sets;
+};
+struct StreamArms {
+    StreamFn plain;
+    decltype(&stream_search_kernel<1, false, FacetArgs>) facet;
+    decltype(&stream_search_kernel<1, false, SetArgs>) sets;
+};
 template <class Cfg, bool P16> static TiledArms tiled_arms() {
-    return {search_kernel<Cfg, false, P16>, search_kernel<Cfg, true, P16>, search_kernel<Cfg, false, P16, FacetArgs>};
+    return {search_kernel<Cfg, false, P16>, search_kernel<Cfg, true, P16>, search_kernel<Cfg, false, P16, FacetArgs>,
+            search_kernel<Cfg, false, P16, SetArgs>};
 }
 template <int NQ, bool P16> static StreamArms stream_arms() {
-    return {stream_search_kernel<NQ, P16>, stream_search_kernel<NQ, P16, FacetArgs>};
+    return {stream_search_kernel<NQ, P16>, stream_search_kernel<NQ, P16, FacetArgs>, stream_search_kernel<NQ, P16, SetArgs>};
 }
 
 // The exact search of plan p over the index rows (fp32 or bf16): partial lists, or every score into scores_out.  run_flag:
-// the guarded pass of the filter path, which has a timer slot of its own.  fa.allow != NULL: the FACET arms (never with
-// scores_out).  (Kernel tables: bf16 rows first.)
+// the guarded pass of the filter path, which has a timer slot of its own.  sa: the FACET or the SETS arms (arm_of; never
+// with scores_out).  (Kernel tables: bf16 rows first.)
 static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, int k, const int32_t* ei,
-                        const int32_t* eo, const FacetArgs& fa, u64* partial, float* scores_out, const int* run_flag,
+                        const int32_t* eo, const SetArgs& sa, u64* partial, float* scores_out, const int* run_flag,
                         hipStream_t st) {
     static const TiledArms tiled[2][3] = {{tiled_arms<CfgBig, true>(), tiled_arms<CfgMid, true>(), tiled_arms<CfgSmall, true>()},
                                           {tiled_arms<CfgBig, false>(), tiled_arms<CfgMid, false>(), tiled_arms<CfgSmall, false>()}};
@@ -1080,16 +1153,16 @@ static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, 
     int rc;
     if (p.variant == 3) {
         const int nq = p.BN == 1 ? 0 : p.BN == 2 ? 1 : p.BN == 4 ? 2 : 3;
-        const bool f = fa.allow != nullptr;
-        const size_t smem = nq == 0 ? StreamSmem<1>::bytes(k, f) : nq == 1 ? StreamSmem<2>::bytes(k, f)
-                            : nq == 2 ? StreamSmem<4>::bytes(k, f) : StreamSmem<8>::bytes(k, f);
-        rc = launch_arm(stream[nq][r].plain, stream[nq][r].facet, fa, false, T_SEARCH_KERNEL, dim3(p.n_chunks), dim3(ST_ROWS),
-                        smem, st, (const void*)ix->rows, ix->n_rows, ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset,
+        const bool f = arm_of(sa) != ARM_PLAIN, s = arm_of(sa) == ARM_SETS;
+        const size_t smem = nq == 0 ? StreamSmem<1>::bytes(k, f, s) : nq == 1 ? StreamSmem<2>::bytes(k, f, s)
+                            : nq == 2 ? StreamSmem<4>::bytes(k, f, s) : StreamSmem<8>::bytes(k, f, s);
+        rc = launch_arm(stream[nq][r].plain, stream[nq][r].facet, stream[nq][r].sets, sa, false, T_SEARCH_KERNEL,
+                        dim3(p.n_chunks), dim3(ST_ROWS), smem, st, (const void*)ix->rows, ix->n_rows, ix->dim, qn, Q, k, ei, eo, (uint32_t)ix->row_offset,
                         p.n_row_tiles, p.tiles_per_chunk, partial);
     } else {
         const TiledArms& t = tiled[r][p.variant];
-        rc = launch_arm(scores_out ? t.scores : t.plain, t.facet, fa, true, run_flag == nullptr ? T_SEARCH_KERNEL : T_SEARCH_FALLBACK,
-                        dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st, (const void*)ix->rows, ix->n_rows,
+        rc = launch_arm(scores_out ? t.scores : t.plain, t.facet, t.sets, sa, true,
+                        run_flag == nullptr ? T_SEARCH_KERNEL : T_SEARCH_FALLBACK, dim3(p.n_chunks * p.n_qtiles), dim3(CfgBig::THREADS), p.smem, st, (const void*)ix->rows, ix->n_rows,
                         ix->dim, qn, p.Qpad, Q, k, ei, eo, (uint32_t)ix->row_offset, p.n_row_tiles, p.tiles_per_chunk,
                         p.n_qtiles, partial, scores_out, run_flag);
     }
@@ -1100,10 +1173,10 @@ static int launch_exact(const Index* ix, const Plan& p, const float* qn, int Q, 
 static_assert(CfgBig::THREADS == CfgMid::THREADS && CfgMid::THREADS == CfgSmall::THREADS, "launch_exact: one block size");
 
 // Filter (f16x3 MFMA, approximate) -> merge -> verify (exact chains on the candidates) -> exact search that runs
-// only if some query could not be proven.  Same outputs, bit for bit, as the exact search.  fa.allow != NULL: the filter
-// pass and the guarded exact pass both run their FACET arm with the same masks.
+// only if some query could not be proven.  Same outputs, bit for bit, as the exact search.  The filter pass and the
+// guarded exact pass both run the arm of `sa` (arm_of) with the same masks and set ids.
 static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, const float* q, int Q, int k,
-                               const int32_t* ei, const int32_t* eo, const FacetArgs& fa, int64_t* out_idx,
+                               const int32_t* ei, const int32_t* eo, const SetArgs& sa, int64_t* out_idx,
                                float* out_score, u64* out_keys, void* ws, hipStream_t st) {
     char* base = reinterpret_cast<char*>(ws);
     float* qn = reinterpret_cast<float*>(base);
@@ -1120,14 +1193,16 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
     if (f.resident) {
         hipLaunchKernelGGL(split_queries_act_kernel, dim3((unsigned)((nq / 4 + 255) / 256 < 1024 ? (nq / 4 + 255) / 256 : 1024)),
                            dim3(256), 0, st, (const float*)qn, nq / 4, qh, ql, flag);
-        rc = launch_arm(resident_search_kernel<CfgRes>, resident_search_kernel<CfgRes, FacetArgs>, fa, true, T_SEARCH_KERNEL,
+        rc = launch_arm(resident_search_kernel<CfgRes>, resident_search_kernel<CfgRes, FacetArgs>,
+                        resident_search_kernel<CfgRes, SetArgs>, sa, true, T_SEARCH_KERNEL,
                         dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st, (const _Float16*)ix->frag, ix->n_rows,
                         (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
                         f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     } else {
         hipLaunchKernelGGL(split_planes_kernel<false>, dim3((unsigned)((nq + 255) / 256 < 1024 ? (nq + 255) / 256 : 1024)),
                            dim3(256), 0, st, (const void*)qn, nq, qh, ql, flag);
-        rc = launch_arm(staged_search_kernel<CfgFilter>, staged_search_kernel<CfgFilter, FacetArgs>, fa, true, T_SEARCH_KERNEL,
+        rc = launch_arm(staged_search_kernel<CfgFilter>, staged_search_kernel<CfgFilter, FacetArgs>,
+                        staged_search_kernel<CfgFilter, SetArgs>, sa, true, T_SEARCH_KERNEL,
                         dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st, (const _Float16*)ix->plane_hi,
                         (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q,
                         f.kp, ei, eo, (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
@@ -1140,26 +1215,33 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
                        filter_eps(ix->dim), out_idx, out_score, out_keys, flag);
     ICREC_HIP(hipGetLastError());
     // exact pass: every workgroup returns at once unless verify raised the flag
-    if (int rc2 = launch_exact(ix, ex, qn, Q, k, ei, eo, fa, partial, nullptr, flag, st)) return rc2;
+    if (int rc2 = launch_exact(ix, ex, qn, Q, k, ei, eo, sa, partial, nullptr, flag, st)) return rc2;
     launch_merge(partial, ex.n_chunks, ex.Qpad, Q, k, out_idx, out_score, out_keys, flag, st);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
 }
 
 // allow != NULL (icrec_search_faceted): every selecting kernel runs its FACET arm on the index's facets.
+// set_ids != NULL (icrec_search_in_sets): every selecting kernel runs its SETS arm on the index's row sets, with the
+// allow masks if there are any.
 static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei, const int32_t* eo, int64_t* out_idx,
                       float* out_score, u64* out_keys, float* scores_out, void* ws, size_t ws_bytes, hipStream_t st,
-                      const uint32_t* allow = nullptr) {
+                      const uint32_t* allow = nullptr, const int32_t* set_ids = nullptr, int sets_per_query = 0) {
     ICREC_REQUIRE(ix && q, "icrec_search: NULL index or queries");
     ICREC_REQUIRE(Q >= 1, "icrec_search: n_queries must be >= 1 (got %d)", Q);
     ICREC_REQUIRE(k >= 1 && k <= ICREC_MAX_K, "icrec_search: k must be in [1, %d] (got %d)", ICREC_MAX_K, k);
     ICREC_REQUIRE((ei == nullptr) == (eo == nullptr), "icrec_search: excl_idx and excl_off must both be set or both NULL");
     ICREC_REQUIRE(allow == nullptr || ix->facets != nullptr, "icrec_search_faceted: allow masks on an index without facets");
-    const bool facet = allow != nullptr;
-    const FacetArgs fa{ix->facets, allow, ix->n_facets};
+    ICREC_REQUIRE(set_ids == nullptr || ix->rowsets != nullptr, "icrec_search_in_sets: set ids on an index without row sets");
+    ICREC_REQUIRE(set_ids == nullptr || (sets_per_query >= 1 && sets_per_query <= ICREC_MAX_SETS_PER_QUERY),
+                  "icrec_search_in_sets: sets_per_query must be in [1, %d] (got %d)", ICREC_MAX_SETS_PER_QUERY, sets_per_query);
+    // (the SETS arm without allow masks: no facet words are read and the masks it loads are all ones)
+    const FacetArgs fa = allow ? FacetArgs{ix->facets, allow, ix->n_facets} : FacetArgs{nullptr, nullptr, 0};
+    const SetArgs sa{fa, ix->rowsets, set_ids, ix->n_rowsets, sets_per_query, rowset_words(ix->n_rows)};
+    const Arm arm = arm_of(sa);
     if (scores_out == nullptr && (ix->plane_hi != nullptr || ix->frag != nullptr)) {
-        const Plan ex = make_plan(ix, Q, k, false, facet);
-        const FilterPlan f = make_filter_plan(ix, Q, k, ex, facet);
+        const Plan ex = make_plan(ix, Q, k, false, arm);
+        const FilterPlan f = make_filter_plan(ix, Q, k, ex, arm);
         if (f.use) {
             if (ws_bytes < f.ws_total || ws == nullptr) {
                 set_error("icrec_search: workspace too small (%zu < %zu)", ws_bytes, f.ws_total);
@@ -1167,10 +1249,10 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
             }
             ICREC_HIP(hipSetDevice(ix->device));
             ScopedTimer whole(T_SEARCH, st);
-            return run_search_filtered(ix, f, ex, q, Q, k, ei, eo, fa, out_idx, out_score, out_keys, ws, st);
+            return run_search_filtered(ix, f, ex, q, Q, k, ei, eo, sa, out_idx, out_score, out_keys, ws, st);
         }
     }
-    const Plan p = make_plan(ix, Q, k, scores_out == nullptr, facet);
+    const Plan p = make_plan(ix, Q, k, scores_out == nullptr, arm);
     if (ws_bytes < p.ws_total || ws == nullptr) {
         set_error("icrec_search: workspace too small (%zu < %zu)", ws_bytes, p.ws_total);
         return ICREC_ENOMEM;
@@ -1181,7 +1263,7 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
     u64* partial = reinterpret_cast<u64*>(reinterpret_cast<char*>(ws) + p.ws_q);
     hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3((p.Qpad + 3) / 4), dim3(256), 0, st, q, (void*)qn, (int64_t)Q,
                        (int64_t)p.Qpad, ix->dim, 1e-12f, p.variant == 3 ? p.Qpad : 0);
-    if (int rc = launch_exact(ix, p, qn, Q, k, ei, eo, fa, partial, scores_out, nullptr, st)) return rc;
+    if (int rc = launch_exact(ix, p, qn, Q, k, ei, eo, sa, partial, scores_out, nullptr, st)) return rc;
     if (out_idx || out_keys) {
         if (!launch_merge_block(partial, p.n_chunks, p.Qpad, Q, k, out_idx, out_score, out_keys, st))
             launch_merge(partial, p.n_chunks, p.Qpad, Q, k, out_idx, out_score, out_keys, nullptr, st);
@@ -1223,6 +1305,20 @@ int icrec_search_faceted(icrec_index* h, const float* q_dev, int32_t n_queries, 
     ICREC_REQUIRE(out_idx_dev && out_score_dev, "icrec_search_faceted: NULL output");
     return run_search(reinterpret_cast<Index*>(h), q_dev, n_queries, k, excl_idx_dev, excl_off_dev, out_idx_dev,
                       out_score_dev, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream, allow_dev);
+}
+
+size_t icrec_search_in_sets_workspace_bytes(const icrec_index* h, int32_t n_queries, int32_t k) {
+    return icrec_search_workspace_bytes(h, n_queries, k);  // the plans of a set-restricted search cut the rows the same way
+}
+
+int icrec_search_in_sets(icrec_index* h, const float* q_dev, int32_t n_queries, int32_t k, const int32_t* excl_idx_dev,
+                         const int32_t* excl_off_dev, const uint32_t* allow_dev, const int32_t* set_ids_dev,
+                         int32_t sets_per_query, int64_t* out_idx_dev, float* out_score_dev, void* ws, size_t ws_bytes,
+                         void* stream) {
+    ICREC_REQUIRE(out_idx_dev && out_score_dev, "icrec_search_in_sets: NULL output");
+    return run_search(reinterpret_cast<Index*>(h), q_dev, n_queries, k, excl_idx_dev, excl_off_dev, out_idx_dev,
+                      out_score_dev, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream, allow_dev, set_ids_dev,
+                      sets_per_query);
 }
 
 int icrec_search_partial(icrec_index* h, const float* q_dev, int32_t n_queries, int32_t k, const int32_t* excl_idx_dev,

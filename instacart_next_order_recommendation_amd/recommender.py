@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .encoder import DeviceEncoder
 from .model_io import LoadedModel, load_model_dir
-from .search import DeviceIndex, IvfIndex, facet_masks, train_centroids
+from .search import DeviceIndex, IvfIndex, facet_masks, rowset_bits, rowset_ids, train_centroids
 
 logger = logging.getLogger(__name__)
 
@@ -197,17 +197,84 @@ def boost_plan(boosts, boost_weight, only_boosted: bool, n_queries: int, pid_to_
     return lists, bool(only_boosted)
 
 
-def ann_plan(probes, n_lists, *, aisles=None, departments=None, boosts=None, only_boosted: bool = False):
+def load_product_sets(product_sets) -> dict:
+    """Recommender(product_sets=): a mapping set name -> iterable of product ids, or the path of a JSON file of that
+    shape -> {name: [product id, ...]} in the mapping's order (the order of the set ids on the index).  ValueError: not
+    a mapping, no set at all, more than ICREC_MAX_ROWSETS sets, a set whose members are a string."""
+    if isinstance(product_sets, (str, Path)):
+        product_sets = json.loads(Path(product_sets).read_text())
+    if not hasattr(product_sets, "items"):
+        raise ValueError("product_sets must be a mapping set name -> product ids, or a JSON file of that shape")
+    if not 1 <= len(product_sets) <= _native.ICREC_MAX_ROWSETS:
+        raise ValueError(f"product_sets must hold 1 .. {_native.ICREC_MAX_ROWSETS} sets, got {len(product_sets)}")
+    out = {}
+    for name, ids in product_sets.items():
+        if isinstance(ids, (str, bytes)) or hasattr(ids, "items"):
+            raise ValueError(f"the members of product set {name!r} must be a list of product ids")
+        out[str(name)] = [str(p) for p in ids]
+    return out
+
+
+def within_ids(within, names) -> Optional[list[int]]:
+    """One request's `within` argument, checked before any GPU work -> None (unconstrained) or the ids of the named
+    product sets: a set name, or up to ICREC_MAX_SETS_PER_QUERY names (the request sees their intersection; no name
+    at all constrains nothing).  names: the recommender's set names in id order, None for a recommender without
+    sets.  ValueError: within on a recommender without sets, an unknown name, a fifth name."""
+    if within is None:
+        return None
+    if names is None:
+        raise ValueError("within needs a recommender built with product_sets")
+    asked = [within] if isinstance(within, str) else list(within)
+    if len(asked) > _native.ICREC_MAX_SETS_PER_QUERY:
+        raise ValueError(f"within names {len(asked)} product sets, more than {_native.ICREC_MAX_SETS_PER_QUERY}")
+    code = {name: i for i, name in enumerate(names)}
+    for name in asked:
+        if name not in code:
+            raise ValueError(f"unknown product set {name!r}")
+    return [code[name] for name in asked]
+
+
+def within_plan(within, n_queries: int, names):
+    """A batch's `within` argument (None, or one entry per query, each as within_ids takes it) -> None (no query is
+    constrained: the plain path) or the per-query id lists (None for an unconstrained query) rowset_ids takes."""
+    if within is None:
+        return None
+    if isinstance(within, (str, bytes)):
+        raise ValueError("within of a batch is a sequence with one entry per query")
+    within = list(within)
+    if len(within) != n_queries:
+        raise ValueError(f"within has {len(within)} entries for {n_queries} queries")
+    lists = [within_ids(w, names) for w in within]
+    return None if all(ids is None for ids in lists) else lists
+
+
+def boosts_within(lists, set_ids, member):
+    """The host side of `boosts` under `within`: each query's {row: weight} list (boost_plan's; None: no list) without
+    the rows outside one of the query's product sets.  icrec_boost_select does not look at row sets, so a listed row
+    it is given is a row it may return; with these rows dropped and the candidates searched inside the sets, its
+    result is the top k of the admissible rows under cosine + weight.  set_ids: within_plan's per-query id lists,
+    member: bool [n_sets, n_rows], the recommender's own copy of the membership."""
+    out = []
+    for pairs, ids in zip(lists, set_ids):
+        if pairs is None or not ids:
+            out.append(pairs)
+        else:
+            out.append({r: w for r, w in pairs.items() if all(member[s, r] for s in ids)})
+    return out
+
+
+def ann_plan(probes, n_lists, *, aisles=None, departments=None, boosts=None, only_boosted: bool = False, within=None):
     """A request's `probes` argument, checked before any GPU work -> None (the exact search: probes is None) or the
     number of lists the IVF search scans.  n_lists: the lists of the recommender's IvfIndex, None without one
-    (Recommender(ann_lists=None)).  ValueError: probes without an IVF index, probes together with aisles, departments
-    or boosts (the IVF scan reads neither facets nor boost lists), probes outside [1, min(n_lists, ICREC_MAX_K)]."""
+    (Recommender(ann_lists=None)).  ValueError: probes without an IVF index, probes together with aisles, departments,
+    boosts or within (the IVF scan reads neither facets nor boost lists nor row sets), probes outside
+    [1, min(n_lists, ICREC_MAX_K)]."""
     if probes is None:
         return None
     if n_lists is None:
         raise ValueError("probes needs a recommender built with ann_lists")
     for what, given in (("aisles", aisles is not None), ("departments", departments is not None),
-                        ("boosts", boosts is not None or bool(only_boosted))):
+                        ("boosts", boosts is not None or bool(only_boosted)), ("within", within is not None)):
         if given:
             raise ValueError(f"probes cannot be combined with {what}: the IVF search takes exclusions and diversity only")
     limit = min(int(n_lists), _native.ICREC_MAX_K)
@@ -268,9 +335,11 @@ class Recommender:
     """Two-tower recommender: same surface as the reference's Recommender (:133-225)."""
 
     _ann: Optional[IvfIndex] = None  # the IVF index beside _index (ann_lists), searched by requests that pass `probes`
+    product_sets: Optional[list[str]] = None  # the names of the product sets (product_sets=), in set id order
+    _set_member: Optional[np.ndarray] = None  # bool [n_sets, n_products]: the host's copy of the membership
 
     def __init__(self, model_dir: Path | str, corpus_path: Path, batch_size: int = 64, use_index: bool = True,
-                 ann_lists: int | None = None):
+                 ann_lists: int | None = None, product_sets=None):
         self.model_dir = self._resolve_model_dir(model_dir)
         self.corpus_path = Path(corpus_path).resolve()
         self.product_ids, self.product_texts = self._load_corpus()
@@ -284,6 +353,7 @@ class Recommender:
         self._index = DeviceIndex(self.product_embeddings, self.device,
                                   storage=os.getenv("ICREC_INDEX_STORAGE", "f32+filter"))
         self._set_facets()
+        self._set_product_sets(product_sets)
         # ann_lists: an IVF index of that many lists beside the exact one (a second copy of the rows); only requests
         # that pass `probes` search it
         self._ann = IvfIndex(self._index, train_centroids(self._index, int(ann_lists))) if ann_lists else None
@@ -344,6 +414,36 @@ class Recommender:
         if parsed:
             self._index.set_facets(parsed[2])
 
+    def _member_row(self, product_ids) -> np.ndarray:
+        """bool [n_products]: which catalog rows the given product ids name; ids the catalog does not have are skipped."""
+        row = np.zeros(len(self.product_ids), bool)
+        rows = [self._pid_to_row[p] for p in product_ids if p in self._pid_to_row]
+        row[rows] = True
+        return row
+
+    def _set_product_sets(self, product_sets) -> None:
+        """Named product sets (store assortments, "in stock", "vegan": a product may be in any number of them) onto
+        the index as row sets, in the mapping's order; the host keeps the membership (boosts_within reads it).  None:
+        the recommender has no sets and `within` raises."""
+        self.product_sets, self._set_member = None, None
+        if product_sets is None:
+            return
+        table = load_product_sets(product_sets)
+        self._set_member = np.stack([self._member_row(ids) for ids in table.values()])
+        self._index.set_rowsets(rowset_bits(self._set_member, len(self.product_ids)))
+        self.product_sets = list(table)
+
+    def update_product_set(self, name: str, product_ids) -> None:
+        """Replace the members of one product set (an in-stock set that changes through the day); ids the catalog does
+        not have are skipped.  The next request sees the new members.  A set-up call on the index: never while a
+        request is being served.  ValueError: a recommender without sets, an unknown name."""
+        ids = within_ids(name, self.product_sets)
+        if ids is None or isinstance(product_ids, (str, bytes)):
+            raise ValueError("update_product_set takes a set name and a list of product ids")
+        row = self._member_row(product_ids)
+        self._index.write_rowset(ids[0], rowset_bits(row[None, :], len(self.product_ids))[0])
+        self._set_member[ids[0]] = row
+
     # -- the hot path -------------------------------------------------------------------------
     def _k(self, top_k: int) -> int:
         """The search width for a request's top_k, checked before any GPU work: at least 1 (the reference's loop
@@ -391,7 +491,7 @@ class Recommender:
         return [None if a is None and d is None else (a, d) for a, d in zip(*per_facet)]
 
     def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None, mmr=None,
-                       boost=None, probes=None):
+                       boost=None, probes=None, sets=None):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
         current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  allow: per-query
         facet constraints (_facet_allow).  mmr: (lambda, candidates) of diversity_plan - the search is then
@@ -400,7 +500,13 @@ class Recommender:
         listed rows on the device (DeviceIndex.search_boosted; with only_boosted there is no search), at the width the
         MMR re-selection consumes when there is one, inside the search time.
         probes: ann_plan's count - the IVF index is searched instead of the exact one (never with allow or boost), at
-        the candidate width when mmr is given; the re-selection reads the exact index's rows."""
+        the candidate width when mmr is given; the re-selection reads the exact index's rows.
+        sets: within_plan's per-query set ids - every search is restricted to them (DeviceIndex.search(sets=)); the
+        listed rows of `boost` outside a query's sets are dropped here, on the host (boosts_within)."""
+        if sets is not None:
+            if boost is not None:
+                boost = (boosts_within(boost[0], sets, self._set_member), boost[1])
+            sets = rowset_ids(sets, len(cu) - 1, None, self.device)
         if allow is not None:
             allow = facet_masks(allow, len(cu) - 1, self._index.n_facets, self.device)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
@@ -415,13 +521,14 @@ class Recommender:
             if mmr is not None:
                 idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
         elif boost is not None:
-            idx, sc = self._index.search_boosted(emb, k if mmr is None else mmr[1], boost[0], ex, allow, only=boost[1])
+            idx, sc = self._index.search_boosted(emb, k if mmr is None else mmr[1], boost[0], ex, allow, only=boost[1],
+                                                 sets=sets)
             if mmr is not None:
                 idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
         elif mmr is None:
-            idx, sc = self._index.search(emb, k, ex, allow)
+            idx, sc = self._index.search(emb, k, ex, allow, sets)
         else:
-            idx, sc = self._index.search_diverse(emb, k, mmr[0], mmr[1], ex, allow)
+            idx, sc = self._index.search_diverse(emb, k, mmr[0], mmr[1], ex, allow, sets)
         if ev:
             ev[2].record(stream)
         idx, sc = idx.cpu().numpy(), sc.cpu().numpy()  # synchronises the stream
@@ -429,13 +536,15 @@ class Recommender:
 
     def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, aisles=None,
                        departments=None, diversity=None, candidates=None, boosts=None, boost_weight=None,
-                       only_boosted=False, probes=None):
+                       only_boosted=False, probes=None, within=None):
         """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path (always
-        when the request names aisles or departments, asks for diversity, boosts products, or probes the IVF index).
+        when the request names aisles, departments or product sets, asks for diversity, boosts products, or probes the
+        IVF index).
         -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
         probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
-                          boosts=boosts, only_boosted=only_boosted)
+                          boosts=boosts, only_boosted=only_boosted, within=within)
+        sets = within_plan(None if within is None else [within], 1, self.product_sets)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         allow = self._facet_allow(None if aisles is None else [aisles], None if departments is None else [departments], 1)
         boost = boost_plan([boosts], boost_weight, only_boosted, 1, self._pid_to_row)
@@ -444,11 +553,11 @@ class Recommender:
         tok_ms = (time.time() - t0) * 1000
         ex = self._exclusion_rows([exclude_product_ids])
         rows = ex[0] if ex else []
-        fast = self._fast_path() if allow is None and mmr is None and boost is None and probes is None else None
+        fast = self._fast_path() if allow is None and mmr is None and boost is None and probes is None and sets is None else None
         if fast is not None and fast.supports(len(ids), k, len(rows)):
             idx, sc, *ms = fast.run(ids, k, rows, timed=timed)
         else:
-            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr, boost, probes)
+            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr, boost, probes, sets)
             idx, sc = idx[0], sc[0]
         results = self._to_results(idx, sc)
         return (results, tok_ms + ms[0], ms[1]) if timed else results
@@ -461,14 +570,16 @@ class Recommender:
                         aisles: Optional[Sequence[Optional[Sequence[str]]]] = None,
                         departments: Optional[Sequence[Optional[Sequence[str]]]] = None,
                         diversity: float | None = None, candidates: int | None = None, boosts=None,
-                        boost_weight: float | None = None, only_boosted: bool = False, probes: int | None = None
-                        ) -> list[list[tuple[str, float]]]:
+                        boost_weight: float | None = None, only_boosted: bool = False, probes: int | None = None,
+                        within=None) -> list[list[tuple[str, float]]]:
         """Many contexts in one GPU pass; element i equals recommend(queries[i], ...).  aisles / departments: per
         query None or the admitted names, as recommend takes them.  diversity / candidates: one value for the whole
         batch, as recommend takes them.  boosts: None or one entry per query, each as recommend takes it; boost_weight
-        and only_boosted: one value for the whole batch.  probes: one value for the whole batch, as recommend takes it."""
+        and only_boosted: one value for the whole batch.  probes: one value for the whole batch, as recommend takes it.
+        within: None or one entry per query, each None or as recommend takes it."""
         probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
-                          boosts=boosts, only_boosted=only_boosted)
+                          boosts=boosts, only_boosted=only_boosted, within=within)
+        sets = within_plan(within, len(queries), self.product_sets)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
         if not queries:
@@ -477,7 +588,7 @@ class Recommender:
         ex = self._exclusion_rows(exclude_product_ids)
         allow = self._facet_allow(aisles, departments, len(queries))
         idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow, mmr=mmr, boost=boost,
-                                      probes=probes)
+                                      probes=probes, sets=sets)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))]
 
     def recommend_batches(self, batches, top_k: int = 10, exclude_product_ids=None):
@@ -496,11 +607,12 @@ class Recommender:
 
     def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None, *, aisles=None,
                               departments=None, diversity: float | None = None, candidates: int | None = None,
-                              boosts=None, boost_weight: float | None = None, only_boosted: bool = False):
+                              boosts=None, boost_weight: float | None = None, only_boosted: bool = False, within=None):
         """recommend_batch plus (embedding ms incl. host tokenisation, similarity ms) from HIP events
         on the launch stream — what the micro-batching server reports as per-request stats.  A diversified batch's
         re-selection and a boosted batch's merge count into the similarity time."""
         k = self._k(top_k)
+        sets = within_plan(within, len(queries), self.product_sets)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
         ex = self._exclusion_rows(exclude_product_ids)
@@ -508,14 +620,14 @@ class Recommender:
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed(list(queries))
         tok_ms = (time.time() - t0) * 1000
-        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow, mmr=mmr, boost=boost)
+        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow, mmr=mmr, boost=boost, sets=sets)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))], tok_ms + enc_ms, sim_ms
 
     def recommend(self, query: str, top_k: int = 10,
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
-                  only_boosted: bool = False, probes: int | None = None) -> list[tuple[str, float]]:
+                  only_boosted: bool = False, probes: int | None = None, within=None) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
         One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0".
         aisles / departments (keyword-only; names from .aisles / .departments): only products of one of these aisles
@@ -544,10 +656,17 @@ class Recommender:
         centroids match the query best (IvfIndex.search): the exact top_k of those lists, approximate only in which
         products it looks at; probes = ann_lists is the exact search's result.  It composes with exclude_product_ids
         and with diversity (the IVF search is then `candidates` wide) and takes the un-captured path; together with
-        aisles, departments or boosts, or without ann_lists, it raises ValueError.  probes None is the plain request."""
+        aisles, departments or boosts, or without ann_lists, it raises ValueError.  probes None is the plain request.
+        within (keyword-only; a recommender built with product_sets): a product set's name, or up to four names: only
+        products that are in EVERY named set ("sold at this store" and "in stock") - the result of excluding every
+        other product (DeviceIndex.search(sets=)).  It composes with exclude_product_ids, aisles, departments and
+        diversity through the search, and with boosts / only_boosted: boosted products outside the sets are dropped, and
+        the result is the top_k of the products inside them under cosine + weight.  Such a request takes the
+        un-captured path.  An unknown name, a fifth name, within on a recommender without product sets or together
+        with probes raise ValueError before any GPU work."""
         return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments,
                                    diversity=diversity, candidates=candidates, boosts=boosts, boost_weight=boost_weight,
-                                   only_boosted=only_boosted, probes=probes)
+                                   only_boosted=only_boosted, probes=probes, within=within)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -571,7 +690,7 @@ class MonitoredRecommender(Recommender):
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
-                  only_boosted: bool = False, probes: int | None = None) -> list[tuple[str, float]]:
+                  only_boosted: bool = False, probes: int | None = None, within=None) -> list[tuple[str, float]]:
         """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
         replays (fastpath.py): the three timing fields keep their meaning there.  A diversified request's
         re-selection and a boosted request's merge count into the similarity time."""
@@ -579,7 +698,7 @@ class MonitoredRecommender(Recommender):
         results, encode_ms, sim_ms = self._recommend_one(query, top_k, exclude_product_ids, timed=True, aisles=aisles,
                                                          departments=departments, diversity=diversity,
                                                          candidates=candidates, boosts=boosts, boost_weight=boost_weight,
-                                                         only_boosted=only_boosted, probes=probes)
+                                                         only_boosted=only_boosted, probes=probes, within=within)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

@@ -79,6 +79,56 @@ def facet_masks(allow, n_queries: int, n_facets: int, device=None):
     return torch.from_numpy(m.view(np.int32)).to(device).view(torch.uint32)
 
 
+def rowset_bits(members, n_rows: int) -> np.ndarray:
+    """Row sets -> the bitmaps icrec_index_set_rowsets takes, uint32 [S, ceil(n_rows / 32)]: bit r & 31 of word r >> 5 of
+    set s says that row r is in s.  `members` is a sequence of S iterables of rows 0..n_rows-1, or a bool array
+    [S, n_rows]."""
+    n_rows = int(n_rows)
+    if n_rows < 1:
+        raise ValueError(f"n_rows must be >= 1, got {n_rows}")
+    W = (n_rows + 31) // 32
+    if isinstance(members, np.ndarray) and members.dtype == np.bool_:
+        if members.ndim != 2 or members.shape[1] != n_rows:
+            raise ValueError(f"a bool membership array must be [S, {n_rows}], got {members.shape}")
+        padded = np.zeros((members.shape[0], W * 32), np.uint8)
+        padded[:, :n_rows] = members
+        return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u4").astype(np.uint32)
+    bits = np.zeros((len(members), W), np.uint32)
+    for s, rows in enumerate(members):
+        r = np.unique(np.fromiter((int(v) for v in rows), np.int64))
+        if r.size and (r[0] < 0 or r[-1] >= n_rows):
+            raise ValueError(f"set {s} names row {int(r[0] if r[0] < 0 else r[-1])}, outside 0..{n_rows - 1}")
+        np.bitwise_or.at(bits[s], r >> 5, np.uint32(1) << (r & 31).astype(np.uint32))
+    return bits
+
+
+def rowset_ids(within, n_queries: int, sets_per_query: Optional[int] = None, device=None):
+    """Per-query set ids -> the slots icrec_search_in_sets takes, int32 [n_queries, m] filled with -1 (a free slot; a
+    torch tensor on `device`, a numpy array without one).  within[i] is None (query i is unconstrained), an int, or up
+    to ICREC_MAX_SETS_PER_QUERY ints; m = sets_per_query, or the longest entry (at least 1) without one."""
+    if len(within) != n_queries:
+        raise ValueError(f"within has {len(within)} entries for {n_queries} queries")
+    lists = []
+    for i, w in enumerate(within):
+        ids = [] if w is None else [int(w)] if isinstance(w, (int, np.integer)) else [int(v) for v in w]
+        if len(ids) > _native.ICREC_MAX_SETS_PER_QUERY:
+            raise ValueError(f"within[{i}] names {len(ids)} sets, more than ICREC_MAX_SETS_PER_QUERY = "
+                             f"{_native.ICREC_MAX_SETS_PER_QUERY}")
+        lists.append(ids)
+    longest = max((len(ids) for ids in lists), default=0)
+    m = max(longest, 1) if sets_per_query is None else int(sets_per_query)
+    if not 1 <= m <= _native.ICREC_MAX_SETS_PER_QUERY:
+        raise ValueError(f"sets_per_query must be in [1, {_native.ICREC_MAX_SETS_PER_QUERY}], got {m}")
+    if longest > m:
+        raise ValueError(f"an entry of within names {longest} sets for sets_per_query = {m}")
+    out = np.full((n_queries, m), -1, np.int32)
+    for i, ids in enumerate(lists):
+        out[i, :len(ids)] = ids
+    if device is None:
+        return out
+    return torch.from_numpy(out).to(device)
+
+
 def boost_csr(boosts, n_queries: int, device: Optional[torch.device] = None):
     """Per-query boost lists -> (off int32[Q+1], rows int32, w float32, max_len): the CSR icrec_boost_select takes, each
     query's rows ascending, on `device` (numpy arrays without one); max_len is the longest list.  boosts[i] is None (no
@@ -168,6 +218,37 @@ class DeviceIndex:
         """Facet values per row (0: none set)."""
         return int(_native.lib().icrec_index_facets(self._h))
 
+    def set_rowsets(self, bits) -> None:
+        """Give the index its row sets, uint32 [n_sets, ceil(n_rows / 32)] bitmaps over the local rows (rowset_bits
+        builds them; for a catalog: one per store assortment, "in stock", "vegan"), or take them away with None.  A
+        set-up call: never while a search on this index runs.  Only searches that pass `sets` look at them."""
+        L = _native.lib()
+        if bits is None:
+            _native.check(L.icrec_index_set_rowsets(self._h, None, 0), "icrec_index_set_rowsets")
+            return
+        b = self._rowset_words(bits, 2)
+        _native.check(L.icrec_index_set_rowsets(self._h, b.ctypes.data_as(C.c_void_p), int(b.shape[0])),
+                      "icrec_index_set_rowsets")
+
+    def write_rowset(self, set_id: int, bits) -> None:
+        """Replace one set's bitmap, uint32 [ceil(n_rows / 32)] (an in-stock set that changes through the day).  A
+        set-up call like set_rowsets; a captured graph replayed afterwards follows the new members."""
+        b = self._rowset_words(bits, 1)
+        _native.check(_native.lib().icrec_index_write_rowset(self._h, int(set_id), b.ctypes.data_as(C.c_void_p)),
+                      "icrec_index_write_rowset")
+
+    def _rowset_words(self, bits, ndim: int) -> np.ndarray:
+        b = np.asarray(bits)
+        W = (self.n_rows + 31) // 32
+        if b.dtype != np.uint32 or b.ndim != ndim or b.shape[-1] != W:
+            raise ValueError(f"row set bitmaps must be uint32 {'[n_sets, ' if ndim == 2 else '['}{W}], got {b.dtype} {b.shape}")
+        return np.ascontiguousarray(b)
+
+    @property
+    def n_rowsets(self) -> int:
+        """Row sets of the index (0: none set)."""
+        return int(_native.lib().icrec_index_rowsets(self._h))
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _native.lib().icrec_index_destroy(self._h)
@@ -205,30 +286,48 @@ class DeviceIndex:
             raise ValueError(f"allow must be a contiguous uint32 tensor [{Q}, {nf}, {_native.ICREC_FACET_MASK_WORDS}] "
                              f"on {self.device}, got {allow.dtype} {tuple(allow.shape)} on {allow.device}")
 
+    def _check_sets(self, sets: torch.Tensor, Q: int) -> None:
+        if sets.dtype != torch.int32 or sets.device != self.device or not sets.is_contiguous() or sets.dim() != 2 \
+                or sets.shape[0] != Q or not 1 <= sets.shape[1] <= _native.ICREC_MAX_SETS_PER_QUERY:
+            raise ValueError(f"sets must be a contiguous int32 tensor [{Q}, 1..{_native.ICREC_MAX_SETS_PER_QUERY}] on "
+                             f"{self.device}, got {sets.dtype} {tuple(sets.shape)} on {sets.device}")
+
     # ------------------------------------------------------------------ API
-    def search(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None):
+    def search(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None,
+               sets: Optional[torch.Tensor] = None):
         """Top-k rows per query: (idx int64[Q,k] with -1 pads, score float32[Q,k]).
         Order: score descending, lower row first on ties.  `exclude`: per-query local rows.  `allow`: the queries'
         facet masks, a device uint32 tensor [Q, n_facets, 8] (facet_masks builds it): only rows whose facet values
-        the masks admit are returned - the same bits as excluding every other row."""
+        the masks admit are returned - the same bits as excluding every other row.  `sets`: the queries' row set ids,
+        a device int32 tensor [Q, 1..4] (rowset_ids builds it): only rows in every named set are returned - again the
+        bits of excluding every other row; -1 is a free slot, an id the index does not have admits nothing."""
         q = self._queries(q)
         Q = int(q.shape[0])
         ei, eo = exclusion_csr(exclude, Q, self.device)
         idx = torch.empty((Q, k), dtype=torch.int64, device=self.device)
         sc = torch.empty((Q, k), dtype=torch.float32, device=self.device)
-        self.search_into(q, k, ei, eo, idx, sc, allow=allow)
+        self.search_into(q, k, ei, eo, idx, sc, allow=allow, sets=sets)
         return idx, sc
 
     def search_into(self, q: torch.Tensor, k: int, excl_idx: Optional[torch.Tensor], excl_off: Optional[torch.Tensor],
                     out_idx: torch.Tensor, out_score: torch.Tensor, ws: Optional[torch.Tensor] = None,
-                    allow: Optional[torch.Tensor] = None) -> None:
+                    allow: Optional[torch.Tensor] = None, sets: Optional[torch.Tensor] = None) -> None:
         """Allocation-free form of `search` on caller-owned device buffers (hipGraph-capturable once the
         workspace for this (Q, k) exists, or with `ws` of the caller's own): q float32 [Q, dim],
-        out_idx int64 [Q, k], out_score float32 [Q, k].  The kernels read `allow` when they run: a captured graph
-        follows what the mask buffer holds at replay."""
+        out_idx int64 [Q, k], out_score float32 [Q, k].  The kernels read `allow`, `sets` and the index's row sets
+        when they run: a captured graph follows what the buffers hold at replay."""
         Q = int(q.shape[0])
         if ws is None:
             ws = self._workspace(Q, k)
+        if sets is not None:
+            self._check_sets(sets, Q)
+            if allow is not None:
+                self._check_allow(allow, Q)
+            _native.check(_native.lib().icrec_search_in_sets(self._h, ptr(q), Q, k, ptr(excl_idx), ptr(excl_off), ptr(allow),
+                                                             ptr(sets), int(sets.shape[1]), ptr(out_idx), ptr(out_score),
+                                                             ptr(ws), ws.numel(), stream_ptr(self.device)),
+                          "icrec_search_in_sets")
+            return
         if allow is not None:
             self._check_allow(allow, Q)
             _native.check(_native.lib().icrec_search_faceted(self._h, ptr(q), Q, k, ptr(excl_idx), ptr(excl_off), ptr(allow),
@@ -268,11 +367,12 @@ class DeviceIndex:
         _native.mmr_select(self._h, idx, rel, top_k, lam, out_idx, out_rel, ws, self.device)
 
     def search_diverse(self, q, top_k: int, lam: float, candidates: int,
-                       exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None):
-        """`search(q, candidates, exclude, allow)` followed by `mmr_select(.., top_k, lam)` on its result, without a
-        host step in between: the top_k most relevant-yet-diverse of each query's `candidates` best rows, with their
+                       exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None,
+                       sets: Optional[torch.Tensor] = None):
+        """`search(q, candidates, exclude, allow, sets)` followed by `mmr_select(.., top_k, lam)` on its result, without
+        a host step in between: the top_k most relevant-yet-diverse of each query's `candidates` best rows, with their
         cosine scores, in selection order (not score-descending)."""
-        idx, sc = self.search(q, candidates, exclude, allow)
+        idx, sc = self.search(q, candidates, exclude, allow, sets)
         return self.mmr_select(idx, sc, top_k, lam)
 
     def boost_select(self, q, idx: Optional[torch.Tensor], sc: Optional[torch.Tensor], boosts, top_k: int,
@@ -323,12 +423,15 @@ class DeviceIndex:
                              top_k, out_idx, out_score, ws, self.device)
 
     def search_boosted(self, q, k: int, boosts, exclude: Optional[Sequence[Iterable[int]]] = None,
-                       allow: Optional[torch.Tensor] = None, only: bool = False):
-        """`search(q, k, exclude, allow)` followed by `boost_select(.., boosts, k, exclude, allow)` on its result,
+                       allow: Optional[torch.Tensor] = None, only: bool = False, sets: Optional[torch.Tensor] = None):
+        """`search(q, k, exclude, allow, sets)` followed by `boost_select(.., boosts, k, exclude, allow)` on its result,
         without a host step in between: the k best rows of the shard under cosine + weight.  only=True ranks each
-        query's listed rows alone ("buy it again": the history, best first) and runs no search."""
+        query's listed rows alone ("buy it again": the history, best first) and runs no search.  `sets` restricts the
+        search's candidates only: icrec_boost_select does not look at row sets, so the caller lists no row outside
+        the query's sets (the recommender drops them on the host); the result is then the top k of the admissible
+        rows under cosine + weight."""
         q = self._queries(q)
-        idx, sc = (None, None) if only else self.search(q, k, exclude, allow)
+        idx, sc = (None, None) if only else self.search(q, k, exclude, allow, sets)
         return self.boost_select(q, idx, sc, boosts, k, exclude, allow)
 
     def search_partial(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None) -> torch.Tensor:
