@@ -550,6 +550,66 @@ ICREC_API int icrec_boost_select(icrec_index* idx, const float* q_dev, int32_t n
                        int32_t top_k, int64_t* out_idx_dev, float* out_score_dev,
                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Caps per facet value on a search result ("at most two products of one aisle, at most five of one department"):
+ * walk each query's k candidates in their order and keep a candidate only while every capped facet still has room for
+ * its value, entirely on the device.  Unlike a facet mask, which admits or forbids a value, a cap counts; unlike
+ * icrec_mmr_select it neither looks at similarities nor changes the order of what it keeps.
+ *   cand_idx_dev    int64[n_queries, k]       a search's out_idx: global rows, -1 pads
+ *   cand_score_dev  float[n_queries, k]       its out_score
+ *   caps_dev        int32[n_queries][ICREC_MAX_FACETS]  caps_dev[q * ICREC_MAX_FACETS + f]; a cap <= 0 constrains nothing
+ *   n_prior_dev     int32[n_queries]          picks an earlier round left in the out rows, or NULL (none)
+ *   allow_dev       uint32[n_queries, n_facets, ICREC_FACET_MASK_WORDS]  the masks the candidates were searched with,
+ *                                             or NULL (all ones); only read to make allow_next_dev
+ *   top_k           in [1, ICREC_MAX_K]       picks wanted per query, the priors included; it may exceed k
+ *   out_idx_dev     int64[n_queries, top_k]   IN/OUT when n_prior_dev is given, otherwise OUT
+ *   out_score_dev   float[n_queries, top_k]   likewise
+ *   out_state_dev   int32[n_queries][2]       {picks, done}
+ *   allow_next_dev  uint32[n_queries, n_facets, ICREC_FACET_MASK_WORDS] or NULL; may equal allow_dev
+ * The definition, which the result follows bit for bit:
+ *   Validity.  Candidate j is valid iff cand >= 0 and cand - row_offset lies in [0, n_rows) of idx.  A negative entry
+ *     is a PAD; any other invalid entry is skipped.  An invalid candidate's facet word is never read.
+ *   Values.  v_f(r) is byte f of the index's facet word of local row r (icrec_index_set_facets), for
+ *     f < icrec_index_facets(idx).  A cap on a facet the index does not have is ignored.
+ *   Prior picks.  p0 = clamp(n_prior[q], 0, top_k), or 0 when n_prior_dev is NULL.  Entries [0, p0) of the query's out
+ *     rows are kept as they are, and each valid one of them adds 1 to count[f][v_f] for every facet.
+ *   Walk.  Candidates are taken in position order j = 0 .. k-1, until there are top_k picks.  A valid candidate whose
+ *     global row equals an earlier pick, prior or of this call, is skipped.  Otherwise it is KEPT iff
+ *     count[f][v_f] < cap[f] for every facet f with cap[f] > 0.  A kept candidate is appended - its index, and
+ *     cand_score with its bits unchanged - and its counts go up by one.
+ *   Result.  The picks first, then -1 / 0.0f pads.  state = {picks, done}; done = 1 iff picks == top_k or any of the k
+ *     candidate entries is a pad: a pad means that the search which made the list ran out of admissible rows.
+ *   Next masks (allow_next_dev given).  The query's allow_dev words, or all ones when allow_dev is NULL, with bit v of
+ *     facet f cleared for every capped facet f and every value v with count[f][v] >= cap[f].
+ * A query's result has the same bits alone and inside any batch, for every row storage and row_offset.
+ * Consequence: the capped top_k of the WHOLE catalog, in rounds.  Let O be the order in which icrec_search_in_sets
+ * (or icrec_boost_select over it) ranks the rows that a query's exclusions, masks and sets admit, and G the greedy
+ * capped walk of all of O: the definition above with O as the candidates.  Run a round - search k wide, then
+ * icrec_cap_select with the picks so far as priors - and, while done == 0, repeat with the masks allow_next, the
+ * exclusions united with the picks, and k >= top_k - picks.  The final picks are G's first top_k, because
+ *   - a round walks a prefix of what is left of O: the walk stops early only at top_k picks, and a list without a pad
+ *     that is walked to its end is the k best rows the search admits;
+ *   - a row the walk rejected has a value whose count reached its cap, and counts only grow: G rejects it as well, and
+ *     it can never be kept later;
+ *   - so the next search, which leaves out the picks and every row with a saturated value, lists exactly the unwalked
+ *     rows that can still be kept (every walked row is a pick or has a saturated value), in O's order, and walking
+ *     them with the counts so far continues G where the round before stopped;
+ *   - a round that is not done walked k >= 1 rows to the end and kept fewer than top_k - picks <= k of them, so it
+ *     rejected one: at least one more (facet, value) is saturated after it.  The rounds are at most the number of
+ *     (facet, value) pairs plus one.
+ * With boosts the adjusted scores order O; rows that icrec_boost_select lists but the next masks forbid are dropped by
+ * its own validity rule.  The sharded search and icrec_ivf_search are not covered by this argument.
+ * ICREC_EINVAL, before any HIP call, and nothing is launched: a NULL among idx, the candidates, caps_dev, the outputs or
+ * the state; n_queries < 1; k outside [1, ICREC_MAX_K]; top_k outside [1, ICREC_MAX_K]; an index without facets.
+ * Asynchronous on `stream`: one launch of one wave per query, no workspace, nothing is allocated, nothing
+ * synchronises, and the call can be captured into a hipGraph.  Caps, priors and masks are read from device memory when
+ * the kernel runs.  Apart from allow_next_dev == allow_dev the outputs must not alias the inputs. */
+ICREC_API int icrec_cap_select(icrec_index* idx,
+                     const int64_t* cand_idx_dev, const float* cand_score_dev, int32_t n_queries, int32_t k,
+                     const int32_t* caps_dev, const int32_t* n_prior_dev, const uint32_t* allow_dev,
+                     int32_t top_k,
+                     int64_t* out_idx_dev, float* out_score_dev, int32_t* out_state_dev,
+                     uint32_t* allow_next_dev, void* stream);
+
 /* IVF: an inverted-file index over an icrec_index (the base).  The rows are split into n_lists lists around centroids;
  * a query scans only the nprobe lists whose centroids it matches best.  Approximate in WHICH rows it looks at, exact
  * in everything else.  The definition, which every result follows bit for bit:
@@ -846,7 +906,8 @@ ICREC_API const char* icrec_version(void);
  *            when the fallback ran,
  *        5 = icrec_mmr_select's similarity-matrix kernel, 6 = its selection kernel,
  *        7 = icrec_boost_select's scoring kernel, 8 = its selection kernel,
- *        10 = icrec_ivf_search's list scan kernel (9 is a spare of the encoder's). */
+ *        10 = icrec_ivf_search's list scan kernel (9 is a spare of the encoder's),
+ *        11 = icrec_cap_select's kernel. */
 ICREC_API int icrec_timing_enable(int on);
 ICREC_API int icrec_timing_reset(void);
 ICREC_API int icrec_timing_query(int which, double* avg_ms, int64_t* n_launches);

@@ -46,7 +46,7 @@ EXPORTS = [
     "icrec_index_set_rowsets", "icrec_index_write_rowset", "icrec_index_rowsets",
     "icrec_search_in_sets_workspace_bytes", "icrec_search_in_sets",
     "icrec_mmr_select_workspace_bytes", "icrec_mmr_select",
-    "icrec_boost_select_workspace_bytes", "icrec_boost_select",
+    "icrec_boost_select_workspace_bytes", "icrec_boost_select", "icrec_cap_select",
     "icrec_ivf_create", "icrec_ivf_destroy", "icrec_ivf_lists", "icrec_ivf_layout",
     "icrec_ivf_search_workspace_bytes", "icrec_ivf_search",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
@@ -162,6 +162,7 @@ def lib() -> C.CDLL:
         "icrec_mmr_select": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, sz, vp]),
         "icrec_boost_select_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_boost_select": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+        "icrec_cap_select": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "icrec_ivf_create": (C.c_int, [vp, vp, i32, C.POINTER(vp)]),
         "icrec_ivf_destroy": (C.c_int, [vp]),
         "icrec_ivf_lists": (i32, [vp]),
@@ -275,6 +276,18 @@ def boost_select(index_handle, q, cand_idx, cand_score, boost_off, boost_rows, b
                                    ptr(boost_rows), ptr(boost_w), int(max_boosts), ptr(excl_idx), ptr(excl_off), ptr(allow),
                                    int(top_k), ptr(out_idx), ptr(out_score), ptr(ws), ws.numel(), stream_ptr(device)),
           "icrec_boost_select")
+
+
+def cap_select(index_handle, cand_idx, cand_score, caps, n_prior, allow, top_k: int, out_idx, out_score, out_state,
+               allow_next, device) -> None:
+    """icrec_cap_select on device tensors: cand_idx int64 [Q, k] and cand_score float32 [Q, k] in, caps int32
+    [Q, ICREC_MAX_FACETS], n_prior int32 [Q] or None, allow uint32 [Q, n_facets, 8] or None, out_idx int64 [Q, top_k] and
+    out_score float32 [Q, top_k] (in/out with n_prior), out_state int32 [Q, 2] out, allow_next like allow (or allow
+    itself) or None; asynchronous on `device`'s current stream."""
+    Q, k = int(cand_idx.shape[0]), int(cand_idx.shape[1])
+    check(lib().icrec_cap_select(index_handle, ptr(cand_idx), ptr(cand_score), Q, k, ptr(caps), ptr(n_prior), ptr(allow),
+                                 int(top_k), ptr(out_idx), ptr(out_score), ptr(out_state), ptr(allow_next),
+                                 stream_ptr(device)), "icrec_cap_select")
 
 
 def timing_enable(on: bool) -> None:

@@ -12,6 +12,7 @@ ignored; a missing model directory or corpus file is an error).
                                                       [--ann-lists N --probes P]
                                                       [--boost PID[=W]]... [--boost-weight W] [--only-boosted]
                                                       [--product-sets FILE --within NAME]...
+                                                      [--max-per-aisle N] [--max-per-department N]
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
 and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
@@ -161,6 +162,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="JSON file {set name: [product id, ...]}: named product sets (store assortments, in stock, ...)")
     ap.add_argument("--within", action="append", default=None, metavar="NAME",
                     help="only products of this --product-sets set (repeatable, up to 4: products in every named set)")
+    ap.add_argument("--max-per-aisle", type=int, default=None, metavar="N",
+                    help="at most N results of one aisle (the best N of it, in the ranking's order)")
+    ap.add_argument("--max-per-department", type=int, default=None, metavar="N",
+                    help="at most N results of one department")
     return ap
 
 
@@ -209,8 +214,9 @@ def main(argv=None) -> int:
     try:
         hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department,
                              diversity=args.diversity, candidates=args.candidates, boosts=boosts or None,
-                             only_boosted=args.only_boosted, probes=probes, within=args.within)
-    except ValueError as e:  # an aisle / department / product set the catalog does not have, a bad --diversity / --candidates / --boost / --probes
+                             only_boosted=args.only_boosted, probes=probes, within=args.within,
+                             max_per_aisle=args.max_per_aisle, max_per_department=args.max_per_department)
+    except ValueError as e:  # an aisle / department / product set the catalog does not have, a bad --diversity / --candidates / --boost / --probes / --max-per-*
         raise SystemExit(str(e))
     if args.json:
         for rank, (pid, score) in enumerate(hits, 1):

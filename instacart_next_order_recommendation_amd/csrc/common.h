@@ -1,7 +1,7 @@
 // common.h — host-side error plumbing, the declarations of sort.hip's key sorters and prefix-sum launcher, and the
 // device helpers shared by the gfx950 kernels: ranking keys (search.hip, sort.hip, cf.hip, boost.hip), the
-// (value, position) key (mmr.hip, rerank.hip), the shard row rule (mmr.hip, boost.hip, rerank.hip), the LDS bitonic
-// network, wave reductions, the workgroup scan (sort.hip, rerank.hip, comm.hip), the fp32 MFMA tile engine
+// (value, position) key (mmr.hip, rerank.hip), the shard row rule (mmr.hip, boost.hip, rerank.hip, cap.hip), the LDS
+// bitonic network, wave reductions, the workgroup scan (sort.hip, rerank.hip, comm.hip), the fp32 MFMA tile engine
 // (search.hip) and the gathered exact-cosine wave tile (mmr.hip, boost.hip).
 #pragma once
 
@@ -45,7 +45,7 @@ struct TimingSlot {
     int64_t n = 0;
 };
 enum { T_SEARCH_KERNEL = 0, T_FFN_UP = 1, T_ENCODE = 2, T_SEARCH = 3, T_SEARCH_FALLBACK = 4, T_MMR_GRAM = 5, T_MMR_SELECT = 6,
-       T_BOOST_SCORE = 7, T_BOOST_SELECT = 8, T_FFN_UP_SMALL = 9 /* a spare of encoder.hip's */, T_IVF_SCAN = 10, T_NSLOTS = 11 };
+       T_BOOST_SCORE = 7, T_BOOST_SELECT = 8, T_FFN_UP_SMALL = 9 /* a spare of encoder.hip's */, T_IVF_SCAN = 10, T_CAP_SELECT = 11, T_NSLOTS = 12 };
 bool timing_on();
 // Records [start, stop] around a launch when timing is enabled; resolved lazily at query time.
 struct ScopedTimer {

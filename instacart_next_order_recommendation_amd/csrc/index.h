@@ -1,6 +1,6 @@
 // index.h — what an icrec_index handle points to, shared by index.hip (which creates and destroys it), search.hip
 // (which builds its filter storage and searches it), sort.hip (icrec_rank_all), mmr.hip and boost.hip (which read its
-// stored rows), and the device code that index.hip, search.hip and boost.hip share: the row normalisation kernel, the
+// stored rows), cap.hip (which reads its facet words), and the device code that index.hip, search.hip and boost.hip share: the row normalisation kernel, the
 // exclusion search, the facet test and the row set words.  What needs no handle - the shard row rule, the gathered
 // exact-cosine tile that mmr.hip and boost.hip read the stored rows with - is in common.h.
 #pragma once

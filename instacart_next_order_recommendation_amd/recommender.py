@@ -263,18 +263,42 @@ def boosts_within(lists, set_ids, member):
     return out
 
 
-def ann_plan(probes, n_lists, *, aisles=None, departments=None, boosts=None, only_boosted: bool = False, within=None):
+def cap_plan(max_per_aisle, max_per_department, has_facets: bool):
+    """A request's `max_per_aisle` / `max_per_department` arguments, checked before any GPU work -> None (the plain
+    request: both are None) or the caps (aisle, department) DeviceIndex.search_capped takes, 0 for the one that is None.
+    Each is a positive integer; ValueError for anything else, and for caps on a catalog without facets."""
+    caps = []
+    for what, v in (("max_per_aisle", max_per_aisle), ("max_per_department", max_per_department)):
+        if v is None:
+            caps.append(0)
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 2**31 - 1:
+            raise ValueError(f"{what} must be an integer >= 1, got {v!r}")
+        caps.append(int(v))
+    if caps == [0, 0]:
+        return None
+    if not has_facets:
+        raise ValueError("max_per_aisle / max_per_department need a catalog with aisle / department facets (its texts "
+                         "are not in the 'Product: .. Aisle: .. Department: ..' format)")
+    return caps[0], caps[1]
+
+
+def ann_plan(probes, n_lists, *, aisles=None, departments=None, boosts=None, only_boosted: bool = False, within=None,
+             max_per_aisle=None, max_per_department=None):
     """A request's `probes` argument, checked before any GPU work -> None (the exact search: probes is None) or the
     number of lists the IVF search scans.  n_lists: the lists of the recommender's IvfIndex, None without one
     (Recommender(ann_lists=None)).  ValueError: probes without an IVF index, probes together with aisles, departments,
-    boosts or within (the IVF scan reads neither facets nor boost lists nor row sets), probes outside
+    boosts, within, max_per_aisle or max_per_department (the IVF scan reads neither facets nor boost lists nor row sets,
+    and the rounds of a capped request are exact searches), probes outside
     [1, min(n_lists, ICREC_MAX_K)]."""
     if probes is None:
         return None
     if n_lists is None:
         raise ValueError("probes needs a recommender built with ann_lists")
     for what, given in (("aisles", aisles is not None), ("departments", departments is not None),
-                        ("boosts", boosts is not None or bool(only_boosted)), ("within", within is not None)):
+                        ("boosts", boosts is not None or bool(only_boosted)), ("within", within is not None),
+                        ("max_per_aisle", max_per_aisle is not None),
+                        ("max_per_department", max_per_department is not None)):
         if given:
             raise ValueError(f"probes cannot be combined with {what}: the IVF search takes exclusions and diversity only")
     limit = min(int(n_lists), _native.ICREC_MAX_K)
@@ -337,6 +361,8 @@ class Recommender:
     _ann: Optional[IvfIndex] = None  # the IVF index beside _index (ann_lists), searched by requests that pass `probes`
     product_sets: Optional[list[str]] = None  # the names of the product sets (product_sets=), in set id order
     _set_member: Optional[np.ndarray] = None  # bool [n_sets, n_products]: the host's copy of the membership
+    aisles: Optional[list[str]] = None  # the catalog's aisle and department names (_set_facets); None: it has no facets
+    departments: Optional[list[str]] = None
 
     def __init__(self, model_dir: Path | str, corpus_path: Path, batch_size: int = 64, use_index: bool = True,
                  ann_lists: int | None = None, product_sets=None):
@@ -491,7 +517,7 @@ class Recommender:
         return [None if a is None and d is None else (a, d) for a, d in zip(*per_facet)]
 
     def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None, mmr=None,
-                       boost=None, probes=None, sets=None):
+                       boost=None, probes=None, sets=None, caps=None, width=None):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
         current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  allow: per-query
         facet constraints (_facet_allow).  mmr: (lambda, candidates) of diversity_plan - the search is then
@@ -502,7 +528,11 @@ class Recommender:
         probes: ann_plan's count - the IVF index is searched instead of the exact one (never with allow or boost), at
         the candidate width when mmr is given; the re-selection reads the exact index's rows.
         sets: within_plan's per-query set ids - every search is restricted to them (DeviceIndex.search(sets=)); the
-        listed rows of `boost` outside a query's sets are dropped here, on the host (boosts_within)."""
+        listed rows of `boost` outside a query's sets are dropped here, on the host (boosts_within).
+        caps: cap_plan's (aisle, department) caps (never with probes) - without mmr the k results are the capped walk
+        of the whole ranking, boosted when boost is given (DeviceIndex.search_capped, `width` candidates per round:
+        the request's `candidates`, or None for the default); with mmr the caps thin the candidate list in one round
+        (DeviceIndex.cap_select at the candidates' own width) and the re-selection picks from what is left."""
         if sets is not None:
             if boost is not None:
                 boost = (boosts_within(boost[0], sets, self._set_member), boost[1])
@@ -516,7 +546,17 @@ class Recommender:
         emb = self.model.encoder.encode_packed_host(ids, cu)
         if ev:
             ev[1].record(stream)
-        if probes is not None:
+        if caps is not None and mmr is None:
+            idx, sc = self._index.search_capped(emb, k, caps, width, ex, allow, sets, None if boost is None else boost[0],
+                                                only=bool(boost and boost[1]))
+        elif caps is not None:
+            if boost is None:
+                idx, sc = self._index.search(emb, mmr[1], ex, allow, sets)
+            else:
+                idx, sc = self._index.search_boosted(emb, mmr[1], boost[0], ex, allow, only=boost[1], sets=sets)
+            idx, sc = self._index.cap_select(idx, sc, caps, mmr[1])[:2]
+            idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
+        elif probes is not None:
             idx, sc = self._ann.search(emb, k if mmr is None else mmr[1], probes, ex)
             if mmr is not None:
                 idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
@@ -536,14 +576,16 @@ class Recommender:
 
     def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, aisles=None,
                        departments=None, diversity=None, candidates=None, boosts=None, boost_weight=None,
-                       only_boosted=False, probes=None, within=None):
+                       only_boosted=False, probes=None, within=None, max_per_aisle=None, max_per_department=None):
         """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path (always
-        when the request names aisles, departments or product sets, asks for diversity, boosts products, or probes the
-        IVF index).
+        when the request names aisles, departments or product sets, asks for diversity, boosts products, probes the
+        IVF index, or caps the products per aisle or department).
         -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
         probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
-                          boosts=boosts, only_boosted=only_boosted, within=within)
+                          boosts=boosts, only_boosted=only_boosted, within=within, max_per_aisle=max_per_aisle,
+                          max_per_department=max_per_department)
+        caps = cap_plan(max_per_aisle, max_per_department, self.aisles is not None)
         sets = within_plan(None if within is None else [within], 1, self.product_sets)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         allow = self._facet_allow(None if aisles is None else [aisles], None if departments is None else [departments], 1)
@@ -553,11 +595,12 @@ class Recommender:
         tok_ms = (time.time() - t0) * 1000
         ex = self._exclusion_rows([exclude_product_ids])
         rows = ex[0] if ex else []
-        fast = self._fast_path() if allow is None and mmr is None and boost is None and probes is None and sets is None else None
+        fast = self._fast_path() if allow is None and mmr is None and boost is None and probes is None and sets is None \
+            and caps is None else None
         if fast is not None and fast.supports(len(ids), k, len(rows)):
             idx, sc, *ms = fast.run(ids, k, rows, timed=timed)
         else:
-            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr, boost, probes, sets)
+            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr, boost, probes, sets, caps, candidates)
             idx, sc = idx[0], sc[0]
         results = self._to_results(idx, sc)
         return (results, tok_ms + ms[0], ms[1]) if timed else results
@@ -571,14 +614,18 @@ class Recommender:
                         departments: Optional[Sequence[Optional[Sequence[str]]]] = None,
                         diversity: float | None = None, candidates: int | None = None, boosts=None,
                         boost_weight: float | None = None, only_boosted: bool = False, probes: int | None = None,
-                        within=None) -> list[list[tuple[str, float]]]:
+                        within=None, max_per_aisle: int | None = None,
+                        max_per_department: int | None = None) -> list[list[tuple[str, float]]]:
         """Many contexts in one GPU pass; element i equals recommend(queries[i], ...).  aisles / departments: per
         query None or the admitted names, as recommend takes them.  diversity / candidates: one value for the whole
         batch, as recommend takes them.  boosts: None or one entry per query, each as recommend takes it; boost_weight
         and only_boosted: one value for the whole batch.  probes: one value for the whole batch, as recommend takes it.
-        within: None or one entry per query, each None or as recommend takes it."""
+        within: None or one entry per query, each None or as recommend takes it.  max_per_aisle / max_per_department: one
+        value for the whole batch, as recommend takes them."""
         probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
-                          boosts=boosts, only_boosted=only_boosted, within=within)
+                          boosts=boosts, only_boosted=only_boosted, within=within, max_per_aisle=max_per_aisle,
+                          max_per_department=max_per_department)
+        caps = cap_plan(max_per_aisle, max_per_department, self.aisles is not None)
         sets = within_plan(within, len(queries), self.product_sets)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
@@ -588,7 +635,7 @@ class Recommender:
         ex = self._exclusion_rows(exclude_product_ids)
         allow = self._facet_allow(aisles, departments, len(queries))
         idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow, mmr=mmr, boost=boost,
-                                      probes=probes, sets=sets)
+                                      probes=probes, sets=sets, caps=caps, width=candidates)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))]
 
     def recommend_batches(self, batches, top_k: int = 10, exclude_product_ids=None):
@@ -607,11 +654,13 @@ class Recommender:
 
     def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None, *, aisles=None,
                               departments=None, diversity: float | None = None, candidates: int | None = None,
-                              boosts=None, boost_weight: float | None = None, only_boosted: bool = False, within=None):
+                              boosts=None, boost_weight: float | None = None, only_boosted: bool = False, within=None,
+                              max_per_aisle: int | None = None, max_per_department: int | None = None):
         """recommend_batch plus (embedding ms incl. host tokenisation, similarity ms) from HIP events
         on the launch stream — what the micro-batching server reports as per-request stats.  A diversified batch's
-        re-selection and a boosted batch's merge count into the similarity time."""
+        re-selection, a boosted batch's merge and a capped batch's rounds count into the similarity time."""
         k = self._k(top_k)
+        caps = cap_plan(max_per_aisle, max_per_department, self.aisles is not None)
         sets = within_plan(within, len(queries), self.product_sets)
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
@@ -620,14 +669,16 @@ class Recommender:
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed(list(queries))
         tok_ms = (time.time() - t0) * 1000
-        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow, mmr=mmr, boost=boost, sets=sets)
+        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow, mmr=mmr, boost=boost, sets=sets,
+                                                      caps=caps, width=candidates)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))], tok_ms + enc_ms, sim_ms
 
     def recommend(self, query: str, top_k: int = 10,
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
-                  only_boosted: bool = False, probes: int | None = None, within=None) -> list[tuple[str, float]]:
+                  only_boosted: bool = False, probes: int | None = None, within=None, max_per_aisle: int | None = None,
+                  max_per_department: int | None = None) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
         One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0".
         aisles / departments (keyword-only; names from .aisles / .departments): only products of one of these aisles
@@ -663,10 +714,22 @@ class Recommender:
         diversity through the search, and with boosts / only_boosted: boosted products outside the sets are dropped, and
         the result is the top_k of the products inside them under cosine + weight.  Such a request takes the
         un-captured path.  An unknown name, a fifth name, within on a recommender without product sets or together
-        with probes raise ValueError before any GPU work."""
+        with probes raise ValueError before any GPU work.
+        max_per_aisle / max_per_department (keyword-only; positive integers): at most that many products of one aisle /
+        of one department in the result.  The result is the walk of the COMPLETE ranking of the admissible products,
+        best first, that keeps a product only while its aisle and its department have room - exactly, however deep
+        in the ranking the last product lies (DeviceIndex.search_capped: `candidates` products per search, default
+        min(128, 4 * top_k); a request whose candidates are used up before top_k products are kept is searched
+        again without the aisles and departments that are full).  The order and the scores are the search's own.  It
+        composes with exclude_product_ids, aisles, departments and within, and with boosts / only_boosted: the ranking
+        that is walked is then the boosted one.  With diversity the caps thin the `candidates`-wide list in one round
+        and the re-selection picks from what is left, so the result keeps the caps.  Such a request takes the
+        un-captured path; both None is the plain request: the same launches, the same results.  A value that is not an
+        integer >= 1, caps on a catalog without facets or together with probes raise ValueError before any GPU work."""
         return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments,
                                    diversity=diversity, candidates=candidates, boosts=boosts, boost_weight=boost_weight,
-                                   only_boosted=only_boosted, probes=probes, within=within)
+                                   only_boosted=only_boosted, probes=probes, within=within, max_per_aisle=max_per_aisle,
+                                   max_per_department=max_per_department)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -690,7 +753,8 @@ class MonitoredRecommender(Recommender):
                   exclude_product_ids: set[str] | None = None, *, aisles: Optional[Sequence[str]] = None,
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
-                  only_boosted: bool = False, probes: int | None = None, within=None) -> list[tuple[str, float]]:
+                  only_boosted: bool = False, probes: int | None = None, within=None, max_per_aisle: int | None = None,
+                  max_per_department: int | None = None) -> list[tuple[str, float]]:
         """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
         replays (fastpath.py): the three timing fields keep their meaning there.  A diversified request's
         re-selection and a boosted request's merge count into the similarity time."""
@@ -698,7 +762,9 @@ class MonitoredRecommender(Recommender):
         results, encode_ms, sim_ms = self._recommend_one(query, top_k, exclude_product_ids, timed=True, aisles=aisles,
                                                          departments=departments, diversity=diversity,
                                                          candidates=candidates, boosts=boosts, boost_weight=boost_weight,
-                                                         only_boosted=only_boosted, probes=probes, within=within)
+                                                         only_boosted=only_boosted, probes=probes, within=within,
+                                                         max_per_aisle=max_per_aisle,
+                                                         max_per_department=max_per_department)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

@@ -164,6 +164,22 @@ def boost_csr(boosts, n_queries: int, device: Optional[torch.device] = None):
     return torch.from_numpy(off).to(device), torch.from_numpy(rows_a).to(device), torch.from_numpy(w_a).to(device), max_len
 
 
+def cap_pairs(caps, n_queries: int, device=None):
+    """Per-facet caps -> the table icrec_cap_select takes, int32 [n_queries, ICREC_MAX_FACETS] (a torch tensor on
+    `device`, a numpy array without one).  caps is one sequence of ICREC_MAX_FACETS ints for all queries, or
+    [n_queries, ICREC_MAX_FACETS] ints; an entry <= 0 (or None) leaves that facet uncapped."""
+    F = _native.ICREC_MAX_FACETS
+    c = np.asarray([[0 if v is None else v for v in row] for row in caps] if np.ndim(caps) == 2
+                   else [0 if v is None else v for v in caps])
+    if c.dtype.kind not in "iu" or c.shape not in ((F,), (n_queries, F)):
+        raise ValueError(f"caps must be {F} ints or ints [{n_queries}, {F}], got {c.dtype} {c.shape}")
+    c = np.clip(c.astype(np.int64), 0, 2**31 - 1).astype(np.int32)
+    out = np.array(np.broadcast_to(c, (n_queries, F)), order="C")  # (a writable copy)
+    if device is None:
+        return out
+    return torch.from_numpy(out).to(device)
+
+
 ROW_STORAGE = {"f32": 0, "bf16": 1, "f32+filter": 2, "bf16+filter": 3}  # ICREC_ROWS_* in include/icrec.h
 
 
@@ -433,6 +449,108 @@ class DeviceIndex:
         q = self._queries(q)
         idx, sc = (None, None) if only else self.search(q, k, exclude, allow, sets)
         return self.boost_select(q, idx, sc, boosts, k, exclude, allow)
+
+    def cap_select(self, idx: torch.Tensor, sc: torch.Tensor, caps, top_k: int, allow: Optional[torch.Tensor] = None):
+        """Caps per facet value on a search result (icrec_cap_select): idx int64 [Q, k] candidate rows as `search`
+        returns them (-1 pads; rows outside this shard are skipped) and sc float32 [Q, k] their scores, both device
+        tensors, caps as cap_pairs takes them (or its device tensor), allow the masks the candidates were searched with (or None)
+        -> (idx int64 [Q, top_k], score float32 [Q, top_k], state int32 [Q, 2], allow_next uint32 [Q, n_facets, 8]) on
+        the device: each query's candidates in their order, without those whose aisle (facet 0) or department (facet 1)
+        already has its cap of rows before them; state[q] = (picks, done), done = 0 where fewer than top_k rows were
+        kept and the list held no pad - a wider or a further search may then find more (search_capped runs those
+        rounds); allow_next = allow without the values that are full."""
+        if idx.dim() != 2 or idx.dtype != torch.int64 or sc.dtype != torch.float32 or sc.shape != idx.shape:
+            raise ValueError(f"idx must be int64 [Q, k] and sc float32 [Q, k], got {idx.dtype} {tuple(idx.shape)} "
+                             f"and {sc.dtype} {tuple(sc.shape)}")
+        idx, sc = idx.to(self.device).contiguous(), sc.to(self.device).contiguous()
+        Q = int(idx.shape[0])
+        out_idx = torch.empty((Q, top_k), dtype=torch.int64, device=self.device)
+        out_sc = torch.empty((Q, top_k), dtype=torch.float32, device=self.device)
+        state = torch.empty((Q, 2), dtype=torch.int32, device=self.device)
+        allow_next = torch.empty((Q, max(self.n_facets, 1), _native.ICREC_FACET_MASK_WORDS), dtype=torch.int32,
+                                 device=self.device).view(torch.uint32)
+        caps = caps if isinstance(caps, torch.Tensor) else cap_pairs(caps, Q, self.device)
+        self.cap_select_into(idx, sc, caps, top_k, out_idx, out_sc, state, allow=allow, allow_next=allow_next)
+        return out_idx, out_sc, state, allow_next
+
+    def cap_select_into(self, idx: torch.Tensor, sc: torch.Tensor, caps: torch.Tensor, top_k: int, out_idx: torch.Tensor,
+                        out_score: torch.Tensor, out_state: torch.Tensor, n_prior: Optional[torch.Tensor] = None,
+                        allow: Optional[torch.Tensor] = None, allow_next: Optional[torch.Tensor] = None) -> None:
+        """Allocation-free form of `cap_select` on caller-owned contiguous device buffers (hipGraph-capturable; there is
+        no workspace): caps int32 [Q, 2], out_state int32 [Q, 2].  With n_prior int32 [Q] the first n_prior[q] entries
+        of a query's out rows are picks of an earlier round: they stay, count towards the caps, and the walk appends
+        behind them.  allow_next may be `allow` itself.  The kernel reads caps, n_prior and allow when it runs."""
+        Q = int(idx.shape[0])
+        if caps.dtype != torch.int32 or tuple(caps.shape) != (Q, _native.ICREC_MAX_FACETS) or not caps.is_contiguous():
+            raise ValueError(f"caps must be a contiguous int32 tensor [{Q}, {_native.ICREC_MAX_FACETS}], got {caps.dtype} "
+                             f"{tuple(caps.shape)}")
+        if n_prior is not None and (n_prior.dtype != torch.int32 or tuple(n_prior.shape) != (Q,) or not n_prior.is_contiguous()):
+            raise ValueError(f"n_prior must be a contiguous int32 tensor [{Q}], got {n_prior.dtype} {tuple(n_prior.shape)}")
+        for m in (allow, allow_next):
+            if m is not None:
+                self._check_allow(m, Q)
+        _native.cap_select(self._h, idx, sc, caps, n_prior, allow, top_k, out_idx, out_score, out_state, allow_next,
+                           self.device)
+
+    #: rounds the last search_capped needed (1: every query was done after the first search)
+    last_cap_rounds = 0
+
+    def search_capped(self, q, top_k: int, caps, candidates: Optional[int] = None,
+                      exclude: Optional[Sequence[Iterable[int]]] = None, allow: Optional[torch.Tensor] = None,
+                      sets: Optional[torch.Tensor] = None, boosts=None, only: bool = False):
+        """The top_k rows per query under caps per facet value, exactly: the greedy walk of the query's complete ranking
+        of the admissible rows that keeps a row only while its aisle (facet 0) and department (facet 1) have fewer
+        than caps rows before it -> (idx int64 [Q, top_k] with -1 pads, score float32 [Q, top_k]), in the search's
+        order.  caps as cap_pairs takes them; exclude, allow and sets as `search` takes them; boosts (and only) as
+        search_boosted takes them - the ranking is then the boosted one.
+        Round 1 searches `candidates` wide (default min(128, 4 * top_k), clipped to the shard, never below top_k) for
+        all queries and walks the lists on the device (cap_select).  A query whose list ran out before top_k rows
+        were kept goes into a further round: searched again without its picks and without the aisles and departments
+        that are full, walked again with the picks as priors - until no query is left (include/icrec.h has the proof
+        that this is the walk of the whole ranking).  Between rounds the host reads the states and the picks of the
+        unfinished queries and merges the picks into their exclusion lists.  last_cap_rounds: the rounds it took."""
+        q = self._queries(q)
+        Q = int(q.shape[0])
+        top_k = int(top_k)
+        if not 1 <= top_k <= _native.ICREC_MAX_K:
+            raise ValueError(f"top_k must be in [1, {_native.ICREC_MAX_K}], got {top_k}")
+        k = min(_native.ICREC_MAX_K, 4 * top_k) if candidates is None else int(candidates)
+        if not 1 <= k <= _native.ICREC_MAX_K:
+            raise ValueError(f"candidates must be in [1, {_native.ICREC_MAX_K}], got {candidates!r}")
+        k = max(min(k, self.n_rows), min(top_k, self.n_rows))
+        caps = cap_pairs(caps, Q, self.device)
+        if exclude is not None and len(exclude) != Q:
+            raise ValueError(f"exclude has {len(exclude)} entries for {Q} queries")
+        if boosts is not None and len(boosts) != Q:
+            raise ValueError(f"boosts has {len(boosts)} entries for {Q} queries")
+
+        def ranked(q_, exclude_, allow_, sets_, boosts_):
+            if boosts_ is None:
+                return self.search(q_, k, exclude_, allow_, sets_)
+            return self.search_boosted(q_, k, boosts_, exclude_, allow_, only, sets_)
+
+        out_idx, out_sc, state, allow_next = self.cap_select(*ranked(q, exclude, allow, sets, boosts), caps, top_k, allow)
+        self.last_cap_rounds = 1
+        words = allow_next.view(torch.int32)  # (torch indexes int32, not uint32)
+        while True:
+            left = torch.nonzero(state[:, 1] == 0)[:, 0]  # (the comparison's result read by nonzero synchronises)
+            if left.numel() == 0:
+                return out_idx, out_sc
+            if self.last_cap_rounds > _native.ICREC_MAX_FACETS * 256 + 1:
+                raise _native.IcrecError("search_capped: more rounds than facet values")  # (the proof's bound)
+            self.last_cap_rounds += 1
+            sub = left.tolist()
+            o_idx, o_sc = out_idx[left], out_sc[left]
+            picks = o_idx.cpu().numpy() - self.row_offset
+            n_prior = state[left, 0].contiguous()
+            excl = [sorted(set(int(v) for v in (exclude[i] if exclude is not None else ())) | set(row[row >= 0].tolist()))
+                    for i, row in zip(sub, picks)]
+            masks = words[left].contiguous().view(torch.uint32)
+            st = torch.empty((len(sub), 2), dtype=torch.int32, device=self.device)
+            c_idx, c_sc = ranked(q[left], excl, masks, None if sets is None else sets[left].contiguous(),
+                                 None if boosts is None else [boosts[i] for i in sub])
+            self.cap_select_into(c_idx, c_sc, caps[left].contiguous(), top_k, o_idx, o_sc, st, n_prior, masks, masks)
+            out_idx[left], out_sc[left], state[left], words[left] = o_idx, o_sc, st, masks.view(torch.int32)
 
     def search_partial(self, q, k: int, exclude: Optional[Sequence[Iterable[int]]] = None) -> torch.Tensor:
         """Shard-local sorted lists as packed keys, int64-viewed uint64 [Q,k] (see icrec_search_partial)."""

@@ -1,0 +1,170 @@
+"""Recommender.recommend(..., max_per_aisle=, max_per_department=) end to end on the GPU, on the synthetic 2-layer model
+directory and 700-product catalog of the MMR recommender test: a capped request equals the one-pass capped walk of the
+COMPLETE plain ranking (taken through the plain request itself, 128 products at a time), a batch equals the single
+requests, no caps is today's request on the graph path, and with diversity the result is tests/mmr_reference.py
+applied to the capped candidate pool."""
+from __future__ import annotations
+
+import json
+
+import numpy as np
+import pytest
+
+from instacart_next_order_recommendation_amd import synthetic as syn
+from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
+from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, catalog_facets
+from tests import mmr_reference
+from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def rec(tmp_path_factory, torch_cuda):
+    tmp = tmp_path_factory.mktemp("cap_rec")
+    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
+    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
+    corpus_path = tmp / "processed" / "eval_corpus.json"
+    corpus_path.parent.mkdir()
+    corpus_path.write_text(json.dumps(syn.synthetic_catalog(700)))
+    r = MonitoredRecommender(model_dir, corpus_path, use_index=False)
+    assert r._fast is not None and r._index.n_facets == 2
+    return r
+
+
+QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
+
+
+@pytest.fixture(scope="module")
+def codes(rec):
+    """{product id: (aisle code, department code)} from the catalog texts."""
+    return {p: tuple(int(v) for v in c) for p, c in zip(rec.product_ids, catalog_facets(rec.product_texts)[2])}
+
+
+@pytest.fixture(scope="module")
+def rankings(rec):
+    """Every query's complete plain ranking [(product id, score)] of the 700 products: the plain top 128, then the top
+    128 of what is left, and so on - requests that existed before caps did."""
+    out = {}
+    for q in QUERIES:
+        full: list = []
+        while len(full) < len(rec.product_ids):
+            more = rec.recommend(q, 128, exclude_product_ids={p for p, _ in full})
+            assert more
+            full += more
+        assert len(full) == len({p for p, _ in full}) == 700
+        out[q] = full
+    return out
+
+
+def walk(ranked, codes, caps, top_k, skip=()):
+    """The one-pass capped walk of a ranked [(product id, score)] list; caps = (aisle, department), None = no cap."""
+    count = ({}, {})
+    kept = []
+    for p, s in ranked:
+        if len(kept) == top_k:
+            break
+        if p in skip or any(cap is not None and count[f].get(codes[p][f], 0) >= cap for f, cap in enumerate(caps)):
+            continue
+        kept.append((p, s))
+        for f in (0, 1):
+            count[f][codes[p][f]] = count[f].get(codes[p][f], 0) + 1
+    return kept
+
+
+def respects(result, codes, caps):
+    for f, cap in enumerate(caps):
+        if cap is not None:
+            values = [codes[p][f] for p, _ in result]
+            assert max((values.count(v) for v in set(values)), default=0) <= cap
+
+
+def test_capped_requests_equal_the_walk_of_the_complete_ranking(rec, codes, rankings):
+    rounds, changed = [], 0
+    for q in QUERIES:
+        full = rankings[q]
+        for kw, caps in ((dict(max_per_aisle=1, candidates=20), (1, None)), (dict(max_per_department=2), (None, 2)),
+                         (dict(max_per_aisle=2, max_per_department=5), (2, 5)),
+                         (dict(max_per_department=1, candidates=128), (None, 1))):
+            got = rec.recommend(q, 20, **kw)
+            rounds.append(rec._index.last_cap_rounds)
+            assert got == walk(full, codes, caps, 20), (q, kw)
+            respects(got, codes, caps)
+            changed += got != full[:20]
+        drop = {p for p, _ in full[:3]}
+        got = rec.recommend(q, 10, exclude_product_ids=drop, departments=rec.departments[:4], max_per_aisle=1)
+        inside = [(p, s) for p, s in full if rec.departments[codes[p][1]] in rec.departments[:4]]
+        assert got == walk(inside, codes, (1, None), 10, skip=drop)
+    assert changed > 0 and max(rounds) >= 2, rounds  # the caps bind, and some request needed a continuation round
+
+
+def test_batch_equals_single_calls(rec, codes):
+    excl = [None, {"1", "2", "3"}, None, {"10"}, None]
+    departments = [None, None, rec.departments[:6], None, [rec.departments[0], rec.departments[2]]]
+    for kw in (dict(max_per_aisle=1, candidates=20), dict(max_per_aisle=2, max_per_department=3)):
+        batch = rec.recommend_batch(QUERIES, 20, excl, departments=departments, **kw)
+        for i, q in enumerate(QUERIES):
+            assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], departments=departments[i], **kw), i
+            respects(batch[i], codes, (kw.get("max_per_aisle"), kw.get("max_per_department")))
+        timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 20, excl, departments=departments, **kw)
+        assert timed == batch and enc_ms > 0 and sim_ms > 0
+
+
+def test_no_caps_is_the_plain_request_on_the_graph_path(rec, monkeypatch):
+    fast = rec._fast_path()
+    calls = []
+    real_run = type(fast).run
+
+    def run(self, *a, **kw):
+        calls.append(1)
+        return real_run(self, *a, **kw)
+
+    monkeypatch.setattr(type(fast), "run", run)
+    for q in QUERIES:
+        assert rec.recommend(q, 20, max_per_aisle=None, max_per_department=None) == rec.recommend(q, 20)
+    assert len(calls) == 2 * len(QUERIES)
+    rec.recommend(QUERIES[0], 20, max_per_aisle=2)  # a capped request takes the un-captured path
+    assert len(calls) == 2 * len(QUERIES)
+    assert rec.recommend_batch(QUERIES, 20, max_per_aisle=None) == rec.recommend_batch(QUERIES, 20)
+
+
+def test_with_diversity_mmr_picks_from_the_capped_pool(rec, codes, rankings):
+    p_hat = mmr_reference.stored_rows(rec.product_embeddings, rec._index.storage)
+    for q in QUERIES:
+        for caps, kw in (((2, None), dict(max_per_aisle=2)), ((None, 3), dict(max_per_department=3))):
+            pool = walk(rankings[q][:80], codes, caps, 80)  # ONE round over the 80 candidates: no continuation
+            cand = np.asarray([[rec._pid_to_row[p] for p, _ in pool]], np.int64)
+            rel = np.asarray([[s for _, s in pool]], np.float32)
+            idx, out = mmr_reference.mmr_select(p_hat, cand, rel, min(20, len(pool)), 0.5)
+            want = [(rec.product_ids[int(i)], float(s)) for i, s in zip(idx[0], out[0]) if i >= 0]
+            got = rec.recommend(q, 20, diversity=0.5, candidates=80, **kw)
+            assert got == want and got
+            respects(got, codes, caps)
+
+
+def test_boosted_and_capped(rec, codes, rankings):
+    """Zero-weight boosts leave the ranking as it is, so the capped walk is that of the plain ranking; only_boosted
+    walks the listed products alone."""
+    q = QUERIES[0]
+    full = rankings[q]
+    listed = [p for p, _ in full[5:300:7]]
+    assert rec.recommend(q, 20, boosts=listed, boost_weight=0.0, max_per_aisle=1) == walk(full, codes, (1, None), 20)
+    got = rec.recommend(q, 20, boosts=listed, boost_weight=0.0, only_boosted=True, max_per_department=2)
+    assert got == walk([(p, s) for p, s in full if p in set(listed)], codes, (None, 2), 20)
+
+
+def test_bad_arguments_raise_before_any_gpu_work(rec, monkeypatch):
+    def no_gpu(*a, **kw):
+        raise AssertionError("GPU work before the argument check")
+
+    monkeypatch.setattr(rec, "_encode_search", no_gpu)
+    monkeypatch.setattr(type(rec._fast_path()), "run", no_gpu)
+    for bad in (0, -2, 1.5, "3", True):
+        with pytest.raises(ValueError, match="max_per_aisle"):
+            rec.recommend(QUERIES[0], 20, max_per_aisle=bad)
+        with pytest.raises(ValueError, match="max_per_department"):
+            rec.recommend_batch(QUERIES[:2], 20, max_per_department=bad)
+        with pytest.raises(ValueError, match="max_per_aisle"):
+            rec.recommend_batch_timed(QUERIES[:2], 20, max_per_aisle=bad)
+    with pytest.raises(ValueError, match="probes"):
+        rec.recommend(QUERIES[0], 20, max_per_aisle=2, probes=4)  # (this recommender has no IVF index either)
