@@ -338,6 +338,38 @@ ICREC_API int32_t icrec_index_device(const icrec_index* idx);  /* HIP device ord
  * widened exactly); used by the parity tests and by EmbeddingIndex.save.     */
 ICREC_API int icrec_index_export(const icrec_index* idx, float* rows_dev, void* stream);
 
+/* The filter copy of a *_FILTER storage as f16 bits, row-major [n_rows, dim] each: the values the filter pass
+ * multiplies, as stored - the hi/lo planes, or for the resident form (dim 384) the packed fragments un-packed (their
+ * values carry the fragments' scale, 1024).  hi_dev, lo_dev: DEVICE memory; asynchronous on `stream`.  ICREC_EINVAL for
+ * a NULL argument or a storage without a filter copy.  Beside icrec_index_export, for the parity tests: a search's
+ * result cannot show a filter copy that is merely stale. */
+ICREC_API int icrec_index_export_filter(const icrec_index* idx, uint16_t* hi_dev, uint16_t* lo_dev, void* stream);
+
+/* Rewrite rows of the index in place: a product's text changed, or the encoder was trained again and every row did.
+ *   rows_dev     float[m, dim]  the new rows in DEVICE memory, of any norm
+ *   row_ids_dev  int32[m]       the LOCAL rows they replace, in DEVICE memory, ascending and unique
+ * For every entry i with 0 <= row_ids[i] < n_rows, everything the index keeps for that row becomes what
+ * icrec_index_create_ex would have written for it from rows[i], bit for bit: the stored row (the same normalisation in
+ * the same reduction order, the same division, the same bfloat16 rounding) and, in the *_FILTER storages, its filter
+ * copy in whichever form the handle has - the row's entries of the hi/lo planes, or for dim 384 its lane slots of the
+ * packed fragments - made from the STORED (rounded) value.  No other row and no padding row of the fragments changes:
+ * after the call the handle is the one icrec_index_create_ex makes from the edited matrix.  Facets, row sets, the row
+ * offset and every pointer of the handle stay: a graph captured before the write and replayed after it searches the new
+ * rows.
+ * An entry outside [0, n_rows) is skipped before any address is formed from it (the ids live in device memory, where
+ * the host cannot refuse them).  A list that is not ascending and unique gives an unspecified result for the rows it
+ * names, until they are written again, but a memory-safe one: nothing outside the index's arrays is ever written.
+ * Asynchronous on `stream` and ordered like any other work on it: no workspace, nothing is allocated, nothing
+ * synchronises; capturable into a hipGraph, the ids and the rows being read from device memory when the kernel runs (a
+ * replay follows what the two buffers then hold).  The caller must not let it run concurrently with a call on the same
+ * index on another stream.  One launch, one wavefront per written row: rewriting all n_rows rows is how a re-trained
+ * model is brought in.
+ * m == 0 returns ICREC_OK and launches nothing.  ICREC_EINVAL, before any HIP call: a NULL idx, m < 0, a NULL pointer
+ * with m > 0.
+ * An icrec_ivf over the index owns its copy of the rows and does not see a write (see icrec_ivf_create). */
+ICREC_API int icrec_index_write_rows(icrec_index* idx, const float* rows_dev, const int32_t* row_ids_dev,
+                                     int32_t m, void* stream);
+
 ICREC_API size_t icrec_search_workspace_bytes(const icrec_index* idx, int32_t n_queries,
                                     int32_t k);
 
@@ -379,6 +411,15 @@ ICREC_API int icrec_search(icrec_index* idx, const float* q_dev, int32_t n_queri
 ICREC_API int icrec_index_set_facets(icrec_index* idx, const uint8_t* facets_host, int32_t n_facets);
 /* Facets per row of the index: 0 when none are set, -1 for a NULL handle. */
 ICREC_API int32_t icrec_index_facets(const icrec_index* idx);
+/* Replace the facet values of m rows (a product moved to another aisle).
+ *   row_ids_host  int32[m]                               HOST pointer: LOCAL rows, ascending and unique
+ *   facets_host   uint8[m, icrec_index_facets(idx)]      HOST pointer: their new values
+ * Nothing else changes, the zero padding behind the last row included.  ICREC_EINVAL, changing nothing: an index
+ * without facets, a row outside [0, n_rows), rows that are not ascending and unique, a NULL argument, m < 0.  A set-up
+ * call like icrec_index_write_rowset: it copies, may allocate host memory and synchronise.  A captured graph replayed
+ * afterwards follows the new values. */
+ICREC_API int icrec_index_write_facets(icrec_index* idx, const int32_t* row_ids_host, const uint8_t* facets_host,
+                                       int32_t m);
 
 /* Scratch bytes of icrec_search_faceted (0 for a bad argument); equal to icrec_search_workspace_bytes. */
 ICREC_API size_t icrec_search_faceted_workspace_bytes(const icrec_index* idx, int32_t n_queries, int32_t k);
@@ -637,7 +678,9 @@ typedef struct icrec_ivf icrec_ivf;
 /* Build the IVF.  centroids_dev: float[n_lists, dim] in DEVICE memory.  ICREC_EINVAL: a NULL argument, n_lists < 1 or
  * n_lists > n_rows, a base of 2^31 rows or more.  A set-up call like icrec_index_set_facets: it allocates (the
  * gathered rows: as many bytes as the base's rows), synchronises, assigns the rows in passes over slices of them, sorts
- * on the host, and must never be issued while a call on the base index is running. */
+ * on the host, and must never be issued while a call on the base index is running.
+ * The IVF owns its copy of the rows and their assignment: it does not see icrec_index_write_rows on the base.  After a
+ * write, destroy it and create it again from the same centroids. */
 ICREC_API int icrec_ivf_create(icrec_index* base, const float* centroids_dev, int32_t n_lists, icrec_ivf** out);
 ICREC_API int icrec_ivf_destroy(icrec_ivf* ivf);
 ICREC_API int32_t icrec_ivf_lists(const icrec_ivf* ivf);                      /* n_lists; -1 for NULL */
@@ -907,7 +950,8 @@ ICREC_API const char* icrec_version(void);
  *        5 = icrec_mmr_select's similarity-matrix kernel, 6 = its selection kernel,
  *        7 = icrec_boost_select's scoring kernel, 8 = its selection kernel,
  *        10 = icrec_ivf_search's list scan kernel (9 is a spare of the encoder's),
- *        11 = icrec_cap_select's kernel. */
+ *        11 = icrec_cap_select's kernel,
+ *        12 = icrec_index_write_rows' kernel. */
 ICREC_API int icrec_timing_enable(int on);
 ICREC_API int icrec_timing_reset(void);
 ICREC_API int icrec_timing_query(int which, double* avg_ms, int64_t* n_launches);

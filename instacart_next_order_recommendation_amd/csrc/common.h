@@ -45,7 +45,8 @@ struct TimingSlot {
     int64_t n = 0;
 };
 enum { T_SEARCH_KERNEL = 0, T_FFN_UP = 1, T_ENCODE = 2, T_SEARCH = 3, T_SEARCH_FALLBACK = 4, T_MMR_GRAM = 5, T_MMR_SELECT = 6,
-       T_BOOST_SCORE = 7, T_BOOST_SELECT = 8, T_FFN_UP_SMALL = 9 /* a spare of encoder.hip's */, T_IVF_SCAN = 10, T_CAP_SELECT = 11, T_NSLOTS = 12 };
+       T_BOOST_SCORE = 7, T_BOOST_SELECT = 8, T_FFN_UP_SMALL = 9 /* a spare of encoder.hip's */, T_IVF_SCAN = 10, T_CAP_SELECT = 11,
+       T_INDEX_WRITE = 12, T_NSLOTS = 13 };
 bool timing_on();
 // Records [start, stop] around a launch when timing is enabled; resolved lazily at query time.
 struct ScopedTimer {

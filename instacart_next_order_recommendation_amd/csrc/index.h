@@ -45,6 +45,12 @@ using row_elem_t = std::conditional_t<P16, uint16_t, float>;
 // text set.
 constexpr int FILTER_DIM_STEP = 64;
 int build_filter_storage(Index* ix);
+// search.hip, for index.hip's icrec_index_write_rows (arguments checked, m >= 1): rows row_ids_dev[0 .. m) of the index
+// - the stored rows and, in a *_FILTER storage, their planes or fragment slots - become what icrec_index_create_ex
+// makes of rows_dev[0 .. m), in one launch on `st`; ids outside [0, n_rows) are skipped on the device.  And for
+// icrec_index_export_filter (the handle has a filter copy): that copy as row-major f16 bits [n_rows, dim] each.
+int write_index_rows(Index* ix, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, hipStream_t st);
+int export_filter_storage(const Index* ix, uint16_t* hi_dev, uint16_t* lo_dev, hipStream_t st);
 
 #ifdef __HIPCC__
 

@@ -1,6 +1,7 @@
 // index.hip — the life cycle of an icrec_index handle (index.h: struct Index): creation with row normalisation,
-// facets, row sets, export, the accessors and destruction; and icrec_normalize_rows.  The filter storages' layout belongs to the
-// kernels that read it: search.hip builds it (build_filter_storage).
+// facets, row sets, rows and facets rewritten in place, export, the accessors and destruction; and icrec_normalize_rows.
+// The filter storages' layout belongs to the kernels that read it: search.hip builds it (build_filter_storage), rewrites
+// it with the rows (write_index_rows) and un-packs it (export_filter_storage).
 #include <stdlib.h>
 
 #include <new>
@@ -210,6 +211,56 @@ int icrec_index_export(const icrec_index* h, float* rows_dev, void* stream) {
         ICREC_HIP(hipMemcpyAsync(rows_dev, ix->rows, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return ICREC_OK;
+}
+
+int icrec_index_write_rows(icrec_index* h, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, void* stream) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix, "icrec_index_write_rows: NULL index");
+    ICREC_REQUIRE(m >= 0, "icrec_index_write_rows: m must be >= 0 (got %d)", m);
+    if (m == 0) return ICREC_OK;
+    ICREC_REQUIRE(rows_dev && row_ids_dev, "icrec_index_write_rows: NULL argument");
+    ICREC_HIP(hipSetDevice(ix->device));
+    ScopedTimer tm(T_INDEX_WRITE, (hipStream_t)stream);
+    return write_index_rows(ix, rows_dev, row_ids_dev, m, (hipStream_t)stream);
+}
+
+int icrec_index_write_facets(icrec_index* h, const int32_t* row_ids_host, const uint8_t* facets_host, int32_t m) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix, "icrec_index_write_facets: NULL index");
+    ICREC_REQUIRE(m >= 0, "icrec_index_write_facets: m must be >= 0 (got %d)", m);
+    ICREC_REQUIRE(m == 0 || (row_ids_host && facets_host), "icrec_index_write_facets: NULL argument");
+    ICREC_REQUIRE(ix->facets != nullptr, "icrec_index_write_facets: the index has no facets");
+    for (int32_t i = 0; i < m; ++i) {
+        ICREC_REQUIRE(row_ids_host[i] >= 0 && row_ids_host[i] < ix->n_rows, "icrec_index_write_facets: row %d is outside [0, %lld)",
+                      row_ids_host[i], (long long)ix->n_rows);
+        ICREC_REQUIRE(i == 0 || row_ids_host[i] > row_ids_host[i - 1], "icrec_index_write_facets: the rows must be ascending and unique");
+    }
+    if (m == 0) return ICREC_OK;
+    ICREC_HIP(hipSetDevice(ix->device));
+    // the words from the first named row to the last: down, patched, up again (a blocking copy each way)
+    const int64_t first = row_ids_host[0], count = (int64_t)row_ids_host[m - 1] - first + 1;
+    std::vector<uint16_t> words;
+    try {
+        words.resize((size_t)count);
+    } catch (const std::bad_alloc&) {
+        set_error("icrec_index_write_facets: no host memory for %zu bytes", (size_t)count * 2);
+        return ICREC_ENOMEM;
+    }
+    ICREC_HIP(hipMemcpy(words.data(), ix->facets + first, (size_t)count * 2, hipMemcpyDeviceToHost));
+    const int nf = ix->n_facets;
+    for (int32_t i = 0; i < m; ++i)
+        words[row_ids_host[i] - first] =
+            nf == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * (size_t)i] | (facets_host[2 * (size_t)i + 1] << 8));
+    ICREC_HIP(hipMemcpy(ix->facets + first, words.data(), (size_t)count * 2, hipMemcpyHostToDevice));
+    return ICREC_OK;
+}
+
+int icrec_index_export_filter(const icrec_index* h, uint16_t* hi_dev, uint16_t* lo_dev, void* stream) {
+    const Index* ix = reinterpret_cast<const Index*>(h);
+    ICREC_REQUIRE(ix && hi_dev && lo_dev, "icrec_index_export_filter: NULL argument");
+    ICREC_REQUIRE(ix->frag || ix->plane_hi, "icrec_index_export_filter: the index's storage has no filter copy");
+    ICREC_HIP(hipSetDevice(ix->device));
+    return export_filter_storage(ix, hi_dev, lo_dev, (hipStream_t)stream);
 }
 
 int icrec_normalize_rows(const float* x_dev, float* out_dev, int64_t n_rows, int32_t dim, float eps, int device,

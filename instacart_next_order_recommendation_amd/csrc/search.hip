@@ -980,6 +980,125 @@ int build_filter_storage(Index* ix) {
     return ICREC_OK;
 }
 
+// ---------------------------------------------------------------- rows rewritten in place (icrec_index_write_rows)
+// One wavefront per written row w: row ids[w] of the index becomes what icrec_index_create_ex makes of x[w].  The norm
+// is normalize_rows_kernel's, lane for lane (64 strided fmaf partials, the xor butterfly, the same division), so the
+// stored bits are a fresh index's.  The STORED values (bf16: rounded, widened back) go through LDS, so that a lane
+// then owns 8 consecutive k and every store is 16 bytes: the row itself, and from the same values its filter copy -
+// the planes as split_planes_kernel splits them, or the row's lane slots of its 2 * dim / 16 fragments as
+// pack_rows_kernel packs them (lane (h << 5 | r) of fragment (row / 32, ks) holds k = 16 ks + 8 h .. + 7: chunk
+// c = 2 ks + h).  An id outside [0, n_rows) writes nothing: it is tested before any address is formed from it.
+// No other row's bytes are touched; the padding rows of the last fragment round stay zero.
+constexpr int WRITE_NO_FILTER = 0, WRITE_PLANES = 1, WRITE_FRAGS = 2;
+template <bool OUT16, int FILT>
+__global__ __launch_bounds__(256) void write_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ ids, int m,
+                                                         void* __restrict__ rowsv, int64_t n_rows, int dim,
+                                                         _Float16* __restrict__ hi, _Float16* __restrict__ lo,
+                                                         _Float16* __restrict__ frag) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* st = reinterpret_cast<float*>(smem_raw) + (size_t)wave * dim;  // this wave's stored values
+    const int64_t w = (int64_t)blockIdx.x * 4 + wave;
+    int64_t row = -1;  // wave-uniform
+    if (w < m) {
+        const int32_t id = ids[w];
+        if (id >= 0 && id < n_rows) row = id;
+    }
+    if (row >= 0) {
+        const float* xr = x + w * dim;
+        float acc = 0.0f;
+        for (int i = lane; i < dim; i += 64) {
+            float v = xr[i];
+            acc = fmaf(v, v, acc);
+        }
+        float nrm = sqrtf(wave_sum_f32(acc));
+        float den = nrm > 1e-12f ? nrm : 1e-12f;
+        for (int i = lane; i < dim; i += 64) {
+            const float v = xr[i] / den;
+            st[i] = OUT16 ? bf16_lo(bf16_rne(v)) : v;
+        }
+    }
+    __syncthreads();
+    if (row < 0) return;
+    for (int c = lane; c < dim / 8; c += 64) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(st + 8 * c), b = *reinterpret_cast<const f32x4*>(st + 8 * c + 4);
+        const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+        if (OUT16) {
+            u32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = (__float_as_uint(v[2 * j]) >> 16) | (__float_as_uint(v[2 * j + 1]) & 0xFFFF0000u);
+            *reinterpret_cast<u32x4*>(static_cast<uint16_t*>(rowsv) + row * dim + 8 * c) = o;
+        } else {
+            float* out = static_cast<float*>(rowsv) + row * dim + 8 * c;
+            *reinterpret_cast<f32x4*>(out) = a;
+            *reinterpret_cast<f32x4*>(out + 4) = b;
+        }
+        if (FILT == WRITE_NO_FILTER) continue;
+        half8 ph, pl;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            _Float16 s, t;
+            if (FILT == WRITE_PLANES) split_f16(v[j], s, t);
+            else split_scaled(v[j], WT_SW, s, t);
+            ph[j] = s;
+            pl[j] = t;
+        }
+        if (FILT == WRITE_PLANES) {
+            *reinterpret_cast<half8*>(hi + row * dim + 8 * c) = ph;
+            *reinterpret_cast<half8*>(lo + row * dim + 8 * c) = pl;
+        } else {
+            const int64_t fr = (row >> 5) * (dim / 16) + (c >> 1);
+            _Float16* at = frag + fr * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(row & 31)) * 8;
+            *reinterpret_cast<half8*>(at) = ph;
+            *reinterpret_cast<half8*>(at + WT_FRAG) = pl;
+        }
+    }
+}
+
+// index.h: icrec_index_write_rows after its argument checks (m >= 1): one launch, nothing allocated.
+int write_index_rows(Index* ix, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, hipStream_t st) {
+    const bool rows16 = rows_are_bf16(ix);
+    const int filt = ix->frag ? WRITE_FRAGS : ix->plane_hi ? WRITE_PLANES : WRITE_NO_FILTER;
+    typedef void (*kernel_t)(const float*, const int32_t*, int, void*, int64_t, int, _Float16*, _Float16*, _Float16*);
+    static const kernel_t kernels[2][3] = {
+        {write_rows_kernel<false, WRITE_NO_FILTER>, write_rows_kernel<false, WRITE_PLANES>, write_rows_kernel<false, WRITE_FRAGS>},
+        {write_rows_kernel<true, WRITE_NO_FILTER>, write_rows_kernel<true, WRITE_PLANES>, write_rows_kernel<true, WRITE_FRAGS>}};
+    hipLaunchKernelGGL(kernels[rows16][filt], dim3((unsigned)(((int64_t)m + 3) / 4)), dim3(256), (size_t)4 * ix->dim * sizeof(float), st,
+                       rows_dev, row_ids_dev, (int)m, ix->rows, ix->n_rows, ix->dim, ix->plane_hi, ix->plane_lo, ix->frag);
+    ICREC_HIP(hipGetLastError());
+    return ICREC_OK;
+}
+
+// The resident form's fragments un-packed to row-major planes (icrec_index_export_filter): one thread per (row, 8 k).
+__global__ __launch_bounds__(256) void unpack_rows_kernel(const _Float16* __restrict__ frag, int64_t n_rows, int K,
+                                                          _Float16* __restrict__ hi, _Float16* __restrict__ lo) {
+    const int chunks = K / 8;
+    for (int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x; id < n_rows * chunks; id += (int64_t)gridDim.x * 256) {
+        const int64_t row = id / chunks;
+        const int c = (int)(id % chunks);
+        const int64_t fr = (row >> 5) * (K / 16) + (c >> 1);
+        const _Float16* at = frag + fr * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(row & 31)) * 8;
+        *reinterpret_cast<half8*>(hi + row * K + 8 * c) = *reinterpret_cast<const half8*>(at);
+        *reinterpret_cast<half8*>(lo + row * K + 8 * c) = *reinterpret_cast<const half8*>(at + WT_FRAG);
+    }
+}
+
+// index.h: icrec_index_export_filter after its argument checks.
+int export_filter_storage(const Index* ix, uint16_t* hi_dev, uint16_t* lo_dev, hipStream_t st) {
+    const int64_t n = ix->n_rows * ix->dim;
+    if (ix->frag) {
+        const int64_t blocks = (n / 8 + 255) / 256;
+        hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st,
+                           (const _Float16*)ix->frag, ix->n_rows, ix->dim, reinterpret_cast<_Float16*>(hi_dev),
+                           reinterpret_cast<_Float16*>(lo_dev));
+        ICREC_HIP(hipGetLastError());
+    } else {
+        ICREC_HIP(hipMemcpyAsync(hi_dev, ix->plane_hi, (size_t)n * 2, hipMemcpyDeviceToDevice, st));
+        ICREC_HIP(hipMemcpyAsync(lo_dev, ix->plane_lo, (size_t)n * 2, hipMemcpyDeviceToDevice, st));
+    }
+    return ICREC_OK;
+}
+
 // Filter + verify (ICREC_ROWS_F32_FILTER): batches of at least FILTER_MIN_Q queries are ranked by the f16x3 filter
 // pass with FILTER_SLACK extra list entries, then verified exactly.  filter_eps(dim) bounds |filter score - exact score|
 // for unit vectors: the f16 split drops <= 3 * 2^-22 per product (Cauchy-Schwarz: <= 7.2e-7 per score) and either

@@ -116,16 +116,67 @@ def catalog_facets(texts: Sequence[str]):
     names: tuple[dict[str, int], dict[str, int]] = ({}, {})
     codes = np.zeros((len(texts), 2), np.uint8)
     for i, text in enumerate(texts):
-        d = text.rfind(". Department: ")
-        a = text.rfind(". Aisle: ", 0, d) if d >= 0 else -1
-        if a < 0 or not text.endswith("."):
+        parsed = text_facets(text)
+        if parsed is None:
             return None
-        for f, value in enumerate((text[a + len(". Aisle: "):d], text[d + len(". Department: "):-1])):
+        for f, value in enumerate(parsed):
             code = names[f].setdefault(value, len(names[f]))
             if code > 255:
                 return None
             codes[i, f] = code
     return list(names[0]), list(names[1]), codes
+
+
+def text_facets(text: str) -> Optional[tuple[str, str]]:
+    """(aisle, department) of one catalog text as catalog_facets parses it, or None when it does not parse."""
+    d = text.rfind(". Department: ")
+    a = text.rfind(". Aisle: ", 0, d) if d >= 0 else -1
+    if a < 0 or not text.endswith("."):
+        return None
+    return text[a + len(". Aisle: "):d], text[d + len(". Department: "):-1]
+
+
+def product_update_plan(updates, pid_to_row, product_texts, aisles, departments):
+    """Recommender.update_products' argument, checked before any GPU work.  updates: a mapping product id -> new text;
+    pid_to_row and product_texts: the catalog's rows and current texts; aisles / departments: its facet names, None for
+    a catalog without facets
+    -> (rows ascending, their new texts, facet codes uint8 [m, 2] or None without facets, aisle names, department names).
+    A name the catalog does not have yet is appended to (a copy of) its list, so every existing code stays what it is
+    (catalog_facets numbers by first appearance; a name no product carries any more keeps its code).  An empty
+    mapping gives no rows.  ValueError: not a mapping, an id the catalog does not have (adding a product is a re-index),
+    a text that is not a string, on a catalog with facets a text that does not parse as
+    'Product: .. Aisle: .. Department: ..', a 257th aisle or department name."""
+    if not hasattr(updates, "items"):
+        raise ValueError("updates must be a mapping product id -> new text")
+    pairs = []
+    for pid, text in updates.items():
+        if pid not in pid_to_row or not 0 <= pid_to_row[pid] < len(product_texts):
+            raise ValueError(f"unknown product id {pid!r}: update_products rewrites products the catalog has; adding one "
+                             "is a re-index")
+        if not isinstance(text, str):
+            raise ValueError(f"the new text of product {pid!r} must be a string, got {type(text).__name__}")
+        pairs.append((int(pid_to_row[pid]), text))
+    pairs.sort(key=lambda p: p[0])
+    rows, texts = [r for r, _ in pairs], [t for _, t in pairs]
+    if aisles is None:
+        return rows, texts, None, None, None
+    names = (list(aisles), list(departments))
+    code = tuple({name: i for i, name in enumerate(known)} for known in names)
+    codes = np.zeros((len(rows), 2), np.uint8)
+    for i, text in enumerate(texts):
+        parsed = text_facets(text)
+        if parsed is None:
+            raise ValueError(f"the new text of row {rows[i]} is not in the 'Product: .. Aisle: .. Department: ..' format "
+                             "of this catalog")
+        for f, value in enumerate(parsed):
+            if value not in code[f]:
+                if len(names[f]) >= 256:
+                    raise ValueError(f"{value!r} would be the 257th {'aisle' if f == 0 else 'department'} name; a facet "
+                                     "has 256 values")
+                code[f][value] = len(names[f])
+                names[f].append(value)
+            codes[i, f] = code[f][value]
+    return rows, texts, codes, names[0], names[1]
 
 
 def diversity_plan(diversity, candidates, top_k: int, n_products: int):
@@ -469,6 +520,41 @@ class Recommender:
         row = self._member_row(product_ids)
         self._index.write_rowset(ids[0], rowset_bits(row[None, :], len(self.product_ids))[0])
         self._set_member[ids[0]] = row
+
+    def update_products(self, updates) -> None:
+        """Give products new texts without a re-index: updates is a mapping product id -> new text.  The new texts are
+        encoded as the catalog was (normalize_embeddings=True), their rows and filter copies are rewritten on the
+        device in place (DeviceIndex.write_rows: afterwards the index is bit for bit the one a new Recommender builds
+        from the edited corpus) and, on a catalog with facets, so are their aisle and department codes
+        (DeviceIndex.write_facets; a new aisle or department name is appended to .aisles / .departments, the codes of
+        the others stay).  product_texts, pid_to_text and product_embeddings follow, and the IVF index of a
+        recommender built with ann_lists is built again from its centroids (IvfIndex.rebuild).  No pointer of the
+        index changes: the captured single-request graphs stay and answer from the new rows.
+        ValueError, with nothing changed: an id the catalog does not have (adding or removing a product changes the
+        number of rows and stays a re-index), a text that does not parse on a catalog with facets, a 257th aisle or
+        department name (product_update_plan).  An empty mapping does nothing.
+        The limits: it is a set-up call on the index, never to be made while a request is being served.  The corpus
+        file and the on-disk EmbeddingIndex cache are not rewritten: a process started later reads the old texts.  A
+        RerankedRecommender built on this recommender keeps its own token store and must be built again.  Product sets
+        are untouched: a product's membership is changed with update_product_set."""
+        rows, texts, codes, aisles, departments = product_update_plan(updates, self._pid_to_row, self.product_texts,
+                                                                       self.aisles, self.departments)
+        if not rows:
+            return
+        emb = self.model.encode(texts, show_progress_bar=False, normalize_embeddings=True)
+        self._index.write_rows(rows, emb)
+        if codes is not None:
+            self._index.write_facets(rows, codes)
+        torch.cuda.current_stream(self.device).synchronize()  # the graphs replay on a stream of their own
+        if not self.product_embeddings.flags.writeable:
+            self.product_embeddings = np.array(self.product_embeddings)
+        self.product_embeddings[rows] = emb
+        for r, text in zip(rows, texts):
+            self.product_texts[r] = text
+            self.pid_to_text[self.product_ids[r]] = text
+        self.aisles, self.departments = aisles, departments
+        if self._ann is not None:
+            self._ann.rebuild()
 
     # -- the hot path -------------------------------------------------------------------------
     def _k(self, top_k: int) -> int:

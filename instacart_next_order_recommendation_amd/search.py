@@ -265,6 +265,87 @@ class DeviceIndex:
         """Row sets of the index (0: none set)."""
         return int(_native.lib().icrec_index_rowsets(self._h))
 
+    def _sorted_rows(self, row_ids, m: int, what: str):
+        """Host row ids -> (ids int32 ascending, the permutation that sorted them); ValueError for a count other than m,
+        an id outside [0, n_rows) or a duplicate.  Needs no device."""
+        ids = np.asarray(row_ids.cpu() if isinstance(row_ids, torch.Tensor) else row_ids)
+        if ids.size == 0:
+            ids = ids.astype(np.int64)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu" or ids.shape[0] != m:
+            raise ValueError(f"{what}: row_ids must be {m} integers, got {ids.dtype} {ids.shape}")
+        ids = ids.astype(np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.n_rows):
+            bad = int(ids.min() if ids.min() < 0 else ids.max())
+            raise ValueError(f"{what}: row {bad} is outside 0..{self.n_rows - 1}")
+        order = np.argsort(ids, kind="stable")
+        ids = ids[order]
+        if (np.diff(ids) == 0).any():
+            raise ValueError(f"{what}: row {int(ids[1:][np.diff(ids) == 0][0])} is named twice")
+        return ids.astype(np.int32), order
+
+    def write_rows(self, row_ids, embeddings) -> None:
+        """Rewrite rows in place (icrec_index_write_rows): embeddings [m, dim] of any norm replace the LOCAL rows
+        row_ids, after which the index - stored rows and filter copy - is bit for bit the one built from the edited
+        matrix; no pointer of the handle changes, so captured graphs stay valid and search the new rows.  row_ids: m
+        host integers in any order (range and duplicates are checked here, ValueError; ids and rows are sorted
+        together), or a device int32 tensor [m], ascending and unique, which the kernel reads as it is (entries outside
+        the index are skipped).  Asynchronous on the current stream; the caller keeps it from running beside a search
+        of this index on another stream.  An IvfIndex over this index does not see the write: IvfIndex.rebuild."""
+        rows = torch.as_tensor(embeddings)
+        if rows.dim() != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"embeddings must be [m, {self.dim}], got {tuple(rows.shape)}")
+        m = int(rows.shape[0])
+        if isinstance(row_ids, torch.Tensor) and row_ids.is_cuda:
+            if row_ids.dtype != torch.int32 or tuple(row_ids.shape) != (m,):
+                raise ValueError(f"device row_ids must be int32 [{m}], got {row_ids.dtype} {tuple(row_ids.shape)}")
+            ids_dev = row_ids.to(self.device).contiguous()
+        else:
+            ids, order = self._sorted_rows(row_ids, m, "write_rows")
+            if m == 0:
+                return
+            rows = rows[torch.from_numpy(order).to(rows.device)]
+            ids_dev = torch.from_numpy(ids).to(self.device)
+        if m == 0:
+            return
+        self.write_rows_into(ids_dev, rows.to(device=self.device, dtype=torch.float32).contiguous())
+
+    def write_rows_into(self, ids_dev: torch.Tensor, rows_dev: torch.Tensor) -> None:
+        """Allocation-free form of `write_rows` on caller-owned contiguous device buffers (hipGraph-capturable; there is
+        no workspace): ids_dev int32 [m] ascending and unique, rows_dev float32 [m, dim].  The kernel reads both when
+        it runs: a captured graph follows what the buffers hold at replay."""
+        m = int(ids_dev.shape[0])
+        if ids_dev.dtype != torch.int32 or ids_dev.dim() != 1 or not ids_dev.is_contiguous() or ids_dev.device != self.device:
+            raise ValueError(f"ids_dev must be a contiguous int32 tensor [m] on {self.device}, got {ids_dev.dtype} "
+                             f"{tuple(ids_dev.shape)} on {ids_dev.device}")
+        if rows_dev.dtype != torch.float32 or tuple(rows_dev.shape) != (m, self.dim) or not rows_dev.is_contiguous() \
+                or rows_dev.device != self.device:
+            raise ValueError(f"rows_dev must be a contiguous float32 tensor [{m}, {self.dim}] on {self.device}, got "
+                             f"{rows_dev.dtype} {tuple(rows_dev.shape)} on {rows_dev.device}")
+        _native.check(_native.lib().icrec_index_write_rows(self._h, ptr(rows_dev), ptr(ids_dev), m, stream_ptr(self.device)),
+                      "icrec_index_write_rows")
+
+    def write_facets(self, row_ids, values) -> None:
+        """Replace the facet values of the LOCAL rows row_ids (host integers, any order, no duplicates) with values,
+        uint8 [m, n_facets] (icrec_index_write_facets).  A set-up call like write_rowset; a captured graph replayed
+        afterwards follows the new values."""
+        v = np.asarray(values)
+        if v.dtype != np.uint8 or v.ndim != 2 or v.shape[1] != (self.n_facets or v.shape[1]):
+            raise ValueError(f"facet values must be uint8 [m, {self.n_facets}], got {v.dtype} {v.shape}")
+        ids, order = self._sorted_rows(row_ids, int(v.shape[0]), "write_facets")
+        v = np.ascontiguousarray(v[order])
+        _native.check(_native.lib().icrec_index_write_facets(self._h, ids.ctypes.data_as(C.c_void_p),
+                                                             v.ctypes.data_as(C.c_void_p), int(ids.shape[0])),
+                      "icrec_index_write_facets")
+
+    def export_filter(self):
+        """The filter copy of a "+filter" storage, (hi, lo) float16 [n_rows, dim] on the device: the values the filter
+        pass multiplies, as stored (parity checks only)."""
+        hi = torch.empty((self.n_rows, self.dim), dtype=torch.float16, device=self.device)
+        lo = torch.empty_like(hi)
+        _native.check(_native.lib().icrec_index_export_filter(self._h, ptr(hi), ptr(lo), stream_ptr(self.device)),
+                      "icrec_index_export_filter")
+        return hi, lo
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _native.lib().icrec_index_destroy(self._h)
@@ -612,11 +693,25 @@ class IvfIndex:
         c = torch.as_tensor(centroids)
         if c.dim() != 2 or c.shape[1] != index.dim:
             raise ValueError(f"centroids must be [n_lists, {index.dim}], got {tuple(c.shape)}")
-        c = c.to(device=self.device, dtype=torch.float32).contiguous()
+        self.centroids = c.to(device=self.device, dtype=torch.float32).contiguous().clone()  # kept for rebuild()
+        self._h = None
+        self._create()
+
+    def _create(self) -> None:
         h = C.c_void_p()
         torch.cuda.synchronize(self.device)
-        _native.check(_native.lib().icrec_ivf_create(index._h, ptr(c), int(c.shape[0]), C.byref(h)), "icrec_ivf_create")
+        _native.check(_native.lib().icrec_ivf_create(self.index._h, ptr(self.centroids), int(self.centroids.shape[0]),
+                                                     C.byref(h)), "icrec_ivf_create")
         self._h = h
+
+    def rebuild(self) -> None:
+        """Destroy the IVF and create it again over the same index with the same centroids: the copy of the rows and
+        their assignment as they are after DeviceIndex.write_rows, which an IVF does not see.  A set-up call like the
+        constructor; a graph captured over the old handle must be captured again."""
+        if getattr(self, "_h", None):
+            _native.lib().icrec_ivf_destroy(self._h)
+            self._h = None
+        self._create()
 
     @property
     def n_lists(self) -> int:

@@ -1,0 +1,186 @@
+"""Recommender.update_products end to end on the GPU, in the world of test_rowset_recommender_gpu: a synthetic 2-layer
+model directory, a 700-product synthetic catalog with aisle / department facets, product sets, and a second recommender
+with an IVF index.  After five products got new texts, every kind of request answers exactly as a new recommender built
+on the edited corpus file answers it - product ids and scores; facet codes may differ, names do not."""
+from __future__ import annotations
+
+import json
+
+import pytest
+import torch
+
+from instacart_next_order_recommendation_amd import synthetic as syn
+from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
+from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, text_facets
+from instacart_next_order_recommendation_amd.search import IvfIndex
+from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+
+N = 700
+SETS = {
+    "store-1": [str(i) for i in range(1, N + 1) if i % 5 < 2],
+    "in-stock": [str(i) for i in range(1, N + 1) if i % 7 != 0],
+}
+NEW_AISLE, NEW_DEPT = "aisle 999 winter shelf", "dept novel"
+CHANGED = ["17", "256", "257", "400", "700"]
+
+
+def name_of(text):
+    return text[len("Product: "):text.rfind(". Aisle: ")]
+
+
+def make_updates(corpus):
+    """Five products: one moved to another existing aisle, one into a NEW aisle and department, one renamed, one given
+    exactly another product's text (a tie: the lower row first), one whose text stays."""
+    a17, d17 = text_facets(corpus["17"])
+    other = next(text_facets(t)[0] for t in corpus.values() if text_facets(t)[0] != a17)
+    return {
+        "17": f"Product: {name_of(corpus['17'])}. Aisle: {other}. Department: {d17}.",
+        "256": f"Product: {name_of(corpus['256'])}. Aisle: {NEW_AISLE}. Department: {NEW_DEPT}.",
+        "257": f"Product: Crimson Harvest Granola. Aisle: {text_facets(corpus['257'])[0]}. Department: {text_facets(corpus['257'])[1]}.",
+        "400": corpus["100"],
+        "700": corpus["700"],
+    }, other
+
+
+@pytest.fixture(scope="module")
+def world(tmp_path_factory, torch_cuda):
+    tmp = tmp_path_factory.mktemp("update_products")
+    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
+    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
+    corpus = syn.synthetic_catalog(N)
+    corpus_path = tmp / "processed" / "eval_corpus.json"
+    corpus_path.parent.mkdir()
+    corpus_path.write_text(json.dumps(corpus))
+    updates, moved_to = make_updates(corpus)
+    edited_path = tmp / "edited" / "eval_corpus.json"
+    edited_path.parent.mkdir()
+    edited_path.write_text(json.dumps({**corpus, **updates}))
+    queries = syn.synthetic_user_contexts(4, seed=9) + [
+        f"[+1d w0h1] {name_of(corpus['100'])}.", "[+1d w0h1] Crimson Harvest Granola.",
+        f"[+2d w3h9] {name_of(corpus['256'])}, {name_of(corpus['17'])}."]
+
+    rec = MonitoredRecommender(model_dir, corpus_path, use_index=False, product_sets=SETS)
+    ann = MonitoredRecommender(model_dir, corpus_path, use_index=False, ann_lists=8)
+    fast = rec._fast
+    assert fast is not None and rec._index.storage.endswith("filter")
+    before = [rec.recommend(q, 20) for q in queries]                                      # the graphs are captured BEFORE the write
+    before_scores = [rec.recommend(q, 20, boosts=dict.fromkeys(CHANGED + ["100"], 0.0), only_boosted=True) for q in queries]
+    pointers = (rec._index._h.value, id(rec._index))
+    rec.update_products(dict(reversed(list(updates.items()))))                            # (any order)
+    ann.update_products(updates)
+    assert rec._fast_path() is fast and (rec._index._h.value, id(rec._index)) == pointers
+    fresh = MonitoredRecommender(model_dir, edited_path, use_index=False, product_sets=SETS)
+    return {"rec": rec, "ann": ann, "fresh": fresh, "queries": queries, "updates": updates, "corpus": corpus,
+            "before": before, "before_scores": before_scores, "moved_to": moved_to, "model_dir": model_dir}
+
+
+def test_host_state_follows(world):
+    rec, fresh, updates = world["rec"], world["fresh"], world["updates"]
+    assert rec.product_texts == fresh.product_texts and rec.pid_to_text == fresh.pid_to_text
+    assert rec.product_embeddings.tobytes() == fresh.product_embeddings.tobytes()
+    assert rec.aisles[-1] == NEW_AISLE and rec.departments[-1] == NEW_DEPT
+    assert set(fresh.aisles) <= set(rec.aisles) and set(fresh.departments) <= set(rec.departments)
+    assert (rec._index.export() == fresh._index.export()).all()
+    for got, want in zip(rec._index.export_filter(), fresh._index.export_filter()):
+        assert (got.view(torch.int16) == want.view(torch.int16)).all()
+    assert rec.pid_to_text["400"] == world["corpus"]["100"] and rec.pid_to_text["17"] == updates["17"]
+
+
+def test_graph_path_and_batches_answer_from_the_new_rows(world, monkeypatch):
+    rec, fresh, queries = world["rec"], world["fresh"], world["queries"]
+    fast = rec._fast_path()
+    calls = []
+    real_run = type(fast).run
+
+    def run(self, *a, **kw):
+        calls.append(self)
+        return real_run(self, *a, **kw)
+
+    monkeypatch.setattr(type(fast), "run", run)
+    got = [rec.recommend(q, 20) for q in queries]
+    assert calls and all(c is fast for c in calls)                                        # the graphs captured before the write
+    assert got == [fresh.recommend(q, 20) for q in queries]
+    assert rec.recommend_batch(queries, 20) == fresh.recommend_batch(queries, 20) == got
+    excl = [{p for p, _ in g[:3]} for g in got]
+    assert rec.recommend_batch(queries, 20, excl) == fresh.recommend_batch(queries, 20, excl)
+    for q, was in zip(queries, world["before_scores"]):
+        # the changed products' own scores: the new texts', and product 400 now carries product 100's text - equal
+        # scores, the lower row first
+        now = rec.recommend(q, 20, boosts=dict.fromkeys(CHANGED + ["100"], 0.0), only_boosted=True)
+        assert now == fresh.recommend(q, 20, boosts=dict.fromkeys(CHANGED + ["100"], 0.0), only_boosted=True)
+        s = dict(now)
+        assert s["100"] == s["400"] and [p for p, _ in now].index("100") + 1 == [p for p, _ in now].index("400")
+        assert s["700"] == dict(was)["700"] and s["100"] == dict(was)["100"]              # unchanged texts, unchanged scores
+        assert all(s[p] != dict(was)[p] for p in ("17", "256", "257", "400"))
+
+
+def test_facets_sets_boosts_caps_and_diversity(world):
+    rec, fresh, queries = world["rec"], world["fresh"], world["queries"]
+    for q in queries[3:]:
+        new = rec.recommend(q, 20, aisles=[NEW_AISLE])
+        assert new == fresh.recommend(q, 20, aisles=[NEW_AISLE]) and [p for p, _ in new] == ["256"]
+        a = [world["moved_to"], NEW_AISLE, rec.aisles[0]]
+        got = rec.recommend(q, 20, aisles=a)
+        assert got == fresh.recommend(q, 20, aisles=a) and "17" in {p for p, _ in rec.recommend(q, 128, aisles=a[:1])}
+        old_aisle = text_facets(world["corpus"]["17"])[0]
+        assert "17" not in {p for p, _ in rec.recommend(q, 128, aisles=[old_aisle])}
+        d = [NEW_DEPT, rec.departments[1]]
+        assert rec.recommend(q, 20, departments=d) == fresh.recommend(q, 20, departments=d)
+        assert rec.recommend(q, 20, departments=[NEW_DEPT]) == fresh.recommend(q, 20, departments=[NEW_DEPT])
+        for w in ("store-1", ["store-1", "in-stock"]):
+            assert rec.recommend(q, 20, within=w) == fresh.recommend(q, 20, within=w)
+        boosts = {"256": 0.5, "400": 0.25, "17": 1.0, "3": 0.1}
+        assert rec.recommend(q, 20, boosts=boosts) == fresh.recommend(q, 20, boosts=boosts)
+        assert rec.recommend(q, 20, boosts=boosts, only_boosted=True) == fresh.recommend(q, 20, boosts=boosts, only_boosted=True)
+        assert rec.recommend(q, 20, max_per_aisle=1) == fresh.recommend(q, 20, max_per_aisle=1)
+        assert rec.recommend(q, 20, max_per_aisle=2, max_per_department=3) == \
+            fresh.recommend(q, 20, max_per_aisle=2, max_per_department=3)
+        assert rec.recommend(q, 10, diversity=0.4) == fresh.recommend(q, 10, diversity=0.4)
+    a = [[NEW_AISLE], None, [world["moved_to"]]]
+    assert rec.recommend_batch(queries[:3], 20, aisles=a) == fresh.recommend_batch(queries[:3], 20, aisles=a)
+
+
+def test_probes_after_the_ivf_was_built_again(world):
+    ann, fresh, queries = world["ann"], world["fresh"], world["queries"]
+    assert ann._ann is not None and ann._ann.n_lists == 8
+    fresh._ann = IvfIndex(fresh._index, ann._ann.centroids)                               # the updated recommender's centroids
+    try:
+        for q in queries:
+            exact = fresh.recommend(q, 20)
+            assert ann.recommend(q, 20) == exact
+            assert ann.recommend(q, 20, probes=8) == exact
+            assert ann.recommend(q, 20, probes=2) == fresh.recommend(q, 20, probes=2)
+            assert ann.recommend(q, 10, probes=2, diversity=0.3) == fresh.recommend(q, 10, probes=2, diversity=0.3)
+        assert ann.recommend_batch(queries, 20, probes=2) == fresh.recommend_batch(queries, 20, probes=2)
+    finally:
+        fresh._ann.close()
+        fresh._ann = None
+
+
+def test_a_bad_update_changes_nothing(world, monkeypatch):
+    rec, queries, updates = world["rec"], world["queries"], world["updates"]
+    answers = [rec.recommend(q, 20) for q in queries]
+    facets = [rec.recommend(q, 20, aisles=[NEW_AISLE, world["moved_to"]]) for q in queries]
+    texts, aisles = list(rec.product_texts), list(rec.aisles)
+    stored = rec._index.export().clone()
+
+    def no_gpu(*a, **kw):
+        raise AssertionError("GPU work before the argument check")
+
+    monkeypatch.setattr(type(rec._index), "write_rows", no_gpu)
+    monkeypatch.setattr(type(rec.model), "encode", no_gpu)
+    good = "Product: Plain Oats. Aisle: one more new aisle. Department: dept novel."
+    with pytest.raises(ValueError, match="unknown product id"):
+        rec.update_products({"5": good, "no such product": good})
+    with pytest.raises(ValueError, match="format"):
+        rec.update_products({"5": good, "6": "Plain oats, 500 g"})
+    rec.update_products({})                                                               # nothing to do: no GPU work either
+    monkeypatch.undo()
+    assert rec.product_texts == texts and rec.aisles == aisles
+    assert (rec._index.export() == stored).all()
+    assert [rec.recommend(q, 20) for q in queries] == answers
+    assert [rec.recommend(q, 20, aisles=[NEW_AISLE, world["moved_to"]]) for q in queries] == facets
+    with pytest.raises(ValueError, match="unknown aisle"):
+        rec.recommend(queries[0], 20, aisles=["one more new aisle"])
