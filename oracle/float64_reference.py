@@ -18,10 +18,11 @@ The weights are the fp32 blob (include/icrec.h order, split with synthetic.blob_
 
 `fault=(name, layer)` makes ONE stage of ONE layer wrong on purpose.  The faults exist only here: tests use them to
 prove that a per-token comparison against this reference would notice the mistakes a kernel rewrite can make
-(tests/test_token_states.py).  FAULTS lists the names.
+(tests/test_token_states.py, tests/test_value_ranges.py).  FAULTS and RANGE_FAULTS list the names.
 """
 from __future__ import annotations
 
+import collections
 import math
 from typing import Optional
 
@@ -41,6 +42,20 @@ FAULTS = {
     "zero_head_last_row": "head 0's context of each sequence's last token is zero",
     "ln_eps_1e-5": "both LayerNorms of the layer use eps 1e-5 instead of the shape's",
 }
+
+#: faults of the GELU's value range: what a clamp, a dropped tail or a poor fit of the kernels' erfc polynomial does.
+#: Two of them change nothing while |u| <= 3 (every pre-GELU value of the "standard" and "sharp" weight sets), so they
+#: stand beside FAULTS, whose entries tests/test_token_states.py requires on those sets, and are asserted where the
+#: inputs reach them: the "heavy" set and the GELU probes (tests/test_value_ranges.py).  `fault=` accepts both tables.
+RANGE_FAULTS = {
+    "gelu_tail_dropped": "gelu(u) = max(u, 0) wherever |u| > 3 (the erfc term dropped outside the middle)",
+    "gelu_clamp_4": "the erfc argument is clamped at 4: gelu(u) = max(u, 0) - |u|/2 erfc(min(|u|, 4) / sqrt 2)",
+    "gelu_erfc_rel_1e-3": "the erfc term is 1.001 times too large (a poor polynomial fit)",
+}
+
+#: what `stats` receives per layer
+LayerStats = collections.namedtuple(
+    "LayerStats", "logit_std mean_max_softmax share_u_gt_3 share_u_gt_5_75 max_abs_u")
 
 #: how a linear layer adds its K products (Float64Bert's `linears`)
 LINEARS = ("blas", "single_accumulator")
@@ -98,13 +113,14 @@ class Float64Bert:
 
     @torch.no_grad()
     def encode(self, ids: np.ndarray, cu: np.ndarray, fault: Optional[tuple] = None, stats: Optional[list] = None):
-        """ids int[T], cu int[n+1] (packed sequences).  `stats`, when a list, receives per layer
-        (std of the pre-softmax logits, mean over rows of the largest softmax weight)."""
+        """ids int[T], cu int[n+1] (packed sequences).  `stats`, when a list, receives one LayerStats per layer: std of
+        the pre-softmax logits, mean over rows of the largest softmax weight, the shares of the pre-GELU values u with
+        |u| > 3 and with |u| > 5.75, and the largest |u|."""
         s, p = self.shape, self.p
         H, nh = s.hidden, s.heads
         d = H // nh
         fname, flayer = fault if fault is not None else (None, -1)
-        if fname is not None and fname not in FAULTS:
+        if fname is not None and fname not in FAULTS and fname not in RANGE_FAULTS:
             raise ValueError(f"unknown fault {fname!r}")
         ids_t = torch.from_numpy(np.asarray(ids, np.int64))
         cu = np.asarray(cu, np.int64)
@@ -147,13 +163,21 @@ class Float64Bert:
                 if f == "stale_last_row" and n > 1:
                     c[n - 1] = c[n - 2]
                 ctx[a:b] = c
-            if stats is not None:
-                m = logit_sum / logit_n
-                stats.append((math.sqrt(max(logit_sq / logit_n - m * m, 0.0)), pmax_sum / pmax_n))
             x = self._ln(self._linear(ctx, q + "attention.output.dense") + x, q + "attention.output.LayerNorm", eps)
             u = self._linear(x, q + "intermediate.dense")
+            if stats is not None:
+                m, au = logit_sum / logit_n, u.abs()
+                stats.append(LayerStats(math.sqrt(max(logit_sq / logit_n - m * m, 0.0)), pmax_sum / pmax_n,
+                                        float((au > 3.0).double().mean()), float((au > 5.75).double().mean()),
+                                        float(au.max())))
             if f == "tanh_gelu":
                 g = 0.5 * u * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (u + 0.044715 * u ** 3)))
+            elif f in ("gelu_clamp_4", "gelu_erfc_rel_1e-3"):  # gelu(u) = max(u, 0) - |u|/2 erfc(|u| / sqrt 2)
+                t = u.abs().clamp(max=4.0) if f == "gelu_clamp_4" else u.abs()
+                erfc = (1.001 if f == "gelu_erfc_rel_1e-3" else 1.0) * torch.erfc(t / math.sqrt(2.0))
+                g = u.clamp(min=0.0) - 0.5 * u.abs() * erfc
+            elif f == "gelu_tail_dropped":
+                g = torch.where(u.abs() > 3.0, u.clamp(min=0.0), 0.5 * u * (1.0 + torch.erf(u / math.sqrt(2.0))))
             else:
                 g = 0.5 * u * (1.0 + torch.erf(u / math.sqrt(2.0)))
             if f == "gelu_f16":

@@ -23,9 +23,9 @@ EDGE_LENS = [1, 2, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129, 159, 160, 
 MIXED_LENS = [5, 33, 128, 256, 1, 2, 64, 97]
 
 
-def _check(what, mode, r, emb, tok, first_seq=0, n_seqs=None):
+def _check(what, mode, r, emb, tok, first_seq=0, n_seqs=None, margin=None):
     """tok (sequences [first_seq, first_seq + n_seqs) of r's batch; all by default) against the float64 hidden states
-    within margin x E_ref, and tok mean-pooled in float64 against emb."""
+    within margin x E_ref (MARGINS' entry unless `margin` is given), and tok mean-pooled in float64 against emb."""
     s, kind = r["s"], r["kind"]
     n_seqs = r["cu"].size - 1 - first_seq if n_seqs is None else n_seqs
     cu = r["cu"][first_seq: first_seq + n_seqs + 1].astype(np.int64)
@@ -34,7 +34,7 @@ def _check(what, mode, r, emb, tok, first_seq=0, n_seqs=None):
     cu = cu - cu[0]
     assert tok.shape == want.shape and tok.dtype == np.float32 and np.isfinite(tok).all()
     ts.check(f"token states [{what}] mode={mode} hidden={s.hidden} layers={s.layers} weights={kind} tokens={tok.shape[0]}",
-             tok, want, ora, ts.MARGINS[(mode, s.hidden, kind)], cu)
+             tok, want, ora, ts.MARGINS[(mode, s.hidden, kind)] if margin is None else margin, cu)
     # The embedding of the same call is the mean of these rows, normalised.  fp32 pooling sums n rows one after the
     # other: |error of the mean| <= n u mean|h| (u = 2^-24); the two normalisations (fmaf chain of H / 64, a 6-step
     # butterfly, sqrt, divide) cost at most 32 more roundings of a component that is <= 1.

@@ -7,6 +7,9 @@ of an fp32 implementation against the float64 reference ON THE SAME INPUTS under
 fp32 C oracle, or, where a case has an attention bias (the oracle knows none), the reference's own code in float32 -
 and the margin comes from MARGINS (chosen from the ratios measured on the MI355X, profiles/token_state_errors.md) or,
 with a bias, TOKEN_MARGINS / EMB_MARGINS (profiles/attention_bias_errors.md).
+
+The value-range tests (tests/test_value_ranges.py, tests/test_value_ranges_gpu.py) add the "heavy" weight set and the
+pointwise GELU probes, with RANGE_MARGINS; they stand beside KINDS and the tables above, not in them.
 """
 from __future__ import annotations
 
@@ -23,6 +26,41 @@ KINDS = ("standard", "sharp")
 #: reference's pre-softmax logits have a standard deviation >= 2 in EVERY layer on `calibration_batch()`; found by
 #: `find_qk_scale` (tests/test_token_states.py re-runs the search and checks the statistics).
 SHARP_QK_SCALE = {(384, 6): 4.0, (384, 2): 4.0, (384, 1): 2.0 ** 1.75, (768, 2): 2.0 ** 1.5}
+
+#: The weight sets and probe models of the value-range tests (tests/test_value_ranges.py, tests/test_value_ranges_gpu.py);
+#: kept out of KINDS, which indexes the margin tables of the bias and CLS tests.
+RANGE_KINDS = ("heavy",)
+
+#: What the "heavy" set meets in EVERY layer on `calibration_batch()`: share of pre-GELU values with |u| > 3, share with
+#: |u| > 5.75 (where the f16x3 GELU clamps its polynomial's argument), mean over rows of the largest softmax weight.
+#: HEAVY_AIMS is what the search asks for, 5 % inside, so that the assertions never sit on a rounding edge;
+#: HEAVY_LIMITS (largest |u|, logit std) keep the set in a trained model's range and far from plane saturation.
+HEAVY_THRESHOLDS = (0.20, 0.02, 0.90)
+HEAVY_AIMS = (0.21, 0.021, 0.92)
+HEAVY_LIMITS = (64.0, 128.0)
+
+#: (factor on Wq and Wk, factor on every intermediate.dense.weight) of the "heavy" set, per (hidden, layers); found by
+#: `find_heavy_scales` (tests/test_value_ranges.py re-runs the search and checks the conditions).
+HEAVY_SCALES = {(384, 6): (16.0, 2.0 ** 2.75), (384, 2): (2.0 ** 3.75, 2.0 ** 2.5), (384, 1): (2.0 ** 3.75, 2.0 ** 2.5),
+                (768, 2): (2.0 ** 3.25, 4.0)}
+
+#: margin on E_ref per (gemm mode, hidden, "heavy" | "probe"): (per-token-row rms, max abs).  Each is the smallest of
+#: {2, 3, 4, 6, 8, 12, 16} that leaves 1.5x headroom over the worst ratio E_gpu / E_ref measured on the MI355X over every
+#: case of tests/test_value_ranges_gpu.py (profiles/token_state_errors.md, "Value ranges", holds the ratios).  The set
+#: reaches 16 because, where one term dominates a sum (one-hot P.V, the probes' single-weight GEMM), the planes'
+#: 2^-21 relative split error stands a factor 8 above fp32's 2^-24.
+RANGE_MARGINS = {
+    ("f32", 384, "heavy"): (2, 2), ("f32", 384, "probe"): (2, 2),
+    ("f32", 768, "heavy"): (2, 2), ("f32", 768, "probe"): (2, 2),
+    ("f16x3", 384, "heavy"): (2, 2), ("f16x3", 384, "probe"): (4, 6),
+    ("f16x3", 768, "heavy"): (2, 3), ("f16x3", 768, "probe"): (3, 6),
+}
+
+
+def range_margin(mode: str, hidden: int, kind: str):
+    """RANGE_MARGINS' entry of a weight set of the value-range tests: every probe model shares "probe"."""
+    return RANGE_MARGINS[(mode, hidden, "probe" if kind in PROBE_KINDS else kind)]
+
 
 #: margin on E_ref per (gemm mode, hidden, weight set): (per-token-row rms, max abs).  Each is the smallest of
 #: {2, 3, 4, 6, 8} that leaves 1.5x headroom over the worst ratio E_gpu / E_ref measured on the MI355X over every case
@@ -61,7 +99,8 @@ def shape(hidden: int, layers: int) -> syn.BertShape:
     return syn.BertShape(vocab_size=VOCAB, layers=layers, **WIDTHS[hidden])
 
 
-def weights(kind: str, s: syn.BertShape, seed: int = 17, qk_scale: float | None = None) -> np.ndarray:
+def weights(kind: str, s: syn.BertShape, seed: int = 17, qk_scale: float | None = None,
+            w1_scale: float | None = None) -> np.ndarray:
     """The weight blob of a set.
 
     "standard": synthetic_bert_weights at BERT's init, std 0.02 (logits are tiny, softmax is nearly uniform).
@@ -69,17 +108,52 @@ def weights(kind: str, s: syn.BertShape, seed: int = 17, qk_scale: float | None 
                 with 6 or 2 layers, 3.36 with 1 layer, 2.83 at hidden 768 with 2 layers; logit std 3.1 - 4.1 per layer
                 against 0.15 for "standard", the largest softmax weight of a row averages 0.32 - 0.41 against 0.012:
                 attention is peaked, not one-hot), every LayerNorm gain replaced by 2^u with u uniform in
-                [-1, 1] (gains over [0.5, 2]), biases left as generated (non-zero)."""
+                [-1, 1] (gains over [0.5, 2]), biases left as generated (non-zero).
+    "heavy":    "sharp" with the larger Q/K factor of HEAVY_SCALES and its factor on every intermediate.dense.weight
+                (found by find_heavy_scales: 16 and 6.73 at hidden 384 with 6 layers, 13.5 and 5.66 with 2 or 1, 9.51
+                and 4 at hidden 768): the range of a trained checkpoint - per layer the largest softmax weight of a
+                row averages 0.93 - 0.96 (logit std 35 - 59), 24 - 34 % of the pre-GELU values lie beyond |u| = 3 and
+                2.3 - 6.5 % beyond 5.75, the largest is 12 - 16.
+    "probe0" ... "probe3", "probe_large" (one layer): "standard" with the FFN turned into a function evaluator -
+                intermediate.dense.weight = 0 and its bias = probe_sweep(kind), so that every token's pre-GELU vector
+                IS the sweep (the accumulator is 0 in either GEMM mode); output.dense.weight[f, f + hidden c] = 1 (exact
+                in the weight planes) and 0 elsewhere, c = probe_chunk(kind), output.dense.bias = 0: the block's output
+                is LN(gelu(sweep[f + hidden c]) + x[f]) per token."""
     w = syn.synthetic_bert_weights(s, seed=seed, std=0.02)
     if kind == "standard":
         return w
-    assert kind == "sharp", kind
-    scale = float(qk_scale if qk_scale is not None else SHARP_QK_SCALE[(s.hidden, s.layers)])
+    if kind in PROBE_KINDS:
+        assert s.layers == 1, "the GELU probes are one-layer models"
+        sd = syn.blob_to_state_dict(w, s)  # views into w
+        sd["encoder.layer.0.intermediate.dense.weight"][:] = 0.0
+        sd["encoder.layer.0.intermediate.dense.bias"][:] = probe_sweep(kind, s)
+        w2 = sd["encoder.layer.0.output.dense.weight"]  # [hidden, intermediate]
+        w2[:] = 0.0
+        f = np.arange(s.hidden)
+        w2[f, f + s.hidden * probe_chunk(kind)] = 1.0
+        sd["encoder.layer.0.output.dense.bias"][:] = 0.0
+        return w
+    assert kind == "sharp" or kind in RANGE_KINDS, kind
+    if kind == "heavy":
+        heavy = HEAVY_SCALES.get((s.hidden, s.layers), (None, None))
+        scale = float(qk_scale if qk_scale is not None else heavy[0])
+        w1_scale = float(w1_scale if w1_scale is not None else heavy[1])
+    else:
+        assert w1_scale is None
+        scale = float(qk_scale if qk_scale is not None else SHARP_QK_SCALE[(s.hidden, s.layers)])
     for t, (name, a) in enumerate(syn.blob_to_state_dict(w, s).items()):  # views into w
-        if name.endswith(("query.weight", "key.weight")):
-            a *= np.float32(scale)
-        elif name.endswith("LayerNorm.weight"):
+        if name.endswith("LayerNorm.weight"):
             a[:] = np.exp2(2.0 * syn.uniform(seed + 1, t, a.size) - 1.0).astype(np.float32)
+    return _scale_qk_w1(w, s, scale, w1_scale if kind == "heavy" else 1.0)
+
+
+def _scale_qk_w1(w: np.ndarray, s: syn.BertShape, qk_scale: float, w1_scale: float) -> np.ndarray:
+    """Wq and Wk times qk_scale, every intermediate.dense.weight times w1_scale, in place."""
+    for name, a in syn.blob_to_state_dict(w, s).items():  # views into w
+        if name.endswith(("query.weight", "key.weight")):
+            a *= np.float32(qk_scale)
+        elif name.endswith("intermediate.dense.weight") and w1_scale != 1.0:
+            a *= np.float32(w1_scale)
     return w
 
 
@@ -90,11 +164,83 @@ def calibration_batch():
 
 def logit_stats(w: np.ndarray, s: syn.BertShape, ids, cu):
     """Per layer (std of the pre-softmax logits, mean largest softmax weight of a row) in the float64 reference."""
+    return [(st.logit_std, st.mean_max_softmax) for st in layer_stats(w, s, ids, cu)]
+
+
+def layer_stats(w: np.ndarray, s: syn.BertShape, ids, cu):
+    """Per layer the float64 reference's LayerStats: logit std, mean largest softmax weight of a row, the shares of
+    pre-GELU values with |u| > 3 and with |u| > 5.75, the largest |u|."""
     from oracle import float64_reference as f64
 
     stats: list = []
     f64.encode(w, s, ids, cu, stats=stats)
     return stats
+
+
+def heavy_conditions(stats, aim: bool = False) -> dict:
+    """What the "heavy" set must meet in EVERY layer, as name -> bool: HEAVY_THRESHOLDS (with `aim`, HEAVY_AIMS: what
+    the search asks for, 5 % inside) and HEAVY_LIMITS."""
+    u3, u575, pmax = HEAVY_AIMS if aim else HEAVY_THRESHOLDS
+    max_u, max_std = HEAVY_LIMITS
+    return {"share |u| > 3": min(st.share_u_gt_3 for st in stats) >= u3,
+            "share |u| > 5.75": min(st.share_u_gt_5_75 for st in stats) >= u575,
+            "mean max softmax weight": min(st.mean_max_softmax for st in stats) >= pmax,
+            "largest |u|": max(st.max_abs_u for st in stats) < max_u,
+            "logit std": max(st.logit_std for st in stats) < max_std}
+
+
+def find_heavy_scales(s: syn.BertShape, seed: int = 17):
+    """(Q/K factor, W1 factor) of the "heavy" set, each the smallest 2^(k/4), k = 0, 1, ..., on calibration_batch(),
+    the Q/K factor first: one under which every layer's largest softmax weight of a row averages HEAVY_AIMS' 0.92 with
+    the W1 factor still 1; then, with that Q/K factor in place, the smallest W1 factor that brings every layer's shares
+    of |u| > 3 and > 5.75 to their aims.  A larger FFN output is a less peaked next layer (at 6 layers the W1 factor
+    that the shares need takes the last layer's softmax weight from 0.94 to below 0.90), so the pair counts only if
+    every layer then meets ALL of heavy_conditions(aim=True); if not, the next Q/K factor is tried."""
+    ids, cu = calibration_batch()
+    base = weights("heavy", s, seed, qk_scale=1.0, w1_scale=1.0)  # generated once: a factor of 1 changes no bit
+
+    def conditions(qk, w1):
+        return heavy_conditions(layer_stats(_scale_qk_w1(base.copy(), s, qk, w1), s, ids, cu), aim=True)
+
+    for qk in (float(2.0 ** (k / 4)) for k in range(0, 33)):
+        if not conditions(qk, 1.0)["mean max softmax weight"]:
+            continue
+        for w1 in (float(2.0 ** (k / 4)) for k in range(0, 33)):
+            c = conditions(qk, w1)
+            if c["share |u| > 3"] and c["share |u| > 5.75"]:  # both grow with the W1 factor
+                if all(c.values()):
+                    return qk, w1
+                break
+    raise AssertionError("no Q/K and W1 factors up to 256 meet the heavy set's conditions")
+
+
+#: the FFN values of the pointwise GELU probes (`probe_sweep`), beside a grid over [-8, 8]: signed zeros, values whose
+#: square underflows, the faults' |u| = 3, the kernel's clamp 5.75 and its fp32 neighbours on both sides
+PROBE_SPECIALS = [sg * v for v in (0.0, 1e-30, 1e-8, 3.0, float(np.nextafter(np.float32(5.75), np.float32(0))), 5.75,
+                                   float(np.nextafter(np.float32(5.75), np.float32(8)))) for sg in (1.0, -1.0)]
+#: the values of the large-value probe
+PROBE_LARGE = [10.0, -10.0, 30.0, -30.0, 100.0, -100.0]
+#: the probe models: chunk c of the sweep (PROBE_KINDS[c], c < 4) and the large-value probe
+PROBE_KINDS = ("probe0", "probe1", "probe2", "probe3", "probe_large")
+
+
+def probe_sweep(kind: str, s: syn.BertShape) -> np.ndarray:
+    """The pre-GELU vector (float32 [intermediate]) every token of a probe model has.  "probe0" ... "probe3": the
+    PROBE_SPECIALS and an even grid over [-8, 8], shuffled with a fixed seed so that neighbours on the grid land in
+    different chunks of `hidden` values.  "probe_large": the PROBE_LARGE values at the head of a shuffled even grid
+    over [-1, 1] - a probe of their own, because a row with a 100 in it has a standard deviation of 4 - 5, by which
+    its LayerNorm would scale every other element's error down."""
+    rng = np.random.default_rng(29)
+    if kind == "probe_large":
+        return np.concatenate([PROBE_LARGE, rng.permutation(np.linspace(-1.0, 1.0, s.intermediate - len(PROBE_LARGE)))]
+                              ).astype(np.float32)
+    grid = np.linspace(-8.0, 8.0, s.intermediate - len(PROBE_SPECIALS))
+    return rng.permutation(np.concatenate([PROBE_SPECIALS, grid])).astype(np.float32)
+
+
+def probe_chunk(kind: str) -> int:
+    """Which `hidden` values of the sweep a probe model's FFN-down projection passes on."""
+    return 0 if kind == "probe_large" else PROBE_KINDS.index(kind)
 
 
 def find_qk_scale(s: syn.BertShape, seed: int = 17) -> float:
