@@ -370,6 +370,63 @@ ICREC_API int icrec_index_export_filter(const icrec_index* idx, uint16_t* hi_dev
 ICREC_API int icrec_index_write_rows(icrec_index* idx, const float* rows_dev, const int32_t* row_ids_dev,
                                      int32_t m, void* stream);
 
+/* Add and remove rows in place: a catalog gains and loses products every day, and the handle - with its facets, its row
+ * sets and everything its users captured or uploaded - lives on.
+ *
+ * Capacity.  Every array of a handle (the rows, the hi/lo planes or the packed fragments, the facet words, the row set
+ * bitmaps) is sized for `capacity` rows, of which the first n_rows exist; icrec_index_create_ex makes capacity ==
+ * n_rows.  The fragments hold whole 256-row rounds of the capacity, the facet words whole 256-row tiles of it, and one
+ * row set takes ceil(capacity / 256) * 8 words on the device; bits_host of icrec_index_set_rowsets and
+ * icrec_index_write_rowset stays ceil(n_rows / 32) words per set.  What a fresh index keeps zero behind its last row
+ * stays zero after every call below: the fragment lane slots, the facet words and the row set bits of rows >= n_rows.
+ * The stored rows and the planes past n_rows are unspecified; nothing addresses them.  So after any sequence of these
+ * calls the handle searches, exports and ranks, bit for bit, as the handle icrec_index_create_ex builds from the
+ * resulting matrix (with the resulting facets and sets) does.
+ *
+ * Contract of icrec_index_reserve, icrec_index_append_rows and icrec_index_remove_rows:
+ *   - they are set-up calls: never while a search (or any other call) on the handle runs;
+ *   - after the host-side checks, append and remove are asynchronous on `stream` and ordered like other work on it
+ *     (they may allocate a staging block the first time, and wait for their own previous copy out of it); reserve
+ *     allocates, synchronises the device and returns when the copy is done;
+ *   - n_rows is a launch argument of every search kernel, so UNLIKE icrec_index_write_rows: a graph captured before
+ *     any of the three calls is INVALID afterwards and must be captured again (reserve changes every pointer as well);
+ *     workspace sizes depend on n_rows and are asked for again;
+ *   - an icrec_ivf over the handle owns a copy of the rows in list order: destroy it and create it again;
+ *   - they work on the LOCAL rows of any handle, whatever its row_offset; keeping the shards of a sharded search
+ *     consistent is the caller's business. */
+/* Rows the handle's arrays are sized for (0: NULL handle). */
+ICREC_API int64_t icrec_index_capacity(const icrec_index* idx);
+/* Re-allocate every array of the handle for `capacity` rows (n_rows <= capacity, row_offset + capacity < 2^32 - 1; it
+ * may shrink down to n_rows), copy the live contents device to device and free the old arrays.  The storage form (planes
+ * or fragments) was chosen at creation and stays.  ICREC_EINVAL for a capacity out of range; ICREC_ENOMEM when an
+ * allocation fails - the handle is then unchanged.  capacity == icrec_index_capacity(idx) does nothing. */
+ICREC_API int icrec_index_reserve(icrec_index* idx, int64_t capacity);
+/* Append m rows: they become rows n_rows .. n_rows + m - 1, normalised and stored exactly as icrec_index_create_ex would
+ * store them (icrec_index_write_rows' kernel and arithmetic, lane for lane), with their filter copy.
+ *   rows_dev     float[m, dim]             the new rows in DEVICE memory, of any norm
+ *   facets_host  uint8[m, n_facets]        HOST pointer, required exactly when the index has facets (copied before
+ *                                          the call returns)
+ * The new rows are members of no row set (icrec_index_write_rowset makes them members).  n_rows grows on the host when
+ * the call is made.  m == 0 returns ICREC_OK and does nothing.  ICREC_EINVAL, changing nothing: a NULL idx, m < 0, NULL
+ * rows_dev, n_rows + m > capacity (reserve first), facets_host missing or unexpected. */
+ICREC_API int icrec_index_append_rows(icrec_index* idx, const float* rows_dev, int32_t m, const uint8_t* facets_host,
+                                      void* stream);
+/* Remove m rows by swapping from the tail: O(m) work, whatever n_rows is.
+ *   row_ids_host  int32[m]  HOST pointer: LOCAL rows, ascending and unique, inside [0, n_rows); m < n_rows
+ *   dst_out, src_out  int32[m]  HOST arrays that receive the move plan;  n_moves_out  int32*  its length
+ * The plan.  new_n = n_rows - m.  The holes are the removed ids below new_n, ascending; the fillers are the surviving
+ * rows at or past new_n, ascending; there are as many of one as of the other, and filler i moves into hole i:
+ * row src_out[i] becomes row dst_out[i], for i < *n_moves_out (<= m).  Every other surviving row keeps its number.
+ * Afterwards the handle is bit for bit the one built from the matrix with those moves applied and cut to new_n rows: a
+ * move copies the STORED bits of the row (no second normalisation), its entries of the planes or its lane slots of the
+ * fragments, its facet word and its bit of every row set; then the fragment slots, facet words and row set bits of the
+ * rows [new_n, old n_rows) are cleared, in a second launch behind the moves.  The caller applies the plan to whatever it
+ * keeps per row (ids, texts, memberships).  n_rows shrinks on the host when the call is made.
+ * m == 0 returns ICREC_OK with *n_moves_out = 0.  ICREC_EINVAL, changing nothing: a NULL argument, m < 0, m >= n_rows, an
+ * id outside [0, n_rows), ids that are not ascending and unique. */
+ICREC_API int icrec_index_remove_rows(icrec_index* idx, const int32_t* row_ids_host, int32_t m, int32_t* dst_out,
+                                      int32_t* src_out, int32_t* n_moves_out, void* stream);
+
 ICREC_API size_t icrec_search_workspace_bytes(const icrec_index* idx, int32_t n_queries,
                                     int32_t k);
 
@@ -679,12 +736,13 @@ typedef struct icrec_ivf icrec_ivf;
  * n_lists > n_rows, a base of 2^31 rows or more.  A set-up call like icrec_index_set_facets: it allocates (the
  * gathered rows: as many bytes as the base's rows), synchronises, assigns the rows in passes over slices of them, sorts
  * on the host, and must never be issued while a call on the base index is running.
- * The IVF owns its copy of the rows and their assignment: it does not see icrec_index_write_rows on the base.  After a
- * write, destroy it and create it again from the same centroids. */
+ * The IVF owns its copy of the rows and their assignment: it does not see icrec_index_write_rows, _append_rows or
+ * _remove_rows on the base.  After any of them, destroy it and create it again from the same centroids; until then it
+ * answers from the rows (and row numbers) the base had when it was built. */
 ICREC_API int icrec_ivf_create(icrec_index* base, const float* centroids_dev, int32_t n_lists, icrec_ivf** out);
 ICREC_API int icrec_ivf_destroy(icrec_ivf* ivf);
 ICREC_API int32_t icrec_ivf_lists(const icrec_ivf* ivf);                      /* n_lists; -1 for NULL */
-/* perm_dev int32[n_rows] and list_off_dev int64[n_lists + 1] (device memory) <- the layout; asynchronous on `stream`. */
+/* n_rows = the base's rows when the IVF was built.  perm_dev int32[n_rows] and list_off_dev int64[n_lists + 1] (device memory) <- the layout; asynchronous on `stream`. */
 ICREC_API int icrec_ivf_layout(const icrec_ivf* ivf, int32_t* perm_dev, int64_t* list_off_dev, void* stream);
 /* Scratch bytes of icrec_ivf_search (0 for a bad argument). */
 ICREC_API size_t icrec_ivf_search_workspace_bytes(const icrec_ivf* ivf, int32_t n_queries, int32_t k, int32_t nprobe);

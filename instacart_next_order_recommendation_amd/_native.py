@@ -38,6 +38,7 @@ EXPORTS = [
     "icrec_index_create", "icrec_index_create_ex", "icrec_index_destroy", "icrec_index_rows", "icrec_index_storage",
     "icrec_index_export", "icrec_index_dim", "icrec_index_device",
     "icrec_index_write_rows", "icrec_index_write_facets", "icrec_index_export_filter",
+    "icrec_index_capacity", "icrec_index_reserve", "icrec_index_append_rows", "icrec_index_remove_rows",
     "icrec_comm_unique_id", "icrec_comm_init", "icrec_comm_destroy", "icrec_comm_rank", "icrec_comm_world",
     "icrec_search_sharded_workspace_bytes", "icrec_search_sharded",
     "icrec_search_sharded_excl_workspace_bytes", "icrec_search_sharded_excl", "icrec_index_row_offset",
@@ -150,6 +151,10 @@ def lib() -> C.CDLL:
         "icrec_index_write_rows": (C.c_int, [vp, vp, vp, i32, vp]),
         "icrec_index_write_facets": (C.c_int, [vp, vp, vp, i32]),
         "icrec_index_export_filter": (C.c_int, [vp, vp, vp, vp]),
+        "icrec_index_capacity": (i64, [vp]),
+        "icrec_index_reserve": (C.c_int, [vp, i64]),
+        "icrec_index_append_rows": (C.c_int, [vp, vp, i32, vp, vp]),
+        "icrec_index_remove_rows": (C.c_int, [vp, vp, i32, vp, vp, vp, vp]),
         "icrec_search_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_search": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
         "icrec_search_partial": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),

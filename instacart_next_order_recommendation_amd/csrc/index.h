@@ -19,18 +19,25 @@ struct Index {
     int64_t frag_row_tiles = 0;    // 32-row tiles in `frag` (whole rounds of CfgRes::BM rows)
     int storage = ICREC_ROWS_F32;
     int64_t n_rows = 0;
+    int64_t capacity = 0;          // rows every array is sized for (>= n_rows; == n_rows until icrec_index_reserve)
     int dim = 0;
     int64_t row_offset = 0;
     int device = 0;
     int n_cu = 256;
     int stream_max_q = 8;          // ICREC_STREAM_MAX_Q at creation
-    uint16_t* facets = nullptr;    // icrec_index_set_facets: one word per row, zero padded to whole 256-row tiles
+    uint16_t* facets = nullptr;    // icrec_index_set_facets: one word per row, zero padded to whole 256-row tiles of the capacity
     int n_facets = 0;
-    uint32_t* rowsets = nullptr;   // icrec_index_set_rowsets: [n_rowsets][rowset_words(n_rows)] bitmaps over the local rows
+    uint32_t* rowsets = nullptr;   // icrec_index_set_rowsets: [n_rowsets][rowset_words(capacity)] bitmaps over the local rows
     int n_rowsets = 0;
+    // icrec_index_append_rows / _remove_rows: what they copy to the device (facet words, the move plan) goes through this
+    // pinned block, so that the copy is asynchronous; stage_event marks the end of the last copy out of it
+    void* stage_host = nullptr;
+    int32_t* plan_dev = nullptr;   // [2][plan_cap]: the moves' destinations, then their sources
+    size_t stage_bytes = 0, plan_cap = 0;
+    hipEvent_t stage_event = nullptr;
 };
 
-// Words of one row set on the device: ceil(n_rows / 32) bitmap words, zero padded to whole 256-row tiles (8 words per
+// Words of one row set on the device, for an index of that capacity: ceil(n_rows / 32) bitmap words, zero padded to whole 256-row tiles (8 words per
 // tile, the widest tile any search kernel walks), as the facet words are: every tile of every kernel reads inside it.
 static inline int64_t rowset_words(int64_t n_rows) { return (n_rows + 255) / 256 * 8; }
 
@@ -49,8 +56,23 @@ int build_filter_storage(Index* ix);
 // - the stored rows and, in a *_FILTER storage, their planes or fragment slots - become what icrec_index_create_ex
 // makes of rows_dev[0 .. m), in one launch on `st`; ids outside [0, n_rows) are skipped on the device.  And for
 // icrec_index_export_filter (the handle has a filter copy): that copy as row-major f16 bits [n_rows, dim] each.
-int write_index_rows(Index* ix, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, hipStream_t st);
+// With row_ids_dev == NULL (icrec_index_append_rows) the written rows are base_row .. base_row + m - 1 instead, tested
+// against n_rows = base_row + m.
+int write_index_rows(Index* ix, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, int64_t base_row, hipStream_t st);
 int export_filter_storage(const Index* ix, uint16_t* hi_dev, uint16_t* lo_dev, hipStream_t st);
+// search.hip, for icrec_index_reserve: the handle's filter copy (planes or fragments, whichever it has) allocated for
+// `capacity` rows, the fragments zeroed, with the copy of the live rows launched on the null stream.  ICREC_ENOMEM with
+// nothing allocated; the handle is not changed.
+struct FilterStorage {
+    _Float16 *plane_hi = nullptr, *plane_lo = nullptr, *frag = nullptr;
+    int64_t frag_row_tiles = 0;
+};
+int reserve_filter_storage(const Index* ix, int64_t capacity, FilterStorage* out);
+// search.hip, for icrec_index_remove_rows (arguments checked): moves src[i] -> dst[i] of everything the index keeps per
+// row (dst, src: device arrays of n_moves entries, dst < new_n <= src < old_n), then the fragment slots, facet words and
+// row set bits of rows [new_n, old_n) cleared; two launches on `st`, the second behind the first.
+int move_index_rows(Index* ix, const int32_t* dst_dev, const int32_t* src_dev, int32_t n_moves, int64_t new_n, int64_t old_n,
+                    hipStream_t st);
 
 #ifdef __HIPCC__
 

@@ -1,7 +1,9 @@
 // index.hip — the life cycle of an icrec_index handle (index.h: struct Index): creation with row normalisation,
-// facets, row sets, rows and facets rewritten in place, export, the accessors and destruction; and icrec_normalize_rows.
+// facets, row sets, rows and facets rewritten in place, capacity reserved, rows appended and removed in place, export, the
+// accessors and destruction; and icrec_normalize_rows.
 // The filter storages' layout belongs to the kernels that read it: search.hip builds it (build_filter_storage), rewrites
-// it with the rows (write_index_rows) and un-packs it (export_filter_storage).
+// it with the rows (write_index_rows), moves and clears it with them (move_index_rows), re-allocates it
+// (reserve_filter_storage) and un-packs it (export_filter_storage).
 #include <stdlib.h>
 
 #include <new>
@@ -23,6 +25,32 @@ static int stream_max_q_from_env() {
     const char* e = getenv("ICREC_STREAM_MAX_Q");
     const int v = e ? atoi(e) : 8;
     return v > 8 ? 8 : v < 0 ? 0 : v;
+}
+
+// The index's pinned staging block, at least `bytes`, once the last asynchronous copy out of it has finished
+// (icrec_index_append_rows' facet words, icrec_index_remove_rows' plan); NULL with the error text set.
+static void* stage_block(Index* ix, size_t bytes) {
+    if (ix->stage_event == nullptr && hipEventCreateWithFlags(&ix->stage_event, hipEventDisableTiming) != hipSuccess) {
+        ix->stage_event = nullptr;
+        set_error("hipEventCreate failed");
+        return nullptr;
+    }
+    if (hipEventSynchronize(ix->stage_event) != hipSuccess) {
+        set_error("hipEventSynchronize failed");
+        return nullptr;
+    }
+    if (ix->stage_bytes < bytes) {
+        (void)hipHostFree(ix->stage_host);
+        ix->stage_host = nullptr;
+        ix->stage_bytes = 0;
+        if (hipHostMalloc(&ix->stage_host, bytes, hipHostMallocDefault) != hipSuccess) {
+            ix->stage_host = nullptr;
+            set_error("hipHostMalloc of %zu bytes failed", bytes);
+            return nullptr;
+        }
+        ix->stage_bytes = bytes;
+    }
+    return ix->stage_host;
 }
 
 }  // namespace icrec
@@ -53,7 +81,7 @@ int icrec_index_create_ex(const float* rows_dev, int64_t n_rows, int32_t dim, in
         return ICREC_ENODEV;
     }
     Index* ix = new Index();
-    ix->n_rows = n_rows; ix->dim = dim; ix->row_offset = row_offset; ix->device = device; ix->storage = storage;
+    ix->n_rows = n_rows; ix->capacity = n_rows; ix->dim = dim; ix->row_offset = row_offset; ix->device = device; ix->storage = storage;
     ix->n_cu = prop.multiProcessorCount;
     ix->stream_max_q = stream_max_q_from_env();
     auto fail = [&]() {  // a hipMalloc failed: free what the index holds so far
@@ -95,6 +123,9 @@ int icrec_index_destroy(icrec_index* h) {
     hipFree(ix->frag);
     hipFree(ix->facets);
     (void)hipFree(ix->rowsets);
+    (void)hipFree(ix->plan_dev);
+    (void)hipHostFree(ix->stage_host);
+    if (ix->stage_event) (void)hipEventDestroy(ix->stage_event);
     delete ix;
     return ICREC_OK;
 }
@@ -111,8 +142,8 @@ int icrec_index_set_facets(icrec_index* h, const uint8_t* facets_host, int32_t n
     }
     ICREC_REQUIRE(n_facets >= 1 && n_facets <= ICREC_MAX_FACETS, "icrec_index_set_facets: n_facets must be in [1, %d] (got %d)",
                   ICREC_MAX_FACETS, n_facets);
-    // one word per row, zero padded to whole 256-row tiles (the widest tile any search kernel walks)
-    const size_t padded = (size_t)((ix->n_rows + 255) / 256) * 256;
+    // one word per row, zero padded to whole 256-row tiles (the widest tile any search kernel walks) of the capacity
+    const size_t padded = (size_t)((ix->capacity + 255) / 256) * 256;
     std::vector<uint16_t> words(padded, 0);
     for (int64_t i = 0; i < ix->n_rows; ++i)
         words[i] = n_facets == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * i] | (facets_host[2 * i + 1] << 8));
@@ -135,9 +166,9 @@ int icrec_index_set_facets(icrec_index* h, const uint8_t* facets_host, int32_t n
 int32_t icrec_index_facets(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->n_facets : -1; }
 
 // One set's words as the device keeps them: the caller's ceil(n_rows / 32) words with the bits at or past n_rows
-// cleared, zero padded to rowset_words(n_rows).
+// cleared, zero padded to rowset_words(capacity).
 static void pad_rowset(const Index* ix, const uint32_t* src, uint32_t* dst) {
-    const int64_t w = (ix->n_rows + 31) / 32, padded = rowset_words(ix->n_rows);
+    const int64_t w = (ix->n_rows + 31) / 32, padded = rowset_words(ix->capacity);
     for (int64_t i = 0; i < w; ++i) dst[i] = src[i];
     if (ix->n_rows % 32) dst[w - 1] &= (1u << (ix->n_rows % 32)) - 1u;
     for (int64_t i = w; i < padded; ++i) dst[i] = 0u;
@@ -155,7 +186,7 @@ int icrec_index_set_rowsets(icrec_index* h, const uint32_t* bits_host, int32_t n
     }
     ICREC_REQUIRE(n_sets >= 1 && n_sets <= ICREC_MAX_ROWSETS, "icrec_index_set_rowsets: n_sets must be in [1, %d] (got %d)",
                   ICREC_MAX_ROWSETS, n_sets);
-    const size_t w = (size_t)((ix->n_rows + 31) / 32), padded = (size_t)rowset_words(ix->n_rows);
+    const size_t w = (size_t)((ix->n_rows + 31) / 32), padded = (size_t)rowset_words(ix->capacity);
     std::vector<uint32_t> words;
     try {
         words.resize(padded * n_sets);
@@ -186,7 +217,7 @@ int icrec_index_write_rowset(icrec_index* h, int32_t set, const uint32_t* bits_h
     ICREC_REQUIRE(ix->rowsets != nullptr, "icrec_index_write_rowset: the index has no row sets");
     ICREC_REQUIRE(set >= 0 && set < ix->n_rowsets, "icrec_index_write_rowset: set must be in [0, %d) (got %d)", ix->n_rowsets, set);
     ICREC_HIP(hipSetDevice(ix->device));
-    const size_t padded = (size_t)rowset_words(ix->n_rows);
+    const size_t padded = (size_t)rowset_words(ix->capacity);
     std::vector<uint32_t> words(padded);
     pad_rowset(ix, bits_host, words.data());
     ICREC_HIP(hipMemcpy(ix->rowsets + (size_t)set * padded, words.data(), padded * 4, hipMemcpyHostToDevice));
@@ -221,7 +252,143 @@ int icrec_index_write_rows(icrec_index* h, const float* rows_dev, const int32_t*
     ICREC_REQUIRE(rows_dev && row_ids_dev, "icrec_index_write_rows: NULL argument");
     ICREC_HIP(hipSetDevice(ix->device));
     ScopedTimer tm(T_INDEX_WRITE, (hipStream_t)stream);
-    return write_index_rows(ix, rows_dev, row_ids_dev, m, (hipStream_t)stream);
+    return write_index_rows(ix, rows_dev, row_ids_dev, m, 0, (hipStream_t)stream);
+}
+
+int64_t icrec_index_capacity(const icrec_index* h) { return h ? reinterpret_cast<const Index*>(h)->capacity : 0; }
+
+int icrec_index_reserve(icrec_index* h, int64_t capacity) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix, "icrec_index_reserve: NULL index");
+    ICREC_REQUIRE(capacity >= ix->n_rows, "icrec_index_reserve: capacity %lld is below the index's %lld rows", (long long)capacity,
+                  (long long)ix->n_rows);
+    ICREC_REQUIRE(ix->row_offset + capacity < 0xFFFFFFFFll, "icrec_index_reserve: row_offset + capacity must be < 2^32-1");
+    if (capacity == ix->capacity) return ICREC_OK;
+    ICREC_HIP(hipSetDevice(ix->device));
+    ICREC_HIP(hipDeviceSynchronize());  // whatever still reads or writes the old arrays, on any stream
+    const size_t row_bytes = (size_t)ix->dim * (rows_are_bf16(ix) ? 2 : 4);
+    const size_t facet_words = (size_t)((capacity + 255) / 256) * 256;
+    const size_t old_words = (size_t)rowset_words(ix->capacity), new_words = (size_t)rowset_words(capacity);
+    void* rows = nullptr;
+    uint16_t* facets = nullptr;
+    uint32_t* rowsets = nullptr;
+    FilterStorage fs;
+    auto drop = [&](int rc) {  // the handle keeps its arrays: free the new ones
+        (void)hipFree(rows); (void)hipFree(facets); (void)hipFree(rowsets);
+        (void)hipFree(fs.plane_hi); (void)hipFree(fs.plane_lo); (void)hipFree(fs.frag);
+        return rc;
+    };
+    if (hipMalloc(&rows, (size_t)capacity * row_bytes) != hipSuccess ||
+        (ix->facets && hipMalloc(&facets, facet_words * 2) != hipSuccess) ||
+        (ix->rowsets && hipMalloc(&rowsets, new_words * 4 * ix->n_rowsets) != hipSuccess)) {
+        set_error("icrec_index_reserve: hipMalloc for %lld rows failed", (long long)capacity);
+        return drop(ICREC_ENOMEM);
+    }
+    if (int rc = reserve_filter_storage(ix, capacity, &fs)) return drop(rc);
+    hipError_t e = hipMemcpyAsync(rows, ix->rows, (size_t)ix->n_rows * row_bytes, hipMemcpyDeviceToDevice, 0);
+    if (e == hipSuccess && facets) {  // the words past n_rows are zero in the old array too
+        e = hipMemsetAsync(facets, 0, facet_words * 2, 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(facets, ix->facets, (size_t)ix->n_rows * 2, hipMemcpyDeviceToDevice, 0);
+    }
+    if (e == hipSuccess && rowsets) {  // set by set: the stride changes; the live words of a set are a prefix of both strides
+        e = hipMemsetAsync(rowsets, 0, new_words * 4 * ix->n_rowsets, 0);
+        const size_t live = (size_t)((ix->n_rows + 31) / 32) * 4;
+        if (e == hipSuccess)
+            e = hipMemcpy2DAsync(rowsets, new_words * 4, ix->rowsets, old_words * 4, live, (size_t)ix->n_rowsets,
+                                 hipMemcpyDeviceToDevice, 0);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) {
+        set_error("icrec_index_reserve: copying the index failed: %s", hipGetErrorString(e));
+        return drop(ICREC_EHIP);
+    }
+    (void)hipFree(ix->rows); (void)hipFree(ix->facets); (void)hipFree(ix->rowsets);
+    (void)hipFree(ix->plane_hi); (void)hipFree(ix->plane_lo); (void)hipFree(ix->frag);
+    ix->rows = rows; ix->facets = facets; ix->rowsets = rowsets;
+    ix->plane_hi = fs.plane_hi; ix->plane_lo = fs.plane_lo; ix->frag = fs.frag;
+    if (fs.frag) ix->frag_row_tiles = fs.frag_row_tiles;
+    ix->capacity = capacity;
+    return ICREC_OK;
+}
+
+int icrec_index_append_rows(icrec_index* h, const float* rows_dev, int32_t m, const uint8_t* facets_host, void* stream) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix, "icrec_index_append_rows: NULL index");
+    ICREC_REQUIRE(m >= 0, "icrec_index_append_rows: m must be >= 0 (got %d)", m);
+    if (m == 0) return ICREC_OK;
+    ICREC_REQUIRE(rows_dev, "icrec_index_append_rows: NULL argument");
+    ICREC_REQUIRE(ix->n_rows + m <= ix->capacity, "icrec_index_append_rows: %lld + %d rows exceed the capacity %lld (icrec_index_reserve)",
+                  (long long)ix->n_rows, m, (long long)ix->capacity);
+    ICREC_REQUIRE(facets_host || !ix->facets, "icrec_index_append_rows: the index has facets, facets_host is required");
+    ICREC_REQUIRE(!facets_host || ix->facets, "icrec_index_append_rows: facets_host on an index without facets");
+    ICREC_HIP(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (ix->facets) {
+        uint16_t* words = static_cast<uint16_t*>(stage_block(ix, (size_t)m * 2));
+        if (words == nullptr) return ICREC_ENOMEM;
+        for (int32_t i = 0; i < m; ++i)
+            words[i] = ix->n_facets == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * (size_t)i] | (facets_host[2 * (size_t)i + 1] << 8));
+        ICREC_HIP(hipMemcpyAsync(ix->facets + ix->n_rows, words, (size_t)m * 2, hipMemcpyHostToDevice, st));
+        ICREC_HIP(hipEventRecord(ix->stage_event, st));
+    }
+    // the rows' bits of every row set are zero already: the new rows are members of no set
+    if (int rc = write_index_rows(ix, rows_dev, nullptr, m, ix->n_rows, st)) return rc;
+    ix->n_rows += m;
+    return ICREC_OK;
+}
+
+int icrec_index_remove_rows(icrec_index* h, const int32_t* row_ids_host, int32_t m, int32_t* dst_out, int32_t* src_out,
+                            int32_t* n_moves_out, void* stream) {
+    Index* ix = reinterpret_cast<Index*>(h);
+    ICREC_REQUIRE(ix, "icrec_index_remove_rows: NULL index");
+    ICREC_REQUIRE(m >= 0, "icrec_index_remove_rows: m must be >= 0 (got %d)", m);
+    ICREC_REQUIRE(n_moves_out && (m == 0 || (row_ids_host && dst_out && src_out)), "icrec_index_remove_rows: NULL argument");
+    ICREC_REQUIRE(m < ix->n_rows, "icrec_index_remove_rows: removing %d of %lld rows would leave the index empty", m,
+                  (long long)ix->n_rows);
+    for (int32_t i = 0; i < m; ++i) {
+        ICREC_REQUIRE(row_ids_host[i] >= 0 && row_ids_host[i] < ix->n_rows, "icrec_index_remove_rows: row %d is outside [0, %lld)",
+                      row_ids_host[i], (long long)ix->n_rows);
+        ICREC_REQUIRE(i == 0 || row_ids_host[i] > row_ids_host[i - 1], "icrec_index_remove_rows: the rows must be ascending and unique");
+    }
+    *n_moves_out = 0;
+    if (m == 0) return ICREC_OK;
+    // the plan: the holes (removed rows below new_n, ascending) take the survivors at or past new_n, ascending
+    const int64_t old_n = ix->n_rows, new_n = old_n - m;
+    int32_t n_moves = 0;
+    while (n_moves < m && row_ids_host[n_moves] < new_n) ++n_moves;  // (ascending: the holes come first)
+    ICREC_HIP(hipSetDevice(ix->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (n_moves > 0) {
+        int32_t* plan = static_cast<int32_t*>(stage_block(ix, (size_t)n_moves * 8));
+        if (plan == nullptr) return ICREC_ENOMEM;
+        if (ix->plan_cap < (size_t)n_moves) {
+            ICREC_HIP(hipStreamSynchronize(st));  // an earlier removal on this stream may still read the old block
+            (void)hipFree(ix->plan_dev);
+            ix->plan_dev = nullptr;
+            ix->plan_cap = 0;
+            if (hipMalloc(&ix->plan_dev, (size_t)n_moves * 8) != hipSuccess) {
+                ix->plan_dev = nullptr;
+                set_error("icrec_index_remove_rows: hipMalloc of %zu bytes failed", (size_t)n_moves * 8);
+                return ICREC_ENOMEM;
+            }
+            ix->plan_cap = (size_t)n_moves;
+        }
+        int32_t t = n_moves, i = 0;  // ids[t ..] are the removed rows of the tail
+        for (int64_t row = new_n; i < n_moves; ++row) {
+            if (t < m && row_ids_host[t] == row) { ++t; continue; }
+            plan[i] = row_ids_host[i];
+            plan[n_moves + i] = (int32_t)row;
+            ++i;
+        }
+        ICREC_HIP(hipMemcpyAsync(ix->plan_dev, plan, (size_t)n_moves * 8, hipMemcpyHostToDevice, st));
+        ICREC_HIP(hipEventRecord(ix->stage_event, st));
+        memcpy(dst_out, plan, (size_t)n_moves * 4);
+        memcpy(src_out, plan + n_moves, (size_t)n_moves * 4);
+    }
+    if (int rc = move_index_rows(ix, ix->plan_dev, ix->plan_dev + n_moves, n_moves, new_n, old_n, st)) return rc;
+    ix->n_rows = new_n;
+    *n_moves_out = n_moves;
+    return ICREC_OK;
 }
 
 int icrec_index_write_facets(icrec_index* h, const int32_t* row_ids_host, const uint8_t* facets_host, int32_t m) {

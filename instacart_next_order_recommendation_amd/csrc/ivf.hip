@@ -22,6 +22,7 @@ struct Ivf {
     const Index* base = nullptr;
     icrec_index* cent = nullptr;   // the centroids, ICREC_ROWS_F32, row offset 0
     int n_lists = 0;
+    int64_t n_rows = 0;            // the base's rows when the IVF was made (the base may gain or lose rows: icrec_index_append_rows)
     void* rows = nullptr;          // the base's stored rows in perm order, in the base's row element type
     int32_t* perm = nullptr;       // [n_rows] local rows sorted by (list, row)
     int64_t* list_off = nullptr;   // [n_lists + 1]
@@ -331,6 +332,7 @@ int icrec_ivf_create(icrec_index* base, const float* centroids_dev, int32_t n_li
         set_error("icrec_ivf_create: gathering the rows failed");
         return fail(ICREC_EHIP);
     }
+    v->n_rows = n;
     *out = reinterpret_cast<icrec_ivf*>(v);
     return ICREC_OK;
 }
@@ -341,7 +343,7 @@ int icrec_ivf_layout(const icrec_ivf* h, int32_t* perm_dev, int64_t* list_off_de
     const Ivf* v = reinterpret_cast<const Ivf*>(h);
     ICREC_REQUIRE(v && perm_dev && list_off_dev, "icrec_ivf_layout: NULL argument");
     ICREC_HIP(hipSetDevice(v->base->device));
-    ICREC_HIP(hipMemcpyAsync(perm_dev, v->perm, (size_t)v->base->n_rows * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    ICREC_HIP(hipMemcpyAsync(perm_dev, v->perm, (size_t)v->n_rows * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     ICREC_HIP(hipMemcpyAsync(list_off_dev, v->list_off, ((size_t)v->n_lists + 1) * 8, hipMemcpyDeviceToDevice,
                              (hipStream_t)stream));
     return ICREC_OK;

@@ -949,7 +949,7 @@ static_assert(FILTER_DIM_STEP == HBK, "index.hip admits the dims whose rows the 
 
 // index.h: the filter storage of a new index, in the layout the pass that will read it expects.
 int build_filter_storage(Index* ix) {
-    const int64_t n_rows = ix->n_rows;
+    const int64_t n_rows = ix->n_rows;  // (== the capacity: a new index)
     const int dim = ix->dim;
     const bool rows16 = rows_are_bf16(ix);
     const char* res_env = getenv("ICREC_FILTER_RESIDENT");  // "0": staged form; a number > 1: row limit of the resident form (A/B)
@@ -989,10 +989,11 @@ int build_filter_storage(Index* ix) {
 // pack_rows_kernel packs them (lane (h << 5 | r) of fragment (row / 32, ks) holds k = 16 ks + 8 h .. + 7: chunk
 // c = 2 ks + h).  An id outside [0, n_rows) writes nothing: it is tested before any address is formed from it.
 // No other row's bytes are touched; the padding rows of the last fragment round stay zero.
+// ids == NULL (icrec_index_append_rows): written row w is row base + w instead, under the same test.
 constexpr int WRITE_NO_FILTER = 0, WRITE_PLANES = 1, WRITE_FRAGS = 2;
 template <bool OUT16, int FILT>
-__global__ __launch_bounds__(256) void write_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ ids, int m,
-                                                         void* __restrict__ rowsv, int64_t n_rows, int dim,
+__global__ __launch_bounds__(256) void write_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ ids, int64_t base,
+                                                         int m, void* __restrict__ rowsv, int64_t n_rows, int dim,
                                                          _Float16* __restrict__ hi, _Float16* __restrict__ lo,
                                                          _Float16* __restrict__ frag) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1001,7 +1002,7 @@ __global__ __launch_bounds__(256) void write_rows_kernel(const float* __restrict
     const int64_t w = (int64_t)blockIdx.x * 4 + wave;
     int64_t row = -1;  // wave-uniform
     if (w < m) {
-        const int32_t id = ids[w];
+        const int64_t id = ids ? (int64_t)ids[w] : base + w;
         if (id >= 0 && id < n_rows) row = id;
     }
     if (row >= 0) {
@@ -1056,16 +1057,150 @@ __global__ __launch_bounds__(256) void write_rows_kernel(const float* __restrict
 }
 
 // index.h: icrec_index_write_rows after its argument checks (m >= 1): one launch, nothing allocated.
-int write_index_rows(Index* ix, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, hipStream_t st) {
+int write_index_rows(Index* ix, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, int64_t base_row, hipStream_t st) {
     const bool rows16 = rows_are_bf16(ix);
     const int filt = ix->frag ? WRITE_FRAGS : ix->plane_hi ? WRITE_PLANES : WRITE_NO_FILTER;
-    typedef void (*kernel_t)(const float*, const int32_t*, int, void*, int64_t, int, _Float16*, _Float16*, _Float16*);
+    typedef void (*kernel_t)(const float*, const int32_t*, int64_t, int, void*, int64_t, int, _Float16*, _Float16*, _Float16*);
     static const kernel_t kernels[2][3] = {
         {write_rows_kernel<false, WRITE_NO_FILTER>, write_rows_kernel<false, WRITE_PLANES>, write_rows_kernel<false, WRITE_FRAGS>},
         {write_rows_kernel<true, WRITE_NO_FILTER>, write_rows_kernel<true, WRITE_PLANES>, write_rows_kernel<true, WRITE_FRAGS>}};
     hipLaunchKernelGGL(kernels[rows16][filt], dim3((unsigned)(((int64_t)m + 3) / 4)), dim3(256), (size_t)4 * ix->dim * sizeof(float), st,
-                       rows_dev, row_ids_dev, (int)m, ix->rows, ix->n_rows, ix->dim, ix->plane_hi, ix->plane_lo, ix->frag);
+                       rows_dev, row_ids_dev, base_row, (int)m, ix->rows, row_ids_dev ? ix->n_rows : base_row + m, ix->dim,
+                       ix->plane_hi, ix->plane_lo, ix->frag);
     ICREC_HIP(hipGetLastError());
+    return ICREC_OK;
+}
+
+// ---------------------------------------------------------------- rows moved in place (icrec_index_remove_rows)
+// One wavefront per move i: everything the index keeps for row src[i] is copied to row dst[i] as the STORED bits - the
+// planes and the fragments are functions of the stored values alone, not of the row's position, so nothing is
+// normalised or split again.  16-byte loads and stores: the row, its slice of both planes or its lane slots (from
+// fragment (src / 32, ks), lane (h << 5 | src & 31), to fragment (dst / 32, ks), lane (h << 5 | dst & 31): the
+// addressing of write_rows_kernel and unpack_rows_kernel).  Then the facet word (one 16-bit store) and the row's bit
+// in every row set: several destinations can share a 32-bit word, so the bit is set or cleared atomically.
+// Sources (>= new_n) and destinations (< new_n) are disjoint and each is named once: no wave writes what another reads.
+// Nothing is cleared here - a source's word or fragment tile may hold other sources that a later wave still reads;
+// clear_rows_kernel runs behind this launch.  A move outside dst < new_n <= src < old_n is skipped before any address
+// is formed from it.
+template <bool OUT16, int FILT>
+__global__ __launch_bounds__(256) void move_rows_kernel(const int32_t* __restrict__ dst, const int32_t* __restrict__ src,
+                                                        int n_moves, int64_t new_n, int64_t old_n, void* rowsv, int dim,
+                                                        _Float16* hi, _Float16* lo, _Float16* frag, uint16_t* facets,
+                                                        uint32_t* sets, int n_sets, int64_t set_words) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= n_moves) return;
+    const int64_t d = dst[w], s = src[w];  // wave-uniform
+    if (d < 0 || d >= new_n || s < new_n || s >= old_n) return;
+    const int row_chunks = dim * (OUT16 ? 2 : 4) / 16;
+    const u32x4* rs = reinterpret_cast<const u32x4*>(static_cast<const char*>(rowsv) + (size_t)s * row_chunks * 16);
+    u32x4* rd = reinterpret_cast<u32x4*>(static_cast<char*>(rowsv) + (size_t)d * row_chunks * 16);
+    for (int c = lane; c < row_chunks; c += 64) rd[c] = rs[c];
+    if (FILT != WRITE_NO_FILTER) {
+        for (int c = lane; c < dim / 8; c += 64) {
+            if (FILT == WRITE_PLANES) {
+                *reinterpret_cast<half8*>(hi + d * dim + 8 * c) = *reinterpret_cast<const half8*>(hi + s * dim + 8 * c);
+                *reinterpret_cast<half8*>(lo + d * dim + 8 * c) = *reinterpret_cast<const half8*>(lo + s * dim + 8 * c);
+            } else {
+                const _Float16* from = frag + ((s >> 5) * (dim / 16) + (c >> 1)) * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(s & 31)) * 8;
+                _Float16* to = frag + ((d >> 5) * (dim / 16) + (c >> 1)) * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(d & 31)) * 8;
+                *reinterpret_cast<half8*>(to) = *reinterpret_cast<const half8*>(from);
+                *reinterpret_cast<half8*>(to + WT_FRAG) = *reinterpret_cast<const half8*>(from + WT_FRAG);
+            }
+        }
+    }
+    if (facets != nullptr && lane == 0) facets[d] = facets[s];
+    for (int t = lane; t < n_sets; t += 64) {
+        uint32_t* bits = sets + (size_t)t * set_words;
+        const uint32_t bit = 1u << (d & 31);
+        if ((bits[s >> 5] >> (s & 31)) & 1u) atomicOr(bits + (d >> 5), bit);
+        else atomicAnd(bits + (d >> 5), ~bit);
+    }
+}
+
+// Behind move_rows_kernel: the rows [new_n, old_n) leave the index, and what a fresh index keeps zero past its last row
+// becomes zero again - their fragment lane slots and facet words (one wavefront per row), and their bits of every row
+// set (the threads of the whole grid over (set, word) pairs: the word that straddles new_n keeps its low bits).  The
+// stored rows and the planes past n_rows are addressed by nothing and stay as they are.  Every slot, word and bitmap
+// word is written by one thread of this launch and read by none.
+template <bool FRAGS>
+__global__ __launch_bounds__(256) void clear_rows_kernel(int64_t new_n, int64_t old_n, int dim, _Float16* frag, uint16_t* facets,
+                                                         uint32_t* sets, int n_sets, int64_t set_words) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = new_n + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row < old_n) {
+        if (FRAGS) {
+            half8 z;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) z[j] = (_Float16)0.0f;
+            for (int c = lane; c < dim / 8; c += 64) {
+                _Float16* at = frag + ((row >> 5) * (dim / 16) + (c >> 1)) * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(row & 31)) * 8;
+                *reinterpret_cast<half8*>(at) = z;
+                *reinterpret_cast<half8*>(at + WT_FRAG) = z;
+            }
+        }
+        if (facets != nullptr && lane == 0) facets[row] = 0;
+    }
+    const int64_t w0 = new_n >> 5, nw = ((old_n + 31) >> 5) - w0;  // the words that hold a bit of the tail
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nw * n_sets; i += (int64_t)gridDim.x * 256) {
+        uint32_t* word = sets + (size_t)(i / nw) * set_words + w0 + i % nw;
+        *word = (i % nw == 0 && (new_n & 31)) ? *word & ((1u << (new_n & 31)) - 1u) : 0u;
+    }
+}
+
+// index.h: icrec_index_remove_rows after its argument checks: two launches, nothing allocated.
+int move_index_rows(Index* ix, const int32_t* dst_dev, const int32_t* src_dev, int32_t n_moves, int64_t new_n, int64_t old_n,
+                    hipStream_t st) {
+    const bool rows16 = rows_are_bf16(ix);
+    const int filt = ix->frag ? WRITE_FRAGS : ix->plane_hi ? WRITE_PLANES : WRITE_NO_FILTER;
+    typedef void (*kernel_t)(const int32_t*, const int32_t*, int, int64_t, int64_t, void*, int, _Float16*, _Float16*, _Float16*,
+                             uint16_t*, uint32_t*, int, int64_t);
+    static const kernel_t kernels[2][3] = {
+        {move_rows_kernel<false, WRITE_NO_FILTER>, move_rows_kernel<false, WRITE_PLANES>, move_rows_kernel<false, WRITE_FRAGS>},
+        {move_rows_kernel<true, WRITE_NO_FILTER>, move_rows_kernel<true, WRITE_PLANES>, move_rows_kernel<true, WRITE_FRAGS>}};
+    const int n_sets = ix->rowsets ? ix->n_rowsets : 0;
+    const int64_t words = rowset_words(ix->capacity);
+    if (n_moves > 0) {
+        hipLaunchKernelGGL(kernels[rows16][filt], dim3((unsigned)(((int64_t)n_moves + 3) / 4)), dim3(256), 0, st, dst_dev, src_dev,
+                           (int)n_moves, new_n, old_n, ix->rows, ix->dim, ix->plane_hi, ix->plane_lo, ix->frag, ix->facets,
+                           ix->rowsets, n_sets, words);
+        ICREC_HIP(hipGetLastError());
+    }
+    if (ix->frag || ix->facets || n_sets > 0) {
+        hipLaunchKernelGGL((ix->frag ? clear_rows_kernel<true> : clear_rows_kernel<false>), dim3((unsigned)((old_n - new_n + 3) / 4)),
+                           dim3(256), 0, st, new_n, old_n, ix->dim, ix->frag, ix->facets, ix->rowsets, n_sets, words);
+        ICREC_HIP(hipGetLastError());
+    }
+    return ICREC_OK;
+}
+
+// index.h: icrec_index_reserve's filter copy at the new capacity.  The fragments are a function of the row tile alone
+// (fragment (row / 32, ks)), so the live rows are a prefix of the new array; whole rounds of CfgRes::BM rows of the
+// capacity, zero behind the live rows as build_filter_storage leaves them.
+int reserve_filter_storage(const Index* ix, int64_t capacity, FilterStorage* out) {
+    if (ix->frag) {
+        out->frag_row_tiles = ((capacity + CfgRes::BM - 1) / CfgRes::BM) * (CfgRes::BM / 32);
+        const size_t tile_bytes = (size_t)RES_KS * 2 * WT_FRAG * sizeof(_Float16), bytes = (size_t)out->frag_row_tiles * tile_bytes;
+        if (hipMalloc(&out->frag, bytes) != hipSuccess) {
+            out->frag = nullptr;
+            set_error("icrec_index_reserve: hipMalloc of the filter fragments (%zu bytes) failed", bytes);
+            return ICREC_ENOMEM;
+        }
+        const size_t live = (size_t)((ix->n_rows + 31) / 32) * tile_bytes;  // (<= both arrays: n_rows <= either capacity)
+        ICREC_HIP(hipMemcpyAsync(out->frag, ix->frag, live, hipMemcpyDeviceToDevice, 0));
+        ICREC_HIP(hipMemsetAsync(reinterpret_cast<char*>(out->frag) + live, 0, bytes - live, 0));
+    } else if (ix->plane_hi) {
+        const size_t bytes = (size_t)capacity * ix->dim * 2, live = (size_t)ix->n_rows * ix->dim * 2;
+        hipError_t e1 = hipMalloc(&out->plane_hi, bytes), e2 = e1 == hipSuccess ? hipMalloc(&out->plane_lo, bytes) : e1;
+        if (e1 != hipSuccess || e2 != hipSuccess) {
+            if (e1 == hipSuccess) (void)hipFree(out->plane_hi);
+            out->plane_hi = out->plane_lo = nullptr;
+            set_error("icrec_index_reserve: hipMalloc of the filter planes (2 x %zu bytes) failed", bytes);
+            return ICREC_ENOMEM;
+        }
+        ICREC_HIP(hipMemcpyAsync(out->plane_hi, ix->plane_hi, live, hipMemcpyDeviceToDevice, 0));
+        ICREC_HIP(hipMemcpyAsync(out->plane_lo, ix->plane_lo, live, hipMemcpyDeviceToDevice, 0));
+    }
     return ICREC_OK;
 }
 
@@ -1356,7 +1491,7 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
                   "icrec_search_in_sets: sets_per_query must be in [1, %d] (got %d)", ICREC_MAX_SETS_PER_QUERY, sets_per_query);
     // (the SETS arm without allow masks: no facet words are read and the masks it loads are all ones)
     const FacetArgs fa = allow ? FacetArgs{ix->facets, allow, ix->n_facets} : FacetArgs{nullptr, nullptr, 0};
-    const SetArgs sa{fa, ix->rowsets, set_ids, ix->n_rowsets, sets_per_query, rowset_words(ix->n_rows)};
+    const SetArgs sa{fa, ix->rowsets, set_ids, ix->n_rowsets, sets_per_query, rowset_words(ix->capacity)};
     const Arm arm = arm_of(sa);
     if (scores_out == nullptr && (ix->plane_hi != nullptr || ix->frag != nullptr)) {
         const Plan ex = make_plan(ix, Q, k, false, arm);

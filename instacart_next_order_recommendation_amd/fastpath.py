@@ -102,6 +102,13 @@ class SingleRequestPath:
         self.buckets = BUCKETS + ((ceiling,) if ceiling > BUCKETS[-1] else ())
         self._graphs: dict[tuple[int, int], _Captured] = {}
 
+    def reset(self) -> None:
+        """Drop the captured graphs and their scratch; each shape is captured again on its next request.  Needed after
+        the index's rows were added or removed (DeviceIndex.reserve / append_rows / remove_rows): n_rows is a launch
+        argument of the captured search kernels and reserve moves the arrays they point to."""
+        torch.cuda.synchronize(self.encoder.device)
+        self._graphs.clear()
+
     def supports(self, n_tokens: int, k: int, n_excluded: int) -> bool:
         return 1 <= n_tokens <= self.buckets[-1] and n_excluded <= MAX_EXCLUDED and k <= self.index.n_rows
 

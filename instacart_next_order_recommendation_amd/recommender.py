@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .encoder import DeviceEncoder
 from .model_io import LoadedModel, load_model_dir
-from .search import DeviceIndex, IvfIndex, facet_masks, rowset_bits, rowset_ids, train_centroids
+from .search import DeviceIndex, IvfIndex, apply_moves, facet_masks, rowset_bits, rowset_ids, train_centroids
 
 logger = logging.getLogger(__name__)
 
@@ -143,7 +143,7 @@ def product_update_plan(updates, pid_to_row, product_texts, aisles, departments)
     -> (rows ascending, their new texts, facet codes uint8 [m, 2] or None without facets, aisle names, department names).
     A name the catalog does not have yet is appended to (a copy of) its list, so every existing code stays what it is
     (catalog_facets numbers by first appearance; a name no product carries any more keeps its code).  An empty
-    mapping gives no rows.  ValueError: not a mapping, an id the catalog does not have (adding a product is a re-index),
+    mapping gives no rows.  ValueError: not a mapping, an id the catalog does not have (add_products adds one),
     a text that is not a string, on a catalog with facets a text that does not parse as
     'Product: .. Aisle: .. Department: ..', a 257th aisle or department name."""
     if not hasattr(updates, "items"):
@@ -151,8 +151,8 @@ def product_update_plan(updates, pid_to_row, product_texts, aisles, departments)
     pairs = []
     for pid, text in updates.items():
         if pid not in pid_to_row or not 0 <= pid_to_row[pid] < len(product_texts):
-            raise ValueError(f"unknown product id {pid!r}: update_products rewrites products the catalog has; adding one "
-                             "is a re-index")
+            raise ValueError(f"unknown product id {pid!r}: update_products rewrites products the catalog has; "
+                             "add_products adds one")
         if not isinstance(text, str):
             raise ValueError(f"the new text of product {pid!r} must be a string, got {type(text).__name__}")
         pairs.append((int(pid_to_row[pid]), text))
@@ -177,6 +177,64 @@ def product_update_plan(updates, pid_to_row, product_texts, aisles, departments)
                 names[f].append(value)
             codes[i, f] = code[f][value]
     return rows, texts, codes, names[0], names[1]
+
+
+def product_add_plan(additions, pid_to_row, aisles, departments):
+    """Recommender.add_products' argument, checked before any GPU work.  additions: a mapping product id -> text;
+    pid_to_row: the catalog's rows; aisles / departments: its facet names, None for a catalog without facets
+    -> (the new ids in the mapping's order, their texts, facet codes uint8 [m, 2] or None without facets, aisle names,
+    department names).  A name the catalog does not have yet is appended behind (a copy of) its list, as
+    product_update_plan does.  An empty mapping gives no ids.  ValueError: not a mapping, an id the catalog already has,
+    a text that is not a string, on a catalog with facets a text that does not parse, a 257th aisle or department
+    name.  (A mapping cannot name an id twice.)"""
+    if not hasattr(additions, "items"):
+        raise ValueError("additions must be a mapping product id -> text")
+    ids, texts = [], []
+    for pid, text in additions.items():
+        if pid in pid_to_row:
+            raise ValueError(f"product id {pid!r} is in the catalog already: update_products gives it a new text")
+        if not isinstance(text, str):
+            raise ValueError(f"the text of product {pid!r} must be a string, got {type(text).__name__}")
+        ids.append(pid)
+        texts.append(text)
+    if aisles is None:
+        return ids, texts, None, None, None
+    names = (list(aisles), list(departments))
+    code = tuple({name: i for i, name in enumerate(known)} for known in names)
+    codes = np.zeros((len(ids), 2), np.uint8)
+    for i, text in enumerate(texts):
+        parsed = text_facets(text)
+        if parsed is None:
+            raise ValueError(f"the text of product {ids[i]!r} is not in the 'Product: .. Aisle: .. Department: ..' format "
+                             "of this catalog")
+        for f, value in enumerate(parsed):
+            if value not in code[f]:
+                if len(names[f]) >= 256:
+                    raise ValueError(f"{value!r} would be the 257th {'aisle' if f == 0 else 'department'} name; a facet "
+                                     "has 256 values")
+                code[f][value] = len(names[f])
+                names[f].append(value)
+            codes[i, f] = code[f][value]
+    return ids, texts, codes, names[0], names[1]
+
+
+def product_remove_plan(product_ids, pid_to_row) -> list[int]:
+    """Recommender.remove_products' argument, checked before any GPU work: a list of product ids -> their rows, in the
+    list's order.  ValueError: a string instead of a list, an id the catalog does not have, an id named twice, a list
+    that names every product (a catalog is never empty)."""
+    if isinstance(product_ids, (str, bytes)) or hasattr(product_ids, "items"):
+        raise ValueError("remove_products takes a list of product ids")
+    rows, seen = [], set()
+    for pid in product_ids:
+        if pid not in pid_to_row:
+            raise ValueError(f"unknown product id {pid!r}: remove_products removes products the catalog has")
+        if pid in seen:
+            raise ValueError(f"product id {pid!r} is named twice")
+        seen.add(pid)
+        rows.append(int(pid_to_row[pid]))
+    if rows and len(rows) >= len(pid_to_row):
+        raise ValueError("remove_products: removing every product would leave the catalog empty")
+    return rows
 
 
 def diversity_plan(diversity, candidates, top_k: int, n_products: int):
@@ -412,6 +470,7 @@ class Recommender:
     _ann: Optional[IvfIndex] = None  # the IVF index beside _index (ann_lists), searched by requests that pass `probes`
     product_sets: Optional[list[str]] = None  # the names of the product sets (product_sets=), in set id order
     _set_member: Optional[np.ndarray] = None  # bool [n_sets, n_products]: the host's copy of the membership
+    _emb_block: Optional[np.ndarray] = None  # add_products / remove_products: the block product_embeddings is a view of
     aisles: Optional[list[str]] = None  # the catalog's aisle and department names (_set_facets); None: it has no facets
     departments: Optional[list[str]] = None
 
@@ -530,8 +589,8 @@ class Recommender:
         the others stay).  product_texts, pid_to_text and product_embeddings follow, and the IVF index of a
         recommender built with ann_lists is built again from its centroids (IvfIndex.rebuild).  No pointer of the
         index changes: the captured single-request graphs stay and answer from the new rows.
-        ValueError, with nothing changed: an id the catalog does not have (adding or removing a product changes the
-        number of rows and stays a re-index), a text that does not parse on a catalog with facets, a 257th aisle or
+        ValueError, with nothing changed: an id the catalog does not have (add_products and remove_products change the
+        number of rows), a text that does not parse on a catalog with facets, a 257th aisle or
         department name (product_update_plan).  An empty mapping does nothing.
         The limits: it is a set-up call on the index, never to be made while a request is being served.  The corpus
         file and the on-disk EmbeddingIndex cache are not rewritten: a process started later reads the old texts.  A
@@ -555,6 +614,90 @@ class Recommender:
         self.aisles, self.departments = aisles, departments
         if self._ann is not None:
             self._ann.rebuild()
+
+    def _after_resize(self) -> None:
+        """The number of rows changed: wait for the device, drop the captured single-request graphs (n_rows is an
+        argument of their search kernels, and a reserve moved the arrays) and build the IVF index again from its
+        centroids."""
+        torch.cuda.current_stream(self.device).synchronize()
+        if self._fast is not None:
+            self._fast.reset()
+        if self._ann is not None:
+            self._ann.rebuild()
+
+    def _embedding_block(self, room: int) -> np.ndarray:
+        """The host block product_embeddings is a view of the front of, writable and with room for `room` more rows
+        (grown by doubling, like the index's capacity): adding and removing products then costs the host what it costs
+        the device, the edited rows and not the catalog."""
+        n, block = len(self.product_embeddings), self._emb_block
+        if block is None or self.product_embeddings.base is not block or block.shape[0] < n + room:
+            block = np.empty((max(2 * n, n + room), self.product_embeddings.shape[1]), np.float32)
+            block[:n] = self.product_embeddings
+            self._emb_block = block
+            self.product_embeddings = block[:n]
+        return block
+
+    def add_products(self, additions) -> None:
+        """Add products without a re-index: additions is a mapping product id -> text.  The texts are encoded as the
+        catalog was (normalize_embeddings=True) and appended to the device index in place (DeviceIndex.append_rows,
+        which doubles the index's capacity when it is full), on a catalog with facets together with their aisle and
+        department codes (a new name is appended behind .aisles / .departments).  The new products take the rows behind
+        the last one, in the mapping's order, and join no product set (update_product_set).  product_ids,
+        product_texts, pid_to_text, product_embeddings and the host's set membership follow; the captured
+        single-request graphs are dropped and captured again on the next request, and the IVF index of a recommender
+        built with ann_lists is built again from its centroids.
+        ValueError, with nothing changed: an id the catalog already has, a text that does not parse on a catalog with
+        facets, a 257th aisle or department name (product_add_plan).  An empty mapping does nothing.
+        The limits are update_products': a set-up call, never made while a request is being served; the corpus file
+        and the on-disk EmbeddingIndex cache are not rewritten; a RerankedRecommender built on this recommender keeps
+        its own token store and must be built again."""
+        ids, texts, codes, aisles, departments = product_add_plan(additions, self._pid_to_row, self.aisles, self.departments)
+        if not ids:
+            return
+        emb = np.asarray(self.model.encode(texts, show_progress_bar=False, normalize_embeddings=True), np.float32)
+        new_rows = self._index.append_rows(emb, codes)
+        block, n = self._embedding_block(len(ids)), len(self.product_ids)
+        block[n:n + len(ids)] = emb
+        self.product_embeddings = block[:n + len(ids)]
+        for r, pid, text in zip(new_rows, ids, texts):
+            self.product_ids.append(pid)
+            self.product_texts.append(text)
+            self.pid_to_text[pid] = text
+            self._pid_to_row[pid] = r
+        if codes is not None:
+            self.aisles, self.departments = aisles, departments
+        if self._set_member is not None:
+            self._set_member = np.concatenate([self._set_member, np.zeros((self._set_member.shape[0], len(ids)), bool)], axis=1)
+        self._after_resize()
+
+    def remove_products(self, product_ids) -> None:
+        """Remove products without a re-index: product_ids is a list of ids the catalog has.  Their rows leave the device
+        index in place (DeviceIndex.remove_rows): the last surviving rows move into the places of the removed ones, so
+        the cost follows the number of removed products, not the catalog.  ROW ORDER: afterwards the rows are in the
+        swapped order - .product_ids is the truth, not the corpus file's key order.  product_ids, product_texts,
+        pid_to_text, product_embeddings and the host's set membership follow the moves (a moved product stays in its
+        sets); aisle and department names stay, also those no product carries any more.  The captured single-request
+        graphs are dropped, the IVF index is built again from its centroids.
+        ValueError, with nothing changed: an id the catalog does not have, an id named twice, a list that names every
+        product (product_remove_plan).  An empty list does nothing.  The limits are add_products'."""
+        rows = product_remove_plan(product_ids, self._pid_to_row)
+        if not rows:
+            return
+        dst, src = self._index.remove_rows(rows)
+        new_n = len(self.product_ids) - len(rows)
+        for r in rows:
+            pid = self.product_ids[r]
+            del self.pid_to_text[pid], self._pid_to_row[pid]
+        for d, s in zip(dst.tolist(), src.tolist()):
+            self.product_ids[d], self.product_texts[d] = self.product_ids[s], self.product_texts[s]
+            self._pid_to_row[self.product_ids[d]] = d
+        del self.product_ids[new_n:], self.product_texts[new_n:]
+        block = self._embedding_block(0)
+        block[dst] = block[src]
+        self.product_embeddings = block[:new_n]
+        if self._set_member is not None:
+            self._set_member = apply_moves(self._set_member, new_n, dst, src, axis=1)
+        self._after_resize()
 
     # -- the hot path -------------------------------------------------------------------------
     def _k(self, top_k: int) -> int:

@@ -180,6 +180,41 @@ def cap_pairs(caps, n_queries: int, device=None):
     return torch.from_numpy(out).to(device)
 
 
+def removal_moves(n_rows: int, row_ids):
+    """The move plan of icrec_index_remove_rows, without a device: removing the rows `row_ids` (integers in [0, n_rows),
+    any order, unique, fewer than n_rows) leaves new_n = n_rows - m rows; the holes (removed rows below new_n, ascending)
+    are filled by the surviving rows at or past new_n, ascending -> (new_n, dst int32 [n_moves], src int32 [n_moves]):
+    row src[i] becomes row dst[i], every other surviving row keeps its number.  ValueError for an id out of range, a
+    duplicate, or a removal that would leave nothing."""
+    n_rows = int(n_rows)
+    ids = np.asarray(row_ids)
+    if ids.size == 0:
+        ids = ids.astype(np.int64)
+    if ids.ndim != 1 or ids.dtype.kind not in "iu":
+        raise ValueError(f"removal_moves: row_ids must be a list of integers, got {ids.dtype} {ids.shape}")
+    ids = np.sort(ids.astype(np.int64))
+    if ids.size and (ids[0] < 0 or ids[-1] >= n_rows):
+        raise ValueError(f"removal_moves: row {int(ids[0] if ids[0] < 0 else ids[-1])} is outside 0..{n_rows - 1}")
+    if (np.diff(ids) == 0).any():
+        raise ValueError(f"removal_moves: row {int(ids[1:][np.diff(ids) == 0][0])} is named twice")
+    if ids.size >= n_rows:
+        raise ValueError(f"removal_moves: removing {ids.size} of {n_rows} rows would leave the index empty")
+    new_n = n_rows - int(ids.size)
+    dst = ids[ids < new_n]
+    src = np.setdiff1d(np.arange(new_n, n_rows, dtype=np.int64), ids[ids >= new_n], assume_unique=True)
+    return new_n, dst.astype(np.int32), src.astype(np.int32)
+
+
+def apply_moves(array, new_n: int, dst, src, axis: int = 0):
+    """A per-row host array after a removal: entries src moved onto entries dst along `axis`, cut to new_n (a copy)."""
+    a = np.array(array, copy=True)
+    sel = [slice(None)] * a.ndim
+    sel_d, sel_s, cut = list(sel), list(sel), list(sel)
+    sel_d[axis], sel_s[axis], cut[axis] = np.asarray(dst, np.int64), np.asarray(src, np.int64), slice(0, int(new_n))
+    a[tuple(sel_d)] = a[tuple(sel_s)]
+    return np.ascontiguousarray(a[tuple(cut)])
+
+
 ROW_STORAGE = {"f32": 0, "bf16": 1, "f32+filter": 2, "bf16+filter": 3}  # ICREC_ROWS_* in include/icrec.h
 
 
@@ -336,6 +371,69 @@ class DeviceIndex:
         _native.check(_native.lib().icrec_index_write_facets(self._h, ids.ctypes.data_as(C.c_void_p),
                                                              v.ctypes.data_as(C.c_void_p), int(ids.shape[0])),
                       "icrec_index_write_facets")
+
+    @property
+    def capacity(self) -> int:
+        """Rows the index's device arrays are sized for (n_rows until `reserve`)."""
+        return int(_native.lib().icrec_index_capacity(self._h))
+
+    def reserve(self, capacity: int) -> None:
+        """Size every device array of the index for `capacity` >= n_rows rows (icrec_index_reserve): allocates, copies
+        device to device, frees the old arrays.  Nothing a search returns changes.  A set-up call: never while a search
+        on this index runs; graphs captured over the index must be captured again, an IvfIndex rebuilt."""
+        _native.check(_native.lib().icrec_index_reserve(self._h, int(capacity)), "icrec_index_reserve")
+
+    def append_rows(self, embeddings, facets=None) -> range:
+        """Append rows (icrec_index_append_rows): embeddings [m, dim] of any norm become rows n_rows .. n_rows + m - 1,
+        stored as a fresh index stores them; facets uint8 [m, n_facets], required exactly when the index has facets.
+        The new rows belong to no row set (write_rowset).  A full index reserves max(2 * capacity, n_rows + m) first.
+        Returns the range of the new rows and updates n_rows.  A set-up call under `reserve`'s contract; asynchronous
+        on the current stream."""
+        rows = torch.as_tensor(embeddings)
+        if rows.dim() != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"embeddings must be [m, {self.dim}], got {tuple(rows.shape)}")
+        m = int(rows.shape[0])
+        nf = self.n_facets
+        v = None
+        if (facets is None) != (nf == 0):
+            raise ValueError(f"append_rows: facets must be {'given' if nf else 'None'}: the index has {nf} facets")
+        if facets is not None:
+            v = np.ascontiguousarray(np.asarray(facets))
+            if v.dtype != np.uint8 or v.shape != (m, nf):
+                raise ValueError(f"facets must be uint8 [{m}, {nf}], got {v.dtype} {v.shape}")
+        if m == 0:
+            return range(self.n_rows, self.n_rows)
+        cap = self.capacity
+        if self.n_rows + m > cap:
+            self.reserve(max(2 * cap, self.n_rows + m))
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        _native.check(_native.lib().icrec_index_append_rows(self._h, ptr(rows), m,
+                                                            None if v is None else v.ctypes.data_as(C.c_void_p),
+                                                            stream_ptr(self.device)), "icrec_index_append_rows")
+        first = self.n_rows
+        self.n_rows += m
+        return range(first, self.n_rows)
+
+    def remove_rows(self, row_ids):
+        """Remove the LOCAL rows row_ids (host integers in any order; range and duplicates are checked here, ValueError)
+        by swapping survivors from the tail into their places (icrec_index_remove_rows) -> (dst, src) int32 numpy
+        arrays: row src[i] is now row dst[i], every other surviving row kept its number, and n_rows shrank by
+        len(row_ids) - `removal_moves` states the plan.  The caller applies it to what it keeps per row.  A set-up
+        call under `reserve`'s contract; asynchronous on the current stream."""
+        ids = np.asarray(row_ids.cpu() if isinstance(row_ids, torch.Tensor) else row_ids)
+        ids, _ = self._sorted_rows(ids, int(ids.shape[0]) if ids.ndim == 1 else -1, "remove_rows")
+        m = int(ids.shape[0])
+        if m >= self.n_rows:
+            raise ValueError(f"remove_rows: removing {m} of {self.n_rows} rows would leave the index empty")
+        dst, src = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32)
+        n_moves = C.c_int32(0)
+        ids = np.ascontiguousarray(ids)
+        _native.check(_native.lib().icrec_index_remove_rows(self._h, ids.ctypes.data_as(C.c_void_p), m,
+                                                            dst.ctypes.data_as(C.c_void_p), src.ctypes.data_as(C.c_void_p),
+                                                            C.byref(n_moves), stream_ptr(self.device)),
+                      "icrec_index_remove_rows")
+        self.n_rows -= m
+        return dst[:n_moves.value].copy(), src[:n_moves.value].copy()
 
     def export_filter(self):
         """The filter copy of a "+filter" storage, (hi, lo) float16 [n_rows, dim] on the device: the values the filter
@@ -703,10 +801,12 @@ class IvfIndex:
         _native.check(_native.lib().icrec_ivf_create(self.index._h, ptr(self.centroids), int(self.centroids.shape[0]),
                                                      C.byref(h)), "icrec_ivf_create")
         self._h = h
+        self.n_rows = self.index.n_rows  # the rows of this copy: the index may gain or lose rows until rebuild()
 
     def rebuild(self) -> None:
         """Destroy the IVF and create it again over the same index with the same centroids: the copy of the rows and
-        their assignment as they are after DeviceIndex.write_rows, which an IVF does not see.  A set-up call like the
+        their assignment as they are after DeviceIndex.write_rows, append_rows or remove_rows, which an IVF does not see
+        (after reserve its base's arrays have moved as well).  A set-up call like the
         constructor; a graph captured over the old handle must be captured again."""
         if getattr(self, "_h", None):
             _native.lib().icrec_ivf_destroy(self._h)
@@ -732,7 +832,7 @@ class IvfIndex:
     def layout(self):
         """(perm int32 [n_rows], list_off int64 [n_lists + 1]) device tensors: the local rows sorted by (list, row) and
         the list boundaries in that order."""
-        perm = torch.empty(self.index.n_rows, dtype=torch.int32, device=self.device)
+        perm = torch.empty(self.n_rows, dtype=torch.int32, device=self.device)
         off = torch.empty(self.n_lists + 1, dtype=torch.int64, device=self.device)
         _native.check(_native.lib().icrec_ivf_layout(self._h, ptr(perm), ptr(off), stream_ptr(self.device)),
                       "icrec_ivf_layout")

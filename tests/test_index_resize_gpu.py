@@ -1,0 +1,325 @@
+"""icrec_index_reserve / _append_rows / _remove_rows on the GPU: after any sequence of them the handle is, bit for bit, the
+handle icrec_index_create_ex builds from the resulting matrix, facets and row sets - the stored rows, the filter planes or
+fragments, and what every kernel family finds - for every row storage, with holes, fillers and appended rows on the edges
+of the 32-row fragment tiles, the 32-bit bitmap words and the 256-row rounds (n = 1,061 = 4 x 256 + 32 + 5).  A numpy
+model (matrix, facet bytes, membership of 3 row sets) is edited with the returned moves; every state is compared with a
+FRESH index built from the model."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from instacart_next_order_recommendation_amd import _native
+from instacart_next_order_recommendation_amd.search import (DeviceIndex, IvfIndex, apply_moves, facet_masks, removal_moves,
+                                                            rowset_bits, rowset_ids)
+from tests.search_harness import assert_search, torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+
+N = 1061
+CASES = [("f32", 32), ("f32", 96), ("f32", 384), ("f32", 4096), ("bf16", 64), ("bf16", 384),
+         ("f32+filter", 128), ("f32+filter", 384), ("bf16+filter", 128), ("bf16+filter", 384)]
+CASE_IDS = [f"{s}-{d}" for s, d in CASES]
+K = 20
+ALLOW_KINDS = [(list(range(0, 120, 3)), None), (None, [1, 4, 7]), (list(range(60)), list(range(10))), None, ([7], [5])]
+SET_KINDS = [[0], [1, 2], None, [2], [0, 1, 2]]
+
+
+def bits(t):
+    """A device tensor's elements as unsigned integers of their width, on the host."""
+    a = t.cpu().contiguous()
+    return a.view({2: torch.int16, 4: torch.int32}[a.element_size()]).numpy()
+
+
+class Model:
+    """The host's statement of an index: E float32 [n, dim] the rows it was given, F uint8 [n, 2] their facet bytes,
+    M bool [3, n] the membership of 3 row sets."""
+
+    def __init__(self, rng, n, dim):
+        self.rng, self.dim = rng, dim
+        self.E, self.F, self.M = self.rows(n)
+
+    def rows(self, m):
+        E = self.rng.standard_normal((m, self.dim)).astype(np.float32) * np.float32(3.0)          # (not unit rows)
+        F = np.stack([self.rng.integers(0, 120, m), self.rng.integers(0, 21, m)], axis=1).astype(np.uint8)
+        return E, F, self.rng.random((3, m)) < 0.5
+
+    @property
+    def n(self):
+        return self.E.shape[0]
+
+    def build(self, storage):
+        ix = DeviceIndex(self.E, storage=storage)
+        ix.set_facets(self.F)
+        ix.set_rowsets(rowset_bits(self.M, self.n))
+        return ix
+
+    def remove(self, ix, ids):
+        """Remove rows from the index and from the model with the moves the index returns; the plan is removal_moves'.
+        -> the vectors of the removed rows."""
+        ids = np.asarray(ids, np.int64)
+        gone = self.E[ids].copy()
+        new_n, want_dst, want_src = removal_moves(self.n, ids)
+        dst, src = ix.remove_rows(self.rng.permutation(ids))                                      # (host ids in any order)
+        np.testing.assert_array_equal(dst, want_dst)
+        np.testing.assert_array_equal(src, want_src)
+        assert ix.n_rows == new_n == int(_native.lib().icrec_index_rows(ix._h))
+        self.E, self.F = apply_moves(self.E, new_n, dst, src), apply_moves(self.F, new_n, dst, src)
+        self.M = apply_moves(self.M, new_n, dst, src, axis=1)
+        return gone
+
+    def append(self, ix, m):
+        """Append m new rows to the index and to the model (members of no set) -> their vectors."""
+        E, F, _ = self.rows(m)
+        first = self.n
+        assert ix.append_rows(E, F) == range(first, first + m)
+        assert ix.n_rows == first + m == int(_native.lib().icrec_index_rows(ix._h))
+        self.E, self.F = np.concatenate([self.E, E]), np.concatenate([self.F, F])
+        self.M = np.concatenate([self.M, np.zeros((3, m), bool)], axis=1)
+        return E
+
+
+def assert_same_index(ix, fresh):
+    assert ix.n_rows == fresh.n_rows
+    np.testing.assert_array_equal(bits(ix.export()), bits(fresh.export()))
+    if ix.storage.endswith("filter"):
+        for got, want in zip(ix.export_filter(), fresh.export_filter()):
+            np.testing.assert_array_equal(bits(got), bits(want))
+
+
+def assert_state(ix, model, probes, rng):
+    """ix against a fresh index of the model: the exports, and every search family with the probe vectors (rows that were
+    removed or appended: a ghost row or a missing one shows as a score of 1.0 on one side only) among the queries."""
+    fresh = model.build(ix.storage)
+    try:
+        assert_same_index(ix, fresh)
+        n, dim = model.n, model.dim
+        k = min(K, n)
+        for Q in (1, 8, 40, 256):                   # streaming, tiled, and in the filter storages the filter pass
+            q = rng.standard_normal((Q, dim)).astype(np.float32)
+            take = min(Q, len(probes))
+            q[:take] = probes[(np.arange(take) + Q) % len(probes)]
+            qd = torch.from_numpy(q).to(ix.device)
+            want = [t.cpu().numpy() for t in fresh.search(qd, k)]
+            assert_search(ix.search(qd, k), want)
+            assert (want[0] < n).all()
+            allow = [ALLOW_KINDS[i % len(ALLOW_KINDS)] for i in range(Q)]
+            masks = facet_masks(allow, Q, 2, ix.device)
+            got, want = ix.search(qd, k, allow=masks), fresh.search(qd, k, allow=masks)
+            assert_search(got, [t.cpu().numpy() for t in want])
+            sets = rowset_ids([SET_KINDS[i % len(SET_KINDS)] for i in range(Q)], Q, device=ix.device)
+            got, want = ix.search(qd, k, sets=sets), fresh.search(qd, k, sets=sets)
+            assert_search(got, [t.cpu().numpy() for t in want])
+            if Q == 40:   # the sets bind: a query restricted to set 0 returns members of set 0 alone
+                rows = want[0].cpu().numpy()[0]
+                assert model.M[0][rows[rows >= 0]].all() and not model.M[0].all()
+        q = torch.from_numpy(np.concatenate([probes[:2], rng.standard_normal((1, dim)).astype(np.float32)])).to(ix.device)
+        order = ix.rank_all(q)
+        assert tuple(order.shape) == (3, n)
+        np.testing.assert_array_equal(order.cpu().numpy(), fresh.rank_all(q).cpu().numpy())
+    finally:
+        fresh.close()
+
+
+@pytest.mark.parametrize("storage,dim", CASES, ids=CASE_IDS)
+def test_resized_index_is_the_fresh_index(torch_cuda, storage, dim):
+    rng = np.random.default_rng(2000 + dim + len(storage))
+    model = Model(rng, N, dim)
+    ix = model.build(storage)
+    lib = _native.lib()
+    try:
+        assert ix.capacity == N
+        some = model.E[[0, 1060]].copy()
+        # (a) capacity alone: nothing observable changes (the row set stride does: rowset_words(1300) != rowset_words(1061))
+        ix.reserve(1300)
+        assert ix.capacity == 1300 and ix.n_rows == N
+        assert_state(ix, model, some, rng)
+        # (d) hole and filler in one bitmap word and one 32-row fragment tile: 1059 -> 1057, 1060 -> 1058
+        model.M[:, 1057:1061] = np.asarray([[1, 0, 0, 1], [0, 1, 1, 0], [1, 1, 0, 0]], bool)
+        ix.write_rowset(0, rowset_bits(model.M[:1], N)[0])                                       # (at the new stride)
+        ix.write_rowset(1, rowset_bits(model.M[1:2], N)[0])
+        ix.write_rowset(2, rowset_bits(model.M[2:], N)[0])
+        gone = model.remove(ix, [1057, 1058])
+        assert model.n == 1059
+        assert_state(ix, model, np.concatenate([gone, model.E[1057:1059]]), rng)
+        # (e) every id >= new_n: no moves; the removed rows are members of sets (their bits must not outlive them)
+        model.M[:, 1057:1059] = True
+        for s in range(3):
+            ix.write_rowset(s, rowset_bits(model.M[s:s + 1], model.n)[0])
+        gone = model.remove(ix, [1057, 1058])
+        assert model.n == 1057
+        assert_state(ix, model, gone, rng)
+        # (f) m = 0
+        before = bits(ix.export())
+        assert model.remove(ix, []).shape[0] == 0
+        assert ix.append_rows(np.zeros((0, dim), np.float32), np.zeros((0, 2), np.uint8)) == range(1057, 1057)
+        np.testing.assert_array_equal(bits(ix.export()), before)
+        # (g), (i) 2 rows into the ragged tile, into the slots just freed: they are members of no set
+        new = model.append(ix, 2)
+        assert_state(ix, model, np.concatenate([new, gone]), rng)
+        new = model.append(ix, 2)
+        model.M[:, 1059] = True                                                                  # an appended row joins the sets
+        for s in range(3):
+            ix.write_rowset(s, rowset_bits(model.M[s:s + 1], model.n)[0])
+        assert_state(ix, model, new, rng)
+        # (c) new_n = 1,025: one more than a round
+        tail = rng.permutation(np.arange(1025, 1061))[:33]
+        gone = model.remove(ix, np.concatenate([[3, 1000, 1024], tail]))
+        assert model.n == 1025
+        assert_state(ix, model, np.concatenate([gone[:8], model.E[[3, 1000, 1024]]]), rng)
+        new = model.append(ix, 36)                                                               # across the 32-row edge at 1,056
+        assert_state(ix, model, new[[0, 30, 31, 35]], rng)
+        # (b) new_n = 1,024, exactly a round: holes on the tile, word and round edges, the other ids in the tail
+        tail = rng.permutation(np.arange(1024, 1061))[:31]
+        gone = model.remove(ix, np.concatenate([[0, 31, 32, 255, 256, 1023], tail]))
+        assert model.n == 1024
+        assert_state(ix, model, np.concatenate([gone[:6], model.E[[0, 31, 32, 255, 256, 1023]]]), rng)
+        gone = model.remove(ix, [7, 640, 1019, 1021, 1023])
+        assert model.n == 1019
+        assert_state(ix, model, np.concatenate([gone, model.E[[7, 640]]]), rng)
+        # (h) across the 32-row and 256-row edges at 1,024 and 1,280, to the capacity exactly
+        new = model.append(ix, 281)
+        assert model.n == 1300 == ix.capacity
+        assert_state(ix, model, new[[0, 4, 5, 260, 261, 280]], rng)
+        rows = torch.zeros((1, dim), device=ix.device)
+        f = np.zeros((1, 2), np.uint8)
+        assert lib.icrec_index_append_rows(ix._h, C.c_void_p(rows.data_ptr()), 1, f.ctypes.data_as(C.c_void_p), None) == -1
+        assert b"capacity" in lib.icrec_last_error()                                             # full at the C ABI
+        # (j) DeviceIndex.append_rows past the capacity grows it
+        new = model.append(ix, 5)
+        assert ix.capacity == 2600 and model.n == 1305
+        assert_state(ix, model, new, rng)
+    finally:
+        ix.close()
+
+
+def test_refusals_change_nothing(torch_cuda):
+    rng = np.random.default_rng(23)
+    dim = 384
+    model = Model(rng, N, dim)
+    ix = model.build("f32+filter")
+    plain = DeviceIndex(model.E[:40])
+    lib = _native.lib()
+    try:
+        ix.reserve(1100)
+        before = bits(ix.export())
+        dst, src = np.zeros(N, np.int32), np.zeros(N, np.int32)
+        n_moves = C.c_int32(-7)
+
+        def remove(handle, ids):
+            a = np.asarray(ids, np.int32)
+            return lib.icrec_index_remove_rows(handle, a.ctypes.data_as(C.c_void_p), a.size, dst.ctypes.data_as(C.c_void_p),
+                                               src.ctypes.data_as(C.c_void_p), C.byref(n_moves), None)
+
+        for bad, why in (([5, 3], b"ascending"), ([3, 3], b"ascending"), ([3, N], b"outside"), ([-1, 3], b"outside"),
+                         (np.arange(N), b"empty")):
+            assert remove(ix._h, bad) == -1
+            assert why in lib.icrec_last_error(), lib.icrec_last_error()
+        assert n_moves.value == -7 and not dst.any() and not src.any()
+        rows = torch.from_numpy(model.E[:40]).to(ix.device)
+        f = model.F[:40].copy()
+        assert lib.icrec_index_append_rows(ix._h, C.c_void_p(rows.data_ptr()), 40, f.ctypes.data_as(C.c_void_p), None) == -1
+        assert b"capacity" in lib.icrec_last_error()                                             # 1,061 + 40 > 1,100
+        assert lib.icrec_index_append_rows(ix._h, C.c_void_p(rows.data_ptr()), 2, None, None) == -1
+        assert b"facets_host is required" in lib.icrec_last_error()                              # a faceted index
+        assert lib.icrec_index_append_rows(plain._h, C.c_void_p(rows.data_ptr()), 0, None, None) == 0
+        assert lib.icrec_index_append_rows(ix._h, None, 2, f.ctypes.data_as(C.c_void_p), None) == -1
+        assert lib.icrec_index_append_rows(ix._h, C.c_void_p(rows.data_ptr()), -1, f.ctypes.data_as(C.c_void_p), None) == -1
+        assert lib.icrec_index_reserve(ix._h, N - 1) == -1
+        assert b"below" in lib.icrec_last_error()
+        assert lib.icrec_index_reserve(ix._h, 2**32) == -1
+        with pytest.raises(ValueError, match="named twice"):
+            ix.remove_rows([3, 3])
+        with pytest.raises(ValueError, match="outside"):
+            ix.remove_rows([N])
+        with pytest.raises(ValueError, match="empty"):
+            ix.remove_rows(np.arange(N))
+        with pytest.raises(ValueError, match="facets"):
+            ix.append_rows(model.E[:2])
+        with pytest.raises(ValueError, match="facets"):
+            plain.append_rows(np.zeros((2, dim), np.float32), f[:2])
+        with pytest.raises(_native.IcrecError, match="below"):
+            ix.reserve(5)
+        assert ix.n_rows == N == int(lib.icrec_index_rows(ix._h)) and ix.capacity == 1100 and plain.capacity == 40
+        np.testing.assert_array_equal(bits(ix.export()), before)
+        assert_state(ix, model, model.E[:2], rng)
+        # an index without facets or sets: the same calls, nothing but rows to move; reserve may shrink down to n_rows
+        plain.reserve(64)
+        assert plain.append_rows(model.E[40:60]) == range(40, 60)
+        d, s = plain.remove_rows([0, 59, 31])
+        E = apply_moves(model.E[:60], 57, d, s)
+        plain.reserve(57)
+        assert plain.capacity == 57
+        fresh = DeviceIndex(E)
+        assert_same_index(plain, fresh)
+        q = torch.from_numpy(model.E[[0, 59, 58, 31]]).to(ix.device)
+        assert_search(plain.search(q, K), [t.cpu().numpy() for t in fresh.search(q, K)])
+        fresh.close()
+    finally:
+        ix.close()
+        plain.close()
+
+
+GRAPH_CASES = [("f32", 384, (1, 40)), ("bf16+filter", 384, (1, 256))]
+
+
+@pytest.mark.parametrize("storage,dim,Qs", GRAPH_CASES, ids=[f"{s}-{d}" for s, d, _ in GRAPH_CASES])
+def test_graph_captured_after_a_resize(torch_cuda, storage, dim, Qs):
+    rng = np.random.default_rng(29)
+    model = Model(rng, N, dim)
+    ix = model.build(storage)
+    try:
+        gone = model.remove(ix, [0, 31, 1040, 1060])
+        new = model.append(ix, 70)                                                               # (grows: every pointer moves)
+        assert ix.capacity == 2 * N
+        fresh = model.build(storage)
+        for Q in Qs:
+            q = rng.standard_normal((Q, dim)).astype(np.float32)
+            q[0] = new[69]
+            if Q > 4:
+                q[1:5] = gone
+            qd = torch.from_numpy(q).to(ix.device)
+            idx = torch.empty((Q, K), dtype=torch.int64, device=ix.device)
+            sc = torch.empty((Q, K), dtype=torch.float32, device=ix.device)
+            ws = torch.empty(int(_native.lib().icrec_search_workspace_bytes(ix._h, Q, K)), dtype=torch.uint8, device=ix.device)
+            ix.search_into(qd, K, None, None, idx, sc, ws=ws)                                    # first launches outside the capture
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                ix.search_into(qd, K, None, None, idx, sc, ws=ws)
+            idx.fill_(-5)
+            g.replay()
+            torch.cuda.synchronize()
+            assert_search((idx, sc), [t.cpu().numpy() for t in fresh.search(qd, K)])
+            assert idx[0, 0].item() == model.n - 1
+        fresh.close()
+    finally:
+        ix.close()
+
+
+@pytest.mark.parametrize("storage", ["f32", "bf16"])
+def test_ivf_rebuilt_after_a_resize(torch_cuda, storage):
+    rng = np.random.default_rng(31)
+    dim = 384
+    model = Model(rng, N, dim)
+    ix = model.build(storage)
+    cent = rng.standard_normal((8, dim)).astype(np.float32)
+    ivf = IvfIndex(ix, cent)
+    try:
+        gone = model.remove(ix, [0, 255, 256, 1030, 1060])
+        new = model.append(ix, 9)
+        assert tuple(ivf.layout()[0].shape) == (N,)                                              # the stale copy keeps its own size
+        ivf.rebuild()
+        assert tuple(ivf.layout()[0].shape) == (model.n,)
+        q = np.concatenate([gone, new, rng.standard_normal((26, dim)).astype(np.float32)])
+        fresh = model.build(storage)
+        want = [t.cpu().numpy() for t in fresh.search(q, K)]
+        assert_search(ivf.search(q, K, ivf.n_lists), want)
+        assert_search(ix.search(q, K), want)
+        fresh.close()
+    finally:
+        ivf.close()
+        ix.close()
