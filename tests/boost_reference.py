@@ -60,10 +60,10 @@ def _valid_listed(rows, n, excl_i, admit_i):
     return ok
 
 
-def full_catalog(scores, lists, top_k, excl=None, admit=None, only=False, row_offset=0, max_boosts=None):
-    """scores: catalog_scores' [Q, n]; lists: per-query (rows, weights); excl: per-query local rows or None; admit: bool
-    [Q, n] or None -> (idx int64 [Q, top_k], score float32 [Q, top_k]) with -1 / 0 pads: the top_k of the whole catalog
-    under the adjusted scores.  only=True: of the listed rows alone."""
+def adjusted_catalog(scores, lists, excl=None, admit=None, only=False, max_boosts=None):
+    """The ranking a boosted request selects from: scores with the valid listed rows' entries replaced by their adjusted
+    scores, and the admission that goes with it (only=True: the listed rows alone) -> (adjusted float32 [Q, n], admit
+    bool [Q, n] or None).  full_catalog takes its top_k; a capped walk (cap_reference.greedy_walk) walks all of it."""
     Q, n = scores.shape
     adjusted = np.array(scores, np.float32)
     listed = np.zeros((Q, n), bool)
@@ -74,6 +74,14 @@ def full_catalog(scores, lists, top_k, excl=None, admit=None, only=False, row_of
         listed[i, rows[ok]] = True
     if only:
         admit = listed if admit is None else admit & listed
+    return adjusted, admit
+
+
+def full_catalog(scores, lists, top_k, excl=None, admit=None, only=False, row_offset=0, max_boosts=None):
+    """scores: catalog_scores' [Q, n]; lists: per-query (rows, weights); excl: per-query local rows or None; admit: bool
+    [Q, n] or None -> (idx int64 [Q, top_k], score float32 [Q, top_k]) with -1 / 0 pads: the top_k of the whole catalog
+    under the adjusted scores.  only=True: of the listed rows alone."""
+    adjusted, admit = adjusted_catalog(scores, lists, excl, admit, only, max_boosts)
     return select_from_scores(adjusted, top_k, excl, row_offset, admit)
 
 

@@ -62,6 +62,18 @@ def cap_select(F, cand, score, caps, top_k, n_prior=None, out_idx=None, out_scor
     return idx, sc, state, nxt
 
 
+def _ranked(scores_row, rows, head=4096):
+    """`rows` in full_ranking's order, lazily: of a long list first the rows that score above its head-th best, ranked
+    among themselves, and the others only if the walk gets that far."""
+    if rows.size <= 4 * head:
+        yield from rows[full_ranking(scores_row[rows])]
+        return
+    s = scores_row[rows]
+    bar = np.partition(s, rows.size - head)[rows.size - head]
+    for part in (rows[s > bar], rows[~(s > bar)]):
+        yield from part[full_ranking(scores_row[part])]
+
+
 def greedy_walk(scores, F, caps, top_k, excl=None, admit=None, row_offset=0):
     """The one-pass statement: per query the complete ranking of its admissible rows (score descending, row ascending,
     -0 as +0; excl[i] and admit [Q, n] as select_from_scores takes them), walked once from the best row down, keeping a
@@ -80,10 +92,10 @@ def greedy_walk(scores, F, caps, top_k, excl=None, admit=None, row_offset=0):
         count = np.zeros((F.shape[1], 256), np.int64)
         capped = [f for f in range(F.shape[1]) if caps[q, f] > 0]
         m = 0
-        for r in full_ranking(scores[q]):
+        for r in _ranked(scores[q], np.flatnonzero(ok)):
             if m == top_k:
                 break
-            if ok[r] and all(count[f, F[r, f]] < caps[q, f] for f in capped):
+            if all(count[f, F[r, f]] < caps[q, f] for f in capped):
                 idx[q, m], sc[q, m] = row_offset + r, scores[q, r] + np.float32(0.0)
                 m += 1
                 count[np.arange(F.shape[1]), F[r]] += 1

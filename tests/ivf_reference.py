@@ -43,16 +43,33 @@ def probes(q, C, nprobe):
     return oracle.search(q, C, nprobe)[0]
 
 
-def search(q, P, C, k, nprobe, excl=None, row_offset=0, storage="f32", assignment=None):
-    """The IVF search's result (idx int64 [Q, k], score float32 [Q, k]).  assignment: assign(stored_rows(P, storage), C)
-    where the caller has it already."""
+def search(q, P, C, k, nprobe, excl=None, row_offset=0, storage="f32", assignment=None, scores=None):
+    """The IVF search's result (idx int64 [Q, k], score float32 [Q, k]).  assignment: assign(stored_rows(P, storage), C),
+    scores: oracle.scores(oracle.normalize_rows(q), stored_rows(P, storage)), where the caller has them already."""
     q = np.ascontiguousarray(q, np.float32)
-    P_stored = stored_rows(P, storage)
+    if assignment is None or scores is None:
+        P_stored = stored_rows(P, storage)
     if assignment is None:
         assignment = assign(P_stored, C)
+    if scores is None:
+        scores = oracle.scores(oracle.normalize_rows(q), P_stored)
     pr = probes(q, C, nprobe)
-    admit = (assignment[None, None, :] == pr[:, :, None]).any(axis=1)
-    return search_harness.select_from_scores(oracle.scores(oracle.normalize_rows(q), P_stored), k, excl, row_offset, admit)
+    admit = np.zeros(scores.shape, bool)
+    for j in range(pr.shape[1]):
+        admit |= assignment[None, :] == pr[:, j, None]
+    return search_harness.select_from_scores(scores, k, excl, row_offset, admit)
+
+
+MERGE_MAX_LISTS = search_harness.MERGE_MAX_LISTS
+
+
+def plan_slices(n_cu, Q, nprobe):
+    """csrc/ivf.hip's plan_slices restated: the slices S every probed list of a call is cut into; slice s of a list of
+    `tiles` 256-row tiles walks tiles [s * tps, (s + 1) * tps), tps = ceil(tiles / S)."""
+    target, items = 2 * n_cu, Q * nprobe
+    if items >= target:
+        return 1
+    return min((target + items - 1) // items, MERGE_MAX_LISTS // nprobe)
 
 
 # ---------------------------------------------------------------- the crafted catalog

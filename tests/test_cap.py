@@ -28,6 +28,21 @@ def native():
 
 
 # ---------------------------------------------------------------- the reference against a brute-force walk
+def test_lazy_ranking_is_the_full_ranking():
+    """cap_reference._ranked, whose long-list branch ranks the head first, against full_ranking of the same rows: ties
+    across the bar, -0 beside +0, all rows equal, and a head longer than, equal to and shorter than the list."""
+    from tests.search_harness import full_ranking
+
+    rng = np.random.default_rng(5)
+    for n, head, values in ((300, 8, 7), (300, 8, 1), (33, 8, 3), (32, 8, 5), (500, 16, 40), (64, 1, 2)):
+        s = rng.integers(-values, values + 1, n).astype(np.float32) * np.float32(0.25)
+        s[rng.random(n) < 0.2] *= np.float32(-0.0) if values > 1 else np.float32(1)        # some zeros of either sign
+        rows = np.flatnonzero(rng.random(n) < 0.8)
+        want = rows[full_ranking(s[rows])]
+        np.testing.assert_array_equal(np.fromiter(ref._ranked(s, rows, head=head), np.int64), want)
+        np.testing.assert_array_equal(np.fromiter(ref._ranked(s, rows), np.int64), want)
+
+
 def brute_force(F, cand, caps, top_k):
     """One query without priors, pads or duplicates, written the other way round: candidate j is kept iff, for every
     capped facet, fewer than cap of the KEPT candidates before it share its value - decided from the kept set, with

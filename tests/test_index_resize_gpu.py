@@ -13,8 +13,9 @@ import pytest
 import torch
 
 from instacart_next_order_recommendation_amd import _native
-from instacart_next_order_recommendation_amd.search import (DeviceIndex, IvfIndex, apply_moves, facet_masks, removal_moves,
-                                                            rowset_bits, rowset_ids)
+from instacart_next_order_recommendation_amd.search import (DeviceIndex, IvfIndex, apply_moves, facet_masks, rowset_bits,
+                                                            rowset_ids)
+from tests.index_model import Model
 from tests.search_harness import assert_search, torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -32,54 +33,6 @@ def bits(t):
     """A device tensor's elements as unsigned integers of their width, on the host."""
     a = t.cpu().contiguous()
     return a.view({2: torch.int16, 4: torch.int32}[a.element_size()]).numpy()
-
-
-class Model:
-    """The host's statement of an index: E float32 [n, dim] the rows it was given, F uint8 [n, 2] their facet bytes,
-    M bool [3, n] the membership of 3 row sets."""
-
-    def __init__(self, rng, n, dim):
-        self.rng, self.dim = rng, dim
-        self.E, self.F, self.M = self.rows(n)
-
-    def rows(self, m):
-        E = self.rng.standard_normal((m, self.dim)).astype(np.float32) * np.float32(3.0)          # (not unit rows)
-        F = np.stack([self.rng.integers(0, 120, m), self.rng.integers(0, 21, m)], axis=1).astype(np.uint8)
-        return E, F, self.rng.random((3, m)) < 0.5
-
-    @property
-    def n(self):
-        return self.E.shape[0]
-
-    def build(self, storage):
-        ix = DeviceIndex(self.E, storage=storage)
-        ix.set_facets(self.F)
-        ix.set_rowsets(rowset_bits(self.M, self.n))
-        return ix
-
-    def remove(self, ix, ids):
-        """Remove rows from the index and from the model with the moves the index returns; the plan is removal_moves'.
-        -> the vectors of the removed rows."""
-        ids = np.asarray(ids, np.int64)
-        gone = self.E[ids].copy()
-        new_n, want_dst, want_src = removal_moves(self.n, ids)
-        dst, src = ix.remove_rows(self.rng.permutation(ids))                                      # (host ids in any order)
-        np.testing.assert_array_equal(dst, want_dst)
-        np.testing.assert_array_equal(src, want_src)
-        assert ix.n_rows == new_n == int(_native.lib().icrec_index_rows(ix._h))
-        self.E, self.F = apply_moves(self.E, new_n, dst, src), apply_moves(self.F, new_n, dst, src)
-        self.M = apply_moves(self.M, new_n, dst, src, axis=1)
-        return gone
-
-    def append(self, ix, m):
-        """Append m new rows to the index and to the model (members of no set) -> their vectors."""
-        E, F, _ = self.rows(m)
-        first = self.n
-        assert ix.append_rows(E, F) == range(first, first + m)
-        assert ix.n_rows == first + m == int(_native.lib().icrec_index_rows(ix._h))
-        self.E, self.F = np.concatenate([self.E, E]), np.concatenate([self.F, F])
-        self.M = np.concatenate([self.M, np.zeros((3, m), bool)], axis=1)
-        return E
 
 
 def assert_same_index(ix, fresh):
