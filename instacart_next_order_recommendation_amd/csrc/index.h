@@ -1,8 +1,9 @@
-// index.h — what an icrec_index handle points to, shared by index.hip (which creates and destroys it), search.hip
-// (which builds its filter storage and searches it), sort.hip (icrec_rank_all), mmr.hip and boost.hip (which read its
-// stored rows), cap.hip (which reads its facet words), and the device code that index.hip, search.hip and boost.hip share: the row normalisation kernel, the
-// exclusion search, the facet test and the row set words.  What needs no handle - the shard row rule, the gathered
-// exact-cosine tile that mmr.hip and boost.hip read the stored rows with - is in common.h.
+// index.h — what an icrec_index handle points to, shared by index.hip (which creates, edits and destroys it),
+// storage.hip (which writes, moves, clears, resizes and exports what it keeps per row; storage.h), search.hip (which
+// searches it), sort.hip (icrec_rank_all), mmr.hip and boost.hip (which read its stored rows), cap.hip (which reads its
+// facet words), and the device code that index.hip, storage.hip, search.hip and boost.hip share: the row normalisation
+// kernel, the exclusion search, the facet test and the row set words.  What needs no handle - the shard row rule, the
+// gathered exact-cosine tile that mmr.hip and boost.hip read the stored rows with - is in common.h.
 #pragma once
 
 #include <type_traits>
@@ -11,12 +12,15 @@
 
 namespace icrec {
 
+// The filter pass's copy of the rows of a *_FILTER storage, in one of two layouts (storage.h): both planes, or `frag`.
+struct FilterStorage {
+    _Float16 *plane_hi = nullptr, *plane_lo = nullptr;  // staged filter pass: row-major f16 hi/lo planes of `rows`
+    _Float16* frag = nullptr;                           // resident filter pass (dim 384): frag_row_tiles(capacity) tiles of packed fragments
+};
+
 struct Index {
     void* rows = nullptr;  // normalised [n_rows, dim], fp32 or bf16 bits
-    _Float16* plane_hi = nullptr;  // ICREC_ROWS_F32_FILTER: f16 hi/lo planes of `rows` for the filter pass
-    _Float16* plane_lo = nullptr;
-    _Float16* frag = nullptr;      // resident filter pass (dim 384, <= RES_MAX_ROWS rows): the rows as packed fragments
-    int64_t frag_row_tiles = 0;    // 32-row tiles in `frag` (whole rounds of CfgRes::BM rows)
+    FilterStorage filter;
     int storage = ICREC_ROWS_F32;
     int64_t n_rows = 0;
     int64_t capacity = 0;          // rows every array is sized for (>= n_rows; == n_rows until icrec_index_reserve)
@@ -40,39 +44,13 @@ struct Index {
 // Words of one row set on the device, for an index of that capacity: ceil(n_rows / 32) bitmap words, zero padded to whole 256-row tiles (8 words per
 // tile, the widest tile any search kernel walks), as the facet words are: every tile of every kernel reads inside it.
 static inline int64_t rowset_words(int64_t n_rows) { return (n_rows + 255) / 256 * 8; }
+// Facet words of an index of that capacity: one per row, zero padded to the same whole 256-row tiles.
+static inline int64_t facet_words(int64_t capacity) { return (capacity + 255) / 256 * 256; }
 
 static inline bool rows_are_bf16(const Index* ix) { return ix->storage == ICREC_ROWS_BF16 || ix->storage == ICREC_ROWS_BF16_FILTER; }
 // One stored value of `rows` in a kernel templated on "the rows are bf16": bf16 bits or a float.
 template <bool P16>
 using row_elem_t = std::conditional_t<P16, uint16_t, float>;
-
-// search.hip, for index.hip's icrec_index_create_ex: the filter pass's copy of the normalised rows of a *_FILTER
-// storage (whose dim is a multiple of FILTER_DIM_STEP), in the layout of the pass that will read it - `frag` or the two
-// planes.  Allocates and launches on the null stream; ICREC_ENOMEM (a hipMalloc failed) or ICREC_EHIP with the error
-// text set.
-constexpr int FILTER_DIM_STEP = 64;
-int build_filter_storage(Index* ix);
-// search.hip, for index.hip's icrec_index_write_rows (arguments checked, m >= 1): rows row_ids_dev[0 .. m) of the index
-// - the stored rows and, in a *_FILTER storage, their planes or fragment slots - become what icrec_index_create_ex
-// makes of rows_dev[0 .. m), in one launch on `st`; ids outside [0, n_rows) are skipped on the device.  And for
-// icrec_index_export_filter (the handle has a filter copy): that copy as row-major f16 bits [n_rows, dim] each.
-// With row_ids_dev == NULL (icrec_index_append_rows) the written rows are base_row .. base_row + m - 1 instead, tested
-// against n_rows = base_row + m.
-int write_index_rows(Index* ix, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, int64_t base_row, hipStream_t st);
-int export_filter_storage(const Index* ix, uint16_t* hi_dev, uint16_t* lo_dev, hipStream_t st);
-// search.hip, for icrec_index_reserve: the handle's filter copy (planes or fragments, whichever it has) allocated for
-// `capacity` rows, the fragments zeroed, with the copy of the live rows launched on the null stream.  ICREC_ENOMEM with
-// nothing allocated; the handle is not changed.
-struct FilterStorage {
-    _Float16 *plane_hi = nullptr, *plane_lo = nullptr, *frag = nullptr;
-    int64_t frag_row_tiles = 0;
-};
-int reserve_filter_storage(const Index* ix, int64_t capacity, FilterStorage* out);
-// search.hip, for icrec_index_remove_rows (arguments checked): moves src[i] -> dst[i] of everything the index keeps per
-// row (dst, src: device arrays of n_moves entries, dst < new_n <= src < old_n), then the fragment slots, facet words and
-// row set bits of rows [new_n, old_n) cleared; two launches on `st`, the second behind the first.
-int move_index_rows(Index* ix, const int32_t* dst_dev, const int32_t* src_dev, int32_t n_moves, int64_t new_n, int64_t old_n,
-                    hipStream_t st);
 
 #ifdef __HIPCC__
 

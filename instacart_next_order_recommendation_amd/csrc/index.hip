@@ -1,17 +1,27 @@
 // index.hip — the life cycle of an icrec_index handle (index.h: struct Index): creation with row normalisation,
 // facets, row sets, rows and facets rewritten in place, capacity reserved, rows appended and removed in place, export, the
-// accessors and destruction; and icrec_normalize_rows.
-// The filter storages' layout belongs to the kernels that read it: search.hip builds it (build_filter_storage), rewrites
-// it with the rows (write_index_rows), moves and clears it with them (move_index_rows), re-allocates it
-// (reserve_filter_storage) and un-packs it (export_filter_storage).
+// accessors and destruction; and icrec_normalize_rows.  It checks the arguments and owns the host side (facet words, row
+// sets, the move plan); what the handle keeps per row on the device is written by storage.hip (storage.h).
 #include <stdlib.h>
 
 #include <new>
 #include <vector>
 
-#include "index.h"
+#include "storage.h"
 
 namespace icrec {
+
+// Row i's facet word from the caller's n_facets (1 or 2) bytes per row: facet 0 in the low byte.
+static inline uint16_t facet_word(const uint8_t* b, size_t i, int n_facets) { return n_facets == 1 ? b[i] : (uint16_t)(b[2 * i] | (b[2 * i + 1] << 8)); }
+
+// m host row ids, ascending, unique, inside [0, n_rows); `fn`: the entry point, for the error text.
+static int check_row_ids(const char* fn, const int32_t* ids, int32_t m, int64_t n_rows) {
+    for (int32_t i = 0; i < m; ++i) {
+        ICREC_REQUIRE(ids[i] >= 0 && ids[i] < n_rows, "%s: row %d is outside [0, %lld)", fn, ids[i], (long long)n_rows);
+        ICREC_REQUIRE(i == 0 || ids[i] > ids[i - 1], "%s: the rows must be ascending and unique", fn);
+    }
+    return ICREC_OK;
+}
 
 // bf16 rows widened back to fp32 (icrec_index_export)
 __global__ __launch_bounds__(256) void widen_bf16_kernel(const uint16_t* __restrict__ in, float* __restrict__ out, int64_t n) {
@@ -116,14 +126,9 @@ int32_t icrec_index_device(const icrec_index* h) { return h ? reinterpret_cast<c
 int icrec_index_destroy(icrec_index* h) {
     Index* ix = reinterpret_cast<Index*>(h);
     if (!ix) return ICREC_OK;
-    hipSetDevice(ix->device);
-    hipFree(ix->rows);
-    hipFree(ix->plane_hi);
-    hipFree(ix->plane_lo);
-    hipFree(ix->frag);
-    hipFree(ix->facets);
-    (void)hipFree(ix->rowsets);
-    (void)hipFree(ix->plan_dev);
+    (void)hipSetDevice(ix->device);
+    (void)hipFree(ix->rows); (void)hipFree(ix->facets); (void)hipFree(ix->rowsets); (void)hipFree(ix->plan_dev);
+    free_filter_storage(&ix->filter);
     (void)hipHostFree(ix->stage_host);
     if (ix->stage_event) (void)hipEventDestroy(ix->stage_event);
     delete ix;
@@ -143,10 +148,9 @@ int icrec_index_set_facets(icrec_index* h, const uint8_t* facets_host, int32_t n
     ICREC_REQUIRE(n_facets >= 1 && n_facets <= ICREC_MAX_FACETS, "icrec_index_set_facets: n_facets must be in [1, %d] (got %d)",
                   ICREC_MAX_FACETS, n_facets);
     // one word per row, zero padded to whole 256-row tiles (the widest tile any search kernel walks) of the capacity
-    const size_t padded = (size_t)((ix->capacity + 255) / 256) * 256;
+    const size_t padded = (size_t)facet_words(ix->capacity);
     std::vector<uint16_t> words(padded, 0);
-    for (int64_t i = 0; i < ix->n_rows; ++i)
-        words[i] = n_facets == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * i] | (facets_host[2 * i + 1] << 8));
+    for (int64_t i = 0; i < ix->n_rows; ++i) words[i] = facet_word(facets_host, (size_t)i, n_facets);
     uint16_t* dev = nullptr;
     if (hipMalloc(&dev, padded * 2) != hipSuccess) {
         set_error("icrec_index_set_facets: hipMalloc of %zu bytes failed", padded * 2);
@@ -267,7 +271,7 @@ int icrec_index_reserve(icrec_index* h, int64_t capacity) {
     ICREC_HIP(hipSetDevice(ix->device));
     ICREC_HIP(hipDeviceSynchronize());  // whatever still reads or writes the old arrays, on any stream
     const size_t row_bytes = (size_t)ix->dim * (rows_are_bf16(ix) ? 2 : 4);
-    const size_t facet_words = (size_t)((capacity + 255) / 256) * 256;
+    const size_t n_facet_words = (size_t)facet_words(capacity);
     const size_t old_words = (size_t)rowset_words(ix->capacity), new_words = (size_t)rowset_words(capacity);
     void* rows = nullptr;
     uint16_t* facets = nullptr;
@@ -275,11 +279,11 @@ int icrec_index_reserve(icrec_index* h, int64_t capacity) {
     FilterStorage fs;
     auto drop = [&](int rc) {  // the handle keeps its arrays: free the new ones
         (void)hipFree(rows); (void)hipFree(facets); (void)hipFree(rowsets);
-        (void)hipFree(fs.plane_hi); (void)hipFree(fs.plane_lo); (void)hipFree(fs.frag);
+        free_filter_storage(&fs);
         return rc;
     };
     if (hipMalloc(&rows, (size_t)capacity * row_bytes) != hipSuccess ||
-        (ix->facets && hipMalloc(&facets, facet_words * 2) != hipSuccess) ||
+        (ix->facets && hipMalloc(&facets, n_facet_words * 2) != hipSuccess) ||
         (ix->rowsets && hipMalloc(&rowsets, new_words * 4 * ix->n_rowsets) != hipSuccess)) {
         set_error("icrec_index_reserve: hipMalloc for %lld rows failed", (long long)capacity);
         return drop(ICREC_ENOMEM);
@@ -287,7 +291,7 @@ int icrec_index_reserve(icrec_index* h, int64_t capacity) {
     if (int rc = reserve_filter_storage(ix, capacity, &fs)) return drop(rc);
     hipError_t e = hipMemcpyAsync(rows, ix->rows, (size_t)ix->n_rows * row_bytes, hipMemcpyDeviceToDevice, 0);
     if (e == hipSuccess && facets) {  // the words past n_rows are zero in the old array too
-        e = hipMemsetAsync(facets, 0, facet_words * 2, 0);
+        e = hipMemsetAsync(facets, 0, n_facet_words * 2, 0);
         if (e == hipSuccess) e = hipMemcpyAsync(facets, ix->facets, (size_t)ix->n_rows * 2, hipMemcpyDeviceToDevice, 0);
     }
     if (e == hipSuccess && rowsets) {  // set by set: the stride changes; the live words of a set are a prefix of both strides
@@ -303,10 +307,8 @@ int icrec_index_reserve(icrec_index* h, int64_t capacity) {
         return drop(ICREC_EHIP);
     }
     (void)hipFree(ix->rows); (void)hipFree(ix->facets); (void)hipFree(ix->rowsets);
-    (void)hipFree(ix->plane_hi); (void)hipFree(ix->plane_lo); (void)hipFree(ix->frag);
-    ix->rows = rows; ix->facets = facets; ix->rowsets = rowsets;
-    ix->plane_hi = fs.plane_hi; ix->plane_lo = fs.plane_lo; ix->frag = fs.frag;
-    if (fs.frag) ix->frag_row_tiles = fs.frag_row_tiles;
+    free_filter_storage(&ix->filter);
+    ix->rows = rows; ix->facets = facets; ix->rowsets = rowsets; ix->filter = fs;
     ix->capacity = capacity;
     return ICREC_OK;
 }
@@ -326,8 +328,7 @@ int icrec_index_append_rows(icrec_index* h, const float* rows_dev, int32_t m, co
     if (ix->facets) {
         uint16_t* words = static_cast<uint16_t*>(stage_block(ix, (size_t)m * 2));
         if (words == nullptr) return ICREC_ENOMEM;
-        for (int32_t i = 0; i < m; ++i)
-            words[i] = ix->n_facets == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * (size_t)i] | (facets_host[2 * (size_t)i + 1] << 8));
+        for (int32_t i = 0; i < m; ++i) words[i] = facet_word(facets_host, (size_t)i, ix->n_facets);
         ICREC_HIP(hipMemcpyAsync(ix->facets + ix->n_rows, words, (size_t)m * 2, hipMemcpyHostToDevice, st));
         ICREC_HIP(hipEventRecord(ix->stage_event, st));
     }
@@ -345,11 +346,7 @@ int icrec_index_remove_rows(icrec_index* h, const int32_t* row_ids_host, int32_t
     ICREC_REQUIRE(n_moves_out && (m == 0 || (row_ids_host && dst_out && src_out)), "icrec_index_remove_rows: NULL argument");
     ICREC_REQUIRE(m < ix->n_rows, "icrec_index_remove_rows: removing %d of %lld rows would leave the index empty", m,
                   (long long)ix->n_rows);
-    for (int32_t i = 0; i < m; ++i) {
-        ICREC_REQUIRE(row_ids_host[i] >= 0 && row_ids_host[i] < ix->n_rows, "icrec_index_remove_rows: row %d is outside [0, %lld)",
-                      row_ids_host[i], (long long)ix->n_rows);
-        ICREC_REQUIRE(i == 0 || row_ids_host[i] > row_ids_host[i - 1], "icrec_index_remove_rows: the rows must be ascending and unique");
-    }
+    if (int rc = check_row_ids("icrec_index_remove_rows", row_ids_host, m, ix->n_rows)) return rc;
     *n_moves_out = 0;
     if (m == 0) return ICREC_OK;
     // the plan: the holes (removed rows below new_n, ascending) take the survivors at or past new_n, ascending
@@ -397,11 +394,7 @@ int icrec_index_write_facets(icrec_index* h, const int32_t* row_ids_host, const 
     ICREC_REQUIRE(m >= 0, "icrec_index_write_facets: m must be >= 0 (got %d)", m);
     ICREC_REQUIRE(m == 0 || (row_ids_host && facets_host), "icrec_index_write_facets: NULL argument");
     ICREC_REQUIRE(ix->facets != nullptr, "icrec_index_write_facets: the index has no facets");
-    for (int32_t i = 0; i < m; ++i) {
-        ICREC_REQUIRE(row_ids_host[i] >= 0 && row_ids_host[i] < ix->n_rows, "icrec_index_write_facets: row %d is outside [0, %lld)",
-                      row_ids_host[i], (long long)ix->n_rows);
-        ICREC_REQUIRE(i == 0 || row_ids_host[i] > row_ids_host[i - 1], "icrec_index_write_facets: the rows must be ascending and unique");
-    }
+    if (int rc = check_row_ids("icrec_index_write_facets", row_ids_host, m, ix->n_rows)) return rc;
     if (m == 0) return ICREC_OK;
     ICREC_HIP(hipSetDevice(ix->device));
     // the words from the first named row to the last: down, patched, up again (a blocking copy each way)
@@ -414,10 +407,7 @@ int icrec_index_write_facets(icrec_index* h, const int32_t* row_ids_host, const 
         return ICREC_ENOMEM;
     }
     ICREC_HIP(hipMemcpy(words.data(), ix->facets + first, (size_t)count * 2, hipMemcpyDeviceToHost));
-    const int nf = ix->n_facets;
-    for (int32_t i = 0; i < m; ++i)
-        words[row_ids_host[i] - first] =
-            nf == 1 ? facets_host[i] : (uint16_t)(facets_host[2 * (size_t)i] | (facets_host[2 * (size_t)i + 1] << 8));
+    for (int32_t i = 0; i < m; ++i) words[row_ids_host[i] - first] = facet_word(facets_host, (size_t)i, ix->n_facets);
     ICREC_HIP(hipMemcpy(ix->facets + first, words.data(), (size_t)count * 2, hipMemcpyHostToDevice));
     return ICREC_OK;
 }
@@ -425,7 +415,7 @@ int icrec_index_write_facets(icrec_index* h, const int32_t* row_ids_host, const 
 int icrec_index_export_filter(const icrec_index* h, uint16_t* hi_dev, uint16_t* lo_dev, void* stream) {
     const Index* ix = reinterpret_cast<const Index*>(h);
     ICREC_REQUIRE(ix && hi_dev && lo_dev, "icrec_index_export_filter: NULL argument");
-    ICREC_REQUIRE(ix->frag || ix->plane_hi, "icrec_index_export_filter: the index's storage has no filter copy");
+    ICREC_REQUIRE(filter_layout(ix) != LAYOUT_NONE, "icrec_index_export_filter: the index's storage has no filter copy");
     ICREC_HIP(hipSetDevice(ix->device));
     return export_filter_storage(ix, hi_dev, lo_dev, (hipStream_t)stream);
 }

@@ -1,23 +1,21 @@
 // search.hip — cosine scoring fused with per-query top-k selection (no score matrix is ever written): the score +
-// select kernels, the filter + verify path with the filter storage's layout, and their planning.  The partial lists
-// are merged by sort.hip's sorters (common.h); the index handle's life cycle is index.hip's.
+// select kernels, the filter + verify path, and their planning: what a search launches.  The partial lists are merged
+// by sort.hip's sorters (common.h); the index handle's life cycle is index.hip's, and what the handle keeps per row -
+// the filter copy this file reads included - is written by storage.hip (storage.h).
 //
 // Replaces, on the device:
 //   sentence_transformers.util.cos_sim(query_emb, product_embeddings)  serve_recommendations.py:214/:250
 //   scores.argsort(descending=True)                                      :215/:251
 //   the exclusion / top-k Python loop                                    :216-225/:254-262
 // of the reference's src/inference/serve_recommendations.py.
-#include <stdlib.h>
-
 #include "common.h"
-#include "gemm_x3.h"
-#include "index.h"
+#include "storage.h"
 #include "stream.h"
-#include "wt_gemm.h"
 
 namespace icrec {
 
-// (row normalisation, the exclusion search and the facet test live in index.h: boost.hip uses them too)
+// (row normalisation, the exclusion search and the facet test live in index.h: boost.hip uses them too; split_planes_kernel,
+// which splits the staged pass's queries as storage.hip splits the rows, in storage.h)
 
 // ---------------------------------------------------------------- score + select
 
@@ -464,13 +462,13 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void staged_search_kernel(
 
 // ---- the RESIDENT filter pass's operands.  This pass keeps the v_mfma_f32_32x32x16_f16 form of the weights-direct
 // engine (its selection code is written for the 32x32 accumulator map; the pass is ~3 % of a recommend step): catalog
-// rows packed as [32-row tile][16-deep k-step][plane] fragments of 1 KB, lane (h << 5 | r) holding row r,
-// k = 16 ks + 8 h .. +7.  (The encoder's linear layers use the 16x16x32 form, wt_gemm.h.)  The query tile's two
+// rows packed as [32-row tile][16-deep k-step][plane] fragments of 1 KB (storage.h: frag_slot has the layout, and
+// r32_frag_off / r32_w_load walk it by the same 2 * WT_FRAG stride, lane * 8 inside a plane).
+// (The encoder's linear layers use the 16x16x32 form, wt_gemm.h.)  The query tile's two
 // activation planes, [64 queries][384] halfs each, live in LDS for the whole block in the layout of the encoder's
 // fused kernels (768-B rows as three XOR-swizzled 256-B sub-rows).
 constexpr int RES_XPLANE = 64 * 768;
 constexpr int RES_X_BYTES = 2 * RES_XPLANE;
-constexpr int RES_KS = 24;  // k-steps of 16: the resident pass is built for dim = 384
 
 __device__ __forceinline__ size_t r32_frag_off(int nt, int ks, int KS) { return ((size_t)nt * KS + ks) * (2 * WT_FRAG); }
 __device__ __forceinline__ void r32_w_load(half8& wh, half8& wl, const _Float16* wp, int ks, unsigned lo8) {
@@ -792,52 +790,6 @@ __global__ __launch_bounds__(ST_ROWS, 2) void stream_search_kernel(
 }
 
 // ---------------------------------------------------------------- filter + verify (ICREC_ROWS_F32_FILTER)
-// fp32 values -> f16 hi/lo planes: the queries of the staged filter pass per call, the catalog rows once at index
-// creation; clears the fallback flag if given.
-template <bool SRC16>  // SRC16: the source is bfloat16 bits (ICREC_ROWS_BF16_FILTER rows), widened exactly first
-__global__ __launch_bounds__(256) void split_planes_kernel(const void* __restrict__ src, size_t n, _Float16* __restrict__ hi,
-                                                           _Float16* __restrict__ lo, int* __restrict__ flag) {
-    if (flag != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *flag = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float v = SRC16 ? bf16_lo(static_cast<const uint16_t*>(src)[i]) : static_cast<const float*>(src)[i];
-        _Float16 a, b;
-        split_f16(v, a, b);
-        hi[i] = a;
-        lo[i] = b;
-    }
-}
-
-// Resident filter pass: the (normalised) catalog rows as packed weight fragments - fragment (row tile rt, k-step ks,
-// plane) = 512 halfs at ((rt * KS + ks) * 2 + plane) * 512, lane l = (h << 5 | r) holds row rt*32 + r, k = 16 ks + 8 h
-// .. +7, hi = f16(1024 x), lo = f16(1024 x - hi) (wt_gemm.h) - once at index creation; rows past n_rows are zero.
-template <bool SRC16>
-__global__ __launch_bounds__(256) void pack_rows_kernel(const void* __restrict__ src, int64_t n_rows, int K, int64_t n_frag,
-                                                        _Float16* __restrict__ out) {
-    const int KS = K / 16;
-    for (int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x; id < n_frag * 64; id += (int64_t)gridDim.x * 256) {
-        const int64_t fr = id >> 6;
-        const int lane = (int)(id & 63), r = lane & 31, h = lane >> 5;
-        const int64_t rt = fr / KS;
-        const int ks = (int)(fr % KS);
-        const int64_t row = rt * 32 + r;
-        half8 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v = 0.0f;
-            if (row < n_rows) {
-                const size_t at = (size_t)row * K + ks * 16 + 8 * h + j;
-                v = SRC16 ? bf16_lo(static_cast<const uint16_t*>(src)[at]) : static_cast<const float*>(src)[at];
-            }
-            _Float16 a, b;
-            split_scaled(v, WT_SW, a, b);
-            hi[j] = a;
-            lo[j] = b;
-        }
-        *reinterpret_cast<half8*>(out + fr * (2 * WT_FRAG) + lane * 8) = hi;
-        *reinterpret_cast<half8*>(out + fr * (2 * WT_FRAG) + WT_FRAG + lane * 8) = lo;
-    }
-}
-
 // queries -> the engine's activation planes (hi/lo of 16 x, wt_gemm.h: split_act4), row-major [Qpad][K]; clears the flag
 __global__ __launch_bounds__(256) void split_queries_act_kernel(const float* __restrict__ src, size_t n4, _Float16* __restrict__ hi,
                                                                 _Float16* __restrict__ lo, int* __restrict__ flag) {
@@ -939,300 +891,9 @@ typedef TileCfg<4, 1, 2, 2> CfgMid;    // 256 rows x  64 queries
 typedef TileCfg<4, 1, 2, 1> CfgSmall;  // 256 rows x  32 queries
 typedef TileCfg<2, 2, 2, 1> CfgFilter;  // 128 rows x  64 queries, f16 planes (filter pass)
 typedef TileCfg<8, 1, 1, 2> CfgRes;     // 256 rows x  64 queries per round, 8 waves (resident filter pass)
-// Filter storages of dimension 384 keep the rows as the packed fragments of the resident filter pass INSTEAD of the
-// row-major planes (same bytes).  Every 64-query block streams its chunk of the shard through L2; the blocks of a
-// chunk sit on one XCD (xcd_remap) and walk it in step, so HBM still sees each fragment about once.  Measured against
-// the staged pass (same box, top-20): 49,688 rows x 1,024 queries 0.26 vs 0.39 ms; 2 M rows 4.5 vs 6.5 ms; 10 M rows
-// 19.6 vs 30.1 ms, x 4,096 queries 74 vs 124 ms (425 TF-equivalent = 0.51 of the 3-pass f16 roof).
-constexpr int64_t RES_MAX_ROWS = (int64_t)1 << 40;  // no limit (ICREC_FILTER_RESIDENT=<n> sets one, =0 forces the staged form)
 static_assert(FILTER_DIM_STEP == HBK, "index.hip admits the dims whose rows the staged pass walks in whole slabs");
-
-// index.h: the filter storage of a new index, in the layout the pass that will read it expects.
-int build_filter_storage(Index* ix) {
-    const int64_t n_rows = ix->n_rows;  // (== the capacity: a new index)
-    const int dim = ix->dim;
-    const bool rows16 = rows_are_bf16(ix);
-    const char* res_env = getenv("ICREC_FILTER_RESIDENT");  // "0": staged form; a number > 1: row limit of the resident form (A/B)
-    const int64_t res_max = res_env && atoll(res_env) > 1 ? atoll(res_env) : RES_MAX_ROWS;
-    if (dim == 16 * RES_KS && n_rows <= res_max && !(res_env && res_env[0] == '0' && res_env[1] == 0)) {
-        // resident filter pass: packed fragments instead of the row-major planes
-        ix->frag_row_tiles = ((n_rows + CfgRes::BM - 1) / CfgRes::BM) * (CfgRes::BM / 32);
-        const int64_t n_frag = ix->frag_row_tiles * RES_KS;
-        if (hipMalloc(&ix->frag, (size_t)n_frag * 2 * WT_FRAG * sizeof(_Float16)) != hipSuccess) {
-            set_error("icrec_index_create: hipMalloc of the filter fragments (%zu bytes) failed", (size_t)n_frag * 2 * WT_FRAG * 2);
-            return ICREC_ENOMEM;
-        }
-        // fragments of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
-        hipLaunchKernelGGL((rows16 ? pack_rows_kernel<true> : pack_rows_kernel<false>), dim3(4096), dim3(256), 0, 0,
-                           (const void*)ix->rows, n_rows, dim, n_frag, ix->frag);
-    } else {
-        const size_t n = (size_t)n_rows * dim;
-        hipError_t e1 = hipMalloc(&ix->plane_hi, n * 2), e2 = hipMalloc(&ix->plane_lo, n * 2);
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            set_error("icrec_index_create: hipMalloc of the filter planes (2 x %zu bytes) failed", n * 2);
-            return ICREC_ENOMEM;
-        }
-        // planes of the ROUNDED rows (bf16): the filter then approximates exactly what the exact pass computes
-        hipLaunchKernelGGL((rows16 ? split_planes_kernel<true> : split_planes_kernel<false>), dim3(4096), dim3(256), 0, 0,
-                           (const void*)ix->rows, n, ix->plane_hi, ix->plane_lo, (int*)nullptr);
-    }
-    ICREC_HIP(hipGetLastError());
-    return ICREC_OK;
-}
-
-// ---------------------------------------------------------------- rows rewritten in place (icrec_index_write_rows)
-// One wavefront per written row w: row ids[w] of the index becomes what icrec_index_create_ex makes of x[w].  The norm
-// is normalize_rows_kernel's, lane for lane (64 strided fmaf partials, the xor butterfly, the same division), so the
-// stored bits are a fresh index's.  The STORED values (bf16: rounded, widened back) go through LDS, so that a lane
-// then owns 8 consecutive k and every store is 16 bytes: the row itself, and from the same values its filter copy -
-// the planes as split_planes_kernel splits them, or the row's lane slots of its 2 * dim / 16 fragments as
-// pack_rows_kernel packs them (lane (h << 5 | r) of fragment (row / 32, ks) holds k = 16 ks + 8 h .. + 7: chunk
-// c = 2 ks + h).  An id outside [0, n_rows) writes nothing: it is tested before any address is formed from it.
-// No other row's bytes are touched; the padding rows of the last fragment round stay zero.
-// ids == NULL (icrec_index_append_rows): written row w is row base + w instead, under the same test.
-constexpr int WRITE_NO_FILTER = 0, WRITE_PLANES = 1, WRITE_FRAGS = 2;
-template <bool OUT16, int FILT>
-__global__ __launch_bounds__(256) void write_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ ids, int64_t base,
-                                                         int m, void* __restrict__ rowsv, int64_t n_rows, int dim,
-                                                         _Float16* __restrict__ hi, _Float16* __restrict__ lo,
-                                                         _Float16* __restrict__ frag) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* st = reinterpret_cast<float*>(smem_raw) + (size_t)wave * dim;  // this wave's stored values
-    const int64_t w = (int64_t)blockIdx.x * 4 + wave;
-    int64_t row = -1;  // wave-uniform
-    if (w < m) {
-        const int64_t id = ids ? (int64_t)ids[w] : base + w;
-        if (id >= 0 && id < n_rows) row = id;
-    }
-    if (row >= 0) {
-        const float* xr = x + w * dim;
-        float acc = 0.0f;
-        for (int i = lane; i < dim; i += 64) {
-            float v = xr[i];
-            acc = fmaf(v, v, acc);
-        }
-        float nrm = sqrtf(wave_sum_f32(acc));
-        float den = nrm > 1e-12f ? nrm : 1e-12f;
-        for (int i = lane; i < dim; i += 64) {
-            const float v = xr[i] / den;
-            st[i] = OUT16 ? bf16_lo(bf16_rne(v)) : v;
-        }
-    }
-    __syncthreads();
-    if (row < 0) return;
-    for (int c = lane; c < dim / 8; c += 64) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(st + 8 * c), b = *reinterpret_cast<const f32x4*>(st + 8 * c + 4);
-        const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-        if (OUT16) {
-            u32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = (__float_as_uint(v[2 * j]) >> 16) | (__float_as_uint(v[2 * j + 1]) & 0xFFFF0000u);
-            *reinterpret_cast<u32x4*>(static_cast<uint16_t*>(rowsv) + row * dim + 8 * c) = o;
-        } else {
-            float* out = static_cast<float*>(rowsv) + row * dim + 8 * c;
-            *reinterpret_cast<f32x4*>(out) = a;
-            *reinterpret_cast<f32x4*>(out + 4) = b;
-        }
-        if (FILT == WRITE_NO_FILTER) continue;
-        half8 ph, pl;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            _Float16 s, t;
-            if (FILT == WRITE_PLANES) split_f16(v[j], s, t);
-            else split_scaled(v[j], WT_SW, s, t);
-            ph[j] = s;
-            pl[j] = t;
-        }
-        if (FILT == WRITE_PLANES) {
-            *reinterpret_cast<half8*>(hi + row * dim + 8 * c) = ph;
-            *reinterpret_cast<half8*>(lo + row * dim + 8 * c) = pl;
-        } else {
-            const int64_t fr = (row >> 5) * (dim / 16) + (c >> 1);
-            _Float16* at = frag + fr * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(row & 31)) * 8;
-            *reinterpret_cast<half8*>(at) = ph;
-            *reinterpret_cast<half8*>(at + WT_FRAG) = pl;
-        }
-    }
-}
-
-// index.h: icrec_index_write_rows after its argument checks (m >= 1): one launch, nothing allocated.
-int write_index_rows(Index* ix, const float* rows_dev, const int32_t* row_ids_dev, int32_t m, int64_t base_row, hipStream_t st) {
-    const bool rows16 = rows_are_bf16(ix);
-    const int filt = ix->frag ? WRITE_FRAGS : ix->plane_hi ? WRITE_PLANES : WRITE_NO_FILTER;
-    typedef void (*kernel_t)(const float*, const int32_t*, int64_t, int, void*, int64_t, int, _Float16*, _Float16*, _Float16*);
-    static const kernel_t kernels[2][3] = {
-        {write_rows_kernel<false, WRITE_NO_FILTER>, write_rows_kernel<false, WRITE_PLANES>, write_rows_kernel<false, WRITE_FRAGS>},
-        {write_rows_kernel<true, WRITE_NO_FILTER>, write_rows_kernel<true, WRITE_PLANES>, write_rows_kernel<true, WRITE_FRAGS>}};
-    hipLaunchKernelGGL(kernels[rows16][filt], dim3((unsigned)(((int64_t)m + 3) / 4)), dim3(256), (size_t)4 * ix->dim * sizeof(float), st,
-                       rows_dev, row_ids_dev, base_row, (int)m, ix->rows, row_ids_dev ? ix->n_rows : base_row + m, ix->dim,
-                       ix->plane_hi, ix->plane_lo, ix->frag);
-    ICREC_HIP(hipGetLastError());
-    return ICREC_OK;
-}
-
-// ---------------------------------------------------------------- rows moved in place (icrec_index_remove_rows)
-// One wavefront per move i: everything the index keeps for row src[i] is copied to row dst[i] as the STORED bits - the
-// planes and the fragments are functions of the stored values alone, not of the row's position, so nothing is
-// normalised or split again.  16-byte loads and stores: the row, its slice of both planes or its lane slots (from
-// fragment (src / 32, ks), lane (h << 5 | src & 31), to fragment (dst / 32, ks), lane (h << 5 | dst & 31): the
-// addressing of write_rows_kernel and unpack_rows_kernel).  Then the facet word (one 16-bit store) and the row's bit
-// in every row set: several destinations can share a 32-bit word, so the bit is set or cleared atomically.
-// Sources (>= new_n) and destinations (< new_n) are disjoint and each is named once: no wave writes what another reads.
-// Nothing is cleared here - a source's word or fragment tile may hold other sources that a later wave still reads;
-// clear_rows_kernel runs behind this launch.  A move outside dst < new_n <= src < old_n is skipped before any address
-// is formed from it.
-template <bool OUT16, int FILT>
-__global__ __launch_bounds__(256) void move_rows_kernel(const int32_t* __restrict__ dst, const int32_t* __restrict__ src,
-                                                        int n_moves, int64_t new_n, int64_t old_n, void* rowsv, int dim,
-                                                        _Float16* hi, _Float16* lo, _Float16* frag, uint16_t* facets,
-                                                        uint32_t* sets, int n_sets, int64_t set_words) {
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= n_moves) return;
-    const int64_t d = dst[w], s = src[w];  // wave-uniform
-    if (d < 0 || d >= new_n || s < new_n || s >= old_n) return;
-    const int row_chunks = dim * (OUT16 ? 2 : 4) / 16;
-    const u32x4* rs = reinterpret_cast<const u32x4*>(static_cast<const char*>(rowsv) + (size_t)s * row_chunks * 16);
-    u32x4* rd = reinterpret_cast<u32x4*>(static_cast<char*>(rowsv) + (size_t)d * row_chunks * 16);
-    for (int c = lane; c < row_chunks; c += 64) rd[c] = rs[c];
-    if (FILT != WRITE_NO_FILTER) {
-        for (int c = lane; c < dim / 8; c += 64) {
-            if (FILT == WRITE_PLANES) {
-                *reinterpret_cast<half8*>(hi + d * dim + 8 * c) = *reinterpret_cast<const half8*>(hi + s * dim + 8 * c);
-                *reinterpret_cast<half8*>(lo + d * dim + 8 * c) = *reinterpret_cast<const half8*>(lo + s * dim + 8 * c);
-            } else {
-                const _Float16* from = frag + ((s >> 5) * (dim / 16) + (c >> 1)) * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(s & 31)) * 8;
-                _Float16* to = frag + ((d >> 5) * (dim / 16) + (c >> 1)) * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(d & 31)) * 8;
-                *reinterpret_cast<half8*>(to) = *reinterpret_cast<const half8*>(from);
-                *reinterpret_cast<half8*>(to + WT_FRAG) = *reinterpret_cast<const half8*>(from + WT_FRAG);
-            }
-        }
-    }
-    if (facets != nullptr && lane == 0) facets[d] = facets[s];
-    for (int t = lane; t < n_sets; t += 64) {
-        uint32_t* bits = sets + (size_t)t * set_words;
-        const uint32_t bit = 1u << (d & 31);
-        if ((bits[s >> 5] >> (s & 31)) & 1u) atomicOr(bits + (d >> 5), bit);
-        else atomicAnd(bits + (d >> 5), ~bit);
-    }
-}
-
-// Behind move_rows_kernel: the rows [new_n, old_n) leave the index, and what a fresh index keeps zero past its last row
-// becomes zero again - their fragment lane slots and facet words (one wavefront per row), and their bits of every row
-// set (the threads of the whole grid over (set, word) pairs: the word that straddles new_n keeps its low bits).  The
-// stored rows and the planes past n_rows are addressed by nothing and stay as they are.  Every slot, word and bitmap
-// word is written by one thread of this launch and read by none.
-template <bool FRAGS>
-__global__ __launch_bounds__(256) void clear_rows_kernel(int64_t new_n, int64_t old_n, int dim, _Float16* frag, uint16_t* facets,
-                                                         uint32_t* sets, int n_sets, int64_t set_words) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = new_n + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row < old_n) {
-        if (FRAGS) {
-            half8 z;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) z[j] = (_Float16)0.0f;
-            for (int c = lane; c < dim / 8; c += 64) {
-                _Float16* at = frag + ((row >> 5) * (dim / 16) + (c >> 1)) * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(row & 31)) * 8;
-                *reinterpret_cast<half8*>(at) = z;
-                *reinterpret_cast<half8*>(at + WT_FRAG) = z;
-            }
-        }
-        if (facets != nullptr && lane == 0) facets[row] = 0;
-    }
-    const int64_t w0 = new_n >> 5, nw = ((old_n + 31) >> 5) - w0;  // the words that hold a bit of the tail
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nw * n_sets; i += (int64_t)gridDim.x * 256) {
-        uint32_t* word = sets + (size_t)(i / nw) * set_words + w0 + i % nw;
-        *word = (i % nw == 0 && (new_n & 31)) ? *word & ((1u << (new_n & 31)) - 1u) : 0u;
-    }
-}
-
-// index.h: icrec_index_remove_rows after its argument checks: two launches, nothing allocated.
-int move_index_rows(Index* ix, const int32_t* dst_dev, const int32_t* src_dev, int32_t n_moves, int64_t new_n, int64_t old_n,
-                    hipStream_t st) {
-    const bool rows16 = rows_are_bf16(ix);
-    const int filt = ix->frag ? WRITE_FRAGS : ix->plane_hi ? WRITE_PLANES : WRITE_NO_FILTER;
-    typedef void (*kernel_t)(const int32_t*, const int32_t*, int, int64_t, int64_t, void*, int, _Float16*, _Float16*, _Float16*,
-                             uint16_t*, uint32_t*, int, int64_t);
-    static const kernel_t kernels[2][3] = {
-        {move_rows_kernel<false, WRITE_NO_FILTER>, move_rows_kernel<false, WRITE_PLANES>, move_rows_kernel<false, WRITE_FRAGS>},
-        {move_rows_kernel<true, WRITE_NO_FILTER>, move_rows_kernel<true, WRITE_PLANES>, move_rows_kernel<true, WRITE_FRAGS>}};
-    const int n_sets = ix->rowsets ? ix->n_rowsets : 0;
-    const int64_t words = rowset_words(ix->capacity);
-    if (n_moves > 0) {
-        hipLaunchKernelGGL(kernels[rows16][filt], dim3((unsigned)(((int64_t)n_moves + 3) / 4)), dim3(256), 0, st, dst_dev, src_dev,
-                           (int)n_moves, new_n, old_n, ix->rows, ix->dim, ix->plane_hi, ix->plane_lo, ix->frag, ix->facets,
-                           ix->rowsets, n_sets, words);
-        ICREC_HIP(hipGetLastError());
-    }
-    if (ix->frag || ix->facets || n_sets > 0) {
-        hipLaunchKernelGGL((ix->frag ? clear_rows_kernel<true> : clear_rows_kernel<false>), dim3((unsigned)((old_n - new_n + 3) / 4)),
-                           dim3(256), 0, st, new_n, old_n, ix->dim, ix->frag, ix->facets, ix->rowsets, n_sets, words);
-        ICREC_HIP(hipGetLastError());
-    }
-    return ICREC_OK;
-}
-
-// index.h: icrec_index_reserve's filter copy at the new capacity.  The fragments are a function of the row tile alone
-// (fragment (row / 32, ks)), so the live rows are a prefix of the new array; whole rounds of CfgRes::BM rows of the
-// capacity, zero behind the live rows as build_filter_storage leaves them.
-int reserve_filter_storage(const Index* ix, int64_t capacity, FilterStorage* out) {
-    if (ix->frag) {
-        out->frag_row_tiles = ((capacity + CfgRes::BM - 1) / CfgRes::BM) * (CfgRes::BM / 32);
-        const size_t tile_bytes = (size_t)RES_KS * 2 * WT_FRAG * sizeof(_Float16), bytes = (size_t)out->frag_row_tiles * tile_bytes;
-        if (hipMalloc(&out->frag, bytes) != hipSuccess) {
-            out->frag = nullptr;
-            set_error("icrec_index_reserve: hipMalloc of the filter fragments (%zu bytes) failed", bytes);
-            return ICREC_ENOMEM;
-        }
-        const size_t live = (size_t)((ix->n_rows + 31) / 32) * tile_bytes;  // (<= both arrays: n_rows <= either capacity)
-        ICREC_HIP(hipMemcpyAsync(out->frag, ix->frag, live, hipMemcpyDeviceToDevice, 0));
-        ICREC_HIP(hipMemsetAsync(reinterpret_cast<char*>(out->frag) + live, 0, bytes - live, 0));
-    } else if (ix->plane_hi) {
-        const size_t bytes = (size_t)capacity * ix->dim * 2, live = (size_t)ix->n_rows * ix->dim * 2;
-        hipError_t e1 = hipMalloc(&out->plane_hi, bytes), e2 = e1 == hipSuccess ? hipMalloc(&out->plane_lo, bytes) : e1;
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            if (e1 == hipSuccess) (void)hipFree(out->plane_hi);
-            out->plane_hi = out->plane_lo = nullptr;
-            set_error("icrec_index_reserve: hipMalloc of the filter planes (2 x %zu bytes) failed", bytes);
-            return ICREC_ENOMEM;
-        }
-        ICREC_HIP(hipMemcpyAsync(out->plane_hi, ix->plane_hi, live, hipMemcpyDeviceToDevice, 0));
-        ICREC_HIP(hipMemcpyAsync(out->plane_lo, ix->plane_lo, live, hipMemcpyDeviceToDevice, 0));
-    }
-    return ICREC_OK;
-}
-
-// The resident form's fragments un-packed to row-major planes (icrec_index_export_filter): one thread per (row, 8 k).
-__global__ __launch_bounds__(256) void unpack_rows_kernel(const _Float16* __restrict__ frag, int64_t n_rows, int K,
-                                                          _Float16* __restrict__ hi, _Float16* __restrict__ lo) {
-    const int chunks = K / 8;
-    for (int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x; id < n_rows * chunks; id += (int64_t)gridDim.x * 256) {
-        const int64_t row = id / chunks;
-        const int c = (int)(id % chunks);
-        const int64_t fr = (row >> 5) * (K / 16) + (c >> 1);
-        const _Float16* at = frag + fr * (2 * WT_FRAG) + (((c & 1) << 5) | (int)(row & 31)) * 8;
-        *reinterpret_cast<half8*>(hi + row * K + 8 * c) = *reinterpret_cast<const half8*>(at);
-        *reinterpret_cast<half8*>(lo + row * K + 8 * c) = *reinterpret_cast<const half8*>(at + WT_FRAG);
-    }
-}
-
-// index.h: icrec_index_export_filter after its argument checks.
-int export_filter_storage(const Index* ix, uint16_t* hi_dev, uint16_t* lo_dev, hipStream_t st) {
-    const int64_t n = ix->n_rows * ix->dim;
-    if (ix->frag) {
-        const int64_t blocks = (n / 8 + 255) / 256;
-        hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st,
-                           (const _Float16*)ix->frag, ix->n_rows, ix->dim, reinterpret_cast<_Float16*>(hi_dev),
-                           reinterpret_cast<_Float16*>(lo_dev));
-        ICREC_HIP(hipGetLastError());
-    } else {
-        ICREC_HIP(hipMemcpyAsync(hi_dev, ix->plane_hi, (size_t)n * 2, hipMemcpyDeviceToDevice, st));
-        ICREC_HIP(hipMemcpyAsync(lo_dev, ix->plane_lo, (size_t)n * 2, hipMemcpyDeviceToDevice, st));
-    }
-    return ICREC_OK;
-}
+static_assert(CfgRes::BM == RES_ROUND_ROWS && RES_XPLANE == 64 * 2 * 16 * RES_KS,
+              "storage.hip sizes the fragments in the resident pass's rounds, for the k-steps its query planes hold");
 
 // Filter + verify (ICREC_ROWS_F32_FILTER): batches of at least FILTER_MIN_Q queries are ranked by the f16x3 filter
 // pass with FILTER_SLACK extra list entries, then verified exactly.  filter_eps(dim) bounds |filter score - exact score|
@@ -1324,8 +985,8 @@ struct FilterPlan {
 static FilterPlan make_filter_plan(const Index* ix, int Q, int k, const Plan& exact, Arm arm = ARM_PLAIN) {
     FilterPlan f;
     f.kp = filter_list_len(k);
-    f.resident = ix->frag != nullptr;
-    f.use = (ix->plane_hi != nullptr || f.resident) && Q >= FILTER_MIN_Q && f.kp <= ICREC_MAX_K;
+    f.resident = ix->filter.frag != nullptr;
+    f.use = (ix->filter.plane_hi != nullptr || f.resident) && Q >= FILTER_MIN_Q && f.kp <= ICREC_MAX_K;
     // resident form: the query planes leave 64 KB of LDS for the lists (k <= 92); longer lists take the exact search,
     // which is the faster one there anyway (measured at 49,688 rows, Q = 1,024, k = 100: staged filter 2.5 ms, exact 1.5 ms)
     // (with the allow masks of a faceted search: k <= 84; with the set words of a set-restricted one: k <= 76)
@@ -1449,7 +1110,7 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
                            dim3(256), 0, st, (const float*)qn, nq / 4, qh, ql, flag);
         rc = launch_arm(resident_search_kernel<CfgRes>, resident_search_kernel<CfgRes, FacetArgs>,
                         resident_search_kernel<CfgRes, SetArgs>, sa, true, T_SEARCH_KERNEL,
-                        dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st, (const _Float16*)ix->frag, ix->n_rows,
+                        dim3(f.n_chunks * f.n_qtiles), dim3(CfgRes::THREADS), f.smem, st, (const _Float16*)ix->filter.frag, ix->n_rows,
                         (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q, f.kp, ei, eo, (uint32_t)ix->row_offset,
                         f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     } else {
@@ -1457,8 +1118,8 @@ static int run_search_filtered(Index* ix, const FilterPlan& f, const Plan& ex, c
                            dim3(256), 0, st, (const void*)qn, nq, qh, ql, flag);
         rc = launch_arm(staged_search_kernel<CfgFilter>, staged_search_kernel<CfgFilter, FacetArgs>,
                         staged_search_kernel<CfgFilter, SetArgs>, sa, true, T_SEARCH_KERNEL,
-                        dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st, (const _Float16*)ix->plane_hi,
-                        (const _Float16*)ix->plane_lo, ix->n_rows, ix->dim, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q,
+                        dim3(f.n_chunks * f.n_qtiles), dim3(CfgFilter::THREADS), f.smem, st, (const _Float16*)ix->filter.plane_hi,
+                        (const _Float16*)ix->filter.plane_lo, ix->n_rows, ix->dim, (const _Float16*)qh, (const _Float16*)ql, f.Qpad, Q,
                         f.kp, ei, eo, (uint32_t)ix->row_offset, f.n_row_tiles, f.tiles_per_chunk, f.n_qtiles, partial);
     }
     if (rc) return rc;
@@ -1493,7 +1154,7 @@ static int run_search(Index* ix, const float* q, int Q, int k, const int32_t* ei
     const FacetArgs fa = allow ? FacetArgs{ix->facets, allow, ix->n_facets} : FacetArgs{nullptr, nullptr, 0};
     const SetArgs sa{fa, ix->rowsets, set_ids, ix->n_rowsets, sets_per_query, rowset_words(ix->capacity)};
     const Arm arm = arm_of(sa);
-    if (scores_out == nullptr && (ix->plane_hi != nullptr || ix->frag != nullptr)) {
+    if (scores_out == nullptr && (ix->filter.plane_hi != nullptr || ix->filter.frag != nullptr)) {
         const Plan ex = make_plan(ix, Q, k, false, arm);
         const FilterPlan f = make_filter_plan(ix, Q, k, ex, arm);
         if (f.use) {
