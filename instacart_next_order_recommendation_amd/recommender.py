@@ -136,6 +136,31 @@ def text_facets(text: str) -> Optional[tuple[str, str]]:
     return text[a + len(". Aisle: "):d], text[d + len(". Department: "):-1]
 
 
+def _facet_codes(texts, aisles, departments, whose):
+    """The facet half of product_update_plan and product_add_plan: texts -> (codes uint8 [m, 2], aisle names, department
+    names), (None, None, None) for a catalog without facets (aisles is None).  A name the catalog does not have yet is
+    appended to (a copy of) its list, so every existing code stays.  ValueError: a text that does not parse - whose(i)
+    names text i in it - and a 257th aisle or department name."""
+    if aisles is None:
+        return None, None, None
+    names = (list(aisles), list(departments))
+    code = tuple({name: i for i, name in enumerate(known)} for known in names)
+    codes = np.zeros((len(texts), 2), np.uint8)
+    for i, text in enumerate(texts):
+        parsed = text_facets(text)
+        if parsed is None:
+            raise ValueError(f"{whose(i)} is not in the 'Product: .. Aisle: .. Department: ..' format of this catalog")
+        for f, value in enumerate(parsed):
+            if value not in code[f]:
+                if len(names[f]) >= 256:
+                    raise ValueError(f"{value!r} would be the 257th {'aisle' if f == 0 else 'department'} name; a facet "
+                                     "has 256 values")
+                code[f][value] = len(names[f])
+                names[f].append(value)
+            codes[i, f] = code[f][value]
+    return codes, names[0], names[1]
+
+
 def product_update_plan(updates, pid_to_row, product_texts, aisles, departments):
     """Recommender.update_products' argument, checked before any GPU work.  updates: a mapping product id -> new text;
     pid_to_row and product_texts: the catalog's rows and current texts; aisles / departments: its facet names, None for
@@ -158,25 +183,7 @@ def product_update_plan(updates, pid_to_row, product_texts, aisles, departments)
         pairs.append((int(pid_to_row[pid]), text))
     pairs.sort(key=lambda p: p[0])
     rows, texts = [r for r, _ in pairs], [t for _, t in pairs]
-    if aisles is None:
-        return rows, texts, None, None, None
-    names = (list(aisles), list(departments))
-    code = tuple({name: i for i, name in enumerate(known)} for known in names)
-    codes = np.zeros((len(rows), 2), np.uint8)
-    for i, text in enumerate(texts):
-        parsed = text_facets(text)
-        if parsed is None:
-            raise ValueError(f"the new text of row {rows[i]} is not in the 'Product: .. Aisle: .. Department: ..' format "
-                             "of this catalog")
-        for f, value in enumerate(parsed):
-            if value not in code[f]:
-                if len(names[f]) >= 256:
-                    raise ValueError(f"{value!r} would be the 257th {'aisle' if f == 0 else 'department'} name; a facet "
-                                     "has 256 values")
-                code[f][value] = len(names[f])
-                names[f].append(value)
-            codes[i, f] = code[f][value]
-    return rows, texts, codes, names[0], names[1]
+    return (rows, texts, *_facet_codes(texts, aisles, departments, lambda i: f"the new text of row {rows[i]}"))
 
 
 def product_add_plan(additions, pid_to_row, aisles, departments):
@@ -197,25 +204,7 @@ def product_add_plan(additions, pid_to_row, aisles, departments):
             raise ValueError(f"the text of product {pid!r} must be a string, got {type(text).__name__}")
         ids.append(pid)
         texts.append(text)
-    if aisles is None:
-        return ids, texts, None, None, None
-    names = (list(aisles), list(departments))
-    code = tuple({name: i for i, name in enumerate(known)} for known in names)
-    codes = np.zeros((len(ids), 2), np.uint8)
-    for i, text in enumerate(texts):
-        parsed = text_facets(text)
-        if parsed is None:
-            raise ValueError(f"the text of product {ids[i]!r} is not in the 'Product: .. Aisle: .. Department: ..' format "
-                             "of this catalog")
-        for f, value in enumerate(parsed):
-            if value not in code[f]:
-                if len(names[f]) >= 256:
-                    raise ValueError(f"{value!r} would be the 257th {'aisle' if f == 0 else 'department'} name; a facet "
-                                     "has 256 values")
-                code[f][value] = len(names[f])
-                names[f].append(value)
-            codes[i, f] = code[f][value]
-    return ids, texts, codes, names[0], names[1]
+    return (ids, texts, *_facet_codes(texts, aisles, departments, lambda i: f"the text of product {ids[i]!r}"))
 
 
 def product_remove_plan(product_ids, pid_to_row) -> list[int]:
@@ -293,6 +282,8 @@ def boost_rows(boosts, boost_weight, only_boosted: bool, pid_to_row) -> Optional
 def boost_plan(boosts, boost_weight, only_boosted: bool, n_queries: int, pid_to_row):
     """A batch's boost arguments (boosts: None or one entry per query, each as boost_rows takes it; boost_weight and
     only_boosted: one value for the batch) -> None (the plain path) or (per-query {row: weight} or None, only_boosted)."""
+    if boosts is None and boost_weight is None and not only_boosted:
+        return None
     if boosts is None:
         boosts = [None] * n_queries
     elif hasattr(boosts, "items") or isinstance(boosts, (str, bytes)):
@@ -376,6 +367,8 @@ def cap_plan(max_per_aisle, max_per_department, has_facets: bool):
     """A request's `max_per_aisle` / `max_per_department` arguments, checked before any GPU work -> None (the plain
     request: both are None) or the caps (aisle, department) DeviceIndex.search_capped takes, 0 for the one that is None.
     Each is a positive integer; ValueError for anything else, and for caps on a catalog without facets."""
+    if max_per_aisle is None and max_per_department is None:
+        return None
     caps = []
     for what, v in (("max_per_aisle", max_per_aisle), ("max_per_department", max_per_department)):
         if v is None:
@@ -384,8 +377,6 @@ def cap_plan(max_per_aisle, max_per_department, has_facets: bool):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 2**31 - 1:
             raise ValueError(f"{what} must be an integer >= 1, got {v!r}")
         caps.append(int(v))
-    if caps == [0, 0]:
-        return None
     if not has_facets:
         raise ValueError("max_per_aisle / max_per_department need a catalog with aisle / department facets (its texts "
                          "are not in the 'Product: .. Aisle: .. Department: ..' format)")
@@ -414,6 +405,28 @@ def ann_plan(probes, n_lists, *, aisles=None, departments=None, boosts=None, onl
     if isinstance(probes, bool) or int(probes) != probes or not 1 <= int(probes) <= limit:
         raise ValueError(f"probes must be an integer in [1, {limit}], got {probes!r}")
     return int(probes)
+
+
+@dataclass(frozen=True)
+class RequestPlan:
+    """What a request asks beyond (queries, top_k, exclusions), checked (Recommender._plan); None / False: not asked."""
+
+    allow: Optional[list] = None  # per query None or (aisle codes, department codes): Recommender._facet_allow
+    sets: Optional[list] = None  # per query None or the ids of its product sets: within_plan
+    boost: Optional[list] = None  # per query None or {row: weight}, without the rows outside the query's sets
+    only_boosted: bool = False  # rank the rows of `boost` alone: no search
+    caps: Optional[tuple] = None  # (aisle, department) caps: cap_plan
+    mmr: Optional[tuple] = None  # (lambda, candidates): diversity_plan
+    probes: Optional[int] = None  # the lists of the IVF index to scan: ann_plan
+    width: Optional[int] = None  # the request's raw `candidates`: what DeviceIndex.search_capped searches per round
+
+    @property
+    def plain(self) -> bool:
+        """Nothing asked: the search is `DeviceIndex.search(q, k, exclude)`, which the graph path may serve."""
+        return (self.allow, self.sets, self.boost, self.caps, self.mmr, self.probes) == (None,) * 6
+
+
+PLAIN = RequestPlan()  # what Recommender._plan returns for every request that asks nothing
 
 
 class SbertModel:
@@ -745,29 +758,41 @@ class Recommender:
             return None
         return [None if a is None and d is None else (a, d) for a, d in zip(*per_facet)]
 
-    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, timed: bool = False, allow=None, mmr=None,
-                       boost=None, probes=None, sets=None, caps=None, width=None):
+    def _plan(self, n_queries: int, top_k: int, *, aisles=None, departments=None, diversity=None, candidates=None,
+              boosts=None, boost_weight=None, only_boosted=False, probes=None, within=None, max_per_aisle=None,
+              max_per_department=None) -> RequestPlan:
+        """A request's options in recommend_batch's form (aisles, departments, boosts and within: None or one entry per
+        query), checked before any GPU work -> its RequestPlan; the one caller of the *_plan functions, in the order ann,
+        caps, within, diversity, facets, boosts.  Boosted rows outside a query's product sets are dropped here.  A request
+        that asks nothing gets the shared PLAIN (`candidates` alone asks nothing: it is only a width)."""
+        if probes is not None:  # (n_lists is a library call: made for the requests that probe)
+            probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
+                              boosts=boosts, only_boosted=only_boosted, within=within, max_per_aisle=max_per_aisle,
+                              max_per_department=max_per_department)
+        caps = cap_plan(max_per_aisle, max_per_department, self.aisles is not None)
+        sets = within_plan(within, n_queries, self.product_sets)
+        mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
+        allow = self._facet_allow(aisles, departments, n_queries)
+        boost, only = boost_plan(boosts, boost_weight, only_boosted, n_queries, self._pid_to_row) or (None, False)
+        if (allow, sets, boost, caps, mmr, probes) == (None,) * 6:
+            return PLAIN
+        if boost is not None and sets is not None:
+            boost = boosts_within(boost, sets, self._set_member)
+        return RequestPlan(allow, sets, boost, only, caps, mmr, probes, candidates)  # (the fields' order; keywords cost 0.3 us)
+
+    def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, plan: RequestPlan, timed: bool = False):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
-        current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  allow: per-query
-        facet constraints (_facet_allow).  mmr: (lambda, candidates) of diversity_plan - the search is then
-        `candidates` wide and the k results are re-selected from it on the device, inside the search time.
-        boost: (per-query {row: weight} or None, only_boosted) of boost_plan - the search result is merged with the
-        listed rows on the device (DeviceIndex.search_boosted; with only_boosted there is no search), at the width the
-        MMR re-selection consumes when there is one, inside the search time.
-        probes: ann_plan's count - the IVF index is searched instead of the exact one (never with allow or boost), at
-        the candidate width when mmr is given; the re-selection reads the exact index's rows.
-        sets: within_plan's per-query set ids - every search is restricted to them (DeviceIndex.search(sets=)); the
-        listed rows of `boost` outside a query's sets are dropped here, on the host (boosts_within).
-        caps: cap_plan's (aisle, department) caps (never with probes) - without mmr the k results are the capped walk
-        of the whole ranking, boosted when boost is given (DeviceIndex.search_capped, `width` candidates per round:
-        the request's `candidates`, or None for the default); with mmr the caps thin the candidate list in one round
-        (DeviceIndex.cap_select at the candidates' own width) and the re-selection picks from what is left."""
-        if sets is not None:
-            if boost is not None:
-                boost = (boosts_within(boost[0], sets, self._set_member), boost[1])
-            sets = rowset_ids(sets, len(cu) - 1, None, self.device)
-        if allow is not None:
-            allow = facet_masks(allow, len(cu) - 1, self._index.n_facets, self.device)
+        current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  The search is three steps:
+        1. the SOURCE ranking, w wide: the IVF index's with plan.probes (it takes exclusions only), else
+           DeviceIndex.ranked under plan.allow's masks and plan.sets' ids (with plan.boost the listed rows are merged in);
+        2. with plan.caps, one round of DeviceIndex.cap_select thins the list at its own width;
+        3. with plan.mmr = (lambda, candidates), w = candidates and DeviceIndex.mmr_select re-selects the k results
+           from the exact index's rows; without it w = k.
+        The exception is caps without mmr: the k results are the capped walk of the WHOLE source ranking, which
+        DeviceIndex.search_capped takes in rounds of plan.width candidates (None: its default)."""
+        n = len(cu) - 1
+        sets = None if plan.sets is None else rowset_ids(plan.sets, n, None, self.device)
+        allow = None if plan.allow is None else facet_masks(plan.allow, n, self._index.n_facets, self.device)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
         stream = torch.cuda.current_stream(self.device)
         if ev:
@@ -775,61 +800,43 @@ class Recommender:
         emb = self.model.encoder.encode_packed_host(ids, cu)
         if ev:
             ev[1].record(stream)
-        if caps is not None and mmr is None:
-            idx, sc = self._index.search_capped(emb, k, caps, width, ex, allow, sets, None if boost is None else boost[0],
-                                                only=bool(boost and boost[1]))
-        elif caps is not None:
-            if boost is None:
-                idx, sc = self._index.search(emb, mmr[1], ex, allow, sets)
-            else:
-                idx, sc = self._index.search_boosted(emb, mmr[1], boost[0], ex, allow, only=boost[1], sets=sets)
-            idx, sc = self._index.cap_select(idx, sc, caps, mmr[1])[:2]
-            idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
-        elif probes is not None:
-            idx, sc = self._ann.search(emb, k if mmr is None else mmr[1], probes, ex)
-            if mmr is not None:
-                idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
-        elif boost is not None:
-            idx, sc = self._index.search_boosted(emb, k if mmr is None else mmr[1], boost[0], ex, allow, only=boost[1],
-                                                 sets=sets)
-            if mmr is not None:
-                idx, sc = self._index.mmr_select(idx, sc, k, mmr[0])
-        elif mmr is None:
-            idx, sc = self._index.search(emb, k, ex, allow, sets)
+        if plan.caps is not None and plan.mmr is None:
+            idx, sc = self._index.search_capped(emb, k, plan.caps, plan.width, ex, allow, sets, plan.boost,
+                                                only=plan.only_boosted)
         else:
-            idx, sc = self._index.search_diverse(emb, k, mmr[0], mmr[1], ex, allow, sets)
+            w = k if plan.mmr is None else plan.mmr[1]
+            if plan.probes is not None:
+                idx, sc = self._ann.search(emb, w, plan.probes, ex)
+            else:
+                idx, sc = self._index.ranked(emb, w, ex, allow, sets, plan.boost, plan.only_boosted)
+            if plan.caps is not None:
+                idx, sc = self._index.cap_select(idx, sc, plan.caps, w)[:2]
+            if plan.mmr is not None:
+                idx, sc = self._index.mmr_select(idx, sc, k, plan.mmr[0])
         if ev:
             ev[2].record(stream)
         idx, sc = idx.cpu().numpy(), sc.cpu().numpy()  # synchronises the stream
         return (idx, sc, ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])) if ev else (idx, sc)
 
-    def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, aisles=None,
-                       departments=None, diversity=None, candidates=None, boosts=None, boost_weight=None,
-                       only_boosted=False, probes=None, within=None, max_per_aisle=None, max_per_department=None):
-        """One request: a replayed hipGraph (fastpath.py) when one supports it, else the un-captured path (always
-        when the request names aisles, departments or product sets, asks for diversity, boosts products, probes the
-        IVF index, or caps the products per aisle or department).
-        -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
+    def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, **options):
+        """One request (options: recommend's keywords): a replayed hipGraph (fastpath.py) when its plan is plain - no
+        aisles, departments, product sets, diversity, boosts, probes or caps - and a graph supports it, else the
+        un-captured path.  -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
-        probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
-                          boosts=boosts, only_boosted=only_boosted, within=within, max_per_aisle=max_per_aisle,
-                          max_per_department=max_per_department)
-        caps = cap_plan(max_per_aisle, max_per_department, self.aisles is not None)
-        sets = within_plan(None if within is None else [within], 1, self.product_sets)
-        mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
-        allow = self._facet_allow(None if aisles is None else [aisles], None if departments is None else [departments], 1)
-        boost = boost_plan([boosts], boost_weight, only_boosted, 1, self._pid_to_row)
+        for name in ("aisles", "departments", "within", "boosts"):  # the per-query options, in the batch's form
+            if options.get(name) is not None:
+                options[name] = [options[name]]
+        plan = self._plan(1, top_k, **options)
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed([query])
         tok_ms = (time.time() - t0) * 1000
         ex = self._exclusion_rows([exclude_product_ids])
         rows = ex[0] if ex else []
-        fast = self._fast_path() if allow is None and mmr is None and boost is None and probes is None and sets is None \
-            and caps is None else None
+        fast = self._fast_path() if plan.plain else None
         if fast is not None and fast.supports(len(ids), k, len(rows)):
             idx, sc, *ms = fast.run(ids, k, rows, timed=timed)
         else:
-            idx, sc, *ms = self._encode_search(ids, cu, k, ex, timed, allow, mmr, boost, probes, sets, caps, candidates)
+            idx, sc, *ms = self._encode_search(ids, cu, k, ex, plan, timed)
             idx, sc = idx[0], sc[0]
         results = self._to_results(idx, sc)
         return (results, tok_ms + ms[0], ms[1]) if timed else results
@@ -851,20 +858,14 @@ class Recommender:
         and only_boosted: one value for the whole batch.  probes: one value for the whole batch, as recommend takes it.
         within: None or one entry per query, each None or as recommend takes it.  max_per_aisle / max_per_department: one
         value for the whole batch, as recommend takes them."""
-        probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
-                          boosts=boosts, only_boosted=only_boosted, within=within, max_per_aisle=max_per_aisle,
-                          max_per_department=max_per_department)
-        caps = cap_plan(max_per_aisle, max_per_department, self.aisles is not None)
-        sets = within_plan(within, len(queries), self.product_sets)
-        mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
-        boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
+        plan = self._plan(len(queries), top_k, aisles=aisles, departments=departments, diversity=diversity,
+                          candidates=candidates, boosts=boosts, boost_weight=boost_weight, only_boosted=only_boosted,
+                          probes=probes, within=within, max_per_aisle=max_per_aisle, max_per_department=max_per_department)
         if not queries:
             return []
         k = self._k(top_k)
         ex = self._exclusion_rows(exclude_product_ids)
-        allow = self._facet_allow(aisles, departments, len(queries))
-        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, allow=allow, mmr=mmr, boost=boost,
-                                      probes=probes, sets=sets, caps=caps, width=candidates)
+        idx, sc = self._encode_search(*self.model.tokenizer.packed(list(queries)), k, ex, plan)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))]
 
     def recommend_batches(self, batches, top_k: int = 10, exclude_product_ids=None):
@@ -889,17 +890,14 @@ class Recommender:
         on the launch stream — what the micro-batching server reports as per-request stats.  A diversified batch's
         re-selection, a boosted batch's merge and a capped batch's rounds count into the similarity time."""
         k = self._k(top_k)
-        caps = cap_plan(max_per_aisle, max_per_department, self.aisles is not None)
-        sets = within_plan(within, len(queries), self.product_sets)
-        mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
-        boost = boost_plan(boosts, boost_weight, only_boosted, len(queries), self._pid_to_row)
+        plan = self._plan(len(queries), top_k, aisles=aisles, departments=departments, diversity=diversity,
+                          candidates=candidates, boosts=boosts, boost_weight=boost_weight, only_boosted=only_boosted,
+                          within=within, max_per_aisle=max_per_aisle, max_per_department=max_per_department)
         ex = self._exclusion_rows(exclude_product_ids)
-        allow = self._facet_allow(aisles, departments, len(queries))
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed(list(queries))
         tok_ms = (time.time() - t0) * 1000
-        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, timed=True, allow=allow, mmr=mmr, boost=boost, sets=sets,
-                                                      caps=caps, width=candidates)
+        idx, sc, enc_ms, sim_ms = self._encode_search(ids, cu, k, ex, plan, timed=True)
         return [self._to_results(idx[i], sc[i]) for i in range(len(queries))], tok_ms + enc_ms, sim_ms
 
     def recommend(self, query: str, top_k: int = 10,

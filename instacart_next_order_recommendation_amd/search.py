@@ -215,6 +215,30 @@ def apply_moves(array, new_n: int, dst, src, axis: int = 0):
     return np.ascontiguousarray(a[tuple(cut)])
 
 
+def _out_pair(Q: int, k: int, device):
+    """The (idx int64 [Q, k], score float32 [Q, k]) pair a ranking call writes, uninitialised on `device`."""
+    return (torch.empty((Q, k), dtype=torch.int64, device=device), torch.empty((Q, k), dtype=torch.float32, device=device))
+
+
+def _candidates(idx: torch.Tensor, sc: torch.Tensor, device, score: str = "sc", Q=None):
+    """A candidate pair as `search` returns it, checked - idx int64 [Q, k], its scores (named `score` in the error)
+    float32 [Q, k], with Q rows when Q is given - and contiguous on `device`."""
+    if idx.dim() != 2 or idx.dtype != torch.int64 or sc.dtype != torch.float32 or sc.shape != idx.shape \
+            or (Q is not None and idx.shape[0] != Q):
+        rows = "Q" if Q is None else Q
+        raise ValueError(f"idx must be int64 [{rows}, k] and {score} float32 [{rows}, k], got {idx.dtype} {tuple(idx.shape)} "
+                         f"and {sc.dtype} {tuple(sc.shape)}")
+    return idx.to(device).contiguous(), sc.to(device).contiguous()
+
+
+def _block(scratch, need: int, shape: str, *args):
+    """The current stream's block of `scratch` (a StreamScratch) for a call that needs `need` bytes; 0 is how a
+    *_workspace_bytes entry refuses a shape: IcrecError with shape.format(*args)."""
+    if need == 0:
+        raise _native.IcrecError("bad " + shape.format(*args))
+    return scratch.block(need)
+
+
 ROW_STORAGE = {"f32": 0, "bf16": 1, "f32+filter": 2, "bf16+filter": 3}  # ICREC_ROWS_* in include/icrec.h
 
 
@@ -462,9 +486,7 @@ class DeviceIndex:
     def _workspace(self, n_queries: int, k: int) -> torch.Tensor:
         """This stream's scratch block, large enough for one search of this shape."""
         need = int(_native.lib().icrec_search_workspace_bytes(self._h, n_queries, k))
-        if need == 0:
-            raise _native.IcrecError(f"bad search shape: n_queries={n_queries}, k={k}")
-        return self._ws_by_stream.block(need)
+        return _block(self._ws_by_stream, need, "search shape: n_queries={}, k={}", n_queries, k)
 
     def _queries(self, q) -> torch.Tensor:
         q = torch.as_tensor(q)
@@ -499,8 +521,7 @@ class DeviceIndex:
         q = self._queries(q)
         Q = int(q.shape[0])
         ei, eo = exclusion_csr(exclude, Q, self.device)
-        idx = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        sc = torch.empty((Q, k), dtype=torch.float32, device=self.device)
+        idx, sc = _out_pair(Q, k, self.device)
         self.search_into(q, k, ei, eo, idx, sc, allow=allow, sets=sets)
         return idx, sc
 
@@ -540,12 +561,8 @@ class DeviceIndex:
         -> (idx int64 [Q, top_k], rel float32 [Q, top_k]) on the device, in SELECTION order: the most relevant
         candidate first, then at each step the candidate that maximises lam * rel - (1 - lam) * (its greatest
         similarity to a row already picked).  lam = 1 keeps the relevance order, lam = 0 only avoids similarity."""
-        if idx.dim() != 2 or idx.dtype != torch.int64 or rel.dtype != torch.float32 or rel.shape != idx.shape:
-            raise ValueError(f"idx must be int64 [Q, k] and rel float32 [Q, k], got {idx.dtype} {tuple(idx.shape)} "
-                             f"and {rel.dtype} {tuple(rel.shape)}")
-        idx, rel = idx.to(self.device).contiguous(), rel.to(self.device).contiguous()
-        out_idx = torch.empty((idx.shape[0], top_k), dtype=torch.int64, device=self.device)
-        out_rel = torch.empty((idx.shape[0], top_k), dtype=torch.float32, device=self.device)
+        idx, rel = _candidates(idx, rel, self.device, "rel")
+        out_idx, out_rel = _out_pair(int(idx.shape[0]), top_k, self.device)
         self.mmr_select_into(idx, rel, top_k, lam, out_idx, out_rel)
         return out_idx, out_rel
 
@@ -556,9 +573,7 @@ class DeviceIndex:
         Q, k = int(idx.shape[0]), int(idx.shape[1])
         if ws is None:
             need = int(_native.lib().icrec_mmr_select_workspace_bytes(self._h, Q, k))
-            if need == 0:
-                raise _native.IcrecError(f"bad mmr_select shape: n_queries={Q}, k={k}")
-            ws = self._mmr_ws_by_stream.block(need)
+            ws = _block(self._mmr_ws_by_stream, need, "mmr_select shape: n_queries={}, k={}", Q, k)
         _native.mmr_select(self._h, idx, rel, top_k, lam, out_idx, out_rel, ws, self.device)
 
     def search_diverse(self, q, top_k: int, lam: float, candidates: int,
@@ -583,15 +598,10 @@ class DeviceIndex:
         if (idx is None) != (sc is None):
             raise ValueError("idx and sc must both be given or both be None")
         if idx is not None:
-            if idx.dim() != 2 or idx.dtype != torch.int64 or sc.dtype != torch.float32 or sc.shape != idx.shape \
-                    or idx.shape[0] != Q:
-                raise ValueError(f"idx must be int64 [{Q}, k] and sc float32 [{Q}, k], got {idx.dtype} {tuple(idx.shape)} "
-                                 f"and {sc.dtype} {tuple(sc.shape)}")
-            idx, sc = idx.to(self.device).contiguous(), sc.to(self.device).contiguous()
+            idx, sc = _candidates(idx, sc, self.device, Q=Q)
         off, rows, w, max_len = boost_csr(boosts, Q, self.device)
         ei, eo = exclusion_csr(exclude, Q, self.device)
-        out_idx = torch.empty((Q, top_k), dtype=torch.int64, device=self.device)
-        out_sc = torch.empty((Q, top_k), dtype=torch.float32, device=self.device)
+        out_idx, out_sc = _out_pair(Q, top_k, self.device)
         self.boost_select_into(q, idx, sc, off, rows, w, max_len if idx is not None else max(max_len, 1), top_k, ei, eo,
                                allow, out_idx, out_sc)
         return out_idx, out_sc
@@ -611,9 +621,7 @@ class DeviceIndex:
             self._check_allow(allow, Q)
         if ws is None:
             need = int(_native.lib().icrec_boost_select_workspace_bytes(self._h, Q, max_boosts))
-            if need == 0:
-                raise _native.IcrecError(f"bad boost_select shape: n_queries={Q}, max_boosts={max_boosts}")
-            ws = self._boost_ws_by_stream.block(need)
+            ws = _block(self._boost_ws_by_stream, need, "boost_select shape: n_queries={}, max_boosts={}", Q, max_boosts)
         _native.boost_select(self._h, q, idx, sc, boost_off, boost_rows, boost_w, max_boosts, excl_idx, excl_off, allow,
                              top_k, out_idx, out_score, ws, self.device)
 
@@ -629,6 +637,12 @@ class DeviceIndex:
         idx, sc = (None, None) if only else self.search(q, k, exclude, allow, sets)
         return self.boost_select(q, idx, sc, boosts, k, exclude, allow)
 
+    def ranked(self, q, k: int, exclude=None, allow=None, sets=None, boosts=None, only: bool = False):
+        """The source ranking of a request, k wide: `search`, or with boosts (per-query lists, not None) `search_boosted`."""
+        if boosts is None:
+            return self.search(q, k, exclude, allow, sets)
+        return self.search_boosted(q, k, boosts, exclude, allow, only, sets)
+
     def cap_select(self, idx: torch.Tensor, sc: torch.Tensor, caps, top_k: int, allow: Optional[torch.Tensor] = None):
         """Caps per facet value on a search result (icrec_cap_select): idx int64 [Q, k] candidate rows as `search`
         returns them (-1 pads; rows outside this shard are skipped) and sc float32 [Q, k] their scores, both device
@@ -638,13 +652,9 @@ class DeviceIndex:
         already has its cap of rows before them; state[q] = (picks, done), done = 0 where fewer than top_k rows were
         kept and the list held no pad - a wider or a further search may then find more (search_capped runs those
         rounds); allow_next = allow without the values that are full."""
-        if idx.dim() != 2 or idx.dtype != torch.int64 or sc.dtype != torch.float32 or sc.shape != idx.shape:
-            raise ValueError(f"idx must be int64 [Q, k] and sc float32 [Q, k], got {idx.dtype} {tuple(idx.shape)} "
-                             f"and {sc.dtype} {tuple(sc.shape)}")
-        idx, sc = idx.to(self.device).contiguous(), sc.to(self.device).contiguous()
+        idx, sc = _candidates(idx, sc, self.device)
         Q = int(idx.shape[0])
-        out_idx = torch.empty((Q, top_k), dtype=torch.int64, device=self.device)
-        out_sc = torch.empty((Q, top_k), dtype=torch.float32, device=self.device)
+        out_idx, out_sc = _out_pair(Q, top_k, self.device)
         state = torch.empty((Q, 2), dtype=torch.int32, device=self.device)
         allow_next = torch.empty((Q, max(self.n_facets, 1), _native.ICREC_FACET_MASK_WORDS), dtype=torch.int32,
                                  device=self.device).view(torch.uint32)
@@ -702,13 +712,8 @@ class DeviceIndex:
             raise ValueError(f"exclude has {len(exclude)} entries for {Q} queries")
         if boosts is not None and len(boosts) != Q:
             raise ValueError(f"boosts has {len(boosts)} entries for {Q} queries")
-
-        def ranked(q_, exclude_, allow_, sets_, boosts_):
-            if boosts_ is None:
-                return self.search(q_, k, exclude_, allow_, sets_)
-            return self.search_boosted(q_, k, boosts_, exclude_, allow_, only, sets_)
-
-        out_idx, out_sc, state, allow_next = self.cap_select(*ranked(q, exclude, allow, sets, boosts), caps, top_k, allow)
+        out_idx, out_sc, state, allow_next = self.cap_select(*self.ranked(q, k, exclude, allow, sets, boosts, only), caps, top_k,
+                                                             allow)
         self.last_cap_rounds = 1
         words = allow_next.view(torch.int32)  # (torch indexes int32, not uint32)
         while True:
@@ -726,8 +731,8 @@ class DeviceIndex:
                     for i, row in zip(sub, picks)]
             masks = words[left].contiguous().view(torch.uint32)
             st = torch.empty((len(sub), 2), dtype=torch.int32, device=self.device)
-            c_idx, c_sc = ranked(q[left], excl, masks, None if sets is None else sets[left].contiguous(),
-                                 None if boosts is None else [boosts[i] for i in sub])
+            c_idx, c_sc = self.ranked(q[left], k, excl, masks, None if sets is None else sets[left].contiguous(),
+                                      None if boosts is None else [boosts[i] for i in sub], only)
             self.cap_select_into(c_idx, c_sc, caps[left].contiguous(), top_k, o_idx, o_sc, st, n_prior, masks, masks)
             out_idx[left], out_sc[left], state[left], words[left] = o_idx, o_sc, st, masks.view(torch.int32)
 
@@ -841,10 +846,8 @@ class IvfIndex:
     def _workspace(self, n_queries: int, k: int, probes: int) -> torch.Tensor:
         """This stream's scratch block, large enough for one search of this shape."""
         need = int(_native.lib().icrec_ivf_search_workspace_bytes(self._h, n_queries, k, probes))
-        if need == 0:
-            raise _native.IcrecError(f"bad IVF search shape: n_queries={n_queries}, k={k}, probes={probes} "
-                                     f"of {self.n_lists} lists")
-        return self._ws_by_stream.block(need)
+        return _block(self._ws_by_stream, need, "IVF search shape: n_queries={}, k={}, probes={} of {} lists",
+                      n_queries, k, probes, self.centroids.shape[0])
 
     def search(self, q, k: int, probes: int, exclude: Optional[Sequence[Iterable[int]]] = None):
         """The k best rows of each query's `probes` best lists: (idx int64[Q,k] with -1 pads, score float32[Q,k]),
@@ -852,8 +855,7 @@ class IvfIndex:
         q = self.index._queries(q)
         Q = int(q.shape[0])
         ei, eo = exclusion_csr(exclude, Q, self.device)
-        idx = torch.empty((Q, k), dtype=torch.int64, device=self.device)
-        sc = torch.empty((Q, k), dtype=torch.float32, device=self.device)
+        idx, sc = _out_pair(Q, k, self.device)
         self.search_into(q, k, probes, ei, eo, idx, sc)
         return idx, sc
 
@@ -913,8 +915,7 @@ def merge_topk(keys: torch.Tensor, k: int):
         raise ValueError("keys must be [n_lists, Q, k]")
     keys = keys.contiguous()
     n_lists, Q = int(keys.shape[0]), int(keys.shape[1])
-    idx = torch.empty((Q, k), dtype=torch.int64, device=keys.device)
-    sc = torch.empty((Q, k), dtype=torch.float32, device=keys.device)
+    idx, sc = _out_pair(Q, k, keys.device)
     _native.check(_native.lib().icrec_merge_topk(ptr(keys), n_lists, Q, k, ptr(idx), ptr(sc), keys.device.index,
                                                  stream_ptr(keys.device)), "icrec_merge_topk")
     return idx, sc

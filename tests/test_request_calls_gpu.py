@@ -1,0 +1,171 @@
+"""The sequence of libicrec calls a request makes, per combination of request features: recommend (un-captured),
+recommend_batch and recommend_batch_timed on one synthetic recommender (2-layer model, 300 products, an IVF index of 4
+lists, two product sets, five queries) with `_native._lib` behind a recording proxy.  Every trace is compared with the
+composition rule written once in `expected`: encode, then a SOURCE ranking (IVF search, the boosted products alone, or
+a search followed by the boost merge), then optionally the caps, then optionally the MMR re-selection - with caps and
+no diversity, source + caps repeated once per round of DeviceIndex.search_capped.  What the calls compute is pinned by
+the test_*_recommender_gpu.py files; this file pins which calls are made, in which order, at which widths."""
+from __future__ import annotations
+
+import json
+
+import pytest
+
+from instacart_next_order_recommendation_amd import _native
+from instacart_next_order_recommendation_amd import synthetic as syn
+from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
+from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender
+from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+
+N = 300
+SETS = {"store": [str(i) for i in range(1, N + 1) if i % 3], "stock": [str(i) for i in range(1, N + 1) if i % 2 == 0]}
+QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
+K, WIDE, NARROW = 10, 40, 12  # top_k; the candidates of a diversified request; those of a capped one (rounds follow)
+
+# entry -> the positions of (n_queries, the widths) among its arguments (include/icrec.h)
+RECORDED = {
+    "icrec_encode": (3,), "icrec_encode_ex": (3,),
+    "icrec_search": (2, 3), "icrec_search_faceted": (2, 3), "icrec_search_in_sets": (2, 3),
+    "icrec_boost_select": (2, 5, 13),   # n_queries, k of the candidates (0: none), top_k
+    "icrec_cap_select": (3, 4, 8),      # n_queries, k, top_k
+    "icrec_mmr_select": (3, 4, 5),      # n_queries, k, top_k
+    "icrec_ivf_search": (2, 3),
+}
+
+
+class RecordingLib:
+    """libicrec with the calls to RECORDED's entries noted in order as (name without "icrec_", n_queries, widths ..);
+    every other entry (workspace sizes, accessors) goes through unrecorded."""
+
+    def __init__(self, real):
+        self._real, self.trace = real, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+        if name not in RECORDED:
+            return fn
+
+        def call(*args):
+            self.trace.append((name[len("icrec_"):].replace("encode_ex", "encode"),) + tuple(int(args[i]) for i in RECORDED[name]))
+            return fn(*args)
+
+        return call
+
+
+@pytest.fixture(scope="module")
+def rec(tmp_path_factory, torch_cuda):
+    tmp = tmp_path_factory.mktemp("request_calls")
+    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
+    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
+    corpus_path = tmp / "processed" / "eval_corpus.json"
+    corpus_path.parent.mkdir()
+    corpus_path.write_text(json.dumps(syn.synthetic_catalog(N)))
+    r = MonitoredRecommender(model_dir, corpus_path, use_index=False, ann_lists=4, product_sets=SETS)
+    assert r._index.n_facets == 2 and r._index.n_rowsets == 2 and r._ann.n_lists == 4
+    return r
+
+
+@pytest.fixture()
+def lib(rec, monkeypatch):
+    proxy = RecordingLib(_native.lib())
+    monkeypatch.setattr(_native, "_lib", proxy)
+    monkeypatch.setattr(rec, "_fast", None)  # the graph path replays captured launches: the traced calls go around it
+    return proxy
+
+
+def source(f, Q, w, later_round=False):
+    """The calls of a source ranking of width w.  A capped request's rounds after the first always carry masks."""
+    if "probes" in f:
+        return [("ivf_search", Q, w)]
+    if "only_boosted" in f:
+        return [("boost_select", Q, 0, w)]
+    search = "search_in_sets" if "sets" in f else "search_faceted" if "allow" in f or later_round else "search"
+    return [(search, Q, w)] + ([("boost_select", Q, w, w)] if "boosts" in f else [])
+
+
+def expected(f, Q, k, w, round_queries):
+    """The rule.  f: the request's features; w: the candidate width, k: the result count; round_queries: the number of
+    queries in each round of a capped request without diversity."""
+    out = [("encode", Q)]
+    if "caps" in f and "diversity" not in f:
+        for r, Qr in enumerate(round_queries):
+            out += source(f, Qr, w, later_round=r > 0) + [("cap_select", Qr, w, k)]
+        return out
+    out += source(f, Q, w)
+    if "caps" in f:
+        out.append(("cap_select", Q, w, w))
+    if "diversity" in f:
+        out.append(("mmr_select", Q, w, k))
+    return out
+
+
+BASES = {"plain": (), "allow": ("allow",), "sets": ("sets",), "sets + allow": ("sets", "allow"), "boosts": ("boosts",),
+         "only_boosted": ("only_boosted",), "boosts + sets": ("boosts", "sets"), "probes": ("probes",)}
+CASES = ([(b,) for b in BASES]
+         + [(b, "diversity") for b in ("plain", "allow", "boosts", "only_boosted", "probes", "sets")]
+         + [(b, "caps") for b in ("plain", "allow", "sets", "boosts", "only_boosted")]
+         + [(b, "caps", "diversity") for b in ("plain", "boosts")])
+
+
+def request(rec, features, n):
+    """The keywords of a request with these features: the per-query ones as lists of n entries, or, for n = None,
+    as recommend takes them."""
+    listed = [[p for p in rec.product_ids[i::7]] for i in range(5)]  # 40-odd products each, inside and outside the sets
+    per_query = {
+        "allow": ("departments", [rec.departments[:10], None, rec.departments[3:9], rec.departments[:2], None]),
+        "sets": ("within", ["store", ["store", "stock"], None, "stock", "store"]),
+        "boosts": ("boosts", listed), "only_boosted": ("boosts", listed),
+    }
+    kw = {}
+    for f in features:
+        if f in per_query:
+            name, values = per_query[f]
+            kw[name] = values[0] if n is None else values[:n]
+    if "boosts" in features or "only_boosted" in features:
+        kw["boost_weight"] = 0.5
+    if "only_boosted" in features:
+        kw["only_boosted"] = True
+    if "probes" in features:
+        kw["probes"] = 2
+    if "diversity" in features:
+        kw.update(diversity=0.3, candidates=WIDE)
+    if "caps" in features:
+        kw["max_per_department"] = 1
+        kw.setdefault("candidates", NARROW)
+    return kw
+
+
+def check(lib, rec, features, Q, call):
+    del lib.trace[:]
+    rec._index.last_cap_rounds = 0
+    results = call()
+    trace = list(lib.trace)
+    capped_walk = "caps" in features and "diversity" not in features
+    w = K if features <= {"allow", "sets", "boosts", "only_boosted", "probes"} else NARROW if capped_walk else WIDE
+    round_queries = [t[1] for t in trace if t[0] == "cap_select"] if capped_walk else []
+    if capped_walk:
+        assert len(round_queries) == rec._index.last_cap_rounds >= 1, (features, trace)
+        assert round_queries[0] == Q and all(1 <= b <= a for a, b in zip(round_queries, round_queries[1:])), (features, trace)
+    else:
+        assert rec._index.last_cap_rounds == 0  # search_capped did not run
+    assert trace == expected(features, Q, K, w, round_queries), (features, trace)
+    return results, rec._index.last_cap_rounds
+
+
+@pytest.mark.parametrize("case", CASES, ids=[" + ".join(c) for c in CASES])
+def test_calls_follow_the_composition_rule(rec, lib, case):
+    features = frozenset(BASES[case[0]]) | frozenset(case[1:])
+    kw = request(rec, features, None)
+    one, _ = check(lib, rec, features, 1, lambda: rec.recommend(QUERIES[0], K, exclude_product_ids={"7", "8"}, **kw))
+    assert len(one) <= K and (one or "only_boosted" in features)
+    kw = request(rec, features, len(QUERIES))
+    excl = [{"7", "8"}, None, {"1"}, None, None]
+    batch, rounds = check(lib, rec, features, len(QUERIES), lambda: rec.recommend_batch(QUERIES, K, excl, **kw))
+    assert batch[0] == one
+    if case == ("plain", "caps"):
+        assert rounds >= 2  # one department each of 12 candidates: some query's list ran out before 10 were kept
+    if "probes" not in features:  # (recommend_batch_timed has no probes keyword)
+        timed, _ = check(lib, rec, features, len(QUERIES), lambda: rec.recommend_batch_timed(QUERIES, K, excl, **kw)[0])
+        assert timed == batch
