@@ -887,6 +887,56 @@ ICREC_API int icrec_ir_metrics(const int64_t* ranked_rows_dev, int32_t depth, co
                      void* workspace_dev, size_t workspace_bytes, int device, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Rank fusion: two ranked lists of the same ids (icrec_search's out_idx and   */
+/* icrec_cf_rank's out_idx over the same corpus rows) merged into one by       */
+/* POSITION: a cosine and an integer co-occurrence count share no scale, so    */
+/* each list contributes a weight per position (reciprocal rank fusion and its */
+/* weighted relatives) and the sums are ranked.  Needs no handle.              */
+/* ------------------------------------------------------------------------- */
+
+/*   a_idx_dev     int64[n_queries, ka]       list A: ids, best first, negative = pad
+ *   b_idx_dev     int64[n_queries, kb]       list B, likewise; ka, kb in [1, ICREC_MAX_K], they need not be equal
+ *   a_gate_dev    int32[n_queries, ka] or NULL, b_gate_dev int32[n_queries, kb] or NULL: an entry counts only where its
+ *                                            gate is > 0.  The gate is icrec_cf_rank's out_score: a candidate that
+ *                                            co-occurs with nothing in the history is not a recommendation, and an
+ *                                            empty history must not vote for corpus rows 0 .. k-1.
+ *   a_w_dev       float[ka], b_w_dev float[kb]  the weight of each position, one table per list, shared by all queries;
+ *                                            device memory, so no value can be refused by the host
+ *   n_ids         in [1, 2^32 - 1]           ids lie in [0, n_ids)
+ *   excl_idx_dev / excl_off_dev              icrec_search's exclusion CSR (ascending and unique per segment), or both NULL
+ *   top_k         in [1, ICREC_MAX_K]        it may exceed the number of distinct live ids
+ *   out_idx_dev   int64[n_queries, top_k]    out_score_dev float[n_queries, top_k]
+ *   out_pos_dev   int32[n_queries, top_k, 2] or NULL: the positions in A and in B that produced each result, -1 where
+ *                                            the id is not live in that list
+ * The definition, which the result follows bit for bit:
+ *   Live entry.  Entry j of list L is live iff 0 <= id < n_ids, and its gate is NULL or > 0, and id is not in the query's
+ *     exclusion segment (an id above 2^31 - 1 cannot be excluded), and no position j' < j of the same list holds the same
+ *     id and passes the three tests before (the first passing occurrence wins: a gated-off first occurrence does not
+ *     hide a gated-on second one).  Nothing is read through a dead id.
+ *   Effective weight.  e_L(j) = w_L[j] if w_L[j] > 0 (+inf included), else +0.0f: a NaN, a negative value and -0 count
+ *     as +0.
+ *   Fused score.  f(id) = eA + eB, one fp32 addition; eL is the effective weight of the id's live entry in L, or +0.0f
+ *     when it has none.  f is never NaN and never -0.
+ *   Result.  The ids with a live entry in A or in B, ordered by f descending compared as floats, lower id first on ties
+ *     (the order of icrec_search_partial's keys).  The first top_k are written, then -1 / 0.0f / {-1, -1} pads.
+ * Consequences.  Swapping the roles of A and B gives the same out_idx / out_score bits (fp32 addition commutes), with
+ * the out_pos columns swapped.  With B entirely dead and a_w strictly decreasing and positive, the result is A's live
+ * entries in A's order (f = a_w[j] + 0 = a_w[j]).  A query has the same bits alone and inside any batch.
+ * ICREC_EINVAL, before any HIP call, and nothing is launched: a NULL among the lists, the tables, out_idx_dev,
+ * out_score_dev; excl_idx_dev and excl_off_dev not both set or both NULL; n_queries < 1; ka, kb or top_k outside
+ * [1, ICREC_MAX_K]; n_ids outside [1, 2^32 - 1] (a key holds a 32-bit id).
+ * Asynchronous on `stream`: one launch of one workgroup per query, no workspace, nothing is allocated, nothing
+ * synchronises, and the call can be captured into a hipGraph.  Gates, tables and exclusions are read from device memory
+ * when the kernel runs.  The outputs must not alias the inputs. */
+ICREC_API int icrec_fuse_select(
+    const int64_t* a_idx_dev, const int32_t* a_gate_dev, int32_t ka, const float* a_w_dev,
+    const int64_t* b_idx_dev, const int32_t* b_gate_dev, int32_t kb, const float* b_w_dev,
+    int32_t n_queries, int64_t n_ids,
+    const int32_t* excl_idx_dev, const int32_t* excl_off_dev,
+    int32_t top_k, int64_t* out_idx_dev, float* out_score_dev, int32_t* out_pos_dev,
+    int device, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU exchange (new design, the reference has none:      */
 /* serve_recommendations.py:172-181 only picks a device).  One process per    */
 /* GPU; the catalog is row-sharded (each rank's icrec_index carries its       */

@@ -54,7 +54,7 @@ EXPORTS = [
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
     "icrec_cf_create", "icrec_cf_destroy", "icrec_cf_orders", "icrec_cf_items", "icrec_cf_candidates", "icrec_cf_nnz",
     "icrec_cf_tile", "icrec_cf_rank_workspace_bytes", "icrec_cf_rank", "icrec_cf_rank_all_workspace_bytes",
-    "icrec_cf_rank_all", "icrec_ir_metrics_workspace_bytes", "icrec_ir_metrics",
+    "icrec_cf_rank_all", "icrec_ir_metrics_workspace_bytes", "icrec_ir_metrics", "icrec_fuse_select",
     "icrec_tokenizer_create", "icrec_tokenizer_create_ex", "icrec_tokenizer_destroy", "icrec_tokenizer_vocab_size", "icrec_tokenize",
     "icrec_last_error", "icrec_version",
     "icrec_timing_enable", "icrec_timing_reset", "icrec_timing_query",
@@ -195,6 +195,7 @@ def lib() -> C.CDLL:
         "icrec_cf_rank_all": (C.c_int, [vp, vp, vp, i32, vp, vp, sz, vp]),
         "icrec_ir_metrics_workspace_bytes": (sz, [i32]),
         "icrec_ir_metrics": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, sz, C.c_int, vp]),
+        "icrec_fuse_select": (C.c_int, [vp, vp, i32, vp, vp, vp, i32, vp, i32, i64, vp, vp, i32, vp, vp, vp, C.c_int, vp]),
         "icrec_normalize_rows": (C.c_int, [vp, vp, i64, i32, C.c_float, C.c_int, vp]),
         "icrec_tokenizer_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]),
         "icrec_tokenizer_create_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
@@ -297,6 +298,18 @@ def cap_select(index_handle, cand_idx, cand_score, caps, n_prior, allow, top_k: 
     check(lib().icrec_cap_select(index_handle, ptr(cand_idx), ptr(cand_score), Q, k, ptr(caps), ptr(n_prior), ptr(allow),
                                  int(top_k), ptr(out_idx), ptr(out_score), ptr(out_state), ptr(allow_next),
                                  stream_ptr(device)), "icrec_cap_select")
+
+
+def fuse_select(a_idx, a_gate, a_w, b_idx, b_gate, b_w, n_ids: int, excl_idx, excl_off, top_k: int, out_idx, out_score,
+                out_pos, device) -> None:
+    """icrec_fuse_select on device tensors: a_idx int64 [Q, ka] and b_idx int64 [Q, kb] in, their gates int32 of the
+    same shapes or None, a_w float32 [ka] and b_w float32 [kb], the search's exclusion CSR or None, out_idx int64
+    [Q, top_k] and out_score float32 [Q, top_k] out, out_pos int32 [Q, top_k, 2] or None; asynchronous on `device`'s
+    current stream."""
+    Q, ka, kb = int(a_idx.shape[0]), int(a_idx.shape[1]), int(b_idx.shape[1])
+    check(lib().icrec_fuse_select(ptr(a_idx), ptr(a_gate), ka, ptr(a_w), ptr(b_idx), ptr(b_gate), kb, ptr(b_w), Q, int(n_ids),
+                                  ptr(excl_idx), ptr(excl_off), int(top_k), ptr(out_idx), ptr(out_score), ptr(out_pos),
+                                  device.index, stream_ptr(device)), "icrec_fuse_select")
 
 
 def timing_enable(on: bool) -> None:

@@ -24,7 +24,7 @@ from . import _native, ir_metrics
 from ._native import ptr, stream_ptr
 from .model_io import load_model_dir
 from .recommender import SbertModel
-from .search import DeviceIndex
+from .search import DeviceIndex, fuse_select, rrf_weights
 
 
 def _evaluate(baseline, relevant_docs: dict[str, set[str]], depth: int, queries_per_pass: int | None,
@@ -233,12 +233,32 @@ class ItemItemCFBaseline:
             off[i + 1] = len(flat)
         return torch.from_numpy(off).to(self.device), torch.from_numpy(np.asarray(flat, np.int32)).to(self.device)
 
-    def rank_rows_scores(self, query_ids: list[str], depth: int | None) -> tuple[torch.Tensor, torch.Tensor | None]:
-        """One pass on the device: (rows int64 [Q, depth or n_candidates], int32 scores [Q, depth] or None)."""
+    def history_csr_from(self, histories) -> tuple[torch.Tensor, torch.Tensor]:
+        """history_csr for ad-hoc histories: per query an iterable of product ids (None: an empty history) -> the same
+        (off, items) device CSR, each history's item numbers ascending and unique, unknown products dropped."""
+        off = np.zeros(len(histories) + 1, np.int32)
+        flat: list[int] = []
+        for i, h in enumerate(histories):
+            flat.extend(sorted({self.item_of[p] for p in (h or ()) if p in self.item_of}))
+            off[i + 1] = len(flat)
+        return torch.from_numpy(off).to(self.device), torch.from_numpy(np.asarray(flat, np.int32)).to(self.device)
+
+    def rank_workspace_bytes(self, n_queries: int, depth: int) -> int:
+        """icrec_cf_rank_workspace_bytes: what one pass of rank_rows_scores(.., depth) over n_queries allocates."""
+        return int(_native.lib().icrec_cf_rank_workspace_bytes(self._h, int(n_queries), int(depth))) if self._h else 0
+
+    def rank_rows_scores(self, query_ids, depth: int | None) -> tuple[torch.Tensor, torch.Tensor | None]:
+        """One pass on the device: (rows int64 [Q, depth or n_candidates], int32 scores [Q, depth] or None).
+        query_ids: a list of eval query ids, or the (off, items) device CSR history_csr / history_csr_from return."""
         if self._h is None:
             raise _native.IcrecError("ItemItemCFBaseline has an empty corpus: nothing to rank")
-        L, Q = _native.lib(), len(query_ids)
-        off, items = self.history_csr(query_ids)
+        L = _native.lib()
+        if isinstance(query_ids, tuple) and len(query_ids) == 2 and isinstance(query_ids[0], torch.Tensor):
+            off, items = query_ids
+            Q = int(off.numel()) - 1
+        else:
+            Q = len(query_ids)
+            off, items = self.history_csr(query_ids)
         st = stream_ptr(self.device)
         if depth is None:
             ws = torch.empty(max(int(L.icrec_cf_rank_all_workspace_bytes(self._h, Q)), 1), dtype=torch.uint8, device=self.device)
@@ -284,3 +304,60 @@ class ItemItemCFBaseline:
                  queries_per_pass: int | None = None) -> dict[str, float]:
         """compute_ir_metrics(rank_all(depth=depth), relevant_docs) without leaving the device."""
         return _evaluate(self, relevant_docs, depth, queries_per_pass)
+
+
+class HybridBaseline:
+    """The content ranking and the item-item CF ranking of the same corpus rows fused by position on the device
+    (reciprocal rank fusion, icrec_fuse_select): per pass the content search and icrec_cf_rank run `depth` wide on the
+    same queries, and a product's fused score is 1 / (rrf_c + its content position + 1) + cf_weight / (rrf_c + its CF
+    position + 1), a list that does not hold it adding 0.  The CF scores gate the CF list: a candidate that co-occurs
+    with nothing in the history does not vote.  Same `rank_rows` / `rank_all(depth)` / `evaluate` contracts as the two
+    baselines it is built from."""
+
+    def __init__(self, content: ContentBasedBaseline, cf: ItemItemCFBaseline, depth: int = 100, cf_weight: float = 1.0,
+                 rrf_c: float = 60.0):
+        if list(content.product_ids) != list(cf.product_ids):
+            raise ValueError("HybridBaseline: the content and the CF baseline must rank the same product ids in the same order")
+        if not 1 <= depth <= _native.ICREC_MAX_K:
+            raise ValueError(f"depth must be in [1, {_native.ICREC_MAX_K}]")
+        if torch.device(content.device) != torch.device(cf.device):
+            raise ValueError(f"HybridBaseline: the baselines live on {content.device} and {cf.device}")
+        self.content, self.cf, self.depth = content, cf, int(depth)
+        self.cf_weight, self.rrf_c = float(cf_weight), float(rrf_c)
+        self.product_ids, self.device = cf.product_ids, cf.device
+        self.eval_queries = content.eval_queries
+
+    def _tables(self, depth: int):
+        """(the content list's, the CF list's) position tables on the device."""
+        return (torch.from_numpy(rrf_weights(depth, self.rrf_c, 1.0)).to(self.device),
+                torch.from_numpy(rrf_weights(depth, self.rrf_c, self.cf_weight)).to(self.device))
+
+    def _row_passes(self, depth: int | None, queries_per_pass: int | None):
+        depth = self.depth if depth is None else depth
+        if not 1 <= depth <= _native.ICREC_MAX_K:
+            raise ValueError(f"depth must be in [1, {_native.ICREC_MAX_K}]")
+        a_w, b_w = self._tables(depth)
+        for a_idx, qids in self.content._row_passes(depth, queries_per_pass):
+            b_idx, b_sc = self.cf.rank_rows_scores(qids, depth)
+            yield fuse_select(a_idx, b_idx, a_w, b_w, depth, len(self.product_ids), b_gate=b_sc)[0], qids
+
+    def rank_rows(self, depth: int | None = None, queries_per_pass: int | None = None) -> tuple[torch.Tensor, list[str]]:
+        """(int64 [Q, depth] corpus rows on the device, best first with -1 pads; the query ids in row order).  depth
+        None: the constructor's."""
+        passes = list(self._row_passes(depth, queries_per_pass))
+        return torch.cat([r for r, _ in passes]), [q for _, qs in passes for q in qs]
+
+    def rank_all(self, depth: int | None = None, queries_per_pass: int | None = None) -> dict[str, list[str]]:
+        """query_id -> product ids by fused score, best first (lower corpus row first on ties): the best `depth` of
+        the union of the two `depth`-wide lists."""
+        out: dict[str, list[str]] = {}
+        for rows, qids in self._row_passes(depth, queries_per_pass):
+            rows = rows.cpu().numpy()
+            for i, qid in enumerate(qids):
+                out[qid] = [self.product_ids[j] for j in rows[i] if j >= 0]
+        return out
+
+    def evaluate(self, relevant_docs: dict[str, set[str]], depth: int | None = None,
+                 queries_per_pass: int | None = None) -> dict[str, float]:
+        """compute_ir_metrics(rank_all(depth), relevant_docs) without leaving the device."""
+        return _evaluate(self, relevant_docs, self.depth if depth is None else depth, queries_per_pass)

@@ -13,6 +13,8 @@ ignored; a missing model directory or corpus file is an error).
                                                       [--boost PID[=W]]... [--boost-weight W] [--only-boosted]
                                                       [--product-sets FILE --within NAME]...
                                                       [--max-per-aisle N] [--max-per-department N]
+                                                      [--cf-data-dir DIR --cf-processed-dir DIR --history PID...
+                                                       [--cf-weight W] [--rrf-c C]]
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
 and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
@@ -20,6 +22,7 @@ processed_dir, data_dir, model_name, content_only, cf_only).
 
     python -m instacart_next_order_recommendation_amd baselines --config configs/baselines.yaml [--cf-only]
                                                                 [--reorder-boost W]
+                                                                [--hybrid [--cf-weight W] [--rrf-c C]]
 """
 from __future__ import annotations
 
@@ -84,6 +87,11 @@ def baselines_main(argv) -> int:
     ap.add_argument("--reorder-boost", type=float, default=None, metavar="W",
                     help="a third block: the content-based ranking with W added to the scores of the products of the "
                          "user's earlier orders (the histories the CF baseline reads)")
+    ap.add_argument("--hybrid", action="store_true",
+                    help="a further block: the content-based and the CF ranking fused by position on the GPU (reciprocal "
+                         "rank fusion); needs both baselines")
+    ap.add_argument("--cf-weight", type=float, default=1.0, metavar="W", help="--hybrid: the weight of the CF list (default 1)")
+    ap.add_argument("--rrf-c", type=float, default=60.0, metavar="C", help="--hybrid: the constant of 1 / (C + rank) (default 60)")
     args = ap.parse_args(argv)
     path = args.config or (Path("configs/baselines.yaml") if Path("configs/baselines.yaml").exists() else None)
     raw = (yaml.safe_load(Path(path).read_text()) or {}) if path else {}
@@ -92,12 +100,16 @@ def baselines_main(argv) -> int:
     data_dir = Path(args.data_dir or str(cfg["data_dir"]))
     model_name = Path(args.model_name or str(cfg["model_name"]))
     content_only, cf_only = args.content_only or bool(cfg["content_only"]), args.cf_only or bool(cfg["cf_only"])
+    if args.hybrid and (content_only or cf_only):
+        raise SystemExit("--hybrid fuses the two baselines: it cannot be combined with --content-only or --cf-only")
+    if args.hybrid and not (args.cf_weight >= 0.0 and -1.0 < args.rrf_c < float("inf")):
+        raise SystemExit("--cf-weight takes a weight >= 0 and --rrf-c a finite constant > -1")
     if not (processed_dir / "eval_queries.json").exists():
         raise SystemExit(f"{processed_dir} holds no eval_queries.json (this build never downloads one)")
     if args.reorder_boost is not None and (cf_only or not args.reorder_boost >= 0.0):
         raise SystemExit("--reorder-boost takes a weight >= 0 and needs the content-based baseline (not --cf-only)")
 
-    from .baselines import ContentBasedBaseline, ItemItemCFBaseline
+    from .baselines import ContentBasedBaseline, HybridBaseline, ItemItemCFBaseline
     from .ir_metrics import load_eval_data
 
     eval_queries, eval_corpus, relevant = load_eval_data(processed_dir)
@@ -114,6 +126,9 @@ def baselines_main(argv) -> int:
         histories = cf.eval_order_to_history if not content_only else ItemItemCFBaseline.load_arrays(data_dir, processed_dir)["histories"]
         print_metrics(f"Content-based + reorder boost ({args.reorder_boost:g})",
                       cb.evaluate(relevant, boosts=histories, boost_weight=args.reorder_boost))
+    if args.hybrid:
+        hybrid = HybridBaseline(cb, cf, cf_weight=args.cf_weight, rrf_c=args.rrf_c)
+        print_metrics(f"Hybrid (rank fusion, cf weight {args.cf_weight:g}, c {args.rrf_c:g})", hybrid.evaluate(relevant))
     return 0
 
 
@@ -166,7 +181,35 @@ def build_parser() -> argparse.ArgumentParser:
                     help="at most N results of one aisle (the best N of it, in the ranking's order)")
     ap.add_argument("--max-per-department", type=int, default=None, metavar="N",
                     help="at most N results of one department")
+    ap.add_argument("--cf-data-dir", type=Path, default=None, metavar="DIR",
+                    help="with --cf-processed-dir: build the item-item CF baseline from DIR's orders.csv and "
+                         "order_products__prior.csv, for --history")
+    ap.add_argument("--cf-processed-dir", type=Path, default=None, metavar="DIR",
+                    help="the processed directory of the CF baseline; its eval_corpus.json must list the corpus' products")
+    ap.add_argument("--history", action="append", default=None, metavar="PID",
+                    help="a product of the user's earlier orders (repeatable): the results are the content ranking fused "
+                         "with the CF ranking of these products; the scores are then fused scores")
+    ap.add_argument("--cf-weight", type=float, default=1.0, metavar="W", help="the weight of the CF list in the fusion (default 1)")
+    ap.add_argument("--rrf-c", type=float, default=60.0, metavar="C", help="the constant of 1 / (C + rank) in the fusion (default 60)")
     return ap
+
+
+def fusion_args(args) -> bool:
+    """The --cf-* / --history arguments checked against each other and the rest: the two directories go together,
+    --history needs them, and a fused request takes --top-k and --candidates only.  -> whether a CF baseline is built."""
+    if (args.cf_data_dir is None) != (args.cf_processed_dir is None):
+        raise SystemExit("--cf-data-dir and --cf-processed-dir go together")
+    if args.history and args.cf_data_dir is None:
+        raise SystemExit("--history needs --cf-data-dir and --cf-processed-dir")
+    if args.history:
+        for flag, given in (("--aisle", args.aisle), ("--department", args.department), ("--diversity", args.diversity),
+                            ("--probes", args.probes), ("--boost", args.boost), ("--only-boosted", args.only_boosted),
+                            ("--within", args.within), ("--max-per-aisle", args.max_per_aisle),
+                            ("--max-per-department", args.max_per_department)):
+            if given:
+                raise SystemExit(f"--history cannot be combined with {flag}: the CF list is the best of the whole catalog "
+                                 "and knows none of these constraints")
+    return args.cf_data_dir is not None
 
 
 def ann_args(args) -> tuple[int | None, int | None]:
@@ -185,6 +228,7 @@ def main(argv=None) -> int:
         return baselines_main(argv[1:])
     args = build_parser().parse_args(argv)
     ann_lists, probes = ann_args(args)
+    with_cf = fusion_args(args)
     if args.within and args.product_sets is None:
         raise SystemExit("--within needs --product-sets")
     if args.product_sets is not None and not args.product_sets.exists():
@@ -209,13 +253,22 @@ def main(argv=None) -> int:
         product_sets = load_product_sets(args.product_sets) if args.product_sets is not None else None
     except ValueError as e:  # (a file that is not JSON raises json.JSONDecodeError, a ValueError too)
         raise SystemExit(f"--product-sets {args.product_sets}: {e}")
-    rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"],
-                      ann_lists=ann_lists, product_sets=product_sets)
+    cf = None
+    if with_cf:
+        from .baselines import ItemItemCFBaseline
+
+        cf = ItemItemCFBaseline(args.cf_data_dir, args.cf_processed_dir)
+    try:
+        rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"],
+                          ann_lists=ann_lists, product_sets=product_sets, cf=cf)
+    except ValueError as e:  # the CF baseline's corpus is not the catalog
+        raise SystemExit(str(e))
     try:
         hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department,
                              diversity=args.diversity, candidates=args.candidates, boosts=boosts or None,
                              only_boosted=args.only_boosted, probes=probes, within=args.within,
-                             max_per_aisle=args.max_per_aisle, max_per_department=args.max_per_department)
+                             max_per_aisle=args.max_per_aisle, max_per_department=args.max_per_department,
+                             history=args.history, cf_weight=args.cf_weight, rrf_c=args.rrf_c)
     except ValueError as e:  # an aisle / department / product set the catalog does not have, a bad --diversity / --candidates / --boost / --probes / --max-per-*
         raise SystemExit(str(e))
     if args.json:

@@ -29,7 +29,8 @@ import torch
 from . import _native
 from .encoder import DeviceEncoder
 from .model_io import LoadedModel, load_model_dir
-from .search import DeviceIndex, IvfIndex, apply_moves, facet_masks, rowset_bits, rowset_ids, train_centroids
+from .search import (DeviceIndex, IvfIndex, apply_moves, facet_masks, fuse_select, rowset_bits, rowset_ids, rrf_weights,
+                     train_centroids)
 
 logger = logging.getLogger(__name__)
 
@@ -407,6 +408,55 @@ def ann_plan(probes, n_lists, *, aisles=None, departments=None, boosts=None, onl
     return int(probes)
 
 
+def fusion_plan(history, cf_weight, rrf_c, has_cf: bool, n_queries: int, top_k: int, candidates, n_products: int, *,
+                aisles=None, departments=None, within=None, boosts=None, only_boosted: bool = False, diversity=None,
+                probes=None, max_per_aisle=None, max_per_department=None):
+    """A batch's `history` / `cf_weight` / `rrf_c` arguments (history: None or one entry per query, each None or an
+    iterable of product ids), checked before any GPU work -> None (the plain path: history is None, or every entry
+    is) or (per-query id lists, cf_weight, rrf_c, the width of both lists).  In a batch that fuses, a None entry
+    counts as [].  The width is `candidates`, default min(ICREC_MAX_K, 4 * top_k), clipped to the catalog, never below
+    top_k's own clipped width.  ValueError: history on a recommender without cf, a string for a history, a count
+    mismatch, cf_weight not a number >= 0, rrf_c not finite or <= -1, history together with aisles, departments,
+    within, boosts / only_boosted, diversity, probes, max_per_aisle or max_per_department."""
+    if history is None:
+        return None
+    if isinstance(history, (str, bytes)) or hasattr(history, "items"):
+        raise ValueError("history of a batch is a sequence with one entry per query")
+    history = list(history)
+    if len(history) != n_queries:
+        raise ValueError(f"history has {len(history)} entries for {n_queries} queries")
+    if any(isinstance(h, (str, bytes)) or hasattr(h, "items") for h in history):
+        raise ValueError("history must be an iterable of product ids, not a string or a mapping")
+    if all(h is None for h in history):
+        return None
+    if not has_cf:
+        raise ValueError("history needs a recommender built with cf (an ItemItemCFBaseline over the same products)")
+    for what, given in (("aisles", aisles is not None), ("departments", departments is not None),
+                        ("within", within is not None), ("boosts", boosts is not None or bool(only_boosted)),
+                        ("diversity", diversity is not None and float(diversity) != 0.0), ("probes", probes is not None),
+                        ("max_per_aisle", max_per_aisle is not None),
+                        ("max_per_department", max_per_department is not None)):
+        if given:
+            raise ValueError(f"history cannot be combined with {what}: the CF list is the best of the WHOLE catalog and "
+                             "knows no facets, product sets, boosts, caps or IVF lists; it takes exclude_product_ids and "
+                             "candidates only")
+
+    def number(v):
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            return float("nan")
+
+    if not 0.0 <= number(cf_weight):  # (a NaN fails the comparison); rrf_weights' own rules, under this call's names
+        raise ValueError(f"cf_weight must be a number >= 0, got {cf_weight!r}")
+    if not -1.0 < number(rrf_c) < float("inf"):
+        raise ValueError(f"rrf_c must be finite and > -1, got {rrf_c!r}")
+    top_k = max(int(top_k), 1)
+    n = int(candidates) if candidates is not None else min(_native.ICREC_MAX_K, 4 * top_k)
+    width = max(min(n, n_products), min(top_k, n_products))
+    return [[str(p) for p in (h or ())] for h in history], float(cf_weight), float(rrf_c), width
+
+
 @dataclass(frozen=True)
 class RequestPlan:
     """What a request asks beyond (queries, top_k, exclusions), checked (Recommender._plan); None / False: not asked."""
@@ -419,11 +469,12 @@ class RequestPlan:
     mmr: Optional[tuple] = None  # (lambda, candidates): diversity_plan
     probes: Optional[int] = None  # the lists of the IVF index to scan: ann_plan
     width: Optional[int] = None  # the request's raw `candidates`: what DeviceIndex.search_capped searches per round
+    fuse: Optional[tuple] = None  # (per-query history ids, cf_weight, rrf_c, the width of both lists): fusion_plan
 
     @property
     def plain(self) -> bool:
         """Nothing asked: the search is `DeviceIndex.search(q, k, exclude)`, which the graph path may serve."""
-        return (self.allow, self.sets, self.boost, self.caps, self.mmr, self.probes) == (None,) * 6
+        return (self.allow, self.sets, self.boost, self.caps, self.mmr, self.probes, self.fuse) == (None,) * 7
 
 
 PLAIN = RequestPlan()  # what Recommender._plan returns for every request that asks nothing
@@ -486,14 +537,16 @@ class Recommender:
     _emb_block: Optional[np.ndarray] = None  # add_products / remove_products: the block product_embeddings is a view of
     aisles: Optional[list[str]] = None  # the catalog's aisle and department names (_set_facets); None: it has no facets
     departments: Optional[list[str]] = None
+    _cf = None  # the ItemItemCFBaseline over the same products (cf=), ranked by requests that pass `history`
 
     def __init__(self, model_dir: Path | str, corpus_path: Path, batch_size: int = 64, use_index: bool = True,
-                 ann_lists: int | None = None, product_sets=None):
+                 ann_lists: int | None = None, product_sets=None, cf=None):
         self.model_dir = self._resolve_model_dir(model_dir)
         self.corpus_path = Path(corpus_path).resolve()
         self.product_ids, self.product_texts = self._load_corpus()
         self.pid_to_text = dict(zip(self.product_ids, self.product_texts))
         self._pid_to_row = {pid: i for i, pid in enumerate(self.product_ids)}
+        self._set_cf(cf)
         self.device = self._inference_device()
         self.model = self._load_model()
         self.product_embeddings = self._load_or_build_embeddings(batch_size, use_index)
@@ -562,6 +615,14 @@ class Recommender:
         self.aisles, self.departments = (parsed[0], parsed[1]) if parsed else (None, None)
         if parsed:
             self._index.set_facets(parsed[2])
+
+    def _set_cf(self, cf) -> None:
+        """cf: an ItemItemCFBaseline whose candidates are numbered like the catalog rows - cf.corpus_ids equal to
+        product_ids, the same ids in the same order - or None.  ValueError otherwise, before the model is loaded."""
+        if cf is not None and list(cf.corpus_ids) != list(self.product_ids):
+            raise ValueError("cf.corpus_ids must be the catalog's product_ids, the same ids in the same order: the CF "
+                             "candidates are numbered like the catalog rows")
+        self._cf = cf
 
     def _member_row(self, product_ids) -> np.ndarray:
         """bool [n_products]: which catalog rows the given product ids name; ids the catalog does not have are skipped."""
@@ -692,7 +753,11 @@ class Recommender:
         sets); aisle and department names stay, also those no product carries any more.  The captured single-request
         graphs are dropped, the IVF index is built again from its centroids.
         ValueError, with nothing changed: an id the catalog does not have, an id named twice, a list that names every
-        product (product_remove_plan).  An empty list does nothing.  The limits are add_products'."""
+        product (product_remove_plan), a recommender built with cf (the removal renumbers rows, and the CF handle
+        cannot follow).  An empty list does nothing.  The limits are add_products'."""
+        if self._cf is not None:
+            raise ValueError("remove_products renumbers catalog rows, which the cf baseline of this recommender cannot "
+                             "follow: build the recommender again")
         rows = product_remove_plan(product_ids, self._pid_to_row)
         if not rows:
             return
@@ -760,11 +825,11 @@ class Recommender:
 
     def _plan(self, n_queries: int, top_k: int, *, aisles=None, departments=None, diversity=None, candidates=None,
               boosts=None, boost_weight=None, only_boosted=False, probes=None, within=None, max_per_aisle=None,
-              max_per_department=None) -> RequestPlan:
+              max_per_department=None, history=None, cf_weight=1.0, rrf_c=60.0) -> RequestPlan:
         """A request's options in recommend_batch's form (aisles, departments, boosts and within: None or one entry per
         query), checked before any GPU work -> its RequestPlan; the one caller of the *_plan functions, in the order ann,
-        caps, within, diversity, facets, boosts.  Boosted rows outside a query's product sets are dropped here.  A request
-        that asks nothing gets the shared PLAIN (`candidates` alone asks nothing: it is only a width)."""
+        caps, within, diversity, facets, boosts, fusion.  Boosted rows outside a query's product sets are dropped here.
+        A request that asks nothing gets the shared PLAIN (`candidates` alone asks nothing: it is only a width)."""
         if probes is not None:  # (n_lists is a library call: made for the requests that probe)
             probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
                               boosts=boosts, only_boosted=only_boosted, within=within, max_per_aisle=max_per_aisle,
@@ -774,11 +839,17 @@ class Recommender:
         mmr = diversity_plan(diversity, candidates, top_k, len(self.product_ids))
         allow = self._facet_allow(aisles, departments, n_queries)
         boost, only = boost_plan(boosts, boost_weight, only_boosted, n_queries, self._pid_to_row) or (None, False)
-        if (allow, sets, boost, caps, mmr, probes) == (None,) * 6:
+        fuse = None
+        if history is not None:
+            fuse = fusion_plan(history, cf_weight, rrf_c, self._cf is not None, n_queries, top_k, candidates,
+                               len(self.product_ids), aisles=aisles, departments=departments, within=within, boosts=boosts,
+                               only_boosted=only_boosted, diversity=diversity, probes=probes, max_per_aisle=max_per_aisle,
+                               max_per_department=max_per_department)
+        if (allow, sets, boost, caps, mmr, probes, fuse) == (None,) * 7:
             return PLAIN
         if boost is not None and sets is not None:
             boost = boosts_within(boost, sets, self._set_member)
-        return RequestPlan(allow, sets, boost, only, caps, mmr, probes, candidates)  # (the fields' order; keywords cost 0.3 us)
+        return RequestPlan(allow, sets, boost, only, caps, mmr, probes, candidates, fuse)  # (the fields' order; keywords cost 0.3 us)
 
     def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, plan: RequestPlan, timed: bool = False):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
@@ -789,7 +860,10 @@ class Recommender:
         3. with plan.mmr = (lambda, candidates), w = candidates and DeviceIndex.mmr_select re-selects the k results
            from the exact index's rows; without it w = k.
         The exception is caps without mmr: the k results are the capped walk of the WHOLE source ranking, which
-        DeviceIndex.search_capped takes in rounds of plan.width candidates (None: its default)."""
+        DeviceIndex.search_capped takes in rounds of plan.width candidates (None: its default).
+        With plan.fuse the fused list is a fourth kind of source ranking, and the only step (fusion_plan refuses the
+        rest): the content search w wide under the exclusions, icrec_cf_rank w wide on the histories, and fuse_select
+        with the same exclusions to k (_fused)."""
         n = len(cu) - 1
         sets = None if plan.sets is None else rowset_ids(plan.sets, n, None, self.device)
         allow = None if plan.allow is None else facet_masks(plan.allow, n, self._index.n_facets, self.device)
@@ -800,7 +874,9 @@ class Recommender:
         emb = self.model.encoder.encode_packed_host(ids, cu)
         if ev:
             ev[1].record(stream)
-        if plan.caps is not None and plan.mmr is None:
+        if plan.fuse is not None:
+            idx, sc = self._fused(emb, k, ex, plan.fuse)
+        elif plan.caps is not None and plan.mmr is None:
             idx, sc = self._index.search_capped(emb, k, plan.caps, plan.width, ex, allow, sets, plan.boost,
                                                 only=plan.only_boosted)
         else:
@@ -818,12 +894,35 @@ class Recommender:
         idx, sc = idx.cpu().numpy(), sc.cpu().numpy()  # synchronises the stream
         return (idx, sc, ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])) if ev else (idx, sc)
 
+    #: the CF workspace one pass of _cf_ranked may allocate, and icrec_cf_rank's own limit on the queries of a call
+    CF_PASS_BYTES, CF_PASS_QUERIES = 1 << 30, 65535
+
+    def _cf_ranked(self, histories, w: int):
+        """(rows int64 [n, w], scores int32 [n, w]) of icrec_cf_rank on per-query product-id lists, in passes of at
+        most CF_PASS_QUERIES queries whose workspace (icrec_cf_rank_workspace_bytes) stays under CF_PASS_BYTES."""
+        n = len(histories)
+        step = min(n, self.CF_PASS_QUERIES)
+        while step > 1 and self._cf.rank_workspace_bytes(step, w) >= self.CF_PASS_BYTES:
+            step = (step + 1) // 2
+        parts = [self._cf.rank_rows_scores(self._cf.history_csr_from(histories[s:s + step]), w) for s in range(0, n, step)]
+        return (parts[0] if len(parts) == 1 else tuple(torch.cat(t) for t in zip(*parts)))
+
+    def _fused(self, emb: torch.Tensor, k: int, ex, fuse):
+        """The fused source ranking of plan.fuse = (histories, cf_weight, rrf_c, w): (idx, fused scores) [n, k].  Rows
+        that add_products appended lie beyond the CF candidates: CF never lists them, the content list may."""
+        histories, cf_weight, rrf_c, w = fuse
+        a_idx, _ = self._index.search(emb, w, ex)
+        b_idx, b_sc = self._cf_ranked(histories, w)
+        a_w = torch.from_numpy(rrf_weights(w, rrf_c, 1.0)).to(self.device)
+        b_w = torch.from_numpy(rrf_weights(w, rrf_c, cf_weight)).to(self.device)
+        return fuse_select(a_idx, b_idx, a_w, b_w, k, len(self.product_ids), b_gate=b_sc, exclude=ex)
+
     def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, **options):
         """One request (options: recommend's keywords): a replayed hipGraph (fastpath.py) when its plan is plain - no
-        aisles, departments, product sets, diversity, boosts, probes or caps - and a graph supports it, else the
+        aisles, departments, product sets, diversity, boosts, probes, caps or history - and a graph supports it, else the
         un-captured path.  -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
-        for name in ("aisles", "departments", "within", "boosts"):  # the per-query options, in the batch's form
+        for name in ("aisles", "departments", "within", "boosts", "history"):  # the per-query options, in the batch's form
             if options.get(name) is not None:
                 options[name] = [options[name]]
         plan = self._plan(1, top_k, **options)
@@ -851,16 +950,20 @@ class Recommender:
                         diversity: float | None = None, candidates: int | None = None, boosts=None,
                         boost_weight: float | None = None, only_boosted: bool = False, probes: int | None = None,
                         within=None, max_per_aisle: int | None = None,
-                        max_per_department: int | None = None) -> list[list[tuple[str, float]]]:
+                        max_per_department: int | None = None, history=None, cf_weight: float = 1.0,
+                        rrf_c: float = 60.0) -> list[list[tuple[str, float]]]:
         """Many contexts in one GPU pass; element i equals recommend(queries[i], ...).  aisles / departments: per
         query None or the admitted names, as recommend takes them.  diversity / candidates: one value for the whole
         batch, as recommend takes them.  boosts: None or one entry per query, each as recommend takes it; boost_weight
         and only_boosted: one value for the whole batch.  probes: one value for the whole batch, as recommend takes it.
         within: None or one entry per query, each None or as recommend takes it.  max_per_aisle / max_per_department: one
-        value for the whole batch, as recommend takes them."""
+        value for the whole batch, as recommend takes them.  history: None or one entry per query, each None or as
+        recommend takes it (in a batch that fuses, a None entry counts as []); cf_weight and rrf_c: one value for the
+        whole batch."""
         plan = self._plan(len(queries), top_k, aisles=aisles, departments=departments, diversity=diversity,
                           candidates=candidates, boosts=boosts, boost_weight=boost_weight, only_boosted=only_boosted,
-                          probes=probes, within=within, max_per_aisle=max_per_aisle, max_per_department=max_per_department)
+                          probes=probes, within=within, max_per_aisle=max_per_aisle, max_per_department=max_per_department,
+                          history=history, cf_weight=cf_weight, rrf_c=rrf_c)
         if not queries:
             return []
         k = self._k(top_k)
@@ -885,14 +988,17 @@ class Recommender:
     def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None, *, aisles=None,
                               departments=None, diversity: float | None = None, candidates: int | None = None,
                               boosts=None, boost_weight: float | None = None, only_boosted: bool = False, within=None,
-                              max_per_aisle: int | None = None, max_per_department: int | None = None):
+                              max_per_aisle: int | None = None, max_per_department: int | None = None, history=None,
+                              cf_weight: float = 1.0, rrf_c: float = 60.0):
         """recommend_batch plus (embedding ms incl. host tokenisation, similarity ms) from HIP events
         on the launch stream — what the micro-batching server reports as per-request stats.  A diversified batch's
-        re-selection, a boosted batch's merge and a capped batch's rounds count into the similarity time."""
+        re-selection, a boosted batch's merge, a capped batch's rounds and a fused batch's CF ranking and fusion count into
+        the similarity time."""
         k = self._k(top_k)
         plan = self._plan(len(queries), top_k, aisles=aisles, departments=departments, diversity=diversity,
                           candidates=candidates, boosts=boosts, boost_weight=boost_weight, only_boosted=only_boosted,
-                          within=within, max_per_aisle=max_per_aisle, max_per_department=max_per_department)
+                          within=within, max_per_aisle=max_per_aisle, max_per_department=max_per_department,
+                          history=history, cf_weight=cf_weight, rrf_c=rrf_c)
         ex = self._exclusion_rows(exclude_product_ids)
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed(list(queries))
@@ -905,7 +1011,8 @@ class Recommender:
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
                   only_boosted: bool = False, probes: int | None = None, within=None, max_per_aisle: int | None = None,
-                  max_per_department: int | None = None) -> list[tuple[str, float]]:
+                  max_per_department: int | None = None, history=None, cf_weight: float = 1.0,
+                  rrf_c: float = 60.0) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
         One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0".
         aisles / departments (keyword-only; names from .aisles / .departments): only products of one of these aisles
@@ -952,11 +1059,26 @@ class Recommender:
         that is walked is then the boosted one.  With diversity the caps thin the `candidates`-wide list in one round
         and the re-selection picks from what is left, so the result keeps the caps.  Such a request takes the
         un-captured path; both None is the plain request: the same launches, the same results.  A value that is not an
-        integer >= 1, caps on a catalog without facets or together with probes raise ValueError before any GPU work."""
+        integer >= 1, caps on a catalog without facets or together with probes raise ValueError before any GPU work.
+        history (keyword-only; a recommender built with cf=): the products of the user's earlier orders, an iterable
+        of product ids.  The content search and the item-item CF ranking of the history (icrec_cf_rank) both run
+        `candidates` wide (default min(128, 4 * top_k), clipped to the catalog) and are fused by POSITION on the GPU
+        (reciprocal rank fusion, icrec_fuse_select): a product's fused score is 1 / (rrf_c + its content position + 1)
+        + cf_weight / (rrf_c + its CF position + 1), positions counted from 0 and a list that does not hold the
+        product adding 0.  The returned scores are these fused scores, not cosines.  A CF candidate that co-occurs with
+        nothing in the history does not vote.  CF never lists a product of the history itself (the reference's rule),
+        the content list may: pass them as exclude_product_ids to drop them.  history=None is the plain request: the
+        same launches, the same results.  history=[], or ids the CF baskets do not know, takes the fused path with a
+        dead CF list: the content order, with fused scores.  It composes with exclude_product_ids and candidates only:
+        together with aisles, departments, within, boosts / only_boosted, diversity, probes, max_per_aisle or
+        max_per_department it raises ValueError before any GPU work (a CF list is the best of the whole catalog and
+        knows none of these constraints), as do history on a recommender without cf, cf_weight not a number >= 0 and
+        rrf_c not finite or <= -1.  Such a request takes the un-captured path."""
         return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments,
                                    diversity=diversity, candidates=candidates, boosts=boosts, boost_weight=boost_weight,
                                    only_boosted=only_boosted, probes=probes, within=within, max_per_aisle=max_per_aisle,
-                                   max_per_department=max_per_department)
+                                   max_per_department=max_per_department, history=history, cf_weight=cf_weight,
+                                   rrf_c=rrf_c)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -981,7 +1103,8 @@ class MonitoredRecommender(Recommender):
                   departments: Optional[Sequence[str]] = None, diversity: float | None = None,
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
                   only_boosted: bool = False, probes: int | None = None, within=None, max_per_aisle: int | None = None,
-                  max_per_department: int | None = None) -> list[tuple[str, float]]:
+                  max_per_department: int | None = None, history=None, cf_weight: float = 1.0,
+                  rrf_c: float = 60.0) -> list[tuple[str, float]]:
         """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
         replays (fastpath.py): the three timing fields keep their meaning there.  A diversified request's
         re-selection and a boosted request's merge count into the similarity time."""
@@ -991,7 +1114,8 @@ class MonitoredRecommender(Recommender):
                                                          candidates=candidates, boosts=boosts, boost_weight=boost_weight,
                                                          only_boosted=only_boosted, probes=probes, within=within,
                                                          max_per_aisle=max_per_aisle,
-                                                         max_per_department=max_per_department)
+                                                         max_per_department=max_per_department, history=history,
+                                                         cf_weight=cf_weight, rrf_c=rrf_c)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

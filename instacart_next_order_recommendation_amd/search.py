@@ -909,6 +909,86 @@ def train_centroids(index: DeviceIndex, n_lists: int, iters: int = 10, sample: i
     return cent.contiguous()
 
 
+def rrf_weights(depth: int, c: float = 60.0, weight: float = 1.0) -> np.ndarray:
+    """The position table of reciprocal rank fusion, float32 [depth]: t[j] = float32(weight / (c + j + 1)), computed
+    in float64 and rounded once.  ValueError: depth outside [1, ICREC_MAX_K], c not finite or <= -1 (a position's
+    denominator must be positive), weight not a number >= 0."""
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= int(depth) <= _native.ICREC_MAX_K:
+        raise ValueError(f"depth must be an integer in [1, {_native.ICREC_MAX_K}], got {depth!r}")
+    def number(v):
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            return float("nan")
+
+    c64, w64 = number(c), number(weight)
+    if not (np.isfinite(c64) and c64 > -1.0):
+        raise ValueError(f"c must be finite and > -1, got {c!r}")
+    if not 0.0 <= w64:  # (a NaN fails the comparison)
+        raise ValueError(f"weight must be a number >= 0, got {weight!r}")
+    with np.errstate(over="ignore"):
+        return (np.float64(w64) / (np.float64(c64) + np.arange(1, int(depth) + 1, dtype=np.float64))).astype(np.float32)
+
+
+def _fuse_list(idx: torch.Tensor, gate, w, name: str, device, Q=None):
+    """One list of fuse_select, checked: idx int64 [Q, k], gate None or int32 [Q, k], w float32 [k] (a tensor, or
+    anything numpy converts) -> the three, contiguous on `device`."""
+    if idx.dim() != 2 or idx.dtype != torch.int64 or not 1 <= idx.shape[1] <= _native.ICREC_MAX_K \
+            or (Q is not None and idx.shape[0] != Q):
+        raise ValueError(f"{name}_idx must be int64 [{'Q' if Q is None else Q}, 1..{_native.ICREC_MAX_K}], got {idx.dtype} "
+                         f"{tuple(idx.shape)}")
+    if gate is not None and (gate.dtype != torch.int32 or gate.shape != idx.shape):
+        raise ValueError(f"{name}_gate must be int32 {tuple(idx.shape)}, got {gate.dtype} {tuple(gate.shape)}")
+    if not isinstance(w, torch.Tensor):
+        w = torch.from_numpy(np.ascontiguousarray(w, np.float32))
+    if w.dtype != torch.float32 or tuple(w.shape) != (idx.shape[1],):
+        raise ValueError(f"{name}_w must be float32 [{idx.shape[1]}], got {w.dtype} {tuple(w.shape)}")
+    return idx.to(device).contiguous(), None if gate is None else gate.to(device).contiguous(), w.to(device).contiguous()
+
+
+def fuse_select(a_idx: torch.Tensor, b_idx: torch.Tensor, a_w, b_w, top_k: int, n_ids: int,
+                a_gate: Optional[torch.Tensor] = None, b_gate: Optional[torch.Tensor] = None,
+                exclude: Optional[Sequence[Iterable[int]]] = None, positions: bool = False):
+    """Weighted rank fusion of two ranked id lists (icrec_fuse_select): a_idx int64 [Q, ka] and b_idx int64 [Q, kb]
+    device tensors as `DeviceIndex.search` and icrec_cf_rank return them (best first, negative = pad), a_w [ka] and
+    b_w [kb] the weight of each position (rrf_weights builds them), gates int32 like the lists (an entry counts where
+    its gate is > 0; icrec_cf_rank's scores) or None, exclude per-query ids as `search` takes them
+    -> (idx int64 [Q, top_k] with -1 pads, fused score float32 [Q, top_k]) on a_idx's device, ordered by
+    e_a(position in A) + e_b(position in B) descending, lower id first on ties; with positions=True also
+    pos int32 [Q, top_k, 2], each result's positions in A and B (-1: not in that list)."""
+    device = _native.hip_device(a_idx.device, "fuse_select")
+    a_idx, a_gate, a_w = _fuse_list(a_idx, a_gate, a_w, "a", device)
+    Q = int(a_idx.shape[0])
+    b_idx, b_gate, b_w = _fuse_list(b_idx, b_gate, b_w, "b", device, Q)
+    ei, eo = exclusion_csr(exclude, Q, device)
+    out_idx, out_sc = _out_pair(Q, top_k, device)
+    pos = torch.empty((Q, top_k, 2), dtype=torch.int32, device=device) if positions else None
+    fuse_select_into(a_idx, b_idx, a_w, b_w, top_k, n_ids, out_idx, out_sc, a_gate, b_gate, ei, eo, pos)
+    return (out_idx, out_sc, pos) if positions else (out_idx, out_sc)
+
+
+def fuse_select_into(a_idx: torch.Tensor, b_idx: torch.Tensor, a_w: torch.Tensor, b_w: torch.Tensor, top_k: int, n_ids: int,
+                     out_idx: torch.Tensor, out_score: torch.Tensor, a_gate: Optional[torch.Tensor] = None,
+                     b_gate: Optional[torch.Tensor] = None, excl_idx: Optional[torch.Tensor] = None,
+                     excl_off: Optional[torch.Tensor] = None, out_pos: Optional[torch.Tensor] = None) -> None:
+    """Allocation-free form of `fuse_select` on caller-owned contiguous device buffers (hipGraph-capturable; there is
+    no workspace): the lists, gates and tables as `fuse_select` describes them, the exclusions as the device CSR
+    exclusion_csr builds, out_idx int64 [Q, top_k], out_score float32 [Q, top_k], out_pos int32 [Q, top_k, 2] or None.
+    The kernel reads gates, tables and exclusions when it runs."""
+    Q = int(a_idx.shape[0])
+    for name, t, dtype, shape in (("a_idx", a_idx, torch.int64, (Q, a_idx.shape[1])), ("b_idx", b_idx, torch.int64, (Q, b_idx.shape[1])),
+                                  ("a_gate", a_gate, torch.int32, tuple(a_idx.shape)), ("b_gate", b_gate, torch.int32, tuple(b_idx.shape)),
+                                  ("a_w", a_w, torch.float32, (a_idx.shape[1],)), ("b_w", b_w, torch.float32, (b_idx.shape[1],)),
+                                  ("out_idx", out_idx, torch.int64, (Q, top_k)), ("out_score", out_score, torch.float32, (Q, top_k)),
+                                  ("out_pos", out_pos, torch.int32, (Q, top_k, 2))):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+                              or t.device != a_idx.device):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor {tuple(shape)} on {a_idx.device}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    _native.fuse_select(a_idx, a_gate, a_w, b_idx, b_gate, b_w, n_ids, excl_idx, excl_off, top_k, out_idx, out_score, out_pos,
+                        a_idx.device)
+
+
 def merge_topk(keys: torch.Tensor, k: int):
     """Merge sorted partial key lists [n_lists, Q, k] (int64-viewed uint64) into (idx, score) [Q,k]."""
     if keys.dim() != 3 or keys.shape[2] != k:
