@@ -44,7 +44,8 @@ static TimingSlot g_slots[T_NSLOTS];
 
 bool timing_on() { return g_timing; }
 
-ScopedTimer::ScopedTimer(int slot_, hipStream_t s) : slot(slot_), stream(s) {
+void ScopedTimer::start(hipStream_t s) {
+    stream = s;
     if (!g_timing) return;
     if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
     hipEventRecord(a, stream);

@@ -50,10 +50,12 @@ enum { T_SEARCH_KERNEL = 0, T_FFN_UP = 1, T_ENCODE = 2, T_SEARCH = 3, T_SEARCH_F
 bool timing_on();
 // Records [start, stop] around a launch when timing is enabled; resolved lazily at query time.
 struct ScopedTimer {
-    ScopedTimer(int slot, hipStream_t s);
+    ScopedTimer(int slot, hipStream_t s) : slot(slot) { start(s); }
+    explicit ScopedTimer(int slot) : slot(slot) {}  // idle (nothing recorded) unless start() is called later in its scope
+    void start(hipStream_t s);
     ~ScopedTimer();
     int slot;
-    hipStream_t stream;
+    hipStream_t stream = nullptr;
     hipEvent_t a = nullptr, b = nullptr;
 };
 

@@ -1,6 +1,11 @@
-// encoder.hip — the SentenceTransformer forward on gfx950: BertModel (6 post-LN layers),
-// masked mean pooling, L2 normalisation; token-packed (varlen), fp32 throughout, every GEMM
-// and both attention products on v_mfma_f32_32x32x2_f32.
+// encoder.hip — the encoder handle and its forward pass on gfx950: a post-LN BertModel of hidden 384 (32-dim heads) or
+// 768 (64-dim heads) over token-packed (varlen) batches, in exact fp32 or in f16x3 arithmetic (gemm_mode), then mean or
+// CLS pooling with L2 normalisation (icrec_encode_ex) or the pair score head (icrec_score_pairs).
+// Here: the embedding, LayerNorm, fp32 GEMM, pooling, token-output, CLS-gather and score-head kernels; `Encoder`, its
+// creation and setters; the workspace layout; the per-layer schedule of both arithmetics (encode_x3, encode_f32) and the
+// one forward path (forward) behind the two public entries.  The f16x3 layer kernels are encoder_x3.h's.  Attention -
+// its kernels, length buckets, launch order and stream split - is attention.hip's: this file fills an AttentionArgs per
+// call and calls run_attention once per layer (attention.h).
 //
 // Replaces the device work of SentenceTransformer.encode as called at
 //   /root/reference/src/inference/serve_recommendations.py:195-200 (catalog index build)
@@ -13,7 +18,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "common.h"
+#include "attention.h"
 #include "wt_gemm.h"
 #include "encoder_x3.h"
 
@@ -147,613 +152,6 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void linear_kernel(const float* __
                     out[row * N + col] = v;
                 }
             }
-    }
-}
-
-// ---------------------------------------------------------------- attention (tf:111-136, 164-203)
-// One workgroup = one (sequence, head) and up to sixteen 32-row query blocks (one per wave), for heads of D = 32
-// (hidden 384) or D = 64 dims (hidden 768: BERT-base).
-// S^T = K.Q^T is computed with keys on the accumulator rows, so each lane ends up with the
-// scores of ONE query (column = lane & 31) against 16 keys per 32-key tile.  The softmax is
-// then lane-local plus one exchange with lane^32, and the exponentiated accumulator registers
-// are fed back unchanged as the A operand of P.V (A[i=query][k=key]): no transpose, no LDS
-// round trip.  Key order inside the P.V chain is therefore, per 32-key tile,
-//   e = 0..15: key (e&3)+8(e>>2) then key (e&3)+8(e>>2)+4
-// and the softmax denominator is the sum of the two half-wave partial sums; the oracle
-// (icrec_oracle.c, attention block) accumulates in exactly this order.  A wave's output is D / 32 tiles of 32 x 32
-// (dims 32 dt + r of the lane's column).
-//
-// One launch per length bucket: NKT = max 32-key tiles (1, 2, 4, 6, 8, 16), and as many waves; sequences of
-// nlo < nkt <= NKT key tiles belong to the launch.  A workgroup whose sequence belongs to another bucket exits at once,
-// so short sequences run with the LDS footprint / occupancy of their own bucket even in a mixed batch.
-// K and V of the (sequence, head) live in LDS; each wave's 32 query rows come straight from
-// global memory into the B-operand registers.
-//
-// Key tiles that LDS holds at once: a 32-dim head's K and V fit whole (KC = NKT); a 64-dim head's take twice the LDS, so
-// its longest bucket (9-16 tiles, up to 512 keys) is staged in chunks of 8 tiles, twice - K alone for the row maximum,
-// then K and V for the exponentials and P.V.  The per-query arithmetic depends neither on the bucket nor on the
-// chunking: a sequence gives the same bits whichever launch serves it.
-constexpr int att_kc(int D, int NKT) { return D == 64 && NKT > 8 ? 8 : NKT; }
-
-// A row's denominator from the two half-waves' partial sums: half 0's + half 1's, in both halves.
-__device__ __forceinline__ float join_halves(float v, int h) {
-    const float other = __shfl_xor(v, 32, 64);
-    return h == 0 ? v + other : other + v;
-}
-
-// Relative-position attention bias (MPNet / T5 style; icrec_encoder_set_attention_bias): the BIAS arm of both kernels
-// adds bias[head][key - query] to every scaled logit, in every layer.  The device table holds, per head, ATT_BIAS_LD
-// floats in log2 units (pre-multiplied by log2(e), like the scale): entry ICREC_MAX_SEQLEN - 1 + (key - query), the last
-// one padding.  A workgroup copies its head's row into LDS (4 KB) ahead of the first staging barrier; a lane owns one
-// query, so register e of key tile kt reads entry  att_bias_base(..) + 32 kt + (e & 3) + 8 (e >> 2)  - per tile 16 reads
-// at immediate offsets from one address, consecutive lanes on consecutive banks.  Keys and queries past the sequence
-// (clamped rows, masked / never stored) stay inside the table: both positions are below ICREC_MAX_SEQLEN.
-// The biased logit is ONE fma, scale * s + bias, and the row maximum is taken over it - whatever the bucket, the
-// chunking or the dispatch form: the same bits for a sequence alone and inside any batch.
-constexpr int ATT_BIAS_LD = 2 * ICREC_MAX_SEQLEN;
-__device__ __forceinline__ void att_bias_to_lds(float* dst, const float* __restrict__ bias, int hd, int tid, int nthreads) {
-    const f32x4* src = reinterpret_cast<const f32x4*>(bias + (size_t)hd * ATT_BIAS_LD);
-    for (int i = tid; i < ATT_BIAS_LD / 4; i += nthreads) reinterpret_cast<f32x4*>(dst)[i] = src[i];
-}
-// entry of (query qb*32 + r, key acc_row(0, lane)) of key tile 0
-__device__ __forceinline__ int att_bias_base(int qb, int lane) {
-    return ICREC_MAX_SEQLEN - 1 - (qb * 32 + (lane & 31)) + acc_row(0, lane);
-}
-
-// Exact fp32 form (gemm_mode F32): both products on v_mfma_f32_32x32x2_f32, head dims in pairs ascending.
-// Output: the fp32 context rows.
-template <int D, int NKT, bool BIAS = false>
-__global__ __launch_bounds__(NKT * 64) void attention_kernel(const float* __restrict__ qkv,
-                                                             const int32_t* __restrict__ cu, int heads, int H,
-                                                             float scale_log2e, float* __restrict__ ctx, int nlo,
-                                                             const float* __restrict__ bias) {
-    constexpr int KC = att_kc(D, NKT);
-    constexpr int LDK = D + 4;  // K LDS row stride (even/odd split layout, like the GEMM tiles)
-    // Sixteen score tiles do not fit in registers (and 64-dim heads leave room for none): each tile is then computed
-    // twice - once for the row maximum, once more for its exponentials, which the P.V product consumes at once.  Same
-    // MFMA chain both times, and the denominator and P.V accumulate in the same order as in the all-in-registers form:
-    // the same bits.
-    constexpr bool RECOMP = D == 64 || NKT > 8;
-    __shared__ __attribute__((aligned(16))) float Ks[KC * 32 * LDK];
-    __shared__ __attribute__((aligned(16))) float Vs[KC * 32 * D];
-    __shared__ float Ls[NKT * 32];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int s = blockIdx.x / heads, hd = blockIdx.x % heads;
-    const int t0 = cu[s], L = cu[s + 1] - t0;
-    const int nkt = (L + 31) >> 5;
-    if (nkt > NKT || nkt <= nlo) return;  // another bucket's sequence
-    const int ld = 3 * H;
-    const int r = lane & 31, h = lane >> 5, qb = wave;
-    const bool active = qb < nkt;  // wave-uniform; idle waves still take part in the barriers of the staging
-    const float* bt = nullptr;  // this lane's window of the head's bias row (BIAS), visible behind the staging barrier
-    if constexpr (BIAS) {
-        __shared__ __attribute__((aligned(16))) float Bs[ATT_BIAS_LD];
-        att_bias_to_lds(Bs, bias, hd, tid, NKT * 64);
-        bt = Bs + att_bias_base(qb, lane);
-    }
-    float4 qf[D / 8];  // this lane's query row -> B fragments (lane half h supplies the even / odd dims of every pair)
-    {
-        int qr = qb * 32 + r;
-        qr = qr < L ? qr : L - 1;
-        const float4* qp = reinterpret_cast<const float4*>(qkv + (size_t)(t0 + qr) * ld + hd * D);
-#pragma unroll
-        for (int kq = 0; kq < D / 8; ++kq) {
-            const float4 a = qp[2 * kq], b = qp[2 * kq + 1];
-            qf[kq] = h == 0 ? make_float4(a.x, a.z, b.x, b.z) : make_float4(a.y, a.w, b.y, b.w);
-        }
-    }
-    const bool once = KC == NKT || nkt <= KC;  // the whole sequence fits: staged once, K and V
-    // key tiles [c0, c0 + KC) -> LDS (K in the even/odd split layout, V row-major); rows past L are clamped (masked
-    // below / never stored)
-    auto stage = [&](int c0, bool with_v) {
-        if (!once) __syncthreads();  // the previous chunk's readers are done
-        const int nk = (nkt - c0 < KC ? nkt - c0 : KC) * 32;
-        for (int id = tid; id < nk * (D / 4); id += NKT * 64) {
-            const int row = id / (D / 4), c = id % (D / 4);
-            const int key = c0 * 32 + row, rr = key < L ? key : L - 1;
-            const float* src = qkv + (size_t)(t0 + rr) * ld + hd * D + c * 4;
-            const float4 kv = *reinterpret_cast<const float4*>(src + H);
-            float* kp = Ks + row * LDK + (c >> 1) * 8 + (c & 1) * 2;
-            *reinterpret_cast<float2*>(kp) = make_float2(kv.x, kv.z);
-            *reinterpret_cast<float2*>(kp + 4) = make_float2(kv.y, kv.w);
-            if (with_v) *reinterpret_cast<float4*>(Vs + row * D + c * 4) = *reinterpret_cast<const float4*>(src + 2 * H);
-        }
-        __syncthreads();
-    };
-    // scores of key tile kt (staged from c0) in log2 units (scale * log2(e) folded), tail keys at -inf:
-    // t[e] = scale_log2e * sum_d K[kt*32 + krow(e)][d] * Q[qb*32 + r][d]   (BIAS: ... + bias[krow(e) - query], one fma)
-    auto score_tile = [&](int kt, int c0) {
-        f32x16 t;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t[e] = 0.0f;
-#pragma unroll
-        for (int kq = 0; kq < D / 8; ++kq) {
-            const float4 kf = *reinterpret_cast<const float4*>(Ks + ((kt - c0) * 32 + r) * LDK + kq * 8 + h * 4);
-            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[kq].x, t, 0, 0, 0);
-            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[kq].y, t, 0, 0, 0);
-            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[kq].z, t, 0, 0, 0);
-            t = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[kq].w, t, 0, 0, 0);
-        }
-        const bool last = kt == nkt - 1;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            float v;
-            if constexpr (BIAS) v = fmaf(t[e], scale_log2e, bt[kt * 32 + (e & 3) + 8 * (e >> 2)]);
-            else v = t[e] * scale_log2e;
-            if (last && kt * 32 + acc_row(e, lane) >= L) v = -INFINITY;
-            t[e] = v;
-        }
-        return t;
-    };
-    // O += P.V for key tile kt, with P taken straight from the accumulator registers
-    f32x16 o[D / 32];
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[dt][e] = 0.0f;
-    auto pv_tile = [&](int kt, int c0, const f32x16& p) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int key = (kt - c0) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-#pragma unroll
-            for (int dt = 0; dt < D / 32; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(p[e], Vs[key * D + 32 * dt + r], o[dt], 0, 0, 0);
-        }
-    };
-    // every key tile of the sequence, chunk by chunk (one chunk when the sequence was staged whole)
-    auto for_tiles = [&](bool with_v, auto&& f) {
-#pragma unroll
-        for (int c0 = 0; c0 < NKT; c0 += KC) {
-            if (c0 < nkt) {
-                if (!once) stage(c0, with_v);
-                if (active) {
-                    const int c1 = c0 + KC < nkt ? c0 + KC : nkt;
-                    for (int kt = c0; kt < c1; ++kt) f(kt, c0);
-                }
-            }
-        }
-    };
-    if (once) stage(0, true);
-    // p = 2^(v - max); denominator = this half-wave's keys ascending, then the two halves added
-    float lsum = 0.0f;
-    if constexpr (RECOMP) {
-        float mx = -INFINITY;
-        for_tiles(false, [&](int kt, int c0) {
-            const f32x16 t = score_tile(kt, c0);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
-        });
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        for_tiles(true, [&](int kt, int c0) {
-            f32x16 t = score_tile(kt, c0);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float p = __builtin_amdgcn_exp2f(t[e] - mx);
-                t[e] = p;
-                lsum = lsum + p;
-            }
-            pv_tile(kt, c0, t);
-        });
-    } else if (active) {
-        f32x16 sc[NKT];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-            if (kt < nkt) {
-                sc[kt] = score_tile(kt, 0);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sc[kt][e]);
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-            if (kt < nkt) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float p = __builtin_amdgcn_exp2f(sc[kt][e] - mx);
-                    sc[kt][e] = p;
-                    lsum = lsum + p;
-                }
-            }
-        }
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-            if (kt < nkt) pv_tile(kt, 0, sc[kt]);
-    }
-    if (!active) return;  // (no barrier below)
-    lsum = join_halves(lsum, h);
-    if (h == 0) Ls[wave * 32 + r] = lsum;
-    // ---- normalise rows by their denominator and store (row = query, column = head dim);
-    // Ls was written by this wave's own lanes (wave-local LDS ordering makes it visible).
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int qrow = acc_row(e, lane);
-        const int tq = qb * 32 + qrow;
-        if (tq < L) {
-            const float l = Ls[wave * 32 + qrow];
-            float* dst = ctx + (size_t)(t0 + tq) * H + hd * D + r;
-#pragma unroll
-            for (int dt = 0; dt < D / 32; ++dt) dst[32 * dt] = o[dt][e] / l;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- dispatch order of the attention workgroups
-// order[0 .. n_seqs) = the sequences sorted by key-tile count, longest first (counting sort over the
-// ICREC_MAX_SEQLEN / 32 possible counts; the order inside one count is whatever the atomics give - the workgroups are
-// independent, results do not depend on it).  The attention launches map workgroup b to sequence order[b / heads]: each
-// bucket's workgroups are then dispatched longest-first with the other buckets' (empty) workgroups behind them instead
-// of in between, so a launch does not end on a few long sequences that started last.
-__global__ __launch_bounds__(1024) void seq_order_kernel(const int32_t* __restrict__ cu, int n_seqs,
-                                                         int32_t* __restrict__ order) {
-    constexpr int NB = ICREC_MAX_SEQLEN / 32;  // bin NB - nkt holds the sequences of nkt key tiles
-    __shared__ int hist[NB];
-    const int tid = threadIdx.x;
-    if (tid < NB) hist[tid] = 0;
-    __syncthreads();
-    auto bin = [&](int s) {
-        const int L = cu[s + 1] - cu[s];
-        const int nkt = (L + 31) >> 5;
-        return NB - (nkt < 1 ? 1 : (nkt > NB ? NB : nkt));
-    };
-    for (int s0 = tid; s0 < n_seqs; s0 += 1024) atomicAdd(&hist[bin(n_seqs - 1 - s0)], 1);
-    __syncthreads();
-    if (tid == 0) {  // exclusive prefix sum: hist[b] becomes the first slot of bin b
-        int run = 0;
-        for (int b = 0; b < NB; ++b) { const int c = hist[b]; hist[b] = run; run += c; }
-    }
-    __syncthreads();
-    for (int s0 = tid; s0 < n_seqs; s0 += 1024) {
-        const int s = n_seqs - 1 - s0;
-        order[atomicAdd(&hist[bin(s)], 1)] = s;
-    }
-}
-
-// ---------------------------------------------------------------- attention, f16x3 arithmetic
-// Same structure as attention_kernel (one block per (sequence, head), S^T on the accumulator rows, P fed
-// back from the accumulators), with both products on the f16 MFMA by the 3-term split of wt_gemm.h (one accumulator,
-// the plane scales folded into constants: see the kernel):
-//   S^T ~ K_hi.Q_hi + K_hi.Q_lo + K_lo.Q_hi        O ~ P_hi.V_hi + P_hi.V_lo + P_lo.V_hi
-// K is staged as hi/lo f16 planes [key][D] with the 16-B chunks of a row XOR-swizzled (att_k_swz), V as row-major hi/lo
-// planes [key][D] read through the transposing LDS read; Q (per wave) and P (per tile, straight from the accumulators)
-// are split in registers.
-// For a 32-key tile and k-step s, slot j of lane-half h is key 4h + (j&3) + 8(2s + (j>>2)) — the keys
-// accumulator register e = 8s + j holds — on both operands.
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-
-// ds_read_b64_tr_b16 (gfx950): all 64 lanes must be active; `p` is this lane's Mechanism address (8-byte aligned)
-__device__ __forceinline__ half4 lds_read_tr(const _Float16* p) {
-    typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-    return __builtin_bit_cast(half4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                                         (__attribute__((address_space(3))) fp16x4*)(reinterpret_cast<uintptr_t>(p))));
-}
-
-// Swizzle key of a K plane row: 64-B rows (D = 32) repeat their bank pattern every 4 rows, 128-B rows (D = 64) every row.
-constexpr int att_k_swz(int D, int row) { return D == 32 ? (row >> 2) & 3 : row & 7; }
-// Workgroups per CU the register allocation aims at (32-dim heads; 64-dim heads are bound by their LDS).
-constexpr int att_x3_wgs(int D, int NKT) { return D != 32 ? 1 : NKT >= 6 ? 4 : NKT == 4 ? 3 : 1; }
-
-// Output: the context as f16 hi/lo planes (`ch` / `cl`).  order: seq_order_kernel's dispatch order, or nullptr.
-// nqb: the query blocks to compute, from block 0 - NKT for all of them; 1 for the last layer of a CLS-pooled encoder,
-// which reads each sequence's first row only: every wave still stages K / V and meets every barrier, only wave 0 runs
-// the score / softmax / P.V loop and stores its tile, the very bits a full launch gives those rows.
-// BIAS: the relative-position bias arm (see att_bias_to_lds), 4 KB of LDS more.
-template <int D, int NKT, bool BIAS = false>  // NKT waves, one per 32-row query block
-__global__ __launch_bounds__(NKT * 64, att_x3_wgs(D, NKT)) void attention_x3_kernel(
-    const float* __restrict__ qkv, const int32_t* __restrict__ cu, int heads, int H, float scale_log2e,
-    _Float16* __restrict__ ch, _Float16* __restrict__ cl, const int32_t* __restrict__ order, int nlo, int nqb,
-    const float* __restrict__ bias) {
-    // Single-accumulator form of the split (wt_gemm.h): every operand is carried as hi/lo f16 planes of 16 x (Q, K, V)
-    // or 1024 p (the probabilities), the three products of a k-step accumulate into ONE fp32 tile, and the power-of-two
-    // scales are folded into constants: S' = 256 S, O' = 16384 sum_k p_k V_k, l' = 1024 sum_k p_k, O = O' / (16 l').
-    // All splits are the 3-instruction form (mask / subtract / v_cvt_pkrtz pairs).
-    //
-    // Long buckets (NKT >= 6) and 64-dim heads, RECOMP: the score tiles are computed TWICE - once for the row maximum
-    // (on the hi x hi products alone, see score_tile), once more in full for the exponentials, each tile consumed by the
-    // PV product as soon as it exists - instead of all of them being held in 128 registers between the two passes: 16
-    // more MFMAs per wave, and the 32-dim kernel drops under 128 VGPRs; with the output tile parked on the K
-    // planes (behind one more barrier) it also drops to 67 KB of LDS - TWO workgroups per CU, so one's staging and
-    // barrier phases run under the other's arithmetic.
-    constexpr int KC = att_kc(D, NKT), G = D / 4;  // G: 4-dim groups of a row
-    constexpr bool RECOMP = D == 64 || NKT >= 6;
-    // The two places where the widths differ for speed, not for width.  32-dim heads issue all of a thread's K/V loads
-    // before the first one is consumed (PREFETCH) and park each wave's output tile (hi | lo) on the K planes once all waves
-    // have left them, to write it out 16 B per lane - 4 store instructions instead of 32 two-byte ones (PARK; the NKT
-    // tiles fill the K planes exactly).  64-dim heads stage with a plain loop and store straight from the accumulators.
-    constexpr bool PREFETCH = D == 32, PARK = D == 32;
-    static_assert(!PARK || KC == NKT, "the parked output tiles need the K planes of all NKT key tiles");
-    __shared__ __attribute__((aligned(16))) _Float16 Kbuf[2 * KC * 32 * D];
-    _Float16* const Kh = Kbuf;
-    _Float16* const Kl = Kbuf + KC * 32 * D;
-    // V as it arrives: row-major hi / lo planes [key][D] (one 8-byte store per thread and plane where the
-    // transposed image took four 2-byte ones); the P.V product reads its B operand - 4 consecutive keys of one head
-    // dimension per lane - with the transposing LDS read (ds_read_b64_tr_b16: per 16-lane group a block of 4 keys x 16
-    // dims, lane 4q + p supplying the address of key q, dims 4p..4p+3, lane i receiving dim i of the 4 keys; at D = 32 a
-    // 32-lane half covers 4 rows of 64 B = every bank once).
-    __shared__ __attribute__((aligned(16))) _Float16 Vh[KC * 32 * D];
-    __shared__ __attribute__((aligned(16))) _Float16 Vl[KC * 32 * D];
-    __shared__ float Ls[NKT * 32];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sidx = blockIdx.x / heads, hd = blockIdx.x % heads;
-    const int s = order != nullptr ? order[sidx] : sidx;  // seq_order_kernel: longest first
-    const int t0 = cu[s], L = cu[s + 1] - t0;
-    const int nkt = (L + 31) >> 5;
-    if (nkt > NKT || nkt <= nlo) return;  // another bucket's sequence
-    const int ld = 3 * H;
-    const int r = lane & 31, h = lane >> 5, qb = wave;
-    const bool active = qb < nkt && qb < nqb;  // wave-uniform; idle waves still take part in the barriers
-    const float* bt = nullptr;  // this lane's window of the head's bias row (BIAS), visible behind the staging barrier
-    if constexpr (BIAS) {
-        __shared__ __attribute__((aligned(16))) float Bs[ATT_BIAS_LD];
-        att_bias_to_lds(Bs, bias, hd, tid, NKT * 64);
-        bt = Bs + att_bias_base(qb, lane);
-    }
-    half8 qh[D / 16], ql[D / 16];  // B operand of S^T: this lane's query row, dims 16 ks + 8 h .. +7
-    {
-        int qr = qb * 32 + r;
-        qr = qr < L ? qr : L - 1;
-        const float* qp = qkv + (size_t)(t0 + qr) * ld + hd * D;
-#pragma unroll
-        for (int ks = 0; ks < D / 16; ++ks) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 8 * h);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(qp + 16 * ks + 8 * h + 4);
-            half4 ah, al, bh, bl;
-            split_act4(a, ah, al);
-            split_act4(b, bh, bl);
-            qh[ks] = half8{ah[0], ah[1], ah[2], ah[3], bh[0], bh[1], bh[2], bh[3]};
-            ql[ks] = half8{al[0], al[1], al[2], al[3], bl[0], bl[1], bl[2], bl[3]};
-        }
-    }
-    const bool once = KC == NKT || nkt <= KC;  // the whole sequence fits: staged once, K and V
-    // key tiles [c0, c0 + KC) -> the LDS planes; rows past L are clamped (masked below / never stored)
-    auto stage = [&](int c0, bool with_v) {
-        if (!once) __syncthreads();  // the previous chunk's readers are done
-        const int nk = (nkt - c0 < KC ? nkt - c0 : KC) * 32;
-        auto src_of = [&](int id) {  // item id = (row, 4-dim group) of the chunk
-            const int key = c0 * 32 + id / G, rr = key < L ? key : L - 1;
-            return qkv + (size_t)(t0 + rr) * ld + hd * D + (id % G) * 4;
-        };
-        auto put = [&](int id, const f32x4& k, const f32x4& v) {
-            const int row = id / G, c = id % G;
-            half4 khi, klo;
-            split_act4(k, khi, klo);
-            if (with_v) {
-                half4 vhi, vlo;
-                split_act4(v, vhi, vlo);
-                *reinterpret_cast<half4*>(Vh + row * D + c * 4) = vhi;
-                *reinterpret_cast<half4*>(Vl + row * D + c * 4) = vlo;
-            }
-            const int off = row * D + ((((c >> 1) ^ att_k_swz(D, row)) << 3) | ((c & 1) << 2));
-            *reinterpret_cast<half4*>(Kh + off) = khi;
-            *reinterpret_cast<half4*>(Kl + off) = klo;
-        };
-        if constexpr (PREFETCH) {
-            constexpr int STG = KC * 32 * G / (NKT * 64);
-            static_assert(KC * 32 * G % (NKT * 64) == 0, "staging: whole rounds");
-            f32x4 kreg[STG], vreg[STG];
-#pragma unroll
-            for (int it = 0; it < STG; ++it) {
-                const float* src = src_of(tid + it * NKT * 64);
-                kreg[it] = *reinterpret_cast<const f32x4*>(src + H);
-                if (with_v) vreg[it] = *reinterpret_cast<const f32x4*>(src + 2 * H);
-            }
-#pragma unroll
-            for (int it = 0; it < STG; ++it)
-                if (tid + it * NKT * 64 < nk * G) put(tid + it * NKT * 64, kreg[it], vreg[it]);
-        } else {
-            for (int id = tid; id < nk * G; id += NKT * 64) {
-                const float* src = src_of(id);
-                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (with_v) v = *reinterpret_cast<const f32x4*>(src + 2 * H);
-                put(id, *reinterpret_cast<const f32x4*>(src + H), v);
-            }
-        }
-        __syncthreads();
-    };
-    // raw scores S' = 256 S of key tile kt (staged from c0) for this wave's 32 queries, keys beyond the sequence at -inf
-    // (only the one tile that has any pays for the selects: uniform branch)
-    // hi_only (the row-maxima pass): the hi x hi products alone - a third of the MFMAs.  The
-    // softmax does not care which shift it is given as long as the exponentials stay in range; this approximate maximum
-    // can sit below the true one by at most 2^-10 |q| |k| in score units, the planes of p' = 2^10 p have 2^6 of head room,
-    // and the exponent is clamped for whatever lies beyond (|q| |k| > 2.4e4: two hundred times a BERT head's).
-    auto score_tile = [&](int kt, int c0, bool hi_only) {
-        f32x16 t;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t[e] = 0.0f;
-        const int row = (kt - c0) * 32 + r;
-#pragma unroll
-        for (int ks = 0; ks < D / 16; ++ks) {
-            const int off = row * D + (((2 * ks + h) ^ att_k_swz(D, row)) << 3);
-            const half8 kh = *reinterpret_cast<const half8*>(Kh + off);
-            const half8 kl = *reinterpret_cast<const half8*>(Kl + off);
-            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], t, 0, 0, 0);
-            if (hi_only) continue;
-            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], t, 0, 0, 0);
-            t = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], t, 0, 0, 0);
-        }
-        if (kt == nkt - 1 && kt * 32 + 32 > L) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (kt * 32 + acc_row(e, lane) >= L) t[e] = -INFINITY;
-        }
-        return t;
-    };
-    // O' += P'.V for key tile kt: pt is a tile of p' = 1024 p in the accumulator layout; o[dt] holds head dims 32 dt + r
-    f32x16 o[D / 32];
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[dt][e] = 0.0f;
-    auto pv_tile = [&](int kt, int c0, const f32x16& pt) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 ph, pl;
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                half2w a, b;
-                split_pair_prescaled(pt[8 * ks + j], pt[8 * ks + j + 1], a, b);
-                ph[j] = a[0]; ph[j + 1] = a[1];
-                pl[j] = b[0]; pl[j + 1] = b[1];
-            }
-            // this lane's head dim, keys base .. base+3 and base+8 .. base+11: two transposed 4-key x 16-dim blocks per plane
-            const int base = (kt - c0) * 32 + 4 * h + 16 * ks;
-#pragma unroll
-            for (int dt = 0; dt < D / 32; ++dt) {
-                const int tr_at = (base + ((lane & 15) >> 2)) * D + 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-                const half4 v0h = lds_read_tr(Vh + tr_at);
-                const half4 v1h = lds_read_tr(Vh + tr_at + 8 * D);
-                const half4 v0l = lds_read_tr(Vl + tr_at);
-                const half4 v1l = lds_read_tr(Vl + tr_at + 8 * D);
-                const half8 vh = {v0h[0], v0h[1], v0h[2], v0h[3], v1h[0], v1h[1], v1h[2], v1h[3]};
-                const half8 vl = {v0l[0], v0l[1], v0l[2], v0l[3], v1l[0], v1l[1], v1l[2], v1l[3]};
-                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh, o[dt], 0, 0, 0);
-                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl, o[dt], 0, 0, 0);
-                o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh, o[dt], 0, 0, 0);
-            }
-        }
-    };
-    // every key tile of the sequence, chunk by chunk (one chunk when the sequence was staged whole)
-    auto for_tiles = [&](bool with_v, auto&& f) {
-#pragma unroll
-        for (int c0 = 0; c0 < NKT; c0 += KC) {
-            if (c0 < nkt) {
-                if (!once) stage(c0, with_v);
-                if (active) {
-#pragma unroll
-                    for (int j = 0; j < KC; ++j)
-                        if (c0 + j < nkt) f(c0 + j, c0);
-                }
-            }
-        }
-    };
-    typedef float float2w __attribute__((ext_vector_type(2)));
-    const float cs = scale_log2e * (1.0f / 256.0f);  // scores in log2 units from S' = 256 S
-    // Softmax on the raw scores (S' = 256 S): the maximum is taken before scaling, and scale, shift and the 2^10 factor
-    // of p' = 1024 p go into one fma in front of the exponential: p' = 2^(S' cs - max' cs + 10).
-    // BIAS: the logit in log2 units is v = S' cs + bias, one fma; the maximum is taken over v (a maximum over S' alone
-    // would let a large bias on a small logit run past every head room), and p' = 2^(v - max + 10).  On the hi x hi
-    // maximum of the RECOMP form the exponent clamp still covers what the two dropped products add, as without a bias.
-    auto biased = [&](f32x16& t, int kt) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t[e] = fmaf(t[e], cs, bt[kt * 32 + (e & 3) + 8 * (e >> 2)]);
-    };
-    // row sums l' = sum_k p'_k: two interleaved chains per lane (packed adds), the halves of a row joined by a shuffle
-    float2w ls2 = float2w{0.0f, 0.0f};
-    auto join_rows = [&]() {
-        const float lrow = join_halves(ls2[0] + ls2[1], h);
-        if (h == 0) Ls[wave * 32 + r] = lrow;  // read back by this wave's own lanes only
-    };
-    if (once) stage(0, true);
-    if constexpr (RECOMP) {
-        float mx = -INFINITY;
-        for_tiles(false, [&](int kt, int c0) {
-            f32x16 t = score_tile(kt, c0, true);
-            if constexpr (BIAS) biased(t, kt);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, t[e]);
-        });
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float shift = BIAS ? 10.0f - mx : fmaf(-mx, cs, 10.0f);
-        for_tiles(true, [&](int kt, int c0) {
-            f32x16 t = score_tile(kt, c0, false);
-            if constexpr (BIAS) {
-                biased(t, kt);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(t[e] + shift, 15.9f));
-            } else {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) t[e] = __builtin_amdgcn_exp2f(fminf(fmaf(t[e], cs, shift), 15.9f));
-            }
-#pragma unroll
-            for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{t[e], t[e + 1]};
-            pv_tile(kt, c0, t);
-        });
-        if (active) join_rows();
-    } else if (active) {
-        f32x16 sc[NKT];
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-            if (kt < nkt) {
-                sc[kt] = score_tile(kt, 0, false);
-                if constexpr (BIAS) biased(sc[kt], kt);
-            }
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-            if (kt < nkt) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sc[kt][e]);
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float shift = BIAS ? 10.0f - mx : fmaf(-mx, cs, 10.0f);
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-            if (kt < nkt) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    sc[kt][e] = __builtin_amdgcn_exp2f(BIAS ? sc[kt][e] + shift : fmaf(sc[kt][e], cs, shift));
-            }
-        }
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-            if (kt < nkt) {
-#pragma unroll
-                for (int e = 0; e < 16; e += 2) ls2 = ls2 + float2w{sc[kt][e], sc[kt][e + 1]};
-            }
-        }
-        join_rows();
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-            if (kt < nkt) pv_tile(kt, 0, sc[kt]);
-    }
-    if (PARK) __syncthreads();  // every wave has left the K planes: they become the output tiles
-    if (!active) return;
-    // normalise, split into the hi / lo planes and store: PARK row-major into the wave's LDS tile, else to memory
-    _Float16* const ob = Kbuf + wave * (2 * 32 * D);
-#pragma unroll
-    for (int e = 0; e < 16; e += 2) {
-        const int q0 = acc_row(e, lane), q1 = acc_row(e + 1, lane);
-        const float s0 = 0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q0]);
-        const float s1 = 0.0625f * __builtin_amdgcn_rcpf(Ls[wave * 32 + q1]);
-        const int tq0 = qb * 32 + q0, tq1 = qb * 32 + q1;
-#pragma unroll
-        for (int dt = 0; dt < D / 32; ++dt) {
-            half2w hi, lo;
-            split_pair_prescaled(o[dt][e] * s0 * WT_SA, o[dt][e + 1] * s1 * WT_SA, hi, lo);
-            const int c = 32 * dt + r;
-            if constexpr (PARK) {
-                ob[q0 * D + c] = hi[0];
-                ob[q1 * D + c] = hi[1];
-                ob[32 * D + q0 * D + c] = lo[0];
-                ob[32 * D + q1 * D + c] = lo[1];
-            } else {
-                if (tq0 < L) {
-                    ch[(size_t)(t0 + tq0) * H + hd * D + c] = hi[0];
-                    cl[(size_t)(t0 + tq0) * H + hd * D + c] = lo[0];
-                }
-                if (tq1 < L) {
-                    ch[(size_t)(t0 + tq1) * H + hd * D + c] = hi[1];
-                    cl[(size_t)(t0 + tq1) * H + hd * D + c] = lo[1];
-                }
-            }
-        }
-    }
-    if constexpr (PARK) {
-#pragma unroll
-        for (int t = 0; t < D / 16; ++t) {
-            const int id = lane + 64 * t, qrow = id / (D / 8), c8 = (id % (D / 8)) * 8;
-            const int tq = qb * 32 + qrow;
-            if (tq < L) {
-                const size_t at = (size_t)(t0 + tq) * H + hd * D + c8;
-                *reinterpret_cast<u32x4*>(ch + at) = *reinterpret_cast<const u32x4*>(ob + qrow * D + c8);
-                *reinterpret_cast<u32x4*>(cl + at) = *reinterpret_cast<const u32x4*>(ob + 32 * D + qrow * D + c8);
-            }
-        }
     }
 }
 
@@ -926,7 +324,7 @@ struct Encoder {
     int n_cu = 256;
     int max_seqlen = 256;       // longest sequence icrec_encode accepts (icrec_encoder_set_max_seqlen)
     int pooling = ICREC_POOL_MEAN;  // icrec_encoder_set_pooling
-    float* att_bias = nullptr;  // icrec_encoder_set_attention_bias: [heads][ATT_BIAS_LD] in log2 units, or none
+    float* att_bias = nullptr;  // icrec_encoder_set_attention_bias: AttentionArgs::bias, or none
     float* score_head = nullptr;  // icrec_encoder_set_score_head: Wp^T [H in][H out], bp[H], wc[H], bc[1], or none
     float* blob = nullptr;      // the uploaded weight blob
     float* extra = nullptr;     // repacked Wqkv / bqkv
@@ -956,28 +354,24 @@ struct Encoder {
     // than one round by definition, so a larger value changes nothing).  Every combination is supported and gives the
     // same bits; with tail_m > small_m a remainder longer than small_m takes the layer kernels (activation-resident QKV,
     // fused layer kernel) on the side stream instead of the latency form.
-    // Side stream + events of one caller stream: the short remainder of a large batch (batch_tail) and the shorter
-    // attention buckets run beside the batch kernels of the same layer instead of behind them.  One set per caller
-    // stream (created on first use, kept for the encoder's life), so that concurrent icrec_encode calls on different
-    // streams - DeviceEncoder runs the two halves of a batch that way - do not queue behind each other's side work.
-    // Every fork and join records `ev` and waits on it at once (link), so one event serves them all.
-    struct Side {
-        hipStream_t caller = nullptr, side = nullptr;
-        hipEvent_t ev = nullptr;
-    };
+    // Side stream + event of one caller stream (attention.h: SideStream, link): the short remainder of a large batch
+    // (batch_tail) and the shorter attention buckets run beside the batch kernels of the same layer instead of behind
+    // them.  One set per caller stream (created on first use, kept for the encoder's life), so that concurrent
+    // icrec_encode calls on different streams - DeviceEncoder runs the two halves of a batch that way - do not queue
+    // behind each other's side work.
     std::mutex side_mu;
-    std::vector<Side*> sides;
+    std::vector<SideStream*> sides;
 };
 
-static int side_for(Encoder* e, hipStream_t caller, Encoder::Side** out) {
+static int side_for(Encoder* e, hipStream_t caller, SideStream** out) {
     std::lock_guard<std::mutex> lock(e->side_mu);
     *out = nullptr;
-    for (Encoder::Side* sd : e->sides)
+    for (SideStream* sd : e->sides)
         if (sd->caller == caller) { *out = sd; return ICREC_OK; }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (caller && hipStreamIsCapturing(caller, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
         return ICREC_OK;  // no stream / event creation inside a capture: the call stays on the caller's stream
-    Encoder::Side* sd = new Encoder::Side();
+    SideStream* sd = new SideStream();
     sd->caller = caller;
     ICREC_HIP(hipStreamCreateWithFlags(&sd->side, hipStreamNonBlocking));
     ICREC_HIP(hipEventCreateWithFlags(&sd->ev, hipEventDisableTiming));
@@ -1023,11 +417,12 @@ struct EncBufs {
           hl(hh + T * c.intermediate) {}
 };
 
-// A CLS-pooled f16x3 encoder reads row cu[s] of the last hidden state and nothing else: its last layer runs attention for
-// query block 0 of each (sequence, head) and the post-attention chain over n_seqs compact rows (encode_x3), which take
-// their scratch from the caller's workspace behind the call's own regions.
-static bool cls_prunes(const Encoder* e) {
-    return e->pooling == ICREC_POOL_CLS && e->cls_prune && e->cfg.gemm_mode == ICREC_GEMM_F16X3;
+// An f16x3 encoder whose caller reads row cu[s] of the last hidden state and nothing else runs its last layer's attention
+// for query block 0 of each (sequence, head) and the post-attention chain over n_seqs compact rows (encode_x3), which
+// take their scratch from the caller's workspace behind the call's own regions.  A pair's score reads those rows
+// whatever the handle's pooling mode; an embedding does under CLS pooling only (pooled: the pooling mode matters).
+static bool prunes_last_layer(const Encoder* e, bool pooled) {
+    return (!pooled || e->pooling == ICREC_POOL_CLS) && e->cls_prune && e->cfg.gemm_mode == ICREC_GEMM_F16X3;
 }
 
 typedef TileCfg<2, 2, 2, 2> GemmBig;  // 128 x 128 output tile, 4 waves
@@ -1041,6 +436,11 @@ static int env_knob(const char* name, int fallback, long long hi) {
     const long long v = strtoll(s, &end, 10);
     if (end == s) return fallback;
     return (int)(v < 0 ? 0 : v > hi ? hi : v);
+}
+// An on/off switch from the environment: on unless its value starts with '0'.
+static bool env_switch(const char* name) {
+    const char* s = getenv(name);
+    return !(s && s[0] == '0');
 }
 
 template <bool GELU>
@@ -1082,50 +482,6 @@ static void launch_wt_linear(const _Float16* Xh, const _Float16* Xl, int T, int 
     }
 }
 
-// The attention length buckets, in launch order: 9-16 key tiles first (257-512 tokens: the longest bucket starts first),
-// then from the shortest up.  f16x3 batches over 32-dim heads take 5-8 key tiles in two buckets; single sequences, fp32
-// and 64-dim heads in one.
-// Bucket k serves [ATT_LO[k], ATT_HI[k]] key tiles with the kernel <NKT = ATT_HI[k]> (NKT waves per workgroup).
-enum AttBucket { ATT_9_16, ATT_1, ATT_2, ATT_3_4, ATT_5_6, ATT_7_8, ATT_5_8, ATT_N };
-constexpr int ATT_LO[ATT_N] = {9, 1, 2, 3, 5, 7, 5}, ATT_HI[ATT_N] = {16, 1, 2, 4, 6, 8, 8};
-
-// Launch, in AttBucket order, the buckets in `mask` (bits 1 << AttBucket) that the call needs: for a batch every bucket
-// that can occur for max_seqlen (one whose workgroups all exit costs a few microseconds), else the one that holds it.
-// X3: the f16x3 kernel, context out as planes (attention_x3_kernel); otherwise exact fp32 rows (attention_kernel).
-// block0_only (X3): query block 0 of every (sequence, head) alone - the pruned last layer of a CLS-pooled encoder.
-// bias: the encoder's relative-position table (the kernels' BIAS arm), or nullptr: the launches of an encoder without one.
-template <bool X3>
-static void launch_attention(unsigned mask, const icrec_bert_cfg& c, const EncBufs& b, const int32_t* cu, int n_seqs,
-                             int max_seqlen, const int32_t* order, const float* bias, hipStream_t st,
-                             bool block0_only = false) {
-    const int nkt_max = (max_seqlen + 31) / 32;
-    const int dh = c.hidden / c.heads;  // 32 or 64 (icrec_encoder_create)
-    const bool single = n_seqs == 1, split_5_8 = X3 && !single && dh == 32;
-    const float sl2e = (1.0f / sqrtf((float)dh)) * 1.44269504088896340736f;
-    for (int k = 0; k < ATT_N; ++k) {
-        if (!(mask >> k & 1) || (split_5_8 ? k == ATT_5_8 : k == ATT_5_6 || k == ATT_7_8) || nkt_max < ATT_LO[k] ||
-            (single && nkt_max > ATT_HI[k]))
-            continue;
-        const dim3 grid(n_seqs * c.heads), block(ATT_HI[k] * 64);
-        if constexpr (X3) {  // (only 32-dim heads split 5-8 key tiles)
-#define ICREC_ATT_ROW(K, D, B) {K<D, 16, B>, K<D, 1, B>, K<D, 2, B>, K<D, 4, B>, D == 32 ? K<32, 6, B> : nullptr, D == 32 ? K<32, 8, B> : nullptr, K<D, 8, B>}
-            static const decltype(&attention_x3_kernel<32, 1>) kern[2][2][ATT_N] = {
-                {ICREC_ATT_ROW(attention_x3_kernel, 32, false), ICREC_ATT_ROW(attention_x3_kernel, 64, false)},
-                {ICREC_ATT_ROW(attention_x3_kernel, 32, true), ICREC_ATT_ROW(attention_x3_kernel, 64, true)}};
-#undef ICREC_ATT_ROW
-            hipLaunchKernelGGL(kern[bias != nullptr][dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e,
-                               b.ch, b.cl, order, ATT_LO[k] - 1, block0_only ? 1 : ATT_HI[k], bias);
-        } else {
-#define ICREC_ATT_ROW(D, B) {attention_kernel<D, 16, B>, attention_kernel<D, 1, B>, attention_kernel<D, 2, B>, attention_kernel<D, 4, B>, nullptr, nullptr, attention_kernel<D, 8, B>}
-            static const decltype(&attention_kernel<32, 1>) kern[2][2][ATT_N] = {
-                {ICREC_ATT_ROW(32, false), ICREC_ATT_ROW(64, false)}, {ICREC_ATT_ROW(32, true), ICREC_ATT_ROW(64, true)}};
-#undef ICREC_ATT_ROW
-            hipLaunchKernelGGL(kern[bias != nullptr][dh == 64][k], grid, block, 0, st, b.qkv, cu, c.heads, c.hidden, sl2e,
-                               b.ctx, ATT_LO[k] - 1, bias);
-        }
-    }
-}
-
 }  // namespace icrec
 
 using namespace icrec;
@@ -1161,16 +517,11 @@ int icrec_encoder_create(const float* weights_host, size_t n_floats, const icrec
     e->device = device;
     e->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     e->max_seqlen = cfg->max_position < 256 ? cfg->max_position : 256;
-    {
-        const char* fuse_env = getenv("ICREC_FUSE");
-        const char* side_env = getenv("ICREC_SIDE_STREAM");
-        e->fuse = !(fuse_env && fuse_env[0] == '0');
-        e->small_m = env_knob("ICREC_SMALL_M", e->small_m, SMALL_M_MAX);
-        e->tail_m = env_knob("ICREC_TAIL_M", e->tail_m, 64LL * e->n_cu - 1);
-        e->side_stream = !(side_env && side_env[0] == '0');
-        const char* prune_env = getenv("ICREC_CLS_PRUNE");
-        e->cls_prune = !(prune_env && prune_env[0] == '0');
-    }
+    e->fuse = env_switch("ICREC_FUSE");
+    e->side_stream = env_switch("ICREC_SIDE_STREAM");
+    e->cls_prune = env_switch("ICREC_CLS_PRUNE");
+    e->small_m = env_knob("ICREC_SMALL_M", e->small_m, SMALL_M_MAX);
+    e->tail_m = env_knob("ICREC_TAIL_M", e->tail_m, 64LL * e->n_cu - 1);
     const size_t H = cfg->hidden, I = cfg->intermediate;
     const size_t mat_per_layer = 3 * H * H + H * H + I * H + H * I;
     const bool x3 = cfg->gemm_mode == ICREC_GEMM_F16X3;
@@ -1232,7 +583,7 @@ int icrec_encoder_destroy(icrec_encoder* h) {
     if (e->planes) (void)hipFree(e->planes);
     if (e->att_bias) (void)hipFree(e->att_bias);
     if (e->score_head) (void)hipFree(e->score_head);
-    for (Encoder::Side* sd : e->sides) {  // (side_for keeps a side only once its stream and event exist)
+    for (SideStream* sd : e->sides) {  // (side_for keeps a side only once its stream and event exist)
         (void)hipStreamSynchronize(sd->side);
         (void)hipStreamDestroy(sd->side);
         (void)hipEventDestroy(sd->ev);
@@ -1276,12 +627,12 @@ int icrec_encoder_set_attention_bias(icrec_encoder* h, const float* bias_host, i
     ICREC_REQUIRE(heads == e->cfg.heads, "icrec_encoder_set_attention_bias: heads must be %d, the encoder's (got %d)", e->cfg.heads, heads);
     constexpr int N = 2 * ICREC_MAX_SEQLEN - 1;
     // log2 units, like the kernels' scale: the product in double, rounded once
-    std::vector<float> tab((size_t)heads * ATT_BIAS_LD, 0.0f);
+    std::vector<float> tab((size_t)heads * AttentionArgs::BIAS_LD, 0.0f);
     for (int hd = 0; hd < heads; ++hd)
         for (int i = 0; i < N; ++i) {
             const float v = bias_host[(size_t)hd * N + i];
             ICREC_REQUIRE(v - v == 0.0f, "icrec_encoder_set_attention_bias: entry [%d][%d] is not finite", hd, i);
-            tab[(size_t)hd * ATT_BIAS_LD + i] = (float)((double)v * 1.44269504088896340736);
+            tab[(size_t)hd * AttentionArgs::BIAS_LD + i] = (float)((double)v * 1.44269504088896340736);
         }
     float* dev = e->att_bias;
     if (!dev && hipMalloc(&dev, tab.size() * 4) != hipSuccess) {
@@ -1345,15 +696,18 @@ int32_t icrec_encoder_has_score_head(const icrec_encoder* h) {
     return e ? (e->score_head != nullptr) : -1;
 }
 
-// The call's own regions, then (cls_prunes) the compact rows' of the pruned last layer.
-static size_t workspace_bytes(const Encoder* e, int64_t T, int n_seqs) {
-    return enc_ws(e->cfg, T).total + (cls_prunes(e) ? enc_ws(e->cfg, n_seqs, true).total : 0);
+// The call's own regions, then (prunes_last_layer) the compact rows' of the pruned last layer; 0 for arguments no call takes.
+static size_t workspace_bytes(const Encoder* e, int64_t T, int n_seqs, bool pooled) {
+    if (!e || T < 1 || n_seqs < 1) return 0;
+    return enc_ws(e->cfg, T).total + (prunes_last_layer(e, pooled) ? enc_ws(e->cfg, n_seqs, true).total : 0);
 }
 
 size_t icrec_encode_workspace_bytes(const icrec_encoder* h, int64_t total_tokens, int32_t n_seqs) {
-    const Encoder* e = reinterpret_cast<const Encoder*>(h);
-    if (!e || total_tokens < 1 || n_seqs < 1) return 0;
-    return workspace_bytes(e, total_tokens, n_seqs);
+    return workspace_bytes(reinterpret_cast<const Encoder*>(h), total_tokens, n_seqs, true);
+}
+
+size_t icrec_score_pairs_workspace_bytes(const icrec_encoder* h, int64_t total_tokens, int32_t n_seqs) {
+    return workspace_bytes(reinterpret_cast<const Encoder*>(h), total_tokens, n_seqs, false);
 }
 
 // How icrec_encode splits a batch of T tokens (f16x3 mode): [0, T - tail) through the batch kernels in whole rounds of
@@ -1371,31 +725,18 @@ int icrec_encode_batch_split(const icrec_encoder* h, int64_t total_tokens, int64
     return ICREC_OK;
 }
 
-// Embeddings + LayerNorm.  f16x3 mode leaves the fp32 x region unused (the residual stream is its two planes): it carries
-// the attention dispatch order of batches, returned here (nullptr: workgroup b serves sequence b / heads, as unfused).
+// Embeddings + LayerNorm, into b.x (fp32) or b.xh / b.xl (f16x3: the residual stream is its two planes).
 // seg_b_dev (icrec_score_pairs): each sequence's first position of token type 1 - the kernel's SEG arm; nullptr: type 0.
-static const int32_t* embed(const Encoder* e, const EncBufs& b, const int32_t* ids_dev, const int32_t* cu_dev,
-                            const int32_t* seg_b_dev, int n_seqs, int T, hipStream_t st) {
+static void embed(const Encoder* e, const EncBufs& b, const int32_t* ids_dev, const int32_t* cu_dev,
+                  const int32_t* seg_b_dev, int n_seqs, int T, hipStream_t st) {
     const icrec_bert_cfg& c = e->cfg;
     const bool x3 = c.gemm_mode == ICREC_GEMM_F16X3;
-    int32_t* order = nullptr;
-    if (x3 && n_seqs >= 64 && e->fuse) {
-        order = reinterpret_cast<int32_t*>(b.x);
-        hipLaunchKernelGGL(seq_order_kernel, dim3(1), dim3(1024), 0, st, cu_dev, n_seqs, order);
-    }
     auto kern =
         for_hidden(c.hidden, [x3](auto h) { return x3 ? embed_ln_kernel<h(), true> : embed_ln_kernel<h(), false>; });
     if (seg_b_dev)
         kern = for_hidden(c.hidden, [x3](auto h) { return x3 ? embed_ln_kernel<h(), true, true> : embed_ln_kernel<h(), false, true>; });
     hipLaunchKernelGGL(kern, dim3((T + 3) / 4), dim3(256), 0, st, ids_dev, cu_dev, n_seqs, T, e->word, e->pos, e->type, e->eg, e->eb, c.ln_eps, c.vocab_size,
                        c.max_position, b.x, b.xh, b.xl, seg_b_dev);
-    return order;
-}
-
-// One fork or join: work enqueued on `to` from here on runs behind everything enqueued on `from` so far.
-static hipError_t link(const Encoder::Side* sd, hipStream_t from, hipStream_t to) {
-    const hipError_t err = hipEventRecord(sd->ev, from);
-    return err != hipSuccess ? err : hipStreamWaitEvent(to, sd->ev, 0);
 }
 
 // A token range of an f16x3 call, rows [r0, r0 + n) on stream st, and the form its kernels take, decided once per call.
@@ -1413,19 +754,24 @@ struct Range {
     bool ffn_ln_to_next(int l, int layers) const { return fold && l + 1 < layers; }  // to the next QKV's prologue
 };
 
-// cls: the compact rows' regions when the last layer is pruned to each sequence's first token (cls_prunes), else nullptr.
-// The last hidden state is then rows [0, n_seqs) of cls->xh / cls->xl and b's x planes stay one layer behind.
+// cls: the compact rows' regions when the last layer is pruned to each sequence's first token (prunes_last_layer), else
+// nullptr.  The last hidden state is then rows [0, n_seqs) of cls->xh / cls->xl and b's x planes stay one layer behind.
 static int encode_x3(Encoder* e, const EncBufs& b, const EncBufs* cls, const int32_t* cu_dev, int n_seqs, int T,
-                     int max_seqlen, const int32_t* order, hipStream_t st) {
+                     int max_seqlen, hipStream_t st) {
     const icrec_bert_cfg& c = e->cfg;
     const int H = c.hidden, I = c.intermediate;
     const auto ln_wt = for_hidden(H, [](auto h) { return ln_wt_kernel<h()>; });
-    const bool split_att = H == HID && e->side_stream && n_seqs >= 64 && max_seqlen > 128;  // batches with a long bucket
+    // Fused batches dispatch their attention workgroups longest sequence first; the order lives in the fp32 x region,
+    // which f16x3 mode leaves unused.  The unfused reference chain runs in natural order.
+    int32_t* const order = n_seqs >= 64 && e->fuse ? reinterpret_cast<int32_t*>(b.x) : nullptr;
+    if (order) attention_dispatch_order(cu_dev, n_seqs, order, st);
+    AttentionArgs att = {b.qkv, cu_dev, n_seqs, max_seqlen, c.heads, H, e->att_bias, order, nullptr, b.ch, b.cl, false};
+    const bool split_att = e->side_stream && attention_wants_side(att);
     // Token ranges: [0, T_main) goes through the batch kernels in whole rounds of one 64-token workgroup per CU, a short
     // remainder [T_main, T) through the small-batch kernels (same arithmetic, same bits) instead of costing every batch
     // kernel an extra, almost empty round.
     const int T_tail = batch_tail(e, T), T_main = T - T_tail;
-    Encoder::Side* sd = nullptr;
+    SideStream* sd = nullptr;
     if (e->side_stream && (T_tail || split_att))
         if (int rc_ = side_for(e, st, &sd)) return rc_;
     // The remainder's kernels run on the side stream: its QKV beside the batch QKV, its attention-out / FFN chain beside
@@ -1500,19 +846,8 @@ static int encode_x3(Encoder* e, const EncBufs& b, const EncBufs* cls, const int
         if (T_tail && tail.launches_qkv(l)) qkv_stage(tail, l);
         if (main.launches_qkv(l)) qkv_stage(main, l);
         if (tail_on_side) ICREC_HIP(link(sd, sd->side, st));
-        if (split_att && sd) {
-            // the long bucket keeps one 8-wave workgroup per CU busy (LDS) with issue slots to spare: the shorter
-            // buckets' workgroups run beside it from the side stream instead of after it (sequences of 9-16 key tiles:
-            // that bucket goes first, on the caller's stream, ahead of the side stream's)
-            ICREC_HIP(link(sd, st, sd->side));
-            const unsigned side_buckets = 1u << ATT_1 | 1u << ATT_2 | 1u << ATT_3_4 | 1u << ATT_7_8;
-            launch_attention<true>(1u << ATT_9_16, c, b, cu_dev, n_seqs, max_seqlen, order, e->att_bias, st, pruned);
-            launch_attention<true>(side_buckets, c, b, cu_dev, n_seqs, max_seqlen, order, e->att_bias, sd->side, pruned);
-            launch_attention<true>(1u << ATT_5_6, c, b, cu_dev, n_seqs, max_seqlen, order, e->att_bias, st, pruned);
-            ICREC_HIP(link(sd, sd->side, st));
-        } else {
-            launch_attention<true>(~0u, c, b, cu_dev, n_seqs, max_seqlen, order, e->att_bias, st, pruned);
-        }
+        att.block0_only = pruned;
+        if (int rc_ = run_attention(att, st, split_att ? sd : nullptr)) return rc_;
         if (pruned) {
             // Rows cu[s] of the context (query block 0 wrote them) and of x -> compact rows, then the unfused chain over
             // those n_seqs rows on the caller's stream, in the form their number picks.  The side stream joined above
@@ -1537,10 +872,11 @@ static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev,
     const icrec_bert_cfg& c = e->cfg;
     const int H = c.hidden, I = c.intermediate, rows_grid = (T + 3) / 4;
     const auto add_ln = for_hidden(H, [](auto h) { return add_ln_kernel<h()>; });
+    const AttentionArgs att = {b.qkv, cu_dev, n_seqs, max_seqlen, c.heads, H, e->att_bias, nullptr, b.ctx, nullptr, nullptr, false};
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& L = e->layers[l];
         launch_linear<false>(b.x, T, H, L.Wqkv, 3 * H, L.bqkv, b.qkv, st);
-        launch_attention<false>(~0u, c, b, cu_dev, n_seqs, max_seqlen, nullptr, e->att_bias, st);
+        if (int rc_ = run_attention(att, st, nullptr)) return rc_;
         launch_linear<false>(b.ctx, T, H, L.Wo, H, L.bo, b.t1, st);
         hipLaunchKernelGGL(add_ln, dim3(rows_grid), dim3(256), 0, st, b.t1, b.x, T, L.g1, L.b1n,
                            c.ln_eps, b.xh, b.xl);
@@ -1555,6 +891,48 @@ static int encode_f32(const Encoder* e, const EncBufs& b, const int32_t* cu_dev,
     return ICREC_OK;
 }
 
+// Where a call left the last hidden state its entry reads: fp32 rows `x` or (f16x3) the planes `xh` / `xl`; sequence s's
+// first token is row cu[s] or, compact (the pruned last layer: nothing but those rows exists), row s.
+struct LastRows {
+    const float* x;
+    const _Float16 *xh, *xl;
+    bool compact;
+};
+
+// The forward pass behind icrec_encode_ex and icrec_score_pairs, after the entry's own argument checks (`who`: its name,
+// the prefix of every error message): the shared checks, the workspace, then embeddings (seg_b_dev: see embed) and every
+// layer on `st`.  pooled: the entry reads what the handle's pooling mode says, else each sequence's first token alone;
+// every_token: it also reads every token's state.  timer: started once the call is admitted, or nullptr.
+static int forward(Encoder* e, const char* who, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* seg_b_dev,
+                   int32_t n_seqs, int64_t T64, int32_t max_seqlen, bool pooled, bool every_token, void* ws,
+                   size_t ws_bytes, hipStream_t st, ScopedTimer* timer, LastRows* last) {
+    ICREC_REQUIRE(n_seqs >= 1 && T64 >= n_seqs && T64 < (1ll << 31), "%s: bad n_seqs/total_tokens (%d, %lld)", who, n_seqs, (long long)T64);
+    ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= e->max_seqlen, "%s: max_seqlen must be in [1, %d] (got %d)", who, e->max_seqlen, max_seqlen);
+    const int T = (int)T64;
+    const size_t need = workspace_bytes(e, T, n_seqs, pooled);
+    if (!ws || ws_bytes < need) {
+        set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+        return ICREC_ENOMEM;
+    }
+    ICREC_HIP(hipSetDevice(e->device));
+    if (timer) timer->start(st);
+    char* base = reinterpret_cast<char*>(ws);
+    const icrec_bert_cfg& c = e->cfg;
+    const EncWs w = enc_ws(c, T);
+    const EncBufs b(base, w, c, T);
+    const EncBufs cls(base + w.total, enc_ws(c, n_seqs, true), c, n_seqs);  // (inside the workspace only if prunes_last_layer)
+    // The last layer is pruned to each sequence's first token when nothing else of it is read: not when the caller
+    // wants every token's state, and not when every token is a first token (nothing to save).
+    const bool pruned = prunes_last_layer(e, pooled) && !every_token && n_seqs < T;
+    embed(e, b, ids_dev, cu_dev, seg_b_dev, n_seqs, T, st);
+    if (int rc_ = c.gemm_mode == ICREC_GEMM_F16X3 ? encode_x3(e, b, pruned ? &cls : nullptr, cu_dev, n_seqs, T, max_seqlen, st)
+                                                  : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
+        return rc_;
+    const EncBufs& r = pruned ? cls : b;
+    *last = {r.x, r.xh, r.xl, pruned};
+    return ICREC_OK;
+}
+
 int icrec_encode(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev, int32_t n_seqs, int64_t T64,
                  int32_t max_seqlen, float* out_dev, void* ws, size_t ws_bytes, void* stream) {
     return icrec_encode_ex(h, ids_dev, cu_dev, n_seqs, T64, max_seqlen, out_dev, nullptr, ws, ws_bytes, stream);
@@ -1566,54 +944,26 @@ int icrec_encode_ex(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_
     Encoder* e = reinterpret_cast<Encoder*>(h);
     ICREC_REQUIRE(e && ids_dev && cu_dev && out_dev, "icrec_encode: NULL argument");
     ICREC_REQUIRE((reinterpret_cast<uintptr_t>(tokens_out_dev) & 15) == 0, "icrec_encode_ex: tokens_out_dev must be 16-byte aligned");
-    ICREC_REQUIRE(n_seqs >= 1 && T64 >= n_seqs && T64 < (1ll << 31), "icrec_encode: bad n_seqs/total_tokens (%d, %lld)", n_seqs, (long long)T64);
-    ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= e->max_seqlen, "icrec_encode: max_seqlen must be in [1, %d] (got %d)", e->max_seqlen, max_seqlen);
-    const int T = (int)T64;
-    const EncWs w = enc_ws(e->cfg, T);
-    const size_t need = workspace_bytes(e, T, n_seqs);
-    if (!ws || ws_bytes < need) {
-        set_error("icrec_encode: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ICREC_ENOMEM;
-    }
-    ICREC_HIP(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)stream;
-    ScopedTimer whole(T_ENCODE, st);
-    char* base = reinterpret_cast<char*>(ws);
-    const icrec_bert_cfg& c = e->cfg;
-    const int H = c.hidden;
-    const bool x3 = c.gemm_mode == ICREC_GEMM_F16X3;
-    const EncBufs b(base, w, c, T);
-    // The last layer is pruned to each sequence's first token when nothing else of it is read: not when the caller
-    // wants every token's state, and not when every token is a first token (nothing to save).
-    const bool pruned = cls_prunes(e) && !tokens_out_dev && n_seqs < T;
-    const EncBufs cls(base + w.total, enc_ws(c, n_seqs, true), c, n_seqs);  // (inside the workspace only if cls_prunes)
-    const int32_t* order = embed(e, b, ids_dev, cu_dev, nullptr, n_seqs, T, st);
-    if (int rc_ = x3 ? encode_x3(e, b, pruned ? &cls : nullptr, cu_dev, n_seqs, T, max_seqlen, order, st)
-                     : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
+    ScopedTimer whole(T_ENCODE);  // (forward starts it)
+    LastRows last;
+    if (int rc_ = forward(e, "icrec_encode", ids_dev, cu_dev, nullptr, n_seqs, T64, max_seqlen, true, tokens_out_dev != nullptr,
+                          ws, ws_bytes, st, &whole, &last))
         return rc_;
+    const int H = e->cfg.hidden;
+    const bool x3 = e->cfg.gemm_mode == ICREC_GEMM_F16X3;
     const auto pool =
         for_hidden(H, [x3](auto h) { return x3 ? pool_norm_kernel<h(), true> : pool_norm_kernel<h(), false>; });
-    const EncBufs& last = pruned ? cls : b;  // where the last hidden state of the pooled rows is
-    const int pool_rows = e->pooling != ICREC_POOL_CLS ? POOL_ROWS_MEAN : pruned ? POOL_ROWS_CLS_COMPACT : POOL_ROWS_CLS;
-    hipLaunchKernelGGL(pool, dim3(n_seqs), dim3(H), 0, st, last.x, last.xh, last.xl, cu_dev, c.n_normalize, out_dev,
+    const int pool_rows = e->pooling != ICREC_POOL_CLS ? POOL_ROWS_MEAN : last.compact ? POOL_ROWS_CLS_COMPACT : POOL_ROWS_CLS;
+    hipLaunchKernelGGL(pool, dim3(n_seqs), dim3(H), 0, st, last.x, last.xh, last.xl, cu_dev, e->cfg.n_normalize, out_dev,
                        pool_rows);
     if (tokens_out_dev) {  // hidden is a multiple of 4: every thread's 4 features are 16 (planes: 8) bytes, aligned
-        const size_t n4 = (size_t)T * H / 4;
+        const size_t n4 = (size_t)T64 * H / 4;  // (every token's state is wanted: `last` is every row)
         hipLaunchKernelGGL(x3 ? tokens_out_kernel<true> : tokens_out_kernel<false>, dim3((unsigned)((n4 + 255) / 256)),
-                           dim3(256), 0, st, b.x, b.xh, b.xl, n4, tokens_out_dev);
+                           dim3(256), 0, st, last.x, last.xh, last.xl, n4, tokens_out_dev);
     }
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
-}
-
-// A pair's score reads row cu[s] of the last hidden state and nothing else, whatever the handle's pooling mode: in f16x3
-// mode the last layer is pruned as a CLS-pooled encoder's is, its compact rows behind the call's own regions.
-static bool score_prunes(const Encoder* e) { return e->cls_prune && e->cfg.gemm_mode == ICREC_GEMM_F16X3; }
-
-size_t icrec_score_pairs_workspace_bytes(const icrec_encoder* h, int64_t total_tokens, int32_t n_seqs) {
-    const Encoder* e = reinterpret_cast<const Encoder*>(h);
-    if (!e || total_tokens < 1 || n_seqs < 1) return 0;
-    return enc_ws(e->cfg, total_tokens).total + (score_prunes(e) ? enc_ws(e->cfg, n_seqs, true).total : 0);
 }
 
 int icrec_score_pairs(icrec_encoder* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* seg_b_dev,
@@ -1622,35 +972,19 @@ int icrec_score_pairs(icrec_encoder* h, const int32_t* ids_dev, const int32_t* c
     Encoder* e = reinterpret_cast<Encoder*>(h);
     ICREC_REQUIRE(e && ids_dev && cu_dev && seg_b_dev && scores_out_dev, "icrec_score_pairs: NULL argument");
     ICREC_REQUIRE(e->score_head, "icrec_score_pairs: the encoder has no score head (icrec_encoder_set_score_head)");
-    ICREC_REQUIRE(n_seqs >= 1 && T64 >= n_seqs && T64 < (1ll << 31), "icrec_score_pairs: bad n_seqs/total_tokens (%d, %lld)", n_seqs, (long long)T64);
-    ICREC_REQUIRE(max_seqlen >= 1 && max_seqlen <= e->max_seqlen, "icrec_score_pairs: max_seqlen must be in [1, %d] (got %d)", e->max_seqlen, max_seqlen);
-    const int T = (int)T64;
-    const size_t need = icrec_score_pairs_workspace_bytes(h, T, n_seqs);
-    if (!ws || ws_bytes < need) {
-        set_error("icrec_score_pairs: workspace too small (%zu < %zu)", ws_bytes, need);
-        return ICREC_ENOMEM;
-    }
-    ICREC_HIP(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)stream;
-    char* base = reinterpret_cast<char*>(ws);
-    const icrec_bert_cfg& c = e->cfg;
-    const int H = c.hidden;
-    const bool x3 = c.gemm_mode == ICREC_GEMM_F16X3;
-    const EncWs w = enc_ws(c, T);
-    const EncBufs b(base, w, c, T);
-    const bool pruned = score_prunes(e) && n_seqs < T;  // (every token a first token: nothing to save)
-    const EncBufs cls(base + w.total, enc_ws(c, n_seqs, true), c, n_seqs);  // (inside the workspace only if score_prunes)
-    const int32_t* order = embed(e, b, ids_dev, cu_dev, seg_b_dev, n_seqs, T, st);
-    if (int rc_ = x3 ? encode_x3(e, b, pruned ? &cls : nullptr, cu_dev, n_seqs, T, max_seqlen, order, st)
-                     : encode_f32(e, b, cu_dev, n_seqs, T, max_seqlen, st))
+    LastRows last;
+    if (int rc_ = forward(e, "icrec_score_pairs", ids_dev, cu_dev, seg_b_dev, n_seqs, T64, max_seqlen, false, false, ws,
+                          ws_bytes, st, nullptr, &last))
         return rc_;
-    const EncBufs& last = pruned ? cls : b;
+    const int H = e->cfg.hidden;
+    const bool x3 = e->cfg.gemm_mode == ICREC_GEMM_F16X3;
     const float *const wpt = e->score_head, *const bp = wpt + (size_t)H * H, *const wc = bp + H, *const bc = wc + H;
     const auto kern =
         for_hidden(H, [x3](auto h) { return x3 ? score_head_kernel<h(), true> : score_head_kernel<h(), false>; });
     const int per_wg = H == HID_BASE ? HEAD_SEQS<HID_BASE> : HEAD_SEQS<HID>;
     hipLaunchKernelGGL(kern, dim3((n_seqs + per_wg - 1) / per_wg), dim3(384), 0, st, last.x, last.xh, last.xl, cu_dev,
-                       n_seqs, pruned, wpt, bp, wc, bc, scores_out_dev);
+                       n_seqs, last.compact, wpt, bp, wc, bc, scores_out_dev);
     ICREC_HIP(hipGetLastError());
     return ICREC_OK;
 }

@@ -1,6 +1,8 @@
 // encoder_x3.h — the linear layers of the encoder in f16x3 arithmetic (gemm_mode F16X3, the default) on the
 // weights-direct engine of wt_gemm.h: QKV projection, attention-output projection + residual + LayerNorm, the fused
-// FFN block, their small-batch forms, the packed-weight builder.  Included by encoder.hip only.
+// FFN block, their small-batch forms, the packed-weight builder.  Included by encoder.hip only (it defines
+// non-template __global__ functions: a second unit that included it would define them again); the attention between the
+// QKV projection and the attention-output projection is attention.hip's.
 //
 // Reference arithmetic: transformers/models/bert/modeling_bert.py (tf:) — BertSelfAttention.query/key/value tf:175-177,
 // BertSelfOutput tf:289-293, BertIntermediate tf:334-337 (erf-GELU), BertOutput tf:347-351.

@@ -40,7 +40,7 @@
  *   row reductions over d elems : 64 strided partial sums (lane l takes l, l+64, ...),
  *                                 then a butterfly (xor 32,16,8,4,2,1)
  *   attention P.V and softmax sum : the key order of the MFMA accumulator layout (see the
- *                                 attention block below and csrc/encoder.hip:attention_kernel)
+ *                                 attention block below and csrc/attention.hip:attention_kernel)
  * Ties in ranking: higher score first, then LOWER row index first (the
  * reference's torch.argsort(descending=True) is unstable on ties; this is the
  * build's own documented policy).

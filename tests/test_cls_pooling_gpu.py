@@ -183,6 +183,48 @@ def test_mean_encoder_is_untouched(monkeypatch, mode):
     never.close(); explicit.close()
 
 
+def test_encode_workspace_bound_is_exact(monkeypatch):
+    """icrec_encode_ex on a 2-layer hidden-384 f16x3 encoder, sequences of 5, 33 and 64 tokens, for a mean-pooled, a
+    CLS-pooled and a CLS-pooled ICREC_CLS_PRUNE=0 handle: exactly icrec_encode_workspace_bytes bytes are enough and give
+    the bits of a larger workspace, one byte less is ICREC_ENOMEM.  The pruned handle asks for more than the mean-pooled
+    one (its compact rows), the unpruned one for the same."""
+    import torch
+
+    from instacart_next_order_recommendation_amd import _native
+
+    L = _native.lib()
+    s = ts.shape(384, 2)
+    w = ts.weights("sharp", s)
+    ids, cu = packed([5, 33, 64], 3, ts.VOCAB)
+    n, T = cu.size - 1, int(cu[-1])
+    d_ids, d_cu = torch.from_numpy(ids).cuda(), torch.from_numpy(cu).cuda()
+    need = {}
+    for name, kw in (("mean", {}), ("cls", {"pooling": "cls"}), ("cls_full", {"pooling": "cls", "ICREC_CLS_PRUNE": 0})):
+        enc = make_encoder(monkeypatch, w, s, **kw)
+        need[name] = int(L.icrec_encode_workspace_bytes(enc._h, T, n))
+        assert need[name] > 0
+
+        def encode(ws, nbytes):
+            out = torch.zeros((n, s.hidden), dtype=torch.float32, device="cuda")
+            rc = L.icrec_encode_ex(enc._h, _native.ptr(d_ids), _native.ptr(d_cu), n, T, 64, _native.ptr(out), None,
+                                   _native.ptr(ws), nbytes, _native.stream_ptr(enc.device))
+            torch.cuda.synchronize()
+            return rc, out.cpu().numpy()
+
+        roomy = torch.zeros(2 * need[name] + 4096, dtype=torch.uint8, device="cuda")
+        rc, want = encode(roomy, roomy.numel())
+        assert rc == 0 and np.isfinite(want).all() and np.abs(want).max() > 0
+        exact = torch.zeros(need[name], dtype=torch.uint8, device="cuda")
+        rc, got = encode(exact, need[name])
+        assert rc == 0, L.icrec_last_error()
+        np.testing.assert_array_equal(got, want, err_msg=name)
+        rc, untouched = encode(exact, need[name] - 1)
+        assert rc == -3 and b"workspace" in L.icrec_last_error()  # ICREC_ENOMEM
+        assert not untouched.any()  # a refused call launches nothing
+        enc.close()
+    assert need["cls"] > need["mean"] == need["cls_full"]
+
+
 # ---------------------------------------------------------------- 5. poisoned workspace
 @pytest.mark.parametrize("shape", ["short_batch", "long_batch", "eight", "single"])
 @pytest.mark.parametrize("hidden", [384, 768])
