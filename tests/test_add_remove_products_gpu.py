@@ -1,20 +1,18 @@
-"""Recommender.add_products / remove_products end to end on the GPU, in the world of test_update_products_gpu: a synthetic
-2-layer model directory, a 700-product synthetic catalog with aisle / department facets, two product sets, and a second
-recommender with an IVF index.  After five products were added and seven removed, every kind of request answers exactly
-as a new recommender answers it that was built on a corpus file written in the edited recommender's row order."""
+"""Recommender.add_products / remove_products end to end on the GPU, on the default world of tests/recommender_harness.py:
+a synthetic 2-layer model directory, a 700-product synthetic catalog with aisle / department facets, two product sets,
+and a second recommender with an IVF index.  After five products were added and seven removed, every kind of request
+answers exactly as a new recommender answers it that was built on a corpus file written in the edited recommender's row
+order."""
 from __future__ import annotations
-
-import json
 
 import numpy as np
 import pytest
 import torch
 
 from instacart_next_order_recommendation_amd import synthetic as syn
-from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, text_facets
 from instacart_next_order_recommendation_amd.search import IvfIndex
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import graph_replays, no_gpu, synthetic_world, torch_cuda, write_corpus  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,12 +45,7 @@ def make_additions(corpus):
 @pytest.fixture(scope="module")
 def world(tmp_path_factory, torch_cuda):
     tmp = tmp_path_factory.mktemp("add_remove_products")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus = syn.synthetic_catalog(N)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(corpus))
+    model_dir, corpus_path, corpus = synthetic_world(tmp, N)
     additions = make_additions(corpus)
     queries = syn.synthetic_user_contexts(4, seed=9) + [
         f"[+1d w0h1] {name_of(corpus['100'])}.", "[+1d w0h1] Crimson Harvest Granola.",
@@ -65,9 +58,7 @@ def world(tmp_path_factory, torch_cuda):
     for r in (rec, ann):
         r.add_products(additions)
         r.remove_products(REMOVED)
-    edited_path = tmp / "edited" / "eval_corpus.json"
-    edited_path.parent.mkdir()
-    edited_path.write_text(json.dumps({pid: rec.pid_to_text[pid] for pid in rec.product_ids}))   # rec's row order
+    edited_path = write_corpus(tmp / "edited", {pid: rec.pid_to_text[pid] for pid in rec.product_ids})   # rec's row order
     fresh = MonitoredRecommender(model_dir, edited_path, use_index=False, product_sets=SETS)
     return {"rec": rec, "ann": ann, "fresh": fresh, "queries": queries, "additions": additions, "corpus": corpus,
             "before": before}
@@ -96,14 +87,7 @@ def test_host_state_follows(world):
 def test_requests_answer_as_a_new_recommender(world, monkeypatch):
     rec, fresh, queries, additions = world["rec"], world["fresh"], world["queries"], world["additions"]
     fast = rec._fast_path()
-    calls = []
-    real_run = type(fast).run
-
-    def run(self, *a, **kw):
-        calls.append(self)
-        return real_run(self, *a, **kw)
-
-    monkeypatch.setattr(type(fast), "run", run)
+    calls = graph_replays(rec, monkeypatch)
     got = [rec.recommend(q, 20) for q in queries]
     assert calls and all(c is fast for c in calls)                                        # the graph path, captured again
     assert got == [fresh.recommend(q, 20) for q in queries] and got != world["before"]
@@ -183,10 +167,6 @@ def test_a_bad_edit_changes_nothing(world, monkeypatch):
     answers = [rec.recommend(q, 20) for q in queries]
     ids, texts, aisles = list(rec.product_ids), list(rec.product_texts), list(rec.aisles)
     stored = rec._index.export().clone()
-
-    def no_gpu(*a, **kw):
-        raise AssertionError("GPU work before the argument check")
-
     monkeypatch.setattr(type(rec._index), "append_rows", no_gpu)
     monkeypatch.setattr(type(rec._index), "remove_rows", no_gpu)
     monkeypatch.setattr(type(rec.model), "encode", no_gpu)

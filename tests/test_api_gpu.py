@@ -7,23 +7,18 @@ from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
+from tests.recommender_harness import synthetic_world, torch_cuda  # noqa: F401  (torch_cuda: fixture)
+
 pytestmark = pytest.mark.gpu
 
 
-def test_concurrent_requests_equal_direct_calls(tmp_path, monkeypatch):
-    import torch
-
-    assert torch.cuda.is_available()
+def test_concurrent_requests_equal_direct_calls(tmp_path, monkeypatch, torch_cuda):
     from fastapi.testclient import TestClient
 
     from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd.api.app import app
-    from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 
-    model_dir = write_synthetic_model_dir(tmp_path / "model", seed=2)
-    corpus_path = tmp_path / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(500)))
+    model_dir, corpus_path, _ = synthetic_world(tmp_path, 500, model_seed=2, shape=None)
     (corpus_path.parent / "eval_queries.json").write_text(json.dumps({"7": syn.synthetic_user_contexts(1, seed=7)[0]}))
     monkeypatch.setenv("MODEL_DIR", str(model_dir))
     monkeypatch.setenv("CORPUS_PATH", str(corpus_path))

@@ -4,14 +4,13 @@ dispatch form, CLS pooling with a bias, the setter's semantics, poisoned workspa
 model directory served end to end."""
 from __future__ import annotations
 
-import json
-
 import numpy as np
 import pytest
 
 from tests import relative_bias as tb
 from tests import token_states as ts
 from tests.encoder_harness import FORMS, long_rounds_plus_remainder, make_encoder, packed, poisoned_runs, replay_matches_eager, run
+from tests.recommender_harness import synthetic_world
 
 pytestmark = pytest.mark.gpu
 
@@ -212,13 +211,11 @@ def e2e_reference(model_dir, product_texts, queries):
 
 def e2e_inputs(tmp_path):
     from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.model_io import synthetic_mpnet_vocab, write_synthetic_model_dir
+    from instacart_next_order_recommendation_amd.model_io import synthetic_mpnet_vocab
 
     shape = syn.BertShape(vocab_size=len(synthetic_mpnet_vocab()), layers=2, type_vocab=1, ln_eps=1e-5, **ts.WIDTHS[768])
-    model_dir = write_synthetic_model_dir(tmp_path / "mpnet", seed=E2E_SEEDS["model"], shape=shape, architecture="mpnet")
-    corpus_path = tmp_path / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(300, seed=E2E_SEEDS["catalog"])))
+    model_dir, corpus_path, _ = synthetic_world(tmp_path, 300, model_seed=E2E_SEEDS["model"], shape=shape,
+                                                catalog_seed=E2E_SEEDS["catalog"], architecture="mpnet")
     queries = syn.synthetic_user_contexts(5, seed=E2E_SEEDS["queries"]) + ["[+1d w0h1] Milk."]
     return model_dir, corpus_path, queries
 

@@ -4,13 +4,12 @@ bert-base-nli-mean-tokens): both GEMM modes against the oracle, every f16x3 form
 Recommender end to end on a 768-wide model directory."""
 from __future__ import annotations
 
-import json
-
 import numpy as np
 import pytest
 
 from oracle import oracle
 from tests.encoder_harness import EMB_TOL, make_encoder, n_cu, oracle_rows, packed, poisoned_runs, round_plus_remainder, run
+from tests.recommender_harness import QUERIES, synthetic_world, two_layer_shape
 
 pytestmark = pytest.mark.gpu
 
@@ -129,18 +128,14 @@ def test_recommender_end_to_end(tmp_path, monkeypatch):
     """A synthetic 768-wide model directory and a 700-product catalog through Recommender: (700, 768) embeddings,
     recommend() on the graph path == the plain batch path, and the top-20 ids those of the oracle pipeline up to its
     first near-tie (adjacent oracle scores within 1e-5)."""
-    from instacart_next_order_recommendation_amd import synthetic as syn
+    from dataclasses import replace
+
     from instacart_next_order_recommendation_amd.encoder import pack_token_ids
-    from instacart_next_order_recommendation_amd.model_io import load_model_dir, write_synthetic_model_dir
+    from instacart_next_order_recommendation_amd.model_io import load_model_dir
     from instacart_next_order_recommendation_amd.recommender import Recommender
 
-    vocab = len(syn.synthetic_vocab())
-    shape = syn.BertShape(vocab_size=vocab, hidden=768, heads=12, intermediate=3072, layers=2)
-    model_dir = write_synthetic_model_dir(tmp_path / "model", seed=3, shape=shape)
-    corpus = syn.synthetic_catalog(700)
-    corpus_path = tmp_path / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(corpus))
+    shape = replace(two_layer_shape(), hidden=768, heads=12, intermediate=3072)
+    model_dir, corpus_path, _ = synthetic_world(tmp_path, shape=shape)
     rec = Recommender(model_dir, corpus_path)
     assert rec.model.shape.hidden == 768
     assert rec.product_embeddings.shape == (700, 768) and rec.product_embeddings.dtype == np.float32
@@ -152,8 +147,7 @@ def test_recommender_end_to_end(tmp_path, monkeypatch):
     P = oracle.encode(loaded.weights, cfg, pids, cu_p)
     assert np.abs(rec.product_embeddings - P).max() < EMB_TOL
 
-    queries = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
-    for q in queries:
+    for q in QUERIES:
         got = rec.recommend(q, 20, None)
         assert got == rec.recommend_batch([q], 20, [None])[0]  # graph path == plain path, bit for bit
         ids, cu, _ = pack_token_ids(rec.model.tokenizer([q]))

@@ -1,5 +1,5 @@
-"""Recommender.recommend(..., boosts=, boost_weight=, only_boosted=) end to end on the GPU, on the synthetic 2-layer
-model directory and 700-product catalog of the MMR recommender test: a boosted request equals tests/boost_reference.py's
+"""Recommender.recommend(..., boosts=, boost_weight=, only_boosted=) end to end on the GPU, on the default world of
+tests/recommender_harness.py (2-layer model directory, 700 products): a boosted request equals tests/boost_reference.py's
 full-catalog form applied to `product_embeddings`, bit for bit; no boosts is today's request on the graph path; and the
 content-based baseline's boosted ranking on tests/golden/cf_small equals the reference on the baseline's own
 embeddings."""
@@ -11,31 +11,23 @@ import math
 import numpy as np
 import pytest
 
-from instacart_next_order_recommendation_amd import synthetic as syn
 from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender
 from tests import boost_reference as ref
 from tests import mmr_reference
 from tests.cf_cases import FIXTURE
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import (QUERIES, as_results, assert_batch_equals_single_calls, forbid_gpu_work, graph_replays,
+                                       synthetic_world, torch_cuda)  # noqa: F401  (torch_cuda: fixture)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def rec(tmp_path_factory, torch_cuda):
-    tmp = tmp_path_factory.mktemp("boost_rec")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(700)))
-    r = MonitoredRecommender(model_dir, corpus_path, use_index=False)
+    w = synthetic_world(tmp_path_factory.mktemp("boost_rec"))
+    r = MonitoredRecommender(w.model_dir, w.corpus_path, use_index=False)
     assert r._fast is not None and r._index.n_facets == 2
     return r
-
-
-QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
 
 
 @pytest.fixture(scope="module")
@@ -78,7 +70,7 @@ def expected(rec, scores, i, b, top_k, exclude=(), department=None, only=False, 
     if department is not None:
         admit = np.asarray([[t.endswith(f". Department: {department}.") for t in rec.product_texts]], bool)
     idx, sc = ref.full_catalog(scores[i:i + 1], [as_list(rec, b, weight)], top_k, excl, admit, only)
-    return [(rec.product_ids[int(r)], float(s)) for r, s in zip(idx[0], sc[0]) if r >= 0]
+    return as_results(rec, idx[0], sc[0])
 
 
 def test_boosted_request_equals_the_reference(rec, scores, boosts):
@@ -97,15 +89,7 @@ def test_boosted_request_equals_the_reference(rec, scores, boosts):
 
 
 def test_no_boosts_is_the_plain_request_on_the_graph_path(rec, boosts, monkeypatch):
-    fast = rec._fast_path()
-    calls = []
-    real_run = type(fast).run
-
-    def run(self, *a, **kw):
-        calls.append(1)
-        return real_run(self, *a, **kw)
-
-    monkeypatch.setattr(type(fast), "run", run)
+    calls = graph_replays(rec, monkeypatch)
     for q in QUERIES:
         plain = rec.recommend(q, 20)
         assert rec.recommend(q, 20, boosts=None) == plain
@@ -151,7 +135,7 @@ def test_composes_with_departments_exclusions_and_diversity(rec, scores, boosts)
         cand = np.asarray([[rec._pid_to_row[p] for p, _ in wide]], np.int64)
         rel = np.asarray([[s for _, s in wide]], np.float32)
         idx, out = mmr_reference.mmr_select(p_hat, cand, rel, 10, 0.5)
-        want = [(rec.product_ids[int(r)], float(s)) for r, s in zip(idx[0], out[0]) if r >= 0]
+        want = as_results(rec, idx[0], out[0])
         assert rec.recommend(q, 10, exclude_product_ids=drop, boosts=boosts[i], diversity=0.5) == want
         reordered += want != wide[:10]
     assert reordered > 0  # the re-selection changes lists
@@ -162,19 +146,12 @@ def test_batch_equals_single_calls(rec, boosts):
     excl = [None, {"1", "2", "3"}, None, {"10"}, None]
     departments = [None, None, [rec.departments[1]], None, [rec.departments[0], rec.departments[2]]]
     per_query = [boosts[0], None, boosts[2], {}, boosts[4]]
-    batch = rec.recommend_batch(QUERIES, 20, excl, departments=departments, boosts=per_query)
-    for i, q in enumerate(QUERIES):
-        assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], departments=departments[i], boosts=per_query[i]), i
+    batch = assert_batch_equals_single_calls(rec, QUERIES, 20, excl, departments=departments, boosts=per_query)
     assert batch != rec.recommend_batch(QUERIES, 20, excl, departments=departments)
     ids = [list(b) if b else b for b in per_query]
-    batch = rec.recommend_batch(QUERIES, 20, excl, boosts=ids, boost_weight=0.2, only_boosted=True, diversity=0.4, candidates=70)
-    for i, q in enumerate(QUERIES):
-        assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], boosts=ids[i], boost_weight=0.2,
-                                         only_boosted=True, diversity=0.4, candidates=70), i
+    batch = assert_batch_equals_single_calls(rec, QUERIES, 20, excl, boosts=ids, boost_weight=0.2, only_boosted=True,
+                                             diversity=0.4, candidates=70)
     assert batch[1] == [] and batch[3] == [] and len(batch[0]) == 20
-    timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 20, excl, departments=departments, boosts=per_query)
-    assert timed == rec.recommend_batch(QUERIES, 20, excl, departments=departments, boosts=per_query)
-    assert enc_ms > 0 and sim_ms > 0
 
 
 def test_monitored_fills_last_metrics(rec, boosts):
@@ -186,11 +163,7 @@ def test_monitored_fills_last_metrics(rec, boosts):
 
 
 def test_bad_arguments_raise_before_any_gpu_work(rec, monkeypatch):
-    def no_gpu(*a, **kw):
-        raise AssertionError("GPU work before the argument check")
-
-    monkeypatch.setattr(rec, "_encode_search", no_gpu)
-    monkeypatch.setattr(type(rec._fast_path()), "run", no_gpu)
+    forbid_gpu_work(rec, monkeypatch)
     for bad in (math.nan, -0.1, "x"):
         with pytest.raises(ValueError, match=">= 0"):
             rec.recommend(QUERIES[0], 20, boosts={"1": bad})

@@ -1,38 +1,27 @@
-"""Recommender.recommend(..., max_per_aisle=, max_per_department=) end to end on the GPU, on the synthetic 2-layer model
-directory and 700-product catalog of the MMR recommender test: a capped request equals the one-pass capped walk of the
-COMPLETE plain ranking (taken through the plain request itself, 128 products at a time), a batch equals the single
+"""Recommender.recommend(..., max_per_aisle=, max_per_department=) end to end on the GPU, on the default world of
+tests/recommender_harness.py (2-layer model directory, 700 products): a capped request equals the one-pass capped walk of
+the COMPLETE plain ranking (taken through the plain request itself, 128 products at a time), a batch equals the single
 requests, no caps is today's request on the graph path, and with diversity the result is tests/mmr_reference.py
 applied to the capped candidate pool."""
 from __future__ import annotations
 
-import json
-
 import numpy as np
 import pytest
 
-from instacart_next_order_recommendation_amd import synthetic as syn
-from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, catalog_facets
 from tests import mmr_reference
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import (QUERIES, as_results, assert_batch_equals_single_calls, forbid_gpu_work, graph_replays,
+                                       synthetic_world, torch_cuda)  # noqa: F401  (torch_cuda: fixture)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def rec(tmp_path_factory, torch_cuda):
-    tmp = tmp_path_factory.mktemp("cap_rec")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(700)))
-    r = MonitoredRecommender(model_dir, corpus_path, use_index=False)
+    w = synthetic_world(tmp_path_factory.mktemp("cap_rec"))
+    r = MonitoredRecommender(w.model_dir, w.corpus_path, use_index=False)
     assert r._fast is not None and r._index.n_facets == 2
     return r
-
-
-QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
 
 
 @pytest.fixture(scope="module")
@@ -102,24 +91,12 @@ def test_batch_equals_single_calls(rec, codes):
     excl = [None, {"1", "2", "3"}, None, {"10"}, None]
     departments = [None, None, rec.departments[:6], None, [rec.departments[0], rec.departments[2]]]
     for kw in (dict(max_per_aisle=1, candidates=20), dict(max_per_aisle=2, max_per_department=3)):
-        batch = rec.recommend_batch(QUERIES, 20, excl, departments=departments, **kw)
-        for i, q in enumerate(QUERIES):
-            assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], departments=departments[i], **kw), i
-            respects(batch[i], codes, (kw.get("max_per_aisle"), kw.get("max_per_department")))
-        timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 20, excl, departments=departments, **kw)
-        assert timed == batch and enc_ms > 0 and sim_ms > 0
+        for row in assert_batch_equals_single_calls(rec, QUERIES, 20, excl, departments=departments, **kw):
+            respects(row, codes, (kw.get("max_per_aisle"), kw.get("max_per_department")))
 
 
 def test_no_caps_is_the_plain_request_on_the_graph_path(rec, monkeypatch):
-    fast = rec._fast_path()
-    calls = []
-    real_run = type(fast).run
-
-    def run(self, *a, **kw):
-        calls.append(1)
-        return real_run(self, *a, **kw)
-
-    monkeypatch.setattr(type(fast), "run", run)
+    calls = graph_replays(rec, monkeypatch)
     for q in QUERIES:
         assert rec.recommend(q, 20, max_per_aisle=None, max_per_department=None) == rec.recommend(q, 20)
     assert len(calls) == 2 * len(QUERIES)
@@ -136,9 +113,8 @@ def test_with_diversity_mmr_picks_from_the_capped_pool(rec, codes, rankings):
             cand = np.asarray([[rec._pid_to_row[p] for p, _ in pool]], np.int64)
             rel = np.asarray([[s for _, s in pool]], np.float32)
             idx, out = mmr_reference.mmr_select(p_hat, cand, rel, min(20, len(pool)), 0.5)
-            want = [(rec.product_ids[int(i)], float(s)) for i, s in zip(idx[0], out[0]) if i >= 0]
             got = rec.recommend(q, 20, diversity=0.5, candidates=80, **kw)
-            assert got == want and got
+            assert got == as_results(rec, idx[0], out[0]) and got
             respects(got, codes, caps)
 
 
@@ -154,11 +130,7 @@ def test_boosted_and_capped(rec, codes, rankings):
 
 
 def test_bad_arguments_raise_before_any_gpu_work(rec, monkeypatch):
-    def no_gpu(*a, **kw):
-        raise AssertionError("GPU work before the argument check")
-
-    monkeypatch.setattr(rec, "_encode_search", no_gpu)
-    monkeypatch.setattr(type(rec._fast_path()), "run", no_gpu)
+    forbid_gpu_work(rec, monkeypatch)
     for bad in (0, -2, 1.5, "3", True):
         with pytest.raises(ValueError, match="max_per_aisle"):
             rec.recommend(QUERIES[0], 20, max_per_aisle=bad)

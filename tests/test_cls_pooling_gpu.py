@@ -5,7 +5,6 @@ poisoned workspaces, the ABI's refusals, and a BGE-shaped model directory served
 from __future__ import annotations
 
 import ctypes as C
-import json
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ from tests import cls_pooling as cp
 from tests import token_states as ts
 from tests.encoder_harness import (EMB_TOL, FORMS, long_rounds_plus_remainder, make_encoder, packed, poisoned_runs,
                                    replay_matches_eager, run)
+from tests.recommender_harness import synthetic_world
 
 pytestmark = pytest.mark.gpu
 
@@ -289,14 +289,11 @@ def test_bge_shaped_model_dir_through_recommender(tmp_path):
 
     from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd.encoder import pack_token_ids
-    from instacart_next_order_recommendation_amd.model_io import load_model_dir, write_synthetic_model_dir
+    from instacart_next_order_recommendation_amd.model_io import load_model_dir
     from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, Recommender
 
     shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=12)
-    model_dir = write_synthetic_model_dir(tmp_path / "bge", seed=8, shape=shape, pooling="cls")
-    corpus_path = tmp_path / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(300)))
+    model_dir, corpus_path, _ = synthetic_world(tmp_path, 300, model_seed=8, shape=shape, pooling="cls")
     queries = syn.synthetic_user_contexts(5, seed=9) + ["[+1d w0h1] Milk."]
     excl = [set(), {"1", "2"}, None, {"no-such-id"}, set(str(i) for i in range(1, 40)), set()]
 

@@ -1,33 +1,25 @@
-"""Recommender.recommend(..., aisles=, departments=) end to end on the GPU: a synthetic 2-layer model directory and a
-700-product synthetic catalog.  A faceted request equals, bit for bit, the request that excludes every other product."""
+"""Recommender.recommend(..., aisles=, departments=) end to end on the GPU, on the default world of
+tests/recommender_harness.py: a synthetic 2-layer model directory and a 700-product synthetic catalog.  A faceted request
+equals, bit for bit, the request that excludes every other product."""
 from __future__ import annotations
 
 import json
 
 import pytest
 
-from instacart_next_order_recommendation_amd import synthetic as syn
-from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, catalog_facets
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import (QUERIES, assert_batch_equals_single_calls, graph_replays, synthetic_world,  # noqa: F401
+                                       torch_cuda)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def rec(tmp_path_factory, torch_cuda):
-    tmp = tmp_path_factory.mktemp("facet_rec")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(700)))
-    r = MonitoredRecommender(model_dir, corpus_path, use_index=False)
+    w = synthetic_world(tmp_path_factory.mktemp("facet_rec"))
+    r = MonitoredRecommender(w.model_dir, w.corpus_path, use_index=False)
     assert r._fast is not None and r._index.n_facets == 2
     return r
-
-
-QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
 
 
 def others(rec, aisles=None, departments=None):
@@ -78,13 +70,9 @@ def test_batch_equals_single_calls(rec):
     aisles = [[a], None, [a, a2], None, []]
     departments = [None, [d], [d, d2], None, None]
     excl = [None, None, {"1", "2", "3"}, {"10"}, None]
-    batch = rec.recommend_batch(QUERIES, 20, excl, aisles=aisles, departments=departments)
-    for i, q in enumerate(QUERIES):
-        assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], aisles=aisles[i], departments=departments[i]), i
+    batch = assert_batch_equals_single_calls(rec, QUERIES, 20, excl, aisles=aisles, departments=departments)
     assert batch[4] == []
     assert batch[3] == rec.recommend(QUERIES[3], 20, exclude_product_ids={"10"})
-    timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 20, excl, aisles=aisles, departments=departments)
-    assert timed == batch and enc_ms > 0 and sim_ms > 0
 
 
 def test_monitored_fills_last_metrics(rec):
@@ -99,15 +87,7 @@ def test_monitored_fills_last_metrics(rec):
 def test_unfiltered_requests_stay_on_the_graph_path(rec, monkeypatch):
     """recommend() without a facet argument replays the captured graph as before (SingleRequestPath.run is called) and
     returns what the plain batch path returns; a faceted request does not go through it."""
-    fast = rec._fast_path()
-    calls = []
-    real_run = type(fast).run
-
-    def run(self, *a, **kw):
-        calls.append(1)
-        return real_run(self, *a, **kw)
-
-    monkeypatch.setattr(type(fast), "run", run)
+    calls = graph_replays(rec, monkeypatch)
     for q in QUERIES:
         assert rec.recommend(q, 20) == rec.recommend_batch([q], 20, [None])[0]
     assert len(calls) == len(QUERIES)

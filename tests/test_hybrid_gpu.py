@@ -5,7 +5,6 @@ catalog of 300 with seeded baskets against the reference's fusion of DeviceIndex
 add_products / update_products.  Both tests assert, on the reference's positions, that their data exercises the merge."""
 from __future__ import annotations
 
-import json
 import random
 
 import numpy as np
@@ -19,13 +18,10 @@ from instacart_next_order_recommendation_amd.recommender import Recommender
 from instacart_next_order_recommendation_amd.search import rrf_weights
 from tests import fuse_reference as ref
 from tests.cf_cases import FIXTURE, numpy_rank
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import (as_results, assert_batch_equals_single_calls, synthetic_world, torch_cuda,  # noqa: F401
+                                       two_layer_shape)
 
 pytestmark = pytest.mark.gpu
-
-
-def two_layer_model(path, seed):
-    return write_synthetic_model_dir(path, seed=seed, shape=syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2))
 
 
 def assert_merge_is_exercised(pos, idx, n_queries):
@@ -41,7 +37,7 @@ def assert_merge_is_exercised(pos, idx, n_queries):
 # ---------------------------------------------------------------- HybridBaseline
 def test_hybrid_baseline_on_the_cf_fixture(tmp_path, torch_cuda):
     queries, corpus, relevant = load_eval_data(FIXTURE / "processed")
-    cb = ContentBasedBaseline(queries, corpus, two_layer_model(tmp_path / "m", 6))
+    cb = ContentBasedBaseline(queries, corpus, write_synthetic_model_dir(tmp_path / "m", seed=6, shape=two_layer_shape()))
     cf = ItemItemCFBaseline(FIXTURE / "data", FIXTURE / "processed")
     n = len(cb.product_ids)
     assert n == 60 and len(queries) >= 30
@@ -102,15 +98,11 @@ def seeded_histories(ids):
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory, torch_cuda):
-    tmp = tmp_path_factory.mktemp("hybrid_rec")
-    corpus = syn.synthetic_catalog(N_PRODUCTS)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(corpus))
+    model_dir, corpus_path, corpus = synthetic_world(tmp_path_factory.mktemp("hybrid_rec"), N_PRODUCTS)
     ids = list(corpus)
     baskets = seeded_baskets(ids)
     cf = ItemItemCFBaseline.from_arrays(baskets, {}, ids)
-    rec = Recommender(two_layer_model(tmp / "model", 3), corpus_path, use_index=False, cf=cf)
+    rec = Recommender(model_dir, corpus_path, use_index=False, cf=cf)
     item_baskets = [[rec._pid_to_row[p] for p in b] for b in baskets]
     return rec, item_baskets, seeded_histories(ids)
 
@@ -126,7 +118,7 @@ def expected(rec, item_baskets, queries, histories, top_k, exclude=None, w=None,
     ranked = numpy_rank(item_baskets, items, n_cf, w)
     b, b_sc = np.asarray([r for r, _ in ranked], np.int64), np.asarray([s for _, s in ranked], np.int32)
     idx, sc, pos = ref.fuse_select(a, b, rrf_weights(w, rrf_c), rrf_weights(w, rrf_c, cf_weight), top_k, n, b_gate=b_sc, exclude=ex)
-    return [[(rec.product_ids[int(r)], float(s)) for r, s in zip(idx[i], sc[i]) if r >= 0] for i in range(len(queries))], pos, idx
+    return [as_results(rec, idx[i], sc[i]) for i in range(len(queries))], pos, idx
 
 
 def test_recommend_with_history_equals_the_reference(world):
@@ -152,12 +144,8 @@ def test_recommend_with_history_equals_the_reference(world):
 def test_batch_rows_equal_the_single_requests(world):
     rec, baskets, histories = world
     excl = [None, {"1", "2", "3"}, None, {"10"}, None, None, set(histories[6]), None]
-    batch = rec.recommend_batch(QUERIES, 10, excl, history=histories)
-    for i, q in enumerate(QUERIES):
-        assert batch[i] == rec.recommend(q, 10, exclude_product_ids=excl[i], history=histories[i]), i
+    batch = assert_batch_equals_single_calls(rec, QUERIES, 10, excl, history=histories)
     assert batch == expected(rec, baskets, QUERIES, histories, 10, exclude=excl)[0]
-    timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 10, excl, history=histories)
-    assert timed == batch and enc_ms > 0 and sim_ms > 0
     # in a batch that fuses, a None entry counts as []
     some, same = [histories[0], None, histories[2]], [histories[0], [], histories[2]]
     assert rec.recommend_batch(QUERIES[:3], 10, history=some) == rec.recommend_batch(QUERIES[:3], 10, history=same)

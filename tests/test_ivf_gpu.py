@@ -3,18 +3,16 @@ bit, at the edges of the 256-row tiles and of the slices a list is cut into; gra
 Recommender(ann_lists=...)."""
 from __future__ import annotations
 
-import json
-
 import numpy as np
 import pytest
 import torch
 
 from instacart_next_order_recommendation_amd import synthetic as syn
-from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, diversity_plan
 from instacart_next_order_recommendation_amd.search import DeviceIndex, IvfIndex, train_centroids
 from oracle import oracle
 from tests import ivf_reference as ref
+from tests.recommender_harness import QUERIES, as_results, graph_replays, synthetic_world
 from tests.search_harness import (assert_search, distinct_exclusions, n_cu, tie_block_catalog,  # noqa: F401
                                   torch_cuda)
 
@@ -229,33 +227,17 @@ N_LISTS = 16
 
 @pytest.fixture(scope="module")
 def rec(tmp_path_factory, torch_cuda):
-    tmp = tmp_path_factory.mktemp("ivf_rec")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(700)))
-    r = MonitoredRecommender(model_dir, corpus_path, use_index=False, ann_lists=N_LISTS)
+    w = synthetic_world(tmp_path_factory.mktemp("ivf_rec"))
+    r = MonitoredRecommender(w.model_dir, w.corpus_path, use_index=False, ann_lists=N_LISTS)
     assert r._fast is not None and r._ann.n_lists == N_LISTS
     return r
-
-
-QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
 
 
 def test_recommend_with_probes(rec, monkeypatch):
     perm, off = (t.cpu().numpy() for t in rec._ann.layout())
     list_of = np.empty(700, np.int64)
     list_of[perm] = np.repeat(np.arange(N_LISTS), np.diff(off))
-    fast = rec._fast_path()
-    calls = []
-    real_run = type(fast).run
-
-    def run(self, *a, **kw):
-        calls.append(1)
-        return real_run(self, *a, **kw)
-
-    monkeypatch.setattr(type(fast), "run", run)
+    calls = graph_replays(rec, monkeypatch)
     for q in QUERIES:
         plain = rec.recommend(q, 20)
         calls.clear()
@@ -270,8 +252,7 @@ def test_recommend_with_probes(rec, monkeypatch):
         lam, width = diversity_plan(0.5, None, 20, 700)
         emb = torch.from_numpy(rec.model.encode([q])).to(rec.device)
         idx, sc = rec._index.mmr_select(*rec._ann.search(emb, width, 4), 20, lam)
-        want = rec._to_results(idx[0].cpu().numpy(), sc[0].cpu().numpy())
-        assert rec.recommend(q, 20, diversity=0.5, probes=4) == want
+        assert rec.recommend(q, 20, diversity=0.5, probes=4) == as_results(rec, idx[0].cpu().numpy(), sc[0].cpu().numpy())
     assert rec.recommend_batch(QUERIES, 20, probes=N_LISTS) == rec.recommend_batch(QUERIES, 20)
     assert rec.recommend_batch(QUERIES, 20, probes=2) == [rec.recommend(q, 20, probes=2) for q in QUERIES]
     with pytest.raises(ValueError, match="aisles"):

@@ -1,32 +1,25 @@
-"""Recommender.recommend(..., diversity=, candidates=) end to end on the GPU, on the synthetic 2-layer model directory
-and 700-product catalog of the facet recommender test: a diversified request equals tests/mmr_reference.py applied to
-the `candidates`-wide plain result, bit for bit, and diversity None / 0 is today's request."""
+"""Recommender.recommend(..., diversity=, candidates=) end to end on the GPU, on the default world of
+tests/recommender_harness.py (2-layer model directory, 700 products): a diversified request equals tests/mmr_reference.py
+applied to the `candidates`-wide plain result, bit for bit, and diversity None / 0 is today's request."""
 from __future__ import annotations
 
-import json
 import math
 
 import numpy as np
 import pytest
 
-from instacart_next_order_recommendation_amd import synthetic as syn
-from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender
 from tests import mmr_reference as ref
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import (QUERIES, as_results, assert_batch_equals_single_calls, forbid_gpu_work, graph_replays,
+                                       synthetic_world, torch_cuda)  # noqa: F401  (torch_cuda: fixture)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def rec(tmp_path_factory, torch_cuda):
-    tmp = tmp_path_factory.mktemp("mmr_rec")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(700)))
-    r = MonitoredRecommender(model_dir, corpus_path, use_index=False)
+    w = synthetic_world(tmp_path_factory.mktemp("mmr_rec"))
+    r = MonitoredRecommender(w.model_dir, w.corpus_path, use_index=False)
     assert r._fast is not None and r._index.n_facets == 2
     return r
 
@@ -36,27 +29,16 @@ def p_hat(rec):
     return ref.stored_rows(rec.product_embeddings, rec._index.storage)
 
 
-QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
-
-
 def expected(rec, p_hat, wide, top_k, lam):
     """The reference's re-selection of a plain (product id, score) result."""
     cand = np.asarray([[rec._pid_to_row[p] for p, _ in wide]], np.int64)
     rel = np.asarray([[s for _, s in wide]], np.float32)  # (a float32 score survives the trip through a Python float)
     idx, out = ref.mmr_select(p_hat, cand, rel, top_k, lam)
-    return [(rec.product_ids[int(i)], float(s)) for i, s in zip(idx[0], out[0]) if i >= 0]
+    return as_results(rec, idx[0], out[0])
 
 
 def test_no_diversity_is_the_plain_request_on_the_graph_path(rec, monkeypatch):
-    fast = rec._fast_path()
-    calls = []
-    real_run = type(fast).run
-
-    def run(self, *a, **kw):
-        calls.append(1)
-        return real_run(self, *a, **kw)
-
-    monkeypatch.setattr(type(fast), "run", run)
+    calls = graph_replays(rec, monkeypatch)
     for q in QUERIES:
         plain = rec.recommend(q, 20)
         assert rec.recommend(q, 20, diversity=None) == plain
@@ -98,13 +80,8 @@ def test_composes_with_departments_and_exclusions(rec, p_hat):
 def test_batch_equals_single_calls(rec):
     excl = [None, {"1", "2", "3"}, None, {"10"}, None]
     departments = [None, None, [rec.departments[1]], None, [rec.departments[0], rec.departments[2]]]
-    batch = rec.recommend_batch(QUERIES, 20, excl, departments=departments, diversity=0.4, candidates=70)
-    for i, q in enumerate(QUERIES):
-        assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], departments=departments[i], diversity=0.4,
-                                         candidates=70), i
+    batch = assert_batch_equals_single_calls(rec, QUERIES, 20, excl, departments=departments, diversity=0.4, candidates=70)
     assert batch != rec.recommend_batch(QUERIES, 20, excl, departments=departments)
-    timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 20, excl, departments=departments, diversity=0.4, candidates=70)
-    assert timed == batch and enc_ms > 0 and sim_ms > 0
 
 
 def test_monitored_fills_last_metrics(rec):
@@ -116,11 +93,7 @@ def test_monitored_fills_last_metrics(rec):
 
 
 def test_bad_arguments_raise_before_any_gpu_work(rec, monkeypatch):
-    def no_gpu(*a, **kw):
-        raise AssertionError("GPU work before the argument check")
-
-    monkeypatch.setattr(rec, "_encode_search", no_gpu)
-    monkeypatch.setattr(type(rec._fast_path()), "run", no_gpu)
+    forbid_gpu_work(rec, monkeypatch)
     for bad in (-0.1, 1.5, math.nan):
         with pytest.raises(ValueError, match="diversity"):
             rec.recommend(QUERIES[0], 20, diversity=bad)

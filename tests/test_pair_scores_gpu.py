@@ -5,13 +5,13 @@ poisoned workspaces, graph capture, the ABI's refusals, and a reranked recommend
 from __future__ import annotations
 
 import ctypes as C
-import json
 
 import numpy as np
 import pytest
 
 from tests import pair_reference as pr
 from tests.encoder_harness import FORMS, make_encoder, run
+from tests.recommender_harness import synthetic_world
 
 pytestmark = pytest.mark.gpu
 
@@ -240,18 +240,13 @@ def test_reranked_recommender_end_to_end(tmp_path):
 
     from instacart_next_order_recommendation_amd import synthetic as syn
     from instacart_next_order_recommendation_amd.model_io import (assemble_pairs, load_cross_encoder_dir,
-                                                                  write_synthetic_cross_encoder_dir, write_synthetic_model_dir)
+                                                                  write_synthetic_cross_encoder_dir)
     from instacart_next_order_recommendation_amd.recommender import Recommender
     from instacart_next_order_recommendation_amd.reranker import CrossEncoderReranker, RerankedRecommender
 
-    n_vocab = len(syn.synthetic_vocab())
-    bi_dir = write_synthetic_model_dir(tmp_path / "bi", seed=8, shape=syn.BertShape(vocab_size=n_vocab, layers=2))
-    ce_shape = syn.BertShape(vocab_size=n_vocab, layers=2, n_normalize=0)
+    bi_dir, corpus_path, catalog = synthetic_world(tmp_path, 300, model_seed=8)
+    ce_shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2, n_normalize=0)
     ce_dir = write_synthetic_cross_encoder_dir(tmp_path / "ce", seed=9, shape=ce_shape, activation="identity")
-    corpus_path = tmp_path / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    catalog = syn.synthetic_catalog(300)
-    corpus_path.write_text(json.dumps(catalog))
     rec = Recommender(bi_dir, corpus_path)
     rr = CrossEncoderReranker(ce_dir)
     assert rr.activation == "identity" and rr.encoder.has_score_head and rr.encoder.gemm_mode == "f16x3"

@@ -3,39 +3,35 @@ oracle run on the same token ids; EmbeddingIndex build / reuse; MonitoredRecomme
 from __future__ import annotations
 
 import json
+import logging
 
 import numpy as np
 import pytest
+import torch
+import yaml
+
+from instacart_next_order_recommendation_amd import cli
+from instacart_next_order_recommendation_amd import synthetic as syn
+from instacart_next_order_recommendation_amd._native import IcrecError
+from instacart_next_order_recommendation_amd.encoder import DeviceEncoder, pack_token_ids
+from instacart_next_order_recommendation_amd.model_io import load_model_dir
+from instacart_next_order_recommendation_amd.recommender import EmbeddingIndex, MonitoredRecommender, Recommender
+from oracle import oracle
+from tests.recommender_harness import synthetic_world, torch_cuda  # noqa: F401  (torch_cuda: fixture)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def world(tmp_path_factory):
-    import torch
-
-    assert torch.cuda.is_available()
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
-
-    root = tmp_path_factory.mktemp("rec")
-    model_dir = write_synthetic_model_dir(root / "model", seed=1)
-    corpus = syn.synthetic_catalog(700)
-    corpus_path = root / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(corpus))
-    return {"model_dir": model_dir, "corpus_path": corpus_path, "corpus": corpus,
-            "queries": syn.synthetic_user_contexts(6, seed=9)}
+def world(tmp_path_factory, torch_cuda):
+    """The MiniLM-shaped (6-layer) model directory of seed 1, 700 products and six contexts."""
+    w = synthetic_world(tmp_path_factory.mktemp("rec"), model_seed=1, shape=None)
+    return {**w._asdict(), "queries": syn.synthetic_user_contexts(6, seed=9)}
 
 
 def _oracle_pipeline(rec, queries, k, excl_pids):
     """The reference's recommend() restated with the oracle on the recommender's own token ids."""
-    from oracle import oracle
-
     cfg = oracle.cfg_for(rec.model.shape)
-    from instacart_next_order_recommendation_amd.encoder import pack_token_ids
-    from instacart_next_order_recommendation_amd.model_io import load_model_dir
-
     w = load_model_dir(rec.model_dir).weights
     ids, cu, _ = pack_token_ids(rec.model.tokenizer(queries))
     q_emb = oracle.encode(w, cfg, ids, cu)
@@ -48,8 +44,6 @@ def _oracle_pipeline(rec, queries, k, excl_pids):
 
 
 def test_recommender_end_to_end(world):
-    from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, Recommender
-
     rec = Recommender(world["model_dir"], world["corpus_path"])
     assert rec.product_ids == list(world["corpus"].keys())
     assert rec.pid_to_text["1"] == world["corpus"]["1"]
@@ -90,8 +84,6 @@ def test_recommender_end_to_end(world):
 
 
 def test_use_index_false_and_stale_cache(world, tmp_path):
-    from instacart_next_order_recommendation_amd.recommender import EmbeddingIndex, Recommender
-
     corpus_path = tmp_path / "eval_corpus.json"
     small = dict(list(world["corpus"].items())[:40])
     corpus_path.write_text(json.dumps(small))
@@ -105,9 +97,6 @@ def test_use_index_false_and_stale_cache(world, tmp_path):
 
 
 def test_inference_device_env(world, monkeypatch):
-    from instacart_next_order_recommendation_amd._native import IcrecError
-    from instacart_next_order_recommendation_amd.recommender import Recommender
-
     monkeypatch.setenv("INFERENCE_DEVICE", "cpu")
     with pytest.raises(IcrecError):
         Recommender(world["model_dir"], world["corpus_path"])
@@ -118,9 +107,6 @@ def test_inference_device_env(world, monkeypatch):
 def test_graph_fast_path_equals_plain_path(world, monkeypatch):
     """recommend() through the replayed hipGraph == the un-captured batch path, bit for bit, across
     token buckets, k values, exclusions and repeated replays."""
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.recommender import Recommender
-
     rec = Recommender(world["model_dir"], world["corpus_path"])
     assert rec._fast is not None
     queries = ["[+1d w0h1] Milk.", world["queries"][0], world["queries"][1],
@@ -143,11 +129,6 @@ def test_monitored_recommender_runs_on_the_graph_path(world, monkeypatch, caplog
     request cut at the encode / search seam with HIP events around the two replays: same results as the plain
     class's one-graph path and as the un-captured path, bit for bit; the three timing fields are filled; the
     `recommendation_served` record carries the user id."""
-    import logging
-
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, Recommender
-
     mon = MonitoredRecommender(world["model_dir"], world["corpus_path"])
     assert mon._fast is not None
     queries = ["[+1d w0h1] Milk.", world["queries"][0], "; ".join(syn.synthetic_user_contexts(8, seed=77))]
@@ -176,11 +157,6 @@ def test_two_different_batches_with_equal_split_point(world):
     """encode_packed_host on two DIFFERENT batches of the same size whose first halves hold the same token count:
     the second half's rebased cu_seqlens must come from the call's own sequence boundaries (an address-keyed cache
     once handed the second batch the first batch's boundaries)."""
-    import torch
-
-    from instacart_next_order_recommendation_amd.encoder import DeviceEncoder
-    from instacart_next_order_recommendation_amd.model_io import load_model_dir
-
     lm = load_model_dir(world["model_dir"])
     enc = DeviceEncoder(lm.weights, lm.shape, "cuda:0")
     n = 2 * DeviceEncoder.SPLIT_MIN_SEQS
@@ -214,8 +190,6 @@ def test_encode_without_flag_normalisation(world):
     """SentenceTransformer.encode(normalize_embeddings=False): one normalisation pass fewer.  The synthetic model
     directory has a Normalize module, so the output is still a unit vector and equals the default up to one
     division by ~1.0; without that module it would be the raw mean pool."""
-    from instacart_next_order_recommendation_amd.recommender import Recommender
-
     rec = Recommender(world["model_dir"], world["corpus_path"])
     texts = ["[+3d w1h10] Organic Milk, Whole Wheat Bread.", "Product: Oat Milk. Aisle: aisle 3. Department: dept tea."]
     a = rec.model.encode(texts, normalize_embeddings=True)
@@ -227,17 +201,8 @@ def test_encode_without_flag_normalisation(world):
 
 def test_cli_runs_demo_query(tmp_path, capsys):
     """`python -m instacart_next_order_recommendation_amd --config ...` (reference: python -m src.inference)."""
-    import json
-
-    import yaml
-
-    from instacart_next_order_recommendation_amd import cli, synthetic as syn
-    from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
-
-    model_dir = write_synthetic_model_dir(tmp_path / "model", seed=1)
-    corpus = tmp_path / "eval_corpus.json"
-    corpus.write_text(json.dumps(syn.synthetic_catalog(200)))
-    (tmp_path / "eval_queries.json").write_text(json.dumps({"42": "[+1d w2h9] Greek Yogurt, Honey."}))
+    model_dir, corpus, _ = synthetic_world(tmp_path, 200, model_seed=1, shape=None)
+    (corpus.parent / "eval_queries.json").write_text(json.dumps({"42": "[+1d w2h9] Greek Yogurt, Honey."}))
     for extra, argv, origin in (({}, [], "built-in demo context"), ({"query": "[+2d w0h8] Oat Milk."}, [], "(config)"),
                                 ({"eval_query_id": "42"}, [], "eval_queries.json[42]"),
                                 ({"query": "ignored"}, ["--query", "[+3d w1h7] Rye Bread."], "(command line)")):
@@ -255,8 +220,6 @@ def test_cli_runs_demo_query(tmp_path, capsys):
 def test_graph_path_ignores_rows_outside_the_sequence(world):
     """The hipGraph fast path encodes a fixed row count (the token bucket); rows past the real sequence hold whatever
     the buffers held before.  Poison every buffer the captured graph owns: the result must not change."""
-    from instacart_next_order_recommendation_amd.recommender import Recommender
-
     rec = Recommender(world["model_dir"], world["corpus_path"])
     q = world["queries"][1]
     want = rec.recommend(q, top_k=10)
@@ -272,9 +235,6 @@ def test_recommend_batches_pipeline_equals_recommend_batch(world):
     """recommend_batches() overlaps the host tokenisation of batch j+1 with the GPU work of batch j and reads batch j
     back after batch j+1 has been launched: every batch must equal recommend_batch() on the same inputs, bit for bit
     (same launches, one stream, in order) - with exclusions, ragged batch sizes and an empty batch in the stream."""
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.recommender import Recommender
-
     rec = Recommender(world["model_dir"], world["corpus_path"])
     qs = syn.synthetic_user_contexts(37, seed=21)
     batches = [qs[:8], qs[8:9], [], qs[9:30], qs[30:]]
@@ -293,9 +253,6 @@ def test_index_used_from_the_callers_stream_inside_a_recommend_batches_loop(worl
     """While the generator is suspended at `yield`, batch j+1's search is already in flight on the pipeline's side
     stream.  A consumer that searches the SAME index from its own stream between yields (recommend_batch, scores) must
     not disturb it, nor be disturbed: the index keeps one scratch block per stream (pipeline.py)."""
-    from instacart_next_order_recommendation_amd import synthetic as syn
-    from instacart_next_order_recommendation_amd.recommender import Recommender
-
     rec = Recommender(world["model_dir"], world["corpus_path"])
     qs = syn.synthetic_user_contexts(96, seed=33)
     batches = [qs[i:i + 16] for i in range(0, 96, 16)]

@@ -7,21 +7,16 @@ no diversity, source + caps repeated once per round of DeviceIndex.search_capped
 the test_*_recommender_gpu.py files; this file pins which calls are made, in which order, at which widths."""
 from __future__ import annotations
 
-import json
-
 import pytest
 
 from instacart_next_order_recommendation_amd import _native
-from instacart_next_order_recommendation_amd import synthetic as syn
-from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import QUERIES, synthetic_world, torch_cuda  # noqa: F401  (torch_cuda: fixture)
 
 pytestmark = pytest.mark.gpu
 
 N = 300
 SETS = {"store": [str(i) for i in range(1, N + 1) if i % 3], "stock": [str(i) for i in range(1, N + 1) if i % 2 == 0]}
-QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
 K, WIDE, NARROW = 10, 40, 12  # top_k; the candidates of a diversified request; those of a capped one (rounds follow)
 
 # entry -> the positions of (n_queries, the widths) among its arguments (include/icrec.h)
@@ -56,13 +51,8 @@ class RecordingLib:
 
 @pytest.fixture(scope="module")
 def rec(tmp_path_factory, torch_cuda):
-    tmp = tmp_path_factory.mktemp("request_calls")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(N)))
-    r = MonitoredRecommender(model_dir, corpus_path, use_index=False, ann_lists=4, product_sets=SETS)
+    w = synthetic_world(tmp_path_factory.mktemp("request_calls"), N)
+    r = MonitoredRecommender(w.model_dir, w.corpus_path, use_index=False, ann_lists=4, product_sets=SETS)
     assert r._index.n_facets == 2 and r._index.n_rowsets == 2 and r._ann.n_lists == 4
     return r
 

@@ -4,12 +4,11 @@ around every output, the selection against best_first, rerank_into's logits bit 
 packing, the recommender end to end against its device_assembly=False twin, and the ABI's refusals."""
 from __future__ import annotations
 
-import json
-
 import numpy as np
 import pytest
 
 from tests import rerank_cases as rc
+from tests.recommender_harness import synthetic_world
 
 pytestmark = pytest.mark.gpu
 
@@ -163,18 +162,12 @@ def stack(tmp_path_factory):
     """A synthetic bi-encoder, a synthetic cross-encoder (hidden 384, 2 layers, sigmoid) and a 300-product catalog."""
     if not _STACK:
         from instacart_next_order_recommendation_amd import synthetic as syn
-        from instacart_next_order_recommendation_amd.model_io import write_synthetic_cross_encoder_dir, write_synthetic_model_dir
+        from instacart_next_order_recommendation_amd.model_io import write_synthetic_cross_encoder_dir
 
         root = tmp_path_factory.mktemp("rerank_device")
-        n_vocab = len(syn.synthetic_vocab())
-        _STACK["bi_dir"] = write_synthetic_model_dir(root / "bi", seed=8, shape=syn.BertShape(vocab_size=n_vocab, layers=2))
-        _STACK["ce_dir"] = write_synthetic_cross_encoder_dir(root / "ce", seed=9,
-                                                             shape=syn.BertShape(vocab_size=n_vocab, layers=2, n_normalize=0))
-        _STACK["catalog"] = syn.synthetic_catalog(300)
-        path = root / "processed" / "eval_corpus.json"
-        path.parent.mkdir()
-        path.write_text(json.dumps(_STACK["catalog"]))
-        _STACK["corpus_path"] = path
+        _STACK["bi_dir"], _STACK["corpus_path"], _STACK["catalog"] = synthetic_world(root, 300, model_seed=8)
+        ce_shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2, n_normalize=0)
+        _STACK["ce_dir"] = write_synthetic_cross_encoder_dir(root / "ce", seed=9, shape=ce_shape)
         _STACK["contexts"] = syn.synthetic_user_contexts(12, seed=9)
     return _STACK
 

@@ -1,6 +1,6 @@
-"""Recommender.recommend(..., within=) end to end on the GPU: a synthetic 2-layer model directory, a 700-product
-synthetic catalog and four product sets.  A request inside product sets equals, ids and scores, the request that
-excludes every product outside them."""
+"""Recommender.recommend(..., within=) end to end on the GPU, on the default world of tests/recommender_harness.py (a
+synthetic 2-layer model directory, a 700-product synthetic catalog) and four product sets.  A request inside product
+sets equals, ids and scores, the request that excludes every product outside them."""
 from __future__ import annotations
 
 import json
@@ -8,10 +8,9 @@ import json
 import pytest
 import yaml
 
-from instacart_next_order_recommendation_amd import synthetic as syn
-from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import (QUERIES, assert_batch_equals_single_calls, forbid_gpu_work, graph_replays,  # noqa: F401
+                                       synthetic_world, torch_cuda)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +26,10 @@ SETS = {
 @pytest.fixture(scope="module")
 def world(tmp_path_factory, torch_cuda):
     tmp = tmp_path_factory.mktemp("rowset_rec")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(syn.synthetic_catalog(N)))
+    w = synthetic_world(tmp, N)
     sets_path = tmp / "product_sets.json"
     sets_path.write_text(json.dumps(SETS))
-    r = MonitoredRecommender(model_dir, corpus_path, use_index=False, product_sets=sets_path)   # the JSON file form
+    r = MonitoredRecommender(w.model_dir, w.corpus_path, use_index=False, product_sets=sets_path)   # the JSON file form
     assert r._fast is not None and r._index.n_rowsets == 4 and r.product_sets == list(SETS)
     return r, sets_path
 
@@ -42,9 +37,6 @@ def world(tmp_path_factory, torch_cuda):
 @pytest.fixture()
 def rec(world):
     return world[0]
-
-
-QUERIES = syn.synthetic_user_contexts(4, seed=9) + ["[+1d w0h1] Milk."]
 
 
 def outside(rec, *names, sets=SETS):
@@ -97,13 +89,9 @@ def test_within_composes_with_aisles_diversity_and_boosts(rec):
 def test_batch_with_per_query_within(rec):
     within = ["store-1", None, ["store-2", "in-stock"], "tiny", []]
     excl = [None, None, {"3", "6", "9"}, {"30"}, None]
-    batch = rec.recommend_batch(QUERIES, 20, excl, within=within)
-    for i, q in enumerate(QUERIES):
-        assert batch[i] == rec.recommend(q, 20, exclude_product_ids=excl[i], within=within[i]), i
+    batch = assert_batch_equals_single_calls(rec, QUERIES, 20, excl, within=within)
     assert batch[1] == rec.recommend(QUERIES[1], 20) and sorted(p for p, _ in batch[3]) == ["3", "300"]
     assert batch[2] == rec.recommend(QUERIES[2], 20, exclude_product_ids=outside(rec, "store-2", "in-stock") | excl[2])
-    timed, enc_ms, sim_ms = rec.recommend_batch_timed(QUERIES, 20, excl, within=within)
-    assert timed == batch and enc_ms > 0 and sim_ms > 0
     assert rec.recommend_batch(QUERIES, 20, excl, within=[None] * 5) == rec.recommend_batch(QUERIES, 20, excl)
     rec.last_metrics = None
     got = rec.recommend(QUERIES[0], 20, user_id="u7", within="store-2")
@@ -111,9 +99,7 @@ def test_batch_with_per_query_within(rec):
 
 
 def test_bad_within_raises_before_any_gpu_work(rec, monkeypatch):
-    def no_gpu(*a, **kw):
-        raise AssertionError("GPU work before the argument check")
-    monkeypatch.setattr(type(rec), "_encode_search", no_gpu)
+    forbid_gpu_work(rec, monkeypatch)
     with pytest.raises(ValueError, match="no such set"):
         rec.recommend(QUERIES[0], 20, within="no such set")
     with pytest.raises(ValueError, match="more than 4"):
@@ -127,15 +113,7 @@ def test_bad_within_raises_before_any_gpu_work(rec, monkeypatch):
 
 
 def test_requests_without_within_stay_on_the_graph_path(rec, monkeypatch):
-    fast = rec._fast_path()
-    calls = []
-    real_run = type(fast).run
-
-    def run(self, *a, **kw):
-        calls.append(1)
-        return real_run(self, *a, **kw)
-
-    monkeypatch.setattr(type(fast), "run", run)
+    calls = graph_replays(rec, monkeypatch)
     plain = rec.recommend(QUERIES[0], 20)
     assert len(calls) == 1
     assert rec.recommend(QUERIES[0], 20, within="store-1") != plain and len(calls) == 1

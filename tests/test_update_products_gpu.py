@@ -1,19 +1,16 @@
-"""Recommender.update_products end to end on the GPU, in the world of test_rowset_recommender_gpu: a synthetic 2-layer
-model directory, a 700-product synthetic catalog with aisle / department facets, product sets, and a second recommender
-with an IVF index.  After five products got new texts, every kind of request answers exactly as a new recommender built
-on the edited corpus file answers it - product ids and scores; facet codes may differ, names do not."""
+"""Recommender.update_products end to end on the GPU, on the default world of tests/recommender_harness.py: a synthetic
+2-layer model directory, a 700-product synthetic catalog with aisle / department facets, product sets, and a second
+recommender with an IVF index.  After five products got new texts, every kind of request answers exactly as a new
+recommender built on the edited corpus file answers it - product ids and scores; facet codes may differ, names do not."""
 from __future__ import annotations
-
-import json
 
 import pytest
 import torch
 
 from instacart_next_order_recommendation_amd import synthetic as syn
-from instacart_next_order_recommendation_amd.model_io import write_synthetic_model_dir
 from instacart_next_order_recommendation_amd.recommender import MonitoredRecommender, text_facets
 from instacart_next_order_recommendation_amd.search import IvfIndex
-from tests.search_harness import torch_cuda  # noqa: F401  (fixture)
+from tests.recommender_harness import graph_replays, no_gpu, synthetic_world, torch_cuda, write_corpus  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,16 +44,9 @@ def make_updates(corpus):
 @pytest.fixture(scope="module")
 def world(tmp_path_factory, torch_cuda):
     tmp = tmp_path_factory.mktemp("update_products")
-    shape = syn.BertShape(vocab_size=len(syn.synthetic_vocab()), layers=2)
-    model_dir = write_synthetic_model_dir(tmp / "model", seed=3, shape=shape)
-    corpus = syn.synthetic_catalog(N)
-    corpus_path = tmp / "processed" / "eval_corpus.json"
-    corpus_path.parent.mkdir()
-    corpus_path.write_text(json.dumps(corpus))
+    model_dir, corpus_path, corpus = synthetic_world(tmp, N)
     updates, moved_to = make_updates(corpus)
-    edited_path = tmp / "edited" / "eval_corpus.json"
-    edited_path.parent.mkdir()
-    edited_path.write_text(json.dumps({**corpus, **updates}))
+    edited_path = write_corpus(tmp / "edited", {**corpus, **updates})
     queries = syn.synthetic_user_contexts(4, seed=9) + [
         f"[+1d w0h1] {name_of(corpus['100'])}.", "[+1d w0h1] Crimson Harvest Granola.",
         f"[+2d w3h9] {name_of(corpus['256'])}, {name_of(corpus['17'])}."]
@@ -91,14 +81,7 @@ def test_host_state_follows(world):
 def test_graph_path_and_batches_answer_from_the_new_rows(world, monkeypatch):
     rec, fresh, queries = world["rec"], world["fresh"], world["queries"]
     fast = rec._fast_path()
-    calls = []
-    real_run = type(fast).run
-
-    def run(self, *a, **kw):
-        calls.append(self)
-        return real_run(self, *a, **kw)
-
-    monkeypatch.setattr(type(fast), "run", run)
+    calls = graph_replays(rec, monkeypatch)
     got = [rec.recommend(q, 20) for q in queries]
     assert calls and all(c is fast for c in calls)                                        # the graphs captured before the write
     assert got == [fresh.recommend(q, 20) for q in queries]
@@ -165,10 +148,6 @@ def test_a_bad_update_changes_nothing(world, monkeypatch):
     facets = [rec.recommend(q, 20, aisles=[NEW_AISLE, world["moved_to"]]) for q in queries]
     texts, aisles = list(rec.product_texts), list(rec.aisles)
     stored = rec._index.export().clone()
-
-    def no_gpu(*a, **kw):
-        raise AssertionError("GPU work before the argument check")
-
     monkeypatch.setattr(type(rec._index), "write_rows", no_gpu)
     monkeypatch.setattr(type(rec.model), "encode", no_gpu)
     good = "Product: Plain Oats. Aisle: one more new aisle. Department: dept novel."
