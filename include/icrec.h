@@ -648,6 +648,49 @@ ICREC_API int icrec_boost_select(icrec_index* idx, const float* q_dev, int32_t n
                        int32_t top_k, int64_t* out_idx_dev, float* out_score_dev,
                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Queries composed from stored rows: "similar items" (the query IS a row of the index), "more like these, less like
+ * those" (Rocchio feedback: the text's vector moved toward accepted products and away from dismissed ones), a profile
+ * from a basket (the weighted sum of its rows, no text at all) - built on the device from the rows the index holds,
+ * between icrec_encode and the search.  Only the query vector changes, so everything the searches do composes with it. */
+#define ICREC_MAX_TERMS 1024   /* terms read per query */
+
+/* q'[i] = a[i] * q_hat[i] + the sum over query i's terms of w * row, in list order.
+ *   base_dev       float[n_queries, dim]     the text part (icrec_encode's output; not normalised), or NULL: none
+ *   base_w_dev     float[n_queries]          a, the weight of the text part; NULL: every a = 1
+ *   term_off_dev   int32[n_queries+1]        CSR offsets into term_rows_dev / term_w_dev
+ *   term_rows_dev  int32[...]                each query's LOCAL rows, in the order given: NOT sorted, the order defines
+ *                                            the sum
+ *   term_w_dev     float[...]                their weights, of either sign; NULL: every w = 1
+ *   max_terms      in [0, ICREC_MAX_TERMS]   only the first max_terms entries of a segment are read
+ *   out_dev        float[n_queries, dim]     q'; NOT normalised (icrec_search and its siblings normalise their queries)
+ * There is no workspace.  base_dev and out_dev are 16-byte aligned (rows of dim floats are, from an aligned start).
+ * The definition, which the result follows bit for bit:
+ *   Base.  With base_dev, q_hat is the row normalised as icrec_search normalises a query (normalize_rows_kernel): 64
+ *     partial sums s_l = fmaf(x[i], x[i], s_l) over i = l, l + 64, .. ascending, added by the xor butterfly 32 .. 1,
+ *     den = max(sqrt(sum), 1e-12), q_hat[j] = x[j] / den.  Then acc[j] = a * q_hat[j], one fp32 multiplication; an a
+ *     that is not finite counts as 0.  Without base_dev, acc[j] = +0.
+ *   Terms read.  Query i's segment is entries [term_off[i], term_off[i+1]) of term_rows_dev, of which the first
+ *     max_terms are read; a segment whose end lies before its start is empty.  The offsets must lie inside the arrays.
+ *   Valid term.  0 <= row < n_rows and w is finite.  An invalid term contributes nothing and its row is never read (the
+ *     lists live on the device, where the host cannot refuse them): the call is memory-safe for any rows and weights.
+ *     A row listed twice is two terms.
+ *   Sum.  The valid terms in list order: acc[j] = acc[j] + (w * p[j]), two fp32 roundings - the product, then the sum -
+ *     and no fused multiply-add.  p is the index's STORED normalised row (bf16 storage widened exactly).  The filter
+ *     planes and fragments are not used.
+ *   Result.  out[i][j] = acc[j].
+ * A query's result has the same bits alone and inside any batch; the storages F32 and F32_FILTER give the same bits,
+ * and so do BF16 and BF16_FILTER.  One term of weight 1 without a base gives the stored row.  A zero result is a legal
+ * query: the search scores every row 0 and returns the lowest rows.
+ * ICREC_EINVAL, before any HIP call: a NULL among idx, term_off_dev, out_dev; term_rows_dev NULL with max_terms > 0;
+ * n_queries < 1; max_terms outside [0, ICREC_MAX_TERMS]; base_dev NULL together with max_terms == 0; base_w_dev set
+ * without base_dev.  Nothing is launched on an error.
+ * out_dev must not alias base_dev.  Asynchronous on `stream`: nothing is allocated, nothing synchronises, it is ONE
+ * launch, and the call can be captured into a hipGraph.  The lists and weights are read from device memory when the
+ * kernel runs: a replayed graph follows what the buffers hold then. */
+ICREC_API int icrec_compose_queries(icrec_index* idx, const float* base_dev, const float* base_w_dev, int32_t n_queries,
+                          const int32_t* term_off_dev, const int32_t* term_rows_dev, const float* term_w_dev,
+                          int32_t max_terms, float* out_dev, void* stream);
+
 /* Caps per facet value on a search result ("at most two products of one aisle, at most five of one department"):
  * walk each query's k candidates in their order and keep a candidate only while every capped facet still has room for
  * its value, entirely on the device.  Unlike a facet mask, which admits or forbids a value, a cap counts; unlike

@@ -15,6 +15,7 @@ LIB_PATH = _PKG / "libicrec.so"
 
 ICREC_MAX_K = 128
 ICREC_MAX_BOOSTS = 1024
+ICREC_MAX_TERMS = 1024
 ICREC_MAX_FACETS = 2
 ICREC_FACET_MASK_WORDS = 8
 ICREC_MAX_ROWSETS = 65535
@@ -48,7 +49,7 @@ EXPORTS = [
     "icrec_index_set_rowsets", "icrec_index_write_rowset", "icrec_index_rowsets",
     "icrec_search_in_sets_workspace_bytes", "icrec_search_in_sets",
     "icrec_mmr_select_workspace_bytes", "icrec_mmr_select",
-    "icrec_boost_select_workspace_bytes", "icrec_boost_select", "icrec_cap_select",
+    "icrec_boost_select_workspace_bytes", "icrec_boost_select", "icrec_compose_queries", "icrec_cap_select",
     "icrec_ivf_create", "icrec_ivf_destroy", "icrec_ivf_lists", "icrec_ivf_layout",
     "icrec_ivf_search_workspace_bytes", "icrec_ivf_search",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
@@ -171,6 +172,7 @@ def lib() -> C.CDLL:
         "icrec_mmr_select": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, sz, vp]),
         "icrec_boost_select_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_boost_select": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+        "icrec_compose_queries": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]),
         "icrec_cap_select": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "icrec_ivf_create": (C.c_int, [vp, vp, i32, C.POINTER(vp)]),
         "icrec_ivf_destroy": (C.c_int, [vp]),
@@ -286,6 +288,15 @@ def boost_select(index_handle, q, cand_idx, cand_score, boost_off, boost_rows, b
                                    ptr(boost_rows), ptr(boost_w), int(max_boosts), ptr(excl_idx), ptr(excl_off), ptr(allow),
                                    int(top_k), ptr(out_idx), ptr(out_score), ptr(ws), ws.numel(), stream_ptr(device)),
           "icrec_boost_select")
+
+
+def compose_queries(index_handle, base, base_w, n_queries: int, term_off, term_rows, term_w, max_terms: int, out,
+                    device) -> None:
+    """icrec_compose_queries on device tensors: base float32 [Q, dim] and base_w float32 [Q] (or None), the terms as
+    term_off int32 [Q+1], term_rows int32 and term_w float32 (or None), out float32 [Q, dim]; asynchronous on `device`'s
+    current stream."""
+    check(lib().icrec_compose_queries(index_handle, ptr(base), ptr(base_w), int(n_queries), ptr(term_off), ptr(term_rows),
+                                      ptr(term_w), int(max_terms), ptr(out), stream_ptr(device)), "icrec_compose_queries")
 
 
 def cap_select(index_handle, cand_idx, cand_score, caps, n_prior, allow, top_k: int, out_idx, out_score, out_state,

@@ -132,9 +132,9 @@ def baselines_main(argv) -> int:
     return 0
 
 
-def parse_boosts(entries):
-    """The --boost PID[=W] arguments -> (mapping PID -> W or None for an entry without a weight); ValueError for a W
-    that is not a number."""
+def parse_boosts(entries, flag: str = "--boost"):
+    """The --boost PID[=W] arguments (or another flag's of that form) -> (mapping PID -> W or None for an entry without
+    a weight); ValueError for a W that is not a number."""
     out = {}
     for e in entries or ():
         pid, eq, w = e.rpartition("=")
@@ -144,8 +144,23 @@ def parse_boosts(entries):
         try:
             out[pid] = float(w)
         except ValueError:
-            raise ValueError(f"--boost {e!r}: {w!r} is not a weight")
+            raise ValueError(f"{flag} {e!r}: {w!r} is not a weight")
     return out
+
+
+def parse_feedback(entries, flag: str):
+    """The --like / --unlike PID[=W] arguments -> None (none given), the list of ids when no entry has a weight (they
+    share --like-weight / --unlike-weight), or the mapping PID -> W when every entry has one; ValueError for a W that
+    is not a number, an id given twice, and a mix of entries with and without =W."""
+    if not entries:
+        return None
+    pairs = parse_boosts(entries, flag)
+    if len(pairs) != len(entries):
+        raise ValueError(f"{flag}: a product id is given twice")
+    weighted = [w is not None for w in pairs.values()]
+    if any(weighted) and not all(weighted):
+        raise ValueError(f"{flag}: give every product its =W or none (they then share {flag}-weight)")
+    return pairs if all(weighted) else list(pairs)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -191,6 +206,18 @@ def build_parser() -> argparse.ArgumentParser:
                          "with the CF ranking of these products; the scores are then fused scores")
     ap.add_argument("--cf-weight", type=float, default=1.0, metavar="W", help="the weight of the CF list in the fusion (default 1)")
     ap.add_argument("--rrf-c", type=float, default=60.0, metavar="C", help="the constant of 1 / (C + rank) in the fusion (default 60)")
+    ap.add_argument("--like", action="append", default=None, metavar="PID[=W]",
+                    help="a product the user accepted: the query vector moves toward it (repeatable; without =W the "
+                         "products share --like-weight)")
+    ap.add_argument("--unlike", action="append", default=None, metavar="PID[=W]",
+                    help="a product the user dismissed: the query vector moves away from it (repeatable; without =W the "
+                         "products share --unlike-weight)")
+    ap.add_argument("--query-weight", type=float, default=1.0, metavar="A", help="the weight of the text's vector (default 1)")
+    ap.add_argument("--like-weight", type=float, default=1.0, metavar="B", help="the weight of the --like centroid (default 1)")
+    ap.add_argument("--unlike-weight", type=float, default=0.5, metavar="C", help="the weight of the --unlike centroid (default 0.5)")
+    ap.add_argument("--similar-to", default=None, metavar="PID",
+                    help="similar items: rank by similarity with this catalog product instead of a text (not with --query, "
+                         "--like, --unlike); the product itself is left out")
     return ap
 
 
@@ -233,6 +260,14 @@ def main(argv=None) -> int:
         raise SystemExit("--within needs --product-sets")
     if args.product_sets is not None and not args.product_sets.exists():
         raise SystemExit(f"product sets file {args.product_sets} does not exist")
+    if args.similar_to is not None:
+        for flag, given in (("--query", args.query), ("--like", args.like), ("--unlike", args.unlike)):
+            if given:
+                raise SystemExit(f"--similar-to cannot be combined with {flag}: the product is the whole query")
+    try:
+        like, unlike = parse_feedback(args.like, "--like"), parse_feedback(args.unlike, "--unlike")
+    except ValueError as e:
+        raise SystemExit(str(e))
     cfg = read_settings(args.config)
     if not cfg["corpus"].exists():
         raise SystemExit(f"corpus file {cfg['corpus']} does not exist (this build never downloads one)")
@@ -263,12 +298,19 @@ def main(argv=None) -> int:
                           ann_lists=ann_lists, product_sets=product_sets, cf=cf)
     except ValueError as e:  # the CF baseline's corpus is not the catalog
         raise SystemExit(str(e))
+    options = dict(aisles=args.aisle, departments=args.department, diversity=args.diversity, candidates=args.candidates,
+                   boosts=boosts or None, only_boosted=args.only_boosted, probes=probes, within=args.within,
+                   max_per_aisle=args.max_per_aisle, max_per_department=args.max_per_department, history=args.history,
+                   cf_weight=args.cf_weight, rrf_c=args.rrf_c)
     try:
-        hits = rec.recommend(query=query, top_k=top_k, aisles=args.aisle, departments=args.department,
-                             diversity=args.diversity, candidates=args.candidates, boosts=boosts or None,
-                             only_boosted=args.only_boosted, probes=probes, within=args.within,
-                             max_per_aisle=args.max_per_aisle, max_per_department=args.max_per_department,
-                             history=args.history, cf_weight=args.cf_weight, rrf_c=args.rrf_c)
+        if args.similar_to is not None:
+            query, origin = f"products similar to {args.similar_to}", "--similar-to"
+            hits = rec.similar_products(args.similar_to, top_k, **options)
+        else:
+            hits = rec.recommend(query=query, top_k=top_k, like=like, unlike=unlike, query_weight=args.query_weight,
+                                 like_weight=args.like_weight, unlike_weight=args.unlike_weight, **options)
+    except KeyError:
+        raise SystemExit(f"--similar-to {args.similar_to!r}: the catalog has no such product")
     except ValueError as e:  # an aisle / department / product set the catalog does not have, a bad --diversity / --candidates / --boost / --probes / --max-per-*
         raise SystemExit(str(e))
     if args.json:

@@ -1,6 +1,6 @@
 // index.h — what an icrec_index handle points to, shared by index.hip (which creates, edits and destroys it),
 // storage.hip (which writes, moves, clears, resizes and exports what it keeps per row; storage.h), search.hip (which
-// searches it), sort.hip (icrec_rank_all), mmr.hip and boost.hip (which read its stored rows), cap.hip (which reads its
+// searches it), sort.hip (icrec_rank_all), mmr.hip, boost.hip and compose.hip (which read its stored rows), cap.hip (which reads its
 // facet words), and the device code that index.hip, storage.hip, search.hip and boost.hip share: the row normalisation
 // kernel, the exclusion search, the facet test and the row set words.  What needs no handle - the shard row rule, the
 // gathered exact-cosine tile that mmr.hip and boost.hip read the stored rows with - is in common.h.

@@ -19,7 +19,7 @@ import json
 import logging
 import os
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from pathlib import Path
 from typing import Optional, Sequence
 
@@ -457,6 +457,77 @@ def fusion_plan(history, cf_weight, rrf_c, has_cf: bool, n_queries: int, top_k: 
     return [[str(p) for p in (h or ())] for h in history], float(cf_weight), float(rrf_c), width
 
 
+def compose_terms(like, unlike, like_weight, unlike_weight, pid_to_row) -> Optional[list[tuple[int, float]]]:
+    """One request's `like` / `unlike` arguments, checked before any GPU work -> None (the plain request: no known id in
+    either) or the terms DeviceIndex.compose_queries takes, [(catalog row, weight), ...]: `like` in the given order,
+    then `unlike` with negated weights.  Each is None, an iterable of product ids - its n known ids then take
+    like_weight / n each (-unlike_weight / n for unlike: Rocchio's centroids) - or a mapping id -> weight, taken as
+    written (negated for unlike).  Ids the catalog does not have are skipped, as boost_rows skips them.  ValueError: a
+    string for either, a weight (or like_weight, unlike_weight) that is not a finite number >= 0, an id in both, an id
+    twice in one list, more than ICREC_MAX_TERMS known ids in total."""
+    def weight(v, what):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if not 0.0 <= f < float("inf"):  # (a NaN fails the comparison)
+            raise ValueError(f"{what} must be a finite number >= 0, got {v!r}")
+        return f
+
+    scale = {"like": weight(like_weight, "like_weight"), "unlike": -weight(unlike_weight, "unlike_weight")}
+    terms: list[tuple[int, float]] = []
+    seen: dict = {}
+    for name, given in (("like", like), ("unlike", unlike)):
+        if given is None:
+            continue
+        if isinstance(given, (str, bytes)):
+            raise ValueError(f"{name} must be a mapping product id -> weight or an iterable of product ids, not a string")
+        pairs = [(p, weight(v, f"the {name} weight of {p!r}")) for p, v in given.items()] if hasattr(given, "items") \
+            else [(p, None) for p in given]
+        for p, _ in pairs:
+            if seen.get(p) == name:
+                raise ValueError(f"product id {p!r} is named twice in {name}")
+            if p in seen:
+                raise ValueError(f"product id {p!r} is in both like and unlike")
+            seen[p] = name
+        known = [(pid_to_row[p], v) for p, v in pairs if p in pid_to_row]
+        sign = 1.0 if name == "like" else -1.0
+        terms.extend((r, scale[name] / len(known) if v is None else sign * v) for r, v in known)
+    if len(terms) > _native.ICREC_MAX_TERMS:
+        raise ValueError(f"{len(terms)} like / unlike products exceed the limit {_native.ICREC_MAX_TERMS}")
+    return terms or None
+
+
+def compose_plan(like, unlike, query_weight, like_weight, unlike_weight, n_queries: int, pid_to_row):
+    """A batch's `like` / `unlike` arguments (each None or one entry per query, each entry as compose_terms takes it;
+    query_weight, like_weight and unlike_weight: one value for the batch), checked before any GPU work -> None (the
+    plain path: no query has a known id) or per query None or (query_weight, [(row, weight), ...]).  ValueError:
+    compose_terms', like / unlike that is not a sequence with one entry per query, query_weight not a finite number
+    >= 0."""
+    if like is None and unlike is None:
+        return None
+    lists = {}
+    for name, given in (("like", like), ("unlike", unlike)):
+        if given is None:
+            given = [None] * n_queries
+        elif isinstance(given, (str, bytes)) or hasattr(given, "items") or not hasattr(given, "__len__"):
+            raise ValueError(f"{name} of a batch is a sequence with one entry per query")
+        given = list(given)
+        if len(given) != n_queries:
+            raise ValueError(f"{name} has {len(given)} entries for {n_queries} queries")
+        lists[name] = given
+    try:
+        a = float(query_weight)
+    except (TypeError, ValueError):
+        a = float("nan")
+    if not 0.0 <= a < float("inf"):
+        raise ValueError(f"query_weight must be a finite number >= 0, got {query_weight!r}")
+    terms = [compose_terms(lk, ul, like_weight, unlike_weight, pid_to_row) for lk, ul in zip(lists["like"], lists["unlike"])]
+    if all(t is None for t in terms):
+        return None
+    return [None if t is None else (a, t) for t in terms]
+
+
 @dataclass(frozen=True)
 class RequestPlan:
     """What a request asks beyond (queries, top_k, exclusions), checked (Recommender._plan); None / False: not asked."""
@@ -470,11 +541,12 @@ class RequestPlan:
     probes: Optional[int] = None  # the lists of the IVF index to scan: ann_plan
     width: Optional[int] = None  # the request's raw `candidates`: what DeviceIndex.search_capped searches per round
     fuse: Optional[tuple] = None  # (per-query history ids, cf_weight, rrf_c, the width of both lists): fusion_plan
+    compose: Optional[list] = None  # per query None or (query weight, [(row, weight), ...]): compose_plan
 
     @property
     def plain(self) -> bool:
         """Nothing asked: the search is `DeviceIndex.search(q, k, exclude)`, which the graph path may serve."""
-        return (self.allow, self.sets, self.boost, self.caps, self.mmr, self.probes, self.fuse) == (None,) * 7
+        return (self.allow, self.sets, self.boost, self.caps, self.mmr, self.probes, self.fuse, self.compose) == (None,) * 8
 
 
 PLAIN = RequestPlan()  # what Recommender._plan returns for every request that asks nothing
@@ -825,10 +897,12 @@ class Recommender:
 
     def _plan(self, n_queries: int, top_k: int, *, aisles=None, departments=None, diversity=None, candidates=None,
               boosts=None, boost_weight=None, only_boosted=False, probes=None, within=None, max_per_aisle=None,
-              max_per_department=None, history=None, cf_weight=1.0, rrf_c=60.0) -> RequestPlan:
-        """A request's options in recommend_batch's form (aisles, departments, boosts and within: None or one entry per
-        query), checked before any GPU work -> its RequestPlan; the one caller of the *_plan functions, in the order ann,
-        caps, within, diversity, facets, boosts, fusion.  Boosted rows outside a query's product sets are dropped here.
+              max_per_department=None, history=None, cf_weight=1.0, rrf_c=60.0, like=None, unlike=None,
+              query_weight=1.0, like_weight=1.0, unlike_weight=0.5) -> RequestPlan:
+        """A request's options in recommend_batch's form (aisles, departments, boosts, within, like and unlike: None or
+        one entry per query), checked before any GPU work -> its RequestPlan; the one caller of the *_plan functions, in
+        the order ann, caps, within, diversity, facets, boosts, fusion, compose.  Boosted rows outside a query's product
+        sets are dropped here.
         A request that asks nothing gets the shared PLAIN (`candidates` alone asks nothing: it is only a width)."""
         if probes is not None:  # (n_lists is a library call: made for the requests that probe)
             probes = ann_plan(probes, self._ann.n_lists if self._ann else None, aisles=aisles, departments=departments,
@@ -845,15 +919,19 @@ class Recommender:
                                len(self.product_ids), aisles=aisles, departments=departments, within=within, boosts=boosts,
                                only_boosted=only_boosted, diversity=diversity, probes=probes, max_per_aisle=max_per_aisle,
                                max_per_department=max_per_department)
-        if (allow, sets, boost, caps, mmr, probes, fuse) == (None,) * 7:
+        compose = compose_plan(like, unlike, query_weight, like_weight, unlike_weight, n_queries, self._pid_to_row)
+        if (allow, sets, boost, caps, mmr, probes, fuse, compose) == (None,) * 8:
             return PLAIN
         if boost is not None and sets is not None:
             boost = boosts_within(boost, sets, self._set_member)
-        return RequestPlan(allow, sets, boost, only, caps, mmr, probes, candidates, fuse)  # (the fields' order; keywords cost 0.3 us)
+        return RequestPlan(allow, sets, boost, only, caps, mmr, probes, candidates, fuse, compose)  # (the fields' order; keywords cost 0.3 us)
 
     def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, plan: RequestPlan, timed: bool = False):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
-        current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  The search is three steps:
+        current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  With plan.compose the
+        encoder's vectors are replaced by the composed queries right after the encode (_composed; it counts into the
+        search time); ids None (recommend_from_products) runs no encoder at all: the queries are plan.compose's terms
+        alone.  The search is three steps:
         1. the SOURCE ranking, w wide: the IVF index's with plan.probes (it takes exclusions only), else
            DeviceIndex.ranked under plan.allow's masks and plan.sets' ids (with plan.boost the listed rows are merged in);
         2. with plan.caps, one round of DeviceIndex.cap_select thins the list at its own width;
@@ -864,16 +942,18 @@ class Recommender:
         With plan.fuse the fused list is a fourth kind of source ranking, and the only step (fusion_plan refuses the
         rest): the content search w wide under the exclusions, icrec_cf_rank w wide on the histories, and fuse_select
         with the same exclusions to k (_fused)."""
-        n = len(cu) - 1
+        n = len(cu) - 1 if ids is not None else len(plan.compose)
         sets = None if plan.sets is None else rowset_ids(plan.sets, n, None, self.device)
         allow = None if plan.allow is None else facet_masks(plan.allow, n, self._index.n_facets, self.device)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
         stream = torch.cuda.current_stream(self.device)
         if ev:
             ev[0].record(stream)
-        emb = self.model.encoder.encode_packed_host(ids, cu)
+        emb = self.model.encoder.encode_packed_host(ids, cu) if ids is not None else None
         if ev:
             ev[1].record(stream)
+        if plan.compose is not None:
+            emb = self._composed(emb, plan.compose)
         if plan.fuse is not None:
             idx, sc = self._fused(emb, k, ex, plan.fuse)
         elif plan.caps is not None and plan.mmr is None:
@@ -893,6 +973,18 @@ class Recommender:
             ev[2].record(stream)
         idx, sc = idx.cpu().numpy(), sc.cpu().numpy()  # synchronises the stream
         return (idx, sc, ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])) if ev else (idx, sc)
+
+    def _composed(self, emb: Optional[torch.Tensor], compose) -> torch.Tensor:
+        """The queries of plan.compose (per query None or (query weight, terms)) on the encoder's vectors emb [n, dim], or
+        without a text part when emb is None: DeviceIndex.compose_queries.  A query without terms keeps the encoder's
+        own vector, bit for bit: it is then the request it is alone."""
+        q = self._index.compose_queries(emb, [c and c[1] for c in compose],
+                                        None if emb is None else [c[0] if c else 1.0 for c in compose])
+        untouched = [i for i, c in enumerate(compose) if c is None]
+        if emb is not None and untouched:
+            at = torch.tensor(untouched, dtype=torch.int64, device=self.device)
+            q[at] = emb[at]
+        return q
 
     #: the CF workspace one pass of _cf_ranked may allocate, and icrec_cf_rank's own limit on the queries of a call
     CF_PASS_BYTES, CF_PASS_QUERIES = 1 << 30, 65535
@@ -919,10 +1011,10 @@ class Recommender:
 
     def _recommend_one(self, query: str, top_k: int, exclude_product_ids, timed: bool = False, **options):
         """One request (options: recommend's keywords): a replayed hipGraph (fastpath.py) when its plan is plain - no
-        aisles, departments, product sets, diversity, boosts, probes, caps or history - and a graph supports it, else the
+        aisles, departments, product sets, diversity, boosts, probes, caps, history, like or unlike - and a graph supports it, else the
         un-captured path.  -> results; timed=True: (results, encode ms incl. host tokenisation, search ms)."""
         k = self._k(top_k)
-        for name in ("aisles", "departments", "within", "boosts", "history"):  # the per-query options, in the batch's form
+        for name in ("aisles", "departments", "within", "boosts", "history", "like", "unlike"):  # the per-query options, in the batch's form
             if options.get(name) is not None:
                 options[name] = [options[name]]
         plan = self._plan(1, top_k, **options)
@@ -951,7 +1043,8 @@ class Recommender:
                         boost_weight: float | None = None, only_boosted: bool = False, probes: int | None = None,
                         within=None, max_per_aisle: int | None = None,
                         max_per_department: int | None = None, history=None, cf_weight: float = 1.0,
-                        rrf_c: float = 60.0) -> list[list[tuple[str, float]]]:
+                        rrf_c: float = 60.0, like=None, unlike=None, query_weight: float = 1.0,
+                        like_weight: float = 1.0, unlike_weight: float = 0.5) -> list[list[tuple[str, float]]]:
         """Many contexts in one GPU pass; element i equals recommend(queries[i], ...).  aisles / departments: per
         query None or the admitted names, as recommend takes them.  diversity / candidates: one value for the whole
         batch, as recommend takes them.  boosts: None or one entry per query, each as recommend takes it; boost_weight
@@ -959,11 +1052,13 @@ class Recommender:
         within: None or one entry per query, each None or as recommend takes it.  max_per_aisle / max_per_department: one
         value for the whole batch, as recommend takes them.  history: None or one entry per query, each None or as
         recommend takes it (in a batch that fuses, a None entry counts as []); cf_weight and rrf_c: one value for the
-        whole batch."""
+        whole batch.  like / unlike: None or one entry per query, each None or as recommend takes it; query_weight,
+        like_weight and unlike_weight: one value for the whole batch."""
         plan = self._plan(len(queries), top_k, aisles=aisles, departments=departments, diversity=diversity,
                           candidates=candidates, boosts=boosts, boost_weight=boost_weight, only_boosted=only_boosted,
                           probes=probes, within=within, max_per_aisle=max_per_aisle, max_per_department=max_per_department,
-                          history=history, cf_weight=cf_weight, rrf_c=rrf_c)
+                          history=history, cf_weight=cf_weight, rrf_c=rrf_c, like=like, unlike=unlike,
+                          query_weight=query_weight, like_weight=like_weight, unlike_weight=unlike_weight)
         if not queries:
             return []
         k = self._k(top_k)
@@ -989,7 +1084,8 @@ class Recommender:
                               departments=None, diversity: float | None = None, candidates: int | None = None,
                               boosts=None, boost_weight: float | None = None, only_boosted: bool = False, within=None,
                               max_per_aisle: int | None = None, max_per_department: int | None = None, history=None,
-                              cf_weight: float = 1.0, rrf_c: float = 60.0):
+                              cf_weight: float = 1.0, rrf_c: float = 60.0, like=None, unlike=None,
+                              query_weight: float = 1.0, like_weight: float = 1.0, unlike_weight: float = 0.5):
         """recommend_batch plus (embedding ms incl. host tokenisation, similarity ms) from HIP events
         on the launch stream — what the micro-batching server reports as per-request stats.  A diversified batch's
         re-selection, a boosted batch's merge, a capped batch's rounds and a fused batch's CF ranking and fusion count into
@@ -998,7 +1094,8 @@ class Recommender:
         plan = self._plan(len(queries), top_k, aisles=aisles, departments=departments, diversity=diversity,
                           candidates=candidates, boosts=boosts, boost_weight=boost_weight, only_boosted=only_boosted,
                           within=within, max_per_aisle=max_per_aisle, max_per_department=max_per_department,
-                          history=history, cf_weight=cf_weight, rrf_c=rrf_c)
+                          history=history, cf_weight=cf_weight, rrf_c=rrf_c, like=like, unlike=unlike,
+                          query_weight=query_weight, like_weight=like_weight, unlike_weight=unlike_weight)
         ex = self._exclusion_rows(exclude_product_ids)
         t0 = time.time()
         ids, cu = self.model.tokenizer.packed(list(queries))
@@ -1012,7 +1109,8 @@ class Recommender:
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
                   only_boosted: bool = False, probes: int | None = None, within=None, max_per_aisle: int | None = None,
                   max_per_department: int | None = None, history=None, cf_weight: float = 1.0,
-                  rrf_c: float = 60.0) -> list[tuple[str, float]]:
+                  rrf_c: float = 60.0, like=None, unlike=None, query_weight: float = 1.0, like_weight: float = 1.0,
+                  unlike_weight: float = 0.5) -> list[tuple[str, float]]:
         """Top-k (product_id, score) by cosine similarity, best first (reference :206-225).
         One query = one hipGraph replay (fastpath.py) when ICREC_USE_GRAPH is not "0".
         aisles / departments (keyword-only; names from .aisles / .departments): only products of one of these aisles
@@ -1073,12 +1171,62 @@ class Recommender:
         together with aisles, departments, within, boosts / only_boosted, diversity, probes, max_per_aisle or
         max_per_department it raises ValueError before any GPU work (a CF list is the best of the whole catalog and
         knows none of these constraints), as do history on a recommender without cf, cf_weight not a number >= 0 and
-        rrf_c not finite or <= -1.  Such a request takes the un-captured path."""
+        rrf_c not finite or <= -1.  Such a request takes the un-captured path.
+        like / unlike (keyword-only; "more like these, less like those", Rocchio feedback): products the user accepted
+        and products the user dismissed, each an iterable of product ids or a mapping product id -> weight >= 0.  The
+        query vector is built on the GPU from the catalog's own stored rows, between the encode and the search
+        (DeviceIndex.compose_queries): query_weight * the normalised text vector + the sum of weight * row over like,
+        in the given order, - the same over unlike.  An iterable of n known ids gives each like_weight / n (unlike:
+        unlike_weight / n) - the centroids of Rocchio's formula; a mapping gives the weights as written.  Defaults:
+        query_weight 1, like_weight 1, unlike_weight 0.5.  The scores are the cosines of the products with the moved
+        vector.  Only the query changes, so it composes with EVERY other option, probes, history (the content list
+        of the fusion is searched with the moved vector) and only_boosted included.  Liked products are NOT removed
+        from the result - a reorder is a good recommendation here; pass them as exclude_product_ids to drop them.
+        Ids the catalog does not have are skipped; like and unlike both None, or without a known id, is the plain
+        request: the same launches, the same results.  A string, a weight that is not a finite number >= 0, an id in
+        both, an id twice in one list or more than 1,024 known ids raise ValueError before any GPU work.  Such a
+        request takes the un-captured path."""
         return self._recommend_one(query, top_k, exclude_product_ids, aisles=aisles, departments=departments,
                                    diversity=diversity, candidates=candidates, boosts=boosts, boost_weight=boost_weight,
                                    only_boosted=only_boosted, probes=probes, within=within, max_per_aisle=max_per_aisle,
                                    max_per_department=max_per_department, history=history, cf_weight=cf_weight,
-                                   rrf_c=rrf_c)
+                                   rrf_c=rrf_c, like=like, unlike=unlike, query_weight=query_weight,
+                                   like_weight=like_weight, unlike_weight=unlike_weight)
+
+    def recommend_from_products(self, products, top_k: int = 10, exclude_product_ids: set[str] | None = None,
+                                **options) -> list[tuple[str, float]]:
+        """Top-k (product_id, score) for a query made of catalog products alone - a basket's or a user's profile: the
+        weighted sum of the products' stored rows, built on the GPU (DeviceIndex.compose_queries without a base).  No
+        text, no encoder launch.  products takes the forms of recommend's `like`: an iterable of ids (its n known ids
+        weigh like_weight / n each, like_weight an option, default 1) or a mapping id -> weight >= 0.  options: recommend's
+        other keywords (aisles, within, boosts, diversity, probes, ...; not like / unlike / query_weight).  The
+        products themselves are not removed from the result: pass them as exclude_product_ids to drop them.  No known
+        id returns []; bad arguments raise ValueError before any GPU work."""
+        for name in ("like", "unlike", "query_weight", "unlike_weight"):
+            if name in options:
+                raise ValueError(f"recommend_from_products takes no {name}: the products are the whole query")
+        terms = compose_terms(products, None, options.pop("like_weight", 1.0), 0.0, self._pid_to_row)
+        k = self._k(top_k)
+        for name in ("aisles", "departments", "within", "boosts", "history"):  # the per-query options, in the batch's form
+            if options.get(name) is not None:
+                options[name] = [options[name]]
+        plan = replace(self._plan(1, top_k, **options), compose=[(0.0, terms)])
+        if terms is None:
+            return []
+        idx, sc = self._encode_search(None, None, k, self._exclusion_rows([exclude_product_ids]), plan)
+        return self._to_results(idx[0], sc[0])
+
+    def similar_products(self, product_id, top_k: int = 10, exclude_self: bool = True, **options) -> list[tuple[str, float]]:
+        """"Similar items" on a product page: the top-k by cosine similarity with the product's own stored row -
+        recommend_from_products({product_id: 1.0}) with the product itself excluded (exclude_self=False keeps it: it
+        then comes first, with a score of 1 up to the rounding of its row's norm).  options: recommend_from_products',
+        exclude_product_ids included.  KeyError: an id the catalog does not have."""
+        if product_id not in self._pid_to_row:
+            raise KeyError(product_id)
+        exclude = set(options.pop("exclude_product_ids", None) or ())
+        if exclude_self:
+            exclude.add(product_id)
+        return self.recommend_from_products({product_id: 1.0}, top_k, exclude or None, **options)
 
     def _fast_path(self):
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
@@ -1104,7 +1252,8 @@ class MonitoredRecommender(Recommender):
                   candidates: int | None = None, boosts=None, boost_weight: float | None = None,
                   only_boosted: bool = False, probes: int | None = None, within=None, max_per_aisle: int | None = None,
                   max_per_department: int | None = None, history=None, cf_weight: float = 1.0,
-                  rrf_c: float = 60.0) -> list[tuple[str, float]]:
+                  rrf_c: float = 60.0, like=None, unlike=None, query_weight: float = 1.0, like_weight: float = 1.0,
+                  unlike_weight: float = 0.5) -> list[tuple[str, float]]:
         """On the graph path the request replays cut at the encode / search seam, with HIP events around the two
         replays (fastpath.py): the three timing fields keep their meaning there.  A diversified request's
         re-selection and a boosted request's merge count into the similarity time."""
@@ -1115,7 +1264,9 @@ class MonitoredRecommender(Recommender):
                                                          only_boosted=only_boosted, probes=probes, within=within,
                                                          max_per_aisle=max_per_aisle,
                                                          max_per_department=max_per_department, history=history,
-                                                         cf_weight=cf_weight, rrf_c=rrf_c)
+                                                         cf_weight=cf_weight, rrf_c=rrf_c, like=like, unlike=unlike,
+                                                         query_weight=query_weight, like_weight=like_weight,
+                                                         unlike_weight=unlike_weight)
         self.note_served(results, user_id, encode_ms, sim_ms, (time.time() - start) * 1000)
         return results
 

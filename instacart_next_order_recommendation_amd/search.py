@@ -164,6 +164,32 @@ def boost_csr(boosts, n_queries: int, device: Optional[torch.device] = None):
     return torch.from_numpy(off).to(device), torch.from_numpy(rows_a).to(device), torch.from_numpy(w_a).to(device), max_len
 
 
+def term_csr(terms, n_queries: int, device: Optional[torch.device] = None):
+    """Per-query term lists -> (off int32[Q+1], rows int32, w float32): the CSR icrec_compose_queries takes, on `device`
+    (numpy arrays without one).  terms[i] is None (no term), a mapping row -> weight, or a sequence of (row, weight)
+    pairs, which may name a row twice.  ORDER-PRESERVING: a query's terms stay in the order given, because the order
+    defines the sum (boost_csr sorts; this must not).  rows and w hold at least one entry, so that they are never a NULL
+    pointer.  ValueError: a count mismatch, more than ICREC_MAX_TERMS terms in one list."""
+    if len(terms) != n_queries:
+        raise ValueError(f"terms has {len(terms)} entries for {n_queries} queries")
+    off = np.zeros(n_queries + 1, np.int32)
+    rows: list[int] = []
+    w: list[float] = []
+    for i, t in enumerate(terms):
+        pairs = [] if t is None else list(t.items()) if hasattr(t, "items") else list(t)
+        if len(pairs) > _native.ICREC_MAX_TERMS:
+            raise ValueError(f"terms[{i}] lists {len(pairs)} terms, more than ICREC_MAX_TERMS = {_native.ICREC_MAX_TERMS}")
+        for r, v in pairs:
+            rows.append(int(r))
+            w.append(float(v))
+        off[i + 1] = len(rows)
+    rows_a = np.asarray(rows or [0], np.int32)
+    w_a = np.asarray(w or [0.0], np.float32)
+    if device is None:
+        return off, rows_a, w_a
+    return torch.from_numpy(off).to(device), torch.from_numpy(rows_a).to(device), torch.from_numpy(w_a).to(device)
+
+
 def cap_pairs(caps, n_queries: int, device=None):
     """Per-facet caps -> the table icrec_cap_select takes, int32 [n_queries, ICREC_MAX_FACETS] (a torch tensor on
     `device`, a numpy array without one).  caps is one sequence of ICREC_MAX_FACETS ints for all queries, or
@@ -642,6 +668,59 @@ class DeviceIndex:
         if boosts is None:
             return self.search(q, k, exclude, allow, sets)
         return self.search_boosted(q, k, boosts, exclude, allow, only, sets)
+
+    def compose_queries(self, base, terms, base_weight=None) -> torch.Tensor:
+        """Queries composed from the index's stored rows (icrec_compose_queries): out[i] = a[i] * normalised base[i] +
+        the sum of weight * stored row over terms[i], in the order given -> float32 [Q, dim] on the device, NOT
+        normalised (the searches normalise their queries).  base: the text vectors [Q, dim] (or one, [dim]), or None
+        (no text part; Q is then len(terms)); terms: the per-query lists term_csr takes (LOCAL rows, weights of either
+        sign), or None with a base; base_weight: None (every a = 1), one number for all queries, or Q numbers.  One
+        term of weight 1 without a base is the stored row ("similar items"); positive and negative terms on a base are
+        Rocchio feedback; terms alone are a basket's profile."""
+        if base is None and terms is None:
+            raise ValueError("compose_queries needs a base, terms, or both")
+        if base is not None:
+            base = self._queries(base)
+        Q = int(base.shape[0]) if base is not None else len(terms)
+        if Q < 1:
+            raise ValueError("compose_queries needs at least one query")
+        off, rows, w = term_csr(terms if terms is not None else [None] * Q, Q)
+        max_terms = int(np.diff(off).max())
+        off, rows, w = (torch.from_numpy(a).to(self.device) for a in (off, rows, w))
+        if base is None:
+            if base_weight is not None:
+                raise ValueError("base_weight needs a base")
+            max_terms = max(max_terms, 1)  # (a query without a known term is then the zero vector)
+        base_w = None
+        if base_weight is not None:
+            base_w = torch.as_tensor(base_weight, dtype=torch.float32).reshape(-1)
+            if base_w.numel() not in (1, Q):
+                raise ValueError(f"base_weight must be one number or {Q} numbers, got {base_w.numel()}")
+            base_w = base_w.expand(Q).to(self.device).contiguous()
+        out = torch.empty((Q, self.dim), dtype=torch.float32, device=self.device)
+        self.compose_queries_into(base, base_w, off, rows, w, max_terms, out)
+        return out
+
+    def compose_queries_into(self, base: Optional[torch.Tensor], base_w: Optional[torch.Tensor], off: torch.Tensor,
+                             rows: torch.Tensor, w: Optional[torch.Tensor], max_terms: int, out: torch.Tensor) -> None:
+        """Allocation-free form of `compose_queries` on caller-owned contiguous device buffers (hipGraph-capturable;
+        there is no workspace): base float32 [Q, dim] or None, base_w float32 [Q] or None, the terms as term_csr lays
+        them out (w None: every weight is 1), of which the first max_terms entries per query are read, out float32
+        [Q, dim].  The kernel reads the lists and weights when it runs: a captured graph follows what the buffers hold
+        at replay.  out must not alias base."""
+        Q = int(out.shape[0])
+        for name, t, dtype, shape in (("base", base, torch.float32, (Q, self.dim)), ("base_w", base_w, torch.float32, (Q,)),
+                                      ("off", off, torch.int32, (Q + 1,)), ("rows", rows, torch.int32, None),
+                                      ("w", w, torch.float32, None), ("out", out, torch.float32, (Q, self.dim))):
+            if t is None:
+                continue
+            if t.dtype != dtype or t.device != self.device or not t.is_contiguous() or t.dim() != (len(shape) if shape else 1) \
+                    or (shape is not None and tuple(t.shape) != shape):
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor {list(shape) if shape else '[nnz]'} on "
+                                 f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if w is not None and w.shape[0] != rows.shape[0]:
+            raise ValueError(f"rows and w must have one entry per term, got {rows.shape[0]} and {w.shape[0]}")
+        _native.compose_queries(self._h, base, base_w, Q, off, rows, w, max_terms, out, self.device)
 
     def cap_select(self, idx: torch.Tensor, sc: torch.Tensor, caps, top_k: int, allow: Optional[torch.Tensor] = None):
         """Caps per facet value on a search result (icrec_cap_select): idx int64 [Q, k] candidate rows as `search`
