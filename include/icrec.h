@@ -691,6 +691,74 @@ ICREC_API int icrec_compose_queries(icrec_index* idx, const float* base_dev, con
                           const int32_t* term_off_dev, const int32_t* term_rows_dev, const float* term_w_dev,
                           int32_t max_terms, float* out_dev, void* stream);
 
+/* A query adapter learned from (context, product) pairs: the encoder and the stored rows stay frozen, a linear map on
+ * the query side is trained with the reference's loss (src/training/train_sbert.py: MultipleNegativesRankingLoss,
+ * scale 30) against the rows the index already holds.  Only the query vector changes - q' = q + D q, applied between
+ * icrec_encode and icrec_compose_queries / the search - so no product is re-encoded, the index keeps its bits and every
+ * search composes with it.
+ * An adapter of width d owns D (fp32, d x d, row-major, zero when created), a transposed copy of D for the apply
+ * kernel, AdamW's moments m and v, and the step count t.  d is a multiple of 32 in [32, ICREC_ADAPTER_MAX_DIM].  The
+ * arrays are never moved after create: a captured graph that holds an icrec_adapter_apply stays valid across training,
+ * as one that holds a search does across icrec_index_write_rows, and follows what the arrays hold when it replays.
+ *
+ * Apply, bit-exact and independent of the batch.  For a query q and each output r:
+ *     acc = +0;  for c = 0 .. d-1 in order:  acc = acc + (D[r][c] * q[c]);   q'[r] = q[r] + acc
+ *   every product and every sum one fp32 rounding (two per term, as in icrec_compose_queries): no fused multiply-add,
+ *   no MFMA.  D = 0 gives q' == q value for value.  q' is not normalised: every search normalises its queries.
+ *
+ * Loss, over B anchors a_i (fp32 [B, d]) and C >= B candidate rows cand[0 .. C): candidate i is anchor i's positive, the
+ * rest are extra negatives; v_j is the STORED row cand[j] (fp32, or bf16 widened exactly).
+ *     z_i = apply(a_i),  n_i = max(|z_i|, 1e-12),  u_i = z_i / n_i,  s_ij = scale * (u_i . v_j)
+ *     loss = the mean over the counted anchors of (logsumexp_j s_ij - s_ii)
+ *   Masked: a candidate outside [0, n_rows), for every anchor; a candidate j != i with cand[j] == cand[i], for anchor i
+ *   (a second copy of the anchor's own positive).  An anchor whose own positive is outside the range is not counted and
+ *   has no gradient.  No anchor counted: the loss is 0 and the gradient is 0.  A row number that was not checked never
+ *   becomes an address: the call is memory-safe for any candidate list.
+ * Gradient.  P = softmax_j(s_ij) over the unmasked candidates, G_ij = (P_ij - [i == j]) / counted,
+ *     du_i = scale * sum_j G_ij v_j,   dz_i = (du_i - u_i (u_i . du_i)) / n_i,   dD = sum_i dz_i a_i^T
+ *   The dot products u . v and the sums over j and i are fp32 fmaf chains (the f32 MFMA) in a fixed order; the row
+ *   maximum is subtracted before exp.  There are no floating-point atomics: the same inputs give the same bits.
+ * Update (update != 0): torch.optim.AdamW's step t + 1 on D - D = D * (1 - lr * weight_decay),
+ *     m = m + (g - m) * (1 - beta1),  v = v * beta2 + (1 - beta2) * g * g,
+ *     D = D - (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   with the bias corrections computed by the host in double - then t = t + 1. */
+#define ICREC_ADAPTER_MAX_DIM 1024
+#define ICREC_ADAPTER_MAX_BATCH 1024        /* B in [1, ICREC_ADAPTER_MAX_BATCH] */
+#define ICREC_ADAPTER_MAX_CANDIDATES 8192   /* C in [B, ICREC_ADAPTER_MAX_CANDIDATES] */
+typedef struct icrec_adapter icrec_adapter;
+
+/* ICREC_EINVAL: a NULL out, a dim that is not a multiple of 32 in [32, ICREC_ADAPTER_MAX_DIM].  Set-up calls, like
+ * icrec_index_create: create, destroy, set_state and get_state synchronise the device. */
+ICREC_API int icrec_adapter_create(int32_t dim, int device, icrec_adapter** out);
+ICREC_API int icrec_adapter_destroy(icrec_adapter* adapter);
+ICREC_API int32_t icrec_adapter_dim(const icrec_adapter* adapter);
+/* delta_host, m_host, v_host: float[dim, dim] in HOST memory; m_host and v_host may be NULL (set_state: zeros;
+ * get_state: not wanted, as may delta_host and t_out).  t >= 0 is the number of AdamW steps taken. */
+ICREC_API int icrec_adapter_set_state(icrec_adapter* adapter, const float* delta_host, const float* m_host,
+                            const float* v_host, int64_t t);
+ICREC_API int icrec_adapter_get_state(const icrec_adapter* adapter, float* delta_host, float* m_host, float* v_host,
+                            int64_t* t_out);
+/* out[i] = apply(q[i]) for n >= 1 queries, float[n, dim] in DEVICE memory, out_dev != q_dev.  ONE launch on `stream`,
+ * no workspace, nothing allocated, nothing synchronises: it can be captured into a hipGraph.  ICREC_EINVAL: a NULL
+ * pointer, n < 1, out_dev == q_dev. */
+ICREC_API int icrec_adapter_apply(const icrec_adapter* adapter, const float* q_dev, int32_t n, float* out_dev, void* stream);
+/* The loss and dD of one batch against idx's stored rows and, with update != 0, the AdamW step.
+ *   anchors_dev    float[B, dim]      the anchors (icrec_encode's output)
+ *   cand_rows_dev  int32[C]           LOCAL rows of idx; candidate i < B is anchor i's positive
+ *   loss_out_dev   float[1]           the loss
+ *   grad_out_dev   float[dim, dim]    dD, or NULL: not wanted
+ * Workspace: icrec_adapter_step_workspace_bytes(adapter, B, C) bytes on the adapter's device (0 for sizes outside the
+ * limits).  Three launches on `stream`; nothing is allocated, nothing synchronises.  The step count and the bias
+ * corrections are the host's: they are taken when the call is made.
+ * ICREC_EINVAL, before any HIP call: a NULL among idx, adapter, anchors_dev, cand_rows_dev, loss_out_dev, the workspace;
+ * an index whose dim or device differs from the adapter's, or without rows; B or C outside the limits; a workspace that
+ * is too small; a hyper-parameter that is not finite; with update != 0, a beta outside [0, 1) or a negative eps. */
+ICREC_API size_t icrec_adapter_step_workspace_bytes(const icrec_adapter* adapter, int32_t B, int32_t C);
+ICREC_API int icrec_adapter_step(icrec_index* idx, icrec_adapter* adapter, const float* anchors_dev, int32_t B,
+                       const int32_t* cand_rows_dev, int32_t C, float scale, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int32_t update, float* loss_out_dev, float* grad_out_dev,
+                       void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Caps per facet value on a search result ("at most two products of one aisle, at most five of one department"):
  * walk each query's k candidates in their order and keep a candidate only while every capped facet still has room for
  * its value, entirely on the device.  Unlike a facet mask, which admits or forbids a value, a cap counts; unlike

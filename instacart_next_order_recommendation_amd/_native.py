@@ -16,6 +16,9 @@ LIB_PATH = _PKG / "libicrec.so"
 ICREC_MAX_K = 128
 ICREC_MAX_BOOSTS = 1024
 ICREC_MAX_TERMS = 1024
+ICREC_ADAPTER_MAX_DIM = 1024
+ICREC_ADAPTER_MAX_BATCH = 1024
+ICREC_ADAPTER_MAX_CANDIDATES = 8192
 ICREC_MAX_FACETS = 2
 ICREC_FACET_MASK_WORDS = 8
 ICREC_MAX_ROWSETS = 65535
@@ -50,6 +53,8 @@ EXPORTS = [
     "icrec_search_in_sets_workspace_bytes", "icrec_search_in_sets",
     "icrec_mmr_select_workspace_bytes", "icrec_mmr_select",
     "icrec_boost_select_workspace_bytes", "icrec_boost_select", "icrec_compose_queries", "icrec_cap_select",
+    "icrec_adapter_create", "icrec_adapter_destroy", "icrec_adapter_dim", "icrec_adapter_set_state",
+    "icrec_adapter_get_state", "icrec_adapter_apply", "icrec_adapter_step_workspace_bytes", "icrec_adapter_step",
     "icrec_ivf_create", "icrec_ivf_destroy", "icrec_ivf_lists", "icrec_ivf_layout",
     "icrec_ivf_search_workspace_bytes", "icrec_ivf_search",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
@@ -174,6 +179,15 @@ def lib() -> C.CDLL:
         "icrec_boost_select": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
         "icrec_compose_queries": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]),
         "icrec_cap_select": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "icrec_adapter_create": (C.c_int, [i32, C.c_int, C.POINTER(vp)]),
+        "icrec_adapter_destroy": (C.c_int, [vp]),
+        "icrec_adapter_dim": (i32, [vp]),
+        "icrec_adapter_set_state": (C.c_int, [vp, vp, vp, vp, i64]),
+        "icrec_adapter_get_state": (C.c_int, [vp, vp, vp, vp, C.POINTER(i64)]),
+        "icrec_adapter_apply": (C.c_int, [vp, vp, i32, vp, vp]),
+        "icrec_adapter_step_workspace_bytes": (sz, [vp, i32, i32]),
+        "icrec_adapter_step": (C.c_int, [vp, vp, vp, i32, vp, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                         C.c_float, i32, vp, vp, vp, sz, vp]),
         "icrec_ivf_create": (C.c_int, [vp, vp, i32, C.POINTER(vp)]),
         "icrec_ivf_destroy": (C.c_int, [vp]),
         "icrec_ivf_lists": (i32, [vp]),

@@ -1,0 +1,251 @@
+"""A query adapter learned from (context, product) pairs on the GPU (include/icrec.h, icrec_adapter_*).
+
+The reference trains its bi-encoder with MultipleNegativesRankingLoss(scale=30) over (anchor, positive) pairs
+(src/training/train_sbert.py).  Here the encoder and the stored product rows stay frozen and a linear map on the query
+side, q' = q + D q, is trained with that loss against the rows the index already holds: no product is re-encoded, the
+index keeps its bits, and every request option composes with it because only the query vector changes.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from pathlib import Path
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _native
+
+DEFAULT_SCALE = 30.0  # the reference's loss_scale
+
+
+def schedule(step: int, total: int, warmup: int) -> float:
+    """The factor on the learning rate at 0-based `step` of `total`: linear warm-up over the first `warmup` steps, then
+    a cosine to zero (the reference's warmup_steps = int(0.1 * total), lr_scheduler_type="cosine")."""
+    if step < warmup:
+        return step / max(1, warmup)
+    progress = (step - warmup) / max(1, total - warmup)
+    return max(0.0, 0.5 * (1.0 + math.cos(math.pi * progress)))
+
+
+def fit_plan(n_pairs: int, epochs, batch_size, negatives, lr, weight_decay, scale):
+    """QueryAdapter.fit's sizes and hyper-parameters, checked before any GPU work -> (batch, steps per epoch, total steps,
+    warm-up steps).  drop_last as the reference has it, unless there is less than one batch: then the pairs are one
+    batch.  ValueError: no pair, epochs < 1, batch_size outside [1, ICREC_ADAPTER_MAX_BATCH], negatives < 0 or
+    batch_size + negatives above ICREC_ADAPTER_MAX_CANDIDATES, lr / weight_decay / scale not finite, lr or weight_decay
+    negative."""
+    def integer(v, what, lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{what} must be an integer in [{lo}, {hi}], got {v!r}")
+        return int(v)
+
+    def number(v, what, lo=None):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if not math.isfinite(f) or (lo is not None and f < lo):
+            raise ValueError(f"{what} must be a finite number" + (f" >= {lo}" if lo is not None else "") + f", got {v!r}")
+        return f
+
+    if n_pairs < 1:
+        raise ValueError("fit needs at least one (anchor, positive) pair")
+    epochs = integer(epochs, "epochs", 1, 2**31 - 1)
+    batch_size = integer(batch_size, "batch_size", 1, _native.ICREC_ADAPTER_MAX_BATCH)
+    negatives = integer(negatives, "negatives", 0, _native.ICREC_ADAPTER_MAX_CANDIDATES)
+    if batch_size + negatives > _native.ICREC_ADAPTER_MAX_CANDIDATES:
+        raise ValueError(f"batch_size + negatives = {batch_size + negatives} exceeds the limit "
+                         f"{_native.ICREC_ADAPTER_MAX_CANDIDATES}")
+    number(lr, "lr", 0.0)
+    number(weight_decay, "weight_decay", 0.0)
+    number(scale, "scale")
+    batch = min(batch_size, n_pairs)
+    per_epoch = n_pairs // batch
+    total = epochs * per_epoch
+    return batch, per_epoch, total, int(0.1 * total)
+
+
+class QueryAdapter:
+    """An icrec_adapter: D (fp32, dim x dim, zero when created), AdamW's moments and the step count, on one HIP device.
+    The arrays never move, so a captured graph that holds apply_into stays valid while the adapter trains."""
+
+    def __init__(self, dim: int, device: str | torch.device = "cuda:0"):
+        self.device = _native.hip_device(device, "QueryAdapter")
+        self.dim = int(dim)
+        self.scale = DEFAULT_SCALE  # the scale of the loss it was trained with (fit; kept by save / load)
+        self._h = C.c_void_p()
+        _native.check(_native.lib().icrec_adapter_create(self.dim, self.device.index, C.byref(self._h)), "icrec_adapter_create")
+        self._scratch = _native.StreamScratch(self.device)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _native.lib().icrec_adapter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- apply ---------------------------------------------------------------------------------------
+    def _rows(self, q: torch.Tensor, what: str) -> torch.Tensor:
+        if not isinstance(q, torch.Tensor):
+            q = torch.as_tensor(np.asarray(q, np.float32))
+        q = q.to(self.device, torch.float32).contiguous()
+        if q.ndim != 2 or q.shape[1] != self.dim or q.shape[0] < 1:
+            raise ValueError(f"{what} must be float32 [n >= 1, {self.dim}], got {tuple(q.shape)}")
+        return q
+
+    def apply(self, q) -> torch.Tensor:
+        """q' = q + D q for queries [n, dim] -> a new device tensor; bit-exact and the same alone or in any batch.  Not
+        normalised: every search normalises its queries."""
+        q = self._rows(q, "q")
+        out = torch.empty_like(q)
+        self.apply_into(q, out)
+        return out
+
+    def apply_into(self, q: torch.Tensor, out: torch.Tensor) -> None:
+        """icrec_adapter_apply on device tensors float32 [n, dim], out not q: one launch on the current stream, no
+        scratch - capturable."""
+        _native.check(_native.lib().icrec_adapter_apply(self._h, _native.ptr(q), int(q.shape[0]), _native.ptr(out),
+                                                        _native.stream_ptr(self.device)), "icrec_adapter_apply")
+
+    # -- training ------------------------------------------------------------------------------------
+    def _step(self, index, anchors, cand_rows, scale, lr, betas, eps, weight_decay, update: bool, loss_out, grad_out):
+        anchors = self._rows(anchors, "anchors")
+        if not isinstance(cand_rows, torch.Tensor):
+            cand_rows = torch.as_tensor(np.asarray(cand_rows, np.int64))
+        if cand_rows.dtype != torch.int32:  # a row beyond int32 is out of range for any index: -1, not its low 32 bits
+            wide = cand_rows.to(torch.int64)
+            cand_rows = torch.where((wide < 0) | (wide > 2**31 - 1), torch.full_like(wide, -1), wide)
+        cand = cand_rows.to(self.device, torch.int32).contiguous()
+        if cand.ndim != 1:
+            raise ValueError(f"cand_rows must be a list of rows, got shape {tuple(cand.shape)}")
+        B, n_cand = int(anchors.shape[0]), int(cand.shape[0])
+        L = _native.lib()
+        need = int(L.icrec_adapter_step_workspace_bytes(self._h, B, n_cand))
+        ws = self._scratch.block(max(need, 256))
+        _native.check(L.icrec_adapter_step(index._h, self._h, _native.ptr(anchors), B, _native.ptr(cand), n_cand, float(scale),
+                                           float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                           1 if update else 0, _native.ptr(loss_out), _native.ptr(grad_out), _native.ptr(ws),
+                                           ws.numel(), _native.stream_ptr(self.device)), "icrec_adapter_step")
+
+    def loss_and_grad(self, index, anchors, cand_rows, scale: float = DEFAULT_SCALE):
+        """(loss float32 [], dD float32 [dim, dim]) on the device, of the anchors [B, dim] against index's stored rows
+        cand_rows [C >= B] (candidate i is anchor i's positive); the adapter is not changed."""
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        grad = torch.empty((self.dim, self.dim), dtype=torch.float32, device=self.device)
+        self._step(index, anchors, cand_rows, scale, 0.0, (0.9, 0.999), 1e-8, 0.0, False, loss, grad)
+        return loss[0], grad
+
+    def step(self, index, anchors, cand_rows, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
+             scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None):
+        """One AdamW step (torch.optim.AdamW's formula) on the batch's gradient -> the batch's loss before the step, a
+        float32 [] device tensor (loss_out: a float32 [1] device tensor to write it to).  No host synchronisation."""
+        loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=self.device)
+        self._step(index, anchors, cand_rows, scale, lr, betas, eps, weight_decay, True, loss, grad_out)
+        return loss[0]
+
+    def fit(self, index, anchor_embeddings, positive_rows, epochs: int = 5, batch_size: int = 64, negatives: int = 0,
+            lr: float = 2e-3, weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0) -> list[float]:
+        """Train on pairs (anchor_embeddings[i], the stored row positive_rows[i]) -> the per-step losses.  Each epoch
+        walks a fresh shuffle in batches of batch_size with in-batch negatives plus `negatives` rows drawn from the
+        whole index; the shuffles and draws come from a CPU torch.Generator seeded with `seed`, so a run is
+        reproducible.  As the reference trains: warm-up over the first 10 % of the steps, then a cosine schedule;
+        drop_last (unless there is less than one batch); scale 30.  The host is read back once, at the end."""
+        rows = torch.as_tensor(np.asarray(positive_rows, np.int64))
+        if rows.ndim != 1:
+            raise ValueError("positive_rows must be a list of rows")
+        batch, per_epoch, total, warmup = fit_plan(int(rows.shape[0]), epochs, batch_size, negatives, lr, weight_decay, scale)
+        anchors = self._rows(anchor_embeddings, "anchor_embeddings")
+        if anchors.shape[0] != rows.shape[0]:
+            raise ValueError(f"{anchors.shape[0]} anchors for {rows.shape[0]} positives")
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        rows_dev = rows.to(self.device, torch.int32)
+        losses = torch.zeros(total, dtype=torch.float32, device=self.device)
+        s = 0
+        for _ in range(int(epochs)):
+            perm = torch.randperm(int(rows.shape[0]), generator=gen)
+            for b in range(per_epoch):
+                at = perm[b * batch:(b + 1) * batch].to(self.device)
+                cand = rows_dev[at]
+                if negatives:
+                    extra = torch.randint(0, index.n_rows, (int(negatives),), generator=gen, dtype=torch.int64)
+                    cand = torch.cat([cand, extra.to(self.device, torch.int32)])
+                self.step(index, anchors[at], cand, float(lr) * schedule(s, total, warmup), weight_decay=weight_decay,
+                          scale=scale, loss_out=losses[s:s + 1])
+                s += 1
+        self.scale = float(scale)
+        return losses.cpu().tolist()
+
+    # -- state ---------------------------------------------------------------------------------------
+    @property
+    def steps(self) -> int:
+        """AdamW steps taken."""
+        t = C.c_int64(0)
+        _native.check(_native.lib().icrec_adapter_get_state(self._h, None, None, None, C.byref(t)), "icrec_adapter_get_state")
+        return int(t.value)
+
+    def state(self) -> dict:
+        """{"delta", "m", "v": float32 [dim, dim] host arrays, "t": steps taken}."""
+        arrays = {name: np.empty((self.dim, self.dim), np.float32) for name in ("delta", "m", "v")}
+        t = C.c_int64(0)
+        _native.check(_native.lib().icrec_adapter_get_state(self._h, *(C.c_void_p(a.ctypes.data) for a in arrays.values()),
+                                                            C.byref(t)), "icrec_adapter_get_state")
+        return {**arrays, "t": int(t.value)}
+
+    def load_state(self, state: dict) -> None:
+        """state()'s dictionary back onto the device; "m" and "v" may be missing or None (zeros), "t" defaults to 0."""
+        arrays = []
+        for name in ("delta", "m", "v"):
+            a = state.get(name)
+            if a is None:
+                if name == "delta":
+                    raise ValueError("load_state needs 'delta'")
+                arrays.append(None)
+                continue
+            a = np.ascontiguousarray(np.asarray(a, np.float32))
+            if a.shape != (self.dim, self.dim):
+                raise ValueError(f"{name} must be [{self.dim}, {self.dim}], got {a.shape}")
+            if not np.isfinite(a).all():
+                raise ValueError(f"{name} holds values that are not finite")
+            arrays.append(a)
+        _native.check(_native.lib().icrec_adapter_set_state(
+            self._h, *(C.c_void_p(a.ctypes.data if a is not None else 0) for a in arrays), int(state.get("t", 0) or 0)),
+            "icrec_adapter_set_state")
+
+    def save(self, path) -> None:
+        """An .npz of D, dim, scale and the number of steps (not the moments: a saved adapter is for serving)."""
+        write_adapter_file(path, self.state()["delta"], self.scale, self.steps)
+
+    @classmethod
+    def load(cls, path, device: str | torch.device = "cuda:0") -> "QueryAdapter":
+        delta, scale, steps = read_adapter_file(path)
+        adapter = cls(delta.shape[0], device)
+        adapter.load_state({"delta": delta, "t": steps})
+        adapter.scale = scale
+        return adapter
+
+
+def write_adapter_file(path, delta: np.ndarray, scale: float, steps: int) -> None:
+    """The adapter file: an .npz of delta float32 [dim, dim], dim, scale, steps - written to exactly `path`."""
+    delta = np.ascontiguousarray(np.asarray(delta, np.float32))
+    if delta.ndim != 2 or delta.shape[0] != delta.shape[1]:
+        raise ValueError(f"delta must be square, got {delta.shape}")
+    with open(Path(path), "wb") as f:
+        np.savez(f, delta=delta, dim=np.int64(delta.shape[0]), scale=np.float64(scale), steps=np.int64(steps))
+
+
+def read_adapter_file(path) -> tuple[np.ndarray, float, int]:
+    """-> (delta float32 [dim, dim], scale, steps) of an adapter file.  ValueError: a file without these arrays, a delta
+    that is not [dim, dim] or not finite."""
+    with np.load(Path(path)) as z:  # allow_pickle stays False
+        missing = [name for name in ("delta", "dim", "scale", "steps") if name not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not an adapter file (no {missing[0]!r})")
+        delta, dim, scale, steps = np.asarray(z["delta"], np.float32), int(z["dim"]), float(z["scale"]), int(z["steps"])
+    if delta.shape != (dim, dim) or not np.isfinite(delta).all():
+        raise ValueError(f"{path}: delta must be a finite [{dim}, {dim}] matrix, got {delta.shape}")
+    return delta, scale, steps

@@ -22,6 +22,7 @@ import torch
 
 from . import _native, ir_metrics
 from ._native import ptr, stream_ptr
+from .adapter import QueryAdapter
 from .model_io import load_model_dir
 from .recommender import SbertModel
 from .search import DeviceIndex, fuse_select, rrf_weights
@@ -42,10 +43,12 @@ def _evaluate(baseline, relevant_docs: dict[str, set[str]], depth: int, queries_
 
 class ContentBasedBaseline:
     """Same constructor and `rank_all` contract as the reference class, with `model_name` a LOCAL
-    SentenceTransformer directory (no hub access)."""
+    SentenceTransformer directory (no hub access).  adapter: a QueryAdapter, or the file one was saved to, that every
+    query vector goes through before the search (q' = q + D q; adapter.py) - the corpus embeddings are what they are
+    without it, so `evaluate` reports the eight metrics with and without the adapter over the same index."""
 
     def __init__(self, eval_queries: dict[str, str], eval_corpus: dict[str, str], model_name: str | Path,
-                 batch_size: int = 64, device: str | torch.device = "cuda:0"):
+                 batch_size: int = 64, device: str | torch.device = "cuda:0", adapter=None):
         self.eval_queries = eval_queries
         self.eval_corpus = eval_corpus
         self.product_ids = list(eval_corpus.keys())
@@ -55,6 +58,16 @@ class ContentBasedBaseline:
         self.corpus_embeddings = self.model.encode(self.corpus_texts, batch_size=batch_size,
                                                    show_progress_bar=True, normalize_embeddings=True)
         self._index = DeviceIndex(self.corpus_embeddings, self.device)
+        if adapter is not None and not isinstance(adapter, QueryAdapter):
+            adapter = QueryAdapter.load(adapter, self.device)
+        if adapter is not None and adapter.dim != self._index.dim:
+            raise ValueError(f"the adapter is {adapter.dim} wide, the model {self._index.dim}")
+        self.adapter = adapter
+
+    def _query_embeddings(self, qids) -> torch.Tensor:
+        """The queries' vectors on the device, through the adapter when there is one."""
+        emb = self.model.encode_to_device([self.eval_queries[q] for q in qids])
+        return emb if self.adapter is None else self.adapter.apply(emb)
 
     def rank_all(self, depth: int | None = None, queries_per_pass: int | None = None) -> dict[str, list[str]]:
         """query_id -> product ids by cosine similarity, best first (score desc, then lower corpus row first
@@ -70,7 +83,7 @@ class ContentBasedBaseline:
         out: dict[str, list[str]] = {}
         for s in range(0, len(query_ids), queries_per_pass):
             qids = query_ids[s:s + queries_per_pass]
-            emb = self.model.encode_to_device([self.eval_queries[q] for q in qids])
+            emb = self._query_embeddings(qids)
             idx = self._index.rank_all(emb) if full else self._index.search(emb, depth)[0]
             idx = idx.cpu().numpy()
             for i, qid in enumerate(qids):
@@ -97,7 +110,7 @@ class ContentBasedBaseline:
         for s in range(0, len(query_ids), step):
             qids = query_ids[s:s + step]
             lists = None if boosts is None else self.boost_lists(qids, boosts, boost_weight)
-            emb = self.model.encode_to_device([self.eval_queries[q] for q in qids])
+            emb = self._query_embeddings(qids)
             yield (self._index.search(emb, depth) if lists is None else self._index.search_boosted(emb, depth, lists))[0], qids
 
     def rank_rows(self, depth: int = 100, queries_per_pass: int | None = None, boosts: dict | None = None,

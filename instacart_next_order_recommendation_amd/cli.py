@@ -15,6 +15,16 @@ ignored; a missing model directory or corpus file is an error).
                                                       [--max-per-aisle N] [--max-per-department N]
                                                       [--cf-data-dir DIR --cf-processed-dir DIR --history PID...
                                                        [--cf-weight W] [--rrf-c C]]
+                                                      [--adapter FILE]
+
+`--adapter FILE` (or the optional `adapter_path` key of the config) puts a learned query adapter (adapter.py) behind the
+encoder.  `fit-adapter` as the first argument learns one from (context, product) pairs - lines of
+{"anchor": text, "positive": product_id} - against the catalog's stored rows and writes it to --out:
+
+    python -m instacart_next_order_recommendation_amd fit-adapter --config configs/inference.yaml --pairs FILE.jsonl
+                                                                  --out FILE [--epochs N] [--batch-size B]
+                                                                  [--negatives M] [--lr LR] [--weight-decay WD]
+                                                                  [--scale S] [--seed N]
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
 and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
@@ -23,6 +33,7 @@ processed_dir, data_dir, model_name, content_only, cf_only).
     python -m instacart_next_order_recommendation_amd baselines --config configs/baselines.yaml [--cf-only]
                                                                 [--reorder-boost W]
                                                                 [--hybrid [--cf-weight W] [--rrf-c C]]
+                                                                [--adapter FILE]
 """
 from __future__ import annotations
 
@@ -34,7 +45,7 @@ from pathlib import Path
 import yaml
 
 _DEFAULTS = {"model_dir": "models/two_tower_sbert/final", "corpus": "processed/p5_mp20_ef0.1/eval_corpus.json",
-             "use_index": True, "query": None, "eval_query_id": None, "top_k": 10}
+             "use_index": True, "query": None, "eval_query_id": None, "top_k": 10, "adapter_path": None}
 _FALLBACK_QUERY = "[+7d w4h14] Organic Milk, Whole Wheat Bread."  # the reference's demo context
 
 
@@ -44,7 +55,74 @@ def read_settings(path: Path | None) -> dict:
     cfg = {key: (raw[key] if raw.get(key) is not None else default) for key, default in _DEFAULTS.items()}
     cfg["model_dir"], cfg["corpus"] = Path(str(cfg["model_dir"])), Path(str(cfg["corpus"]))
     cfg["top_k"], cfg["use_index"] = int(cfg["top_k"]), bool(cfg["use_index"])
+    cfg["adapter_path"] = Path(str(cfg["adapter_path"])) if cfg["adapter_path"] else None
     return cfg
+
+
+def adapter_file(cfg: dict, override: Path | None) -> Path | None:
+    """The adapter file of a run: --adapter beats the config's adapter_path; None: no adapter.  A file that does not
+    exist ends the run."""
+    path = override or cfg["adapter_path"]
+    if path is not None and not Path(path).exists():
+        raise SystemExit(f"adapter file {path} does not exist")
+    return path
+
+
+def read_pairs(path: Path) -> list[tuple[str, str]]:
+    """A .jsonl of {"anchor": context text, "positive": product id} -> [(text, id)]; blank lines are skipped.  ValueError
+    names the first line that is not such an object."""
+    pairs = []
+    for n, line in enumerate(Path(path).read_text().splitlines(), 1):
+        if not line.strip():
+            continue
+        try:
+            row = json.loads(line)
+            pairs.append((row["anchor"], str(row["positive"])))
+        except (ValueError, KeyError, TypeError):
+            raise ValueError(f"{path}:{n}: not a {{\"anchor\": ..., \"positive\": ...}} object")
+        if not isinstance(pairs[-1][0], str):
+            raise ValueError(f"{path}:{n}: the anchor must be a string")
+    return pairs
+
+
+def fit_adapter_main(argv) -> int:
+    ap = argparse.ArgumentParser(prog="instacart_next_order_recommendation_amd fit-adapter",
+                                 description="Learn a query adapter from (context, product) pairs on the GPU.")
+    ap.add_argument("--config", type=Path, default=None, help="YAML settings (default: configs/inference.yaml): model_dir, corpus")
+    ap.add_argument("--pairs", type=Path, required=True, metavar="FILE.jsonl",
+                    help='lines of {"anchor": context text, "positive": product_id}')
+    ap.add_argument("--out", type=Path, required=True, metavar="FILE", help="where the adapter is written (.npz)")
+    ap.add_argument("--adapter", type=Path, default=None, metavar="FILE", help="an adapter to train further")
+    ap.add_argument("--epochs", type=int, default=5)
+    ap.add_argument("--batch-size", type=int, default=64)
+    ap.add_argument("--negatives", type=int, default=0, help="extra catalog rows drawn per step beside the in-batch negatives")
+    ap.add_argument("--lr", type=float, default=2e-3)
+    ap.add_argument("--weight-decay", type=float, default=0.01)
+    ap.add_argument("--scale", type=float, default=30.0, help="the loss scale (the reference trains with 30)")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    cfg = read_settings(args.config)
+    if not cfg["corpus"].exists():
+        raise SystemExit(f"corpus file {cfg['corpus']} does not exist (this build never downloads one)")
+    if not args.pairs.exists():
+        raise SystemExit(f"pairs file {args.pairs} does not exist")
+    start = adapter_file(cfg, args.adapter)
+    try:
+        pairs = read_pairs(args.pairs)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+    from .recommender import Recommender
+
+    rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"], adapter=start)
+    try:
+        losses = rec.fit_adapter(pairs, epochs=args.epochs, batch_size=args.batch_size, negatives=args.negatives, lr=args.lr,
+                                 weight_decay=args.weight_decay, scale=args.scale, seed=args.seed)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    rec._adapter.save(args.out)
+    print(f"{len(pairs)} pairs, {len(losses)} steps: loss {losses[0]:.4f} -> {losses[-1]:.4f}; adapter written to {args.out}")
+    return 0
 
 
 def pick_query(cfg: dict, override: str | None) -> tuple[str, str]:
@@ -92,6 +170,8 @@ def baselines_main(argv) -> int:
                          "rank fusion); needs both baselines")
     ap.add_argument("--cf-weight", type=float, default=1.0, metavar="W", help="--hybrid: the weight of the CF list (default 1)")
     ap.add_argument("--rrf-c", type=float, default=60.0, metavar="C", help="--hybrid: the constant of 1 / (C + rank) (default 60)")
+    ap.add_argument("--adapter", type=Path, default=None, metavar="FILE",
+                    help="a further block: the content-based ranking with this query adapter behind the encoder")
     args = ap.parse_args(argv)
     path = args.config or (Path("configs/baselines.yaml") if Path("configs/baselines.yaml").exists() else None)
     raw = (yaml.safe_load(Path(path).read_text()) or {}) if path else {}
@@ -108,6 +188,8 @@ def baselines_main(argv) -> int:
         raise SystemExit(f"{processed_dir} holds no eval_queries.json (this build never downloads one)")
     if args.reorder_boost is not None and (cf_only or not args.reorder_boost >= 0.0):
         raise SystemExit("--reorder-boost takes a weight >= 0 and needs the content-based baseline (not --cf-only)")
+    if args.adapter is not None and (cf_only or not args.adapter.exists()):
+        raise SystemExit("--adapter takes an existing adapter file and needs the content-based baseline (not --cf-only)")
 
     from .baselines import ContentBasedBaseline, HybridBaseline, ItemItemCFBaseline
     from .ir_metrics import load_eval_data
@@ -119,6 +201,12 @@ def baselines_main(argv) -> int:
             raise SystemExit(f"model_name {model_name} is not a local model directory (nothing is fetched from a hub)")
         cb = ContentBasedBaseline(eval_queries, eval_corpus, model_name=model_name)
         print_metrics("Content-based (untrained SBERT)", cb.evaluate(relevant))
+        if args.adapter is not None:
+            from .adapter import QueryAdapter
+
+            cb.adapter = QueryAdapter.load(args.adapter, cb.device)
+            print_metrics(f"Content-based + query adapter ({args.adapter.name})", cb.evaluate(relevant))
+            cb.adapter = None
     if not content_only:
         cf = ItemItemCFBaseline(data_dir, processed_dir)
         print_metrics("Collaborative filtering (item-item)", cf.evaluate(relevant))
@@ -215,6 +303,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--query-weight", type=float, default=1.0, metavar="A", help="the weight of the text's vector (default 1)")
     ap.add_argument("--like-weight", type=float, default=1.0, metavar="B", help="the weight of the --like centroid (default 1)")
     ap.add_argument("--unlike-weight", type=float, default=0.5, metavar="C", help="the weight of the --unlike centroid (default 0.5)")
+    ap.add_argument("--adapter", type=Path, default=None, metavar="FILE",
+                    help="a learned query adapter (fit-adapter) behind the encoder; overrides adapter_path of the config")
     ap.add_argument("--similar-to", default=None, metavar="PID",
                     help="similar items: rank by similarity with this catalog product instead of a text (not with --query, "
                          "--like, --unlike); the product itself is left out")
@@ -253,6 +343,8 @@ def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else list(argv)
     if argv and argv[0] == "baselines":
         return baselines_main(argv[1:])
+    if argv and argv[0] == "fit-adapter":
+        return fit_adapter_main(argv[1:])
     args = build_parser().parse_args(argv)
     ann_lists, probes = ann_args(args)
     with_cf = fusion_args(args)
@@ -272,6 +364,7 @@ def main(argv=None) -> int:
     if not cfg["corpus"].exists():
         raise SystemExit(f"corpus file {cfg['corpus']} does not exist (this build never downloads one)")
     query, origin = pick_query(cfg, args.query)
+    adapter = adapter_file(cfg, args.adapter)
     top_k = args.top_k or cfg["top_k"]
     try:
         boosts = parse_boosts(args.boost)
@@ -295,8 +388,8 @@ def main(argv=None) -> int:
         cf = ItemItemCFBaseline(args.cf_data_dir, args.cf_processed_dir)
     try:
         rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"],
-                          ann_lists=ann_lists, product_sets=product_sets, cf=cf)
-    except ValueError as e:  # the CF baseline's corpus is not the catalog
+                          ann_lists=ann_lists, product_sets=product_sets, cf=cf, adapter=adapter)
+    except ValueError as e:  # the CF baseline's corpus is not the catalog; an adapter file of another width
         raise SystemExit(str(e))
     options = dict(aisles=args.aisle, departments=args.department, diversity=args.diversity, candidates=args.candidates,
                    boosts=boosts or None, only_boosted=args.only_boosted, probes=probes, within=args.within,

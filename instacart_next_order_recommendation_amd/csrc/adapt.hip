@@ -1,0 +1,579 @@
+// adapt.hip — a query-side linear adapter learned from (context, product) pairs against the rows the index holds
+// (icrec_adapter_*).  The encoder and the stored rows stay frozen; only q' = q + D q changes, so every search composes.
+//   apply_kernel    one launch: a workgroup keeps a tile of queries in LDS, a lane owns one output's chain over c
+//   forward_kernel  the step's (a): z = apply(a), n = max(|z|, 1e-12), u = z / n
+//   logits_kernel   the step's (b): one workgroup per 32 anchors; S^T = V U^T on the f32 MFMA over gathered stored
+//                   rows, two sweeps over the candidates (row maximum and sum, then P recomputed and P V), dz in the
+//                   epilogue, one loss per anchor
+//   grad_kernel     the step's (c): one wave per 32 x 32 tile of dD = dZ^T A, walking the batch in order, AdamW in its
+//                   epilogue; one more workgroup sums the anchors' losses in index order
+// The definitions (the two roundings of apply, the masking rules, the gradient, torch's AdamW) are in include/icrec.h;
+// tests/adapter_reference.py states them in numpy and torch.  No floating-point atomics anywhere: every sum has one order.
+#include <math.h>
+
+#include <vector>
+
+#include "index.h"
+
+namespace icrec {
+
+struct Adapter {
+    float* delta = nullptr;    // [dim][dim] row-major
+    float* delta_t = nullptr;  // its transpose: apply's lane r reads delta_t[c][r], coalesced
+    float* m = nullptr;        // AdamW's first and second moments
+    float* v = nullptr;
+    int dim = 0;
+    int device = 0;
+    int64_t t = 0;             // AdamW steps taken
+};
+
+namespace {
+
+constexpr int APPLY_THREADS = 64;  // apply_kernel: one wave, a lane per output
+constexpr int APPLY_TILE = 8;      // queries of its tile: each element of D is read once per tile
+constexpr int FWD_THREADS = 256;
+constexpr int FWD_TILE = 4;        // anchors of a forward workgroup: one per wave for the norms
+constexpr int LOGIT_THREADS = 256;
+constexpr int LOGIT_WAVES = LOGIT_THREADS / 64;
+constexpr int ANCHOR_TILE = 32;
+constexpr int GRAD_DEPTH = 8;      // MFMA steps (two anchors each) whose operands grad_kernel loads at once
+constexpr int GRAD_BLOCK = 64;     // anchors of one chain of grad_kernel: the sum over the batch has two short levels
+static_assert(GRAD_BLOCK % (2 * GRAD_DEPTH) == 0, "a block of anchors is whole groups of steps");
+constexpr int MAX_OWN_TILES = ICREC_ADAPTER_MAX_DIM / 32 / LOGIT_WAVES;  // feature tiles of dU^T a wave accumulates
+static_assert(ICREC_ADAPTER_MAX_DIM % (32 * LOGIT_WAVES) == 0, "the feature tiles are dealt to the waves");
+static_assert(ICREC_ADAPTER_MAX_CANDIDATES * sizeof(int32_t) <= 32768, "a step's checked candidate rows are staged in LDS");
+static_assert(ICREC_ADAPTER_MAX_BATCH * sizeof(float) <= 4096, "the anchors' losses are staged in LDS");
+
+// acc[j] = the chain over c = 0 .. d-1 of acc = acc + (D[r][c] * q_j[c]) for the T queries at qs (LDS, [T][d]): two
+// roundings per term, c ascending.  dt is D transposed.
+template <int T>
+__device__ __forceinline__ void apply_chains(const float* __restrict__ dt, int d, int r, const float* qs, float (&acc)[T]) {
+#pragma unroll
+    for (int j = 0; j < T; ++j) acc[j] = 0.0f;
+    for (int c = 0; c < d; c += 4) {
+        float w[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u] = dt[(size_t)(c + u) * d + r];
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(qs + j * d + c);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[j] = __fadd_rn(acc[j], __fmul_rn(w[u], x[u]));
+        }
+    }
+}
+
+// Queries q0 .. q0 + T - 1 (zeros behind the last of n) -> LDS.
+template <int T>
+__device__ __forceinline__ void stage_queries(float* qs, const float* __restrict__ q, int64_t q0, int64_t n, int d, int tid,
+                                              int n_threads) {
+    for (int i = tid; i < T * d; i += n_threads) {
+        const int64_t row = q0 + i / d;
+        qs[i] = row < n ? q[row * d + i % d] : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(APPLY_THREADS) void apply_kernel(const float* __restrict__ dt, int d, const float* __restrict__ q,
+                                                              int64_t n, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float qs[APPLY_TILE * ICREC_ADAPTER_MAX_DIM];
+    const int64_t q0 = (int64_t)blockIdx.x * APPLY_TILE;
+    stage_queries<APPLY_TILE>(qs, q, q0, n, d, threadIdx.x, APPLY_THREADS);
+    __syncthreads();
+    const int r = blockIdx.y * APPLY_THREADS + threadIdx.x;
+    if (r >= d) return;
+    float acc[APPLY_TILE];
+    apply_chains<APPLY_TILE>(dt, d, r, qs, acc);
+#pragma unroll
+    for (int j = 0; j < APPLY_TILE; ++j)
+        if (q0 + j < n) out[(q0 + j) * d + r] = __fadd_rn(qs[j * d + r], acc[j]);
+}
+
+// z = apply(a) into LDS, then wave w takes anchor w of the tile: n = max(sqrt(sum z^2), 1e-12) in normalize_rows_kernel's
+// order (64 strided fmaf partials, the xor butterfly), u = z / n.
+__global__ __launch_bounds__(FWD_THREADS) void forward_kernel(const float* __restrict__ dt, int d, const float* __restrict__ a,
+                                                              int B, float* __restrict__ U, float* __restrict__ nrm) {
+    __shared__ __attribute__((aligned(16))) float as[FWD_TILE * ICREC_ADAPTER_MAX_DIM];
+    __shared__ float zs[FWD_TILE * ICREC_ADAPTER_MAX_DIM];
+    const int tid = threadIdx.x;
+    const int64_t a0 = (int64_t)blockIdx.x * FWD_TILE;
+    stage_queries<FWD_TILE>(as, a, a0, B, d, tid, FWD_THREADS);
+    __syncthreads();
+    for (int r = tid; r < d; r += FWD_THREADS) {
+        float acc[FWD_TILE];
+        apply_chains<FWD_TILE>(dt, d, r, as, acc);
+#pragma unroll
+        for (int j = 0; j < FWD_TILE; ++j) zs[j * d + r] = __fadd_rn(as[j * d + r], acc[j]);
+    }
+    __syncthreads();
+    const int lane = tid & 63, j = tid >> 6;
+    const int64_t i = a0 + j;
+    if (i >= B) return;
+    float s = 0.0f;
+    for (int c = lane; c < d; c += 64) s = fmaf(zs[j * d + c], zs[j * d + c], s);
+    const float len = sqrtf(wave_sum_f32(s));
+    const float den = len > 1e-12f ? len : 1e-12f;
+    for (int c = lane; c < d; c += 64) U[i * d + c] = zs[j * d + c] / den;
+    if (lane == 0) nrm[i] = den;
+}
+
+__device__ __forceinline__ float stored_value(const float* p) { return *p; }
+__device__ __forceinline__ float stored_value(const uint16_t* p) { return __uint_as_float((uint32_t)*p << 16); }
+
+// (m, l) of a softmax over two disjoint parts: the maximum, and the sums moved onto it; (-inf, 0) is the empty part.
+__device__ __forceinline__ void merge_max_sum(float& m, float& l, float m2, float l2) {
+    const float M = fmaxf(m, m2);
+    if (M == -INFINITY) return;
+    l = l * expf(m - M) + l2 * expf(m2 - M);
+    m = M;
+}
+
+// One workgroup per 32 anchors, four waves.  The tile S^T[candidate][anchor] = V U^T is gathered_tile's: operand A the
+// stored row of the tile's candidate, operand B the anchor's u, so a lane holds ONE anchor (its column, lane & 31) and
+// sixteen candidates (acc_row).  A candidate's row number is checked once, into LDS, as -1 or the row: no other value
+// becomes an address, and a masked candidate's tile row is computed on row 0 and dropped.
+// Sweep 1: wave w walks candidate tiles w, w + 4, ..; a lane keeps the running (maximum, sum) of its anchor over its
+// candidates, then the two halves of the wave and the four waves are merged in that order.
+// Sweep 2, per group of four candidate tiles: wave w recomputes its tile, turns it into G = (P - delta) / counted and
+// leaves it in LDS as [candidate][anchor]; after the barrier every wave adds the group's four tiles, in order, into the
+// feature tiles of dU^T = V^T G it owns (tile t belongs to wave t % 4) - G as operand B needs no lane movement, operand
+// A is the stored rows' features t * 32 + (lane & 31), 128 contiguous bytes per candidate.  A group's 128 candidates
+// are one fmaf chain from zero and the groups' sums are added in group order: two short levels instead of one chain
+// of up to 8,192 terms, whose rounding error would grow with its length.
+// Epilogue: du = scale * acc, the dot u . du over the waves' feature tiles through LDS in wave order,
+// dz = (du - u (u . du)) / n.
+template <bool P16>
+__global__ __launch_bounds__(LOGIT_THREADS) void logits_kernel(const void* __restrict__ rows, int K, int64_t n_rows,
+                                                               const float* __restrict__ U, const float* __restrict__ nrm,
+                                                               const int32_t* __restrict__ cand, int B, int C, float scale,
+                                                               float* __restrict__ dZ, float* __restrict__ loss_i) {
+    typedef row_elem_t<P16> Row;
+    __shared__ int32_t crow[ICREC_ADAPTER_MAX_CANDIDATES];  // the checked row of candidate j, or -1
+    __shared__ float gs[LOGIT_WAVES][32][32];
+    __shared__ float m_s[LOGIT_WAVES][32], l_s[LOGIT_WAVES][32], dot_s[LOGIT_WAVES][32], spos[32];
+    __shared__ int counted_s;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, l31 = lane & 31;
+    const Row* stored = static_cast<const Row*>(rows);
+    if (tid == 0) counted_s = 0;
+    if (tid < 32) spos[tid] = 0.0f;
+    __syncthreads();
+    int mine = 0;
+    for (int j = tid; j < C; j += LOGIT_THREADS) {
+        const int32_t r = cand[j];
+        const bool ok = r >= 0 && (int64_t)r < n_rows;
+        crow[j] = ok ? r : -1;
+        mine += (ok && j < B) ? 1 : 0;
+    }
+    if (mine) atomicAdd(&counted_s, mine);  // an integer count: any order gives the same value
+    __syncthreads();
+    const int n_counted = counted_s;
+    const float inv_counted = n_counted > 0 ? 1.0f / (float)n_counted : 0.0f;
+    const int i = blockIdx.x * ANCHOR_TILE + l31;  // this lane's anchor
+    const bool in_b = i < B;
+    const int pos = in_b ? crow[i] : -1;
+    const bool counted = pos >= 0;
+    const float* pu = U + (size_t)(in_b ? i : B - 1) * K;
+    const int n_ct = (C + 31) / 32;
+
+    float m = -INFINITY, l = 0.0f;
+    for (int ct = w; ct < n_ct; ct += LOGIT_WAVES) {
+        const int ja = ct * 32 + l31;
+        const int ra = ja < C ? crow[ja] : -1;
+        f32x16 acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+        gathered_tile(acc, stored + (size_t)(ra < 0 ? 0 : ra) * K, pu, K, h);
+        float sv[16], tm = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int j = ct * 32 + acc_row(e, lane);
+            const int rj = j < C ? crow[j] : -1;
+            const float s = scale * acc[e];
+            if (j == i && in_b) spos[l31] = s;  // one lane of the workgroup meets its anchor's own positive
+            sv[e] = (rj < 0 || (j != i && rj == pos)) ? -INFINITY : s;
+            tm = fmaxf(tm, sv[e]);
+        }
+        if (tm > -INFINITY) {
+            const float nm = fmaxf(m, tm);
+            float add = 0.0f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) add += expf(sv[e] - nm);
+            l = l * expf(m - nm) + add;
+            m = nm;
+        }
+    }
+    {
+        const float m_o = __shfl_xor(m, 32, 64), l_o = __shfl_xor(l, 32, 64);
+        float m0 = h ? m_o : m, l0 = h ? l_o : l;  // half 0's part first, in both halves
+        merge_max_sum(m0, l0, h ? m : m_o, h ? l : l_o);
+        if (h == 0) {
+            m_s[w][l31] = m0;
+            l_s[w][l31] = l0;
+        }
+    }
+    __syncthreads();
+    float M = m_s[0][l31], L = l_s[0][l31];
+#pragma unroll
+    for (int x = 1; x < LOGIT_WAVES; ++x) merge_max_sum(M, L, m_s[x][l31], l_s[x][l31]);
+    if (!counted) {  // neither a loss nor a gradient; keep the arithmetic below finite
+        M = 0.0f;
+        L = 1.0f;
+    }
+    if (w == 0 && h == 0 && in_b) loss_i[i] = counted ? (M + logf(L)) - spos[l31] : 0.0f;
+    const float inv_l = 1.0f / L;
+
+    f32x16 du[MAX_OWN_TILES], du_group[MAX_OWN_TILES];
+#pragma unroll
+    for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) du[tt][e] = 0.0f;
+    const int n_ft = K / 32;
+    for (int g = 0; g < n_ct; g += LOGIT_WAVES) {
+        const int ct = g + w;
+        if (ct < n_ct) {
+            const int ja = ct * 32 + l31;
+            const int ra = ja < C ? crow[ja] : -1;
+            f32x16 acc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+            gathered_tile(acc, stored + (size_t)(ra < 0 ? 0 : ra) * K, pu, K, h);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int jr = acc_row(e, lane), j = ct * 32 + jr;
+                const int rj = j < C ? crow[j] : -1;
+                const bool masked = rj < 0 || (j != i && rj == pos);
+                const float p = masked ? 0.0f : expf(scale * acc[e] - M) * inv_l;
+                gs[w][jr][l31] = counted ? (p - (j == i ? 1.0f : 0.0f)) * inv_counted : 0.0f;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) du_group[tt][e] = 0.0f;
+        for (int x = 0; x < LOGIT_WAVES && g + x < n_ct; ++x) {
+            float gb[16];
+            size_t off[16];
+            bool live[16];
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {  // step s sums over candidates 2s (lanes 0-31) and 2s + 1 (lanes 32-63)
+                const int jr = 2 * s + h, j = (g + x) * 32 + jr;
+                const int rj = j < C ? crow[j] : -1;
+                gb[s] = gs[x][jr][l31];
+                live[s] = rj >= 0;
+                off[s] = (size_t)(rj < 0 ? 0 : rj) * K + l31;
+            }
+#pragma unroll
+            for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
+                const int t = w + tt * LOGIT_WAVES;
+                if (t < n_ft) {
+                    float va[16];
+#pragma unroll
+                    for (int s = 0; s < 16; ++s) va[s] = stored_value(stored + off[s] + t * 32);
+#pragma unroll
+                    for (int s = 0; s < 16; ++s)
+                        du_group[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(live[s] ? va[s] : 0.0f, gb[s], du_group[tt], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) du[tt][e] += du_group[tt][e];
+        __syncthreads();
+    }
+
+    float part = 0.0f;
+#pragma unroll
+    for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
+        const int t = w + tt * LOGIT_WAVES;
+        if (t < n_ft) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                du[tt][e] = scale * du[tt][e];
+                part += pu[t * 32 + acc_row(e, lane)] * du[tt][e];
+            }
+        }
+    }
+    {
+        const float o = __shfl_xor(part, 32, 64);
+        const float both = (h ? o : part) + (h ? part : o);
+        if (h == 0) dot_s[w][l31] = both;
+    }
+    __syncthreads();
+    float dot = dot_s[0][l31];
+#pragma unroll
+    for (int x = 1; x < LOGIT_WAVES; ++x) dot += dot_s[x][l31];
+    if (!in_b) return;
+    const float den = nrm[i];
+#pragma unroll
+    for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
+        const int t = w + tt * LOGIT_WAVES;
+        if (t < n_ft) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int f = t * 32 + acc_row(e, lane);
+                dZ[(size_t)i * K + f] = (du[tt][e] - pu[f] * dot) / den;
+            }
+        }
+    }
+}
+
+struct AdamW {
+    float lr, one_minus_b1, b2, one_minus_b2, eps, decay, bc1, sqrt_bc2;  // decay = 1 - lr * weight_decay
+};
+
+// Workgroups 0 .. (K/32)^2 - 1, one wave each: tile (tr, tc) of dD[r][c] = sum over i of dz_i[r] a_i[c], i ascending
+// (an MFMA step adds anchors 2s and 2s + 1 in that order; GRAD_BLOCK anchors are one chain, the blocks' sums are added
+// in order); with `update`, torch's AdamW on the tile's elements - each
+// element of D, its transposed copy, m and v is read and written by one lane.  The last workgroup sums the anchors'
+// losses in index order and divides by the counted anchors.
+__global__ __launch_bounds__(64) void grad_kernel(const float* __restrict__ dZ, const float* __restrict__ a, int B, int K,
+                                                  const int32_t* __restrict__ cand, int64_t n_rows,
+                                                  const float* __restrict__ loss_i, float* __restrict__ loss_out,
+                                                  float* __restrict__ grad_out, int update, AdamW o, float* __restrict__ delta,
+                                                  float* __restrict__ delta_t, float* __restrict__ m, float* __restrict__ v) {
+    const int lane = threadIdx.x, h = lane >> 5, l31 = lane & 31;
+    const int n_t = K / 32;
+    if ((int)blockIdx.x == n_t * n_t) {
+        __shared__ float ls[ICREC_ADAPTER_MAX_BATCH];
+        __shared__ int counted_s;
+        if (lane == 0) counted_s = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int i = lane; i < B; i += 64) {
+            const int32_t r = cand[i];
+            mine += (r >= 0 && (int64_t)r < n_rows) ? 1 : 0;
+            ls[i] = loss_i[i];
+        }
+        if (mine) atomicAdd(&counted_s, mine);
+        __syncthreads();
+        if (lane == 0) {
+            float s = 0.0f;
+            for (int i = 0; i < B; ++i) s += ls[i];
+            *loss_out = counted_s > 0 ? s / (float)counted_s : 0.0f;
+        }
+        return;
+    }
+    const int tr = blockIdx.x / n_t, tc = blockIdx.x % n_t;
+    const float* pz = dZ + tr * 32 + l31;
+    const float* pa = a + tc * 32 + l31;
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+    for (int b0 = 0; b0 < B; b0 += GRAD_BLOCK) {  // a block of anchors is one chain from zero; the blocks are added in order
+        f32x16 part;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) part[e] = 0.0f;
+        const int b1 = b0 + GRAD_BLOCK < B ? b0 + GRAD_BLOCK : B;
+        for (int i0 = b0; i0 < b1; i0 += 2 * GRAD_DEPTH) {  // the loads of GRAD_DEPTH steps are issued before the first MFMA
+            float z[GRAD_DEPTH], x[GRAD_DEPTH];
+#pragma unroll
+            for (int s = 0; s < GRAD_DEPTH; ++s) {
+                const int i = i0 + 2 * s + h;
+                z[s] = i < b1 ? pz[(size_t)i * K] : 0.0f;
+                x[s] = i < b1 ? pa[(size_t)i * K] : 0.0f;
+            }
+#pragma unroll
+            for (int s = 0; s < GRAD_DEPTH; ++s) part = __builtin_amdgcn_mfma_f32_32x32x2f32(z[s], x[s], part, 0, 0, 0);
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] += part[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int r = tr * 32 + acc_row(e, lane), c = tc * 32 + l31;
+        const size_t at = (size_t)r * K + c;
+        const float g = acc[e];
+        if (grad_out != nullptr) grad_out[at] = g;
+        if (update) {
+            float p = delta[at] * o.decay;
+            const float m1 = m[at] + (g - m[at]) * o.one_minus_b1;
+            const float v1 = v[at] * o.b2 + o.one_minus_b2 * g * g;
+            p = p - (o.lr / o.bc1) * (m1 / (sqrtf(v1) / o.sqrt_bc2 + o.eps));
+            delta[at] = p;
+            delta_t[(size_t)c * K + r] = p;
+            m[at] = m1;
+            v[at] = v1;
+        }
+    }
+}
+
+bool dim_ok(int32_t dim) { return dim >= 32 && dim <= ICREC_ADAPTER_MAX_DIM && dim % 32 == 0; }
+
+void release(Adapter* ad) {
+    (void)hipFree(ad->delta);
+    (void)hipFree(ad->delta_t);
+    (void)hipFree(ad->m);
+    (void)hipFree(ad->v);
+    delete ad;
+}
+
+// The workspace of a step: u [B][dim], dz [B][dim], the norms [B], the losses [B].
+struct StepWorkspace {
+    size_t u, dz, nrm, loss, total;
+    StepWorkspace(int dim, int B) {
+        const size_t rows = align256((size_t)B * dim * sizeof(float)), col = align256((size_t)B * sizeof(float));
+        u = 0;
+        dz = rows;
+        nrm = 2 * rows;
+        loss = 2 * rows + col;
+        total = 2 * rows + 2 * col;
+    }
+};
+
+}  // namespace
+}  // namespace icrec
+
+using namespace icrec;
+
+extern "C" {
+
+int icrec_adapter_create(int32_t dim, int device, icrec_adapter** out) {
+    ICREC_REQUIRE(out != nullptr, "icrec_adapter_create: NULL out");
+    *out = nullptr;
+    ICREC_REQUIRE(dim_ok(dim), "icrec_adapter_create: dim must be a multiple of 32 in [32, %d] (got %d)",
+                  ICREC_ADAPTER_MAX_DIM, dim);
+    ICREC_HIP(hipSetDevice(device));
+    Adapter* ad = new Adapter();
+    ad->dim = dim;
+    ad->device = device;
+    const size_t bytes = (size_t)dim * dim * sizeof(float);
+    float** arrays[4] = {&ad->delta, &ad->delta_t, &ad->m, &ad->v};
+    for (float** p : arrays)
+        if (hipMalloc(p, bytes) != hipSuccess || hipMemset(*p, 0, bytes) != hipSuccess) {
+            set_error("icrec_adapter_create: hipMalloc of %zu bytes failed", bytes);
+            release(ad);
+            return ICREC_ENOMEM;
+        }
+    ICREC_HIP(hipDeviceSynchronize());
+    *out = reinterpret_cast<icrec_adapter*>(ad);
+    return ICREC_OK;
+}
+
+int icrec_adapter_destroy(icrec_adapter* h) {
+    Adapter* ad = reinterpret_cast<Adapter*>(h);
+    if (ad == nullptr) return ICREC_OK;
+    (void)hipSetDevice(ad->device);
+    (void)hipDeviceSynchronize();
+    release(ad);
+    return ICREC_OK;
+}
+
+int32_t icrec_adapter_dim(const icrec_adapter* h) { return h ? reinterpret_cast<const Adapter*>(h)->dim : 0; }
+
+int icrec_adapter_set_state(icrec_adapter* h, const float* delta_host, const float* m_host, const float* v_host, int64_t t) {
+    Adapter* ad = reinterpret_cast<Adapter*>(h);
+    ICREC_REQUIRE(ad != nullptr, "icrec_adapter_set_state: NULL adapter");
+    ICREC_REQUIRE(delta_host != nullptr, "icrec_adapter_set_state: NULL delta");
+    ICREC_REQUIRE(t >= 0, "icrec_adapter_set_state: t must be >= 0 (got %lld)", (long long)t);
+    const int d = ad->dim;
+    const size_t n = (size_t)d * d, bytes = n * sizeof(float);
+    std::vector<float> tr(n);
+    for (int r = 0; r < d; ++r)
+        for (int c = 0; c < d; ++c) tr[(size_t)c * d + r] = delta_host[(size_t)r * d + c];
+    ICREC_HIP(hipSetDevice(ad->device));
+    ICREC_HIP(hipDeviceSynchronize());  // a set-up call: whatever still reads the arrays finishes first
+    ICREC_HIP(hipMemcpy(ad->delta, delta_host, bytes, hipMemcpyHostToDevice));
+    ICREC_HIP(hipMemcpy(ad->delta_t, tr.data(), bytes, hipMemcpyHostToDevice));
+    if (m_host != nullptr) ICREC_HIP(hipMemcpy(ad->m, m_host, bytes, hipMemcpyHostToDevice));
+    else ICREC_HIP(hipMemset(ad->m, 0, bytes));
+    if (v_host != nullptr) ICREC_HIP(hipMemcpy(ad->v, v_host, bytes, hipMemcpyHostToDevice));
+    else ICREC_HIP(hipMemset(ad->v, 0, bytes));
+    ICREC_HIP(hipDeviceSynchronize());
+    ad->t = t;
+    return ICREC_OK;
+}
+
+int icrec_adapter_get_state(const icrec_adapter* h, float* delta_host, float* m_host, float* v_host, int64_t* t_out) {
+    const Adapter* ad = reinterpret_cast<const Adapter*>(h);
+    ICREC_REQUIRE(ad != nullptr, "icrec_adapter_get_state: NULL adapter");
+    const size_t bytes = (size_t)ad->dim * ad->dim * sizeof(float);
+    ICREC_HIP(hipSetDevice(ad->device));
+    ICREC_HIP(hipDeviceSynchronize());
+    if (delta_host != nullptr) ICREC_HIP(hipMemcpy(delta_host, ad->delta, bytes, hipMemcpyDeviceToHost));
+    if (m_host != nullptr) ICREC_HIP(hipMemcpy(m_host, ad->m, bytes, hipMemcpyDeviceToHost));
+    if (v_host != nullptr) ICREC_HIP(hipMemcpy(v_host, ad->v, bytes, hipMemcpyDeviceToHost));
+    if (t_out != nullptr) *t_out = ad->t;
+    return ICREC_OK;
+}
+
+int icrec_adapter_apply(const icrec_adapter* h, const float* q_dev, int32_t n, float* out_dev, void* stream) {
+    const Adapter* ad = reinterpret_cast<const Adapter*>(h);
+    ICREC_REQUIRE(ad != nullptr, "icrec_adapter_apply: NULL adapter");
+    ICREC_REQUIRE(q_dev != nullptr && out_dev != nullptr, "icrec_adapter_apply: NULL q or out");
+    ICREC_REQUIRE(q_dev != out_dev, "icrec_adapter_apply: out must not be q");
+    ICREC_REQUIRE(n >= 1, "icrec_adapter_apply: n must be >= 1 (got %d)", n);
+    ICREC_HIP(hipSetDevice(ad->device));
+    const dim3 grid((unsigned)((n + APPLY_TILE - 1) / APPLY_TILE), (unsigned)((ad->dim + APPLY_THREADS - 1) / APPLY_THREADS));
+    hipLaunchKernelGGL(apply_kernel, grid, dim3(APPLY_THREADS), 0, (hipStream_t)stream, (const float*)ad->delta_t, ad->dim,
+                       q_dev, (int64_t)n, out_dev);
+    ICREC_HIP(hipGetLastError());
+    return ICREC_OK;
+}
+
+size_t icrec_adapter_step_workspace_bytes(const icrec_adapter* h, int32_t B, int32_t C) {
+    const Adapter* ad = reinterpret_cast<const Adapter*>(h);
+    if (ad == nullptr || B < 1 || B > ICREC_ADAPTER_MAX_BATCH || C < B || C > ICREC_ADAPTER_MAX_CANDIDATES) return 0;
+    return StepWorkspace(ad->dim, B).total;
+}
+
+int icrec_adapter_step(icrec_index* idx, icrec_adapter* h, const float* anchors_dev, int32_t B, const int32_t* cand_rows_dev,
+                       int32_t C, float scale, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int32_t update, float* loss_out_dev, float* grad_out_dev, void* workspace_dev, size_t workspace_bytes,
+                       void* stream) {
+    const Index* ix = reinterpret_cast<const Index*>(idx);
+    Adapter* ad = reinterpret_cast<Adapter*>(h);
+    ICREC_REQUIRE(ix != nullptr, "icrec_adapter_step: NULL idx");
+    ICREC_REQUIRE(ad != nullptr, "icrec_adapter_step: NULL adapter");
+    ICREC_REQUIRE(anchors_dev != nullptr && cand_rows_dev != nullptr, "icrec_adapter_step: NULL anchors or cand_rows");
+    ICREC_REQUIRE(loss_out_dev != nullptr, "icrec_adapter_step: NULL loss_out");
+    ICREC_REQUIRE(workspace_dev != nullptr, "icrec_adapter_step: NULL workspace");
+    ICREC_REQUIRE(ix->dim == ad->dim, "icrec_adapter_step: the index has dim %d, the adapter %d", ix->dim, ad->dim);
+    ICREC_REQUIRE(ix->device == ad->device, "icrec_adapter_step: the index is on device %d, the adapter on %d", ix->device,
+                  ad->device);
+    ICREC_REQUIRE(ix->n_rows >= 1, "icrec_adapter_step: the index has no rows");
+    ICREC_REQUIRE(B >= 1 && B <= ICREC_ADAPTER_MAX_BATCH, "icrec_adapter_step: B must be in [1, %d] (got %d)",
+                  ICREC_ADAPTER_MAX_BATCH, B);
+    ICREC_REQUIRE(C >= B && C <= ICREC_ADAPTER_MAX_CANDIDATES, "icrec_adapter_step: C must be in [B, %d] (got %d, B %d)",
+                  ICREC_ADAPTER_MAX_CANDIDATES, C, B);
+    ICREC_REQUIRE(isfinite(scale) && isfinite(lr) && isfinite(beta1) && isfinite(beta2) && isfinite(eps) && isfinite(weight_decay),
+                  "icrec_adapter_step: a hyper-parameter is not finite");
+    ICREC_REQUIRE(!update || (beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f),
+                  "icrec_adapter_step: beta1 and beta2 must be in [0, 1) and eps >= 0");
+    const StepWorkspace ws(ad->dim, B);
+    ICREC_REQUIRE(workspace_bytes >= ws.total, "icrec_adapter_step: the workspace has %zu bytes, %zu are needed",
+                  workspace_bytes, ws.total);
+    ICREC_HIP(hipSetDevice(ad->device));
+    hipStream_t st = (hipStream_t)stream;
+    char* base = static_cast<char*>(workspace_dev);
+    float* U = reinterpret_cast<float*>(base + ws.u);
+    float* dZ = reinterpret_cast<float*>(base + ws.dz);
+    float* nrm = reinterpret_cast<float*>(base + ws.nrm);
+    float* loss_i = reinterpret_cast<float*>(base + ws.loss);
+    const int d = ad->dim;
+    AdamW o{};
+    if (update) {  // the bias corrections of step t + 1, in double
+        const double t1 = (double)(ad->t + 1);
+        o.lr = lr;
+        o.one_minus_b1 = (float)(1.0 - (double)beta1);
+        o.b2 = beta2;
+        o.one_minus_b2 = (float)(1.0 - (double)beta2);
+        o.eps = eps;
+        o.decay = (float)(1.0 - (double)lr * (double)weight_decay);
+        o.bc1 = (float)(1.0 - pow((double)beta1, t1));
+        o.sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, t1));
+    }
+    hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((B + FWD_TILE - 1) / FWD_TILE)), dim3(FWD_THREADS), 0, st,
+                       (const float*)ad->delta_t, d, anchors_dev, (int)B, U, nrm);
+    hipLaunchKernelGGL((rows_are_bf16(ix) ? logits_kernel<true> : logits_kernel<false>),
+                       dim3((unsigned)((B + ANCHOR_TILE - 1) / ANCHOR_TILE)), dim3(LOGIT_THREADS), 0, st, (const void*)ix->rows, d,
+                       ix->n_rows, (const float*)U, (const float*)nrm, cand_rows_dev, (int)B, (int)C, scale, dZ, loss_i);
+    hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((d / 32) * (d / 32) + 1)), dim3(64), 0, st, (const float*)dZ, anchors_dev,
+                       (int)B, d, cand_rows_dev, ix->n_rows, (const float*)loss_i, loss_out_dev, grad_out_dev, update ? 1 : 0, o,
+                       ad->delta, ad->delta_t, ad->m, ad->v);
+    ICREC_HIP(hipGetLastError());
+    if (update) ad->t += 1;
+    return ICREC_OK;
+}
+
+}  // extern "C"

@@ -32,7 +32,7 @@ class _Captured:
     unified addressing) — round 3's graph had four device-to-device and two device-to-host copy nodes around the 47
     kernels."""
 
-    def __init__(self, enc: DeviceEncoder, index: DeviceIndex, bucket: int, k: int):
+    def __init__(self, enc: DeviceEncoder, index: DeviceIndex, bucket: int, k: int, adapter=None):
         dev = enc.device
         self.bucket, self.k = bucket, k
         # device staging, one H2D per request: [cu (2) | excl_off (2) | ids (bucket) | excl_idx (MAX_EXCLUDED)]; the views
@@ -44,6 +44,8 @@ class _Captured:
         self.ids = self.d_in[4:4 + bucket]
         self.excl_idx = self.d_in[4 + bucket:]
         self.emb = torch.empty((1, enc.shape.hidden), dtype=torch.float32, device=dev)
+        # with a query adapter: one apply node between the two bodies, into a buffer of its own (the graph stays a chain)
+        self.adapted = torch.empty_like(self.emb) if adapter is not None else None
         # results: written by icrec_search directly into pinned host memory
         self.h_idx = torch.full((1, k), -1, dtype=torch.int64).pin_memory()
         self.h_sc = torch.zeros((1, k), dtype=torch.float32).pin_memory()
@@ -59,7 +61,11 @@ class _Captured:
             enc.encode_into(self.ids, self.cu, 1, bucket, bucket, self.emb, self.enc_ws)
 
         def body_search():
-            index.search_into(self.emb, k, self.excl_idx, self.excl_off, self.out_idx, self.out_sc, self.srch_ws)
+            q = self.emb
+            if adapter is not None:
+                adapter.apply_into(self.emb, self.adapted)
+                q = self.adapted
+            index.search_into(q, k, self.excl_idx, self.excl_off, self.out_idx, self.out_sc, self.srch_ws)
 
         self._bodies = (body_encode, body_search)
         side = torch.cuda.Stream(device=dev)
@@ -95,8 +101,8 @@ class _Captured:
 class SingleRequestPath:
     """encode + search for ONE query through a replayed hipGraph."""
 
-    def __init__(self, encoder: DeviceEncoder, index: DeviceIndex):
-        self.encoder, self.index = encoder, index
+    def __init__(self, encoder: DeviceEncoder, index: DeviceIndex, adapter=None):
+        self.encoder, self.index, self.adapter = encoder, index, adapter
         # requests of 257 tokens up to the encoder's ceiling share one bucket at that ceiling (9-16 key tiles)
         ceiling = encoder.max_seq_length
         self.buckets = BUCKETS + ((ceiling,) if ceiling > BUCKETS[-1] else ())
@@ -108,6 +114,13 @@ class SingleRequestPath:
         argument of the captured search kernels and reserve moves the arrays they point to."""
         torch.cuda.synchronize(self.encoder.device)
         self._graphs.clear()
+
+    def set_adapter(self, adapter) -> None:
+        """The QueryAdapter every captured request applies between its encode and its search, or None: none.  The graphs
+        are dropped - the apply is a node of theirs.  Training the adapter in place changes no pointer and needs no
+        reset: a replay follows the weights it finds."""
+        self.reset()
+        self.adapter = adapter
 
     def supports(self, n_tokens: int, k: int, n_excluded: int) -> bool:
         return 1 <= n_tokens <= self.buckets[-1] and n_excluded <= MAX_EXCLUDED and k <= self.index.n_rows
@@ -125,7 +138,7 @@ class SingleRequestPath:
         bucket = next(b for b in self.buckets if n <= b)
         c = self._graphs.get((bucket, k))
         if c is None:
-            c = self._graphs[(bucket, k)] = _Captured(self.encoder, self.index, bucket, k)
+            c = self._graphs[(bucket, k)] = _Captured(self.encoder, self.index, bucket, k, self.adapter)
         h = c.h_in
         h[0] = 0
         h[1] = n

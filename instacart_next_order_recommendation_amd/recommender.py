@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _native
+from .adapter import DEFAULT_SCALE, QueryAdapter, fit_plan
 from .encoder import DeviceEncoder
 from .model_io import LoadedModel, load_model_dir
 from .search import (DeviceIndex, IvfIndex, apply_moves, facet_masks, fuse_select, rowset_bits, rowset_ids, rrf_weights,
@@ -528,6 +529,29 @@ def compose_plan(like, unlike, query_weight, like_weight, unlike_weight, n_queri
     return [None if t is None else (a, t) for t in terms]
 
 
+def adapter_pairs_plan(pairs, pid_to_row, epochs, batch_size, negatives, lr, weight_decay, scale):
+    """Recommender.fit_adapter's arguments, checked before any GPU work: pairs is a sequence of (context text, product
+    id) -> (the texts, the catalog rows of their products).  ValueError: a string or a mapping for pairs, an entry that
+    is not a (text, id) pair, a context that is not a string, a product id the catalog does not have (a pair teaches
+    nothing without its stored row), and fit_plan's: no pair, sizes outside the kernel's limits, a hyper-parameter that
+    is not a finite number."""
+    if isinstance(pairs, (str, bytes)) or hasattr(pairs, "items"):
+        raise ValueError("pairs must be a sequence of (context text, product id)")
+    texts, rows = [], []
+    for i, pair in enumerate(pairs):
+        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
+            raise ValueError(f"pair {i} is not a (context text, product id) pair: {pair!r}")
+        text, pid = pair
+        if not isinstance(text, str):
+            raise ValueError(f"the context of pair {i} must be a string, got {type(text).__name__}")
+        if pid not in pid_to_row:
+            raise ValueError(f"unknown product id {pid!r} in pair {i}: an adapter is trained against the catalog's stored rows")
+        texts.append(text)
+        rows.append(int(pid_to_row[pid]))
+    fit_plan(len(texts), epochs, batch_size, negatives, lr, weight_decay, scale)
+    return texts, rows
+
+
 @dataclass(frozen=True)
 class RequestPlan:
     """What a request asks beyond (queries, top_k, exclusions), checked (Recommender._plan); None / False: not asked."""
@@ -610,9 +634,11 @@ class Recommender:
     aisles: Optional[list[str]] = None  # the catalog's aisle and department names (_set_facets); None: it has no facets
     departments: Optional[list[str]] = None
     _cf = None  # the ItemItemCFBaseline over the same products (cf=), ranked by requests that pass `history`
+    _adapter: Optional[QueryAdapter] = None  # the query adapter every text query goes through (adapter=, set_adapter)
+    _fast = None
 
     def __init__(self, model_dir: Path | str, corpus_path: Path, batch_size: int = 64, use_index: bool = True,
-                 ann_lists: int | None = None, product_sets=None, cf=None):
+                 ann_lists: int | None = None, product_sets=None, cf=None, adapter=None):
         self.model_dir = self._resolve_model_dir(model_dir)
         self.corpus_path = Path(corpus_path).resolve()
         self.product_ids, self.product_texts = self._load_corpus()
@@ -636,6 +662,8 @@ class Recommender:
             from .fastpath import SingleRequestPath
 
             self._fast = SingleRequestPath(self.model.encoder, self._index)
+        if adapter is not None:
+            self.set_adapter(adapter)
 
     # -- construction helpers (names follow the reference) ---------------------------------
     def _resolve_model_dir(self, model_dir: Path | str) -> Path | str:
@@ -695,6 +723,42 @@ class Recommender:
             raise ValueError("cf.corpus_ids must be the catalog's product_ids, the same ids in the same order: the CF "
                              "candidates are numbered like the catalog rows")
         self._cf = cf
+
+    def set_adapter(self, adapter) -> None:
+        """Install a query adapter - a QueryAdapter, or the path of a file QueryAdapter.save wrote - or remove it (None).
+        The adapter is the recommender's, not a request's: every query with a text part (recommend, recommend_batch,
+        recommend_batches, recommend_batch_timed) is q' = q + D q right after the encode, before like / unlike compose
+        it; recommend_from_products and similar_products, whose queries are stored rows already, do not use it.  With
+        None nothing new is launched anywhere.  The captured single-request graphs are dropped and captured again on
+        the next request (with the adapter they hold one more node); training the installed adapter in place needs no
+        reset.  A set-up call, like update_products.  ValueError: an adapter of another width or on another device."""
+        if adapter is not None and not isinstance(adapter, QueryAdapter):
+            adapter = QueryAdapter.load(adapter, self.device)
+        if adapter is not None and (adapter.dim != self._index.dim or adapter.device != self.device):
+            raise ValueError(f"the adapter is {adapter.dim} wide on {adapter.device}, the index {self._index.dim} wide on "
+                             f"{self.device}")
+        self._adapter = adapter
+        if self._fast is not None:
+            self._fast.set_adapter(adapter)
+
+    def fit_adapter(self, pairs, epochs: int = 5, batch_size: int = 64, negatives: int = 0, lr: float = 2e-3,
+                    weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0) -> list[float]:
+        """Learn the query adapter from (context text, product id) pairs - clicks or purchases on this catalog - with the
+        reference's loss (MultipleNegativesRankingLoss, scale 30; QueryAdapter.fit) -> the per-step losses.  The
+        contexts are encoded once with the frozen encoder; the positives are catalog products, so their embeddings are
+        the index's stored rows and no product is encoded.  The installed adapter is trained further, in place (the
+        captured graphs stay and answer from the new weights); without one a new adapter is trained and installed.
+        negatives: extra rows drawn from the whole catalog per step, beside the in-batch negatives.  ValueError before
+        any GPU work: adapter_pairs_plan's - above all a product id the catalog does not have.  A set-up call: never
+        while a request is being served."""
+        texts, rows = adapter_pairs_plan(pairs, self._pid_to_row, epochs, batch_size, negatives, lr, weight_decay, scale)
+        anchors = self.model.encode_to_device(texts)
+        adapter = self._adapter if self._adapter is not None else QueryAdapter(self._index.dim, self.device)
+        losses = adapter.fit(self._index, anchors, rows, epochs, batch_size, negatives, lr, weight_decay, scale, seed)
+        torch.cuda.current_stream(self.device).synchronize()  # the graphs replay on a stream of their own
+        if adapter is not self._adapter:
+            self.set_adapter(adapter)
+        return losses
 
     def _member_row(self, product_ids) -> np.ndarray:
         """bool [n_products]: which catalog rows the given product ids name; ids the catalog does not have are skipped."""
@@ -928,9 +992,9 @@ class Recommender:
 
     def _encode_search(self, ids: np.ndarray, cu: np.ndarray, k: int, ex, plan: RequestPlan, timed: bool = False):
         """Packed token ids -> (idx, scores) host arrays [n, k] through the un-captured encode and search on the
-        current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  With plan.compose the
-        encoder's vectors are replaced by the composed queries right after the encode (_composed; it counts into the
-        search time); ids None (recommend_from_products) runs no encoder at all: the queries are plan.compose's terms
+        current stream; timed=True adds (encode ms, search ms) from HIP events around the two.  With an adapter set the
+        encoder's vectors go through it first (QueryAdapter.apply); with plan.compose they are then replaced by the
+        composed queries (_composed; both count into the search time); ids None (recommend_from_products) runs no encoder at all: the queries are plan.compose's terms
         alone.  The search is three steps:
         1. the SOURCE ranking, w wide: the IVF index's with plan.probes (it takes exclusions only), else
            DeviceIndex.ranked under plan.allow's masks and plan.sets' ids (with plan.boost the listed rows are merged in);
@@ -952,6 +1016,8 @@ class Recommender:
         emb = self.model.encoder.encode_packed_host(ids, cu) if ids is not None else None
         if ev:
             ev[1].record(stream)
+        if self._adapter is not None and emb is not None:
+            emb = self._adapter.apply(emb)
         if plan.compose is not None:
             emb = self._composed(emb, plan.compose)
         if plan.fuse is not None:
@@ -1077,7 +1143,14 @@ class Recommender:
         def exclude(j):
             return self._exclusion_rows(exclude_product_ids[j]) if exclude_product_ids is not None else None
 
-        for idx, sc in pipelined_search(self.model.tokenizer, self.model.encoder, self._index.search, batches, k, exclude):
+        search = self._index.search
+        if self._adapter is not None:
+            adapter = self._adapter
+
+            def search(emb, k, excl):
+                return self._index.search(adapter.apply(emb), k, excl)
+
+        for idx, sc in pipelined_search(self.model.tokenizer, self.model.encoder, search, batches, k, exclude):
             yield [self._to_results(idx[i], sc[i]) for i in range(idx.shape[0])]
 
     def recommend_batch_timed(self, queries: Sequence[str], top_k: int = 10, exclude_product_ids=None, *, aisles=None,
@@ -1232,7 +1305,7 @@ class Recommender:
         """The hipGraph single-request path, rebuilt when the index or the model was replaced under it (a captured
         graph bakes the index / encoder handles), or None under ICREC_USE_GRAPH=0."""
         if self._fast is not None and (self._fast.index is not self._index or self._fast.encoder is not self.model.encoder):
-            self._fast = type(self._fast)(self.model.encoder, self._index)
+            self._fast = type(self._fast)(self.model.encoder, self._index, self._adapter)
         return self._fast
 
 
