@@ -6,7 +6,13 @@
 //                   rows, two sweeps over the candidates (row maximum and sum, then P recomputed and P V), dz in the
 //                   epilogue, one loss per anchor
 //   grad_kernel     the step's (c): one wave per 32 x 32 tile of dD = dZ^T A, walking the batch in order, AdamW in its
-//                   epilogue; one more workgroup sums the anchors' losses in index order
+//                   epilogue; one more workgroup sums the anchors' losses: each block of GRAD_BLOCK = 64 anchors is
+//                   one chain from zero in index order, the blocks' sums are added in block order - the order of
+//                   every other sum of this unit - both levels in double, then the division by the counted anchors
+//                   and the mean's one rounding to float32 (as one float32 chain the B = 1,024 losses measured 3.26x
+//                   the float32 reference's error at width 32, beside a margin of 2; in two float32 levels a batch
+//                   of 65 still measured 6.29x beside a margin of 6: a chain of 64 rounds at the sum's ulp 64 times
+//                   and the mean is compared at half of ITS ulp)
 // The definitions (the two roundings of apply, the masking rules, the gradient, torch's AdamW) are in include/icrec.h;
 // tests/adapter_reference.py states them in numpy and torch.  No floating-point atomics anywhere: every sum has one order.
 #include <math.h>
@@ -43,6 +49,8 @@ constexpr int MAX_OWN_TILES = ICREC_ADAPTER_MAX_DIM / 32 / LOGIT_WAVES;  // feat
 static_assert(ICREC_ADAPTER_MAX_DIM % (32 * LOGIT_WAVES) == 0, "the feature tiles are dealt to the waves");
 static_assert(ICREC_ADAPTER_MAX_CANDIDATES * sizeof(int32_t) <= 32768, "a step's checked candidate rows are staged in LDS");
 static_assert(ICREC_ADAPTER_MAX_BATCH * sizeof(float) <= 4096, "the anchors' losses are staged in LDS");
+constexpr int LOSS_BLOCKS = (ICREC_ADAPTER_MAX_BATCH + GRAD_BLOCK - 1) / GRAD_BLOCK;  // blocks of anchors whose losses a lane sums
+static_assert(LOSS_BLOCKS <= 64, "one lane of the last workgroup per block of losses");
 
 // acc[j] = the chain over c = 0 .. d-1 of acc = acc + (D[r][c] * q_j[c]) for the T queries at qs (LDS, [T][d]): two
 // roundings per term, c ascending.  dt is D transposed.
@@ -326,7 +334,8 @@ struct AdamW {
 // (an MFMA step adds anchors 2s and 2s + 1 in that order; GRAD_BLOCK anchors are one chain, the blocks' sums are added
 // in order); with `update`, torch's AdamW on the tile's elements - each
 // element of D, its transposed copy, m and v is read and written by one lane.  The last workgroup sums the anchors'
-// losses in index order and divides by the counted anchors.
+// losses in the same two levels, in double - lane b adds block b's GRAD_BLOCK losses from zero in index order, lane 0
+// adds the blocks' sums in block order - and divides by the counted anchors: the mean is rounded to float32 once.
 __global__ __launch_bounds__(64) void grad_kernel(const float* __restrict__ dZ, const float* __restrict__ a, int B, int K,
                                                   const int32_t* __restrict__ cand, int64_t n_rows,
                                                   const float* __restrict__ loss_i, float* __restrict__ loss_out,
@@ -336,6 +345,7 @@ __global__ __launch_bounds__(64) void grad_kernel(const float* __restrict__ dZ, 
     const int n_t = K / 32;
     if ((int)blockIdx.x == n_t * n_t) {
         __shared__ float ls[ICREC_ADAPTER_MAX_BATCH];
+        __shared__ double bs[LOSS_BLOCKS];
         __shared__ int counted_s;
         if (lane == 0) counted_s = 0;
         __syncthreads();
@@ -347,10 +357,18 @@ __global__ __launch_bounds__(64) void grad_kernel(const float* __restrict__ dZ, 
         }
         if (mine) atomicAdd(&counted_s, mine);
         __syncthreads();
+        const int n_b = (B + GRAD_BLOCK - 1) / GRAD_BLOCK;
+        if (lane < n_b) {  // lane b: block b's losses, one chain from zero in index order, in double
+            const int b1 = (lane + 1) * GRAD_BLOCK < B ? (lane + 1) * GRAD_BLOCK : B;
+            double s = 0.0;
+            for (int i = lane * GRAD_BLOCK; i < b1; ++i) s += (double)ls[i];
+            bs[lane] = s;
+        }
+        __syncthreads();
         if (lane == 0) {
-            float s = 0.0f;
-            for (int i = 0; i < B; ++i) s += ls[i];
-            *loss_out = counted_s > 0 ? s / (float)counted_s : 0.0f;
+            double s = 0.0;
+            for (int b = 0; b < n_b; ++b) s += bs[b];  // the blocks' sums in block order
+            *loss_out = counted_s > 0 ? (float)(s / (double)counted_s) : 0.0f;  // the mean's one float32 rounding
         }
         return;
     }

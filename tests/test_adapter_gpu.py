@@ -12,8 +12,8 @@ from instacart_next_order_recommendation_amd import _native
 from instacart_next_order_recommendation_amd.adapter import QueryAdapter
 from instacart_next_order_recommendation_amd.search import DeviceIndex
 from tests import adapter_reference as ref
+from tests.adapter_cases import candidates, check_step, small_delta, unit_rows
 from tests.search_harness import torch_cuda  # noqa: F401
-from tests.token_states import check
 
 pytestmark = pytest.mark.gpu
 
@@ -21,16 +21,9 @@ DEV = "cuda:0"
 
 #: margin on E_ref per (storage, dim), for the gradient's rms and max-abs error and for the loss: the smallest of
 #: {2, 3, 4, 6, 8} that leaves 1.5x headroom over the worst ratio measured on the MI355X (profiles/adapter_errors.md)
-MARGINS = {("f32", 32): 2, ("f32", 64): 4, ("f32", 96): 6, ("f32", 384): 6, ("bf16", 384): 6, ("bf16", 768): 6}
-
-
-def unit_rows(rng, n, d):
-    x = rng.standard_normal((n, d))
-    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
-
-
-def small_delta(rng, d):
-    return (rng.standard_normal((d, d)) * (0.05 / np.sqrt(d))).astype(np.float32)
+MARGINS = {("f32", 32): 2, ("f32", 64): 4, ("f32", 96): 6, ("f32", 384): 6, ("bf16", 384): 6, ("bf16", 768): 6,
+           # the pairs only tests/test_adapter_edges_gpu.py runs (worst ratios 1.09, 1.05, 1.08, 1.08, 1.01)
+           ("bf16", 64): 2, ("bf16", 128): 2, ("f32", 768): 2, ("f32", 1024): 2, ("bf16", 1024): 2}
 
 
 def adapter_with(delta, m=None, v=None, t=0) -> QueryAdapter:
@@ -66,30 +59,6 @@ def test_apply_is_bit_exact_and_batch_independent(torch_cuda, d):
 
 
 # ---------------------------------------------------------------- loss and gradient
-def candidates(kind, rng, B, C, n_rows):
-    """The candidate rows of a case: distinct rows, or one of the special lists (B >= 8, C >= B + 4)."""
-    cand = rng.choice(n_rows, C, replace=False) if C <= n_rows else rng.integers(0, n_rows, C)
-    if kind == "repeated positives":
-        cand[1] = cand[0]
-        cand[B - 1] = cand[0]
-        cand[5] = cand[4]
-    elif kind == "negative equals a positive":
-        cand[B] = cand[2]
-        cand[B + 1] = cand[2]
-        cand[C - 1] = cand[B - 1]
-    elif kind == "ids out of range":
-        cand[B] = -1
-        cand[B + 2] = n_rows
-        cand[C - 1] = 2**31 - 1
-    elif kind == "positive out of range":
-        cand[0] = n_rows
-        cand[3] = -1
-        cand[B - 1] = -(2**31)
-    else:
-        assert kind == "plain"
-    return cand.astype(np.int64)
-
-
 CASES = [  # (dim, B, C, storage, scale, kind)
     (32, 2, 2, "f32", 30.0, "plain"),
     (96, 33, 33, "f32", 30.0, "plain"),
@@ -123,15 +92,8 @@ def test_loss_and_gradient_within_margin_of_the_float32_reference(torch_cuda, di
     ad = adapter_with(delta)
     loss, grad = ad.loss_and_grad(ix, torch.from_numpy(anchors).to(DEV), torch.from_numpy(cand), scale)
     loss, grad = float(loss.cpu()), grad.cpu().numpy()
-    assert np.isfinite(loss) and np.isfinite(grad).all()
-    margin = MARGINS[(storage, dim)]
-    # the loss: a float32 value is in general half an ulp off, whatever luck the float32 reference had on this draw
-    e_ref = max(abs(ref_loss - want_loss), float(np.spacing(np.float32(abs(want_loss)))) / 2)
-    e_gpu = abs(loss - want_loss)
     what = f"adapter {storage} d{dim} B{B} C{C} scale {scale:g} {kind}"
-    print(f"RATIO {what} loss: E_gpu {e_gpu:.3e}, E_ref {e_ref:.3e}, ratio {e_gpu / e_ref:.2f} (margin {margin})")
-    check(what + " grad", grad, want_grad, ref_grad, (margin, margin))
-    assert e_gpu <= margin * e_ref, what
+    check_step(what, loss, grad, want_loss, want_grad, ref_loss, ref_grad, MARGINS[(storage, dim)])
     assert ad.steps == 0 and np.array_equal(ad.state()["delta"], delta)  # loss_and_grad changes nothing
     ix.close()
 

@@ -1,6 +1,7 @@
 """icrec_compose_queries on the GPU against tests/compose_reference.py: every comparison is on the bits.  The shapes are
 the smallest that reach each path of the kernel - U = 8 stored rows in flight per thread, so term counts 0, 1, U, U + 1,
-2U + 1 and a longer list cut by max_terms; 16-byte pieces of 4 fp32 or 8 bf16 values over 256 threads, so dims 32 (a
+2U + 1 and a longer list cut by max_terms, and 255, 256, 257, 1,024 and a cut 1,030 at max_terms = ICREC_MAX_TERMS, where
+the 256 threads stage a segment in several passes; 16-byte pieces of 4 fp32 or 8 bf16 values over 256 threads, so dims 32 (a
 few lanes own a piece), 96 (fp32 only), 384 and 4,096 (a thread walks several pieces); 1, 5 and 1,025 queries - with
 term rows and weights the host would refuse, a reversed segment, shards, index edits, the search behind it and a
 captured graph."""
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from instacart_next_order_recommendation_amd import _native
 from instacart_next_order_recommendation_amd.search import DeviceIndex, apply_moves, removal_moves
 from oracle import oracle
 from tests import compose_reference as ref
@@ -102,6 +104,51 @@ def test_bit_equal_for_every_dim_storage_and_batch_size(torch_cuda, dim, storage
         one = run(ix, None, None, np.array([0, 1, 2], np.int32), np.array([N_ROWS - 1, 17], np.int32), None, 1)
         assert_bits(one, p_hat[[N_ROWS - 1, 17]])
         assert_bits(ix.export().cpu().numpy()[[N_ROWS - 1, 17]], one)
+    finally:
+        ix.close()
+
+
+LIMIT_LENGTHS = (255, 256, 257, _native.ICREC_MAX_TERMS, _native.ICREC_MAX_TERMS + 6)  # the last is cut by max_terms
+
+
+@pytest.mark.parametrize("dim,storage", [(32, "f32"), (384, "f32"), (384, "bf16")], ids=["32-f32", "384-f32", "384-bf16"])
+def test_bit_equal_at_the_term_limit(torch_cuda, dim, storage):
+    """max_terms = ICREC_MAX_TERMS: the kernel's 256 threads stage a segment and the pad behind it in a second pass
+    that holds only the pad (255, 256 terms) or its last term too (257), and in five passes (1,024 terms and the cut
+    1,030); a chain is up to 1,024 terms long."""
+    rng = np.random.default_rng(dim + 7 * len(storage))
+    P = rng.standard_normal((N_ROWS, dim)).astype(np.float32)
+    p_hat = ref.stored_rows(P, storage)
+    limit = _native.ICREC_MAX_TERMS
+    assert limit == 1024 and LIMIT_LENGTHS == (255, 256, 257, 1024, 1030)
+    off = np.concatenate([[0], np.cumsum(LIMIT_LENGTHS)]).astype(np.int32)
+    Q, nnz = len(LIMIT_LENGTHS), int(off[-1])
+    rows = rng.integers(0, N_ROWS, nnz).astype(np.int32)
+    w = rng.uniform(-1.5, 1.5, nnz).astype(np.float32)
+    rows[3::13], rows[5::17], rows[7::19] = -1, N_ROWS, INT32_MAX
+    w[4::13], w[6::17], w[8::19], w[9::7] = np.nan, np.inf, -np.inf, 0.0
+    for i, n in enumerate(LIMIT_LENGTHS):  # a term that does not count at the edges of the staging passes and of the limit
+        if n > 255:
+            rows[off[i] + 255] = -1
+        if n > 256:
+            rows[off[i] + 256], w[off[i] + 256] = 11, np.nan
+        if n > 1023:
+            rows[off[i] + 1023] = N_ROWS
+    rows[off[Q - 1] + limit:off[Q]] = rng.integers(0, N_ROWS, 6)  # behind the limit: terms that would count, with weights
+    w[off[Q - 1] + limit:off[Q]] = 100.0                          # .. nothing could hide
+    counted = [sum(ref.term_valid(rows[t], w[t], N_ROWS) for t in range(off[i], min(off[i + 1], off[i] + limit))) for i in range(Q)]
+    assert min(counted) > 150 and counted[4] > 600
+    base, a = draw_base(rng, Q, dim)
+    a[:] = [1.0, 0.0, -1.0, 0.5, 1.0]
+    ix = DeviceIndex(P, storage=storage)
+    try:
+        want = ref.compose(p_hat, base, a, off, rows, w, limit)
+        assert np.isfinite(want).all()
+        assert (bits(want[4]) != bits(ref.compose(p_hat, base[4:], a[4:], off[4:], rows, w, limit + 6)[0])).any()  # the cut shows
+        assert_bits(run(ix, base, a, off, rows, w, limit), want)
+        for i in range(Q):  # the same bits alone
+            assert_bits(run(ix, base[i:i + 1], a[i:i + 1], off[i:i + 2], rows, w, limit), want[i:i + 1])
+        assert_bits(run(ix, None, None, off, rows, w, limit), ref.compose(p_hat, None, None, off, rows, w, limit))
     finally:
         ix.close()
 
