@@ -758,6 +758,39 @@ ICREC_API int icrec_adapter_step(icrec_index* idx, icrec_adapter* adapter, const
                        const int32_t* cand_rows_dev, int32_t C, float scale, float lr, float beta1, float beta2, float eps,
                        float weight_decay, int32_t update, float* loss_out_dev, float* grad_out_dev,
                        void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The same step against the WHOLE catalog: every stored row of idx is a candidate, there is no list and no sampling -
+ * plain cross-entropy with labels.
+ *   pos_rows_dev   int32[B]           LOCAL rows of idx; pos_rows[i] is anchor i's positive
+ *   the other arguments as in icrec_adapter_step
+ * Loss.  z, n, u as above.  n_rows is idx's row count when the call is made; the rows between n_rows and the capacity
+ * (icrec_index_reserve, icrec_index_remove_rows) are never read as candidates.
+ *     s_ir = scale * (u_i . v_r) for every local row r in [0, n_rows), v_r the stored row (fp32, or bf16 widened exactly)
+ *     loss = the mean over the counted anchors of (logsumexp_r s_ir - s_i,pos_i)
+ *   Anchor i is counted iff pos_rows[i] lies in [0, n_rows); a value that failed that check never becomes an address.
+ *   An anchor that is not counted has neither a loss nor a gradient; no anchor counted: the loss is 0 and the gradient
+ *   is 0 exactly.  Nothing else is masked: two anchors may share a positive, and a row equal to some anchor's positive
+ *   is just that row.
+ * Gradient.  P = softmax_r(s_ir), G_ir = (P_ir - [r == pos_i]) / counted, du_i = scale * sum_r G_ir v_r; dz, dD and the
+ *   AdamW update as in icrec_adapter_step.
+ * Order.  The rows are cut into n_splits splits of rows_per_split rows (the last one shorter), every split but the
+ *   last a whole number of groups of 128 rows; icrec_adapter_catalog_plan states the cut, which depends on B and
+ *   n_rows only, never on the device.  A sum over rows is: a group of 128 rows one fmaf chain from zero, the groups of
+ *   a split added in order, the splits added in split order; the (maximum, sum) pairs of the softmax merge in that
+ *   same order.  No floating-point atomics: the same inputs give the same bits.
+ * Workspace: icrec_adapter_step_catalog_workspace_bytes(adapter, idx, B) bytes for idx's CURRENT row count (0 for a B
+ * outside the limits, a NULL handle or an index without rows); every byte the step reads it has written before.  Six
+ * launches on `stream`; nothing is allocated, nothing synchronises.
+ * ICREC_EINVAL, before any HIP call: a NULL among idx, adapter, anchors_dev, pos_rows_dev, loss_out_dev, the workspace;
+ * an index whose dim or device differs from the adapter's, or without rows; B outside [1, ICREC_ADAPTER_MAX_BATCH]; a
+ * workspace that is too small; a hyper-parameter that is not finite; with update != 0, a beta outside [0, 1) or a
+ * negative eps.  icrec_adapter_catalog_plan: a NULL pointer, B outside the limits, n_rows < 1. */
+ICREC_API size_t icrec_adapter_step_catalog_workspace_bytes(const icrec_adapter* adapter, const icrec_index* idx, int32_t B);
+ICREC_API int icrec_adapter_step_catalog(icrec_index* idx, icrec_adapter* adapter, const float* anchors_dev, int32_t B,
+                               const int32_t* pos_rows_dev, float scale, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, int32_t update, float* loss_out_dev, float* grad_out_dev,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
+ICREC_API int icrec_adapter_catalog_plan(const icrec_adapter* adapter, int32_t B, int64_t n_rows, int32_t* n_splits,
+                               int64_t* rows_per_split);
 
 /* Caps per facet value on a search result ("at most two products of one aisle, at most five of one department"):
  * walk each query's k candidates in their order and keep a candidate only while every capped facet still has room for

@@ -55,6 +55,7 @@ EXPORTS = [
     "icrec_boost_select_workspace_bytes", "icrec_boost_select", "icrec_compose_queries", "icrec_cap_select",
     "icrec_adapter_create", "icrec_adapter_destroy", "icrec_adapter_dim", "icrec_adapter_set_state",
     "icrec_adapter_get_state", "icrec_adapter_apply", "icrec_adapter_step_workspace_bytes", "icrec_adapter_step",
+    "icrec_adapter_step_catalog_workspace_bytes", "icrec_adapter_step_catalog", "icrec_adapter_catalog_plan",
     "icrec_ivf_create", "icrec_ivf_destroy", "icrec_ivf_lists", "icrec_ivf_layout",
     "icrec_ivf_search_workspace_bytes", "icrec_ivf_search",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
@@ -188,6 +189,10 @@ def lib() -> C.CDLL:
         "icrec_adapter_step_workspace_bytes": (sz, [vp, i32, i32]),
         "icrec_adapter_step": (C.c_int, [vp, vp, vp, i32, vp, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                          C.c_float, i32, vp, vp, vp, sz, vp]),
+        "icrec_adapter_step_catalog_workspace_bytes": (sz, [vp, vp, i32]),
+        "icrec_adapter_step_catalog": (C.c_int, [vp, vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                 C.c_float, i32, vp, vp, vp, sz, vp]),
+        "icrec_adapter_catalog_plan": (C.c_int, [vp, i32, i64, C.POINTER(i32), C.POINTER(i64)]),
         "icrec_ivf_create": (C.c_int, [vp, vp, i32, C.POINTER(vp)]),
         "icrec_ivf_destroy": (C.c_int, [vp]),
         "icrec_ivf_lists": (i32, [vp]),

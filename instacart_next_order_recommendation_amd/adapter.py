@@ -18,6 +18,7 @@ import torch
 from . import _native
 
 DEFAULT_SCALE = 30.0  # the reference's loss_scale
+ALL_NEGATIVES = "all"  # fit's negatives= for the whole catalog: every stored row is a candidate, none is drawn
 
 
 def schedule(step: int, total: int, warmup: int) -> float:
@@ -32,8 +33,9 @@ def schedule(step: int, total: int, warmup: int) -> float:
 def fit_plan(n_pairs: int, epochs, batch_size, negatives, lr, weight_decay, scale):
     """QueryAdapter.fit's sizes and hyper-parameters, checked before any GPU work -> (batch, steps per epoch, total steps,
     warm-up steps).  drop_last as the reference has it, unless there is less than one batch: then the pairs are one
-    batch.  ValueError: no pair, epochs < 1, batch_size outside [1, ICREC_ADAPTER_MAX_BATCH], negatives < 0 or
-    batch_size + negatives above ICREC_ADAPTER_MAX_CANDIDATES, lr / weight_decay / scale not finite, lr or weight_decay
+    batch.  ValueError: no pair, epochs < 1, batch_size outside [1, ICREC_ADAPTER_MAX_BATCH], negatives neither "all"
+    (every stored row, by catalog steps) nor an integer >= 0, batch_size + negatives above
+    ICREC_ADAPTER_MAX_CANDIDATES, lr / weight_decay / scale not finite, lr or weight_decay
     negative."""
     def integer(v, what, lo, hi):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
@@ -53,8 +55,9 @@ def fit_plan(n_pairs: int, epochs, batch_size, negatives, lr, weight_decay, scal
         raise ValueError("fit needs at least one (anchor, positive) pair")
     epochs = integer(epochs, "epochs", 1, 2**31 - 1)
     batch_size = integer(batch_size, "batch_size", 1, _native.ICREC_ADAPTER_MAX_BATCH)
-    negatives = integer(negatives, "negatives", 0, _native.ICREC_ADAPTER_MAX_CANDIDATES)
-    if batch_size + negatives > _native.ICREC_ADAPTER_MAX_CANDIDATES:
+    if not (isinstance(negatives, str) and negatives == ALL_NEGATIVES):  # "all": catalog steps, which have no list
+        negatives = integer(negatives, "negatives", 0, _native.ICREC_ADAPTER_MAX_CANDIDATES)
+    if not isinstance(negatives, str) and batch_size + negatives > _native.ICREC_ADAPTER_MAX_CANDIDATES:
         raise ValueError(f"batch_size + negatives = {batch_size + negatives} exceeds the limit "
                          f"{_native.ICREC_ADAPTER_MAX_CANDIDATES}")
     number(lr, "lr", 0.0)
@@ -113,16 +116,21 @@ class QueryAdapter:
                                                         _native.stream_ptr(self.device)), "icrec_adapter_apply")
 
     # -- training ------------------------------------------------------------------------------------
+    def _row_list(self, rows, what: str) -> torch.Tensor:
+        """Row numbers as an int32 device list; a row beyond int32 is out of range for any index: -1, not its low 32 bits."""
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.as_tensor(np.asarray(rows, np.int64))
+        if rows.dtype != torch.int32:
+            wide = rows.to(torch.int64)
+            rows = torch.where((wide < 0) | (wide > 2**31 - 1), torch.full_like(wide, -1), wide)
+        rows = rows.to(self.device, torch.int32).contiguous()
+        if rows.ndim != 1:
+            raise ValueError(f"{what} must be a list of rows, got shape {tuple(rows.shape)}")
+        return rows
+
     def _step(self, index, anchors, cand_rows, scale, lr, betas, eps, weight_decay, update: bool, loss_out, grad_out):
         anchors = self._rows(anchors, "anchors")
-        if not isinstance(cand_rows, torch.Tensor):
-            cand_rows = torch.as_tensor(np.asarray(cand_rows, np.int64))
-        if cand_rows.dtype != torch.int32:  # a row beyond int32 is out of range for any index: -1, not its low 32 bits
-            wide = cand_rows.to(torch.int64)
-            cand_rows = torch.where((wide < 0) | (wide > 2**31 - 1), torch.full_like(wide, -1), wide)
-        cand = cand_rows.to(self.device, torch.int32).contiguous()
-        if cand.ndim != 1:
-            raise ValueError(f"cand_rows must be a list of rows, got shape {tuple(cand.shape)}")
+        cand = self._row_list(cand_rows, "cand_rows")
         B, n_cand = int(anchors.shape[0]), int(cand.shape[0])
         L = _native.lib()
         need = int(L.icrec_adapter_step_workspace_bytes(self._h, B, n_cand))
@@ -148,12 +156,70 @@ class QueryAdapter:
         self._step(index, anchors, cand_rows, scale, lr, betas, eps, weight_decay, True, loss, grad_out)
         return loss[0]
 
-    def fit(self, index, anchor_embeddings, positive_rows, epochs: int = 5, batch_size: int = 64, negatives: int = 0,
+    def _step_catalog(self, index, anchors, positive_rows, scale, lr, betas, eps, weight_decay, update: bool, loss_out,
+                      grad_out):
+        anchors = self._rows(anchors, "anchors")
+        pos = self._row_list(positive_rows, "positive_rows")
+        B = int(anchors.shape[0])
+        if int(pos.shape[0]) != B:
+            raise ValueError(f"{B} anchors for {int(pos.shape[0])} positives")
+        L = _native.lib()
+        need = int(L.icrec_adapter_step_catalog_workspace_bytes(self._h, index._h, B))
+        ws = self._scratch.block(max(need, 256))
+        _native.check(L.icrec_adapter_step_catalog(index._h, self._h, _native.ptr(anchors), B, _native.ptr(pos), float(scale),
+                                                   float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                                   1 if update else 0, _native.ptr(loss_out), _native.ptr(grad_out),
+                                                   _native.ptr(ws), ws.numel(), _native.stream_ptr(self.device)),
+                      "icrec_adapter_step_catalog")
+
+    def loss_and_grad_catalog(self, index, anchors, positive_rows, scale: float = DEFAULT_SCALE):
+        """loss_and_grad against the WHOLE catalog: the cross-entropy of anchors [B, dim] over every stored row of index,
+        positive_rows [B] the labels (an anchor whose row is outside the index is not counted); no candidate list, no
+        sampling.  The adapter is not changed."""
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        grad = torch.empty((self.dim, self.dim), dtype=torch.float32, device=self.device)
+        self._step_catalog(index, anchors, positive_rows, scale, 0.0, (0.9, 0.999), 1e-8, 0.0, False, loss, grad)
+        return loss[0], grad
+
+    def step_catalog(self, index, anchors, positive_rows, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                     weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None,
+                     loss_out: Optional[torch.Tensor] = None):
+        """step against the whole catalog (loss_and_grad_catalog's loss): one AdamW step -> the batch's loss before the
+        step, a float32 [] device tensor.  No host synchronisation."""
+        loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=self.device)
+        self._step_catalog(index, anchors, positive_rows, scale, lr, betas, eps, weight_decay, True, loss, grad_out)
+        return loss[0]
+
+    def catalog_loss(self, index, anchors, positive_rows, scale: Optional[float] = None) -> float:
+        """The exact loss of a held-out set: the mean over its counted pairs of the cross-entropy against every stored
+        row.  Batches of at most ICREC_ADAPTER_MAX_BATCH; the batch means are combined, weighted by their counted
+        anchors, in double on the host, which is read back once.  scale=None: the adapter's own scale."""
+        anchors = self._rows(anchors, "anchors")
+        pos = self._row_list(positive_rows, "positive_rows")
+        n = int(anchors.shape[0])
+        if int(pos.shape[0]) != n:
+            raise ValueError(f"{n} anchors for {int(pos.shape[0])} positives")
+        scale = self.scale if scale is None else float(scale)
+        step = _native.ICREC_ADAPTER_MAX_BATCH
+        starts = range(0, n, step)
+        means = torch.zeros(len(starts), dtype=torch.float32, device=self.device)
+        for k, lo in enumerate(starts):
+            self._step_catalog(index, anchors[lo:lo + step], pos[lo:lo + step], scale, 0.0, (0.9, 0.999), 1e-8, 0.0, False,
+                               means[k:k + 1], None)
+        in_range = ((pos >= 0) & (pos < int(index.n_rows))).to(torch.float64)
+        counted = torch.stack([in_range[lo:lo + step].sum() for lo in starts])
+        host = torch.stack([means.to(torch.float64), counted]).cpu().numpy()  # the one read-back
+        total = float(host[1].sum())
+        return float((host[0] * host[1]).sum() / total) if total > 0 else 0.0
+
+    def fit(self, index, anchor_embeddings, positive_rows, epochs: int = 5, batch_size: int = 64, negatives=0,
             lr: float = 2e-3, weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0) -> list[float]:
         """Train on pairs (anchor_embeddings[i], the stored row positive_rows[i]) -> the per-step losses.  Each epoch
         walks a fresh shuffle in batches of batch_size with in-batch negatives plus `negatives` rows drawn from the
         whole index; the shuffles and draws come from a CPU torch.Generator seeded with `seed`, so a run is
-        reproducible.  As the reference trains: warm-up over the first 10 % of the steps, then a cosine schedule;
+        reproducible.  negatives="all": every step is a step_catalog - the exact cross-entropy against every stored
+        row, nothing drawn beside the shuffles.  As the reference trains: warm-up over the first 10 % of the steps,
+        then a cosine schedule;
         drop_last (unless there is less than one batch); scale 30.  The host is read back once, at the end."""
         rows = torch.as_tensor(np.asarray(positive_rows, np.int64))
         if rows.ndim != 1:
@@ -163,6 +229,7 @@ class QueryAdapter:
         if anchors.shape[0] != rows.shape[0]:
             raise ValueError(f"{anchors.shape[0]} anchors for {rows.shape[0]} positives")
         gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        exact = isinstance(negatives, str)  # fit_plan admitted "all" only
         rows_dev = rows.to(self.device, torch.int32)
         losses = torch.zeros(total, dtype=torch.float32, device=self.device)
         s = 0
@@ -171,6 +238,11 @@ class QueryAdapter:
             for b in range(per_epoch):
                 at = perm[b * batch:(b + 1) * batch].to(self.device)
                 cand = rows_dev[at]
+                if exact:
+                    self.step_catalog(index, anchors[at], cand, float(lr) * schedule(s, total, warmup),
+                                      weight_decay=weight_decay, scale=scale, loss_out=losses[s:s + 1])
+                    s += 1
+                    continue
                 if negatives:
                     extra = torch.randint(0, index.n_rows, (int(negatives),), generator=gen, dtype=torch.int64)
                     cand = torch.cat([cand, extra.to(self.device, torch.int32)])

@@ -23,7 +23,7 @@ encoder.  `fit-adapter` as the first argument learns one from (context, product)
 
     python -m instacart_next_order_recommendation_amd fit-adapter --config configs/inference.yaml --pairs FILE.jsonl
                                                                   --out FILE [--epochs N] [--batch-size B]
-                                                                  [--negatives M] [--lr LR] [--weight-decay WD]
+                                                                  [--negatives M|all] [--lr LR] [--weight-decay WD]
                                                                   [--scale S] [--seed N]
 
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
@@ -85,6 +85,11 @@ def read_pairs(path: Path) -> list[tuple[str, str]]:
     return pairs
 
 
+def negatives_arg(text: str):
+    """--negatives: an integer, or 'all' (QueryAdapter.fit's negatives="all")."""
+    return "all" if text == "all" else int(text)
+
+
 def fit_adapter_main(argv) -> int:
     ap = argparse.ArgumentParser(prog="instacart_next_order_recommendation_amd fit-adapter",
                                  description="Learn a query adapter from (context, product) pairs on the GPU.")
@@ -95,7 +100,9 @@ def fit_adapter_main(argv) -> int:
     ap.add_argument("--adapter", type=Path, default=None, metavar="FILE", help="an adapter to train further")
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batch-size", type=int, default=64)
-    ap.add_argument("--negatives", type=int, default=0, help="extra catalog rows drawn per step beside the in-batch negatives")
+    ap.add_argument("--negatives", type=negatives_arg, default=0, metavar="M|all",
+                    help="extra catalog rows drawn per step beside the in-batch negatives; 'all': every step is the exact "
+                         "cross-entropy against the whole catalog, nothing is drawn")
     ap.add_argument("--lr", type=float, default=2e-3)
     ap.add_argument("--weight-decay", type=float, default=0.01)
     ap.add_argument("--scale", type=float, default=30.0, help="the loss scale (the reference trains with 30)")

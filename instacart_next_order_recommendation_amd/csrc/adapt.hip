@@ -13,6 +13,8 @@
 //                   the float32 reference's error at width 32, beside a margin of 2; in two float32 levels a batch
 //                   of 65 still measured 6.29x beside a margin of 6: a chain of 64 rounds at the sum's ulp 64 times
 //                   and the mean is compared at half of ITS ulp)
+//   catalog_*       the step against the WHOLE catalog (icrec_adapter_step_catalog): (b) split over (anchor tiles x
+//                   row splits) workgroups with an ordered merge between its two sweeps; described where they stand
 // The definitions (the two roundings of apply, the masking rules, the gradient, torch's AdamW) are in include/icrec.h;
 // tests/adapter_reference.py states them in numpy and torch.  No floating-point atomics anywhere: every sum has one order.
 #include <math.h>
@@ -416,6 +418,291 @@ __global__ __launch_bounds__(64) void grad_kernel(const float* __restrict__ dZ, 
     }
 }
 
+// ---------------------------------------------------------------- the whole-catalog step (icrec_adapter_step_catalog)
+// Every stored row is a candidate, so there is no list: the rows [0, n_rows) are cut into n_splits splits of
+// rows_per_split rows (whole groups of CATALOG_GROUP = 128; the last split takes what is left), and the middle of the
+// step is a grid of (anchor tiles x splits) workgroups, sized by catalog_plan from (B, n_rows) alone.  Two sweeps, as
+// logits_kernel has them, with the merge of the splits between them:
+//   catalog_max_sum_kernel  sweep 1: (maximum, sum) of every anchor over the workgroup's split, and the positive's logit
+//   catalog_merge_kernel    the splits' pairs merged in split order -> (M, L) per anchor; the counted anchors
+//   catalog_du_kernel       sweep 2: P recomputed against (M, L), G = (P - [r == pos]) / counted, the split's part of
+//                           dU^T = V^T G, one part per split in the workspace
+//   catalog_finish_kernel   the parts added in split order, du = scale * sum, u . du, dz, the anchor's loss
+// The tiles are logits_kernel's (a lane holds ONE anchor and sixteen rows of a 32 x 32 tile), but a tile's rows are
+// CONTIGUOUS: tile row j of the tile at `first` is row first + j, a row at or behind `end` is computed on the split's
+// first row and dropped by its INDEX - nothing depends on what lies behind n_rows.
+constexpr int CATALOG_GROUP = 32 * LOGIT_WAVES;   // rows of one chain of a sum over rows: a tile per wave
+constexpr int CATALOG_TARGET_WORKGROUPS = 512;    // anchor tiles x splits aimed at: two per CU of a 256-CU chip
+constexpr int CATALOG_MAX_SPLITS = 512;
+constexpr int MERGE_DEPTH = 8;                    // splits whose values the merging kernels load at once
+constexpr int FINISH_THREADS = 256;
+constexpr int FINISH_OWN = ICREC_ADAPTER_MAX_DIM / FINISH_THREADS;  // features a finishing thread owns, at most
+static_assert(ICREC_ADAPTER_MAX_DIM % FINISH_THREADS == 0, "the features are dealt to the finishing threads");
+
+// The cut of n_rows rows for a batch of B: as many splits as bring anchor tiles x splits to CATALOG_TARGET_WORKGROUPS,
+// at most CATALOG_MAX_SPLITS and at most one per group of rows; every split the same whole number of groups, which
+// fixes their number.  It depends on nothing but its arguments.
+struct CatalogPlan {
+    int n_splits;
+    int64_t rows_per_split;
+};
+CatalogPlan catalog_plan(int B, int64_t n_rows) {
+    const int64_t n_groups = (n_rows + CATALOG_GROUP - 1) / CATALOG_GROUP;
+    const int n_tiles = (B + ANCHOR_TILE - 1) / ANCHOR_TILE;
+    int64_t want = (CATALOG_TARGET_WORKGROUPS + n_tiles - 1) / n_tiles;
+    if (want > CATALOG_MAX_SPLITS) want = CATALOG_MAX_SPLITS;
+    if (want > n_groups) want = n_groups;
+    const int64_t groups_per_split = (n_groups + want - 1) / want;
+    return CatalogPlan{(int)((n_groups + groups_per_split - 1) / groups_per_split), groups_per_split * CATALOG_GROUP};
+}
+
+// The lane's anchor of a catalog workgroup: its positive when it is counted (-1 otherwise: it equals no row).
+__device__ __forceinline__ int64_t catalog_positive(const int32_t* __restrict__ pos_rows, int i, int B, int64_t n_rows) {
+    if (i >= B) return -1;
+    const int32_t r = pos_rows[i];
+    return (r >= 0 && (int64_t)r < n_rows) ? (int64_t)r : -1;
+}
+
+// Sweep 1.  Per group of 128 rows wave w takes tile w: a lane's (maximum, sum) over its sixteen rows, the two halves of
+// the wave merged (half 0 first), the four waves' pairs through LDS merged in wave order into the group's pair, the
+// groups' pairs merged in group order - every wave keeps the same running pair.  The pairs of a group are double
+// buffered, so one barrier per group stands between its writes and its reads.
+template <bool P16>
+__global__ __launch_bounds__(LOGIT_THREADS) void catalog_max_sum_kernel(const void* __restrict__ rows, int K, int64_t n_rows,
+                                                                        int64_t rows_per_split, const float* __restrict__ U,
+                                                                        const int32_t* __restrict__ pos_rows, int B, float scale,
+                                                                        float* __restrict__ m_part, float* __restrict__ l_part,
+                                                                        float* __restrict__ s_pos) {
+    typedef row_elem_t<P16> Row;
+    __shared__ float m_s[2][LOGIT_WAVES][32], l_s[2][LOGIT_WAVES][32];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, l31 = lane & 31;
+    const Row* stored = static_cast<const Row*>(rows);
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_split;
+    const int64_t end = r0 + rows_per_split < n_rows ? r0 + rows_per_split : n_rows;
+    const int i = blockIdx.x * ANCHOR_TILE + l31;  // this lane's anchor
+    const bool in_b = i < B;
+    const int64_t pos = catalog_positive(pos_rows, i, B, n_rows);
+    const float* pu = U + (size_t)(in_b ? i : B - 1) * K;
+    float m = -INFINITY, l = 0.0f;
+    int buf = 0;
+    for (int64_t g0 = r0; g0 < end; g0 += CATALOG_GROUP, buf ^= 1) {
+        const int64_t first = g0 + w * 32;
+        float tm = -INFINITY, tl = 0.0f;
+        if (first < end) {
+            const int64_t ra = first + l31;
+            f32x16 acc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+            gathered_tile(acc, stored + (size_t)(ra < end ? ra : r0) * K, pu, K, h);
+            float sv[16];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int64_t r = first + acc_row(e, lane);
+                const float s = scale * acc[e];
+                if (r < end && r == pos) s_pos[i] = s;  // one lane of the grid meets a counted anchor's positive
+                sv[e] = r < end ? s : -INFINITY;
+                tm = fmaxf(tm, sv[e]);
+            }
+            if (tm > -INFINITY) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) tl += expf(sv[e] - tm);
+            }
+        }
+        const float m_o = __shfl_xor(tm, 32, 64), l_o = __shfl_xor(tl, 32, 64);
+        float m0 = h ? m_o : tm, l0 = h ? l_o : tl;  // half 0's part first, in both halves
+        merge_max_sum(m0, l0, h ? tm : m_o, h ? tl : l_o);
+        if (h == 0) {
+            m_s[buf][w][l31] = m0;
+            l_s[buf][w][l31] = l0;
+        }
+        __syncthreads();
+        float gm = m_s[buf][0][l31], gl = l_s[buf][0][l31];
+#pragma unroll
+        for (int x = 1; x < LOGIT_WAVES; ++x) merge_max_sum(gm, gl, m_s[buf][x][l31], l_s[buf][x][l31]);
+        merge_max_sum(m, l, gm, gl);
+    }
+    if (w == 0 && h == 0 && in_b) {
+        m_part[(size_t)blockIdx.y * B + i] = m;
+        l_part[(size_t)blockIdx.y * B + i] = l;
+    }
+}
+
+// One workgroup: thread i merges anchor i's pairs in split order and the workgroup counts the anchors whose positive is
+// in range.  ml[0 .. B) the maxima, ml[B .. 2B) the sums; an anchor that is not counted gets (0, 1), which keeps
+// sweep 2's arithmetic finite.
+__global__ __launch_bounds__(ICREC_ADAPTER_MAX_BATCH) void catalog_merge_kernel(const float* __restrict__ m_part,
+                                                                                const float* __restrict__ l_part, int n_splits,
+                                                                                const int32_t* __restrict__ pos_rows, int B,
+                                                                                int64_t n_rows, float* __restrict__ ml,
+                                                                                int32_t* __restrict__ counted_out) {
+    __shared__ int counted_s;
+    const int i = threadIdx.x;
+    if (i == 0) counted_s = 0;
+    __syncthreads();
+    const bool counted = catalog_positive(pos_rows, i, B, n_rows) >= 0;
+    if (counted) atomicAdd(&counted_s, 1);  // an integer count: any order gives the same value
+    if (i < B) {
+        float m = -INFINITY, l = 0.0f;
+        for (int s0 = 0; s0 < n_splits; s0 += MERGE_DEPTH) {  // the loads of MERGE_DEPTH splits are issued before the first merge
+            float pm[MERGE_DEPTH], pl[MERGE_DEPTH];
+#pragma unroll
+            for (int x = 0; x < MERGE_DEPTH; ++x) {  // behind the last split: the empty part, which changes nothing
+                const bool in = s0 + x < n_splits;
+                pm[x] = in ? m_part[(size_t)(s0 + x) * B + i] : -INFINITY;
+                pl[x] = in ? l_part[(size_t)(s0 + x) * B + i] : 0.0f;
+            }
+#pragma unroll
+            for (int x = 0; x < MERGE_DEPTH; ++x) merge_max_sum(m, l, pm[x], pl[x]);
+        }
+        ml[i] = counted ? m : 0.0f;
+        ml[B + i] = counted ? l : 1.0f;
+    }
+    __syncthreads();
+    if (i == 0) *counted_out = counted_s;
+}
+
+// Sweep 2, logits_kernel's over contiguous rows: per group of 128 rows wave w recomputes its tile, leaves
+// G = (P - [r == pos]) / counted in LDS as [row][anchor], and after the barrier every wave adds the group's tiles, in
+// order, into the feature tiles of dU^T it owns.  A group is one chain from zero, the groups are added in order; the
+// split's sums go to part[split][anchor][feature], unscaled.
+template <bool P16>
+__global__ __launch_bounds__(LOGIT_THREADS) void catalog_du_kernel(const void* __restrict__ rows, int K, int64_t n_rows,
+                                                                   int64_t rows_per_split, const float* __restrict__ U,
+                                                                   const float* __restrict__ ml,
+                                                                   const int32_t* __restrict__ counted_in,
+                                                                   const int32_t* __restrict__ pos_rows, int B, float scale,
+                                                                   float* __restrict__ part) {
+    typedef row_elem_t<P16> Row;
+    __shared__ float gs[LOGIT_WAVES][32][32];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, l31 = lane & 31;
+    const Row* stored = static_cast<const Row*>(rows);
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_split;
+    const int64_t end = r0 + rows_per_split < n_rows ? r0 + rows_per_split : n_rows;
+    const int i = blockIdx.x * ANCHOR_TILE + l31;
+    const bool in_b = i < B;
+    const int64_t pos = catalog_positive(pos_rows, i, B, n_rows);
+    const bool counted = pos >= 0;
+    const int n_counted = *counted_in;
+    const float inv_counted = n_counted > 0 ? 1.0f / (float)n_counted : 0.0f;
+    const float M = in_b ? ml[i] : 0.0f;
+    const float inv_l = 1.0f / (in_b ? ml[B + i] : 1.0f);
+    const float* pu = U + (size_t)(in_b ? i : B - 1) * K;
+    const int n_ft = K / 32;
+
+    f32x16 du[MAX_OWN_TILES], du_group[MAX_OWN_TILES];
+#pragma unroll
+    for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) du[tt][e] = 0.0f;
+    for (int64_t g0 = r0; g0 < end; g0 += CATALOG_GROUP) {
+        const int64_t first = g0 + w * 32;
+        if (first < end) {
+            const int64_t ra = first + l31;
+            f32x16 acc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+            gathered_tile(acc, stored + (size_t)(ra < end ? ra : r0) * K, pu, K, h);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int jr = acc_row(e, lane);
+                const int64_t r = first + jr;
+                const float p = r < end ? expf(scale * acc[e] - M) * inv_l : 0.0f;
+                gs[w][jr][l31] = counted ? (p - (r == pos ? 1.0f : 0.0f)) * inv_counted : 0.0f;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) du_group[tt][e] = 0.0f;
+        for (int x = 0; x < LOGIT_WAVES && g0 + x * 32 < end; ++x) {
+            float gb[16];
+            size_t off[16];
+            bool live[16];
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {  // step s sums over rows 2s (lanes 0-31) and 2s + 1 (lanes 32-63) of the tile
+                const int jr = 2 * s + h;
+                const int64_t r = g0 + x * 32 + jr;
+                gb[s] = gs[x][jr][l31];
+                live[s] = r < end;
+                off[s] = (size_t)(live[s] ? r : r0) * K + l31;
+            }
+#pragma unroll
+            for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
+                const int t = w + tt * LOGIT_WAVES;
+                if (t < n_ft) {
+                    float va[16];
+#pragma unroll
+                    for (int s = 0; s < 16; ++s) va[s] = stored_value(stored + off[s] + t * 32);
+#pragma unroll
+                    for (int s = 0; s < 16; ++s)
+                        du_group[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(live[s] ? va[s] : 0.0f, gb[s], du_group[tt], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) du[tt][e] += du_group[tt][e];
+        __syncthreads();
+    }
+    if (!in_b) return;
+    float* out = part + ((size_t)blockIdx.y * B + i) * K;
+#pragma unroll
+    for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
+        const int t = w + tt * LOGIT_WAVES;
+        if (t < n_ft) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) out[t * 32 + acc_row(e, lane)] = du[tt][e];
+        }
+    }
+}
+
+// One workgroup per anchor, a thread per feature f = tid, tid + 256, ..: the splits' parts added in split order,
+// du = scale * sum; u . du as each thread's chain over its features ascending, the wave's xor butterfly, the four
+// waves in wave order; dz = (du - u (u . du)) / n; the anchor's loss (0 when it is not counted: s_pos is then not read).
+__global__ __launch_bounds__(FINISH_THREADS) void catalog_finish_kernel(const float* __restrict__ part, int n_splits, int B, int K,
+                                                                        const float* __restrict__ U, const float* __restrict__ nrm,
+                                                                        const float* __restrict__ ml, const float* __restrict__ s_pos,
+                                                                        const int32_t* __restrict__ pos_rows, int64_t n_rows,
+                                                                        float scale, float* __restrict__ dZ,
+                                                                        float* __restrict__ loss_i) {
+    __shared__ float dot_s[FINISH_THREADS / 64];
+    const int tid = threadIdx.x, i = blockIdx.x;
+    const float* pu = U + (size_t)i * K;
+    float du[FINISH_OWN], dot = 0.0f;
+#pragma unroll
+    for (int o = 0; o < FINISH_OWN; ++o) {
+        const int f = tid + o * FINISH_THREADS;
+        du[o] = 0.0f;
+        if (f < K) {
+            float acc = part[(size_t)i * K + f];
+            for (int s0 = 1; s0 < n_splits; s0 += MERGE_DEPTH) {  // loads first, then the additions in split order
+                float v[MERGE_DEPTH];
+#pragma unroll
+                for (int x = 0; x < MERGE_DEPTH; ++x) v[x] = s0 + x < n_splits ? part[((size_t)(s0 + x) * B + i) * K + f] : 0.0f;
+#pragma unroll
+                for (int x = 0; x < MERGE_DEPTH; ++x) acc = s0 + x < n_splits ? acc + v[x] : acc;
+            }
+            du[o] = scale * acc;
+            dot += pu[f] * du[o];
+        }
+    }
+    dot = wave_sum_f32(dot);
+    if ((tid & 63) == 0) dot_s[tid >> 6] = dot;
+    __syncthreads();
+    dot = dot_s[0];
+#pragma unroll
+    for (int x = 1; x < FINISH_THREADS / 64; ++x) dot += dot_s[x];
+    const float den = nrm[i];
+#pragma unroll
+    for (int o = 0; o < FINISH_OWN; ++o) {
+        const int f = tid + o * FINISH_THREADS;
+        if (f < K) dZ[(size_t)i * K + f] = (du[o] - pu[f] * dot) / den;
+    }
+    if (tid == 0) loss_i[i] = catalog_positive(pos_rows, i, B, n_rows) >= 0 ? (ml[i] + logf(ml[B + i])) - s_pos[i] : 0.0f;
+}
+
 bool dim_ok(int32_t dim) { return dim >= 32 && dim <= ICREC_ADAPTER_MAX_DIM && dim % 32 == 0; }
 
 void release(Adapter* ad) {
@@ -424,6 +711,21 @@ void release(Adapter* ad) {
     (void)hipFree(ad->m);
     (void)hipFree(ad->v);
     delete ad;
+}
+
+// AdamW's constants for step t + 1, the bias corrections in double.
+AdamW adamw_of(int64_t t, float lr, float beta1, float beta2, float eps, float weight_decay) {
+    const double t1 = (double)(t + 1);
+    AdamW o{};
+    o.lr = lr;
+    o.one_minus_b1 = (float)(1.0 - (double)beta1);
+    o.b2 = beta2;
+    o.one_minus_b2 = (float)(1.0 - (double)beta2);
+    o.eps = eps;
+    o.decay = (float)(1.0 - (double)lr * (double)weight_decay);
+    o.bc1 = (float)(1.0 - pow((double)beta1, t1));
+    o.sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, t1));
+    return o;
 }
 
 // The workspace of a step: u [B][dim], dz [B][dim], the norms [B], the losses [B].
@@ -436,6 +738,23 @@ struct StepWorkspace {
         nrm = 2 * rows;
         loss = 2 * rows + col;
         total = 2 * rows + 2 * col;
+    }
+};
+
+// The workspace of a catalog step: the list step's arrays, then the positives' logits [B], (M, L) [2][B], the counted
+// anchors, the splits' maxima and sums [n_splits][B] each, and the splits' parts of dU [n_splits][B][dim].
+struct CatalogWorkspace {
+    StepWorkspace step;
+    size_t s_pos, ml, counted, m_part, l_part, part, total;
+    CatalogWorkspace(int dim, int B, int n_splits) : step(dim, B) {
+        const size_t col = align256((size_t)B * sizeof(float)), cols = align256((size_t)n_splits * B * sizeof(float));
+        s_pos = step.total;
+        ml = s_pos + col;
+        counted = ml + align256(2 * (size_t)B * sizeof(float));
+        m_part = counted + 256;
+        l_part = m_part + cols;
+        part = l_part + cols;
+        total = part + align256((size_t)n_splits * B * dim * sizeof(float));
     }
 };
 
@@ -569,18 +888,7 @@ int icrec_adapter_step(icrec_index* idx, icrec_adapter* h, const float* anchors_
     float* nrm = reinterpret_cast<float*>(base + ws.nrm);
     float* loss_i = reinterpret_cast<float*>(base + ws.loss);
     const int d = ad->dim;
-    AdamW o{};
-    if (update) {  // the bias corrections of step t + 1, in double
-        const double t1 = (double)(ad->t + 1);
-        o.lr = lr;
-        o.one_minus_b1 = (float)(1.0 - (double)beta1);
-        o.b2 = beta2;
-        o.one_minus_b2 = (float)(1.0 - (double)beta2);
-        o.eps = eps;
-        o.decay = (float)(1.0 - (double)lr * (double)weight_decay);
-        o.bc1 = (float)(1.0 - pow((double)beta1, t1));
-        o.sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, t1));
-    }
+    const AdamW o = update ? adamw_of(ad->t, lr, beta1, beta2, eps, weight_decay) : AdamW{};
     hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((B + FWD_TILE - 1) / FWD_TILE)), dim3(FWD_THREADS), 0, st,
                        (const float*)ad->delta_t, d, anchors_dev, (int)B, U, nrm);
     hipLaunchKernelGGL((rows_are_bf16(ix) ? logits_kernel<true> : logits_kernel<false>),
@@ -588,6 +896,89 @@ int icrec_adapter_step(icrec_index* idx, icrec_adapter* h, const float* anchors_
                        ix->n_rows, (const float*)U, (const float*)nrm, cand_rows_dev, (int)B, (int)C, scale, dZ, loss_i);
     hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((d / 32) * (d / 32) + 1)), dim3(64), 0, st, (const float*)dZ, anchors_dev,
                        (int)B, d, cand_rows_dev, ix->n_rows, (const float*)loss_i, loss_out_dev, grad_out_dev, update ? 1 : 0, o,
+                       ad->delta, ad->delta_t, ad->m, ad->v);
+    ICREC_HIP(hipGetLastError());
+    if (update) ad->t += 1;
+    return ICREC_OK;
+}
+
+int icrec_adapter_catalog_plan(const icrec_adapter* h, int32_t B, int64_t n_rows, int32_t* n_splits, int64_t* rows_per_split) {
+    ICREC_REQUIRE(h != nullptr, "icrec_adapter_catalog_plan: NULL adapter");
+    ICREC_REQUIRE(n_splits != nullptr && rows_per_split != nullptr, "icrec_adapter_catalog_plan: NULL n_splits or rows_per_split");
+    ICREC_REQUIRE(B >= 1 && B <= ICREC_ADAPTER_MAX_BATCH, "icrec_adapter_catalog_plan: B must be in [1, %d] (got %d)",
+                  ICREC_ADAPTER_MAX_BATCH, B);
+    ICREC_REQUIRE(n_rows >= 1, "icrec_adapter_catalog_plan: n_rows must be >= 1 (got %lld)", (long long)n_rows);
+    const CatalogPlan plan = catalog_plan(B, n_rows);
+    *n_splits = plan.n_splits;
+    *rows_per_split = plan.rows_per_split;
+    return ICREC_OK;
+}
+
+size_t icrec_adapter_step_catalog_workspace_bytes(const icrec_adapter* h, const icrec_index* idx, int32_t B) {
+    const Adapter* ad = reinterpret_cast<const Adapter*>(h);
+    const Index* ix = reinterpret_cast<const Index*>(idx);
+    if (ad == nullptr || ix == nullptr || ix->n_rows < 1 || B < 1 || B > ICREC_ADAPTER_MAX_BATCH) return 0;
+    return CatalogWorkspace(ad->dim, B, catalog_plan(B, ix->n_rows).n_splits).total;
+}
+
+int icrec_adapter_step_catalog(icrec_index* idx, icrec_adapter* h, const float* anchors_dev, int32_t B,
+                               const int32_t* pos_rows_dev, float scale, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, int32_t update, float* loss_out_dev, float* grad_out_dev, void* workspace_dev,
+                               size_t workspace_bytes, void* stream) {
+    const Index* ix = reinterpret_cast<const Index*>(idx);
+    Adapter* ad = reinterpret_cast<Adapter*>(h);
+    ICREC_REQUIRE(ix != nullptr, "icrec_adapter_step_catalog: NULL idx");
+    ICREC_REQUIRE(ad != nullptr, "icrec_adapter_step_catalog: NULL adapter");
+    ICREC_REQUIRE(anchors_dev != nullptr && pos_rows_dev != nullptr, "icrec_adapter_step_catalog: NULL anchors or pos_rows");
+    ICREC_REQUIRE(loss_out_dev != nullptr, "icrec_adapter_step_catalog: NULL loss_out");
+    ICREC_REQUIRE(workspace_dev != nullptr, "icrec_adapter_step_catalog: NULL workspace");
+    ICREC_REQUIRE(ix->dim == ad->dim, "icrec_adapter_step_catalog: the index has dim %d, the adapter %d", ix->dim, ad->dim);
+    ICREC_REQUIRE(ix->device == ad->device, "icrec_adapter_step_catalog: the index is on device %d, the adapter on %d",
+                  ix->device, ad->device);
+    ICREC_REQUIRE(ix->n_rows >= 1, "icrec_adapter_step_catalog: the index has no rows");
+    ICREC_REQUIRE(B >= 1 && B <= ICREC_ADAPTER_MAX_BATCH, "icrec_adapter_step_catalog: B must be in [1, %d] (got %d)",
+                  ICREC_ADAPTER_MAX_BATCH, B);
+    ICREC_REQUIRE(isfinite(scale) && isfinite(lr) && isfinite(beta1) && isfinite(beta2) && isfinite(eps) && isfinite(weight_decay),
+                  "icrec_adapter_step_catalog: a hyper-parameter is not finite");
+    ICREC_REQUIRE(!update || (beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f),
+                  "icrec_adapter_step_catalog: beta1 and beta2 must be in [0, 1) and eps >= 0");
+    const int64_t n_rows = ix->n_rows;  // the rows of this call: the plan, every bound and the count use this one value
+    const CatalogPlan plan = catalog_plan(B, n_rows);
+    const CatalogWorkspace ws(ad->dim, B, plan.n_splits);
+    ICREC_REQUIRE(workspace_bytes >= ws.total, "icrec_adapter_step_catalog: the workspace has %zu bytes, %zu are needed",
+                  workspace_bytes, ws.total);
+    ICREC_HIP(hipSetDevice(ad->device));
+    hipStream_t st = (hipStream_t)stream;
+    char* base = static_cast<char*>(workspace_dev);
+    float* U = reinterpret_cast<float*>(base + ws.step.u);
+    float* dZ = reinterpret_cast<float*>(base + ws.step.dz);
+    float* nrm = reinterpret_cast<float*>(base + ws.step.nrm);
+    float* loss_i = reinterpret_cast<float*>(base + ws.step.loss);
+    float* s_pos = reinterpret_cast<float*>(base + ws.s_pos);
+    float* ml = reinterpret_cast<float*>(base + ws.ml);
+    int32_t* counted = reinterpret_cast<int32_t*>(base + ws.counted);
+    float* m_part = reinterpret_cast<float*>(base + ws.m_part);
+    float* l_part = reinterpret_cast<float*>(base + ws.l_part);
+    float* part = reinterpret_cast<float*>(base + ws.part);
+    const int d = ad->dim;
+    const AdamW o = update ? adamw_of(ad->t, lr, beta1, beta2, eps, weight_decay) : AdamW{};
+    const bool p16 = rows_are_bf16(ix);
+    const dim3 grid((unsigned)((B + ANCHOR_TILE - 1) / ANCHOR_TILE), (unsigned)plan.n_splits);
+    hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((B + FWD_TILE - 1) / FWD_TILE)), dim3(FWD_THREADS), 0, st,
+                       (const float*)ad->delta_t, d, anchors_dev, (int)B, U, nrm);
+    hipLaunchKernelGGL((p16 ? catalog_max_sum_kernel<true> : catalog_max_sum_kernel<false>), grid, dim3(LOGIT_THREADS), 0, st,
+                       (const void*)ix->rows, d, n_rows, plan.rows_per_split, (const float*)U, pos_rows_dev, (int)B, scale,
+                       m_part, l_part, s_pos);
+    hipLaunchKernelGGL(catalog_merge_kernel, dim3(1), dim3(ICREC_ADAPTER_MAX_BATCH), 0, st, (const float*)m_part,
+                       (const float*)l_part, plan.n_splits, pos_rows_dev, (int)B, n_rows, ml, counted);
+    hipLaunchKernelGGL((p16 ? catalog_du_kernel<true> : catalog_du_kernel<false>), grid, dim3(LOGIT_THREADS), 0, st,
+                       (const void*)ix->rows, d, n_rows, plan.rows_per_split, (const float*)U, (const float*)ml,
+                       (const int32_t*)counted, pos_rows_dev, (int)B, scale, part);
+    hipLaunchKernelGGL(catalog_finish_kernel, dim3((unsigned)B), dim3(FINISH_THREADS), 0, st, (const float*)part, plan.n_splits,
+                       (int)B, d, (const float*)U, (const float*)nrm, (const float*)ml, (const float*)s_pos, pos_rows_dev, n_rows,
+                       scale, dZ, loss_i);
+    hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((d / 32) * (d / 32) + 1)), dim3(64), 0, st, (const float*)dZ, anchors_dev,
+                       (int)B, d, pos_rows_dev, n_rows, (const float*)loss_i, loss_out_dev, grad_out_dev, update ? 1 : 0, o,
                        ad->delta, ad->delta_t, ad->m, ad->v);
     ICREC_HIP(hipGetLastError());
     if (update) ad->t += 1;

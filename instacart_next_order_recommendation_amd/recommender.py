@@ -741,14 +741,15 @@ class Recommender:
         if self._fast is not None:
             self._fast.set_adapter(adapter)
 
-    def fit_adapter(self, pairs, epochs: int = 5, batch_size: int = 64, negatives: int = 0, lr: float = 2e-3,
+    def fit_adapter(self, pairs, epochs: int = 5, batch_size: int = 64, negatives=0, lr: float = 2e-3,
                     weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0) -> list[float]:
         """Learn the query adapter from (context text, product id) pairs - clicks or purchases on this catalog - with the
         reference's loss (MultipleNegativesRankingLoss, scale 30; QueryAdapter.fit) -> the per-step losses.  The
         contexts are encoded once with the frozen encoder; the positives are catalog products, so their embeddings are
         the index's stored rows and no product is encoded.  The installed adapter is trained further, in place (the
         captured graphs stay and answer from the new weights); without one a new adapter is trained and installed.
-        negatives: extra rows drawn from the whole catalog per step, beside the in-batch negatives.  ValueError before
+        negatives: extra rows drawn from the whole catalog per step, beside the in-batch negatives, or "all": every
+        step is the exact cross-entropy against every stored row (QueryAdapter.step_catalog).  ValueError before
         any GPU work: adapter_pairs_plan's - above all a product id the catalog does not have.  A set-up call: never
         while a request is being served."""
         texts, rows = adapter_pairs_plan(pairs, self._pid_to_row, epochs, batch_size, negatives, lr, weight_decay, scale)
