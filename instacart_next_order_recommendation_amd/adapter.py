@@ -128,67 +128,56 @@ class QueryAdapter:
             raise ValueError(f"{what} must be a list of rows, got shape {tuple(rows.shape)}")
         return rows
 
-    def _step(self, index, anchors, cand_rows, scale, lr, betas, eps, weight_decay, update: bool, loss_out, grad_out):
+    def _step(self, catalog: bool, index, anchors, rows, scale, lr=0.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              update: bool = False, grad_out=None, loss_out=None, want_grad: bool = False):
+        """One call of icrec_adapter_step (rows: the candidate list) or, with `catalog`, of icrec_adapter_step_catalog
+        (rows: a positive per anchor) -> (loss float32 [], grad_out).  Without `update` the adapter is not changed;
+        want_grad: a new grad_out."""
         anchors = self._rows(anchors, "anchors")
-        cand = self._row_list(cand_rows, "cand_rows")
-        B, n_cand = int(anchors.shape[0]), int(cand.shape[0])
+        rows = self._row_list(rows, "positive_rows" if catalog else "cand_rows")
+        B, n = int(anchors.shape[0]), int(rows.shape[0])
         L = _native.lib()
-        need = int(L.icrec_adapter_step_workspace_bytes(self._h, B, n_cand))
-        ws = self._scratch.block(max(need, 256))
-        _native.check(L.icrec_adapter_step(index._h, self._h, _native.ptr(anchors), B, _native.ptr(cand), n_cand, float(scale),
-                                           float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                                           1 if update else 0, _native.ptr(loss_out), _native.ptr(grad_out), _native.ptr(ws),
-                                           ws.numel(), _native.stream_ptr(self.device)), "icrec_adapter_step")
+        if catalog:
+            if n != B:
+                raise ValueError(f"{B} anchors for {n} positives")
+            name, n_cand = "icrec_adapter_step_catalog", ()  # no list: its C is the index's row count
+            need = L.icrec_adapter_step_catalog_workspace_bytes(self._h, index._h, B)
+        else:
+            name, n_cand = "icrec_adapter_step", (n,)
+            need = L.icrec_adapter_step_workspace_bytes(self._h, B, n)
+        ws = self._scratch.block(max(int(need), 256))
+        loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=self.device)
+        if want_grad:
+            grad_out = torch.empty((self.dim, self.dim), dtype=torch.float32, device=self.device)
+        _native.check(getattr(L, name)(index._h, self._h, _native.ptr(anchors), B, _native.ptr(rows), *n_cand, float(scale),
+                                       float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                       1 if update else 0, _native.ptr(loss), _native.ptr(grad_out), _native.ptr(ws),
+                                       ws.numel(), _native.stream_ptr(self.device)), name)
+        return loss[0], grad_out
 
     def loss_and_grad(self, index, anchors, cand_rows, scale: float = DEFAULT_SCALE):
         """(loss float32 [], dD float32 [dim, dim]) on the device, of the anchors [B, dim] against index's stored rows
         cand_rows [C >= B] (candidate i is anchor i's positive); the adapter is not changed."""
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        grad = torch.empty((self.dim, self.dim), dtype=torch.float32, device=self.device)
-        self._step(index, anchors, cand_rows, scale, 0.0, (0.9, 0.999), 1e-8, 0.0, False, loss, grad)
-        return loss[0], grad
+        return self._step(False, index, anchors, cand_rows, scale, want_grad=True)
 
     def step(self, index, anchors, cand_rows, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
              scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None):
         """One AdamW step (torch.optim.AdamW's formula) on the batch's gradient -> the batch's loss before the step, a
         float32 [] device tensor (loss_out: a float32 [1] device tensor to write it to).  No host synchronisation."""
-        loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=self.device)
-        self._step(index, anchors, cand_rows, scale, lr, betas, eps, weight_decay, True, loss, grad_out)
-        return loss[0]
-
-    def _step_catalog(self, index, anchors, positive_rows, scale, lr, betas, eps, weight_decay, update: bool, loss_out,
-                      grad_out):
-        anchors = self._rows(anchors, "anchors")
-        pos = self._row_list(positive_rows, "positive_rows")
-        B = int(anchors.shape[0])
-        if int(pos.shape[0]) != B:
-            raise ValueError(f"{B} anchors for {int(pos.shape[0])} positives")
-        L = _native.lib()
-        need = int(L.icrec_adapter_step_catalog_workspace_bytes(self._h, index._h, B))
-        ws = self._scratch.block(max(need, 256))
-        _native.check(L.icrec_adapter_step_catalog(index._h, self._h, _native.ptr(anchors), B, _native.ptr(pos), float(scale),
-                                                   float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                                                   1 if update else 0, _native.ptr(loss_out), _native.ptr(grad_out),
-                                                   _native.ptr(ws), ws.numel(), _native.stream_ptr(self.device)),
-                      "icrec_adapter_step_catalog")
+        return self._step(False, index, anchors, cand_rows, scale, lr, betas, eps, weight_decay, True, grad_out, loss_out)[0]
 
     def loss_and_grad_catalog(self, index, anchors, positive_rows, scale: float = DEFAULT_SCALE):
         """loss_and_grad against the WHOLE catalog: the cross-entropy of anchors [B, dim] over every stored row of index,
         positive_rows [B] the labels (an anchor whose row is outside the index is not counted); no candidate list, no
         sampling.  The adapter is not changed."""
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        grad = torch.empty((self.dim, self.dim), dtype=torch.float32, device=self.device)
-        self._step_catalog(index, anchors, positive_rows, scale, 0.0, (0.9, 0.999), 1e-8, 0.0, False, loss, grad)
-        return loss[0], grad
+        return self._step(True, index, anchors, positive_rows, scale, want_grad=True)
 
     def step_catalog(self, index, anchors, positive_rows, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                      weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None,
                      loss_out: Optional[torch.Tensor] = None):
         """step against the whole catalog (loss_and_grad_catalog's loss): one AdamW step -> the batch's loss before the
         step, a float32 [] device tensor.  No host synchronisation."""
-        loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=self.device)
-        self._step_catalog(index, anchors, positive_rows, scale, lr, betas, eps, weight_decay, True, loss, grad_out)
-        return loss[0]
+        return self._step(True, index, anchors, positive_rows, scale, lr, betas, eps, weight_decay, True, grad_out, loss_out)[0]
 
     def catalog_loss(self, index, anchors, positive_rows, scale: Optional[float] = None) -> float:
         """The exact loss of a held-out set: the mean over its counted pairs of the cross-entropy against every stored
@@ -204,8 +193,7 @@ class QueryAdapter:
         starts = range(0, n, step)
         means = torch.zeros(len(starts), dtype=torch.float32, device=self.device)
         for k, lo in enumerate(starts):
-            self._step_catalog(index, anchors[lo:lo + step], pos[lo:lo + step], scale, 0.0, (0.9, 0.999), 1e-8, 0.0, False,
-                               means[k:k + 1], None)
+            self._step(True, index, anchors[lo:lo + step], pos[lo:lo + step], scale, loss_out=means[k:k + 1])
         in_range = ((pos >= 0) & (pos < int(index.n_rows))).to(torch.float64)
         counted = torch.stack([in_range[lo:lo + step].sum() for lo in starts])
         host = torch.stack([means.to(torch.float64), counted]).cpu().numpy()  # the one read-back
@@ -237,17 +225,12 @@ class QueryAdapter:
             perm = torch.randperm(int(rows.shape[0]), generator=gen)
             for b in range(per_epoch):
                 at = perm[b * batch:(b + 1) * batch].to(self.device)
-                cand = rows_dev[at]
-                if exact:
-                    self.step_catalog(index, anchors[at], cand, float(lr) * schedule(s, total, warmup),
-                                      weight_decay=weight_decay, scale=scale, loss_out=losses[s:s + 1])
-                    s += 1
-                    continue
-                if negatives:
+                cand = rows_dev[at]  # the batch's positives: a catalog step's labels, the head of a list step's candidates
+                if not exact and negatives:
                     extra = torch.randint(0, index.n_rows, (int(negatives),), generator=gen, dtype=torch.int64)
                     cand = torch.cat([cand, extra.to(self.device, torch.int32)])
-                self.step(index, anchors[at], cand, float(lr) * schedule(s, total, warmup), weight_decay=weight_decay,
-                          scale=scale, loss_out=losses[s:s + 1])
+                (self.step_catalog if exact else self.step)(index, anchors[at], cand, float(lr) * schedule(s, total, warmup),
+                                                            weight_decay=weight_decay, scale=scale, loss_out=losses[s:s + 1])
                 s += 1
         self.scale = float(scale)
         return losses.cpu().tolist()

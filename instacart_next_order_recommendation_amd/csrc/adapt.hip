@@ -2,9 +2,19 @@
 // (icrec_adapter_*).  The encoder and the stored rows stay frozen; only q' = q + D q changes, so every search composes.
 //   apply_kernel    one launch: a workgroup keeps a tile of queries in LDS, a lane owns one output's chain over c
 //   forward_kernel  the step's (a): z = apply(a), n = max(|z|, 1e-12), u = z / n
-//   logits_kernel   the step's (b): one workgroup per 32 anchors; S^T = V U^T on the f32 MFMA over gathered stored
-//                   rows, two sweeps over the candidates (row maximum and sum, then P recomputed and P V), dz in the
-//                   epilogue, one loss per anchor
+//   the step's (b)  S^T = V U^T on the f32 MFMA over gathered stored rows, in two sweeps over the rows: each anchor's
+//                   (maximum, sum), then P recomputed, G = (P - [positive]) / counted and dU^T = V^T G; then dz and one
+//                   loss per anchor.  It has two forms, which differ in where a tile row's stored row comes from - a
+//                   ROW SOURCE, ListRows or SpanRows - and share everything written over one: score_tile, store_g,
+//                   add_group (sweep 2's accumulation, the unit's register budget), merge_halves / merge_waves of
+//                   (maximum, sum), for_owned_tiles, row_in_range
+//     logits_kernel   the list step (icrec_adapter_step), over ListRows: one workgroup per 32 anchors does both
+//                     sweeps over the candidate list and the epilogue
+//     catalog_*       the step against the WHOLE catalog (icrec_adapter_step_catalog), over SpanRows: (anchor tiles x
+//                     row splits) workgroups - catalog_max_sum_kernel is sweep 1, catalog_merge_kernel the ordered
+//                     merge of the splits, catalog_du_kernel sweep 2, catalog_finish_kernel the epilogue
+//                   The two sweep 1s and the two epilogues are NOT shared: their sums have different orders, each stated
+//                   where it stands
 //   grad_kernel     the step's (c): one wave per 32 x 32 tile of dD = dZ^T A, walking the batch in order, AdamW in its
 //                   epilogue; one more workgroup sums the anchors' losses: each block of GRAD_BLOCK = 64 anchors is
 //                   one chain from zero in index order, the blocks' sums are added in block order - the order of
@@ -13,8 +23,7 @@
 //                   the float32 reference's error at width 32, beside a margin of 2; in two float32 levels a batch
 //                   of 65 still measured 6.29x beside a margin of 6: a chain of 64 rounds at the sum's ulp 64 times
 //                   and the mean is compared at half of ITS ulp)
-//   catalog_*       the step against the WHOLE catalog (icrec_adapter_step_catalog): (b) split over (anchor tiles x
-//                   row splits) workgroups with an ordered merge between its two sweeps; described where they stand
+// On the host both entries run check_step, launch_forward, their own (b), launch_grad.
 // The definitions (the two roundings of apply, the masking rules, the gradient, torch's AdamW) are in include/icrec.h;
 // tests/adapter_reference.py states them in numpy and torch.  No floating-point atomics anywhere: every sum has one order.
 #include <math.h>
@@ -137,27 +146,167 @@ __device__ __forceinline__ void merge_max_sum(float& m, float& l, float m2, floa
     m = M;
 }
 
-// One workgroup per 32 anchors, four waves.  The tile S^T[candidate][anchor] = V U^T is gathered_tile's: operand A the
-// stored row of the tile's candidate, operand B the anchor's u, so a lane holds ONE anchor (its column, lane & 31) and
-// sixteen candidates (acc_row).  A candidate's row number is checked once, into LDS, as -1 or the row: no other value
-// becomes an address, and a masked candidate's tile row is computed on row 0 and dropped.
-// Sweep 1: wave w walks candidate tiles w, w + 4, ..; a lane keeps the running (maximum, sum) of its anchor over its
-// candidates, then the two halves of the wave and the four waves are merged in that order.
-// Sweep 2, per group of four candidate tiles: wave w recomputes its tile, turns it into G = (P - delta) / counted and
-// leaves it in LDS as [candidate][anchor]; after the barrier every wave adds the group's four tiles, in order, into the
-// feature tiles of dU^T = V^T G it owns (tile t belongs to wave t % 4) - G as operand B needs no lane movement, operand
-// A is the stored rows' features t * 32 + (lane & 31), 128 contiguous bytes per candidate.  A group's 128 candidates
-// are one fmaf chain from zero and the groups' sums are added in group order: two short levels instead of one chain
-// of up to 8,192 terms, whose rounding error would grow with its length.
-// Epilogue: du = scale * acc, the dot u . du over the waves' feature tiles through LDS in wave order,
-// dz = (du - u (u . du)) / n.
+// r names a stored row of an index of n_rows rows.  An anchor is counted iff its positive does, and no other value
+// becomes an address.
+__device__ __forceinline__ bool row_in_range(int32_t r, int64_t n_rows) { return r >= 0 && (int64_t)r < n_rows; }
+
+// ---------------------------------------------------------------- the step's (b): what its two forms share
+// Both forms of (b) - logits_kernel over a candidate list, the catalog_* kernels over every stored row - run on
+// workgroups of four waves that hold ONE tile of 32 anchors and walk the rows in groups of four 32-row tiles, tile x of
+// a group being wave x's.  A tile S^T[row][anchor] = V U^T is gathered_tile's: operand A the stored row of the lane's
+// tile row, operand B the anchor's u, so a lane holds ONE anchor (its column, lane & 31) and sixteen tile rows (acc_row).
+// The one thing the two forms do differently is where tile row jr of tile x gets its stored row; a ROW SOURCE says
+// that, for one group and this lane's anchor, and everything below is written once over a source:
+//   tile_live(x)    does tile x of the group exist
+//   row(x, jr)      the stored row of its tile row jr, or -1: the tile row is dropped, and computed on fallback()
+//   positive(x, jr) is it the anchor's positive
+//   masked(x, jr)   does it stay out of the anchor's softmax
+// The sources are passed by value and resolved when the kernel is compiled: nothing branches on the caller.
+
+// The candidate list, checked once into LDS as -1 or the row.  A candidate out of range is masked for everybody, a far
+// copy of the anchor's positive for that anchor; a dropped tile row is computed on row 0.
+struct ListRows {
+    const int32_t* crow;  // LDS: the checked row of candidate j, or -1
+    int C, n_ct;          // the candidates and their tiles
+    int g;                // the group's first tile
+    int i, pos;           // this lane's anchor: candidate i is its positive, pos = crow[i], or -1 when it is not counted
+    __device__ __forceinline__ bool tile_live(int x) const { return g + x < n_ct; }
+    __device__ __forceinline__ int row(int x, int jr) const {
+        const int j = (g + x) * 32 + jr;
+        return j < C ? crow[j] : -1;
+    }
+    __device__ __forceinline__ int fallback() const { return 0; }
+    __device__ __forceinline__ bool positive(int x, int jr) const { return (g + x) * 32 + jr == i; }
+    __device__ __forceinline__ bool masked(int x, int jr) const {
+        const int rj = row(x, jr);
+        return rj < 0 || (!positive(x, jr) && rj == pos);
+    }
+};
+
+// A split [r0, end) of the stored rows: a tile's rows are CONTIGUOUS, tile row jr of the tile at `first` is row
+// first + jr.  A row at or behind `end` is computed on the split's first row and dropped by its INDEX - nothing depends
+// on what lies behind n_rows - and nothing else is masked.
+struct SpanRows {
+    int64_t g0, end, r0;  // the group's first row; the end and the first row of the workgroup's split
+    int64_t pos;          // the positive of this lane's anchor, or -1 when it is not counted
+    __device__ __forceinline__ bool tile_live(int x) const { return g0 + x * 32 < end; }
+    __device__ __forceinline__ int64_t row(int x, int jr) const {
+        const int64_t r = g0 + x * 32 + jr;
+        return r < end ? r : -1;
+    }
+    __device__ __forceinline__ int64_t fallback() const { return r0; }
+    __device__ __forceinline__ bool positive(int x, int jr) const { return g0 + x * 32 + jr == pos; }
+    __device__ __forceinline__ bool masked(int x, int jr) const { return row(x, jr) < 0; }
+};
+
+// The score tile: tile x of the group against the anchors at pu, this lane's stored row or the fallback row.
+template <class Row, class Source>
+__device__ __forceinline__ f32x16 score_tile(const Row* __restrict__ stored, const Source src, int x,
+                                             const float* __restrict__ pu, int K, int lane) {
+    const auto ra = src.row(x, lane & 31);
+    f32x16 acc = {};
+    gathered_tile(acc, stored + (size_t)(ra < 0 ? src.fallback() : ra) * K, pu, K, lane >> 5);
+    return acc;
+}
+
+// The two halves of a wave hold (m, l) of the same anchors over different rows: half 0's part first, in both halves.
+__device__ __forceinline__ void merge_halves(float& m, float& l, int h) {
+    const float m_o = __shfl_xor(m, 32, 64), l_o = __shfl_xor(l, 32, 64);
+    float m0 = h ? m_o : m, l0 = h ? l_o : l;
+    merge_max_sum(m0, l0, h ? m : m_o, h ? l : l_o);
+    m = m0;
+    l = l0;
+}
+
+// The four waves' merged halves through LDS, in wave order, behind one barrier: every wave leaves with the same pair.
+__device__ __forceinline__ void merge_waves(float& m, float& l, float (*m_s)[32], float (*l_s)[32], int w, int h, int l31) {
+    merge_halves(m, l, h);
+    if (h == 0) {
+        m_s[w][l31] = m;
+        l_s[w][l31] = l;
+    }
+    __syncthreads();
+    m = m_s[0][l31];
+    l = l_s[0][l31];
+#pragma unroll
+    for (int x = 1; x < LOGIT_WAVES; ++x) merge_max_sum(m, l, m_s[x][l31], l_s[x][l31]);
+}
+
+// body(tt, t) for the feature tiles t = w, w + 4, .. of dU^T that wave w owns, tt counting them.
+template <class Body>
+__device__ __forceinline__ void for_owned_tiles(int w, int K, Body body) {
+    const int n_ft = K / 32;
+#pragma unroll
+    for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
+        const int t = w + tt * LOGIT_WAVES;
+        if (t < n_ft) body(tt, t);
+    }
+}
+
+// Sweep 2's tile: P recomputed from the score tile against the final (M, 1 / L), G = (P - [positive]) / counted left
+// in LDS as [tile row][anchor] - where it is operand B of dU^T = V^T G with no lane movement.
+template <class Source>
+__device__ __forceinline__ void store_g(float (*gs)[32], const f32x16& acc, const Source src, int x, int lane, float scale,
+                                        float M, float inv_l, bool counted, float inv_counted) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int jr = acc_row(e, lane);
+        const float p = src.masked(x, jr) ? 0.0f : expf(scale * acc[e] - M) * inv_l;
+        gs[jr][lane & 31] = counted ? (p - (src.positive(x, jr) ? 1.0f : 0.0f)) * inv_counted : 0.0f;
+    }
+}
+
+// Sweep 2's accumulation: every wave adds the group's tiles, in order, into the feature tiles of dU^T it owns - operand
+// A the stored rows' features t * 32 + (lane & 31), 128 contiguous bytes per row, a dropped row's value replaced by
+// zero.  A group's 128 rows are one fmaf chain from zero and the groups' sums are added in group order: two short
+// levels instead of one chain of up to 8,192 terms, whose rounding error would grow with its length.  du and du_group
+// are the kernels' register budget (eight tiles twice at d = 1,024: 256 VGPRs and most AGPRs, one wave per SIMD, no
+// scratch - DESIGN.md 4.23 has the compiler's counts).  Small things decide it, 64-bit index arithmetic in the unrolled
+// part and what is hoisted above it among them: ask the compiler (-Rpass-analysis=kernel-resource-usage) after a change.
+template <class Row, class Source>
+__device__ __forceinline__ void add_group(f32x16 (&du)[MAX_OWN_TILES], const Row* __restrict__ stored, const Source src,
+                                          const float (*gs)[32][32], int K, int w, int lane) {
+    const int h = lane >> 5, l31 = lane & 31;
+    f32x16 du_group[MAX_OWN_TILES] = {};
+    for (int x = 0; x < LOGIT_WAVES && src.tile_live(x); ++x) {
+        float gb[16];
+        size_t off[16];
+        bool live[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {  // step s sums over tile rows 2s (lanes 0-31) and 2s + 1 (lanes 32-63)
+            const int jr = 2 * s + h;
+            const auto r = src.row(x, jr);
+            gb[s] = gs[x][jr][l31];
+            live[s] = r >= 0;
+            off[s] = (size_t)(live[s] ? r : src.fallback()) * K + l31;
+        }
+        for_owned_tiles(w, K, [&](int tt, int t) {
+            float va[16];
+#pragma unroll
+            for (int s = 0; s < 16; ++s) va[s] = stored_value(stored + off[s] + t * 32);
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                du_group[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(live[s] ? va[s] : 0.0f, gb[s], du_group[tt], 0, 0, 0);
+        });
+    }
+#pragma unroll
+    for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) du[tt][e] += du_group[tt][e];
+}
+
+// The list step's (b), all of it: one workgroup per 32 anchors.  A candidate's row number is checked once, into LDS.
+// Sweep 1: wave w walks candidate tiles w, w + 4, ..; a lane keeps the RUNNING (maximum, sum) of its anchor over its
+// candidates, and the halves and the waves are merged once, at the end.  Sweep 2, per group: wave w's tile -> G, the
+// barrier, the group's accumulation.  Epilogue, in MFMA layout: du = scale * acc, the dot u . du over the waves'
+// feature tiles through LDS in wave order, dz = (du - u (u . du)) / n.
 template <bool P16>
 __global__ __launch_bounds__(LOGIT_THREADS) void logits_kernel(const void* __restrict__ rows, int K, int64_t n_rows,
                                                                const float* __restrict__ U, const float* __restrict__ nrm,
                                                                const int32_t* __restrict__ cand, int B, int C, float scale,
                                                                float* __restrict__ dZ, float* __restrict__ loss_i) {
     typedef row_elem_t<P16> Row;
-    __shared__ int32_t crow[ICREC_ADAPTER_MAX_CANDIDATES];  // the checked row of candidate j, or -1
+    __shared__ int32_t crow[ICREC_ADAPTER_MAX_CANDIDATES];
     __shared__ float gs[LOGIT_WAVES][32][32];
     __shared__ float m_s[LOGIT_WAVES][32], l_s[LOGIT_WAVES][32], dot_s[LOGIT_WAVES][32], spos[32];
     __shared__ int counted_s;
@@ -169,7 +318,7 @@ __global__ __launch_bounds__(LOGIT_THREADS) void logits_kernel(const void* __res
     int mine = 0;
     for (int j = tid; j < C; j += LOGIT_THREADS) {
         const int32_t r = cand[j];
-        const bool ok = r >= 0 && (int64_t)r < n_rows;
+        const bool ok = row_in_range(r, n_rows);
         crow[j] = ok ? r : -1;
         mine += (ok && j < B) ? 1 : 0;
     }
@@ -185,21 +334,17 @@ __global__ __launch_bounds__(LOGIT_THREADS) void logits_kernel(const void* __res
     const int n_ct = (C + 31) / 32;
 
     float m = -INFINITY, l = 0.0f;
-    for (int ct = w; ct < n_ct; ct += LOGIT_WAVES) {
-        const int ja = ct * 32 + l31;
-        const int ra = ja < C ? crow[ja] : -1;
-        f32x16 acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-        gathered_tile(acc, stored + (size_t)(ra < 0 ? 0 : ra) * K, pu, K, h);
+    for (int g = 0; g < n_ct; g += LOGIT_WAVES) {
+        const ListRows src{crow, C, n_ct, g, i, pos};
+        if (!src.tile_live(w)) break;
+        const f32x16 acc = score_tile(stored, src, w, pu, K, lane);
         float sv[16], tm = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int j = ct * 32 + acc_row(e, lane);
-            const int rj = j < C ? crow[j] : -1;
+            const int jr = acc_row(e, lane);
             const float s = scale * acc[e];
-            if (j == i && in_b) spos[l31] = s;  // one lane of the workgroup meets its anchor's own positive
-            sv[e] = (rj < 0 || (j != i && rj == pos)) ? -INFINITY : s;
+            if (src.positive(w, jr) && in_b) spos[l31] = s;  // one lane of the workgroup meets its anchor's own positive
+            sv[e] = src.masked(w, jr) ? -INFINITY : s;
             tm = fmaxf(tm, sv[e]);
         }
         if (tm > -INFINITY) {
@@ -211,99 +356,31 @@ __global__ __launch_bounds__(LOGIT_THREADS) void logits_kernel(const void* __res
             m = nm;
         }
     }
-    {
-        const float m_o = __shfl_xor(m, 32, 64), l_o = __shfl_xor(l, 32, 64);
-        float m0 = h ? m_o : m, l0 = h ? l_o : l;  // half 0's part first, in both halves
-        merge_max_sum(m0, l0, h ? m : m_o, h ? l : l_o);
-        if (h == 0) {
-            m_s[w][l31] = m0;
-            l_s[w][l31] = l0;
-        }
-    }
-    __syncthreads();
-    float M = m_s[0][l31], L = l_s[0][l31];
-#pragma unroll
-    for (int x = 1; x < LOGIT_WAVES; ++x) merge_max_sum(M, L, m_s[x][l31], l_s[x][l31]);
-    if (!counted) {  // neither a loss nor a gradient; keep the arithmetic below finite
-        M = 0.0f;
-        L = 1.0f;
-    }
+    merge_waves(m, l, m_s, l_s, w, h, l31);
+    const float M = counted ? m : 0.0f, L = counted ? l : 1.0f;  // not counted: no loss, no gradient, finite arithmetic below
     if (w == 0 && h == 0 && in_b) loss_i[i] = counted ? (M + logf(L)) - spos[l31] : 0.0f;
     const float inv_l = 1.0f / L;
 
-    f32x16 du[MAX_OWN_TILES], du_group[MAX_OWN_TILES];
-#pragma unroll
-    for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) du[tt][e] = 0.0f;
-    const int n_ft = K / 32;
+    f32x16 du[MAX_OWN_TILES] = {};
     for (int g = 0; g < n_ct; g += LOGIT_WAVES) {
-        const int ct = g + w;
-        if (ct < n_ct) {
-            const int ja = ct * 32 + l31;
-            const int ra = ja < C ? crow[ja] : -1;
-            f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-            gathered_tile(acc, stored + (size_t)(ra < 0 ? 0 : ra) * K, pu, K, h);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int jr = acc_row(e, lane), j = ct * 32 + jr;
-                const int rj = j < C ? crow[j] : -1;
-                const bool masked = rj < 0 || (j != i && rj == pos);
-                const float p = masked ? 0.0f : expf(scale * acc[e] - M) * inv_l;
-                gs[w][jr][l31] = counted ? (p - (j == i ? 1.0f : 0.0f)) * inv_counted : 0.0f;
-            }
+        const ListRows src{crow, C, n_ct, g, i, pos};
+        if (src.tile_live(w)) {
+            const f32x16 acc = score_tile(stored, src, w, pu, K, lane);
+            store_g(gs[w], acc, src, w, lane, scale, M, inv_l, counted, inv_counted);
         }
         __syncthreads();
-#pragma unroll
-        for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) du_group[tt][e] = 0.0f;
-        for (int x = 0; x < LOGIT_WAVES && g + x < n_ct; ++x) {
-            float gb[16];
-            size_t off[16];
-            bool live[16];
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {  // step s sums over candidates 2s (lanes 0-31) and 2s + 1 (lanes 32-63)
-                const int jr = 2 * s + h, j = (g + x) * 32 + jr;
-                const int rj = j < C ? crow[j] : -1;
-                gb[s] = gs[x][jr][l31];
-                live[s] = rj >= 0;
-                off[s] = (size_t)(rj < 0 ? 0 : rj) * K + l31;
-            }
-#pragma unroll
-            for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
-                const int t = w + tt * LOGIT_WAVES;
-                if (t < n_ft) {
-                    float va[16];
-#pragma unroll
-                    for (int s = 0; s < 16; ++s) va[s] = stored_value(stored + off[s] + t * 32);
-#pragma unroll
-                    for (int s = 0; s < 16; ++s)
-                        du_group[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(live[s] ? va[s] : 0.0f, gb[s], du_group[tt], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) du[tt][e] += du_group[tt][e];
+        add_group(du, stored, src, gs, K, w, lane);
         __syncthreads();
     }
 
     float part = 0.0f;
+    for_owned_tiles(w, K, [&](int tt, int t) {
 #pragma unroll
-    for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
-        const int t = w + tt * LOGIT_WAVES;
-        if (t < n_ft) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                du[tt][e] = scale * du[tt][e];
-                part += pu[t * 32 + acc_row(e, lane)] * du[tt][e];
-            }
+        for (int e = 0; e < 16; ++e) {
+            du[tt][e] = scale * du[tt][e];
+            part += pu[t * 32 + acc_row(e, lane)] * du[tt][e];
         }
-    }
+    });
     {
         const float o = __shfl_xor(part, 32, 64);
         const float both = (h ? o : part) + (h ? part : o);
@@ -315,18 +392,15 @@ __global__ __launch_bounds__(LOGIT_THREADS) void logits_kernel(const void* __res
     for (int x = 1; x < LOGIT_WAVES; ++x) dot += dot_s[x][l31];
     if (!in_b) return;
     const float den = nrm[i];
+    for_owned_tiles(w, K, [&](int tt, int t) {
 #pragma unroll
-    for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
-        const int t = w + tt * LOGIT_WAVES;
-        if (t < n_ft) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int f = t * 32 + acc_row(e, lane);
-                dZ[(size_t)i * K + f] = (du[tt][e] - pu[f] * dot) / den;
-            }
+        for (int e = 0; e < 16; ++e) {
+            const int f = t * 32 + acc_row(e, lane);
+            dZ[(size_t)i * K + f] = (du[tt][e] - pu[f] * dot) / den;
         }
-    }
+    });
 }
+
 
 struct AdamW {
     float lr, one_minus_b1, b2, one_minus_b2, eps, decay, bc1, sqrt_bc2;  // decay = 1 - lr * weight_decay
@@ -354,7 +428,7 @@ __global__ __launch_bounds__(64) void grad_kernel(const float* __restrict__ dZ, 
         int mine = 0;
         for (int i = lane; i < B; i += 64) {
             const int32_t r = cand[i];
-            mine += (r >= 0 && (int64_t)r < n_rows) ? 1 : 0;
+            mine += row_in_range(r, n_rows) ? 1 : 0;
             ls[i] = loss_i[i];
         }
         if (mine) atomicAdd(&counted_s, mine);
@@ -460,13 +534,13 @@ CatalogPlan catalog_plan(int B, int64_t n_rows) {
 __device__ __forceinline__ int64_t catalog_positive(const int32_t* __restrict__ pos_rows, int i, int B, int64_t n_rows) {
     if (i >= B) return -1;
     const int32_t r = pos_rows[i];
-    return (r >= 0 && (int64_t)r < n_rows) ? (int64_t)r : -1;
+    return row_in_range(r, n_rows) ? (int64_t)r : -1;
 }
 
-// Sweep 1.  Per group of 128 rows wave w takes tile w: a lane's (maximum, sum) over its sixteen rows, the two halves of
-// the wave merged (half 0 first), the four waves' pairs through LDS merged in wave order into the group's pair, the
-// groups' pairs merged in group order - every wave keeps the same running pair.  The pairs of a group are double
-// buffered, so one barrier per group stands between its writes and its reads.
+// Sweep 1.  Per group of 128 rows wave w takes tile w: a lane's (maximum, sum) over its sixteen rows, then the halves
+// and the waves merged PER GROUP into the group's pair, the groups' pairs merged in group order - every wave keeps the
+// same running pair.  The pairs of a group are double buffered, so merge_waves' one barrier per group stands between
+// its writes and its reads.
 template <bool P16>
 __global__ __launch_bounds__(LOGIT_THREADS) void catalog_max_sum_kernel(const void* __restrict__ rows, int K, int64_t n_rows,
                                                                         int64_t rows_per_split, const float* __restrict__ U,
@@ -486,39 +560,26 @@ __global__ __launch_bounds__(LOGIT_THREADS) void catalog_max_sum_kernel(const vo
     float m = -INFINITY, l = 0.0f;
     int buf = 0;
     for (int64_t g0 = r0; g0 < end; g0 += CATALOG_GROUP, buf ^= 1) {
-        const int64_t first = g0 + w * 32;
-        float tm = -INFINITY, tl = 0.0f;
-        if (first < end) {
-            const int64_t ra = first + l31;
-            f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-            gathered_tile(acc, stored + (size_t)(ra < end ? ra : r0) * K, pu, K, h);
+        const SpanRows src{g0, end, r0, pos};
+        float gm = -INFINITY, gl = 0.0f;
+        if (src.tile_live(w)) {
+            const f32x16 acc = score_tile(stored, src, w, pu, K, lane);
             float sv[16];
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int64_t r = first + acc_row(e, lane);
+                const int jr = acc_row(e, lane);
                 const float s = scale * acc[e];
-                if (r < end && r == pos) s_pos[i] = s;  // one lane of the grid meets a counted anchor's positive
-                sv[e] = r < end ? s : -INFINITY;
-                tm = fmaxf(tm, sv[e]);
+                const bool out = src.masked(w, jr);
+                if (!out && src.positive(w, jr)) s_pos[i] = s;  // one lane of the grid meets a counted anchor's positive
+                sv[e] = out ? -INFINITY : s;
+                gm = fmaxf(gm, sv[e]);
             }
-            if (tm > -INFINITY) {
+            if (gm > -INFINITY) {
 #pragma unroll
-                for (int e = 0; e < 16; ++e) tl += expf(sv[e] - tm);
+                for (int e = 0; e < 16; ++e) gl += expf(sv[e] - gm);
             }
         }
-        const float m_o = __shfl_xor(tm, 32, 64), l_o = __shfl_xor(tl, 32, 64);
-        float m0 = h ? m_o : tm, l0 = h ? l_o : tl;  // half 0's part first, in both halves
-        merge_max_sum(m0, l0, h ? tm : m_o, h ? tl : l_o);
-        if (h == 0) {
-            m_s[buf][w][l31] = m0;
-            l_s[buf][w][l31] = l0;
-        }
-        __syncthreads();
-        float gm = m_s[buf][0][l31], gl = l_s[buf][0][l31];
-#pragma unroll
-        for (int x = 1; x < LOGIT_WAVES; ++x) merge_max_sum(gm, gl, m_s[buf][x][l31], l_s[buf][x][l31]);
+        merge_waves(gm, gl, m_s[buf], l_s[buf], w, h, l31);
         merge_max_sum(m, l, gm, gl);
     }
     if (w == 0 && h == 0 && in_b) {
@@ -526,6 +587,7 @@ __global__ __launch_bounds__(LOGIT_THREADS) void catalog_max_sum_kernel(const vo
         l_part[(size_t)blockIdx.y * B + i] = l;
     }
 }
+
 
 // One workgroup: thread i merges anchor i's pairs in split order and the workgroup counts the anchors whose positive is
 // in range.  ml[0 .. B) the maxima, ml[B .. 2B) the sums; an anchor that is not counted gets (0, 1), which keeps
@@ -561,10 +623,9 @@ __global__ __launch_bounds__(ICREC_ADAPTER_MAX_BATCH) void catalog_merge_kernel(
     if (i == 0) *counted_out = counted_s;
 }
 
-// Sweep 2, logits_kernel's over contiguous rows: per group of 128 rows wave w recomputes its tile, leaves
-// G = (P - [r == pos]) / counted in LDS as [row][anchor], and after the barrier every wave adds the group's tiles, in
-// order, into the feature tiles of dU^T it owns.  A group is one chain from zero, the groups are added in order; the
-// split's sums go to part[split][anchor][feature], unscaled.
+// Sweep 2 over the workgroup's split, per group of 128 rows as logits_kernel has it per group of four candidate tiles:
+// wave w's tile -> G against the merged (M, L), the barrier, the group's accumulation.  The split's sums go to
+// part[split][anchor][feature], unscaled.
 template <bool P16>
 __global__ __launch_bounds__(LOGIT_THREADS) void catalog_du_kernel(const void* __restrict__ rows, int K, int64_t n_rows,
                                                                    int64_t rows_per_split, const float* __restrict__ U,
@@ -574,7 +635,7 @@ __global__ __launch_bounds__(LOGIT_THREADS) void catalog_du_kernel(const void* _
                                                                    float* __restrict__ part) {
     typedef row_elem_t<P16> Row;
     __shared__ float gs[LOGIT_WAVES][32][32];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, l31 = lane & 31;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31;
     const Row* stored = static_cast<const Row*>(rows);
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_split;
     const int64_t end = r0 + rows_per_split < n_rows ? r0 + rows_per_split : n_rows;
@@ -587,76 +648,26 @@ __global__ __launch_bounds__(LOGIT_THREADS) void catalog_du_kernel(const void* _
     const float M = in_b ? ml[i] : 0.0f;
     const float inv_l = 1.0f / (in_b ? ml[B + i] : 1.0f);
     const float* pu = U + (size_t)(in_b ? i : B - 1) * K;
-    const int n_ft = K / 32;
 
-    f32x16 du[MAX_OWN_TILES], du_group[MAX_OWN_TILES];
-#pragma unroll
-    for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) du[tt][e] = 0.0f;
+    f32x16 du[MAX_OWN_TILES] = {};
     for (int64_t g0 = r0; g0 < end; g0 += CATALOG_GROUP) {
-        const int64_t first = g0 + w * 32;
-        if (first < end) {
-            const int64_t ra = first + l31;
-            f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-            gathered_tile(acc, stored + (size_t)(ra < end ? ra : r0) * K, pu, K, h);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int jr = acc_row(e, lane);
-                const int64_t r = first + jr;
-                const float p = r < end ? expf(scale * acc[e] - M) * inv_l : 0.0f;
-                gs[w][jr][l31] = counted ? (p - (r == pos ? 1.0f : 0.0f)) * inv_counted : 0.0f;
-            }
+        const SpanRows src{g0, end, r0, pos};
+        if (src.tile_live(w)) {
+            const f32x16 acc = score_tile(stored, src, w, pu, K, lane);
+            store_g(gs[w], acc, src, w, lane, scale, M, inv_l, counted, inv_counted);
         }
         __syncthreads();
-#pragma unroll
-        for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) du_group[tt][e] = 0.0f;
-        for (int x = 0; x < LOGIT_WAVES && g0 + x * 32 < end; ++x) {
-            float gb[16];
-            size_t off[16];
-            bool live[16];
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {  // step s sums over rows 2s (lanes 0-31) and 2s + 1 (lanes 32-63) of the tile
-                const int jr = 2 * s + h;
-                const int64_t r = g0 + x * 32 + jr;
-                gb[s] = gs[x][jr][l31];
-                live[s] = r < end;
-                off[s] = (size_t)(live[s] ? r : r0) * K + l31;
-            }
-#pragma unroll
-            for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
-                const int t = w + tt * LOGIT_WAVES;
-                if (t < n_ft) {
-                    float va[16];
-#pragma unroll
-                    for (int s = 0; s < 16; ++s) va[s] = stored_value(stored + off[s] + t * 32);
-#pragma unroll
-                    for (int s = 0; s < 16; ++s)
-                        du_group[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(live[s] ? va[s] : 0.0f, gb[s], du_group[tt], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int tt = 0; tt < MAX_OWN_TILES; ++tt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) du[tt][e] += du_group[tt][e];
+        add_group(du, stored, src, gs, K, w, lane);
         __syncthreads();
     }
     if (!in_b) return;
     float* out = part + ((size_t)blockIdx.y * B + i) * K;
+    for_owned_tiles(w, K, [&](int tt, int t) {
 #pragma unroll
-    for (int tt = 0; tt < MAX_OWN_TILES; ++tt) {
-        const int t = w + tt * LOGIT_WAVES;
-        if (t < n_ft) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) out[t * 32 + acc_row(e, lane)] = du[tt][e];
-        }
-    }
+        for (int e = 0; e < 16; ++e) out[t * 32 + acc_row(e, lane)] = du[tt][e];
+    });
 }
+
 
 // One workgroup per anchor, a thread per feature f = tid, tid + 256, ..: the splits' parts added in split order,
 // du = scale * sum; u . du as each thread's chain over its features ascending, the wave's xor butterfly, the four
@@ -713,18 +724,24 @@ void release(Adapter* ad) {
     delete ad;
 }
 
+// A step's hyper-parameters, as both entries take them.
+struct Hyper {
+    float scale, lr, beta1, beta2, eps, weight_decay;
+    bool update;
+};
+
 // AdamW's constants for step t + 1, the bias corrections in double.
-AdamW adamw_of(int64_t t, float lr, float beta1, float beta2, float eps, float weight_decay) {
+AdamW adamw_of(int64_t t, const Hyper& hp) {
     const double t1 = (double)(t + 1);
     AdamW o{};
-    o.lr = lr;
-    o.one_minus_b1 = (float)(1.0 - (double)beta1);
-    o.b2 = beta2;
-    o.one_minus_b2 = (float)(1.0 - (double)beta2);
-    o.eps = eps;
-    o.decay = (float)(1.0 - (double)lr * (double)weight_decay);
-    o.bc1 = (float)(1.0 - pow((double)beta1, t1));
-    o.sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, t1));
+    o.lr = hp.lr;
+    o.one_minus_b1 = (float)(1.0 - (double)hp.beta1);
+    o.b2 = hp.beta2;
+    o.one_minus_b2 = (float)(1.0 - (double)hp.beta2);
+    o.eps = hp.eps;
+    o.decay = (float)(1.0 - (double)hp.lr * (double)hp.weight_decay);
+    o.bc1 = (float)(1.0 - pow((double)hp.beta1, t1));
+    o.sqrt_bc2 = (float)sqrt(1.0 - pow((double)hp.beta2, t1));
     return o;
 }
 
@@ -757,6 +774,54 @@ struct CatalogWorkspace {
         total = part + align256((size_t)n_splits * B * dim * sizeof(float));
     }
 };
+
+// What the two step entries check alike.  `fn`, the entry's name, opens every message; `list` names its row list.
+int check_step(const char* fn, const char* list, const Index* ix, const Adapter* ad, const float* anchors_dev,
+               const int32_t* rows_dev, const float* loss_out_dev, const void* workspace_dev, int32_t B, const Hyper& hp) {
+    ICREC_REQUIRE(ix != nullptr, "%s: NULL idx", fn);
+    ICREC_REQUIRE(ad != nullptr, "%s: NULL adapter", fn);
+    ICREC_REQUIRE(anchors_dev != nullptr && rows_dev != nullptr, "%s: NULL anchors or %s", fn, list);
+    ICREC_REQUIRE(loss_out_dev != nullptr, "%s: NULL loss_out", fn);
+    ICREC_REQUIRE(workspace_dev != nullptr, "%s: NULL workspace", fn);
+    ICREC_REQUIRE(ix->dim == ad->dim, "%s: the index has dim %d, the adapter %d", fn, ix->dim, ad->dim);
+    ICREC_REQUIRE(ix->device == ad->device, "%s: the index is on device %d, the adapter on %d", fn, ix->device, ad->device);
+    ICREC_REQUIRE(ix->n_rows >= 1, "%s: the index has no rows", fn);
+    ICREC_REQUIRE(B >= 1 && B <= ICREC_ADAPTER_MAX_BATCH, "%s: B must be in [1, %d] (got %d)", fn, ICREC_ADAPTER_MAX_BATCH, B);
+    ICREC_REQUIRE(isfinite(hp.scale) && isfinite(hp.lr) && isfinite(hp.beta1) && isfinite(hp.beta2) && isfinite(hp.eps) &&
+                      isfinite(hp.weight_decay),
+                  "%s: a hyper-parameter is not finite", fn);
+    ICREC_REQUIRE(!hp.update || (hp.beta1 >= 0.0f && hp.beta1 < 1.0f && hp.beta2 >= 0.0f && hp.beta2 < 1.0f && hp.eps >= 0.0f),
+                  "%s: beta1 and beta2 must be in [0, 1) and eps >= 0", fn);
+    return ICREC_OK;
+}
+
+// The arrays every step's workspace begins with.
+struct StepArrays {
+    float *U, *dZ, *nrm, *loss_i;
+    StepArrays(char* base, const StepWorkspace& ws)
+        : U(reinterpret_cast<float*>(base + ws.u)), dZ(reinterpret_cast<float*>(base + ws.dz)),
+          nrm(reinterpret_cast<float*>(base + ws.nrm)), loss_i(reinterpret_cast<float*>(base + ws.loss)) {}
+};
+
+// The step's (a): u and the norms of the anchors.
+void launch_forward(const Adapter* ad, const float* anchors_dev, int B, const StepArrays& a, hipStream_t st) {
+    hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((B + FWD_TILE - 1) / FWD_TILE)), dim3(FWD_THREADS), 0, st,
+                       (const float*)ad->delta_t, ad->dim, anchors_dev, B, a.U, a.nrm);
+}
+
+// The step's (c), from the dZ and the losses its (b) left: dD, AdamW when asked for, the mean loss.  rows_dev[0 .. B)
+// are the anchors' positives.  It ends the entry: the launches' error, and the step counted.
+int launch_grad(Adapter* ad, const Hyper& hp, const float* anchors_dev, int B, const int32_t* rows_dev, int64_t n_rows,
+                const StepArrays& a, float* loss_out_dev, float* grad_out_dev, hipStream_t st) {
+    const int d = ad->dim;
+    const AdamW o = hp.update ? adamw_of(ad->t, hp) : AdamW{};
+    hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((d / 32) * (d / 32) + 1)), dim3(64), 0, st, (const float*)a.dZ, anchors_dev,
+                       B, d, rows_dev, n_rows, (const float*)a.loss_i, loss_out_dev, grad_out_dev, hp.update ? 1 : 0, o,
+                       ad->delta, ad->delta_t, ad->m, ad->v);
+    ICREC_HIP(hipGetLastError());
+    if (hp.update) ad->t += 1;
+    return ICREC_OK;
+}
 
 }  // namespace
 }  // namespace icrec
@@ -860,47 +925,26 @@ int icrec_adapter_step(icrec_index* idx, icrec_adapter* h, const float* anchors_
                        void* stream) {
     const Index* ix = reinterpret_cast<const Index*>(idx);
     Adapter* ad = reinterpret_cast<Adapter*>(h);
-    ICREC_REQUIRE(ix != nullptr, "icrec_adapter_step: NULL idx");
-    ICREC_REQUIRE(ad != nullptr, "icrec_adapter_step: NULL adapter");
-    ICREC_REQUIRE(anchors_dev != nullptr && cand_rows_dev != nullptr, "icrec_adapter_step: NULL anchors or cand_rows");
-    ICREC_REQUIRE(loss_out_dev != nullptr, "icrec_adapter_step: NULL loss_out");
-    ICREC_REQUIRE(workspace_dev != nullptr, "icrec_adapter_step: NULL workspace");
-    ICREC_REQUIRE(ix->dim == ad->dim, "icrec_adapter_step: the index has dim %d, the adapter %d", ix->dim, ad->dim);
-    ICREC_REQUIRE(ix->device == ad->device, "icrec_adapter_step: the index is on device %d, the adapter on %d", ix->device,
-                  ad->device);
-    ICREC_REQUIRE(ix->n_rows >= 1, "icrec_adapter_step: the index has no rows");
-    ICREC_REQUIRE(B >= 1 && B <= ICREC_ADAPTER_MAX_BATCH, "icrec_adapter_step: B must be in [1, %d] (got %d)",
-                  ICREC_ADAPTER_MAX_BATCH, B);
+    const Hyper hp{scale, lr, beta1, beta2, eps, weight_decay, update != 0};
+    const int rc = check_step("icrec_adapter_step", "cand_rows", ix, ad, anchors_dev, cand_rows_dev, loss_out_dev, workspace_dev,
+                              B, hp);
+    if (rc != ICREC_OK) return rc;
     ICREC_REQUIRE(C >= B && C <= ICREC_ADAPTER_MAX_CANDIDATES, "icrec_adapter_step: C must be in [B, %d] (got %d, B %d)",
                   ICREC_ADAPTER_MAX_CANDIDATES, C, B);
-    ICREC_REQUIRE(isfinite(scale) && isfinite(lr) && isfinite(beta1) && isfinite(beta2) && isfinite(eps) && isfinite(weight_decay),
-                  "icrec_adapter_step: a hyper-parameter is not finite");
-    ICREC_REQUIRE(!update || (beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f),
-                  "icrec_adapter_step: beta1 and beta2 must be in [0, 1) and eps >= 0");
     const StepWorkspace ws(ad->dim, B);
     ICREC_REQUIRE(workspace_bytes >= ws.total, "icrec_adapter_step: the workspace has %zu bytes, %zu are needed",
                   workspace_bytes, ws.total);
     ICREC_HIP(hipSetDevice(ad->device));
     hipStream_t st = (hipStream_t)stream;
-    char* base = static_cast<char*>(workspace_dev);
-    float* U = reinterpret_cast<float*>(base + ws.u);
-    float* dZ = reinterpret_cast<float*>(base + ws.dz);
-    float* nrm = reinterpret_cast<float*>(base + ws.nrm);
-    float* loss_i = reinterpret_cast<float*>(base + ws.loss);
-    const int d = ad->dim;
-    const AdamW o = update ? adamw_of(ad->t, lr, beta1, beta2, eps, weight_decay) : AdamW{};
-    hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((B + FWD_TILE - 1) / FWD_TILE)), dim3(FWD_THREADS), 0, st,
-                       (const float*)ad->delta_t, d, anchors_dev, (int)B, U, nrm);
+    const StepArrays a(static_cast<char*>(workspace_dev), ws);
+    launch_forward(ad, anchors_dev, B, a, st);
     hipLaunchKernelGGL((rows_are_bf16(ix) ? logits_kernel<true> : logits_kernel<false>),
-                       dim3((unsigned)((B + ANCHOR_TILE - 1) / ANCHOR_TILE)), dim3(LOGIT_THREADS), 0, st, (const void*)ix->rows, d,
-                       ix->n_rows, (const float*)U, (const float*)nrm, cand_rows_dev, (int)B, (int)C, scale, dZ, loss_i);
-    hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((d / 32) * (d / 32) + 1)), dim3(64), 0, st, (const float*)dZ, anchors_dev,
-                       (int)B, d, cand_rows_dev, ix->n_rows, (const float*)loss_i, loss_out_dev, grad_out_dev, update ? 1 : 0, o,
-                       ad->delta, ad->delta_t, ad->m, ad->v);
-    ICREC_HIP(hipGetLastError());
-    if (update) ad->t += 1;
-    return ICREC_OK;
+                       dim3((unsigned)((B + ANCHOR_TILE - 1) / ANCHOR_TILE)), dim3(LOGIT_THREADS), 0, st, (const void*)ix->rows,
+                       ad->dim, ix->n_rows, (const float*)a.U, (const float*)a.nrm, cand_rows_dev, (int)B, (int)C, scale, a.dZ,
+                       a.loss_i);
+    return launch_grad(ad, hp, anchors_dev, B, cand_rows_dev, ix->n_rows, a, loss_out_dev, grad_out_dev, st);
 }
+
 
 int icrec_adapter_catalog_plan(const icrec_adapter* h, int32_t B, int64_t n_rows, int32_t* n_splits, int64_t* rows_per_split) {
     ICREC_REQUIRE(h != nullptr, "icrec_adapter_catalog_plan: NULL adapter");
@@ -927,21 +971,10 @@ int icrec_adapter_step_catalog(icrec_index* idx, icrec_adapter* h, const float* 
                                size_t workspace_bytes, void* stream) {
     const Index* ix = reinterpret_cast<const Index*>(idx);
     Adapter* ad = reinterpret_cast<Adapter*>(h);
-    ICREC_REQUIRE(ix != nullptr, "icrec_adapter_step_catalog: NULL idx");
-    ICREC_REQUIRE(ad != nullptr, "icrec_adapter_step_catalog: NULL adapter");
-    ICREC_REQUIRE(anchors_dev != nullptr && pos_rows_dev != nullptr, "icrec_adapter_step_catalog: NULL anchors or pos_rows");
-    ICREC_REQUIRE(loss_out_dev != nullptr, "icrec_adapter_step_catalog: NULL loss_out");
-    ICREC_REQUIRE(workspace_dev != nullptr, "icrec_adapter_step_catalog: NULL workspace");
-    ICREC_REQUIRE(ix->dim == ad->dim, "icrec_adapter_step_catalog: the index has dim %d, the adapter %d", ix->dim, ad->dim);
-    ICREC_REQUIRE(ix->device == ad->device, "icrec_adapter_step_catalog: the index is on device %d, the adapter on %d",
-                  ix->device, ad->device);
-    ICREC_REQUIRE(ix->n_rows >= 1, "icrec_adapter_step_catalog: the index has no rows");
-    ICREC_REQUIRE(B >= 1 && B <= ICREC_ADAPTER_MAX_BATCH, "icrec_adapter_step_catalog: B must be in [1, %d] (got %d)",
-                  ICREC_ADAPTER_MAX_BATCH, B);
-    ICREC_REQUIRE(isfinite(scale) && isfinite(lr) && isfinite(beta1) && isfinite(beta2) && isfinite(eps) && isfinite(weight_decay),
-                  "icrec_adapter_step_catalog: a hyper-parameter is not finite");
-    ICREC_REQUIRE(!update || (beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps >= 0.0f),
-                  "icrec_adapter_step_catalog: beta1 and beta2 must be in [0, 1) and eps >= 0");
+    const Hyper hp{scale, lr, beta1, beta2, eps, weight_decay, update != 0};
+    const int rc = check_step("icrec_adapter_step_catalog", "pos_rows", ix, ad, anchors_dev, pos_rows_dev, loss_out_dev,
+                              workspace_dev, B, hp);
+    if (rc != ICREC_OK) return rc;
     const int64_t n_rows = ix->n_rows;  // the rows of this call: the plan, every bound and the count use this one value
     const CatalogPlan plan = catalog_plan(B, n_rows);
     const CatalogWorkspace ws(ad->dim, B, plan.n_splits);
@@ -950,10 +983,7 @@ int icrec_adapter_step_catalog(icrec_index* idx, icrec_adapter* h, const float* 
     ICREC_HIP(hipSetDevice(ad->device));
     hipStream_t st = (hipStream_t)stream;
     char* base = static_cast<char*>(workspace_dev);
-    float* U = reinterpret_cast<float*>(base + ws.step.u);
-    float* dZ = reinterpret_cast<float*>(base + ws.step.dz);
-    float* nrm = reinterpret_cast<float*>(base + ws.step.nrm);
-    float* loss_i = reinterpret_cast<float*>(base + ws.step.loss);
+    const StepArrays a(base, ws.step);
     float* s_pos = reinterpret_cast<float*>(base + ws.s_pos);
     float* ml = reinterpret_cast<float*>(base + ws.ml);
     int32_t* counted = reinterpret_cast<int32_t*>(base + ws.counted);
@@ -961,28 +991,22 @@ int icrec_adapter_step_catalog(icrec_index* idx, icrec_adapter* h, const float* 
     float* l_part = reinterpret_cast<float*>(base + ws.l_part);
     float* part = reinterpret_cast<float*>(base + ws.part);
     const int d = ad->dim;
-    const AdamW o = update ? adamw_of(ad->t, lr, beta1, beta2, eps, weight_decay) : AdamW{};
     const bool p16 = rows_are_bf16(ix);
     const dim3 grid((unsigned)((B + ANCHOR_TILE - 1) / ANCHOR_TILE), (unsigned)plan.n_splits);
-    hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((B + FWD_TILE - 1) / FWD_TILE)), dim3(FWD_THREADS), 0, st,
-                       (const float*)ad->delta_t, d, anchors_dev, (int)B, U, nrm);
+    launch_forward(ad, anchors_dev, B, a, st);
     hipLaunchKernelGGL((p16 ? catalog_max_sum_kernel<true> : catalog_max_sum_kernel<false>), grid, dim3(LOGIT_THREADS), 0, st,
-                       (const void*)ix->rows, d, n_rows, plan.rows_per_split, (const float*)U, pos_rows_dev, (int)B, scale,
+                       (const void*)ix->rows, d, n_rows, plan.rows_per_split, (const float*)a.U, pos_rows_dev, (int)B, scale,
                        m_part, l_part, s_pos);
     hipLaunchKernelGGL(catalog_merge_kernel, dim3(1), dim3(ICREC_ADAPTER_MAX_BATCH), 0, st, (const float*)m_part,
                        (const float*)l_part, plan.n_splits, pos_rows_dev, (int)B, n_rows, ml, counted);
     hipLaunchKernelGGL((p16 ? catalog_du_kernel<true> : catalog_du_kernel<false>), grid, dim3(LOGIT_THREADS), 0, st,
-                       (const void*)ix->rows, d, n_rows, plan.rows_per_split, (const float*)U, (const float*)ml,
+                       (const void*)ix->rows, d, n_rows, plan.rows_per_split, (const float*)a.U, (const float*)ml,
                        (const int32_t*)counted, pos_rows_dev, (int)B, scale, part);
     hipLaunchKernelGGL(catalog_finish_kernel, dim3((unsigned)B), dim3(FINISH_THREADS), 0, st, (const float*)part, plan.n_splits,
-                       (int)B, d, (const float*)U, (const float*)nrm, (const float*)ml, (const float*)s_pos, pos_rows_dev, n_rows,
-                       scale, dZ, loss_i);
-    hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((d / 32) * (d / 32) + 1)), dim3(64), 0, st, (const float*)dZ, anchors_dev,
-                       (int)B, d, pos_rows_dev, n_rows, (const float*)loss_i, loss_out_dev, grad_out_dev, update ? 1 : 0, o,
-                       ad->delta, ad->delta_t, ad->m, ad->v);
-    ICREC_HIP(hipGetLastError());
-    if (update) ad->t += 1;
-    return ICREC_OK;
+                       (int)B, d, (const float*)a.U, (const float*)a.nrm, (const float*)ml, (const float*)s_pos, pos_rows_dev,
+                       n_rows, scale, a.dZ, a.loss_i);
+    return launch_grad(ad, hp, anchors_dev, B, pos_rows_dev, n_rows, a, loss_out_dev, grad_out_dev, st);
 }
+
 
 }  // extern "C"
