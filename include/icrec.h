@@ -791,6 +791,52 @@ ICREC_API int icrec_adapter_step_catalog(icrec_index* idx, icrec_adapter* adapte
                                void* workspace_dev, size_t workspace_bytes, void* stream);
 ICREC_API int icrec_adapter_catalog_plan(const icrec_adapter* adapter, int32_t B, int64_t n_rows, int32_t* n_splits,
                                int64_t* rows_per_split);
+/* The step over per-anchor lists with graded targets: what a deployed recommender records (per request the products
+ * shown and what happened to each) and what a teacher gives (per query its candidates with a score each).  Every
+ * anchor has its own candidates and non-negative targets instead of one label: the listwise softmax cross-entropy.
+ *   list_off_dev    int32[B+1]  CSR offsets
+ *   list_rows_dev   int32[...]  LOCAL rows of idx, per anchor, in any order
+ *   list_target_dev float[...]  gains >= 0 (or a teacher's probabilities)
+ *   max_len         in [1, ICREC_ADAPTER_MAX_LIST]: entries read per segment
+ *   the other arguments as in icrec_adapter_step
+ * Entries read.  Anchor i's segment is [list_off[i], list_off[i+1]); only its first max_len entries are read.  A
+ *   segment whose end lies before its start is empty.  The offsets must lie inside the arrays (icrec_compose_queries'
+ *   convention).
+ * Live entry.  An entry is live when 0 <= row < n_rows (n_rows as of the call) and its target is finite and >= 0.  An
+ *   entry that is not live contributes nothing, to the softmax or to the targets, and its row is never read.  No
+ *   unchecked value becomes an address: the call is memory-safe for any device lists.  A row listed twice is two
+ *   entries.
+ * Counted anchor.  Anchor i is counted iff T_i, the sum of its live targets, is finite and > 0.  An anchor that is not
+ *   counted has neither loss nor gradient.  If no anchor is counted, the loss is 0 and the gradient is exactly 0.
+ * Loss.  z, n, u as in icrec_adapter_step.  s_e = scale * (u_i . v_row(e)), on the STORED row (bf16 widened exactly);
+ *     t_e = target_e / T_i;   loss_i = logsumexp_e s_e - sum_e t_e s_e, over the live entries
+ *   The loss is the mean of loss_i over the counted anchors, summed as icrec_adapter_step sums: two levels in double,
+ *   rounded once.
+ * Gradient.  P = softmax_e(s_e), G_e = (P_e - t_e) / counted, du_i = scale * sum_e G_e v_e; dz, dD and the AdamW update
+ *   are exactly icrec_adapter_step's.
+ * Order.  u_i . v is, per lane of a wave of 64, an fmaf chain over the row's 16-byte pieces lane, lane + 64, ..
+ *   (4 fp32 or 8 bf16 features each, features ascending), then the xor butterfly 32, 16, .., 1 over the lanes.  T_i,
+ *   the softmax's sum (fp32, the maximum subtracted before exp) and sum_e t_e s_e (in double; loss_i is rounded to fp32
+ *   once) are each a lane's chain over entries lane, lane + 64, .. in list order, then that butterfly.  The sum over e
+ *   of du is, per feature, groups of 128 entries - each one fmaf chain from zero in list order - added in group order.
+ *   u . du is an fmaf chain over the features of a piece, the butterfly over a wave's 64 pieces, the four waves in
+ *   order.  No floating-point atomics: the same inputs give the same bits.
+ * Consequences: a list with one live entry has loss exactly 0 and gradient exactly 0; if every anchor's list is one
+ *   shared list of distinct in-range rows and the targets are one-hot at position i, the loss is icrec_adapter_step's
+ *   on that candidate list.
+ * Workspace: icrec_adapter_step_lists_workspace_bytes(adapter, B) bytes (0 outside the limits / NULL).  Four launches
+ *   on `stream`; nothing is allocated, nothing synchronises.
+ * ICREC_EINVAL, before any HIP call: icrec_adapter_step's conditions, a NULL among the three list arrays, max_len
+ *   outside its range. */
+#define ICREC_ADAPTER_MAX_LIST 1024      /* entries read per anchor */
+ICREC_API size_t icrec_adapter_step_lists_workspace_bytes(const icrec_adapter* adapter, int32_t B);   /* 0 outside the limits / NULL */
+ICREC_API int icrec_adapter_step_lists(icrec_index* idx, icrec_adapter* adapter, const float* anchors_dev, int32_t B,
+                             const int32_t* list_off_dev   /* int32[B+1]  CSR offsets                                  */,
+                             const int32_t* list_rows_dev  /* int32[...]  LOCAL rows of idx, per anchor, in any order   */,
+                             const float*   list_target_dev/* float[...]  gains >= 0 (or a teacher's probabilities)     */,
+                             int32_t max_len               /* [1, ICREC_ADAPTER_MAX_LIST]: entries read per segment     */,
+                             float scale, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t update,
+                             float* loss_out_dev, float* grad_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Caps per facet value on a search result ("at most two products of one aisle, at most five of one department"):
  * walk each query's k candidates in their order and keep a candidate only while every capped facet still has room for

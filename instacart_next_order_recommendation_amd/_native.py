@@ -19,6 +19,7 @@ ICREC_MAX_TERMS = 1024
 ICREC_ADAPTER_MAX_DIM = 1024
 ICREC_ADAPTER_MAX_BATCH = 1024
 ICREC_ADAPTER_MAX_CANDIDATES = 8192
+ICREC_ADAPTER_MAX_LIST = 1024
 ICREC_MAX_FACETS = 2
 ICREC_FACET_MASK_WORDS = 8
 ICREC_MAX_ROWSETS = 65535
@@ -56,6 +57,7 @@ EXPORTS = [
     "icrec_adapter_create", "icrec_adapter_destroy", "icrec_adapter_dim", "icrec_adapter_set_state",
     "icrec_adapter_get_state", "icrec_adapter_apply", "icrec_adapter_step_workspace_bytes", "icrec_adapter_step",
     "icrec_adapter_step_catalog_workspace_bytes", "icrec_adapter_step_catalog", "icrec_adapter_catalog_plan",
+    "icrec_adapter_step_lists_workspace_bytes", "icrec_adapter_step_lists",
     "icrec_ivf_create", "icrec_ivf_destroy", "icrec_ivf_lists", "icrec_ivf_layout",
     "icrec_ivf_search_workspace_bytes", "icrec_ivf_search",
     "icrec_scores", "icrec_normalize_rows", "icrec_rank_all_workspace_bytes", "icrec_rank_all",
@@ -193,6 +195,9 @@ def lib() -> C.CDLL:
         "icrec_adapter_step_catalog": (C.c_int, [vp, vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                                  C.c_float, i32, vp, vp, vp, sz, vp]),
         "icrec_adapter_catalog_plan": (C.c_int, [vp, i32, i64, C.POINTER(i32), C.POINTER(i64)]),
+        "icrec_adapter_step_lists_workspace_bytes": (sz, [vp, i32]),
+        "icrec_adapter_step_lists": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, C.c_float, C.c_float, C.c_float, C.c_float,
+                                               C.c_float, C.c_float, i32, vp, vp, vp, sz, vp]),
         "icrec_ivf_create": (C.c_int, [vp, vp, i32, C.POINTER(vp)]),
         "icrec_ivf_destroy": (C.c_int, [vp]),
         "icrec_ivf_lists": (i32, [vp]),

@@ -69,6 +69,37 @@ def fit_plan(n_pairs: int, epochs, batch_size, negatives, lr, weight_decay, scal
     return batch, per_epoch, total, int(0.1 * total)
 
 
+def impression_csr(lists, B: int, device: str | torch.device = "cpu"):
+    """Per-anchor impression lists -> (off int32 [B + 1], rows int32 [n], target float32 [n], max_len) as tensors on
+    `device`: icrec_adapter_step_lists' three arrays and the longest list (at least 1).  Each of the B lists is a
+    mapping {row: gain} or a sequence of (row, gain); a row named twice in one list keeps the larger gain, at its first
+    place.  A row beyond int32 becomes -1 (out of range for any index); gains are not judged here - the step drops an
+    entry whose gain is negative or not finite.  ValueError: a string, not B lists, more than ICREC_ADAPTER_MAX_LIST
+    entries in one list."""
+    if isinstance(lists, (str, bytes)):
+        raise ValueError("lists must be one list of (row, gain) per anchor, not a string")
+    lists = list(lists)
+    if len(lists) != int(B):
+        raise ValueError(f"{int(B)} anchors for {len(lists)} lists")
+    off, rows, target = [0], [], []
+    for i, entries in enumerate(lists):
+        if isinstance(entries, (str, bytes)):
+            raise ValueError(f"list {i} must be a mapping row -> gain or a sequence of (row, gain), not a string")
+        best: dict[int, float] = {}
+        for row, gain in (entries.items() if hasattr(entries, "items") else entries):
+            row, gain = int(row), float(gain)
+            if row not in best or gain > best[row]:
+                best[row] = gain
+        if len(best) > _native.ICREC_ADAPTER_MAX_LIST:
+            raise ValueError(f"list {i} has {len(best)} entries, the limit is {_native.ICREC_ADAPTER_MAX_LIST}")
+        rows.extend(r if 0 <= r <= 2**31 - 1 else -1 for r in best)
+        target.extend(best.values())
+        off.append(len(rows))
+    max_len = max(1, max((b - a for a, b in zip(off, off[1:])), default=1))
+    return (torch.tensor(off, dtype=torch.int32, device=device), torch.tensor(rows, dtype=torch.int32, device=device),
+            torch.tensor(target, dtype=torch.float32, device=device), max_len)
+
+
 class QueryAdapter:
     """An icrec_adapter: D (fp32, dim x dim, zero when created), AdamW's moments and the step count, on one HIP device.
     The arrays never move, so a captured graph that holds apply_into stays valid while the adapter trains."""
@@ -129,31 +160,139 @@ class QueryAdapter:
         return rows
 
     def _step(self, catalog: bool, index, anchors, rows, scale, lr=0.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-              update: bool = False, grad_out=None, loss_out=None, want_grad: bool = False):
-        """One call of icrec_adapter_step (rows: the candidate list) or, with `catalog`, of icrec_adapter_step_catalog
-        (rows: a positive per anchor) -> (loss float32 [], grad_out).  Without `update` the adapter is not changed;
-        want_grad: a new grad_out."""
+              update: bool = False, grad_out=None, loss_out=None, want_grad: bool = False, lists=None):
+        """One call of icrec_adapter_step (rows: the candidate list), with `catalog` of icrec_adapter_step_catalog
+        (rows: a positive per anchor) or, with `lists` (_csr's four values; rows is None), of icrec_adapter_step_lists
+        -> (loss float32 [], grad_out).  Without `update` the adapter is not changed; want_grad: a new grad_out."""
         anchors = self._rows(anchors, "anchors")
-        rows = self._row_list(rows, "positive_rows" if catalog else "cand_rows")
-        B, n = int(anchors.shape[0]), int(rows.shape[0])
+        B = int(anchors.shape[0])
         L = _native.lib()
-        if catalog:
-            if n != B:
-                raise ValueError(f"{B} anchors for {n} positives")
-            name, n_cand = "icrec_adapter_step_catalog", ()  # no list: its C is the index's row count
-            need = L.icrec_adapter_step_catalog_workspace_bytes(self._h, index._h, B)
+        if lists is not None:
+            off, list_rows, target, max_len = lists
+            if int(off.shape[0]) != B + 1:
+                raise ValueError(f"{B} anchors for {int(off.shape[0]) - 1} lists")
+            name, what = "icrec_adapter_step_lists", (_native.ptr(off), _native.ptr(list_rows), _native.ptr(target), int(max_len))
+            need = L.icrec_adapter_step_lists_workspace_bytes(self._h, B)
         else:
-            name, n_cand = "icrec_adapter_step", (n,)
-            need = L.icrec_adapter_step_workspace_bytes(self._h, B, n)
+            rows = self._row_list(rows, "positive_rows" if catalog else "cand_rows")
+            n = int(rows.shape[0])
+            if catalog:
+                if n != B:
+                    raise ValueError(f"{B} anchors for {n} positives")
+                name, what = "icrec_adapter_step_catalog", (_native.ptr(rows),)  # no list: its C is the index's row count
+                need = L.icrec_adapter_step_catalog_workspace_bytes(self._h, index._h, B)
+            else:
+                name, what = "icrec_adapter_step", (_native.ptr(rows), n)
+                need = L.icrec_adapter_step_workspace_bytes(self._h, B, n)
         ws = self._scratch.block(max(int(need), 256))
         loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=self.device)
         if want_grad:
             grad_out = torch.empty((self.dim, self.dim), dtype=torch.float32, device=self.device)
-        _native.check(getattr(L, name)(index._h, self._h, _native.ptr(anchors), B, _native.ptr(rows), *n_cand, float(scale),
+        _native.check(getattr(L, name)(index._h, self._h, _native.ptr(anchors), B, *what, float(scale),
                                        float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                        1 if update else 0, _native.ptr(loss), _native.ptr(grad_out), _native.ptr(ws),
                                        ws.numel(), _native.stream_ptr(self.device)), name)
         return loss[0], grad_out
+
+    # -- per-anchor lists ----------------------------------------------------------------------------
+    def _csr(self, lists, B: int):
+        """lists as the step takes them: impression_csr's values on this device, from per-anchor lists or from an
+        (off, rows, target, max_len) already made (tensors of any device; kept alive by the caller's tuple)."""
+        if isinstance(lists, tuple) and len(lists) == 4 and isinstance(lists[0], torch.Tensor):
+            off, rows, target, max_len = lists
+        else:
+            off, rows, target, max_len = impression_csr(lists, B, self.device)
+        off = off.to(self.device, torch.int32).contiguous()
+        rows = rows.to(self.device, torch.int32).contiguous()
+        target = target.to(self.device, torch.float32).contiguous()
+        if off.ndim != 1 or rows.ndim != 1 or target.shape != rows.shape:
+            raise ValueError("lists: off, rows and target must be flat, rows and target of one length")
+        if rows.numel() == 0:  # nothing listed at all: one dropped entry, so that the arrays exist
+            rows, target = rows.new_full((1,), -1), target.new_zeros(1)
+            off = torch.zeros_like(off)
+        return off, rows, target, int(max_len)
+
+    def loss_and_grad_lists(self, index, anchors, lists, scale: float = DEFAULT_SCALE):
+        """(loss float32 [], dD float32 [dim, dim]) of the listwise softmax cross-entropy (include/icrec.h,
+        icrec_adapter_step_lists): anchor i against its own list of (stored row of index, gain >= 0) - per anchor a
+        mapping or a sequence of pairs, or impression_csr's tuple.  The adapter is not changed."""
+        lists = self._csr(lists, int(np.shape(anchors)[0]))
+        return self._step(False, index, anchors, None, scale, want_grad=True, lists=lists)
+
+    def step_lists(self, index, anchors, lists, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
+                   scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None,
+                   loss_out: Optional[torch.Tensor] = None):
+        """step on loss_and_grad_lists' loss: one AdamW step -> the batch's loss before the step, a float32 [] device
+        tensor.  No host synchronisation when `lists` is impression_csr's tuple on this device."""
+        lists = self._csr(lists, int(np.shape(anchors)[0]))
+        return self._step(False, index, anchors, None, scale, lr, betas, eps, weight_decay, True, grad_out, loss_out,
+                          lists=lists)[0]
+
+    @staticmethod
+    def _padded(csr, n_rows: int):
+        """A CSR's entries read as [B, max_len] device matrices (rows, targets; -1 / 0 behind a segment's end) and the
+        anchors the step counts: T_i, the sum of the live targets, finite and > 0."""
+        off, rows, target, max_len = csr
+        lo = off[:-1].to(torch.int64)
+        length = (off[1:].to(torch.int64) - lo).clamp(0, max_len)
+        at = torch.arange(max_len, device=off.device)[None, :]
+        inside = at < length[:, None]
+        idx = torch.where(inside, lo[:, None] + at, torch.zeros_like(at))
+        r = torch.where(inside, rows[idx], torch.full_like(rows[idx], -1))
+        t = torch.where(inside, target[idx], torch.zeros_like(target[idx]))
+        live = (r >= 0) & (r < int(n_rows)) & torch.isfinite(t) & (t >= 0)
+        T = torch.where(live, t, torch.zeros_like(t)).sum(dim=1)
+        return r, t, torch.isfinite(T) & (T > 0)
+
+    def lists_loss(self, index, anchors, lists, scale: Optional[float] = None) -> float:
+        """The listwise loss of a held-out set: the mean over its counted anchors.  Batches of at most
+        ICREC_ADAPTER_MAX_BATCH; the batch means are combined, weighted by their counted anchors, in double on the
+        host, which is read back once.  scale=None: the adapter's own scale."""
+        anchors = self._rows(anchors, "anchors")
+        n = int(anchors.shape[0])
+        off, rows, target, max_len = self._csr(lists, n)
+        if int(off.shape[0]) != n + 1:
+            raise ValueError(f"{n} anchors for {int(off.shape[0]) - 1} lists")
+        scale = self.scale if scale is None else float(scale)
+        step = _native.ICREC_ADAPTER_MAX_BATCH
+        starts = range(0, n, step)
+        means = torch.zeros(len(starts), dtype=torch.float32, device=self.device)
+        for k, lo in enumerate(starts):
+            self._step(False, index, anchors[lo:lo + step], None, scale, loss_out=means[k:k + 1],
+                       lists=(off[lo:lo + step + 1].contiguous(), rows, target, max_len))
+        is_counted = self._padded((off, rows, target, max_len), index.n_rows)[2].to(torch.float64)
+        counted = torch.stack([is_counted[lo:lo + step].sum() for lo in starts])
+        host = torch.stack([means.to(torch.float64), counted]).cpu().numpy()  # the one read-back
+        total = float(host[1].sum())
+        return float((host[0] * host[1]).sum() / total) if total > 0 else 0.0
+
+    def fit_lists(self, index, anchor_embeddings, lists, epochs: int = 5, batch_size: int = 64, lr: float = 2e-3,
+                  weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0) -> list[float]:
+        """Train on (anchor_embeddings[i], lists[i]) with step_lists -> the per-step losses.  fit's shuffles (a CPU
+        torch.Generator seeded with `seed`), warm-up, cosine schedule, drop_last and single read-back; nothing is drawn
+        beside the shuffles: an anchor's negatives are the entries of its own list."""
+        anchors = self._rows(anchor_embeddings, "anchor_embeddings")
+        n = int(anchors.shape[0])
+        csr = self._csr(lists, n)
+        if int(csr[0].shape[0]) != n + 1:
+            raise ValueError(f"{n} anchors for {int(csr[0].shape[0]) - 1} lists")
+        batch, per_epoch, total, warmup = fit_plan(n, epochs, batch_size, 0, lr, weight_decay, scale)
+        max_len = csr[3]
+        rows_pad, target_pad, _ = self._padded(csr, index.n_rows)  # a batch is a gather of whole padded lists
+        off = torch.arange(batch + 1, dtype=torch.int32, device=self.device) * max_len
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        losses = torch.zeros(total, dtype=torch.float32, device=self.device)
+        s = 0
+        for _ in range(int(epochs)):
+            perm = torch.randperm(n, generator=gen)
+            for b in range(per_epoch):
+                at = perm[b * batch:(b + 1) * batch].to(self.device)
+                self._step(False, index, anchors[at], None, scale, float(lr) * schedule(s, total, warmup),
+                           weight_decay=weight_decay, update=True, loss_out=losses[s:s + 1],
+                           lists=(off, rows_pad[at].reshape(-1), target_pad[at].reshape(-1), max_len))
+                s += 1
+        self.scale = float(scale)
+        return losses.cpu().tolist()
 
     def loss_and_grad(self, index, anchors, cand_rows, scale: float = DEFAULT_SCALE):
         """(loss float32 [], dD float32 [dim, dim]) on the device, of the anchors [B, dim] against index's stored rows

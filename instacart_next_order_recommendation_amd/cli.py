@@ -26,6 +26,10 @@ encoder.  `fit-adapter` as the first argument learns one from (context, product)
                                                                   [--negatives M|all] [--lr LR] [--weight-decay WD]
                                                                   [--scale S] [--seed N]
 
+With `--lists FILE.jsonl [--gain EVENT=G ...]` in place of `--pairs` it learns from impression lists - lines of
+{"anchor": text, "products": {product_id: event name or gain, ...}}, what was shown for a context and what happened to
+each product - with the listwise loss (Recommender.fit_adapter_lists; impression=0 click=1 add_to_cart=2 purchase=4).
+
 `baselines` as the first argument runs the reference's `python -m src.baselines.run_baselines` instead: the content-based
 and the item-item CF baseline over a processed directory, eight IR metrics each (configs/baselines.yaml; keys
 processed_dir, data_dir, model_name, content_only, cf_only).
@@ -85,6 +89,43 @@ def read_pairs(path: Path) -> list[tuple[str, str]]:
     return pairs
 
 
+def read_lists(path: Path) -> tuple[list[tuple[str, dict]], list[str]]:
+    """A .jsonl of {"anchor": context text, "products": {product id: event name or gain}} -> ([(text, products)], what
+    names each of them in a message: "FILE:line"); blank lines are skipped.  ValueError names the first line that is not
+    such an object."""
+    lists, where = [], []
+    for n, line in enumerate(Path(path).read_text().splitlines(), 1):
+        if not line.strip():
+            continue
+        try:
+            row = json.loads(line)
+            anchor, products = row["anchor"], row["products"]
+        except (ValueError, KeyError, TypeError):
+            raise ValueError(f"{path}:{n}: not a {{\"anchor\": ..., \"products\": {{...}}}} object")
+        if not isinstance(anchor, str):
+            raise ValueError(f"{path}:{n}: the anchor must be a string")
+        if not isinstance(products, dict):
+            raise ValueError(f"{path}:{n}: products must be an object of product id -> event name or gain")
+        lists.append((anchor, {str(pid): v for pid, v in products.items()}))
+        where.append(f"{path}:{n}")
+    return lists, where
+
+
+def gain_args(entries, defaults: dict) -> dict:
+    """--gain EVENT=G ...: `defaults` with the named events' gains replaced or added.  ValueError: an entry that is not
+    EVENT=number."""
+    gains = dict(defaults)
+    for entry in entries or []:
+        event, sep, value = entry.partition("=")
+        try:
+            gains[event] = float(value)
+        except ValueError:
+            sep = ""
+        if not sep or not event:
+            raise ValueError(f"--gain takes EVENT=number, got {entry!r}")
+    return gains
+
+
 def negatives_arg(text: str):
     """--negatives: an integer, or 'all' (QueryAdapter.fit's negatives="all")."""
     return "all" if text == "all" else int(text)
@@ -94,8 +135,13 @@ def fit_adapter_main(argv) -> int:
     ap = argparse.ArgumentParser(prog="instacart_next_order_recommendation_amd fit-adapter",
                                  description="Learn a query adapter from (context, product) pairs on the GPU.")
     ap.add_argument("--config", type=Path, default=None, help="YAML settings (default: configs/inference.yaml): model_dir, corpus")
-    ap.add_argument("--pairs", type=Path, required=True, metavar="FILE.jsonl",
+    ap.add_argument("--pairs", type=Path, default=None, metavar="FILE.jsonl",
                     help='lines of {"anchor": context text, "positive": product_id}')
+    ap.add_argument("--lists", type=Path, default=None, metavar="FILE.jsonl",
+                    help='instead of --pairs: impression lists, lines of {"anchor": context text, "products": {product_id: '
+                         'event name or gain}}, trained with the listwise loss')
+    ap.add_argument("--gain", action="append", default=None, metavar="EVENT=G",
+                    help="with --lists: the gain of an event (default: impression=0 click=1 add_to_cart=2 purchase=4)")
     ap.add_argument("--out", type=Path, required=True, metavar="FILE", help="where the adapter is written (.npz)")
     ap.add_argument("--adapter", type=Path, default=None, metavar="FILE", help="an adapter to train further")
     ap.add_argument("--epochs", type=int, default=5)
@@ -108,14 +154,25 @@ def fit_adapter_main(argv) -> int:
     ap.add_argument("--scale", type=float, default=30.0, help="the loss scale (the reference trains with 30)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
+    if (args.pairs is None) == (args.lists is None):
+        ap.error("exactly one of --pairs and --lists must be given")
+    if args.gain and args.lists is None:
+        ap.error("--gain goes with --lists")
     cfg = read_settings(args.config)
     if not cfg["corpus"].exists():
         raise SystemExit(f"corpus file {cfg['corpus']} does not exist (this build never downloads one)")
-    if not args.pairs.exists():
-        raise SystemExit(f"pairs file {args.pairs} does not exist")
+    source = args.pairs if args.lists is None else args.lists
+    if not source.exists():
+        raise SystemExit(f"{'pairs' if args.lists is None else 'lists'} file {source} does not exist")
     start = adapter_file(cfg, args.adapter)
     try:
-        pairs = read_pairs(args.pairs)
+        if args.lists is None:
+            pairs = read_pairs(args.pairs)
+        else:
+            from .recommender import DEFAULT_GAINS
+
+            gains = gain_args(args.gain, DEFAULT_GAINS)
+            pairs, where = read_lists(args.lists)
     except ValueError as e:
         raise SystemExit(str(e))
 
@@ -123,12 +180,17 @@ def fit_adapter_main(argv) -> int:
 
     rec = Recommender(model_dir=cfg["model_dir"], corpus_path=cfg["corpus"], use_index=cfg["use_index"], adapter=start)
     try:
-        losses = rec.fit_adapter(pairs, epochs=args.epochs, batch_size=args.batch_size, negatives=args.negatives, lr=args.lr,
-                                 weight_decay=args.weight_decay, scale=args.scale, seed=args.seed)
+        if args.lists is None:
+            losses = rec.fit_adapter(pairs, epochs=args.epochs, batch_size=args.batch_size, negatives=args.negatives,
+                                     lr=args.lr, weight_decay=args.weight_decay, scale=args.scale, seed=args.seed)
+        else:
+            losses = rec.fit_adapter_lists(pairs, gains, epochs=args.epochs, batch_size=args.batch_size, lr=args.lr,
+                                           weight_decay=args.weight_decay, scale=args.scale, seed=args.seed, where=where)
     except ValueError as e:
         raise SystemExit(str(e))
     rec._adapter.save(args.out)
-    print(f"{len(pairs)} pairs, {len(losses)} steps: loss {losses[0]:.4f} -> {losses[-1]:.4f}; adapter written to {args.out}")
+    print(f"{len(pairs)} {'pairs' if args.lists is None else 'lists'}, {len(losses)} steps: loss {losses[0]:.4f} -> "
+          f"{losses[-1]:.4f}; adapter written to {args.out}")
     return 0
 
 

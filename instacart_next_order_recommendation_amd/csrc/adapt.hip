@@ -23,7 +23,10 @@
 //                   the float32 reference's error at width 32, beside a margin of 2; in two float32 levels a batch
 //                   of 65 still measured 6.29x beside a margin of 6: a chain of 64 rounds at the sum's ulp 64 times
 //                   and the mean is compared at half of ITS ulp)
-// On the host both entries run check_step, launch_forward, their own (b), launch_grad.
+//   lists_*         the step over PER-ANCHOR lists with graded targets (icrec_adapter_step_lists): no shared rows, so no
+//                   MFMA tile - lists_plan_kernel (the anchors' target sums and flag rows) and lists_kernel (a workgroup
+//                   per anchor: two gathered sweeps over its own entries) stand where (b) does
+// On the host every step entry runs check_step, launch_forward, its own middle, launch_grad.
 // The definitions (the two roundings of apply, the masking rules, the gradient, torch's AdamW) are in include/icrec.h;
 // tests/adapter_reference.py states them in numpy and torch.  No floating-point atomics anywhere: every sum has one order.
 #include <math.h>
@@ -714,6 +717,229 @@ __global__ __launch_bounds__(FINISH_THREADS) void catalog_finish_kernel(const fl
     if (tid == 0) loss_i[i] = catalog_positive(pos_rows, i, B, n_rows) >= 0 ? (ml[i] + logf(ml[B + i])) - s_pos[i] : 0.0f;
 }
 
+// ---------------------------------------------------------------- the step over per-anchor lists (icrec_adapter_step_lists)
+// Every anchor has its OWN entries (a CSR segment of rows with a target each), so there is no tile of anchors against
+// shared rows and no MFMA: the middle is a gathered matrix-vector product per anchor, twice.
+//   lists_plan_kernel  a wave per anchor: T, the sum of its live targets, and a flag row - 0 when the anchor is counted,
+//                      -1 when it is not - so that grad_kernel's row_in_range recount of the flags is the mean's divisor
+//   lists_kernel       a workgroup per anchor: the segment checked once into LDS (a dropped entry as row -1, computed
+//                      on row 0 behind a select, as compose_kernel does); sweep 1, a wave per entry, LISTS_SCORE_DEPTH
+//                      entries in flight per wave, the scores kept in LDS; (maximum, sum) and the targets' part of the
+//                      loss; G into LDS; sweep 2, compose_kernel's inner loop with the weights G; the epilogue
+// The orders (include/icrec.h states them): a score is the lane's fmaf chain over its 16-byte pieces lane, lane + 64, ..
+// features ascending, then the xor butterfly; a sum over entries in sweep 1 is the lane's chain over entries lane,
+// lane + 64, .. then the butterfly (every wave computes the same values, so nothing is broadcast); sweep 2 adds groups
+// of LISTS_GROUP entries, each one fmaf chain from zero in list order, in group order - logits_kernel's two levels.
+constexpr int LISTS_THREADS = 256;
+constexpr int LISTS_WAVES = LISTS_THREADS / 64;
+constexpr int LISTS_SCORE_DEPTH = 4;  // entries whose pieces a wave of sweep 1 loads before the first fmaf
+constexpr int LISTS_DEPTH = 8;        // entries whose pieces a thread of sweep 2 loads before the first fmaf
+constexpr int LISTS_GROUP = 128;      // entries of one chain of sweep 2
+static_assert(ICREC_ADAPTER_MAX_DIM / 4 <= LISTS_THREADS, "a thread of sweep 2 owns at most one piece of a row");
+static_assert(LISTS_GROUP % LISTS_DEPTH == 0 && LISTS_SCORE_DEPTH <= LISTS_DEPTH, "the pad behind a segment covers both sweeps");
+
+// The entries read of anchor i's segment: its first max_len, none when its end lies before its start.
+__device__ __forceinline__ int segment_entries(const int32_t* __restrict__ off, int i, int max_len, int& lo) {
+    lo = off[i];
+    const int64_t n = (int64_t)off[i + 1] - lo;
+    return n <= 0 ? 0 : (n < max_len ? (int)n : max_len);
+}
+
+// Is the entry live: a row of the index, a target that is finite and not negative.  Nothing else becomes an address.
+__device__ __forceinline__ bool entry_live(int32_t r, float target, int64_t n_rows) {
+    return row_in_range(r, n_rows) && finite_f32(target) && target >= 0.0f;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(LISTS_THREADS) void lists_plan_kernel(const int32_t* __restrict__ off, const int32_t* __restrict__ rows,
+                                                                   const float* __restrict__ target, int B, int max_len,
+                                                                   int64_t n_rows, float* __restrict__ T_out,
+                                                                   int32_t* __restrict__ flag_out) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * LISTS_WAVES + (threadIdx.x >> 6);
+    if (i >= B) return;  // a whole wave
+    int lo;
+    const int n_e = segment_entries(off, i, max_len, lo);
+    float t = 0.0f;
+    for (int e = lane; e < n_e; e += 64) {
+        const int32_t r = rows[(int64_t)lo + e];
+        const float x = target[(int64_t)lo + e];
+        t += entry_live(r, x, n_rows) ? x : 0.0f;
+    }
+    t = wave_sum_f32(t);
+    if (lane == 0) {
+        T_out[i] = t;
+        flag_out[i] = (finite_f32(t) && t > 0.0f) ? 0 : -1;
+    }
+}
+
+template <bool P16>
+__global__ __launch_bounds__(LISTS_THREADS) void lists_kernel(const void* __restrict__ rows, int K, int64_t n_rows,
+                                                              const float* __restrict__ U, const float* __restrict__ nrm,
+                                                              const int32_t* __restrict__ off, const int32_t* __restrict__ list_rows,
+                                                              const float* __restrict__ list_target, int max_len,
+                                                              const float* __restrict__ T_in, const int32_t* __restrict__ flag,
+                                                              int B, float scale, float* __restrict__ dZ,
+                                                              float* __restrict__ loss_i) {
+    typedef row_elem_t<P16> Row;
+    constexpr int P = P16 ? 8 : 4;  // features of one piece
+    __shared__ int32_t e_row[ICREC_ADAPTER_MAX_LIST + LISTS_DEPTH];  // -1: a dropped entry, or the pad behind the last one
+    __shared__ float e_t[ICREC_ADAPTER_MAX_LIST];                    // t_e = target / T; 0 for a dropped entry
+    __shared__ float e_g[ICREC_ADAPTER_MAX_LIST + LISTS_DEPTH];      // G_e; 0 for a dropped entry and in the pad
+    __shared__ float s_s[ICREC_ADAPTER_MAX_LIST];                    // s_e; -inf for a dropped entry
+    __shared__ __attribute__((aligned(16))) float us[ICREC_ADAPTER_MAX_DIM];
+    __shared__ float dot_s[LISTS_WAVES];
+    __shared__ int counted_s;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = blockIdx.x;
+    const int n_pc = K / P;
+    float* dz = dZ + (size_t)i * K;
+    if (flag[i] != 0) {  // not counted: neither loss nor gradient (the whole workgroup leaves)
+        for (int f = tid; f < K; f += LISTS_THREADS) dz[f] = 0.0f;
+        if (tid == 0) loss_i[i] = 0.0f;
+        return;
+    }
+    if (tid == 0) counted_s = 0;
+    __syncthreads();
+    int lo;
+    const int n_e = segment_entries(off, i, max_len, lo);
+    const float T = T_in[i];  // finite and > 0: the anchor is counted
+    for (int e = tid; e < n_e + LISTS_DEPTH; e += LISTS_THREADS) {
+        int32_t r = -1;
+        float t = 0.0f;
+        if (e < n_e) {
+            r = list_rows[(int64_t)lo + e];
+            const float x = list_target[(int64_t)lo + e];
+            const bool live = entry_live(r, x, n_rows);
+            r = live ? r : -1;
+            t = live ? x / T : 0.0f;
+        }
+        e_row[e] = r;
+        if (e < n_e) e_t[e] = t;
+    }
+    for (int f = tid; f < K; f += LISTS_THREADS) us[f] = U[(size_t)i * K + f];
+    int mine = 0;
+    for (int a = tid; a < B; a += LISTS_THREADS) mine += flag[a] == 0 ? 1 : 0;
+    if (mine) atomicAdd(&counted_s, mine);  // an integer count: any order gives the same value
+    __syncthreads();
+    const float inv_counted = 1.0f / (float)counted_s;  // this anchor is one of them
+
+    // sweep 1: wave w scores entries [e0, e0 + LISTS_SCORE_DEPTH), their pieces loaded before the first fmaf
+    const Row* stored = static_cast<const Row*>(rows);
+    for (int e0 = w * LISTS_SCORE_DEPTH; e0 < n_e; e0 += LISTS_WAVES * LISTS_SCORE_DEPTH) {
+        int row[LISTS_SCORE_DEPTH];
+        float dot[LISTS_SCORE_DEPTH];
+#pragma unroll
+        for (int u = 0; u < LISTS_SCORE_DEPTH; ++u) {
+            row[u] = e_row[e0 + u];
+            dot[u] = 0.0f;
+        }
+        for (int c = lane; c < n_pc; c += 64) {
+            u32x4 piece[LISTS_SCORE_DEPTH];
+#pragma unroll
+            for (int u = 0; u < LISTS_SCORE_DEPTH; ++u)  // every load is issued: a dropped entry reads row 0
+                piece[u] = *reinterpret_cast<const u32x4*>(stored + (int64_t)(row[u] < 0 ? 0 : row[u]) * K + c * P);
+            float x[P];
+#pragma unroll
+            for (int v = 0; v < P / 4; ++v) {
+                const f32x4 q = *reinterpret_cast<const f32x4*>(us + c * P + 4 * v);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[4 * v + j] = q[j];
+            }
+#pragma unroll
+            for (int u = 0; u < LISTS_SCORE_DEPTH; ++u)
+#pragma unroll
+                for (int j = 0; j < P; ++j) dot[u] = fmaf(piece_value<P16>(piece[u], j), x[j], dot[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < LISTS_SCORE_DEPTH; ++u) {
+            const float d = wave_sum_f32(dot[u]);
+            if (lane == 0 && e0 + u < n_e) s_s[e0 + u] = row[u] < 0 ? -INFINITY : scale * d;
+        }
+    }
+    __syncthreads();
+
+    // the anchor's (maximum, sum) and sum of t_e s_e, the same chains in every wave
+    float m = -INFINITY;
+    for (int e = lane; e < n_e; e += 64) m = fmaxf(m, s_s[e]);
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) m = fmaxf(m, __shfl_xor(m, k, 64));
+    float l = 0.0f;
+    double ts = 0.0;
+    for (int e = lane; e < n_e; e += 64) {
+        const float s = s_s[e];
+        l += expf(s - m);  // a dropped entry: exp(-inf) = 0
+        if (e_row[e] >= 0) ts += (double)e_t[e] * (double)s;
+    }
+    l = wave_sum_f32(l);
+    ts = wave_sum_f64(ts);
+    if (tid == 0) loss_i[i] = (float)(((double)m + log((double)l)) - ts);
+    const float inv_l = 1.0f / l;
+    for (int e = tid; e < n_e + LISTS_DEPTH; e += LISTS_THREADS)
+        e_g[e] = (e < n_e && e_row[e] >= 0) ? (expf(s_s[e] - m) * inv_l - e_t[e]) * inv_counted : 0.0f;
+    __syncthreads();
+
+    // sweep 2: thread c owns piece c of every row; du = scale * sum_e G_e v_e
+    const int c = tid;
+    const bool own = c < n_pc;
+    float du[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) du[j] = 0.0f;
+    if (own) {
+        const Row* col = stored + c * P;
+        for (int g0 = 0; g0 < n_e; g0 += LISTS_GROUP) {
+            float part[P];
+#pragma unroll
+            for (int j = 0; j < P; ++j) part[j] = 0.0f;
+            const int g1 = g0 + LISTS_GROUP < n_e ? g0 + LISTS_GROUP : n_e;
+            for (int t0 = g0; t0 < g1; t0 += LISTS_DEPTH) {
+                u32x4 piece[LISTS_DEPTH];
+                int row[LISTS_DEPTH];
+#pragma unroll
+                for (int u = 0; u < LISTS_DEPTH; ++u) {
+                    row[u] = e_row[t0 + u];
+                    piece[u] = *reinterpret_cast<const u32x4*>(col + (int64_t)(row[u] < 0 ? 0 : row[u]) * K);
+                }
+#pragma unroll
+                for (int u = 0; u < LISTS_DEPTH; ++u) {
+                    const float g = e_g[t0 + u];
+#pragma unroll
+                    for (int j = 0; j < P; ++j) {
+                        const float sum = fmaf(g, piece_value<P16>(piece[u], j), part[j]);
+                        part[j] = row[u] < 0 ? part[j] : sum;  // a select, not a branch: the waits stay counted
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < P; ++j) du[j] += part[j];
+        }
+    }
+    float dot = 0.0f;
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        du[j] = scale * du[j];
+        if (own) dot = fmaf(us[c * P + j], du[j], dot);
+    }
+    dot = wave_sum_f32(dot);
+    if (lane == 0) dot_s[w] = dot;
+    __syncthreads();
+    dot = dot_s[0];
+#pragma unroll
+    for (int x = 1; x < LISTS_WAVES; ++x) dot += dot_s[x];
+    if (!own) return;
+    const float den = nrm[i];
+#pragma unroll
+    for (int v = 0; v < P / 4; ++v) {
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (du[4 * v + j] - us[c * P + 4 * v + j] * dot) / den;
+        *reinterpret_cast<f32x4*>(dz + c * P + 4 * v) = o;
+    }
+}
+
 bool dim_ok(int32_t dim) { return dim >= 32 && dim <= ICREC_ADAPTER_MAX_DIM && dim % 32 == 0; }
 
 void release(Adapter* ad) {
@@ -775,7 +1001,19 @@ struct CatalogWorkspace {
     }
 };
 
-// What the two step entries check alike.  `fn`, the entry's name, opens every message; `list` names its row list.
+// The workspace of a step over lists: the list step's arrays, then the anchors' target sums [B] and flag rows [B].
+struct ListsWorkspace {
+    StepWorkspace step;
+    size_t t_sum, flag, total;
+    ListsWorkspace(int dim, int B) : step(dim, B) {
+        const size_t col = align256((size_t)B * sizeof(float));
+        t_sum = step.total;
+        flag = t_sum + col;
+        total = flag + col;
+    }
+};
+
+// What the step entries check alike.  `fn`, the entry's name, opens every message; `list` names its row list.
 int check_step(const char* fn, const char* list, const Index* ix, const Adapter* ad, const float* anchors_dev,
                const int32_t* rows_dev, const float* loss_out_dev, const void* workspace_dev, int32_t B, const Hyper& hp) {
     ICREC_REQUIRE(ix != nullptr, "%s: NULL idx", fn);
@@ -1006,6 +1244,47 @@ int icrec_adapter_step_catalog(icrec_index* idx, icrec_adapter* h, const float* 
                        (int)B, d, (const float*)a.U, (const float*)a.nrm, (const float*)ml, (const float*)s_pos, pos_rows_dev,
                        n_rows, scale, a.dZ, a.loss_i);
     return launch_grad(ad, hp, anchors_dev, B, pos_rows_dev, n_rows, a, loss_out_dev, grad_out_dev, st);
+}
+
+size_t icrec_adapter_step_lists_workspace_bytes(const icrec_adapter* h, int32_t B) {
+    const Adapter* ad = reinterpret_cast<const Adapter*>(h);
+    if (ad == nullptr || B < 1 || B > ICREC_ADAPTER_MAX_BATCH) return 0;
+    return ListsWorkspace(ad->dim, B).total;
+}
+
+int icrec_adapter_step_lists(icrec_index* idx, icrec_adapter* h, const float* anchors_dev, int32_t B,
+                             const int32_t* list_off_dev, const int32_t* list_rows_dev, const float* list_target_dev,
+                             int32_t max_len, float scale, float lr, float beta1, float beta2, float eps, float weight_decay,
+                             int32_t update, float* loss_out_dev, float* grad_out_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream) {
+    const Index* ix = reinterpret_cast<const Index*>(idx);
+    Adapter* ad = reinterpret_cast<Adapter*>(h);
+    const Hyper hp{scale, lr, beta1, beta2, eps, weight_decay, update != 0};
+    const int rc = check_step("icrec_adapter_step_lists", "list_off", ix, ad, anchors_dev, list_off_dev, loss_out_dev,
+                              workspace_dev, B, hp);
+    if (rc != ICREC_OK) return rc;
+    ICREC_REQUIRE(list_rows_dev != nullptr && list_target_dev != nullptr, "icrec_adapter_step_lists: NULL list_rows or list_target");
+    ICREC_REQUIRE(max_len >= 1 && max_len <= ICREC_ADAPTER_MAX_LIST, "icrec_adapter_step_lists: max_len must be in [1, %d] (got %d)",
+                  ICREC_ADAPTER_MAX_LIST, max_len);
+    const int64_t n_rows = ix->n_rows;  // the rows of this call: both kernels check against this one value
+    const ListsWorkspace ws(ad->dim, B);
+    ICREC_REQUIRE(workspace_bytes >= ws.total, "icrec_adapter_step_lists: the workspace has %zu bytes, %zu are needed",
+                  workspace_bytes, ws.total);
+    ICREC_HIP(hipSetDevice(ad->device));
+    hipStream_t st = (hipStream_t)stream;
+    char* base = static_cast<char*>(workspace_dev);
+    const StepArrays a(base, ws.step);
+    float* t_sum = reinterpret_cast<float*>(base + ws.t_sum);
+    int32_t* flag = reinterpret_cast<int32_t*>(base + ws.flag);
+    launch_forward(ad, anchors_dev, B, a, st);
+    hipLaunchKernelGGL(lists_plan_kernel, dim3((unsigned)((B + LISTS_WAVES - 1) / LISTS_WAVES)), dim3(LISTS_THREADS), 0, st,
+                       list_off_dev, list_rows_dev, list_target_dev, (int)B, (int)max_len, n_rows, t_sum, flag);
+    hipLaunchKernelGGL((rows_are_bf16(ix) ? lists_kernel<true> : lists_kernel<false>), dim3((unsigned)B), dim3(LISTS_THREADS), 0,
+                       st, (const void*)ix->rows, ad->dim, n_rows, (const float*)a.U, (const float*)a.nrm, list_off_dev,
+                       list_rows_dev, list_target_dev, (int)max_len, (const float*)t_sum, (const int32_t*)flag, (int)B, scale,
+                       a.dZ, a.loss_i);
+    // the flag rows stand in for the positives: row 0 is in range for a counted anchor, -1 is not
+    return launch_grad(ad, hp, anchors_dev, B, flag, n_rows, a, loss_out_dev, grad_out_dev, st);
 }
 
 

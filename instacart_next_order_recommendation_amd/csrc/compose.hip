@@ -14,16 +14,6 @@ constexpr int COMPOSE_THREADS = 256;  // 4 waves; a thread owns one 16-byte piec
 constexpr int COMPOSE_DEPTH = 8;      // stored rows whose loads a thread issues before the first add
 static_assert(ICREC_MAX_TERMS * (sizeof(int32_t) + sizeof(float)) <= 16384, "a query's terms are staged in LDS");
 
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-
-// Feature j (0 .. P-1) of the 16 bytes a thread loaded from a stored row: a float, or bf16 bits widened exactly (word w
-// holds feature 2w in its low half and 2w + 1 in its high half).
-template <bool P16>
-__device__ __forceinline__ float piece_value(const u32x4& x, int j) {
-    if (P16) return (j & 1) ? bf16_hi(x[j >> 1]) : bf16_lo(x[j >> 1]);
-    return __uint_as_float(x[j]);
-}
-
 // One workgroup per query.  The per-feature chains acc[j] = acc[j] + (w * p[j]) are independent of each other and
 // ordered along the terms, so the parallelism is the features (16 bytes of every stored row per thread: 4 fp32 or 8
 // bf16 values; at dim 32 most threads own nothing, at 4,096 a thread walks several pieces) and the loads in flight: a

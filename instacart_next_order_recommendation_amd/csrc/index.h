@@ -54,6 +54,17 @@ using row_elem_t = std::conditional_t<P16, uint16_t, float>;
 
 #ifdef __HIPCC__
 
+// ---------------------------------------------------------------- a stored row by 16-byte pieces (compose.hip, adapt.hip)
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+
+// Feature j (0 .. P-1) of the 16 bytes a thread loaded from a stored row: a float, or bf16 bits widened exactly (word w
+// holds feature 2w in its low half and 2w + 1 in its high half).
+template <bool P16>
+__device__ __forceinline__ float piece_value(const u32x4& x, int j) {
+    if (P16) return (j & 1) ? bf16_hi(x[j >> 1]) : bf16_lo(x[j >> 1]);
+    return __uint_as_float(x[j]);
+}
+
 // ---------------------------------------------------------------- row normalisation
 // out = x / max(|x|_2, eps) — torch.nn.functional.normalize(p=2, dim=1) as cos_sim applies it.
 // One wavefront per row; reduction order = 64 strided fmaf partials + xor butterfly, identical

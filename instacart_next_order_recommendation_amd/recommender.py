@@ -17,6 +17,7 @@ from __future__ import annotations
 import hashlib
 import json
 import logging
+import math
 import os
 import time
 from dataclasses import dataclass, replace
@@ -552,6 +553,55 @@ def adapter_pairs_plan(pairs, pid_to_row, epochs, batch_size, negatives, lr, wei
     return texts, rows
 
 
+#: the gain of each event a deployed recommender records per shown product (the reference's four event types)
+DEFAULT_GAINS = {"impression": 0, "click": 1, "add_to_cart": 2, "purchase": 4}
+
+
+def adapter_lists_plan(impressions, pid_to_row, gains, epochs, batch_size, lr, weight_decay, scale, where=None):
+    """Recommender.fit_adapter_lists' arguments, checked before any GPU work: impressions is a sequence of (context text,
+    {product id: event name or number}) -> (the texts, per context its list [(catalog row, gain)]).  An event name is
+    looked up in `gains`, a number is the gain itself.  `where`: what names impression i in a message (a file's
+    "FILE:line"), else its position.  ValueError: a string or a mapping for impressions, an entry that is not a (text,
+    mapping) pair, a context that is not a string, a product id the catalog does not have, an event `gains` does not
+    have, a gain that is negative or not finite (in `gains` too), more than ICREC_ADAPTER_MAX_LIST products in one
+    list, a list without a positive gain (it teaches nothing), and fit_plan's."""
+    if isinstance(impressions, (str, bytes)) or hasattr(impressions, "items"):
+        raise ValueError("impressions must be a sequence of (context text, {product id: event or gain})")
+
+    def gain_of(v, what):
+        if isinstance(v, str):
+            if v not in gains:
+                raise ValueError(f"unknown event {v!r} {what} (known: {', '.join(sorted(gains))})")
+            v = gains[v]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"a gain must be a finite number >= 0, got {v!r} {what}")
+        return float(v)
+
+    for event in gains:
+        gain_of(gains[event], f"for event {event!r}")
+    texts, lists = [], []
+    for i, entry in enumerate(impressions):
+        at = where[i] if where is not None else f"impression {i}"
+        if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__") or len(entry) != 2 or not hasattr(entry[1], "items"):
+            raise ValueError(f"{at} is not a (context text, {{product id: event or gain}}) pair: {entry!r}")
+        text, products = entry
+        if not isinstance(text, str):
+            raise ValueError(f"{at}: the context must be a string, got {type(text).__name__}")
+        if len(products) > _native.ICREC_ADAPTER_MAX_LIST:
+            raise ValueError(f"{at} lists {len(products)} products, the limit is {_native.ICREC_ADAPTER_MAX_LIST}")
+        entries = []
+        for pid, v in products.items():
+            if pid not in pid_to_row:
+                raise ValueError(f"unknown product id {pid!r} in {at}: an adapter is trained against the catalog's stored rows")
+            entries.append((int(pid_to_row[pid]), gain_of(v, f"for product {pid!r} in {at}")))
+        if not any(g > 0 for _, g in entries):
+            raise ValueError(f"{at} has no product with a positive gain: it teaches nothing")
+        texts.append(text)
+        lists.append(entries)
+    fit_plan(len(texts), epochs, batch_size, 0, lr, weight_decay, scale)
+    return texts, lists
+
+
 @dataclass(frozen=True)
 class RequestPlan:
     """What a request asks beyond (queries, top_k, exclusions), checked (Recommender._plan); None / False: not asked."""
@@ -754,12 +804,30 @@ class Recommender:
         while a request is being served."""
         texts, rows = adapter_pairs_plan(pairs, self._pid_to_row, epochs, batch_size, negatives, lr, weight_decay, scale)
         anchors = self.model.encode_to_device(texts)
+        return self._train_adapter(lambda adapter: adapter.fit(self._index, anchors, rows, epochs, batch_size, negatives, lr,
+                                                               weight_decay, scale, seed))
+
+    def _train_adapter(self, train) -> list[float]:
+        """train(adapter) -> losses, on the installed adapter in place, or on a new one that is then installed."""
         adapter = self._adapter if self._adapter is not None else QueryAdapter(self._index.dim, self.device)
-        losses = adapter.fit(self._index, anchors, rows, epochs, batch_size, negatives, lr, weight_decay, scale, seed)
+        losses = train(adapter)
         torch.cuda.current_stream(self.device).synchronize()  # the graphs replay on a stream of their own
         if adapter is not self._adapter:
             self.set_adapter(adapter)
         return losses
+
+    def fit_adapter_lists(self, impressions, gains=DEFAULT_GAINS, epochs: int = 5, batch_size: int = 64, lr: float = 2e-3,
+                          weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0, where=None) -> list[float]:
+        """Learn the query adapter from impression lists - per context the products that were shown and what happened
+        to each: (context text, {product id: event name or gain}) - with the listwise softmax cross-entropy
+        (QueryAdapter.fit_lists) -> the per-step losses.  An event's gain comes from `gains` (the reference's four event
+        types); a context's negatives are its own shown-but-ignored products, nothing is drawn.  The contexts are
+        encoded once, no product is encoded, and the installed adapter is trained in place, as fit_adapter does.
+        ValueError before any GPU work: adapter_lists_plan's.  A set-up call: never while a request is being served."""
+        texts, lists = adapter_lists_plan(impressions, self._pid_to_row, gains, epochs, batch_size, lr, weight_decay, scale, where)
+        anchors = self.model.encode_to_device(texts)
+        return self._train_adapter(lambda adapter: adapter.fit_lists(self._index, anchors, lists, epochs, batch_size, lr,
+                                                                     weight_decay, scale, seed))
 
     def _member_row(self, product_ids) -> np.ndarray:
         """bool [n_products]: which catalog rows the given product ids name; ids the catalog does not have are skipped."""

@@ -20,6 +20,7 @@ import torch
 
 from . import _native
 from ._native import ptr, stream_ptr
+from .adapter import DEFAULT_SCALE, fit_plan
 from .encoder import DeviceEncoder
 from .model_io import assemble_pairs, load_cross_encoder_dir, strip_specials
 
@@ -53,11 +54,14 @@ class CrossEncoderReranker:
         score_packed call, then the model's activation (sigmoid in float32, or the raw logit)."""
         if len(a_ids) == 0:
             return np.zeros(0, np.float32)
+        return self.activate(self.logit_ids(a_ids, b_ids).cpu().numpy())
+
+    def logit_ids(self, a_ids: Sequence[np.ndarray], b_ids: Sequence[np.ndarray]) -> torch.Tensor:
+        """score_ids' raw logits, float32 [n >= 1] on the device."""
         ids, cu, seg_b = assemble_pairs(a_ids, b_ids, self.max_seq_length, self.cls_id, self.sep_id)
         dev = self.encoder.device
-        logits = self.encoder.score_packed(torch.from_numpy(ids).to(dev), torch.from_numpy(cu).to(dev),
-                                           torch.from_numpy(seg_b).to(dev), int(np.diff(cu).max())).cpu().numpy()
-        return self.activate(logits)
+        return self.encoder.score_packed(torch.from_numpy(ids).to(dev), torch.from_numpy(cu).to(dev),
+                                         torch.from_numpy(seg_b).to(dev), int(np.diff(cu).max()))
 
     def activate(self, logits: np.ndarray) -> np.ndarray:
         """The model's activation on raw float32 logits: sigmoid in float32, or the logit itself."""
@@ -339,6 +343,53 @@ class RerankedRecommender:
             return self._results(*c.run(ids, q_side, rows))
         idx, logit = self._rerank_batch(ids, cu, [q_side], k, top, ex)
         return self._results(idx[0], logit[0])
+
+    def distill_adapter(self, contexts: Sequence[str], candidates: Optional[int] = None, temperature: float = 1.0,
+                        **fit) -> list[float]:
+        """Teach the first stage's query adapter what the cross-encoder prefers, without labels: every context's
+        `candidates` products (default: self.candidates) are retrieved with the CURRENT first stage, the cross-encoder
+        gives each its raw logit, the targets are softmax(logits / temperature) over a context's candidates (torch, on
+        the device), and the recommender's adapter is trained on these lists (QueryAdapter.fit_lists; `fit`: its epochs,
+        batch_size, lr, weight_decay, scale, seed) - installed if there was none, in place otherwise -> the per-step
+        losses.  The logits come from the host-assembled path, in chunks of RERANK_TOKENS_PER_CALL tokens: a set-up
+        call, never while a request is being served.  ValueError before any GPU work: no context, one that is not a
+        string, candidates outside [1, ICREC_ADAPTER_MAX_LIST], a temperature that is not finite and > 0, fit_plan's."""
+        rec = self.recommender
+        contexts = list(contexts) if not isinstance(contexts, (str, bytes)) else None
+        if not contexts or not all(isinstance(c, str) for c in contexts):
+            raise ValueError("contexts must be a non-empty sequence of strings")
+        k = self.candidates if candidates is None else candidates
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _native.ICREC_ADAPTER_MAX_LIST:
+            raise ValueError(f"candidates must be an integer in [1, {_native.ICREC_ADAPTER_MAX_LIST}], got {k!r}")
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.integer, np.floating)) or not 0 < temperature < float("inf"):
+            raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+        unknown = set(fit) - {"epochs", "batch_size", "lr", "weight_decay", "scale", "seed"}
+        if unknown:
+            raise ValueError(f"distill_adapter takes fit_lists' arguments, not {sorted(unknown)}")
+        fit_plan(len(contexts), fit.get("epochs", 5), fit.get("batch_size", 64), 0, fit.get("lr", 2e-3),
+                 fit.get("weight_decay", 0.01), fit.get("scale", DEFAULT_SCALE))
+        k = int(k)
+        found = rec.recommend_batch(contexts, k)
+        q_sides = self.reranker.side_ids(contexts)
+        dev = rec.device
+        rows = torch.full((len(contexts), k), -1, dtype=torch.int32)
+        logits = torch.full((len(contexts), k), float("-inf"), dtype=torch.float32, device=dev)
+        for lo, hi in self._chunks([len(q) for q in q_sides], k):
+            a = [q_sides[i] for i in range(lo, hi) for _ in found[i]]
+            if not a:
+                continue
+            scores = self.reranker.logit_ids(a, [self._product_side[pid] for i in range(lo, hi) for pid, _ in found[i]])
+            at = 0
+            for i in range(lo, hi):
+                n = len(found[i])
+                rows[i, :n] = torch.tensor([rec._pid_to_row[pid] for pid, _ in found[i]], dtype=torch.int32)
+                logits[i, :n] = scores[at:at + n]
+                at += n
+        target = torch.nan_to_num(torch.softmax(logits / float(temperature), dim=1), nan=0.0)  # (nothing found: no target)
+        lists = (torch.arange(len(contexts) + 1, dtype=torch.int32, device=dev) * k, rows.to(dev).reshape(-1),
+                 target.reshape(-1), k)
+        anchors = rec.model.encode_to_device(contexts)
+        return rec._train_adapter(lambda adapter: adapter.fit_lists(rec._index, anchors, lists, **fit))
 
     def recommend_batch(self, queries: Sequence[str], top_k: int = 10,
                         exclude_product_ids: Optional[Sequence[Optional[set[str]]]] = None
