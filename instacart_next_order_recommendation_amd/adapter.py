@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from pathlib import Path
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -100,6 +100,15 @@ def impression_csr(lists, B: int, device: str | torch.device = "cpu"):
             torch.tensor(target, dtype=torch.float32, device=device), max_len)
 
 
+class _Batch(NamedTuple):
+    """A step's anchors and targets, checked against each other by one of QueryAdapter's three builders: the C entry that
+    takes them, its arguments between B and scale (a tensor goes as its pointer, kept alive here), its workspace's bytes."""
+    name: str
+    anchors: torch.Tensor
+    args: tuple
+    workspace: int
+
+
 class QueryAdapter:
     """An icrec_adapter: D (fp32, dim x dim, zero when created), AdamW's moments and the step count, on one HIP device.
     The arrays never move, so a captured graph that holds apply_into stays valid while the adapter trains."""
@@ -159,40 +168,133 @@ class QueryAdapter:
             raise ValueError(f"{what} must be a list of rows, got shape {tuple(rows.shape)}")
         return rows
 
-    def _step(self, catalog: bool, index, anchors, rows, scale, lr=0.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-              update: bool = False, grad_out=None, loss_out=None, want_grad: bool = False, lists=None):
-        """One call of icrec_adapter_step (rows: the candidate list), with `catalog` of icrec_adapter_step_catalog
-        (rows: a positive per anchor) or, with `lists` (_csr's four values; rows is None), of icrec_adapter_step_lists
-        -> (loss float32 [], grad_out).  Without `update` the adapter is not changed; want_grad: a new grad_out."""
-        anchors = self._rows(anchors, "anchors")
-        B = int(anchors.shape[0])
-        L = _native.lib()
-        if lists is not None:
-            off, list_rows, target, max_len = lists
-            if int(off.shape[0]) != B + 1:
-                raise ValueError(f"{B} anchors for {int(off.shape[0]) - 1} lists")
-            name, what = "icrec_adapter_step_lists", (_native.ptr(off), _native.ptr(list_rows), _native.ptr(target), int(max_len))
-            need = L.icrec_adapter_step_lists_workspace_bytes(self._h, B)
-        else:
-            rows = self._row_list(rows, "positive_rows" if catalog else "cand_rows")
-            n = int(rows.shape[0])
-            if catalog:
-                if n != B:
-                    raise ValueError(f"{B} anchors for {n} positives")
-                name, what = "icrec_adapter_step_catalog", (_native.ptr(rows),)  # no list: its C is the index's row count
-                need = L.icrec_adapter_step_catalog_workspace_bytes(self._h, index._h, B)
-            else:
-                name, what = "icrec_adapter_step", (_native.ptr(rows), n)
-                need = L.icrec_adapter_step_workspace_bytes(self._h, B, n)
-        ws = self._scratch.block(max(int(need), 256))
+    def _pairs(self, anchors, cand_rows) -> _Batch:  # a candidate list, candidate i anchor i's positive
+        anchors, rows = self._rows(anchors, "anchors"), self._row_list(cand_rows, "cand_rows")
+        B, n = int(anchors.shape[0]), int(rows.shape[0])
+        return _Batch("icrec_adapter_step", anchors, (rows, n), _native.lib().icrec_adapter_step_workspace_bytes(self._h, B, n))
+
+    def _labels(self, index, anchors, positive_rows) -> _Batch:  # a positive per anchor; its C is the index's row count
+        anchors, rows = self._rows(anchors, "anchors"), self._row_list(positive_rows, "positive_rows")
+        if rows.shape[0] != anchors.shape[0]:
+            raise ValueError(f"{anchors.shape[0]} anchors for {rows.shape[0]} positives")
+        return _Batch("icrec_adapter_step_catalog", anchors, (rows,),
+                      _native.lib().icrec_adapter_step_catalog_workspace_bytes(self._h, index._h, int(anchors.shape[0])))
+
+    def _lists(self, anchors, csr) -> _Batch:  # _csr's four values
+        anchors, (off, rows, target, max_len) = self._rows(anchors, "anchors"), csr
+        if off.shape[0] != anchors.shape[0] + 1:
+            raise ValueError(f"{anchors.shape[0]} anchors for {off.shape[0] - 1} lists")
+        return _Batch("icrec_adapter_step_lists", anchors, (off, rows, target, int(max_len)),
+                      _native.lib().icrec_adapter_step_lists_workspace_bytes(self._h, int(anchors.shape[0])))
+
+    def _step(self, index, batch: _Batch, scale, lr=0.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              update: bool = False, grad_out=None, loss_out=None, want_grad: bool = False):
+        """One call of the batch's entry -> (loss float32 [], grad_out).  Without `update` the adapter is not changed;
+        want_grad: a new grad_out."""
+        ws = self._scratch.block(max(int(batch.workspace), 256))
         loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=self.device)
         if want_grad:
             grad_out = torch.empty((self.dim, self.dim), dtype=torch.float32, device=self.device)
-        _native.check(getattr(L, name)(index._h, self._h, _native.ptr(anchors), B, *what, float(scale),
-                                       float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                                       1 if update else 0, _native.ptr(loss), _native.ptr(grad_out), _native.ptr(ws),
-                                       ws.numel(), _native.stream_ptr(self.device)), name)
+        middle = (_native.ptr(a) if isinstance(a, torch.Tensor) else a for a in batch.args)
+        _native.check(getattr(_native.lib(), batch.name)(
+            index._h, self._h, _native.ptr(batch.anchors), int(batch.anchors.shape[0]), *middle, float(scale), float(lr),
+            float(betas[0]), float(betas[1]), float(eps), float(weight_decay), 1 if update else 0, _native.ptr(loss),
+            _native.ptr(grad_out), _native.ptr(ws), ws.numel(), _native.stream_ptr(self.device)), batch.name)
         return loss[0], grad_out
+
+    def _held_out_loss(self, index, batch_of, counted: torch.Tensor, scale) -> float:
+        """catalog_loss and lists_loss: batch_of(lo, hi) is the batch of anchors [lo, hi); counted, float64 [n] on the
+        device, is 1 where the step counts the anchor."""
+        scale = self.scale if scale is None else float(scale)
+        n, step = int(counted.shape[0]), _native.ICREC_ADAPTER_MAX_BATCH
+        starts = range(0, n, step)
+        means = torch.zeros(len(starts), dtype=torch.float32, device=self.device)
+        for k, lo in enumerate(starts):
+            self._step(index, batch_of(lo, min(lo + step, n)), scale, loss_out=means[k:k + 1])
+        per_batch = torch.stack([counted[lo:lo + step].sum() for lo in starts])
+        host = torch.stack([means.to(torch.float64), per_batch]).cpu().numpy()  # the one read-back
+        total = float(host[1].sum())
+        return float((host[0] * host[1]).sum() / total) if total > 0 else 0.0
+
+    def _train(self, index, n: int, batch_of, plan, epochs, lr, weight_decay, scale, seed) -> list[float]:
+        """fit's and fit_lists' loop over fit_plan's `plan`; batch_of(at, gen) is the batch of the n examples' subset
+        `at` (device indices) and may draw from gen, the seeded CPU generator, after the epoch's shuffle."""
+        batch, per_epoch, total, warmup = plan
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        losses = torch.zeros(total, dtype=torch.float32, device=self.device)
+        s = 0
+        for _ in range(int(epochs)):
+            perm = torch.randperm(n, generator=gen)
+            for b in range(per_epoch):
+                at = perm[b * batch:(b + 1) * batch].to(self.device)
+                self._step(index, batch_of(at, gen), scale, float(lr) * schedule(s, total, warmup),
+                           weight_decay=weight_decay, update=True, loss_out=losses[s:s + 1])
+                s += 1
+        self.scale = float(scale)
+        return losses.cpu().tolist()
+
+    # -- pairs and the whole catalog -----------------------------------------------------------------
+    def loss_and_grad(self, index, anchors, cand_rows, scale: float = DEFAULT_SCALE):
+        """(loss float32 [], dD float32 [dim, dim]) on the device, of the anchors [B, dim] against index's stored rows
+        cand_rows [C >= B] (candidate i is anchor i's positive); the adapter is not changed."""
+        return self._step(index, self._pairs(anchors, cand_rows), scale, want_grad=True)
+
+    def step(self, index, anchors, cand_rows, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
+             scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None):
+        """One AdamW step (torch.optim.AdamW's formula) on the batch's gradient -> the batch's loss before the step, a
+        float32 [] device tensor (loss_out: a float32 [1] device tensor to write it to).  No host synchronisation."""
+        return self._step(index, self._pairs(anchors, cand_rows), scale, lr, betas, eps, weight_decay, True, grad_out, loss_out)[0]
+
+    def loss_and_grad_catalog(self, index, anchors, positive_rows, scale: float = DEFAULT_SCALE):
+        """loss_and_grad against the WHOLE catalog: the cross-entropy of anchors [B, dim] over every stored row of index,
+        positive_rows [B] the labels (an anchor whose row is outside the index is not counted); no candidate list, no
+        sampling.  The adapter is not changed."""
+        return self._step(index, self._labels(index, anchors, positive_rows), scale, want_grad=True)
+
+    def step_catalog(self, index, anchors, positive_rows, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                     weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None,
+                     loss_out: Optional[torch.Tensor] = None):
+        """step against the whole catalog (loss_and_grad_catalog's loss): one AdamW step -> the batch's loss before the
+        step, a float32 [] device tensor.  No host synchronisation."""
+        return self._step(index, self._labels(index, anchors, positive_rows), scale, lr, betas, eps, weight_decay, True,
+                          grad_out, loss_out)[0]
+
+    def catalog_loss(self, index, anchors, positive_rows, scale: Optional[float] = None) -> float:
+        """The exact loss of a held-out set: the mean over its counted pairs of the cross-entropy against every stored
+        row.  Batches of at most ICREC_ADAPTER_MAX_BATCH; the batch means are combined, weighted by their counted
+        anchors, in double on the host, which is read back once.  scale=None: the adapter's own scale."""
+        _, anchors, (pos,), _ = self._labels(index, anchors, positive_rows)  # the whole set, checked as a batch is
+        in_range = ((pos >= 0) & (pos < int(index.n_rows))).to(torch.float64)
+        return self._held_out_loss(index, lambda lo, hi: self._labels(index, anchors[lo:hi], pos[lo:hi]), in_range, scale)
+
+    def fit(self, index, anchor_embeddings, positive_rows, epochs: int = 5, batch_size: int = 64, negatives=0,
+            lr: float = 2e-3, weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0) -> list[float]:
+        """Train on pairs (anchor_embeddings[i], the stored row positive_rows[i]) -> the per-step losses.  Each epoch
+        walks a fresh shuffle in batches of batch_size with in-batch negatives plus `negatives` rows drawn from the
+        whole index; the shuffles and draws come from a CPU torch.Generator seeded with `seed`, so a run is
+        reproducible.  negatives="all": every step is a step_catalog - the exact cross-entropy against every stored
+        row, nothing drawn beside the shuffles.  As the reference trains: warm-up over the first 10 % of the steps, then
+        a cosine schedule; drop_last (unless there is less than one batch); scale 30.  One read-back, at the end."""
+        rows = torch.as_tensor(np.asarray(positive_rows, np.int64))
+        if rows.ndim != 1:
+            raise ValueError("positive_rows must be a list of rows")
+        plan = fit_plan(int(rows.shape[0]), epochs, batch_size, negatives, lr, weight_decay, scale)
+        anchors = self._rows(anchor_embeddings, "anchor_embeddings")
+        if anchors.shape[0] != rows.shape[0]:
+            raise ValueError(f"{anchors.shape[0]} anchors for {rows.shape[0]} positives")
+        exact = isinstance(negatives, str)  # fit_plan admitted "all" only
+        rows_dev = rows.to(self.device, torch.int32)
+
+        def batch_of(at, gen):
+            cand = rows_dev[at]  # the batch's positives: a catalog step's labels, the head of a list step's candidates
+            if exact:
+                return self._labels(index, anchors[at], cand)
+            if negatives:
+                extra = torch.randint(0, index.n_rows, (int(negatives),), generator=gen, dtype=torch.int64)
+                cand = torch.cat([cand, extra.to(self.device, torch.int32)])
+            return self._pairs(anchors[at], cand)
+
+        return self._train(index, int(rows.shape[0]), batch_of, plan, epochs, lr, weight_decay, scale, seed)
 
     # -- per-anchor lists ----------------------------------------------------------------------------
     def _csr(self, lists, B: int):
@@ -216,17 +318,15 @@ class QueryAdapter:
         """(loss float32 [], dD float32 [dim, dim]) of the listwise softmax cross-entropy (include/icrec.h,
         icrec_adapter_step_lists): anchor i against its own list of (stored row of index, gain >= 0) - per anchor a
         mapping or a sequence of pairs, or impression_csr's tuple.  The adapter is not changed."""
-        lists = self._csr(lists, int(np.shape(anchors)[0]))
-        return self._step(False, index, anchors, None, scale, want_grad=True, lists=lists)
+        return self._step(index, self._lists(anchors, self._csr(lists, int(np.shape(anchors)[0]))), scale, want_grad=True)
 
     def step_lists(self, index, anchors, lists, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
                    scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None,
                    loss_out: Optional[torch.Tensor] = None):
         """step on loss_and_grad_lists' loss: one AdamW step -> the batch's loss before the step, a float32 [] device
         tensor.  No host synchronisation when `lists` is impression_csr's tuple on this device."""
-        lists = self._csr(lists, int(np.shape(anchors)[0]))
-        return self._step(False, index, anchors, None, scale, lr, betas, eps, weight_decay, True, grad_out, loss_out,
-                          lists=lists)[0]
+        batch = self._lists(anchors, self._csr(lists, int(np.shape(anchors)[0])))
+        return self._step(index, batch, scale, lr, betas, eps, weight_decay, True, grad_out, loss_out)[0]
 
     @staticmethod
     def _padded(csr, n_rows: int):
@@ -244,135 +344,33 @@ class QueryAdapter:
         T = torch.where(live, t, torch.zeros_like(t)).sum(dim=1)
         return r, t, torch.isfinite(T) & (T > 0)
 
+    def _all_lists(self, anchors, what: str, lists):  # a whole set, checked as a batch is: _rows' anchors, _csr's lists
+        anchors = self._rows(anchors, what)
+        return anchors, self._lists(anchors, self._csr(lists, int(anchors.shape[0]))).args
+
     def lists_loss(self, index, anchors, lists, scale: Optional[float] = None) -> float:
         """The listwise loss of a held-out set: the mean over its counted anchors.  Batches of at most
         ICREC_ADAPTER_MAX_BATCH; the batch means are combined, weighted by their counted anchors, in double on the
         host, which is read back once.  scale=None: the adapter's own scale."""
-        anchors = self._rows(anchors, "anchors")
-        n = int(anchors.shape[0])
-        off, rows, target, max_len = self._csr(lists, n)
-        if int(off.shape[0]) != n + 1:
-            raise ValueError(f"{n} anchors for {int(off.shape[0]) - 1} lists")
-        scale = self.scale if scale is None else float(scale)
-        step = _native.ICREC_ADAPTER_MAX_BATCH
-        starts = range(0, n, step)
-        means = torch.zeros(len(starts), dtype=torch.float32, device=self.device)
-        for k, lo in enumerate(starts):
-            self._step(False, index, anchors[lo:lo + step], None, scale, loss_out=means[k:k + 1],
-                       lists=(off[lo:lo + step + 1].contiguous(), rows, target, max_len))
-        is_counted = self._padded((off, rows, target, max_len), index.n_rows)[2].to(torch.float64)
-        counted = torch.stack([is_counted[lo:lo + step].sum() for lo in starts])
-        host = torch.stack([means.to(torch.float64), counted]).cpu().numpy()  # the one read-back
-        total = float(host[1].sum())
-        return float((host[0] * host[1]).sum() / total) if total > 0 else 0.0
+        anchors, csr = self._all_lists(anchors, "anchors", lists)
+        off, rows, target, max_len = csr
+        return self._held_out_loss(
+            index, lambda lo, hi: self._lists(anchors[lo:hi], (off[lo:hi + 1].contiguous(), rows, target, max_len)),
+            self._padded(csr, index.n_rows)[2].to(torch.float64), scale)
 
     def fit_lists(self, index, anchor_embeddings, lists, epochs: int = 5, batch_size: int = 64, lr: float = 2e-3,
                   weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0) -> list[float]:
         """Train on (anchor_embeddings[i], lists[i]) with step_lists -> the per-step losses.  fit's shuffles (a CPU
         torch.Generator seeded with `seed`), warm-up, cosine schedule, drop_last and single read-back; nothing is drawn
         beside the shuffles: an anchor's negatives are the entries of its own list."""
-        anchors = self._rows(anchor_embeddings, "anchor_embeddings")
-        n = int(anchors.shape[0])
-        csr = self._csr(lists, n)
-        if int(csr[0].shape[0]) != n + 1:
-            raise ValueError(f"{n} anchors for {int(csr[0].shape[0]) - 1} lists")
-        batch, per_epoch, total, warmup = fit_plan(n, epochs, batch_size, 0, lr, weight_decay, scale)
+        anchors, csr = self._all_lists(anchor_embeddings, "anchor_embeddings", lists)
+        plan = fit_plan(int(anchors.shape[0]), epochs, batch_size, 0, lr, weight_decay, scale)
         max_len = csr[3]
         rows_pad, target_pad, _ = self._padded(csr, index.n_rows)  # a batch is a gather of whole padded lists
-        off = torch.arange(batch + 1, dtype=torch.int32, device=self.device) * max_len
-        gen = torch.Generator(device="cpu").manual_seed(int(seed))
-        losses = torch.zeros(total, dtype=torch.float32, device=self.device)
-        s = 0
-        for _ in range(int(epochs)):
-            perm = torch.randperm(n, generator=gen)
-            for b in range(per_epoch):
-                at = perm[b * batch:(b + 1) * batch].to(self.device)
-                self._step(False, index, anchors[at], None, scale, float(lr) * schedule(s, total, warmup),
-                           weight_decay=weight_decay, update=True, loss_out=losses[s:s + 1],
-                           lists=(off, rows_pad[at].reshape(-1), target_pad[at].reshape(-1), max_len))
-                s += 1
-        self.scale = float(scale)
-        return losses.cpu().tolist()
-
-    def loss_and_grad(self, index, anchors, cand_rows, scale: float = DEFAULT_SCALE):
-        """(loss float32 [], dD float32 [dim, dim]) on the device, of the anchors [B, dim] against index's stored rows
-        cand_rows [C >= B] (candidate i is anchor i's positive); the adapter is not changed."""
-        return self._step(False, index, anchors, cand_rows, scale, want_grad=True)
-
-    def step(self, index, anchors, cand_rows, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
-             scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None):
-        """One AdamW step (torch.optim.AdamW's formula) on the batch's gradient -> the batch's loss before the step, a
-        float32 [] device tensor (loss_out: a float32 [1] device tensor to write it to).  No host synchronisation."""
-        return self._step(False, index, anchors, cand_rows, scale, lr, betas, eps, weight_decay, True, grad_out, loss_out)[0]
-
-    def loss_and_grad_catalog(self, index, anchors, positive_rows, scale: float = DEFAULT_SCALE):
-        """loss_and_grad against the WHOLE catalog: the cross-entropy of anchors [B, dim] over every stored row of index,
-        positive_rows [B] the labels (an anchor whose row is outside the index is not counted); no candidate list, no
-        sampling.  The adapter is not changed."""
-        return self._step(True, index, anchors, positive_rows, scale, want_grad=True)
-
-    def step_catalog(self, index, anchors, positive_rows, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                     weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, grad_out: Optional[torch.Tensor] = None,
-                     loss_out: Optional[torch.Tensor] = None):
-        """step against the whole catalog (loss_and_grad_catalog's loss): one AdamW step -> the batch's loss before the
-        step, a float32 [] device tensor.  No host synchronisation."""
-        return self._step(True, index, anchors, positive_rows, scale, lr, betas, eps, weight_decay, True, grad_out, loss_out)[0]
-
-    def catalog_loss(self, index, anchors, positive_rows, scale: Optional[float] = None) -> float:
-        """The exact loss of a held-out set: the mean over its counted pairs of the cross-entropy against every stored
-        row.  Batches of at most ICREC_ADAPTER_MAX_BATCH; the batch means are combined, weighted by their counted
-        anchors, in double on the host, which is read back once.  scale=None: the adapter's own scale."""
-        anchors = self._rows(anchors, "anchors")
-        pos = self._row_list(positive_rows, "positive_rows")
-        n = int(anchors.shape[0])
-        if int(pos.shape[0]) != n:
-            raise ValueError(f"{n} anchors for {int(pos.shape[0])} positives")
-        scale = self.scale if scale is None else float(scale)
-        step = _native.ICREC_ADAPTER_MAX_BATCH
-        starts = range(0, n, step)
-        means = torch.zeros(len(starts), dtype=torch.float32, device=self.device)
-        for k, lo in enumerate(starts):
-            self._step(True, index, anchors[lo:lo + step], pos[lo:lo + step], scale, loss_out=means[k:k + 1])
-        in_range = ((pos >= 0) & (pos < int(index.n_rows))).to(torch.float64)
-        counted = torch.stack([in_range[lo:lo + step].sum() for lo in starts])
-        host = torch.stack([means.to(torch.float64), counted]).cpu().numpy()  # the one read-back
-        total = float(host[1].sum())
-        return float((host[0] * host[1]).sum() / total) if total > 0 else 0.0
-
-    def fit(self, index, anchor_embeddings, positive_rows, epochs: int = 5, batch_size: int = 64, negatives=0,
-            lr: float = 2e-3, weight_decay: float = 0.01, scale: float = DEFAULT_SCALE, seed: int = 0) -> list[float]:
-        """Train on pairs (anchor_embeddings[i], the stored row positive_rows[i]) -> the per-step losses.  Each epoch
-        walks a fresh shuffle in batches of batch_size with in-batch negatives plus `negatives` rows drawn from the
-        whole index; the shuffles and draws come from a CPU torch.Generator seeded with `seed`, so a run is
-        reproducible.  negatives="all": every step is a step_catalog - the exact cross-entropy against every stored
-        row, nothing drawn beside the shuffles.  As the reference trains: warm-up over the first 10 % of the steps,
-        then a cosine schedule;
-        drop_last (unless there is less than one batch); scale 30.  The host is read back once, at the end."""
-        rows = torch.as_tensor(np.asarray(positive_rows, np.int64))
-        if rows.ndim != 1:
-            raise ValueError("positive_rows must be a list of rows")
-        batch, per_epoch, total, warmup = fit_plan(int(rows.shape[0]), epochs, batch_size, negatives, lr, weight_decay, scale)
-        anchors = self._rows(anchor_embeddings, "anchor_embeddings")
-        if anchors.shape[0] != rows.shape[0]:
-            raise ValueError(f"{anchors.shape[0]} anchors for {rows.shape[0]} positives")
-        gen = torch.Generator(device="cpu").manual_seed(int(seed))
-        exact = isinstance(negatives, str)  # fit_plan admitted "all" only
-        rows_dev = rows.to(self.device, torch.int32)
-        losses = torch.zeros(total, dtype=torch.float32, device=self.device)
-        s = 0
-        for _ in range(int(epochs)):
-            perm = torch.randperm(int(rows.shape[0]), generator=gen)
-            for b in range(per_epoch):
-                at = perm[b * batch:(b + 1) * batch].to(self.device)
-                cand = rows_dev[at]  # the batch's positives: a catalog step's labels, the head of a list step's candidates
-                if not exact and negatives:
-                    extra = torch.randint(0, index.n_rows, (int(negatives),), generator=gen, dtype=torch.int64)
-                    cand = torch.cat([cand, extra.to(self.device, torch.int32)])
-                (self.step_catalog if exact else self.step)(index, anchors[at], cand, float(lr) * schedule(s, total, warmup),
-                                                            weight_decay=weight_decay, scale=scale, loss_out=losses[s:s + 1])
-                s += 1
-        self.scale = float(scale)
-        return losses.cpu().tolist()
+        off = torch.arange(plan[0] + 1, dtype=torch.int32, device=self.device) * max_len
+        return self._train(index, int(anchors.shape[0]), lambda at, gen: self._lists(
+            anchors[at], (off, rows_pad[at].reshape(-1), target_pad[at].reshape(-1), max_len)),
+            plan, epochs, lr, weight_decay, scale, seed)
 
     # -- state ---------------------------------------------------------------------------------------
     @property

@@ -950,7 +950,7 @@ void release(Adapter* ad) {
     delete ad;
 }
 
-// A step's hyper-parameters, as both entries take them.
+// A step's hyper-parameters, as every entry takes them.
 struct Hyper {
     float scale, lr, beta1, beta2, eps, weight_decay;
     bool update;
@@ -971,11 +971,11 @@ AdamW adamw_of(int64_t t, const Hyper& hp) {
     return o;
 }
 
-// The workspace of a step: u [B][dim], dz [B][dim], the norms [B], the losses [B].
+// The workspace of a step: u [B][dim], dz [B][dim], the norms [B], the losses [B].  col: the bytes of a float per anchor.
 struct StepWorkspace {
-    size_t u, dz, nrm, loss, total;
-    StepWorkspace(int dim, int B) {
-        const size_t rows = align256((size_t)B * dim * sizeof(float)), col = align256((size_t)B * sizeof(float));
+    size_t col, u, dz, nrm, loss, total;
+    StepWorkspace(int dim, int B) : col(align256((size_t)B * sizeof(float))) {
+        const size_t rows = align256((size_t)B * dim * sizeof(float));
         u = 0;
         dz = rows;
         nrm = 2 * rows;
@@ -990,9 +990,9 @@ struct CatalogWorkspace {
     StepWorkspace step;
     size_t s_pos, ml, counted, m_part, l_part, part, total;
     CatalogWorkspace(int dim, int B, int n_splits) : step(dim, B) {
-        const size_t col = align256((size_t)B * sizeof(float)), cols = align256((size_t)n_splits * B * sizeof(float));
+        const size_t cols = align256((size_t)n_splits * B * sizeof(float));
         s_pos = step.total;
-        ml = s_pos + col;
+        ml = s_pos + step.col;
         counted = ml + align256(2 * (size_t)B * sizeof(float));
         m_part = counted + 256;
         l_part = m_part + cols;
@@ -1006,60 +1006,78 @@ struct ListsWorkspace {
     StepWorkspace step;
     size_t t_sum, flag, total;
     ListsWorkspace(int dim, int B) : step(dim, B) {
-        const size_t col = align256((size_t)B * sizeof(float));
         t_sum = step.total;
-        flag = t_sum + col;
-        total = flag + col;
+        flag = t_sum + step.col;
+        total = flag + step.col;
     }
 };
 
-// What the step entries check alike.  `fn`, the entry's name, opens every message; `list` names its row list.
-int check_step(const char* fn, const char* list, const Index* ix, const Adapter* ad, const float* anchors_dev,
-               const int32_t* rows_dev, const float* loss_out_dev, const void* workspace_dev, int32_t B, const Hyper& hp) {
-    ICREC_REQUIRE(ix != nullptr, "%s: NULL idx", fn);
-    ICREC_REQUIRE(ad != nullptr, "%s: NULL adapter", fn);
-    ICREC_REQUIRE(anchors_dev != nullptr && rows_dev != nullptr, "%s: NULL anchors or %s", fn, list);
-    ICREC_REQUIRE(loss_out_dev != nullptr, "%s: NULL loss_out", fn);
-    ICREC_REQUIRE(workspace_dev != nullptr, "%s: NULL workspace", fn);
-    ICREC_REQUIRE(ix->dim == ad->dim, "%s: the index has dim %d, the adapter %d", fn, ix->dim, ad->dim);
-    ICREC_REQUIRE(ix->device == ad->device, "%s: the index is on device %d, the adapter on %d", fn, ix->device, ad->device);
-    ICREC_REQUIRE(ix->n_rows >= 1, "%s: the index has no rows", fn);
-    ICREC_REQUIRE(B >= 1 && B <= ICREC_ADAPTER_MAX_BATCH, "%s: B must be in [1, %d] (got %d)", fn, ICREC_ADAPTER_MAX_BATCH, B);
-    ICREC_REQUIRE(isfinite(hp.scale) && isfinite(hp.lr) && isfinite(hp.beta1) && isfinite(hp.beta2) && isfinite(hp.eps) &&
-                      isfinite(hp.weight_decay),
-                  "%s: a hyper-parameter is not finite", fn);
-    ICREC_REQUIRE(!hp.update || (hp.beta1 >= 0.0f && hp.beta1 < 1.0f && hp.beta2 >= 0.0f && hp.beta2 < 1.0f && hp.eps >= 0.0f),
-                  "%s: beta1 and beta2 must be in [0, 1) and eps >= 0", fn);
-    return ICREC_OK;
-}
+// What the three step entries take alike, and what they do alike with it.  An entry reads: check(), its own checks, its
+// workspace's layout, forward(), its own launches from U and nrm to dZ and loss_i, and grad() as its tail.
+struct Step {
+    const char* fn;  // the entry's name: it opens every message
+    const Index* ix;
+    Adapter* ad;
+    const float* anchors_dev;
+    int32_t B;
+    Hyper hp;
+    float *loss_out_dev, *grad_out_dev;
+    char* base;  // the workspace
+    size_t workspace_bytes;
+    hipStream_t st;
+    float *U = nullptr, *dZ = nullptr, *nrm = nullptr, *loss_i = nullptr;  // every workspace begins with them: forward()
 
-// The arrays every step's workspace begins with.
-struct StepArrays {
-    float *U, *dZ, *nrm, *loss_i;
-    StepArrays(char* base, const StepWorkspace& ws)
-        : U(reinterpret_cast<float*>(base + ws.u)), dZ(reinterpret_cast<float*>(base + ws.dz)),
-          nrm(reinterpret_cast<float*>(base + ws.nrm)), loss_i(reinterpret_cast<float*>(base + ws.loss)) {}
+    Step(const char* fn, icrec_index* idx, icrec_adapter* h, const float* anchors_dev, int32_t B, const Hyper& hp,
+         float* loss_out_dev, float* grad_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream)
+        : fn(fn), ix(reinterpret_cast<const Index*>(idx)), ad(reinterpret_cast<Adapter*>(h)), anchors_dev(anchors_dev), B(B),
+          hp(hp), loss_out_dev(loss_out_dev), grad_out_dev(grad_out_dev), base(static_cast<char*>(workspace_dev)),
+          workspace_bytes(workspace_bytes), st((hipStream_t)stream) {}
+
+    template <class T = float>
+    T* at(size_t offset) const { return reinterpret_cast<T*>(base + offset); }
+
+    // What the entries check alike; `list` names the entry's row list, rows_dev.
+    int check(const char* list, const int32_t* rows_dev) const {
+        ICREC_REQUIRE(ix != nullptr, "%s: NULL idx", fn);
+        ICREC_REQUIRE(ad != nullptr, "%s: NULL adapter", fn);
+        ICREC_REQUIRE(anchors_dev != nullptr && rows_dev != nullptr, "%s: NULL anchors or %s", fn, list);
+        ICREC_REQUIRE(loss_out_dev != nullptr, "%s: NULL loss_out", fn);
+        ICREC_REQUIRE(base != nullptr, "%s: NULL workspace", fn);
+        ICREC_REQUIRE(ix->dim == ad->dim, "%s: the index has dim %d, the adapter %d", fn, ix->dim, ad->dim);
+        ICREC_REQUIRE(ix->device == ad->device, "%s: the index is on device %d, the adapter on %d", fn, ix->device, ad->device);
+        ICREC_REQUIRE(ix->n_rows >= 1, "%s: the index has no rows", fn);
+        ICREC_REQUIRE(B >= 1 && B <= ICREC_ADAPTER_MAX_BATCH, "%s: B must be in [1, %d] (got %d)", fn, ICREC_ADAPTER_MAX_BATCH, B);
+        ICREC_REQUIRE(isfinite(hp.scale) && isfinite(hp.lr) && isfinite(hp.beta1) && isfinite(hp.beta2) && isfinite(hp.eps) &&
+                          isfinite(hp.weight_decay),
+                      "%s: a hyper-parameter is not finite", fn);
+        ICREC_REQUIRE(!hp.update || (hp.beta1 >= 0.0f && hp.beta1 < 1.0f && hp.beta2 >= 0.0f && hp.beta2 < 1.0f && hp.eps >= 0.0f),
+                      "%s: beta1 and beta2 must be in [0, 1) and eps >= 0", fn);
+        return ICREC_OK;
+    }
+
+    // A workspace short of the entry's `total` bytes refused; then the step's (a): u and the norms of the anchors.
+    int forward(const StepWorkspace& ws, size_t total) {
+        ICREC_REQUIRE(workspace_bytes >= total, "%s: the workspace has %zu bytes, %zu are needed", fn, workspace_bytes, total);
+        ICREC_HIP(hipSetDevice(ad->device));
+        U = at(ws.u), dZ = at(ws.dz), nrm = at(ws.nrm), loss_i = at(ws.loss);
+        hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((B + FWD_TILE - 1) / FWD_TILE)), dim3(FWD_THREADS), 0, st,
+                           (const float*)ad->delta_t, ad->dim, anchors_dev, (int)B, U, nrm);
+        return ICREC_OK;
+    }
+
+    // The step's (c), from the dZ and the losses its (b) left: dD, AdamW when asked for, the mean loss.  rows_dev[0 .. B)
+    // are the anchors' positives.  It ends the entry: the launches' error, and the step counted.
+    int grad(const int32_t* rows_dev) {
+        const int d = ad->dim;
+        const AdamW o = hp.update ? adamw_of(ad->t, hp) : AdamW{};
+        hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((d / 32) * (d / 32) + 1)), dim3(64), 0, st, (const float*)dZ, anchors_dev,
+                           (int)B, d, rows_dev, ix->n_rows, (const float*)loss_i, loss_out_dev, grad_out_dev, hp.update ? 1 : 0, o,
+                           ad->delta, ad->delta_t, ad->m, ad->v);
+        ICREC_HIP(hipGetLastError());
+        if (hp.update) ad->t += 1;
+        return ICREC_OK;
+    }
 };
-
-// The step's (a): u and the norms of the anchors.
-void launch_forward(const Adapter* ad, const float* anchors_dev, int B, const StepArrays& a, hipStream_t st) {
-    hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((B + FWD_TILE - 1) / FWD_TILE)), dim3(FWD_THREADS), 0, st,
-                       (const float*)ad->delta_t, ad->dim, anchors_dev, B, a.U, a.nrm);
-}
-
-// The step's (c), from the dZ and the losses its (b) left: dD, AdamW when asked for, the mean loss.  rows_dev[0 .. B)
-// are the anchors' positives.  It ends the entry: the launches' error, and the step counted.
-int launch_grad(Adapter* ad, const Hyper& hp, const float* anchors_dev, int B, const int32_t* rows_dev, int64_t n_rows,
-                const StepArrays& a, float* loss_out_dev, float* grad_out_dev, hipStream_t st) {
-    const int d = ad->dim;
-    const AdamW o = hp.update ? adamw_of(ad->t, hp) : AdamW{};
-    hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((d / 32) * (d / 32) + 1)), dim3(64), 0, st, (const float*)a.dZ, anchors_dev,
-                       B, d, rows_dev, n_rows, (const float*)a.loss_i, loss_out_dev, grad_out_dev, hp.update ? 1 : 0, o,
-                       ad->delta, ad->delta_t, ad->m, ad->v);
-    ICREC_HIP(hipGetLastError());
-    if (hp.update) ad->t += 1;
-    return ICREC_OK;
-}
 
 }  // namespace
 }  // namespace icrec
@@ -1161,26 +1179,20 @@ int icrec_adapter_step(icrec_index* idx, icrec_adapter* h, const float* anchors_
                        int32_t C, float scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                        int32_t update, float* loss_out_dev, float* grad_out_dev, void* workspace_dev, size_t workspace_bytes,
                        void* stream) {
-    const Index* ix = reinterpret_cast<const Index*>(idx);
-    Adapter* ad = reinterpret_cast<Adapter*>(h);
-    const Hyper hp{scale, lr, beta1, beta2, eps, weight_decay, update != 0};
-    const int rc = check_step("icrec_adapter_step", "cand_rows", ix, ad, anchors_dev, cand_rows_dev, loss_out_dev, workspace_dev,
-                              B, hp);
+    Step s("icrec_adapter_step", idx, h, anchors_dev, B, Hyper{scale, lr, beta1, beta2, eps, weight_decay, update != 0},
+           loss_out_dev, grad_out_dev, workspace_dev, workspace_bytes, stream);
+    int rc = s.check("cand_rows", cand_rows_dev);
     if (rc != ICREC_OK) return rc;
     ICREC_REQUIRE(C >= B && C <= ICREC_ADAPTER_MAX_CANDIDATES, "icrec_adapter_step: C must be in [B, %d] (got %d, B %d)",
                   ICREC_ADAPTER_MAX_CANDIDATES, C, B);
-    const StepWorkspace ws(ad->dim, B);
-    ICREC_REQUIRE(workspace_bytes >= ws.total, "icrec_adapter_step: the workspace has %zu bytes, %zu are needed",
-                  workspace_bytes, ws.total);
-    ICREC_HIP(hipSetDevice(ad->device));
-    hipStream_t st = (hipStream_t)stream;
-    const StepArrays a(static_cast<char*>(workspace_dev), ws);
-    launch_forward(ad, anchors_dev, B, a, st);
-    hipLaunchKernelGGL((rows_are_bf16(ix) ? logits_kernel<true> : logits_kernel<false>),
-                       dim3((unsigned)((B + ANCHOR_TILE - 1) / ANCHOR_TILE)), dim3(LOGIT_THREADS), 0, st, (const void*)ix->rows,
-                       ad->dim, ix->n_rows, (const float*)a.U, (const float*)a.nrm, cand_rows_dev, (int)B, (int)C, scale, a.dZ,
-                       a.loss_i);
-    return launch_grad(ad, hp, anchors_dev, B, cand_rows_dev, ix->n_rows, a, loss_out_dev, grad_out_dev, st);
+    const StepWorkspace ws(s.ad->dim, B);
+    rc = s.forward(ws, ws.total);
+    if (rc != ICREC_OK) return rc;
+    hipLaunchKernelGGL((rows_are_bf16(s.ix) ? logits_kernel<true> : logits_kernel<false>),
+                       dim3((unsigned)((B + ANCHOR_TILE - 1) / ANCHOR_TILE)), dim3(LOGIT_THREADS), 0, s.st,
+                       (const void*)s.ix->rows, s.ad->dim, s.ix->n_rows, (const float*)s.U, (const float*)s.nrm, cand_rows_dev,
+                       (int)B, (int)C, scale, s.dZ, s.loss_i);
+    return s.grad(cand_rows_dev);
 }
 
 
@@ -1207,43 +1219,32 @@ int icrec_adapter_step_catalog(icrec_index* idx, icrec_adapter* h, const float* 
                                const int32_t* pos_rows_dev, float scale, float lr, float beta1, float beta2, float eps,
                                float weight_decay, int32_t update, float* loss_out_dev, float* grad_out_dev, void* workspace_dev,
                                size_t workspace_bytes, void* stream) {
-    const Index* ix = reinterpret_cast<const Index*>(idx);
-    Adapter* ad = reinterpret_cast<Adapter*>(h);
-    const Hyper hp{scale, lr, beta1, beta2, eps, weight_decay, update != 0};
-    const int rc = check_step("icrec_adapter_step_catalog", "pos_rows", ix, ad, anchors_dev, pos_rows_dev, loss_out_dev,
-                              workspace_dev, B, hp);
+    Step s("icrec_adapter_step_catalog", idx, h, anchors_dev, B, Hyper{scale, lr, beta1, beta2, eps, weight_decay, update != 0},
+           loss_out_dev, grad_out_dev, workspace_dev, workspace_bytes, stream);
+    int rc = s.check("pos_rows", pos_rows_dev);
     if (rc != ICREC_OK) return rc;
-    const int64_t n_rows = ix->n_rows;  // the rows of this call: the plan, every bound and the count use this one value
+    const int64_t n_rows = s.ix->n_rows;  // the rows of this call: the plan, every bound and the count use this one value
     const CatalogPlan plan = catalog_plan(B, n_rows);
-    const CatalogWorkspace ws(ad->dim, B, plan.n_splits);
-    ICREC_REQUIRE(workspace_bytes >= ws.total, "icrec_adapter_step_catalog: the workspace has %zu bytes, %zu are needed",
-                  workspace_bytes, ws.total);
-    ICREC_HIP(hipSetDevice(ad->device));
-    hipStream_t st = (hipStream_t)stream;
-    char* base = static_cast<char*>(workspace_dev);
-    const StepArrays a(base, ws.step);
-    float* s_pos = reinterpret_cast<float*>(base + ws.s_pos);
-    float* ml = reinterpret_cast<float*>(base + ws.ml);
-    int32_t* counted = reinterpret_cast<int32_t*>(base + ws.counted);
-    float* m_part = reinterpret_cast<float*>(base + ws.m_part);
-    float* l_part = reinterpret_cast<float*>(base + ws.l_part);
-    float* part = reinterpret_cast<float*>(base + ws.part);
-    const int d = ad->dim;
-    const bool p16 = rows_are_bf16(ix);
+    const CatalogWorkspace ws(s.ad->dim, B, plan.n_splits);
+    rc = s.forward(ws.step, ws.total);
+    if (rc != ICREC_OK) return rc;
+    float *s_pos = s.at(ws.s_pos), *ml = s.at(ws.ml), *m_part = s.at(ws.m_part), *l_part = s.at(ws.l_part), *part = s.at(ws.part);
+    int32_t* counted = s.at<int32_t>(ws.counted);
+    const int d = s.ad->dim;
+    const bool p16 = rows_are_bf16(s.ix);
     const dim3 grid((unsigned)((B + ANCHOR_TILE - 1) / ANCHOR_TILE), (unsigned)plan.n_splits);
-    launch_forward(ad, anchors_dev, B, a, st);
-    hipLaunchKernelGGL((p16 ? catalog_max_sum_kernel<true> : catalog_max_sum_kernel<false>), grid, dim3(LOGIT_THREADS), 0, st,
-                       (const void*)ix->rows, d, n_rows, plan.rows_per_split, (const float*)a.U, pos_rows_dev, (int)B, scale,
+    hipLaunchKernelGGL((p16 ? catalog_max_sum_kernel<true> : catalog_max_sum_kernel<false>), grid, dim3(LOGIT_THREADS), 0, s.st,
+                       (const void*)s.ix->rows, d, n_rows, plan.rows_per_split, (const float*)s.U, pos_rows_dev, (int)B, scale,
                        m_part, l_part, s_pos);
-    hipLaunchKernelGGL(catalog_merge_kernel, dim3(1), dim3(ICREC_ADAPTER_MAX_BATCH), 0, st, (const float*)m_part,
+    hipLaunchKernelGGL(catalog_merge_kernel, dim3(1), dim3(ICREC_ADAPTER_MAX_BATCH), 0, s.st, (const float*)m_part,
                        (const float*)l_part, plan.n_splits, pos_rows_dev, (int)B, n_rows, ml, counted);
-    hipLaunchKernelGGL((p16 ? catalog_du_kernel<true> : catalog_du_kernel<false>), grid, dim3(LOGIT_THREADS), 0, st,
-                       (const void*)ix->rows, d, n_rows, plan.rows_per_split, (const float*)a.U, (const float*)ml,
+    hipLaunchKernelGGL((p16 ? catalog_du_kernel<true> : catalog_du_kernel<false>), grid, dim3(LOGIT_THREADS), 0, s.st,
+                       (const void*)s.ix->rows, d, n_rows, plan.rows_per_split, (const float*)s.U, (const float*)ml,
                        (const int32_t*)counted, pos_rows_dev, (int)B, scale, part);
-    hipLaunchKernelGGL(catalog_finish_kernel, dim3((unsigned)B), dim3(FINISH_THREADS), 0, st, (const float*)part, plan.n_splits,
-                       (int)B, d, (const float*)a.U, (const float*)a.nrm, (const float*)ml, (const float*)s_pos, pos_rows_dev,
-                       n_rows, scale, a.dZ, a.loss_i);
-    return launch_grad(ad, hp, anchors_dev, B, pos_rows_dev, n_rows, a, loss_out_dev, grad_out_dev, st);
+    hipLaunchKernelGGL(catalog_finish_kernel, dim3((unsigned)B), dim3(FINISH_THREADS), 0, s.st, (const float*)part, plan.n_splits,
+                       (int)B, d, (const float*)s.U, (const float*)s.nrm, (const float*)ml, (const float*)s_pos, pos_rows_dev,
+                       n_rows, scale, s.dZ, s.loss_i);
+    return s.grad(pos_rows_dev);
 }
 
 size_t icrec_adapter_step_lists_workspace_bytes(const icrec_adapter* h, int32_t B) {
@@ -1257,34 +1258,27 @@ int icrec_adapter_step_lists(icrec_index* idx, icrec_adapter* h, const float* an
                              int32_t max_len, float scale, float lr, float beta1, float beta2, float eps, float weight_decay,
                              int32_t update, float* loss_out_dev, float* grad_out_dev, void* workspace_dev,
                              size_t workspace_bytes, void* stream) {
-    const Index* ix = reinterpret_cast<const Index*>(idx);
-    Adapter* ad = reinterpret_cast<Adapter*>(h);
-    const Hyper hp{scale, lr, beta1, beta2, eps, weight_decay, update != 0};
-    const int rc = check_step("icrec_adapter_step_lists", "list_off", ix, ad, anchors_dev, list_off_dev, loss_out_dev,
-                              workspace_dev, B, hp);
+    Step s("icrec_adapter_step_lists", idx, h, anchors_dev, B, Hyper{scale, lr, beta1, beta2, eps, weight_decay, update != 0},
+           loss_out_dev, grad_out_dev, workspace_dev, workspace_bytes, stream);
+    int rc = s.check("list_off", list_off_dev);
     if (rc != ICREC_OK) return rc;
     ICREC_REQUIRE(list_rows_dev != nullptr && list_target_dev != nullptr, "icrec_adapter_step_lists: NULL list_rows or list_target");
     ICREC_REQUIRE(max_len >= 1 && max_len <= ICREC_ADAPTER_MAX_LIST, "icrec_adapter_step_lists: max_len must be in [1, %d] (got %d)",
                   ICREC_ADAPTER_MAX_LIST, max_len);
-    const int64_t n_rows = ix->n_rows;  // the rows of this call: both kernels check against this one value
-    const ListsWorkspace ws(ad->dim, B);
-    ICREC_REQUIRE(workspace_bytes >= ws.total, "icrec_adapter_step_lists: the workspace has %zu bytes, %zu are needed",
-                  workspace_bytes, ws.total);
-    ICREC_HIP(hipSetDevice(ad->device));
-    hipStream_t st = (hipStream_t)stream;
-    char* base = static_cast<char*>(workspace_dev);
-    const StepArrays a(base, ws.step);
-    float* t_sum = reinterpret_cast<float*>(base + ws.t_sum);
-    int32_t* flag = reinterpret_cast<int32_t*>(base + ws.flag);
-    launch_forward(ad, anchors_dev, B, a, st);
-    hipLaunchKernelGGL(lists_plan_kernel, dim3((unsigned)((B + LISTS_WAVES - 1) / LISTS_WAVES)), dim3(LISTS_THREADS), 0, st,
+    const int64_t n_rows = s.ix->n_rows;  // the rows of this call: both kernels check against this one value
+    const ListsWorkspace ws(s.ad->dim, B);
+    rc = s.forward(ws.step, ws.total);
+    if (rc != ICREC_OK) return rc;
+    float* t_sum = s.at(ws.t_sum);
+    int32_t* flag = s.at<int32_t>(ws.flag);
+    hipLaunchKernelGGL(lists_plan_kernel, dim3((unsigned)((B + LISTS_WAVES - 1) / LISTS_WAVES)), dim3(LISTS_THREADS), 0, s.st,
                        list_off_dev, list_rows_dev, list_target_dev, (int)B, (int)max_len, n_rows, t_sum, flag);
-    hipLaunchKernelGGL((rows_are_bf16(ix) ? lists_kernel<true> : lists_kernel<false>), dim3((unsigned)B), dim3(LISTS_THREADS), 0,
-                       st, (const void*)ix->rows, ad->dim, n_rows, (const float*)a.U, (const float*)a.nrm, list_off_dev,
+    hipLaunchKernelGGL((rows_are_bf16(s.ix) ? lists_kernel<true> : lists_kernel<false>), dim3((unsigned)B), dim3(LISTS_THREADS), 0,
+                       s.st, (const void*)s.ix->rows, s.ad->dim, n_rows, (const float*)s.U, (const float*)s.nrm, list_off_dev,
                        list_rows_dev, list_target_dev, (int)max_len, (const float*)t_sum, (const int32_t*)flag, (int)B, scale,
-                       a.dZ, a.loss_i);
+                       s.dZ, s.loss_i);
     // the flag rows stand in for the positives: row 0 is in range for a counted anchor, -1 is not
-    return launch_grad(ad, hp, anchors_dev, B, flag, n_rows, a, loss_out_dev, grad_out_dev, st);
+    return s.grad(flag);
 }
 
 

@@ -1,17 +1,17 @@
 """Shared inputs of the whole-catalog adapter step's tests: csrc/adapt.hip's split rule restated, the cases of
 tests/test_adapter_catalog_gpu.py - each names the path it aims at, and tests/test_adapter_catalog.py shows without a GPU
-that it gets there - and their float64 and float32 references, computed once.  Importing this needs no GPU."""
+that it gets there - and their float64 and float32 references (tests/adapter_harness.py), computed once.  Importing this needs no GPU."""
 from __future__ import annotations
 
 import functools
 from typing import NamedTuple
 
 import numpy as np
-import torch
 
-from tests import adapter_catalog_reference as cref
 from tests import adapter_reference as ref
-from tests.adapter_cases import ANCHOR_TILE, INT32_MAX, INT32_MIN, MAX_BATCH, small_delta, unit_rows
+from tests.adapter_cases import ANCHOR_TILE, INT32_MAX, INT32_MIN, MAX_BATCH
+from tests.adapter_harness import _frozen, small_delta, unit_rows
+from tests.adapter_harness import references as references_of
 
 # csrc/adapt.hip's cut of the catalog, restated: the rows are walked in groups of GROUP (a 32-row tile per wave); the
 # middle kernels run on (anchor tiles x splits) workgroups, as many splits as bring that product to TARGET_WORKGROUPS,
@@ -92,12 +92,6 @@ def edge_labels(rng, B, n_rows):
     return pos
 
 
-def _frozen(*arrays):
-    for a in arrays:
-        a.setflags(write=False)
-    return arrays
-
-
 @functools.lru_cache(maxsize=None)
 def inputs(name: str):
     """(P float32 [n_rows, dim] as given to the index, the rows it stores, anchors [B, dim], D [dim, dim], pos int64 [B])
@@ -117,17 +111,9 @@ def inputs(name: str):
         assert plan(c.B, c.n_rows)[0] >= 8 and 7 < plan(c.B, c.n_rows)[1]
         P[last], pos[0] = u[0], 5
         P[7], pos[1] = u[1], last - 9
-    return _frozen(P, cref.stored_rows(P, c.storage), anchors, delta, pos)
+    return _frozen(P, ref.stored_rows(P, c.storage), anchors, delta, pos)
 
 
-@functools.lru_cache(maxsize=None)
-def references(name: str, scale: float):
-    """(float64 loss, float64 gradient, float32 loss, float32 gradient) of a case by tests/adapter_catalog_reference.py."""
-    _, rows, anchors, delta, pos = inputs(name)
-    want = cref.loss_and_grad(delta, anchors, rows, pos, scale, torch.float64)
-    ref32 = cref.loss_and_grad(delta, anchors, rows, pos, scale, torch.float32)
-    _frozen(want[1], ref32[1])
-    return want[0], want[1], ref32[0], ref32[1]
-
+references = functools.partial(references_of, "catalog", inputs)  # (name, scale) -> float64 and float32 loss and gradient
 
 assert all(c.B <= MAX_BATCH for c in CASES)

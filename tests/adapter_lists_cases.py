@@ -1,17 +1,17 @@
 """Shared inputs of the tests of icrec_adapter_step_lists: the cases - each names the path of csrc/adapt.hip's
 lists_plan_kernel / lists_kernel it aims at, and tests/test_adapter_lists.py shows without a GPU, from the reference's
-masks, that it gets there - their float64 and float32 references, computed once, and the one comparison of a device
-step with them.  Importing this needs no GPU."""
+masks, that it gets there - with their float64 and float32 references (tests/adapter_harness.py), computed once.
+Importing this needs no GPU."""
 from __future__ import annotations
 
 import functools
 from typing import NamedTuple
 
 import numpy as np
-import torch
 
-from tests import adapter_lists_reference as lref
-from tests.adapter_cases import _frozen, check_step, small_delta, unit_rows
+from tests import adapter_reference as ref
+from tests.adapter_harness import _frozen, small_delta, unit_rows
+from tests.adapter_harness import references as references_of
 
 # csrc/adapt.hip's shape of the step, restated: a wave of lists_kernel scores SCORE_DEPTH entries at once and the four
 # waves walk the list in strides of WAVES * SCORE_DEPTH; a lane sums entries lane, lane + 64, ..; sweep 2 loads DEPTH
@@ -20,8 +20,6 @@ WAVES, SCORE_DEPTH, DEPTH, GROUP, GRAD_BLOCK = 4, 4, 8, 128, 64
 MAX_LIST, MAX_BATCH = 1024, 1024  # include/icrec.h's ICREC_ADAPTER_MAX_LIST, ICREC_ADAPTER_MAX_BATCH
 GAINS = np.asarray([0, 0, 0, 0, 1, 2, 4], np.float32)  # the default gains of the four event types, mostly impressions
 EDGE_LENGTHS = (1, 2, 63, 64, 65, 100)
-
-check = check_step  # (what, loss, grad, want_loss, want_grad, ref_loss, ref_grad, margin): RATIO lines, then the asserts
 
 
 class Case(NamedTuple):
@@ -62,7 +60,7 @@ def uniform_lists(rng, B, L, n_rows):
     rows = np.stack([rng.choice(n_rows, L, replace=False) for _ in range(B)])
     gains = rng.choice(GAINS, (B, L))
     gains[np.arange(B), rng.integers(0, L, B)] = 4.0
-    return lref.uniform_csr(rows, gains)
+    return ref.uniform_csr(rows, gains)
 
 
 def length_lists(rng, B, n_rows):
@@ -150,23 +148,7 @@ def inputs(name: str):
         assert c.lists == "long heads"
         lists = long_head_lists(rng, c.B, c.L, c.n_rows, c.max_len)
     _frozen(P, anchors, delta, *lists[:3])
-    return P, _frozen(lref.stored_rows(P, c.storage))[0], anchors, delta, lists
+    return P, _frozen(ref.stored_rows(P, c.storage))[0], anchors, delta, lists
 
 
-@functools.lru_cache(maxsize=None)
-def references(name: str, scale: float):
-    """(float64 loss, float64 gradient, float32 loss, float32 gradient) of a case by tests/adapter_lists_reference.py."""
-    _, stored, anchors, delta, lists = inputs(name)
-    want = lref.loss_and_grad(delta, anchors, stored, *lists, scale, torch.float64)
-    ref32 = lref.loss_and_grad(delta, anchors, stored, *lists, scale, torch.float32)
-    _frozen(want[1], ref32[1])
-    return want[0], want[1], ref32[0], ref32[1]
-
-
-def device_lists(lists, device):
-    """A case's lists as QueryAdapter takes them ready made: (off int32, rows int32, target float32, max_len) on `device`;
-    a row beyond int32 is out of range for any index: -1."""
-    off, rows, target, max_len = lists
-    rows = np.where((rows < 0) | (rows > 2**31 - 1), -1, rows)
-    return (torch.from_numpy(off.astype(np.int32)).to(device), torch.from_numpy(rows.astype(np.int32)).to(device),
-            torch.from_numpy(np.ascontiguousarray(target, np.float32)).to(device), int(max_len))
+references = functools.partial(references_of, "lists", inputs)  # (name, scale) -> float64 and float32 loss and gradient

@@ -6,9 +6,11 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+import torch
 
 from instacart_next_order_recommendation_amd import _native
 from tests import adapter_cases as ac
+from tests import adapter_harness as h
 from tests import adapter_reference as ref
 from tests.token_states import row_errors
 
@@ -134,7 +136,7 @@ def test_references_are_finite_and_the_float32_error_is_positive(name, scale):
     assert want_loss > 0 and np.abs(want_grad).max() > 0
     e_rms, e_abs = row_errors(ref_grad, want_grad)
     assert e_rms > 0 and e_abs > 0
-    assert max(abs(ref_loss - want_loss), ac.loss_floor(want_loss)) > 0
+    assert max(abs(ref_loss - want_loss), h.loss_floor(want_loss)) > 0
     assert ac.references(name, scale)[1] is want_grad and not want_grad.flags.writeable  # computed once, left unchanged
 
 
@@ -153,20 +155,20 @@ def test_the_adamw_bound_is_one_ieee_float32_meets(d):
     """The AdamW bound of the GPU tests, on the kernel's formula in numpy float32: met everywhere; test_adapter_gpu's
     form of it (|term| for the Adam term's magnitude) is the same number wherever m and (g - m)(1 - beta1) do not cancel
     and is missed by correct float32 arithmetic where they do, at d = 1024."""
-    P, anchors, cand, delta, m, v = ac.adamw_inputs(d)
-    g = ref.loss_and_grad(delta, anchors, ref.stored_rows(P), cand, 30.0, ac.torch.float32)[1].astype(np.float32)
+    P, anchors, cand, delta, m, v = h.adamw_inputs(d)
+    g = ref.loss_and_grad(delta, anchors, ref.stored_rows(P), cand, 30.0, torch.float32)[1].astype(np.float32)
     before = {"delta": delta, "m": m, "v": v, "t": 7}
-    p, m1, v1 = ac.adamw_float32(delta, m, v, 7, g, *ac.ADAMW_HYPER)
+    p, m1, v1 = h.adamw_float32(delta, m, v, 7, g, *h.ADAMW_HYPER)
     after = {"delta": p, "m": m1, "v": v1, "t": 8}
-    use_delta, use_m, use_v, use_plain, t = ac.adamw_bound_use(before, g, after)
+    use_delta, use_m, use_v, use_plain, t = h.adamw_bound_use(before, g, after)
     print(f"AdamW d{d}: bound use D {use_delta.max():.2f} m {use_m.max():.2f} v {use_v.max():.2f}; "
           f"with |term|: {use_plain.max():.2f}, {(use_plain > 1).sum()} of {use_plain.size} elements over")
-    ac.assert_adamw(before, g, after)
+    h.assert_adamw(before, g, after)
     assert t == 8 and (use_plain >= use_delta * (1 - 1e-9)).all()
     same_sign = m.astype(np.float64) * (g.astype(np.float64) - m) >= 0
     assert same_sign.any() and np.allclose(use_plain[same_sign], use_delta[same_sign], rtol=1e-6)
     if d == 1024:
         assert (use_plain > 1).sum() > 100 and use_plain.max() > 8
     # a wrong bias correction (t instead of t + 1) is far outside it
-    wrong = ac.adamw_float32(delta, m, v, 6, g, *ac.ADAMW_HYPER)
-    assert ac.adamw_bound_use(before, g, {"delta": wrong[0], "m": wrong[1], "v": wrong[2], "t": 8})[0].max() > 1000
+    wrong = h.adamw_float32(delta, m, v, 6, g, *h.ADAMW_HYPER)
+    assert h.adamw_bound_use(before, g, {"delta": wrong[0], "m": wrong[1], "v": wrong[2], "t": 8})[0].max() > 1000

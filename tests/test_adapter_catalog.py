@@ -9,14 +9,13 @@ import torch
 
 from instacart_next_order_recommendation_amd import adapter, cli
 from tests import adapter_catalog_cases as cases
-from tests import adapter_catalog_reference as cref
 from tests import adapter_reference as ref
-from tests.adapter_cases import small_delta, unit_rows
+from tests.adapter_harness import small_delta, unit_rows
 
 
 def world(B=6, n_rows=40, d=16, seed=0):
     rng = np.random.default_rng(seed)
-    return cref.stored_rows(unit_rows(rng, n_rows, d)), unit_rows(rng, B, d).astype(np.float64), small_delta(rng, d).astype(np.float64)
+    return ref.stored_rows(unit_rows(rng, n_rows, d)), unit_rows(rng, B, d).astype(np.float64), small_delta(rng, d).astype(np.float64)
 
 
 def as_list(pos, n_rows):
@@ -27,7 +26,7 @@ def as_list(pos, n_rows):
 def test_reference_is_the_list_reference_over_the_whole_catalog_when_positives_are_distinct():
     rows, anchors, delta = world()
     pos = np.array([3, 39, 0, 12, 7, 20])
-    loss, grad = cref.loss_and_grad(delta, anchors, rows, pos, 30.0)
+    loss, grad = ref.loss_and_grad_catalog(delta, anchors, rows, pos, 30.0)
     want_loss, want_grad = ref.loss_and_grad(delta, anchors, rows, as_list(pos, 40), 30.0)
     assert loss == pytest.approx(want_loss, rel=1e-13)
     np.testing.assert_allclose(grad, want_grad, rtol=1e-10, atol=1e-15)
@@ -35,18 +34,18 @@ def test_reference_is_the_list_reference_over_the_whole_catalog_when_positives_a
     out = pos.copy()
     out[1], out[4] = 40, -1
     kept = [0, 2, 3, 5]
-    loss, grad = cref.loss_and_grad(delta, anchors, rows, out, 30.0)
-    want_loss, want_grad = cref.loss_and_grad(delta, anchors[kept], rows, pos[kept], 30.0)
+    loss, grad = ref.loss_and_grad_catalog(delta, anchors, rows, out, 30.0)
+    want_loss, want_grad = ref.loss_and_grad_catalog(delta, anchors[kept], rows, pos[kept], 30.0)
     assert loss == pytest.approx(want_loss, rel=1e-13)
     np.testing.assert_allclose(grad, want_grad, rtol=1e-10, atol=1e-15)
-    loss, grad = cref.loss_and_grad(delta, anchors, rows, np.array([-1, 40, 99, 2**31 - 1, -2**31, 41]), 30.0)
+    loss, grad = ref.loss_and_grad_catalog(delta, anchors, rows, np.array([-1, 40, 99, 2**31 - 1, -2**31, 41]), 30.0)
     assert loss == 0.0 and not grad.any()
 
 
 def test_a_shared_positive_is_not_masked_unlike_the_list_rule():
     rows, anchors, delta = world()
     pos = np.array([3, 3, 0, 12, 7, 20])  # anchors 0 and 1 share row 3
-    loss, grad = cref.loss_and_grad(delta, anchors, rows, pos, 30.0)
+    loss, grad = ref.loss_and_grad_catalog(delta, anchors, rows, pos, 30.0)
     # the list rule masks anchor 1's copy of row 3 for anchor 0 and the reverse; with the copy dropped from the list
     # instead, the list IS the catalog once more, and only then do the two agree
     cand = np.concatenate([pos, np.setdiff1d(np.arange(40), pos)])
@@ -63,14 +62,14 @@ def test_a_shared_positive_is_not_masked_unlike_the_list_rule():
 def test_gradient_is_the_derivative_of_the_loss():
     rows, anchors, delta = world(B=4, n_rows=9, d=4, seed=2)
     pos = np.array([3, 3, 8, 9])
-    _, grad = cref.loss_and_grad(delta, anchors, rows, pos, 30.0)
+    _, grad = ref.loss_and_grad_catalog(delta, anchors, rows, pos, 30.0)
     h = 1e-6
     for r in range(4):
         for c in range(4):
             up, down = delta.copy(), delta.copy()
             up[r, c] += h
             down[r, c] -= h
-            fd = (cref.loss_and_grad(up, anchors, rows, pos, 30.0)[0] - cref.loss_and_grad(down, anchors, rows, pos, 30.0)[0]) / (2 * h)
+            fd = (ref.loss_and_grad_catalog(up, anchors, rows, pos, 30.0)[0] - ref.loss_and_grad_catalog(down, anchors, rows, pos, 30.0)[0]) / (2 * h)
             assert abs(fd - grad[r, c]) <= 1e-6 * max(1.0, abs(grad[r, c])), (r, c)
 
 
@@ -107,7 +106,7 @@ def test_each_gpu_case_reaches_the_path_it_names():
     for name in ("labels-f32", "labels-bf16"):
         c = by[name]
         pos = cases.inputs(name)[4]
-        counted = cref.counted(pos, c.n_rows)
+        counted = ref.counted_labels(pos, c.n_rows)
         lo = cases.UNCOUNTED_ANCHOR_TILE * 32
         assert c.B > lo + 32 and not counted[lo:lo + 32].any() and counted[lo + 32:].all()
         assert pos[0] == 0 and pos[1] == c.n_rows - 1 and len({int(pos[i]) for i in cases.SHARED}) == 1
@@ -145,16 +144,16 @@ def test_fit_plan_and_the_command_line_accept_all():
 def test_reference_with_catalog_steps_solves_the_learning_task():
     """tests/test_adapter.py's task and thresholds, every step against all 2,048 rows."""
     P, a_train, p_train, a_held, p_held = ref.learning_task()
-    rows = cref.stored_rows(P)
+    rows = ref.stored_rows(P)
     d = ref.TASK_DIM
     delta, m, v, t = np.zeros((d, d)), np.zeros((d, d)), np.zeros((d, d)), 0
     assert ref.recall_at(ref.top_rows(a_held, rows, 10), p_held) <= 0.05
     losses = []
     for step in range(ref.TASK_STEPS):
         at = ref.task_batch(step)
-        loss, grad = cref.loss_and_grad(delta, a_train[at], rows, p_train[at], ref.TASK_SCALE, torch.float64)
-        delta, m, v, t, _ = cref.adamw(delta, m, v, t, grad, ref.TASK_LR, weight_decay=ref.TASK_DECAY)
+        loss, grad = ref.loss_and_grad_catalog(delta, a_train[at], rows, p_train[at], ref.TASK_SCALE, torch.float64)
+        delta, m, v, t, _ = ref.adamw(delta, m, v, t, grad, ref.TASK_LR, weight_decay=ref.TASK_DECAY)
         losses.append(loss)
-    after = ref.recall_at(ref.top_rows(cref.apply(delta, a_held), rows, 10), p_held)
+    after = ref.recall_at(ref.top_rows(ref.apply(delta, a_held), rows, 10), p_held)
     print(f"recall@10 -> {after:.4f}, loss {losses[0]:.3f} -> {losses[-1]:.3f}")
     assert after >= 0.99 and losses[-1] < 0.5 * losses[0]

@@ -1,7 +1,8 @@
-"""icrec_adapter_step_catalog on the GPU against tests/adapter_catalog_reference.py: the loss and its gradient within
-margin x the float32 reference's own error (tests/adapter_cases.check_step's convention; measured ratios and the margins'
-choice: profiles/adapter_catalog_errors.md) on the cases of tests/adapter_catalog_cases.py, the labels' rules, the index
-after every kind of edit, determinism, AdamW, the argument checks, and the learning task end to end."""
+"""icrec_adapter_step_catalog on the GPU against tests/adapter_reference.py's loss_and_grad_catalog: the loss and its
+gradient within margin x the float32 reference's own error (tests/adapter_harness.check_step's convention; measured ratios
+and the margins' choice: profiles/adapter_catalog_errors.md) on the cases of tests/adapter_catalog_cases.py, the labels'
+rules, the index after every kind of edit, determinism, AdamW, the argument checks, and the learning task end to end.
+What the three kinds of step are tested for alike has its one body in tests/adapter_harness.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,28 +12,16 @@ import pytest
 import torch
 
 from instacart_next_order_recommendation_amd import _native
-from instacart_next_order_recommendation_amd.adapter import QueryAdapter
 from instacart_next_order_recommendation_amd.search import DeviceIndex
 from tests import adapter_catalog_cases as cases
-from tests import adapter_catalog_reference as cref
+from tests import adapter_harness as h
 from tests import adapter_reference as ref
-from tests.adapter_cases import ADAMW_HYPER, assert_adamw, check_step, loss_floor, small_delta, unit_rows
+from tests.adapter_harness import DEV, adapter_with, loss_floor, small_delta, unit_rows
 from tests.search_harness import torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-
-#: margin on E_ref per (storage, dim), for the gradient's rms and max-abs error and for the loss: the smallest of
-#: {2, 3, 4, 6, 8} that leaves 1.5x headroom over the worst ratio measured on the MI355X (profiles/adapter_catalog_errors.md)
-MARGINS = {("f32", 32): 2, ("f32", 64): 2, ("f32", 96): 2, ("f32", 384): 4, ("f32", 1024): 2,
-           ("bf16", 64): 2, ("bf16", 128): 2, ("bf16", 384): 4, ("bf16", 768): 4, ("bf16", 1024): 2}
-
-
-def adapter_with(delta, m=None, v=None, t=0) -> QueryAdapter:
-    ad = QueryAdapter(delta.shape[0], DEV)
-    ad.load_state({"delta": delta, "m": m, "v": v, "t": t})
-    return ad
+MARGINS = h.KINDS["catalog"].margins
 
 
 def device_plan(ad, B, n_rows):
@@ -44,27 +33,15 @@ def device_plan(ad, B, n_rows):
 # ---------------------------------------------------------------- loss and gradient
 @pytest.mark.parametrize("name,scale", cases.STEPS, ids=lambda v: str(v))
 def test_loss_and_gradient_within_margin_of_the_float32_reference(torch_cuda, name, scale):
-    c = cases.CASE_BY_NAME[name]
-    P, _, anchors, delta, pos = cases.inputs(name)
-    ix = DeviceIndex(P, DEV, storage=c.storage)
-    ad = adapter_with(delta)
-    assert device_plan(ad, c.B, c.n_rows) == cases.plan(c.B, c.n_rows)
-    loss, grad = ad.loss_and_grad_catalog(ix, torch.from_numpy(anchors).to(DEV), torch.from_numpy(pos), scale)
-    loss, grad = float(loss.cpu()), grad.cpu().numpy()
-    check_step(f"catalog {name} scale {scale:g}", loss, grad, *cases.references(name, scale), MARGINS[(c.storage, c.dim)])
-    assert ad.steps == 0 and np.array_equal(ad.state()["delta"], delta)  # loss_and_grad_catalog changes nothing
-    ix.close()
+    def split_rule(ad, c):  # the library cuts the catalog as tests/adapter_catalog_cases.plan restates it
+        assert device_plan(ad, c.B, c.n_rows) == cases.plan(c.B, c.n_rows)
+
+    h.check_case("catalog", cases, name, scale, split_rule)
 
 
 def test_nobody_counted_is_exactly_zero(torch_cuda):
-    rng = np.random.default_rng(5)
-    ix = DeviceIndex(unit_rows(rng, 300, 64), DEV, storage="f32")
-    ad = adapter_with(small_delta(rng, 64))
-    anchors = torch.from_numpy(unit_rows(rng, 40, 64)).to(DEV)
-    for pos in ([300], [-1, 300, 2**31 - 1, -2**31, 2**40], [-1] * 40):
-        loss, grad = ad.loss_and_grad_catalog(ix, anchors[:len(pos)], torch.tensor(pos))
-        assert float(loss.cpu()) == 0.0 and not grad.cpu().numpy().any(), pos
-    ix.close()
+    h.check_exact_zeros("catalog", 300, 40, [(pos, len(pos), torch.tensor(pos)) for pos in
+                                             ([300], [-1, 300, 2**31 - 1, -2**31, 2**40], [-1] * 40)])
 
 
 # ---------------------------------------------------------------- index states
@@ -79,17 +56,11 @@ def test_the_rows_the_index_holds_after_every_kind_of_edit(torch_cuda, storage):
     delta = small_delta(rng, d)
     ad = adapter_with(delta)
     anchors = unit_rows(rng, B, d)
-    a_dev = torch.from_numpy(anchors).to(DEV)
-    margin = MARGINS[(storage.split("+")[0], d)]
 
     def agree(what, pos):
         assert ix.n_rows == P.shape[0]
-        rows = cref.stored_rows(P, storage)
-        want = cref.loss_and_grad(delta, anchors, rows, pos, scale, torch.float64)
-        ref32 = cref.loss_and_grad(delta, anchors, rows, pos, scale, torch.float32)
-        loss, grad = ad.loss_and_grad_catalog(ix, a_dev, torch.from_numpy(pos), scale)
-        check_step(f"catalog {storage} {what}", float(loss.cpu()), grad.cpu().numpy(), *want, *ref32, margin)
-        return float(loss.cpu())
+        h.check_against_reference("catalog", f"catalog {storage} {what}", ix, ad, anchors, delta, ref.stored_rows(P, storage),
+                                  pos, storage, scale)
 
     pos = rng.integers(0, 300, B).astype(np.int64)
     pos[:3] = (0, 299, 299)
@@ -126,23 +97,8 @@ def test_the_same_inputs_give_the_same_bits(torch_cuda):
     for name in ("f32-384", "batch-limit"):
         c = cases.CASE_BY_NAME[name]
         P, _, anchors, delta, pos = cases.inputs(name)
-        ix = DeviceIndex(P, DEV, storage=c.storage)
-        a_dev, p_dev = torch.from_numpy(anchors).to(DEV), torch.from_numpy(pos)
         m, v = small_delta(np.random.default_rng(1), c.dim), np.abs(small_delta(np.random.default_rng(2), c.dim))
-        seen = []
-        for how in ("plain", "again", "no grad_out", "NaN workspace"):
-            ad = adapter_with(delta, m, v, 3)
-            grad = None if how == "no grad_out" else torch.empty((c.dim, c.dim), dtype=torch.float32, device=DEV)
-            if how == "NaN workspace":
-                need = int(_native.lib().icrec_adapter_step_catalog_workspace_bytes(ad._h, ix._h, c.B))
-                ad._scratch.block(need).fill_(0xFF)  # every float of it a NaN, every int -1
-            loss = ad.step_catalog(ix, a_dev, p_dev, 1e-3, grad_out=grad)
-            state = ad.state()
-            assert state["t"] == 4
-            seen.append((loss.cpu().numpy().tobytes(), state["delta"].tobytes(), state["m"].tobytes(), state["v"].tobytes(),
-                         None if grad is None else grad.cpu().numpy().tobytes()))
-        assert seen[0] == seen[1] == seen[3] and seen[2][:4] == seen[0][:4], name
-        ix.close()
+        h.check_determinism("catalog", P, c.storage, anchors, pos, delta, m, v)
 
 
 # ---------------------------------------------------------------- update
@@ -153,21 +109,7 @@ def test_adamw_step_on_the_steps_own_gradient(torch_cuda, d):
     pos = rng.integers(0, 500, 40)
     m = (rng.standard_normal((d, d)) * 1e-3).astype(np.float32)
     v = (rng.random((d, d)) * 1e-5).astype(np.float32)
-    ix = DeviceIndex(P, DEV, storage="f32")
-    ad = adapter_with(small_delta(rng, d), m, v, 7)
-    a_dev, p_dev = torch.from_numpy(anchors).to(DEV), torch.from_numpy(pos)
-    before = ad.state()
-    want_loss, want_grad = ad.loss_and_grad_catalog(ix, a_dev, p_dev)
-    assert ad.steps == 7 and all(np.array_equal(ad.state()[k], before[k]) for k in ("delta", "m", "v"))
-    lr, b1, b2, eps, wd = ADAMW_HYPER
-    grad = torch.empty((d, d), dtype=torch.float32, device=DEV)
-    loss = ad.step_catalog(ix, a_dev, p_dev, lr, (b1, b2), eps, wd, grad_out=grad)
-    assert torch.equal(grad, want_grad) and torch.equal(loss, want_loss) and float(grad.abs().max()) > 0
-    after = ad.state()
-    assert ad.steps == 8
-    assert_adamw(before, grad.cpu().numpy(), after)
-    assert np.array_equal(ad.apply(a_dev).cpu().numpy(), ref.apply(after["delta"], anchors))  # the apply copy followed
-    ix.close()
+    h.check_adamw("catalog", P, anchors, pos, small_delta(rng, d), m, v)
 
 
 # ---------------------------------------------------------------- arguments
@@ -179,41 +121,16 @@ def test_argument_checks_and_catalog_loss(torch_cuda):
     ad = adapter_with(delta)
     anchors = torch.from_numpy(unit_rows(rng, 4, 64)).to(DEV)
     pos = torch.tensor([1, 2, 3, 4])
-    with pytest.raises(_native.IcrecError, match="the index has dim 64, the adapter 32"):
-        QueryAdapter(32, DEV).loss_and_grad_catalog(ix, anchors[:, :32].contiguous(), pos)
+    h.check_shared_arguments("catalog", ix, ad, anchors, pos.numpy())
     with pytest.raises(_native.IcrecError, match="B must be in"):
         ad.loss_and_grad_catalog(ix, anchors.repeat(257, 1), torch.zeros(1028, dtype=torch.int64))
     with pytest.raises(ValueError, match="4 anchors for 3 positives"):
         ad.loss_and_grad_catalog(ix, anchors, pos[:3])
-    for kw in (dict(lr=float("nan")), dict(lr=1e-3, scale=float("inf")), dict(lr=1e-3, weight_decay=float("nan")),
-               dict(lr=1e-3, eps=float("inf"))):
-        with pytest.raises(_native.IcrecError, match="not finite"):
-            ad.step_catalog(ix, anchors, pos, **kw)
-    with pytest.raises(_native.IcrecError, match="beta1 and beta2"):
-        ad.step_catalog(ix, anchors, pos, 1e-3, betas=(1.0, 0.999))
-    with pytest.raises(_native.IcrecError, match="beta1 and beta2"):
-        ad.step_catalog(ix, anchors, pos, 1e-3, eps=-1.0)
     L = _native.lib()
-    need = int(L.icrec_adapter_step_catalog_workspace_bytes(ad._h, ix._h, 4))
-    assert need > 0
     assert L.icrec_adapter_step_catalog_workspace_bytes(ad._h, ix._h, 0) == 0
     assert L.icrec_adapter_step_catalog_workspace_bytes(ad._h, ix._h, 1025) == 0
     assert L.icrec_adapter_step_catalog_workspace_bytes(None, ix._h, 4) == 0
     assert L.icrec_adapter_step_catalog_workspace_bytes(ad._h, None, 4) == 0
-    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
-    loss = torch.empty(1, device=DEV)
-    p32 = pos.to(DEV, torch.int32)
-
-    def call(idx=ix._h, adapter=ad._h, a=_native.ptr(anchors), B=4, p=_native.ptr(p32), out=_native.ptr(loss), w=_native.ptr(ws),
-             n=need):
-        return L.icrec_adapter_step_catalog(idx, adapter, a, B, p, 30.0, 0.0, 0.9, 0.999, 1e-8, 0.0, 0, out, None, w, n, None)
-
-    assert call() == 0
-    for kw, text in ((dict(idx=None), b"NULL idx"), (dict(adapter=None), b"NULL adapter"), (dict(a=None), b"NULL anchors"),
-                     (dict(p=None), b"NULL anchors or pos_rows"), (dict(out=None), b"NULL loss_out"),
-                     (dict(w=None), b"NULL workspace"), (dict(B=0), b"B must be in"), (dict(B=1025), b"B must be in"),
-                     (dict(n=need - 1), b"workspace")):  # .. a workspace one byte short
-        assert call(**kw) == -1 and text in L.icrec_last_error(), kw
     n_splits, per_split = C.c_int32(0), C.c_int64(0)
     for B, n_rows in ((0, 10), (1025, 10), (4, 0)):
         assert L.icrec_adapter_catalog_plan(ad._h, B, n_rows, C.byref(n_splits), C.byref(per_split)) == -1
@@ -225,8 +142,8 @@ def test_argument_checks_and_catalog_loss(torch_cuda):
     labels = rng.integers(0, 700, 2500).astype(np.int64)
     labels[::97] = -1
     labels[1024:1030] = 700
-    want = cref.mean_loss(delta, held, cref.stored_rows(P, "f32"), labels, 20.0)
-    ref32 = cref.loss_and_grad(delta, held, cref.stored_rows(P, "f32"), labels, 20.0, torch.float32)[0]
+    want = ref.mean_loss_catalog(delta, held, ref.stored_rows(P, "f32"), labels, 20.0)
+    ref32 = ref.loss_and_grad_catalog(delta, held, ref.stored_rows(P, "f32"), labels, 20.0, torch.float32)[0]
     ad.scale = 20.0
     got = ad.catalog_loss(ix, torch.from_numpy(held).to(DEV), labels)
     e_ref = max(abs(ref32 - want), loss_floor(want))
@@ -241,35 +158,18 @@ def test_argument_checks_and_catalog_loss(torch_cuda):
 def test_catalog_steps_learn_the_rotation_end_to_end(torch_cuda):
     """The thresholds tests/test_adapter_gpu.py holds the list step to: held-out recall@10 through icrec_search at most
     0.05 before and at least 0.9 after 100 steps, the loss at least halved."""
-    P, a_train, p_train, a_held, p_held = ref.learning_task()
-    ix = DeviceIndex(P, DEV, storage="f32")
-    ad = QueryAdapter(ref.TASK_DIM, DEV)
-    held = torch.from_numpy(a_held).to(DEV)
-    a_dev, p_dev = torch.from_numpy(a_train).to(DEV), torch.from_numpy(p_train).to(DEV, torch.int32)
-
-    def recall():
-        return ref.recall_at(ix.search(ad.apply(held), 10)[0].cpu().numpy(), p_held)
-
-    before, held_before = recall(), ad.catalog_loss(ix, held, p_held)
-    losses = torch.zeros(ref.TASK_STEPS, device=DEV)
-    for step in range(ref.TASK_STEPS):
-        at = ref.task_batch(step)
-        ad.step_catalog(ix, a_dev[at], p_dev[at], ref.TASK_LR, weight_decay=ref.TASK_DECAY, scale=ref.TASK_SCALE,
-                        loss_out=losses[step:step + 1])
-    after, held_after = recall(), ad.catalog_loss(ix, held, p_held)
-    losses = losses.cpu().numpy()
-    print(f"recall@10 {before:.4f} -> {after:.4f}, loss {losses[0]:.3f} -> {losses[-1]:.3f}, held-out {held_before:.3f} -> "
-          f"{held_after:.3f}")
-    assert before <= 0.05 and after >= 0.9 and ad.steps == ref.TASK_STEPS
-    assert np.isfinite(losses).all() and losses[-1] < 0.5 * losses[0] and held_after < 0.5 * held_before
+    task = ref.learning_task()
+    p_train, a_held, p_held = task[2], task[3], task[4]
+    p_dev, held = torch.from_numpy(p_train).to(DEV, torch.int32), torch.from_numpy(a_held).to(DEV)
+    ix, ad, after, losses, (held_before, held_after) = h.train_on_task(
+        "catalog", task, lambda at: p_dev[at], lambda ix, ad: ad.catalog_loss(ix, held, p_held))
+    print(f"held-out {held_before:.3f} -> {held_after:.3f}")
+    assert after >= 0.9 and losses[-1] < 0.5 * losses[0] and held_after < 0.5 * held_before
     # fit(negatives="all"): reproducible from its seed, drop_last, every step a catalog step
-    runs = []
-    for _ in range(2):
-        fitted = QueryAdapter(ref.TASK_DIM, DEV)
-        got = fitted.fit(ix, a_dev[:1000], p_train[:1000], epochs=2, batch_size=128, negatives="all", lr=5e-3, seed=4)
-        runs.append((got, fitted.state()["delta"].tobytes()))
-        assert len(got) == 2 * (1000 // 128) and fitted.steps == len(got)
-    assert runs[0] == runs[1] and runs[0][0][-1] < runs[0][0][0]
+    a_dev = torch.from_numpy(task[1]).to(DEV)
+    h.check_fit_is_reproducible(lambda fitted: fitted.fit(ix, a_dev[:1000], p_train[:1000], epochs=2, batch_size=128,
+                                                          negatives="all", lr=5e-3, seed=4), 2 * (1000 // 128))
+    ad.close()
     ix.close()
 
 

@@ -1,6 +1,6 @@
 """icrec_adapter_step at the limits include/icrec.h states and on the paths of csrc/adapt.hip the first test file stops
 short of: the cases of tests/adapter_cases.py (tests/test_adapter_cases.py shows without a GPU which path each reaches)
-under test_adapter_gpu's rule and margins, the filter storages and a row offset on the bits, steps after index edits on
+under tests/adapter_harness.py's rule and margins, the filter storages and a row offset on the bits, steps after index edits on
 the same handle, AdamW's tile mapping at the narrowest and the widest D and its first steps from zero moments, and
 determinism at B = 1024, C = 8192."""
 from __future__ import annotations
@@ -11,46 +11,26 @@ import torch
 
 from instacart_next_order_recommendation_amd.search import DeviceIndex, apply_moves, removal_moves
 from tests import adapter_cases as ac
+from tests import adapter_harness as h
 from tests import adapter_reference as ref
+from tests.adapter_harness import DEV, adapter_with, bits
 from tests.search_harness import torch_cuda  # noqa: F401
-from tests.test_adapter_gpu import DEV, MARGINS, adapter_with
 
 pytestmark = pytest.mark.gpu
-
-
-def device_step(ix, ad, anchors, cand, scale=30.0):
-    """loss_and_grad on host arrays -> (loss float, gradient numpy)."""
-    loss, grad = ad.loss_and_grad(ix, torch.from_numpy(np.ascontiguousarray(anchors)).to(DEV), torch.from_numpy(np.asarray(cand)), scale)
-    return float(loss.cpu()), grad.cpu().numpy()
-
-
-def bits(loss: float, grad: np.ndarray):
-    return np.float32(loss).tobytes(), np.ascontiguousarray(grad, np.float32).tobytes()
 
 
 # ---------------------------------------------------------------- loss and gradient at the limits and on the masked paths
 @pytest.mark.parametrize("name,scale", ac.STEPS, ids=[f"{n}-{s:g}" for n, s in ac.STEPS])
 def test_loss_and_gradient_of_the_edge_cases(torch_cuda, name, scale):
-    c = ac.CASE_BY_NAME[name]
-    P, _, anchors, delta, cand = ac.inputs(name)
-    ix = DeviceIndex(P, DEV, storage=c.storage)
-    ad = adapter_with(delta)
-    try:
-        loss, grad = device_step(ix, ad, anchors, cand, scale)
-        what = f"adapter {c.storage} d{c.dim} B{c.B} C{c.C} scale {scale:g} {name}"
-        ac.check_step(what, loss, grad, *ac.references(name, scale), MARGINS[(c.storage, c.dim)])
-        assert ad.steps == 0 and np.array_equal(ad.state()["delta"], delta)
-    finally:
-        ad.close()
-        ix.close()
+    h.check_case("pairs", ac, name, scale)
 
 
 # ---------------------------------------------------------------- storages and the row offset
 def test_filter_storages_and_a_row_offset_give_the_same_bits(torch_cuda):
     rng = np.random.default_rng(41)
     d, B, C, n_rows = 384, 65, 300, 300
-    P = ac.unit_rows(rng, n_rows, d)
-    anchors, delta = ac.unit_rows(rng, B, d), ac.small_delta(rng, d)
+    P = h.unit_rows(rng, n_rows, d)
+    anchors, delta = h.unit_rows(rng, B, d), h.small_delta(rng, d)
     cand = ac.masked_id_mix(rng, B, C, n_rows)
     valid, masked, counted = ref.masks(cand, B, n_rows)
     assert 0 < counted.sum() < B and not valid[B:].all() and (masked & valid[None, :]).any()
@@ -59,7 +39,7 @@ def test_filter_storages_and_a_row_offset_give_the_same_bits(torch_cuda):
         ix = DeviceIndex(P, DEV, row_offset=row_offset, storage=storage)
         ad = adapter_with(delta)
         try:
-            loss, grad = device_step(ix, ad, anchors, cand)
+            loss, grad = h.device_step("pairs", ix, ad, anchors, cand)
             assert loss > 0 and np.abs(grad).max() > 0
             got[storage, row_offset] = bits(loss, grad)
         finally:
@@ -77,8 +57,7 @@ def test_after_index_edits_on_the_same_handle(torch_cuda, storage):
     rng = np.random.default_rng(43)
     d, B, C, n0 = 384, 65, 300, 300
     M = rng.standard_normal((n0, d)).astype(np.float32)
-    anchors, delta = ac.unit_rows(rng, B, d), ac.small_delta(rng, d)
-    margin = MARGINS[(storage.split("+")[0], d)]
+    anchors, delta = h.unit_rows(rng, B, d), h.small_delta(rng, d)
     ix = DeviceIndex(M, DEV, storage=storage)
     ad = adapter_with(delta)
     try:
@@ -92,11 +71,8 @@ def test_after_index_edits_on_the_same_handle(torch_cuda, storage):
             valid, _, counted = ref.masks(cand, B, n)
             assert counted[9] and not counted[10] and valid[B] and not valid[B + 2]
             assert dropped is None or (dropped >= n and not counted[11])
-            rows = ref.stored_rows(M, storage)
-            want = ref.loss_and_grad(delta, anchors, rows, cand, 30.0, torch.float64)
-            ref32 = ref.loss_and_grad(delta, anchors, rows, cand, 30.0, torch.float32)
-            loss, grad = device_step(ix, ad, anchors, cand)
-            ac.check_step(f"adapter {storage} d{d} B{B} C{C} {what}", loss, grad, *want, *ref32, margin)
+            h.check_against_reference("pairs", f"adapter {storage} d{d} B{B} C{C} {what}", ix, ad, anchors, delta,
+                                      ref.stored_rows(M, storage), cand, storage)
             return cand, counted
 
         check("fresh")
@@ -125,12 +101,12 @@ def test_after_index_edits_on_the_same_handle(torch_cuda, storage):
 
 
 # ---------------------------------------------------------------- AdamW
-HYPER, assert_adamw = ac.ADAMW_HYPER, ac.assert_adamw
+HYPER, assert_adamw = h.ADAMW_HYPER, h.assert_adamw
 
 
 @pytest.mark.parametrize("d", [32, 1024])
 def test_adamw_tile_mapping_at_one_tile_and_at_1024_tiles(torch_cuda, d):
-    P, anchors, cand, delta, m, v = ac.adamw_inputs(d)
+    P, anchors, cand, delta, m, v = h.adamw_inputs(d)
     ix = DeviceIndex(P, DEV, storage="f32")
     anchors, cand = torch.from_numpy(anchors).to(DEV), torch.from_numpy(cand)
     ad = adapter_with(delta, m, v, 7)
@@ -156,12 +132,12 @@ def test_adamw_first_steps_from_zero_moments(torch_cuda, start):
     rng = np.random.default_rng(53)
     d, B, C, dead = 96, 40, 64, 17
     decay = np.float32(1.0 - HYPER[0] * HYPER[4])
-    ix = DeviceIndex(ac.unit_rows(rng, 500, d), DEV, storage="f32")
-    delta = np.zeros((d, d), np.float32) if start == "zero D" else ac.small_delta(rng, d)
+    ix = DeviceIndex(h.unit_rows(rng, 500, d), DEV, storage="f32")
+    delta = np.zeros((d, d), np.float32) if start == "zero D" else h.small_delta(rng, d)
     ad = adapter_with(delta)  # m = v = 0, t = 0: where training starts
     try:
         for t in (1, 2, 3):
-            a = ac.unit_rows(rng, B, d)
+            a = h.unit_rows(rng, B, d)
             a[:, dead] = 0.0  # dD[r][dead] = sum_i dz_i[r] * 0: exactly zero in every step
             cand = torch.from_numpy(rng.choice(500, C, replace=False))
             before = ad.state()
@@ -191,20 +167,5 @@ def test_step_is_deterministic_at_the_limits(torch_cuda):
     assert (c.B, c.C) == (ac.MAX_BATCH, ac.MAX_CANDIDATES)
     P, _, anchors, delta, cand = ac.inputs(name)
     rng = np.random.default_rng(59)
-    m, v = ac.small_delta(rng, c.dim), np.abs(ac.small_delta(rng, c.dim))
-    ix = DeviceIndex(P, DEV, storage=c.storage)
-    a_dev, cand_dev = torch.from_numpy(anchors).to(DEV), torch.from_numpy(cand)
-    seen = []
-    try:
-        for _ in range(2):
-            ad = adapter_with(delta, m, v, 3)
-            grad = torch.empty((c.dim, c.dim), dtype=torch.float32, device=DEV)
-            loss = ad.step(ix, a_dev, cand_dev, 1e-3, grad_out=grad)
-            state = ad.state()
-            seen.append((loss.cpu().numpy().tobytes(), grad.cpu().numpy().tobytes(), state["delta"].tobytes(), state["m"].tobytes(),
-                         state["v"].tobytes(), state["t"]))
-            ad.close()
-        assert seen[0] == seen[1] and seen[0][5] == 4
-        assert np.frombuffer(seen[0][0], np.float32)[0] > 0 and np.frombuffer(seen[0][1], np.float32).any()
-    finally:
-        ix.close()
+    m, v = h.small_delta(rng, c.dim), np.abs(h.small_delta(rng, c.dim))
+    h.check_determinism("pairs", P, c.storage, anchors, cand, delta, m, v)

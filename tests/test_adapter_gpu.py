@@ -1,7 +1,8 @@
 """icrec_adapter_* on the GPU against tests/adapter_reference.py: apply bit for bit, the loss and its gradient within
 margin x the float32 reference's own error (tests/token_states.check's convention; measured ratios and the margins'
 choice: profiles/adapter_errors.md), determinism, AdamW against the float64 formula, the argument checks that need a
-device, and the learning task end to end through icrec_search."""
+device, and the learning task end to end through icrec_search.  What the three kinds of step are tested for alike has
+its one body in tests/adapter_harness.py."""
 from __future__ import annotations
 
 import numpy as np
@@ -11,25 +12,13 @@ import torch
 from instacart_next_order_recommendation_amd import _native
 from instacart_next_order_recommendation_amd.adapter import QueryAdapter
 from instacart_next_order_recommendation_amd.search import DeviceIndex
+from tests import adapter_harness as h
 from tests import adapter_reference as ref
-from tests.adapter_cases import candidates, check_step, small_delta, unit_rows
+from tests.adapter_cases import candidates
+from tests.adapter_harness import DEV, adapter_with, small_delta, unit_rows
 from tests.search_harness import torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-
-#: margin on E_ref per (storage, dim), for the gradient's rms and max-abs error and for the loss: the smallest of
-#: {2, 3, 4, 6, 8} that leaves 1.5x headroom over the worst ratio measured on the MI355X (profiles/adapter_errors.md)
-MARGINS = {("f32", 32): 2, ("f32", 64): 4, ("f32", 96): 6, ("f32", 384): 6, ("bf16", 384): 6, ("bf16", 768): 6,
-           # the pairs only tests/test_adapter_edges_gpu.py runs (worst ratios 1.09, 1.05, 1.08, 1.08, 1.01)
-           ("bf16", 64): 2, ("bf16", 128): 2, ("f32", 768): 2, ("f32", 1024): 2, ("bf16", 1024): 2}
-
-
-def adapter_with(delta, m=None, v=None, t=0) -> QueryAdapter:
-    ad = QueryAdapter(delta.shape[0], DEV)
-    ad.load_state({"delta": delta, "m": m, "v": v, "t": t})
-    return ad
 
 
 # ---------------------------------------------------------------- apply
@@ -86,83 +75,38 @@ def test_loss_and_gradient_within_margin_of_the_float32_reference(torch_cuda, di
     rows = ref.stored_rows(P, storage)
     anchors, delta = unit_rows(rng, B, dim), small_delta(rng, dim)
     cand = candidates(kind, rng, B, C, n_rows)
-    want_loss, want_grad = ref.loss_and_grad(delta, anchors, rows, cand, scale, torch.float64)
-    ref_loss, ref_grad = ref.loss_and_grad(delta, anchors, rows, cand, scale, torch.float32)
     ix = DeviceIndex(P, DEV, storage=storage)
     ad = adapter_with(delta)
-    loss, grad = ad.loss_and_grad(ix, torch.from_numpy(anchors).to(DEV), torch.from_numpy(cand), scale)
-    loss, grad = float(loss.cpu()), grad.cpu().numpy()
     what = f"adapter {storage} d{dim} B{B} C{C} scale {scale:g} {kind}"
-    check_step(what, loss, grad, want_loss, want_grad, ref_loss, ref_grad, MARGINS[(storage, dim)])
+    h.check_against_reference("pairs", what, ix, ad, anchors, delta, rows, cand, storage, scale)
     assert ad.steps == 0 and np.array_equal(ad.state()["delta"], delta)  # loss_and_grad changes nothing
     ix.close()
 
 
 def test_gradients_that_are_exactly_zero(torch_cuda):
-    rng = np.random.default_rng(5)
-    P = unit_rows(rng, 50, 64)
-    ix = DeviceIndex(P, DEV, storage="f32")
-    ad = adapter_with(small_delta(rng, 64))
-    anchors = torch.from_numpy(unit_rows(rng, 5, 64)).to(DEV)
-    for B, cand in ((1, [7]), (5, [9, 9, 9, 9, 9]), (3, [-1, 50, 99]), (2, [50, 3])):  # .., nobody counted (twice)
-        loss, grad = ad.loss_and_grad(ix, anchors[:B], torch.tensor(cand))
-        assert float(loss.cpu()) == 0.0 and not grad.cpu().numpy().any(), cand
-    ix.close()
+    h.check_exact_zeros("pairs", 50, 5, [(cand, B, torch.tensor(cand)) for B, cand in  # .., nobody counted (twice)
+                                         ((1, [7]), (5, [9, 9, 9, 9, 9]), (3, [-1, 50, 99]), (2, [50, 3]))])
 
 
 def test_step_is_deterministic(torch_cuda):
     rng = np.random.default_rng(6)
     d, B, C = 384, 65, 300
-    P = unit_rows(rng, 1000, d)
-    ix = DeviceIndex(P, DEV, storage="f32")
-    anchors = torch.from_numpy(unit_rows(rng, B, d)).to(DEV)
-    cand = torch.from_numpy(rng.integers(-1, 1001, C))
+    P, anchors = unit_rows(rng, 1000, d), unit_rows(rng, B, d)
+    cand = rng.integers(-1, 1001, C)
     delta, m, v = small_delta(rng, d), small_delta(rng, d), np.abs(small_delta(rng, d))
-    seen = []
-    for _ in range(2):
-        ad = adapter_with(delta, m, v, 3)
-        grad = torch.empty((d, d), dtype=torch.float32, device=DEV)
-        loss = ad.step(ix, anchors, cand, 1e-3, grad_out=grad)
-        state = ad.state()
-        seen.append((loss.cpu().numpy().tobytes(), grad.cpu().numpy().tobytes(), state["delta"].tobytes(), state["m"].tobytes(),
-                     state["v"].tobytes(), state["t"]))
-    assert seen[0] == seen[1] and seen[0][5] == 4
-    ix.close()
+    h.check_determinism("pairs", P, "f32", anchors, cand, delta, m, v)
 
 
 def test_adamw_step_matches_the_float64_formula(torch_cuda):
     rng = np.random.default_rng(7)
     d, B, C = 96, 40, 64
-    # the hyper-parameters are `float` arguments of the C ABI: the formula is given the values the call carries (1 - 0.999
-    # differs from 1 - float32(0.999) by 1.3e-5 of itself, far outside any rounding budget)
-    lr, b1, b2, eps, wd = (float(np.float32(x)) for x in (1e-2, 0.9, 0.999, 1e-8, 0.01))
-    P = unit_rows(rng, 500, d)
-    ix = DeviceIndex(P, DEV, storage="f32")
-    anchors = torch.from_numpy(unit_rows(rng, B, d)).to(DEV)
-    cand = torch.from_numpy(rng.choice(500, C, replace=False))
+    P, anchors = unit_rows(rng, 500, d), unit_rows(rng, B, d)
+    cand = rng.choice(500, C, replace=False)
     delta = small_delta(rng, d)
     m = (rng.standard_normal((d, d)) * 1e-3).astype(np.float32)
     v = (rng.random((d, d)) * 1e-5).astype(np.float32)
-    ad = adapter_with(delta, m, v, 7)
-    before_loss, before_grad = ad.loss_and_grad(ix, anchors, cand)  # update = 0 leaves the state untouched
-    state = ad.state()
-    assert state["t"] == 7 and all(np.array_equal(state[k], a) for k, a in (("delta", delta), ("m", m), ("v", v)))
-    grad = torch.empty((d, d), dtype=torch.float32, device=DEV)
-    loss = ad.step(ix, anchors, cand, lr, (b1, b2), eps, wd, grad_out=grad)
-    assert torch.equal(grad, before_grad) and torch.equal(loss, before_loss)
-    g = grad.cpu().numpy()
-    assert np.abs(g).max() > 0
-    want_delta, want_m, want_v, t, term = ref.adamw(delta, m, v, 7, g, lr, b1, b2, eps, wd)
-    state = ad.state()
-    assert state["t"] == t == 8 and ad.steps == 8
-    # eight roundings in the formula, each half an ulp of a magnitude bounded by the terms below: derived, not measured
-    u = 8 * 2.0**-24
-    assert (np.abs(state["delta"] - want_delta) <= u * (np.abs(delta) + np.abs(term))).all()
-    g64, m64 = g.astype(np.float64), m.astype(np.float64)
-    assert (np.abs(state["m"] - want_m) <= u * (np.abs(m64) + (1 - b1) * np.abs(g64 - m64))).all()
-    assert (np.abs(state["v"] - want_v) <= u * (b2 * np.abs(v) + (1 - b2) * g64 ** 2)).all()
-    assert np.array_equal(ad.apply(anchors).cpu().numpy(), ref.apply(state["delta"], anchors.cpu().numpy()))  # the apply copy followed
-    ix.close()
+    use = h.adamw_bound_use(*h.check_adamw("pairs", P, anchors, cand, delta, m, v))
+    assert use[3].max() <= 1  # the inline form of D's bound, which this test held before assert_adamw's
 
 
 def test_argument_checks_and_state_round_trip(torch_cuda, tmp_path):
@@ -171,28 +115,15 @@ def test_argument_checks_and_state_round_trip(torch_cuda, tmp_path):
     anchors = torch.from_numpy(unit_rows(rng, 4, 64)).to(DEV)
     cand = torch.tensor([1, 2, 3, 4])
     ad = adapter_with(small_delta(rng, 64))
-    with pytest.raises(_native.IcrecError, match="the index has dim 64, the adapter 32"):
-        QueryAdapter(32, DEV).loss_and_grad(ix, anchors[:, :32].contiguous(), cand)
+    h.check_shared_arguments("pairs", ix, ad, anchors, cand.numpy())
     with pytest.raises(_native.IcrecError, match=r"C must be in \[B"):
         ad.loss_and_grad(ix, anchors, cand[:3])
     with pytest.raises(_native.IcrecError, match="C must be in"):
         ad.loss_and_grad(ix, anchors, torch.zeros(8193, dtype=torch.int64))
     with pytest.raises(_native.IcrecError, match="B must be in"):
         ad.loss_and_grad(ix, anchors.repeat(257, 1), torch.zeros(1028, dtype=torch.int64))
-    for kw in (dict(lr=float("nan")), dict(lr=1e-3, scale=float("inf")), dict(lr=1e-3, weight_decay=float("nan")),
-               dict(lr=1e-3, eps=float("inf"))):
-        with pytest.raises(_native.IcrecError, match="not finite"):
-            ad.step(ix, anchors, cand, **kw)
-    with pytest.raises(_native.IcrecError, match="beta1 and beta2"):
-        ad.step(ix, anchors, cand, 1e-3, betas=(1.0, 0.999))
     L = _native.lib()
-    need = int(L.icrec_adapter_step_workspace_bytes(ad._h, 4, 4))
-    assert need > 0 and L.icrec_adapter_step_workspace_bytes(ad._h, 4, 3) == 0
-    ws = torch.empty(need - 1, dtype=torch.uint8, device=DEV)
-    loss = torch.empty(1, device=DEV)
-    rc = L.icrec_adapter_step(ix._h, ad._h, _native.ptr(anchors), 4, _native.ptr(cand.to(DEV, torch.int32)), 4, 30.0, 0.0, 0.9,
-                              0.999, 1e-8, 0.0, 0, _native.ptr(loss), None, _native.ptr(ws), ws.numel(), None)
-    assert rc == -1 and b"workspace" in L.icrec_last_error()
+    assert L.icrec_adapter_step_workspace_bytes(ad._h, 4, 4) > 0 and L.icrec_adapter_step_workspace_bytes(ad._h, 4, 3) == 0
     assert ad.steps == 0  # no refused call took a step
     # state -> file -> a new adapter: the same delta, scale and steps, and the same apply
     ad.step(ix, anchors, cand, 1e-3)
@@ -209,32 +140,14 @@ def test_argument_checks_and_state_round_trip(torch_cuda, tmp_path):
 def test_adapter_learns_the_rotation_end_to_end(torch_cuda):
     """Held-out recall@10 through icrec_search: at most 0.05 before, at least 0.9 after 100 steps (the float64
     reference reaches 1.0: tests/test_adapter.py)."""
-    P, a_train, p_train, a_held, p_held = ref.learning_task()
-    ix = DeviceIndex(P, DEV, storage="f32")
-    ad = QueryAdapter(ref.TASK_DIM, DEV)
-    held = torch.from_numpy(a_held).to(DEV)
-    a_dev, p_dev = torch.from_numpy(a_train).to(DEV), torch.from_numpy(p_train).to(DEV, torch.int32)
-
-    def recall():
-        return ref.recall_at(ix.search(ad.apply(held), 10)[0].cpu().numpy(), p_held)
-
-    before = recall()
-    losses = torch.zeros(ref.TASK_STEPS, device=DEV)
-    for step in range(ref.TASK_STEPS):
-        at = ref.task_batch(step)
-        ad.step(ix, a_dev[at], p_dev[at], ref.TASK_LR, weight_decay=ref.TASK_DECAY, scale=ref.TASK_SCALE,
-                loss_out=losses[step:step + 1])
-    after = recall()
-    losses = losses.cpu().numpy()
-    print(f"recall@10 {before:.4f} -> {after:.4f}, loss {losses[0]:.3f} -> {losses[-1]:.3f}")
-    assert before <= 0.05 and after >= 0.9 and ad.steps == ref.TASK_STEPS
-    assert np.isfinite(losses).all() and losses[-1] < 0.5 * losses[0]
+    task = ref.learning_task()
+    p_train = task[2]
+    p_dev = torch.from_numpy(p_train).to(DEV, torch.int32)
+    ix, ad, after, losses, _ = h.train_on_task("pairs", task, lambda at: p_dev[at])
+    assert after >= 0.9 and losses[-1] < 0.5 * losses[0]
     # fit: reproducible from its seed, drop_last, the schedule's first step has lr 0 and leaves delta at zero
-    runs = []
-    for _ in range(2):
-        fitted = QueryAdapter(ref.TASK_DIM, DEV)
-        got = fitted.fit(ix, a_dev[:1000], p_train[:1000], epochs=2, batch_size=128, negatives=64, lr=5e-3, seed=4)
-        runs.append((got, fitted.state()["delta"].tobytes()))
-        assert len(got) == 2 * (1000 // 128) and fitted.steps == len(got)
-    assert runs[0] == runs[1] and runs[0][0][-1] < runs[0][0][0]
+    a_dev = torch.from_numpy(task[1]).to(DEV)
+    h.check_fit_is_reproducible(lambda fitted: fitted.fit(ix, a_dev[:1000], p_train[:1000], epochs=2, batch_size=128,
+                                                          negatives=64, lr=5e-3, seed=4), 2 * (1000 // 128))
+    ad.close()
     ix.close()

@@ -1,6 +1,6 @@
-"""The adapter's step over per-anchor lists without a GPU: tests/adapter_lists_reference.py against the pair reference
-on a shared one-hot list and against central differences, that every case of tests/adapter_lists_cases.py reaches the
-path it names, impression_csr, the plan function's refusals, the command line's --lists and --gain, and the C entry's
+"""The adapter's step over per-anchor lists without a GPU: tests/adapter_reference.py's loss_and_grad_lists against the
+pair reference on a shared one-hot list and against central differences, that every case of
+tests/adapter_lists_cases.py reaches the path it names, impression_csr, the plan function's refusals, the command line's --lists and --gain, and the C entry's
 refusals before any HIP call."""
 from __future__ import annotations
 
@@ -12,7 +12,6 @@ from instacart_next_order_recommendation_amd import _native, cli
 from instacart_next_order_recommendation_amd.adapter import impression_csr
 from instacart_next_order_recommendation_amd.recommender import DEFAULT_GAINS, Recommender, adapter_lists_plan
 from tests import adapter_lists_cases as lc
-from tests import adapter_lists_reference as lref
 from tests import adapter_reference as ref
 from tests.recommender_harness import forbid_gpu_work
 from tests.test_adapter import NoModel, StubPath, world
@@ -26,7 +25,7 @@ def test_shared_one_hot_list_is_the_pair_loss_in_float64():
     want_loss, want_grad = ref.loss_and_grad(delta, anchors, rows, cand, 30.0)
     one_hot = np.zeros((5, 17), np.float32)
     one_hot[np.arange(5), np.arange(5)] = 3.0  # any positive gain: t = gain / T = 1
-    loss, grad = lref.loss_and_grad(delta, anchors, rows, *lref.uniform_csr(np.tile(cand, (5, 1)), one_hot), 30.0)
+    loss, grad = ref.loss_and_grad_lists(delta, anchors, rows, *ref.uniform_csr(np.tile(cand, (5, 1)), one_hot), 30.0)
     assert abs(loss - want_loss) <= 1e-12 and np.abs(grad - want_grad).max() <= 1e-12
 
 
@@ -35,8 +34,8 @@ def test_gradient_matches_central_differences():
     off = np.asarray([0, 4, 4, 9, 7])  # an empty segment and one whose end lies before its start
     lrows = np.asarray([3, 7, 12, 0, 5, 5, -1, 2, 9])
     target = np.asarray([1, 0, 4, 2, 0.5, 2, 1, np.nan, 0], np.float32)
-    loss, grad = lref.loss_and_grad(delta, anchors, rows, off, lrows, target, 4, 30.0)
-    _, _, _, live, counted = lref.masks(off, lrows, target, 4, 12)
+    loss, grad = ref.loss_and_grad_lists(delta, anchors, rows, off, lrows, target, 4, 30.0)
+    _, _, _, live, counted = ref.masks_lists(off, lrows, target, 4, 12)
     assert counted.tolist() == [True, False, True, False] and live.sum() == 3 + 2 and np.abs(grad).max() > 1e-3
     h = 1e-6
     for r in range(6):
@@ -44,18 +43,18 @@ def test_gradient_matches_central_differences():
             up, down = delta.copy(), delta.copy()
             up[r, c] += h
             down[r, c] -= h
-            fd = (lref.loss_and_grad(up, anchors, rows, off, lrows, target, 4, 30.0)[0]
-                  - lref.loss_and_grad(down, anchors, rows, off, lrows, target, 4, 30.0)[0]) / (2 * h)
+            fd = (ref.loss_and_grad_lists(up, anchors, rows, off, lrows, target, 4, 30.0)[0]
+                  - ref.loss_and_grad_lists(down, anchors, rows, off, lrows, target, 4, 30.0)[0]) / (2 * h)
             assert abs(fd - grad[r, c]) <= 1e-6 * max(1.0, abs(grad[r, c])), (r, c, fd, grad[r, c])
 
 
 def test_one_live_entry_and_nobody_counted_are_exactly_zero():
     rows, anchors, delta = world(d=8, n_rows=12, B=3)
     one = (np.asarray([0, 1, 4, 5]), np.asarray([3, -1, 5, 12, 7]), np.asarray([2, 1, 1, 1, 0.5], np.float32), 8)
-    loss, grad = lref.loss_and_grad(delta, anchors, rows, *one, 30.0)
-    assert lref.masks(*one, 12)[4].all() and loss == 0.0 and np.abs(grad).max() <= 1e-15
+    loss, grad = ref.loss_and_grad_lists(delta, anchors, rows, *one, 30.0)
+    assert ref.masks_lists(*one, 12)[4].all() and loss == 0.0 and np.abs(grad).max() <= 1e-15
     nobody = (np.asarray([0, 2, 2, 4]), np.asarray([3, 4, 12, -1]), np.asarray([0, 0, 1, 1], np.float32), 8)
-    assert lref.loss_and_grad(delta, anchors, rows, *nobody, 30.0) == (0.0, pytest.approx(np.zeros((8, 8))))
+    assert ref.loss_and_grad_lists(delta, anchors, rows, *nobody, 30.0) == (0.0, pytest.approx(np.zeros((8, 8))))
 
 
 # ---------------------------------------------------------------- the cases reach their paths
@@ -69,7 +68,7 @@ def test_every_case_reaches_the_path_it_names():
         _, stored, anchors, delta, lists = lc.inputs(c.name)
         off, rows, target, max_len = lists
         assert off.shape == (c.B + 1,) and 1 <= max_len <= lc.MAX_LIST and off.min() >= 0 and off.max() <= len(rows)
-        r, t, read, live, counted = lref.masks(*lists, c.n_rows)
+        r, t, read, live, counted = ref.masks_lists(*lists, c.n_rows)
         assert counted.any() and stored.shape == (c.n_rows, c.dim)
         lengths = read.sum(axis=1)
         seen_lengths |= set(lengths.tolist())
@@ -114,8 +113,8 @@ def test_every_case_reaches_the_path_it_names():
 
 def test_one_live_entry_in_a_case_has_no_loss_of_its_own():
     _, stored, anchors, delta, lists = lc.inputs("edge-lengths")
-    losses, counted = lref.per_anchor_losses(delta, anchors, stored, *lists, 30.0)
-    lengths = lref.masks(*lists, stored.shape[0])[2].sum(axis=1)
+    losses, counted = ref.per_anchor_losses(delta, anchors, stored, *lists, 30.0)
+    lengths = ref.masks_lists(*lists, stored.shape[0])[2].sum(axis=1)
     assert counted.all() and (losses.numpy()[lengths == 1] == 0).all() and (losses.numpy()[lengths > 1] > 0).all()
 
 

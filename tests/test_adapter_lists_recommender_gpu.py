@@ -11,7 +11,7 @@ import torch
 from instacart_next_order_recommendation_amd import synthetic as syn
 from instacart_next_order_recommendation_amd.recommender import DEFAULT_GAINS, MonitoredRecommender, Recommender
 from tests.recommender_harness import QUERIES, forbid_gpu_work, graph_replays, synthetic_world, torch_cuda  # noqa: F401  (fixture)
-from tests.test_adapter_recommender_gpu import by_hand
+from tests.adapter_harness import by_hand
 
 pytestmark = pytest.mark.gpu
 
